@@ -20,10 +20,20 @@ The ranks rendezvous over a gloo process group (the ncclUniqueId broadcast, the 
 timings); torch's NCCL process group is never created, so ONE RCCL serves the process: the one libdrp.so binds at
 run time (config.rccl in the line names its version and file).
 
-The default one-GPU run also carries a `sweep` block: the other BASELINE workloads (20 particles -- the small-pile
-regime --, configs[3] 50 / 150 / 600 particles, the per-GPU share of configs[4], the reference's live GD planner
-shape), 20 iterations each after 5 warm-ups.  --config selects one of them as the headline instead; c5 is the strong-scaling one (4096 samples in
-total).  --force-comm attaches a one-rank RCCL communicator and runs the update through ncclAllGather.
+A plain run does only what its headline needs: set up, W warm-ups, the K timed iterations, the outputs (--dump-outputs)
+and the line.  Everything else it measures is behind --full: the per-kernel calibration iterations and the rooflines
+built on them, the synchronised median pass, the fp32-MFMA engine run, the CPU baseline and, on the default one-GPU run,
+a `sweep` block: the other BASELINE workloads (20 particles -- the small-pile regime --, configs[3] 50 / 150 / 600
+particles, the per-GPU share of configs[4], the reference's live GD planner shape), 20 iterations each after 5 warm-ups,
+one whole MPC step and one training iteration.  --config selects one of them as the headline instead; c5 is the
+strong-scaling one (4096 samples in total).  --force-comm attaches a one-rank RCCL communicator and runs the update
+through ncclAllGather.
+
+--dump-outputs DIR writes what the last timed iteration computed, as a caller of it receives it, to DIR/<name>.npy
+(float32 / float64, at most DUMP_BUDGET bytes; rank 0's block of samples when sharded): the MPPI iteration's updated
+nominal sequence, its sampled pushes, their final rewards and predicted states (a fixed, seeded subset of the samples
+when they do not fit), or the GD iteration's updated pushes.  The inputs depend on the arguments alone, and with or
+without --full the timed iterations compute the same thing, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -68,6 +78,13 @@ FLOP_PER_NODE = {'node_encode': 2 * (5 * 64 + 2 * 64 * 64), 'project': 2 * 2 * 6
                  'update': 2 * 64 * 64, 'predict': 2 * (64 * 64 + 3 * 64)}
 EXIT_WORLD_MISMATCH = 4      # WORLD_SIZE / --gpus / ncclCommCount disagree
 EXIT_TIMEOUT = 124           # the self-launched ranks did not finish in --timeout seconds
+# the line's keys in this order, whichever of them it carries (a plain run leaves out what --full adds)
+LINE_FIRST = ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline',
+              'ms_per_step_median', 'value_median', 'rank_ms_per_step', 'dtype', 'data', 'config', 'roofline', 'roofline_backward',
+              'kernel_ms_per_iteration', 'roofline_scatter', 'alt_engine', 'cpu_baseline', 'gpu_active_s', 'sweep', 'mpc_step',
+              'train_step')
+DUMP_BUDGET = 64 << 20       # --dump-outputs: bytes over all files, .npy headers included
+DUMP_SEED = 0                # ... the seed of the subset of samples written when they do not all fit
 
 
 def parse():
@@ -101,6 +118,11 @@ def parse():
     ap.add_argument('--elite', type=int, default=64)
     ap.add_argument('--timeout', type=float, default=1500.0,
                     help='self-launched ranks (--gpus N without a launcher): seconds before the parent ends them and exits %d' % EXIT_TIMEOUT)
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beyond the headline: kernel calibration and rooflines, the median pass, the '
+                         'fp32-MFMA engine run, the CPU baseline and (default one-GPU run) the sweep, MPC-step and training blocks')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed iteration computed to DIR/<name>.npy (float32 / float64, at most 64 MB)')
     ap.add_argument('--fault-rank', type=int, default=None, help=argparse.SUPPRESS)   # tests: this rank exits(7) after the warm-up
     args = ap.parse_args()
     cfg = args.config or ('c2' if args.gpus == 1 else 'c3')
@@ -122,7 +144,7 @@ def parse():
         # about 10 s of host work for the dense formulation: its cost per sample grows with N^2
         args.cpu_samples = int(min(1024, max(4, 128 * (300.0 / args.particles) ** 2 * 10.0 / args.horizon)))
     args.config_name = cfg if not custom else 'custom'
-    args.do_sweep = args.sweep or (args.config is None and not custom and args.gpus == 1 and not args.no_sweep
+    args.do_sweep = args.sweep or (args.full and args.config is None and not custom and args.gpus == 1 and not args.no_sweep
                                    and args.engine in ('auto', 'fused') and not args.force_comm)
     return args
 
@@ -263,6 +285,32 @@ def host_cpu_model():
     except Exception:
         pass
     return 'unknown'
+
+
+def dump_outputs(out_dir, fixed=None, per_sample=None):
+    """--dump-outputs: every array as out_dir/<name>.npy, float32 or float64.  The `per_sample` arrays share their first axis
+    (the samples); when everything together would pass DUMP_BUDGET, all of them keep the same fixed, seeded subset of
+    samples (in ascending order), as many as fit."""
+    fixed, per_sample = dict(fixed or {}), dict(per_sample or {})
+    arrays = dict(fixed, **per_sample)
+    for k, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        arrays[k] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    header = 128                                               # an .npy header of these shapes
+    total = sum(a.nbytes + header for a in arrays.values())
+    kept = None
+    if total > DUMP_BUDGET and per_sample:
+        n = arrays[next(iter(per_sample))].shape[0]
+        row = sum(arrays[k][0].nbytes for k in per_sample)
+        room = DUMP_BUDGET - sum(arrays[k].nbytes + header for k in fixed) - header * len(per_sample)
+        kept = np.sort(np.random.default_rng(DUMP_SEED).choice(n, max(1, room // row), replace=False))
+        for k in per_sample:
+            arrays[k] = np.ascontiguousarray(arrays[k][kept])
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a)
+    sys.stderr.write('bench.py: outputs %s in %s%s\n' % (', '.join('%s%s' % (k, list(a.shape)) for k, a in arrays.items()), out_dir,
+                     '' if kept is None else ' (%d of %d samples, seed %d)' % (len(kept), n, DUMP_SEED)))
 
 
 def cpu_baseline(args, sd, s0, dens, attr, G, goal_coor, cam):
@@ -425,17 +473,23 @@ class Rig(object):
         self.goal_n = N
 
 
-def bench_mppi(rig, N, ns, H, s_lo, steps, warmup, step_extra, fence, classes, want_median, fault=False):
-    """W warm-ups, one calibration iteration per kernel class (HIP-event probe), then EXACTLY `steps` timed iterations
-    bracketed by fence().  step_extra(eng): the update that ends an iteration.  -> dict of raw measurements."""
+def bench_mppi(rig, N, ns, H, s_lo, steps, warmup, step_extra, fence, classes, want_median, fault=False, dump=None):
+    """W warm-ups, then EXACTLY `steps` timed iterations bracketed by fence().  With kernel `classes` (--full) first one
+    calibration iteration per class (HIP-event probe) after the warm-ups, then the session begins again and warms up
+    again, so the timed iterations compute what they compute without them; the dominant class stays probed while they
+    run.  step_extra(eng): the update that ends an iteration.  dump(eng): called right after the timed iterations.
+    -> dict of raw measurements."""
     eng, syn = rig.eng, rig.syn
     rig.goal(N)
     s0, dens, attr = syn.make_pile(N, 1, seed=0)
     lo, hi = syn.action_limits()
     nominal = syn.nominal_pushes(H, seed=0)
-    eng.mpc_begin(s0, attr, dens, nominal, n_sample=ns, sigma=0.3 * 24 / 12.0, beta_filter=0.7,
-                  reward_weight=0.1, act_lo=lo, act_hi=hi, seed=1234, sample_offset=s_lo)
     it = [0]
+
+    def begin():
+        eng.mpc_begin(s0, attr, dens, nominal, n_sample=ns, sigma=0.3 * 24 / 12.0, beta_filter=0.7,
+                      reward_weight=0.1, act_lo=lo, act_hi=hi, seed=1234, sample_offset=s_lo)
+        it[0] = 0
 
     def step():
         eng.mpc_sample(it[0])
@@ -443,6 +497,7 @@ def bench_mppi(rig, N, ns, H, s_lo, steps, warmup, step_extra, fence, classes, w
         step_extra(eng)
         it[0] += 1
 
+    begin()
     for _ in range(warmup):
         step()
     if fault:
@@ -450,26 +505,34 @@ def bench_mppi(rig, N, ns, H, s_lo, steps, warmup, step_extra, fence, classes, w
         os._exit(7)                     # a rank that is simply gone: no clean-up, no goodbye to the group
     fence()
     per_class = {}
-    dom_work = None
-    for kc in classes:
-        # one iteration per kernel class; the propagation kernels also COUNT what they execute in theirs (the counters
-        # cost time: never inside the timed region)
-        eng.probe_begin('prop+work' if kc == 'prop' else kc)
-        step()
-        per_class[kc] = eng.probe_read()
-        if kc == 'prop' and per_class[kc][1] > 0:
-            dom_work = eng.probe_work()
-            dom_work['launches'] = per_class[kc][1]
-    dominant = max(per_class, key=lambda k: per_class[k][0])
-    cnt_last = eng.debug_fetch('nbr_cnt', (ns, N), np.uint8)
-    eng.probe_begin(dominant)
-    eng.dispatch_reset()
+    dom_work, dominant, cnt_last = None, None, None
+    if classes:
+        for kc in classes:
+            # one iteration per kernel class; the propagation kernels also COUNT what they execute in theirs (the counters
+            # cost time: never inside the timed region)
+            eng.probe_begin('prop+work' if kc == 'prop' else kc)
+            step()
+            per_class[kc] = eng.probe_read()
+            if kc == 'prop' and per_class[kc][1] > 0:
+                dom_work = eng.probe_work()
+                dom_work['launches'] = per_class[kc][1]
+        dominant = max(per_class, key=lambda k: per_class[k][0])
+        cnt_last = eng.debug_fetch('nbr_cnt', (ns, N), np.uint8)
+        begin()
+        for _ in range(warmup):
+            step()
+        eng.probe_begin(dominant)
+        eng.dispatch_reset()
     fence()
     t0 = time.perf_counter()
     for _ in range(steps):
         step()
     fence()
     dt = time.perf_counter() - t0
+    if dump is not None:
+        dump(eng)
+    if not classes:
+        return {'dt': dt, 'median': None, 'per_class': per_class, 'step': step}
     dom_ms, dom_n = eng.probe_read()
     eng.probe_begin(None)
     ran = eng.last_dispatch()            # the kernel variants the timed iterations launched (drp_last_dispatch)
@@ -539,8 +602,10 @@ def scatter_roofline(ns, N, kbar, agg_ms, agg_n, traffic_bytes):
             'traffic': traffic_bytes, 'traffic_source': TRAFFIC_SOURCE if traffic_bytes else None})
 
 
-def bench_gd(rig, N, traj, nb, H, steps, warmup, fence, rank=0, want_median=True):
-    """The gradient-descent planner's iteration (drp_gd_step) at traj x nb rows of N particles."""
+def bench_gd(rig, N, traj, nb, H, steps, warmup, fence, rank=0, want_median=True, full=True, dump=None):
+    """The gradient-descent planner's iteration (drp_gd_step) at traj x nb rows of N particles: W warm-ups, then `steps`
+    timed iterations.  `full`: one calibration iteration per kernel class after the warm-ups, then the run begins again and
+    warms up again (as bench_mppi), the dominant class probed while the timed iterations run, and the rooflines."""
     eng, syn = rig.eng, rig.syn
     rig.goal(N)
     B = traj * nb
@@ -557,24 +622,32 @@ def bench_gd(rig, N, traj, nb, H, steps, warmup, fence, rank=0, want_median=True
     fence()
     per_class = {}
     dom_work = None
-    for kc in GD_CLASSES:
-        eng.probe_begin('prop+work' if kc == 'prop' else kc)
-        step()
-        per_class[kc] = eng.probe_read()
-        if kc == 'prop' and per_class[kc][1] > 0:
-            dom_work = eng.probe_work()
-            dom_work['launches'] = per_class[kc][1]
-    dominant = max(per_class, key=lambda k: per_class[k][0])
-    cnt = eng.debug_fetch('nbr_cnt', (B, N), np.uint8)
-    kbar = float(cnt.mean())
-    eng.probe_begin(dominant)
-    eng.dispatch_reset()
+    if full:
+        for kc in GD_CLASSES:
+            eng.probe_begin('prop+work' if kc == 'prop' else kc)
+            step()
+            per_class[kc] = eng.probe_read()
+            if kc == 'prop' and per_class[kc][1] > 0:
+                dom_work = eng.probe_work()
+                dom_work['launches'] = per_class[kc][1]
+        dominant = max(per_class, key=lambda k: per_class[k][0])
+        cnt = eng.debug_fetch('nbr_cnt', (B, N), np.uint8)
+        kbar = float(cnt.mean())
+        eng.gd_begin(s0, attr, dens, acts, 0.05, lo, hi)
+        for _ in range(warmup):
+            step()
+        eng.probe_begin(dominant)
+        eng.dispatch_reset()
     fence()
     t0 = time.perf_counter()
     for _ in range(steps):
         step()
     fence()
     dt = time.perf_counter() - t0
+    if dump is not None:
+        dump(eng)
+    if not full:
+        return {'dt': dt, 'median': None, 'B': B, 'step': step}
     dom_ms, dom_n = eng.probe_read()
     eng.probe_begin(None)
     ran = eng.last_dispatch()
@@ -917,12 +990,20 @@ def run_rank(args):
 
     N, H = args.particles, args.horizon
     out, cpu_args = None, None
+    dump_here = args.dump_outputs is not None and rank == 0
+
+    def dump_mppi(e):
+        got = e.mpc_get(actions=True, rewards=True, states=True, nominal=True)
+        dump_outputs(args.dump_outputs, fixed={'nominal': got['nominal']},
+                     per_sample={'actions': got['actions'], 'rewards': got['rewards'], 'states': got['states']})
     if args.config_name == 'gd-demo':
         nb = 30
         rows = args.samples_total_job // world
         traj = max(1, rows // nb)
-        g = bench_gd(rig, N, traj, nb, H, args.steps, args.warmup, fence, rank=rank)
-        dt, med = max_over_ranks(g['dt']), max_over_ranks(g['median'])
+        g = bench_gd(rig, N, traj, nb, H, args.steps, args.warmup, fence, rank=rank, want_median=args.full, full=args.full,
+                     dump=(lambda e: dump_outputs(args.dump_outputs, per_sample={'actions': e.gd_actions()})) if dump_here else None)
+        dt = max_over_ranks(g['dt'])
+        med = max_over_ranks(g['median']) if args.full else None
         rank_ms = per_rank_ms(g['dt'])
         if rank == 0:
             from dyn_res_pile_manip_amd.planners import particle_num_to_iter_time
@@ -930,16 +1011,18 @@ def run_rank(args):
             out = {'metric': 'MPC rollout-steps/sec (samples x particles x steps/sec)', 'value': world * B * N * H * args.steps / dt,
                    'unit': 'particle-steps/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
                    'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-                   'ms_per_step_median': med * 1e3, 'value_median': world * B * N * H / med, 'rank_ms_per_step': rank_ms,
+                   'rank_ms_per_step': rank_ms,
                    'dtype': 'f32 (forward MLP products as split fp16 / bf16 MFMA terms, backward node stages on fp32 MFMA, fp32 accumulate)',
                    'data': 'synthetic',
                    'config': {'workload': args.workload, 'name': args.config_name, 'n_particles': N, 'n_trajectories_per_gpu': traj,
-                              'n_batch': nb, 'rows_per_gpu': B, 'n_look_ahead': H, 'engine': 'fused', 'mean_in_degree': g['kbar'],
+                              'n_batch': nb, 'rows_per_gpu': B, 'n_look_ahead': H, 'engine': 'fused', 'mean_in_degree': g.get('kbar'),
                               'parallelism': 'trajectories sharded x%d, no collective' % world,
                               'reference_time_model_ms': particle_num_to_iter_time(N)},     # planners.py:25-28, batch 300 on its GPU
-                   'roofline': g['roofline'], 'roofline_backward': g['roofline_backward'],
-                   'kernel_ms_per_iteration': {k: round(v[0], 4) for k, v in g['per_class'].items()},
-                   'cpu_baseline': None}
+                   'cpu_baseline': None, 'gpu_active_s': round(float(g['dt']), 3)}
+        if rank == 0 and args.full:
+            out['ms_per_step_median'], out['value_median'] = med * 1e3, world * B * N * H / med
+            out['roofline'], out['roofline_backward'] = g['roofline'], g['roofline_backward']
+            out['kernel_ms_per_iteration'] = {k: round(v[0], 4) for k, v in g['per_class'].items()}
             if world == 1 and not args.no_cpu_baseline:
                 from oracle import propnet_dense as od
                 syn = rig.syn
@@ -972,16 +1055,17 @@ def run_rank(args):
             else:
                 e.mpc_update_device()
 
-        m = bench_mppi(rig, N, ns, H, s_lo, args.steps, args.warmup, update, fence, KERNEL_CLASSES, want_median=True,
-                       fault=(args.fault_rank == rank))
-        dt, med = max_over_ranks(m['dt']), max_over_ranks(m['median'])
+        m = bench_mppi(rig, N, ns, H, s_lo, args.steps, args.warmup, update, fence, KERNEL_CLASSES if args.full else None,
+                       want_median=args.full, fault=(args.fault_rank == rank), dump=dump_mppi if dump_here else None)
+        dt = max_over_ranks(m['dt'])
+        med = max_over_ranks(m['median']) if args.full else None
         rank_ms = per_rank_ms(m['dt'])
         step = m['step']
         # the same K steps on the pure-fp32 MFMA engine (bit-for-bit an fp32 fma chain), for reference; its un-fused
         # pipeline has the segmented sum ("scatter-add") as a kernel of its own, timed here with the HIP-event probe
         alt, scatter = None, None
         tj = load_traffic() if (N, ns) == (300, 1024) else {}
-        if engine != 'mfma' and not args.no_alt:
+        if args.full and engine != 'mfma' and not args.no_alt:
             eng.set_engine(rig._lib.ENGINES['mfma'])
             for _ in range(2):
                 step()
@@ -1002,15 +1086,6 @@ def run_rank(args):
                    'ms_per_step': dta / args.steps * 1e3}
             eng.set_engine(rig._lib.ENGINES[engine])
         if rank == 0:
-            roof = mppi_roofline(rig, m, N, ns, H, args.steps)
-            # HBM-side bytes per launch of this kernel from rocprofv3 PMC passes (FETCH_SIZE x2 + WRITE_SIZE,
-            # profiles/summarize_pmc.py), collected on this same workload
-            roof['traffic'], roof['traffic_source'] = None, None
-            tkey = 'prop3' if (m['dominant'] == 'prop' and roof.get('propagation_steps_per_launch', 0) >= 3) else m['dominant']
-            tb = tj.get(engine, {}).get(tkey, {}).get('hbm_bytes_per_launch')
-            if tb:
-                roof['traffic'], roof['traffic_source'] = tb, TRAFFIC_SOURCE
-            roof = ordered(roof)
             comm_label = None
             if use_rccl:
                 comm_label = 'rccl, %d rank%s' % (world, '' if world == 1 else 's')
@@ -1020,8 +1095,7 @@ def run_rank(args):
                 'metric': 'MPC rollout-steps/sec (samples x particles x steps/sec)',
                 'value': args.samples_total_job * N * H * args.steps / dt, 'unit': 'particle-steps/s', 'n_gpus': world,
                 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True,
-                'scaling': args.scaling, 'vs_baseline': None,
-                'ms_per_step_median': med * 1e3, 'value_median': args.samples_total_job * N * H / med, 'rank_ms_per_step': rank_ms,
+                'scaling': args.scaling, 'vs_baseline': None, 'rank_ms_per_step': rank_ms,
                 'dtype': 'f32' if engine in ('valu', 'mfma') else 'f32 (MLP products as split fp16 / bf16 MFMA terms, fp32 accumulate)',
                 'data': 'synthetic',
                 'config': {'workload': args.workload, 'name': args.config_name,
@@ -1031,13 +1105,24 @@ def run_rank(args):
                            'rccl': ({'comm_count': comm_info['n_ranks'], 'version': comm_info['version_str'],
                                      'library': comm_info['path'], 'ranks': rccl_ranks} if comm_info else None),
                            'rendezvous': 'gloo (id broadcast, barrier, timing reductions)' if world > 1 else None,
-                           'mean_in_degree': m['kbar'], 'parallelism': 'samples sharded x%d' % world,
+                           'mean_in_degree': m.get('kbar'), 'parallelism': 'samples sharded x%d' % world,
                            'update': 'softmax mean (optimize_action)' if args.update == 'mppi' else 'mean of the %d best (elite)' % args.elite},
-                'roofline': roof,
-                'kernel_ms_per_iteration': {k: round(v[0], 4) for k, v in m['per_class'].items()},
-                'roofline_scatter': scatter, 'alt_engine': alt,
             }
             out['cpu_baseline'] = None
+            out['gpu_active_s'] = round(float(m['dt']), 3)
+        if rank == 0 and args.full:
+            roof = mppi_roofline(rig, m, N, ns, H, args.steps)
+            # HBM-side bytes per launch of this kernel from rocprofv3 PMC passes (FETCH_SIZE x2 + WRITE_SIZE,
+            # profiles/summarize_pmc.py), collected on this same workload
+            roof['traffic'], roof['traffic_source'] = None, None
+            tkey = 'prop3' if (m['dominant'] == 'prop' and roof.get('propagation_steps_per_launch', 0) >= 3) else m['dominant']
+            tb = tj.get(engine, {}).get(tkey, {}).get('hbm_bytes_per_launch')
+            if tb:
+                roof['traffic'], roof['traffic_source'] = tb, TRAFFIC_SOURCE
+            out['ms_per_step_median'], out['value_median'] = med * 1e3, args.samples_total_job * N * H / med
+            out['roofline'] = ordered(roof)
+            out['kernel_ms_per_iteration'] = {k: round(v[0], 4) for k, v in m['per_class'].items()}
+            out['roofline_scatter'], out['alt_engine'] = scatter, alt
             cpu_args = (args, rig.sd, m['s0'], m['dens'], m['attr'], rig.G, rig.goal_coor, rig.cam) if (world == 1 and not args.no_cpu_baseline) else None
             out['gpu_active_s'] = round(float(m['dt'] + (m['median'] or 0.0) * args.steps + (dta if alt else 0.0)), 3)
     if rank == 0 and args.do_sweep and world == 1:
@@ -1051,7 +1136,9 @@ def run_rank(args):
     if rank == 0 and cpu_args is not None:
         out['cpu_baseline'] = cpu_baseline(*cpu_args)
     if rank == 0:
-        print(json.dumps(out), flush=True)
+        if not args.full:
+            del out['config']['mean_in_degree']          # read off the calibration iteration
+        print(json.dumps(ordered(out, LINE_FIRST)), flush=True)
     if world > 1:
         dist.barrier()
     eng.close()

@@ -24,7 +24,7 @@ def _run(cmd, env=None):
 
 
 def test_single_gpu_line_has_the_contract_fields():
-    d = _run([sys.executable, 'bench.py', '--steps', '3', '--warmup', '1', '--samples', '256', '--cpu-samples', '4'])
+    d = _run([sys.executable, 'bench.py', '--full', '--steps', '3', '--warmup', '1', '--samples', '256', '--cpu-samples', '4'])
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
               'vs_baseline', 'dtype', 'data', 'config', 'roofline', 'cpu_baseline', 'roofline_scatter'):
         assert k in d, k
@@ -66,6 +66,33 @@ def test_single_gpu_line_has_the_contract_fields():
     assert 1500.0 < r['sclk_mhz_under_load'] < 2600.0
     assert abs(r['frac_at_measured_clock'] - r['frac'] * 2400.0 / r['sclk_mhz_under_load']) < 1e-9
     assert set(c['seconds_by_threads']) == set(c['value_by_threads']) and c['cores'] == int(min(c['seconds_by_threads'], key=lambda k: c['seconds_by_threads'][k]))
+
+
+def test_a_plain_run_times_its_steps_and_dumps_what_a_full_run_computes(tmp_path):
+    """Without --full the line carries the headline and nothing that takes runs of its own; --dump-outputs writes what the
+    last timed iteration computed, and the same arguments with --full (calibration iterations, probed timed iterations, the
+    median pass) compute the same."""
+    import numpy as np
+    args = ['--steps', '3', '--warmup', '1', '--samples', '256']
+    plain, full = tmp_path / 'plain', tmp_path / 'full'
+    d = _run([sys.executable, 'bench.py'] + args + ['--dump-outputs', str(plain)])
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'config'):
+        assert k in d, k
+    assert d['n_gpus'] == 1 and d['steps'] == 3 and d['warmup'] == 1 and d['higher_is_better'] is True
+    assert abs(d['value'] - 256 * 300 * 10 / (d['ms_per_step'] * 1e-3)) < 1e-6 * d['value']
+    for k in ('roofline', 'kernel_ms_per_iteration', 'roofline_scatter', 'alt_engine', 'ms_per_step_median', 'sweep'):
+        assert k not in d, k
+    assert d['cpu_baseline'] is None
+    f = _run([sys.executable, 'bench.py', '--full', '--no-alt', '--no-cpu-baseline'] + args + ['--dump-outputs', str(full)])
+    assert 'roofline' in f and 'kernel_ms_per_iteration' in f
+    names = sorted(os.listdir(str(plain)))
+    assert names == ['actions.npy', 'nominal.npy', 'rewards.npy', 'states.npy'] and sorted(os.listdir(str(full))) == names
+    shapes = {'actions.npy': (256, 10, 4), 'nominal.npy': (10, 4), 'rewards.npy': (256,), 'states.npy': (256, 10, 300, 3)}
+    assert sum(os.path.getsize(str(plain / n)) for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(str(plain / n)), np.load(str(full / n))
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape == shapes[n] and np.isfinite(a).all(), n
+        np.testing.assert_allclose(a, b, rtol=1e-5, atol=1e-6, err_msg=n)
 
 
 def test_the_propagation_kernels_count_what_they_execute():
@@ -113,7 +140,7 @@ def test_the_propagation_kernels_count_what_they_execute():
 
 
 def test_the_sweep_block_carries_the_other_baseline_workloads():
-    d = _run([sys.executable, 'bench.py', '--steps', '2', '--warmup', '1', '--samples', '128', '--no-alt', '--no-cpu-baseline',
+    d = _run([sys.executable, 'bench.py', '--full', '--steps', '2', '--warmup', '1', '--samples', '128', '--no-alt', '--no-cpu-baseline',
               '--sweep'])
     names = [e['name'] for e in d['sweep']]
     assert names == ['p20', 'c4-50', 'c4-150', 'c4-600', 'c5-share', 'gd-demo']

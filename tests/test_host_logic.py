@@ -117,6 +117,37 @@ def test_visible_gpu_count_follows_the_visibility_variables(monkeypatch):
     assert bench.visible_gpu_count() == 1
 
 
+def test_dumped_outputs_are_a_seeded_subset_of_the_samples_within_the_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs (bench.dump_outputs): float32 / float64 files only; samples that do not all fit keep the same
+    fixed subset in every per-sample array, the same subset on every call, and the files stay within the budget."""
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_BUDGET', 1 << 20)
+    B, H, N = 512, 4, 50
+    row = np.arange(B, dtype=np.float32)
+    arrays = {'actions': np.broadcast_to(row[:, None, None], (B, H, 4)), 'rewards': row.copy(),
+              'states': np.broadcast_to(row[:, None, None, None], (B, H, N, 3))}
+    nominal = np.linspace(0, 1, H * 4).reshape(H, 4)
+    got = []
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), fixed={'nominal': nominal, 'count': np.arange(3)}, per_sample=arrays)
+        files = sorted(os.listdir(str(tmp_path / d)))
+        assert files == ['actions.npy', 'count.npy', 'nominal.npy', 'rewards.npy', 'states.npy']
+        assert sum(os.path.getsize(str(tmp_path / d / f)) for f in files) <= 1 << 20
+        got.append({f[:-4]: np.load(str(tmp_path / d / f)) for f in files})
+    a = got[0]
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    np.testing.assert_array_equal(a['nominal'], nominal)
+    np.testing.assert_array_equal(a['count'], [0.0, 1.0, 2.0])
+    kept = a['rewards']
+    assert 0 < len(kept) < B and (np.diff(kept) > 0).all()
+    np.testing.assert_array_equal(a['actions'][:, 0, 0], kept)
+    np.testing.assert_array_equal(a['states'][:, 0, 0, 0], kept)
+    for k in a:
+        np.testing.assert_array_equal(got[1][k], a[k])
+    bench.dump_outputs(str(tmp_path / 'c'), per_sample={'rewards': row})               # fits: every sample, as given
+    np.testing.assert_array_equal(np.load(str(tmp_path / 'c' / 'rewards.npy')), row)
+
+
 def test_the_planners_result_slots_are_the_librarys():
     """planners.GD_SLOTS mirrors include/drp.h's DRP_GD_SLOTS (drp_gd_step_async refuses slots beyond it), and the planner
     never has more iterations in flight than there are slots."""

@@ -3,7 +3,7 @@
 for rep in 1 2; do
   for lib in "$@"; do
     echo "== $lib"
-    DRP_LIB=$PWD/$lib python bench.py --no-cpu-baseline --no-alt --steps 30 --warmup 5 2>/dev/null | python -c "
+    DRP_LIB=$PWD/$lib python bench.py --full --no-cpu-baseline --no-alt --steps 30 --warmup 5 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

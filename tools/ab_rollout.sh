@@ -2,7 +2,7 @@
 # km_rollout (the whole rollout in one launch) against the step-by-step pipeline, per particle count
 for n in "$@"; do
   for v in "DRP_DUMMY=0" "DRP_NO_ROLLOUT_FUSED=1"; do
-    env $v python bench.py --particles $n --samples 1024 --horizon 10 --steps 30 --warmup 5 --no-alt --no-cpu-baseline 2>/dev/null | python -c "
+    env $v python bench.py --particles $n --samples 1024 --horizon 10 --steps 30 --warmup 5 --full --no-alt --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -19,18 +19,18 @@ pmc() {  # tag, pass name, counters (one string), bench arguments...
   rocprofv3 --pmc $ctr --output-format csv -d $O/${tag}_${pass} -- python3 bench.py "$@" > $O/${tag}_${pass}.log 2>&1
   python3 profiles/reduce_pmc.py $(ls $O/${tag}_${pass}/*/*_counter_collection.csv | head -1) $O/summ/r06_${tag}_pmc_${pass}_per_kernel.csv
 }
-B="--steps 10 --warmup 2 --no-alt --no-cpu-baseline --no-sweep"
+B="--steps 10 --warmup 2 --full --no-alt --no-cpu-baseline --no-sweep"
 run fused $B
 pmc fused fetch FETCH_SIZE $B
 pmc fused write WRITE_SIZE $B
 pmc fused sq "$SQ" $B
 python3 profiles/summarize_pmc.py fused $(ls $O/fused_fetch/*/*_counter_collection.csv | head -1) $(ls $O/fused_write/*/*_counter_collection.csv | head -1) > $O/summ/traffic_fused.txt
-M="--steps 10 --warmup 2 --engine mfma --no-alt --no-cpu-baseline --no-sweep"
+M="--steps 10 --warmup 2 --full --engine mfma --no-alt --no-cpu-baseline --no-sweep"
 run mfma $M
 pmc mfma fetch FETCH_SIZE $M
 pmc mfma write WRITE_SIZE $M
 python3 profiles/summarize_pmc.py mfma $(ls $O/mfma_fetch/*/*_counter_collection.csv | head -1) $(ls $O/mfma_write/*/*_counter_collection.csv | head -1) > $O/summ/traffic_mfma.txt
-G="--config gd-demo --steps 30 --warmup 3 --no-cpu-baseline"
+G="--config gd-demo --steps 30 --warmup 3 --full --no-cpu-baseline"
 run gd_demo $G
 pmc gd_demo fetch FETCH_SIZE $G
 pmc gd_demo write WRITE_SIZE $G
@@ -39,7 +39,7 @@ pmc gd_demo sq2 "$SQ2" $G
 python3 profiles/summarize_pmc.py gd-demo $(ls $O/gd_demo_fetch/*/*_counter_collection.csv | head -1) $(ls $O/gd_demo_write/*/*_counter_collection.csv | head -1) > $O/summ/traffic_gd.txt
 # the sweep's workloads: kernel stats, HBM-side bytes and the MFMA / VALU counters of their dominant kernel
 for c in p20 c4-50 c4-150 c4-600 c5-share; do
-  S="--config $c --steps 5 --warmup 2 --no-alt --no-cpu-baseline --no-sweep"
+  S="--config $c --steps 5 --warmup 2 --full --no-alt --no-cpu-baseline --no-sweep"
   run $c $S
   pmc $c fetch FETCH_SIZE $S
   pmc $c write WRITE_SIZE $S
@@ -82,8 +82,8 @@ python3 -m pytest tests/test_gpu_census.py -q -s 2>&1 | grep -v "^\.$" | grep "c
 python3 tools/gd_timing.py 5 10 20 30 40 50 100 > $O/summ/r06_gd_timing.txt 2>&1
 python3 tools/planner_timing.py > $O/summ/r06_planner_timing.txt 2>&1
 # the bench lines of this build on this box
-python3 bench.py > $O/summ/r06_bench_default.json 2> $O/bench_default.err
-python3 bench.py --config gd-demo > $O/summ/r06_bench_gd_demo.json 2>/dev/null
+python3 bench.py --full > $O/summ/r06_bench_default.json 2> $O/bench_default.err
+python3 bench.py --config gd-demo --full > $O/summ/r06_bench_gd_demo.json 2>/dev/null
 # keep only the summaries (the traces are large)
 find $O -name "*kernel_trace.csv" -delete
 find $O -name "*counter_collection.csv" -delete

@@ -6,7 +6,7 @@
 # a line where the alternative wins by more than a few per cent on a new part or driver is the one to re-tune.
 run() {  # samples particles "ENV=..."|-
   if [ "$3" = "-" ]; then pre=""; else pre="$3"; fi
-  env $pre python bench.py --particles $2 --samples $1 --horizon 10 --steps 120 --warmup 30 --no-alt --no-cpu-baseline --no-sweep 2>/dev/null | python -c "
+  env $pre python bench.py --particles $2 --samples $1 --horizon 10 --steps 120 --warmup 30 --full --no-alt --no-cpu-baseline --no-sweep 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):
