@@ -31,7 +31,6 @@ int drp_create(int device, drp_ctx** out) {
     if (const char* e = getenv("DRP_GRAPH_CELLS_HALO")) c->graph_cells_halo = (float)atof(e);
     c->rollout_fused = getenv("DRP_NO_ROLLOUT_FUSED") == nullptr;
     c->repack_device = getenv("DRP_NO_REPACK_DEVICE") == nullptr;
-    c->bwd_edge_mfma = getenv("DRP_NO_BWD_EDGE_MFMA") == nullptr;
     c->prop_spread = getenv("DRP_NO_PROP_SPREAD") == nullptr;
     c->wgrad_mfma = getenv("DRP_NO_WGRAD_MFMA") == nullptr;
     c->wgrad_defer = getenv("DRP_NO_WGRAD_DEFER") == nullptr;
@@ -42,7 +41,6 @@ int drp_create(int device, drp_ctx** out) {
     if (const char* e = getenv("DRP_PROP_PAIR_DEG10")) c->prop_pair_deg10 = std::max(0, atoi(e));
     c->bwd_fused = getenv("DRP_NO_BWD_FUSED") == nullptr;
     c->bwd_rows = getenv("DRP_NO_BWD_ROWS") == nullptr;
-    c->bwd_valu_stages = getenv("DRP_BWD_VALU_STAGES") != nullptr;
     if (const char* e = getenv("DRP_TRAIN_PARTS")) c->train_parts = atoi(e);
     c->debug_force_giveup = getenv("DRP_DEBUG_FORCE_GIVEUP") != nullptr;
     c->train_copy_upload = getenv("DRP_TRAIN_COPY_UPLOAD") != nullptr;
@@ -65,14 +63,13 @@ int drp_create(int device, drp_ctx** out) {
         hipFuncSetAttribute((const void*)k_graph_strips_q<GRAPH_THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
         hipFuncSetAttribute((const void*)k_graph_strips_q<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
         hipFuncSetAttribute((const void*)kb_reward, hipFuncAttributeMaxDynamicSharedMemorySize, (int)KB_REWARD_LDS(4096)) != hipSuccess ||
-        hipFuncSetAttribute((const void*)kb_edge_encode, hipFuncAttributeMaxDynamicSharedMemorySize, (int)KB_EDGE_ENCODE_LDS) != hipSuccess ||
         hipFuncSetAttribute((const void*)kb_reverse_lists<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)KB_REV_LDS(KB_REV_LDS_MAX_N, 1)) != hipSuccess ||
         hipFuncSetAttribute((const void*)kb_reverse_lists<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)KB_REV_LDS(KB_REV_LDS_MAX_N, 1)) != hipSuccess ||
         hipFuncSetAttribute((const void*)k_aggregate_lds, hipFuncAttributeMaxDynamicSharedMemorySize,
                             K_AGG_LDS_MAX_N * 256) != hipSuccess) {
         (void)hipStreamDestroy(c->stream);
         delete c;
-        return fail(nullptr, DRP_EHIP, "hipFuncSetAttribute (dynamic LDS size of k_graph, kb_edge_encode, kb_reverse_lists or k_aggregate_lds) failed");
+        return fail(nullptr, DRP_EHIP, "hipFuncSetAttribute (dynamic LDS size of k_graph, kb_reverse_lists or k_aggregate_lds) failed");
     }
     // the MFMA kernels keep packed weights + per-wave transposition tiles in LDS (> 64 KiB)
     if (hipFuncSetAttribute((const void*)km_edge_encode, hipFuncAttributeMaxDynamicSharedMemorySize, KM_EDGE_LDS) != hipSuccess ||

@@ -26,7 +26,7 @@ enum DispatchVariant {
     DV_PROP3 = DV_PROP + 16,        // + 12 TAPE + 6 PAIR + 2 cache (0 off, 1 on, 2 on with the rows kept in registers) + WORK
     DV_ROLLOUT = DV_PROP3 + 24,     // + 6 PAIR + 2 cache + WORK
     DV_REWARD = DV_ROLLOUT + 12, DV_BWD_REWARD, DV_REV_256, DV_REV_1024, DV_BWD_ROWS, DV_BWD_STEP, DV_BWD_STAGES_MFMA,
-    DV_BWD_STAGES_VALU, DV_BWD_EDGE_MFMA, DV_BWD_EDGE_VALU, DV_TRAIN_NODE_FUSED, DV_TRAIN_NODE_FUSED_COOP, DV_TRAIN_NODE_MFMA, DV_TRAIN_NODE_VALU, DV_WGRAD_MFMA, DV_WGRAD_VALU,
+    DV_BWD_EDGE_MFMA, DV_TRAIN_NODE_FUSED, DV_TRAIN_NODE_FUSED_COOP, DV_TRAIN_NODE_MFMA, DV_WGRAD_MFMA, DV_WGRAD_VALU,
     DV_WGRAD_DEFERRED, DV_MPPI_SOFTMAX, DV_ELITE_SORT, DV_ELITE_ROUNDS, DV_FPS_REG, DV_FPS_MEM, DV_DT_CV5, DV_DT_EXACT,
     DV_TRAIN_BARRIER_RETRY,
     DV_COUNT
@@ -76,13 +76,10 @@ void dv_name(int id, char* buf, size_t n, bool* by_default) {
         case DV_BWD_ROWS: s = "bwd:kmb_rows_bwd"; break;
         case DV_BWD_STEP: s = "bwd:kmb_step_bwd"; break;
         case DV_BWD_STAGES_MFMA: s = "bwd:stages kmb_*"; break;
-        case DV_BWD_STAGES_VALU: s = "bwd:stages kb_*"; dflt = false; break;              // DRP_BWD_VALU_STAGES=1 (KMB_MIN_TILES is 1 since round 3)
         case DV_BWD_EDGE_MFMA: s = "bwd:kmb_edge_encode"; break;
-        case DV_BWD_EDGE_VALU: s = "bwd:kb_edge_encode"; dflt = false; break;
         case DV_TRAIN_NODE_FUSED: s = "train:kmb_step_bwd<dump>"; dflt = false; break;    // DRP_TRAIN_COOP=0 (by default a workgroup of the one-launch pass has one tile)
         case DV_TRAIN_NODE_FUSED_COOP: s = "train:kmb_step_bwd<dump,coop>"; break;
         case DV_TRAIN_NODE_MFMA: s = "train:stages kmb_*"; break;
-        case DV_TRAIN_NODE_VALU: s = "train:stages kb_*"; dflt = false; break;
         case DV_WGRAD_MFMA: s = "train:kt_wgrad_mfma"; break;
         case DV_WGRAD_VALU: s = "train:kt_wgrad"; dflt = false; break;
         case DV_WGRAD_DEFERRED: s = "train:deferred wgrad lists"; break;
@@ -234,7 +231,6 @@ struct drp_ctx {
     bool train_copy_upload = false; // DRP_TRAIN_COPY_UPLOAD=1: the training batch goes up by a copy on the stream instead of inside kt_unpack_inputs
     bool debug_force_giveup = false; // DRP_DEBUG_FORCE_GIVEUP=1 (tests): drp_train_step's first pass ends as if kmb_step_bwd's barrier had timed out
     int train_parts = 0;            // DRP_TRAIN_PARTS=n: workgroups per group of samples in the trainer's kmb_step_bwd (0: as many as there are CUs for)
-    bool bwd_valu_stages = false;   // DRP_BWD_VALU_STAGES=1: the reverse-mode node stages on the VALU row kernels (kb_predict ... kb_node_encode; cross-check)
     bool bwd_rows = true;           // DRP_NO_BWD_ROWS=1: piles of up to 256 particles through kmb_step_bwd (rows through memory) instead of kmb_rows_bwd
     bool prop3_order = true;        // false: km_prop3's tiles in the natural row order instead of by in-degree
     int prop_pair_rows = 128;       // DRP_PROP_PAIR_ROWS: a workgroup of the whole-sample kernels with up to so many rows runs tiles of
@@ -398,7 +394,6 @@ struct drp_ctx {
                                     // of samples (fewer workgroups than half the CUs) / whenever the plain sweep is chosen
     bool wgrad_mfma = true;         // DRP_NO_WGRAD_MFMA=1: the weight gradients' outer-product sums on the VALU kernel (kt_wgrad_multi)
     bool prop_spread = true;        // DRP_NO_PROP_SPREAD=1: km_prop's tiles eight to a workgroup whatever their number
-    bool bwd_edge_mfma = true;      // DRP_NO_BWD_EDGE_MFMA=1: the relation encoder's backward on the VALU kernel (kb_edge_encode)
     bool repack_device = true;      // DRP_NO_REPACK_DEVICE=1: fetch the blob and run the host packers (the round-2 path)
 
     // km_rollout's argument block (device copy + what it holds)

@@ -20,57 +20,31 @@ int gd_forward_backward(drp_ctx* c) {
     const size_t bn = (size_t)B * N;
     const size_t hstride = (size_t)H * N * 3;
     hipStream_t st = c->stream;
-    const bool rev_lds = N <= KB_REV_LDS_MAX_N && !c->rev_global_only;
     float* states = ptr<float>(c->states);
-    float* eh = ptr<float>(c->eff_hist);
-    unsigned* mh = ptr<unsigned>(c->tape_mask);
     auto d2d = [&](void* dst, const void* src, size_t bytes) -> int {
         HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st));
         return DRP_OK;
     };
-    // ---- forward on the fused engine; km_prop<., TAPE> leaves what the backward pass needs: the
-    //      effect after the encoder and after every propagation step, and the ReLU masks of the edges
-    const int saved_engine = c->engine;
-    c->engine = c->gd_engine;
     // the self-edge constants depend on attributes and densities only: computed once per GD problem,
     // again only if a rollout in between has reused the buffer
-    int rc = DRP_OK;
     if (c->gd_cself_tag != c->cself_tag || c->gd_cself_tag == 0) {
-        rc = prepare_cself(c, nb, N, B, &c->gd_cself, &c->gd_cself_ok);
+        const int rc = prepare_cself(c, nb, N, B, &c->gd_cself, &c->gd_cself_ok, c->gd_engine);
         c->gd_cself_tag = c->cself_tag;
+        CHK(rc);
     }
-    const float* cself = c->gd_cself;
-    const uint8_t* cself_ok = c->gd_cself_ok;
+    // ---- forward on the fused engine with tape
     bool rev_built = false;
-    for (int t = 0; t < H && rc == DRP_OK; ++t) {
-        StepArgs a{};
-        if (t == 0) { a.s_prev = ptr<float>(c->s_in); a.prev_mod = nb; a.prev_stride = (size_t)N * 3; }
-        else { a.s_prev = states + (size_t)(t - 1) * N * 3; a.prev_mod = B; a.prev_stride = hstride; }
-        a.attr = ptr<float>(c->attr); a.attr_mod = nb;
-        a.dens = ptr<float>(c->dens); a.dens_mod = nb;
-        a.actions = ptr<float>(c->actions) + (size_t)t * 4; a.act_stride = (size_t)H * 4;
-        a.build_graph = true;
-        a.s_out = states + (size_t)t * N * 3; a.out_stride = hstride;
-        a.B = B; a.N = N;
-        a.eff_hist = eh + (size_t)t * 4 * bn * 64;
-        a.mask_hist = mh + (size_t)t * DRP_PSTEP * bn * DRP_K * 2;
-        a.cself = cself; a.cself_ok = cself_ok;
-        if (H == 1) { a.rev_off = ptr<int>(c->rev_off); a.rev = ptr<int>(c->rev); a.rev_built = &rev_built; }   // one set of reversed lists: the only step's
-        // the step's impulses and neighbour lists are part of the tape: the step writes them there (its
-        // workspace pointers are lent the tape's slices for the call) instead of being copied afterwards
-        void* const save_sd = c->s_delta.p; void* const save_idx = c->nbr_idx.p; void* const save_cnt = c->nbr_cnt.p;
-        c->s_delta.p = ptr<float>(c->tape_sdelta) + (size_t)t * bn * 3;
-        c->nbr_idx.p = ptr<int16_t>(c->tape_idx) + (size_t)t * bn * DRP_K;
-        c->nbr_cnt.p = ptr<uint8_t>(c->tape_cnt) + (size_t)t * bn;
-        rc = run_step(c, a);
-        c->s_delta.p = save_sd; c->nbr_idx.p = save_idx; c->nbr_cnt.p = save_cnt;
-        if (rc != DRP_OK) break;
+    {
+        TapeFwd f{};
+        f.s0 = ptr<float>(c->s_in); f.s0_mod = nb; f.s0_stride = (size_t)N * 3;
+        f.mod = nb;
+        f.actions = ptr<float>(c->actions);
+        f.tape = true;
+        f.cself = c->gd_cself; f.cself_ok = c->gd_cself_ok;
+        if (H == 1) { f.rev_off = ptr<int>(c->rev_off); f.rev = ptr<int>(c->rev); f.rev_built = &rev_built; }   // one set of reversed lists: the only step's
+        CHK(run_tape_forward(c, c->gd_engine, B, N, H, f));
     }
-    c->engine = saved_engine;
-    CHK(rc);
     // reward of the final step only (planners.py:436-438) and its gradient, in one launch
-    const float* vw = ptr<float>(c->w_valu);
-    const float* wraw = ptr<float>(c->w_raw);
     float* g_state = ptr<float>(c->g_state);                 // [H][B,N,3]
     {
         ProbeScope ps(c, KC_BWD_REWARD);
@@ -83,22 +57,20 @@ int gd_forward_backward(drp_ctx* c) {
         const float* s_prev = (t == 0) ? ptr<float>(c->s_in) : states + (size_t)(t - 1) * N * 3;
         const int prev_mod = (t == 0) ? nb : B;
         const size_t prev_stride = (t == 0) ? (size_t)N * 3 : hstride;
-        float* eht = eh + (size_t)t * 4 * bn * 64;
-        const unsigned* mht = mh + (size_t)t * DRP_PSTEP * bn * DRP_K * 2;
         const int16_t* idx = ptr<int16_t>(c->tape_idx) + (size_t)t * bn * DRP_K;
-        const uint8_t* cnt = ptr<uint8_t>(c->tape_cnt) + (size_t)t * bn;
         float* g_out = g_state + (size_t)t * bn * 3;
-        float* gah = ptr<float>(c->g_agg_hist);
-        if (!rev_built) {
-            ProbeScope ps(c, KC_BWD_LISTS);
-            c->dv(N <= 512 ? DV_REV_256 : DV_REV_1024);
-            if (N <= 512)
-                hipLaunchKernelGGL(kb_reverse_lists<256>, dim3(B), dim3(256), KB_REV_LDS(N, rev_lds), st, idx,
-                                   cnt, N, ptr<int>(c->rev_off), ptr<int>(c->rev), rev_lds ? 1 : 0, (const int*)nullptr);
-            else
-                hipLaunchKernelGGL(kb_reverse_lists<1024>, dim3(B), dim3(1024), KB_REV_LDS(N, rev_lds), st, idx,
-                                   cnt, N, ptr<int>(c->rev_off), ptr<int>(c->rev), rev_lds ? 1 : 0, (const int*)nullptr);
-        }
+        BwdStep s{};
+        s.B = B; s.N = N; s.mod = nb;
+        s.eht = ptr<float>(c->eff_hist) + (size_t)t * 4 * bn * 64;
+        s.mht = ptr<unsigned>(c->tape_mask) + (size_t)t * DRP_PSTEP * bn * DRP_K * 2;
+        s.cnt = ptr<uint8_t>(c->tape_cnt) + (size_t)t * bn;
+        s.rev_off = ptr<int>(c->rev_off); s.rev = ptr<int>(c->rev);
+        s.sdelta = ptr<float>(c->tape_sdelta) + (size_t)t * bn * 3;
+        s.g_out = g_out;
+        s.gah = ptr<float>(c->g_agg_hist);
+        s.ge_tmp = ptr<float>(c->g_eff); s.g_cnode = ptr<float>(c->g_cnode);
+        for (int v = 0; v < 3; ++v) { s.d.ge[v] = ptr<float>(c->g_eff); s.d.gp[v] = ptr<float>(c->g_proj); }
+        if (!rev_built) launch_reverse_lists(c, idx, s.cnt, N, B, nullptr, 0);
         const int spw_b = (B + c->n_cu - 1) / c->n_cu;
         if (c->bwd_fused && c->bwd_rows && N <= KMB_ROWS_MAX) {
             // piles of up to 256 particles: a workgroup takes groups of whole samples with at most 256 rows, a wave keeps
@@ -113,89 +85,22 @@ int gd_forward_backward(drp_ctx* c) {
             c->dv(DV_BWD_ROWS);
             hipLaunchKernelGGL(kmb_rows_bwd, dim3((unsigned)(n_groups < (long)c->n_cu ? n_groups : (long)c->n_cu)), dim3(64 * KMB_FUSED_WAVES),
                                KMB_ROWS_LDS, st, ptr<float>(c->w_mfma), ptr<float>(c->w_mfma_bwd), ptr<uint16_t>(c->w_split6),
-                               ptr<uint16_t>(c->w_split6_bwd), eht, mht, cnt, ptr<int>(c->rev_off),
-                               ptr<int>(c->rev), g_out, (size_t)N * 3, ptr<float>(c->tape_sdelta) + (size_t)t * bn * 3, ptr<float>(c->attr),
-                               nb, ptr<float>(c->dens), nb, N, B, gps, t > 0 ? gah : (float*)nullptr, ptr<float>(c->g_sdelta));
+                               ptr<uint16_t>(c->w_split6_bwd), s.eht, s.mht, s.cnt, s.rev_off, s.rev, g_out, (size_t)N * 3, s.sdelta,
+                               ptr<float>(c->attr), nb, ptr<float>(c->dens), nb, N, B, gps, t > 0 ? s.gah : (float*)nullptr,
+                               ptr<float>(c->g_sdelta));
         } else if (c->bwd_fused && whole_samples(c, B, N) && ((long)spw_b * N + 31) / 32 >= c->bwd_fused_min_tiles) {
             // chip-filling batches: everything between the reward's gradient and the impulses' in one launch,
             // a workgroup owning whole samples (kmb_step_bwd)
             ProbeScope ps(c, KC_BWD_NODE);
             c->dv(DV_BWD_STEP);
             hipLaunchKernelGGL((kmb_step_bwd<false, false>), dim3((unsigned)((B + spw_b - 1) / spw_b)), dim3(64 * KMB_FUSED_WAVES), KMB_FUSED_LDS, st,
-                               ptr<float>(c->w_mfma), ptr<float>(c->w_mfma_bwd), eht, mht, cnt, ptr<int>(c->rev_off), ptr<int>(c->rev),
-                               g_out, (size_t)N * 3, ptr<float>(c->tape_sdelta) + (size_t)t * bn * 3, ptr<float>(c->attr), nb,
-                               ptr<float>(c->dens), nb, N, B, spw_b, ptr<float>(c->g_eff), ptr<float>(c->g_cnode), gah,
+                               ptr<float>(c->w_mfma), ptr<float>(c->w_mfma_bwd), s.eht, s.mht, s.cnt, s.rev_off, s.rev,
+                               g_out, (size_t)N * 3, s.sdelta, ptr<float>(c->attr), nb,
+                               ptr<float>(c->dens), nb, N, B, spw_b, s.ge_tmp, s.g_cnode, s.gah,
                                ptr<float>(c->g_sdelta), KmbDump{}, 1, (unsigned*)nullptr, (unsigned*)nullptr);
-        } else if ((long)B * ((N + 31) / 32) >= KMB_MIN_TILES && !c->bwd_valu_stages) {      // node stages on the matrix cores
-            const float* mw = ptr<float>(c->w_mfma);
-            const float* mb = ptr<float>(c->w_mfma_bwd);
-            const long node_tiles = (long)B * ((N + 31) / 32);
-            const dim3 ngrid(mfma_grid_spread(c, node_tiles)), nblk(64 * MFMA_WAVES);
-            c->dv(DV_BWD_STAGES_MFMA);
-            { ProbeScope ps(c, KC_BWD_NODE);
-            hipLaunchKernelGGL(kmb_predict, ngrid, nblk, KMB_PREDICT_LDS, st, mw, mb, eht + 3 * bn * 64, g_out, (size_t)N * 3, N, B,
-                               ptr<float>(c->g_eff), (float*)nullptr, (float*)nullptr);
-            }
-            // update of the last propagation step, then per step: edge terms, and in one launch the
-            // projection of this step with the update of the one before
-            { ProbeScope ps(c, KC_BWD_NODE);
-            hipLaunchKernelGGL((kmb_node_step<false, true>), ngrid, nblk, KMB_STEP_LDS(false, true), st, mb, ptr<float>(c->g_eff),
-                               ptr<float>(c->g_eff), (const float*)nullptr, eht + (size_t)DRP_PSTEP * bn * 64, ptr<float>(c->g_cnode), 1,
-                               gah + (size_t)(DRP_PSTEP - 1) * bn * 64, N, B);
-            }
-            for (int p = DRP_PSTEP - 1; p >= 0; --p) {
-                float* g_agg_p = gah + (size_t)p * bn * 64;
-                const unsigned* mask_p = mht + (size_t)p * bn * DRP_K * 2;
-                { ProbeScope ps(c, KC_BWD_EDGE);
-                hipLaunchKernelGGL(kb_edge_terms, dim3(B), dim3(256), 0, st, g_agg_p, mask_p, cnt, ptr<int>(c->rev_off),
-                                   ptr<int>(c->rev), N, ptr<float>(c->g_proj), 1);
-                }
-                if (p > 0)
-                    { ProbeScope ps(c, KC_BWD_NODE);
-                    hipLaunchKernelGGL((kmb_node_step<true, true>), ngrid, nblk, KMB_STEP_LDS(true, true), st, mb,
-                                       ptr<float>(c->g_eff), ptr<float>(c->g_eff), ptr<float>(c->g_proj), eht + (size_t)p * bn * 64,
-                                       ptr<float>(c->g_cnode), 0, gah + (size_t)(p - 1) * bn * 64, N, B);
-                    }
-                else
-                    { ProbeScope ps(c, KC_BWD_NODE);
-                    hipLaunchKernelGGL((kmb_node_step<true, false>), ngrid, nblk, KMB_STEP_LDS(true, false), st, mb,
-                                       ptr<float>(c->g_eff), ptr<float>(c->g_eff), ptr<float>(c->g_proj), (const float*)nullptr, (float*)nullptr, 0,
-                                       (float*)nullptr, N, B);
-                    }
-            }
-            { ProbeScope ps(c, KC_BWD_NODE);
-            hipLaunchKernelGGL(kmb_node_encode, ngrid, nblk, KMB_NODE_ENCODE_LDS, st, mw, mb,
-                               ptr<float>(c->tape_sdelta) + (size_t)t * bn * 3, ptr<float>(c->attr), nb, ptr<float>(c->dens), nb,
-                               eht, ptr<float>(c->g_eff), ptr<float>(c->g_cnode), N, B, ptr<float>(c->g_sdelta), (float*)nullptr,
-                               (float*)nullptr, (float*)nullptr, (float*)nullptr);
-            }
         } else {
-            c->dv(DV_BWD_STAGES_VALU);
-            { ProbeScope ps(c, KC_BWD_NODE);
-            hipLaunchKernelGGL(kb_predict, dim3(B), dim3(256), 0, st, vw, wraw, eht + 3 * bn * 64, g_out, (size_t)N * 3, N,
-                               ptr<float>(c->g_eff), (float*)nullptr, (float*)nullptr, 1);
-            }
-            for (int p = DRP_PSTEP - 1; p >= 0; --p) {
-                float* g_agg_p = gah + (size_t)p * bn * 64;
-                const unsigned* mask_p = mht + (size_t)p * bn * DRP_K * 2;
-                { ProbeScope ps(c, KC_BWD_NODE);
-                hipLaunchKernelGGL(kb_update, dim3(B), dim3(256), 0, st, wraw, eht + (size_t)(p + 1) * bn * 64,
-                                   ptr<float>(c->g_eff), ptr<float>(c->g_cnode), p == DRP_PSTEP - 1 ? 1 : 0, N, g_agg_p, 1);
-                }
-                { ProbeScope ps(c, KC_BWD_EDGE);
-                hipLaunchKernelGGL(kb_edge_terms, dim3(B), dim3(256), 0, st, g_agg_p, mask_p, cnt, ptr<int>(c->rev_off),
-                                   ptr<int>(c->rev), N, ptr<float>(c->g_proj), 1);
-                }
-                { ProbeScope ps(c, KC_BWD_NODE);
-                hipLaunchKernelGGL(kb_project, dim3(B), dim3(256), 0, st, wraw, ptr<float>(c->g_proj), N, ptr<float>(c->g_eff), 1);
-                }
-            }
-            { ProbeScope ps(c, KC_BWD_NODE);
-            hipLaunchKernelGGL(kb_node_encode, dim3(B), dim3(256), 0, st, vw, wraw,
-                               ptr<float>(c->tape_sdelta) + (size_t)t * bn * 3, ptr<float>(c->attr), nb, ptr<float>(c->dens),
-                               nb, eht, ptr<float>(c->g_eff), ptr<float>(c->g_cnode), N, ptr<float>(c->g_sdelta),
-                               (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, 1);
-            }
+            c->dv(DV_BWD_STAGES_MFMA);
+            launch_node_stages(c, s, dim3(B), 1, nullptr);
         }
         float* g_prev = nullptr;
         if (t > 0) {
@@ -203,17 +108,12 @@ int gd_forward_backward(drp_ctx* c) {
             g_prev = g_state + (size_t)(t - 1) * bn * 3;
             CHK(d2d(g_prev, g_out, bn * 3 * sizeof(float)));
             { ProbeScope ps(c, KC_BWD_EDGE);
-            c->dv(c->bwd_edge_mfma ? DV_BWD_EDGE_MFMA : DV_BWD_EDGE_VALU);
-            if (c->bwd_edge_mfma)
-                launch_edge_encode_mfma(c, s_prev, prev_mod, prev_stride, nb, idx, cnt, gah, mht, bn, N, B, ptr<float>(c->gpos_edge), KbEdgeDump{});
-            else
-                hipLaunchKernelGGL(kb_edge_encode, dim3(B), dim3(256), KB_EDGE_ENCODE_LDS, st, vw, wraw,
-                                   s_prev, prev_mod, prev_stride, ptr<float>(c->attr), nb, ptr<float>(c->dens), nb, idx, cnt,
-                                   gah, mht, bn, N, g_prev, (size_t)N * 3, ptr<float>(c->gpos_edge), KbEdgeDump{}, 1);
+            c->dv(DV_BWD_EDGE_MFMA);
+            launch_edge_encode_mfma(c, s_prev, prev_mod, prev_stride, nb, idx, s.cnt, s.gah, s.mht, bn, N, B, ptr<float>(c->gpos_edge), KbEdgeDump{});
             }
             { ProbeScope ps(c, KC_BWD_EDGE);
             hipLaunchKernelGGL(kb_gather_pos, dim3((N + 255) / 256, B), dim3(256), 0, st, ptr<float>(c->gpos_edge),
-                               ptr<int>(c->rev_off), ptr<int>(c->rev), N, g_prev, (size_t)N * 3, c->bwd_edge_mfma ? 1 : 0, cnt);
+                               s.rev_off, s.rev, N, g_prev, (size_t)N * 3, s.cnt);
             }
         }
         { ProbeScope ps(c, KC_BWD_PUSH);
@@ -249,21 +149,11 @@ int drp_gd_begin(drp_ctx* c, const float* s0, const float* attr, const float* de
     CHK(ensure_step_ws(c, B, N, c->gd_engine));
     CHK(ensure(c, c->states, (size_t)H * bn * 3 * sizeof(float)));
     CHK(ensure(c, c->rewards, (size_t)B * sizeof(float)));
-    CHK(ensure(c, c->eff_hist, (size_t)H * 4 * bn * 64 * sizeof(float)));
-    CHK(ensure(c, c->tape_sdelta, (size_t)H * bn * 3 * sizeof(float)));
-    CHK(ensure(c, c->tape_idx, (size_t)H * bn * DRP_K * sizeof(int16_t)));
-    CHK(ensure(c, c->tape_cnt, (size_t)H * bn));
-    CHK(ensure(c, c->tape_mask, (size_t)H * DRP_PSTEP * bn * DRP_K * 2 * sizeof(unsigned)));
-    CHK(ensure(c, c->g_agg_hist, (size_t)DRP_PSTEP * bn * 64 * sizeof(float)));
-    CHK(ensure(c, c->rev_off, (size_t)B * (N + 1) * sizeof(int)));
-    CHK(ensure(c, c->rev, bn * DRP_K * sizeof(int)));
-    CHK(ensure(c, c->gpos_edge, bn * DRP_K * 4 * sizeof(float)));
+    CHK(ensure_tape(c, B, N, H, 1));
     CHK(ensure(c, c->g_eff, bn * 64 * sizeof(float)));
     CHK(ensure(c, c->g_cnode, bn * 64 * sizeof(float)));
-    CHK(ensure(c, c->g_agg, bn * 64 * sizeof(float)));
     CHK(ensure(c, c->g_proj, bn * 128 * sizeof(float)));
     CHK(ensure(c, c->g_state, (size_t)H * bn * 3 * sizeof(float)));
-    CHK(ensure(c, c->g_sdelta, bn * 3 * sizeof(float)));
     CHK(ensure(c, c->g_act, (size_t)B * H * 4 * sizeof(float)));
     CHK(ensure(c, c->adam_m, (size_t)B * H * 4 * sizeof(float)));
     CHK(ensure(c, c->adam_v, (size_t)B * H * 4 * sizeof(float)));

@@ -656,10 +656,11 @@ int run_reward(drp_ctx* c, const float* state, size_t row_stride, int rows, int 
 // H-step rollout over device-resident s0/attr/dens (in s_in/attr/dens, nb rows) and actions.
 // Self-edge constant of the fused engine (k_cself): one vector per sample, constant over a whole
 // rollout (it depends on the attributes and the density only).  Null pointers when it does not apply.
-int prepare_cself(drp_ctx* c, int attr_mod, int N, int B, const float** cself, const uint8_t** cself_ok) {
+int prepare_cself(drp_ctx* c, int attr_mod, int N, int B, const float** cself, const uint8_t** cself_ok, int engine = -1) {
+    if (engine < 0) engine = c->engine;
     *cself = nullptr;
     *cself_ok = nullptr;
-    if (c->engine == DRP_ENGINE_FUSED && c->self_const) {
+    if (engine == DRP_ENGINE_FUSED && c->self_const) {
         CHK(ensure(c, c->cself, (size_t)B * 64 * sizeof(float) + (size_t)B));
         float* cs = ptr<float>(c->cself);
         uint8_t* ok = reinterpret_cast<uint8_t*>(cs + (size_t)B * 64);
@@ -921,6 +922,193 @@ void launch_wgrad(drp_ctx* c, const float* g, int ldg, const float* x, int ldx, 
     q.ldg = ldg; q.ldx = ldx; q.lane_stride = lane_stride; q.k_stride = k_stride; q.dens_mod = dens_mod; q.in = IN;
     q.blocks = (int)blocks;
     c->wg_jobs.push_back(q);
+}
+
+// ---- reverse mode, shared by the gradient-descent planner (capi_gd.h) and the trainer (capi_train.h) ------------------
+
+// the tape of H steps of B x N and the backward pass's buffers, sized alike for both; `rev_sets` steps' reversed lists
+// (the planner builds them step by step, the trainer all at once)
+int ensure_tape(drp_ctx* c, int B, int N, int H, int rev_sets) {
+    const size_t bn = (size_t)B * N;
+    CHK(ensure(c, c->eff_hist, (size_t)H * 4 * bn * 64 * sizeof(float)));
+    CHK(ensure(c, c->tape_sdelta, (size_t)H * bn * 3 * sizeof(float)));
+    CHK(ensure(c, c->tape_idx, (size_t)H * bn * DRP_K * sizeof(int16_t)));
+    CHK(ensure(c, c->tape_cnt, (size_t)H * bn));
+    CHK(ensure(c, c->tape_mask, (size_t)H * DRP_PSTEP * bn * DRP_K * 2 * sizeof(unsigned)));
+    CHK(ensure(c, c->g_agg_hist, (size_t)DRP_PSTEP * bn * 64 * sizeof(float)));
+    CHK(ensure(c, c->rev_off, (size_t)rev_sets * B * (N + 1) * sizeof(int)));
+    CHK(ensure(c, c->rev, (size_t)rev_sets * bn * DRP_K * sizeof(int)));
+    CHK(ensure(c, c->gpos_edge, bn * DRP_K * 4 * sizeof(float)));
+    CHK(ensure(c, c->g_sdelta, bn * 3 * sizeof(float)));
+    return DRP_OK;
+}
+
+// The forward pass of H steps on `engine` into c->states.  Step t's impulses are tape_sdelta's slice t; with `tape` its
+// neighbour lists are the tape's slices too (the step's workspace pointers are lent the slices for the call instead of
+// copies afterwards), and km_prop<., TAPE> leaves beside them what the backward pass needs: the effect after the encoder
+// and after every propagation step, the ReLU masks of the edges, with `agg_hist` the aggregated edge effects.
+struct TapeFwd {
+    const float* s0; int s0_mod; size_t s0_stride;   // the first step's input; the later steps read the step before's output
+    int mod;                                         // attributes and densities: sample b reads row b % mod
+    const float* actions;                            // [B][H][4], or null: the impulses are data, already in tape_sdelta
+    bool padded;
+    bool tape;                                       // false: the forward pass alone
+    bool agg_hist;
+    const float* cself; const uint8_t* cself_ok;
+    int* rev_off = nullptr; int* rev = nullptr;      // horizon 1: the reversed lists in the lists' own launch where it can
+    bool* rev_built = nullptr;                       //   (StepArgs)
+};
+int run_tape_forward(drp_ctx* c, int engine, int B, int N, int H, const TapeFwd& f) {
+    struct Lend {                                    // the context's engine and workspaces again, however the loop ends
+        drp_ctx* c; int engine; void* sd; void* idx; void* cnt;
+        ~Lend() { c->engine = engine; c->s_delta.p = sd; c->nbr_idx.p = idx; c->nbr_cnt.p = cnt; }
+    } lend{c, c->engine, c->s_delta.p, c->nbr_idx.p, c->nbr_cnt.p};
+    c->engine = engine;
+    const size_t bn = (size_t)B * N, hstride = (size_t)H * N * 3;
+    float* states = ptr<float>(c->states);
+    for (int t = 0; t < H; ++t) {
+        StepArgs a{};
+        if (t == 0) { a.s_prev = f.s0; a.prev_mod = f.s0_mod; a.prev_stride = f.s0_stride; }
+        else { a.s_prev = states + (size_t)(t - 1) * N * 3; a.prev_mod = B; a.prev_stride = hstride; }
+        a.attr = ptr<float>(c->attr); a.attr_mod = f.mod;
+        a.dens = ptr<float>(c->dens); a.dens_mod = f.mod;
+        if (f.actions) { a.actions = f.actions + (size_t)t * 4; a.act_stride = (size_t)H * 4; }
+        a.build_graph = true;
+        a.s_out = states + (size_t)t * N * 3; a.out_stride = hstride;
+        a.B = B; a.N = N;
+        a.cself = f.cself; a.cself_ok = f.cself_ok;
+        a.padded = f.padded;
+        a.rev_off = f.rev_off; a.rev = f.rev; a.rev_built = f.rev_built;
+        c->s_delta.p = ptr<float>(c->tape_sdelta) + (size_t)t * bn * 3;
+        if (f.tape) {
+            c->nbr_idx.p = ptr<int16_t>(c->tape_idx) + (size_t)t * bn * DRP_K;
+            c->nbr_cnt.p = ptr<uint8_t>(c->tape_cnt) + (size_t)t * bn;
+            a.eff_hist = ptr<float>(c->eff_hist) + (size_t)t * 4 * bn * 64;
+            a.mask_hist = ptr<unsigned>(c->tape_mask) + (size_t)t * DRP_PSTEP * bn * DRP_K * 2;
+            if (f.agg_hist) a.agg_hist = ptr<float>(c->agg_hist) + (size_t)t * 3 * bn * 64;
+        }
+        CHK(run_step(c, a));
+    }
+    return DRP_OK;
+}
+
+// the reversed lists of `sets` samples' neighbour lists into rev_off / rev, a workgroup each; `nums` (nullable): the
+// particle counts, set s reading nums[s % nums_mod] (0: nums[s])
+void launch_reverse_lists(drp_ctx* c, const int16_t* idx, const uint8_t* cnt, int N, int sets, const int* nums, int nums_mod) {
+    const bool rev_lds = N <= KB_REV_LDS_MAX_N && !c->rev_global_only;
+    ProbeScope ps(c, KC_BWD_LISTS);
+    c->dv(N <= 512 ? DV_REV_256 : DV_REV_1024);
+    if (N <= 512)
+        hipLaunchKernelGGL(kb_reverse_lists<256>, dim3(sets), dim3(256), KB_REV_LDS(N, rev_lds), c->stream, idx, cnt, N,
+                           ptr<int>(c->rev_off), ptr<int>(c->rev), rev_lds ? 1 : 0, nums, nums_mod);
+    else
+        hipLaunchKernelGGL(kb_reverse_lists<1024>, dim3(sets), dim3(1024), KB_REV_LDS(N, rev_lds), c->stream, idx, cnt, N,
+                           ptr<int>(c->rev_off), ptr<int>(c->rev), rev_lds ? 1 : 0, nums, nums_mod);
+}
+
+// one rollout step of the backward pass, as its node stages read and write it
+struct BwdStep {
+    int B, N;
+    int mod;                        // attributes and densities: sample b reads row b % mod
+    const float* eht;               // the step's tape: effects [4][B*N][64], ReLU masks [3][B*N*10][2], neighbour counts
+    const unsigned* mht;
+    const uint8_t* cnt;
+    const int* rev_off; const int* rev;
+    const float* sdelta;            // the step's impulses [B*N][3]
+    const float* g_out;             // d loss / d the step's output state [B][N*3]
+    float* gah;                     // g_agg of the three propagation steps [3][B*N][64]
+    float* ge_tmp;                  // the predictor's gradient, which the particle encoder's reads
+    float* g_cnode;
+    KmbDump d;                      // d.ge / d.gp: the propagation steps' pre-activation gradients and edge terms (one buffer for
+                                    // all of them, or one each for the trainer's deferred weight gradients); the dumps for the
+                                    // weight gradients, null for none
+};
+
+// The trainer's weight-gradient jobs of a rollout step's node stages, each to be queued once its operands exist: behind
+// the predictor; per propagation step p = 2, 1, 0 behind its update and behind its edge terms; behind the last update;
+// behind the particle encoder
+struct NodeWgrad {
+    drp_ctx* c;
+    float* G;                       // the gradient blob
+    const float* aht;               // the step's aggregated edge effects [3][B*N][64]
+    const float* dens;
+    void predictor(const BwdStep& s) const {
+        const size_t bn = (size_t)s.B * s.N;
+        launch_wgrad<64>(c, s.d.gh, 64, s.eht + 3 * bn * 64, 64, (long)bn, G + W_PR0_W, 64, 1, G + W_PR0_B, nullptr, nullptr, 1, 1);
+        launch_wgrad<3>(c, s.d.hact, 64, s.g_out, 3, (long)bn, G + W_PR1_W, 1, 64, nullptr, nullptr, nullptr, 1, 1);
+    }
+    void update(const BwdStep& s, int p) const {       // particle propagator, aggregate columns
+        const size_t bn = (size_t)s.B * s.N;
+        launch_wgrad<64>(c, s.d.ge[DRP_PSTEP - 1 - p], 64, aht + (size_t)p * bn * 64, 64, (long)bn, G + W_PP_W + 64, 129, 1,
+                         nullptr, nullptr, nullptr, 1, 1);
+    }
+    void edge_terms(const BwdStep& s, int p) const {   // relation propagator, receiver and sender columns
+        const size_t bn = (size_t)s.B * s.N;
+        launch_wgrad<64>(c, s.d.gp[p], 128, s.eht + (size_t)p * bn * 64, 64, (long)bn, G + W_RP_W + 64, 193, 1,
+                         nullptr, nullptr, nullptr, 1, 1);
+        launch_wgrad<64>(c, s.d.gp[p] + 64, 128, s.eht + (size_t)p * bn * 64, 64, (long)bn, G + W_RP_W + 128, 193, 1,
+                         nullptr, nullptr, nullptr, 1, 1);
+    }
+    void cnode(const BwdStep& s) const {               // particle propagator, encoder columns + density column + bias
+        const size_t bn = (size_t)s.B * s.N;
+        launch_wgrad<64>(c, s.g_cnode, 64, s.eht, 64, (long)bn, G + W_PP_W, 129, 1, G + W_PP_B, G + W_PP_W + 128, dens, s.B,
+                         (long)s.N);
+    }
+    void encoder(const BwdStep& s) const {             // particle encoder
+        const size_t bn = (size_t)s.B * s.N;
+        launch_wgrad<64>(c, s.d.gpe, 64, s.d.a1n, 64, (long)bn, G + W_PE2_W, 64, 1, G + W_PE2_B, nullptr, nullptr, 1, 1);
+        launch_wgrad<5>(c, s.d.gh1, 64, s.d.xn, 8, (long)bn, G + W_PE0_W, 5, 1, G + W_PE0_B, nullptr, nullptr, 1, 1);
+    }
+};
+
+// The node stages of a rollout step's backward pass, a launch per stage on the matrix cores: the predictor, the update of
+// the last propagation step, then per propagation step the edge terms (kb_edge_terms on `egrid`, `chunks` workgroups per
+// sample) and in one launch the projection of this step with the update of the one before, the particle encoder.
+// `wg` (nullable): weight-gradient jobs to queue in between.
+void launch_node_stages(drp_ctx* c, const BwdStep& s, dim3 egrid, int chunks, const NodeWgrad* wg) {
+    hipStream_t st = c->stream;
+    const int B = s.B, N = s.N;
+    const size_t bn = (size_t)B * N, bn64 = bn * 64;
+    const KmbDump& d = s.d;
+    const float* mw = ptr<float>(c->w_mfma);
+    const float* mb = ptr<float>(c->w_mfma_bwd);
+    const dim3 ngrid(mfma_grid_spread(c, (long)B * ((N + 31) / 32))), nblk(64 * MFMA_WAVES);
+    { ProbeScope ps(c, KC_BWD_NODE);
+    hipLaunchKernelGGL(kmb_predict, ngrid, nblk, KMB_PREDICT_LDS, st, mw, mb, s.eht + 3 * bn64, s.g_out, (size_t)N * 3, N, B,
+                       s.ge_tmp, d.hact, d.gh);
+    }
+    if (wg) wg->predictor(s);
+    { ProbeScope ps(c, KC_BWD_NODE);
+    hipLaunchKernelGGL((kmb_node_step<false, true>), ngrid, nblk, KMB_STEP_LDS(false, true), st, mb, s.ge_tmp, d.ge[0],
+                       (const float*)nullptr, s.eht + (size_t)DRP_PSTEP * bn64, s.g_cnode, 1, s.gah + (size_t)(DRP_PSTEP - 1) * bn64, N, B);
+    }
+    for (int p = DRP_PSTEP - 1; p >= 0; --p) {
+        if (wg) wg->update(s, p);
+        { ProbeScope ps(c, KC_BWD_EDGE);
+        hipLaunchKernelGGL(kb_edge_terms, egrid, dim3(256), 0, st, s.gah + (size_t)p * bn64, s.mht + (size_t)p * bn * DRP_K * 2,
+                           s.cnt, s.rev_off, s.rev, N, d.gp[p], chunks);
+        }
+        if (wg) {
+            wg->edge_terms(s, p);
+            flush_wgrad(c);                              // (not deferred:) before the next kernel overwrites g_eff (and, next step, g_proj)
+        }
+        ProbeScope ps(c, KC_BWD_NODE);
+        if (p > 0)
+            hipLaunchKernelGGL((kmb_node_step<true, true>), ngrid, nblk, KMB_STEP_LDS(true, true), st, mb, d.ge[DRP_PSTEP - 1 - p],
+                               d.ge[DRP_PSTEP - p], d.gp[p], s.eht + (size_t)p * bn64, s.g_cnode, 0, s.gah + (size_t)(p - 1) * bn64, N, B);
+        else
+            hipLaunchKernelGGL((kmb_node_step<true, false>), ngrid, nblk, KMB_STEP_LDS(true, false), st, mb, d.ge[DRP_PSTEP - 1],
+                               s.ge_tmp, d.gp[0], (const float*)nullptr, (float*)nullptr, 0, (float*)nullptr, N, B);
+    }
+    if (wg) wg->cnode(s);
+    { ProbeScope ps(c, KC_BWD_NODE);
+    hipLaunchKernelGGL(kmb_node_encode, ngrid, nblk, KMB_NODE_ENCODE_LDS, st, mw, mb, s.sdelta, ptr<float>(c->attr), s.mod,
+                       ptr<float>(c->dens), s.mod, s.eht, s.ge_tmp, s.g_cnode, N, B, ptr<float>(c->g_sdelta), d.gpe, d.a1n, d.gh1, d.xn);
+    }
+    if (wg) {
+        wg->encoder(s);
+        flush_wgrad(c);
+    }
 }
 
 // The one-shot entry points stage their inputs in the buffers the planner sessions keep their state in

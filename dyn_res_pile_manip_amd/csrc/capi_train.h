@@ -30,56 +30,25 @@ int train_forward_backward(drp_ctx* c, int B, int N, bool backward) {
     const size_t hstride = (size_t)H * N * 3;                 // predicted states [B][H][N][3]
     const size_t in_stride = (size_t)(H + 1) * N * 3;         // given states     [B][H+1][N][3]
     hipStream_t st = c->stream;
-    const bool rev_lds = N <= KB_REV_LDS_MAX_N && !c->rev_global_only;
     float* states = ptr<float>(c->states);
     const float* given = tr_given(c);
     const int* nums = tr_nums(c, B, N);
-    float* eh = ptr<float>(c->eff_hist);
-    unsigned* mh = ptr<unsigned>(c->tape_mask);
-    float* ah = ptr<float>(c->agg_hist);
     float* g_state = ptr<float>(c->g_state);
     double* loss = c->tr_loss_host ? c->tr_loss_host : ptr<double>(c->tr_loss);      // pinned host memory: the terms land where the caller reads them
     const float scale = 1.0f / (float)(H * B);
-    const int saved_engine = c->engine;
-    c->engine = c->tr_engine;
-    const float* cself = nullptr;
-    const uint8_t* cself_ok = nullptr;
-    int rc = prepare_cself(c, B, N, B, &cself, &cself_ok);
-    for (int t = 0; t < H && rc == DRP_OK; ++t) {
-        // with a backward pass to follow, the step's impulses and neighbour lists are part of the tape: its workspace
-        // pointers are lent the tape's slices for the call (as the GD planner does) instead of three copies afterwards
-        void* const save_sd = c->s_delta.p; void* const save_idx = c->nbr_idx.p; void* const save_cnt = c->nbr_cnt.p;
-        struct Lend {
-            drp_ctx* c; void* sd; void* idx; void* cnt;
-            ~Lend() { c->s_delta.p = sd; c->nbr_idx.p = idx; c->nbr_cnt.p = cnt; }
-        } lend{c, save_sd, save_idx, save_cnt};
-        // this step's impulses are data (train/train_gnn_dyn.py:181): the step-major copy kt_unpack_inputs left (the tape's)
-        c->s_delta.p = ptr<float>(c->tape_sdelta) + (size_t)t * bn * 3;
-        if (backward) {
-            c->nbr_idx.p = ptr<int16_t>(c->tape_idx) + (size_t)t * bnk;
-            c->nbr_cnt.p = ptr<uint8_t>(c->tape_cnt) + (size_t)t * bn;
-        }
-        StepArgs a{};
-        if (t == 0) { a.s_prev = given; a.prev_mod = B; a.prev_stride = in_stride; }
-        else { a.s_prev = states + (size_t)(t - 1) * N * 3; a.prev_mod = B; a.prev_stride = hstride; }
-        a.attr = ptr<float>(c->attr); a.attr_mod = B;
-        a.dens = ptr<float>(c->dens); a.dens_mod = B;
-        a.actions = nullptr; a.act_stride = 0;
-        a.build_graph = true;
-        a.s_out = states + (size_t)t * N * 3; a.out_stride = hstride;
-        a.B = B; a.N = N;
-        a.cself = cself; a.cself_ok = cself_ok;
-        a.padded = true;                // collate_fn pads with zero rows: coincident particles
-        if (backward) {
-            a.eff_hist = eh + (size_t)t * 4 * bn64;
-            a.mask_hist = mh + (size_t)t * DRP_PSTEP * bnk * 2;
-            a.agg_hist = ah + (size_t)t * 3 * bn64;
-        }
-        rc = run_step(c, a);
-        if (rc != DRP_OK) break;
+    {
+        const float* cself = nullptr;
+        const uint8_t* cself_ok = nullptr;
+        CHK(prepare_cself(c, B, N, B, &cself, &cself_ok, c->tr_engine));
+        TapeFwd f{};
+        f.s0 = given; f.s0_mod = B; f.s0_stride = in_stride;
+        f.mod = B;
+        f.actions = nullptr;            // this step's impulses are data (train/train_gnn_dyn.py:181): the step-major copy kt_unpack_inputs left
+        f.padded = true;                // collate_fn pads with zero rows: coincident particles
+        f.tape = backward; f.agg_hist = true;
+        f.cself = cself; f.cself_ok = cself_ok;
+        CHK(run_tape_forward(c, c->tr_engine, B, N, H, f));
     }
-    c->engine = saved_engine;
-    CHK(rc);
     // the loss of every step and d loss / d s_pred_t (train/train_gnn_dyn.py:184-186, :203) in one launch
     hipLaunchKernelGGL(kt_mse_grad, dim3(B, H), dim3(256), 0, st, states, hstride, given + (size_t)N * 3, in_stride,
                        nums, N, scale, g_state, loss, backward ? ptr<float>(c->tr_grad) : (float*)nullptr,
@@ -87,28 +56,17 @@ int train_forward_backward(drp_ctx* c, int B, int N, bool backward) {
     HIPCHK(c, hipGetLastError());
     if (!backward) return DRP_OK;
 
-    const float* vw = ptr<float>(c->w_valu);
-    const float* wraw = ptr<float>(c->w_raw);
     float* G = ptr<float>(c->tr_grad);
-    // a training batch is a handful of samples: split each sample's rows over workgroups
-    // (row kernels: one receiver per wave and pass; edge kernels: one receiver per 16 lanes)
-    auto pick = [&](int rows_per_block) {
-        int ch = (N + rows_per_block - 1) / rows_per_block;
-        if (ch > 4096 / B) ch = 4096 / B;
-        return ch < 1 ? 1 : ch;
-    };
-    const int chunks = pick(4), chunks16 = pick(16);
-    const dim3 rgrid((unsigned)(B * chunks)), egrid((unsigned)(B * chunks16));
+    // a training batch is a handful of samples: the edge terms' kernel splits each sample's rows over workgroups (one
+    // receiver per 16 lanes)
+    int chunks16 = (N + 15) / 16;
+    if (chunks16 > 4096 / B) chunks16 = 4096 / B;
+    if (chunks16 < 1) chunks16 = 1;
+    const dim3 egrid((unsigned)(B * chunks16));
     const float* dens = ptr<float>(c->dens);
     // the reversed lists of ALL rollout steps in one launch (the tape holds every step's lists; a training batch is a handful
     // of workgroups per step)
-    c->dv(N <= 512 ? DV_REV_256 : DV_REV_1024);
-    if (N <= 512)
-        hipLaunchKernelGGL(kb_reverse_lists<256>, dim3(B * H), dim3(256), KB_REV_LDS(N, rev_lds), st, ptr<int16_t>(c->tape_idx),
-                           ptr<uint8_t>(c->tape_cnt), N, ptr<int>(c->rev_off), ptr<int>(c->rev), rev_lds ? 1 : 0, nums, B);
-    else
-        hipLaunchKernelGGL(kb_reverse_lists<1024>, dim3(B * H), dim3(1024), KB_REV_LDS(N, rev_lds), st, ptr<int16_t>(c->tape_idx),
-                           ptr<uint8_t>(c->tape_cnt), N, ptr<int>(c->rev_off), ptr<int>(c->rev), rev_lds ? 1 : 0, nums, B);
+    launch_reverse_lists(c, ptr<int16_t>(c->tape_idx), ptr<uint8_t>(c->tape_cnt), N, B * H, nums, B);
     // deferred weight gradients: what a job reads keeps a buffer per rollout step t (g_eff and g_proj: per propagation step
     // too; slot 0 of g_eff is the transient copy the predictor writes and the particle encoder reads)
     const bool defer = c->wg_defer_now;
@@ -119,8 +77,7 @@ int train_forward_backward(drp_ctx* c, int B, int N, bool backward) {
     // 4 x <= 300 particles: 40): every tile is a chain of memory round trips, and the stage kernels spread the same gathers
     // over more threads (32 x 300: 2.6 ms per iteration staged, 4.3 in one launch)
     const long f_tiles = (long)B * ((N + 31) / 32);
-    const bool fused = defer && c->bwd_fused && !c->bwd_valu_stages &&
-                       (c->train_fused >= 0 ? c->train_fused != 0 : f_tiles <= c->n_cu / 4);
+    const bool fused = defer && c->bwd_fused && (c->train_fused >= 0 ? c->train_fused != 0 : f_tiles <= c->n_cu / 4);
     const int f_spw = (B + c->n_cu - 1) / c->n_cu, f_groups = (B + f_spw - 1) / f_spw;
     int f_parts = 1;
     bool f_coop = false;
@@ -137,176 +94,65 @@ int train_forward_backward(drp_ctx* c, int B, int N, bool backward) {
     unsigned* const f_bar = reinterpret_cast<unsigned*>(G + TR_GRAD_PAD);        // [H][f_groups] arrival counters, then the give-up flag
     for (int t = H - 1; t >= 0; --t) {
         const size_t tt = per_t * (size_t)t;
-        float* const ge_tmp = ptr<float>(c->g_eff);
-        auto ge_v = [&](int v) { return ptr<float>(c->g_eff) + per_t * ((size_t)(t * 3 + v) + 1) * bn64; };   // v = 0, 1, 2: steps 2, 1, 0
-        auto gp_v = [&](int p) { return ptr<float>(c->g_proj) + per_t * (size_t)(t * 3 + p) * bn64 * 2; };
-        float* const g_cnode_t = ptr<float>(c->g_cnode) + tt * bn64;
-        float* const tr_hact_t = ptr<float>(c->tr_hact) + tt * bn64;
-        float* const tr_gh_t = ptr<float>(c->tr_gh) + tt * bn64;
-        float* const tr_gpe_t = ptr<float>(c->tr_gpe) + tt * bn64;
-        float* const tr_a1n_t = ptr<float>(c->tr_a1n) + tt * bn64;
-        float* const tr_gh1_t = ptr<float>(c->tr_gh1) + tt * bn64;
-        float* const tr_xn_t = ptr<float>(c->tr_xn) + tt * bn * 8;
         KbEdgeDump ed{ptr<float>(c->ed_re) + tt * bnk * 64, ptr<float>(c->ed_a2) + tt * bnk * 64, ptr<float>(c->ed_a1) + tt * bnk * 64,
                       ptr<float>(c->ed_x0) + tt * bnk * 8, ptr<float>(c->ed_gce) + tt * bnk * 64, ptr<float>(c->ed_g3) + tt * bnk * 64,
                       ptr<float>(c->ed_g2) + tt * bnk * 64, ptr<float>(c->ed_g1) + tt * bnk * 64};
         const float* s_prev = (t == 0) ? given : states + (size_t)(t - 1) * N * 3;
         const size_t prev_stride = (t == 0) ? in_stride : hstride;
-        float* eht = eh + (size_t)t * 4 * bn64;
-        const unsigned* mht = mh + (size_t)t * DRP_PSTEP * bnk * 2;
-        float* aht = ah + (size_t)t * 3 * bn64;
         const int16_t* idx = ptr<int16_t>(c->tape_idx) + (size_t)t * bnk;
-        const uint8_t* cnt = ptr<uint8_t>(c->tape_cnt) + (size_t)t * bn;
         float* g_out = g_state + (size_t)t * bn * 3;
-        float* gah = ptr<float>(c->g_agg_hist);
-        int* const rev_off_t = ptr<int>(c->rev_off) + (size_t)t * B * (N + 1);
-        int* const rev_t = ptr<int>(c->rev) + (size_t)t * bnk;
-        // node-level stages: on the matrix cores when the batch has enough 32-row tiles to fill the chip,
-        // otherwise the row kernels chunked over (sample, rows)
+        BwdStep s{};
+        s.B = B; s.N = N; s.mod = B;
+        s.eht = ptr<float>(c->eff_hist) + (size_t)t * 4 * bn64;
+        s.mht = ptr<unsigned>(c->tape_mask) + (size_t)t * DRP_PSTEP * bnk * 2;
+        s.cnt = ptr<uint8_t>(c->tape_cnt) + (size_t)t * bn;
+        s.rev_off = ptr<int>(c->rev_off) + (size_t)t * B * (N + 1);
+        s.rev = ptr<int>(c->rev) + (size_t)t * bnk;
+        s.sdelta = ptr<float>(c->tape_sdelta) + (size_t)t * bn * 3;
+        s.g_out = g_out;
+        s.gah = ptr<float>(c->g_agg_hist);
+        s.ge_tmp = ptr<float>(c->g_eff);
+        s.g_cnode = ptr<float>(c->g_cnode) + tt * bn64;
+        s.d.hact = ptr<float>(c->tr_hact) + tt * bn64; s.d.gh = ptr<float>(c->tr_gh) + tt * bn64;
+        for (int v = 0; v < 3; ++v) {           // v = 0, 1, 2: propagation steps 2, 1, 0 of ge; p = v of gp
+            s.d.ge[v] = ptr<float>(c->g_eff) + per_t * ((size_t)(t * 3 + v) + 1) * bn64;
+            s.d.gp[v] = ptr<float>(c->g_proj) + per_t * (size_t)(t * 3 + v) * bn64 * 2;
+        }
+        s.d.gpe = ptr<float>(c->tr_gpe) + tt * bn64; s.d.a1n = ptr<float>(c->tr_a1n) + tt * bn64;
+        s.d.gh1 = ptr<float>(c->tr_gh1) + tt * bn64; s.d.xn = ptr<float>(c->tr_xn) + tt * bn * 8;
+        const NodeWgrad wg{c, G, ptr<float>(c->agg_hist) + (size_t)t * 3 * bn64, dens};
         if (fused) {
             // everything between the loss gradient and the relation encoder's backward in ONE launch (kmb_step_bwd<DUMP>): the
-            // operands of the weight gradients are its dumps; same queue order as the stage kernels below
+            // operands of the weight gradients are its dumps; the jobs in the stage kernels' queue order
             c->dv(f_coop ? DV_TRAIN_NODE_FUSED_COOP : DV_TRAIN_NODE_FUSED);
-            KmbDump dump{};
-            dump.hact = tr_hact_t; dump.gh = tr_gh_t;
-            for (int v = 0; v < 3; ++v) { dump.ge[v] = ge_v(v); dump.gp[v] = gp_v(v); }
-            dump.gpe = tr_gpe_t; dump.a1n = tr_a1n_t; dump.gh1 = tr_gh1_t; dump.xn = tr_xn_t;
-#define STEP_BWD_ARGS ptr<float>(c->w_mfma), ptr<float>(c->w_mfma_bwd), eht, mht, cnt, rev_off_t, rev_t, g_out, (size_t)N * 3, \
-                      ptr<float>(c->tape_sdelta) + (size_t)t * bn * 3, ptr<float>(c->attr), B, dens, B, N, B, f_spw, ge_tmp, \
-                      g_cnode_t, gah, ptr<float>(c->g_sdelta), dump, f_parts, f_bar + (size_t)t * f_groups, f_bar + (size_t)H * f_groups
+#define STEP_BWD_ARGS ptr<float>(c->w_mfma), ptr<float>(c->w_mfma_bwd), s.eht, s.mht, s.cnt, s.rev_off, s.rev, g_out, (size_t)N * 3, \
+                      s.sdelta, ptr<float>(c->attr), B, dens, B, N, B, f_spw, s.ge_tmp, s.g_cnode, s.gah, ptr<float>(c->g_sdelta), s.d, \
+                      f_parts, f_bar + (size_t)t * f_groups, f_bar + (size_t)H * f_groups
             if (f_coop)
                 hipLaunchKernelGGL((kmb_step_bwd<true, true>), dim3((unsigned)(f_groups * f_parts)), dim3(64 * KMB_FUSED_WAVES), KMB_COOP_LDS, st, STEP_BWD_ARGS);
             else
                 hipLaunchKernelGGL((kmb_step_bwd<true, false>), dim3((unsigned)(f_groups * f_parts)), dim3(64 * KMB_FUSED_WAVES), KMB_FUSED_LDS, st, STEP_BWD_ARGS);
 #undef STEP_BWD_ARGS
-            launch_wgrad<64>(c, tr_gh_t, 64, eht + 3 * bn64, 64, (long)bn, G + W_PR0_W, 64, 1, G + W_PR0_B, nullptr, nullptr, 1, 1);
-            launch_wgrad<3>(c, tr_hact_t, 64, g_out, 3, (long)bn, G + W_PR1_W, 1, 64, nullptr, nullptr, nullptr, 1, 1);
+            wg.predictor(s);
             for (int p = DRP_PSTEP - 1; p >= 0; --p) {
-                launch_wgrad<64>(c, ge_v(DRP_PSTEP - 1 - p), 64, aht + (size_t)p * bn64, 64, (long)bn, G + W_PP_W + 64, 129, 1,
-                                 nullptr, nullptr, nullptr, 1, 1);
-                launch_wgrad<64>(c, gp_v(p), 128, eht + (size_t)p * bn64, 64, (long)bn, G + W_RP_W + 64, 193, 1,
-                                 nullptr, nullptr, nullptr, 1, 1);
-                launch_wgrad<64>(c, gp_v(p) + 64, 128, eht + (size_t)p * bn64, 64, (long)bn, G + W_RP_W + 128, 193,
-                                 1, nullptr, nullptr, nullptr, 1, 1);
+                wg.update(s, p);
+                wg.edge_terms(s, p);
             }
-            launch_wgrad<64>(c, g_cnode_t, 64, eht, 64, (long)bn, G + W_PP_W, 129, 1, G + W_PP_B, G + W_PP_W + 128,
-                             dens, B, (long)N);
-            launch_wgrad<64>(c, tr_gpe_t, 64, tr_a1n_t, 64, (long)bn, G + W_PE2_W, 64, 1, G + W_PE2_B,
-                             nullptr, nullptr, 1, 1);
-            launch_wgrad<5>(c, tr_gh1_t, 64, tr_xn_t, 8, (long)bn, G + W_PE0_W, 5, 1, G + W_PE0_B,
-                            nullptr, nullptr, 1, 1);
-        } else if ((long)B * ((N + 31) / 32) >= KMB_MIN_TILES && !c->bwd_valu_stages) {
-            const float* mw = ptr<float>(c->w_mfma);
-            const float* mb = ptr<float>(c->w_mfma_bwd);
-            const long node_tiles = (long)B * ((N + 31) / 32);
-            const dim3 ngrid(mfma_grid_spread(c, node_tiles)), nblk(64 * MFMA_WAVES);
-            c->dv(DV_TRAIN_NODE_MFMA);
-            // predictor
-            hipLaunchKernelGGL(kmb_predict, ngrid, nblk, KMB_PREDICT_LDS, st, mw, mb, eht + 3 * bn64, g_out, (size_t)N * 3, N, B,
-                               ge_tmp, tr_hact_t, tr_gh_t);
-            launch_wgrad<64>(c, tr_gh_t, 64, eht + 3 * bn64, 64, (long)bn, G + W_PR0_W, 64, 1, G + W_PR0_B, nullptr,
-                             nullptr, 1, 1);
-            launch_wgrad<3>(c, tr_hact_t, 64, g_out, 3, (long)bn, G + W_PR1_W, 1, 64, nullptr, nullptr, nullptr, 1, 1);
-            // update of the last propagation step; then per step the edge terms and, in one launch, the
-            // projection of this step with the update of the one before (k_backward_mfma.h)
-            hipLaunchKernelGGL((kmb_node_step<false, true>), ngrid, nblk, KMB_STEP_LDS(false, true), st, mb, ge_tmp, ge_v(0),
-                               (const float*)nullptr, eht + (size_t)DRP_PSTEP * bn64, g_cnode_t, 1,
-                               gah + (size_t)(DRP_PSTEP - 1) * bn64, N, B);
-            for (int p = DRP_PSTEP - 1; p >= 0; --p) {
-                float* g_agg_p = gah + (size_t)p * bn64;
-                const unsigned* mask_p = mht + (size_t)p * bnk * 2;
-                float* const ge_p = ge_v(DRP_PSTEP - 1 - p);     // the pre-activation gradient of step p
-                float* const gp_p = gp_v(p);
-                // particle propagator, aggregate columns
-                launch_wgrad<64>(c, ge_p, 64, aht + (size_t)p * bn64, 64, (long)bn, G + W_PP_W + 64, 129, 1,
-                                 nullptr, nullptr, nullptr, 1, 1);
-                hipLaunchKernelGGL(kb_edge_terms, egrid, dim3(256), 0, st, g_agg_p, mask_p, cnt, rev_off_t,
-                                   rev_t, N, gp_p, chunks16);
-                // relation propagator, receiver and sender columns
-                launch_wgrad<64>(c, gp_p, 128, eht + (size_t)p * bn64, 64, (long)bn, G + W_RP_W + 64, 193, 1,
-                                 nullptr, nullptr, nullptr, 1, 1);
-                launch_wgrad<64>(c, gp_p + 64, 128, eht + (size_t)p * bn64, 64, (long)bn, G + W_RP_W + 128, 193,
-                                 1, nullptr, nullptr, nullptr, 1, 1);
-                flush_wgrad(c);                          // (not deferred:) before the next kernel overwrites g_eff (and, next step, g_proj)
-                if (p > 0)
-                    hipLaunchKernelGGL((kmb_node_step<true, true>), ngrid, nblk, KMB_STEP_LDS(true, true), st, mb,
-                                       ge_p, ge_v(DRP_PSTEP - p), gp_p, eht + (size_t)p * bn64,
-                                       g_cnode_t, 0, gah + (size_t)(p - 1) * bn64, N, B);
-                else
-                    hipLaunchKernelGGL((kmb_node_step<true, false>), ngrid, nblk, KMB_STEP_LDS(true, false), st, mb,
-                                       ge_p, ge_tmp, gp_p, (const float*)nullptr, (float*)nullptr, 0,
-                                       (float*)nullptr, N, B);
-            }
-            // particle propagator, encoder columns + density column + bias; particle encoder
-            launch_wgrad<64>(c, g_cnode_t, 64, eht, 64, (long)bn, G + W_PP_W, 129, 1, G + W_PP_B, G + W_PP_W + 128,
-                             dens, B, (long)N);
-            hipLaunchKernelGGL(kmb_node_encode, ngrid, nblk, KMB_NODE_ENCODE_LDS, st, mw, mb,
-                               ptr<float>(c->tape_sdelta) + (size_t)t * bn * 3, ptr<float>(c->attr), B, dens, B, eht,
-                               ge_tmp, g_cnode_t, N, B, ptr<float>(c->g_sdelta), tr_gpe_t,
-                               tr_a1n_t, tr_gh1_t, tr_xn_t);
-            launch_wgrad<64>(c, tr_gpe_t, 64, tr_a1n_t, 64, (long)bn, G + W_PE2_W, 64, 1, G + W_PE2_B,
-                             nullptr, nullptr, 1, 1);
-            launch_wgrad<5>(c, tr_gh1_t, 64, tr_xn_t, 8, (long)bn, G + W_PE0_W, 5, 1, G + W_PE0_B,
-                            nullptr, nullptr, 1, 1);
-            flush_wgrad(c);
+            wg.cnode(s);
+            wg.encoder(s);
         } else {
-            c->dv(DV_TRAIN_NODE_VALU);
-            // predictor
-            hipLaunchKernelGGL(kb_predict, rgrid, dim3(256), 0, st, vw, wraw, eht + 3 * bn64, g_out, (size_t)N * 3, N,
-                               ptr<float>(c->g_eff), ptr<float>(c->tr_hact), ptr<float>(c->tr_gh), chunks);
-            launch_wgrad<64>(c, ptr<float>(c->tr_gh), 64, eht + 3 * bn64, 64, (long)bn, G + W_PR0_W, 64, 1, G + W_PR0_B, nullptr,
-                             nullptr, 1, 1);
-            launch_wgrad<3>(c, ptr<float>(c->tr_hact), 64, g_out, 3, (long)bn, G + W_PR1_W, 1, 64, nullptr, nullptr, nullptr, 1, 1);
-            for (int p = DRP_PSTEP - 1; p >= 0; --p) {
-                float* g_agg_p = gah + (size_t)p * bn64;
-                const unsigned* mask_p = mht + (size_t)p * bnk * 2;
-                hipLaunchKernelGGL(kb_update, rgrid, dim3(256), 0, st, wraw, eht + (size_t)(p + 1) * bn64,
-                                   ptr<float>(c->g_eff), ptr<float>(c->g_cnode), p == DRP_PSTEP - 1 ? 1 : 0, N, g_agg_p, chunks);
-                // particle propagator, aggregate columns: g_eff now holds the pre-activation gradient
-                launch_wgrad<64>(c, ptr<float>(c->g_eff), 64, aht + (size_t)p * bn64, 64, (long)bn, G + W_PP_W + 64, 129, 1,
-                                 nullptr, nullptr, nullptr, 1, 1);
-                hipLaunchKernelGGL(kb_edge_terms, egrid, dim3(256), 0, st, g_agg_p, mask_p, cnt, rev_off_t,
-                                   rev_t, N, ptr<float>(c->g_proj), chunks16);
-                // relation propagator, receiver and sender columns
-                launch_wgrad<64>(c, ptr<float>(c->g_proj), 128, eht + (size_t)p * bn64, 64, (long)bn, G + W_RP_W + 64, 193, 1,
-                                 nullptr, nullptr, nullptr, 1, 1);
-                launch_wgrad<64>(c, ptr<float>(c->g_proj) + 64, 128, eht + (size_t)p * bn64, 64, (long)bn, G + W_RP_W + 128, 193,
-                                 1, nullptr, nullptr, nullptr, 1, 1);
-                flush_wgrad(c);                          // before kb_project overwrites g_eff
-                hipLaunchKernelGGL(kb_project, rgrid, dim3(256), 0, st, wraw, ptr<float>(c->g_proj), N, ptr<float>(c->g_eff), chunks);
-            }
-            // particle propagator, encoder columns + density column + bias; particle encoder
-            launch_wgrad<64>(c, ptr<float>(c->g_cnode), 64, eht, 64, (long)bn, G + W_PP_W, 129, 1, G + W_PP_B, G + W_PP_W + 128,
-                             dens, B, (long)N);
-            hipLaunchKernelGGL(kb_node_encode, rgrid, dim3(256), 0, st, vw, wraw,
-                               ptr<float>(c->tape_sdelta) + (size_t)t * bn * 3, ptr<float>(c->attr), B, dens, B, eht,
-                               ptr<float>(c->g_eff), ptr<float>(c->g_cnode), N, ptr<float>(c->g_sdelta), ptr<float>(c->tr_gpe),
-                               ptr<float>(c->tr_a1n), ptr<float>(c->tr_gh1), ptr<float>(c->tr_xn), chunks);
-            launch_wgrad<64>(c, ptr<float>(c->tr_gpe), 64, ptr<float>(c->tr_a1n), 64, (long)bn, G + W_PE2_W, 64, 1, G + W_PE2_B,
-                             nullptr, nullptr, 1, 1);
-            launch_wgrad<5>(c, ptr<float>(c->tr_gh1), 64, ptr<float>(c->tr_xn), 8, (long)bn, G + W_PE0_W, 5, 1, G + W_PE0_B,
-                            nullptr, nullptr, 1, 1);
-            flush_wgrad(c);
+            c->dv(DV_TRAIN_NODE_MFMA);
+            launch_node_stages(c, s, egrid, chunks16, &wg);
         }
         // the previous step's output feeds this step as s_cur: residual + relation encoder
-        float* g_prev = nullptr;
-        if (t > 0) {
-            g_prev = g_state + (size_t)(t - 1) * bn * 3;
-            // the residual's share: with the matrix-core edge kernel nothing touches g_prev before kb_gather_pos, which adds it first
-            if (!c->bwd_edge_mfma)
-                hipLaunchKernelGGL(kt_add, dim3((unsigned)((bn * 3 + 255) / 256)), dim3(256), 0, st, g_prev, g_out, bn * 3);
-        }
-        c->dv(c->bwd_edge_mfma ? DV_BWD_EDGE_MFMA : DV_BWD_EDGE_VALU);
-        if (c->bwd_edge_mfma)
-            launch_edge_encode_mfma(c, s_prev, B, prev_stride, B, idx, cnt, gah, mht, bn, N, B,
-                                    g_prev != nullptr ? ptr<float>(c->gpos_edge) : (float*)nullptr, ed);
-        else
-            hipLaunchKernelGGL(kb_edge_encode, rgrid, dim3(256), KB_EDGE_ENCODE_LDS, st, vw, wraw, s_prev, B,
-                               prev_stride, ptr<float>(c->attr), B, dens, B, idx, cnt, gah, mht, bn, N, g_prev, (size_t)N * 3, ptr<float>(c->gpos_edge), ed, chunks);
+        float* g_prev = t > 0 ? g_state + (size_t)(t - 1) * bn * 3 : nullptr;
+        c->dv(DV_BWD_EDGE_MFMA);
+        launch_edge_encode_mfma(c, s_prev, B, prev_stride, B, idx, s.cnt, s.gah, s.mht, bn, N, B,
+                                g_prev != nullptr ? ptr<float>(c->gpos_edge) : (float*)nullptr, ed);
+        // the residual's share: nothing touches g_prev before kb_gather_pos, which adds it first
         if (g_prev != nullptr)
             hipLaunchKernelGGL(kb_gather_pos, dim3((N + 255) / 256, B), dim3(256), 0, st, ptr<float>(c->gpos_edge),
-                               rev_off_t, rev_t, N, g_prev, (size_t)N * 3, c->bwd_edge_mfma ? 1 : 0, cnt,
-                               c->bwd_edge_mfma ? (const float*)g_out : (const float*)nullptr);
+                               s.rev_off, s.rev, N, g_prev, (size_t)N * 3, s.cnt, (const float*)g_out);
         launch_wgrad<64>(c, ed.gce, 64, ed.re, 64, (long)bnk, G + W_RP_W, 193, 1, G + W_RP_B, G + W_RP_W + 192, dens, B,
                          (long)N * DRP_K);
         launch_wgrad<64>(c, ed.g3, 64, ed.a2, 64, (long)bnk, G + W_RE4_W, 64, 1, G + W_RE4_B, nullptr, nullptr, 1, 1);
@@ -484,25 +330,15 @@ int drp_train_step(drp_ctx* c, const float* states, const float* states_delta, c
         // deferred weight gradients keep every job's operands until the end of the backward pass: H copies of the node-level
         // dumps (3 H + 1 of g_eff, 3 H of g_proj) and of the relation encoder's dumps -- 0.24 GB per rollout step at 32 x 300
         const size_t keep_bytes = (size_t)H * (16 * bn64 + 7 * bnk * 64 + bnk * 8 + bn * 8) * sizeof(float);
-        const bool defer = c->wgrad_defer && (long)B * ((N + 31) / 32) >= KMB_MIN_TILES && !c->bwd_valu_stages && keep_bytes <= ((size_t)8 << 30);
+        const bool defer = c->wgrad_defer && keep_bytes <= ((size_t)8 << 30);
         c->wg_defer_now = defer;
         defer_batch = defer;
         const size_t kt = defer ? (size_t)H : 1;
-        CHK(ensure(c, c->eff_hist, (size_t)H * 4 * bn64 * sizeof(float)));
+        CHK(ensure_tape(c, B, N, H, H));
         CHK(ensure(c, c->agg_hist, (size_t)H * 3 * bn64 * sizeof(float)));
-        CHK(ensure(c, c->tape_sdelta, (size_t)H * bn * 3 * sizeof(float)));
-        CHK(ensure(c, c->tape_idx, (size_t)H * bnk * sizeof(int16_t)));
-        CHK(ensure(c, c->tape_cnt, (size_t)H * bn));
-        CHK(ensure(c, c->tape_mask, (size_t)H * DRP_PSTEP * bnk * 2 * sizeof(unsigned)));
-        CHK(ensure(c, c->g_agg_hist, (size_t)DRP_PSTEP * bn64 * sizeof(float)));
-        CHK(ensure(c, c->rev_off, (size_t)H * B * (N + 1) * sizeof(int)));
-        CHK(ensure(c, c->rev, (size_t)H * bnk * sizeof(int)));
-        CHK(ensure(c, c->gpos_edge, bnk * 4 * sizeof(float)));
         CHK(ensure(c, c->g_eff, (defer ? 3 * kt + 1 : 1) * bn64 * sizeof(float)));
         CHK(ensure(c, c->g_cnode, kt * bn64 * sizeof(float)));
-        CHK(ensure(c, c->g_agg, bn64 * sizeof(float)));
         CHK(ensure(c, c->g_proj, (defer ? 3 * kt : 1) * bn64 * 2 * sizeof(float)));
-        CHK(ensure(c, c->g_sdelta, bn * 3 * sizeof(float)));
         DevBuf* node64[] = {&c->tr_hact, &c->tr_gh, &c->tr_gpe, &c->tr_a1n, &c->tr_gh1};
         for (DevBuf* b : node64) CHK(ensure(c, *b, kt * bn64 * sizeof(float)));
         CHK(ensure(c, c->tr_xn, kt * bn * 8 * sizeof(float)));

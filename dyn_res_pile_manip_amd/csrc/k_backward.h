@@ -8,9 +8,10 @@
 // Any horizon: the reward is taken at the final step only (planners.py:436-438); going back
 // through a step, the gradient w.r.t. its input positions is the residual's share, plus the
 // relation encoder's (its inputs are position differences), plus gen_s_delta's dependence
-// on the particle position.  fp32 VALU kernels (the node-level stages also exist on the matrix cores,
-// k_backward_mfma.h) over what the fused forward pass (km_prop<., TAPE>) left in HBM: the effect after
-// the encoder and after every propagation step, and the edges' ReLU masks.  The one scatter of the backward pass
+// on the particle position.  Here the fp32 VALU kernels of the pass (the node-level stages and the relation
+// encoder's backward run on the matrix cores, k_backward_mfma.h) over what the fused forward pass
+// (km_prop<., TAPE>) left in HBM: the effect after the encoder and after every propagation step, and the
+// edges' ReLU masks.  The one scatter of the backward pass
 // (gradient of the gathered sender rows) is turned into a gather over reversed neighbour lists
 // (kb_reverse_lists, kb_edge_terms, kb_gather_pos): no atomics, reproducible sums.
 #pragma once
@@ -19,22 +20,9 @@
 #include "k_graph.h"
 #include "k_mlp_valu.h"
 
-// acc[r] += sum_k x[r][k] * W[k*ld + col0 + lane]   (W in torch [out][in] layout read as [k][lane]:
-// the transposed product g_in = W^T g_out)
-template <int IN, int R>
-__device__ __forceinline__ void dense_bcast_ld(const float* __restrict__ W, int ld, int col0, const float (&x)[R],
-                                               float (&acc)[R], int lane) {
-#pragma unroll 8
-    for (int k = 0; k < IN; ++k) {
-        const float w = W[k * ld + col0 + lane];
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[r] = fmaf(bcast_lane(x[r], k), w, acc[r]);
-    }
-}
-
 #define KB_R 4
 
-// The row kernels below run one workgroup per (sample, chunk of rows): `chunks` = 1 when the batch
+// kb_edge_terms runs one workgroup per (sample, chunk of rows): `chunks` = 1 when the batch
 // alone fills the chip (the planner's thousands of samples), more for the trainer's handful.
 struct KbRange { int b, lo, hi; };
 __device__ __forceinline__ KbRange kb_range(int N, int chunks) {
@@ -149,78 +137,6 @@ kb_reward(const float* __restrict__ state, size_t row_stride, int N, const float
     }
 }
 
-// ---- predictor backward: g_eff = W0^T ((W1^T g_out) . [W0 eff + b0 > 0]) ------------------------
-__global__ void __launch_bounds__(256)
-kb_predict(const float* __restrict__ vw, const float* __restrict__ wraw, const float* __restrict__ eff,
-           const float* __restrict__ g_out, size_t g_stride, int N, float* __restrict__ g_eff,
-           float* __restrict__ dump_hact /* nullable [B*N,64]: relu(W0 eff + b0) */,
-           float* __restrict__ dump_gh /* nullable [B*N,64]: gradient at the hidden pre-activation */, int chunks) {
-    __shared__ float w0t[4096], w0[4096];
-    lds_copy(w0t, vw + V_PR0_T, 4096);
-    lds_copy(w0, wraw + W_PR0_W, 4096);
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
-    const KbRange rg = kb_range(N, chunks);
-    const int b = rg.b;
-    const float b0 = vw[V_PR0_B + lane];
-    const float w1x = vw[V_PR1_W + lane], w1y = vw[V_PR1_W + 64 + lane], w1z = vw[V_PR1_W + 128 + lane];
-    const float* go = g_out + (size_t)b * g_stride;
-    for (int base = rg.lo + wave * KB_R; base < rg.hi; base += nwave * KB_R) {
-        float x[KB_R], h[KB_R], gh[KB_R], ge[KB_R];
-#pragma unroll
-        for (int r = 0; r < KB_R; ++r) {
-            x[r] = eff[((size_t)b * N + min(base + r, N - 1)) * 64 + lane];
-            h[r] = b0;
-        }
-        dense_bcast<64, KB_R>(w0t, x, h, lane);
-#pragma unroll
-        for (int r = 0; r < KB_R; ++r) {
-            const int i = min(base + r, N - 1);
-            const float g = w1x * go[i * 3 + 0] + w1y * go[i * 3 + 1] + w1z * go[i * 3 + 2];
-            gh[r] = (h[r] > 0.0f) ? g : 0.0f;
-            ge[r] = 0.0f;
-        }
-        dense_bcast_ld<64, KB_R>(w0, 64, 0, gh, ge, lane);
-#pragma unroll
-        for (int r = 0; r < KB_R; ++r)
-            if (base + r < N) {
-                const size_t row = (size_t)b * N + base + r;
-                g_eff[row * 64 + lane] = ge[r];
-                if (dump_hact != nullptr) { dump_hact[row * 64 + lane] = fmaxf(h[r], 0.0f); dump_gh[row * 64 + lane] = gh[r]; }
-            }
-    }
-}
-
-// ---- node update backward: g_z = g_eff . [eff_next > 0]; g_cnode += g_z; g_agg = W_agg^T g_z;
-//      g_eff <- g_z (the residual's share of the gradient w.r.t. the previous effect)
-__global__ void __launch_bounds__(256)
-kb_update(const float* __restrict__ wraw, const float* __restrict__ eff_next, float* __restrict__ g_eff,
-          float* __restrict__ g_cnode, int first, int N, float* __restrict__ g_agg, int chunks) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
-    const KbRange rg = kb_range(N, chunks);
-    const int b = rg.b;
-    const float* wpp = wraw + W_PP_W;
-    for (int base = rg.lo + wave * KB_R; base < rg.hi; base += nwave * KB_R) {
-        float gz[KB_R], ga[KB_R];
-#pragma unroll
-        for (int r = 0; r < KB_R; ++r) {
-            const size_t row = (size_t)b * N + min(base + r, N - 1);
-            const float g = g_eff[row * 64 + lane];
-            gz[r] = (eff_next[row * 64 + lane] > 0.0f) ? g : 0.0f;
-            ga[r] = 0.0f;
-        }
-        dense_bcast_ld<64, KB_R>(wpp, 129, 64, gz, ga, lane);
-#pragma unroll
-        for (int r = 0; r < KB_R; ++r) {
-            if (base + r >= N) continue;
-            const size_t row = (size_t)b * N + base + r;
-            g_eff[row * 64 + lane] = gz[r];
-            g_cnode[row * 64 + lane] = first ? gz[r] : g_cnode[row * 64 + lane] + gz[r];
-            g_agg[row * 64 + lane] = ga[r];
-        }
-    }
-}
-
 // ---- reversed neighbour lists: for every sender j the edge slots (i*10 + k) it feeds, ascending --
 // The backward pass of the sender gather is a scatter; with the lists reversed it becomes a
 // gather again -- no atomics, a fixed summation order (the first version scattered with fp32 global
@@ -251,7 +167,7 @@ kb_reverse_lists(const int16_t* __restrict__ nbr_idx, const uint8_t* __restrict_
 //      forward pass (km_prop<., TAPE>) leaves the 64 mask bits of every edge slot and propagation
 //      step (8 B instead of a 256-B row); nothing else of the edge stage is kept.  Here: the
 //      receiver term g_proj[i][0:64] = sum_k g_u and, over the reversed lists, the sender term
-//      g_proj[j][64:128] (kb_edge_terms); kb_edge_encode and the weight gradients rebuild g_u the same way.
+//      g_proj[j][64:128] (kb_edge_terms); kmb_edge_encode and the weight gradients rebuild g_u the same way.
 // Mask layout (k_mlp_split.h frag_positive_bits): two words per slot; feature f lives in word
 // (f>>2)&1 at bit 31 - (16*(f>>5) + (f&3) + 4*((f&31)>>3)).  The four features 4q..4q+3 of a float4
 // lane q are one nibble of word q&1.
@@ -303,94 +219,6 @@ kb_edge_terms(const float* __restrict__ g_agg, const unsigned* __restrict__ mask
             acc.w += (nib & 1u) ? v.w : 0.0f;
         }
         *reinterpret_cast<float4*>(gp + (size_t)i * 128 + 64 + q * 4) = acc;
-    }
-}
-
-// ---- projection backward: g_eff += W_r^T g_proj[:, 0:64] + W_s^T g_proj[:, 64:128] -------------
-__global__ void __launch_bounds__(256)
-kb_project(const float* __restrict__ wraw, const float* __restrict__ g_proj, int N, float* __restrict__ g_eff,
-           int chunks) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
-    const KbRange rg = kb_range(N, chunks);
-    const int b = rg.b;
-    const float* wrp = wraw + W_RP_W;
-    for (int base = rg.lo + wave * KB_R; base < rg.hi; base += nwave * KB_R) {
-        float gr[KB_R], gs[KB_R], ge[KB_R];
-#pragma unroll
-        for (int r = 0; r < KB_R; ++r) {
-            const size_t row = (size_t)b * N + min(base + r, N - 1);
-            gr[r] = g_proj[row * 128 + lane];
-            gs[r] = g_proj[row * 128 + 64 + lane];
-            ge[r] = g_eff[row * 64 + lane];
-        }
-        dense_bcast_ld<64, KB_R>(wrp, 193, 64, gr, ge, lane);
-        dense_bcast_ld<64, KB_R>(wrp, 193, 128, gs, ge, lane);
-#pragma unroll
-        for (int r = 0; r < KB_R; ++r)
-            if (base + r < N) g_eff[((size_t)b * N + base + r) * 64 + lane] = ge[r];
-    }
-}
-
-// ---- particle encoder backward: g_pe = g_eff0 + W_pe^T g_cnode; through relu(W2 relu(W1 x + b1) + b2)
-//      to the three impulse inputs: g_s_delta[b,n,0:3]
-__global__ void __launch_bounds__(256)
-kb_node_encode(const float* __restrict__ vw, const float* __restrict__ wraw, const float* __restrict__ s_delta,
-               const float* __restrict__ attr, int attr_mod, const float* __restrict__ dens, int dens_mod,
-               const float* __restrict__ pe, const float* __restrict__ g_eff0, const float* __restrict__ g_cnode,
-               int N, float* __restrict__ g_sdelta,
-               float* __restrict__ dump_gpe /* nullable [B*N,64]: gradient at the encoder's output pre-activation */,
-               float* __restrict__ dump_a1 /* [B*N,64]: relu(W1 x + b1) */,
-               float* __restrict__ dump_gh1 /* [B*N,64]: gradient at the first layer's pre-activation */,
-               float* __restrict__ dump_x /* [B*N,8]: the 5 encoder inputs */, int chunks) {
-    __shared__ float w0t[5 * 64];
-    lds_copy(w0t, vw + V_PE0_T, 5 * 64);
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
-    const KbRange rg = kb_range(N, chunks);
-    const int b = rg.b;
-    const float d = dens[b % dens_mod] / DRP_DENS_SCALE;
-    const float b0 = vw[V_PE0_B + lane];
-    const float* sd = s_delta + (size_t)b * N * 3;
-    const float* at = attr + (size_t)(b % attr_mod) * N;
-    const float w1x = wraw[W_PE0_W + lane * 5 + 0], w1y = wraw[W_PE0_W + lane * 5 + 1], w1z = wraw[W_PE0_W + lane * 5 + 2];
-    for (int base = rg.lo + wave * KB_R; base < rg.hi; base += nwave * KB_R) {
-        float x[KB_R], h1[KB_R], gc[KB_R], gpe[KB_R], gh[KB_R];
-#pragma unroll
-        for (int r = 0; r < KB_R; ++r) {
-            const int i = min(base + r, N - 1);
-            const size_t row = (size_t)b * N + i;
-            float v = 0.0f;
-            if (lane < 3) v = sd[i * 3 + lane];
-            else if (lane == 3) v = at[i];
-            else if (lane == 4) v = d;
-            x[r] = v;
-            h1[r] = b0;
-            gc[r] = g_cnode[row * 64 + lane];
-            gpe[r] = g_eff0[row * 64 + lane];
-        }
-        dense_bcast<5, KB_R>(w0t, x, h1, lane);                      // h1 pre-activation
-        dense_bcast_ld<64, KB_R>(wraw + W_PP_W, 129, 0, gc, gpe, lane);   // + W_pe^T g_cnode
-#pragma unroll
-        for (int r = 0; r < KB_R; ++r) {
-            const size_t row = (size_t)b * N + min(base + r, N - 1);
-            gpe[r] = (pe[row * 64 + lane] > 0.0f) ? gpe[r] : 0.0f;  // through the encoder's output ReLU
-            gh[r] = 0.0f;
-        }
-        dense_bcast_ld<64, KB_R>(wraw + W_PE2_W, 64, 0, gpe, gh, lane);   // W2^T
-#pragma unroll
-        for (int r = 0; r < KB_R; ++r) {
-            const float g = (h1[r] > 0.0f) ? gh[r] : 0.0f;
-            const float ox = wave_sum(g * w1x), oy = wave_sum(g * w1y), oz = wave_sum(g * w1z);
-            const int i = base + r;
-            if (i < N && lane < 3) g_sdelta[((size_t)b * N + i) * 3 + lane] = (lane == 0) ? ox : (lane == 1) ? oy : oz;
-            if (dump_gpe != nullptr && i < N) {
-                const size_t row = (size_t)b * N + i;
-                dump_gpe[row * 64 + lane] = gpe[r];
-                dump_a1[row * 64 + lane] = fmaxf(h1[r], 0.0f);
-                dump_gh1[row * 64 + lane] = g;
-                if (lane < 8) dump_x[row * 8 + lane] = x[r];
-            }
-        }
     }
 }
 
@@ -553,7 +381,7 @@ kb_sdelta(const float* __restrict__ s_cur, int s_mod, size_t s_stride, const flo
     }
 }
 
-// what the weight-gradient pass of the training path needs from kb_edge_encode, per edge slot
+// what the weight-gradient pass of the training path needs from kmb_edge_encode, per edge slot
 // (row = (b*N + i)*10 + k; every slot is written, padded ones with zero gradients)
 struct KbEdgeDump {
     float* re;    // [rows,64] relation encoding relu(h3)
@@ -566,142 +394,13 @@ struct KbEdgeDump {
     float* g1;
 };
 
-// ---- relation encoder backward (horizons > 1, training): the gradient at c_edge (rebuilt from the
-//      propagation steps' masks and g_agg rows) -> through W_e and the three
-//      Linear+ReLU layers (forward recomputed per slot) to the position-difference inputs
-//      x[2:5] = s_r - s_s (gnn_dyn.py:179-180):  g_pos[recv] += g,  g_pos[send] -= g  (atomics)
-// One wave = the slots of one receiver, as k_edge_encode.
-#define KB_EDGE_ENCODE_LDS ((size_t)(6 * 64 + 5 * 4096) * sizeof(float))
-__global__ void __launch_bounds__(256)
-kb_edge_encode(const float* __restrict__ vw, const float* __restrict__ wraw, const float* __restrict__ s_cur, int s_mod,
-               size_t s_stride, const float* __restrict__ attr, int attr_mod, const float* __restrict__ dens,
-               int dens_mod, const int16_t* __restrict__ nbr_idx, const uint8_t* __restrict__ nbr_cnt,
-               const float* __restrict__ g_agg_hist /* [3][B*N,64]: g_agg of the three propagation steps */,
-               const unsigned* __restrict__ mask_hist /* [3][B*N*10][2] */, size_t bn,
-               int N, float* __restrict__ g_pos /* nullable */, size_t gpos_stride,
-               float* __restrict__ gpos_edge /* [B,N,10,4]: the slot's gradient w.r.t. s_r - s_s, for kb_gather_pos */,
-               KbEdgeDump dump, int chunks) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* w0 = lds;               // [6][64] forward packs
-    float* w2 = w0 + 6 * 64;
-    float* w4 = w2 + 4096;
-    float* bwe = w4 + 4096;        // backward (torch [out][in]) copies: W_e, RE4, RE2 -- read 64 rows per
-    float* bw4 = bwe + 4096;       // layer and slot pass; from L2 their latency was the kernel's time
-    float* bw2 = bw4 + 4096;
-    lds_copy(w0, vw + V_RE0_T, 6 * 64);
-    lds_copy(w2, vw + V_RE2_T, 4096);
-    lds_copy(w4, vw + V_RE4_T, 4096);
-    for (int t = threadIdx.x; t < 4096; t += blockDim.x) bwe[t] = wraw[W_RP_W + (t >> 6) * 193 + (t & 63)];
-    lds_copy(bw4, wraw + W_RE4_W, 4096);
-    lds_copy(bw2, wraw + W_RE2_W, 4096);
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
-    const KbRange rg = kb_range(N, chunks);
-    const int b = rg.b;
-    const float d = dens[b % dens_mod] / DRP_DENS_SCALE;
-    const float b0 = vw[V_RE0_B + lane], b2 = vw[V_RE2_B + lane], b4 = vw[V_RE4_B + lane];
-    const float* s = s_cur + (size_t)(b % s_mod) * s_stride;
-    const float* at = attr + (size_t)(b % attr_mod) * N;
-    float* gp = g_pos ? g_pos + (size_t)b * gpos_stride : nullptr;
-    const bool dumping = dump.re != nullptr;
-    const int mbit = kb_mask_bit(lane), mword = kb_mask_word(lane);
-    const float wx = wraw[W_RE0_W + lane * 6 + 2], wy = wraw[W_RE0_W + lane * 6 + 3], wz = wraw[W_RE0_W + lane * 6 + 4];
-    constexpr int R = 5;           // two passes of five slots keep the register count moderate
-    for (int i = rg.lo + wave; i < rg.hi; i += nwave) {
-        const int cnt = nbr_cnt[(size_t)b * N + i];
-        const int16_t* nb = nbr_idx + ((size_t)b * N + i) * DRP_K;
-        const float ar = at[i];
-        const float sr = (lane >= 2 && lane < 5) ? s[i * 3 + lane - 2] : 0.0f;
-        float recv_sum = 0.0f;       // lanes 0..2: sum over this receiver's slots, in slot order
-        float ga3[DRP_PSTEP];
-#pragma unroll
-        for (int p = 0; p < DRP_PSTEP; ++p) ga3[p] = g_agg_hist[((size_t)p * bn + (size_t)b * N + i) * 64 + lane];
-        for (int k0 = 0; k0 < (dumping ? DRP_K : cnt); k0 += R) {
-            float x[R], h1[R], h2[R], h3[R], g[R], t[R];
-            int js[R];
-            const size_t row0 = ((size_t)b * N + i) * DRP_K + k0;
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                js[r] = (k0 + r < cnt) ? (int)nb[k0 + r] : i;
-                float v = 0.0f;
-                if (lane == 0) v = ar;
-                else if (lane == 1) v = at[js[r]];
-                else if (lane < 5) v = sr - s[js[r] * 3 + lane - 2];
-                else if (lane == 5) v = d;
-                x[r] = v;
-                h1[r] = b0;
-                if (dumping && lane < 8) dump.x0[(row0 + r) * 8 + lane] = v;
-            }
-            dense_bcast<6, R>(w0, x, h1, lane);
-#pragma unroll
-            for (int r = 0; r < R; ++r) { x[r] = fmaxf(h1[r], 0.0f); h2[r] = b2; }
-            if (dumping)
-#pragma unroll
-                for (int r = 0; r < R; ++r) dump.a1[(row0 + r) * 64 + lane] = x[r];
-            dense_bcast<64, R>(w2, x, h2, lane);
-#pragma unroll
-            for (int r = 0; r < R; ++r) { x[r] = fmaxf(h2[r], 0.0f); h3[r] = b4; }
-            if (dumping)
-#pragma unroll
-                for (int r = 0; r < R; ++r) dump.a2[(row0 + r) * 64 + lane] = x[r];
-            dense_bcast<64, R>(w4, x, h3, lane);
-            if (dumping)
-#pragma unroll
-                for (int r = 0; r < R; ++r) dump.re[(row0 + r) * 64 + lane] = fmaxf(h3[r], 0.0f);
-            // backward
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                // d loss / d c_edge of the slot: the three propagation steps share c_edge
-                float gv = 0.0f;
-                if (k0 + r < cnt) {
-                    const size_t e = ((size_t)b * N + i) * DRP_K + k0 + r;
-#pragma unroll
-                    for (int p = 0; p < DRP_PSTEP; ++p)
-                        if ((mask_hist[((size_t)p * bn * DRP_K + e) * 2 + mword] >> mbit) & 1u) gv += ga3[p];
-                }
-                g[r] = gv;
-                t[r] = 0.0f;
-            }
-            if (dumping)
-#pragma unroll
-                for (int r = 0; r < R; ++r) dump.gce[(row0 + r) * 64 + lane] = g[r];
-            dense_bcast_ld<64, R>(bwe, 64, 0, g, t, lane);                        // W_e^T
-#pragma unroll
-            for (int r = 0; r < R; ++r) { g[r] = (h3[r] > 0.0f) ? t[r] : 0.0f; t[r] = 0.0f; }
-            if (dumping)
-#pragma unroll
-                for (int r = 0; r < R; ++r) dump.g3[(row0 + r) * 64 + lane] = g[r];
-            dense_bcast_ld<64, R>(bw4, 64, 0, g, t, lane);
-#pragma unroll
-            for (int r = 0; r < R; ++r) { g[r] = (h2[r] > 0.0f) ? t[r] : 0.0f; t[r] = 0.0f; }
-            if (dumping)
-#pragma unroll
-                for (int r = 0; r < R; ++r) dump.g2[(row0 + r) * 64 + lane] = g[r];
-            dense_bcast_ld<64, R>(bw2, 64, 0, g, t, lane);
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const float gh = (h1[r] > 0.0f) ? t[r] : 0.0f;
-                if (dumping) dump.g1[(row0 + r) * 64 + lane] = gh;
-                if (gp == nullptr) continue;
-                const float ox = wave_sum(gh * wx), oy = wave_sum(gh * wy), oz = wave_sum(gh * wz);
-                if (lane < 4) {
-                    const float v = (k0 + r < cnt && lane < 3) ? ((lane == 0) ? ox : (lane == 1) ? oy : oz) : 0.0f;
-                    recv_sum += v;
-                    if (k0 + r < DRP_K) gpos_edge[(((size_t)b * N + i) * DRP_K + k0 + r) * 4 + lane] = v;
-                }
-            }
-        }
-        if (gp != nullptr && lane < 3) gp[(size_t)i * 3 + lane] += recv_sum;     // this wave is the only writer of row i
-    }
-}
-
-// sender part of the relation encoder's position gradient: g_pos[j] -= sum over the edges j feeds,
-// in the order of the reversed lists (no atomics)
+// the relation encoder's position gradient from its per-slot parts (kmb_edge_encode): g_pos[j] += the sum over node j's own
+// slots, in slot order, -= the sum over the edges j feeds, in the order of the reversed lists (no atomics)
 __global__ void __launch_bounds__(256)
 kb_gather_pos(const float* __restrict__ gpos_edge, const int* __restrict__ rev_off, const int* __restrict__ rev, int N,
-              float* __restrict__ g_pos, size_t gpos_stride, int add_recv = 0, const uint8_t* __restrict__ nbr_cnt = nullptr,
+              float* __restrict__ g_pos, size_t gpos_stride, const uint8_t* __restrict__ nbr_cnt,
               const float* __restrict__ g_add = nullptr /* nullable, laid out as g_pos: added first (the residual's share of the
-                                                           next step's gradient -- the trainer's kt_add folded in) */) {
+                                                           next step's gradient) */) {
     const int b = blockIdx.y;
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= N) return;
@@ -714,16 +413,13 @@ kb_gather_pos(const float* __restrict__ gpos_edge, const int* __restrict__ rev_o
         const float* ga = g_add + (size_t)b * gpos_stride + (size_t)j * 3;
         g0 += ga[0]; g1 += ga[1]; g2 += ga[2];
     }
-    if (add_recv) {
-        // receiver part (kmb_edge_encode leaves it here): the sum over the node's own slots, in slot order
-        const int cnt = nbr_cnt[(size_t)b * N + j];
-        float rx = 0.0f, ry = 0.0f, rz = 0.0f;
-        for (int k = 0; k < cnt; ++k) {
-            const float4 v = ge[(size_t)j * DRP_K + k];
-            rx += v.x; ry += v.y; rz += v.z;
-        }
-        g0 += rx; g1 += ry; g2 += rz;
+    const int cnt = nbr_cnt[(size_t)b * N + j];
+    float rx = 0.0f, ry = 0.0f, rz = 0.0f;
+    for (int k = 0; k < cnt; ++k) {
+        const float4 v = ge[(size_t)j * DRP_K + k];
+        rx += v.x; ry += v.y; rz += v.z;
     }
+    g0 += rx; g1 += ry; g2 += rz;
     float ax = 0.0f, ay = 0.0f, az = 0.0f;
     for (int p = ro[j]; p < ro[j + 1]; ++p) {
         const float4 v = ge[rv[p]];

@@ -2,9 +2,8 @@
 // Each stage is a transposed dense product g_in = W^T g_out over B*N rows; computed like the
 // forward chain of k_mlp_mfma.h, D[in][item] = sum_out W^T[in][out] G[out][item], with W^T as the
 // packed A operand and the 32 rows of a tile on the lane columns (v_mfma_f32_32x32x2_f32: exact
-// fp32 products, fp32 accumulation).  The VALU versions (k_backward.h: kb_update, kb_project,
-// kb_predict, kb_node_encode) read their weights row by row from L2 and were latency bound:
-// 930 us of a 2.2 ms planner iteration.
+// fp32 products, fp32 accumulation): a workgroup fills LDS with the packed weights once, where
+// a VALU row kernel would read them row by row from L2 and be latency bound.
 #pragma once
 #include "k_backward.h"
 #include "k_mlp_mfma.h"
@@ -54,8 +53,10 @@ inline void pack_mfma_bwd(const float* w, std::vector<float>& m) {
 }
 
 // One propagation step of the backward pass on the node rows:
-//   PROJECT: g_eff += W_r^T g_proj[:, 0:64] + W_s^T g_proj[:, 64:128]          (kb_project)
-//   UPDATE : g_z = g_eff . [eff_next > 0]; g_eff <- g_z; g_cnode (+)= g_z; g_agg = W_agg^T g_z   (kb_update)
+//   PROJECT: g_eff += W_r^T g_proj[:, 0:64] + W_s^T g_proj[:, 64:128]
+//   UPDATE : g_z = g_eff . [eff_next > 0]; g_eff <- g_z; g_cnode (+)= g_z; g_agg = W_agg^T g_z
+//            (g_z: the gradient at the update's pre-activation; g_eff <- g_z is the residual's share of the
+//            gradient w.r.t. the previous effect)
 // PROJECT of step p and UPDATE of step p-1 touch the same rows only: one launch does both.
 template <bool PROJECT, bool UPDATE>
 __global__ void __launch_bounds__(64 * MFMA_WAVES)
@@ -114,7 +115,7 @@ kmb_node_step(const float* __restrict__ mb, const float* g_eff_in, float* g_eff 
 }
 #define KMB_STEP_LDS(PROJECT, UPDATE) ((size_t)(((PROJECT) ? 2 : 0) + ((UPDATE) ? 1 : 0)) * 4096 * sizeof(float))
 
-// predictor backward (kb_predict): g_eff = W0^T ((W1^T g_out) . [W0 eff + b0 > 0]); optional dumps of
+// predictor backward: g_eff = W0^T ((W1^T g_out) . [W0 eff + b0 > 0]); optional dumps of
 // relu(hidden) and of the hidden pre-activation gradient for the weight gradients
 __global__ void __launch_bounds__(64 * MFMA_WAVES)
 kmb_predict(const float* __restrict__ mw, const float* __restrict__ mb, const float* __restrict__ eff,
@@ -170,8 +171,8 @@ kmb_predict(const float* __restrict__ mw, const float* __restrict__ mb, const fl
 }
 #define KMB_PREDICT_LDS ((size_t)(2 * 4096 + 256) * sizeof(float))
 
-// particle encoder backward (kb_node_encode): g_pe = g_eff0 + W_pe^T g_cnode, through
-// relu(W2 relu(W1 x + b1) + b2) to the three impulse inputs; optional dumps for the weight gradients
+// particle encoder backward: g_pe = g_eff0 + W_pe^T g_cnode, through relu(W2 relu(W1 x + b1) + b2)
+// to the three impulse inputs g_s_delta[b,n,0:3]; optional dumps for the weight gradients
 __global__ void __launch_bounds__(64 * MFMA_WAVES)
 kmb_node_encode(const float* __restrict__ mw, const float* __restrict__ mb, const float* __restrict__ s_delta,
                 const float* __restrict__ attr, int attr_mod, const float* __restrict__ dens, int dens_mod,
@@ -251,9 +252,6 @@ kmb_node_encode(const float* __restrict__ mw, const float* __restrict__ mb, cons
         }
     }
 }
-// below this many 32-row tiles the chunked VALU row kernels of k_backward.h are faster (a workgroup's
-// LDS fill of the packed weights is not amortised)
-#define KMB_MIN_TILES 1          // round 3: the tiles are dealt workgroup-cyclically, so a handful of them (a training batch) runs one per CU
 #define KMB_NODE_ENCODE_LDS ((size_t)(512 + 2 * 4096 + 192) * sizeof(float))
 
 // acc += scale * v where the row's mask word has the element's bit (bit 31 - (16 ob + q)), + 0 elsewhere: one signed
@@ -1011,17 +1009,15 @@ kmb_rows_bwd(const float* __restrict__ mw, const float* __restrict__ mb, const u
 }
 
 // ---- relation encoder backward on the matrix cores (horizons > 1 of the GD planner, training) -------------------
-// What kb_edge_encode (k_backward.h) computes per edge slot, as the forward chain of km_edge_encode run both ways on
-// tiles of 32 slots: the three Linear+ReLU layers forward (fp32 MFMA; only the SIGN of every pre-activation is kept:
-// 96 bits per lane instead of three fragments), the gradient at c_edge rebuilt from the three propagation steps' ReLU
-// masks and the receiver's g_agg rows (the mask words are in fragment order: word = half-wave, bit 31 - register),
-// then W_e^T, layer 4^T, layer 2^T under the kept signs, and the dot with the three position columns of layer 0.
-// The VALU kernel gave a wave one receiver and kept lane = feature: 5 x 16 KB of weights into LDS per FOUR receivers,
-// 106 us per launch at the reference's training batch (4 x 300 particles), the largest single item of an iteration.
-// Every sum has a fixed order (the MFMA's own k order): bit-reproducible.  Differences to kb_edge_encode: the
-// receiver's own position gradient (the sum over its slots) is left to kb_gather_pos (add_recv), which reads
-// gpos_edge anyway; the result agrees with the VALU kernel to fp32 rounding (another summation order), which the
-// tests against the reference's autograd cover (tests/test_gpu_gd.py horizon 2, tests/test_gpu_train.py).
+// Per edge slot: the relation encoder's chain recomputed (the forward chain of km_edge_encode run both ways on tiles of
+// 32 slots): the three Linear+ReLU layers forward (fp32 MFMA; only the SIGN of every pre-activation is kept: 96 bits per
+// lane instead of three fragments), the gradient at c_edge rebuilt from the three propagation steps' ReLU masks and the
+// receiver's g_agg rows (the mask words are in fragment order: word = half-wave, bit 31 - register), then W_e^T,
+// layer 4^T, layer 2^T under the kept signs, and the dot with the three position columns of layer 0 (x[2:5] = s_r - s_s,
+// gnn_dyn.py:179-180): the slot's gradient w.r.t. s_r - s_s, to gpos_edge.  kb_gather_pos adds it to the receiver's
+// position gradient (the sum over its slots) and takes it from the senders' (over the reversed lists): no atomics.
+// Every sum has a fixed order (the MFMA's own k order): bit-reproducible.  The tests against the reference's autograd
+// cover it (tests/test_gpu_gd.py horizon 2, tests/test_gpu_train.py).
 #define KMB_EDGE_ENCODE_LDS ((size_t)(512 + 5 * 4096 + 128 + 192) * sizeof(float))
 __global__ void __launch_bounds__(64 * MFMA_WAVES)
 kmb_edge_encode(const float* __restrict__ mw, const float* __restrict__ mb, const float* __restrict__ s_cur, int s_mod,

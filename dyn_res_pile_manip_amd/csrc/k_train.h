@@ -74,11 +74,6 @@ kt_unpack_inputs(const float* __restrict__ sdelta_in /* [B][H][N][3] */, const f
     }
 }
 
-__global__ void kt_add(float* __restrict__ dst, const float* __restrict__ src, size_t n) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) dst[i] += src[i];
-}
-
 // dW[lane * lane_stride + k * k_stride] += sum_rows g[row][lane] * x[row][k]      k < IN
 // db[lane]                              += sum_rows g[row][lane]                   (nullable)
 // dwd[lane * lane_stride]               += sum_rows g[row][lane] * dens[row / rows_per_sample] / 5000   (nullable)

@@ -242,10 +242,10 @@ def test_deferred_weight_gradients_equal_the_flushed_ones(golden, monkeypatch, c
         np.testing.assert_array_equal(runs[0][3], runs[1][3])
 
 
-def test_training_through_the_valu_stage_kernels(golden, monkeypatch):
-    """DRP_BWD_VALU_STAGES=1: the trainer's node stages on the VALU row kernels (the path batches below KMB_MIN_TILES tiles took
-    until round 3; no default batch reaches it now) -- the reference's loss and every parameter's gradient."""
-    monkeypatch.setenv('DRP_BWD_VALU_STAGES', '1')
+def test_training_through_the_stage_kernels(golden, monkeypatch):
+    """DRP_NO_BWD_FUSED=1: the trainer's node stages a launch per stage (the default for batches of more than n_cu / 4 tiles;
+    the golden batches take the one-launch kernel) -- the reference's loss and every parameter's gradient."""
+    monkeypatch.setenv('DRP_NO_BWD_FUSED', '1')
     from dyn_res_pile_manip_amd.engine import Engine
     g = golden.train
     case = 'b2_r5'
@@ -257,7 +257,7 @@ def test_training_through_the_valu_stage_kernels(golden, monkeypatch):
     loss, grad = eng.train_step(*batch, mode='grad', want_grad=True)
     ran = eng.last_dispatch()
     eng.close()
-    assert 'train:stages kb_*' in ran and 'train:stages kmb_*' not in ran, ran
+    assert 'train:stages kmb_*' in ran and 'train:kmb_step_bwd' not in ran, ran
     assert abs(loss - g[case + '/losses'][0]) < 1e-4 * g[case + '/losses'][0]
     got = weights.state_dict_from_blob(grad)
     for k, _ in weights.STATE_DICT_KEYS:
