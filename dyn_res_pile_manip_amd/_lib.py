@@ -20,6 +20,9 @@ ENGINE_SPLIT = 2
 ENGINE_FUSED = 3
 TRAIN_MODES = {'eval': 0, 'grad': 1, 'update': 2}
 DIST_TRANSFORMS = {'cv5': 0, 'exact': 1}
+RGR_REGRESSOR = 1           # DRP_RGR_REGRESSOR: n_out of the MPCResRgrNoPool head
+RGR_CLASSIFIER = 6          # DRP_RGR_CLASSIFIER: n_out of the MPCResCls head
+RGR_BMAX = 64
 NOISE_TYPES = {'normal': 0, 'uniform': 1, 'total_rand': 2}
 ENGINES = {'valu': ENGINE_VALU, 'mfma': ENGINE_MFMA, 'split': ENGINE_SPLIT, 'fused': ENGINE_FUSED}
 
@@ -132,6 +135,13 @@ SIGNATURES = {
                                       ctypes.POINTER(ctypes.c_int)]),
     'drp_debug_fetch': (ctypes.c_long, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_void_p,
                                         ctypes.c_size_t]),
+    'drp_rgr_load': (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_size_t, ctypes.c_int]),
+    'drp_rgr_forward': (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int, c_float_p]),
+    'drp_rgr_stack': (ctypes.c_int, [ctypes.c_void_p, c_uint8_p, c_uint8_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                     c_float_p]),
+    'drp_rgr_infer': (ctypes.c_int, [ctypes.c_void_p, c_uint8_p, c_uint8_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                     c_float_p]),
+    'drp_rgr_time': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_float_p]),
 }
 
 _lib = None

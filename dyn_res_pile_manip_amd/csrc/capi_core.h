@@ -164,7 +164,10 @@ void drp_destroy(drp_ctx* c) {
                       &c->tr_part, &c->tr_arena, &c->re_shift_dev, &c->tr_grad, &c->tr_m, &c->tr_v, &c->tr_loss, &c->agg_hist,
                       &c->tr_hact, &c->tr_gh, &c->tr_gpe, &c->tr_a1n, &c->tr_gh1, &c->tr_xn, &c->ed_re, &c->ed_a2, &c->ed_a1,
                       &c->ed_x0, &c->ed_gce, &c->ed_g3, &c->ed_g2, &c->ed_g1, &c->roll_args, &c->map_valu, &c->map_mfma, &c->map_mfma_bwd,
-                      &c->wg_jobs_dev, &c->wg_idx_dev};
+                      &c->wg_jobs_dev, &c->wg_idx_dev,
+                      &c->rgr_w, &c->rgr_raw, &c->rgr_x, &c->rgr_a[0], &c->rgr_a[1], &c->rgr_a[2], &c->rgr_a[3], &c->rgr_a[4],
+                      &c->rgr_f[0], &c->rgr_f[1], &c->rgr_f[2], &c->rgr_f[3], &c->rgr_slab, &c->rgr_out, &c->rgr_mask,
+                      &c->rgr_dtmp, &c->rgr_dist, &c->rgr_tab};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (hipEvent_t ev : c->probe_ev) (void)hipEventDestroy(ev);

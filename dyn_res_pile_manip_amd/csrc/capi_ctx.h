@@ -383,6 +383,13 @@ struct drp_ctx {
     // goal pre-processing (row f3)
     DevBuf gl_goal, gl_seg, gl_tmp, gl_dist, gl_blk, gl_pix, gl_fps;
 
+    // resolution regressor (capi_rgr.h): its own weights and workspaces, nothing shared with the PropNet state
+    DevBuf rgr_w, rgr_raw, rgr_x, rgr_a[5], rgr_f[4], rgr_slab, rgr_out, rgr_mask, rgr_dtmp, rgr_dist, rgr_tab;
+    int rgr_nout = 0;               // 0: nothing loaded
+    int rgr_lastB = 0;              // batch of the last forward (debug taps)
+    int rgr_tab_h = 0, rgr_tab_w = 0;   // the image size rgr_tab was built for
+    std::vector<int> rgr_tab_host;      // its host image (INTER_AREA tables: offsets and indices, then the float weights)
+
     // re-packing after an optimiser step on the device (k_train.h): gather maps of the plain packers, pinned copy of the blob
     DevBuf map_valu, map_mfma, map_mfma_bwd;
     bool repack_maps_ready = false;

@@ -167,6 +167,12 @@ long drp_debug_fetch(drp_ctx* c, const char* name, void* out, size_t out_bytes) 
     else if (!strcmp(name, "w_split6_bwd")) { b = &c->w_split6_bwd; bytes = (size_t)SB6_TOTAL * 16; }
     else if (!strcmp(name, "rev_off")) { b = &c->rev_off; bytes = (size_t)c->lastB * (c->lastN + 1) * 4; }
     else if (!strcmp(name, "rev")) { b = &c->rev; bytes = bn * DRP_K * 4; }
+    // the resolution regressor's post-activation taps of its last forward (NHWC [B][H][W][C] for the convolutions)
+    else if (!strncmp(name, "rgr_c", 5) && name[5] >= '1' && name[5] <= '5' && !name[6]) {
+        b = &c->rgr_a[name[5] - '1']; bytes = rgr_conv_out_floats(name[5] - '1', c->rgr_lastB) * 4;
+    } else if (!strncmp(name, "rgr_f", 5) && name[5] >= '1' && name[5] <= '4' && !name[6]) {
+        b = &c->rgr_f[name[5] - '1']; bytes = (size_t)c->rgr_lastB * RGR_FC_OUT[name[5] - '1'] * 4;
+    }
     else return fail(c, DRP_EINVAL, "unknown buffer '%s'", name);
     // a GD session keeps every step's impulses and lists in its tape, not in the step workspace: the last step's
     DevBuf tape{};

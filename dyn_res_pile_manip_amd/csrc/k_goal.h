@@ -38,12 +38,11 @@ __device__ __forceinline__ int dt_block_prefix_min(int v, int* s_w) {
 }
 
 // One workgroup walks the rows.  tmp: [h][w] int32 work image (forward result, then final).
-// LDS: three rows with a 2-pixel border each.
-__global__ void __launch_bounds__(DT_THREADS)
-k_dt_cv5(const uint8_t* __restrict__ src, int h, int w, int* __restrict__ tmp, float* __restrict__ dist) {
-    extern __shared__ int s_rows[];
-    __shared__ int s_w[16];
-    __shared__ int s_carry;
+// LDS: three rows with a 2-pixel border each.  The body is shared with the resolution regressor's paired launch
+// (k_rgr.h); kInv: the zero set is src != 0 instead of src == 0 (the transform of 1 - src).
+template <bool kInv>
+__device__ __forceinline__ void dt_cv5_body(const uint8_t* __restrict__ src, int h, int w, int* __restrict__ tmp,
+                                            float* __restrict__ dist, int* s_rows, int* s_w, int& s_carry) {
     const int tid = threadIdx.x;
     const int ld = w + 4;
     int* r2 = s_rows;              // row i-2 (forward) / i+2 (backward)
@@ -60,7 +59,7 @@ k_dt_cv5(const uint8_t* __restrict__ src, int h, int w, int* __restrict__ tmp, f
             const int j = base + tid;
             int c = 0x7fffffff, v = 0x7fffffff;
             if (j < w) {
-                if (!src[(size_t)i * w + j]) c = 0;
+                if ((src[(size_t)i * w + j] != 0) == kInv) c = 0;
                 else {
                     const int* p2 = r2 + 2 + j;
                     const int* p1 = r1 + 2 + j;
@@ -130,29 +129,40 @@ k_dt_cv5(const uint8_t* __restrict__ src, int h, int w, int* __restrict__ tmp, f
     }
 }
 
+__global__ void __launch_bounds__(DT_THREADS)
+k_dt_cv5(const uint8_t* __restrict__ src, int h, int w, int* __restrict__ tmp, float* __restrict__ dist) {
+    extern __shared__ int s_rows[];
+    __shared__ int s_w[16];
+    __shared__ int s_carry;
+    dt_cv5_body<false>(src, h, w, tmp, dist, s_rows, s_w, s_carry);
+}
+
 // exact transform, phase 1: per column, distance to the nearest zero pixel of the column
 #define EDT_INF 0x3fffffff
-__global__ void __launch_bounds__(256)
-k_edt_cols(const uint8_t* __restrict__ src, int h, int w, int* __restrict__ g) {
-    const int x = blockIdx.x * 256 + threadIdx.x;
-    if (x >= w) return;
+// (kInv as in dt_cv5_body)
+template <bool kInv>
+__device__ __forceinline__ void edt_cols_body(const uint8_t* __restrict__ src, int h, int w, int* __restrict__ g, int x) {
     int d = EDT_INF;
     for (int y = 0; y < h; ++y) {
-        d = src[(size_t)y * w + x] ? (d == EDT_INF ? EDT_INF : d + 1) : 0;
+        d = (src[(size_t)y * w + x] != 0) != kInv ? (d == EDT_INF ? EDT_INF : d + 1) : 0;
         g[(size_t)y * w + x] = d;
     }
     d = EDT_INF;
     for (int y = h - 1; y >= 0; --y) {
-        d = src[(size_t)y * w + x] ? (d == EDT_INF ? EDT_INF : d + 1) : 0;
+        d = (src[(size_t)y * w + x] != 0) != kInv ? (d == EDT_INF ? EDT_INF : d + 1) : 0;
         if (d < g[(size_t)y * w + x]) g[(size_t)y * w + x] = d;
     }
 }
 
-// phase 2: per row, d2[x] = min_x' (x - x')^2 + g[x']^2 ; out = float32(sqrt(float64(d2)))
 __global__ void __launch_bounds__(256)
-k_edt_rows(const int* __restrict__ g, int h, int w, float* __restrict__ dist) {
-    extern __shared__ int s_g[];
-    const int y = blockIdx.x;
+k_edt_cols(const uint8_t* __restrict__ src, int h, int w, int* __restrict__ g) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= w) return;
+    edt_cols_body<false>(src, h, w, g, x);
+}
+
+// phase 2: per row, d2[x] = min_x' (x - x')^2 + g[x']^2 ; out = float32(sqrt(float64(d2)))
+__device__ __forceinline__ void edt_rows_body(const int* __restrict__ g, int w, float* __restrict__ dist, int* s_g, int y) {
     for (int x = threadIdx.x; x < w; x += 256) s_g[x] = g[(size_t)y * w + x];
     __syncthreads();
     for (int x = threadIdx.x; x < w; x += 256) {
@@ -166,6 +176,13 @@ k_edt_rows(const int* __restrict__ g, int h, int w, float* __restrict__ dist) {
         }
         dist[(size_t)y * w + x] = (float)sqrt((double)best);
     }
+}
+
+__global__ void __launch_bounds__(256)
+k_edt_rows(const int* __restrict__ g, int h, int w, float* __restrict__ dist) {
+    extern __shared__ int s_g[];
+    (void)h;
+    edt_rows_body(g, w, dist, s_g, blockIdx.x);
 }
 
 __global__ void k_goal_seg(const float* __restrict__ goal, size_t n, uint8_t* __restrict__ seg) {

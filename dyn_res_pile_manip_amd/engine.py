@@ -149,6 +149,63 @@ class Engine(object):
                                                  src.shape[0], src.shape[1], L.DIST_TRANSFORMS[mode], _fp(out)))
         return out
 
+    # ---- resolution regressor (model/res_regressor.py; include/drp.h drp_rgr_*) -----------------------------------
+    rgr_n_out = 0
+    rgr_owner = None
+
+    def rgr_load(self, blob, n_out):
+        """state_dict blob (res_regressor.blob_from_state_dict) of the regressor (n_out 1) or the classifier (n_out 6)."""
+        b = _f32(blob).reshape(-1)
+        self.rgr_owner = None         # the res_regressor model whose weights the context holds (set by that model)
+        self._ck(self.lib.drp_rgr_load(self.h, _fp(b), b.size, int(n_out)))
+        self.rgr_n_out = int(n_out)
+        self._rgr_lastB = 0
+
+    def rgr_forward(self, x):
+        """x [B,6,224,224], 1 <= B <= 64 -> [B,n_out]"""
+        a = _f32(x)
+        B = a.shape[0] if a.ndim == 4 else 0
+        out = np.empty((max(B, 1), max(self.rgr_n_out, 1)), np.float32)
+        self._ck(self.lib.drp_rgr_forward(self.h, _fp(a), int(B), _fp(out)))
+        self._rgr_lastB = B
+        return out
+
+    def _rgr_masks(self, init, goal):
+        a = np.ascontiguousarray(init, dtype=np.uint8)
+        g = np.ascontiguousarray(goal, dtype=np.uint8)
+        assert a.shape == g.shape and a.ndim == 2, (a.shape, g.shape)
+        return a, g, a.ctypes.data_as(L.c_uint8_p), g.ctypes.data_as(L.c_uint8_p)
+
+    def rgr_stack(self, init, goal, mode='cv5'):
+        """the [6,224,224] input stack of infer_param from two 0/1 masks [h,w] (h, w >= 224)"""
+        a, g, pa, pg = self._rgr_masks(init, goal)
+        out = np.empty((6, 224, 224), np.float32)
+        self._ck(self.lib.drp_rgr_stack(self.h, pa, pg, a.shape[0], a.shape[1], L.DIST_TRANSFORMS[mode], _fp(out)))
+        return out
+
+    def rgr_infer(self, init, goal, mode='cv5'):
+        """stack + forward of one mask pair -> the head's outputs [n_out]"""
+        a, g, pa, pg = self._rgr_masks(init, goal)
+        out = np.empty(max(self.rgr_n_out, 1), np.float32)
+        self._ck(self.lib.drp_rgr_infer(self.h, pa, pg, a.shape[0], a.shape[1], L.DIST_TRANSFORMS[mode], _fp(out)))
+        self._rgr_lastB = 1
+        return out
+
+    def rgr_time(self, B, iters=20, parts=7):
+        """device ms of each of `iters` forward passes at batch B (parts: 1 convolutions, 2 FC1, 4 FC2..head, summed)"""
+        ms = np.empty(int(iters), np.float32)
+        self._ck(self.lib.drp_rgr_time(self.h, int(parts), int(B), int(iters), _fp(ms)))
+        return ms
+
+    def rgr_tap(self, name):
+        """post-activation tap of the last regressor forward: 'c1'..'c5' -> [B,C,H,W] (torch's layout), 'f1'..'f4' -> [B,F]"""
+        B = getattr(self, '_rgr_lastB', 0)
+        if name[0] == 'c':
+            l = int(name[1]) - 1
+            hw, ch = 112 >> l, (64, 128, 256, 512, 512)[l]
+            return self.debug_fetch('rgr_' + name, (B, hw, hw, ch)).transpose(0, 3, 1, 2).copy()
+        return self.debug_fetch('rgr_' + name, (B, (4096, 1024, 256, 64)[int(name[1]) - 1]))
+
     def set_goal_image(self, obs_goal, max_goal_pts, fps_init=0, mode='cv5', want=False):
         """Goal field (env/flex_rewards.py:172-177) and goal pixel subsample (planners.py:620-624) from
         the goal distance image, computed and kept on the device.  want=True also returns

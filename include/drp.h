@@ -331,6 +331,34 @@ int drp_comm_info(drp_ctx* ctx, int* n_ranks, int* rank, int* version, char* pat
  * planners.py:721-727) when the sample axis is sharded; the update itself stays on the device. */
 int drp_comm_allgather(drp_ctx* ctx, const void* send, size_t bytes, void* recv);
 
+/* ---- resolution regressor (model/res_regressor.py:15-177) ---------------------------------------------------
+ * The CNN the MPC loop asks for the particle count at every step (env/flex_env.py:981-998, :1083-1086; config/mpc/config.yaml:53-56
+ * res_sel.active): five Conv2d(k=4, s=2, p=1) + LeakyReLU(0.2), 6 -> 64 -> 128 -> 256 -> 512 -> 512 channels, 224 -> 7 pixels,
+ * NCHW flatten, Linear 25088 -> 4096 -> 1024 -> 256 -> 64 each + LeakyReLU(0.2), head Linear(64, n_out):
+ * MPCResRgrNoPool (n_out 1, infer_param returns int(out)) or MPCResCls (n_out 6, [4, 8, 16, 32, 64, 128][argmax]).
+ * Its weights and workspaces are the context's but apart from the PropNet's: loading or running one never touches the other.
+ * Nothing is allocated before drp_rgr_load, which sizes every buffer for DRP_RGR_BMAX samples.  fp32 throughout; each output
+ * element has one reduction order, fixed per layer and independent of B: a sample's outputs are bit-identical in any batch.
+ * Each call runs on the context's stream and waits once, for its output copy. */
+#define DRP_RGR_REGRESSOR 1     /* n_out of the MPCResRgrNoPool head */
+#define DRP_RGR_CLASSIFIER 6    /* n_out of the MPCResCls head */
+#define DRP_RGR_BMAX 64
+#define DRP_RGR_SIZE 224        /* state_h = state_w */
+/* blob: the state_dict model.{0,2,4,6,8,11,13,15,17,19}.{weight,bias} in that order, torch layouts, n_floats = 114 193 217
+ * (n_out 1) or 114 193 542 (n_out 6); repacked on the device once (conv [Cout][kh][kw][Cin], FC1's columns in NHWC order). */
+int drp_rgr_load(drp_ctx* ctx, const float* blob, size_t n_floats, int n_out);
+/* x [B][6][224][224] (the stack of infer_param), 1 <= B <= DRP_RGR_BMAX -> out [B][n_out].  DRP_ESTATE before drp_rgr_load. */
+int drp_rgr_forward(drp_ctx* ctx, const float* x, int B, float* out);
+/* The stack of infer_param (model/res_regressor.py:146-175) from two [h][w] masks (nonzero = 1), h, w >= 224: the distance
+ * transforms of 1 - mask (dt_mode DRP_DT_CV5 / DRP_DT_EXACT, both in one launch) over h, the two exclusions, each of the six
+ * INTER_AREA-downscaled to 224 x 224 -> x_out [6][224][224] (nullable). */
+int drp_rgr_stack(drp_ctx* ctx, const uint8_t* init, const uint8_t* goal, int h, int w, int dt_mode, float* x_out);
+/* stack + forward at B = 1 -> out [n_out] (the caller applies int() or the argmax) */
+int drp_rgr_infer(drp_ctx* ctx, const uint8_t* init, const uint8_t* goal, int h, int w, int dt_mode, float* out);
+/* Device time of `iters` back-to-back forward passes at batch B on whatever the device buffers hold (measurement only):
+ * parts = a sum of 1 (the convolutions), 2 (FC1: its GEMV and split-K reduction), 4 (FC2..head); ms_out [iters] (HIP events). */
+int drp_rgr_time(drp_ctx* ctx, int parts, int B, int iters, float* ms_out);
+
 /* ---- measurement / debugging ----------------------------------------------------- */
 /* HIP-event timing of one kernel class on the context's stream.  name: "graph",
  * "node_encode", "edge_encode", "project", "aggregate", "update", "predict", "reward",
@@ -368,7 +396,8 @@ int drp_range_info(drp_ctx* ctx, int* shift, double* bound, double* wmax, int* o
 int drp_debug_stall(drp_ctx* ctx, int ms);
 /* copy an intermediate device buffer to the host: "s_delta","nbr_idx","nbr_cnt",
  * "particle_encode"(eff0),"c_node","c_edge","proj","agg","effect"; the weight blob "w_raw" and its packed copies
- * "w_valu","w_mfma","w_mfma_bwd","w_split","w_split6" (byte sizes: the returned value). returns bytes. */
+ * "w_valu","w_mfma","w_mfma_bwd","w_split","w_split6"; the resolution regressor's post-activation taps of its last forward
+ * "rgr_c1".."rgr_c5" (NHWC [B][H][W][C]) and "rgr_f1".."rgr_f4" ([B][features]) (byte sizes: the returned value). returns bytes. */
 long drp_debug_fetch(drp_ctx* ctx, const char* name, void* out, size_t out_bytes);
 
 #ifdef __cplusplus
