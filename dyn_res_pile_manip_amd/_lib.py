@@ -142,6 +142,12 @@ SIGNATURES = {
     'drp_rgr_infer': (ctypes.c_int, [ctypes.c_void_p, c_uint8_p, c_uint8_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      c_float_p]),
     'drp_rgr_time': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_float_p]),
+    'drp_rgr_train_begin': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double]),
+    'drp_rgr_train_step': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.POINTER(ctypes.c_int32),
+                                          ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), c_float_p]),
+    'drp_rgr_train_set_lr': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double]),
+    'drp_rgr_get_weights': (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_size_t]),
+    'drp_rgr_train_time': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_float_p]),
 }
 
 _lib = None

@@ -167,7 +167,8 @@ void drp_destroy(drp_ctx* c) {
                       &c->wg_jobs_dev, &c->wg_idx_dev,
                       &c->rgr_w, &c->rgr_raw, &c->rgr_x, &c->rgr_a[0], &c->rgr_a[1], &c->rgr_a[2], &c->rgr_a[3], &c->rgr_a[4],
                       &c->rgr_f[0], &c->rgr_f[1], &c->rgr_f[2], &c->rgr_f[3], &c->rgr_slab, &c->rgr_out, &c->rgr_mask,
-                      &c->rgr_dtmp, &c->rgr_dist, &c->rgr_tab};
+                      &c->rgr_dtmp, &c->rgr_dist, &c->rgr_tab, &c->rgr_m, &c->rgr_v, &c->rgr_g, &c->rgr_gfull, &c->rgr_dz[0],
+                      &c->rgr_dz[1], &c->rgr_gf, &c->rgr_bpart, &c->rgr_l1, &c->rgr_lossp, &c->rgr_tgt};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (hipEvent_t ev : c->probe_ev) (void)hipEventDestroy(ev);

@@ -389,6 +389,12 @@ struct drp_ctx {
     int rgr_lastB = 0;              // batch of the last forward (debug taps)
     int rgr_tab_h = 0, rgr_tab_w = 0;   // the image size rgr_tab was built for
     std::vector<int> rgr_tab_host;      // its host image (INTER_AREA tables: offsets and indices, then the float weights)
+    // its training (capi_rgr_train.h): allocated from drp_rgr_train_begin on
+    DevBuf rgr_m, rgr_v, rgr_g, rgr_gfull, rgr_dz[2], rgr_gf, rgr_bpart, rgr_l1, rgr_lossp, rgr_tgt;
+    bool rgr_tr_on = false;             // drp_rgr_train_begin since the last drp_rgr_load
+    double rgr_tr_lr = 0.0, rgr_tr_beta1 = 0.9, rgr_tr_lam = 0.0;
+    long rgr_tr_iter = 0;               // Adam steps taken
+    int rgr_tr_lastB = 0;               // batch of the last training step (its inputs stay staged on the device)
 
     // re-packing after an optimiser step on the device (k_train.h): gather maps of the plain packers, pinned copy of the blob
     DevBuf map_valu, map_mfma, map_mfma_bwd;

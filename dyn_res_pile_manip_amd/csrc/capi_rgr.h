@@ -181,6 +181,8 @@ int drp_rgr_load(drp_ctx* c, const float* blob, size_t n_floats, int n_out) {
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     c->rgr_nout = 0;
+    c->rgr_tr_on = false;               // a fresh model: any training in progress ends with its optimiser (capi_rgr_train.h)
+    c->rgr_tr_lastB = 0;
     HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rgr_fc<25088, 16, 16, 8>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 16 * (1568 + 4) * 4));
     CHK(ensure(c, c->rgr_w, o.total * sizeof(float)));

@@ -197,6 +197,56 @@ class Engine(object):
         self._ck(self.lib.drp_rgr_time(self.h, int(parts), int(B), int(iters), _fp(ms)))
         return ms
 
+    def rgr_train_begin(self, lr, beta1=0.9, lam_reg=0.0):
+        """Adam state for the loaded regressor (zeroed, t = 0): torch.optim.Adam(lr, betas=(beta1, 0.999)) and the L1 weight
+        lam_reg of train/train_res_rgr.py:170-183"""
+        self._ck(self.lib.drp_rgr_train_begin(self.h, float(lr), float(beta1), float(lam_reg)))
+
+    def rgr_train_step(self, x, y=None, conf=None, label=None, mode='update', want_grad=False):
+        """x [B,6,224,224]; y [B] and conf [B] (regressor) or label [B] in 0..5 (classifier); mode 'eval' | 'grad' | 'update'
+        -> ((loss, mse|ce, reg) before any update, gradient blob in state_dict order or None; want_grad needs mode 'grad')"""
+        a = _f32(x)
+        B = a.shape[0] if a.ndim == 4 else 0
+        yp = cp = lp = None
+        if y is not None:
+            y = _f32(y).reshape(-1)
+            yp = _fp(y)
+        if conf is not None:
+            conf = _f32(conf).reshape(-1)
+            cp = _fp(conf)
+        if label is not None:
+            label = np.ascontiguousarray(label, dtype=np.int32).reshape(-1)
+            lp = label.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        for v in (y, conf, label):
+            if v is not None and v.size != B:
+                raise ValueError('target of %d values for a batch of %d' % (v.size, B))
+        loss = np.zeros(3, np.float64)
+        grad = None
+        if want_grad:
+            from .res_regressor import n_floats
+            grad = np.empty(n_floats(max(self.rgr_n_out, 1)), np.float32)
+        self._ck(self.lib.drp_rgr_train_step(self.h, _fp(a), yp, cp, lp, int(B), L.TRAIN_MODES[mode], _dp(loss),
+                                             _fp(grad) if grad is not None else None))
+        self._rgr_lastB = B
+        return (float(loss[0]), float(loss[1]), float(loss[2])), grad
+
+    def rgr_train_set_lr(self, lr):
+        self._ck(self.lib.drp_rgr_train_set_lr(self.h, float(lr)))
+
+    def rgr_get_weights(self):
+        """the regressor's device weights as a blob in state_dict order, torch layouts"""
+        from .res_regressor import n_floats
+        out = np.empty(n_floats(max(self.rgr_n_out, 1)), np.float32)
+        self._ck(self.lib.drp_rgr_get_weights(self.h, _fp(out), out.size))
+        return out
+
+    def rgr_train_time(self, B, iters=10):
+        """device ms [iters, 3] of back-to-back UPDATE steps on the last training step's inputs (batch B): forward | loss + FC
+        backward with FC1's Adam step | conv backward + the other parameters' Adam step.  The steps move the weights."""
+        ms = np.empty((int(iters), 3), np.float32)
+        self._ck(self.lib.drp_rgr_train_time(self.h, int(B), int(iters), _fp(ms)))
+        return ms
+
     def rgr_tap(self, name):
         """post-activation tap of the last regressor forward: 'c1'..'c5' -> [B,C,H,W] (torch's layout), 'f1'..'f4' -> [B,F]"""
         B = getattr(self, '_rgr_lastB', 0)

@@ -203,11 +203,26 @@ class _ResModel(object):
         a, b = self._masks(init_img, goal_img)
         return self.engine.rgr_infer(a, b, self.dt_mode)
 
+    def state_dict(self, as_torch=False):
+        """the device's current weights (training moves them) as {key: array} in state_dict order, torch layouts; torch
+        tensors with as_torch=True"""
+        self._check()
+        sd = state_dict_from_blob(self.engine.rgr_get_weights(), self.N_OUT)
+        if as_torch:
+            import torch
+            return {k: torch.from_numpy(v.copy()) for k, v in sd.items()}
+        return sd
+
     def cuda(self, *args, **kwargs):
         return self
 
-    def eval(self):
+    def train(self, mode=True):
+        """nn.Module.train: the network has no dropout or batch norm, nothing changes"""
+        self.training = bool(mode)
         return self
+
+    def eval(self):
+        return self.train(False)
 
     def to(self, *args, **kwargs):
         return self

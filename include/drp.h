@@ -359,6 +359,36 @@ int drp_rgr_infer(drp_ctx* ctx, const uint8_t* init, const uint8_t* goal, int h,
  * parts = a sum of 1 (the convolutions), 2 (FC1: its GEMV and split-K reduction), 4 (FC2..head); ms_out [iters] (HIP events). */
 int drp_rgr_time(drp_ctx* ctx, int parts, int B, int iters, float* ms_out);
 
+/* ---- training the resolution regressor (train/train_res_rgr.py:100-222; loss and update :150-183) ----------------------
+ * One step = the forward above (its outputs bit-identical to drp_rgr_forward's), the loss, the backward pass and Adam, on the
+ * device.  Losses (the phase's `loss`, `mse` | `ce`, `reg`):
+ *   regressor  (n_out 1): mse = mean_b conf[b] (out[b] - y[b])^2                (MSELoss(reduction='none')(out, y) * conf).mean()
+ *   classifier (n_out 6): ce  = mean_b (logsumexp(out[b]) - out[b][label[b]])   CrossEntropyLoss()(out, label)
+ *   reg  = sum |W| / n_W over the 10 weights (biases excluded; n_W = their element count), loss = mse|ce + lam_reg reg; its
+ *          gradient lam_reg sign(W) / n_W with sign(0) = 0.
+ * Optimiser: torch.optim.Adam(lr, betas=(beta1, 0.999)), eps 1e-8, no weight decay, over every parameter (k_adam's formula).
+ * fp32 with float64 loss terms; every value has one fixed reduction order and there are no float atomics, so the same step
+ * sequence gives bit-identical weights (gradients depend on B's split of the work, not on the run).
+ * Memory: Adam's m and v (2 x 4 bytes per parameter) and the workspaces are allocated by drp_rgr_train_begin, the full
+ * gradient buffer and its torch-layout staging copy only once a step asks for grad_out (then kept).  Nothing here touches the
+ * PropNet weights or drp_train_* state. */
+/* Allocates and zeroes Adam's state, t = 0.  DRP_ESTATE before drp_rgr_load; drp_rgr_load ends any training in progress. */
+int drp_rgr_train_begin(drp_ctx* ctx, double lr, double beta1, double lam_reg);
+/* x [B][6][224][224], 1 <= B <= DRP_RGR_BMAX; targets: y [B] and conf [B] for the regressor (label NULL), label [B] in 0..5
+ * for the classifier (y, conf NULL); anything else is DRP_EINVAL.  mode DRP_TRAIN_EVAL (loss only), DRP_TRAIN_GRAD (the
+ * weights stay as they are) or DRP_TRAIN_UPDATE (one Adam step).  loss_out [3] (nullable): loss, mse|ce, reg, always before
+ * the update.  grad_out (nullable, DRP_TRAIN_GRAD only): the gradient, n_floats in state_dict order and torch layouts.
+ * After an update drp_rgr_forward / drp_rgr_infer use the new weights.  DRP_ESTATE before drp_rgr_train_begin. */
+int drp_rgr_train_step(drp_ctx* ctx, const float* x, const float* y, const float* conf, const int32_t* label, int B, int mode,
+                       double* loss_out, float* grad_out);
+int drp_rgr_train_set_lr(drp_ctx* ctx, double lr);
+/* the device's weights back in the blob layout of drp_rgr_load (state_dict order, torch layouts) */
+int drp_rgr_get_weights(drp_ctx* ctx, float* blob_out, size_t n_floats);
+/* Device time of `iters` back-to-back UPDATE steps (they move the weights: measurement only) on the inputs of the last
+ * drp_rgr_train_step, whose batch B must be: ms_out [iters][3] = forward | loss + FC backward with FC1's fused Adam step |
+ * conv backward + Adam over the other parameters (HIP events). */
+int drp_rgr_train_time(drp_ctx* ctx, int B, int iters, float* ms_out);
+
 /* ---- measurement / debugging ----------------------------------------------------- */
 /* HIP-event timing of one kernel class on the context's stream.  name: "graph",
  * "node_encode", "edge_encode", "project", "aggregate", "update", "predict", "reward",
