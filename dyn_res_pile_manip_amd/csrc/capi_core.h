@@ -168,7 +168,9 @@ void drp_destroy(drp_ctx* c) {
                       &c->rgr_w, &c->rgr_raw, &c->rgr_x, &c->rgr_a[0], &c->rgr_a[1], &c->rgr_a[2], &c->rgr_a[3], &c->rgr_a[4],
                       &c->rgr_f[0], &c->rgr_f[1], &c->rgr_f[2], &c->rgr_f[3], &c->rgr_slab, &c->rgr_out, &c->rgr_mask,
                       &c->rgr_dtmp, &c->rgr_dist, &c->rgr_tab, &c->rgr_m, &c->rgr_v, &c->rgr_g, &c->rgr_gfull, &c->rgr_dz[0],
-                      &c->rgr_dz[1], &c->rgr_gf, &c->rgr_bpart, &c->rgr_l1, &c->rgr_lossp, &c->rgr_tgt};
+                      &c->rgr_dz[1], &c->rgr_gf, &c->rgr_bpart, &c->rgr_l1, &c->rgr_lossp, &c->rgr_tgt,
+                      &c->pd_in, &c->pd_blk, &c->pd_meta, &c->pd_pcd, &c->pd_dist, &c->pd_chosen, &c->pd_rec, &c->pd_near,
+                      &c->pd_out};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (hipEvent_t ev : c->probe_ev) (void)hipEventDestroy(ev);
@@ -182,6 +184,9 @@ void drp_destroy(drp_ctx* c) {
     }
     if (c->w_pin) (void)hipHostFree(c->w_pin);
     if (c->tr_pin) (void)hipHostFree(c->tr_pin);
+    if (c->pd_pin) (void)hipHostFree(c->pd_pin);
+    for (hipEvent_t ev : c->pd_ev)
+        if (ev) (void)hipEventDestroy(ev);
     if (c->deg_stat) (void)hipHostFree(c->deg_stat);
     (void)hipStreamDestroy(c->stream);
     delete c;

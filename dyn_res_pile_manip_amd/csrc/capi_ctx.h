@@ -396,6 +396,14 @@ struct drp_ctx {
     long rgr_tr_iter = 0;               // Adam steps taken
     int rgr_tr_lastB = 0;               // batch of the last training step (its inputs stay staged on the device)
 
+    // GNN training batches from recorded episodes (capi_ptcl_dataset.h, row x4): workspaces of its own
+    DevBuf pd_in, pd_blk, pd_meta, pd_pcd, pd_dist, pd_chosen, pd_rec, pd_near, pd_out;
+    void* pd_pin = nullptr;         // pinned staging: the upload arena, then the counts, then the download
+    size_t pd_pin_cap = 0;
+    hipEvent_t pd_ev[7] = {};       // stage boundaries of the last drp_ptcl_dataset_batch (drp_ptcl_dataset_time)
+    bool pd_timed = false;
+    int pd_lastB = 0, pd_nmax = 0;  // shapes of the last batch (debug taps)
+
     // re-packing after an optimiser step on the device (k_train.h): gather maps of the plain packers, pinned copy of the blob
     DevBuf map_valu, map_mfma, map_mfma_bwd;
     bool repack_maps_ready = false;

@@ -147,6 +147,7 @@ long drp_debug_fetch(drp_ctx* c, const char* name, void* out, size_t out_bytes) 
     if (!c || !name || !out) return DRP_EINVAL;
     const size_t bn = (size_t)c->lastB * c->lastN;
     const DevBuf* b = nullptr;
+    DevBuf tap{};
     size_t bytes = 0;
     if (!strcmp(name, "s_delta")) { b = &c->s_delta; bytes = bn * 3 * 4; }
     else if (!strcmp(name, "nbr_idx")) { b = &c->nbr_idx; bytes = bn * DRP_K * 2; }
@@ -173,6 +174,13 @@ long drp_debug_fetch(drp_ctx* c, const char* name, void* out, size_t out_bytes) 
     } else if (!strncmp(name, "rgr_f", 5) && name[5] >= '1' && name[5] <= '4' && !name[6]) {
         b = &c->rgr_f[name[5] - '1']; bytes = (size_t)c->rgr_lastB * RGR_FC_OUT[name[5] - '1'] * 4;
     }
+    // the GNN dataset's intermediates of its last batch: foreground counts [B] and sampler picks [B][4097] (int32),
+    // recentered points [B][n_max][3] (float64), nearest frame-0 particles [B][n_max] (int32)
+    else if (!strcmp(name, "pd_nfg")) {
+        tap.p = ptr<long long>(c->pd_meta) + c->pd_lastB; tap.cap = c->pd_meta.cap; b = &tap; bytes = (size_t)c->pd_lastB * 4;
+    } else if (!strcmp(name, "pd_chosen")) { b = &c->pd_chosen; bytes = (size_t)c->pd_lastB * (PD_CAP + 1) * 4; }
+    else if (!strcmp(name, "pd_recenter")) { b = &c->pd_rec; bytes = (size_t)c->pd_lastB * c->pd_nmax * 3 * 8; }
+    else if (!strcmp(name, "pd_nearest")) { b = &c->pd_near; bytes = (size_t)c->pd_lastB * c->pd_nmax * 4; }
     else return fail(c, DRP_EINVAL, "unknown buffer '%s'", name);
     // a GD session keeps every step's impulses and lists in its tape, not in the step workspace: the last step's
     DevBuf tape{};

@@ -1,0 +1,204 @@
+// capi_ptcl_dataset.h -- a section of the C ABI's translation unit (textually included by drp_capi.hip inside extern "C", after
+// capi_rgr_train.h).
+// Here: GNN training batches from recorded episodes (row x4, dataset/dataset_gnn_dyn.py:86-201; kernels: k_ptcl_dataset.h).
+// The call owns its workspaces (c->pd_*): the PropNet weights, a training / planning session, the regressor and the
+// particle-extraction buffers of drp_obs2ptcl are never touched.
+
+namespace {
+const int PD_BMAX = 1024;
+const int PD_NEV = 7;           // events: start | upload | compaction | fps_rad | recenter | track + pack | download
+
+size_t pd_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+struct PdLayout {               // the upload arena (pinned staging and its device copy)
+    size_t depth, ptcl, radius, push, init, nptcl, ptcl_off, bytes;
+};
+
+PdLayout pd_layout(int B, size_t npix, size_t ptcl_floats, int T) {
+    PdLayout L;
+    size_t o = 0;
+    L.depth = o; o = pd_align(o + (size_t)B * npix * sizeof(uint16_t));
+    L.ptcl = o; o = pd_align(o + ptcl_floats * sizeof(float));
+    L.radius = o; o = pd_align(o + (size_t)B * sizeof(double));
+    L.push = o; o = pd_align(o + (size_t)B * (T - 1) * PD_PUSH * sizeof(double));
+    L.init = o; o = pd_align(o + (size_t)B * sizeof(int));
+    L.nptcl = o; o = pd_align(o + (size_t)B * sizeof(int));
+    L.ptcl_off = o; o = pd_align(o + (size_t)B * sizeof(long long));
+    L.bytes = o;
+    return L;
+}
+
+int pd_pin_ensure(drp_ctx* c, size_t bytes) {
+    if (c->pd_pin_cap >= bytes) return DRP_OK;
+    if (c->pd_pin) {
+        (void)hipStreamSynchronize(c->stream);      // nothing of an earlier call may still copy from / to it
+        (void)hipHostFree(c->pd_pin); c->pd_pin = nullptr; c->pd_pin_cap = 0;
+    }
+    HIPCHK(c, hipHostMalloc(&c->pd_pin, bytes, hipHostMallocDefault));
+    c->pd_pin_cap = bytes;
+    return DRP_OK;
+}
+
+int pd_name(const int32_t* episode, int b) { return episode ? episode[b] : b; }
+}  // namespace
+
+int drp_ptcl_dataset_batch(drp_ctx* c, int B, const uint16_t* depth, int h, int w, double global_scale, const double cam[4],
+                           const double T_cam[16], int T, const int32_t* n_ptcl, const float* particles, const double* radius,
+                           const int32_t* init_idx, const int32_t* n_fg_host, const double* push, const int32_t* episode,
+                           int n_cap, float* states_out, float* sdelta_out, int32_t* counts_out, int* n_max_out) {
+    if (!c || !depth || !cam || !T_cam || !n_ptcl || !particles || !radius || !init_idx || !n_fg_host || !push || !states_out ||
+        !sdelta_out || !counts_out || !n_max_out)
+        return fail(c, DRP_EINVAL, "null argument");
+    if (B < 1 || B > PD_BMAX) return fail(c, DRP_EINVAL, "batch %d outside 1..%d", B, PD_BMAX);
+    if (h <= 0 || w <= 0 || (size_t)h * w > (1u << 26)) return fail(c, DRP_EINVAL, "bad image size %d x %d", h, w);
+    if (T < 2) return fail(c, DRP_EINVAL, "a sample needs at least 2 frames (n_his + n_rollout), got %d", T);
+    if (!(global_scale > 0.0)) return fail(c, DRP_EINVAL, "bad global_scale %g", global_scale);
+    if (n_cap < 1) return fail(c, DRP_EINVAL, "bad output capacity %d", n_cap);
+    size_t ptcl_floats = 0, fg_total = 0;
+    std::vector<long long> ptcl_off(B);
+    for (int b = 0; b < B; ++b) {
+        if (n_ptcl[b] <= 0) return fail(c, DRP_EINVAL, "episode %d: %d particles in its files", pd_name(episode, b), n_ptcl[b]);
+        if (init_idx[b] < 0) return fail(c, DRP_EINVAL, "episode %d: sampler start %d", pd_name(episode, b), init_idx[b]);
+        if (!(radius[b] > 0.0) || !std::isfinite(radius[b]))
+            return fail(c, DRP_EINVAL, "episode %d: bad fps radius %g", pd_name(episode, b), radius[b]);
+        for (int t = 0; t + 1 < T; ++t) {
+            const double* pu = push + ((size_t)b * (T - 1) + t) * PD_PUSH;
+            // dataset_gnn_dyn.py:148-153: a zero-length push divides by zero, a push off the table plane exits
+            if (!(pu[9] > 0.0) || !std::isfinite(pu[9]))
+                return fail(c, DRP_EINVAL, "episode %d: push %d has length %g", pd_name(episode, b), t, pu[9]);
+            if (!(std::fabs(pu[8]) < 1e-6))
+                return fail(c, DRP_EINVAL, "episode %d: push %d leaves the table plane (|push_dir_cam z| = %g >= 1e-6)",
+                            pd_name(episode, b), t, std::fabs(pu[8]));
+        }
+        if (n_fg_host[b] < 0 || (size_t)n_fg_host[b] > (size_t)h * w)
+            return fail(c, DRP_EINVAL, "episode %d: host foreground count %d", pd_name(episode, b), n_fg_host[b]);
+        fg_total += (size_t)n_fg_host[b];
+        ptcl_off[b] = (long long)ptcl_floats;
+        ptcl_floats += (size_t)T * n_ptcl[b] * 4;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    if (c->pd_pin) CHK(guarded_wait(c, nullptr));     // a call that failed before its wait may still copy from the staging
+    for (int e = 0; e < PD_NEV; ++e)
+        if (!c->pd_ev[e]) HIPCHK(c, hipEventCreate(&c->pd_ev[e]));
+    c->pd_timed = false;
+    const size_t npix = (size_t)h * w;
+    const PdLayout L = pd_layout(B, npix, ptcl_floats, T);
+    const size_t meta_bytes = (size_t)2 * B * sizeof(int);
+    CHK(pd_pin_ensure(c, std::max(L.bytes, meta_bytes)));
+    char* pin = static_cast<char*>(c->pd_pin);
+    memcpy(pin + L.depth, depth, (size_t)B * npix * sizeof(uint16_t));
+    memcpy(pin + L.ptcl, particles, ptcl_floats * sizeof(float));
+    memcpy(pin + L.radius, radius, (size_t)B * sizeof(double));
+    memcpy(pin + L.push, push, (size_t)B * (T - 1) * PD_PUSH * sizeof(double));
+    memcpy(pin + L.init, init_idx, (size_t)B * sizeof(int));
+    memcpy(pin + L.nptcl, n_ptcl, (size_t)B * sizeof(int));
+    memcpy(pin + L.ptcl_off, ptcl_off.data(), (size_t)B * sizeof(long long));
+    HIPCHK(c, hipEventRecord(c->pd_ev[0], st));
+    CHK(h2d(c, c->pd_in, pin, L.bytes));
+    HIPCHK(c, hipEventRecord(c->pd_ev[1], st));
+    const char* in = static_cast<const char*>(c->pd_in.p);
+    const uint16_t* d_depth = reinterpret_cast<const uint16_t*>(in + L.depth);
+    const float* d_ptcl = reinterpret_cast<const float*>(in + L.ptcl);
+    const double* d_radius = reinterpret_cast<const double*>(in + L.radius);
+    const double* d_push = reinterpret_cast<const double*>(in + L.push);
+    const int* d_init = reinterpret_cast<const int*>(in + L.init);
+    const int* d_nptcl = reinterpret_cast<const int*>(in + L.nptcl);
+    const long long* d_poff = reinterpret_cast<const long long*>(in + L.ptcl_off);
+    PdCam pc;
+    for (int i = 0; i < 16; ++i) pc.M[i] = T_cam[i];
+    pc.gs = global_scale;
+    pc.fx = cam[0]; pc.fy = cam[1]; pc.cx = cam[2]; pc.cy = cam[3];
+
+    // 1. depth -> clouds: tile counts, one scan over all images' tiles, compaction
+    const int nblk = px_nblk(npix);
+    const size_t ntile = (size_t)B * nblk;
+    CHK(ensure(c, c->pd_blk, (2 * ntile + 2) * sizeof(unsigned long long)));
+    unsigned long long* cnt = ptr<unsigned long long>(c->pd_blk);
+    unsigned long long* off = cnt + ntile;
+    CHK(ensure(c, c->pd_meta, (size_t)B * (2 * sizeof(int) + sizeof(long long))));
+    long long* d_pcd_off = ptr<long long>(c->pd_meta);
+    int* d_nfg = reinterpret_cast<int*>(d_pcd_off + B);
+    int* d_counts = d_nfg + B;
+    // sized by the host's counts; the kernels write and read nothing beyond them if the device disagrees (an error below)
+    const long long pcd_cap = (long long)std::max(fg_total, (size_t)1);
+    CHK(ensure(c, c->pd_pcd, (size_t)pcd_cap * 3 * sizeof(double)));
+    CHK(ensure(c, c->pd_dist, (size_t)pcd_cap * sizeof(double)));
+    hipLaunchKernelGGL(k_pd_count, dim3(nblk, B), dim3(PX_BLOCK), 0, st, d_depth, npix, global_scale * 1000.0, cnt);
+    hipLaunchKernelGGL(k_px_scan_u64, dim3(1), dim3(1024), 0, st, cnt, (int)ntile, off);
+    hipLaunchKernelGGL(k_pd_compact, dim3(nblk, B), dim3(PX_BLOCK), 0, st, d_depth, npix, w, pc, off, pcd_cap, ptr<double>(c->pd_pcd));
+    hipLaunchKernelGGL(k_pd_meta, dim3((B + 255) / 256), dim3(256), 0, st, off, nblk, B, d_nfg, d_pcd_off);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->pd_ev[2], st));
+
+    // 2. fps_rad, one workgroup per sample
+    const int cap = PD_CAP + 1;
+    CHK(ensure(c, c->pd_chosen, (size_t)B * cap * sizeof(int)));
+    hipLaunchKernelGGL(k_pd_fps_rad, dim3(B), dim3(1024), 0, st, ptr<double>(c->pd_pcd), pcd_cap, d_pcd_off, d_nfg, d_init,
+                       d_radius, cap, ptr<double>(c->pd_dist), ptr<int>(c->pd_chosen), d_counts);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->pd_ev[3], st));
+    // the one wait before the download: foreground and particle counts size the rest
+    CHK(d2h(c, pin, d_nfg, meta_bytes));
+    CHK(guarded_wait(c, nullptr));
+    const int* nfg = reinterpret_cast<const int*>(pin);
+    const int* counts = nfg + B;
+    c->pd_lastB = B;
+    c->pd_nmax = 0;
+    for (int b = 0; b < B; ++b) {
+        if (nfg[b] == 0) return fail(c, DRP_EINVAL, "episode %d: the depth image has no foreground pixel", pd_name(episode, b));
+        if (n_fg_host && n_fg_host[b] != nfg[b])
+            return fail(c, DRP_EINVAL, "episode %d: %d foreground pixels on the host, %d on the device", pd_name(episode, b),
+                        n_fg_host[b], nfg[b]);
+        if (init_idx[b] >= nfg[b])
+            return fail(c, DRP_EINVAL, "episode %d: sampler start %d outside the cloud of %d points", pd_name(episode, b),
+                        init_idx[b], nfg[b]);
+        if (counts[b] > PD_CAP)
+            return fail(c, DRP_EINVAL, "episode %d: fps_rad reached the cap of %d particles (radius %g)", pd_name(episode, b),
+                        PD_CAP, radius[b]);
+    }
+    int n_max = 0;
+    for (int b = 0; b < B; ++b) { counts_out[b] = counts[b]; n_max = std::max(n_max, counts[b]); }
+    if (n_max > n_cap) return fail(c, DRP_EINVAL, "the batch needs %d particle slots, the outputs hold %d", n_max, n_cap);
+    *n_max_out = n_max;
+    c->pd_nmax = n_max;
+
+    // 3. recenter (float64)
+    CHK(ensure(c, c->pd_rec, (size_t)B * n_max * 3 * sizeof(double)));
+    hipLaunchKernelGGL(k_pd_recenter, dim3((B * n_max + 3) / 4), dim3(256), 0, st, ptr<double>(c->pd_pcd), d_pcd_off, d_nfg,
+                       ptr<int>(c->pd_chosen), cap, d_counts, d_radius, n_max, B, ptr<double>(c->pd_rec));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->pd_ev[4], st));
+
+    // 4. track and pack
+    const size_t n_states = (size_t)B * T * n_max * 3, n_sdelta = (size_t)B * (T - 1) * n_max * 3;
+    CHK(ensure(c, c->pd_near, (size_t)B * n_max * sizeof(int)));
+    CHK(ensure(c, c->pd_out, (n_states + n_sdelta) * sizeof(float)));
+    const unsigned jb = (unsigned)((n_max + 255) / 256);
+    hipLaunchKernelGGL(k_pd_nearest, dim3(jb, B), dim3(256), 0, st, ptr<double>(c->pd_rec), d_counts, n_max, d_ptcl, d_poff,
+                       d_nptcl, pc, ptr<int>(c->pd_near));
+    hipLaunchKernelGGL(k_pd_pack, dim3(jb, T, B), dim3(256), 0, st, ptr<int>(c->pd_near), d_counts, n_max, T, d_ptcl, d_poff,
+                       d_nptcl, d_push, pc, ptr<float>(c->pd_out), ptr<float>(c->pd_out) + n_states);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->pd_ev[5], st));
+
+    // 5. one download through the pinned staging
+    CHK(pd_pin_ensure(c, (n_states + n_sdelta) * sizeof(float)));
+    CHK(d2h(c, c->pd_pin, c->pd_out.p, (n_states + n_sdelta) * sizeof(float)));
+    HIPCHK(c, hipEventRecord(c->pd_ev[6], st));
+    CHK(guarded_wait(c, nullptr));
+    const float* res = static_cast<const float*>(c->pd_pin);
+    memcpy(states_out, res, n_states * sizeof(float));
+    memcpy(sdelta_out, res + n_states, n_sdelta * sizeof(float));
+    c->pd_timed = true;
+    return DRP_OK;
+}
+
+int drp_ptcl_dataset_time(drp_ctx* c, float* ms_out) {
+    if (!c || !ms_out) return fail(c, DRP_EINVAL, "null argument");
+    if (!c->pd_timed) return fail(c, DRP_ESTATE, "no drp_ptcl_dataset_batch has completed");
+    for (int e = 0; e + 1 < PD_NEV; ++e)
+        if (hipEventElapsedTime(&ms_out[e], c->pd_ev[e], c->pd_ev[e + 1]) != hipSuccess)
+            return fail(c, DRP_EHIP, "hipEventElapsedTime failed");
+    return DRP_OK;
+}

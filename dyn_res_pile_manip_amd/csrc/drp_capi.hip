@@ -44,6 +44,7 @@
 #include "k_rollout.h"
 #include "k_rgr.h"
 #include "k_rgr_bwd.h"
+#include "k_ptcl_dataset.h"
 #include "k_prop_inst.h"       // km_prop / km_prop3 / km_rollout: declared here, instantiated in inst_*.hip
 
 #include "capi_ctx.h"
@@ -59,6 +60,7 @@ extern "C" {
 #include "capi_comm.h"
 #include "capi_rgr.h"
 #include "capi_rgr_train.h"
+#include "capi_ptcl_dataset.h"
 #include "capi_debug.h"
 
 }  // extern "C"

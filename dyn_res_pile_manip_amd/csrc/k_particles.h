@@ -453,13 +453,13 @@ k_px_recenter(const double* __restrict__ pcd, int m, const float* __restrict__ s
 
 // utils.py:438-449 fps_rad: farthest-point sampling of a float64 cloud until every point is within
 // `radius` of a sample (the dataset's particle sampler, dataset/dataset_gnn_dyn.py:99).  One
-// workgroup; distances as np.linalg.norm evaluates them in float64, first maximum as np.argmax.
-__global__ void __launch_bounds__(1024)
-k_px_fps_rad(const double* __restrict__ pcd, int n, double radius, int init_idx, int cap, double* __restrict__ dist,
-             int* __restrict__ chosen, int* __restrict__ count_out) {
-    __shared__ double sval[16];
-    __shared__ int sidx[16];
-    __shared__ int s_last;
+// workgroup of 1024 threads; distances as np.linalg.norm evaluates them in float64, first maximum as
+// np.argmax.  Shared by k_px_fps_rad (one cloud) and k_pd_fps_rad (k_ptcl_dataset.h: one cloud per
+// workgroup); the caller owns the shared arrays.
+__device__ __forceinline__ void px_fps_rad_body(const double* __restrict__ pcd, int n, double radius, int init_idx, int cap,
+                                                double* __restrict__ dist, int* __restrict__ chosen,
+                                                int* __restrict__ count_out, double* sval, int* sidx, int* s_last_p) {
+    int& s_last = *s_last_p;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int last = init_idx, count = 1;
     if (tid == 0) chosen[0] = init_idx;
@@ -497,4 +497,13 @@ k_px_fps_rad(const double* __restrict__ pcd, int n, double radius, int init_idx,
         ++count;
     }
     if (tid == 0) *count_out = count;
+}
+
+__global__ void __launch_bounds__(1024)
+k_px_fps_rad(const double* __restrict__ pcd, int n, double radius, int init_idx, int cap, double* __restrict__ dist,
+             int* __restrict__ chosen, int* __restrict__ count_out) {
+    __shared__ double sval[16];
+    __shared__ int sidx[16];
+    __shared__ int s_last;
+    px_fps_rad_body(pcd, n, radius, init_idx, cap, dist, chosen, count_out, sval, sidx, &s_last);
 }

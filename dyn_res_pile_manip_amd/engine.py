@@ -539,6 +539,62 @@ class Engine(object):
                                        ctypes.byref(nd)))
         return out, r, (nfg.value, nd.value)
 
+    # ---- GNN training batches from recorded episodes (row x4) ------------
+    def ptcl_dataset_batch(self, depth, global_scale, cam_params, T_cam, particles, radius, init_idx, n_fg, push,
+                           episode=None, n_cap=L.PD_CAP):
+        """ParticleDataset.__getitem__ for B samples on the device, collated (drp_ptcl_dataset_batch).
+        depth [B,h,w] uint16; T_cam [4,4] = inv(opencv_T_world); particles: B arrays [T,n_ptcl_b,4] float32; radius [B]
+        = 1/sqrt(den); init_idx [B]; n_fg [B] host foreground counts; push [B,T-1,10] float64.
+        -> (states [B,T,n_max,3] f32, states_delta [B,T-1,n_max,3] f32, counts [B] int32)"""
+        depth = np.ascontiguousarray(depth, dtype=np.uint16)
+        B, h, w = depth.shape
+        parts = [np.ascontiguousarray(p, dtype=np.float32) for p in particles]
+        if len(parts) != B:
+            raise ValueError('%d particle arrays for %d depth images' % (len(parts), B))
+        T = parts[0].shape[0]
+        for p in parts:
+            if p.ndim != 3 or p.shape[0] != T or p.shape[2] != 4:
+                raise ValueError('particles must be [T, n, 4] with one T for the batch, got %s' % (p.shape,))
+        n_ptcl = np.array([p.shape[1] for p in parts], np.int32)
+        flat = np.concatenate([p.ravel() for p in parts]) if B > 1 else parts[0].ravel()
+        push = _f64(push)
+        if push.shape != (B, T - 1, 10):
+            raise ValueError('push must be [B, T-1, 10] = %s, got %s' % ((B, T - 1, 10), push.shape))
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        radius, init, nfg = _f64(radius).reshape(B), i32(init_idx).reshape(B), i32(n_fg).reshape(B)
+        ep = None if episode is None else i32(episode).reshape(B)
+        Tm, cam = _f64(T_cam).reshape(16), _f64(cam_params).reshape(4)
+        n_cap = int(n_cap)
+        # np.empty: only the pages the call writes (B * T * n_max * 3 floats) are ever touched
+        states = np.empty((B * T * n_cap * 3,), np.float32)
+        sdelta = np.empty((B * (T - 1) * n_cap * 3,), np.float32)
+        counts = np.empty((B,), np.int32)
+        n_max = ctypes.c_int()
+        self._ck(self.lib.drp_ptcl_dataset_batch(
+            self.h, B, depth.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)), h, w, float(global_scale), _dp(cam), _dp(Tm),
+            T, ip(n_ptcl), _fp(flat), _dp(radius), ip(init), ip(nfg), _dp(push), None if ep is None else ip(ep), n_cap,
+            _fp(states), _fp(sdelta), ip(counts), ctypes.byref(n_max)))
+        nm = n_max.value
+        self._pd_shape = (B, nm)
+        return (states[:B * T * nm * 3].reshape(B, T, nm, 3), sdelta[:B * (T - 1) * nm * 3].reshape(B, T - 1, nm, 3),
+                counts)
+
+    def ptcl_dataset_time(self):
+        """device ms of the last ptcl_dataset_batch by stage: {'upload', 'compaction', 'fps_rad', 'recenter', 'track_pack',
+        'download'}"""
+        ms = np.empty((6,), np.float32)
+        self._ck(self.lib.drp_ptcl_dataset_time(self.h, _fp(ms)))
+        return dict(zip(('upload', 'compaction', 'fps_rad', 'recenter', 'track_pack', 'download'), ms.tolist()))
+
+    def ptcl_dataset_tap(self, name):
+        """intermediates of the last ptcl_dataset_batch: 'nfg' [B], 'chosen' [B,4097], 'recenter' [B,n_max,3] float64,
+        'nearest' [B,n_max]"""
+        B, nm = getattr(self, '_pd_shape', (0, 0))
+        shape, dt = {'nfg': ((B,), np.int32), 'chosen': ((B, L.PD_CAP + 1), np.int32),
+                     'recenter': ((B, nm, 3), np.float64), 'nearest': ((B, nm), np.int32)}[name]
+        return self.debug_fetch('pd_' + name, shape, dt)
+
     # ---- gradient-descent planner ---------------------------------------
     def gd_begin(self, s0, attr, dens, actions, lr, act_lo, act_hi):
         s0, attr, dens, actions = _f32(s0), _f32(attr), _f32(dens), _f32(actions)

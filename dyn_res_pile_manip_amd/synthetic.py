@@ -187,6 +187,13 @@ def render_depth(n_granules=1500, seed=0, kind='blob', size=SCREEN, grain=0.006,
     cx_w, cy_w = s[0, :, 0].astype(np.float64), s[0, :, 1].astype(np.float64)
     layer = (rng.uniform(0, 1, n_granules) < 0.2).astype(np.float64)
     zc = 0.75 - grain - layer * 1.6 * grain
+    return render_granules(cx_w, cy_w, zc, size=size, grain=grain, global_scale=global_scale, cam_params=cam_params)
+
+
+def render_granules(cx_w, cy_w, zc, size=SCREEN, grain=0.006, global_scale=GLOBAL_SCALE, cam_params=None):
+    """render_depth's image of given granules: centres (cx_w, cy_w, zc) in the camera frame, spheres of radius `grain`
+    over the table plane z = 0.75 -> obs [size,size,5] float32 (colour, alpha, depth in world units)."""
+    n_granules = len(cx_w)
     fx, fy, cx, cy = cam_params if cam_params is not None else demo_cam_params()
     depth = np.full((size, size), 0.75, dtype=np.float64)
     pr = int(np.ceil(fx * grain / 0.7)) + 1
@@ -314,3 +321,64 @@ def pushes_through(s, seed=0):
         acts[b, :2] = aim + 3.0 * d
         acts[b, 2:] = aim - rng.uniform(0.3, 2.0) * d
     return np.clip(acts, lo, hi).astype(np.float32)
+
+
+def _cam_to_world(p):
+    """camera frame of the demo camera -> FleX's world frame (inverse of planners.py:192-209 with it): x = X/24, y = Z/24,
+    z = (18 - Y)/24"""
+    return np.stack([p[:, 0] * GLOBAL_SCALE, 18.0 - p[:, 2] * GLOBAL_SCALE, p[:, 1] * GLOBAL_SCALE], axis=1)
+
+
+def write_episodes(root, n_episode, n_timestep, seed=0, n_granules=1500, grain=0.006):
+    """Recorded episodes in the layout of data_gen/gnn_dyn_data.py:67-109 for the demo camera: root/<episode>/ holds
+    `%d_depth.png` (16-bit, world depth x 1000), `%d_color.png` (RGB, white beyond the table's depth), `%d_particles.npy`
+    (float32 [Ng,4] in FleX's world frame, column 3 = 1) for frames 0..n_timestep, and `actions.p` (pickled float64
+    [n_timestep,4] pushes sx, sy, ex, ey).  The motion is push_episode's analytic stand-in (granules inside the pusher's
+    band advance to the push end, then overlaps relax); each depth image is rendered from the same granules.  Only
+    correctly rounded arithmetic (no vectorised transcendental): the files are byte-identical on any machine."""
+    import math
+    import os
+    import pickle
+    from PIL import Image
+    T_w = 0.8 / 24.0
+    for e in range(int(n_episode)):
+        rng = np.random.default_rng(12000 + 97 * int(seed) + e)
+        kind = 'blob' if e % 2 == 0 else 'uniform'
+        s, _, _ = make_pile(n_granules, 1, seed=12000 + 97 * int(seed) + e, kind=kind)
+        xy = s[0, :, :2].astype(np.float64) * (0.6 if kind == 'uniform' else 1.0)
+        layer = (rng.uniform(0, 1, n_granules) < 0.2).astype(np.float64)
+        zc = 0.75 - grain - layer * 1.6 * grain
+        d = os.path.join(root, '%d' % e)
+        os.makedirs(d, exist_ok=True)
+        actions = np.zeros((int(n_timestep), 4))
+        for t in range(int(n_timestep) + 1):
+            obs = render_granules(xy[:, 0], xy[:, 1], zc, grain=grain)
+            img = obs[..., :3].copy()
+            img[obs[..., -1] > 0.599 / 0.8 * GLOBAL_SCALE] = 255.0
+            Image.fromarray(img.astype(np.uint8)).save(os.path.join(d, '%d_color.png' % t))
+            Image.fromarray((obs[..., -1] * 1000).astype(np.uint16)).save(os.path.join(d, '%d_depth.png' % t))
+            cam = np.stack([xy[:, 0], xy[:, 1], zc], axis=1)
+            ptcl = np.ones((n_granules, 4), np.float32)
+            ptcl[:, :3] = _cam_to_world(cam)
+            np.save(os.path.join(d, '%d_particles.npy' % t), ptcl)
+            if t == n_timestep:
+                break
+            ang = rng.uniform(0, 2 * np.pi)
+            c, sn = math.cos(ang), math.sin(ang)
+            aim = xy[rng.integers(n_granules)] * [GLOBAL_SCALE, -GLOBAL_SCALE] + rng.uniform(-0.3, 0.3, 2)
+            start = np.clip(aim + 3.0 * np.array([c, sn]), -WKSPC_W, WKSPC_W)
+            end = np.clip(aim - rng.uniform(0.3, 2.0) * np.array([c, sn]), -0.7 * WKSPC_W, 0.7 * WKSPC_W)
+            actions[t] = [start[0], start[1], end[0], end[1]]
+            # push (x, y) -> camera (x / 24, -y / 24): granules in the band of half-width 0.8/24 advance to the end
+            sc, ec = start * [1.0, -1.0] / GLOBAL_SCALE, end * [1.0, -1.0] / GLOBAL_SCALE
+            dv = ec - sc
+            length = math.sqrt(dv[0] * dv[0] + dv[1] * dv[1])
+            dirn = dv / length
+            rel = xy - sc[None]
+            u = rel[:, 0] * dirn[0] + rel[:, 1] * dirn[1]
+            v = rel[:, 1] * dirn[0] - rel[:, 0] * dirn[1]
+            band = (u > 0.0) & (u < length) & (np.abs(v) < T_w)
+            xy = xy + ((length - u) * band)[:, None] * dirn[None]
+            xy = _relax_overlaps(xy, 1.6 * grain, iters=3)
+        with open(os.path.join(d, 'actions.p'), 'wb') as fp:
+            pickle.dump(actions, fp)

@@ -4,12 +4,16 @@
   DeviceAdam(model, lr, betas)         :128-131 torch.optim.Adam(model.parameters(), ...) on the device
   run_batch(model, optimizer, data, phase)      :159-210 the loop body for one batch
   train(config, datasets, ...)         :134-246 epochs over 'train' / 'valid' phases, best-model tracking
+  main(config, data_root, train_dir)   :45-130,196-228 the file-level part: seed, log dir, datasets and loaders
+                                       (dataset_gnn_dyn.py), checkpoints, resume; `python -m dyn_res_pile_manip_amd.train_gnn_dyn`
 
 The forward, the loss, the backward pass (state and weight gradients) and the Adam update run
 in `drp_train_step` on the MI355X; nothing here computes on the host.  Data loading
 (`dataset/dataset_gnn_dyn.py`: depth PNGs, pickled actions) is outside the path: `datasets`
 is any pair of iterables of samples shaped like `ParticleDataset.__getitem__`'s return.
 """
+import os
+
 import numpy as np
 
 
@@ -94,16 +98,18 @@ class AverageMeter(object):
         self.avg = self.sum / self.count
 
 
-def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None):
+def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=None, first_epoch=0):
     """train/train_gnn_dyn.py:134-246 without the file I/O: `dataloaders` = {'train': iterable of
-    collated batches, 'valid': ...}.  Returns {'best_valid_loss', 'history': [(epoch, phase, rmse)]}."""
+    collated batches, 'valid': ...}.  Returns {'best_valid_loss', 'history': [(epoch, phase, rmse)]}.
+    ckp(epoch, i, model): called after training batch i when i % ckp_per_iter == 0 (:217-218); first_epoch: the epoch
+    a resumed run starts from (:136)."""
     tc = config['train']
     n_rollout = tc['n_rollout']
     assert tc['n_history'] == 1
     optimizer = DeviceAdam(model, float(tc['lr']), betas=(tc['adam_beta1'], 0.999), n_rollout=n_rollout)
     best_valid_loss = np.inf
     history = []
-    for epoch in range(n_epoch if n_epoch is not None else tc['n_epoch']):
+    for epoch in range(int(first_epoch), n_epoch if n_epoch is not None else tc['n_epoch']):
         for phase in ('train', 'valid'):
             model.train(phase == 'train')
             meter = AverageMeter()
@@ -113,9 +119,115 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None):
                 if log is not None and i % tc['log_per_iter'] == 0:
                     log('%s [%d][%d] LR: %.6f, Loss: %.6f (%.6f)' % (phase, epoch, i, optimizer.param_groups[0]['lr'],
                                                                       np.sqrt(loss), np.sqrt(meter.avg)))
+                if ckp is not None and phase == 'train' and i % tc['ckp_per_iter'] == 0:
+                    ckp(epoch, i, model)
             history.append((epoch, phase, float(np.sqrt(meter.avg))))
             if phase == 'valid' and meter.avg < best_valid_loss:
                 best_valid_loss = meter.avg
                 if on_best is not None:
                     on_best(model.state_dict())           # torch.save(model.state_dict(), net_best.pth), :244
     return {'best_valid_loss': float(best_valid_loss), 'history': history}
+
+
+def default_config():
+    """config/train/gnn_dyn.yaml, the keys main() reads"""
+    return {
+        'dataset': {'global_scale': 24, 'n_episode': 2000, 'n_timestep': 10},
+        'train': {'data_root': 'data/gnn_dyn_data', 'random_seed': 42, 'n_epoch': 2000, 'lr': 0.001, 'adam_beta1': 0.9,
+                  'batch_size': 4, 'nf_hidden': 64, 'num_workers': 5, 'train_valid_ratio': 0.9, 'log_per_iter': 50,
+                  'ckp_per_iter': 1000, 'n_history': 1, 'n_rollout': 5,
+                  'particle': {'nf_effect': 64, 'resume': {'active': False, 'epoch': 0, 'iter': 0, 'folder': 'None'},
+                               'adj_thresh': 0.08, 'add_delta': False}},
+    }
+
+
+def set_seed(seed):
+    """utils.py:195-201"""
+    import random
+    import torch
+    torch.manual_seed(seed)
+    np.random.seed(seed)
+    random.seed(seed)
+
+
+def main(config, data_root=None, train_dir=None, cam=None, chunk=64, threads=8, n_epoch=None, engine=None):
+    """The file-level part of train/train_gnn_dyn.py:train() (:45-130, :196-228): seed, the log directory with config.yaml
+    and log.txt, the 'train' / 'valid' ParticleDatasets and their DeviceLoaders, a fresh model (torch.nn.Linear's default
+    initialisation) or the resumed checkpoint, net_epoch_%d_iter_%d.pth every ckp_per_iter training batches and
+    net_best.pth, all in the state_dict layout PropNetDiffDenModel.load_state_dict reads.  cam = (cam_params,
+    cam_extrinsic), by default the demo camera (synthetic.py; FleX is not available).  Returns train()'s result and
+    the directory."""
+    import time
+    import yaml
+    from . import synthetic, weights
+    from .dataset_gnn_dyn import DeviceLoader, ParticleDataset
+    from .gnn_dyn import PropNetDiffDenModel
+    tc = config['train']
+    resume = tc['particle'].get('resume', {'active': False, 'epoch': 0, 'iter': 0})
+    if cam is None:
+        cam = (synthetic.demo_cam_params(), synthetic.demo_cam_extrinsics())
+    set_seed(tc['random_seed'])
+    if train_dir is None:
+        root = 'data/gnn_dyn_model'
+        train_dir = os.path.join(root, resume['folder'] if resume['active'] else time.strftime('%Y-%m-%d-%H-%M-%S'))
+    os.makedirs(train_dir, exist_ok=True)
+    with open(os.path.join(train_dir, 'config.yaml'), 'w') as f:
+        yaml.safe_dump(config, f)
+    log_name = 'log.txt' if not resume['active'] else 'log_resume_epoch_%d_iter_%d.txt' % (resume['epoch'], resume['iter'])
+    data_root = data_root if data_root is not None else tc['data_root']
+    datasets = {ph: ParticleDataset(data_root, config, ph, cam, engine=engine) for ph in ('train', 'valid')}
+    loaders = {ph: DeviceLoader(datasets[ph], tc['batch_size'], shuffle=(ph == 'train'), chunk=chunk, threads=threads)
+               for ph in ('train', 'valid')}
+    model = PropNetDiffDenModel(config, engine=engine)
+    if resume['active']:
+        path = os.path.join(train_dir, 'net_epoch_%d_iter_%d.pth' % (resume['epoch'], resume['iter']))
+        model.load_state_dict(weights.state_dict_from_blob(weights.load_checkpoint(path)))
+    else:
+        model.load_state_dict(weights.random_state_dict(seed=tc['random_seed'], predictor_scale=1.0))
+    with open(os.path.join(train_dir, log_name), 'w') as log_fout:
+        def log(line):
+            print(line)
+            log_fout.write(line + '\n')
+            log_fout.flush()
+
+        def ckp(epoch, i, m):
+            weights.save_checkpoint(m.state_dict(), os.path.join(train_dir, 'net_epoch_%d_iter_%d.pth' % (epoch, i)))
+
+        def on_best(sd):
+            weights.save_checkpoint(sd, os.path.join(train_dir, 'net_best.pth'))
+
+        result = train(config, model, loaders, n_epoch=n_epoch, log=log, on_best=on_best, ckp=ckp,
+                       first_epoch=resume['epoch'] if resume['active'] and resume['epoch'] > 0 else 0)
+        for epoch, phase, rmse in result['history']:
+            log('%s [%d] Loss: %.6f' % (phase, epoch, rmse))
+    return result, train_dir
+
+
+def _cli(argv=None):
+    import argparse
+    import yaml
+    ap = argparse.ArgumentParser(description='Train the particle dynamics model on recorded episodes (device data path '
+                                             'and device trainer).')
+    ap.add_argument('--config', help='config/train/gnn_dyn.yaml-style file (default: the reference\'s values)')
+    ap.add_argument('--data-root', help='episode directory (default: train.data_root)')
+    ap.add_argument('--train-dir', help='output directory (default: data/gnn_dyn_model/<time>)')
+    ap.add_argument('--n-episode', type=int, help='override dataset.n_episode')
+    ap.add_argument('--n-timestep', type=int, help='override dataset.n_timestep')
+    ap.add_argument('--epochs', type=int, help='override train.n_epoch')
+    ap.add_argument('--chunk', type=int, default=64, help='samples per device call')
+    ap.add_argument('--threads', type=int, default=8, help='decoding threads (at most 16)')
+    a = ap.parse_args(argv)
+    config = default_config()
+    if a.config:
+        with open(a.config) as f:
+            config = yaml.safe_load(f)
+    if a.n_episode is not None:
+        config['dataset']['n_episode'] = a.n_episode
+    if a.n_timestep is not None:
+        config['dataset']['n_timestep'] = a.n_timestep
+    result, d = main(config, a.data_root, a.train_dir, chunk=a.chunk, threads=a.threads, n_epoch=a.epochs)
+    print('best valid loss %.6f, checkpoints in %s' % (np.sqrt(result['best_valid_loss']), d))
+
+
+if __name__ == '__main__':
+    _cli()

@@ -91,3 +91,13 @@ def load_checkpoint(path):
     import torch
     sd = torch.load(path, map_location='cpu')
     return blob_from_state_dict(sd, strict=False)
+
+
+def save_checkpoint(state_dict, path):
+    """torch.save(model.state_dict(), path) (train/train_gnn_dyn.py:217-218, 226): the reference's keys in its order,
+    float32 tensors -- what PropNetDiffDenModel.load_state_dict (here and in the reference) reads back."""
+    import torch
+    from collections import OrderedDict
+    blob = blob_from_state_dict(state_dict)
+    sd = state_dict_from_blob(blob)
+    torch.save(OrderedDict((k, torch.from_numpy(sd[k])) for k, _ in STATE_DICT_KEYS), path)

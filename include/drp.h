@@ -389,6 +389,30 @@ int drp_rgr_get_weights(drp_ctx* ctx, float* blob_out, size_t n_floats);
  * conv backward + Adam over the other parameters (HIP events). */
 int drp_rgr_train_time(drp_ctx* ctx, int B, int iters, float* ms_out);
 
+/* ---- GNN training batches from recorded episodes (row x4) ------------------------- */
+/* ParticleDataset.__getitem__ (dataset/dataset_gnn_dyn.py:86-201) for B samples (1 <= B <= 1024) in one call, collated as
+ * collate_fn (train/train_gnn_dyn.py:20-45) pads them.  Replaces, per sample: the depth PNG / (global_scale * 1000.0) and
+ * depth2fgpcd (:97-98, utils.py:491-506, the float64 rule depth < 0.599/0.8 && depth > 0), fps_rad (:99, utils.py:438-449),
+ * recenter in float64 with r = min(0.02, 0.5 / sqrt(den)) (:101, utils.py:468-477), the KDTree nearest-particle query
+ * (:104-109: brute force in float64, the lowest index on an exact tie), the per-frame gather (:114-118) and the push formula
+ * (:130-194).  Inputs: depth [B][h][w] uint16 (the PNGs as decoded), cam [fx, fy, cx, cy], T_cam = inv(opencv_T_world)
+ * [4][4] row-major (:69-78), T = n_his + n_rollout frames; per sample b: n_ptcl[b] particles per frame, particles = the
+ * samples' frames one after the other, [T][n_ptcl[b]][4] float32 each (FleX's world frame, column 3 ignored), radius[b] =
+ * 1/sqrt(den), init_idx[b] = the sampler's start (numpy's randint(n_fg)), n_fg_host[b] = the foreground count the host drew
+ * it from (the device's must agree), push [B][T-1][10] = s_3d_cam, e_3d_cam, push_dir_cam (unit), push_l in float64 as
+ * :142-147 form them, episode (nullable) = the episode numbers errors name.  Outputs: states [B][T][n_max][3] and
+ * states_delta [B][T-1][n_max][3] float32, zero beyond each count (room for n_cap particle slots), counts_out [B],
+ * *n_max_out.  DRP_EINVAL (the context stays usable) for an empty foreground, a count that disagrees, a zero-length push or
+ * one with |push_dir_cam z| >= 1e-6, a sample that reaches 4096 particles, bad shapes.  Own workspaces: nothing of the
+ * PropNet, training, planning or regressor state is touched.  One wait after the sampler (the counts), one at the end. */
+int drp_ptcl_dataset_batch(drp_ctx* ctx, int B, const uint16_t* depth, int h, int w, double global_scale, const double cam[4],
+                           const double T_cam[16], int T, const int32_t* n_ptcl, const float* particles, const double* radius,
+                           const int32_t* init_idx, const int32_t* n_fg_host, const double* push, const int32_t* episode,
+                           int n_cap, float* states_out, float* sdelta_out, int32_t* counts_out, int* n_max_out);
+/* Device time of the last completed drp_ptcl_dataset_batch by stage (HIP events): ms_out [6] = upload | compaction |
+ * fps_rad | recenter | track + pack | download.  DRP_ESTATE before the first. */
+int drp_ptcl_dataset_time(drp_ctx* ctx, float* ms_out);
+
 /* ---- measurement / debugging ----------------------------------------------------- */
 /* HIP-event timing of one kernel class on the context's stream.  name: "graph",
  * "node_encode", "edge_encode", "project", "aggregate", "update", "predict", "reward",
@@ -427,7 +451,9 @@ int drp_debug_stall(drp_ctx* ctx, int ms);
 /* copy an intermediate device buffer to the host: "s_delta","nbr_idx","nbr_cnt",
  * "particle_encode"(eff0),"c_node","c_edge","proj","agg","effect"; the weight blob "w_raw" and its packed copies
  * "w_valu","w_mfma","w_mfma_bwd","w_split","w_split6"; the resolution regressor's post-activation taps of its last forward
- * "rgr_c1".."rgr_c5" (NHWC [B][H][W][C]) and "rgr_f1".."rgr_f4" ([B][features]) (byte sizes: the returned value). returns bytes. */
+ * "rgr_c1".."rgr_c5" (NHWC [B][H][W][C]) and "rgr_f1".."rgr_f4" ([B][features]); the last drp_ptcl_dataset_batch's
+ * "pd_nfg" ([B] int32), "pd_chosen" ([B][4097] int32), "pd_recenter" ([B][n_max][3] float64), "pd_nearest" ([B][n_max]
+ * int32) (byte sizes: the returned value). returns bytes. */
 long drp_debug_fetch(drp_ctx* ctx, const char* name, void* out, size_t out_bytes);
 
 #ifdef __cplusplus

@@ -1,0 +1,100 @@
+"""Cost of the GNN data path (row x4, drp_ptcl_dataset_batch) on synthetic episodes.
+
+  python tools/dataset_timing.py [--episodes 4] [--threads 8] [--reps 5]
+
+Reports (medians of --reps):
+  - per-stage device time of one call (upload | compaction | fps_rad | recenter | track + pack | download, HIP events) at
+    B = 4 / 64 / 256, particle_den drawn as the reference draws it (uniform 15 .. 6500);
+  - host decoding per sample (depth PNG, particle files, actions.p, push frames) on one thread and on --threads;
+  - DeviceLoader's samples/s at batch 4, chunk 64, against what the device trainer consumes (UPDATE steps at batch 4).
+"""
+import argparse
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--episodes', type=int, default=4)
+    ap.add_argument('--threads', type=int, default=8)
+    ap.add_argument('--reps', type=int, default=5)
+    a = ap.parse_args()
+    import __graft_entry__ as g
+    g.build()
+    from concurrent.futures import ThreadPoolExecutor
+    from dyn_res_pile_manip_amd import synthetic
+    from dyn_res_pile_manip_amd.dataset_gnn_dyn import DeviceLoader, ParticleDataset
+    from dyn_res_pile_manip_amd.engine import Engine
+    from dyn_res_pile_manip_amd.train_gnn_dyn import default_config
+    eng = Engine(0)
+    print('device: %s' % eng.device_info()['name'])
+    cfg = default_config()
+    cfg['dataset'].update(n_episode=a.episodes, n_timestep=10)
+    cfg['train']['train_valid_ratio'] = 1.0
+    with tempfile.TemporaryDirectory() as d:
+        t0 = time.perf_counter()
+        synthetic.write_episodes(d, a.episodes, 10, seed=0)
+        cam = (synthetic.demo_cam_params(), synthetic.demo_cam_extrinsics())
+        ds = ParticleDataset(d, cfg, 'train', cam, engine=eng)
+        print('%d episodes, %d samples (written in %.1f s)' % (a.episodes, len(ds), time.perf_counter() - t0))
+        samples = [ds.load(i) for i in range(len(ds))]
+        print('foreground points per sample: %d .. %d' % (min(s['n_fg'] for s in samples), max(s['n_fg'] for s in samples)))
+        np.random.seed(0)
+        stages = ('upload', 'compaction', 'fps_rad', 'recenter', 'track_pack', 'download')
+        for B in (4, 64, 256):
+            rows, walls, nmax = [], [], []
+            for r in range(a.reps + 1):
+                batch = [samples[(r * B + j) % len(samples)] for j in range(B)]
+                draws = [ds.draw(s) for s in batch]
+                t0 = time.perf_counter()
+                st, _, cnt = ds.run(batch, draws)
+                wall = time.perf_counter() - t0
+                if r == 0:
+                    continue                       # first call: allocations
+                rows.append([ds.engine.ptcl_dataset_time()[k] for k in stages])
+                walls.append(wall * 1e3)
+                nmax.append(int(cnt.max()))
+            med = np.median(np.array(rows), axis=0)
+            print('B=%3d device ms: %s | sum %.2f | call wall %.2f ms | max particles %d' % (
+                B, ' '.join('%s %.3f' % (k, v) for k, v in zip(stages, med)), med.sum(), np.median(walls),
+                max(nmax)))
+        for threads in (1, a.threads):
+            n = 48
+            with ThreadPoolExecutor(max_workers=threads) as pool:
+                t0 = time.perf_counter()
+                list(pool.map(ds.load, [i % len(ds) for i in range(n)]))
+                dt = time.perf_counter() - t0
+            print('host decode: %.2f ms per sample on %d thread(s)' % (dt / n * 1e3, threads))
+        np.random.seed(0)
+        import torch
+        torch.manual_seed(0)
+        loader = DeviceLoader(ds, 4, shuffle=True, chunk=64, threads=a.threads)
+        t0 = time.perf_counter()
+        batches = list(loader)
+        dt = time.perf_counter() - t0
+        print('DeviceLoader batch 4, chunk 64, %d threads: %.0f samples/s' % (a.threads, len(ds) / dt))
+        from dyn_res_pile_manip_amd import weights
+        eng.load_weights(weights.blob_from_state_dict(weights.random_state_dict(seed=0, predictor_scale=1.0)), 0.08)
+        eng.train_begin(5, 1e-3, 0.9)
+        for b in batches[:2]:
+            eng.train_step(*b[:5], mode='update')
+        t0 = time.perf_counter()
+        k = 0
+        for _ in range(5):
+            for b in batches:
+                eng.train_step(*b[:5], mode='update')
+                k += 1
+        dt = time.perf_counter() - t0
+        print('trainer at batch 4: %.2f ms per step = %.0f samples/s' % (dt / k * 1e3, 4 * k / dt))
+    eng.close()
+
+
+if __name__ == '__main__':
+    main()
