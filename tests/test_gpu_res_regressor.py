@@ -115,6 +115,30 @@ def test_forward_taps_against_float64(eng, sds, base_inputs, B):
     assert float(np.abs(out - ref_out).max()) <= 2e-5 * float(np.abs(ref_out).max())
 
 
+def test_forward_layers_componentwise_batch_sweep(eng, sds, blobs, base_inputs):
+    """every tap and the output against float64 on the device's own input to that layer, elementwise to TOL times
+    |W| |A_prev| + |b| (tests/_rgr_train_ref.py: forward_layer_ratios), B from 64 down to 1 in one context, both heads.
+    Measured on the MI355X: <= 2.9e-7 (c2); the CPU float32 stand-in <= 2.1e-7, a conv1 that drops the taps next to the
+    padding 5e-1 (tests/test_rgr_backward_host.py)"""
+    import _rgr_train_ref as R
+    tol = R.CW_TOL
+    worst = {}
+    try:
+        for B, n_out in ((64, 1), (63, 6), (33, 1), (17, 6), (16, 1), (5, 6), (2, 1), (1, 6)):
+            eng.rgr_load(blobs[n_out], n_out)
+            x = batch_of(base_inputs, B)
+            out = eng.rgr_forward(x)
+            r = R.forward_layer_ratios(sds[n_out], x, {t: eng.rgr_tap(t) for t in TAPS}, out)
+            print('[fwd-err] rgr componentwise B=%d n_out=%d: %s' % (
+                B, n_out, ', '.join('%s %.1e' % kv for kv in r.items())))
+            for k, v in r.items():
+                worst[k] = max(worst.get(k, 0.0), v)
+                assert v <= tol, (B, n_out, k, v)
+    finally:
+        eng.rgr_load(blobs[1], 1)
+    print('[fwd-err] rgr componentwise sweep worst: %s' % ', '.join('%s %.1e' % kv for kv in worst.items()))
+
+
 @pytest.mark.parametrize('n_out', [1, 6])
 def test_forward_heads_match_fixture(eng, blobs, base_inputs, z, n_out):
     eng.rgr_load(blobs[n_out], n_out)

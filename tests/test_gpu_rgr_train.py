@@ -211,6 +211,97 @@ def test_gradients_against_float64(eng, z, B):
         assert e <= (TOL_CONV if j < 10 else TOL_FC), (B, k, e)
 
 
+# ---- componentwise against float64 from the device's own activations --------------------------------------------------
+# R.backward64_from_taps restarts the backward in float64 at the device's taps and output, so the masks and dOut are the
+# device's own and only the backward pass's rounding is left; it is held elementwise to TOL_CW times the bound g_abs
+# (tests/_rgr_train_ref.py).  TOL_CW = 1e-5, 17x the worst measured on the MI355X (5.7e-7: the conv5 weight at B = 64; the
+# edge cases <= 1.9e-7) and 80x below the weakest injected fault (8.3e-4: conv1's wgrad without its last split-K slab,
+# tests/test_rgr_backward_host.py, where the CPU float32 stand-in sits at <= 3e-7).
+TOL_CW = R.CW_TOL
+LAM_CW = 5e4
+SWEEP = ((64, 'rgr'), (63, 'cls'), (33, 'rgr'), (17, 'cls'), (16, 'rgr'), (5, 'cls'), (2, 'rgr'), (1, 'cls'))
+
+
+def grad_with_taps(e, batch):
+    """one GRAD step -> (loss triple, gradient state_dict, the step's taps, out of drp_rgr_forward on the same batch); the
+    forward's taps are bit-equal to the step's"""
+    from dyn_res_pile_manip_amd import res_regressor as rr
+    loss, g = step(e, batch, 'grad', want_grad=True)
+    taps = {t: e.rgr_tap(t) for t in R.TAPS}
+    out = e.rgr_forward(batch[0])
+    for t, v in taps.items():
+        np.testing.assert_array_equal(e.rgr_tap(t), v, err_msg=t)
+    return loss, rr.state_dict_from_blob(g, out.shape[1]), taps, out
+
+
+def componentwise(sd, batch, taps, out, g, label):
+    x, y, conf, lab = batch
+    g_ref, g_abs = R.backward64_from_taps(sd, x, taps, out, y=y, conf=conf, label=lab, lam_reg=LAM_CW)
+    r = R.componentwise_ratio(g, g_ref, g_abs)
+    print('[grad-err] rgr componentwise %s: %s' % (label, ', '.join('%s %.1e' % (k[6:], v) for k, v in r.items())))
+    return r, g_ref
+
+
+def test_gradients_componentwise_batch_sweep(eng, z):
+    """B from 64 down to 1 in one context (a stale slab or partial from a larger step would show), both heads"""
+    worst = {}
+    for B, name in SWEEP:
+        n_out = HEADS[name]
+        sd, _ = start(eng, z, n_out, lam=LAM_CW)
+        batch = rand_batch(B, n_out, 300 + B)
+        _, g, taps, out = grad_with_taps(eng, batch)
+        r, _ = componentwise(sd, batch, taps, out, g, '%s B=%d' % (name, B))
+        for k, v in r.items():
+            worst[k] = max(worst.get(k, 0.0), v)
+            assert v <= TOL_CW, (B, name, k, v)
+    print('[grad-err] rgr componentwise sweep worst: %s' % ', '.join('%s %.1e' % (k[6:], v) for k, v in worst.items()))
+
+
+def _edge(name):
+    """(n_out, state_dict, batch) of an edge case"""
+    B = 6
+    if name == 'zero':                  # a conv3 channel and an FC2 row with all-zero weights and bias: post-activation 0
+        return 6, R.zero_units(R.fixture_state_dict(11, 6)), rand_batch(B, 6, 400)
+    if name == 'blank':                 # one sample of x = 0
+        x, y, conf, _ = rand_batch(B, 1, 401)
+        x[2] = 0.0
+        return 1, R.fixture_state_dict(11, 1), (x, y, conf, None)
+    if name == 'saturated':             # head weights scaled until the logits spread by several hundred (in the test)
+        return 6, R.fixture_state_dict(11, 6), (rand_batch(B, 6, 402)[0], None, None, np.arange(B, dtype=np.int32) % 6)
+    x = rand_batch(B + 1, 1, 403)[0]    # 'extreme': conf from 1e-6 to 1, targets far from the output
+    y = np.array([-5e3, 3e4, -2e2, 1e4, 900.0, -7e4, 2e5], np.float32)
+    return 1, R.fixture_state_dict(11, 1), (x, y, np.logspace(-6, 0, B + 1).astype(np.float32), None)
+
+
+@pytest.mark.parametrize('name', ['zero', 'blank', 'saturated', 'extreme'])
+def test_gradients_componentwise_edges(eng, name):
+    from dyn_res_pile_manip_amd import res_regressor as rr
+    n_out, sd, batch = _edge(name)
+    if name == 'saturated':
+        eng.rgr_load(rr.blob_from_state_dict(sd, n_out), n_out)
+        o = eng.rgr_forward(batch[0])
+        sd['model.19.weight'] = sd['model.19.weight'] * np.float32(500.0 / float((o.max(axis=1) - o.min(axis=1)).min()))
+    eng.rgr_load(rr.blob_from_state_dict(sd, n_out), n_out)
+    eng.rgr_train_begin(1e-4, 0.9, LAM_CW)
+    (loss, main, reg), g, taps, out = grad_with_taps(eng, batch)
+    r, g_ref = componentwise(sd, batch, taps, out, g, name)
+    assert max(r.values()) <= TOL_CW, r
+    o = out.astype(np.float64)
+    if n_out == 1:
+        ref = float(np.mean(batch[2].astype(np.float64) * (o[:, 0] - batch[1]) ** 2))
+    else:
+        mx = o.max(axis=1, keepdims=True)
+        ref = float(np.mean(mx[:, 0] + np.log(np.exp(o - mx).sum(axis=1)) - o[np.arange(o.shape[0]), batch[3]]))
+    np.testing.assert_allclose(main, ref, rtol=1e-12)
+    if name == 'zero':                  # the 0.2 rule is visible there: those units still pass a gradient on
+        assert np.abs(taps['c3'][:, R.ZERO_CONV3_CHANNEL]).max() == 0 and np.abs(taps['f2'][:, R.ZERO_FC2_ROW]).max() == 0
+        assert g_ref['model.4.bias'][R.ZERO_CONV3_CHANNEL] != 0 and g_ref['model.13.bias'][R.ZERO_FC2_ROW] != 0
+    if name == 'blank':
+        assert np.all(taps['c1'][2] == taps['c1'][2, :, :1, :1])  # leaky(bias) at every position
+    if name == 'saturated':
+        assert float((o.max(axis=1) - o.min(axis=1)).min()) >= 300.0, o
+
+
 def test_refusals(z):
     from dyn_res_pile_manip_amd import res_regressor as rr
     from dyn_res_pile_manip_amd._lib import DrpError
