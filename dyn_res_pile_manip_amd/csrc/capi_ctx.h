@@ -13,90 +13,13 @@ const char* const kclass_names[KC_COUNT] = {"graph", "node_encode", "edge_encode
                                             "aggregate", "update", "predict", "reward", "mppi", "prop",
                                             "tape_copy", "bwd_reward", "bwd_lists", "bwd_node", "bwd_edge", "bwd_push", "opt"};
 
-// ---- which kernel variant served a launch (drp_last_dispatch) ---------------------------------------------------
-// Every place that chooses between kernels or template instantiations marks the variant it launched in the context; the
-// host asks for the names (drp_last_dispatch) and for the whole list (drp_dispatch_variants).  tests/test_gpu_fuzz_oracle.py
-// draws shapes under the default dispatch, checks each against the oracle and fails if a variant in the list was never hit:
-// a threshold change that orphans an instantiation turns the suite red.
-enum DispatchVariant {
-    DV_GRAPH_PLAIN = 0, DV_GRAPH_Q4, DV_GRAPH_Q4_ENCODE, DV_GRAPH_STRIPS, DV_GRAPH_STRIPS256, DV_GRAPH_CELLS, DV_GRAPH_REV, DV_GRAPH_IN_ROLLOUT,
-    DV_VALU_STEP, DV_NODE_ENCODE, DV_NODE_ENCODE_SPLIT, DV_EDGE_ENCODE, DV_EDGE_ENCODE_SPLIT, DV_AGGREGATE, DV_AGGREGATE_LDS,
-    DV_AGGREGATE_TAPE, DV_UPDATE,
-    DV_PROP,                        // + 8 LAST + 4 TAPE + 2 PAIR + WORK
-    DV_PROP3 = DV_PROP + 16,        // + 12 TAPE + 6 PAIR + 2 cache (0 off, 1 on, 2 on with the rows kept in registers) + WORK
-    DV_ROLLOUT = DV_PROP3 + 24,     // + 6 PAIR + 2 cache + WORK
-    DV_REWARD = DV_ROLLOUT + 12, DV_BWD_REWARD, DV_REV_256, DV_REV_1024, DV_BWD_ROWS, DV_BWD_STEP, DV_BWD_STAGES_MFMA,
-    DV_BWD_EDGE_MFMA, DV_TRAIN_NODE_FUSED, DV_TRAIN_NODE_FUSED_COOP, DV_TRAIN_NODE_MFMA, DV_WGRAD_MFMA, DV_WGRAD_VALU,
-    DV_WGRAD_DEFERRED, DV_MPPI_SOFTMAX, DV_ELITE_SORT, DV_ELITE_ROUNDS, DV_FPS_REG, DV_FPS_MEM, DV_DT_CV5, DV_DT_EXACT,
-    DV_TRAIN_BARRIER_RETRY,
-    DV_COUNT
-};
-// name of variant `id`; *by_default = reachable without an environment switch (DRP_NO_* / drp_probe_begin("prop+work"))
-void dv_name(int id, char* buf, size_t n, bool* by_default) {
-    bool dflt = true;
-    static const char* const cache_names[3] = {"", ",cache", ",cache+rows"};
-    if (id >= DV_PROP && id < DV_PROP3) {
-        const int f = id - DV_PROP;
-        snprintf(buf, n, "km_prop<%s%s%s%s>", (f & 8) ? "last" : "mid", (f & 4) ? ",tape" : "", (f & 2) ? ",pair" : "", (f & 1) ? ",work" : "");
-        dflt = !(f & 1);
-    } else if (id >= DV_PROP3 && id < DV_ROLLOUT) {
-        const int f = id - DV_PROP3;
-        snprintf(buf, n, "km_prop3<%s%s%s%s>", (f / 12) ? "tape" : "plain", ((f / 6) & 1) ? ",pair" : "", cache_names[(f % 6) / 2], (f & 1) ? ",work" : "");
-        // paired tiles mean at most 128 rows per workgroup: the cache always fits and the rows stay in registers, unless
-        // DRP_ECACHE_MAX_MB says otherwise
-        dflt = !(f & 1) && !(((f / 6) & 1) && (f % 6) / 2 != 2);
-    } else if (id >= DV_ROLLOUT && id < DV_REWARD) {
-        const int f = id - DV_ROLLOUT;
-        snprintf(buf, n, "km_rollout<%s%s%s>", (f / 6) ? "pair" : "tile32", cache_names[(f % 6) / 2], (f & 1) ? ",work" : "");
-        dflt = !(f & 1) && !((f / 6) && (f % 6) / 2 != 2);
-    } else {
-        const char* s = "?";
-        switch (id) {
-        case DV_GRAPH_PLAIN: s = "graph:k_graph"; break;
-        case DV_GRAPH_Q4: s = "graph:k_graph_q4"; break;
-        case DV_GRAPH_Q4_ENCODE: s = "graph:km_graph_q4_encode (+ particle encoder)"; break;
-        case DV_GRAPH_STRIPS: s = "graph:k_graph_strips_q<128>"; break;
-        case DV_GRAPH_STRIPS256: s = "graph:k_graph_strips_q<256>"; dflt = false; break;   // from 800 particles, where the cells have taken over (DRP_NO_GRAPH_CELLS=1)
-        case DV_GRAPH_CELLS: s = "graph:k_graph_cells"; break;
-        case DV_GRAPH_REV: s = "graph:k_graph_rev"; break;
-        case DV_GRAPH_IN_ROLLOUT: s = "graph:in km_rollout"; break;
-        case DV_VALU_STEP: s = "valu:k_node_encode..k_predict"; break;
-        case DV_NODE_ENCODE: s = "km_node_encode"; break;
-        case DV_NODE_ENCODE_SPLIT: s = "km_node_encode_split"; break;
-        case DV_EDGE_ENCODE: s = "km_edge_encode"; break;
-        case DV_EDGE_ENCODE_SPLIT: s = "km_edge_encode_split"; break;
-        case DV_AGGREGATE: s = "k_aggregate"; break;
-        case DV_AGGREGATE_LDS: s = "k_aggregate_lds"; break;
-        case DV_AGGREGATE_TAPE: s = "k_aggregate_tape"; break;
-        case DV_UPDATE: s = "km_update"; break;
-        case DV_REWARD: s = "k_reward"; break;
-        case DV_BWD_REWARD: s = "kb_reward"; break;
-        case DV_REV_256: s = "kb_reverse_lists<256>"; break;
-        case DV_REV_1024: s = "kb_reverse_lists<1024>"; break;
-        case DV_BWD_ROWS: s = "bwd:kmb_rows_bwd"; break;
-        case DV_BWD_STEP: s = "bwd:kmb_step_bwd"; break;
-        case DV_BWD_STAGES_MFMA: s = "bwd:stages kmb_*"; break;
-        case DV_BWD_EDGE_MFMA: s = "bwd:kmb_edge_encode"; break;
-        case DV_TRAIN_NODE_FUSED: s = "train:kmb_step_bwd<dump>"; dflt = false; break;    // DRP_TRAIN_COOP=0 (by default a workgroup of the one-launch pass has one tile)
-        case DV_TRAIN_NODE_FUSED_COOP: s = "train:kmb_step_bwd<dump,coop>"; break;
-        case DV_TRAIN_NODE_MFMA: s = "train:stages kmb_*"; break;
-        case DV_WGRAD_MFMA: s = "train:kt_wgrad_mfma"; break;
-        case DV_WGRAD_VALU: s = "train:kt_wgrad"; dflt = false; break;
-        case DV_WGRAD_DEFERRED: s = "train:deferred wgrad lists"; break;
-        case DV_MPPI_SOFTMAX: s = "mppi:k_mppi_partials+update"; break;
-        case DV_ELITE_SORT: s = "mppi:k_elite_local sort"; break;
-        case DV_ELITE_ROUNDS: s = "mppi:k_elite_local rounds"; break;
-        case DV_FPS_REG: s = "k_fps_reg"; break;
-        case DV_FPS_MEM: s = "k_fps"; break;
-        case DV_DT_CV5: s = "k_dt_cv5"; break;
-        case DV_DT_EXACT: s = "k_edt"; break;
-        case DV_TRAIN_BARRIER_RETRY: s = "train:barrier gave up, step re-run with one workgroup per group"; dflt = false; break;   // a shared / masked device
-        default: break;
-        }
-        snprintf(buf, n, "%s", s);
-    }
-    if (by_default) *by_default = dflt;
-}
+// the variant names (DispatchVariant, dv_name), the dispatch policy and the plan functions: host-only, csrc/dispatch.h
+using namespace dispatch;
+static_assert(ENGINE_VALU == DRP_ENGINE_VALU && ENGINE_MFMA == DRP_ENGINE_MFMA && ENGINE_SPLIT == DRP_ENGINE_SPLIT && ENGINE_FUSED == DRP_ENGINE_FUSED &&
+              K == DRP_K && GRAPH_THREADS_ == GRAPH_THREADS && GC_MAX_BANDS_ == GC_MAX_BANDS && GC_THREADS_ == GC_THREADS && PROP_WAVES_ == PROP_WAVES &&
+              EC_UNITS_ == EC_UNITS && ROLLOUT_MAX_ROWS == KM_ROLLOUT_MAX_ROWS && BWD_ROWS_MAX == KMB_ROWS_MAX && COOP_SLOTS == KMB_COOP_SLOTS &&
+              AGG_LDS_MAX_N == K_AGG_LDS_MAX_N && DEG_STAT_ROWS == DEG_STAT_MAX_ROWS && spread_grid(33) == SPREAD_GRID(33),
+              "dispatch.h plans with the kernels' own constants");
 
 struct DevBuf {
     void* p = nullptr;
@@ -209,102 +132,18 @@ struct drp_ctx {
     std::string err;
     int engine = DRP_ENGINE_VALU;
     int n_cu = 256;
-    bool agg_global_only = false;   // always gather sender rows from L2/HBM (timing builds)
-    bool rev_global_only = false;   // DRP_REV_GLOBAL=1: reversed neighbour lists built in global memory (the N > 3072 path)
-    bool self_const = true;         // DRP_NO_SELF_CONST=1: always run the encoder chain on the self slot too
-    bool prop3 = true;              // DRP_NO_PROP3=1: one launch per propagation step even for chip-filling batches
-    int prop3_min_b = 0;            // km_prop3 / kmb_step_bwd from this many samples (0: whole_samples() decides)
-    int prop3_min_tiles = 1;        // km_prop3 from this many tiles per workgroup and step
-    int bwd_fused_min_tiles = 1;    // the same for kmb_step_bwd
-    bool graph_cells = true;        // DRP_NO_GRAPH_CELLS=1: x strips only (k_graph_strips) for large samples
-    int graph_cells_min_n = 400;    // DRP_GRAPH_CELLS_MIN_N: two-dimensional cells from this many particles up (measured: slower at 300, 8 % faster at 450)
-    float graph_cells_halo = 0.0f;  // DRP_GRAPH_CELLS_HALO: first-sweep halo in camera-frame units (default: from the particle count)
-    float graph_cells_hb = 0.0f;    // DRP_GRAPH_CELLS_HB: band height in camera-frame units (default: from the particle count)
-    bool graph_strips = true;       // DRP_NO_GRAPH_STRIPS=1: plain neighbour sweep for every shape
+    DispatchPolicy pol;             // every threshold and switch that decides which kernel runs (dispatch.h; policy_from_env)
     bool comm_always = false;       // DRP_COMM_ALWAYS=1: a one-rank communicator still goes through ncclAllGather (bench.py --force-comm)
-    bool bwd_fused = true;          // DRP_NO_BWD_FUSED=1: the GD planner's backward pass as one launch per stage
-    bool graph_rev = true;          // DRP_NO_GRAPH_REV=1: the GD planner's reversed lists always in a launch of their own (kb_reverse_lists)
-    bool graph_encode = true;       // DRP_NO_GRAPH_ENCODE=1: k_graph_q4 and km_node_encode_split as two launches where they could be one (km_graph_q4_encode)
-    int train_fused = -1;           // DRP_TRAIN_FUSED=0/1: the trainer's node stages as one launch per rollout step (kmb_step_bwd<dump>) never / for any batch (-1: up to n_cu / 4 tiles)
-    int train_coop = -1;            // DRP_TRAIN_COOP=0/1: the workgroup-wide gather of the edge terms off / on whatever the tile count (-1: by tiles per workgroup)
     double* tr_loss_host = nullptr; // drp_train_step: pinned host memory the loss kernel stores its terms to (null: c->tr_loss)
     bool train_copy_upload = false; // DRP_TRAIN_COPY_UPLOAD=1: the training batch goes up by a copy on the stream instead of inside kt_unpack_inputs
     bool debug_force_giveup = false; // DRP_DEBUG_FORCE_GIVEUP=1 (tests): drp_train_step's first pass ends as if kmb_step_bwd's barrier had timed out
-    int train_parts = 0;            // DRP_TRAIN_PARTS=n: workgroups per group of samples in the trainer's kmb_step_bwd (0: as many as there are CUs for)
-    bool bwd_rows = true;           // DRP_NO_BWD_ROWS=1: piles of up to 256 particles through kmb_step_bwd (rows through memory) instead of kmb_rows_bwd
-    bool prop3_order = true;        // false: km_prop3's tiles in the natural row order instead of by in-degree
-    int prop_pair_rows = 128;       // DRP_PROP_PAIR_ROWS: a workgroup of the whole-sample kernels with up to so many rows runs tiles of
-                                    // 16 receivers x two slots (0 = never)
-    int prop_pair_always = 64;      // DRP_PROP_PAIR_ALWAYS: ... whatever the in-degrees up to so many rows (four tiles of 16: a SIMD each),
-    int prop_pair_deg10 = 83;       // DRP_PROP_PAIR_DEG10: above that while the piles' mean in-degree (x 10) is at most this
-    // the mean in-degree the last lists of this shape had (k_deg_stat, every few launches): sum | rows << 24 | N << 48 in
-    // host memory the device writes; only ever a question of speed -- paired and unpaired tiles give the same bits
+    // the mean in-degree the last lists of a shape had (k_deg_stat, every few launches): sum | rows << 24 | N << 48 in host memory
+    // the device writes; the plans take it decoded (deg()), as an input
     unsigned long long* deg_stat = nullptr;
     unsigned long long* deg_stat_dev = nullptr;
     unsigned deg_tick = 0;
-    bool prop_pair(long spw, long N, long B) const {
-        const long rows = spw * N;
-        if (rows > prop_pair_rows) return false;
-        if (rows <= prop_pair_always || deg_stat == nullptr) return true;
-        const unsigned long long v = *reinterpret_cast<volatile const unsigned long long*>(deg_stat);
-        const long sum = (long)(v & 0xffffffull), st_rows = (long)((v >> 24) & 0xffffffull), st_n = (long)(v >> 48);
-        if (st_n != N || st_rows != std::min(B * N, (long)DEG_STAT_MAX_ROWS) || st_rows == 0) return true;   // not known (yet)
-        return sum * 10 <= st_rows * (long)prop_pair_deg10;
-    }
-    bool prop3e = true;             // false: the particle encoder stays its own launch in front of km_prop3
-    bool rollout_fused = true;      // DRP_NO_ROLLOUT_FUSED=1: one graph + one km_prop3 launch per rollout step for small piles too
-    int rollout_max_n = 64;         // DRP_ROLLOUT_MAX_N: km_rollout (the whole rollout in one launch) up to this many particles ...
-    int rollout_mid_n = 256, rollout_mid_rows = 256;  // ... up to 256 particles for workgroups of up to 256 rows (small batches; the
-                                    // kernels with the kept rows and the lists beside the encoder: 256 x 80 / 100 / 128 / 150 / 200 / 256
-                                    // + 23 / + 14 / + 13 / + 13 / + 5 / + 6 %, 512 x 100 / 128 + 13 / + 16 %, 128 x 150 + 7 %, 341 x 96 + 16 %;
-                                    // 64 x 256 - 5 %: above 200 particles only from half a chip of samples; 1024 x 80 / 100 (320 / 400 rows): - 1 %)
-    int rollout_max_rows = 704;     // ... and this many rows (samples x particles) per workgroup.  Measured
-                                    // against the step-by-step pipeline at 1024 samples: +18 % at 10 particles, +12 % at 20, +2 % at
-                                    // 50, +5 % at 64, -1 % at 80, -10 % at 150 (the strip build wins); 50 particles x 4096 samples
-                                    // (800 rows per workgroup) -5 %, 20 x 8192 (640 rows) +7 %
-
-    // Edge-chain cache of the whole-sample kernels (prop_tiles, EC): the relation encoder's chain runs in the first propagation
-    // step only and its output is read back in the other two, from a workgroup-private buffer of 80 KB per tile of 32 receivers
-    // (2.5 KB per receiver).  The cached kernels differ from the recomputing ones in the last place of one sum, so WHICH of the
-    // two serves a sample must not depend on how many samples travel with it (a 1 024-sample shard of an 8 192-sample job, a
-    // rank's half of the planner's 1 500 rows: the sharded and the unsharded run must agree bit for bit): the choice is a function
-    // of the PILE SIZE alone (ec_shape; DRP_ECACHE_MAX_MB=0: never) -- and the buffer stays small by construction instead: a
-    // cached launch gives a workgroup at most ec_rows_cap(N) rows, and a batch that needs more than one such launch is run as
-    // several, one after the other on the stream, over the same buffer (run_rollout, run_step_mfma; 256 workgroups x 9 tiles
-    // x 80 KB = 189 MB, inside the 256 MB of last-level cache).
-    // Which pile sizes: measured with the blocks in place (tools/ab_env_shapes.sh, DRP_ECACHE_MAX_N=64 against 256, one box):
-    // 256 samples x 80 / 100 / 150 / 200 particles + 15 / + 31 / + 35 / + 19 %, 1 024 x 80 / 100 / 128 / 256 + 8 / + 7 / + 7 /
-    // + 3 %, but 1 024 x 150 - 12 % and x 200 - 5 %: one sample of 129 ... 224 particles leaves three to one of a workgroup's
-    // eight waves without a tile.  So: up to ecache_max_n = 128 particles (two samples of up to 128 fill the eight tiles), and
-    // ecache_full_n = 225 ... 256 (one sample, eight tiles).  The TAPE's launches (gradient-descent planner, trainer) write one
-    // history buffer over the whole batch and are not split: their cache covers the whole batch, which pays up to
-    // ecache_tape_max_n = 40 particles at the planner's 1 500 rows (50 particles: 0.398 ms per iteration recomputing, 0.42 cached).
-    int ecache_max_mb = 192;
-    int ecache_hard_max_mb = 4096;  // a cached launch that cannot be split (the tape's: 1 500 x 40 rows are 150 MB) and would need more recomputes:
-                                    // 1.6 million rows -- no caller of the reference comes near; the one place where the batch decides the kernel
-    int ecache_max_n = 128, ecache_full_n = 225, ecache_tape_max_n = 40;
-    DevBuf ecache;
-    // how many float4 a workgroup of `rows` receivers needs
-    static size_t ecache_stride(long rows, bool pair) {
-        const long tiles = pair ? (rows + 15) / 16 : (rows + 31) / 32;
-        return (size_t)tiles * (pair ? 5 : DRP_K) * EC_UNITS;
-    }
-    bool ec_shape(int N, bool tape = false) const {
-        if (ecache_max_mb <= 0) return false;
-        if (tape) return N <= ecache_tape_max_n;
-        return N <= ecache_max_n || (N >= ecache_full_n && N <= 256);
-    }
-    // rows a workgroup of a cached launch may hold: nine tiles of 32 (up to 64 particles: the measured best at 1 024 x 64 is
-    // four samples = eight tiles), eight -- one per wave, rows kept in registers -- above
-    static long ec_rows_cap(int N) { return N <= 64 ? 288 : 256; }
-    // samples per launch of a cached shape: every CU a workgroup of at most ec_rows_cap rows, in whole multiples of `unit`
-    // (the batch columns: row b reads column b % unit of the replicated inputs)
-    long ec_chunk(int N, long unit) const {
-        const long spw = std::max(1L, ec_rows_cap(N) / N);
-        long chunk = (long)n_cu * spw;
-        if (unit > 1) chunk = chunk / unit * unit;
-        return chunk;
-    }
+    DegStat deg() const { return deg_stat ? decode_deg_stat(*reinterpret_cast<volatile const unsigned long long*>(deg_stat)) : DegStat{}; }
+    DevBuf ecache;                  // the edge-chain cache of the whole-sample kernels (dispatch.h: cut_blocks)
 
     // model constants
     bool have_weights = false, have_cam = false, have_goal = false;
@@ -411,10 +250,6 @@ struct drp_ctx {
     void* tr_pin = nullptr;         // pinned staging of a training batch (drp_train_step: one upload)
     size_t tr_pin_cap = 0;
     DevBuf tr_arena, re_shift_dev;  // the batch as uploaded; the shift kt_repack_all derived
-    int graph_q4 = 1;               // DRP_GRAPH_Q4=0 / 1 / 2: four threads per receiver in the plain neighbour sweep -- never / for a handful
-                                    // of samples (fewer workgroups than half the CUs) / whenever the plain sweep is chosen
-    bool wgrad_mfma = true;         // DRP_NO_WGRAD_MFMA=1: the weight gradients' outer-product sums on the VALU kernel (kt_wgrad_multi)
-    bool prop_spread = true;        // DRP_NO_PROP_SPREAD=1: km_prop's tiles eight to a workgroup whatever their number
     bool repack_device = true;      // DRP_NO_REPACK_DEVICE=1: fetch the blob and run the host packers (the round-2 path)
 
     // km_rollout's argument block (device copy + what it holds)

@@ -71,35 +71,24 @@ int gd_forward_backward(drp_ctx* c) {
         s.ge_tmp = ptr<float>(c->g_eff); s.g_cnode = ptr<float>(c->g_cnode);
         for (int v = 0; v < 3; ++v) { s.d.ge[v] = ptr<float>(c->g_eff); s.d.gp[v] = ptr<float>(c->g_proj); }
         if (!rev_built) launch_reverse_lists(c, idx, s.cnt, N, B, nullptr, 0);
-        const int spw_b = (B + c->n_cu - 1) / c->n_cu;
-        if (c->bwd_fused && c->bwd_rows && N <= KMB_ROWS_MAX) {
-            // piles of up to 256 particles: a workgroup takes groups of whole samples with at most 256 rows, a wave keeps
-            // its tile's rows in registers through all phases (kmb_rows_bwd).  Samples per group: the fewest that do not
-            // add a round of groups over the CUs (fewer waves at work per CU, more CUs at work)
-            const int g_max = KMB_ROWS_MAX / N;
-            auto rounds = [&](int g) { return (((long)B + g - 1) / g + c->n_cu - 1) / c->n_cu; };
-            int gps = g_max;
-            while (gps > 1 && rounds(gps - 1) == rounds(g_max)) --gps;
-            const long n_groups = ((long)B + gps - 1) / gps;
+        // rows kernel, whole samples in one launch, or a launch per stage (dispatch.h: plan_backward)
+        const BwdPlan k = plan_backward(c->pol, c->n_cu, B, N);
+        c->dv(k.variant());
+        if (k.kind == BwdPlan::ROWS) {
             ProbeScope ps(c, KC_BWD_NODE);
-            c->dv(DV_BWD_ROWS);
-            hipLaunchKernelGGL(kmb_rows_bwd, dim3((unsigned)(n_groups < (long)c->n_cu ? n_groups : (long)c->n_cu)), dim3(64 * KMB_FUSED_WAVES),
+            hipLaunchKernelGGL(kmb_rows_bwd, dim3((unsigned)k.grid), dim3(64 * KMB_FUSED_WAVES),
                                KMB_ROWS_LDS, st, ptr<float>(c->w_mfma), ptr<float>(c->w_mfma_bwd), ptr<uint16_t>(c->w_split6),
                                ptr<uint16_t>(c->w_split6_bwd), s.eht, s.mht, s.cnt, s.rev_off, s.rev, g_out, (size_t)N * 3, s.sdelta,
-                               ptr<float>(c->attr), nb, ptr<float>(c->dens), nb, N, B, gps, t > 0 ? s.gah : (float*)nullptr,
+                               ptr<float>(c->attr), nb, ptr<float>(c->dens), nb, N, B, k.gps, t > 0 ? s.gah : (float*)nullptr,
                                ptr<float>(c->g_sdelta));
-        } else if (c->bwd_fused && whole_samples(c, B, N) && ((long)spw_b * N + 31) / 32 >= c->bwd_fused_min_tiles) {
-            // chip-filling batches: everything between the reward's gradient and the impulses' in one launch,
-            // a workgroup owning whole samples (kmb_step_bwd)
+        } else if (k.kind == BwdPlan::STEP) {
             ProbeScope ps(c, KC_BWD_NODE);
-            c->dv(DV_BWD_STEP);
-            hipLaunchKernelGGL((kmb_step_bwd<false, false>), dim3((unsigned)((B + spw_b - 1) / spw_b)), dim3(64 * KMB_FUSED_WAVES), KMB_FUSED_LDS, st,
+            hipLaunchKernelGGL((kmb_step_bwd<false, false>), dim3((unsigned)k.grid), dim3(64 * KMB_FUSED_WAVES), KMB_FUSED_LDS, st,
                                ptr<float>(c->w_mfma), ptr<float>(c->w_mfma_bwd), s.eht, s.mht, s.cnt, s.rev_off, s.rev,
                                g_out, (size_t)N * 3, s.sdelta, ptr<float>(c->attr), nb,
-                               ptr<float>(c->dens), nb, N, B, spw_b, s.ge_tmp, s.g_cnode, s.gah,
+                               ptr<float>(c->dens), nb, N, B, k.spw, s.ge_tmp, s.g_cnode, s.gah,
                                ptr<float>(c->g_sdelta), KmbDump{}, 1, (unsigned*)nullptr, (unsigned*)nullptr);
         } else {
-            c->dv(DV_BWD_STAGES_MFMA);
             launch_node_stages(c, s, dim3(B), 1, nullptr);
         }
         float* g_prev = nullptr;

@@ -196,11 +196,11 @@ int ensure_step_ws(drp_ctx* c, int B, int N, int engine = -1) {
     return DRP_OK;
 }
 
-// Every few launches whose pairing depends on it (prop_pair), the mean in-degree of the lists just built goes to host
+// Every few launches whose pairing depends on it (dispatch.h: PairRule), the mean in-degree of the lists just built goes to host
 // memory behind the launch: the next launches of this shape read it there, without waiting for anything.
 static void note_degrees(drp_ctx* c, long spw, long N, long B) {
     const long rows = spw * N;
-    if (rows > c->prop_pair_rows || rows <= c->prop_pair_always) return;
+    if (rows > c->pol.prop_pair_rows || rows <= c->pol.prop_pair_always) return;
     if ((c->deg_tick++ & 7u) != 0) return;
     if (!c->deg_stat) {
         if (hipHostMalloc(reinterpret_cast<void**>(&c->deg_stat), sizeof(unsigned long long), hipHostMallocMapped) != hipSuccess) {
@@ -235,121 +235,64 @@ struct StepArgs {
     const float* cself = nullptr;   // [B,64] self-edge constant + per-sample validity (fused engine, k_cself)
     const uint8_t* cself_ok = nullptr;
     bool padded = false;            // training batches: zero-padded (coincident) particles -> plain k_graph
-    mutable bool encoded = false;   // run_step: the particle encoder already ran, in the neighbour lists' launch (km_graph_q4_encode)
     int* rev_off = nullptr;         // the GD planner's forward, samples of one graph chunk: the reversed lists in the lists' own launch
     int* rev = nullptr;             //   (k_graph_rev); run_step says in rev_built whether it did
     bool* rev_built = nullptr;
 };
 
-// km_prop3 / kmb_step_bwd (a workgroup owns whole samples and runs all propagation steps in one launch) or the
-// per-step kernels (the tiles of all samples dealt over the chip)?  Whole samples whenever (nearly) every CU gets one --
-// and for ANY batch of samples of up to 256 particles (one round of tiles per step for the workgroup's eight waves):
-// a small batch is latency, and one launch per rollout step instead of five is what counts (B = 32 ... 255 at 50 / 100
-// particles: 1.7 - 2.0 -> 1.0 - 1.2 ms per MPPI iteration; 300 particles: 2 - 7 % slower below 200 samples, 27 % faster
-// at 255).
-bool whole_samples(const drp_ctx* c, long B, int N) {
-    if (c->prop3_min_b > 0) return B >= c->prop3_min_b;
-    return B >= c->n_cu - c->n_cu / 5 || N <= 256;
-}
-int graph_chunks(int N) { return (N + GRAPH_THREADS - 1) / GRAPH_THREADS; }
-// neighbour lists: x-strip variant for samples of at least two workgroups (below that a wave's range is the whole
-// sample anyway), plain sweep otherwise and for zero-padded batches (coincident particles tie at the cut)
-void launch_graph(drp_ctx* c, hipStream_t st, const float* s_prev, int prev_mod, size_t prev_stride, const float* actions,
-                  size_t act_stride, float* s_delta, int B, int N, int16_t* nbr_idx, uint8_t* nbr_cnt, int self_first,
-                  bool padded);
-size_t graph_lds(int N) { return (size_t)4 * N * sizeof(float); }
-
-// which build launch_graph picks, in its order: cells, x strips, then k_graph_q4 for a handful of samples
-bool graph_takes_q4(const drp_ctx* c, int B, int N, bool padded) {
-    if (c->graph_cells && c->graph_strips && !padded && N >= c->graph_cells_min_n) return false;
-    if (c->graph_strips && !padded && N > GRAPH_THREADS) return false;
-    return c->graph_q4 != 0 && N >= 64 && (c->graph_q4 == 2 || (long)B * ((N + 127) / 128) * 2 <= c->n_cu);
-}
-// km_prop3 with the particle encoder as its first phase (run_step_mfma): no encoder launch to share
-bool step_has_phase_e(const drp_ctx* c, int B, int N) {
-    const int spw = (int)((B + c->n_cu - 1) / c->n_cu);
-    const bool prop3 = c->engine == DRP_ENGINE_FUSED && c->prop3 && whole_samples(c, B, N) && ((long)spw * N + 31) / 32 >= c->prop3_min_tiles;
-    return prop3 && c->prop3e;
-}
-void launch_graph(drp_ctx* c, hipStream_t st, const float* s_prev, int prev_mod, size_t prev_stride, const float* actions,
-                  size_t act_stride, float* s_delta, int B, int N, int16_t* nbr_idx, uint8_t* nbr_cnt, int self_first,
-                  bool padded) {
-    if (c->graph_cells && c->graph_strips && !padded && N >= c->graph_cells_min_n) {
-        // two-dimensional cells: y bands of height hb ~ sqrt(16 / density) (a 16-receiver block of a band is then about
-        // as wide as the band is high; the density of a pile spread over the 0.4 x 0.4 workspace -- any positive hb
-        // gives the same lists), 1-cm x strips inside a band
-        const size_t Np = ((size_t)N + 3) & ~(size_t)3;
-        float4* sorted = reinterpret_cast<float4*>(c->c_edge.p);
-        int* starts = reinterpret_cast<int*>(sorted + (size_t)B * Np);
-        float hb = sqrtf(16.0f * 0.16f / (float)N);
-        if (c->graph_cells_hb > 0.0f) hb = c->graph_cells_hb;
-        int gy = (int)ceilf(0.64f / hb);
-        if (gy > GC_MAX_BANDS) gy = GC_MAX_BANDS;
-        if (gy < 1) gy = 1;
-        const float inv_hb = (float)gy / 0.64f;
-        const int ncell = gy * GC_XS;
-        c->dv(DV_GRAPH_CELLS);
+// neighbour lists as planned (plan_graph): cells, x strips, four threads per receiver, or the plain sweep; the two builds
+// that share their launch with something else (k_graph_rev, km_graph_q4_encode) are run_step's
+void launch_graph(drp_ctx* c, hipStream_t st, const GraphPlan& g, const float* s_prev, int prev_mod, size_t prev_stride,
+                  const float* actions, size_t act_stride, float* s_delta, int B, int N, int16_t* nbr_idx, uint8_t* nbr_cnt,
+                  int self_first) {
+    // sorted positions and strip / cell starts live in the edge-constant buffer: whatever uses it runs after the lists exist
+    const size_t Np = ((size_t)N + 3) & ~(size_t)3;
+    float4* sorted = reinterpret_cast<float4*>(c->c_edge.p);
+    int* starts = reinterpret_cast<int*>(sorted + (size_t)B * Np);
+    const dim3 grid((unsigned)g.grid);
+    switch (g.kind) {
+    case GraphPlan::CELLS:
+        // two-dimensional cells: y bands, 1-cm x strips inside a band
         hipLaunchKernelGGL(k_graph_sort2, dim3(B), dim3(GRAPH_SORT_THREADS), 0, st, s_prev, prev_mod, prev_stride, actions,
-                           act_stride, s_delta, N, c->cam, gy, inv_hb, sorted, starts);
-        const float halo = c->graph_cells_halo > 0.0f ? c->graph_cells_halo
-                           // expected distance of the 10th neighbour in a pile of this density, with a third to spare
-                           : 1.3f * sqrtf(10.0f * 0.16f / (3.14159265f * (float)N));
-        // receivers are dealt to quarter waves band by band: at most N / 16 + gy quarters, 16 per workgroup
-        const int chunks = ((N + 15) / 16 + gy + GC_THREADS / 16 - 1) / (GC_THREADS / 16);
-        hipLaunchKernelGGL(k_graph_cells, dim3(SPREAD_GRID(B * chunks)), dim3(GC_THREADS), GRAPH_CELLS_LDS(ncell), st,
-                           (const float4*)sorted, (const int*)starts, N, gy, inv_hb, nbr_idx, nbr_cnt, c->thr, chunks,
-                           B * chunks, self_first, halo);
-    }
-    else if (c->graph_strips && !padded && N > GRAPH_THREADS) {
-        // sorted positions and strip starts live in the edge-constant buffer: whatever uses it runs after the lists exist
-        const size_t Np = ((size_t)N + 3) & ~(size_t)3;
-        float4* sorted = reinterpret_cast<float4*>(c->c_edge.p);
-        int* starts = reinterpret_cast<int*>(sorted + (size_t)B * Np);
+                           act_stride, s_delta, N, c->cam, g.gy, g.inv_hb, sorted, starts);
+        hipLaunchKernelGGL(k_graph_cells, grid, dim3(GC_THREADS), GRAPH_CELLS_LDS(g.gy * GC_XS), st,
+                           (const float4*)sorted, (const int*)starts, N, g.gy, g.inv_hb, nbr_idx, nbr_cnt, c->thr, g.chunks,
+                           B * g.chunks, self_first, g.halo);
+        break;
+    case GraphPlan::STRIPS128:
+    case GraphPlan::STRIPS256:
         hipLaunchKernelGGL(k_graph_sort, dim3(B), dim3(GRAPH_SORT_THREADS), 0, st, s_prev, prev_mod, prev_stride, actions,
                            act_stride, s_delta, N, c->cam, sorted, starts);
-        c->dv(N >= 800 ? DV_GRAPH_STRIPS256 : DV_GRAPH_STRIPS);
-        if (N >= 800) {
-            const int chunks = (N + 255) / 256;
-            hipLaunchKernelGGL(k_graph_strips_q<256>, dim3(SPREAD_GRID(B * chunks)), dim3(256), GRAPH_STRIPS_LDS(N, 256), st,
-                               (const float4*)sorted, (const int*)starts, N, nbr_idx, nbr_cnt, c->thr, chunks, B * chunks, self_first);
-        } else {
-            hipLaunchKernelGGL(k_graph_strips_q<GRAPH_THREADS>, dim3(SPREAD_GRID(B * graph_chunks(N))), dim3(GRAPH_THREADS), GRAPH_STRIPS_LDS(N, GRAPH_THREADS), st,
-                               (const float4*)sorted, (const int*)starts, N, nbr_idx, nbr_cnt, c->thr, graph_chunks(N), B * graph_chunks(N), self_first);
-        }
-    }
-    else if (graph_takes_q4(c, B, N, padded)) {
+        if (g.kind == GraphPlan::STRIPS256)
+            hipLaunchKernelGGL(k_graph_strips_q<256>, grid, dim3(256), GRAPH_STRIPS_LDS(N, 256), st,
+                               (const float4*)sorted, (const int*)starts, N, nbr_idx, nbr_cnt, c->thr, g.chunks, B * g.chunks, self_first);
+        else
+            hipLaunchKernelGGL(k_graph_strips_q<GRAPH_THREADS>, grid, dim3(GRAPH_THREADS), GRAPH_STRIPS_LDS(N, GRAPH_THREADS), st,
+                               (const float4*)sorted, (const int*)starts, N, nbr_idx, nbr_cnt, c->thr, g.chunks, B * g.chunks, self_first);
+        break;
+    case GraphPlan::Q4:
         // a handful of samples (training batches): four threads per receiver, each over a quarter of the senders
-        const int chunks = (N + 127) / 128;
-        c->dv(DV_GRAPH_Q4);
-        hipLaunchKernelGGL(k_graph_q4, dim3((unsigned)(B * chunks)), dim3(GRAPH_Q4_THREADS), GRAPH_Q4_LDS(N), st, s_prev, prev_mod,
-                           prev_stride, actions, act_stride, s_delta, N, nbr_idx, nbr_cnt, c->cam, c->thr, chunks, self_first);
-    }
-    else {
-        c->dv(DV_GRAPH_PLAIN);
-        hipLaunchKernelGGL(k_graph, dim3(SPREAD_GRID(B * graph_chunks(N))), dim3(GRAPH_THREADS), graph_lds(N), st, s_prev,
+        hipLaunchKernelGGL(k_graph_q4, grid, dim3(GRAPH_Q4_THREADS), GRAPH_Q4_LDS(N), st, s_prev, prev_mod,
+                           prev_stride, actions, act_stride, s_delta, N, nbr_idx, nbr_cnt, c->cam, c->thr, g.chunks, self_first);
+        break;
+    default:
+        hipLaunchKernelGGL(k_graph, grid, dim3(GRAPH_THREADS), (size_t)4 * N * sizeof(float), st, s_prev,
                            prev_mod, prev_stride, actions, act_stride, s_delta, N, nbr_idx, nbr_cnt, c->cam, c->thr,
-                           graph_chunks(N), B * graph_chunks(N), self_first);
+                           g.chunks, B * g.chunks, self_first);
+        break;
     }
 }
 
-void launch_aggregate(drp_ctx* c, int B, int N) {
+void launch_aggregate(drp_ctx* c, const AggPlan& g, int B, int N) {
     ProbeScope ps(c, KC_AGGREGATE);
-    // a handful of samples (training batches): several workgroups per sample on the global variant
-    int chunks = 1;
-    if (B < c->n_cu / 2) {
-        chunks = (N + 15) / 16;
-        if (chunks > 2048 / B) chunks = 2048 / B;
-        if (chunks < 1) chunks = 1;
-    }
-    c->dv((N <= K_AGG_LDS_MAX_N && !c->agg_global_only && chunks == 1) ? DV_AGGREGATE_LDS : DV_AGGREGATE);
-    if (N <= K_AGG_LDS_MAX_N && !c->agg_global_only && chunks == 1)
+    if (g.lds)
         hipLaunchKernelGGL(k_aggregate_lds, dim3(B), dim3(512), (size_t)N * 256, c->stream,
                            ptr<float>(c->c_edge), ptr<float>(c->proj), ptr<int16_t>(c->nbr_idx),
                            ptr<uint8_t>(c->nbr_cnt), N, ptr<float>(c->agg));
     else
-        hipLaunchKernelGGL(k_aggregate, dim3(B * chunks), dim3(256), 0, c->stream, ptr<float>(c->c_edge),
+        hipLaunchKernelGGL(k_aggregate, dim3(B * g.chunks), dim3(256), 0, c->stream, ptr<float>(c->c_edge),
                            ptr<float>(c->proj), ptr<int16_t>(c->nbr_idx), ptr<uint8_t>(c->nbr_cnt), N,
-                           ptr<float>(c->agg), chunks);
+                           ptr<float>(c->agg), g.chunks);
 }
 
 // kernels whose tile loop is workgroup-cyclic first (tile = block + grid x (wave + 8 round)): one workgroup per tile up to the chip
@@ -363,8 +306,60 @@ int mfma_grid(drp_ctx* c, long ntiles) {
     return (int)(blocks < cap ? (blocks > 0 ? blocks : 1) : cap);
 }
 
-// MLP stages of one step on the fp32 MFMA kernels (graph already built, s_delta in workspace)
-int run_step_mfma(drp_ctx* c, const StepArgs& a) {
+// The instantiations of km_prop / km_prop3 / km_rollout by their flags' index (dispatch.h), filled from the lists that
+// declare and instantiate them (k_prop_inst.h): a launch is table[flags.index()]
+struct PropTables {
+    decltype(&km_prop<false, false, false, false>) prop[PropFlags::COUNT];
+    decltype(&km_prop3<false, false, false, false, false>) prop3[Prop3Flags::COUNT];
+    decltype(&km_rollout<false, false, false, false>) rollout[RolloutFlags::COUNT];
+    int filled = 0;
+};
+const PropTables& prop_tables() {
+    static const PropTables tables = [] {
+        PropTables t{};
+#define KM_TAB_PROP(L, T, P, W) t.prop[PropFlags{L, T, P, W}.index()] = km_prop<L, T, P, W>; ++t.filled;
+#define KM_TAB_PROP3(T, P, E, W, O) t.prop3[Prop3Flags{T, P, (E) ? ((O) ? 2 : 1) : 0, W}.index()] = km_prop3<T, P, E, W, O>; ++t.filled;
+#define KM_TAB_ROLLOUT(P, E, W, O) t.rollout[RolloutFlags{P, (E) ? ((O) ? 2 : 1) : 0, W}.index()] = km_rollout<P, E, W, O>; ++t.filled;
+        KM_PROP_LIST_TAPE(KM_TAB_PROP, false)
+        KM_PROP_LIST_TAPE(KM_TAB_PROP, true)
+        KM_PROP3_LIST_TAPE(KM_TAB_PROP3, false)
+        KM_PROP3_LIST_TAPE(KM_TAB_PROP3, true)
+        KM_ROLLOUT_LIST(KM_TAB_ROLLOUT)
+#undef KM_TAB_PROP
+#undef KM_TAB_PROP3
+#undef KM_TAB_ROLLOUT
+        return t;
+    }();
+    return tables;
+}
+static_assert(sizeof(PropTables::prop) / sizeof(void*) == PropFlags::COUNT && sizeof(PropTables::prop3) / sizeof(void*) == Prop3Flags::COUNT &&
+              sizeof(PropTables::rollout) / sizeof(void*) == RolloutFlags::COUNT, "a table entry per index of the family's flags");
+// drp_create: every entry is there, and may use its dynamic LDS
+bool prop_tables_ready() {
+    const PropTables& t = prop_tables();
+    bool ok = t.filled == PropFlags::COUNT + Prop3Flags::COUNT + RolloutFlags::COUNT;
+    for (int q = 0; q < PropFlags::COUNT && ok; ++q)
+        ok = t.prop[q] && hipFuncSetAttribute((const void*)t.prop[q], hipFuncAttributeMaxDynamicSharedMemorySize, KM_PROP_LDS(PropFlags::from_index(q).last)) == hipSuccess;
+    for (int q = 0; q < Prop3Flags::COUNT && ok; ++q)
+        ok = t.prop3[q] && hipFuncSetAttribute((const void*)t.prop3[q], hipFuncAttributeMaxDynamicSharedMemorySize, KM_PROP3_LDS) == hipSuccess;
+    for (int q = 0; q < RolloutFlags::COUNT && ok; ++q)
+        ok = t.rollout[q] && hipFuncSetAttribute((const void*)t.rollout[q], hipFuncAttributeMaxDynamicSharedMemorySize, KM_ROLLOUT_LDS) == hipSuccess;
+    return ok;
+}
+
+StepShape step_shape(const drp_ctx* c, const StepArgs& a) {
+    StepShape s;
+    s.engine = c->engine; s.B = a.B; s.N = a.N;
+    s.tape = a.eff_hist != nullptr;
+    s.prev_mod = a.prev_mod; s.attr_mod = a.attr_mod; s.dens_mod = a.dens_mod;
+    s.work = c->work_ptr() != nullptr;
+    s.build_graph = a.build_graph; s.padded = a.padded; s.has_actions = a.actions != nullptr; s.wants_rev = a.rev_off != nullptr;
+    s.deg = c->deg();
+    return s;
+}
+
+// MLP stages of one step on the matrix-core kernels as planned (graph already built, s_delta in workspace)
+int run_step_mfma(drp_ctx* c, const StepArgs& a, const StepPlan& k) {
     const int B = a.B, N = a.N;
     hipStream_t st = c->stream;
     const float* mw = ptr<float>(c->w_mfma);
@@ -372,24 +367,16 @@ int run_step_mfma(drp_ctx* c, const StepArgs& a) {
     const long node_tiles = (long)B * ((N + 31) / 32);
     const long edge_tiles = (long)B * ((N * DRP_K + 31) / 32);
     const size_t bn64 = (size_t)B * N * 64;
-    const bool tape = a.eff_hist != nullptr;
+    const bool tape = k.tape;
     // the tape of the reverse-mode kernels: km_prop<., TAPE> on the fused engine; on the fp32 matrix engine (what the
     // gradient-descent planner and the trainer fall back to when the split-fp16 relation encoder refuses the weights or the
     // inputs) the stage kernels run as always and the tape is copied / written beside them (tape_mfma below)
     if (tape && c->engine != DRP_ENGINE_FUSED && c->engine != DRP_ENGINE_MFMA)
         return fail(c, DRP_ESTATE, "the backward tape is written by the fused or the fp32 matrix engine");
-    const bool tape_mfma = tape && c->engine == DRP_ENGINE_MFMA;
-    float* eff0 = (tape && !tape_mfma) ? a.eff_hist : ptr<float>(c->eff);
-    // chip-filling batches on the fused engine: the three propagation steps are one launch (km_prop3), and the
-    // particle encoder is its first phase unless switched off
-    const int tps3 = (N + 31) / 32;
-    const int spw = (int)((B + c->n_cu - 1) / c->n_cu);
-    const bool prop3 = c->engine == DRP_ENGINE_FUSED && c->prop3 && whole_samples(c, B, N) && ((long)spw * N + 31) / 32 >= c->prop3_min_tiles;
-    const bool phase_e = prop3 && c->prop3e;
-    if (!phase_e && !a.encoded) {
+    float* eff0 = (tape && !k.tape_mfma) ? a.eff_hist : ptr<float>(c->eff);
+    if (k.node_encode) {
         ProbeScope ps(c, KC_NODE_ENCODE);
-        c->dv(c->engine == DRP_ENGINE_FUSED ? DV_NODE_ENCODE_SPLIT : DV_NODE_ENCODE);
-        if (c->engine == DRP_ENGINE_FUSED)
+        if (k.fused)
             hipLaunchKernelGGL(km_node_encode_split, dim3(mfma_grid_spread(c, node_tiles)), blk, KM_NODE_SPLIT_LDS, st,
                                ptr<uint16_t>(c->w_split6), mw, ptr<float>(c->s_delta), a.attr, a.attr_mod, a.dens,
                                a.dens_mod, N, B, eff0, ptr<float>(c->c_node), ptr<float>(c->proj));
@@ -398,14 +385,61 @@ int run_step_mfma(drp_ctx* c, const StepArgs& a) {
                                ptr<float>(c->s_delta), a.attr, a.attr_mod, a.dens, a.dens_mod, N, B,
                                ptr<float>(c->eff), ptr<float>(c->c_node), ptr<float>(c->proj));
     }
-    // split engine, small enough samples: the relation encoder is recomputed inside the
-    // aggregate of every propagation step and c_edge is never materialised
-    const bool fused = (c->engine == DRP_ENGINE_FUSED);
-    const bool split = fused || c->engine == DRP_ENGINE_SPLIT || c->engine == DRP_ENGINE_FUSED;
-    if (!fused) {
+    if (k.fused) {
+        // the relation encoder is recomputed inside the propagation kernels and c_edge is never materialised
+        float* pa = ptr<float>(c->proj);
+        float* pb = ptr<float>(c->proj2);
+        unsigned long long* const wk = c->work_ptr();    // not null: the counting instantiations (drp_probe_begin("prop+work"))
+        const dim3 pblk(64 * PROP_WAVES);
+        if (k.prop3) {
+            // one launch per block of samples (dispatch.h: cut_blocks) -- the tape's launches too: the history buffers are laid
+            // out for the whole batch, a block starts `ro` rows into every slot and the kernel takes the slots' stride as an
+            // argument (hist_rows)
+            ProbeScope ps(c, KC_PROP);
+            if (k.blocks.cache) CHK(ensure(c, c->ecache, k.blocks.cache_bytes));
+            note_degrees(c, k.spw, N, B);
+            for (int q = 0; q < k.blocks.n; ++q) {
+                const Block b = k.blocks.block(q);
+                // the block's view of every per-sample buffer: inputs replicated over the batch columns (row b reads column
+                // b % mod) keep their base -- a block starts at a multiple of mod --, everything indexed by the row moves on
+                const size_t ro = (size_t)b.b_off * N;
+                const bool own_prev = a.prev_mod >= B, own_attr = a.attr_mod >= B, own_dens = a.dens_mod >= B;
+                if (b.cache_bytes > c->ecache.cap) CHK(ensure(c, c->ecache, b.cache_bytes));
+                hipLaunchKernelGGL(prop_tables().prop3[k.prop3_flags(b).index()], dim3((unsigned)b.grid), pblk, KM_PROP3_LDS, st,
+                                   ptr<uint16_t>(c->w_split), ptr<uint16_t>(c->w_split6), mw,
+                                   own_prev ? a.s_prev + (size_t)b.b_off * a.prev_stride : a.s_prev, own_prev ? b.Bc : a.prev_mod, a.prev_stride,
+                                   own_attr ? a.attr + ro : a.attr, own_attr ? b.Bc : a.attr_mod,
+                                   own_dens ? a.dens + b.b_off : a.dens, own_dens ? b.Bc : a.dens_mod,
+                                   ptr<int16_t>(c->nbr_idx) + ro * DRP_K, ptr<uint8_t>(c->nbr_cnt) + ro, pa + ro * 128, pb + ro * 128,
+                                   ptr<float>(c->c_node) + ro * 64, (tape ? a.eff_hist : ptr<float>(c->eff)) + ro * 64, N, b.Bc, b.spw,
+                                   k.phase_e ? (const float*)(ptr<float>(c->s_delta) + ro * 3) : (const float*)nullptr,
+                                   a.s_out + (size_t)b.b_off * a.out_stride, a.out_stride,
+                                   a.cself ? a.cself + (size_t)b.b_off * 64 : (const float*)nullptr,
+                                   a.cself_ok ? a.cself_ok + b.b_off : (const uint8_t*)nullptr,
+                                   tape ? a.mask_hist + ro * DRP_K * 2 : (unsigned*)nullptr,
+                                   (tape && a.agg_hist) ? a.agg_hist + ro * 64 : (float*)nullptr, c->re_scale, c->re_inv,
+                                   (c->pol.prop3_order ? 1 : 0), ptr<float4>(c->ecache), b.ec_stride, wk, tape ? (size_t)B * N : (size_t)0);
+            }
+        }
+        for (int p = 0; p < DRP_PSTEP && !k.prop3; ++p) {
+            const bool last = (p + 1 == DRP_PSTEP);
+            ProbeScope ps(c, KC_PROP);
+            const PropFlags f{last, tape, k.pair, k.work};
+            hipLaunchKernelGGL(prop_tables().prop[f.index()], dim3((unsigned)k.grid), pblk, KM_PROP_LDS(last), st,
+                               ptr<uint16_t>(c->w_split), ptr<uint16_t>(c->w_split6), mw, a.s_prev, a.prev_mod, a.prev_stride,
+                               a.attr, a.attr_mod, a.dens, a.dens_mod, ptr<int16_t>(c->nbr_idx), ptr<uint8_t>(c->nbr_cnt), pa,
+                               ptr<float>(c->c_node), tape ? a.eff_hist + (size_t)p * bn64 : ptr<float>(c->eff),
+                               tape ? a.eff_hist + (size_t)(p + 1) * bn64 : ptr<float>(c->eff), N, B, pb, a.s_out, a.out_stride, a.cself, a.cself_ok,
+                               tape ? a.mask_hist + (size_t)p * B * N * DRP_K * 2 : (unsigned*)nullptr,
+                               (tape && a.agg_hist) ? a.agg_hist + (size_t)p * bn64 : (float*)nullptr,
+                               c->re_scale, c->re_inv, k.spread, wk);
+            float* tmp = pa; pa = pb; pb = tmp;
+        }
+        return DRP_OK;
+    }
+    {
         ProbeScope ps(c, KC_EDGE_ENCODE);
-        c->dv(split ? DV_EDGE_ENCODE_SPLIT : DV_EDGE_ENCODE);
-        if (split)
+        if (k.split_encoders)
             hipLaunchKernelGGL(km_edge_encode_split, dim3(mfma_grid(c, edge_tiles)), blk, KM_EDGE_SPLIT_LDS, st,
                                ptr<uint16_t>(c->w_split), mw, a.s_prev, a.prev_mod, a.prev_stride, a.attr,
                                a.attr_mod, a.dens, a.dens_mod, ptr<int16_t>(c->nbr_idx),
@@ -415,141 +449,21 @@ int run_step_mfma(drp_ctx* c, const StepArgs& a) {
                                a.s_prev, a.prev_mod, a.prev_stride, a.attr, a.attr_mod, a.dens, a.dens_mod,
                                ptr<int16_t>(c->nbr_idx), ptr<uint8_t>(c->nbr_cnt), N, B, ptr<float>(c->c_edge));
     }
-    if (fused) {
-        // graph -> node_encode -> the three propagation steps: one launch (km_prop3: a workgroup owns whole
-        // samples and barriers locally between steps) when every CU gets a sample and a workgroup at least
-        // PROP_WAVES tiles per step; otherwise one launch per step with the tiles of all samples dealt over the chip
-        float* pa = ptr<float>(c->proj);
-        float* pb = ptr<float>(c->proj2);
-        if (prop3) {
-            ProbeScope ps(c, KC_PROP);
-            const dim3 pblk(64 * PROP_WAVES);
-            // cached or recomputing: by the pile size alone (drp_ctx::ec_shape).  A cached batch too large for one launch of
-            // at most ec_rows_cap rows per workgroup goes out as several launches over consecutive blocks of samples, the same
-            // cache buffer under each -- the tape's launches too: the history buffers are laid out for the whole batch, a block
-            // starts `ro` rows into every slot and the kernel takes the slots' stride as an argument (hist_rows)
-            bool ec = c->ec_shape(N, tape);
-            long chunk = B;
-            if (ec) {
-                long unit = 1;
-                bool ok = true;
-                for (int mod : {a.prev_mod, a.attr_mod, a.dens_mod})
-                    if (mod < B) { if (unit % mod != 0 && mod % unit != 0) ok = false; else unit = std::max(unit, (long)mod); }
-                const long cap = c->ec_chunk(N, unit);
-                if (ok && cap > 0 && cap < B) chunk = cap;
-            }
-            if (ec) {
-                // a launch that cannot be split (the tape's; batch columns no block is a multiple of) takes a cache over the whole
-                // batch, 2.5 KB per row: beyond ecache_hard_max_mb it recomputes instead of failing for memory
-                const long B0 = std::min((long)B, chunk), spw0 = (B0 + c->n_cu - 1) / c->n_cu;
-                const size_t need = (size_t)((B0 + spw0 - 1) / spw0) * drp_ctx::ecache_stride(spw0 * N, false) * 16;
-                if (need > ((size_t)c->ecache_hard_max_mb << 20)) { ec = false; chunk = B; }
-                else CHK(ensure(c, c->ecache, need));
-            }
-            note_degrees(c, spw, N, B);
-            unsigned long long* const wk = c->work_ptr();    // not null: the counting instantiations (drp_probe_begin("prop+work"))
-            for (long b_off = 0; b_off < B; b_off += chunk) {
-                const int Bc = (int)std::min(chunk, (long)B - b_off);
-                const int spw_c = (Bc + c->n_cu - 1) / c->n_cu;
-                const dim3 grid((unsigned)((Bc + spw_c - 1) / spw_c));
-                // the block's view of every per-sample buffer: inputs replicated over the batch columns (row b reads column
-                // b % mod) keep their base -- a block starts at a multiple of mod --, everything indexed by the row moves on
-                const size_t ro = (size_t)b_off * N;
-                const float* s_prev_c = a.prev_mod >= B ? a.s_prev + (size_t)b_off * a.prev_stride : a.s_prev;
-                const int prev_mod_c = a.prev_mod >= B ? Bc : a.prev_mod;
-                const float* attr_c = a.attr_mod >= B ? a.attr + ro : a.attr;
-                const int attr_mod_c = a.attr_mod >= B ? Bc : a.attr_mod;
-                const float* dens_c = a.dens_mod >= B ? a.dens + b_off : a.dens;
-                const int dens_mod_c = a.dens_mod >= B ? Bc : a.dens_mod;
-                float* eff_base = (tape ? a.eff_hist : ptr<float>(c->eff)) + ro * 64;
-                unsigned* mask_hist = tape ? a.mask_hist + ro * DRP_K * 2 : nullptr;
-                float* agg_hist = (tape && a.agg_hist) ? a.agg_hist + ro * 64 : nullptr;
-                const size_t hist_rows = tape ? (size_t)B * N : 0;
-                const float* sd_c = phase_e ? (const float*)(ptr<float>(c->s_delta) + ro * 3) : (const float*)nullptr;
-                const float* cself_c = a.cself ? a.cself + (size_t)b_off * 64 : nullptr;
-                const uint8_t* cself_ok_c = a.cself_ok ? a.cself_ok + b_off : nullptr;
-#define PROP3_ARGS ptr<uint16_t>(c->w_split), ptr<uint16_t>(c->w_split6), mw, s_prev_c, prev_mod_c, a.prev_stride, \
-                   attr_c, attr_mod_c, dens_c, dens_mod_c, ptr<int16_t>(c->nbr_idx) + ro * DRP_K, ptr<uint8_t>(c->nbr_cnt) + ro, pa + ro * 128, pb + ro * 128, \
-                   ptr<float>(c->c_node) + ro * 64, eff_base, N, Bc, spw_c, sd_c, \
-                   a.s_out + (size_t)b_off * a.out_stride, a.out_stride, cself_c, cself_ok_c, mask_hist, agg_hist, c->re_scale, c->re_inv, (c->prop3_order ? 1 : 0)
-                const bool pair = c->prop_pair(spw_c, N, B);
-                const size_t ec_stride = drp_ctx::ecache_stride((long)spw_c * N, pair);
-                // ONE: no more tiles than waves in a workgroup -- the cached kernel then hands a tile's own rows from one propagation
-                // step to the next in registers
-                const bool one = ec && (pair ? ((long)spw_c * N + 15) / 16 : ((long)spw_c * N + 31) / 32) <= PROP_WAVES;
-                if (ec && (size_t)grid.x * ec_stride * 16 > c->ecache.cap) CHK(ensure(c, c->ecache, (size_t)grid.x * ec_stride * 16));
-#define PROP3_LAUNCH_W(TAPE_, PAIR_, EC_, ONE_) do { \
-                    if (wk) hipLaunchKernelGGL((km_prop3<TAPE_, PAIR_, EC_, true, ONE_>), grid, pblk, KM_PROP3_LDS, st, PROP3_ARGS, ptr<float4>(c->ecache), ec_stride, wk, hist_rows); \
-                    else hipLaunchKernelGGL((km_prop3<TAPE_, PAIR_, EC_, false, ONE_>), grid, pblk, KM_PROP3_LDS, st, PROP3_ARGS, ptr<float4>(c->ecache), ec_stride, wk, hist_rows); } while (0)
-#define PROP3_LAUNCH(TAPE_, PAIR_) do { \
-                    if (one) PROP3_LAUNCH_W(TAPE_, PAIR_, true, true); else if (ec) PROP3_LAUNCH_W(TAPE_, PAIR_, true, false); \
-                    else PROP3_LAUNCH_W(TAPE_, PAIR_, false, false); } while (0)
-                c->dv(DV_PROP3 + 12 * (tape ? 1 : 0) + 6 * (pair ? 1 : 0) + 2 * (one ? 2 : ec ? 1 : 0) + (wk ? 1 : 0));
-                if (!tape && !pair) PROP3_LAUNCH(false, false);
-                else if (!tape) PROP3_LAUNCH(false, true);
-                else if (!pair) PROP3_LAUNCH(true, false);
-                else PROP3_LAUNCH(true, true);
-#undef PROP3_LAUNCH_W
-#undef PROP3_LAUNCH
-#undef PROP3_ARGS
-            }
-        }
-        for (int p = 0; p < DRP_PSTEP && !prop3; ++p) {
-            const bool last = (p + 1 == DRP_PSTEP);
-            ProbeScope ps(c, KC_PROP);
-            long pb_ = (node_tiles + PROP_WAVES - 1) / PROP_WAVES;
-            // few tiles (up to four per CU): one per workgroup first, so that a tile has its SIMD to itself
-            const int spread = (c->prop_spread && node_tiles <= 4L * c->n_cu) ? 1 : 0;
-            // fewer still (up to two per CU): tiles of 16 receivers x two slots, half the slot iterations each
-            const long tiles16 = (long)B * ((N + 15) / 16);
-            const bool pair = spread && c->prop_pair_rows > 0 && node_tiles <= 2L * c->n_cu;
-            if (spread) pb_ = pair ? tiles16 : node_tiles;
-            const dim3 grid((unsigned)(pb_ < c->n_cu ? pb_ : c->n_cu)), pblk(64 * PROP_WAVES);
-            const float* eff_in = tape ? a.eff_hist + (size_t)p * bn64 : ptr<float>(c->eff);
-            float* eff_out = tape ? a.eff_hist + (size_t)(p + 1) * bn64 : ptr<float>(c->eff);
-            unsigned* mask_out = tape ? a.mask_hist + (size_t)p * B * N * DRP_K * 2 : nullptr;
-            float* agg_out = (tape && a.agg_hist) ? a.agg_hist + (size_t)p * bn64 : nullptr;
-#define PROP_ARGS ptr<uint16_t>(c->w_split), ptr<uint16_t>(c->w_split6), mw, a.s_prev, a.prev_mod, a.prev_stride, \
-                  a.attr, a.attr_mod, a.dens, a.dens_mod, ptr<int16_t>(c->nbr_idx), ptr<uint8_t>(c->nbr_cnt), pa, \
-                  ptr<float>(c->c_node), eff_in, eff_out, N, B, pb, a.s_out, a.out_stride, a.cself, a.cself_ok, mask_out, agg_out, \
-                  c->re_scale, c->re_inv, spread, c->work_ptr()
-#define PROP_LAUNCH(PAIR_, WORK_) do { \
-                if (!tape) { \
-                    if (!last) hipLaunchKernelGGL((km_prop<false, false, PAIR_, WORK_>), grid, pblk, KM_PROP_LDS(false), st, PROP_ARGS); \
-                    else hipLaunchKernelGGL((km_prop<true, false, PAIR_, WORK_>), grid, pblk, KM_PROP_LDS(true), st, PROP_ARGS); \
-                } else { \
-                    if (!last) hipLaunchKernelGGL((km_prop<false, true, PAIR_, WORK_>), grid, pblk, KM_PROP_LDS(false), st, PROP_ARGS); \
-                    else hipLaunchKernelGGL((km_prop<true, true, PAIR_, WORK_>), grid, pblk, KM_PROP_LDS(true), st, PROP_ARGS); \
-                } } while (0)
-            c->dv(DV_PROP + 8 * (last ? 1 : 0) + 4 * (tape ? 1 : 0) + 2 * (pair ? 1 : 0) + (c->work_ptr() ? 1 : 0));
-            if (c->work_ptr()) { if (pair) PROP_LAUNCH(true, true); else PROP_LAUNCH(false, true); }
-            else if (pair) PROP_LAUNCH(true, false);
-            else PROP_LAUNCH(false, false);
-#undef PROP_LAUNCH
-#undef PROP_ARGS
-            float* tmp = pa; pa = pb; pb = tmp;
-        }
-        return DRP_OK;
-    }
-    if (tape_mfma) HIPCHK(c, hipMemcpyAsync(a.eff_hist, c->eff.p, bn64 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (k.tape_mfma) HIPCHK(c, hipMemcpyAsync(a.eff_hist, c->eff.p, bn64 * sizeof(float), hipMemcpyDeviceToDevice, st));
     for (int p = 0; p < DRP_PSTEP; ++p) {
-        if (tape_mfma) {
+        if (k.tape_mfma) {
             // the aggregate that also leaves the edges' ReLU bits; the aggregated rows and the effects are copied into the tape
             ProbeScope pa(c, KC_AGGREGATE);
-            int chunks = 1;
-            if (B < c->n_cu / 2) chunks = std::max(1, std::min((N + 15) / 16, 2048 / B));
-            c->dv(DV_AGGREGATE_TAPE);
-            hipLaunchKernelGGL(k_aggregate_tape, dim3(B * chunks), dim3(256), 0, st, ptr<float>(c->c_edge), ptr<float>(c->proj),
-                               ptr<int16_t>(c->nbr_idx), ptr<uint8_t>(c->nbr_cnt), N, ptr<float>(c->agg), chunks,
+            hipLaunchKernelGGL(k_aggregate_tape, dim3(B * k.agg.chunks), dim3(256), 0, st, ptr<float>(c->c_edge), ptr<float>(c->proj),
+                               ptr<int16_t>(c->nbr_idx), ptr<uint8_t>(c->nbr_cnt), N, ptr<float>(c->agg), k.agg.chunks,
                                a.mask_hist + (size_t)p * B * N * DRP_K * 2);
             if (a.agg_hist)
                 HIPCHK(c, hipMemcpyAsync(a.agg_hist + (size_t)p * bn64, c->agg.p, bn64 * sizeof(float), hipMemcpyDeviceToDevice, st));
         } else {
-            launch_aggregate(c, B, N);
+            launch_aggregate(c, k.agg, B, N);
         }
         {
         ProbeScope ps(c, p + 1 < DRP_PSTEP ? KC_UPDATE : KC_PREDICT);
-        c->dv(DV_UPDATE);
         if (p + 1 < DRP_PSTEP)
             hipLaunchKernelGGL(km_update<false>, dim3(mfma_grid(c, node_tiles)), blk, KM_UPD_LDS, st, mw,
                                ptr<float>(c->agg), ptr<float>(c->c_node), ptr<float>(c->eff), N, B,
@@ -560,13 +474,14 @@ int run_step_mfma(drp_ctx* c, const StepArgs& a) {
                                ptr<float>(c->proj), a.s_prev, a.prev_mod, a.prev_stride, a.s_out, a.out_stride);
         }
         // the step's effect is the next tape entry (km_update keeps it in place, the last step's too)
-        if (tape_mfma)
+        if (k.tape_mfma)
             HIPCHK(c, hipMemcpyAsync(a.eff_hist + (size_t)(p + 1) * bn64, c->eff.p, bn64 * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
     return DRP_OK;
 }
 
-// One predict_one_step (model/gnn_dyn.py:209-254) [+ gen_s_delta, planners.py:346] for B samples.
+// One predict_one_step (model/gnn_dyn.py:209-254) [+ gen_s_delta, planners.py:346] for B samples: planned once
+// (dispatch.h: plan_step), every variant the plan launches marked here, then carried out
 int run_step(drp_ctx* c, const StepArgs& a) {
     const int B = a.B, N = a.N;
     hipStream_t st = c->stream;
@@ -574,41 +489,38 @@ int run_step(drp_ctx* c, const StepArgs& a) {
     int16_t* nbr_idx = ptr<int16_t>(c->nbr_idx);
     uint8_t* nbr_cnt = ptr<uint8_t>(c->nbr_cnt);
     const float* vw = ptr<float>(c->w_valu);
-    a.encoded = false;
+    const StepPlan k = plan_step(c->pol, c->n_cu, step_shape(c, a));
+    k.mark(c->dv_hit);
     if (a.build_graph) {
         ProbeScope ps(c, KC_GRAPH);
         const int self_first = (c->engine == DRP_ENGINE_FUSED && a.cself != nullptr) ? 1 : 0;
-        if (a.rev_off != nullptr && N <= GRAPH_THREADS && c->graph_rev) {
-            c->dv(DV_GRAPH_REV);
-            hipLaunchKernelGGL(k_graph_rev, dim3(SPREAD_GRID(B)), dim3(GRAPH_THREADS), (size_t)12 * N * sizeof(int), st, a.s_prev,
+        switch (k.graph.kind) {
+        case GraphPlan::REV:
+            // the GD planner's forward, samples of one graph chunk: the reversed lists in the lists' own launch
+            hipLaunchKernelGGL(k_graph_rev, dim3((unsigned)k.graph.grid), dim3(GRAPH_THREADS), (size_t)12 * N * sizeof(int), st, a.s_prev,
                                a.prev_mod, a.prev_stride, a.actions, a.act_stride, s_delta, N, nbr_idx, nbr_cnt, c->cam, c->thr,
                                B, self_first, a.rev_off, a.rev);
             if (a.rev_built) *a.rev_built = true;
-        } else if (graph_takes_q4(c, B, N, a.padded) && a.actions == nullptr && c->engine == DRP_ENGINE_FUSED && c->graph_encode &&
-                   !step_has_phase_e(c, B, N)) {
+            break;
+        case GraphPlan::Q4_ENCODE:
             // a handful of samples whose impulses are data (the trainer's forward pass): the lists and the particle encoder
             // read nothing of one another -- one launch (k_rollout.h)
-            const int chunks = (N + 127) / 128, n_graph = B * chunks;
-            const long node_tiles = (long)B * ((N + 31) / 32);
-            const bool tape = a.eff_hist != nullptr;
-            c->dv(DV_GRAPH_Q4_ENCODE);
-            hipLaunchKernelGGL(km_graph_q4_encode, dim3((unsigned)(n_graph + mfma_grid_spread(c, node_tiles))), dim3(GRAPH_Q4_THREADS),
+            hipLaunchKernelGGL(km_graph_q4_encode, dim3((unsigned)(k.graph.grid + mfma_grid_spread(c, (long)B * ((N + 31) / 32)))), dim3(GRAPH_Q4_THREADS),
                                KM_GRAPH_Q4_ENCODE_LDS(N), st, a.s_prev, a.prev_mod, a.prev_stride, s_delta, N, B, nbr_idx, nbr_cnt, c->cam,
-                               c->thr, chunks, self_first, n_graph, ptr<uint16_t>(c->w_split6), ptr<float>(c->w_mfma), a.attr, a.attr_mod,
-                               a.dens, a.dens_mod, tape ? a.eff_hist : ptr<float>(c->eff), ptr<float>(c->c_node), ptr<float>(c->proj));
-            a.encoded = true;
-        } else {
-            launch_graph(c, st, a.s_prev, a.prev_mod, a.prev_stride, a.actions, a.act_stride, s_delta, B, N, nbr_idx, nbr_cnt,
-                         self_first, a.padded);
+                               c->thr, k.graph.chunks, self_first, (int)k.graph.grid, ptr<uint16_t>(c->w_split6), ptr<float>(c->w_mfma), a.attr, a.attr_mod,
+                               a.dens, a.dens_mod, k.tape ? a.eff_hist : ptr<float>(c->eff), ptr<float>(c->c_node), ptr<float>(c->proj));
+            break;
+        default:
+            launch_graph(c, st, k.graph, a.s_prev, a.prev_mod, a.prev_stride, a.actions, a.act_stride, s_delta, B, N, nbr_idx, nbr_cnt, self_first);
+            break;
         }
     }
     if (c->engine != DRP_ENGINE_VALU) {
-        int rc = run_step_mfma(c, a);
+        int rc = run_step_mfma(c, a, k);
         if (rc != DRP_OK) return rc;
         HIPCHK(c, hipGetLastError());
         return DRP_OK;
     }
-    c->dv(DV_VALU_STEP);
     {
         ProbeScope ps(c, KC_NODE_ENCODE);
         hipLaunchKernelGGL(k_node_encode<8>, dim3(B), dim3(256), 0, st, vw, s_delta, a.attr,
@@ -626,7 +538,7 @@ int run_step(drp_ctx* c, const StepArgs& a) {
             hipLaunchKernelGGL(k_project<8>, dim3(B), dim3(256), 0, st, vw, ptr<float>(c->eff), N,
                                ptr<float>(c->proj));
         }
-        launch_aggregate(c, B, N);
+        launch_aggregate(c, k.agg, B, N);
         {
             ProbeScope ps(c, KC_UPDATE);
             hipLaunchKernelGGL(k_update<8>, dim3(B), dim3(256), 0, st, vw, ptr<float>(c->agg),
@@ -660,7 +572,7 @@ int prepare_cself(drp_ctx* c, int attr_mod, int N, int B, const float** cself, c
     if (engine < 0) engine = c->engine;
     *cself = nullptr;
     *cself_ok = nullptr;
-    if (engine == DRP_ENGINE_FUSED && c->self_const) {
+    if (engine == DRP_ENGINE_FUSED && c->pol.self_const) {
         CHK(ensure(c, c->cself, (size_t)B * 64 * sizeof(float) + (size_t)B));
         float* cs = ptr<float>(c->cself);
         uint8_t* ok = reinterpret_cast<uint8_t*>(cs + (size_t)B * 64);
@@ -691,27 +603,17 @@ int run_rollout(drp_ctx* c, int nb, int N, int B, int H, bool reward_all, bool r
         CHK(prepare_cself(c, nb, N, B, &cself, &cself_ok));
         if (session) { c->mpc_cself_tag = c->cself_tag; c->mpc_cself = cself; c->mpc_cself_ok = cself_ok; }
     }
-    // small piles on the fused engine: the whole rollout is ONE launch (km_rollout, k_rollout.h) -- a workgroup owns its
-    // samples from the first step to the last, builds their neighbour lists itself and keeps the node matrices in LDS
-    // A cached shape (drp_ctx::ec_shape: by the pile size alone) gives a workgroup at most ec_rows_cap rows; a batch that needs
-    // more goes out as several launches over consecutive blocks of samples (whole multiples of the batch columns)
-    const bool ec = c->engine == DRP_ENGINE_FUSED && c->ec_shape(N);
-    long chunk_r = B;
-    if (ec) { const long cap = c->ec_chunk(N, nb); if (cap > 0 && cap < B) chunk_r = cap; }
-    const int spw_r = (int)((std::min((long)B, chunk_r) + c->n_cu - 1) / c->n_cu);
-    // up to rollout_max_n particles whatever the batch; up to rollout_mid_n while a workgroup holds no more than rollout_mid_rows
-    const bool roll_size = N <= c->rollout_max_n || (N <= c->rollout_mid_n && (long)spw_r * N <= c->rollout_mid_rows && (N <= 200 || B >= c->n_cu / 2));
-    const bool one_launch = c->engine == DRP_ENGINE_FUSED && c->rollout_fused && c->prop3 && c->prop3e && roll_size &&
-                            whole_samples(c, B, N) && ((long)spw_r * N + 31) / 32 >= c->prop3_min_tiles &&
-                            (long)spw_r * N <= KM_ROLLOUT_MAX_ROWS && (long)spw_r * N <= c->rollout_max_rows;
+    // small piles on the fused engine: the whole rollout is ONE launch per block of samples (dispatch.h: plan_rollout)
+    const RolloutPlan k = plan_rollout(c->pol, c->n_cu, c->engine, B, N, nb, c->work_ptr() != nullptr, c->deg());
+    k.mark(c->dv_hit);
+    const bool one_launch = k.one_launch;
     if (one_launch) {
-        const int n_chunks = (int)((B + chunk_r - 1) / chunk_r);
+        const int n_chunks = k.blocks.n;
         std::vector<RolloutArgs> blocks((size_t)n_chunks);
-        std::vector<char> pairs((size_t)n_chunks);
-        if (ec) CHK(ensure(c, c->ecache, (size_t)((std::min((long)B, chunk_r) + spw_r - 1) / spw_r) * drp_ctx::ecache_stride((long)spw_r * N, false) * 16));
+        if (k.blocks.cache) CHK(ensure(c, c->ecache, k.blocks.cache_bytes));
         for (int q = 0; q < n_chunks; ++q) {
-            const long b_off = (long)q * chunk_r;
-            const int Bc = (int)std::min(chunk_r, (long)B - b_off);
+            const Block b = k.blocks.block(q);
+            const long b_off = b.b_off;
             const size_t ro = (size_t)b_off * N;
             RolloutArgs& ra = blocks[(size_t)q];
             ra = RolloutArgs{};
@@ -725,12 +627,10 @@ int run_rollout(drp_ctx* c, int nb, int N, int B, int H, bool reward_all, bool r
             ra.nbr_cnt = ptr<uint8_t>(c->nbr_cnt) + ro; ra.proj_a = ptr<float>(c->proj) + ro * 128; ra.proj_b = ptr<float>(c->proj2) + ro * 128;
             ra.c_node = ptr<float>(c->c_node) + ro * 64; ra.eff = ptr<float>(c->eff) + ro * 64;
             ra.cself = cself ? cself + (size_t)b_off * 64 : nullptr; ra.cself_ok = cself_ok ? cself_ok + b_off : nullptr;
-            ra.N = N; ra.B = Bc; ra.spw = (Bc + c->n_cu - 1) / c->n_cu; ra.nb = nb; ra.H = H; ra.order_rows = (c->prop3_order ? 1 : 0);
+            ra.N = N; ra.B = b.Bc; ra.spw = b.spw; ra.nb = nb; ra.H = H; ra.order_rows = (c->pol.prop3_order ? 1 : 0);
             ra.thr = c->thr; ra.re_scale = c->re_scale; ra.re_inv = c->re_inv; ra.cam = c->cam;
-            const bool pair_q = c->prop_pair(ra.spw, N, B);
-            pairs[(size_t)q] = pair_q ? 1 : 0;
-            ra.ec_stride = drp_ctx::ecache_stride((long)ra.spw * N, pair_q);
-            ra.ecache = ec ? ptr<float4>(c->ecache) : nullptr;
+            ra.ec_stride = b.ec_stride;
+            ra.ecache = k.blocks.cache ? ptr<float4>(c->ecache) : nullptr;
             ra.work = c->work_ptr();
         }
         // the argument blocks sit in device memory; they are uploaded when they change (every iteration of an MPC session
@@ -743,26 +643,13 @@ int run_rollout(drp_ctx* c, int nb, int N, int B, int H, bool reward_all, bool r
             c->roll_args_valid = true;
         }
         ProbeScope ps(c, KC_PROP);
-        c->dv(DV_GRAPH_IN_ROLLOUT);
         for (int q = 0; q < n_chunks; ++q) {
-            const RolloutArgs& ra = blocks[(size_t)q];
-            const bool pair_r = pairs[(size_t)q] != 0;
-            const unsigned grid_r = (unsigned)((ra.B + ra.spw - 1) / ra.spw);
-            // ONE: no more tiles than waves in a workgroup -- the cached kernel then hands a tile's own rows (P_r, its own P_s, its
-            // effect) from one propagation step to the next in registers
-            const long tiles_r = pair_r ? ((long)ra.spw * N + 15) / 16 : ((long)ra.spw * N + 31) / 32;
-            const bool one = ec && tiles_r <= PROP_WAVES;
-#define ROLLOUT_LAUNCH_W(PAIR_, EC_, WORK_, ONE_) hipLaunchKernelGGL((km_rollout<PAIR_, EC_, WORK_, ONE_>), dim3(grid_r), dim3(64 * PROP_WAVES), KM_ROLLOUT_LDS, \
-                                                                     c->stream, ptr<RolloutArgs>(c->roll_args) + q)
-#define ROLLOUT_LAUNCH(PAIR_, EC_, ONE_) do { if (ra.work) ROLLOUT_LAUNCH_W(PAIR_, EC_, true, ONE_); else ROLLOUT_LAUNCH_W(PAIR_, EC_, false, ONE_); } while (0)
-            c->dv(DV_ROLLOUT + 6 * (pair_r ? 1 : 0) + 2 * (one ? 2 : ec ? 1 : 0) + (ra.work ? 1 : 0));
-            if (pair_r) { if (one) ROLLOUT_LAUNCH(true, true, true); else if (ec) ROLLOUT_LAUNCH(true, true, false); else ROLLOUT_LAUNCH(true, false, false); }
-            else { if (one) ROLLOUT_LAUNCH(false, true, true); else if (ec) ROLLOUT_LAUNCH(false, true, false); else ROLLOUT_LAUNCH(false, false, false); }
-#undef ROLLOUT_LAUNCH_W
-#undef ROLLOUT_LAUNCH
+            const Block b = k.blocks.block(q);
+            hipLaunchKernelGGL(prop_tables().rollout[k.flags(b).index()], dim3((unsigned)b.grid), dim3(64 * PROP_WAVES), KM_ROLLOUT_LDS,
+                               c->stream, ptr<RolloutArgs>(c->roll_args) + q);
         }
         HIPCHK(c, hipGetLastError());
-        note_degrees(c, spw_r, N, B);           // the last step's lists
+        note_degrees(c, k.spw, N, B);           // the last step's lists
     }
     for (int t = 0; t < H && !one_launch; ++t) {
         StepArgs a{};
@@ -840,8 +727,8 @@ void flush_wgrad(drp_ctx* c) {
         J.j[q].part = static_cast<float*>(c->tr_part.p) + (size_t)q * KT_WGRAD_MAX_BLOCKS * 66 * 64;
         if (J.j[q].blocks > max_blocks) max_blocks = J.j[q].blocks;
     }
-    c->dv(c->wgrad_mfma ? DV_WGRAD_MFMA : DV_WGRAD_VALU);
-    if (c->wgrad_mfma)
+    c->dv(c->pol.wgrad_mfma ? DV_WGRAD_MFMA : DV_WGRAD_VALU);
+    if (c->pol.wgrad_mfma)
         hipLaunchKernelGGL(kt_wgrad_mfma_multi, dim3((unsigned)max_blocks, (unsigned)n), dim3(256), KT_WGRAD_MULTI_LDS, c->stream, J);
     else
         hipLaunchKernelGGL(kt_wgrad_multi, dim3((unsigned)max_blocks, (unsigned)n), dim3(256), KT_WGRAD_MULTI_LDS, c->stream, J);
@@ -892,14 +779,14 @@ int flush_wgrad_all(drp_ctx* c) {
         CHK(h2d(c, c->wg_idx_dev, c->wg_uploaded.data() + jb, ib));
     }
     c->dv(DV_WGRAD_DEFERRED);
-    c->dv(c->wgrad_mfma ? DV_WGRAD_MFMA : DV_WGRAD_VALU);
+    c->dv(c->pol.wgrad_mfma ? DV_WGRAD_MFMA : DV_WGRAD_VALU);
     const WgradJob* jd = static_cast<const WgradJob*>(c->wg_jobs_dev.p);
     const int* od = static_cast<const int*>(c->wg_idx_dev.p);
     for (int a = 0; a < n;) {
         int b = a;
         while (b < n && c->wg_jobs[order[b]].blocks == c->wg_jobs[order[a]].blocks) ++b;
         const dim3 grid((unsigned)c->wg_jobs[order[a]].blocks, (unsigned)(b - a));
-        if (c->wgrad_mfma) hipLaunchKernelGGL(kt_wgrad_mfma_list, grid, dim3(256), KT_WGRAD_MULTI_LDS, c->stream, jd, od, a);
+        if (c->pol.wgrad_mfma) hipLaunchKernelGGL(kt_wgrad_mfma_list, grid, dim3(256), KT_WGRAD_MULTI_LDS, c->stream, jd, od, a);
         else hipLaunchKernelGGL(kt_wgrad_list, grid, dim3(256), KT_WGRAD_MULTI_LDS, c->stream, jd, od, a);
         a = b;
     }
@@ -995,7 +882,7 @@ int run_tape_forward(drp_ctx* c, int engine, int B, int N, int H, const TapeFwd&
 // the reversed lists of `sets` samples' neighbour lists into rev_off / rev, a workgroup each; `nums` (nullable): the
 // particle counts, set s reading nums[s % nums_mod] (0: nums[s])
 void launch_reverse_lists(drp_ctx* c, const int16_t* idx, const uint8_t* cnt, int N, int sets, const int* nums, int nums_mod) {
-    const bool rev_lds = N <= KB_REV_LDS_MAX_N && !c->rev_global_only;
+    const bool rev_lds = N <= KB_REV_LDS_MAX_N && !c->pol.rev_global_only;
     ProbeScope ps(c, KC_BWD_LISTS);
     c->dv(N <= 512 ? DV_REV_256 : DV_REV_1024);
     if (N <= 512)

@@ -71,26 +71,10 @@ int train_forward_backward(drp_ctx* c, int B, int N, bool backward) {
     // too; slot 0 of g_eff is the transient copy the predictor writes and the particle encoder reads)
     const bool defer = c->wg_defer_now;
     const size_t per_t = defer ? 1 : 0;
-    // The node stages of a rollout step in ONE launch (kmb_step_bwd<dump>): it needs every dump in a buffer of its own (the
-    // deferred weight gradients' layout).  A group of `f_spw` samples is shared by `f_parts` workgroups, the grid at most one
-    // workgroup per CU (the kernel's barrier in memory).  It pays for a handful of tiles only (the reference's batch of
-    // 4 x <= 300 particles: 40): every tile is a chain of memory round trips, and the stage kernels spread the same gathers
-    // over more threads (32 x 300: 2.6 ms per iteration staged, 4.3 in one launch)
-    const long f_tiles = (long)B * ((N + 31) / 32);
-    const bool fused = defer && c->bwd_fused && (c->train_fused >= 0 ? c->train_fused != 0 : f_tiles <= c->n_cu / 4);
-    const int f_spw = (B + c->n_cu - 1) / c->n_cu, f_groups = (B + f_spw - 1) / f_spw;
-    int f_parts = 1;
-    bool f_coop = false;
-    if (fused) {
-        const int group_tiles = (int)(((long)f_spw * N + 31) / 32);
-        f_parts = c->train_parts > 0 ? c->train_parts : c->n_cu / f_groups;
-        if (f_parts > c->n_cu / f_groups) f_parts = c->n_cu / f_groups;
-        if (f_parts > group_tiles) f_parts = group_tiles;
-        if (f_parts < 1) f_parts = 1;
-        // a handful of tiles per workgroup: all eight waves gather a tile's edge terms (a wave on its own is one long chain of
-        // L2 round trips per tile and phase: 27 us against 6); many: a tile per wave, the waves hide each other's latency
-        f_coop = c->train_coop >= 0 ? c->train_coop != 0 : (group_tiles + f_parts - 1) / f_parts <= 2 * KMB_COOP_SLOTS;
-    }
+    // the node stages of a rollout step in ONE launch (kmb_step_bwd<dump>) or a launch per stage (dispatch.h: plan_train_backward)
+    const TrainBwdPlan k = plan_train_backward(c->pol, c->n_cu, B, N, defer);
+    const bool fused = k.fused, f_coop = k.coop;
+    const int f_spw = k.spw, f_groups = k.groups, f_parts = k.parts;
     unsigned* const f_bar = reinterpret_cast<unsigned*>(G + TR_GRAD_PAD);        // [H][f_groups] arrival counters, then the give-up flag
     for (int t = H - 1; t >= 0; --t) {
         const size_t tt = per_t * (size_t)t;
@@ -124,7 +108,7 @@ int train_forward_backward(drp_ctx* c, int B, int N, bool backward) {
         if (fused) {
             // everything between the loss gradient and the relation encoder's backward in ONE launch (kmb_step_bwd<DUMP>): the
             // operands of the weight gradients are its dumps; the jobs in the stage kernels' queue order
-            c->dv(f_coop ? DV_TRAIN_NODE_FUSED_COOP : DV_TRAIN_NODE_FUSED);
+            c->dv(k.variant());
 #define STEP_BWD_ARGS ptr<float>(c->w_mfma), ptr<float>(c->w_mfma_bwd), s.eht, s.mht, s.cnt, s.rev_off, s.rev, g_out, (size_t)N * 3, \
                       s.sdelta, ptr<float>(c->attr), B, dens, B, N, B, f_spw, s.ge_tmp, s.g_cnode, s.gah, ptr<float>(c->g_sdelta), s.d, \
                       f_parts, f_bar + (size_t)t * f_groups, f_bar + (size_t)H * f_groups
@@ -141,7 +125,7 @@ int train_forward_backward(drp_ctx* c, int B, int N, bool backward) {
             wg.cnode(s);
             wg.encoder(s);
         } else {
-            c->dv(DV_TRAIN_NODE_MFMA);
+            c->dv(k.variant());
             launch_node_stages(c, s, egrid, chunks16, &wg);
         }
         // the previous step's output feeds this step as s_cur: residual + relation encoder
@@ -404,9 +388,9 @@ int drp_train_step(drp_ctx* c, const float* states, const float* states_delta, c
             if (mode == DRP_TRAIN_UPDATE) c->tr_iter += 1;
             break;
         }
-        if (attempt > 0 || c->train_parts == 1)
+        if (attempt > 0 || c->pol.train_parts == 1)
             return fail(c, DRP_EHIP, "kmb_step_bwd: a workgroup waited two seconds for the others of its group, with one workgroup per group too");
-        c->train_parts = 1;                     // the device is shared or masked: the groups' workgroups are not all resident
+        c->pol.train_parts = 1;                     // the device is shared or masked: the groups' workgroups are not all resident
         c->dv(DV_TRAIN_BARRIER_RETRY);
     }
     if (loss_out) {

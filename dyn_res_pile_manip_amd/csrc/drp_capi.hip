@@ -47,6 +47,7 @@
 #include "k_ptcl_dataset.h"
 #include "k_prop_inst.h"       // km_prop / km_prop3 / km_rollout: declared here, instantiated in inst_*.hip
 
+#include "dispatch.h"          // host-only: policy, variant flags, plan functions
 #include "capi_ctx.h"
 #include "capi_pipeline.h"
 
