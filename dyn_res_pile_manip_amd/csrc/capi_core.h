@@ -1,5 +1,4 @@
-// capi_core.h -- a section of the C ABI's translation unit (textually included by drp_capi.hip, in this order: capi_ctx.h,
-// capi_pipeline.h, then inside extern "C": capi_core.h, capi_mpc.h, capi_prep.h, capi_gd.h, capi_train.h, capi_comm.h, capi_debug.h).
+// capi_core.h -- a section of the C ABI's translation unit (textually included by drp_capi.hip, which has the order of the sections).
 // Here: life cycle, model constants and the single operations on host buffers (drp_create ... drp_reward).
 
 int drp_create(int device, drp_ctx** out) {
@@ -12,13 +11,10 @@ int drp_create(int device, drp_ctx** out) {
     if (device < 0 || device >= n) return fail(nullptr, DRP_EINVAL, "device %d out of range (%d)", device, n);
     e = hipSetDevice(device);
     if (e != hipSuccess) return fail(nullptr, DRP_EHIP, "hipSetDevice: %s", hipGetErrorString(e));
-    drp_ctx* c = new drp_ctx();
+    std::unique_ptr<drp_ctx> c(new drp_ctx());      // a failure exit below destroys it, its stream included
     c->device = device;
-    e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        delete c;
-        return fail(nullptr, DRP_EHIP, "hipStreamCreate: %s", hipGetErrorString(e));
-    }
+    e = hipStreamCreateWithFlags(&c->stream.s, hipStreamNonBlocking);
+    if (e != hipSuccess) return fail(nullptr, DRP_EHIP, "hipStreamCreate: %s", hipGetErrorString(e));
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
         c->n_cu = prop.multiProcessorCount;
@@ -41,11 +37,8 @@ int drp_create(int device, drp_ctx** out) {
         hipFuncSetAttribute((const void*)kb_reverse_lists<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)KB_REV_LDS(KB_REV_LDS_MAX_N, 1)) != hipSuccess ||
         hipFuncSetAttribute((const void*)kb_reverse_lists<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)KB_REV_LDS(KB_REV_LDS_MAX_N, 1)) != hipSuccess ||
         hipFuncSetAttribute((const void*)k_aggregate_lds, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            K_AGG_LDS_MAX_N * 256) != hipSuccess) {
-        (void)hipStreamDestroy(c->stream);
-        delete c;
+                            K_AGG_LDS_MAX_N * 256) != hipSuccess)
         return fail(nullptr, DRP_EHIP, "hipFuncSetAttribute (dynamic LDS size of k_graph, kb_reverse_lists or k_aggregate_lds) failed");
-    }
     // the MFMA kernels keep packed weights + per-wave transposition tiles in LDS (> 64 KiB)
     if (hipFuncSetAttribute((const void*)km_edge_encode, hipFuncAttributeMaxDynamicSharedMemorySize, KM_EDGE_LDS) != hipSuccess ||
         hipFuncSetAttribute((const void*)km_node_encode, hipFuncAttributeMaxDynamicSharedMemorySize, KM_NODE_LDS) != hipSuccess ||
@@ -60,13 +53,10 @@ int drp_create(int device, drp_ctx** out) {
         hipFuncSetAttribute((const void*)kt_wgrad_multi, hipFuncAttributeMaxDynamicSharedMemorySize, KT_WGRAD_MULTI_LDS) != hipSuccess ||
         hipFuncSetAttribute((const void*)kt_wgrad_mfma_multi, hipFuncAttributeMaxDynamicSharedMemorySize, KT_WGRAD_MULTI_LDS) != hipSuccess ||
         hipFuncSetAttribute((const void*)km_update<false>, hipFuncAttributeMaxDynamicSharedMemorySize, KM_UPD_LDS) != hipSuccess ||
-        hipFuncSetAttribute((const void*)km_update<true>, hipFuncAttributeMaxDynamicSharedMemorySize, KM_UPD_LDS) != hipSuccess) {
-        (void)hipStreamDestroy(c->stream);
-        delete c;
+        hipFuncSetAttribute((const void*)km_update<true>, hipFuncAttributeMaxDynamicSharedMemorySize, KM_UPD_LDS) != hipSuccess)
         return fail(nullptr, DRP_EHIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-    }
     c->engine = DRP_ENGINE_FUSED;
-    *out = c;
+    *out = c.release();
     return DRP_OK;
 }
 
@@ -76,44 +66,7 @@ void drp_destroy(drp_ctx* c) {
     (void)guarded_wait(c, nullptr);           // a collective that cannot finish must not keep the destructor
     helpers_wait(5.0, c);                     // no helper thread of this context (an abort, an init) inside RCCL while its stream goes away
     if (c->comm) { RcclApi* R = rccl_api(); if (R) (void)R->CommDestroy(c->comm); c->comm = nullptr; }
-    DevBuf* bufs[] = {&c->probe_work, &c->ecache, &c->tape_mask, &c->g_agg_hist, &c->rev_off, &c->rev, &c->gpos_edge, &c->tape_sdelta, &c->tape_idx, &c->tape_cnt, &c->eff_hist, &c->g_eff, &c->g_cnode, &c->g_agg, &c->g_proj, &c->g_state,
-                      &c->g_sdelta, &c->g_act, &c->adam_m, &c->adam_v, &c->w_raw, &c->w_valu, &c->w_mfma, &c->w_mfma_bwd, &c->w_split, &c->w_split6, &c->w_split6_bwd, &c->proj2, &c->goal_field, &c->goal_coor, &c->s_in,
-                      &c->attr, &c->dens, &c->s_delta, &c->nbr_idx, &c->nbr_cnt, &c->eff, &c->c_node,
-                      &c->agg, &c->proj, &c->c_edge, &c->states, &c->actions, &c->rewards, &c->s_out,
-                      &c->scratch, &c->nominal, &c->noise, &c->partials, &c->gathered, &c->stats, &c->elite, &c->elite_all, &c->xchg, &c->cself,
-                      &c->px_depth, &c->px_mask, &c->px_blk, &c->px_bmin, &c->px_bmax, &c->px_grid, &c->px_pcd, &c->px_keys,
-                      &c->px_cellcnt, &c->px_cellfill, &c->px_celloff, &c->px_list, &c->px_down, &c->px_down32, &c->px_init,
-                      &c->px_dist, &c->px_chosen, &c->px_pts, &c->px_r, &c->px_rr, &c->px_out,
-                      &c->gl_goal, &c->gl_seg, &c->gl_tmp, &c->gl_dist, &c->gl_blk, &c->gl_pix, &c->gl_fps,
-                      &c->tr_part, &c->tr_arena, &c->re_shift_dev, &c->tr_grad, &c->tr_m, &c->tr_v, &c->tr_loss, &c->agg_hist,
-                      &c->tr_hact, &c->tr_gh, &c->tr_gpe, &c->tr_a1n, &c->tr_gh1, &c->tr_xn, &c->ed_re, &c->ed_a2, &c->ed_a1,
-                      &c->ed_x0, &c->ed_gce, &c->ed_g3, &c->ed_g2, &c->ed_g1, &c->roll_args, &c->map_valu, &c->map_mfma, &c->map_mfma_bwd,
-                      &c->wg_jobs_dev, &c->wg_idx_dev,
-                      &c->rgr_w, &c->rgr_raw, &c->rgr_x, &c->rgr_a[0], &c->rgr_a[1], &c->rgr_a[2], &c->rgr_a[3], &c->rgr_a[4],
-                      &c->rgr_f[0], &c->rgr_f[1], &c->rgr_f[2], &c->rgr_f[3], &c->rgr_slab, &c->rgr_out, &c->rgr_mask,
-                      &c->rgr_dtmp, &c->rgr_dist, &c->rgr_tab, &c->rgr_m, &c->rgr_v, &c->rgr_g, &c->rgr_gfull, &c->rgr_dz[0],
-                      &c->rgr_dz[1], &c->rgr_gf, &c->rgr_bpart, &c->rgr_l1, &c->rgr_lossp, &c->rgr_tgt,
-                      &c->pd_in, &c->pd_blk, &c->pd_meta, &c->pd_pcd, &c->pd_dist, &c->pd_chosen, &c->pd_rec, &c->pd_near,
-                      &c->pd_out};
-    for (DevBuf* b : bufs)
-        if (b->p) (void)hipFree(b->p);
-    for (hipEvent_t ev : c->probe_ev) (void)hipEventDestroy(ev);
-    for (int q = 0; q < DRP_GD_SLOTS; ++q) {
-        if (c->gd_pin[q]) (void)hipHostFree(c->gd_pin[q]);
-        if (c->gd_ev[q]) (void)hipEventDestroy(c->gd_ev[q]);
-    }
-    for (int q = 0; q < 2; ++q) {
-        if (c->mpc_pin[q]) (void)hipHostFree(c->mpc_pin[q]);
-        if (c->mpc_ev[q]) (void)hipEventDestroy(c->mpc_ev[q]);
-    }
-    if (c->w_pin) (void)hipHostFree(c->w_pin);
-    if (c->tr_pin) (void)hipHostFree(c->tr_pin);
-    if (c->pd_pin) (void)hipHostFree(c->pd_pin);
-    for (hipEvent_t ev : c->pd_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    if (c->deg_stat) (void)hipHostFree(c->deg_stat);
-    (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                                 // every member frees what it owns (capi_ctx.h), the stream last
 }
 
 const char* drp_last_error(const drp_ctx* c) { return c ? c->err.c_str() : g_create_error.c_str(); }
@@ -148,31 +101,24 @@ int drp_load_weights(drp_ctx* c, const float* blob, size_t n_floats, float adj_t
     if (n_floats != (size_t)W_TOTAL)
         return fail(c, DRP_EINVAL, "weight blob has %zu floats, expected %d", n_floats, (int)W_TOTAL);
     HIPCHK(c, hipSetDevice(c->device));
-    std::vector<float> v;
+    // the packed host images: every upload below is only enqueued, so they live until the one wait
+    std::vector<float> v, m, mbv;
+    std::vector<uint16_t> sp, sp6;
     pack_valu(blob, v);
     CHK(h2d(c, c->w_raw, blob, n_floats * sizeof(float)));
     CHK(h2d(c, c->w_valu, v.data(), v.size() * sizeof(float)));
-    {
-        std::vector<float> m;
-        pack_mfma(blob, m);
-        CHK(h2d(c, c->w_mfma, m.data(), m.size() * sizeof(float)));
-        std::vector<float> mbv;
-        pack_mfma_bwd(blob, mbv);
-        CHK(h2d(c, c->w_mfma_bwd, mbv.data(), mbv.size() * sizeof(float)));
-        CHK(guarded_wait(c, nullptr));     // mbv is about to go out of scope... kept alive until here
-        set_split_range(c, blob);
-        std::vector<uint16_t> sp;
-        pack_split(blob, sp, c->re_range.shift);
-        CHK(h2d(c, c->w_split, sp.data(), sp.size() * sizeof(uint16_t)));
-        std::vector<uint16_t> sp6;
-        pack_split6(blob, sp6);
-        CHK(h2d(c, c->w_split6, sp6.data(), sp6.size() * sizeof(uint16_t)));
-        // the transposed layers of the GD planner's backward pass in the same split: packed on the device from the raw blob
-        CHK(ensure(c, c->w_split6_bwd, (size_t)SB6_TOTAL * 16));
-        hipLaunchKernelGGL(kt_repack_split6_bwd, dim3(6 * 16), dim3(256), 0, c->stream, ptr<float>(c->w_raw), ptr<uint16_t>(c->w_split6_bwd));
-        CHK(guarded_wait(c, nullptr));     // sp6 too
-        CHK(guarded_wait(c, nullptr));     // m, sp are about to go out of scope
-    }
+    pack_mfma(blob, m);
+    CHK(h2d(c, c->w_mfma, m.data(), m.size() * sizeof(float)));
+    pack_mfma_bwd(blob, mbv);
+    CHK(h2d(c, c->w_mfma_bwd, mbv.data(), mbv.size() * sizeof(float)));
+    set_split_range(c, blob);
+    pack_split(blob, sp, c->re_range.shift);
+    CHK(h2d(c, c->w_split, sp.data(), sp.size() * sizeof(uint16_t)));
+    pack_split6(blob, sp6);
+    CHK(h2d(c, c->w_split6, sp6.data(), sp6.size() * sizeof(uint16_t)));
+    // the transposed layers of the GD planner's backward pass in the same split: packed on the device from the raw blob
+    CHK(ensure(c, c->w_split6_bwd, (size_t)SB6_TOTAL * 16));
+    hipLaunchKernelGGL(kt_repack_split6_bwd, dim3(6 * 16), dim3(256), 0, c->stream, ptr<float>(c->w_raw), ptr<uint16_t>(c->w_split6_bwd));
     CHK(guarded_wait(c, nullptr));
     c->w_host.assign(blob, blob + n_floats);
     c->adj_thresh = adj_thresh;

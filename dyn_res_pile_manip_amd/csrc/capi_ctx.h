@@ -1,5 +1,4 @@
-// capi_ctx.h -- a section of the C ABI's translation unit (textually included by drp_capi.hip, in this order: capi_ctx.h,
-// capi_pipeline.h, then inside extern "C": capi_core.h, capi_mpc.h, capi_prep.h, capi_gd.h, capi_train.h, capi_comm.h, capi_debug.h).
+// capi_ctx.h -- a section of the C ABI's translation unit (textually included by drp_capi.hip, which has the order of the sections).
 // Here: the kernel-variant names, the run-time RCCL binding and the context (struct drp_ctx): every workspace, session and switch.
 
 namespace {
@@ -21,10 +20,60 @@ static_assert(ENGINE_VALU == DRP_ENGINE_VALU && ENGINE_MFMA == DRP_ENGINE_MFMA &
               AGG_LDS_MAX_N == K_AGG_LDS_MAX_N && DEG_STAT_ROWS == DEG_STAT_MAX_ROWS && spread_grid(33) == SPREAD_GRID(33),
               "dispatch.h plans with the kernels' own constants");
 
-struct DevBuf {
+// ---- what a context allocates: each resource is owned by the member that holds it ---------------------------------------
+// Move-only; the destructor frees, release() frees now and leaves the owner empty.  A view into somebody else's memory is a
+// plain pointer, never one of these.
+struct DevBuf {                     // device memory (ensure() grows it)
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    ~DevBuf() { (void)release(); }
+    hipError_t release() { const hipError_t e = p ? hipFree(p) : hipSuccess; p = nullptr; cap = 0; return e; }
 };
+
+struct PinBuf {                     // pinned host memory (ensure_pinned() grows it); cap in bytes
+    void* p = nullptr;
+    size_t cap = 0;
+    unsigned flags = hipHostMallocDefault;
+    explicit PinBuf(unsigned f = hipHostMallocDefault) : flags(f) {}
+    PinBuf(const PinBuf&) = delete;
+    PinBuf& operator=(const PinBuf&) = delete;
+    PinBuf(PinBuf&& o) noexcept : p(o.p), cap(o.cap), flags(o.flags) { o.p = nullptr; o.cap = 0; }
+    PinBuf& operator=(PinBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); std::swap(flags, o.flags); return *this; }
+    ~PinBuf() { (void)release(); }
+    hipError_t release() { const hipError_t e = p ? hipHostFree(p) : hipSuccess; p = nullptr; cap = 0; return e; }
+};
+
+struct Event {
+    hipEvent_t ev = nullptr;
+    Event() = default;
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    Event(Event&& o) noexcept : ev(o.ev) { o.ev = nullptr; }
+    Event& operator=(Event&& o) noexcept { std::swap(ev, o.ev); return *this; }
+    ~Event() { (void)release(); }
+    hipError_t create(unsigned flags = hipEventDefault) { return ev ? hipSuccess : hipEventCreateWithFlags(&ev, flags); }   // once
+    hipError_t release() { const hipError_t e = ev ? hipEventDestroy(ev) : hipSuccess; ev = nullptr; return e; }
+};
+
+struct Stream {                     // the context's one stream; reads as the hipStream_t it holds
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream&) = delete;
+    Stream& operator=(const Stream&) = delete;
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+};
+
+static_assert(!std::is_copy_constructible<DevBuf>::value && !std::is_copy_assignable<DevBuf>::value &&
+              !std::is_copy_constructible<PinBuf>::value && !std::is_copy_assignable<PinBuf>::value &&
+              !std::is_copy_constructible<Event>::value && !std::is_copy_assignable<Event>::value &&
+              !std::is_copy_constructible<Stream>::value && !std::is_copy_assignable<Stream>::value,
+              "a resource has one owner");
 
 // ---- RCCL, bound at run time -----------------------------------------------------------------------------------
 // libdrp.so does not link librccl: a process must not end up with two copies of it (PyTorch ships its own
@@ -127,8 +176,8 @@ double now_s() {
 }  // namespace
 
 struct drp_ctx {
+    Stream stream;                  // declared first, so destroyed last: every buffer, pinned block and event below goes before it
     int device = 0;
-    hipStream_t stream = nullptr;
     std::string err;
     int engine = DRP_ENGINE_VALU;
     int n_cu = 256;
@@ -139,10 +188,10 @@ struct drp_ctx {
     bool debug_force_giveup = false; // DRP_DEBUG_FORCE_GIVEUP=1 (tests): drp_train_step's first pass ends as if kmb_step_bwd's barrier had timed out
     // the mean in-degree the last lists of a shape had (k_deg_stat, every few launches): sum | rows << 24 | N << 48 in host memory
     // the device writes; the plans take it decoded (deg()), as an input
-    unsigned long long* deg_stat = nullptr;
-    unsigned long long* deg_stat_dev = nullptr;
+    PinBuf deg_stat{hipHostMallocMapped};
+    unsigned long long* deg_stat_dev = nullptr;     // the device's address of deg_stat
     unsigned deg_tick = 0;
-    DegStat deg() const { return deg_stat ? decode_deg_stat(*reinterpret_cast<volatile const unsigned long long*>(deg_stat)) : DegStat{}; }
+    DegStat deg() const { return deg_stat.p ? decode_deg_stat(*static_cast<volatile const unsigned long long*>(deg_stat.p)) : DegStat{}; }
     DevBuf ecache;                  // the edge-chain cache of the whole-sample kernels (dispatch.h: cut_blocks)
 
     // model constants
@@ -181,16 +230,14 @@ struct drp_ctx {
     int gd_engine = DRP_ENGINE_FUSED, tr_engine = DRP_ENGINE_FUSED;   // which engine writes the tape (pick_tape_engine)
     bool gd_on = false;
     int gd_nb = 0, gd_N = 0, gd_B = 0, gd_H = 0, gd_iter = 0;
-    float* gd_pin[DRP_GD_SLOTS] = {};        // drp_gd_step_async: pinned host copies [B rewards | B*H*4 pushes] of the iterations in flight,
-    size_t gd_pin_floats = 0;                //   written by the iteration's own kernels (kb_reward, k_adam): no copy on the stream
-    hipEvent_t gd_ev[DRP_GD_SLOTS] = {};
+    PinBuf gd_pin[DRP_GD_SLOTS];             // drp_gd_step_async: pinned host copies [B rewards | B*H*4 pushes] of the iterations in flight,
+    Event gd_ev[DRP_GD_SLOTS];               //   written by the iteration's own kernels (kb_reward, k_adam): no copy on the stream
     float* gd_host_rewards = nullptr;        // where the iteration being enqueued writes them (null: device buffers only)
     float* gd_host_actions = nullptr;
     KbAdam gd_adam = KbAdam{};               // gd_iteration: the optimiser step rides on the last kb_sdelta launch (act == null: gradients only)
     bool gd_pending[DRP_GD_SLOTS] = {};
-    float* mpc_pin[2] = {nullptr, nullptr};  // drp_mpc_fetch_async: [B*H*4 pushes | B final rewards] of two iterations in flight
-    size_t mpc_pin_floats = 0;
-    hipEvent_t mpc_ev[2] = {nullptr, nullptr};
+    PinBuf mpc_pin[2];                       // drp_mpc_fetch_async: [B*H*4 pushes | B final rewards] of two iterations in flight
+    Event mpc_ev[2];
     bool mpc_pending[2] = {false, false};
     unsigned gd_cself_tag = 0;      // the self-edge constants of this GD problem are in c->cself while the tags match
     const float* gd_cself = nullptr;
@@ -237,18 +284,16 @@ struct drp_ctx {
 
     // GNN training batches from recorded episodes (capi_ptcl_dataset.h, row x4): workspaces of its own
     DevBuf pd_in, pd_blk, pd_meta, pd_pcd, pd_dist, pd_chosen, pd_rec, pd_near, pd_out;
-    void* pd_pin = nullptr;         // pinned staging: the upload arena, then the counts, then the download
-    size_t pd_pin_cap = 0;
-    hipEvent_t pd_ev[7] = {};       // stage boundaries of the last drp_ptcl_dataset_batch (drp_ptcl_dataset_time)
+    PinBuf pd_pin;                  // pinned staging: the upload arena, then the counts, then the download
+    Event pd_ev[7];                 // stage boundaries of the last drp_ptcl_dataset_batch (drp_ptcl_dataset_time)
     bool pd_timed = false;
     int pd_lastB = 0, pd_nmax = 0;  // shapes of the last batch (debug taps)
 
     // re-packing after an optimiser step on the device (k_train.h): gather maps of the plain packers, pinned copy of the blob
     DevBuf map_valu, map_mfma, map_mfma_bwd;
     bool repack_maps_ready = false;
-    float* w_pin = nullptr;         // pinned: the blob after an optimiser step [W_TOTAL], then the device's range shift (one int)
-    void* tr_pin = nullptr;         // pinned staging of a training batch (drp_train_step: one upload)
-    size_t tr_pin_cap = 0;
+    PinBuf w_pin;                   // pinned: the blob after an optimiser step [W_TOTAL], then the device's range shift (one int)
+    PinBuf tr_pin;                  // pinned staging of a training batch (drp_train_step: one upload)
     DevBuf tr_arena, re_shift_dev;  // the batch as uploaded; the shift kt_repack_all derived
     bool repack_device = true;      // DRP_NO_REPACK_DEVICE=1: fetch the blob and run the host packers (the round-2 path)
 
@@ -270,7 +315,7 @@ struct drp_ctx {
                                     // counting costs the 300-particle launch 8 %)
     unsigned long long* work_ptr() const { return (probe_cls == KC_PROP && probe_count) ? static_cast<unsigned long long*>(probe_work.p) : nullptr; }
     int probe_cls = -1;
-    std::vector<hipEvent_t> probe_ev;
+    std::vector<Event> probe_ev;
     size_t probe_used = 0;
 };
 

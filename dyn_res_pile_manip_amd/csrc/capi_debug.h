@@ -1,5 +1,4 @@
-// capi_debug.h -- a section of the C ABI's translation unit (textually included by drp_capi.hip, in this order: capi_ctx.h,
-// capi_pipeline.h, then inside extern "C": capi_core.h, capi_mpc.h, capi_prep.h, capi_gd.h, capi_train.h, capi_comm.h, capi_debug.h).
+// capi_debug.h -- a section of the C ABI's translation unit (textually included by drp_capi.hip, which has the order of the sections).
 // Here: measurement and debugging entry points (probes, dispatch introspection, range info, buffer fetch).
 
 // ---- measurement / debugging -----------------------------------------------------------------
@@ -80,7 +79,7 @@ int drp_probe_read(drp_ctx* c, double* total_ms, long* launches) {
     long n = 0;
     for (size_t i = 0; i + 1 < c->probe_used; i += 2) {
         float ms = 0.0f;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->probe_ev[i], c->probe_ev[i + 1]));
+        HIPCHK(c, hipEventElapsedTime(&ms, c->probe_ev[i].ev, c->probe_ev[i + 1].ev));
         tot += ms;
         ++n;
     }
@@ -147,7 +146,9 @@ long drp_debug_fetch(drp_ctx* c, const char* name, void* out, size_t out_bytes) 
     if (!c || !name || !out) return DRP_EINVAL;
     const size_t bn = (size_t)c->lastB * c->lastN;
     const DevBuf* b = nullptr;
-    DevBuf tap{};
+    bool part = false;              // fetch `view` (a part of a buffer, not owned; view_cap bytes from there on) instead of *b
+    const void* view = nullptr;
+    size_t view_cap = 0;
     size_t bytes = 0;
     if (!strcmp(name, "s_delta")) { b = &c->s_delta; bytes = bn * 3 * 4; }
     else if (!strcmp(name, "nbr_idx")) { b = &c->nbr_idx; bytes = bn * DRP_K * 2; }
@@ -177,22 +178,23 @@ long drp_debug_fetch(drp_ctx* c, const char* name, void* out, size_t out_bytes) 
     // the GNN dataset's intermediates of its last batch: foreground counts [B] and sampler picks [B][4097] (int32),
     // recentered points [B][n_max][3] (float64), nearest frame-0 particles [B][n_max] (int32)
     else if (!strcmp(name, "pd_nfg")) {
-        tap.p = ptr<long long>(c->pd_meta) + c->pd_lastB; tap.cap = c->pd_meta.cap; b = &tap; bytes = (size_t)c->pd_lastB * 4;
+        b = &c->pd_meta; part = true; view = ptr<long long>(c->pd_meta) + c->pd_lastB; view_cap = c->pd_meta.cap; bytes = (size_t)c->pd_lastB * 4;
     } else if (!strcmp(name, "pd_chosen")) { b = &c->pd_chosen; bytes = (size_t)c->pd_lastB * (PD_CAP + 1) * 4; }
     else if (!strcmp(name, "pd_recenter")) { b = &c->pd_rec; bytes = (size_t)c->pd_lastB * c->pd_nmax * 3 * 8; }
     else if (!strcmp(name, "pd_nearest")) { b = &c->pd_near; bytes = (size_t)c->pd_lastB * c->pd_nmax * 4; }
     else return fail(c, DRP_EINVAL, "unknown buffer '%s'", name);
     // a GD session keeps every step's impulses and lists in its tape, not in the step workspace: the last step's
-    DevBuf tape{};
     if (c->gd_on && c->gd_H > 0 && bn == (size_t)c->gd_B * c->gd_N) {
         const size_t t = (size_t)c->gd_H - 1;
-        if (b == &c->s_delta) { tape.p = ptr<float>(c->tape_sdelta) + t * bn * 3; tape.cap = bytes; b = &tape; }
-        else if (b == &c->nbr_idx) { tape.p = ptr<int16_t>(c->tape_idx) + t * bn * DRP_K; tape.cap = bytes; b = &tape; }
-        else if (b == &c->nbr_cnt) { tape.p = ptr<uint8_t>(c->tape_cnt) + t * bn; tape.cap = bytes; b = &tape; }
+        if (b == &c->s_delta) { part = true; view = ptr<float>(c->tape_sdelta) + t * bn * 3; view_cap = bytes; }
+        else if (b == &c->nbr_idx) { part = true; view = ptr<int16_t>(c->tape_idx) + t * bn * DRP_K; view_cap = bytes; }
+        else if (b == &c->nbr_cnt) { part = true; view = ptr<uint8_t>(c->tape_cnt) + t * bn; view_cap = bytes; }
     }
-    if (!b->p || bytes == 0 || bytes > b->cap) return fail(c, DRP_ESTATE, "buffer '%s' not populated", name);
+    const void* src = part ? view : b->p;
+    const size_t cap = part ? view_cap : b->cap;
+    if (!src || bytes == 0 || bytes > cap) return fail(c, DRP_ESTATE, "buffer '%s' not populated", name);
     if (out_bytes < bytes) return fail(c, DRP_EINVAL, "buffer '%s' needs %zu bytes", name, bytes);
-    if (hipMemcpyAsync(out, b->p, bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+    if (hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
         return fail(c, DRP_EHIP, "debug fetch failed");
     { const int rc = guarded_wait(c, nullptr); if (rc != DRP_OK) return rc; }
     return (long)bytes;

@@ -1,5 +1,4 @@
-// capi_gd.h -- a section of the C ABI's translation unit (textually included by drp_capi.hip, in this order: capi_ctx.h,
-// capi_pipeline.h, then inside extern "C": capi_core.h, capi_mpc.h, capi_prep.h, capi_gd.h, capi_train.h, capi_comm.h, capi_debug.h).
+// capi_gd.h -- a section of the C ABI's translation unit (textually included by drp_capi.hip, which has the order of the sections).
 // Here: the gradient-descent planner (row f1): forward with tape, reverse mode, Adam, drp_gd_*.
 
 // ---- gradient-descent planner (row f1) ----------------------------------------------------------
@@ -221,24 +220,21 @@ int drp_gd_step_async(drp_ctx* c, int slot) {
     if (c->gd_pending[slot]) return fail(c, DRP_ESTATE, "slot %d holds an iteration nobody has waited for", slot);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t nr = (size_t)c->gd_B, na = (size_t)c->gd_B * c->gd_H * 4;
-    if (c->gd_pin_floats < nr + na) {
-        for (int q = 0; q < DRP_GD_SLOTS; ++q) {
-            if (c->gd_pending[q]) return fail(c, DRP_ESTATE, "the batch grew while an iteration was in flight");
-            if (c->gd_pin[q]) HIPCHK(c, hipHostFree(c->gd_pin[q]));
-            c->gd_pin[q] = nullptr;
-            HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->gd_pin[q]), (nr + na) * sizeof(float), hipHostMallocDefault));
-            if (!c->gd_ev[q]) HIPCHK(c, hipEventCreateWithFlags(&c->gd_ev[q], hipEventDisableTiming));
-        }
-        c->gd_pin_floats = nr + na;
+    for (int q = 0; q < DRP_GD_SLOTS; ++q) {
+        // a slot's block goes only while nothing is in flight: the kernels of a pending iteration write into it
+        if (c->gd_pin[q].cap < (nr + na) * sizeof(float) && c->gd_pending[q])
+            return fail(c, DRP_ESTATE, "the batch grew while an iteration was in flight");
+        CHK(ensure_pinned(c, c->gd_pin[q], (nr + na) * sizeof(float)));
+        HIPCHK(c, c->gd_ev[q].create(hipEventDisableTiming));
     }
     // the iteration's own kernels write the slot (pinned host memory is device-visible): kb_reward the rewards, k_adam
     // the updated pushes -- two copies fewer on the stream per iteration (they were 27 of 197 us at 20 particles)
-    c->gd_host_rewards = c->gd_pin[slot];
-    c->gd_host_actions = c->gd_pin[slot] + nr;
+    c->gd_host_rewards = ptr<float>(c->gd_pin[slot]);
+    c->gd_host_actions = ptr<float>(c->gd_pin[slot]) + nr;
     const int rc_it = gd_iteration(c);
     c->gd_host_rewards = c->gd_host_actions = nullptr;
     CHK(rc_it);
-    HIPCHK(c, hipEventRecord(c->gd_ev[slot], c->stream));
+    HIPCHK(c, hipEventRecord(c->gd_ev[slot].ev, c->stream));
     c->gd_pending[slot] = true;
     return DRP_OK;
 }
@@ -248,10 +244,10 @@ int drp_gd_wait(drp_ctx* c, int slot, float* rewards_out, float* actions_out) {
     if (slot < 0 || slot >= DRP_GD_SLOTS || !c->gd_pending[slot]) return fail(c, DRP_ESTATE, "no iteration in flight in slot %d", slot);
     HIPCHK(c, hipSetDevice(c->device));
     c->gd_pending[slot] = false;
-    CHK(guarded_wait(c, c->gd_ev[slot]));
+    CHK(guarded_wait(c, c->gd_ev[slot].ev));
     const size_t nr = (size_t)c->gd_B, na = (size_t)c->gd_B * c->gd_H * 4;
-    if (rewards_out) memcpy(rewards_out, c->gd_pin[slot], nr * sizeof(float));
-    if (actions_out) memcpy(actions_out, c->gd_pin[slot] + nr, na * sizeof(float));
+    if (rewards_out) memcpy(rewards_out, c->gd_pin[slot].p, nr * sizeof(float));
+    if (actions_out) memcpy(actions_out, ptr<float>(c->gd_pin[slot]) + nr, na * sizeof(float));
     return DRP_OK;
 }
 

@@ -1,5 +1,4 @@
-// capi_mpc.h -- a section of the C ABI's translation unit (textually included by drp_capi.hip, in this order: capi_ctx.h,
-// capi_pipeline.h, then inside extern "C": capi_core.h, capi_mpc.h, capi_prep.h, capi_gd.h, capi_train.h, capi_comm.h, capi_debug.h).
+// capi_mpc.h -- a section of the C ABI's translation unit (textually included by drp_capi.hip, which has the order of the sections).
 // Here: the device-resident sampling planner (drp_mpc_*: sampler, rollout, softmax and elite updates, the one RCCL all-gather) and drp_fps.
 
 // ---- sampling MPC -------------------------------------------------------------------------
@@ -270,20 +269,17 @@ int drp_mpc_fetch_async(drp_ctx* c, int slot) {
     const drp_mpc_params& p = c->mpc;
     const int H = p.n_look_ahead, B = p.n_sample * p.n_batch;
     const size_t na = (size_t)B * H * 4, nr = (size_t)B;
-    if (c->mpc_pin_floats < na + nr) {
-        for (int q = 0; q < 2; ++q) {
-            if (c->mpc_pending[q]) return fail(c, DRP_ESTATE, "the batch grew while an iteration was in flight");
-            if (c->mpc_pin[q]) HIPCHK(c, hipHostFree(c->mpc_pin[q]));
-            c->mpc_pin[q] = nullptr;
-            HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->mpc_pin[q]), (na + nr) * sizeof(float), hipHostMallocDefault));
-            if (!c->mpc_ev[q]) HIPCHK(c, hipEventCreateWithFlags(&c->mpc_ev[q], hipEventDisableTiming));
-        }
-        c->mpc_pin_floats = na + nr;
+    for (int q = 0; q < 2; ++q) {
+        // a slot's block goes only while nothing is in flight: the copies of a pending iteration land in it
+        if (c->mpc_pin[q].cap < (na + nr) * sizeof(float) && c->mpc_pending[q])
+            return fail(c, DRP_ESTATE, "the batch grew while an iteration was in flight");
+        CHK(ensure_pinned(c, c->mpc_pin[q], (na + nr) * sizeof(float)));
+        HIPCHK(c, c->mpc_ev[q].create(hipEventDisableTiming));
     }
-    HIPCHK(c, hipMemcpyAsync(c->mpc_pin[slot], c->actions.p, na * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpy2DAsync(c->mpc_pin[slot] + na, sizeof(float), ptr<float>(c->rewards) + (H - 1), H * sizeof(float),
+    HIPCHK(c, hipMemcpyAsync(c->mpc_pin[slot].p, c->actions.p, na * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpy2DAsync(ptr<float>(c->mpc_pin[slot]) + na, sizeof(float), ptr<float>(c->rewards) + (H - 1), H * sizeof(float),
                                sizeof(float), B, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipEventRecord(c->mpc_ev[slot], c->stream));
+    HIPCHK(c, hipEventRecord(c->mpc_ev[slot].ev, c->stream));
     c->mpc_pending[slot] = true;
     return DRP_OK;
 }
@@ -293,11 +289,11 @@ int drp_mpc_wait(drp_ctx* c, int slot, float* actions, float* rewards) {
     if (slot < 0 || slot > 1 || !c->mpc_pending[slot]) return fail(c, DRP_ESTATE, "no iteration in flight in slot %d", slot);
     HIPCHK(c, hipSetDevice(c->device));
     c->mpc_pending[slot] = false;
-    CHK(guarded_wait(c, c->mpc_ev[slot]));
+    CHK(guarded_wait(c, c->mpc_ev[slot].ev));
     const drp_mpc_params& p = c->mpc;
     const size_t na = (size_t)p.n_sample * p.n_batch * p.n_look_ahead * 4, nr = (size_t)p.n_sample * p.n_batch;
-    if (actions) memcpy(actions, c->mpc_pin[slot], na * sizeof(float));
-    if (rewards) memcpy(rewards, c->mpc_pin[slot] + na, nr * sizeof(float));
+    if (actions) memcpy(actions, c->mpc_pin[slot].p, na * sizeof(float));
+    if (rewards) memcpy(rewards, ptr<float>(c->mpc_pin[slot]) + na, nr * sizeof(float));
     return DRP_OK;
 }
 

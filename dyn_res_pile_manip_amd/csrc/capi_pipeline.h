@@ -1,5 +1,4 @@
-// capi_pipeline.h -- a section of the C ABI's translation unit (textually included by drp_capi.hip, in this order: capi_ctx.h,
-// capi_pipeline.h, then inside extern "C": capi_core.h, capi_mpc.h, capi_prep.h, capi_gd.h, capi_train.h, capi_comm.h, capi_debug.h).
+// capi_pipeline.h -- a section of the C ABI's translation unit (textually included by drp_capi.hip, which has the order of the sections).
 // Here: internal helpers and pipelines: guarded waits, probes, the graph build, one predict_one_step on every engine (run_step), reward, rollouts (run_rollout), weight packing, deferred weight gradients, the range check.
 
 namespace {
@@ -33,17 +32,27 @@ int ensure(drp_ctx* c, DevBuf& b, size_t bytes) {
     if (bytes <= b.cap) return DRP_OK;
     // hipFree waits for the device: behind a collective that cannot finish it would never return
     if (b.p && c && c->comm != nullptr && (c->n_ranks > 1 || c->comm_always)) CHK(guarded_wait(c, nullptr));
-    if (b.p) HIPCHK(c, hipFree(b.p));
-    b.p = nullptr;
-    b.cap = 0;
+    HIPCHK(c, b.release());
     hipError_t e = hipMalloc(&b.p, bytes);
     if (e != hipSuccess) return fail(c, DRP_ENOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
     b.cap = bytes;
     return DRP_OK;
 }
 
+// Pinned host memory: nothing happens when the capacity suffices; otherwise the block goes, a new one comes and the owner records
+// its size.  The caller says, at the call, why nothing can still be reading or writing the old block.
+int ensure_pinned(drp_ctx* c, PinBuf& b, size_t bytes) {
+    if (bytes <= b.cap) return DRP_OK;
+    HIPCHK(c, b.release());
+    HIPCHK(c, hipHostMalloc(&b.p, bytes, b.flags));
+    b.cap = bytes;
+    return DRP_OK;
+}
+
 template <typename T>
 T* ptr(const DevBuf& b) { return static_cast<T*>(b.p); }
+template <typename T>
+T* ptr(const PinBuf& b) { return static_cast<T*>(b.p); }
 
 int h2d(drp_ctx* c, DevBuf& b, const void* src, size_t bytes) {
     CHK(ensure(c, b, bytes));
@@ -156,7 +165,7 @@ int guarded_wait(drp_ctx* c, hipEvent_t ev) {
     }
 }
 
-// RAII-less probe bracket
+// probe bracket: an event before and one after the launches of the probed class
 struct ProbeScope {
     drp_ctx* c;
     bool on;
@@ -168,11 +177,11 @@ struct ProbeScope {
     }
     void rec() {
         if (c->probe_used == c->probe_ev.size()) {
-            hipEvent_t e;
-            if (hipEventCreate(&e) != hipSuccess) { on = false; return; }
-            c->probe_ev.push_back(e);
+            Event e;
+            if (e.create() != hipSuccess) { on = false; return; }
+            c->probe_ev.push_back(std::move(e));
         }
-        (void)hipEventRecord(c->probe_ev[c->probe_used++], c->stream);
+        (void)hipEventRecord(c->probe_ev[c->probe_used++].ev, c->stream);
     }
 };
 
@@ -202,16 +211,14 @@ static void note_degrees(drp_ctx* c, long spw, long N, long B) {
     const long rows = spw * N;
     if (rows > c->pol.prop_pair_rows || rows <= c->pol.prop_pair_always) return;
     if ((c->deg_tick++ & 7u) != 0) return;
-    if (!c->deg_stat) {
-        if (hipHostMalloc(reinterpret_cast<void**>(&c->deg_stat), sizeof(unsigned long long), hipHostMallocMapped) != hipSuccess) {
-            c->deg_stat = nullptr;
+    if (!c->deg_stat.p) {                       // mapped (its flags): the device writes it, the host reads it; without it the plans see no degree
+        if (ensure_pinned(c, c->deg_stat, sizeof(unsigned long long)) != DRP_OK) {
             (void)hipGetLastError();
             return;
         }
-        *c->deg_stat = 0ull;
-        if (hipHostGetDevicePointer(reinterpret_cast<void**>(&c->deg_stat_dev), c->deg_stat, 0) != hipSuccess) {
-            (void)hipHostFree(c->deg_stat);
-            c->deg_stat = nullptr;
+        *ptr<unsigned long long>(c->deg_stat) = 0ull;
+        if (hipHostGetDevicePointer(reinterpret_cast<void**>(&c->deg_stat_dev), c->deg_stat.p, 0) != hipSuccess) {
+            (void)c->deg_stat.release();
             (void)hipGetLastError();
             return;
         }

@@ -1,5 +1,4 @@
-// capi_prep.h -- a section of the C ABI's translation unit (textually included by drp_capi.hip, in this order: capi_ctx.h,
-// capi_pipeline.h, then inside extern "C": capi_core.h, capi_mpc.h, capi_prep.h, capi_gd.h, capi_train.h, capi_comm.h, capi_debug.h).
+// capi_prep.h -- a section of the C ABI's translation unit (textually included by drp_capi.hip, which has the order of the sections).
 // Here: particle extraction from the depth image (row f2) and goal pre-processing (row f3).
 
 // ---- particle extraction (row f2) ---------------------------------------------------------------

@@ -29,14 +29,9 @@ PdLayout pd_layout(int B, size_t npix, size_t ptcl_floats, int T) {
 }
 
 int pd_pin_ensure(drp_ctx* c, size_t bytes) {
-    if (c->pd_pin_cap >= bytes) return DRP_OK;
-    if (c->pd_pin) {
-        (void)hipStreamSynchronize(c->stream);      // nothing of an earlier call may still copy from / to it
-        (void)hipHostFree(c->pd_pin); c->pd_pin = nullptr; c->pd_pin_cap = 0;
-    }
-    HIPCHK(c, hipHostMalloc(&c->pd_pin, bytes, hipHostMallocDefault));
-    c->pd_pin_cap = bytes;
-    return DRP_OK;
+    // nothing of an earlier call may still copy from / to the block that goes
+    if (c->pd_pin.p && c->pd_pin.cap < bytes) (void)hipStreamSynchronize(c->stream);
+    return ensure_pinned(c, c->pd_pin, bytes);
 }
 
 int pd_name(const int32_t* episode, int b) { return episode ? episode[b] : b; }
@@ -78,15 +73,15 @@ int drp_ptcl_dataset_batch(drp_ctx* c, int B, const uint16_t* depth, int h, int 
     }
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    if (c->pd_pin) CHK(guarded_wait(c, nullptr));     // a call that failed before its wait may still copy from the staging
+    if (c->pd_pin.p) CHK(guarded_wait(c, nullptr));     // a call that failed before its wait may still copy from the staging
     for (int e = 0; e < PD_NEV; ++e)
-        if (!c->pd_ev[e]) HIPCHK(c, hipEventCreate(&c->pd_ev[e]));
+        HIPCHK(c, c->pd_ev[e].create());
     c->pd_timed = false;
     const size_t npix = (size_t)h * w;
     const PdLayout L = pd_layout(B, npix, ptcl_floats, T);
     const size_t meta_bytes = (size_t)2 * B * sizeof(int);
     CHK(pd_pin_ensure(c, std::max(L.bytes, meta_bytes)));
-    char* pin = static_cast<char*>(c->pd_pin);
+    char* pin = ptr<char>(c->pd_pin);
     memcpy(pin + L.depth, depth, (size_t)B * npix * sizeof(uint16_t));
     memcpy(pin + L.ptcl, particles, ptcl_floats * sizeof(float));
     memcpy(pin + L.radius, radius, (size_t)B * sizeof(double));
@@ -94,9 +89,9 @@ int drp_ptcl_dataset_batch(drp_ctx* c, int B, const uint16_t* depth, int h, int 
     memcpy(pin + L.init, init_idx, (size_t)B * sizeof(int));
     memcpy(pin + L.nptcl, n_ptcl, (size_t)B * sizeof(int));
     memcpy(pin + L.ptcl_off, ptcl_off.data(), (size_t)B * sizeof(long long));
-    HIPCHK(c, hipEventRecord(c->pd_ev[0], st));
+    HIPCHK(c, hipEventRecord(c->pd_ev[0].ev, st));
     CHK(h2d(c, c->pd_in, pin, L.bytes));
-    HIPCHK(c, hipEventRecord(c->pd_ev[1], st));
+    HIPCHK(c, hipEventRecord(c->pd_ev[1].ev, st));
     const char* in = static_cast<const char*>(c->pd_in.p);
     const uint16_t* d_depth = reinterpret_cast<const uint16_t*>(in + L.depth);
     const float* d_ptcl = reinterpret_cast<const float*>(in + L.ptcl);
@@ -129,7 +124,7 @@ int drp_ptcl_dataset_batch(drp_ctx* c, int B, const uint16_t* depth, int h, int 
     hipLaunchKernelGGL(k_pd_compact, dim3(nblk, B), dim3(PX_BLOCK), 0, st, d_depth, npix, w, pc, off, pcd_cap, ptr<double>(c->pd_pcd));
     hipLaunchKernelGGL(k_pd_meta, dim3((B + 255) / 256), dim3(256), 0, st, off, nblk, B, d_nfg, d_pcd_off);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->pd_ev[2], st));
+    HIPCHK(c, hipEventRecord(c->pd_ev[2].ev, st));
 
     // 2. fps_rad, one workgroup per sample
     const int cap = PD_CAP + 1;
@@ -137,7 +132,7 @@ int drp_ptcl_dataset_batch(drp_ctx* c, int B, const uint16_t* depth, int h, int 
     hipLaunchKernelGGL(k_pd_fps_rad, dim3(B), dim3(1024), 0, st, ptr<double>(c->pd_pcd), pcd_cap, d_pcd_off, d_nfg, d_init,
                        d_radius, cap, ptr<double>(c->pd_dist), ptr<int>(c->pd_chosen), d_counts);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->pd_ev[3], st));
+    HIPCHK(c, hipEventRecord(c->pd_ev[3].ev, st));
     // the one wait before the download: foreground and particle counts size the rest
     CHK(d2h(c, pin, d_nfg, meta_bytes));
     CHK(guarded_wait(c, nullptr));
@@ -168,7 +163,7 @@ int drp_ptcl_dataset_batch(drp_ctx* c, int B, const uint16_t* depth, int h, int 
     hipLaunchKernelGGL(k_pd_recenter, dim3((B * n_max + 3) / 4), dim3(256), 0, st, ptr<double>(c->pd_pcd), d_pcd_off, d_nfg,
                        ptr<int>(c->pd_chosen), cap, d_counts, d_radius, n_max, B, ptr<double>(c->pd_rec));
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->pd_ev[4], st));
+    HIPCHK(c, hipEventRecord(c->pd_ev[4].ev, st));
 
     // 4. track and pack
     const size_t n_states = (size_t)B * T * n_max * 3, n_sdelta = (size_t)B * (T - 1) * n_max * 3;
@@ -180,14 +175,14 @@ int drp_ptcl_dataset_batch(drp_ctx* c, int B, const uint16_t* depth, int h, int 
     hipLaunchKernelGGL(k_pd_pack, dim3(jb, T, B), dim3(256), 0, st, ptr<int>(c->pd_near), d_counts, n_max, T, d_ptcl, d_poff,
                        d_nptcl, d_push, pc, ptr<float>(c->pd_out), ptr<float>(c->pd_out) + n_states);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->pd_ev[5], st));
+    HIPCHK(c, hipEventRecord(c->pd_ev[5].ev, st));
 
     // 5. one download through the pinned staging
     CHK(pd_pin_ensure(c, (n_states + n_sdelta) * sizeof(float)));
-    CHK(d2h(c, c->pd_pin, c->pd_out.p, (n_states + n_sdelta) * sizeof(float)));
-    HIPCHK(c, hipEventRecord(c->pd_ev[6], st));
+    CHK(d2h(c, c->pd_pin.p, c->pd_out.p, (n_states + n_sdelta) * sizeof(float)));
+    HIPCHK(c, hipEventRecord(c->pd_ev[6].ev, st));
     CHK(guarded_wait(c, nullptr));
-    const float* res = static_cast<const float*>(c->pd_pin);
+    const float* res = ptr<const float>(c->pd_pin);
     memcpy(states_out, res, n_states * sizeof(float));
     memcpy(sdelta_out, res + n_states, n_sdelta * sizeof(float));
     c->pd_timed = true;
@@ -198,7 +193,7 @@ int drp_ptcl_dataset_time(drp_ctx* c, float* ms_out) {
     if (!c || !ms_out) return fail(c, DRP_EINVAL, "null argument");
     if (!c->pd_timed) return fail(c, DRP_ESTATE, "no drp_ptcl_dataset_batch has completed");
     for (int e = 0; e + 1 < PD_NEV; ++e)
-        if (hipEventElapsedTime(&ms_out[e], c->pd_ev[e], c->pd_ev[e + 1]) != hipSuccess)
+        if (hipEventElapsedTime(&ms_out[e], c->pd_ev[e].ev, c->pd_ev[e + 1].ev) != hipSuccess)
             return fail(c, DRP_EHIP, "hipEventElapsedTime failed");
     return DRP_OK;
 }

@@ -203,9 +203,7 @@ int drp_rgr_load(drp_ctx* c, const float* blob, size_t n_floats, int n_out) {
     HIPCHK(c, hipGetLastError());
     CHK(guarded_wait(c, nullptr));
     // the staging copy is not kept (457 MB)
-    HIPCHK(c, hipFree(c->rgr_raw.p));
-    c->rgr_raw.p = nullptr;
-    c->rgr_raw.cap = 0;
+    HIPCHK(c, c->rgr_raw.release());
     c->rgr_nout = n_out;
     c->rgr_lastB = 0;
     return DRP_OK;
@@ -248,23 +246,18 @@ int drp_rgr_time(drp_ctx* c, int parts, int B, int iters, float* ms_out) {
     if (B < 1 || B > RGR_BMAX) return fail(c, DRP_EINVAL, "batch %d outside 1..%d", B, RGR_BMAX);
     if (parts < 1 || parts > 7 || iters < 1 || iters > 10000) return fail(c, DRP_EINVAL, "bad parts=%d iters=%d", parts, iters);
     HIPCHK(c, hipSetDevice(c->device));
-    std::vector<hipEvent_t> ev(iters + 1, nullptr);
-    int rc = DRP_OK;
-    for (hipEvent_t& e : ev)
-        if (hipEventCreate(&e) != hipSuccess) { rc = fail(c, DRP_EHIP, "hipEventCreate failed"); break; }
-    if (rc == DRP_OK) {
-        const int lastB = c->rgr_lastB;
-        (void)hipEventRecord(ev[0], c->stream);
-        for (int i = 0; i < iters && rc == DRP_OK; ++i) {
-            rc = rgr_run_forward(c, B, parts);
-            (void)hipEventRecord(ev[i + 1], c->stream);
-        }
-        c->rgr_lastB = (parts == 7 && rc == DRP_OK) ? B : lastB;
-        if (rc == DRP_OK) rc = guarded_wait(c, nullptr);
-        for (int i = 0; i < iters && rc == DRP_OK; ++i)
-            if (hipEventElapsedTime(&ms_out[i], ev[i], ev[i + 1]) != hipSuccess) rc = fail(c, DRP_EHIP, "hipEventElapsedTime failed");
+    std::vector<Event> ev(iters + 1);
+    for (Event& e : ev) HIPCHK(c, e.create());
+    // a partial forward leaves the taps of the last whole one in place
+    struct LastB { drp_ctx* c; int keep; ~LastB() { c->rgr_lastB = keep; } } last_b{c, c->rgr_lastB};
+    (void)hipEventRecord(ev[0].ev, c->stream);
+    for (int i = 0; i < iters; ++i) {
+        CHK(rgr_run_forward(c, B, parts));
+        (void)hipEventRecord(ev[i + 1].ev, c->stream);
     }
-    for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
-    return rc;
+    if (parts == 7) last_b.keep = B;
+    CHK(guarded_wait(c, nullptr));
+    for (int i = 0; i < iters; ++i)
+        HIPCHK(c, hipEventElapsedTime(&ms_out[i], ev[i].ev, ev[i + 1].ev));
+    return DRP_OK;
 }

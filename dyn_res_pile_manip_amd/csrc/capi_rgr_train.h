@@ -39,7 +39,7 @@ void rgr_colsum(drp_ctx* c, const float* dz, int rows, int N, float* g) {
 // full: every gradient to c->rgr_gfull (device layouts, blob offsets), otherwise FC1's is never stored and the others go to
 // c->rgr_g (blob offsets with FC1's weight range cut out).  ev (nullable): 4 events around forward | loss + FC backward (with
 // FC1's Adam step) | conv backward + the other parameters' Adam step.  *nl1 = the number of |W| partials in c->rgr_l1.
-int rgr_enqueue_step(drp_ctx* c, int B, bool bwd, bool update, bool full, hipEvent_t* ev, int* nl1_out) {
+int rgr_enqueue_step(drp_ctx* c, int B, bool bwd, bool update, bool full, Event* ev, int* nl1_out) {
     hipStream_t st = c->stream;
     const int nout = c->rgr_nout;
     const RgrOffsets o = rgr_offsets(nout);
@@ -58,9 +58,9 @@ int rgr_enqueue_step(drp_ctx* c, int B, bool bwd, bool update, bool full, hipEve
     const float bc2_sqrt = (float)sqrt(1.0 - pow(0.999, (double)iter));
     const float b1 = (float)c->rgr_tr_beta1;
 
-    if (ev) (void)hipEventRecord(ev[0], st);
+    if (ev) (void)hipEventRecord(ev[0].ev, st);
     CHK(rgr_run_forward(c, B));
-    if (ev) (void)hipEventRecord(ev[1], st);
+    if (ev) (void)hipEventRecord(ev[1].ev, st);
 
     // sum |W| of every weight (biases excluded) before any update; FC1..FC4's come from their wgrad pass when there is one
     auto l1_of = [&](size_t off, size_t n, int blocks) {
@@ -102,7 +102,7 @@ int rgr_enqueue_step(drp_ctx* c, int B, bool bwd, bool update, bool full, hipEve
                                    1.0f, b1, l1 + nl1);
             nl1 += (int)(grid.x * grid.y);
         }
-        if (ev) (void)hipEventRecord(ev[2], st);
+        if (ev) (void)hipEventRecord(ev[2].ev, st);
         for (int l = 4; l >= 0; --l) {
             const int IH = RGR_CONV_IN[l], OH = IH / 2, cout = RGR_CONV_COUT[l], cin = RGR_CONV_CIN[l], S = RGR_WG_SPLIT[l];
             const float* dz = ptr<float>(c->rgr_dz[l & 1]);
@@ -142,9 +142,9 @@ int rgr_enqueue_step(drp_ctx* c, int B, bool bwd, bool update, bool full, hipEve
                                (unsigned*)nullptr);
         }
     } else if (ev) {
-        (void)hipEventRecord(ev[2], st);
+        (void)hipEventRecord(ev[2].ev, st);
     }
-    if (ev) (void)hipEventRecord(ev[3], st);
+    if (ev) (void)hipEventRecord(ev[3].ev, st);
     HIPCHK(c, hipGetLastError());
     *nl1_out = nl1;
     return DRP_OK;
@@ -272,9 +272,7 @@ int drp_rgr_get_weights(drp_ctx* c, float* blob_out, size_t n_floats) {
     CHK(d2h(c, blob_out, c->rgr_raw.p, o.total * sizeof(float)));
     CHK(guarded_wait(c, nullptr));
     if (!keep) {
-        HIPCHK(c, hipFree(c->rgr_raw.p));
-        c->rgr_raw.p = nullptr;
-        c->rgr_raw.cap = 0;
+        HIPCHK(c, c->rgr_raw.release());
     }
     return DRP_OK;
 }
@@ -287,21 +285,16 @@ int drp_rgr_train_time(drp_ctx* c, int B, int iters, float* ms_out) {
                     c->rgr_tr_lastB);
     if (iters < 1 || iters > 1000) return fail(c, DRP_EINVAL, "bad iters=%d", iters);
     HIPCHK(c, hipSetDevice(c->device));
-    std::vector<hipEvent_t> ev((size_t)4 * iters, nullptr);
-    int rc = DRP_OK;
-    for (hipEvent_t& e : ev)
-        if (hipEventCreate(&e) != hipSuccess) { rc = fail(c, DRP_EHIP, "hipEventCreate failed"); break; }
-    for (int i = 0; i < iters && rc == DRP_OK; ++i) {
+    std::vector<Event> ev((size_t)4 * iters);
+    for (Event& e : ev) HIPCHK(c, e.create());
+    for (int i = 0; i < iters; ++i) {
         int nl1 = 0;
-        rc = rgr_enqueue_step(c, B, true, true, false, &ev[(size_t)4 * i], &nl1);
-        if (rc == DRP_OK) c->rgr_tr_iter += 1;
+        CHK(rgr_enqueue_step(c, B, true, true, false, &ev[(size_t)4 * i], &nl1));
+        c->rgr_tr_iter += 1;
     }
-    if (rc == DRP_OK) rc = guarded_wait(c, nullptr);
-    for (int i = 0; i < iters && rc == DRP_OK; ++i)
-        for (int p = 0; p < 3 && rc == DRP_OK; ++p)
-            if (hipEventElapsedTime(&ms_out[(size_t)3 * i + p], ev[(size_t)4 * i + p], ev[(size_t)4 * i + p + 1]) != hipSuccess)
-                rc = fail(c, DRP_EHIP, "hipEventElapsedTime failed");
-    for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
-    return rc;
+    CHK(guarded_wait(c, nullptr));
+    for (int i = 0; i < iters; ++i)
+        for (int p = 0; p < 3; ++p)
+            HIPCHK(c, hipEventElapsedTime(&ms_out[(size_t)3 * i + p], ev[(size_t)4 * i + p].ev, ev[(size_t)4 * i + p + 1].ev));
+    return DRP_OK;
 }

@@ -1,5 +1,4 @@
-// capi_train.h -- a section of the C ABI's translation unit (textually included by drp_capi.hip, in this order: capi_ctx.h,
-// capi_pipeline.h, then inside extern "C": capi_core.h, capi_mpc.h, capi_prep.h, capi_gd.h, capi_train.h, capi_comm.h, capi_debug.h).
+// capi_train.h -- a section of the C ABI's translation unit (textually included by drp_capi.hip, which has the order of the sections).
 // Here: training on the same kernels (row f4): forward with tape, reverse mode with weight gradients, Adam, re-packing.
 
 // ---- training on the same kernels (row f4) ------------------------------------------------------
@@ -174,7 +173,7 @@ int ensure_repack_maps(drp_ctx* c) {
     CHK(h2d(c, c->map_mfma, mm.data(), mm.size() * sizeof(int)));
     CHK(h2d(c, c->map_mfma_bwd, mmb.data(), mmb.size() * sizeof(int)));
     CHK(guarded_wait(c, nullptr));                   // the vectors go out of scope
-    if (!c->w_pin) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->w_pin), ((size_t)W_TOTAL + 4) * sizeof(float), hipHostMallocDefault));
+    CHK(ensure_pinned(c, c->w_pin, ((size_t)W_TOTAL + 4) * sizeof(float)));      // one size for the context's life: never replaced
     c->repack_maps_ready = true;
     return DRP_OK;
 }
@@ -195,10 +194,10 @@ int repack_on_device(drp_ctx* c, bool blob_in_pin = false /* k_adam has written 
     // the relation encoder's range shift depends on the new weights: the launch above derived it; the blob itself comes
     // back too (it is the host copy drp_get_weights serves, and the host's own range for the calls to come)
     hipLaunchKernelGGL(kt_repack_split, dim3(4 * 16), dim3(256), 0, st, w, 0, ptr<uint16_t>(c->w_split), ptr<int>(c->re_shift_dev),
-                       blob_in_pin ? reinterpret_cast<int*>(c->w_pin + W_TOTAL) : (int*)nullptr);
+                       blob_in_pin ? ptr<int>(c->w_pin) + W_TOTAL : (int*)nullptr);
     if (!blob_in_pin) {
-        HIPCHK(c, hipMemcpyAsync(c->w_pin, c->w_raw.p, (size_t)W_TOTAL * sizeof(float), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(c->w_pin + W_TOTAL, c->re_shift_dev.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(c->w_pin.p, c->w_raw.p, (size_t)W_TOTAL * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(ptr<float>(c->w_pin) + W_TOTAL, c->re_shift_dev.p, sizeof(int), hipMemcpyDeviceToHost, st));
     }
     HIPCHK(c, hipGetLastError());
     return DRP_OK;
@@ -206,10 +205,10 @@ int repack_on_device(drp_ctx* c, bool blob_in_pin = false /* k_adam has written 
 // after the wait: the host's copy of the blob and its range; host and device derive the shift by the same operations --
 // should they ever disagree, the fragments are packed again with the host's
 int finish_repack(drp_ctx* c) {
-    c->w_host.assign(c->w_pin, c->w_pin + W_TOTAL);
+    c->w_host.assign(ptr<float>(c->w_pin), ptr<float>(c->w_pin) + W_TOTAL);
     set_split_range(c, c->w_host.data());
     int dev_shift;
-    memcpy(&dev_shift, c->w_pin + W_TOTAL, sizeof(int));
+    memcpy(&dev_shift, ptr<float>(c->w_pin) + W_TOTAL, sizeof(int));
     if (dev_shift != c->re_range.shift) {
         hipLaunchKernelGGL(kt_repack_split, dim3(4 * 16), dim3(256), 0, c->stream, ptr<float>(c->w_raw), c->re_range.shift,
                            ptr<uint16_t>(c->w_split), (const int*)nullptr);
@@ -269,18 +268,12 @@ int drp_train_step(drp_ctx* c, const float* states, const float* states_delta, c
     // behind the batch: what comes BACK after the one wait -- the loss terms [H][B] and the give-up flag of kmb_step_bwd's
     // barrier (pinned: the copies are asynchronous, nothing on the way touches pageable memory or this frame)
     const size_t back_off = lay.bytes, back_bytes = (size_t)H * B * sizeof(double) + 16;
-    if (c->tr_pin_cap < lay.bytes + back_bytes) {
-        if (c->tr_pin) {
-            // kernels read and write this buffer directly: nothing of an earlier call (one that returned on an error before its
-            // wait, say) may still be in flight when it goes
-            (void)hipStreamSynchronize(c->stream);
-            (void)hipHostFree(c->tr_pin); c->tr_pin = nullptr; c->tr_pin_cap = 0;
-        }
-        HIPCHK(c, hipHostMalloc(&c->tr_pin, lay.bytes + back_bytes, hipHostMallocDefault));
-        c->tr_pin_cap = lay.bytes + back_bytes;
-    }
+    // kernels read and write this buffer directly: nothing of an earlier call (one that returned on an error before its
+    // wait, say) may still be in flight when it goes
+    if (c->tr_pin.p && c->tr_pin.cap < lay.bytes + back_bytes) (void)hipStreamSynchronize(c->stream);
+    CHK(ensure_pinned(c, c->tr_pin, lay.bytes + back_bytes));
     {
-        char* pin = static_cast<char*>(c->tr_pin);
+        char* pin = ptr<char>(c->tr_pin);
         memcpy(pin + lay.states, states, (size_t)B * (H + 1) * N * 3 * sizeof(float));
         memcpy(pin + lay.sdelta, states_delta, (size_t)B * H * N * 3 * sizeof(float));
         memcpy(pin + lay.attrs, attrs, (size_t)B * (H + 1) * N * sizeof(float));
@@ -295,13 +288,13 @@ int drp_train_step(drp_ctx* c, const float* states, const float* states_delta, c
         // the unpacking launch IS the upload: it reads the staged batch from the pinned host buffer (device-visible) and leaves
         // the arena copy for the kernels that read the given states; DRP_TRAIN_COPY_UPLOAD=1: a copy on the stream first
         const bool by_kernel = !c->train_copy_upload;
-        if (!by_kernel) CHK(h2d(c, c->tr_arena, c->tr_pin, lay.bytes));
-        const char* ar = by_kernel ? static_cast<const char*>(c->tr_pin) : static_cast<const char*>(c->tr_arena.p);
+        if (!by_kernel) CHK(h2d(c, c->tr_arena, c->tr_pin.p, lay.bytes));
+        const char* ar = by_kernel ? ptr<const char>(c->tr_pin) : static_cast<const char*>(c->tr_arena.p);
         const size_t total = (size_t)H * bn * 3;
         hipLaunchKernelGGL(kt_unpack_inputs, dim3((unsigned)std::min<size_t>((total + 255) / 256, 1024)), dim3(256), 0, c->stream,
                            reinterpret_cast<const float*>(ar + lay.sdelta), reinterpret_cast<const float*>(ar + lay.attrs),
                            reinterpret_cast<const float*>(ar + lay.dens), B, H, N, ptr<float>(c->tape_sdelta), ptr<float>(c->attr),
-                           ptr<float>(c->dens), by_kernel ? reinterpret_cast<const float4*>(c->tr_pin) : (const float4*)nullptr,
+                           ptr<float>(c->dens), by_kernel ? ptr<const float4>(c->tr_pin) : (const float4*)nullptr,
                            by_kernel ? static_cast<float4*>(c->tr_arena.p) : (float4*)nullptr, by_kernel ? lay.bytes / 16 : (size_t)0);
     }
     CHK(ensure_step_ws(c, B, N, c->tr_engine));
@@ -332,7 +325,7 @@ int drp_train_step(drp_ctx* c, const float* states, const float* states_delta, c
     }
     CHK(ensure(c, c->tr_loss, (size_t)H * B * sizeof(double)));
     c->lastH = H;
-    double* const parts = reinterpret_cast<double*>(static_cast<char*>(c->tr_pin) + back_off);
+    double* const parts = reinterpret_cast<double*>(ptr<char>(c->tr_pin) + back_off);
     unsigned* const gave_up = reinterpret_cast<unsigned*>(parts + (size_t)H * B);
     // kmb_step_bwd's barrier among the workgroups of a group gives up after two seconds (k_backward_mfma.h) and sets a flag
     // behind its counters; the gradient of such a pass is partial.  The optimiser step reads the flag ON THE DEVICE and moves
@@ -367,7 +360,7 @@ int drp_train_step(drp_ctx* c, const float* states, const float* states_delta, c
             hipLaunchKernelGGL(k_adam, dim3((W_TOTAL + 255) / 256), dim3(256), 0, c->stream, ptr<float>(c->w_raw),
                                ptr<float>(c->tr_grad), ptr<float>(c->tr_m), ptr<float>(c->tr_v), (int)W_TOTAL,
                                (float)(c->tr_lr / bc1), (float)sqrt(bc2), make_float4(-inf, -inf, -inf, -inf),
-                               make_float4(inf, inf, inf, inf), (float)c->tr_beta1, direct ? c->w_pin : (float*)nullptr, flag_dev,
+                               make_float4(inf, inf, inf, inf), (float)c->tr_beta1, direct ? ptr<float>(c->w_pin) : (float*)nullptr, flag_dev,
                                direct ? gave_up : (unsigned*)nullptr);
             if (hipGetLastError() != hipSuccess) { (void)drp_sync(c); return fail(c, DRP_EHIP, "k_adam launch"); }
             // the engines read packed copies of the weights: rebuild them from the blob (unchanged if the step was skipped)

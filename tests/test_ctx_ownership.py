@@ -1,0 +1,85 @@
+"""Host: the context's device buffers, pinned blocks, events and stream are owned by the members that hold them
+(csrc/capi_ctx.h), so the raw allocate / free calls of the HIP runtime each have one home in csrc/ and drp_destroy frees by
+destruction.  Read from the sources; nothing is compiled or run."""
+import glob
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, 'dyn_res_pile_manip_amd', 'csrc')
+
+
+def _sources():
+    return {os.path.basename(p): open(p).read() for p in sorted(glob.glob(os.path.join(CSRC, '*.h')) + glob.glob(os.path.join(CSRC, '*.hip')))}
+
+
+def _sites(needle):
+    """(file, line number, line) of every occurrence in csrc/"""
+    return [(f, i + 1, ln) for f, text in _sources().items() for i, ln in enumerate(text.splitlines()) for _ in range(ln.count(needle))]
+
+
+def _body(text, head):
+    """the text of the block that opens on the first line containing `head`, braces matched"""
+    start = text.index(head)
+    i = text.index('{', start)
+    depth = 0
+    for j in range(i, len(text)):
+        depth += text[j] == '{'
+        depth -= text[j] == '}'
+        if depth == 0:
+            return text[start:j + 1]
+    raise AssertionError('unbalanced block after %r' % head)
+
+
+def _only_inside(needle, fname, head):
+    block = _body(_sources()[fname], head)
+    sites = _sites(needle)
+    assert sites, needle
+    assert all(f == fname and ln.strip() in block for f, _, ln in sites), (needle, sites)
+    return sites
+
+
+def test_each_free_has_one_home_in_its_owner():
+    for needle, head in (('hipFree(', 'struct DevBuf {'), ('hipHostFree(', 'struct PinBuf {'), ('hipEventDestroy(', 'struct Event {'),
+                         ('hipStreamDestroy(', 'struct Stream {')):
+        assert len(_only_inside(needle, 'capi_ctx.h', head)) == 1, needle
+
+
+def test_each_allocation_has_one_home():
+    _only_inside('hipMalloc(', 'capi_pipeline.h', 'int ensure(drp_ctx* c, DevBuf& b, size_t bytes) {')
+    _only_inside('hipHostMalloc(', 'capi_pipeline.h', 'int ensure_pinned(drp_ctx* c, PinBuf& b, size_t bytes) {')
+    _only_inside('hipEventCreate', 'capi_ctx.h', 'struct Event {')
+
+
+def test_the_stream_is_the_first_member_and_the_context_has_no_destructor():
+    ctx = _body(_sources()['capi_ctx.h'], 'struct drp_ctx {')
+    members = [ln.strip() for ln in ctx.splitlines()[1:] if ln.strip() and not ln.strip().startswith('//')]
+    assert members[0].startswith('Stream stream;'), members[0]
+    assert '~drp_ctx' not in ctx
+    # no resource is held as a bare pointer or handle any more
+    assert not re.search(r'hipEvent_t\s+\w+(\[|\s*=|;)', ctx) and 'hipStream_t stream' not in ctx
+    for gone in ('gd_pin_floats', 'mpc_pin_floats', 'tr_pin_cap', 'pd_pin_cap'):
+        assert all(gone not in text for text in _sources().values()), gone
+
+
+def test_drp_destroy_frees_by_destruction():
+    body = _body(_sources()['capi_core.h'], 'void drp_destroy(drp_ctx* c) {')
+    assert '&c->' not in body and 'bufs' not in body
+    assert len(body.splitlines()) <= 12, body
+    for step in ('hipSetDevice(c->device)', 'guarded_wait(c, nullptr)', 'helpers_wait(', 'CommDestroy(c->comm)', 'delete c;'):
+        assert step in body, step
+    assert body.index('guarded_wait') < body.index('delete c;')
+    create = _body(_sources()['capi_core.h'], 'int drp_create(int device, drp_ctx** out) {')
+    assert 'std::unique_ptr<drp_ctx>' in create and 'c.release()' in create and 'delete c' not in create
+
+
+def test_the_owners_are_move_only():
+    text = _sources()['capi_ctx.h']
+    m = re.search(r'static_assert\((.*?)"a resource has one owner"\);', text, re.S)
+    assert m, 'the static_assert on the owners is gone'
+    for t in ('DevBuf', 'PinBuf', 'Event'):
+        assert '!std::is_copy_constructible<%s>::value' % t in m.group(1), t
+        assert '!std::is_copy_assignable<%s>::value' % t in m.group(1), t
+        owner = _body(text, 'struct %s {' % t)
+        assert '%s(const %s&) = delete;' % (t, t) in owner and '%s& operator=(const %s&) = delete;' % (t, t) in owner, t
+        assert '~%s() { (void)release(); }' % t in owner, t
