@@ -157,6 +157,14 @@ SIGNATURES = {
                                               ctypes.POINTER(ctypes.c_int32), ctypes.c_int, c_float_p, c_float_p,
                                               ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int)]),
     'drp_ptcl_dataset_time': (ctypes.c_int, [ctypes.c_void_p, c_float_p]),
+    'drp_forward_f64': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p,
+                                       c_int16_p, c_uint8_p, ctypes.c_int, ctypes.c_int, c_double_p]),
+    'drp_step_f64': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p,
+                                    ctypes.c_int, ctypes.c_int, c_double_p]),
+    'drp_f64_tap': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, c_double_p, ctypes.c_size_t]),
+    'drp_debug_set_f64_cap': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t]),
+    'drp_accuracy_probe': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_float_p, c_float_p, c_float_p, c_float_p,
+                                          ctypes.c_int, ctypes.c_int, c_double_p]),
 }
 
 _lib = None

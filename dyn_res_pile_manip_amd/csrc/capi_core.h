@@ -119,6 +119,7 @@ int drp_load_weights(drp_ctx* c, const float* blob, size_t n_floats, float adj_t
     // the transposed layers of the GD planner's backward pass in the same split: packed on the device from the raw blob
     CHK(ensure(c, c->w_split6_bwd, (size_t)SB6_TOTAL * 16));
     hipLaunchKernelGGL(kt_repack_split6_bwd, dim3(6 * 16), dim3(256), 0, c->stream, ptr<float>(c->w_raw), ptr<uint16_t>(c->w_split6_bwd));
+    CHK(f64_refresh_weights(c));          // the float64 yardstick's copy (capi_f64.h)
     CHK(guarded_wait(c, nullptr));
     c->w_host.assign(blob, blob + n_floats);
     c->adj_thresh = adj_thresh;

@@ -1111,6 +1111,15 @@ void set_split_range(drp_ctx* c, const float* blob) {
     c->re_inv = ldexpf(1.0f, -c->re_range.shift);
 }
 
+// the float64 copy of the weights (k_prop_f64.h) from the device's current fp32 blob: enqueued, not waited for
+int f64_refresh_weights(drp_ctx* c) {
+    CHK(ensure(c, c->f64_w, (size_t)KF_W_TOTAL * sizeof(double)));
+    hipLaunchKernelGGL(kf_widen_weights, dim3((KF_W_TOTAL + 255) / 256), dim3(256), 0, c->stream, ptr<float>(c->w_raw), ptr<double>(c->f64_w));
+    HIPCHK(c, hipGetLastError());
+    c->f64_w_valid = true;
+    return DRP_OK;
+}
+
 int check_bn(drp_ctx* c, int B, int N) {
     if (B <= 0 || N <= 0 || N > 4096) return fail(c, DRP_EINVAL, "bad shape B=%d N=%d (N <= 4096)", B, N);
     return DRP_OK;

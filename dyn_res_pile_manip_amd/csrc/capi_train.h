@@ -363,6 +363,7 @@ int drp_train_step(drp_ctx* c, const float* states, const float* states_delta, c
                                make_float4(inf, inf, inf, inf), (float)c->tr_beta1, direct ? ptr<float>(c->w_pin) : (float*)nullptr, flag_dev,
                                direct ? gave_up : (unsigned*)nullptr);
             if (hipGetLastError() != hipSuccess) { (void)drp_sync(c); return fail(c, DRP_EHIP, "k_adam launch"); }
+            c->f64_w_valid = false;           // the float64 copy is of the old blob: the next *_f64 call widens the new one
             // the engines read packed copies of the weights: rebuild them from the blob (unchanged if the step was skipped)
             if (c->repack_device) {
                 const int rc = repack_on_device(c, direct);

@@ -1,6 +1,6 @@
 // C ABI of the engine (include/drp.h): context, device workspaces, kernel pipelines -- ONE translation unit whose text lives in
 // the capi_*.h sections included below (context; pipelines; then the entry points by surface: core, planner, pre-processing,
-// gradient descent, training, RCCL, resolution regressor, measurement).  The propagation kernels' instantiations are translation units of their own.
+// gradient descent, training, RCCL, resolution regressor, float64 yardstick, measurement).  The propagation kernels' instantiations are translation units of their own.
 // Built with: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -c (this file and csrc/inst_*.hip, in parallel), then -shared
 // (__graft_entry__.build)
 #include "../../include/drp.h"
@@ -45,6 +45,7 @@
 #include "k_rgr.h"
 #include "k_rgr_bwd.h"
 #include "k_ptcl_dataset.h"
+#include "k_prop_f64.h"
 #include "k_prop_inst.h"       // km_prop / km_prop3 / km_rollout: declared here, instantiated in inst_*.hip
 
 #include "dispatch.h"          // host-only: policy, variant flags, plan functions
@@ -62,6 +63,7 @@ extern "C" {
 #include "capi_rgr.h"
 #include "capi_rgr_train.h"
 #include "capi_ptcl_dataset.h"
+#include "capi_f64.h"
 #include "capi_debug.h"
 
 }  // extern "C"

@@ -112,14 +112,52 @@ class Engine(object):
         self._ck(self.lib.drp_device_info(self.h, name, 256, ctypes.byref(ncu), ctypes.byref(mem)))
         return {'name': name.value.decode(), 'n_cu': ncu.value, 'hbm_bytes': mem.value}
 
-    def load_weights(self, blob, adj_thresh=0.08):
+    def load_weights(self, blob, adj_thresh=0.08, probe=None, max_disp_rel=None):
+        """probe: None (nothing measured), True (the fixed batch of `probe_batch`; the camera must be set) or a batch
+        (a_cur, s_cur, s_delta, dens): after loading, the selected engine's one-step error against the float64 evaluation is
+        measured on it (`accuracy_probe`) and kept for `range_info()['probe']`.  max_disp_rel: the largest error, as a share
+        of the largest displacement, the caller accepts -- beyond it the fused / split engine gives way to the fp32 matrix
+        engine exactly as after DRP_ERANGE (one RuntimeWarning; the next load_weights restores the choice), whatever
+        `auto_engine` says, and on the fp32 engines, which have nowhere to fall back to, DrpError is raised."""
         blob = _f32(blob).ravel()
+        if max_disp_rel is not None and probe is None:
+            raise ValueError('max_disp_rel needs a probe (probe=True or a batch)')
         self._weights_owner = None                    # whoever believed its weights were resident no longer is right
         self._ck(self.lib.drp_load_weights(self.h, _fp(blob), blob.size, float(adj_thresh)))
-        if self.auto_engine and self.engine_id == L.ENGINE_MFMA and getattr(self, '_auto_switched', False):
+        if ((self.auto_engine or getattr(self, '_probe_switched', False)) and self.engine_id == L.ENGINE_MFMA
+                and getattr(self, '_auto_switched', False)):
             # the fallback was for the OTHER weights: these get the chance of the engine the caller had chosen again
             self.set_engine(getattr(self, '_engine_before_auto', L.ENGINE_FUSED))
             self._auto_switched = False
+            self._probe_switched = False
+        self._probe = None
+        if probe is None:
+            return
+        batch = self.probe_batch() if probe is True else tuple(probe)
+        res = self.accuracy_probe(*batch)             # (a refusal of the range check is handled as every ranged call's)
+        names = dict((v, k) for k, v in L.ENGINES.items())
+        self._probe = dict(res, engine=names[self.engine_id])
+        if max_disp_rel is None or res['disp_rel'] <= max_disp_rel:
+            return
+        msg = ('the %s engine is %.3e of the largest displacement away from the float64 evaluation on these weights '
+               '(particle %d), beyond the %.3e asked for' % (names[self.engine_id], res['disp_rel'], res['worst'], max_disp_rel))
+        if self.engine_id not in (L.ENGINE_FUSED, L.ENGINE_SPLIT):
+            raise L.DrpError(msg + ': the fp32 engines have nowhere to fall back to')
+        import warnings
+        warnings.warn(msg + ': continuing on the fp32 matrix engine', RuntimeWarning, stacklevel=2)
+        self._engine_before_auto = self.engine_id     # restored by the next load_weights: the finding belongs to these weights
+        self.set_engine(L.ENGINE_MFMA)
+        self._auto_switched = True
+        self._probe_switched = True
+
+    def probe_batch(self):
+        """The fixed batch of load_weights(probe=True): 8 samples x 64 particles, one pile and eight pushes of the synthetic
+        scene, seed 0, through gen_s_delta (so the camera must be set) -> (a_cur, s_cur, s_delta, dens)."""
+        from . import synthetic as syn
+        s0, dens, attr = syn.make_pile(64, 1, seed=0)
+        acts = syn.sample_pushes(8, 1, seed=0)[:, 0]
+        s = np.repeat(s0, 8, axis=0)
+        return np.repeat(attr, 8, axis=0), s, self.gen_s_delta(s, acts), np.repeat(dens, 8)
 
     def set_camera(self, m34, global_scale, intr):
         m34 = _f32(m34).ravel()
@@ -312,6 +350,66 @@ class Engine(object):
                                                   nbr_idx.ctypes.data_as(L.c_int16_p),
                                                   nbr_cnt.ctypes.data_as(L.c_uint8_p), B, N, _fp(out)))
         return out
+
+    # ---- the float64 yardstick (include/drp.h: drp_forward_f64 ... drp_accuracy_probe) ---------------------------
+    def step_f64(self, a_cur, s_cur, s_delta, dens):
+        """predict_one_step evaluated in float64 on the device (fp32 inputs and weights widened exactly) -> [B,N,3] float64"""
+        a_cur, s_cur, s_delta, dens = _f32(a_cur), _f32(s_cur), _f32(s_delta), _f32(dens)
+        B, N, _ = s_cur.shape
+        assert a_cur.shape == (B, N) and s_delta.shape == (B, N, 3) and dens.shape == (B,)
+        out = np.empty((B, N, 3), dtype=np.float64)
+        self._ck(self.lib.drp_step_f64(self.h, _fp(a_cur), _fp(s_cur), _fp(s_delta), _fp(dens), B, N, _dp(out)))
+        self._f64_shape = (B, N)
+        return out
+
+    def forward_f64(self, a_cur, s_cur, s_delta, dens, nbr_idx, nbr_cnt):
+        """forward() with explicit relations, in float64 -> [B,N,3] float64"""
+        a_cur, s_cur, s_delta, dens = _f32(a_cur), _f32(s_cur), _f32(s_delta), _f32(dens)
+        nbr_idx = np.ascontiguousarray(nbr_idx, dtype=np.int16)
+        nbr_cnt = np.ascontiguousarray(nbr_cnt, dtype=np.uint8)
+        B, N, _ = s_cur.shape
+        assert a_cur.shape == (B, N) and s_delta.shape == (B, N, 3) and dens.shape == (B,)
+        assert nbr_idx.shape == (B, N, L.DRP_K) and nbr_cnt.shape == (B, N)
+        out = np.empty((B, N, 3), dtype=np.float64)
+        self._ck(self.lib.drp_forward_f64(self.h, _fp(a_cur), _fp(s_cur), _fp(s_delta), _fp(dens),
+                                          nbr_idx.ctypes.data_as(L.c_int16_p), nbr_cnt.ctypes.data_as(L.c_uint8_p), B, N, _dp(out)))
+        self._f64_shape = (B, N)
+        return out
+
+    def f64_tap(self, name):
+        """float64 intermediate of the last step_f64 / forward_f64 / accuracy_probe: 'particle_encode' [B,N,64],
+        'relation_encode' [B,N,10,64], 'effect_rel_p' [B,N,10,64], 'agg_p' and 'effect_p' [B,N,64] (p = 0..2),
+        'particle_pred' [B,N,3]"""
+        B, N = getattr(self, '_f64_shape', (0, 0))
+        if name.startswith(('relation_encode', 'c_edge', 'effect_rel_')):
+            shape = (B, N, L.DRP_K, L.DRP_F)
+        else:
+            shape = (B, N, 3 if name == 'particle_pred' else L.DRP_F)
+        out = np.empty(shape, np.float64)
+        self._ck(self.lib.drp_f64_tap(self.h, name.encode(), _dp(out), out.size))
+        return out
+
+    def set_f64_cap(self, n_bytes=0):
+        """bytes of float64 workspace a *_f64 call may hold (0: the default, 256 MB); the batch is walked in chunks under it"""
+        self._ck(self.lib.drp_debug_set_f64_cap(self.h, int(n_bytes)))
+
+    def accuracy_probe(self, a_cur, s_cur, s_delta, dens, engine=None):
+        """One step on `engine` (default: the selected one) against the float64 evaluation of the same step, reduced on the
+        device -> {'abs': max |s_pred - s_pred_f64|, 'disp': max |s_pred_f64 - s_cur|, 'disp_rel': abs / max(disp, 1e-12),
+        'worst': index b * N + n of the worst particle}.  The selected engine stays selected."""
+        a_cur, s_cur, s_delta, dens = _f32(a_cur), _f32(s_cur), _f32(s_delta), _f32(dens)
+        B, N, _ = s_cur.shape
+        assert a_cur.shape == (B, N) and s_delta.shape == (B, N, 3) and dens.shape == (B,)
+        out = np.zeros(4, np.float64)
+
+        def call(e):
+            return self.lib.drp_accuracy_probe(self.h, int(e), _fp(a_cur), _fp(s_cur), _fp(s_delta), _fp(dens), B, N, _dp(out))
+        if engine is None:
+            self._ranged(lambda: call(self.engine_id))        # of the selected engine: a refusal is handled as its calls' are
+        else:
+            self._ck(call(engine))
+        self._f64_shape = (B, N)
+        return {'abs': float(out[0]), 'disp': float(out[1]), 'disp_rel': float(out[2]), 'worst': int(out[3])}
 
     def rollout(self, s0, attr, dens, actions, want_states=True, want_reward=False):
         s0, attr, dens, actions = _f32(s0), _f32(attr), _f32(dens), _f32(actions)
@@ -709,11 +807,15 @@ class Engine(object):
         return [s for s in buf.value.decode().split(';') if s]
 
     def range_info(self):
-        """{'shift', 'bound', 'wmax', 'ok'} of the split-fp16 relation encoder for the loaded weights (drp_range_info)."""
+        """{'shift', 'bound', 'wmax', 'ok'} of the split-fp16 relation encoder for the loaded weights (drp_range_info); after
+        load_weights(probe=...) also 'probe': {'abs', 'disp', 'disp_rel', 'worst', 'engine'}."""
         k, ok = ctypes.c_int(), ctypes.c_int()
         bound, wmax = ctypes.c_double(), ctypes.c_double()
         self._ck(self.lib.drp_range_info(self.h, ctypes.byref(k), ctypes.byref(bound), ctypes.byref(wmax), ctypes.byref(ok)))
-        return {'shift': k.value, 'bound': bound.value, 'wmax': wmax.value, 'ok': bool(ok.value)}
+        info = {'shift': k.value, 'bound': bound.value, 'wmax': wmax.value, 'ok': bool(ok.value)}
+        if getattr(self, '_probe', None) is not None:
+            info['probe'] = dict(self._probe)         # what load_weights(probe=...) measured, and on which engine
+        return info
 
     def debug_fetch(self, name, shape, dtype=np.float32):
         out = np.empty(shape, dtype=dtype)

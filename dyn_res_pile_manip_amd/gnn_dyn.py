@@ -29,6 +29,21 @@ def _like(out, proto):
     return torch.from_numpy(out).to(device=proto.device, dtype=proto.dtype)
 
 
+def _is_float64(dtype):
+    if dtype is None:
+        return False
+    if str(dtype) == 'torch.float64' or (not str(dtype).startswith('torch.') and np.dtype(dtype) == np.float64):
+        return True
+    raise ValueError('dtype %r: None (the engine\'s fp32) or float64' % (dtype,))
+
+
+def _like64(out, proto):
+    if proto is None:
+        return out
+    import torch
+    return torch.from_numpy(out).to(device=proto.device)
+
+
 def relations_to_lists(Rr, Rs):
     """Dense one-hot Rr/Rs [B,E,N] (model/gnn_dyn.py:248-251) -> receiver-major lists
     nbr_idx [B,N,10] int16, nbr_cnt [B,N] uint8 (edge order preserved per receiver)."""
@@ -133,10 +148,14 @@ class PropNetDiffDenModel(object):
     def to(self, *a, **k):
         return self
 
-    def load_state_dict(self, state_dict, strict=True):
+    def load_state_dict(self, state_dict, strict=True, probe=None, max_disp_rel=None):
+        """probe / max_disp_rel: Engine.load_weights' -- measure the engine against the float64 evaluation on these weights"""
         import weakref
         self._blob = _weights.blob_from_state_dict(state_dict, strict=strict)
-        self.engine.load_weights(self._blob, self.adj_thresh)
+        if probe is None and max_disp_rel is None:
+            self.engine.load_weights(self._blob, self.adj_thresh)
+        else:
+            self.engine.load_weights(self._blob, self.adj_thresh, probe=probe, max_disp_rel=max_disp_rel)
         self.engine._weights_owner = weakref.ref(self)
         self._device_ahead = False
         return self
@@ -158,13 +177,16 @@ class PropNetDiffDenModel(object):
         self.training = bool(mode)
         return self
 
-    def predict_one_step(self, a_cur, s_cur, s_delta, particle_dens, particle_nums=None):
+    def predict_one_step(self, a_cur, s_cur, s_delta, particle_dens, particle_nums=None, dtype=None):
+        """dtype: None (the engine's fp32, returned like the inputs) or float64 (torch.float64 / np.float64): the step evaluated
+        in float64 on the device (Engine.step_f64), returned as doubles on the inputs' device"""
         a, proto = _to_np(a_cur)
         s, _ = _to_np(s_cur)
         sd, _ = _to_np(s_delta)
         d, _ = _to_np(particle_dens)
         assert a.shape == s.shape[:2]            # model/gnn_dyn.py:218-219
         assert s.shape == sd.shape
+        f64 = _is_float64(dtype)
         self._claim()
         if particle_nums is not None:
             # model/gnn_dyn.py:238-241: rows/columns beyond particle_nums[b] leave the graph.
@@ -172,5 +194,9 @@ class PropNetDiffDenModel(object):
             # device, mask them on the host, run forward with explicit relations.
             idx, cnt = self.engine.build_graph(s, sd)
             idx, cnt = mask_lists(idx, particle_nums)
+            if f64:
+                return _like64(self.engine.forward_f64(a, s, sd, d, idx, cnt), proto)
             return _like(self.engine.forward(a, s, sd, d, idx, cnt), proto)
+        if f64:
+            return _like64(self.engine.step_f64(a, s, sd, d), proto)
         return _like(self.engine.step(a, s, sd, d), proto)

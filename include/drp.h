@@ -456,6 +456,41 @@ int drp_debug_stall(drp_ctx* ctx, int ms);
  * int32) (byte sizes: the returned value). returns bytes. */
 long drp_debug_fetch(drp_ctx* ctx, const char* name, void* out, size_t out_bytes);
 
+/* ---- the float64 yardstick: one step evaluated in double on the device, and a probe that holds an engine against it ----
+ * Not a value of drp_set_engine: it has no dispatch plan and leaves no trace in drp_last_dispatch.  It stages in buffers of
+ * its own, so none of these calls ends a planner session, and none changes the engine drp_set_engine selected.
+ *
+ * PropModuleDiffDen.forward (model/gnn_dyn.py:147-198) in float64, relations as lists (as drp_forward); the inputs are the
+ * fp32 values widened exactly, the weights the loaded fp32 blob widened exactly (after a training step: the updated blob).
+ * The reference's own formulation -- relation propagator over cat[relation_encode, effect_r, effect_s, dens] (:186-187),
+ * particle propagator over cat[particle_encode, agg, dens] with the residual inside the ReLU (:191-193, :82-85) -- on
+ * v_mfma_f64_16x16x4_f64.  One reduction order per output (ascending k, ascending slot), no atomics: a sample's result is
+ * the same bits alone, in any batch and from run to run.  The batch is walked in sample chunks under a workspace cap
+ * (256 MB; 24 KB of float64 intermediates per particle), which changes no bit.  Shape limits as drp_forward; a list entry
+ * outside 0..N-1 or a count above 10 is DRP_EINVAL.  s_pred_out [B,N,3] double. */
+int drp_forward_f64(drp_ctx* ctx, const float* a_cur, const float* s_cur, const float* s_delta, const float* dens,
+                    const int16_t* nbr_idx, const uint8_t* nbr_cnt, int B, int N, double* s_pred_out);
+/* predict_one_step (model/gnn_dyn.py:209-254): the lists from the library's own fp32 graph build (bit-exact with the
+ * reference's, :223-251), then the above. */
+int drp_step_f64(drp_ctx* ctx, const float* a_cur, const float* s_cur, const float* s_delta, const float* dens, int B, int N,
+                 double* s_pred_out);
+/* The float64 intermediates of the last drp_forward_f64 / drp_step_f64 / drp_accuracy_probe, n doubles (exactly the tap's size):
+ * "particle_encode" [B,N,64] (:174; also answered as "c_node"), "relation_encode" [B,N,10,64] (:179, receiver-major slots,
+ * zeros past a receiver's count; also "c_edge"), and for the propagation steps p = 0..2 "effect_rel_p" [B,N,10,64] (:186),
+ * "agg_p" [B,N,64] (:189), "effect_p" [B,N,64] (:191; also "particle_effect_p"); "particle_pred" [B,N,3] (:196).
+ * DRP_ESTATE when that call walked its batch in more than one chunk. */
+int drp_f64_tap(drp_ctx* ctx, const char* name, double* out, size_t n);
+/* the workspace cap of the *_f64 calls in bytes (0: the default, 256 MB); one sample is the smallest chunk.  Tests lower it
+ * to force chunking. */
+int drp_debug_set_f64_cap(drp_ctx* ctx, size_t bytes);
+/* drp_step's path on `engine` (DRP_ENGINE_*, any of the four) and drp_step_f64 on the same inputs and the same lists, reduced
+ * on the device: out[0] = max |s_pred_engine - s_pred_f64| (the fp32 value widened, the difference in double),
+ * out[1] = max |s_pred_f64 - s_cur|, out[2] = out[0] / max(out[1], 1e-12) (the error as a share of the largest displacement,
+ * the quantity the 1e-4 parity tolerance is stated in), out[3] = index b * N + n of the worst particle (ties: the lowest).
+ * A refusal of the engine (DRP_ERANGE) is returned as such. */
+int drp_accuracy_probe(drp_ctx* ctx, int engine, const float* a_cur, const float* s_cur, const float* s_delta,
+                       const float* dens, int B, int N, double out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,3 +17,17 @@ for case in ('n64', 'n8'):
         eng.step(a, s, sd, d)
         eff = eng.debug_fetch('effect', ref.shape)
         print('%-4s %-5s final effect: max |err| / max |ref| = %.2e' % (case, name, np.abs(eff - ref).max() / np.abs(ref).max()))
+
+# the float64 yardstick: every engine's one-step error against the device's float64 evaluation of the same step
+# (Engine.accuracy_probe), as a share of the largest displacement, on the seed-0 and on the trained weights
+t = np.load('tests/golden/trained.npz')
+legs = [('seed-0', w, [(g, c + '/') for c in ('n8', 'n64')]),
+        ('trained', np.load('tests/golden/weights_trained.npz'), [(t, 'one_step/%s/' % c) for c in ('n20', 'n50', 'n100', 'n300')])]
+for label, wts, cases in legs:
+    eng.load_weights(weights.blob_from_state_dict(wts), 0.08)
+    for src, p in cases:
+        a, s, sd, d = [src[p + k] for k in ('attr', 's_cur', 's_delta', 'dens')]
+        for name in ('valu', 'mfma', 'split', 'fused'):
+            r = eng.accuracy_probe(a, s, sd, d, engine=_lib.ENGINES[name])
+            print('%-7s %-14s %-5s against float64: max |err| %.3e, largest displacement %.3e, ratio %.3e (particle %d)'
+                  % (label, p, name, r['abs'], r['disp'], r['disp_rel'], r['worst']))
