@@ -18,6 +18,7 @@ ENGINE_VALU = 0
 ENGINE_MFMA = 1
 ENGINE_SPLIT = 2
 ENGINE_FUSED = 3
+ENGINE_LITE = 4             # opt-in reduced products on the fused engine's kernels (include/drp.h: DRP_ENGINE_LITE)
 TRAIN_MODES = {'eval': 0, 'grad': 1, 'update': 2}
 DIST_TRANSFORMS = {'cv5': 0, 'exact': 1}
 RGR_REGRESSOR = 1           # DRP_RGR_REGRESSOR: n_out of the MPCResRgrNoPool head
@@ -26,7 +27,7 @@ RGR_BMAX = 64
 PD_BMAX = 1024              # drp_ptcl_dataset_batch: samples per call
 PD_CAP = 4096               # particles per sample
 NOISE_TYPES = {'normal': 0, 'uniform': 1, 'total_rand': 2}
-ENGINES = {'valu': ENGINE_VALU, 'mfma': ENGINE_MFMA, 'split': ENGINE_SPLIT, 'fused': ENGINE_FUSED}
+ENGINES = {'valu': ENGINE_VALU, 'mfma': ENGINE_MFMA, 'split': ENGINE_SPLIT, 'fused': ENGINE_FUSED, 'lite': ENGINE_LITE}
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
 c_double_p = ctypes.POINTER(ctypes.c_double)

@@ -14,7 +14,7 @@ const char* const kclass_names[KC_COUNT] = {"graph", "node_encode", "edge_encode
 
 // the variant names (DispatchVariant, dv_name), the dispatch policy and the plan functions: host-only, csrc/dispatch.h
 using namespace dispatch;
-static_assert(ENGINE_VALU == DRP_ENGINE_VALU && ENGINE_MFMA == DRP_ENGINE_MFMA && ENGINE_SPLIT == DRP_ENGINE_SPLIT && ENGINE_FUSED == DRP_ENGINE_FUSED &&
+static_assert(ENGINE_VALU == DRP_ENGINE_VALU && ENGINE_MFMA == DRP_ENGINE_MFMA && ENGINE_SPLIT == DRP_ENGINE_SPLIT && ENGINE_FUSED == DRP_ENGINE_FUSED && ENGINE_LITE == DRP_ENGINE_LITE &&
               K == DRP_K && GRAPH_THREADS_ == GRAPH_THREADS && GC_MAX_BANDS_ == GC_MAX_BANDS && GC_THREADS_ == GC_THREADS && PROP_WAVES_ == PROP_WAVES &&
               EC_UNITS_ == EC_UNITS && ROLLOUT_MAX_ROWS == KM_ROLLOUT_MAX_ROWS && BWD_ROWS_MAX == KMB_ROWS_MAX && COOP_SLOTS == KMB_COOP_SLOTS &&
               AGG_LDS_MAX_N == K_AGG_LDS_MAX_N && DEG_STAT_ROWS == DEG_STAT_MAX_ROWS && spread_grid(33) == SPREAD_GRID(33),
@@ -324,6 +324,7 @@ struct drp_ctx {
     DevBuf probe_work;              // PROP_WORK_* counters of the propagation kernels while their class is probed
     bool probe_count = false;       // drp_probe_begin("prop+work"): the kernels count what they execute (not for timed regions: the
                                     // counting costs the 300-particle launch 8 %)
+    bool work_lite = false, work_full = false;   // which term counts the counted launches ran with (drp_probe_work weighs the units by them)
     unsigned long long* work_ptr() const { return (probe_cls == KC_PROP && probe_count) ? static_cast<unsigned long long*>(probe_work.p) : nullptr; }
     int probe_cls = -1;
     std::vector<Event> probe_ev;

@@ -34,6 +34,7 @@ int drp_probe_begin(drp_ctx* c, const char* kernel_class) {
     c->probe_cls = -1;
     c->probe_used = 0;
     c->probe_count = false;
+    c->work_lite = c->work_full = false;
     if (!kernel_class || !*kernel_class) return DRP_OK;
     if (strcmp(kernel_class, "prop+work") == 0) { kernel_class = "prop"; c->probe_count = true; }
     for (int i = 0; i < KC_COUNT; ++i)
@@ -60,9 +61,13 @@ int drp_probe_work(drp_ctx* c, unsigned long long out[8]) {
     for (int q = 0; q < PROP_WORK_SHARDS; ++q)
         for (int i = 0; i < PROP_WORK_COUNT; ++i) w[i] += sh[(size_t)q * PROP_WORK_STRIDE + i];
     for (int i = 0; i < PROP_WORK_COUNT; ++i) out[i] = w[i];
-    // the matrix instructions those units are made of (k_mlp_split.h: the chain of an edge slot, the node layers of a tile)
-    out[5] = (unsigned long long)PROP_MFMA_CHAIN * w[PROP_WORK_CHAIN_SLOTS] + (unsigned long long)PROP_MFMA_NODE * w[PROP_WORK_TILES] +
-             (unsigned long long)PROP_MFMA_NODE_LAST * w[PROP_WORK_TILES_LAST] + (unsigned long long)PROP_MFMA_ENC * w[PROP_WORK_ENC_TILES];
+    // the matrix instructions those units are made of (k_mlp_split.h: the chain of an edge slot, the node layers of a tile), by the
+    // term counts of the engine the counted launches ran on
+    if (c->work_lite && c->work_full)
+        return fail(c, DRP_ESTATE, "the counted launches ran on both the fused and the lite engine: their units weigh differently; count one engine per drp_probe_begin");
+    const bool lite = c->work_lite;
+    out[5] = (unsigned long long)prop_mfma_chain(lite) * w[PROP_WORK_CHAIN_SLOTS] + (unsigned long long)prop_mfma_node(lite) * w[PROP_WORK_TILES] +
+             (unsigned long long)prop_mfma_node_last(lite) * w[PROP_WORK_TILES_LAST] + (unsigned long long)prop_mfma_enc(lite) * w[PROP_WORK_ENC_TILES];
     // shader-clock cycles and 100 MHz ticks between entry and exit, summed over the workgroups of the counted launches
     out[6] = 0; out[7] = 0;
     for (int q = 0; q < PROP_WORK_SHARDS; ++q) {

@@ -187,7 +187,8 @@ int drp_accuracy_probe(drp_ctx* c, int engine, const float* a_cur, const float* 
                        int B, int N, double out[4]) {
     CHK(f64_check_inputs(c, a_cur, s_cur, s_delta, dens, B, N));
     if (!out) return fail(c, DRP_EINVAL, "null buffer");
-    if (engine != DRP_ENGINE_VALU && engine != DRP_ENGINE_MFMA && engine != DRP_ENGINE_SPLIT && engine != DRP_ENGINE_FUSED)
+    if (engine != DRP_ENGINE_VALU && engine != DRP_ENGINE_MFMA && engine != DRP_ENGINE_SPLIT && engine != DRP_ENGINE_FUSED &&
+        engine != DRP_ENGINE_LITE)
         return fail(c, DRP_EINVAL, "engine %d not available in this build", engine);
     F64Scope scope(c);              // restores the selected engine, too
     c->engine = engine;

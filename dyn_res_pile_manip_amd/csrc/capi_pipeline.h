@@ -199,7 +199,7 @@ int ensure_step_ws(drp_ctx* c, int B, int N, int engine = -1) {
     // edge constants [B,N,10,64] for the engines that materialise them; the fused engine only parks the graph build's
     // sorted positions and strip starts there (launch_graph)
     const size_t graph_scratch = (size_t)B * (((size_t)N + 3) & ~(size_t)3) * 16 + (size_t)B * (GC_MAX_BANDS * GC_XS + 1) * sizeof(int);
-    CHK(ensure(c, c->c_edge, engine == DRP_ENGINE_FUSED ? graph_scratch : std::max(graph_scratch, bn * DRP_K * 64 * sizeof(float))));
+    CHK(ensure(c, c->c_edge, engine_is_fused(engine) ? graph_scratch : std::max(graph_scratch, bn * DRP_K * 64 * sizeof(float))));
     c->lastB = B;
     c->lastN = N;
     return DRP_OK;
@@ -319,7 +319,14 @@ struct PropTables {
     decltype(&km_prop<false, false, false, false>) prop[PropFlags::COUNT];
     decltype(&km_prop3<false, false, false, false, false>) prop3[Prop3Flags::COUNT];
     decltype(&km_rollout<false, false, false, false>) rollout[RolloutFlags::COUNT];
+    // the reduced-product instantiations (ENGINE_LITE), by lite_index()
+    decltype(&km_prop<false, false, false, false>) prop_lite[PropFlags::LITE_COUNT];
+    decltype(&km_prop3<false, false, false, false, false>) prop3_lite[Prop3Flags::LITE_COUNT];
+    decltype(&km_rollout<false, false, false, false>) rollout_lite[RolloutFlags::LITE_COUNT];
     int filled = 0;
+    auto of(const PropFlags& f) const { return f.lite ? prop_lite[f.lite_index()] : prop[f.index()]; }
+    auto of(const Prop3Flags& f) const { return f.lite ? prop3_lite[f.lite_index()] : prop3[f.index()]; }
+    auto of(const RolloutFlags& f) const { return f.lite ? rollout_lite[f.lite_index()] : rollout[f.index()]; }
 };
 const PropTables& prop_tables() {
     static const PropTables tables = [] {
@@ -332,6 +339,15 @@ const PropTables& prop_tables() {
         KM_PROP3_LIST_TAPE(KM_TAB_PROP3, false)
         KM_PROP3_LIST_TAPE(KM_TAB_PROP3, true)
         KM_ROLLOUT_LIST(KM_TAB_ROLLOUT)
+#define KM_TAB_PROP_LITE(L, T, P, W) t.prop_lite[PropFlags{L, T, P, W, true}.lite_index()] = km_prop<L, T, P, W, true>; ++t.filled;
+#define KM_TAB_PROP3_LITE(T, P, E, W, O) t.prop3_lite[Prop3Flags{T, P, (E) ? ((O) ? 2 : 1) : 0, W, true}.lite_index()] = km_prop3<T, P, E, W, O, true>; ++t.filled;
+#define KM_TAB_ROLLOUT_LITE(P, E, W, O) t.rollout_lite[RolloutFlags{P, (E) ? ((O) ? 2 : 1) : 0, W, true}.lite_index()] = km_rollout<P, E, W, O, true>; ++t.filled;
+        KM_PROP_LIST_TAPE(KM_TAB_PROP_LITE, false)
+        KM_PROP3_LIST_TAPE(KM_TAB_PROP3_LITE, false)
+        KM_ROLLOUT_LIST(KM_TAB_ROLLOUT_LITE)
+#undef KM_TAB_PROP_LITE
+#undef KM_TAB_PROP3_LITE
+#undef KM_TAB_ROLLOUT_LITE
 #undef KM_TAB_PROP
 #undef KM_TAB_PROP3
 #undef KM_TAB_ROLLOUT
@@ -344,7 +360,13 @@ static_assert(sizeof(PropTables::prop) / sizeof(void*) == PropFlags::COUNT && si
 // drp_create: every entry is there, and may use its dynamic LDS
 bool prop_tables_ready() {
     const PropTables& t = prop_tables();
-    bool ok = t.filled == PropFlags::COUNT + Prop3Flags::COUNT + RolloutFlags::COUNT;
+    bool ok = t.filled == PropFlags::COUNT + Prop3Flags::COUNT + RolloutFlags::COUNT + PropFlags::LITE_COUNT + Prop3Flags::LITE_COUNT + RolloutFlags::LITE_COUNT;
+    for (int q = 0; q < PropFlags::LITE_COUNT && ok; ++q)
+        ok = t.prop_lite[q] && hipFuncSetAttribute((const void*)t.prop_lite[q], hipFuncAttributeMaxDynamicSharedMemorySize, KM_PROP_LDS(PropFlags::from_lite_index(q).last)) == hipSuccess;
+    for (int q = 0; q < Prop3Flags::LITE_COUNT && ok; ++q)
+        ok = t.prop3_lite[q] && hipFuncSetAttribute((const void*)t.prop3_lite[q], hipFuncAttributeMaxDynamicSharedMemorySize, KM_PROP3_LDS) == hipSuccess;
+    for (int q = 0; q < RolloutFlags::LITE_COUNT && ok; ++q)
+        ok = t.rollout_lite[q] && hipFuncSetAttribute((const void*)t.rollout_lite[q], hipFuncAttributeMaxDynamicSharedMemorySize, KM_ROLLOUT_LDS) == hipSuccess;
     for (int q = 0; q < PropFlags::COUNT && ok; ++q)
         ok = t.prop[q] && hipFuncSetAttribute((const void*)t.prop[q], hipFuncAttributeMaxDynamicSharedMemorySize, KM_PROP_LDS(PropFlags::from_index(q).last)) == hipSuccess;
     for (int q = 0; q < Prop3Flags::COUNT && ok; ++q)
@@ -378,13 +400,13 @@ int run_step_mfma(drp_ctx* c, const StepArgs& a, const StepPlan& k) {
     // the tape of the reverse-mode kernels: km_prop<., TAPE> on the fused engine; on the fp32 matrix engine (what the
     // gradient-descent planner and the trainer fall back to when the split-fp16 relation encoder refuses the weights or the
     // inputs) the stage kernels run as always and the tape is copied / written beside them (tape_mfma below)
-    if (tape && c->engine != DRP_ENGINE_FUSED && c->engine != DRP_ENGINE_MFMA)
+    if (tape && c->engine != DRP_ENGINE_FUSED && c->engine != DRP_ENGINE_MFMA)       // (run_tape_forward lends the context one of the two)
         return fail(c, DRP_ESTATE, "the backward tape is written by the fused or the fp32 matrix engine");
     float* eff0 = (tape && !k.tape_mfma) ? a.eff_hist : ptr<float>(c->eff);
     if (k.node_encode) {
         ProbeScope ps(c, KC_NODE_ENCODE);
         if (k.fused)
-            hipLaunchKernelGGL(km_node_encode_split, dim3(mfma_grid_spread(c, node_tiles)), blk, KM_NODE_SPLIT_LDS, st,
+            hipLaunchKernelGGL(k.lite ? km_node_encode_split<true> : km_node_encode_split<false>, dim3(mfma_grid_spread(c, node_tiles)), blk, KM_NODE_SPLIT_LDS, st,
                                ptr<uint16_t>(c->w_split6), mw, ptr<float>(c->s_delta), a.attr, a.attr_mod, a.dens,
                                a.dens_mod, N, B, eff0, ptr<float>(c->c_node), ptr<float>(c->proj));
         else
@@ -397,6 +419,7 @@ int run_step_mfma(drp_ctx* c, const StepArgs& a, const StepPlan& k) {
         float* pa = ptr<float>(c->proj);
         float* pb = ptr<float>(c->proj2);
         unsigned long long* const wk = c->work_ptr();    // not null: the counting instantiations (drp_probe_begin("prop+work"))
+        if (wk) (k.lite ? c->work_lite : c->work_full) = true;
         const dim3 pblk(64 * PROP_WAVES);
         if (k.prop3) {
             // one launch per block of samples (dispatch.h: cut_blocks) -- the tape's launches too: the history buffers are laid
@@ -412,7 +435,7 @@ int run_step_mfma(drp_ctx* c, const StepArgs& a, const StepPlan& k) {
                 const size_t ro = (size_t)b.b_off * N;
                 const bool own_prev = a.prev_mod >= B, own_attr = a.attr_mod >= B, own_dens = a.dens_mod >= B;
                 if (b.cache_bytes > c->ecache.cap) CHK(ensure(c, c->ecache, b.cache_bytes));
-                hipLaunchKernelGGL(prop_tables().prop3[k.prop3_flags(b).index()], dim3((unsigned)b.grid), pblk, KM_PROP3_LDS, st,
+                hipLaunchKernelGGL(prop_tables().of(k.prop3_flags(b)), dim3((unsigned)b.grid), pblk, KM_PROP3_LDS, st,
                                    ptr<uint16_t>(c->w_split), ptr<uint16_t>(c->w_split6), mw,
                                    own_prev ? a.s_prev + (size_t)b.b_off * a.prev_stride : a.s_prev, own_prev ? b.Bc : a.prev_mod, a.prev_stride,
                                    own_attr ? a.attr + ro : a.attr, own_attr ? b.Bc : a.attr_mod,
@@ -431,8 +454,7 @@ int run_step_mfma(drp_ctx* c, const StepArgs& a, const StepPlan& k) {
         for (int p = 0; p < DRP_PSTEP && !k.prop3; ++p) {
             const bool last = (p + 1 == DRP_PSTEP);
             ProbeScope ps(c, KC_PROP);
-            const PropFlags f{last, tape, k.pair, k.work};
-            hipLaunchKernelGGL(prop_tables().prop[f.index()], dim3((unsigned)k.grid), pblk, KM_PROP_LDS(last), st,
+            hipLaunchKernelGGL(prop_tables().of(k.prop_flags(last)), dim3((unsigned)k.grid), pblk, KM_PROP_LDS(last), st,
                                ptr<uint16_t>(c->w_split), ptr<uint16_t>(c->w_split6), mw, a.s_prev, a.prev_mod, a.prev_stride,
                                a.attr, a.attr_mod, a.dens, a.dens_mod, ptr<int16_t>(c->nbr_idx), ptr<uint8_t>(c->nbr_cnt), pa,
                                ptr<float>(c->c_node), tape ? a.eff_hist + (size_t)p * bn64 : ptr<float>(c->eff),
@@ -500,7 +522,7 @@ int run_step(drp_ctx* c, const StepArgs& a) {
     k.mark(c->dv_hit);
     if (a.build_graph) {
         ProbeScope ps(c, KC_GRAPH);
-        const int self_first = (c->engine == DRP_ENGINE_FUSED && a.cself != nullptr) ? 1 : 0;
+        const int self_first = (engine_is_fused(c->engine) && a.cself != nullptr) ? 1 : 0;
         switch (k.graph.kind) {
         case GraphPlan::REV:
             // the GD planner's forward, samples of one graph chunk: the reversed lists in the lists' own launch
@@ -512,7 +534,7 @@ int run_step(drp_ctx* c, const StepArgs& a) {
         case GraphPlan::Q4_ENCODE:
             // a handful of samples whose impulses are data (the trainer's forward pass): the lists and the particle encoder
             // read nothing of one another -- one launch (k_rollout.h)
-            hipLaunchKernelGGL(km_graph_q4_encode, dim3((unsigned)(k.graph.grid + mfma_grid_spread(c, (long)B * ((N + 31) / 32)))), dim3(GRAPH_Q4_THREADS),
+            hipLaunchKernelGGL(k.graph.lite ? km_graph_q4_encode<true> : km_graph_q4_encode<false>, dim3((unsigned)(k.graph.grid + mfma_grid_spread(c, (long)B * ((N + 31) / 32)))), dim3(GRAPH_Q4_THREADS),
                                KM_GRAPH_Q4_ENCODE_LDS(N), st, a.s_prev, a.prev_mod, a.prev_stride, s_delta, N, B, nbr_idx, nbr_cnt, c->cam,
                                c->thr, k.graph.chunks, self_first, (int)k.graph.grid, ptr<uint16_t>(c->w_split6), ptr<float>(c->w_mfma), a.attr, a.attr_mod,
                                a.dens, a.dens_mod, k.tape ? a.eff_hist : ptr<float>(c->eff), ptr<float>(c->c_node), ptr<float>(c->proj));
@@ -579,7 +601,7 @@ int prepare_cself(drp_ctx* c, int attr_mod, int N, int B, const float** cself, c
     if (engine < 0) engine = c->engine;
     *cself = nullptr;
     *cself_ok = nullptr;
-    if (engine == DRP_ENGINE_FUSED && c->pol.self_const) {
+    if (engine_is_fused(engine) && c->pol.self_const) {
         CHK(ensure(c, c->cself, (size_t)B * 64 * sizeof(float) + (size_t)B));
         float* cs = ptr<float>(c->cself);
         uint8_t* ok = reinterpret_cast<uint8_t*>(cs + (size_t)B * 64);
@@ -639,6 +661,7 @@ int run_rollout(drp_ctx* c, int nb, int N, int B, int H, bool reward_all, bool r
             ra.ec_stride = b.ec_stride;
             ra.ecache = k.blocks.cache ? ptr<float4>(c->ecache) : nullptr;
             ra.work = c->work_ptr();
+            if (ra.work) (k.lite ? c->work_lite : c->work_full) = true;
         }
         // the argument blocks sit in device memory; they are uploaded when they change (every iteration of an MPC session
         // passes the same ones), behind whatever still runs on the stream
@@ -652,7 +675,7 @@ int run_rollout(drp_ctx* c, int nb, int N, int B, int H, bool reward_all, bool r
         ProbeScope ps(c, KC_PROP);
         for (int q = 0; q < n_chunks; ++q) {
             const Block b = k.blocks.block(q);
-            hipLaunchKernelGGL(prop_tables().rollout[k.flags(b).index()], dim3((unsigned)b.grid), dim3(64 * PROP_WAVES), KM_ROLLOUT_LDS,
+            hipLaunchKernelGGL(prop_tables().of(k.flags(b)), dim3((unsigned)b.grid), dim3(64 * PROP_WAVES), KM_ROLLOUT_LDS,
                                c->stream, ptr<RolloutArgs>(c->roll_args) + q);
         }
         HIPCHK(c, hipGetLastError());
@@ -1070,7 +1093,7 @@ float push_len_bound(const drp_ctx* c, const float* actions, size_t n) {
 // tape: the caller runs the fused engine whatever drp_set_engine chose (the gradient-descent planner's and the trainer's
 // forward pass write their tape with it)
 int range_check(drp_ctx* c, float max_attr, float max_dens, float max_sdelta, bool tape = false) {
-    if (!tape && c->engine != DRP_ENGINE_FUSED && c->engine != DRP_ENGINE_SPLIT) return DRP_OK;
+    if (!tape && !engine_is_fused(c->engine) && c->engine != DRP_ENGINE_SPLIT) return DRP_OK;
     const double A = max_attr, dm = max_dens / DRP_DENS_SCALE, D = (double)c->adj_thresh + 2.0 * max_sdelta;
     const SplitRange& r = c->re_range;
     if (!c->re_ok)

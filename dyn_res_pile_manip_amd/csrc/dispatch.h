@@ -19,7 +19,11 @@
 namespace dispatch {
 
 // constants of the kernels the plans depend on (capi_ctx.h asserts each against the kernel header's own)
-constexpr int ENGINE_VALU = 0, ENGINE_MFMA = 1, ENGINE_SPLIT = 2, ENGINE_FUSED = 3;     // include/drp.h
+constexpr int ENGINE_VALU = 0, ENGINE_MFMA = 1, ENGINE_SPLIT = 2, ENGINE_FUSED = 3, ENGINE_LITE = 4;     // include/drp.h
+// ENGINE_LITE is the fused engine with fewer product terms in its kernels (k_mlp_split.h: TERMS): every plan below decides as for
+// ENGINE_FUSED -- the same kernels, cuts, grids and thresholds -- and only carries the flag on to the launch tables and the names.
+constexpr bool engine_is_fused(int engine) { return engine == ENGINE_FUSED || engine == ENGINE_LITE; }
+constexpr int engine_for_plan(int engine) { return engine == ENGINE_LITE ? ENGINE_FUSED : engine; }
 constexpr int K = 10;
 constexpr int GRAPH_THREADS_ = 128, GC_MAX_BANDS_ = 32, GC_THREADS_ = 256;
 constexpr int PROP_WAVES_ = 8, EC_UNITS_ = 512;
@@ -43,37 +47,67 @@ enum DispatchVariant {
     DV_BWD_EDGE_MFMA, DV_TRAIN_NODE_FUSED, DV_TRAIN_NODE_FUSED_COOP, DV_TRAIN_NODE_MFMA, DV_WGRAD_MFMA, DV_WGRAD_VALU,
     DV_WGRAD_DEFERRED, DV_MPPI_SOFTMAX, DV_ELITE_SORT, DV_ELITE_ROUNDS, DV_FPS_REG, DV_FPS_MEM, DV_DT_CV5, DV_DT_EXACT,
     DV_TRAIN_BARRIER_RETRY,
+    // the reduced-product instantiations of ENGINE_LITE (forward only: no tape), behind everything else so that no id moves
+    DV_PROP_LITE,                                   // + PropFlags::lite_index()
+    DV_PROP3_LITE = DV_PROP_LITE + 8,               // + Prop3Flags::lite_index()
+    DV_ROLLOUT_LITE = DV_PROP3_LITE + 12,           // + RolloutFlags::lite_index()
+    DV_NODE_ENCODE_SPLIT_LITE = DV_ROLLOUT_LITE + 12, DV_GRAPH_Q4_ENCODE_LITE,
     DV_COUNT
 };
 
 // The template flags of the three families, in one place: the launch tables (capi_pipeline.h), the names and the marks all
 // go through index() / from_index().  cache: 0 off, 1 on, 2 on with a tile's rows kept in registers between the steps.
+// lite: the reduced-product instantiation (never with tape); those have a table and an id range of their own (lite_index, variant).
 struct PropFlags {
-    bool last, tape, pair, work;
-    static constexpr int COUNT = 16;
+    bool last, tape, pair, work, lite = false;
+    static constexpr int COUNT = 16, LITE_COUNT = 8;
     constexpr int index() const { return 8 * (last ? 1 : 0) + 4 * (tape ? 1 : 0) + 2 * (pair ? 1 : 0) + (work ? 1 : 0); }
+    constexpr int lite_index() const { return 4 * (last ? 1 : 0) + 2 * (pair ? 1 : 0) + (work ? 1 : 0); }
+    constexpr int variant() const { return lite ? DV_PROP_LITE + lite_index() : DV_PROP + index(); }
     static constexpr PropFlags from_index(int f) { return PropFlags{(f & 8) != 0, (f & 4) != 0, (f & 2) != 0, (f & 1) != 0}; }
+    static constexpr PropFlags from_lite_index(int f) { return PropFlags{(f & 4) != 0, false, (f & 2) != 0, (f & 1) != 0, true}; }
 };
 struct Prop3Flags {
-    bool tape, pair; int cache; bool work;
-    static constexpr int COUNT = 24;
+    bool tape, pair; int cache; bool work, lite = false;
+    static constexpr int COUNT = 24, LITE_COUNT = 12;
     constexpr int index() const { return 12 * (tape ? 1 : 0) + 6 * (pair ? 1 : 0) + 2 * cache + (work ? 1 : 0); }
+    constexpr int lite_index() const { return 6 * (pair ? 1 : 0) + 2 * cache + (work ? 1 : 0); }
+    constexpr int variant() const { return lite ? DV_PROP3_LITE + lite_index() : DV_PROP3 + index(); }
     static constexpr Prop3Flags from_index(int f) { return Prop3Flags{f / 12 != 0, ((f / 6) & 1) != 0, (f % 6) / 2, (f & 1) != 0}; }
+    static constexpr Prop3Flags from_lite_index(int f) { return Prop3Flags{false, f / 6 != 0, (f % 6) / 2, (f & 1) != 0, true}; }
 };
 struct RolloutFlags {
-    bool pair; int cache; bool work;
-    static constexpr int COUNT = 12;
+    bool pair; int cache; bool work, lite = false;
+    static constexpr int COUNT = 12, LITE_COUNT = 12;
     constexpr int index() const { return 6 * (pair ? 1 : 0) + 2 * cache + (work ? 1 : 0); }
+    constexpr int lite_index() const { return index(); }
+    constexpr int variant() const { return lite ? DV_ROLLOUT_LITE + lite_index() : DV_ROLLOUT + index(); }
     static constexpr RolloutFlags from_index(int f) { return RolloutFlags{f / 6 != 0, (f % 6) / 2, (f & 1) != 0}; }
+    static constexpr RolloutFlags from_lite_index(int f) { return RolloutFlags{f / 6 != 0, (f % 6) / 2, (f & 1) != 0, true}; }
 };
-static_assert(DV_PROP3 - DV_PROP == PropFlags::COUNT && DV_ROLLOUT - DV_PROP3 == Prop3Flags::COUNT && DV_REWARD - DV_ROLLOUT == RolloutFlags::COUNT,
+static_assert(DV_PROP3 - DV_PROP == PropFlags::COUNT && DV_ROLLOUT - DV_PROP3 == Prop3Flags::COUNT && DV_REWARD - DV_ROLLOUT == RolloutFlags::COUNT &&
+              DV_PROP3_LITE - DV_PROP_LITE == PropFlags::LITE_COUNT && DV_ROLLOUT_LITE - DV_PROP3_LITE == Prop3Flags::LITE_COUNT &&
+              DV_NODE_ENCODE_SPLIT_LITE - DV_ROLLOUT_LITE == RolloutFlags::LITE_COUNT,
               "the variant ids leave each family its index range");
 
-// name of variant `id`; *by_default = reachable without an environment switch (DRP_NO_* / drp_probe_begin("prop+work"))
+// name of variant `id`; *by_default = reachable without an environment switch (DRP_NO_* / drp_probe_begin("prop+work")) or an
+// engine chosen by hand (the lite names)
 inline void dv_name(int id, char* buf, size_t n, bool* by_default) {
     bool dflt = true;
     static const char* const cache_names[3] = {"", ",cache", ",cache+rows"};
-    if (id >= DV_PROP && id < DV_PROP3) {
+    if (id >= DV_PROP_LITE && id < DV_PROP3_LITE) {
+        const PropFlags f = PropFlags::from_lite_index(id - DV_PROP_LITE);
+        snprintf(buf, n, "km_prop<%s%s%s,lite>", f.last ? "last" : "mid", f.pair ? ",pair" : "", f.work ? ",work" : "");
+        dflt = false;
+    } else if (id >= DV_PROP3_LITE && id < DV_ROLLOUT_LITE) {
+        const Prop3Flags f = Prop3Flags::from_lite_index(id - DV_PROP3_LITE);
+        snprintf(buf, n, "km_prop3<plain%s%s%s,lite>", f.pair ? ",pair" : "", cache_names[f.cache], f.work ? ",work" : "");
+        dflt = false;
+    } else if (id >= DV_ROLLOUT_LITE && id < DV_NODE_ENCODE_SPLIT_LITE) {
+        const RolloutFlags f = RolloutFlags::from_lite_index(id - DV_ROLLOUT_LITE);
+        snprintf(buf, n, "km_rollout<%s%s%s,lite>", f.pair ? "pair" : "tile32", cache_names[f.cache], f.work ? ",work" : "");
+        dflt = false;
+    } else if (id >= DV_PROP && id < DV_PROP3) {
         const PropFlags f = PropFlags::from_index(id - DV_PROP);
         snprintf(buf, n, "km_prop<%s%s%s%s>", f.last ? "last" : "mid", f.tape ? ",tape" : "", f.pair ? ",pair" : "", f.work ? ",work" : "");
         dflt = !f.work;
@@ -128,6 +162,8 @@ inline void dv_name(int id, char* buf, size_t n, bool* by_default) {
         case DV_FPS_MEM: s = "k_fps"; break;
         case DV_DT_CV5: s = "k_dt_cv5"; break;
         case DV_DT_EXACT: s = "k_edt"; break;
+        case DV_NODE_ENCODE_SPLIT_LITE: s = "km_node_encode_split<lite>"; dflt = false; break;
+        case DV_GRAPH_Q4_ENCODE_LITE: s = "graph:km_graph_q4_encode<lite> (+ particle encoder)"; dflt = false; break;
         case DV_TRAIN_BARRIER_RETRY: s = "train:barrier gave up, step re-run with one workgroup per group"; dflt = false; break;   // a shared / masked device
         default: break;
         }
@@ -396,13 +432,14 @@ struct GraphPlan {
     int chunks = 1;                 // workgroups (CELLS: of 16 quarter waves) per sample
     long grid = 0;                  // of the lists' launch (Q4_ENCODE: its graph part)
     int gy = 0; float inv_hb = 0.0f, halo = 0.0f;   // CELLS: y bands, their inverse height, the first sweep's halo
+    bool lite = false;              // Q4_ENCODE: the encoder's part on the reduced products
     int variant() const {
         switch (kind) {
         case CELLS: return DV_GRAPH_CELLS;
         case STRIPS128: return DV_GRAPH_STRIPS;
         case STRIPS256: return DV_GRAPH_STRIPS256;
         case Q4: return DV_GRAPH_Q4;
-        case Q4_ENCODE: return DV_GRAPH_Q4_ENCODE;
+        case Q4_ENCODE: return lite ? DV_GRAPH_Q4_ENCODE_LITE : DV_GRAPH_Q4_ENCODE;
         case REV: return DV_GRAPH_REV;
         default: return DV_GRAPH_PLAIN;
         }
@@ -413,6 +450,8 @@ struct GraphPlan {
 inline GraphPlan plan_graph(const DispatchPolicy& p, int n_cu, int engine, int B, int N, bool padded, bool has_actions, bool wants_rev,
                             bool no_encoder_launch) {
     GraphPlan g;
+    g.lite = engine == ENGINE_LITE;
+    engine = engine_for_plan(engine);
     if (wants_rev && N <= GRAPH_THREADS_ && p.graph_rev) {
         g.kind = GraphPlan::REV;
         g.grid = spread_grid(B);
@@ -468,8 +507,8 @@ struct StepShape {
     DegStat deg;
 };
 struct StepPlan {
-    int engine = ENGINE_FUSED, N = 1;
-    bool tape = false, work = false;
+    int engine = ENGINE_FUSED, N = 1;   // ENGINE_LITE arrives here as ENGINE_FUSED with `lite` set
+    bool tape = false, work = false, lite = false;
     GraphPlan graph;
     bool fused = false;             // the relation encoder is recomputed inside the propagation kernels (no edge-encode launch)
     bool split_encoders = false;    // the split-fp16 encoders (split and fused engines)
@@ -484,27 +523,29 @@ struct StepPlan {
     void mark(unsigned char* hit) const {
         if (graph.kind != GraphPlan::NONE) hit[graph.variant()] = 1;
         if (engine == ENGINE_VALU) { hit[DV_VALU_STEP] = 1; hit[agg.lds ? DV_AGGREGATE_LDS : DV_AGGREGATE] = 1; return; }
-        if (node_encode) hit[fused ? DV_NODE_ENCODE_SPLIT : DV_NODE_ENCODE] = 1;
+        if (node_encode) hit[fused ? (lite ? DV_NODE_ENCODE_SPLIT_LITE : DV_NODE_ENCODE_SPLIT) : DV_NODE_ENCODE] = 1;
         if (!fused) {
             hit[split_encoders ? DV_EDGE_ENCODE_SPLIT : DV_EDGE_ENCODE] = 1;
             hit[tape_mfma ? DV_AGGREGATE_TAPE : agg.lds ? DV_AGGREGATE_LDS : DV_AGGREGATE] = 1;
             hit[DV_UPDATE] = 1;
         } else if (prop3) {
-            for (int q = 0; q < blocks.n; ++q) hit[DV_PROP3 + prop3_flags(blocks.block(q)).index()] = 1;
+            for (int q = 0; q < blocks.n; ++q) hit[prop3_flags(blocks.block(q)).variant()] = 1;
         } else {
-            hit[DV_PROP + PropFlags{false, tape, pair, work}.index()] = 1;
-            hit[DV_PROP + PropFlags{true, tape, pair, work}.index()] = 1;
+            hit[prop_flags(false).variant()] = 1;
+            hit[prop_flags(true).variant()] = 1;
         }
     }
-    Prop3Flags prop3_flags(const Block& b) const { return Prop3Flags{tape, b.pair, b.cache, work}; }
+    PropFlags prop_flags(bool last) const { return PropFlags{last, tape, pair, work, lite}; }
+    Prop3Flags prop3_flags(const Block& b) const { return Prop3Flags{tape, b.pair, b.cache, work, lite}; }
 };
 inline StepPlan plan_step(const DispatchPolicy& p, int n_cu, const StepShape& s) {
     StepPlan k;
     const int B = s.B, N = s.N;
-    k.engine = s.engine; k.N = N; k.tape = s.tape; k.work = s.work;
-    k.fused = s.engine == ENGINE_FUSED;
-    k.split_encoders = k.fused || s.engine == ENGINE_SPLIT;
-    k.tape_mfma = s.tape && s.engine == ENGINE_MFMA;
+    k.engine = engine_for_plan(s.engine); k.N = N; k.tape = s.tape; k.work = s.work;
+    k.lite = s.engine == ENGINE_LITE && !s.tape;         // the tape is written with the full products, whatever is selected
+    k.fused = k.engine == ENGINE_FUSED;
+    k.split_encoders = k.fused || k.engine == ENGINE_SPLIT;
+    k.tape_mfma = s.tape && k.engine == ENGINE_MFMA;
     k.agg = plan_aggregate(p, n_cu, B, N);
     // chip-filling batches on the fused engine: the three propagation steps are one launch (km_prop3: a workgroup owns whole
     // samples and barriers locally between steps), and the particle encoder is its first phase unless switched off;
@@ -512,8 +553,8 @@ inline StepPlan plan_step(const DispatchPolicy& p, int n_cu, const StepShape& s)
     k.spw = (B + n_cu - 1) / n_cu;
     k.prop3 = k.fused && p.prop3 && detail::whole_samples(p, n_cu, B, N) && detail::tiles32((long)k.spw * N) >= p.prop3_min_tiles;
     k.phase_e = k.prop3 && p.prop3e;
-    if (s.build_graph) k.graph = plan_graph(p, n_cu, s.engine, B, N, s.padded, s.has_actions, s.wants_rev, k.phase_e);
-    k.node_encode = s.engine != ENGINE_VALU && !k.phase_e && k.graph.kind != GraphPlan::Q4_ENCODE;
+    if (s.build_graph) k.graph = plan_graph(p, n_cu, k.lite ? ENGINE_LITE : k.engine, B, N, s.padded, s.has_actions, s.wants_rev, k.phase_e);
+    k.node_encode = k.engine != ENGINE_VALU && !k.phase_e && k.graph.kind != GraphPlan::Q4_ENCODE;
     if (k.prop3) {
         long unit = 1;
         bool ok = true;
@@ -540,17 +581,19 @@ struct RolloutPlan {
     bool one_launch = false;
     int spw = 1;                    // samples per workgroup of the first block
     Blocks blocks;
-    bool work = false;
-    RolloutFlags flags(const Block& b) const { return RolloutFlags{b.pair, b.cache, work}; }
+    bool work = false, lite = false;
+    RolloutFlags flags(const Block& b) const { return RolloutFlags{b.pair, b.cache, work, lite}; }
     void mark(unsigned char* hit) const {
         if (!one_launch) return;
         hit[DV_GRAPH_IN_ROLLOUT] = 1;
-        for (int q = 0; q < blocks.n; ++q) hit[DV_ROLLOUT + flags(blocks.block(q)).index()] = 1;
+        for (int q = 0; q < blocks.n; ++q) hit[flags(blocks.block(q)).variant()] = 1;
     }
 };
 inline RolloutPlan plan_rollout(const DispatchPolicy& p, int n_cu, int engine, int B, int N, int nb, bool work, const DegStat& deg) {
     RolloutPlan r;
     r.work = work;
+    r.lite = engine == ENGINE_LITE;
+    engine = engine_for_plan(engine);
     r.blocks = cut_blocks(p, n_cu, B, N, false, nb, true, deg);
     if (engine != ENGINE_FUSED) { r.blocks.cache = false; r.blocks.cache_bytes = 0; r.blocks.chunk = B; r.blocks.n = 1; }
     r.spw = (int)((std::min((long)B, r.blocks.chunk) + n_cu - 1) / n_cu);

@@ -202,20 +202,33 @@ struct FragB {
     f16x8 hi[4], lo[4];      // per 16-deep k-step
 };
 
+// TERMS.  The helpers of the chain take NT, the number of fp16 terms an operand is carried in: 2 (the default: hi + lo, three
+// products per k-step) or 1 (the `lite` engine, include/drp.h: hi alone, ONE product W_hi x_hi -- the residual's v_fma_mix and
+// the lo conversions are not issued, the lo weights not read from LDS (the fill copies the whole packed blob); relative error 2^-10 from x_hi, 2^-11 from W_hi).  The node
+// layers' helpers (*_split6 further down) take it the same way: 3 bf16 terms and six products, or 2 terms and three products.
+// The kernels carry one flag, LITE, and derive both counts from it.
+__host__ __device__ constexpr int chain_terms(bool lite) { return lite ? 1 : 2; }
+__host__ __device__ constexpr int node_terms(bool lite) { return lite ? 2 : 3; }
+
 // two values -> their fp16 hi pair (round toward zero) and the fp16 pair of the exact residuals
+template <int NT = 2>
 __device__ __forceinline__ void split_pair(float x0, float x1, f16x8& hi, f16x8& lo, int q) {
     const fp16x2_t h = __builtin_amdgcn_cvt_pkrtz(x0, x1);
-    // residuals x - hi in one v_fma_mix_f32 each (the fp16 half is read in place; written as asm because
-    // the compiler folds the multiplication by -1 into a convert + subtract)
-    float r0, r1;
-    asm("v_fma_mix_f32 %0, %2, -1.0, %3 op_sel_hi:[1,0,0]\n\tv_fma_mix_f32 %1, %2, -1.0, %4 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-        : "=&v"(r0), "=&v"(r1) : "v"(h), "v"(x0), "v"(x1));
-    const fp16x2_t l = __builtin_amdgcn_cvt_pkrtz(r0, r1);
-    hi[2 * q] = (_Float16)h[0]; hi[2 * q + 1] = (_Float16)h[1];
-    lo[2 * q] = (_Float16)l[0]; lo[2 * q + 1] = (_Float16)l[1];
+    if constexpr (NT > 1) {
+        // residuals x - hi in one v_fma_mix_f32 each (the fp16 half is read in place; written as asm because
+        // the compiler folds the multiplication by -1 into a convert + subtract)
+        float r0, r1;
+        asm("v_fma_mix_f32 %0, %2, -1.0, %3 op_sel_hi:[1,0,0]\n\tv_fma_mix_f32 %1, %2, -1.0, %4 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
+            : "=&v"(r0), "=&v"(r1) : "v"(h), "v"(x0), "v"(x1));
+        const fp16x2_t l = __builtin_amdgcn_cvt_pkrtz(r0, r1);
+        hi[2 * q] = (_Float16)h[0]; hi[2 * q + 1] = (_Float16)h[1];
+        lo[2 * q] = (_Float16)l[0]; lo[2 * q + 1] = (_Float16)l[1];
+    } else {
+        hi[2 * q] = (_Float16)h[0]; hi[2 * q + 1] = (_Float16)h[1];
+    }
 }
 
-template <bool RELU>
+template <bool RELU, int NT = 2>
 __device__ __forceinline__ void split_frag(const Frag& in, FragB& o) {
 #pragma unroll
     for (int s = 0; s < 4; ++s)
@@ -223,7 +236,7 @@ __device__ __forceinline__ void split_frag(const Frag& in, FragB& o) {
         for (int q = 0; q < 4; ++q) {
             float x0 = in.v[s >> 1][8 * (s & 1) + 2 * q], x1 = in.v[s >> 1][8 * (s & 1) + 2 * q + 1];
             if (RELU) { x0 = relu1(x0); x1 = relu1(x1); }
-            split_pair(x0, x1, o.hi[s], o.lo[s], q);
+            split_pair<NT>(x0, x1, o.hi[s], o.lo[s], q);
         }
 }
 
@@ -233,16 +246,20 @@ struct WOp {
     f16x8 hi, lo;
 };
 
+template <int NT = 2>
 __device__ __forceinline__ WOp wop_load(const f16x8* __restrict__ wp, int s, int ob, int lane) {
     WOp w;
     w.hi = wp[((0 * 2 + ob) * 4 + s) * 64 + lane];
-    w.lo = wp[((1 * 2 + ob) * 4 + s) * 64 + lane];
+    if constexpr (NT > 1) w.lo = wp[((1 * 2 + ob) * 4 + s) * 64 + lane];
     return w;
 }
 
+template <int NT = 2>
 __device__ __forceinline__ void mfma_group(const WOp& w, const FragB& b, Frag& acc, int s, int ob) {
-    acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w.lo, b.hi[s], acc.v[ob], 0, 0, 0);
-    acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w.hi, b.lo[s], acc.v[ob], 0, 0, 0);
+    if constexpr (NT > 1) {
+        acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w.lo, b.hi[s], acc.v[ob], 0, 0, 0);
+        acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w.hi, b.lo[s], acc.v[ob], 0, 0, 0);
+    }
     acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w.hi, b.hi[s], acc.v[ob], 0, 0, 0);
 }
 
@@ -252,50 +269,56 @@ __device__ __forceinline__ void mfma_group(const WOp& w, const FragB& b, Frag& a
 // output was being split) and `next` receives group 0 of the following layer.
 // Group order: k-steps 0,1 for both output blocks (they need only the first half of the
 // previous layer's split), then k-steps 2,3 of block 0, then of block 1.
+template <int NT = 2>
 __device__ __forceinline__ void mfma_layer64_split(const f16x8* __restrict__ wp, const FragB& b, Frag& acc, int lane,
                                                    const WOp& first, const f16x8* __restrict__ wp_next, WOp& next) {
-    WOp w1 = wop_load(wp, 0, 1, lane);
-    mfma_group(first, b, acc, 0, 0);
-    WOp w2 = wop_load(wp, 1, 0, lane);
-    mfma_group(w1, b, acc, 0, 1);
-    w1 = wop_load(wp, 1, 1, lane);
-    mfma_group(w2, b, acc, 1, 0);
-    w2 = wop_load(wp, 2, 0, lane);
-    mfma_group(w1, b, acc, 1, 1);
-    w1 = wop_load(wp, 3, 0, lane);
-    mfma_group(w2, b, acc, 2, 0);
-    w2 = wop_load(wp, 2, 1, lane);
-    mfma_group(w1, b, acc, 3, 0);
-    w1 = wop_load(wp, 3, 1, lane);
-    mfma_group(w2, b, acc, 2, 1);
-    if (wp_next != nullptr) next = wop_load(wp_next, 0, 0, lane);
-    mfma_group(w1, b, acc, 3, 1);
+    WOp w1 = wop_load<NT>(wp, 0, 1, lane);
+    mfma_group<NT>(first, b, acc, 0, 0);
+    WOp w2 = wop_load<NT>(wp, 1, 0, lane);
+    mfma_group<NT>(w1, b, acc, 0, 1);
+    w1 = wop_load<NT>(wp, 1, 1, lane);
+    mfma_group<NT>(w2, b, acc, 1, 0);
+    w2 = wop_load<NT>(wp, 2, 0, lane);
+    mfma_group<NT>(w1, b, acc, 1, 1);
+    w1 = wop_load<NT>(wp, 3, 0, lane);
+    mfma_group<NT>(w2, b, acc, 2, 0);
+    w2 = wop_load<NT>(wp, 2, 1, lane);
+    mfma_group<NT>(w1, b, acc, 3, 0);
+    w1 = wop_load<NT>(wp, 3, 1, lane);
+    mfma_group<NT>(w2, b, acc, 2, 1);
+    if (wp_next != nullptr) next = wop_load<NT>(wp_next, 0, 0, lane);
+    mfma_group<NT>(w1, b, acc, 3, 1);
 }
 
+template <int NT = 2>
 __device__ __forceinline__ void mfma_layer64_split(const f16x8* __restrict__ wp, const FragB& b, Frag& acc, int lane) {
-    WOp first = wop_load(wp, 0, 0, lane), next;
-    mfma_layer64_split(wp, b, acc, lane, first, nullptr, next);
+    WOp first = wop_load<NT>(wp, 0, 0, lane), next;
+    mfma_layer64_split<NT>(wp, b, acc, lane, first, nullptr, next);
 }
 
 // first layer: one k-step over [a_r, a_s, dx, dy, dz, d, 1, 0] (lanes of half 1 supply zeros)
+template <int NT = 2>
 __device__ __forceinline__ void mfma_layer8_split(const f16x8* __restrict__ wp, const float (&x)[8], int h, Frag& acc, int lane) {
     f16x8 bhi, blo;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const float v0 = (h == 0) ? x[2 * q] : 0.0f, v1 = (h == 0) ? x[2 * q + 1] : 0.0f;
-        split_pair(v0, v1, bhi, blo, q);
+        split_pair<NT>(v0, v1, bhi, blo, q);
     }
 #pragma unroll
     for (int ob = 0; ob < 2; ++ob) {
         const f16x8 a_hi = wp[(0 * 2 + ob) * 64 + lane];
-        const f16x8 a_lo = wp[(1 * 2 + ob) * 64 + lane];
-        acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_lo, bhi, acc.v[ob], 0, 0, 0);
-        acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, blo, acc.v[ob], 0, 0, 0);
+        if constexpr (NT > 1) {
+            const f16x8 a_lo = wp[(1 * 2 + ob) * 64 + lane];
+            acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_lo, bhi, acc.v[ob], 0, 0, 0);
+            acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, blo, acc.v[ob], 0, 0, 0);
+        }
         acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, bhi, acc.v[ob], 0, 0, 0);
     }
 }
 
 // the relation-encoder chain of one tile: inputs -> c_edge fragment
+template <int NT = 2>
 __device__ __forceinline__ void edge_chain_split(const f16x8* __restrict__ wsp /*LDS, S_* offsets*/,
                                                  const float* __restrict__ rows /*2^k b2, 2^k b4, b_rp, wd_rp*/,
                                                  const float (&x)[8], float d, int h, int lane, float sc, float inv,
@@ -303,18 +326,18 @@ __device__ __forceinline__ void edge_chain_split(const f16x8* __restrict__ wsp /
     Frag a, c;
     FragB fb;
     frag_zero(a);
-    mfma_layer8_split(wsp + S_RE0, x, h, a, lane);
-    split_frag<true>(a, fb);
+    mfma_layer8_split<NT>(wsp + S_RE0, x, h, a, lane);
+    split_frag<true, NT>(a, fb);
     frag_from_row(rows + 0, h, c);
-    mfma_layer64_split(wsp + S_RE2, fb, c, lane);
-    split_frag<true>(c, fb);
+    mfma_layer64_split<NT>(wsp + S_RE2, fb, c, lane);
+    split_frag<true, NT>(c, fb);
     frag_from_row(rows + 64, h, a);
-    mfma_layer64_split(wsp + S_RE4, fb, a, lane);
-    split_frag<true>(a, fb);
+    mfma_layer64_split<NT>(wsp + S_RE4, fb, a, lane);
+    split_frag<true, NT>(a, fb);
     frag_bias_dens(rows + 128, rows + 192, d, h, out);
 #pragma unroll
     for (int r = 0; r < 16; ++r) { out.v[0][r] *= sc; out.v[1][r] *= sc; }
-    mfma_layer64_split(wsp + S_RPE, fb, out, lane);
+    mfma_layer64_split<NT>(wsp + S_RPE, fb, out, lane);
 #pragma unroll
     for (int r = 0; r < 16; ++r) { out.v[0][r] *= inv; out.v[1][r] *= inv; }
 }
@@ -431,6 +454,9 @@ struct FragB6 {
     bf16x8 p[3][4];          // [part][k-step]
 };
 
+// NT = 3: the three-term split and its six products; NT = 2 (the `lite` engine): two terms, the three products w0 p0, w0 p1,
+// w1 p0 -- the third terms are neither formed nor loaded (TERMS, above)
+template <int NT = 3>
 __device__ __forceinline__ void split_frag6(const Frag& in, FragB6& o) {
 #pragma unroll
     for (int s = 0; s < 4; ++s)
@@ -442,10 +468,11 @@ __device__ __forceinline__ void split_frag6(const Frag& in, FragB6& o) {
             const __bf16 mid = (__bf16)r1;
             o.p[0][s][jj] = hi;
             o.p[1][s][jj] = mid;
-            o.p[2][s][jj] = (__bf16)(r1 - (float)mid);
+            if constexpr (NT > 2) o.p[2][s][jj] = (__bf16)(r1 - (float)mid);
         }
 }
 
+template <int NT = 3>
 __device__ __forceinline__ void mfma_layer64_split6(const bf16x8* __restrict__ wp, const FragB6& b, Frag& acc, int lane) {
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
@@ -453,10 +480,12 @@ __device__ __forceinline__ void mfma_layer64_split6(const bf16x8* __restrict__ w
         for (int ob = 0; ob < 2; ++ob) {
             const bf16x8 w0 = wp[((0 * 2 + ob) * 4 + s) * 64 + lane];
             const bf16x8 w1 = wp[((1 * 2 + ob) * 4 + s) * 64 + lane];
-            const bf16x8 w2 = wp[((2 * 2 + ob) * 4 + s) * 64 + lane];
-            acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2, b.p[0][s], acc.v[ob], 0, 0, 0);
-            acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, b.p[2][s], acc.v[ob], 0, 0, 0);
-            acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, b.p[1][s], acc.v[ob], 0, 0, 0);
+            if constexpr (NT > 2) {
+                const bf16x8 w2 = wp[((2 * 2 + ob) * 4 + s) * 64 + lane];
+                acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2, b.p[0][s], acc.v[ob], 0, 0, 0);
+                acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, b.p[2][s], acc.v[ob], 0, 0, 0);
+                acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, b.p[1][s], acc.v[ob], 0, 0, 0);
+            }
             acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, b.p[0][s], acc.v[ob], 0, 0, 0);
             acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, b.p[1][s], acc.v[ob], 0, 0, 0);
             acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, b.p[0][s], acc.v[ob], 0, 0, 0);
@@ -465,6 +494,7 @@ __device__ __forceinline__ void mfma_layer64_split6(const bf16x8* __restrict__ w
 }
 
 // first layer of the particle encoder on the 6-term split (km_node_encode_split, and km_prop3's phase E)
+template <int NT = 3>
 __device__ __forceinline__ void mfma_layer8_split6(const bf16x8* __restrict__ wp, const float (&x)[8], int h, Frag& acc, int lane) {
     bf16x8 b0, b1, b2;
 #pragma unroll
@@ -475,16 +505,18 @@ __device__ __forceinline__ void mfma_layer8_split6(const bf16x8* __restrict__ wp
         const __bf16 mid = (__bf16)r1;
         b0[jj] = hi;
         b1[jj] = mid;
-        b2[jj] = (__bf16)(r1 - (float)mid);
+        if constexpr (NT > 2) b2[jj] = (__bf16)(r1 - (float)mid);
     }
 #pragma unroll
     for (int ob = 0; ob < 2; ++ob) {
         const bf16x8 w0 = wp[(0 * 2 + ob) * 64 + lane];
         const bf16x8 w1 = wp[(1 * 2 + ob) * 64 + lane];
-        const bf16x8 w2 = wp[(2 * 2 + ob) * 64 + lane];
-        acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2, b0, acc.v[ob], 0, 0, 0);
-        acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, b2, acc.v[ob], 0, 0, 0);
-        acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, b1, acc.v[ob], 0, 0, 0);
+        if constexpr (NT > 2) {
+            const bf16x8 w2 = wp[(2 * 2 + ob) * 64 + lane];
+            acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2, b0, acc.v[ob], 0, 0, 0);
+            acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, b2, acc.v[ob], 0, 0, 0);
+            acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, b1, acc.v[ob], 0, 0, 0);
+        }
         acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, b0, acc.v[ob], 0, 0, 0);
         acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, b1, acc.v[ob], 0, 0, 0);
         acc.v[ob] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, b0, acc.v[ob], 0, 0, 0);
@@ -611,10 +643,19 @@ __device__ __forceinline__ void work_clock_end(const WorkClock& w, unsigned long
         atomicAdd(prop_work_shard(work) + PROP_WORK_CLK_TICKS, (unsigned long long)(__builtin_amdgcn_s_memrealtime() - w.r0));
     }
 }
-#define PROP_MFMA_CHAIN 78
-#define PROP_MFMA_NODE 144
-#define PROP_MFMA_NODE_LAST 96
-#define PROP_MFMA_ENC 204
+// The matrix instructions those units are made of, by the term counts (TERMS) of the instantiation that counted them
+// (drp_probe_work weighs the units with the engine the counted launches ran on).  Products per k-step and output block: the chain's 3 or 1, the node layers' 6 or 3
+__host__ __device__ constexpr unsigned prop_mfma_chain(bool lite) { return 26u * (lite ? 1u : 3u); }          // 2 + 3 x 8 groups
+__host__ __device__ constexpr unsigned prop_mfma_node(bool lite) { return 24u * (lite ? 3u : 6u); }           // W_agg, W_r, W_s
+__host__ __device__ constexpr unsigned prop_mfma_node_last(bool lite) { return 16u * (lite ? 3u : 6u); }      // W_agg, predictor layer 0
+__host__ __device__ constexpr unsigned prop_mfma_enc(bool lite) { return 34u * (lite ? 3u : 6u); }            // 2 + 4 x 8
+#define PROP_MFMA_CHAIN prop_mfma_chain(false)
+#define PROP_MFMA_NODE prop_mfma_node(false)
+#define PROP_MFMA_NODE_LAST prop_mfma_node_last(false)
+#define PROP_MFMA_ENC prop_mfma_enc(false)
+static_assert(PROP_MFMA_CHAIN == 78 && PROP_MFMA_NODE == 144 && PROP_MFMA_NODE_LAST == 96 && PROP_MFMA_ENC == 204 &&
+              prop_mfma_chain(true) == 26 && prop_mfma_node(true) == 72 && prop_mfma_node_last(true) == 48 && prop_mfma_enc(true) == 102,
+              "the matrix instructions of a slot iteration, a tile's node part and an encoder tile");
 struct PropLds {
     const f16x8* wsp;         // edge chain, S_* offsets
     const bf16x8* w_agg;      // W_agg
@@ -676,7 +717,8 @@ __device__ __forceinline__ float dpp_ror8(float x) {
 // Pays where the chain's LATENCY is the bound -- one tile per wave -- and the buffer (2.5 KB per receiver) stays in the
 // last-level cache; at 300 particles x 1024 samples it is 700 MB per rollout step and recomputing costs the same.
 #define EC_UNITS 512             // float4 per (tile, slot iteration): 8 per lane
-template <bool LAST, bool TAPE, bool PAIR, bool CARRY, int EC, bool WORK, bool ONE /* a wave has at most ONE tile per step: no queue, no loop */, class First, class Decode, class RowOf>
+template <bool LAST, bool TAPE, bool PAIR, bool CARRY, int EC, bool WORK, bool ONE /* a wave has at most ONE tile per step: no queue, no loop */,
+          bool LITE /* reduced products (TERMS) */, class First, class Decode, class RowOf>
 __device__ __forceinline__ void prop_tiles(const PropArgs& A, const PropLds& L, First first_of /* this wave's first tile */,
                                            Decode decode /* the others: draws from the workgroup's queue */, RowOf row_of, int lane,
                                            HeadCarry& hc
@@ -700,6 +742,8 @@ __device__ __forceinline__ void prop_tiles(const PropArgs& A, const PropLds& L, 
     const int jr = PAIR ? ((j & 7) | ((j >> 4) << 3)) : j;      // the tile's receiver this column works for
     const int par = PAIR ? ((j >> 3) & 1) : 0;                  // and which of an iteration's slots it runs
     constexpr int KS = PAIR ? 2 : 1;
+    constexpr int CT = chain_terms(LITE), NT6 = node_terms(LITE);
+    static_assert(!(LITE && TAPE), "the tape is written with the full products");
     // attr_mod == dens_mod (n_batch or B) for every caller; s_mod is one of the two as well
     const float inv_mod = 1.0f / (float)attr_mod;
     const bool s_by_sample = s_mod != attr_mod;            // states of a running rollout: one block per sample
@@ -961,17 +1005,17 @@ __device__ __forceinline__ void prop_tiles(const PropArgs& A, const PropLds& L, 
             Frag a, c;
             FragB fb;
             frag_zero(a);
-            mfma_layer8_split(wsp + S_RE0, x, h, a, lane);
-            WOp w0 = wop_load(wsp + S_RE2, 0, 0, lane), wn;
-            split_frag<true>(a, fb);
+            mfma_layer8_split<CT>(wsp + S_RE0, x, h, a, lane);
+            WOp w0 = wop_load<CT>(wsp + S_RE2, 0, 0, lane), wn;
+            split_frag<true, CT>(a, fb);
             frag_from_row(rows + 0, h, c);
-            mfma_layer64_split(wsp + S_RE2, fb, c, lane, w0, wsp + S_RE4, wn);
-            split_frag<true>(c, fb);
+            mfma_layer64_split<CT>(wsp + S_RE2, fb, c, lane, w0, wsp + S_RE4, wn);
+            split_frag<true, CT>(c, fb);
             frag_from_row(rows + 64, h, a);
-            mfma_layer64_split(wsp + S_RE4, fb, a, lane, wn, wsp + S_RPE, w0);
-            split_frag<true>(a, fb);
+            mfma_layer64_split<CT>(wsp + S_RE4, fb, a, lane, wn, wsp + S_RPE, w0);
+            split_frag<true, CT>(a, fb);
             if (EC == 0) c = bpr; else frag_zero(c);
-            mfma_layer64_split(wsp + S_RPE, fb, c, lane, w0, nullptr, wn);
+            mfma_layer64_split<CT>(wsp + S_RPE, fb, c, lane, w0, nullptr, wn);
             if (EC == 1) {
                 // the chain's raw output, for the other two propagation steps; and this step's term the way they form it
                 float4* dst = ec + (size_t)it * EC_UNITS;
@@ -1063,30 +1107,30 @@ __device__ __forceinline__ void prop_tiles(const PropArgs& A, const PropLds& L, 
         }
         if (TAPE && agg_out != nullptr && live) frag_to_row(agg_out + row * 64, h, acc);
         FragB6 f6;
-        split_frag6(acc, f6);
-        mfma_layer64_split6(L.w_agg, f6, e, lane);
+        split_frag6<NT6>(acc, f6);
+        mfma_layer64_split6<NT6>(L.w_agg, f6, e, lane);
         frag_relu(e);
         if (live) frag_to_row(eff + row * 64, h, e);
         const bool keep_rows = ROWS && !LAST && first_tile && hc.rows_ok;        // wave-uniform
         if (keep_rows) hc.re = e;
-        split_frag6(e, f6);
+        split_frag6<NT6>(e, f6);
         __builtin_amdgcn_sched_barrier(0);
         if (more || (CARRY && !LAST)) tf_next = tile_first(hd_next, nbw2_next);          // the head has landed by now
         __builtin_amdgcn_sched_barrier(0);
         if (!LAST) {
             Frag p;
             frag_zero(p);
-            mfma_layer64_split6(L.w_x, f6, p, lane);
+            mfma_layer64_split6<NT6>(L.w_x, f6, p, lane);
             if (live) frag_to_row(proj_next + row * 128, h, p);
             if (keep_rows) hc.rpr = p;
             frag_zero(p);
-            mfma_layer64_split6(L.w_x + 1536, f6, p, lane);
+            mfma_layer64_split6<NT6>(L.w_x + 1536, f6, p, lane);
             if (live) frag_to_row(proj_next + row * 128 + 64, h, p);
             if (keep_rows) hc.rps = p;
         } else {
             Frag hp;
             frag_from_row(L.rows_pr, h, hp);
-            mfma_layer64_split6(L.w_x, f6, hp, lane);
+            mfma_layer64_split6<NT6>(L.w_x, f6, hp, lane);
             frag_relu(hp);
             float out[3];
 #pragma unroll
@@ -1138,7 +1182,8 @@ __device__ __forceinline__ void prop_tiles(const PropArgs& A, const PropLds& L, 
 #define PROP_STAMPS_ARG
 #endif
 
-template <bool LAST, bool TAPE, bool PAIR /* tiles of 16 receivers x two slots (prop_tiles); with `spread` only */, bool WORK>
+template <bool LAST, bool TAPE, bool PAIR /* tiles of 16 receivers x two slots (prop_tiles); with `spread` only */, bool WORK,
+          bool LITE = false /* reduced products (TERMS) */>
 __global__ void __launch_bounds__(64 * PROP_WAVES)
 km_prop(const uint16_t* __restrict__ sw, const uint16_t* __restrict__ sw6, const float* __restrict__ mw,
         const float* __restrict__ s_cur, int s_mod, size_t s_stride,
@@ -1223,7 +1268,7 @@ km_prop(const uint16_t* __restrict__ sw, const uint16_t* __restrict__ sw6, const
         return r;
     };
     HeadCarry hc_none;
-    prop_tiles<LAST, TAPE, PAIR, false, 0, WORK, false>(A, L, [&]() { return decode(wave); }, decode, row_of, lane, hc_none PROP_STAMPS_ARG);
+    prop_tiles<LAST, TAPE, PAIR, false, 0, WORK, false, LITE>(A, L, [&]() { return decode(wave); }, decode, row_of, lane, hc_none PROP_STAMPS_ARG);
     if constexpr (WORK) work_clock_end(wclk, work);
 #ifdef PROP_STAMPS
     st_sum[6] = st_k1 - st_k0;                               // entry -> weights in LDS
@@ -1298,6 +1343,7 @@ __device__ __forceinline__ void prop3_fill_resident(const Prop3Lds& P, const uin
 // on; on exit every wave has passed its last tile (no barrier after it).
 template <bool TAPE, bool PAIR, bool CARRY, bool ECACHE, bool WORK, bool ONE /* the workgroup has no more tiles than waves (the host's promise) */,
           bool ENC_PRE = false /* km_rollout<pair>: the caller has filled the encoder's matrices and reset the tile counter, one barrier ago */,
+          bool LITE = false /* reduced products (TERMS) */,
           class Aux = int /* ENC_PRE: aux(w, nw) -- work for the waves without an encoder tile (the neighbour lists), w-th of nw */>
 __device__ __forceinline__ void prop3_step(const Prop3Lds& P, const uint16_t* __restrict__ sw, const uint16_t* __restrict__ sw6,
                                            const float* __restrict__ mw,
@@ -1354,6 +1400,7 @@ __device__ __forceinline__ void prop3_step(const Prop3Lds& P, const uint16_t* __
     constexpr int tile_rows = PAIR ? 16 : 32;
     const int wg_tiles = PAIR ? (wg_rows + 15) >> 4 : enc_tiles;
     const float inv_N = 1.0f / (float)N;
+    constexpr int NT6 = node_terms(LITE);
     if (phase_e) {
         // ---- phase E: the particle encoder over this workgroup's rows (km_node_encode_split's arithmetic per row)
         const bf16x8* wpe2 = reinterpret_cast<const bf16x8*>(wsp_f);
@@ -1376,22 +1423,22 @@ __device__ __forceinline__ void prop3_step(const Prop3Lds& P, const uint16_t* __
             Frag a, pe, c;
             FragB6 f6;
             frag_zero(a);
-            mfma_layer8_split6(wpe0, x, h, a, lane);
+            mfma_layer8_split6<NT6>(wpe0, x, h, a, lane);
             frag_relu(a);
-            split_frag6(a, f6);
+            split_frag6<NT6>(a, f6);
             frag_from_row(rows_e + 0, h, pe);
-            mfma_layer64_split6(wpe2, f6, pe, lane);
+            mfma_layer64_split6<NT6>(wpe2, f6, pe, lane);
             frag_relu(pe);
             if (live) frag_to_row(eff + row * 64, h, pe);          // TAPE: slot 0 of the effect history
-            split_frag6(pe, f6);
+            split_frag6<NT6>(pe, f6);
             frag_bias_dens(rows_e + 64, rows_e + 128, d, h, c);
-            mfma_layer64_split6(wpe2 + 1536, f6, c, lane);
+            mfma_layer64_split6<NT6>(wpe2 + 1536, f6, c, lane);
             if (live) frag_to_row(c_node + row * 64, h, c);
             frag_zero(c);
-            mfma_layer64_split6(wrs, f6, c, lane);
+            mfma_layer64_split6<NT6>(wrs, f6, c, lane);
             if (live) frag_to_row(proj_a + row * 128, h, c);
             frag_zero(c);
-            mfma_layer64_split6(wrs + 1536, f6, c, lane);
+            mfma_layer64_split6<NT6>(wrs + 1536, f6, c, lane);
             if (live) frag_to_row(proj_a + row * 128 + 64, h, c);
             int qn = 0;
             if (lane == 0) qn = __hip_atomic_fetch_add(tile_ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1549,12 +1596,12 @@ __device__ __forceinline__ void prop3_step(const Prop3Lds& P, const uint16_t* __
             A.agg_out = agg_hist ? agg_hist + (size_t)(p_) * bn64 : nullptr; \
         } \
         if (ECACHE && (p_) == 0) { \
-            prop_tiles<false, TAPE, PAIR, CARRY, 1, WORK, ONE>(A, L, first_of, decode, row_of, lane, hc PROP_STAMPS_ARG); \
+            prop_tiles<false, TAPE, PAIR, CARRY, 1, WORK, ONE, LITE>(A, L, first_of, decode, row_of, lane, hc PROP_STAMPS_ARG); \
         } else if ((p_) + 1 < DRP_PSTEP) { \
-            prop_tiles<false, TAPE, PAIR, CARRY, ECACHE ? 2 : 0, WORK, ONE>(A, L, first_of, decode, row_of, lane, hc PROP_STAMPS_ARG); \
+            prop_tiles<false, TAPE, PAIR, CARRY, ECACHE ? 2 : 0, WORK, ONE, LITE>(A, L, first_of, decode, row_of, lane, hc PROP_STAMPS_ARG); \
         } else { \
             L.w_x = reinterpret_cast<const bf16x8*>(w6_f) + 3 * 1536; \
-            prop_tiles<true, TAPE, PAIR, CARRY, ECACHE ? 2 : 0, WORK, ONE>(A, L, first_of, decode, row_of, lane, hc PROP_STAMPS_ARG); \
+            prop_tiles<true, TAPE, PAIR, CARRY, ECACHE ? 2 : 0, WORK, ONE, LITE>(A, L, first_of, decode, row_of, lane, hc PROP_STAMPS_ARG); \
         } \
         PROP3_STEP_STAMP(p_); \
         ROLL_STAMP(7);                               /* wave 0's tiles of a propagation step */ \
@@ -1579,7 +1626,8 @@ __device__ __forceinline__ void prop3_step(const Prop3Lds& P, const uint16_t* __
 #endif
 }
 
-template <bool TAPE, bool PAIR, bool ECACHE, bool WORK, bool ONE /* no more tiles than waves per workgroup (the host's promise; cached kernels) */>
+template <bool TAPE, bool PAIR, bool ECACHE, bool WORK, bool ONE /* no more tiles than waves per workgroup (the host's promise; cached kernels) */,
+          bool LITE = false /* reduced products (TERMS) */>
 __global__ void __launch_bounds__(64 * PROP_WAVES)
 km_prop3(const uint16_t* __restrict__ sw, const uint16_t* __restrict__ sw6, const float* __restrict__ mw,
          const float* __restrict__ s_cur, int s_mod, size_t s_stride,
@@ -1604,7 +1652,7 @@ km_prop3(const uint16_t* __restrict__ sw, const uint16_t* __restrict__ sw6, cons
     const Prop3Lds P = prop3_lds(lds);
     prop3_fill_resident(P, sw, sw6, mw);
     prop3_step<TAPE, PAIR, PAIR && !TAPE /* the tape's kernel has no register to spare for the carried head; the big kernel's
-                                            allocation is not to move (with it: 256 VGPRs) */, ECACHE, WORK, ONE>(P, sw, sw6, mw, s_cur, s_mod, s_stride, attr, attr_mod, dens, dens_mod, nbr_idx, nbr_cnt, proj_a, proj_b, c_node,
+                                            allocation is not to move (with it: 256 VGPRs) */, ECACHE, WORK, ONE, false, LITE>(P, sw, sw6, mw, s_cur, s_mod, s_stride, attr, attr_mod, dens, dens_mod, nbr_idx, nbr_cnt, proj_a, proj_b, c_node,
                      eff, N, B, spw, s_delta, s_out, out_stride, cself, cself_ok, mask_hist, agg_hist, re_scale, re_inv, order_rows,
                      (int)threadIdx.x, ECACHE ? ecache + (size_t)blockIdx.x * ec_stride : nullptr, work PROP_STAMPS_ARG, 0, TAPE ? hist_rows : 0);
     if constexpr (WORK) work_clock_end(wclk, work);
@@ -1628,11 +1676,13 @@ km_prop3(const uint16_t* __restrict__ sw, const uint16_t* __restrict__ sw6, cons
 // Same contract as km_node_encode (k_mlp_mfma.h); outputs go straight from the accumulator
 // layout to their rows (no LDS transposition tiles: LDS holds the 126 KB of packed weights).
 // (the body of workgroup `blk` of `nblk`, 64 * MFMA_WAVES threads: km_node_encode_split below, and km_graph_q4_encode of k_rollout.h)
+template <bool LITE = false>
 __device__ __forceinline__ void
 node_encode_split_block(const uint16_t* __restrict__ sw6, const float* __restrict__ mw,
                         const float* __restrict__ s_delta, const float* __restrict__ attr, int attr_mod,
                         const float* __restrict__ dens, int dens_mod, int N, int B,
                         float* __restrict__ eff, float* __restrict__ c_node, float* __restrict__ proj, int blk, int nblk, float* lds) {
+    constexpr int NT6 = node_terms(LITE);
     float* w6_f = lds;                         // PE2 | PPE | RPR | RPS (4 x 1536 units) | PE0 (384)
     float* rows = w6_f + (4 * 1536 + 384) * 4; // b_pe2, b_pp, wd_pp
     lds_fill(w6_f, reinterpret_cast<const float*>(sw6) + S6_PE2 * 4, 2 * 1536 * 4);
@@ -1657,31 +1707,32 @@ node_encode_split_block(const uint16_t* __restrict__ sw6, const float* __restric
         Frag a, pe, c;
         FragB6 f6;
         frag_zero(a);
-        mfma_layer8_split6(w6 + 4 * 1536, x, h, a, lane);
+        mfma_layer8_split6<NT6>(w6 + 4 * 1536, x, h, a, lane);
         frag_relu(a);
-        split_frag6(a, f6);
+        split_frag6<NT6>(a, f6);
         frag_from_row(rows + 0, h, pe);
-        mfma_layer64_split6(w6, f6, pe, lane);
+        mfma_layer64_split6<NT6>(w6, f6, pe, lane);
         frag_relu(pe);
         if (live) frag_to_row(eff + row * 64, h, pe);
-        split_frag6(pe, f6);
+        split_frag6<NT6>(pe, f6);
         frag_bias_dens(rows + 64, rows + 128, d, h, c);
-        mfma_layer64_split6(w6 + 1536, f6, c, lane);
+        mfma_layer64_split6<NT6>(w6 + 1536, f6, c, lane);
         if (live) frag_to_row(c_node + row * 64, h, c);
         frag_zero(c);
-        mfma_layer64_split6(w6 + 2 * 1536, f6, c, lane);
+        mfma_layer64_split6<NT6>(w6 + 2 * 1536, f6, c, lane);
         if (live) frag_to_row(proj + row * 128, h, c);
         frag_zero(c);
-        mfma_layer64_split6(w6 + 3 * 1536, f6, c, lane);
+        mfma_layer64_split6<NT6>(w6 + 3 * 1536, f6, c, lane);
         if (live) frag_to_row(proj + row * 128 + 64, h, c);
     }
 }
-DRP_GLOBAL void __launch_bounds__(64 * MFMA_WAVES)
+template <bool LITE = false /* reduced products (TERMS) */>
+__global__ void __launch_bounds__(64 * MFMA_WAVES)
 km_node_encode_split(const uint16_t* __restrict__ sw6, const float* __restrict__ mw,
                      const float* __restrict__ s_delta, const float* __restrict__ attr, int attr_mod,
                      const float* __restrict__ dens, int dens_mod, int N, int B,
                      float* __restrict__ eff, float* __restrict__ c_node, float* __restrict__ proj) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    node_encode_split_block(sw6, mw, s_delta, attr, attr_mod, dens, dens_mod, N, B, eff, c_node, proj, (int)blockIdx.x, (int)gridDim.x, lds);
+    node_encode_split_block<LITE>(sw6, mw, s_delta, attr, attr_mod, dens, dens_mod, N, B, eff, c_node, proj, (int)blockIdx.x, (int)gridDim.x, lds);
 }
 #define KM_NODE_SPLIT_LDS ((size_t)((4 * 1536 + 384) * 4 + 192) * sizeof(float))

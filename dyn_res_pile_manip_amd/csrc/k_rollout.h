@@ -48,7 +48,8 @@ struct RolloutArgs {
     DrpCam cam;
 };
 
-template <bool PAIR, bool ECACHE, bool WORK, bool ONE /* no more tiles than waves per workgroup: rows handed from step to step in registers */>
+template <bool PAIR, bool ECACHE, bool WORK, bool ONE /* no more tiles than waves per workgroup: rows handed from step to step in registers */,
+          bool LITE = false /* reduced products (TERMS, k_mlp_split.h) */>
 __global__ void __launch_bounds__(64 * PROP_WAVES)
 km_rollout(const RolloutArgs* __restrict__ args) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -132,7 +133,7 @@ km_rollout(const RolloutArgs* __restrict__ args) {
                     graph_receiver(p4x + m * N, N, i, thr, self_first, nbr_idx + row * DRP_K, nbr_cnt + row);
                 }
             };
-            prop3_step<false, PAIR, true, ECACHE, WORK, ONE, true>(P, a->sw, a->sw6, a->mw, s_prev, prev_mod, prev_stride, a->attr, nbat, a->dens, nbat, nbr_idx, nbr_cnt,
+            prop3_step<false, PAIR, true, ECACHE, WORK, ONE, true, LITE>(P, a->sw, a->sw6, a->mw, s_prev, prev_mod, prev_stride, a->attr, nbat, a->dens, nbat, nbr_idx, nbr_cnt,
                               a->proj_a, a->proj_b, a->c_node, a->eff, N, B, spw, s_delta, states + (size_t)t * N * 3, hstride,
                               a->cself, a->cself_ok, nullptr, nullptr, a->re_scale, a->re_inv, a->order_rows, tid,
                               ECACHE ? a->ecache + (size_t)blockIdx.x * a->ec_stride : nullptr, a->work PROP_STAMPS_ARG, lists);
@@ -166,7 +167,7 @@ km_rollout(const RolloutArgs* __restrict__ args) {
         }
         __syncthreads();                             // the lists are written, the positions no longer needed
         ROLL_STAMP(2);                               // neighbour lists
-        prop3_step<false, PAIR, true, ECACHE, WORK, ONE>(P, a->sw, a->sw6, a->mw, s_prev, prev_mod, prev_stride, a->attr, nbat, a->dens, nbat, nbr_idx, nbr_cnt,
+        prop3_step<false, PAIR, true, ECACHE, WORK, ONE, false, LITE>(P, a->sw, a->sw6, a->mw, s_prev, prev_mod, prev_stride, a->attr, nbat, a->dens, nbat, nbr_idx, nbr_cnt,
                           a->proj_a, a->proj_b, a->c_node, a->eff, N, B, spw, s_delta, states + (size_t)t * N * 3, hstride,
                           a->cself, a->cself_ok, nullptr, nullptr, a->re_scale, a->re_inv, a->order_rows, tid,
                           ECACHE ? a->ecache + (size_t)blockIdx.x * a->ec_stride : nullptr, a->work PROP_STAMPS_ARG);
@@ -185,7 +186,8 @@ km_rollout(const RolloutArgs* __restrict__ args) {
 // effects, node constants, first projections) read nothing of one another -- one launch, the first `n_graph` workgroups build the
 // lists, the others run the encoder's tiles on their first 64 * MFMA_WAVES threads (the other waves leave at once: a
 // workgroup's barrier counts the waves that are still there).  Either body is the kernel's it comes from: the same bits.
-DRP_GLOBAL void __launch_bounds__(GRAPH_Q4_THREADS)
+template <bool LITE = false /* reduced products in the encoder's part (TERMS, k_mlp_split.h) */>
+__global__ void __launch_bounds__(GRAPH_Q4_THREADS)
 km_graph_q4_encode(const float* __restrict__ s_prev, int prev_mod, size_t prev_stride, const float* __restrict__ s_delta, int N, int B,
                    int16_t* __restrict__ nbr_idx, uint8_t* __restrict__ nbr_cnt, DrpCam cam, float thr, int chunks, int self_first,
                    int n_graph, const uint16_t* __restrict__ sw6, const float* __restrict__ mw, const float* __restrict__ attr,
@@ -199,7 +201,7 @@ km_graph_q4_encode(const float* __restrict__ s_prev, int prev_mod, size_t prev_s
         return;
     }
     if (threadIdx.x >= 64 * MFMA_WAVES) return;
-    node_encode_split_block(sw6, mw, s_delta, attr, attr_mod, dens, dens_mod, N, B, eff, c_node, proj, (int)blockIdx.x - n_graph,
+    node_encode_split_block<LITE>(sw6, mw, s_delta, attr, attr_mod, dens, dens_mod, N, B, eff, c_node, proj, (int)blockIdx.x - n_graph,
                             (int)gridDim.x - n_graph, lds);
 }
 #define KM_GRAPH_Q4_ENCODE_LDS(N) (GRAPH_Q4_LDS(N) > KM_NODE_SPLIT_LDS ? GRAPH_Q4_LDS(N) : KM_NODE_SPLIT_LDS)

@@ -64,7 +64,7 @@ class Engine(object):
         self.device = int(device)
         self.H = 0
         self.auto_engine = bool(auto_engine)
-        self.engine_id = L.ENGINE_FUSED              # drp_create's choice
+        self.engine_id = self.chosen_engine = L.ENGINE_FUSED     # drp_create's choice
         if engine is not None:
             self.set_engine(engine)
 
@@ -90,18 +90,25 @@ class Engine(object):
         try:
             return self._ck(call())
         except L.DrpRangeError as e:
-            if not self.auto_engine or self.engine_id not in (L.ENGINE_FUSED, L.ENGINE_SPLIT):
+            if not self.auto_engine or self.engine_id not in (L.ENGINE_FUSED, L.ENGINE_SPLIT, L.ENGINE_LITE):
                 raise
             import warnings
             warnings.warn('the split-fp16 engine refused the call (%s): continuing on the fp32 matrix engine' % e,
                           RuntimeWarning, stacklevel=3)
-            self._engine_before_auto = self.engine_id   # restored by the next load_weights: the refusal belongs to these weights / inputs
-            self.set_engine(L.ENGINE_MFMA)
-            self._auto_switched = True
+            self._give_way(L.ENGINE_MFMA)               # undone by the next load_weights: the refusal belongs to these weights / inputs
             return self._ck(call())
 
     # ---- constants ----------------------------------------------------------------
     def set_engine(self, engine):
+        """engine: an id or a name of _lib.ENGINES.  'lite' (reduced products on the fused engine's kernels, forward calls only:
+        include/drp.h) is never chosen for the caller; load_weights(probe=..., max_disp_rel=...) is its guard."""
+        if isinstance(engine, str):
+            engine = L.ENGINES[engine]
+        self._give_way(engine)
+        self.chosen_engine = int(engine)              # the caller's choice: written here and nowhere else
+
+    def _give_way(self, engine):
+        """run on `engine` without touching the caller's choice (a range refusal, a probe finding): load_weights returns to it"""
         self._ck(self.lib.drp_set_engine(self.h, int(engine)))
         self.engine_id = int(engine)
 
@@ -118,37 +125,39 @@ class Engine(object):
         measured on it (`accuracy_probe`) and kept for `range_info()['probe']`.  max_disp_rel: the largest error, as a share
         of the largest displacement, the caller accepts -- beyond it the fused / split engine gives way to the fp32 matrix
         engine exactly as after DRP_ERANGE (one RuntimeWarning; the next load_weights restores the choice), whatever
-        `auto_engine` says, and on the fp32 engines, which have nowhere to fall back to, DrpError is raised."""
+        `auto_engine` says, and on the fp32 engines, which have nowhere to fall back to, DrpError is raised.  The lite engine
+        gives way to the fused one first (one RuntimeWarning), which is then probed and held to the same threshold in turn;
+        `range_info()['probe']` names the engine whose figures it holds."""
         blob = _f32(blob).ravel()
         if max_disp_rel is not None and probe is None:
             raise ValueError('max_disp_rel needs a probe (probe=True or a batch)')
         self._weights_owner = None                    # whoever believed its weights were resident no longer is right
         self._ck(self.lib.drp_load_weights(self.h, _fp(blob), blob.size, float(adj_thresh)))
-        if ((self.auto_engine or getattr(self, '_probe_switched', False)) and self.engine_id == L.ENGINE_MFMA
-                and getattr(self, '_auto_switched', False)):
+        if self.engine_id != self.chosen_engine:
             # the fallback was for the OTHER weights: these get the chance of the engine the caller had chosen again
-            self.set_engine(getattr(self, '_engine_before_auto', L.ENGINE_FUSED))
-            self._auto_switched = False
-            self._probe_switched = False
+            self._give_way(self.chosen_engine)
         self._probe = None
         if probe is None:
             return
         batch = self.probe_batch() if probe is True else tuple(probe)
-        res = self.accuracy_probe(*batch)             # (a refusal of the range check is handled as every ranged call's)
-        names = dict((v, k) for k, v in L.ENGINES.items())
-        self._probe = dict(res, engine=names[self.engine_id])
-        if max_disp_rel is None or res['disp_rel'] <= max_disp_rel:
-            return
-        msg = ('the %s engine is %.3e of the largest displacement away from the float64 evaluation on these weights '
-               '(particle %d), beyond the %.3e asked for' % (names[self.engine_id], res['disp_rel'], res['worst'], max_disp_rel))
-        if self.engine_id not in (L.ENGINE_FUSED, L.ENGINE_SPLIT):
-            raise L.DrpError(msg + ': the fp32 engines have nowhere to fall back to')
         import warnings
-        warnings.warn(msg + ': continuing on the fp32 matrix engine', RuntimeWarning, stacklevel=2)
-        self._engine_before_auto = self.engine_id     # restored by the next load_weights: the finding belongs to these weights
-        self.set_engine(L.ENGINE_MFMA)
-        self._auto_switched = True
-        self._probe_switched = True
+        names = dict((v, k) for k, v in L.ENGINES.items())
+        while True:
+            res = self.accuracy_probe(*batch)         # (a refusal of the range check is handled as every ranged call's)
+            self._probe = dict(res, engine=names[self.engine_id])
+            if max_disp_rel is None or res['disp_rel'] <= max_disp_rel:
+                return
+            msg = ('the %s engine is %.3e of the largest displacement away from the float64 evaluation on these weights '
+                   '(particle %d), beyond the %.3e asked for' % (names[self.engine_id], res['disp_rel'], res['worst'], max_disp_rel))
+            if self.engine_id not in (L.ENGINE_FUSED, L.ENGINE_SPLIT, L.ENGINE_LITE):
+                raise L.DrpError(msg + ': the fp32 engines have nowhere to fall back to')
+            # lite gives way to the full products of the same kernels, and those, like the split engine, to fp32
+            nxt = L.ENGINE_FUSED if self.engine_id == L.ENGINE_LITE else L.ENGINE_MFMA
+            warnings.warn(msg + ': continuing on the %s engine' % ('fused' if nxt == L.ENGINE_FUSED else 'fp32 matrix'),
+                          RuntimeWarning, stacklevel=2)
+            self._give_way(nxt)                       # undone by the next load_weights: the finding belongs to these weights
+            if nxt == L.ENGINE_MFMA:
+                return
 
     def probe_batch(self):
         """The fixed batch of load_weights(probe=True): 8 samples x 64 particles, one pile and eight pushes of the synthetic

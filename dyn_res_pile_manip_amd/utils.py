@@ -22,6 +22,11 @@ def get_engine(device=0):
 
 
 def set_engine(engine):
+    """engine: an Engine -- it becomes the process's context -- or an id / a name of _lib.ENGINES ('lite' among them): the MLP
+    kernels the process's context computes with from here on."""
+    if isinstance(engine, (str, int)):
+        get_engine().set_engine(engine)
+        return
     set_default_engine(engine)
 
 

@@ -41,7 +41,7 @@ enum {
     DRP_ENOMEM = -4,
     DRP_ECOMM = -5,     /* RCCL error */
     DRP_ERANGE = -6     /* weights or inputs outside the range the split-fp16 relation encoder of
-                           DRP_ENGINE_FUSED / _SPLIT is scaled for (its hidden activations travel as two fp16
+                           DRP_ENGINE_FUSED / _LITE / _SPLIT is scaled for (its hidden activations travel as two fp16
                            pieces times an exact power of two chosen from the weights): nothing was computed;
                            DRP_ENGINE_MFMA / _VALU have no such limit */
 };
@@ -51,9 +51,25 @@ enum {
     DRP_ENGINE_VALU = 0,  /* fp32 VALU reference kernels */
     DRP_ENGINE_MFMA = 1,  /* fp32 MFMA (v_mfma_f32_32x32x2_f32) kernels */
     DRP_ENGINE_SPLIT = 2, /* as MFMA, relation encoder on split-fp16 (two terms, 3 MFMAs per product) MFMA, fp32 accumulate */
-    DRP_ENGINE_FUSED = 3  /* as SPLIT, encoder recomputed inside each aggregate: the edge-constant
+    DRP_ENGINE_FUSED = 3, /* as SPLIT, encoder recomputed inside each aggregate: the edge-constant
                              buffer is never materialised */
+    DRP_ENGINE_LITE = 4   /* opt-in: the fused engine's kernels with fewer product terms (see below); never chosen for the caller */
 };
+/* DRP_ENGINE_LITE -- reduced-precision forward arithmetic, selected explicitly (drp_set_engine) and by nothing else.
+ *   Relation-encoder chain: ONE product per k-step, W_hi x_hi, where DRP_ENGINE_FUSED forms W_lo x_hi + W_hi x_lo + W_hi x_hi.
+ *     The operands are the ones the fused engine already forms: weights rounded to nearest-even fp16 (relative 2^-11),
+ *     activations rounded toward zero to fp16 (v_cvt_pkrtz_f16_f32, relative 2^-10; absolute 2^-24 in the shifted scale below
+ *     fp16's normal range), the same power-of-two range shift, fp32 accumulation.  26 MFMAs per slot iteration instead of 78.
+ *   Node layers (particle encoder, W_agg, the W_r | W_s projections, predictor layer 0): the two-term bf16 split with the three
+ *     products w0 p0, w0 p1, w1 p0 (dropped terms <= 2^-16 relative); the third terms are neither read from LDS nor formed.
+ *     72 / 48 MFMAs per tile instead of 144 / 96, 102 per encoder tile instead of 204.
+ *   Everything else is the fused engine's, bit for bit: neighbour lists, gen_s_delta, reward, MPPI, the self-edge constant (full
+ *     precision), the edge-chain cache, the dispatch (the same plans; the variant names carry `lite`), and the range check:
+ *     DRP_ERANGE applies exactly as to DRP_ENGINE_FUSED.
+ *   Forward only (drp_step, drp_forward, drp_rollout, drp_mpc_*).  With it selected, drp_gd_* and drp_train_step write their
+ *     tape exactly as with DRP_ENGINE_FUSED selected (the full products; the fp32 matrix engine where the range refuses):
+ *     gradients and trained weights do not depend on the choice.
+ *   What it costs on given weights is what drp_accuracy_probe(engine = DRP_ENGINE_LITE) measures. */
 
 typedef struct drp_ctx drp_ctx;
 
@@ -279,7 +295,8 @@ int drp_obs2ptcl(drp_ctx* ctx, const float* depth_raw, int h, int w, float globa
  * One iteration of planners.py:682-764: rollout -> final-step reward -> loss = -sum(reward)
  * -> d loss / d pushes by reverse mode (through every step of the horizon) -> Adam(lr) step
  * -> clip box.  actions [B,H,4] with B = traj_num * n_batch rows (row = traj * n_batch + batch).
- * The forward pass writes its tape on the fused engine; when drp_set_engine has selected an fp32 engine, or the weights /
+ * The forward pass writes its tape on the fused engine (also when DRP_ENGINE_LITE is selected: the tape never uses the reduced
+ * products); when drp_set_engine has selected an fp32 engine, or the weights /
  * inputs are outside the split-fp16 relation encoder's range, on the fp32 matrix engine instead (slower, same gradients
  * to fp32 rounding): drp_gd_* and drp_train_step never return DRP_ERANGE -- env/flex_env.py:973-976 accepts no other
  * planner than this one. */
@@ -416,7 +433,7 @@ int drp_ptcl_dataset_time(drp_ctx* ctx, float* ms_out);
 /* ---- measurement / debugging ----------------------------------------------------- */
 /* HIP-event timing of one kernel class on the context's stream.  name: "graph",
  * "node_encode", "edge_encode", "project", "aggregate", "update", "predict", "reward",
- * "mppi", "prop" (the fused propagation-step kernel of DRP_ENGINE_FUSED).  drp_probe_read returns total ms and launches since drp_probe_begin. */
+ * "mppi", "prop" (the fused propagation-step kernel of DRP_ENGINE_FUSED / _LITE).  drp_probe_read returns total ms and launches since drp_probe_begin. */
 int drp_probe_begin(drp_ctx* ctx, const char* kernel_class);
 int drp_probe_read(drp_ctx* ctx, double* total_ms, long* launches);
 /* What the propagation kernels (km_prop, km_prop3, km_rollout) EXECUTED since drp_probe_begin(ctx, "prop+work") -- the "prop"
@@ -424,7 +441,8 @@ int drp_probe_read(drp_ctx* ctx, double* total_ms, long* launches);
  * timed region runs under the plain "prop" probe and the counters over an iteration of their own): out[0] slot iterations that ran the relation
  * encoder's chain (78 16-bit MFMAs each), [1] slot iterations served by the edge-chain cache (none), [2] / [3] tiles of
  * propagation steps that are not / are the last (144 / 96), [4] particle-encoder tiles inside the launch (204),
- * [5] the 16-bit MFMAs (32x32x16, 32 768 FLOP each) those add up to; [6] shader-clock cycles (s_memtime) and [7] 100 MHz
+ * [5] the 16-bit MFMAs (32x32x16, 32 768 FLOP each) those add up to, by the engine the counted launches ran on: on
+ * DRP_ENGINE_LITE the units weigh 26, 72 / 48 and 102 (count one engine per drp_probe_begin: DRP_ESTATE otherwise); [6] shader-clock cycles (s_memtime) and [7] 100 MHz
  * ticks (s_memrealtime) between entry and exit of the counted launches, summed over their workgroups: 100 * [6] / [7] is the
  * shader clock in MHz the kernel ran at.  bench.py's roofline numerator and its sclk_mhz_under_load. */
 int drp_probe_work(drp_ctx* ctx, unsigned long long out[8]);
@@ -483,7 +501,7 @@ int drp_f64_tap(drp_ctx* ctx, const char* name, double* out, size_t n);
 /* the workspace cap of the *_f64 calls in bytes (0: the default, 256 MB); one sample is the smallest chunk.  Tests lower it
  * to force chunking. */
 int drp_debug_set_f64_cap(drp_ctx* ctx, size_t bytes);
-/* drp_step's path on `engine` (DRP_ENGINE_*, any of the four) and drp_step_f64 on the same inputs and the same lists, reduced
+/* drp_step's path on `engine` (DRP_ENGINE_*, any of the five) and drp_step_f64 on the same inputs and the same lists, reduced
  * on the device: out[0] = max |s_pred_engine - s_pred_f64| (the fp32 value widened, the difference in double),
  * out[1] = max |s_pred_f64 - s_cur|, out[2] = out[0] / max(out[1], 1e-12) (the error as a share of the largest displacement,
  * the quantity the 1e-4 parity tolerance is stated in), out[3] = index b * N + n of the worst particle (ties: the lowest).

@@ -12,7 +12,7 @@ eng.load_weights(weights.blob_from_state_dict(w), 0.08)
 for case in ('n64', 'n8'):
     a, s, sd, d = [g[case + '/' + k] for k in ('attr', 's_cur', 's_delta', 'dens')]
     ref = g[case + '/particle_effect_2'].reshape(a.shape[0], a.shape[1], 64)
-    for name in ('valu', 'mfma', 'split', 'fused'):
+    for name in ('valu', 'mfma', 'split', 'fused', 'lite'):
         eng.set_engine(_lib.ENGINES[name])
         eng.step(a, s, sd, d)
         eff = eng.debug_fetch('effect', ref.shape)
@@ -27,7 +27,7 @@ for label, wts, cases in legs:
     eng.load_weights(weights.blob_from_state_dict(wts), 0.08)
     for src, p in cases:
         a, s, sd, d = [src[p + k] for k in ('attr', 's_cur', 's_delta', 'dens')]
-        for name in ('valu', 'mfma', 'split', 'fused'):
+        for name in ('valu', 'mfma', 'split', 'fused', 'lite'):
             r = eng.accuracy_probe(a, s, sd, d, engine=_lib.ENGINES[name])
             print('%-7s %-14s %-5s against float64: max |err| %.3e, largest displacement %.3e, ratio %.3e (particle %d)'
                   % (label, p, name, r['abs'], r['disp'], r['disp_rel'], r['worst']))

@@ -42,26 +42,30 @@ for case in range(n_cases):
     dens = (dens * rng.uniform(0.3, 2.0, dens.shape)).astype(np.float32)
     acts = syn.sample_pushes(ns * nb, H, seed=case)
     outs = {}
-    for name in ('valu', 'mfma', 'fused'):
+    for name in ('valu', 'mfma', 'fused', 'lite'):
         eng.set_engine(_lib.ENGINES[name])
         outs[name], _ = eng.rollout(s0, attr, dens, acts)
         assert np.isfinite(outs[name]).all(), (case, name)
     prev = np.tile(s0, (ns, 1, 1))
     for t in range(H):
         disp = max(np.abs(outs['mfma'][:, t] - prev).max(), 1e-7)
-        for name in ('valu', 'fused'):
+        for name in ('valu', 'fused', 'lite'):
+            # lite: the opt-in reduced products (include/drp.h), held to 1e-2 of the displacement here -- its own accuracy is the
+            # probe's and tests/test_gpu_lite.py's business; this run looks for rows that break, not for rounding
+            tol = 1e-2 if name == 'lite' else 1e-4
             per_row = np.abs(outs[name][:, t] - outs['mfma'][:, t]).reshape(ns * nb, -1).max(1) / disp
             if t == 0:
                 e = per_row.max()
-                if e > worst:
+                if e > worst and name != 'lite':
                     worst, worst_at = e, (case, name, t, N, nb, ns, H, kind, scale, mode, float(disp))
-                assert e < 1e-4, (case, name, t, N, nb, ns, H, kind, scale, mode, e)
+                assert e < tol, (case, name, t, N, nb, ns, H, kind, scale, mode, e)
             else:
                 # later steps start from states that differ in the last bits; a receiver whose 10th and 11th
                 # nearest senders are almost equidistant may then pick the other one (rows of dense piles):
                 # most rows must still agree
-                flipped += int((per_row > 1e-4 * (t + 1)).sum())
-                rows_later += per_row.size
+                if name != 'lite':
+                    flipped += int((per_row > 1e-4 * (t + 1)).sum())
+                    rows_later += per_row.size
         prev = outs['mfma'][:, t]
     if N <= 100 and ns * nb <= 6:
         # teacher-forced one-step check against the numpy oracle
