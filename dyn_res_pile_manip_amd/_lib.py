@@ -166,6 +166,8 @@ SIGNATURES = {
     'drp_debug_set_f64_cap': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t]),
     'drp_accuracy_probe': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_float_p, c_float_p, c_float_p, c_float_p,
                                           ctypes.c_int, ctypes.c_int, c_double_p]),
+    'drp_gd_grad_f64': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.c_int, ctypes.c_int, c_float_p,
+                                       ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p]),
 }
 
 _lib = None

@@ -293,12 +293,13 @@ struct drp_ctx {
 
     // float64 one-step evaluation and the accuracy probe (k_prop_f64.h, capi_f64.h): weights, staging and workspaces of its own,
     // nothing shared with the sessions' state -- a *_f64 call or a probe ends no session
-    DevBuf f64_w;                   // the blob widened [W_TOTAL], then its nine 64x64 blocks in MFMA fragment order (KF_W_TOTAL doubles)
+    DevBuf f64_w;                   // the blob widened [W_TOTAL], then its nine 64x64 blocks in MFMA fragment order, then in the transposed order (KF_W_ALL doubles)
     bool f64_w_valid = false;       // drp_load_weights refreshes it; an optimiser step on the device clears it, the next *_f64 call rebuilds
     size_t f64_cap = (size_t)256 << 20;     // bytes of float64 workspace a call may hold: the batch is walked in sample chunks under it
     DevBuf f64_stage[F64_STAGE_BUFS];       // stand in for the step workspaces while a *_f64 call runs (capi_f64.h: F64Scope)
     DevBuf f64_pe, f64_eff, f64_agg, f64_re, f64_erel, f64_pred, f64_out, f64_red;
     int f64_lastB = 0, f64_lastN = 0, f64_chunks = 0;       // of the last *_f64 call (drp_f64_tap)
+    DevBuf gd64_ws, gd64_io;        // drp_gd_grad_f64 (capi_gd_f64.h): a chunk's tape and reverse pass; the batch's inputs and results
 
     // re-packing after an optimiser step on the device (k_train.h): gather maps of the plain packers, pinned copy of the blob
     DevBuf map_valu, map_mfma, map_mfma_bwd;

@@ -61,6 +61,29 @@ int f64_build_lists(drp_ctx* c, int B, int N) {
     return DRP_OK;
 }
 
+// The launches of one step over `rows` particles (whole samples of N): its intermediates into pe [rows,64], re [rows,10,64],
+// eff and agg [3][rows,64], erel [3][rows,10,64], pred [rows,3], the new positions into s_pred [rows,3].  TS: the type of the
+// positions and impulses, float (the one-step calls) or double (the rollout of capi_gd_f64.h, whose intermediates are its tape).
+extern "C++" template <typename TS>
+void f64_launch_step(drp_ctx* c, const double* w, const TS* s_cur, const TS* s_delta, const float* attr, const float* dens,
+                     const int16_t* idx, const uint8_t* cnt, int N, int rows, double* pe, double* re, double* eff, double* agg,
+                     double* erel, double* pred, double* s_pred) {
+    const int erows = rows * DRP_K;
+    const dim3 blk(64 * KF_WAVES);
+    const dim3 pgrid((rows + 16 * KF_WAVES - 1) / (16 * KF_WAVES)), egrid((erows + 16 * KF_WAVES - 1) / (16 * KF_WAVES));
+    const size_t p64 = (size_t)rows * 64, e64 = (size_t)erows * 64;      // a propagation step's slice of the effects / relation effects
+    hipStream_t st = c->stream;
+    hipLaunchKernelGGL((kf_particle_encode<TS>), pgrid, blk, 0, st, w, s_delta, attr, dens, N, rows, pe);
+    hipLaunchKernelGGL((kf_relation_encode<TS>), egrid, blk, 0, st, w, s_cur, attr, dens, idx, cnt, N, erows, re);
+    for (int p = 0; p < DRP_PSTEP; ++p) {
+        const double* eff_prev = p == 0 ? pe : eff + (size_t)(p - 1) * p64;
+        hipLaunchKernelGGL(kf_relation_prop, egrid, blk, 0, st, w, re, eff_prev, dens, idx, cnt, N, erows, erel + (size_t)p * e64);
+        hipLaunchKernelGGL(kf_particle_prop, pgrid, blk, 0, st, w, pe, erel + (size_t)p * e64, eff_prev, dens, cnt, N, rows,
+                           agg + (size_t)p * p64, eff + (size_t)p * p64);
+    }
+    hipLaunchKernelGGL((kf_predict<TS>), pgrid, blk, 0, st, w, eff + (size_t)(DRP_PSTEP - 1) * p64, s_cur, rows, pred, s_pred);
+}
+
 // model/gnn_dyn.py:147-198 in float64 on the staged inputs and lists -> c->f64_out [B,N,3]; launches only.
 // Samples are independent and a row's arithmetic does not know its tile: walking the batch in chunks changes no bit.
 int f64_forward_dev(drp_ctx* c, int B, int N) {
@@ -77,32 +100,20 @@ int f64_forward_dev(drp_ctx* c, int B, int N) {
     CHK(ensure(c, c->f64_pred, pn * 3 * sizeof(double)));
     CHK(ensure(c, c->f64_out, (size_t)B * N * 3 * sizeof(double)));
     const double* w = ptr<double>(c->f64_w);
-    const dim3 blk(64 * KF_WAVES);
-    hipStream_t st = c->stream;
     int chunks = 0;
     for (int b0 = 0; b0 < B; b0 += Bc, ++chunks) {
         const int bc = std::min(Bc, B - b0);
-        const int rows = bc * N, erows = rows * DRP_K;
+        const int rows = bc * N;
         const size_t ro = (size_t)b0 * N;
-        const dim3 pgrid((rows + 16 * KF_WAVES - 1) / (16 * KF_WAVES)), egrid((erows + 16 * KF_WAVES - 1) / (16 * KF_WAVES));
         const float* s_cur = ptr<float>(c->s_in) + ro * 3;
         const float* s_delta = ptr<float>(c->s_delta) + ro * 3;
         const float* attr = ptr<float>(c->attr) + ro;
         const float* dens = ptr<float>(c->dens) + b0;
         const int16_t* idx = ptr<int16_t>(c->nbr_idx) + ro * DRP_K;
         const uint8_t* cnt = ptr<uint8_t>(c->nbr_cnt) + ro;
-        const size_t p64 = (size_t)rows * 64, e64 = (size_t)erows * 64;      // a step's slice of the chunk's effects / relation effects
-        hipLaunchKernelGGL(kf_particle_encode, pgrid, blk, 0, st, w, s_delta, attr, dens, N, rows, ptr<double>(c->f64_pe));
-        hipLaunchKernelGGL(kf_relation_encode, egrid, blk, 0, st, w, s_cur, attr, dens, idx, cnt, N, erows, ptr<double>(c->f64_re));
-        for (int p = 0; p < DRP_PSTEP; ++p) {
-            const double* eff_prev = p == 0 ? ptr<double>(c->f64_pe) : ptr<double>(c->f64_eff) + (size_t)(p - 1) * p64;
-            hipLaunchKernelGGL(kf_relation_prop, egrid, blk, 0, st, w, ptr<double>(c->f64_re), eff_prev, dens, idx, cnt, N, erows,
-                               ptr<double>(c->f64_erel) + (size_t)p * e64);
-            hipLaunchKernelGGL(kf_particle_prop, pgrid, blk, 0, st, w, ptr<double>(c->f64_pe), ptr<double>(c->f64_erel) + (size_t)p * e64,
-                               eff_prev, dens, cnt, N, rows, ptr<double>(c->f64_agg) + (size_t)p * p64, ptr<double>(c->f64_eff) + (size_t)p * p64);
-        }
-        hipLaunchKernelGGL(kf_predict, pgrid, blk, 0, st, w, ptr<double>(c->f64_eff) + (size_t)(DRP_PSTEP - 1) * p64, s_cur, rows,
-                           ptr<double>(c->f64_pred), ptr<double>(c->f64_out) + ro * 3);
+        f64_launch_step<float>(c, w, s_cur, s_delta, attr, dens, idx, cnt, N, rows, ptr<double>(c->f64_pe), ptr<double>(c->f64_re),
+                               ptr<double>(c->f64_eff), ptr<double>(c->f64_agg), ptr<double>(c->f64_erel), ptr<double>(c->f64_pred),
+                               ptr<double>(c->f64_out) + ro * 3);
         HIPCHK(c, hipGetLastError());
     }
     c->f64_lastB = B; c->f64_lastN = N; c->f64_chunks = chunks;

@@ -1136,8 +1136,8 @@ void set_split_range(drp_ctx* c, const float* blob) {
 
 // the float64 copy of the weights (k_prop_f64.h) from the device's current fp32 blob: enqueued, not waited for
 int f64_refresh_weights(drp_ctx* c) {
-    CHK(ensure(c, c->f64_w, (size_t)KF_W_TOTAL * sizeof(double)));
-    hipLaunchKernelGGL(kf_widen_weights, dim3((KF_W_TOTAL + 255) / 256), dim3(256), 0, c->stream, ptr<float>(c->w_raw), ptr<double>(c->f64_w));
+    CHK(ensure(c, c->f64_w, (size_t)KF_W_ALL * sizeof(double)));
+    hipLaunchKernelGGL(kf_widen_weights, dim3((KF_W_ALL + 255) / 256), dim3(256), 0, c->stream, ptr<float>(c->w_raw), ptr<double>(c->f64_w));
     HIPCHK(c, hipGetLastError());
     c->f64_w_valid = true;
     return DRP_OK;

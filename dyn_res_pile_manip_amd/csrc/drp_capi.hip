@@ -46,6 +46,7 @@
 #include "k_rgr_bwd.h"
 #include "k_ptcl_dataset.h"
 #include "k_prop_f64.h"
+#include "k_gd_f64.h"
 #include "k_prop_inst.h"       // km_prop / km_prop3 / km_rollout: declared here, instantiated in inst_*.hip
 
 #include "dispatch.h"          // host-only: policy, variant flags, plan functions
@@ -64,6 +65,7 @@ extern "C" {
 #include "capi_rgr_train.h"
 #include "capi_ptcl_dataset.h"
 #include "capi_f64.h"
+#include "capi_gd_f64.h"
 #include "capi_debug.h"
 
 }  // extern "C"

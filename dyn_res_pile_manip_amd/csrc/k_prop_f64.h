@@ -22,6 +22,8 @@ typedef double kf_d4 __attribute__((ext_vector_type(4)));
 // the 64x64 blocks of the blob, kept a second time in B-fragment order: [block][k-step 16][column tile 4][lane 64]
 enum { KF_PE2 = 0, KF_RE2, KF_RE4, KF_PP_PE, KF_PP_AGG, KF_RP_E, KF_RP_R, KF_RP_S, KF_PR0, KF_BLOCKS };
 #define KF_W_TOTAL ((int)W_TOTAL + KF_BLOCKS * 4096)    // doubles: the blob widened, then the fragments
+// ... and the blocks a third time, in the B-fragment order of the transposed product dX = dY W (k_gd_f64.h): same layout, k = output
+#define KF_W_ALL (KF_W_TOTAL + KF_BLOCKS * 4096)
 // workspace per particle of a chunk, in bytes: particle_encode, 3 effects, 3 aggregates, prediction (64, 3 x 64, 3 x 64, 3 doubles)
 // and per relation slot the encoding and 3 effects (10 x 4 x 64 doubles)
 #define KF_BYTES_PER_PARTICLE ((size_t)(7 * 64 + 3 + DRP_K * 4 * 64) * sizeof(double))
@@ -44,15 +46,18 @@ __device__ __forceinline__ void kf_block_src(int blk, int& base, int& ld) {
 __global__ __launch_bounds__(256) void kf_widen_weights(const float* __restrict__ w, double* __restrict__ w64) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t < (int)W_TOTAL) { w64[t] = (double)w[t]; return; }
-    if (t >= KF_W_TOTAL) return;
-    const int q = t - (int)W_TOTAL, blk = q >> 12, r = q & 4095;
+    if (t >= KF_W_ALL) return;
+    const bool tr = t >= KF_W_TOTAL;
+    const int q = t - (tr ? KF_W_TOTAL : (int)W_TOTAL), blk = q >> 12, r = q & 4095;
     const int ks = r >> 8, jt = (r >> 6) & 3, lane = r & 63;
     int base, ld;
     kf_block_src(blk, base, ld);
-    w64[t] = (double)w[base + (jt * 16 + (lane & 15)) * ld + ks * 4 + (lane >> 4)];
+    w64[t] = tr ? (double)w[base + (ks * 4 + (lane >> 4)) * ld + jt * 16 + (lane & 15)]
+                : (double)w[base + (jt * 16 + (lane & 15)) * ld + ks * 4 + (lane >> 4)];
 }
 
 __device__ __forceinline__ const double* kf_frag(const double* w64, int blk) { return w64 + W_TOTAL + blk * 4096; }
+__device__ __forceinline__ const double* kf_frag_t(const double* w64, int blk) { return w64 + KF_W_TOTAL + blk * 4096; }
 __device__ __forceinline__ double kf_relu(double x) { return x > 0.0 ? x : 0.0; }
 
 // acc[jt] += X W^T for one 64x64 block: a_row is this lane's row of X (64 doubles), k ascending
@@ -72,8 +77,10 @@ __device__ __forceinline__ void kf_zero(kf_d4 acc[4]) {
     for (int jt = 0; jt < 4; ++jt) acc[jt] = kf_d4{0.0, 0.0, 0.0, 0.0};
 }
 
-// particle encoder on [s_delta, a, dens / 5000] (:174-175); rows = particles of the chunk, dens per sample
-__global__ __launch_bounds__(64 * KF_WAVES) void kf_particle_encode(const double* __restrict__ w, const float* __restrict__ s_delta,
+// particle encoder on [s_delta, a, dens / 5000] (:174-175); rows = particles of the chunk, dens per sample.  TS: the type the
+// impulses (below: the positions) come in -- float widened exactly, or double (a rollout that stays in double, k_gd_f64.h)
+template <typename TS>
+__global__ __launch_bounds__(64 * KF_WAVES) void kf_particle_encode(const double* __restrict__ w, const TS* __restrict__ s_delta,
                                                                     const float* __restrict__ attr, const float* __restrict__ dens,
                                                                     int N, int rows, double* __restrict__ pe) {
     __shared__ double X[KF_WAVES][16 * KF_LD];
@@ -106,7 +113,8 @@ __global__ __launch_bounds__(64 * KF_WAVES) void kf_particle_encode(const double
 
 // relation encoder on [a_r, a_s, s_r - s_s, dens / 5000] per list entry (:166-171,:179-180); rows = relation slots
 // (receiver-major, DRP_K per particle); a slot past the receiver's count is written as zeros
-__global__ __launch_bounds__(64 * KF_WAVES) void kf_relation_encode(const double* __restrict__ w, const float* __restrict__ s_cur,
+template <typename TS>
+__global__ __launch_bounds__(64 * KF_WAVES) void kf_relation_encode(const double* __restrict__ w, const TS* __restrict__ s_cur,
                                                                     const float* __restrict__ attr, const float* __restrict__ dens,
                                                                     const int16_t* __restrict__ idx, const uint8_t* __restrict__ cnt,
                                                                     int N, int rows, double* __restrict__ re) {
@@ -228,8 +236,9 @@ __global__ __launch_bounds__(64 * KF_WAVES) void kf_particle_prop(const double* 
 }
 
 // predictor (:196, :110) and + s_cur (:198)
+template <typename TS>
 __global__ __launch_bounds__(64 * KF_WAVES) void kf_predict(const double* __restrict__ w, const double* __restrict__ eff,
-                                                            const float* __restrict__ s_cur, int rows, double* __restrict__ pred,
+                                                            const TS* __restrict__ s_cur, int rows, double* __restrict__ pred,
                                                             double* __restrict__ s_pred) {
     __shared__ double X[KF_WAVES][16 * KF_LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;

@@ -119,7 +119,7 @@ class Engine(object):
         self._ck(self.lib.drp_device_info(self.h, name, 256, ctypes.byref(ncu), ctypes.byref(mem)))
         return {'name': name.value.decode(), 'n_cu': ncu.value, 'hbm_bytes': mem.value}
 
-    def load_weights(self, blob, adj_thresh=0.08, probe=None, max_disp_rel=None):
+    def load_weights(self, blob, adj_thresh=0.08, probe=None, max_disp_rel=None, max_grad_rel=None):
         """probe: None (nothing measured), True (the fixed batch of `probe_batch`; the camera must be set) or a batch
         (a_cur, s_cur, s_delta, dens): after loading, the selected engine's one-step error against the float64 evaluation is
         measured on it (`accuracy_probe`) and kept for `range_info()['probe']`.  max_disp_rel: the largest error, as a share
@@ -127,19 +127,49 @@ class Engine(object):
         engine exactly as after DRP_ERANGE (one RuntimeWarning; the next load_weights restores the choice), whatever
         `auto_engine` says, and on the fp32 engines, which have nowhere to fall back to, DrpError is raised.  The lite engine
         gives way to the fused one first (one RuntimeWarning), which is then probed and held to the same threshold in turn;
-        `range_info()['probe']` names the engine whose figures it holds."""
+        `range_info()['probe']` names the engine whose figures it holds.
+        max_grad_rel: the same guard for the quantity the gradient-descent planner consumes.  After the forward probe (if one
+        was asked for) `gradient_probe` runs on `probe_batch`'s pile under its eight pushes (nb = 1, B = 8, H = 1) with the
+        context's camera and goal -- both must be set: ValueError otherwise, the probe invents no goal -- and is kept as
+        `range_info()['grad_probe']`.  Beyond max_grad_rel on a split-fp16 tape the engine gives way to the fp32 matrix engine
+        (one RuntimeWarning, the next load_weights restores the choice), so the tape is fp32; that tape is probed in turn, and
+        beyond the threshold there too DrpError is raised.  The gradient probe ends a running planner session."""
         blob = _f32(blob).ravel()
         if max_disp_rel is not None and probe is None:
             raise ValueError('max_disp_rel needs a probe (probe=True or a batch)')
+        if max_grad_rel is not None and not (hasattr(self, '_cam') and getattr(self, '_have_goal', False)):
+            raise ValueError('max_grad_rel needs the camera and a goal (set_camera, set_goal / set_goal_image): the gradient '
+                             'probe differentiates the reward of the context\'s own goal')
         self._weights_owner = None                    # whoever believed its weights were resident no longer is right
         self._ck(self.lib.drp_load_weights(self.h, _fp(blob), blob.size, float(adj_thresh)))
         if self.engine_id != self.chosen_engine:
             # the fallback was for the OTHER weights: these get the chance of the engine the caller had chosen again
             self._give_way(self.chosen_engine)
-        self._probe = None
-        if probe is None:
-            return
-        batch = self.probe_batch() if probe is True else tuple(probe)
+        self._probe = self._grad_probe = None
+        if probe is not None:
+            self._forward_guard(self.probe_batch() if probe is True else tuple(probe), max_disp_rel)
+        if max_grad_rel is not None:
+            self._gradient_guard(max_grad_rel)
+
+    def _gradient_guard(self, max_grad_rel):
+        import warnings
+        from . import synthetic as syn
+        s0, dens, attr = syn.make_pile(64, 1, seed=0)
+        acts = syn.sample_pushes(8, 1, seed=0)
+        lo, hi = syn.action_limits()
+        while True:
+            res = self.gradient_probe(s0, attr, dens, acts, lo, hi)
+            self._grad_probe = dict(res)
+            if res['rel'] <= max_grad_rel:
+                return
+            msg = ('the %s tape\'s gradient is %.3e of its largest component away from the float64 evaluation on these weights '
+                   '(component %d), beyond the %.3e asked for' % (res['tape'], res['rel'], res['worst'], max_grad_rel))
+            if res['tape'] != 'fused':
+                raise L.DrpError(msg + ': the fp32 tape has nowhere to fall back to')
+            warnings.warn(msg + ': continuing on the fp32 matrix engine', RuntimeWarning, stacklevel=3)
+            self._give_way(L.ENGINE_MFMA)             # undone by the next load_weights: the finding belongs to these weights
+
+    def _forward_guard(self, batch, max_disp_rel):
         import warnings
         names = dict((v, k) for k, v in L.ENGINES.items())
         while True:
@@ -154,7 +184,7 @@ class Engine(object):
             # lite gives way to the full products of the same kernels, and those, like the split engine, to fp32
             nxt = L.ENGINE_FUSED if self.engine_id == L.ENGINE_LITE else L.ENGINE_MFMA
             warnings.warn(msg + ': continuing on the %s engine' % ('fused' if nxt == L.ENGINE_FUSED else 'fp32 matrix'),
-                          RuntimeWarning, stacklevel=2)
+                          RuntimeWarning, stacklevel=3)
             self._give_way(nxt)                       # undone by the next load_weights: the finding belongs to these weights
             if nxt == L.ENGINE_MFMA:
                 return
@@ -186,6 +216,7 @@ class Engine(object):
         assert field.ndim == 2 and goal_coor.ndim == 2 and goal_coor.shape[1] == 2
         self._ck(self.lib.drp_set_goal(self.h, _fp(field), field.shape[0], field.shape[1],
                                        _fp(goal_coor), goal_coor.shape[0]))
+        self._have_goal = True
 
     def distance_transform(self, src, mode='cv5'):
         """cv2.distanceTransform(src, cv2.DIST_L2, 5) on the device ('cv5': OpenCV's 5x5 chamfer;
@@ -313,12 +344,14 @@ class Engine(object):
         if not want:
             self._ck(self.lib.drp_set_goal_image(self.h, _fp(g), g.shape[0], g.shape[1], L.DIST_TRANSFORMS[mode],
                                                  int(max_goal_pts), int(fps_init), None, None, ctypes.byref(m)))
+            self._have_goal = True
             return m.value
         field = np.empty(g.shape, np.float32)
         coor = np.empty((int(max_goal_pts), 2), np.float32)
         self._ck(self.lib.drp_set_goal_image(self.h, _fp(g), g.shape[0], g.shape[1], L.DIST_TRANSFORMS[mode],
                                              int(max_goal_pts), int(fps_init), _fp(field), _fp(coor),
                                              ctypes.byref(m)))
+        self._have_goal = True
         return field, coor[:m.value].copy()
 
     # ---- single operations --------------------------------------------------------
@@ -419,6 +452,42 @@ class Engine(object):
             self._ck(call(engine))
         self._f64_shape = (B, N)
         return {'abs': float(out[0]), 'disp': float(out[1]), 'disp_rel': float(out[2]), 'worst': int(out[3])}
+
+    # ---- the float64 yardstick of the gradient (include/drp.h: drp_gd_grad_f64) ------------------------------------
+    def gd_grad_f64(self, s0, attr, dens, actions, want_state_grad=False):
+        """One iteration of the GD planner (what gd_begin + gd_grad compute) in float64 on the device: s0 [nb,N,3], attr [nb,N],
+        dens [nb], actions [B,H,4] (row = traj * nb + batch) -> (rewards [B], d loss / d actions [B,H,4][, d loss / d every step's
+        predicted state [B,H,N,3]]) as float64.  A one-shot call in buffers of its own: it ends no session and leaves the
+        selected engine, last_dispatch() and the float64 taps as they were."""
+        s0, attr, dens, actions = _f32(s0), _f32(attr), _f32(dens), _f32(actions)
+        nb, N = (s0.shape[0], s0.shape[1]) if s0.ndim == 3 else (0, 0)
+        B, H = (actions.shape[0], actions.shape[1]) if actions.ndim == 3 else (0, 0)
+        r = np.empty((max(B, 0),), np.float64)
+        g = np.empty((max(B, 0), max(H, 0), 4), np.float64)
+        gs = np.empty((max(B, 0), max(H, 0), max(N, 0), 3), np.float64) if want_state_grad else None
+        self._ck(self.lib.drp_gd_grad_f64(self.h, _fp(s0), _fp(attr), _fp(dens), int(nb), int(N), _fp(actions), int(B), int(H),
+                                          _dp(r), _dp(g), _dp(gs) if want_state_grad else None))
+        return (r, g, gs) if want_state_grad else (r, g)
+
+    def gradient_probe(self, s0, attr, dens, actions, act_lo, act_hi):
+        """The gradient the planner consumes, held against float64: gd_begin + gd_grad on whatever tape the selection gives,
+        then gd_grad_f64 on the same inputs -> {'abs': max |g32 - g64|, 'scale': max |g64|, 'rel': abs / max(scale, 1e-300),
+        'worst': flat index of the worst component (the lowest on a tie; NaN counts as +inf), 'reward_rel': max |r32 - r64| /
+        max |r64|, 'tape': 'fused' | 'mfma'}.  A one-shot like gd_begin: it ENDS a running planner session (mpc_* or gd_*), and
+        it resets the dispatch marks: last_dispatch() afterwards names this call's kernels (the tape's engine is read from them)."""
+        self.dispatch_reset()
+        self.gd_begin(s0, attr, dens, actions, 0.05, act_lo, act_hi)
+        r32, g32, _ = self.gd_grad()
+        # the fp32 matrix engine's tape is the only user of k_aggregate_tape (pick_tape_engine: selected, or after a range refusal)
+        tape = 'mfma' if 'k_aggregate_tape' in self.last_dispatch() else 'fused'
+        r64, g64 = self.gd_grad_f64(s0, attr, dens, actions)
+        err = np.abs(g32.astype(np.float64) - g64).ravel()
+        err = np.where(np.isnan(err), np.inf, err)
+        scale = float(np.abs(g64).max())
+        a = float(err.max())
+        rscale = float(np.abs(r64).max())
+        return {'abs': a, 'scale': scale, 'rel': a / max(scale, 1e-300), 'worst': int(np.argmax(err)),
+                'reward_rel': float(np.abs(r32.astype(np.float64) - r64).max()) / max(rscale, 1e-300), 'tape': tape}
 
     def rollout(self, s0, attr, dens, actions, want_states=True, want_reward=False):
         s0, attr, dens, actions = _f32(s0), _f32(attr), _f32(dens), _f32(actions)
@@ -817,13 +886,16 @@ class Engine(object):
 
     def range_info(self):
         """{'shift', 'bound', 'wmax', 'ok'} of the split-fp16 relation encoder for the loaded weights (drp_range_info); after
-        load_weights(probe=...) also 'probe': {'abs', 'disp', 'disp_rel', 'worst', 'engine'}."""
+        load_weights(probe=...) also 'probe': {'abs', 'disp', 'disp_rel', 'worst', 'engine'}, after load_weights(max_grad_rel=...)
+        'grad_probe': what gradient_probe returned."""
         k, ok = ctypes.c_int(), ctypes.c_int()
         bound, wmax = ctypes.c_double(), ctypes.c_double()
         self._ck(self.lib.drp_range_info(self.h, ctypes.byref(k), ctypes.byref(bound), ctypes.byref(wmax), ctypes.byref(ok)))
         info = {'shift': k.value, 'bound': bound.value, 'wmax': wmax.value, 'ok': bool(ok.value)}
         if getattr(self, '_probe', None) is not None:
             info['probe'] = dict(self._probe)         # what load_weights(probe=...) measured, and on which engine
+        if getattr(self, '_grad_probe', None) is not None:
+            info['grad_probe'] = dict(self._grad_probe)       # what load_weights(max_grad_rel=...) measured, and on which tape
         return info
 
     def debug_fetch(self, name, shape, dtype=np.float32):

@@ -148,14 +148,15 @@ class PropNetDiffDenModel(object):
     def to(self, *a, **k):
         return self
 
-    def load_state_dict(self, state_dict, strict=True, probe=None, max_disp_rel=None):
-        """probe / max_disp_rel: Engine.load_weights' -- measure the engine against the float64 evaluation on these weights"""
+    def load_state_dict(self, state_dict, strict=True, probe=None, max_disp_rel=None, max_grad_rel=None):
+        """probe / max_disp_rel / max_grad_rel: Engine.load_weights' -- measure the engine (and the planner's gradient) against
+        the float64 evaluation on these weights"""
         import weakref
         self._blob = _weights.blob_from_state_dict(state_dict, strict=strict)
-        if probe is None and max_disp_rel is None:
+        if probe is None and max_disp_rel is None and max_grad_rel is None:
             self.engine.load_weights(self._blob, self.adj_thresh)
         else:
-            self.engine.load_weights(self._blob, self.adj_thresh, probe=probe, max_disp_rel=max_disp_rel)
+            self.engine.load_weights(self._blob, self.adj_thresh, probe=probe, max_disp_rel=max_disp_rel, max_grad_rel=max_grad_rel)
         self.engine._weights_owner = weakref.ref(self)
         self._device_ahead = False
         return self

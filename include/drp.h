@@ -509,6 +509,26 @@ int drp_debug_set_f64_cap(drp_ctx* ctx, size_t bytes);
 int drp_accuracy_probe(drp_ctx* ctx, int engine, const float* a_cur, const float* s_cur, const float* s_delta,
                        const float* dens, int B, int N, double out[4]);
 
+/* ---- the float64 yardstick of the gradient (row y2): what drp_gd_begin + drp_gd_grad compute (planners.py:685-745: row =
+ * traj * nb + batch, an H-step rollout, the final step's config_reward_ptcl, loss = -sum reward, reverse mode through every
+ * step), every product and sum in double.  A one-shot call: no drp_gd_begin, no session begun or ended, buffers of its own,
+ * the selected engine, drp_last_dispatch and the degree statistic as before; taps of an earlier *_f64 call stay answered.
+ * Camera, goal field and goal points are the context's, the weights the float64 copy of the loaded blob, all widened exactly.
+ * Forward: gen_s_delta (planners.py:211-257, hard mask included, with its constants 0.8 / 24 and 0.01 as the reference's
+ * expressions give them in double) on the double state; the step's lists from the library's own fp32 graph build on the fp32
+ * roundings of that state and impulse (as drp_step_f64); the step as drp_forward_f64, its intermediates kept as the tape; the
+ * next state stays in double.  The reward (env/flex_rewards.py:189-214) in double: projection, grid_sample's border clamp and
+ * floor-chosen bilinear cell, one-sided chamfer with the lowest particle index winning a tie.  Backward: graph, hard mask,
+ * bilinear cell and arg-min are constants, as autograd treats them.  64-wide blocks on v_mfma_f64_16x16x4_f64; ONE reduction
+ * order per value (ascending k, ascending slot, the sender scatter as a gather over reversed lists in ascending edge order),
+ * no atomics: a row's outputs are the same bits alone, in any batch, from run to run and under any workspace cap
+ * (drp_debug_set_f64_cap: the batch is walked in row chunks, tape 24 KB per particle and step; one row is the smallest chunk).
+ * rewards_out [B], grad_act_out [B,H,4] = d loss / d pushes, grad_state_out [B,H,N,3] = d loss / d every step's predicted state
+ * (as drp_gd_grad); each nullable.  DRP_ESTATE without weights, camera or goal; DRP_EINVAL for non-positive sizes, H > 64, B
+ * not a multiple of nb, N beyond drp_forward's limit.  A zero-length push gives NaN, as the reference. */
+int drp_gd_grad_f64(drp_ctx* ctx, const float* s0, const float* attr, const float* dens, int nb, int N, const float* actions,
+                    int B, int H, double* rewards_out, double* grad_act_out, double* grad_state_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,3 +31,26 @@ for label, wts, cases in legs:
             r = eng.accuracy_probe(a, s, sd, d, engine=_lib.ENGINES[name])
             print('%-7s %-14s %-5s against float64: max |err| %.3e, largest displacement %.3e, ratio %.3e (particle %d)'
                   % (label, p, name, r['abs'], r['disp'], r['disp_rel'], r['worst']))
+
+# --grad: the quantity the live planner consumes.  The gradient of the GD planner's loss on each tape (the fused engine's
+# split-fp16 one, the fp32 matrix engine's) against the device's float64 evaluation of the same iteration
+# (Engine.gradient_probe), per weight set, on the gradient cases of the golden files
+if '--grad' in sys.argv:
+    from dyn_res_pile_manip_amd import synthetic as syn
+    from dyn_res_pile_manip_amd.planners import world2cam_affine
+    eng.set_camera(world2cam_affine(syn.demo_cam_extrinsics()), 24.0, syn.demo_cam_params())
+    G = syn.goal_field(syn.goal_distance_image(syn.goal_mask('I')))
+    lo, hi = syn.action_limits()
+    gr = np.load('tests/golden/grad.npz')
+    legs = [('seed-0', w, [(gr, c + '/') for c in ('h1', 'h2', 'h1_n100')]),
+            ('trained', np.load('tests/golden/weights_trained.npz'), [(t, 'grad/n%d_h%d/' % (n, h)) for n in (20, 50, 100) for h in (1, 2)])]
+    for label, wts, cases in legs:
+        eng.load_weights(weights.blob_from_state_dict(wts), 0.08)
+        for src, p in cases:
+            eng.set_goal(G, src[p + 'goal_coor'])
+            for name in ('fused', 'mfma'):
+                eng.set_engine(_lib.ENGINES[name])
+                r = eng.gradient_probe(src[p + 's_cur'], src[p + 'attr'], src[p + 'dens'], src[p + 'act_seqs'], lo, hi)
+                print('%-7s %-14s %-5s tape against float64: max |g32 - g64| %.3e, max |g64| %.3e, ratio %.3e (component %d), reward %.3e'
+                      % (label, p, r['tape'], r['abs'], r['scale'], r['rel'], r['worst'], r['reward_rel']))
+    eng.set_engine(_lib.ENGINES['fused'])
