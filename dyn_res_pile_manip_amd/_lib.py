@@ -168,6 +168,8 @@ SIGNATURES = {
                                           ctypes.c_int, ctypes.c_int, c_double_p]),
     'drp_gd_grad_f64': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.c_int, ctypes.c_int, c_float_p,
                                        ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p]),
+    'drp_train_grad_f64': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.POINTER(ctypes.c_int32), c_float_p,
+                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p]),
 }
 
 _lib = None

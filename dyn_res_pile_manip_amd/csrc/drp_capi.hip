@@ -47,6 +47,7 @@
 #include "k_ptcl_dataset.h"
 #include "k_prop_f64.h"
 #include "k_gd_f64.h"
+#include "k_train_f64.h"
 #include "k_prop_inst.h"       // km_prop / km_prop3 / km_rollout: declared here, instantiated in inst_*.hip
 
 #include "dispatch.h"          // host-only: policy, variant flags, plan functions
@@ -66,6 +67,7 @@ extern "C" {
 #include "capi_ptcl_dataset.h"
 #include "capi_f64.h"
 #include "capi_gd_f64.h"
+#include "capi_train_f64.h"
 #include "capi_debug.h"
 
 }  // extern "C"

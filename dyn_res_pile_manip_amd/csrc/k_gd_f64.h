@@ -4,7 +4,9 @@
 //
 // The graph, gen_s_delta's hard mask, the bilinear cell and the chamfer arg-min are constants of the reverse pass, as autograd
 // treats them.  The hidden layers of the encoders and of the predictor are not on the tape: the backward kernels evaluate them
-// again with the forward kernels' own expressions (the same bits), for their ReLU masks.
+// again with the forward kernels' own expressions (the same bits), for their ReLU masks.  Those three kernels can also write the
+// hidden layers, their masked gradients and the narrow inputs out (null here): the operands of the weight gradients of
+// k_train_f64.h.
 //
 // The 64-wide blocks run on v_mfma_f64_16x16x4_f64 with the fragment layout at the top of k_prop_f64.h; dX = dY W reads the
 // blocks in the transposed fragment order (kf_frag_t).  The 5-, 6- and 3-wide layers and the reductions are fma / add chains.
@@ -222,7 +224,9 @@ __global__ __launch_bounds__(256) void kg_reward(const double* __restrict__ stat
 
 // ---- predictor backward (model/gnn_dyn.py:196, :110): g_out [rows,3] -> g_eff [rows,64] --------------------------------
 __global__ __launch_bounds__(64 * KG_WAVES) void kg_predict_bwd(const double* __restrict__ w, const double* __restrict__ eff,
-                                                                const double* __restrict__ g_out, int rows, double* __restrict__ g_eff) {
+                                                                const double* __restrict__ g_out, int rows, double* __restrict__ g_eff,
+                                                                double* __restrict__ h_out = nullptr /* [rows,64] the hidden layer ... */,
+                                                                double* __restrict__ gh_out = nullptr /* ... and its masked gradient */) {
     __shared__ double X[KG_WAVES][16 * KF_LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
     const int row0 = (blockIdx.x * KG_WAVES + wave) * 16;
@@ -240,7 +244,12 @@ __global__ __launch_bounds__(64 * KG_WAVES) void kg_predict_bwd(const double* __
             double gh = 0.0;
 #pragma unroll
             for (int k = 0; k < 3; ++k) gh = fma(g_out[grow * 3 + k], w[W_PR1_W + k * 64 + col], gh);
-            x[lrow * KF_LD + col] = (acc[jt][g] + w[W_PR0_B + col]) > 0.0 ? gh : 0.0;
+            const double hv = acc[jt][g] + w[W_PR0_B + col];
+            x[lrow * KF_LD + col] = hv > 0.0 ? gh : 0.0;
+            if (h_out != nullptr && row0 + lrow < rows) {
+                h_out[grow * 64 + col] = kf_relu(hv);
+                gh_out[grow * 64 + col] = hv > 0.0 ? gh : 0.0;
+            }
         }
     __syncthreads();
     kf_zero(acc);
@@ -337,7 +346,10 @@ __global__ __launch_bounds__(256) void kg_gather_bwd(const double* __restrict__ 
 __global__ __launch_bounds__(64 * KG_WAVES) void kg_pencode_bwd(const double* __restrict__ w, const double* __restrict__ s_delta,
                                                                 const float* __restrict__ attr, const float* __restrict__ dens,
                                                                 const double* __restrict__ pe, const double* __restrict__ g_pe, int N,
-                                                                int rows, double* __restrict__ g_sd) {
+                                                                int rows, double* __restrict__ g_sd,
+                                                                double* __restrict__ in_out = nullptr /* [rows,5] the inputs, ... */,
+                                                                double* __restrict__ h_out = nullptr /* [rows,64] the hidden layer ... */,
+                                                                double* __restrict__ gh_out = nullptr /* ... and its masked gradient */) {
     __shared__ double X[KG_WAVES][16 * KF_LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
     const int row0 = (blockIdx.x * KG_WAVES + wave) * 16;
@@ -351,7 +363,10 @@ __global__ __launch_bounds__(64 * KG_WAVES) void kg_pencode_bwd(const double* __
 #pragma unroll
             for (int k = 0; k < 5; ++k) acc = fma(in[k], w[W_PE0_W + o * 5 + k], acc);
             x[r * KF_LD + o] = kf_relu(acc + w[W_PE0_B + o]);
+            if (h_out != nullptr && row0 + r < rows) h_out[row * 64 + o] = x[r * KF_LD + o];
         }
+        if (in_out != nullptr && q == 0 && row0 + r < rows)
+            for (int k = 0; k < 5; ++k) in_out[row * 5 + k] = in[k];
     }
     __syncthreads();
     kf_d4 acc[4];
@@ -363,6 +378,7 @@ __global__ __launch_bounds__(64 * KG_WAVES) void kg_pencode_bwd(const double* __
         for (int g = 0; g < 4; ++g) {
             const int o = (q + 4 * g) * KF_LD + jt * 16 + r;
             x[o] = x[o] > 0.0 ? acc[jt][g] : 0.0;
+            if (gh_out != nullptr && row0 + q + 4 * g < rows) gh_out[(size_t)(row0 + q + 4 * g) * 64 + jt * 16 + r] = x[o];
         }
     __syncthreads();
     if (q < 3 && row0 + r < rows) {
@@ -377,7 +393,12 @@ __global__ __launch_bounds__(64 * KG_WAVES) void kg_rencode_bwd(const double* __
                                                                 const float* __restrict__ attr, const float* __restrict__ dens,
                                                                 const int16_t* __restrict__ idx, const uint8_t* __restrict__ cnt,
                                                                 const double* __restrict__ re, const double* __restrict__ g_re, int N,
-                                                                int erows, double* __restrict__ g_diff) {
+                                                                int erows, double* __restrict__ g_diff,
+                                                                double* __restrict__ in_out = nullptr /* [erows,6] the inputs, ... */,
+                                                                double* __restrict__ h1_out = nullptr, double* __restrict__ h2_out = nullptr
+                                                                /* [erows,64] the two hidden layers ... */,
+                                                                double* __restrict__ g1_out = nullptr, double* __restrict__ g2_out = nullptr
+                                                                /* ... and their masked gradients */) {
     __shared__ double X[KG_WAVES][16 * KF_LD], Y[KG_WAVES][16 * KF_LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
     const int row0 = (blockIdx.x * KG_WAVES + wave) * 16;
@@ -395,7 +416,10 @@ __global__ __launch_bounds__(64 * KG_WAVES) void kg_rencode_bwd(const double* __
 #pragma unroll
             for (int kk = 0; kk < 6; ++kk) acc = fma(in[kk], w[W_RE0_W + o * 6 + kk], acc);
             x[r * KF_LD + o] = kf_relu(acc + w[W_RE0_B + o]);
+            if (h1_out != nullptr && row0 + r < erows) h1_out[e * 64 + o] = x[r * KF_LD + o];
         }
+        if (in_out != nullptr && q == 0 && row0 + r < erows)
+            for (int kk = 0; kk < 6; ++kk) in_out[e * 6 + kk] = in[kk];
     }
     __syncthreads();
     kf_d4 acc[4];
@@ -407,6 +431,7 @@ __global__ __launch_bounds__(64 * KG_WAVES) void kg_rencode_bwd(const double* __
         for (int g = 0; g < 4; ++g) {
             const int col = jt * 16 + r;
             y[(q + 4 * g) * KF_LD + col] = kf_relu(acc[jt][g] + w[W_RE2_B + col]);
+            if (h2_out != nullptr && row0 + q + 4 * g < erows) h2_out[(size_t)(row0 + q + 4 * g) * 64 + col] = y[(q + 4 * g) * KF_LD + col];
         }
     kf_zero(acc);
     kg_mma64_masked(acc, g_re + e * 64, re + e * 64, kf_frag_t(w, KF_RE4), lane);
@@ -416,6 +441,7 @@ __global__ __launch_bounds__(64 * KG_WAVES) void kg_rencode_bwd(const double* __
         for (int g = 0; g < 4; ++g) {
             const int o = (q + 4 * g) * KF_LD + jt * 16 + r;
             y[o] = y[o] > 0.0 ? acc[jt][g] : 0.0;
+            if (g2_out != nullptr && row0 + q + 4 * g < erows) g2_out[(size_t)(row0 + q + 4 * g) * 64 + jt * 16 + r] = y[o];
         }
     __syncthreads();
     kf_zero(acc);
@@ -426,6 +452,7 @@ __global__ __launch_bounds__(64 * KG_WAVES) void kg_rencode_bwd(const double* __
         for (int g = 0; g < 4; ++g) {
             const int o = (q + 4 * g) * KF_LD + jt * 16 + r;
             x[o] = x[o] > 0.0 ? acc[jt][g] : 0.0;
+            if (g1_out != nullptr && row0 + q + 4 * g < erows) g1_out[(size_t)(row0 + q + 4 * g) * 64 + jt * 16 + r] = x[o];
         }
     __syncthreads();
     if (q < 3 && row0 + r < erows) {

@@ -626,6 +626,55 @@ class Engine(object):
                                          L.TRAIN_MODES[mode], ctypes.byref(loss), None if grad is None else _fp(grad)))
         return loss.value, grad
 
+    # ---- the float64 yardstick of the trainer's gradients (include/drp.h: drp_train_grad_f64) ------------------------
+    def train_grad_f64(self, states, states_delta, attrs, particle_nums, particle_dens, want_state=False):
+        """What train_step(mode='grad') computes, in float64 on the device -> (loss, loss_terms [n_rollout, B], gradient blob
+        [38403] in state_dict order[, d loss / d every step's predicted state [B, n_rollout, N, 3]]) as float64.  n_rollout is
+        read from the arrays.  A one-shot call in buffers of its own: no train_begin needed; it ends no session and leaves the
+        trainer's Adam state, the selected engine, last_dispatch() and the float64 taps as they were."""
+        states, states_delta, attrs = _f32(states), _f32(states_delta), _f32(attrs)
+        dens = _f32(particle_dens)
+        nums = np.ascontiguousarray(particle_nums, dtype=np.int32)
+        B, T1, N = (states.shape[0], states.shape[1], states.shape[2]) if states.ndim == 4 else (0, 1, 0)
+        H = T1 - 1
+        if B > 0 and N > 0 and H > 0:
+            assert states.shape == (B, T1, N, 3) and states_delta.shape == (B, H, N, 3)
+            assert attrs.shape == (B, T1, N) and nums.shape == (B,) and dens.shape == (B,)
+        loss = ctypes.c_double()
+        terms = np.empty((max(H, 0), max(B, 0)), np.float64)
+        grad = np.empty((38403,), np.float64)
+        gs = np.empty((max(B, 0), max(H, 0), max(N, 0), 3), np.float64) if want_state else None
+        self._ck(self.lib.drp_train_grad_f64(self.h, _fp(states), _fp(states_delta), _fp(attrs),
+                                             nums.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _fp(dens), int(B), int(N), int(H),
+                                             ctypes.byref(loss), _dp(terms), _dp(grad), _dp(gs) if want_state else None))
+        return (loss.value, terms, grad, gs) if want_state else (loss.value, terms, grad)
+
+    def train_gradient_probe(self, states, states_delta, attrs, particle_nums, particle_dens):
+        """The gradients the trainer consumes, held against float64: train_step(mode='grad', want_grad=True) on whatever tape the
+        selection gives, then train_grad_f64 on the same batch -> {'tensors': {state_dict key: {'max_abs_err', 'max_abs_ref',
+        'rel' = err / max(ref, 1e-300)}}, 'worst': the key of the largest rel, 'rel': that rel, 'loss32', 'loss64', 'loss_diff',
+        'tape': 'fused' | 'mfma'}.  Needs train_begin, like train_step; it changes no weight, Adam moment or iteration count, so a
+        following train_step(mode='update') is what it would have been.  Like train_step it ends a running planner session, and
+        it resets the dispatch marks: last_dispatch() afterwards names this call's kernels."""
+        from .weights import STATE_DICT_KEYS
+        self.dispatch_reset()
+        loss32, g32 = self.train_step(states, states_delta, attrs, particle_nums, particle_dens, mode='grad', want_grad=True)
+        # the fp32 matrix engine's tape is the only user of k_aggregate_tape (pick_tape_engine: selected, or after a range refusal)
+        tape = 'mfma' if 'k_aggregate_tape' in self.last_dispatch() else 'fused'
+        loss64, _, g64 = self.train_grad_f64(states, states_delta, attrs, particle_nums, particle_dens)
+        tensors, off, worst = {}, 0, None
+        for key, shape in STATE_DICT_KEYS:
+            n = int(np.prod(shape))
+            err = np.abs(g32[off:off + n].astype(np.float64) - g64[off:off + n])
+            err = float(np.where(np.isnan(err), np.inf, err).max())
+            ref = float(np.abs(g64[off:off + n]).max())
+            tensors[key] = {'max_abs_err': err, 'max_abs_ref': ref, 'rel': err / max(ref, 1e-300)}
+            if worst is None or tensors[key]['rel'] > tensors[worst]['rel']:
+                worst = key
+            off += n
+        return {'tensors': tensors, 'worst': worst, 'rel': tensors[worst]['rel'], 'loss32': loss32, 'loss64': loss64,
+                'loss_diff': abs(loss32 - loss64), 'tape': tape}
+
     def train_set_lr(self, lr):
         self._ck(self.lib.drp_train_set_lr(self.h, float(lr)))
 

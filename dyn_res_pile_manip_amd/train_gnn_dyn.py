@@ -98,11 +98,22 @@ class AverageMeter(object):
         self.avg = self.sum / self.count
 
 
-def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=None, first_epoch=0):
+def probe_batch(model, data):
+    """Engine.train_gradient_probe on a collated batch: the trainer's fp32 gradients against the float64 evaluation of the same
+    batch on the device; weights, Adam state and iteration count are untouched"""
+    states, states_delta, attrs, particle_nums, particle_dens = [data[i] for i in range(5)]
+    if hasattr(model, '_claim'):
+        model._claim()
+    return model.engine.train_gradient_probe(_np(states), _np(states_delta), _np(attrs), _np(particle_nums, np.int32),
+                                             _np(particle_dens))
+
+
+def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=None, first_epoch=0, grad_probe_every=0):
     """train/train_gnn_dyn.py:134-246 without the file I/O: `dataloaders` = {'train': iterable of
     collated batches, 'valid': ...}.  Returns {'best_valid_loss', 'history': [(epoch, phase, rmse)]}.
     ckp(epoch, i, model): called after training batch i when i % ckp_per_iter == 0 (:217-218); first_epoch: the epoch
-    a resumed run starts from (:136)."""
+    a resumed run starts from (:136).  grad_probe_every = k > 0: every k-th training batch (i % k == 0) is probed before its
+    update (probe_batch); the worst tensor's rel goes to the history as (epoch, 'grad_probe', rel) and to the log."""
     tc = config['train']
     n_rollout = tc['n_rollout']
     assert tc['n_history'] == 1
@@ -114,6 +125,12 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
             model.train(phase == 'train')
             meter = AverageMeter()
             for i, data in enumerate(dataloaders[phase]):
+                if grad_probe_every > 0 and phase == 'train' and i % grad_probe_every == 0:
+                    pr = probe_batch(model, data)
+                    history.append((epoch, 'grad_probe', float(pr['rel'])))
+                    if log is not None:
+                        log('grad_probe [%d][%d] worst %s rel %.3e (%s tape), loss diff %.3e' % (epoch, i, pr['worst'], pr['rel'],
+                                                                                               pr['tape'], pr['loss_diff']))
                 loss = run_batch(model, optimizer, data, phase, n_rollout)
                 meter.update(loss, _np(data[0]).shape[0])
                 if log is not None and i % tc['log_per_iter'] == 0:
@@ -150,7 +167,7 @@ def set_seed(seed):
     random.seed(seed)
 
 
-def main(config, data_root=None, train_dir=None, cam=None, chunk=64, threads=8, n_epoch=None, engine=None):
+def main(config, data_root=None, train_dir=None, cam=None, chunk=64, threads=8, n_epoch=None, engine=None, grad_probe_every=0):
     """The file-level part of train/train_gnn_dyn.py:train() (:45-130, :196-228): seed, the log directory with config.yaml
     and log.txt, the 'train' / 'valid' ParticleDatasets and their DeviceLoaders, a fresh model (torch.nn.Linear's default
     initialisation) or the resumed checkpoint, net_epoch_%d_iter_%d.pth every ckp_per_iter training batches and
@@ -197,8 +214,11 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=64, threads=8, 
             weights.save_checkpoint(sd, os.path.join(train_dir, 'net_best.pth'))
 
         result = train(config, model, loaders, n_epoch=n_epoch, log=log, on_best=on_best, ckp=ckp,
-                       first_epoch=resume['epoch'] if resume['active'] and resume['epoch'] > 0 else 0)
+                       first_epoch=resume['epoch'] if resume['active'] and resume['epoch'] > 0 else 0,
+                       grad_probe_every=grad_probe_every)
         for epoch, phase, rmse in result['history']:
+            if phase == 'grad_probe':                   # logged when it was taken
+                continue
             log('%s [%d] Loss: %.6f' % (phase, epoch, rmse))
     return result, train_dir
 
@@ -216,6 +236,8 @@ def _cli(argv=None):
     ap.add_argument('--epochs', type=int, help='override train.n_epoch')
     ap.add_argument('--chunk', type=int, default=64, help='samples per device call')
     ap.add_argument('--threads', type=int, default=8, help='decoding threads (at most 16)')
+    ap.add_argument('--grad-probe-every', type=int, default=0,
+                    help='hold every k-th training batch\'s gradients against float64 before its update (0: never)')
     a = ap.parse_args(argv)
     config = default_config()
     if a.config:
@@ -225,7 +247,8 @@ def _cli(argv=None):
         config['dataset']['n_episode'] = a.n_episode
     if a.n_timestep is not None:
         config['dataset']['n_timestep'] = a.n_timestep
-    result, d = main(config, a.data_root, a.train_dir, chunk=a.chunk, threads=a.threads, n_epoch=a.epochs)
+    result, d = main(config, a.data_root, a.train_dir, chunk=a.chunk, threads=a.threads, n_epoch=a.epochs,
+                     grad_probe_every=a.grad_probe_every)
     print('best valid loss %.6f, checkpoints in %s' % (np.sqrt(result['best_valid_loss']), d))
 
 

@@ -529,6 +529,32 @@ int drp_accuracy_probe(drp_ctx* ctx, int engine, const float* a_cur, const float
 int drp_gd_grad_f64(drp_ctx* ctx, const float* s0, const float* attr, const float* dens, int nb, int N, const float* actions,
                     int B, int H, double* rewards_out, double* grad_act_out, double* grad_state_out);
 
+/* ---- the float64 yardstick of the trainer's gradients (row y3): what drp_train_step(mode = DRP_TRAIN_GRAD) computes
+ * (train/train_gnn_dyn.py:167-203; layouts as there: states [B, n_rollout+1, N, 3], states_delta [B, n_rollout, N, 3], attrs
+ * [B, n_rollout+1, N], particle_nums [B], particle_dens [B]), every product and sum in double.  A one-shot call: no
+ * drp_train_begin (n_rollout is an argument), no session begun or ended, buffers of its own; the selected engine,
+ * drp_last_dispatch, the degree statistic, the trainer's Adam moments, iteration count, learning rate and launch plan, and the
+ * taps of an earlier *_f64 call are as before.  The weights are the float64 copy of the current blob (after an optimiser step:
+ * the updated one), the inputs widened exactly.
+ * Forward: s_cur = states[:, 0], a_cur = attrs[:, 0]; each step's impulse is states_delta[:, t]; its lists come from the
+ * library's own fp32 graph build, in the trainer's mode for zero-padded batches, on the fp32 roundings of the double state; the
+ * step as drp_forward_f64, its intermediates kept as the tape; s_cur <- s_pred stays in double.  loss_terms_out [n_rollout][B] =
+ * mse(s_pred[b, :n_b], states[b, t+1, :n_b]) / (n_rollout B) as float64 sums of squared double differences; loss_out = their
+ * sum, step-major.  Backward: drp_gd_grad_f64's kernels, the state gradient seeded by 2 (s_pred - s_nxt) / (3 n_b n_rollout B)
+ * on real rows and 0 on padded ones; the impulse is data; the graph is a constant.  Weight gradients dW = G^T X: the 64-wide
+ * blocks on v_mfma_f64_16x16x4_f64 with the rows as the k dimension (the receiver's and sender's effects gathered through the
+ * lists inside the load), the narrow inputs, density columns and biases as one ascending chain per entry; a slot past its
+ * receiver's count contributes exactly zero.  ONE reduction order per value, no atomics: (sample, step) contributions in
+ * ascending row order, added per sample in the order the reverse pass visits the steps, the samples in ascending order in one
+ * chain per entry -- grad_out is the same bits from run to run and under any workspace cap (drp_debug_set_f64_cap: sample
+ * chunks; tape 24 KB per particle and step, 307 KB of accumulators per sample; one sample is the smallest chunk).
+ * grad_out: 38 403 doubles in state_dict order; grad_state_out [B, n_rollout, N, 3] = d loss / d every step's predicted state;
+ * each output nullable.  DRP_ESTATE without weights; DRP_EINVAL for non-positive sizes, n_rollout > 64, N beyond drp_forward's
+ * limit, a particle_nums[b] outside 1..N, null inputs. */
+int drp_train_grad_f64(drp_ctx* ctx, const float* states, const float* states_delta, const float* attrs,
+                       const int32_t* particle_nums, const float* particle_dens, int B, int N, int n_rollout,
+                       double* loss_out, double* loss_terms_out, double* grad_out, double* grad_state_out);
+
 #ifdef __cplusplus
 }
 #endif

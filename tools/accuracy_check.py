@@ -54,3 +54,19 @@ if '--grad' in sys.argv:
                 print('%-7s %-14s %-5s tape against float64: max |g32 - g64| %.3e, max |g64| %.3e, ratio %.3e (component %d), reward %.3e'
                       % (label, p, r['tape'], r['abs'], r['scale'], r['rel'], r['worst'], r['reward_rel']))
     eng.set_engine(_lib.ENGINES['fused'])
+
+# --train-grad: the quantity the trainer consumes.  Every parameter's gradient of train.npz's batches on each tape against the
+# device's float64 evaluation of the same loop body (Engine.train_gradient_probe), per weight set
+if '--train-grad' in sys.argv:
+    tr = np.load('tests/golden/train.npz')
+    for label, wts in (('seed-0', np.load('tests/golden/weights_seed0.npz')), ('trained', np.load('tests/golden/weights_trained.npz'))):
+        eng.load_weights(weights.blob_from_state_dict(wts), 0.08)
+        for case in ('b4_r3', 'b2_r5'):
+            batch = [tr[case + '/' + k] for k in ('states', 'states_delta', 'attrs', 'particle_nums', 'particle_dens')]
+            for name in ('fused', 'mfma'):
+                eng.set_engine(_lib.ENGINES[name])
+                eng.train_begin(batch[0].shape[1] - 1, 1e-3, 0.9)
+                r = eng.train_gradient_probe(*batch)
+                print('%-7s %-6s %-5s tape against float64: worst tensor %s, max |g32 - g64| / max |g64| %.3e, loss difference %.3e'
+                      % (label, case, r['tape'], r['worst'], r['rel'], r['loss_diff']))
+    eng.set_engine(_lib.ENGINES['fused'])
