@@ -299,8 +299,8 @@ struct drp_ctx {
     DevBuf f64_stage[F64_STAGE_BUFS];       // stand in for the step workspaces while a *_f64 call runs (capi_f64.h: F64Scope)
     DevBuf f64_pe, f64_eff, f64_agg, f64_re, f64_erel, f64_pred, f64_out, f64_red;
     int f64_lastB = 0, f64_lastN = 0, f64_chunks = 0;       // of the last *_f64 call (drp_f64_tap)
-    DevBuf gd64_ws, gd64_io;        // drp_gd_grad_f64 (capi_gd_f64.h): a chunk's tape and reverse pass; the batch's inputs and results
-    DevBuf tr64_ws, tr64_io;        // drp_train_grad_f64 (capi_train_f64.h): the same, with the samples' gradient accumulators; batch, loss terms, total
+    DevBuf grad64_ws, grad64_io;    // drp_gd_grad_f64 and drp_train_grad_f64 (capi_grad_f64.h; one-shots that keep nothing between calls): a chunk's tape
+                                    // and reverse pass (the trainer: and its samples' gradient accumulators); the batch's inputs and results
 
     // re-packing after an optimiser step on the device (k_train.h): gather maps of the plain packers, pinned copy of the blob
     DevBuf map_valu, map_mfma, map_mfma_bwd;

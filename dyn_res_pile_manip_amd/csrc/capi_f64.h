@@ -63,7 +63,7 @@ int f64_build_lists(drp_ctx* c, int B, int N) {
 
 // The launches of one step over `rows` particles (whole samples of N): its intermediates into pe [rows,64], re [rows,10,64],
 // eff and agg [3][rows,64], erel [3][rows,10,64], pred [rows,3], the new positions into s_pred [rows,3].  TS: the type of the
-// positions and impulses, float (the one-step calls) or double (the rollout of capi_gd_f64.h, whose intermediates are its tape).
+// positions and impulses, float (the one-step calls) or double (the rollouts of capi_grad_f64.h, whose intermediates are its tape).
 extern "C++" template <typename TS>
 void f64_launch_step(drp_ctx* c, const double* w, const TS* s_cur, const TS* s_delta, const float* attr, const float* dens,
                      const int16_t* idx, const uint8_t* cnt, int N, int rows, double* pe, double* re, double* eff, double* agg,

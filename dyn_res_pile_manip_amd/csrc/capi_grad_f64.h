@@ -1,0 +1,404 @@
+// capi_grad_f64.h -- a section of the C ABI's translation unit (textually included by drp_capi.hip, which has the order of the sections).
+// Here: the two float64 gradients -- one iteration of the gradient-descent planner (drp_gd_grad_f64, the yardstick of the tape
+// engines' gradient, row y2) and the training loop body (drp_train_grad_f64, the yardstick of drp_train_step's gradients, row
+// y3) -- on ONE tape and ONE reverse pass (kernels: k_prop_f64.h forward, k_gd_f64.h backward; k_train_f64.h loss and weight
+// gradients).  They differ in where a step's impulse comes from (the push, or data), in the loss that seeds the reverse pass, in
+// the tail of a reverse step, and in the trainer's weight-gradient launches in between (F64Wgrad).  Like the one-step calls of
+// capi_f64.h they are no engine and no session: they work in buffers of their own under F64Scope, keep nothing between calls
+// and leave the context -- the trainer's Adam state included -- as they found it.
+
+namespace {
+
+// buffers from one allocation, each rounded up to 256 bytes; a null base only measures
+extern "C++" struct F64Carver {
+    char* base;
+    size_t off = 0;
+    template <typename T> void take(T*& p, size_t n) {
+        p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += (n * sizeof(T) + 255) & ~(size_t)255;
+    }
+};
+
+// the tape: every step's intermediates (k_prop_f64.h: KF_BYTES_PER_PARTICLE), states, impulses and lists
+struct F64Tape {
+    double *pe, *re, *eff, *agg, *erel, *pred;          // [H] blocks each
+    double *state, *sd;                                 // [H+1][pn,3], [H][pn,3]
+    int16_t* idx; uint8_t* cnt;                         // [H][pn,10], [H][pn]
+    void carve(F64Carver& a, size_t pn, size_t H) {
+        a.take(pe, H * pn * 64); a.take(re, H * pn * DRP_K * 64); a.take(eff, H * pn * 3 * 64); a.take(agg, H * pn * 3 * 64);
+        a.take(erel, H * pn * 3 * DRP_K * 64); a.take(pred, H * pn * 3);
+        a.take(state, (H + 1) * pn * 3); a.take(sd, H * pn * 3); a.take(idx, H * pn * DRP_K); a.take(cnt, H * pn);
+    }
+    // step t's slices in a chunk of pn rows: `state` is the step's input, state + pn * 3 its output
+    F64Tape step(int t, size_t pn) const {
+        const size_t o = (size_t)t * pn;
+        return F64Tape{pe + o * 64, re + o * DRP_K * 64, eff + o * 3 * 64, agg + o * 3 * 64, erel + o * 3 * DRP_K * 64, pred + o * 3,
+                       state + o * 3, sd + o * 3, idx + o * DRP_K, cnt + o};
+    }
+};
+
+// the reverse pass of one step, and the state gradient of every step
+struct F64Rev {
+    double *g_eff, *g_pre, *g_agg, *g_pe, *g_re, *gr, *gs, *g_sd, *g_diff;
+    double* g_state;                                    // [H][pn,3]
+    double* part;                                       // the planner's scratch of kg_sdelta_bwd [pn,4]; the trainer: n_part = 0
+    int *rev_off, *rev;
+    void carve(F64Carver& a, size_t bc, size_t N, size_t H, size_t n_part) {
+        const size_t pn = bc * N;
+        a.take(g_eff, pn * 64); a.take(g_pre, pn * 64); a.take(g_agg, pn * 64); a.take(g_pe, pn * 64);
+        a.take(g_re, pn * DRP_K * 64); a.take(gr, pn * DRP_K * 64); a.take(gs, pn * DRP_K * 64);
+        a.take(g_sd, pn * 3); a.take(g_diff, pn * DRP_K * 3); a.take(g_state, H * pn * 3); a.take(part, n_part);
+        a.take(rev_off, bc * (N + 1)); a.take(rev, pn * DRP_K);
+    }
+};
+
+// Samples per chunk under the cap and the caller's row limit (one is the smallest chunk; bytes_of(bc): the caller's measuring
+// carve), with the workspace for them and the fp32 graph build's staging (the scope's buffers)
+extern "C++" template <typename F> int f64_size_chunks(drp_ctx* c, int B, int N, size_t row_limit, F bytes_of, size_t* chunk) {
+    size_t Bc = std::min<size_t>({(size_t)B, std::max<size_t>(1, c->f64_cap / bytes_of(1)), std::max<size_t>(1, row_limit)});
+    while (Bc > 1 && bytes_of(Bc) > c->f64_cap) --Bc;
+    CHK(ensure(c, c->grad64_ws, bytes_of(Bc)));
+    CHK(ensure_step_ws(c, (int)Bc, N, -1));
+    CHK(ensure(c, c->s_in, Bc * N * 3 * sizeof(float)));
+    *chunk = Bc;
+    return DRP_OK;
+}
+
+// the whole batch's packed inputs in one upload, `n_res` doubles of results behind a 256-byte boundary (returned)
+int f64_upload_batch(drp_ctx* c, const std::vector<float>& host, size_t n_res, double** res) {
+    const size_t in_bytes = (host.size() * sizeof(float) + 255) & ~(size_t)255;
+    CHK(ensure(c, c->grad64_io, in_bytes + n_res * sizeof(double)));
+    HIPCHK(c, hipMemcpyAsync(c->grad64_io.p, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    *res = reinterpret_cast<double*>(static_cast<char*>(c->grad64_io.p) + in_bytes);
+    return DRP_OK;
+}
+
+// forward with tape over H steps from tape.state[0]: stage(t, s) puts step t's impulse in double into s.sd and the fp32
+// roundings of s.state and of the impulse where the graph build reads them; the lists from the fp32 graph build (`padded`: the
+// trainer's mode) on those roundings; the step in double
+extern "C++" template <typename Stage>
+int f64_tape_forward(drp_ctx* c, const F64Tape& tape, int bc, int N, int H, const float* attr, const float* dens, bool padded,
+                     Stage stage) {
+    const int rows = bc * N;
+    for (int t = 0; t < H; ++t) {
+        const F64Tape s = tape.step(t, (size_t)rows);
+        stage(t, s);
+        const GraphPlan g = plan_graph(c->pol, c->n_cu, c->engine, bc, N, padded, false, false, true);
+        launch_graph(c, c->stream, g, ptr<float>(c->s_in), bc, (size_t)N * 3, (const float*)nullptr, (size_t)0, ptr<float>(c->s_delta),
+                     bc, N, s.idx, s.cnt, 0);
+        f64_launch_step<double>(c, ptr<double>(c->f64_w), s.state, s.sd, attr, dens, s.idx, s.cnt, N, rows, s.pe, s.re, s.eff, s.agg,
+                                s.erel, s.pred, s.state + (size_t)rows * 3);
+        HIPCHK(c, hipGetLastError());
+    }
+    return DRP_OK;
+}
+
+// the reversed lists of `sets` samples' neighbour lists (k_graph.h: reverse_lists) into the call's own buffers
+void f64_reverse_lists(hipStream_t st, const int16_t* idx, const uint8_t* cnt, int N, int sets, int* rev_off, int* rev) {
+    const bool rev_lds = N <= KB_REV_LDS_MAX_N;
+    if (N <= 512)
+        hipLaunchKernelGGL(kb_reverse_lists<256>, dim3(sets), dim3(256), KB_REV_LDS(N, rev_lds), st, idx, cnt, N, rev_off, rev,
+                           rev_lds ? 1 : 0, (const int*)nullptr, 0);
+    else
+        hipLaunchKernelGGL(kb_reverse_lists<1024>, dim3(sets), dim3(1024), KB_REV_LDS(N, rev_lds), st, idx, cnt, N, rev_off, rev,
+                           rev_lds ? 1 : 0, (const int*)nullptr, 0);
+}
+
+// The trainer's weight gradients of a reverse step: what the backward kernels leave for them (hidden layers, their masked
+// gradients, the narrow inputs), the samples' accumulators, and the launches.  A layer's weight gradient: its 64-wide blocks
+// on the matrix instruction, bias and density column as chains.
+struct F64Wgrad {
+    hipStream_t st;
+    int bc, N;
+    const float* dens;
+    double *pr_h, *pr_gh, *pe_h, *pe_gh, *pe_in, *re_h1, *re_h2, *re_g1, *re_g2, *re_in;
+    double* acc;                                        // [bc][W_TOTAL]: a sample's gradient
+    Kt64Job job(const double* g, const double* m, int g_div, int R, int b_off, int d_off, int ld) const {
+        Kt64Job j{};
+        j.g = g; j.m = m; j.g_div = g_div; j.N = N; j.R = R; j.ld = ld; j.b_off = b_off; j.d_off = d_off;
+        return j;
+    }
+    void block(Kt64Job j, const double* x, int x_mode, int w_off, const int16_t* idx, const uint8_t* cnt) const {
+        j.x = x; j.x_mode = x_mode; j.w_off = w_off; j.idx = idx; j.cnt = cnt;
+        hipLaunchKernelGGL(kt64_wgrad64, dim3(4, bc), dim3(256), 0, st, j, acc);
+    }
+    void bias(const Kt64Job& j) const { hipLaunchKernelGGL(kt64_wgrad_bias, dim3(bc), dim3(128), 0, st, j, dens, acc); }
+    void narrow(const double* G, int gw, const double* X, int xw, int R, int w_off, int b_off) const {
+        hipLaunchKernelGGL(kt64_wgrad_narrow, dim3((unsigned)((gw * (xw + 1) + 255) / 256), bc), dim3(256), 0, st, G, gw, X, xw, R, w_off,
+                           b_off, acc);
+    }
+};
+
+// The reverse pass of rollout step t, from g_out = d loss / d the step's output state [bc*N,3] down to r.g_sd (d / d impulse)
+// and r.g_diff (d / d (s_r - s_s) per slot; without `wg` only where a step before this one reads it, t > 0): the reversed
+// lists, the predictor, the propagation steps, the encoders.  s: the tape's slices of the step.  `wg` (nullable): the
+// trainer's weight gradients, queued behind the kernel that leaves their operands; the relation encoder then runs at t == 0
+// too, its weights need its hidden gradients.  The step's share of d loss / d input state is the caller's tail.
+void f64_reverse_step(drp_ctx* c, const F64Tape& s, const F64Rev& r, const double* g_out, int t, int bc, int N, const float* attr,
+                      const float* dens, const F64Wgrad* wg) {
+    hipStream_t st = c->stream;
+    const double* w = ptr<double>(c->f64_w);
+    const int rows = bc * N, erows = rows * DRP_K, R_e = N * DRP_K;
+    const size_t pn = (size_t)rows, en = (size_t)erows;
+    const dim3 tblk(64 * KG_WAVES);
+    const dim3 pgrid((rows + 16 * KG_WAVES - 1) / (16 * KG_WAVES)), egrid((erows + 16 * KG_WAVES - 1) / (16 * KG_WAVES));
+    const F64Wgrad d = wg ? *wg : F64Wgrad{};           // the kernels' dump pointers: null without weight gradients
+    f64_reverse_lists(st, s.idx, s.cnt, N, bc, r.rev_off, r.rev);
+    const double* eff_last = s.eff + (size_t)(DRP_PSTEP - 1) * pn * 64;
+    hipLaunchKernelGGL(kg_predict_bwd, pgrid, tblk, 0, st, w, eff_last, g_out, rows, r.g_eff, d.pr_h, d.pr_gh);
+    if (wg) {
+        wg->narrow(g_out, 3, wg->pr_h, 64, N, W_PR1_W, W_PR1_B);
+        const Kt64Job j = wg->job(wg->pr_gh, nullptr, 1, N, W_PR0_B, -1, 64);
+        wg->block(j, eff_last, KT64_X_ROW, W_PR0_W, nullptr, nullptr);
+        wg->bias(j);
+    }
+    for (int p = DRP_PSTEP - 1; p >= 0; --p) {
+        const int first = p == DRP_PSTEP - 1;
+        const double* eff_prev = p == 0 ? s.pe : s.eff + (size_t)(p - 1) * pn * 64;
+        const double* erel_p = s.erel + (size_t)p * en * 64;
+        hipLaunchKernelGGL(kg_pprop_bwd, pgrid, tblk, 0, st, w, s.eff + (size_t)p * pn * 64, r.g_eff, rows, r.g_pre, r.g_agg, r.g_pe, first);
+        if (wg) {
+            const Kt64Job j = wg->job(r.g_pre, nullptr, 1, N, W_PP_B, W_PP_W + 128, 129);
+            wg->block(j, s.pe, KT64_X_ROW, W_PP_W, nullptr, nullptr);
+            wg->block(j, s.agg + (size_t)p * pn * 64, KT64_X_ROW, W_PP_W + 64, nullptr, nullptr);
+            wg->bias(j);
+        }
+        hipLaunchKernelGGL(kg_rprop_bwd, egrid, tblk, 0, st, w, erel_p, r.g_agg, erows, r.g_re, r.gr, r.gs, first);
+        if (wg) {
+            const Kt64Job j = wg->job(r.g_agg, erel_p, DRP_K, R_e, W_RP_B, W_RP_W + 192, 193);
+            wg->block(j, s.re, KT64_X_ROW, W_RP_W, s.idx, s.cnt);
+            wg->block(j, eff_prev, KT64_X_RECV, W_RP_W + 64, s.idx, s.cnt);
+            wg->block(j, eff_prev, KT64_X_SEND, W_RP_W + 128, s.idx, s.cnt);
+            wg->bias(j);
+        }
+        // effect_0 is the particle encoding itself: its gradient joins the propagators' (p == 0)
+        hipLaunchKernelGGL(kg_gather_bwd, dim3((unsigned)((pn * 64 + 255) / 256)), dim3(256), 0, st, r.g_pre, r.gr, r.gs, s.cnt, r.rev_off,
+                           r.rev, N, rows, p == 0 ? r.g_pe : (const double*)nullptr, r.g_eff);
+    }
+    hipLaunchKernelGGL(kg_pencode_bwd, pgrid, tblk, 0, st, w, s.sd, attr, dens, s.pe, r.g_eff, N, rows, r.g_sd, d.pe_in, d.pe_h, d.pe_gh);
+    if (wg) {
+        const Kt64Job j = wg->job(r.g_eff, s.pe, 1, N, W_PE2_B, -1, 64);
+        wg->block(j, wg->pe_h, KT64_X_ROW, W_PE2_W, nullptr, nullptr);
+        wg->bias(j);
+        wg->narrow(wg->pe_gh, 64, wg->pe_in, 5, N, W_PE0_W, W_PE0_B);
+    }
+    if (wg || t > 0)
+        hipLaunchKernelGGL(kg_rencode_bwd, egrid, tblk, 0, st, w, s.state, attr, dens, s.idx, s.cnt, s.re, r.g_re, N, erows, r.g_diff,
+                           d.re_in, d.re_h1, d.re_h2, d.re_g1, d.re_g2);
+    if (wg) {
+        const Kt64Job j4 = wg->job(r.g_re, s.re, 1, R_e, W_RE4_B, -1, 64);
+        wg->block(j4, wg->re_h2, KT64_X_ROW, W_RE4_W, nullptr, nullptr);
+        wg->bias(j4);
+        const Kt64Job j2 = wg->job(wg->re_g2, nullptr, 1, R_e, W_RE2_B, -1, 64);
+        wg->block(j2, wg->re_h1, KT64_X_ROW, W_RE2_W, nullptr, nullptr);
+        wg->bias(j2);
+        wg->narrow(wg->re_g1, 64, wg->re_in, 6, R_e, W_RE0_W, W_RE0_B);
+    }
+}
+
+// the state gradient of the samples [b0, b0 + bc): chunk layout [H][bc,N,3] -> caller layout [B,H,N,3]
+int f64_copy_state_grad(drp_ctx* c, const double* g_state, int b0, int bc, int N, int H, double* grad_state_out) {
+    const size_t row = (size_t)N * 3 * sizeof(double);
+    for (int t = 0; t < H; ++t)
+        HIPCHK(c, hipMemcpy2DAsync(grad_state_out + ((size_t)b0 * H + t) * N * 3, (size_t)H * row, g_state + (size_t)t * bc * N * 3, row,
+                                   row, bc, hipMemcpyDeviceToHost, c->stream));
+    return DRP_OK;
+}
+
+// ---- the planner's gradient ---------------------------------------------------------------------------------------------
+// a chunk's workspace: the shared parts, then the reward's scratch
+struct Gd64Ws {
+    F64Tape tape;
+    F64Rev rev;
+    double *px, *py, *gx, *gy, *r1t, *dist;
+    int* arg;
+    size_t carve(void* base, size_t bc, size_t N, size_t H, size_t M) {         // -> its bytes
+        F64Carver a{static_cast<char*>(base)};
+        const size_t pn = bc * N;
+        tape.carve(a, pn, H);
+        rev.carve(a, bc, N, H, pn * 4);
+        a.take(px, pn); a.take(py, pn); a.take(gx, pn); a.take(gy, pn); a.take(r1t, pn); a.take(dist, bc * M); a.take(arg, bc * M);
+        return a.off;
+    }
+};
+
+// forward with tape, reward, reverse pass of the rows [b0, b0 + bc): launches and the copies of its results
+int gd64_chunk(drp_ctx* c, const Gd64Ws& k, int b0, int bc, int nb, int N, int H, const float* s0, const float* attr_x,
+               const float* dens_x, const float* actions, double* rewards, double* g_act, double* grad_state_out) {
+    hipStream_t st = c->stream;
+    const size_t pn = (size_t)bc * N;
+    const float* attr = attr_x + (size_t)b0 * N;
+    const float* dens = dens_x + b0;
+    const float* act = actions + (size_t)b0 * H * 4;
+    hipLaunchKernelGGL(kg_init_state, dim3((unsigned)((pn * 3 + 255) / 256)), dim3(256), 0, st, s0, nb, b0, N, (long)(pn * 3), k.tape.state);
+    // ---- forward: gen_s_delta in double
+    CHK(f64_tape_forward(c, k.tape, bc, N, H, attr, dens, false, [&](int t, const F64Tape& s) {
+        hipLaunchKernelGGL(kg_sdelta, dim3(bc), dim3(256), 0, st, s.state, act + (size_t)t * 4, (size_t)H * 4, N, c->cam, s.sd,
+                           ptr<float>(c->s_in), ptr<float>(c->s_delta));
+    }));
+    // ---- reward of the final state and its gradient
+    hipLaunchKernelGGL(kg_reward, dim3(bc), dim3(256), 0, st, k.tape.state + (size_t)H * pn * 3, N, ptr<float>(c->goal_field), c->goal_h,
+                       c->goal_w, ptr<float>(c->goal_coor), c->goal_m, c->cam, k.px, k.py, k.gx, k.gy, k.r1t, k.dist, k.arg, rewards + b0,
+                       k.rev.g_state + (size_t)(H - 1) * pn * 3);
+    // ---- reverse pass, step by step; its tail: gen_s_delta backward and the step's share of d loss / d input state
+    for (int t = H - 1; t >= 0; --t) {
+        const F64Tape s = k.tape.step(t, pn);
+        const double* g_out = k.rev.g_state + (size_t)t * pn * 3;
+        f64_reverse_step(c, s, k.rev, g_out, t, bc, N, attr, dens, nullptr);
+        hipLaunchKernelGGL(kg_sdelta_bwd, dim3(bc), dim3(256), 0, st, s.state, act + (size_t)t * 4, (size_t)H * 4, k.rev.g_sd, g_out,
+                           k.rev.g_diff, s.cnt, k.rev.rev_off, k.rev.rev, N, c->cam, k.rev.part, g_act + (size_t)b0 * H * 4 + (size_t)t * 4,
+                           (size_t)H * 4, t > 0 ? k.rev.g_state + (size_t)(t - 1) * pn * 3 : (double*)nullptr);
+        HIPCHK(c, hipGetLastError());
+    }
+    if (grad_state_out) CHK(f64_copy_state_grad(c, k.rev.g_state, b0, bc, N, H, grad_state_out));
+    return DRP_OK;
+}
+
+// ---- the trainer's gradients --------------------------------------------------------------------------------------------
+// a chunk's workspace: the shared parts, then the weight gradients' operands and accumulators (wg's; the chunk fills in the rest)
+struct Tr64Ws {
+    F64Tape tape;
+    F64Rev rev;
+    F64Wgrad wg;
+    size_t carve(void* base, size_t bc, size_t N, size_t H) {                   // -> its bytes
+        F64Carver a{static_cast<char*>(base)};
+        const size_t pn = bc * N, en = pn * DRP_K;
+        tape.carve(a, pn, H);
+        rev.carve(a, bc, N, H, 0);
+        a.take(wg.pr_h, pn * 64); a.take(wg.pr_gh, pn * 64); a.take(wg.pe_h, pn * 64); a.take(wg.pe_gh, pn * 64); a.take(wg.pe_in, pn * 5);
+        a.take(wg.re_h1, en * 64); a.take(wg.re_h2, en * 64); a.take(wg.re_g1, en * 64); a.take(wg.re_g2, en * 64); a.take(wg.re_in, en * 6);
+        a.take(wg.acc, bc * (size_t)W_TOTAL);
+        return a.off;
+    }
+};
+
+// the batch on the device: the caller's arrays, a_cur = attrs[:, 0] gathered, then the results
+struct Tr64Io {
+    const float *states, *sdelta, *attr, *dens;
+    const int* nums;
+    double *terms, *total;          // [H][B], [W_TOTAL]
+};
+
+// forward with tape, loss, reverse pass with weight gradients of the samples [b0, b0 + bc): launches and the state gradient's copy
+int tr64_chunk(drp_ctx* c, const Tr64Ws& k, const Tr64Io& io, int b0, int bc, int N, int B, int H, double* grad_state_out) {
+    hipStream_t st = c->stream;
+    const size_t pn = (size_t)bc * N;
+    const dim3 lin3((unsigned)((pn * 3 + 255) / 256));
+    const float* attr = io.attr + (size_t)b0 * N;
+    const float* dens = io.dens + b0;
+    hipLaunchKernelGGL(kt64_init_state, lin3, dim3(256), 0, st, io.states, b0, N, H, (long)(pn * 3), k.tape.state);
+    // ---- forward: the impulse is data
+    CHK(f64_tape_forward(c, k.tape, bc, N, H, attr, dens, true, [&](int t, const F64Tape& s) {
+        hipLaunchKernelGGL(kt64_stage_step, lin3, dim3(256), 0, st, s.state, io.sdelta, b0, N, H, t, (long)(pn * 3), s.sd,
+                           ptr<float>(c->s_in), ptr<float>(c->s_delta));
+    }));
+    // ---- every step's loss term and its seed of the reverse pass; the samples' accumulators start at zero
+    hipLaunchKernelGGL(kt64_mse, dim3(bc, H), dim3(256), 0, st, k.tape.state, io.states, io.nums, b0, bc, B, N, H, io.terms, k.rev.g_state);
+    HIPCHK(c, hipMemsetAsync(k.wg.acc, 0, (size_t)bc * W_TOTAL * sizeof(double), st));
+    F64Wgrad wg = k.wg;
+    wg.st = st; wg.bc = bc; wg.N = N; wg.dens = dens;
+    // ---- reverse pass, step by step; its tail: the step's share of d loss / d input state on top of the loss's seed
+    for (int t = H - 1; t >= 0; --t) {
+        const F64Tape s = k.tape.step(t, pn);
+        const double* g_out = k.rev.g_state + (size_t)t * pn * 3;
+        f64_reverse_step(c, s, k.rev, g_out, t, bc, N, attr, dens, &wg);
+        if (t > 0)
+            hipLaunchKernelGGL(kt64_state_bwd, dim3((unsigned)((pn + 255) / 256)), dim3(256), 0, st, g_out, k.rev.g_diff, s.cnt,
+                               k.rev.rev_off, k.rev.rev, N, bc * N, k.rev.g_state + (size_t)(t - 1) * pn * 3);
+        HIPCHK(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(kt64_total, dim3((W_TOTAL + 255) / 256), dim3(256), 0, st, k.wg.acc, bc, io.total);
+    HIPCHK(c, hipGetLastError());
+    if (grad_state_out) CHK(f64_copy_state_grad(c, k.rev.g_state, b0, bc, N, H, grad_state_out));
+    return DRP_OK;
+}
+
+}  // namespace
+
+int drp_gd_grad_f64(drp_ctx* c, const float* s0, const float* attr, const float* dens, int nb, int N, const float* actions, int B,
+                    int H, double* rewards_out, double* grad_act_out, double* grad_state_out) {
+    CHK(need(c, true, true, true));
+    CHK(check_bn(c, B, N));
+    if (!s0 || !attr || !dens || !actions) return fail(c, DRP_EINVAL, "null argument");
+    if (H < 1 || H > 64) return fail(c, DRP_EINVAL, "bad horizon H=%d", H);
+    if (nb <= 0 || B % nb != 0) return fail(c, DRP_EINVAL, "B must be a multiple of n_batch");
+    HIPCHK(c, hipSetDevice(c->device));
+    F64Scope scope(c);
+    if (!c->f64_w_valid) CHK(f64_refresh_weights(c));
+    // rows per chunk: tape, reverse pass and reward scratch together
+    const size_t M = (size_t)c->goal_m;
+    Gd64Ws k{};
+    auto bytes_of = [&](size_t bc) { return k.carve(nullptr, bc, (size_t)N, (size_t)H, M); };
+    size_t Bc;
+    CHK(f64_size_chunks(c, B, N, ((size_t)1 << 24) / (size_t)N, bytes_of, &Bc));
+    k.carve(c->grad64_ws.p, Bc, (size_t)N, (size_t)H, M);
+    // the whole batch's inputs (attributes and densities per row: row = traj * nb + batch) and results
+    const size_t n_s0 = (size_t)nb * N * 3, n_attr = (size_t)B * N, n_act = (size_t)B * H * 4;
+    std::vector<float> host(n_s0 + n_attr + (size_t)B + n_act);
+    memcpy(host.data(), s0, n_s0 * sizeof(float));
+    for (int b = 0; b < B; ++b) {
+        memcpy(host.data() + n_s0 + (size_t)b * N, attr + (size_t)(b % nb) * N, (size_t)N * sizeof(float));
+        host[n_s0 + n_attr + b] = dens[b % nb];
+    }
+    memcpy(host.data() + n_s0 + n_attr + B, actions, n_act * sizeof(float));
+    double* d_rew;
+    CHK(f64_upload_batch(c, host, (size_t)B + n_act, &d_rew));
+    const float* d_in = ptr<float>(c->grad64_io);
+    double* d_gact = d_rew + B;
+    for (int b0 = 0; b0 < B; b0 += (int)Bc)
+        CHK(gd64_chunk(c, k, b0, std::min((int)Bc, B - b0), nb, N, H, d_in, d_in + n_s0, d_in + n_s0 + n_attr, d_in + n_s0 + n_attr + B,
+                       d_rew, d_gact, grad_state_out));
+    if (rewards_out) CHK(d2h(c, rewards_out, d_rew, (size_t)B * sizeof(double)));
+    if (grad_act_out) CHK(d2h(c, grad_act_out, d_gact, n_act * sizeof(double)));
+    return guarded_wait(c, nullptr);        // (the upload's host block lives until here)
+}
+
+int drp_train_grad_f64(drp_ctx* c, const float* states, const float* states_delta, const float* attrs, const int32_t* particle_nums,
+                       const float* particle_dens, int B, int N, int n_rollout, double* loss_out, double* loss_terms_out,
+                       double* grad_out, double* grad_state_out) {
+    CHK(need(c, true, false, false));
+    CHK(check_bn(c, B, N));
+    if (!states || !states_delta || !attrs || !particle_nums || !particle_dens) return fail(c, DRP_EINVAL, "null argument");
+    if (n_rollout < 1 || n_rollout > 64) return fail(c, DRP_EINVAL, "bad n_rollout=%d", n_rollout);
+    for (int b = 0; b < B; ++b)
+        if (particle_nums[b] <= 0 || particle_nums[b] > N)
+            return fail(c, DRP_EINVAL, "particle_nums[%d]=%d outside 1..%d", b, particle_nums[b], N);
+    HIPCHK(c, hipSetDevice(c->device));
+    F64Scope scope(c);
+    if (!c->f64_w_valid) CHK(f64_refresh_weights(c));
+    const int H = n_rollout;
+    // samples per chunk: tape, reverse pass, weight gradients' operands and accumulators together
+    Tr64Ws k{};
+    auto bytes_of = [&](size_t bc) { return k.carve(nullptr, bc, (size_t)N, (size_t)H); };
+    size_t Bc;
+    CHK(f64_size_chunks(c, B, N, ((size_t)1 << 24) / ((size_t)N * DRP_K), bytes_of, &Bc));
+    k.carve(c->grad64_ws.p, Bc, (size_t)N, (size_t)H);
+    // the whole batch's inputs in one upload: states | impulses | attrs[:, 0] | densities | particle counts, then the results
+    const size_t n_st = (size_t)B * (H + 1) * N * 3, n_sd = (size_t)B * H * N * 3, n_at = (size_t)B * N;
+    std::vector<float> host(n_st + n_sd + n_at + (size_t)B + (size_t)B);
+    memcpy(host.data(), states, n_st * sizeof(float));
+    memcpy(host.data() + n_st, states_delta, n_sd * sizeof(float));
+    for (int b = 0; b < B; ++b) memcpy(host.data() + n_st + n_sd + (size_t)b * N, attrs + (size_t)b * (H + 1) * N, (size_t)N * sizeof(float));
+    memcpy(host.data() + n_st + n_sd + n_at, particle_dens, (size_t)B * sizeof(float));
+    memcpy(host.data() + n_st + n_sd + n_at + B, particle_nums, (size_t)B * sizeof(int32_t));
+    const size_t n_terms = (size_t)H * B;
+    Tr64Io io{};
+    CHK(f64_upload_batch(c, host, n_terms + (size_t)W_TOTAL, &io.terms));
+    io.states = ptr<float>(c->grad64_io); io.sdelta = io.states + n_st; io.attr = io.sdelta + n_sd; io.dens = io.attr + n_at;
+    io.nums = reinterpret_cast<const int*>(io.dens + B);
+    io.total = io.terms + n_terms;
+    HIPCHK(c, hipMemsetAsync(io.total, 0, (size_t)W_TOTAL * sizeof(double), c->stream));
+    for (int b0 = 0; b0 < B; b0 += (int)Bc)
+        CHK(tr64_chunk(c, k, io, b0, std::min((int)Bc, B - b0), N, B, H, grad_state_out));
+    std::vector<double> terms(n_terms);
+    CHK(d2h(c, terms.data(), io.terms, n_terms * sizeof(double)));
+    if (grad_out) CHK(d2h(c, grad_out, io.total, (size_t)W_TOTAL * sizeof(double)));
+    CHK(guarded_wait(c, nullptr));          // (the upload's host block lives until here)
+    if (loss_terms_out) memcpy(loss_terms_out, terms.data(), n_terms * sizeof(double));
+    if (loss_out) {
+        double total = 0.0;                 // fixed order: step-major, then sample (as drp_train_step)
+        for (size_t q = 0; q < n_terms; ++q) total += terms[q];
+        *loss_out = total;
+    }
+    return DRP_OK;
+}

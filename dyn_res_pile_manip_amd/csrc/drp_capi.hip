@@ -66,8 +66,7 @@ extern "C" {
 #include "capi_rgr_train.h"
 #include "capi_ptcl_dataset.h"
 #include "capi_f64.h"
-#include "capi_gd_f64.h"
-#include "capi_train_f64.h"
+#include "capi_grad_f64.h"
 #include "capi_debug.h"
 
 }  // extern "C"

@@ -462,10 +462,25 @@ __global__ __launch_bounds__(64 * KG_WAVES) void kg_rencode_bwd(const double* __
     }
 }
 
+// ---- the step's d loss / d input state ------------------------------------------------------------------------------------
+// The relation encoder's share of component k of particle n of sample b, continuing the chain from v: plus g_diff [erows,3] of
+// the particle's own slots ascending, minus g_diff of the slots it is the sender of in the reversed lists' order.
+__device__ __forceinline__ double kg_state_share(double v, const double* __restrict__ g_diff, const uint8_t* __restrict__ cnt,
+                                                 const int* __restrict__ rev_off, const int* __restrict__ rev, int N, size_t b, int n,
+                                                 int k) {
+    const size_t i = b * N + n, e0 = b * N * DRP_K;
+    const int c = (int)cnt[i];
+    const int* ro = rev_off + b * (N + 1);
+    const int* rv = rev + e0;
+    for (int j = 0; j < c; ++j) v += g_diff[(i * DRP_K + j) * 3 + k];
+    for (int j = ro[n]; j < ro[n + 1]; ++j) v -= g_diff[(e0 + rv[j]) * 3 + k];
+    return v;
+}
+
 // ---- gen_s_delta backward and the step's d loss / d input state ---------------------------------------------------------
 // g_act[b, 0:4] = sum_n J_n^T g_sd[n] (particles ascending); g_prev[n] (nullable) = g_out[n] (the + s_cur of the output) + the
-// relation encoder's share (its own slots ascending, minus the slots it is the sender of in the reversed lists' order) +
-// gen_s_delta's dependence on the position.  One workgroup per row; part [rows*N,4]: scratch.
+// relation encoder's share (kg_state_share) + gen_s_delta's dependence on the position.  One workgroup per row; part
+// [rows*N,4]: scratch.
 __global__ __launch_bounds__(256) void kg_sdelta_bwd(const double* __restrict__ s, const float* __restrict__ act, size_t act_stride,
                                                      const double* __restrict__ g_sd, const double* __restrict__ g_out,
                                                      const double* __restrict__ g_diff, const uint8_t* __restrict__ cnt,
@@ -477,8 +492,6 @@ __global__ __launch_bounds__(256) void kg_sdelta_bwd(const double* __restrict__ 
 #pragma unroll
     for (int k = 0; k < 4; ++k) { a[k] = KgDual((double)act[b * act_stride + k]); a[k].d[k] = 1.0; }
     const KgFrame<KgDual> f = kg_frame<KgDual>(cam, a);
-    const int* ro = rev_off + (size_t)b * (N + 1);
-    const int* rv = rev + (size_t)b * N * DRP_K;
     for (int n = threadIdx.x; n < N; n += blockDim.x) {
         const size_t i = (size_t)b * N + n;
         KgDual p[3], out[3];
@@ -495,14 +508,9 @@ __global__ __launch_bounds__(256) void kg_sdelta_bwd(const double* __restrict__ 
 #pragma unroll
         for (int k = 0; k < 4; ++k) part[i * 4 + k] = g7[k];
         if (g_prev != nullptr) {
-            const int c = (int)cnt[i];
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                double v = g_out[i * 3 + k];
-                for (int j = 0; j < c; ++j) v += g_diff[(i * DRP_K + j) * 3 + k];
-                for (int j = ro[n]; j < ro[n + 1]; ++j) v -= g_diff[((size_t)b * N * DRP_K + rv[j]) * 3 + k];
-                g_prev[i * 3 + k] = v + g7[4 + k];
-            }
+            for (int k = 0; k < 3; ++k)
+                g_prev[i * 3 + k] = kg_state_share(g_out[i * 3 + k], g_diff, cnt, rev_off, rev, N, (size_t)b, n, k) + g7[4 + k];
         }
     }
     __syncthreads();

@@ -71,24 +71,18 @@ __global__ __launch_bounds__(256) void kt64_mse(const double* __restrict__ state
     }
 }
 
-// d loss / d s_pred_{t-1} += the step's share: the + s_cur of the output, then the relation encoder's (its own slots ascending,
-// minus the slots it is the sender of in the reversed lists' order).  g_prev holds the MSE's seed of step t - 1 when this runs.
+// d loss / d s_pred_{t-1} += the step's share: the + s_cur of the output, then the relation encoder's (kg_state_share).
+// g_prev holds the MSE's seed of step t - 1 when this runs.
 __global__ __launch_bounds__(256) void kt64_state_bwd(const double* __restrict__ g_out, const double* __restrict__ g_diff,
                                                       const uint8_t* __restrict__ cnt, const int* __restrict__ rev_off,
                                                       const int* __restrict__ rev, int N, int rows, double* __restrict__ g_prev) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= rows) return;
-    const long b = i / N, n = i - b * N;
-    const int c = (int)cnt[i];
-    const int* ro = rev_off + b * (N + 1);
-    const int* rv = rev + b * N * DRP_K;
+    const long b = i / N;
+    const int n = (int)(i - b * N);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        double v = g_prev[i * 3 + k] + g_out[i * 3 + k];
-        for (int j = 0; j < c; ++j) v += g_diff[((size_t)i * DRP_K + j) * 3 + k];
-        for (int j = ro[n]; j < ro[n + 1]; ++j) v -= g_diff[((size_t)b * N * DRP_K + rv[j]) * 3 + k];
-        g_prev[i * 3 + k] = v;
-    }
+    for (int k = 0; k < 3; ++k)
+        g_prev[i * 3 + k] = kg_state_share(g_prev[i * 3 + k] + g_out[i * 3 + k], g_diff, cnt, rev_off, rev, N, (size_t)b, n, k);
 }
 
 // ---- the operands of a 64-wide layer's weight gradient ------------------------------------------------------------------

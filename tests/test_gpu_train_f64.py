@@ -340,3 +340,38 @@ def test_the_trainers_probe_hook_changes_no_weight(golden):
     assert [h for h in res[2][0]['history'] if h[1] != 'grad_probe'] == res[0][0]['history']
     assert [ln for ln in lines[2] if not ln.startswith('grad_probe')] == lines[0]
     assert len([ln for ln in lines[2] if ln.startswith('grad_probe')]) == 2
+
+
+# ---- 8. the planner's float64 gradient shares this call's buffers -----------------------------------------------------
+def test_interleaved_with_gd_grad_f64_on_one_engine(golden):
+    """drp_gd_grad_f64 and drp_train_grad_f64 carve their workspaces from the same two buffers of the context: called in turn on
+    one engine, with shapes that make every call find the buffers as another layout left them, each result is the bits of the
+    same call on a fresh engine that has made no other float64 call"""
+    from test_gpu_gd_f64 import M34, CAM, args_of, synthetic_case
+    G = syn.goal_field(syn.goal_distance_image(syn.goal_mask('I')))
+    case = synthetic_case(17, 3, 2, seed=17)
+
+    def gd(e):
+        return e.gd_grad_f64(*args_of(case), want_state_grad=True)
+    calls = [gd, lambda e: e.train_grad_f64(*hand_made([5, 17, 16], 3), want_state=True), gd,
+             lambda e: e.train_grad_f64(*hand_made([33], 1), want_state=True)]
+
+    def engine():
+        e = new_engine(golden.weights_seed0)
+        e.set_camera(M34, 24.0, CAM)
+        e.set_goal(G, case['goal_coor'])
+        return e
+    shared = engine()
+    try:
+        for q, call in enumerate(calls):
+            got = call(shared)
+            fresh = engine()
+            try:
+                want = call(fresh)
+            finally:
+                fresh.close()
+            assert len(got) == len(want)
+            for a, b in zip(got, want):
+                np.testing.assert_array_equal(np.asarray(a), np.asarray(b), err_msg='call %d' % q)
+    finally:
+        shared.close()
