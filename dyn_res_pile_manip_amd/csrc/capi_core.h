@@ -158,13 +158,13 @@ int drp_gen_s_delta(drp_ctx* c, const float* s_cur, const float* action, int B, 
     if (!s_cur || !action || !out) return fail(c, DRP_EINVAL, "null buffer");
     HIPCHK(c, hipSetDevice(c->device));
     end_sessions(c);
-    CHK(h2d(c, c->s_in, s_cur, (size_t)B * N * 3 * sizeof(float)));
+    CHK(h2d(c, c->ws.s_in, s_cur, (size_t)B * N * 3 * sizeof(float)));
     CHK(h2d(c, c->actions, action, (size_t)B * 4 * sizeof(float)));
-    CHK(ensure(c, c->s_delta, (size_t)B * N * 3 * sizeof(float)));
-    hipLaunchKernelGGL(k_sdelta, dim3(B), dim3(256), 0, c->stream, ptr<float>(c->s_in),
-                       ptr<float>(c->actions), N, ptr<float>(c->s_delta), c->cam);
+    CHK(ensure(c, c->ws.s_delta, (size_t)B * N * 3 * sizeof(float)));
+    hipLaunchKernelGGL(k_sdelta, dim3(B), dim3(256), 0, c->stream, ptr<float>(c->ws.s_in),
+                       ptr<float>(c->actions), N, ptr<float>(c->ws.s_delta), c->cam);
     HIPCHK(c, hipGetLastError());
-    CHK(d2h(c, out, c->s_delta.p, (size_t)B * N * 3 * sizeof(float)));
+    CHK(d2h(c, out, c->ws.s_delta.p, (size_t)B * N * 3 * sizeof(float)));
     return drp_sync(c);
 }
 
@@ -175,19 +175,19 @@ int drp_build_graph(drp_ctx* c, const float* s_cur, const float* s_delta, int B,
     if (!s_cur || !s_delta || !nbr_idx_out || !nbr_cnt_out) return fail(c, DRP_EINVAL, "null buffer");
     HIPCHK(c, hipSetDevice(c->device));
     end_sessions(c);
-    CHK(ensure_step_ws(c, B, N));
-    CHK(h2d(c, c->s_in, s_cur, (size_t)B * N * 3 * sizeof(float)));
-    CHK(h2d(c, c->s_delta, s_delta, (size_t)B * N * 3 * sizeof(float)));
+    CHK(ensure_step_ws(c, c->ws, B, N));
+    CHK(h2d(c, c->ws.s_in, s_cur, (size_t)B * N * 3 * sizeof(float)));
+    CHK(h2d(c, c->ws.s_delta, s_delta, (size_t)B * N * 3 * sizeof(float)));
     {
     ProbeScope ps(c, KC_GRAPH);
     const GraphPlan g = plan_graph(c->pol, c->n_cu, c->engine, B, N, false, false, false, true);    // the lists alone: no launch to share
     c->dv(g.variant());
-    launch_graph(c, c->stream, g, ptr<float>(c->s_in), B, (size_t)N * 3, (const float*)nullptr, (size_t)0,
-                 ptr<float>(c->s_delta), B, N, ptr<int16_t>(c->nbr_idx), ptr<uint8_t>(c->nbr_cnt), 0);
+    launch_graph(c, c->stream, g, ptr<float>(c->ws.s_in), B, (size_t)N * 3, (const float*)nullptr, (size_t)0,
+                 ptr<float>(c->ws.s_delta), B, N, ptr<int16_t>(c->ws.nbr_idx), ptr<uint8_t>(c->ws.nbr_cnt), 0);
     }
     HIPCHK(c, hipGetLastError());
-    CHK(d2h(c, nbr_idx_out, c->nbr_idx.p, (size_t)B * N * DRP_K * sizeof(int16_t)));
-    CHK(d2h(c, nbr_cnt_out, c->nbr_cnt.p, (size_t)B * N));
+    CHK(d2h(c, nbr_idx_out, c->ws.nbr_idx.p, (size_t)B * N * DRP_K * sizeof(int16_t)));
+    CHK(d2h(c, nbr_cnt_out, c->ws.nbr_cnt.p, (size_t)B * N));
     return drp_sync(c);
 }
 
@@ -199,28 +199,28 @@ static int step_common(drp_ctx* c, const float* a_cur, const float* s_cur, const
     if (!a_cur || !s_cur || !s_delta || !dens || !s_pred_out) return fail(c, DRP_EINVAL, "null buffer");
     HIPCHK(c, hipSetDevice(c->device));
     end_sessions(c);
-    CHK(range_check(c, max_abs(a_cur, (size_t)B * N), max_abs(dens, (size_t)B), max_abs(s_delta, (size_t)B * N * 3)));
-    CHK(ensure_step_ws(c, B, N));
+    CHK(range_check(c, c->engine, max_abs(a_cur, (size_t)B * N), max_abs(dens, (size_t)B), max_abs(s_delta, (size_t)B * N * 3)));
+    CHK(ensure_step_ws(c, c->ws, B, N));
     const size_t bn = (size_t)B * N;
-    CHK(h2d(c, c->s_in, s_cur, bn * 3 * sizeof(float)));
-    CHK(h2d(c, c->s_delta, s_delta, bn * 3 * sizeof(float)));
-    CHK(h2d(c, c->attr, a_cur, bn * sizeof(float)));
-    CHK(h2d(c, c->dens, dens, (size_t)B * sizeof(float)));
-    CHK(ensure(c, c->s_out, bn * 3 * sizeof(float)));
+    CHK(h2d(c, c->ws.s_in, s_cur, bn * 3 * sizeof(float)));
+    CHK(h2d(c, c->ws.s_delta, s_delta, bn * 3 * sizeof(float)));
+    CHK(h2d(c, c->ws.attr, a_cur, bn * sizeof(float)));
+    CHK(h2d(c, c->ws.dens, dens, (size_t)B * sizeof(float)));
+    CHK(ensure(c, c->ws.s_out, bn * 3 * sizeof(float)));
     if (nbr_idx) {
-        CHK(h2d(c, c->nbr_idx, nbr_idx, bn * DRP_K * sizeof(int16_t)));
-        CHK(h2d(c, c->nbr_cnt, nbr_cnt, bn));
+        CHK(h2d(c, c->ws.nbr_idx, nbr_idx, bn * DRP_K * sizeof(int16_t)));
+        CHK(h2d(c, c->ws.nbr_cnt, nbr_cnt, bn));
     }
-    StepArgs a{};
-    a.s_prev = ptr<float>(c->s_in); a.prev_mod = B; a.prev_stride = (size_t)N * 3;
-    a.attr = ptr<float>(c->attr); a.attr_mod = B;
-    a.dens = ptr<float>(c->dens); a.dens_mod = B;
+    StepArgs a = step_args(c, c->engine);
+    a.s_prev = ptr<float>(c->ws.s_in); a.prev_mod = B; a.prev_stride = (size_t)N * 3;
+    a.attr = ptr<float>(c->ws.attr); a.attr_mod = B;
+    a.dens = ptr<float>(c->ws.dens); a.dens_mod = B;
     a.actions = nullptr; a.act_stride = 0;
     a.build_graph = (nbr_idx == nullptr);
-    a.s_out = ptr<float>(c->s_out); a.out_stride = (size_t)N * 3;
+    a.s_out = ptr<float>(c->ws.s_out); a.out_stride = (size_t)N * 3;
     a.B = B; a.N = N;
     CHK(run_step(c, a));
-    CHK(d2h(c, s_pred_out, c->s_out.p, bn * 3 * sizeof(float)));
+    CHK(d2h(c, s_pred_out, c->ws.s_out.p, bn * 3 * sizeof(float)));
     return drp_sync(c);
 }
 
@@ -245,10 +245,10 @@ int drp_rollout(drp_ctx* c, const float* s0, const float* attr, const float* den
         return fail(c, DRP_EINVAL, "bad rollout shape nb=%d B=%d H=%d (B must be a multiple of nb)", nb, B, H);
     HIPCHK(c, hipSetDevice(c->device));
     end_sessions(c);
-    CHK(range_check(c, max_abs(attr, (size_t)nb * N), max_abs(dens, (size_t)nb), push_len_bound(c, actions, (size_t)B * H)));
-    CHK(h2d(c, c->s_in, s0, (size_t)nb * N * 3 * sizeof(float)));
-    CHK(h2d(c, c->attr, attr, (size_t)nb * N * sizeof(float)));
-    CHK(h2d(c, c->dens, dens, (size_t)nb * sizeof(float)));
+    CHK(range_check(c, c->engine, max_abs(attr, (size_t)nb * N), max_abs(dens, (size_t)nb), push_len_bound(c, actions, (size_t)B * H)));
+    CHK(h2d(c, c->ws.s_in, s0, (size_t)nb * N * 3 * sizeof(float)));
+    CHK(h2d(c, c->ws.attr, attr, (size_t)nb * N * sizeof(float)));
+    CHK(h2d(c, c->ws.dens, dens, (size_t)nb * sizeof(float)));
     CHK(h2d(c, c->actions, actions, (size_t)B * H * 4 * sizeof(float)));
     CHK(run_rollout(c, nb, N, B, H, reward_out != nullptr, false));
     if (states_out) CHK(d2h(c, states_out, c->states.p, (size_t)B * H * N * 3 * sizeof(float)));
@@ -261,9 +261,9 @@ int drp_reward(drp_ctx* c, const float* state, int Bp, int N, int normalize, flo
     CHK(check_bn(c, Bp, N));
     if (!state || !reward_out) return fail(c, DRP_EINVAL, "null buffer");
     HIPCHK(c, hipSetDevice(c->device));
-    CHK(h2d(c, c->s_out, state, (size_t)Bp * N * 3 * sizeof(float)));
+    CHK(h2d(c, c->ws.s_out, state, (size_t)Bp * N * 3 * sizeof(float)));
     CHK(ensure(c, c->scratch, (size_t)Bp * sizeof(float)));
-    CHK(run_reward(c, ptr<float>(c->s_out), (size_t)N * 3, Bp, N, normalize, ptr<float>(c->scratch)));
+    CHK(run_reward(c, ptr<float>(c->ws.s_out), (size_t)N * 3, Bp, N, normalize, ptr<float>(c->scratch)));
     CHK(d2h(c, reward_out, c->scratch.p, (size_t)Bp * sizeof(float)));
     return drp_sync(c);
 }

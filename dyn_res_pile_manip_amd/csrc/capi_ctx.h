@@ -175,7 +175,20 @@ double now_s() {
 
 }  // namespace
 
-enum { F64_STAGE_BUFS = 14 };     // capi_f64.h: F64Scope
+// One step's workspace (run_step, launch_graph, the rollouts' rows): the staged inputs, the impulses, the neighbour lists, the
+// stage kernels' intermediates, the output.  A *_f64 call swaps the context's against one of its own (capi_f64.h: F64Scope).
+struct StepWs {
+    DevBuf s_in, attr, dens, s_delta, nbr_idx, nbr_cnt, eff, c_node, agg, proj, proj2, c_edge, s_out;
+    DevBuf ecache;                  // the edge-chain cache of the whole-sample kernels (dispatch.h: cut_blocks)
+};
+
+// What a step leaves behind on the host side (F64Scope saves and restores it by value)
+struct StepMarks {
+    int lastB = 0, lastN = 0, lastH = 0;            // last shapes (for debug fetch)
+    int probe_cls = -1;                             // the probed kernel class (drp_probe_begin)
+    unsigned deg_tick = 0;                          // note_degrees: every eighth launch refreshes deg_stat
+    unsigned char dv_hit[DV_COUNT] = {};            // kernel variants launched since drp_dispatch_reset (DispatchVariant)
+};
 
 struct drp_ctx {
     Stream stream;                  // declared first, so destroyed last: every buffer, pinned block and event below goes before it
@@ -192,9 +205,7 @@ struct drp_ctx {
     // the device writes; the plans take it decoded (deg()), as an input
     PinBuf deg_stat{hipHostMallocMapped};
     unsigned long long* deg_stat_dev = nullptr;     // the device's address of deg_stat
-    unsigned deg_tick = 0;
     DegStat deg() const { return deg_stat.p ? decode_deg_stat(*static_cast<volatile const unsigned long long*>(deg_stat.p)) : DegStat{}; }
-    DevBuf ecache;                  // the edge-chain cache of the whole-sample kernels (dispatch.h: cut_blocks)
 
     // model constants
     bool have_weights = false, have_cam = false, have_goal = false;
@@ -209,9 +220,10 @@ struct drp_ctx {
     unsigned cself_tag = 0;         // bumped by every prepare_cself: who filled c->cself last
     int goal_h = 0, goal_w = 0, goal_m = 0;
 
-    // workspaces
-    DevBuf s_in, attr, dens, s_delta, nbr_idx, nbr_cnt, eff, c_node, agg, proj, c_edge, states,
-        actions, rewards, s_out, scratch, proj2;
+    // workspaces: a step's engine and buffers are run_step's arguments (StepArgs); `ws` is what the selected engine's calls pass
+    StepWs ws;
+    StepMarks marks;
+    DevBuf states, actions, rewards, scratch;
 
     // MPC state
     bool mpc_on = false;
@@ -296,7 +308,7 @@ struct drp_ctx {
     DevBuf f64_w;                   // the blob widened [W_TOTAL], then its nine 64x64 blocks in MFMA fragment order, then in the transposed order (KF_W_ALL doubles)
     bool f64_w_valid = false;       // drp_load_weights refreshes it; an optimiser step on the device clears it, the next *_f64 call rebuilds
     size_t f64_cap = (size_t)256 << 20;     // bytes of float64 workspace a call may hold: the batch is walked in sample chunks under it
-    DevBuf f64_stage[F64_STAGE_BUFS];       // stand in for the step workspaces while a *_f64 call runs (capi_f64.h: F64Scope)
+    StepWs f64_ws;                  // stands in for `ws` while a *_f64 call runs (capi_f64.h: F64Scope)
     DevBuf f64_pe, f64_eff, f64_agg, f64_re, f64_erel, f64_pred, f64_out, f64_red;
     int f64_lastB = 0, f64_lastN = 0, f64_chunks = 0;       // of the last *_f64 call (drp_f64_tap)
     DevBuf grad64_ws, grad64_io;    // drp_gd_grad_f64 and drp_train_grad_f64 (capi_grad_f64.h; one-shots that keep nothing between calls): a chunk's tape
@@ -315,20 +327,14 @@ struct drp_ctx {
     std::vector<RolloutArgs> roll_args_host;
     bool roll_args_valid = false;
 
-    // last shapes (for debug fetch)
-    int lastB = 0, lastN = 0, lastH = 0;
-
-    // kernel variants launched since drp_dispatch_reset (DispatchVariant)
-    unsigned char dv_hit[DV_COUNT] = {};
-    void dv(int id) { dv_hit[id] = 1; }
+    void dv(int id) { marks.dv_hit[id] = 1; }
 
     // probe
     DevBuf probe_work;              // PROP_WORK_* counters of the propagation kernels while their class is probed
     bool probe_count = false;       // drp_probe_begin("prop+work"): the kernels count what they execute (not for timed regions: the
                                     // counting costs the 300-particle launch 8 %)
     bool work_lite = false, work_full = false;   // which term counts the counted launches ran with (drp_probe_work weighs the units by them)
-    unsigned long long* work_ptr() const { return (probe_cls == KC_PROP && probe_count) ? static_cast<unsigned long long*>(probe_work.p) : nullptr; }
-    int probe_cls = -1;
+    unsigned long long* work_ptr() const { return (marks.probe_cls == KC_PROP && probe_count) ? static_cast<unsigned long long*>(probe_work.p) : nullptr; }
     std::vector<Event> probe_ev;
     size_t probe_used = 0;
 };

@@ -31,7 +31,7 @@ int drp_debug_prop_span(drp_ctx* c, unsigned long long* out, int n) {
 
 int drp_probe_begin(drp_ctx* c, const char* kernel_class) {
     if (!c) return DRP_EINVAL;
-    c->probe_cls = -1;
+    c->marks.probe_cls = -1;
     c->probe_used = 0;
     c->probe_count = false;
     c->work_lite = c->work_full = false;
@@ -44,7 +44,7 @@ int drp_probe_begin(drp_ctx* c, const char* kernel_class) {
                 CHK(ensure(c, c->probe_work, PROP_WORK_SHARDS * PROP_WORK_STRIDE * sizeof(unsigned long long)));
                 HIPCHK(c, hipMemsetAsync(c->probe_work.p, 0, PROP_WORK_SHARDS * PROP_WORK_STRIDE * sizeof(unsigned long long), c->stream));
             }
-            c->probe_cls = i;
+            c->marks.probe_cls = i;
             return DRP_OK;
         }
     return fail(c, DRP_EINVAL, "unknown kernel class '%s'", kernel_class);
@@ -52,7 +52,7 @@ int drp_probe_begin(drp_ctx* c, const char* kernel_class) {
 
 int drp_probe_work(drp_ctx* c, unsigned long long out[8]) {
     if (!c || !out) return fail(c, DRP_EINVAL, "null argument");
-    if (c->probe_cls != KC_PROP || !c->probe_count || !c->probe_work.p) return fail(c, DRP_ESTATE, "drp_probe_begin(\"prop+work\") not running");
+    if (c->marks.probe_cls != KC_PROP || !c->probe_count || !c->probe_work.p) return fail(c, DRP_ESTATE, "drp_probe_begin(\"prop+work\") not running");
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<unsigned long long> sh((size_t)PROP_WORK_SHARDS * PROP_WORK_STRIDE);
     CHK(d2h(c, sh.data(), c->probe_work.p, sh.size() * sizeof(unsigned long long)));
@@ -104,7 +104,7 @@ __global__ void k_debug_stall(unsigned long long ticks) {
 
 int drp_dispatch_reset(drp_ctx* c) {
     if (!c) return DRP_EINVAL;
-    memset(c->dv_hit, 0, sizeof(c->dv_hit));
+    memset(c->marks.dv_hit, 0, sizeof(c->marks.dv_hit));
     return DRP_OK;
 }
 
@@ -124,7 +124,7 @@ static long dv_join(const unsigned char* hit, bool default_only, char* out, size
 
 long drp_last_dispatch(drp_ctx* c, char* out, size_t out_len) {
     if (!c) return DRP_EINVAL;
-    return dv_join(c->dv_hit, false, out, out_len);
+    return dv_join(c->marks.dv_hit, false, out, out_len);
 }
 
 long drp_dispatch_variants(int default_only, char* out, size_t out_len) { return dv_join(nullptr, default_only != 0, out, out_len); }
@@ -149,20 +149,20 @@ int drp_debug_stall(drp_ctx* c, int ms) {
 
 long drp_debug_fetch(drp_ctx* c, const char* name, void* out, size_t out_bytes) {
     if (!c || !name || !out) return DRP_EINVAL;
-    const size_t bn = (size_t)c->lastB * c->lastN;
+    const size_t bn = (size_t)c->marks.lastB * c->marks.lastN;
     const DevBuf* b = nullptr;
     bool part = false;              // fetch `view` (a part of a buffer, not owned; view_cap bytes from there on) instead of *b
     const void* view = nullptr;
     size_t view_cap = 0;
     size_t bytes = 0;
-    if (!strcmp(name, "s_delta")) { b = &c->s_delta; bytes = bn * 3 * 4; }
-    else if (!strcmp(name, "nbr_idx")) { b = &c->nbr_idx; bytes = bn * DRP_K * 2; }
-    else if (!strcmp(name, "nbr_cnt")) { b = &c->nbr_cnt; bytes = bn; }
-    else if (!strcmp(name, "effect")) { b = &c->eff; bytes = bn * 64 * 4; }
-    else if (!strcmp(name, "c_node")) { b = &c->c_node; bytes = bn * 64 * 4; }
-    else if (!strcmp(name, "c_edge")) { b = &c->c_edge; bytes = bn * DRP_K * 64 * 4; }
-    else if (!strcmp(name, "proj")) { b = &c->proj; bytes = bn * 128 * 4; }
-    else if (!strcmp(name, "agg")) { b = &c->agg; bytes = bn * 64 * 4; }
+    if (!strcmp(name, "s_delta")) { b = &c->ws.s_delta; bytes = bn * 3 * 4; }
+    else if (!strcmp(name, "nbr_idx")) { b = &c->ws.nbr_idx; bytes = bn * DRP_K * 2; }
+    else if (!strcmp(name, "nbr_cnt")) { b = &c->ws.nbr_cnt; bytes = bn; }
+    else if (!strcmp(name, "effect")) { b = &c->ws.eff; bytes = bn * 64 * 4; }
+    else if (!strcmp(name, "c_node")) { b = &c->ws.c_node; bytes = bn * 64 * 4; }
+    else if (!strcmp(name, "c_edge")) { b = &c->ws.c_edge; bytes = bn * DRP_K * 64 * 4; }
+    else if (!strcmp(name, "proj")) { b = &c->ws.proj; bytes = bn * 128 * 4; }
+    else if (!strcmp(name, "agg")) { b = &c->ws.agg; bytes = bn * 64 * 4; }
     else if (!strcmp(name, "stats")) { b = &c->stats; bytes = 8 * sizeof(double); }
     // the blob and its packed copies (tests: the device re-pack after an optimiser step against the host packers)
     else if (!strcmp(name, "w_raw")) { b = &c->w_raw; bytes = (size_t)W_TOTAL * 4; }
@@ -172,7 +172,7 @@ long drp_debug_fetch(drp_ctx* c, const char* name, void* out, size_t out_bytes) 
     else if (!strcmp(name, "w_split")) { b = &c->w_split; bytes = (size_t)S_ALLOC * 16; }
     else if (!strcmp(name, "w_split6")) { b = &c->w_split6; bytes = (size_t)S6_TOTAL * 16; }
     else if (!strcmp(name, "w_split6_bwd")) { b = &c->w_split6_bwd; bytes = (size_t)SB6_TOTAL * 16; }
-    else if (!strcmp(name, "rev_off")) { b = &c->rev_off; bytes = (size_t)c->lastB * (c->lastN + 1) * 4; }
+    else if (!strcmp(name, "rev_off")) { b = &c->rev_off; bytes = (size_t)c->marks.lastB * (c->marks.lastN + 1) * 4; }
     else if (!strcmp(name, "rev")) { b = &c->rev; bytes = bn * DRP_K * 4; }
     // the resolution regressor's post-activation taps of its last forward (NHWC [B][H][W][C] for the convolutions)
     else if (!strncmp(name, "rgr_c", 5) && name[5] >= '1' && name[5] <= '5' && !name[6]) {
@@ -191,9 +191,9 @@ long drp_debug_fetch(drp_ctx* c, const char* name, void* out, size_t out_bytes) 
     // a GD session keeps every step's impulses and lists in its tape, not in the step workspace: the last step's
     if (c->gd_on && c->gd_H > 0 && bn == (size_t)c->gd_B * c->gd_N) {
         const size_t t = (size_t)c->gd_H - 1;
-        if (b == &c->s_delta) { part = true; view = ptr<float>(c->tape_sdelta) + t * bn * 3; view_cap = bytes; }
-        else if (b == &c->nbr_idx) { part = true; view = ptr<int16_t>(c->tape_idx) + t * bn * DRP_K; view_cap = bytes; }
-        else if (b == &c->nbr_cnt) { part = true; view = ptr<uint8_t>(c->tape_cnt) + t * bn; view_cap = bytes; }
+        if (b == &c->ws.s_delta) { part = true; view = ptr<float>(c->tape_sdelta) + t * bn * 3; view_cap = bytes; }
+        else if (b == &c->ws.nbr_idx) { part = true; view = ptr<int16_t>(c->tape_idx) + t * bn * DRP_K; view_cap = bytes; }
+        else if (b == &c->ws.nbr_cnt) { part = true; view = ptr<uint8_t>(c->tape_cnt) + t * bn; view_cap = bytes; }
     }
     const void* src = part ? view : b->p;
     const size_t cap = part ? view_cap : b->cap;

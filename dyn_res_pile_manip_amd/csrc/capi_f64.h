@@ -4,32 +4,24 @@
 
 namespace {
 
-// While a *_f64 call runs, the step workspaces the one-shot entry points stage their inputs in (and run_step / launch_graph
-// work in) are the surface's OWN buffers: the context's are swapped out and come back untouched when the scope ends, so a
-// planner session whose state lives in them goes on as if nothing had happened.  The same holds for what a step leaves behind
-// on the host side: the engine choice, the dispatch marks, the shapes of the last call, the probed class, the degree statistic.
+// While a *_f64 call runs, the step workspace the one-shot entry points stage their inputs in (and run_step / launch_graph
+// work in) is the surface's OWN (c->f64_ws): the context's is swapped out whole and comes back untouched when the scope ends, so
+// a planner session whose state lives in it goes on as if nothing had happened.  The same holds for what a step leaves behind
+// on the host side (StepMarks: the dispatch marks, the shapes of the last call, the probed class) and the degree statistic.
 struct F64Scope {
     drp_ctx* c;
-    int engine, lastB, lastN, lastH, probe_cls;
-    unsigned deg_tick;
+    StepMarks marks;
     unsigned long long deg_val = 0;
-    unsigned char dv_hit[DV_COUNT];
-    DevBuf* slot[F64_STAGE_BUFS];
-    explicit F64Scope(drp_ctx* ctx) : c(ctx), engine(ctx->engine), lastB(ctx->lastB), lastN(ctx->lastN), lastH(ctx->lastH),
-                                      probe_cls(ctx->probe_cls), deg_tick(ctx->deg_tick) {
-        DevBuf* const s[F64_STAGE_BUFS] = {&c->s_in, &c->attr, &c->dens, &c->s_delta, &c->nbr_idx, &c->nbr_cnt, &c->eff, &c->c_node,
-                                           &c->agg, &c->proj, &c->proj2, &c->c_edge, &c->s_out, &c->ecache};
-        memcpy(dv_hit, c->dv_hit, sizeof(dv_hit));
+    explicit F64Scope(drp_ctx* ctx) : c(ctx), marks(ctx->marks) {
         if (c->deg_stat.p) deg_val = *ptr<volatile unsigned long long>(c->deg_stat);
-        c->probe_cls = -1;
-        for (int i = 0; i < F64_STAGE_BUFS; ++i) { slot[i] = s[i]; std::swap(*slot[i], c->f64_stage[i]); }
+        c->marks.probe_cls = -1;
+        std::swap(c->ws, c->f64_ws);
     }
     ~F64Scope() {
         (void)guarded_wait(c, nullptr);         // nothing of this call is in flight when the buffers change hands again
-        for (int i = 0; i < F64_STAGE_BUFS; ++i) std::swap(*slot[i], c->f64_stage[i]);
+        std::swap(c->ws, c->f64_ws);
         if (c->deg_stat.p) *ptr<volatile unsigned long long>(c->deg_stat) = deg_val;
-        memcpy(c->dv_hit, dv_hit, sizeof(dv_hit));
-        c->engine = engine; c->lastB = lastB; c->lastN = lastN; c->lastH = lastH; c->probe_cls = probe_cls; c->deg_tick = deg_tick;
+        c->marks = marks;
     }
 };
 
@@ -44,19 +36,19 @@ int f64_check_inputs(drp_ctx* c, const float* a_cur, const float* s_cur, const f
 // the four inputs into the (scope's) step workspaces, as step_common stages them
 int f64_upload(drp_ctx* c, const float* a_cur, const float* s_cur, const float* s_delta, const float* dens, int B, int N, int engine) {
     const size_t bn = (size_t)B * N;
-    CHK(ensure_step_ws(c, B, N, engine));
-    CHK(h2d(c, c->s_in, s_cur, bn * 3 * sizeof(float)));
-    CHK(h2d(c, c->s_delta, s_delta, bn * 3 * sizeof(float)));
-    CHK(h2d(c, c->attr, a_cur, bn * sizeof(float)));
-    CHK(h2d(c, c->dens, dens, (size_t)B * sizeof(float)));
+    CHK(ensure_step_ws(c, c->ws, B, N, engine));
+    CHK(h2d(c, c->ws.s_in, s_cur, bn * 3 * sizeof(float)));
+    CHK(h2d(c, c->ws.s_delta, s_delta, bn * 3 * sizeof(float)));
+    CHK(h2d(c, c->ws.attr, a_cur, bn * sizeof(float)));
+    CHK(h2d(c, c->ws.dens, dens, (size_t)B * sizeof(float)));
     return DRP_OK;
 }
 
 // the library's own fp32 graph build on the staged inputs (as drp_build_graph): lists into the workspace
 int f64_build_lists(drp_ctx* c, int B, int N) {
     const GraphPlan g = plan_graph(c->pol, c->n_cu, c->engine, B, N, false, false, false, true);
-    launch_graph(c, c->stream, g, ptr<float>(c->s_in), B, (size_t)N * 3, (const float*)nullptr, (size_t)0, ptr<float>(c->s_delta), B, N,
-                 ptr<int16_t>(c->nbr_idx), ptr<uint8_t>(c->nbr_cnt), 0);
+    launch_graph(c, c->stream, g, ptr<float>(c->ws.s_in), B, (size_t)N * 3, (const float*)nullptr, (size_t)0, ptr<float>(c->ws.s_delta), B, N,
+                 ptr<int16_t>(c->ws.nbr_idx), ptr<uint8_t>(c->ws.nbr_cnt), 0);
     HIPCHK(c, hipGetLastError());
     return DRP_OK;
 }
@@ -105,12 +97,12 @@ int f64_forward_dev(drp_ctx* c, int B, int N) {
         const int bc = std::min(Bc, B - b0);
         const int rows = bc * N;
         const size_t ro = (size_t)b0 * N;
-        const float* s_cur = ptr<float>(c->s_in) + ro * 3;
-        const float* s_delta = ptr<float>(c->s_delta) + ro * 3;
-        const float* attr = ptr<float>(c->attr) + ro;
-        const float* dens = ptr<float>(c->dens) + b0;
-        const int16_t* idx = ptr<int16_t>(c->nbr_idx) + ro * DRP_K;
-        const uint8_t* cnt = ptr<uint8_t>(c->nbr_cnt) + ro;
+        const float* s_cur = ptr<float>(c->ws.s_in) + ro * 3;
+        const float* s_delta = ptr<float>(c->ws.s_delta) + ro * 3;
+        const float* attr = ptr<float>(c->ws.attr) + ro;
+        const float* dens = ptr<float>(c->ws.dens) + b0;
+        const int16_t* idx = ptr<int16_t>(c->ws.nbr_idx) + ro * DRP_K;
+        const uint8_t* cnt = ptr<uint8_t>(c->ws.nbr_cnt) + ro;
         f64_launch_step<float>(c, w, s_cur, s_delta, attr, dens, idx, cnt, N, rows, ptr<double>(c->f64_pe), ptr<double>(c->f64_re),
                                ptr<double>(c->f64_eff), ptr<double>(c->f64_agg), ptr<double>(c->f64_erel), ptr<double>(c->f64_pred),
                                ptr<double>(c->f64_out) + ro * 3);
@@ -140,8 +132,8 @@ int drp_forward_f64(drp_ctx* c, const float* a_cur, const float* s_cur, const fl
     }
     F64Scope scope(c);
     CHK(f64_upload(c, a_cur, s_cur, s_delta, dens, B, N, -1));
-    CHK(h2d(c, c->nbr_idx, nbr_idx, bn * DRP_K * sizeof(int16_t)));
-    CHK(h2d(c, c->nbr_cnt, nbr_cnt, bn));
+    CHK(h2d(c, c->ws.nbr_idx, nbr_idx, bn * DRP_K * sizeof(int16_t)));
+    CHK(h2d(c, c->ws.nbr_cnt, nbr_cnt, bn));
     CHK(f64_forward_dev(c, B, N));
     return f64_finish(c, B, N, s_pred_out);
 }
@@ -201,20 +193,19 @@ int drp_accuracy_probe(drp_ctx* c, int engine, const float* a_cur, const float* 
     if (engine != DRP_ENGINE_VALU && engine != DRP_ENGINE_MFMA && engine != DRP_ENGINE_SPLIT && engine != DRP_ENGINE_FUSED &&
         engine != DRP_ENGINE_LITE)
         return fail(c, DRP_EINVAL, "engine %d not available in this build", engine);
-    F64Scope scope(c);              // restores the selected engine, too
-    c->engine = engine;
+    F64Scope scope(c);
     // drp_step's path on that engine: the range check, the lists from the graph build, the step
-    CHK(range_check(c, max_abs(a_cur, (size_t)B * N), max_abs(dens, (size_t)B), max_abs(s_delta, (size_t)B * N * 3)));
+    CHK(range_check(c, engine, max_abs(a_cur, (size_t)B * N), max_abs(dens, (size_t)B), max_abs(s_delta, (size_t)B * N * 3)));
     CHK(f64_upload(c, a_cur, s_cur, s_delta, dens, B, N, engine));
     const size_t bn = (size_t)B * N;
-    CHK(ensure(c, c->s_out, bn * 3 * sizeof(float)));
-    StepArgs a{};
-    a.s_prev = ptr<float>(c->s_in); a.prev_mod = B; a.prev_stride = (size_t)N * 3;
-    a.attr = ptr<float>(c->attr); a.attr_mod = B;
-    a.dens = ptr<float>(c->dens); a.dens_mod = B;
+    CHK(ensure(c, c->ws.s_out, bn * 3 * sizeof(float)));
+    StepArgs a = step_args(c, engine);
+    a.s_prev = ptr<float>(c->ws.s_in); a.prev_mod = B; a.prev_stride = (size_t)N * 3;
+    a.attr = ptr<float>(c->ws.attr); a.attr_mod = B;
+    a.dens = ptr<float>(c->ws.dens); a.dens_mod = B;
     a.actions = nullptr; a.act_stride = 0;
     a.build_graph = true;
-    a.s_out = ptr<float>(c->s_out); a.out_stride = (size_t)N * 3;
+    a.s_out = ptr<float>(c->ws.s_out); a.out_stride = (size_t)N * 3;
     a.B = B; a.N = N;
     CHK(run_step(c, a));
     // the float64 evaluation on the same inputs and the lists that step built
@@ -225,8 +216,8 @@ int drp_accuracy_probe(drp_ctx* c, int engine, const float* a_cur, const float* 
     double* part = ptr<double>(c->f64_red);
     double* res = part + (size_t)parts * 3;
     for (int phase = 0; phase < 2; ++phase)
-        hipLaunchKernelGGL(kf_probe_reduce, dim3(phase == 0 ? parts : 1), dim3(KF_RED_THREADS), 0, c->stream, ptr<float>(c->s_out),
-                           ptr<double>(c->f64_out), ptr<float>(c->s_in), (long)bn, per, part, parts, res, phase);
+        hipLaunchKernelGGL(kf_probe_reduce, dim3(phase == 0 ? parts : 1), dim3(KF_RED_THREADS), 0, c->stream, ptr<float>(c->ws.s_out),
+                           ptr<double>(c->f64_out), ptr<float>(c->ws.s_in), (long)bn, per, part, parts, res, phase);
     HIPCHK(c, hipGetLastError());
     CHK(d2h(c, out, res, 4 * sizeof(double)));
     return guarded_wait(c, nullptr);

@@ -11,7 +11,7 @@ void launch_edge_encode_mfma(drp_ctx* c, const float* s_prev, int prev_mod, size
     const long ntiles = (long)B * (((long)N * DRP_K + 31) / 32);
     const unsigned grid = (unsigned)(ntiles < (long)c->n_cu ? ntiles : (long)c->n_cu);
     hipLaunchKernelGGL(kmb_edge_encode, dim3(grid), dim3(64 * MFMA_WAVES), KMB_EDGE_ENCODE_LDS, c->stream, ptr<float>(c->w_mfma),
-                       ptr<float>(c->w_mfma_bwd), s_prev, prev_mod, prev_stride, ptr<float>(c->attr), nb, ptr<float>(c->dens), nb, idx,
+                       ptr<float>(c->w_mfma_bwd), s_prev, prev_mod, prev_stride, ptr<float>(c->ws.attr), nb, ptr<float>(c->ws.dens), nb, idx,
                        cnt, gah, mht, bn, N, B, gpos_edge, dump);
 }
 int gd_forward_backward(drp_ctx* c) {
@@ -35,7 +35,7 @@ int gd_forward_backward(drp_ctx* c) {
     bool rev_built = false;
     {
         TapeFwd f{};
-        f.s0 = ptr<float>(c->s_in); f.s0_mod = nb; f.s0_stride = (size_t)N * 3;
+        f.s0 = ptr<float>(c->ws.s_in); f.s0_mod = nb; f.s0_stride = (size_t)N * 3;
         f.mod = nb;
         f.actions = ptr<float>(c->actions);
         f.tape = true;
@@ -53,7 +53,7 @@ int gd_forward_backward(drp_ctx* c) {
                            1, g_state + (size_t)(H - 1) * bn * 3, (size_t)N * 3, ptr<float>(c->rewards), c->gd_host_rewards);
     }
     for (int t = H - 1; t >= 0; --t) {
-        const float* s_prev = (t == 0) ? ptr<float>(c->s_in) : states + (size_t)(t - 1) * N * 3;
+        const float* s_prev = (t == 0) ? ptr<float>(c->ws.s_in) : states + (size_t)(t - 1) * N * 3;
         const int prev_mod = (t == 0) ? nb : B;
         const size_t prev_stride = (t == 0) ? (size_t)N * 3 : hstride;
         const int16_t* idx = ptr<int16_t>(c->tape_idx) + (size_t)t * bn * DRP_K;
@@ -78,14 +78,14 @@ int gd_forward_backward(drp_ctx* c) {
             hipLaunchKernelGGL(kmb_rows_bwd, dim3((unsigned)k.grid), dim3(64 * KMB_FUSED_WAVES),
                                KMB_ROWS_LDS, st, ptr<float>(c->w_mfma), ptr<float>(c->w_mfma_bwd), ptr<uint16_t>(c->w_split6),
                                ptr<uint16_t>(c->w_split6_bwd), s.eht, s.mht, s.cnt, s.rev_off, s.rev, g_out, (size_t)N * 3, s.sdelta,
-                               ptr<float>(c->attr), nb, ptr<float>(c->dens), nb, N, B, k.gps, t > 0 ? s.gah : (float*)nullptr,
+                               ptr<float>(c->ws.attr), nb, ptr<float>(c->ws.dens), nb, N, B, k.gps, t > 0 ? s.gah : (float*)nullptr,
                                ptr<float>(c->g_sdelta));
         } else if (k.kind == BwdPlan::STEP) {
             ProbeScope ps(c, KC_BWD_NODE);
             hipLaunchKernelGGL((kmb_step_bwd<false, false>), dim3((unsigned)k.grid), dim3(64 * KMB_FUSED_WAVES), KMB_FUSED_LDS, st,
                                ptr<float>(c->w_mfma), ptr<float>(c->w_mfma_bwd), s.eht, s.mht, s.cnt, s.rev_off, s.rev,
-                               g_out, (size_t)N * 3, s.sdelta, ptr<float>(c->attr), nb,
-                               ptr<float>(c->dens), nb, N, B, k.spw, s.ge_tmp, s.g_cnode, s.gah,
+                               g_out, (size_t)N * 3, s.sdelta, ptr<float>(c->ws.attr), nb,
+                               ptr<float>(c->ws.dens), nb, N, B, k.spw, s.ge_tmp, s.g_cnode, s.gah,
                                ptr<float>(c->g_sdelta), KmbDump{}, 1, (unsigned*)nullptr, (unsigned*)nullptr);
         } else {
             launch_node_stages(c, s, dim3(B), 1, nullptr);
@@ -130,11 +130,11 @@ int drp_gd_begin(drp_ctx* c, const float* s0, const float* attr, const float* de
                              fmaxf(push_len_bound(c, box, 2), push_len_bound(c, actions, (size_t)B * H)), &c->gd_engine));
     }
     const size_t bn = (size_t)B * N;
-    CHK(h2d(c, c->s_in, s0, (size_t)nb * N * 3 * sizeof(float)));
-    CHK(h2d(c, c->attr, attr, (size_t)nb * N * sizeof(float)));
-    CHK(h2d(c, c->dens, dens, (size_t)nb * sizeof(float)));
+    CHK(h2d(c, c->ws.s_in, s0, (size_t)nb * N * 3 * sizeof(float)));
+    CHK(h2d(c, c->ws.attr, attr, (size_t)nb * N * sizeof(float)));
+    CHK(h2d(c, c->ws.dens, dens, (size_t)nb * sizeof(float)));
     CHK(h2d(c, c->actions, actions, (size_t)B * H * 4 * sizeof(float)));
-    CHK(ensure_step_ws(c, B, N, c->gd_engine));
+    CHK(ensure_step_ws(c, c->ws, B, N, c->gd_engine));
     CHK(ensure(c, c->states, (size_t)H * bn * 3 * sizeof(float)));
     CHK(ensure(c, c->rewards, (size_t)B * sizeof(float)));
     CHK(ensure_tape(c, B, N, H, 1));
@@ -153,7 +153,7 @@ int drp_gd_begin(drp_ctx* c, const float* s0, const float* attr, const float* de
     c->gd_cself_tag = 0;
     memcpy(c->gd_lo, act_lo, 4 * sizeof(float));
     memcpy(c->gd_hi, act_hi, 4 * sizeof(float));
-    c->lastH = H;
+    c->marks.lastH = H;
     c->gd_on = true;
     c->mpc_on = false;
     return DRP_OK;

@@ -58,8 +58,8 @@ extern "C++" template <typename F> int f64_size_chunks(drp_ctx* c, int B, int N,
     size_t Bc = std::min<size_t>({(size_t)B, std::max<size_t>(1, c->f64_cap / bytes_of(1)), std::max<size_t>(1, row_limit)});
     while (Bc > 1 && bytes_of(Bc) > c->f64_cap) --Bc;
     CHK(ensure(c, c->grad64_ws, bytes_of(Bc)));
-    CHK(ensure_step_ws(c, (int)Bc, N, -1));
-    CHK(ensure(c, c->s_in, Bc * N * 3 * sizeof(float)));
+    CHK(ensure_step_ws(c, c->ws, (int)Bc, N, -1));
+    CHK(ensure(c, c->ws.s_in, Bc * N * 3 * sizeof(float)));
     *chunk = Bc;
     return DRP_OK;
 }
@@ -84,7 +84,7 @@ int f64_tape_forward(drp_ctx* c, const F64Tape& tape, int bc, int N, int H, cons
         const F64Tape s = tape.step(t, (size_t)rows);
         stage(t, s);
         const GraphPlan g = plan_graph(c->pol, c->n_cu, c->engine, bc, N, padded, false, false, true);
-        launch_graph(c, c->stream, g, ptr<float>(c->s_in), bc, (size_t)N * 3, (const float*)nullptr, (size_t)0, ptr<float>(c->s_delta),
+        launch_graph(c, c->stream, g, ptr<float>(c->ws.s_in), bc, (size_t)N * 3, (const float*)nullptr, (size_t)0, ptr<float>(c->ws.s_delta),
                      bc, N, s.idx, s.cnt, 0);
         f64_launch_step<double>(c, ptr<double>(c->f64_w), s.state, s.sd, attr, dens, s.idx, s.cnt, N, rows, s.pe, s.re, s.eff, s.agg,
                                 s.erel, s.pred, s.state + (size_t)rows * 3);
@@ -234,7 +234,7 @@ int gd64_chunk(drp_ctx* c, const Gd64Ws& k, int b0, int bc, int nb, int N, int H
     // ---- forward: gen_s_delta in double
     CHK(f64_tape_forward(c, k.tape, bc, N, H, attr, dens, false, [&](int t, const F64Tape& s) {
         hipLaunchKernelGGL(kg_sdelta, dim3(bc), dim3(256), 0, st, s.state, act + (size_t)t * 4, (size_t)H * 4, N, c->cam, s.sd,
-                           ptr<float>(c->s_in), ptr<float>(c->s_delta));
+                           ptr<float>(c->ws.s_in), ptr<float>(c->ws.s_delta));
     }));
     // ---- reward of the final state and its gradient
     hipLaunchKernelGGL(kg_reward, dim3(bc), dim3(256), 0, st, k.tape.state + (size_t)H * pn * 3, N, ptr<float>(c->goal_field), c->goal_h,
@@ -290,7 +290,7 @@ int tr64_chunk(drp_ctx* c, const Tr64Ws& k, const Tr64Io& io, int b0, int bc, in
     // ---- forward: the impulse is data
     CHK(f64_tape_forward(c, k.tape, bc, N, H, attr, dens, true, [&](int t, const F64Tape& s) {
         hipLaunchKernelGGL(kt64_stage_step, lin3, dim3(256), 0, st, s.state, io.sdelta, b0, N, H, t, (long)(pn * 3), s.sd,
-                           ptr<float>(c->s_in), ptr<float>(c->s_delta));
+                           ptr<float>(c->ws.s_in), ptr<float>(c->ws.s_delta));
     }));
     // ---- every step's loss term and its seed of the reverse pass; the samples' accumulators start at zero
     hipLaunchKernelGGL(kt64_mse, dim3(bc, H), dim3(256), 0, st, k.tape.state, io.states, io.nums, b0, bc, B, N, H, io.terms, k.rev.g_state);

@@ -19,18 +19,18 @@ int drp_mpc_begin(drp_ctx* c, const drp_mpc_params* p, const float* s0, const fl
                               p->act_hi[0], p->act_hi[1], p->act_lo[2], p->act_lo[3]};
         c->sess_attr_max = max_abs(attr, (size_t)nb * N);
         c->sess_dens_max = max_abs(dens, (size_t)nb);
-        CHK(range_check(c, c->sess_attr_max, c->sess_dens_max, push_len_bound(c, box, 2)));
+        CHK(range_check(c, c->engine, c->sess_attr_max, c->sess_dens_max, push_len_bound(c, box, 2)));
     }
     c->mpc = *p;
-    CHK(h2d(c, c->s_in, s0, (size_t)nb * N * 3 * sizeof(float)));
-    CHK(h2d(c, c->attr, attr, (size_t)nb * N * sizeof(float)));
-    CHK(h2d(c, c->dens, dens, (size_t)nb * sizeof(float)));
+    CHK(h2d(c, c->ws.s_in, s0, (size_t)nb * N * 3 * sizeof(float)));
+    CHK(h2d(c, c->ws.attr, attr, (size_t)nb * N * sizeof(float)));
+    CHK(h2d(c, c->ws.dens, dens, (size_t)nb * sizeof(float)));
     CHK(h2d(c, c->nominal, nominal, (size_t)H * 4 * sizeof(double)));
     CHK(ensure(c, c->actions, (size_t)B * H * 4 * sizeof(float)));
     CHK(ensure(c, c->partials, (size_t)(6 + 4 * H) * sizeof(double)));
     CHK(ensure(c, c->gathered, (size_t)(6 + 4 * H) * sizeof(double) * (size_t)(c->n_ranks > 0 ? c->n_ranks : 1)));
     CHK(ensure(c, c->stats, 8 * sizeof(double)));
-    CHK(ensure_step_ws(c, B, N));
+    CHK(ensure_step_ws(c, c->ws, B, N));
     CHK(ensure(c, c->states, (size_t)B * H * N * 3 * sizeof(float)));
     CHK(ensure(c, c->rewards, (size_t)B * H * sizeof(float)));
     CHK(ensure(c, c->scratch, (size_t)B * sizeof(float)));
@@ -66,7 +66,7 @@ int drp_mpc_set_actions(drp_ctx* c, const float* actions) {
     HIPCHK(c, hipSetDevice(c->device));
     if (!actions) return fail(c, DRP_EINVAL, "null actions");
     const drp_mpc_params& p = c->mpc;
-    CHK(range_check(c, c->sess_attr_max, c->sess_dens_max,
+    CHK(range_check(c, c->engine, c->sess_attr_max, c->sess_dens_max,
                     push_len_bound(c, actions, (size_t)p.n_sample * p.n_batch * p.n_look_ahead)));
     CHK(h2d(c, c->actions, actions, (size_t)p.n_sample * p.n_batch * p.n_look_ahead * 4 * sizeof(float)));
     return DRP_OK;

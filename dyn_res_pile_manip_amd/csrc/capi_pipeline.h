@@ -169,7 +169,7 @@ int guarded_wait(drp_ctx* c, hipEvent_t ev) {
 struct ProbeScope {
     drp_ctx* c;
     bool on;
-    ProbeScope(drp_ctx* ctx, int cls) : c(ctx), on(ctx->probe_cls == cls) {
+    ProbeScope(drp_ctx* ctx, int cls) : c(ctx), on(ctx->marks.probe_cls == cls) {
         if (on) rec();
     }
     ~ProbeScope() {
@@ -185,32 +185,33 @@ struct ProbeScope {
     }
 };
 
-int ensure_step_ws(drp_ctx* c, int B, int N, int engine = -1) {
+int ensure_step_ws(drp_ctx* c, StepWs& ws, int B, int N, int engine = -1) {
     if (engine < 0) engine = c->engine;
+    // (ws.s_in, ws.attr, ws.dens and ws.s_out grow with the upload that fills them, ws.ecache with the plan that wants it)
     const size_t bn = (size_t)B * N;
-    CHK(ensure(c, c->s_delta, bn * 3 * sizeof(float)));
-    CHK(ensure(c, c->nbr_idx, bn * DRP_K * sizeof(int16_t)));
-    CHK(ensure(c, c->nbr_cnt, bn));
-    CHK(ensure(c, c->eff, bn * 64 * sizeof(float)));
-    CHK(ensure(c, c->c_node, bn * 64 * sizeof(float)));
-    CHK(ensure(c, c->agg, bn * 64 * sizeof(float)));
-    CHK(ensure(c, c->proj, bn * 128 * sizeof(float)));
-    CHK(ensure(c, c->proj2, bn * 128 * sizeof(float)));
+    CHK(ensure(c, ws.s_delta, bn * 3 * sizeof(float)));
+    CHK(ensure(c, ws.nbr_idx, bn * DRP_K * sizeof(int16_t)));
+    CHK(ensure(c, ws.nbr_cnt, bn));
+    CHK(ensure(c, ws.eff, bn * 64 * sizeof(float)));
+    CHK(ensure(c, ws.c_node, bn * 64 * sizeof(float)));
+    CHK(ensure(c, ws.agg, bn * 64 * sizeof(float)));
+    CHK(ensure(c, ws.proj, bn * 128 * sizeof(float)));
+    CHK(ensure(c, ws.proj2, bn * 128 * sizeof(float)));
     // edge constants [B,N,10,64] for the engines that materialise them; the fused engine only parks the graph build's
     // sorted positions and strip starts there (launch_graph)
     const size_t graph_scratch = (size_t)B * (((size_t)N + 3) & ~(size_t)3) * 16 + (size_t)B * (GC_MAX_BANDS * GC_XS + 1) * sizeof(int);
-    CHK(ensure(c, c->c_edge, engine_is_fused(engine) ? graph_scratch : std::max(graph_scratch, bn * DRP_K * 64 * sizeof(float))));
-    c->lastB = B;
-    c->lastN = N;
+    CHK(ensure(c, ws.c_edge, engine_is_fused(engine) ? graph_scratch : std::max(graph_scratch, bn * DRP_K * 64 * sizeof(float))));
+    c->marks.lastB = B;
+    c->marks.lastN = N;
     return DRP_OK;
 }
 
 // Every few launches whose pairing depends on it (dispatch.h: PairRule), the mean in-degree of the lists just built goes to host
 // memory behind the launch: the next launches of this shape read it there, without waiting for anything.
-static void note_degrees(drp_ctx* c, long spw, long N, long B) {
+static void note_degrees(drp_ctx* c, const uint8_t* nbr_cnt, long spw, long N, long B) {
     const long rows = spw * N;
     if (rows > c->pol.prop_pair_rows || rows <= c->pol.prop_pair_always) return;
-    if ((c->deg_tick++ & 7u) != 0) return;
+    if ((c->marks.deg_tick++ & 7u) != 0) return;
     if (!c->deg_stat.p) {                       // mapped (its flags): the device writes it, the host reads it; without it the plans see no degree
         if (ensure_pinned(c, c->deg_stat, sizeof(unsigned long long)) != DRP_OK) {
             (void)hipGetLastError();
@@ -223,7 +224,7 @@ static void note_degrees(drp_ctx* c, long spw, long N, long B) {
             return;
         }
     }
-    hipLaunchKernelGGL(k_deg_stat, dim3(1), dim3(1024), 0, c->stream, ptr<uint8_t>(c->nbr_cnt),
+    hipLaunchKernelGGL(k_deg_stat, dim3(1), dim3(1024), 0, c->stream, nbr_cnt,
                        (int)std::min(B * N, (long)DEG_STAT_MAX_ROWS), (int)N, c->deg_stat_dev);
 }
 
@@ -235,6 +236,8 @@ struct StepArgs {
     bool build_graph;                                         // false: nbr lists already in workspace
     float* s_out; size_t out_stride;
     int B, N;
+    int engine;                                               // which engine runs the step
+    float* s_delta; int16_t* nbr_idx; uint8_t* nbr_cnt;       // where the step's impulses and neighbour lists are (or go)
     // tape for the backward pass (fused engine only, km_prop<., TAPE>):
     float* eff_hist = nullptr;      // [4][B*N*64]: effect after the encoder and after every propagation step
     unsigned* mask_hist = nullptr;  // [3][B*N*10][2]: ReLU masks of the relation effects of every propagation step
@@ -246,6 +249,12 @@ struct StepArgs {
     int* rev = nullptr;             //   (k_graph_rev); run_step says in rev_built whether it did
     bool* rev_built = nullptr;
 };
+// a step on the selected engine whose impulses and lists are the context's workspace (sized before: ensure_step_ws)
+StepArgs step_args(const drp_ctx* c, int engine) {
+    StepArgs a{};
+    a.engine = engine; a.s_delta = ptr<float>(c->ws.s_delta); a.nbr_idx = ptr<int16_t>(c->ws.nbr_idx); a.nbr_cnt = ptr<uint8_t>(c->ws.nbr_cnt);
+    return a;
+}
 
 // neighbour lists as planned (plan_graph): cells, x strips, four threads per receiver, or the plain sweep; the two builds
 // that share their launch with something else (k_graph_rev, km_graph_q4_encode) are run_step's
@@ -254,7 +263,7 @@ void launch_graph(drp_ctx* c, hipStream_t st, const GraphPlan& g, const float* s
                   int self_first) {
     // sorted positions and strip / cell starts live in the edge-constant buffer: whatever uses it runs after the lists exist
     const size_t Np = ((size_t)N + 3) & ~(size_t)3;
-    float4* sorted = reinterpret_cast<float4*>(c->c_edge.p);
+    float4* sorted = reinterpret_cast<float4*>(c->ws.c_edge.p);
     int* starts = reinterpret_cast<int*>(sorted + (size_t)B * Np);
     const dim3 grid((unsigned)g.grid);
     switch (g.kind) {
@@ -290,16 +299,14 @@ void launch_graph(drp_ctx* c, hipStream_t st, const GraphPlan& g, const float* s
     }
 }
 
-void launch_aggregate(drp_ctx* c, const AggPlan& g, int B, int N) {
+void launch_aggregate(drp_ctx* c, const AggPlan& g, const int16_t* nbr_idx, const uint8_t* nbr_cnt, int B, int N) {
     ProbeScope ps(c, KC_AGGREGATE);
     if (g.lds)
         hipLaunchKernelGGL(k_aggregate_lds, dim3(B), dim3(512), (size_t)N * 256, c->stream,
-                           ptr<float>(c->c_edge), ptr<float>(c->proj), ptr<int16_t>(c->nbr_idx),
-                           ptr<uint8_t>(c->nbr_cnt), N, ptr<float>(c->agg));
+                           ptr<float>(c->ws.c_edge), ptr<float>(c->ws.proj), nbr_idx, nbr_cnt, N, ptr<float>(c->ws.agg));
     else
-        hipLaunchKernelGGL(k_aggregate, dim3(B * g.chunks), dim3(256), 0, c->stream, ptr<float>(c->c_edge),
-                           ptr<float>(c->proj), ptr<int16_t>(c->nbr_idx), ptr<uint8_t>(c->nbr_cnt), N,
-                           ptr<float>(c->agg), g.chunks);
+        hipLaunchKernelGGL(k_aggregate, dim3(B * g.chunks), dim3(256), 0, c->stream, ptr<float>(c->ws.c_edge),
+                           ptr<float>(c->ws.proj), nbr_idx, nbr_cnt, N, ptr<float>(c->ws.agg), g.chunks);
 }
 
 // kernels whose tile loop is workgroup-cyclic first (tile = block + grid x (wave + 8 round)): one workgroup per tile up to the chip
@@ -378,7 +385,7 @@ bool prop_tables_ready() {
 
 StepShape step_shape(const drp_ctx* c, const StepArgs& a) {
     StepShape s;
-    s.engine = c->engine; s.B = a.B; s.N = a.N;
+    s.engine = a.engine; s.B = a.B; s.N = a.N;
     s.tape = a.eff_hist != nullptr;
     s.prev_mod = a.prev_mod; s.attr_mod = a.attr_mod; s.dens_mod = a.dens_mod;
     s.work = c->work_ptr() != nullptr;
@@ -400,24 +407,24 @@ int run_step_mfma(drp_ctx* c, const StepArgs& a, const StepPlan& k) {
     // the tape of the reverse-mode kernels: km_prop<., TAPE> on the fused engine; on the fp32 matrix engine (what the
     // gradient-descent planner and the trainer fall back to when the split-fp16 relation encoder refuses the weights or the
     // inputs) the stage kernels run as always and the tape is copied / written beside them (tape_mfma below)
-    if (tape && c->engine != DRP_ENGINE_FUSED && c->engine != DRP_ENGINE_MFMA)       // (run_tape_forward lends the context one of the two)
+    if (tape && a.engine != DRP_ENGINE_FUSED && a.engine != DRP_ENGINE_MFMA)       // (run_tape_forward passes one of the two)
         return fail(c, DRP_ESTATE, "the backward tape is written by the fused or the fp32 matrix engine");
-    float* eff0 = (tape && !k.tape_mfma) ? a.eff_hist : ptr<float>(c->eff);
+    float* eff0 = (tape && !k.tape_mfma) ? a.eff_hist : ptr<float>(c->ws.eff);
     if (k.node_encode) {
         ProbeScope ps(c, KC_NODE_ENCODE);
         if (k.fused)
             hipLaunchKernelGGL(k.lite ? km_node_encode_split<true> : km_node_encode_split<false>, dim3(mfma_grid_spread(c, node_tiles)), blk, KM_NODE_SPLIT_LDS, st,
-                               ptr<uint16_t>(c->w_split6), mw, ptr<float>(c->s_delta), a.attr, a.attr_mod, a.dens,
-                               a.dens_mod, N, B, eff0, ptr<float>(c->c_node), ptr<float>(c->proj));
+                               ptr<uint16_t>(c->w_split6), mw, a.s_delta, a.attr, a.attr_mod, a.dens,
+                               a.dens_mod, N, B, eff0, ptr<float>(c->ws.c_node), ptr<float>(c->ws.proj));
         else
             hipLaunchKernelGGL(km_node_encode, dim3(mfma_grid(c, node_tiles)), blk, KM_NODE_LDS, st, mw,
-                               ptr<float>(c->s_delta), a.attr, a.attr_mod, a.dens, a.dens_mod, N, B,
-                               ptr<float>(c->eff), ptr<float>(c->c_node), ptr<float>(c->proj));
+                               a.s_delta, a.attr, a.attr_mod, a.dens, a.dens_mod, N, B,
+                               ptr<float>(c->ws.eff), ptr<float>(c->ws.c_node), ptr<float>(c->ws.proj));
     }
     if (k.fused) {
         // the relation encoder is recomputed inside the propagation kernels and c_edge is never materialised
-        float* pa = ptr<float>(c->proj);
-        float* pb = ptr<float>(c->proj2);
+        float* pa = ptr<float>(c->ws.proj);
+        float* pb = ptr<float>(c->ws.proj2);
         unsigned long long* const wk = c->work_ptr();    // not null: the counting instantiations (drp_probe_begin("prop+work"))
         if (wk) (k.lite ? c->work_lite : c->work_full) = true;
         const dim3 pblk(64 * PROP_WAVES);
@@ -426,29 +433,29 @@ int run_step_mfma(drp_ctx* c, const StepArgs& a, const StepPlan& k) {
             // out for the whole batch, a block starts `ro` rows into every slot and the kernel takes the slots' stride as an
             // argument (hist_rows)
             ProbeScope ps(c, KC_PROP);
-            if (k.blocks.cache) CHK(ensure(c, c->ecache, k.blocks.cache_bytes));
-            note_degrees(c, k.spw, N, B);
+            if (k.blocks.cache) CHK(ensure(c, c->ws.ecache, k.blocks.cache_bytes));
+            note_degrees(c, a.nbr_cnt, k.spw, N, B);
             for (int q = 0; q < k.blocks.n; ++q) {
                 const Block b = k.blocks.block(q);
                 // the block's view of every per-sample buffer: inputs replicated over the batch columns (row b reads column
                 // b % mod) keep their base -- a block starts at a multiple of mod --, everything indexed by the row moves on
                 const size_t ro = (size_t)b.b_off * N;
                 const bool own_prev = a.prev_mod >= B, own_attr = a.attr_mod >= B, own_dens = a.dens_mod >= B;
-                if (b.cache_bytes > c->ecache.cap) CHK(ensure(c, c->ecache, b.cache_bytes));
+                if (b.cache_bytes > c->ws.ecache.cap) CHK(ensure(c, c->ws.ecache, b.cache_bytes));
                 hipLaunchKernelGGL(prop_tables().of(k.prop3_flags(b)), dim3((unsigned)b.grid), pblk, KM_PROP3_LDS, st,
                                    ptr<uint16_t>(c->w_split), ptr<uint16_t>(c->w_split6), mw,
                                    own_prev ? a.s_prev + (size_t)b.b_off * a.prev_stride : a.s_prev, own_prev ? b.Bc : a.prev_mod, a.prev_stride,
                                    own_attr ? a.attr + ro : a.attr, own_attr ? b.Bc : a.attr_mod,
                                    own_dens ? a.dens + b.b_off : a.dens, own_dens ? b.Bc : a.dens_mod,
-                                   ptr<int16_t>(c->nbr_idx) + ro * DRP_K, ptr<uint8_t>(c->nbr_cnt) + ro, pa + ro * 128, pb + ro * 128,
-                                   ptr<float>(c->c_node) + ro * 64, (tape ? a.eff_hist : ptr<float>(c->eff)) + ro * 64, N, b.Bc, b.spw,
-                                   k.phase_e ? (const float*)(ptr<float>(c->s_delta) + ro * 3) : (const float*)nullptr,
+                                   a.nbr_idx + ro * DRP_K, a.nbr_cnt + ro, pa + ro * 128, pb + ro * 128,
+                                   ptr<float>(c->ws.c_node) + ro * 64, (tape ? a.eff_hist : ptr<float>(c->ws.eff)) + ro * 64, N, b.Bc, b.spw,
+                                   k.phase_e ? (const float*)(a.s_delta + ro * 3) : (const float*)nullptr,
                                    a.s_out + (size_t)b.b_off * a.out_stride, a.out_stride,
                                    a.cself ? a.cself + (size_t)b.b_off * 64 : (const float*)nullptr,
                                    a.cself_ok ? a.cself_ok + b.b_off : (const uint8_t*)nullptr,
                                    tape ? a.mask_hist + ro * DRP_K * 2 : (unsigned*)nullptr,
                                    (tape && a.agg_hist) ? a.agg_hist + ro * 64 : (float*)nullptr, c->re_scale, c->re_inv,
-                                   (c->pol.prop3_order ? 1 : 0), ptr<float4>(c->ecache), b.ec_stride, wk, tape ? (size_t)B * N : (size_t)0);
+                                   (c->pol.prop3_order ? 1 : 0), ptr<float4>(c->ws.ecache), b.ec_stride, wk, tape ? (size_t)B * N : (size_t)0);
             }
         }
         for (int p = 0; p < DRP_PSTEP && !k.prop3; ++p) {
@@ -456,9 +463,9 @@ int run_step_mfma(drp_ctx* c, const StepArgs& a, const StepPlan& k) {
             ProbeScope ps(c, KC_PROP);
             hipLaunchKernelGGL(prop_tables().of(k.prop_flags(last)), dim3((unsigned)k.grid), pblk, KM_PROP_LDS(last), st,
                                ptr<uint16_t>(c->w_split), ptr<uint16_t>(c->w_split6), mw, a.s_prev, a.prev_mod, a.prev_stride,
-                               a.attr, a.attr_mod, a.dens, a.dens_mod, ptr<int16_t>(c->nbr_idx), ptr<uint8_t>(c->nbr_cnt), pa,
-                               ptr<float>(c->c_node), tape ? a.eff_hist + (size_t)p * bn64 : ptr<float>(c->eff),
-                               tape ? a.eff_hist + (size_t)(p + 1) * bn64 : ptr<float>(c->eff), N, B, pb, a.s_out, a.out_stride, a.cself, a.cself_ok,
+                               a.attr, a.attr_mod, a.dens, a.dens_mod, a.nbr_idx, a.nbr_cnt, pa,
+                               ptr<float>(c->ws.c_node), tape ? a.eff_hist + (size_t)p * bn64 : ptr<float>(c->ws.eff),
+                               tape ? a.eff_hist + (size_t)(p + 1) * bn64 : ptr<float>(c->ws.eff), N, B, pb, a.s_out, a.out_stride, a.cself, a.cself_ok,
                                tape ? a.mask_hist + (size_t)p * B * N * DRP_K * 2 : (unsigned*)nullptr,
                                (tape && a.agg_hist) ? a.agg_hist + (size_t)p * bn64 : (float*)nullptr,
                                c->re_scale, c->re_inv, k.spread, wk);
@@ -471,40 +478,40 @@ int run_step_mfma(drp_ctx* c, const StepArgs& a, const StepPlan& k) {
         if (k.split_encoders)
             hipLaunchKernelGGL(km_edge_encode_split, dim3(mfma_grid(c, edge_tiles)), blk, KM_EDGE_SPLIT_LDS, st,
                                ptr<uint16_t>(c->w_split), mw, a.s_prev, a.prev_mod, a.prev_stride, a.attr,
-                               a.attr_mod, a.dens, a.dens_mod, ptr<int16_t>(c->nbr_idx),
-                               ptr<uint8_t>(c->nbr_cnt), N, B, ptr<float>(c->c_edge), c->re_scale, c->re_inv);
+                               a.attr_mod, a.dens, a.dens_mod, a.nbr_idx,
+                               a.nbr_cnt, N, B, ptr<float>(c->ws.c_edge), c->re_scale, c->re_inv);
         else
             hipLaunchKernelGGL(km_edge_encode, dim3(mfma_grid(c, edge_tiles)), blk, KM_EDGE_LDS, st, mw,
                                a.s_prev, a.prev_mod, a.prev_stride, a.attr, a.attr_mod, a.dens, a.dens_mod,
-                               ptr<int16_t>(c->nbr_idx), ptr<uint8_t>(c->nbr_cnt), N, B, ptr<float>(c->c_edge));
+                               a.nbr_idx, a.nbr_cnt, N, B, ptr<float>(c->ws.c_edge));
     }
-    if (k.tape_mfma) HIPCHK(c, hipMemcpyAsync(a.eff_hist, c->eff.p, bn64 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (k.tape_mfma) HIPCHK(c, hipMemcpyAsync(a.eff_hist, c->ws.eff.p, bn64 * sizeof(float), hipMemcpyDeviceToDevice, st));
     for (int p = 0; p < DRP_PSTEP; ++p) {
         if (k.tape_mfma) {
             // the aggregate that also leaves the edges' ReLU bits; the aggregated rows and the effects are copied into the tape
             ProbeScope pa(c, KC_AGGREGATE);
-            hipLaunchKernelGGL(k_aggregate_tape, dim3(B * k.agg.chunks), dim3(256), 0, st, ptr<float>(c->c_edge), ptr<float>(c->proj),
-                               ptr<int16_t>(c->nbr_idx), ptr<uint8_t>(c->nbr_cnt), N, ptr<float>(c->agg), k.agg.chunks,
+            hipLaunchKernelGGL(k_aggregate_tape, dim3(B * k.agg.chunks), dim3(256), 0, st, ptr<float>(c->ws.c_edge), ptr<float>(c->ws.proj),
+                               a.nbr_idx, a.nbr_cnt, N, ptr<float>(c->ws.agg), k.agg.chunks,
                                a.mask_hist + (size_t)p * B * N * DRP_K * 2);
             if (a.agg_hist)
-                HIPCHK(c, hipMemcpyAsync(a.agg_hist + (size_t)p * bn64, c->agg.p, bn64 * sizeof(float), hipMemcpyDeviceToDevice, st));
+                HIPCHK(c, hipMemcpyAsync(a.agg_hist + (size_t)p * bn64, c->ws.agg.p, bn64 * sizeof(float), hipMemcpyDeviceToDevice, st));
         } else {
-            launch_aggregate(c, k.agg, B, N);
+            launch_aggregate(c, k.agg, a.nbr_idx, a.nbr_cnt, B, N);
         }
         {
         ProbeScope ps(c, p + 1 < DRP_PSTEP ? KC_UPDATE : KC_PREDICT);
         if (p + 1 < DRP_PSTEP)
             hipLaunchKernelGGL(km_update<false>, dim3(mfma_grid(c, node_tiles)), blk, KM_UPD_LDS, st, mw,
-                               ptr<float>(c->agg), ptr<float>(c->c_node), ptr<float>(c->eff), N, B,
-                               ptr<float>(c->proj), a.s_prev, a.prev_mod, a.prev_stride, a.s_out, a.out_stride);
+                               ptr<float>(c->ws.agg), ptr<float>(c->ws.c_node), ptr<float>(c->ws.eff), N, B,
+                               ptr<float>(c->ws.proj), a.s_prev, a.prev_mod, a.prev_stride, a.s_out, a.out_stride);
         else
             hipLaunchKernelGGL(km_update<true>, dim3(mfma_grid(c, node_tiles)), blk, KM_UPD_LDS, st, mw,
-                               ptr<float>(c->agg), ptr<float>(c->c_node), ptr<float>(c->eff), N, B,
-                               ptr<float>(c->proj), a.s_prev, a.prev_mod, a.prev_stride, a.s_out, a.out_stride);
+                               ptr<float>(c->ws.agg), ptr<float>(c->ws.c_node), ptr<float>(c->ws.eff), N, B,
+                               ptr<float>(c->ws.proj), a.s_prev, a.prev_mod, a.prev_stride, a.s_out, a.out_stride);
         }
         // the step's effect is the next tape entry (km_update keeps it in place, the last step's too)
         if (k.tape_mfma)
-            HIPCHK(c, hipMemcpyAsync(a.eff_hist + (size_t)(p + 1) * bn64, c->eff.p, bn64 * sizeof(float), hipMemcpyDeviceToDevice, st));
+            HIPCHK(c, hipMemcpyAsync(a.eff_hist + (size_t)(p + 1) * bn64, c->ws.eff.p, bn64 * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
     return DRP_OK;
 }
@@ -514,15 +521,15 @@ int run_step_mfma(drp_ctx* c, const StepArgs& a, const StepPlan& k) {
 int run_step(drp_ctx* c, const StepArgs& a) {
     const int B = a.B, N = a.N;
     hipStream_t st = c->stream;
-    float* s_delta = ptr<float>(c->s_delta);
-    int16_t* nbr_idx = ptr<int16_t>(c->nbr_idx);
-    uint8_t* nbr_cnt = ptr<uint8_t>(c->nbr_cnt);
+    float* s_delta = a.s_delta;
+    int16_t* nbr_idx = a.nbr_idx;
+    uint8_t* nbr_cnt = a.nbr_cnt;
     const float* vw = ptr<float>(c->w_valu);
     const StepPlan k = plan_step(c->pol, c->n_cu, step_shape(c, a));
-    k.mark(c->dv_hit);
+    k.mark(c->marks.dv_hit);
     if (a.build_graph) {
         ProbeScope ps(c, KC_GRAPH);
-        const int self_first = (engine_is_fused(c->engine) && a.cself != nullptr) ? 1 : 0;
+        const int self_first = (engine_is_fused(a.engine) && a.cself != nullptr) ? 1 : 0;
         switch (k.graph.kind) {
         case GraphPlan::REV:
             // the GD planner's forward, samples of one graph chunk: the reversed lists in the lists' own launch
@@ -537,14 +544,14 @@ int run_step(drp_ctx* c, const StepArgs& a) {
             hipLaunchKernelGGL(k.graph.lite ? km_graph_q4_encode<true> : km_graph_q4_encode<false>, dim3((unsigned)(k.graph.grid + mfma_grid_spread(c, (long)B * ((N + 31) / 32)))), dim3(GRAPH_Q4_THREADS),
                                KM_GRAPH_Q4_ENCODE_LDS(N), st, a.s_prev, a.prev_mod, a.prev_stride, s_delta, N, B, nbr_idx, nbr_cnt, c->cam,
                                c->thr, k.graph.chunks, self_first, (int)k.graph.grid, ptr<uint16_t>(c->w_split6), ptr<float>(c->w_mfma), a.attr, a.attr_mod,
-                               a.dens, a.dens_mod, k.tape ? a.eff_hist : ptr<float>(c->eff), ptr<float>(c->c_node), ptr<float>(c->proj));
+                               a.dens, a.dens_mod, k.tape ? a.eff_hist : ptr<float>(c->ws.eff), ptr<float>(c->ws.c_node), ptr<float>(c->ws.proj));
             break;
         default:
             launch_graph(c, st, k.graph, a.s_prev, a.prev_mod, a.prev_stride, a.actions, a.act_stride, s_delta, B, N, nbr_idx, nbr_cnt, self_first);
             break;
         }
     }
-    if (c->engine != DRP_ENGINE_VALU) {
+    if (a.engine != DRP_ENGINE_VALU) {
         int rc = run_step_mfma(c, a, k);
         if (rc != DRP_OK) return rc;
         HIPCHK(c, hipGetLastError());
@@ -553,30 +560,30 @@ int run_step(drp_ctx* c, const StepArgs& a) {
     {
         ProbeScope ps(c, KC_NODE_ENCODE);
         hipLaunchKernelGGL(k_node_encode<8>, dim3(B), dim3(256), 0, st, vw, s_delta, a.attr,
-                           a.attr_mod, a.dens, a.dens_mod, N, ptr<float>(c->eff), ptr<float>(c->c_node));
+                           a.attr_mod, a.dens, a.dens_mod, N, ptr<float>(c->ws.eff), ptr<float>(c->ws.c_node));
     }
     {
         ProbeScope ps(c, KC_EDGE_ENCODE);
         hipLaunchKernelGGL(k_edge_encode, dim3(B), dim3(256), (6 * 64 + 3 * 4096) * sizeof(float), st,
                            vw, a.s_prev, a.prev_mod, a.prev_stride, a.attr, a.attr_mod, a.dens,
-                           a.dens_mod, nbr_idx, nbr_cnt, N, ptr<float>(c->c_edge));
+                           a.dens_mod, nbr_idx, nbr_cnt, N, ptr<float>(c->ws.c_edge));
     }
     for (int p = 0; p < DRP_PSTEP; ++p) {
         {
             ProbeScope ps(c, KC_PROJECT);
-            hipLaunchKernelGGL(k_project<8>, dim3(B), dim3(256), 0, st, vw, ptr<float>(c->eff), N,
-                               ptr<float>(c->proj));
+            hipLaunchKernelGGL(k_project<8>, dim3(B), dim3(256), 0, st, vw, ptr<float>(c->ws.eff), N,
+                               ptr<float>(c->ws.proj));
         }
-        launch_aggregate(c, k.agg, B, N);
+        launch_aggregate(c, k.agg, a.nbr_idx, a.nbr_cnt, B, N);
         {
             ProbeScope ps(c, KC_UPDATE);
-            hipLaunchKernelGGL(k_update<8>, dim3(B), dim3(256), 0, st, vw, ptr<float>(c->agg),
-                               ptr<float>(c->c_node), N, ptr<float>(c->eff));
+            hipLaunchKernelGGL(k_update<8>, dim3(B), dim3(256), 0, st, vw, ptr<float>(c->ws.agg),
+                               ptr<float>(c->ws.c_node), N, ptr<float>(c->ws.eff));
         }
     }
     {
         ProbeScope ps(c, KC_PREDICT);
-        hipLaunchKernelGGL(k_predict<8>, dim3(B), dim3(256), 0, st, vw, ptr<float>(c->eff), a.s_prev,
+        hipLaunchKernelGGL(k_predict<8>, dim3(B), dim3(256), 0, st, vw, ptr<float>(c->ws.eff), a.s_prev,
                            a.prev_mod, a.prev_stride, N, a.s_out, a.out_stride);
     }
     HIPCHK(c, hipGetLastError());
@@ -605,8 +612,8 @@ int prepare_cself(drp_ctx* c, int attr_mod, int N, int B, const float** cself, c
         CHK(ensure(c, c->cself, (size_t)B * 64 * sizeof(float) + (size_t)B));
         float* cs = ptr<float>(c->cself);
         uint8_t* ok = reinterpret_cast<uint8_t*>(cs + (size_t)B * 64);
-        hipLaunchKernelGGL(k_cself, dim3(B), dim3(64), 0, c->stream, ptr<float>(c->w_valu), ptr<float>(c->attr), attr_mod,
-                           ptr<float>(c->dens), attr_mod, N, cs, ok);
+        hipLaunchKernelGGL(k_cself, dim3(B), dim3(64), 0, c->stream, ptr<float>(c->w_valu), ptr<float>(c->ws.attr), attr_mod,
+                           ptr<float>(c->ws.dens), attr_mod, N, cs, ok);
         *cself = cs;
         *cself_ok = ok;
         ++c->cself_tag;
@@ -615,10 +622,10 @@ int prepare_cself(drp_ctx* c, int attr_mod, int N, int B, const float** cself, c
 }
 
 int run_rollout(drp_ctx* c, int nb, int N, int B, int H, bool reward_all, bool reward_last, bool session = false) {
-    CHK(ensure_step_ws(c, B, N));
+    CHK(ensure_step_ws(c, c->ws, B, N));
     CHK(ensure(c, c->states, (size_t)B * H * N * 3 * sizeof(float)));
     CHK(ensure(c, c->rewards, (size_t)B * H * sizeof(float)));
-    c->lastH = H;
+    c->marks.lastH = H;
     float* states = ptr<float>(c->states);
     const size_t hstride = (size_t)H * N * 3;
     const float* cself = nullptr;
@@ -634,12 +641,12 @@ int run_rollout(drp_ctx* c, int nb, int N, int B, int H, bool reward_all, bool r
     }
     // small piles on the fused engine: the whole rollout is ONE launch per block of samples (dispatch.h: plan_rollout)
     const RolloutPlan k = plan_rollout(c->pol, c->n_cu, c->engine, B, N, nb, c->work_ptr() != nullptr, c->deg());
-    k.mark(c->dv_hit);
+    k.mark(c->marks.dv_hit);
     const bool one_launch = k.one_launch;
     if (one_launch) {
         const int n_chunks = k.blocks.n;
         std::vector<RolloutArgs> blocks((size_t)n_chunks);
-        if (k.blocks.cache) CHK(ensure(c, c->ecache, k.blocks.cache_bytes));
+        if (k.blocks.cache) CHK(ensure(c, c->ws.ecache, k.blocks.cache_bytes));
         for (int q = 0; q < n_chunks; ++q) {
             const Block b = k.blocks.block(q);
             const long b_off = b.b_off;
@@ -649,17 +656,17 @@ int run_rollout(drp_ctx* c, int nb, int N, int B, int H, bool reward_all, bool r
             ra.sw = ptr<uint16_t>(c->w_split); ra.sw6 = ptr<uint16_t>(c->w_split6); ra.mw = ptr<float>(c->w_mfma);
             // the first state, the attributes and the densities are replicated over the batch columns (row b reads column b % nb;
             // a block starts at a multiple of nb): same base for every block; everything indexed by the row moves on
-            ra.s_in = ptr<float>(c->s_in); ra.attr = ptr<float>(c->attr); ra.dens = ptr<float>(c->dens);
+            ra.s_in = ptr<float>(c->ws.s_in); ra.attr = ptr<float>(c->ws.attr); ra.dens = ptr<float>(c->ws.dens);
             ra.states = states + ro * 3 * H;
             ra.actions = ptr<float>(c->actions) + (size_t)b_off * H * 4;
-            ra.s_delta = ptr<float>(c->s_delta) + ro * 3; ra.nbr_idx = ptr<int16_t>(c->nbr_idx) + ro * DRP_K;
-            ra.nbr_cnt = ptr<uint8_t>(c->nbr_cnt) + ro; ra.proj_a = ptr<float>(c->proj) + ro * 128; ra.proj_b = ptr<float>(c->proj2) + ro * 128;
-            ra.c_node = ptr<float>(c->c_node) + ro * 64; ra.eff = ptr<float>(c->eff) + ro * 64;
+            ra.s_delta = ptr<float>(c->ws.s_delta) + ro * 3; ra.nbr_idx = ptr<int16_t>(c->ws.nbr_idx) + ro * DRP_K;
+            ra.nbr_cnt = ptr<uint8_t>(c->ws.nbr_cnt) + ro; ra.proj_a = ptr<float>(c->ws.proj) + ro * 128; ra.proj_b = ptr<float>(c->ws.proj2) + ro * 128;
+            ra.c_node = ptr<float>(c->ws.c_node) + ro * 64; ra.eff = ptr<float>(c->ws.eff) + ro * 64;
             ra.cself = cself ? cself + (size_t)b_off * 64 : nullptr; ra.cself_ok = cself_ok ? cself_ok + b_off : nullptr;
             ra.N = N; ra.B = b.Bc; ra.spw = b.spw; ra.nb = nb; ra.H = H; ra.order_rows = (c->pol.prop3_order ? 1 : 0);
             ra.thr = c->thr; ra.re_scale = c->re_scale; ra.re_inv = c->re_inv; ra.cam = c->cam;
             ra.ec_stride = b.ec_stride;
-            ra.ecache = k.blocks.cache ? ptr<float4>(c->ecache) : nullptr;
+            ra.ecache = k.blocks.cache ? ptr<float4>(c->ws.ecache) : nullptr;
             ra.work = c->work_ptr();
             if (ra.work) (k.lite ? c->work_lite : c->work_full) = true;
         }
@@ -679,18 +686,18 @@ int run_rollout(drp_ctx* c, int nb, int N, int B, int H, bool reward_all, bool r
                                c->stream, ptr<RolloutArgs>(c->roll_args) + q);
         }
         HIPCHK(c, hipGetLastError());
-        note_degrees(c, k.spw, N, B);           // the last step's lists
+        note_degrees(c, ptr<uint8_t>(c->ws.nbr_cnt), k.spw, N, B);           // the last step's lists
     }
     for (int t = 0; t < H && !one_launch; ++t) {
-        StepArgs a{};
+        StepArgs a = step_args(c, c->engine);
         a.cself = cself; a.cself_ok = cself_ok;
         if (t == 0) {
-            a.s_prev = ptr<float>(c->s_in); a.prev_mod = nb; a.prev_stride = (size_t)N * 3;
+            a.s_prev = ptr<float>(c->ws.s_in); a.prev_mod = nb; a.prev_stride = (size_t)N * 3;
         } else {
             a.s_prev = states + (size_t)(t - 1) * N * 3; a.prev_mod = B; a.prev_stride = hstride;
         }
-        a.attr = ptr<float>(c->attr); a.attr_mod = nb;
-        a.dens = ptr<float>(c->dens); a.dens_mod = nb;
+        a.attr = ptr<float>(c->ws.attr); a.attr_mod = nb;
+        a.dens = ptr<float>(c->ws.dens); a.dens_mod = nb;
         a.actions = ptr<float>(c->actions) + (size_t)t * 4; a.act_stride = (size_t)H * 4;
         a.build_graph = true;
         a.s_out = states + (size_t)t * N * 3; a.out_stride = hstride;
@@ -861,8 +868,7 @@ int ensure_tape(drp_ctx* c, int B, int N, int H, int rev_sets) {
 }
 
 // The forward pass of H steps on `engine` into c->states.  Step t's impulses are tape_sdelta's slice t; with `tape` its
-// neighbour lists are the tape's slices too (the step's workspace pointers are lent the slices for the call instead of
-// copies afterwards), and km_prop<., TAPE> leaves beside them what the backward pass needs: the effect after the encoder
+// neighbour lists are the tape's slices too (StepArgs names the slices: nothing is copied afterwards), and km_prop<., TAPE> leaves beside them what the backward pass needs: the effect after the encoder
 // and after every propagation step, the ReLU masks of the edges, with `agg_hist` the aggregated edge effects.
 struct TapeFwd {
     const float* s0; int s0_mod; size_t s0_stride;   // the first step's input; the later steps read the step before's output
@@ -876,19 +882,14 @@ struct TapeFwd {
     bool* rev_built = nullptr;                       //   (StepArgs)
 };
 int run_tape_forward(drp_ctx* c, int engine, int B, int N, int H, const TapeFwd& f) {
-    struct Lend {                                    // the context's engine and workspaces again, however the loop ends
-        drp_ctx* c; int engine; void* sd; void* idx; void* cnt;
-        ~Lend() { c->engine = engine; c->s_delta.p = sd; c->nbr_idx.p = idx; c->nbr_cnt.p = cnt; }
-    } lend{c, c->engine, c->s_delta.p, c->nbr_idx.p, c->nbr_cnt.p};
-    c->engine = engine;
     const size_t bn = (size_t)B * N, hstride = (size_t)H * N * 3;
     float* states = ptr<float>(c->states);
     for (int t = 0; t < H; ++t) {
-        StepArgs a{};
+        StepArgs a = step_args(c, engine);
         if (t == 0) { a.s_prev = f.s0; a.prev_mod = f.s0_mod; a.prev_stride = f.s0_stride; }
         else { a.s_prev = states + (size_t)(t - 1) * N * 3; a.prev_mod = B; a.prev_stride = hstride; }
-        a.attr = ptr<float>(c->attr); a.attr_mod = f.mod;
-        a.dens = ptr<float>(c->dens); a.dens_mod = f.mod;
+        a.attr = ptr<float>(c->ws.attr); a.attr_mod = f.mod;
+        a.dens = ptr<float>(c->ws.dens); a.dens_mod = f.mod;
         if (f.actions) { a.actions = f.actions + (size_t)t * 4; a.act_stride = (size_t)H * 4; }
         a.build_graph = true;
         a.s_out = states + (size_t)t * N * 3; a.out_stride = hstride;
@@ -896,10 +897,10 @@ int run_tape_forward(drp_ctx* c, int engine, int B, int N, int H, const TapeFwd&
         a.cself = f.cself; a.cself_ok = f.cself_ok;
         a.padded = f.padded;
         a.rev_off = f.rev_off; a.rev = f.rev; a.rev_built = f.rev_built;
-        c->s_delta.p = ptr<float>(c->tape_sdelta) + (size_t)t * bn * 3;
+        a.s_delta = ptr<float>(c->tape_sdelta) + (size_t)t * bn * 3;
         if (f.tape) {
-            c->nbr_idx.p = ptr<int16_t>(c->tape_idx) + (size_t)t * bn * DRP_K;
-            c->nbr_cnt.p = ptr<uint8_t>(c->tape_cnt) + (size_t)t * bn;
+            a.nbr_idx = ptr<int16_t>(c->tape_idx) + (size_t)t * bn * DRP_K;
+            a.nbr_cnt = ptr<uint8_t>(c->tape_cnt) + (size_t)t * bn;
             a.eff_hist = ptr<float>(c->eff_hist) + (size_t)t * 4 * bn * 64;
             a.mask_hist = ptr<unsigned>(c->tape_mask) + (size_t)t * DRP_PSTEP * bn * DRP_K * 2;
             if (f.agg_hist) a.agg_hist = ptr<float>(c->agg_hist) + (size_t)t * 3 * bn * 64;
@@ -1019,8 +1020,8 @@ void launch_node_stages(drp_ctx* c, const BwdStep& s, dim3 egrid, int chunks, co
     }
     if (wg) wg->cnode(s);
     { ProbeScope ps(c, KC_BWD_NODE);
-    hipLaunchKernelGGL(kmb_node_encode, ngrid, nblk, KMB_NODE_ENCODE_LDS, st, mw, mb, s.sdelta, ptr<float>(c->attr), s.mod,
-                       ptr<float>(c->dens), s.mod, s.eht, s.ge_tmp, s.g_cnode, N, B, ptr<float>(c->g_sdelta), d.gpe, d.a1n, d.gh1, d.xn);
+    hipLaunchKernelGGL(kmb_node_encode, ngrid, nblk, KMB_NODE_ENCODE_LDS, st, mw, mb, s.sdelta, ptr<float>(c->ws.attr), s.mod,
+                       ptr<float>(c->ws.dens), s.mod, s.eht, s.ge_tmp, s.g_cnode, N, B, ptr<float>(c->g_sdelta), d.gpe, d.a1n, d.gh1, d.xn);
     }
     if (wg) {
         wg->encoder(s);
@@ -1090,10 +1091,10 @@ float push_len_bound(const drp_ctx* c, const float* actions, size_t n) {
     }
     return fro * sqrtf(l2) / c->cam.gs;
 }
-// tape: the caller runs the fused engine whatever drp_set_engine chose (the gradient-descent planner's and the trainer's
-// forward pass write their tape with it)
-int range_check(drp_ctx* c, float max_attr, float max_dens, float max_sdelta, bool tape = false) {
-    if (!tape && !engine_is_fused(c->engine) && c->engine != DRP_ENGINE_SPLIT) return DRP_OK;
+// engine: the one the caller runs (the gradient-descent planner's and the trainer's forward pass write their tape with the
+// fused one whatever drp_set_engine chose)
+int range_check(drp_ctx* c, int engine, float max_attr, float max_dens, float max_sdelta) {
+    if (!engine_is_fused(engine) && engine != DRP_ENGINE_SPLIT) return DRP_OK;
     const double A = max_attr, dm = max_dens / DRP_DENS_SCALE, D = (double)c->adj_thresh + 2.0 * max_sdelta;
     const SplitRange& r = c->re_range;
     if (!c->re_ok)
@@ -1113,7 +1114,7 @@ int range_check(drp_ctx* c, float max_attr, float max_dens, float max_sdelta, bo
 // live planner of the reference IS the gradient-descent one (env/flex_env.py:973-976): it must not stop on DRP_ERANGE.
 int pick_tape_engine(drp_ctx* c, float max_attr, float max_dens, float max_sdelta, int* engine) {
     if (c->engine == DRP_ENGINE_MFMA || c->engine == DRP_ENGINE_VALU) { *engine = DRP_ENGINE_MFMA; return DRP_OK; }
-    const int rc = range_check(c, max_attr, max_dens, max_sdelta, true);
+    const int rc = range_check(c, DRP_ENGINE_FUSED, max_attr, max_dens, max_sdelta);
     if (rc == DRP_ERANGE) { *engine = DRP_ENGINE_MFMA; c->err.clear(); return DRP_OK; }
     *engine = DRP_ENGINE_FUSED;
     return rc;

@@ -62,7 +62,7 @@ int train_forward_backward(drp_ctx* c, int B, int N, bool backward) {
     if (chunks16 > 4096 / B) chunks16 = 4096 / B;
     if (chunks16 < 1) chunks16 = 1;
     const dim3 egrid((unsigned)(B * chunks16));
-    const float* dens = ptr<float>(c->dens);
+    const float* dens = ptr<float>(c->ws.dens);
     // the reversed lists of ALL rollout steps in one launch (the tape holds every step's lists; a training batch is a handful
     // of workgroups per step)
     launch_reverse_lists(c, ptr<int16_t>(c->tape_idx), ptr<uint8_t>(c->tape_cnt), N, B * H, nums, B);
@@ -109,7 +109,7 @@ int train_forward_backward(drp_ctx* c, int B, int N, bool backward) {
             // operands of the weight gradients are its dumps; the jobs in the stage kernels' queue order
             c->dv(k.variant());
 #define STEP_BWD_ARGS ptr<float>(c->w_mfma), ptr<float>(c->w_mfma_bwd), s.eht, s.mht, s.cnt, s.rev_off, s.rev, g_out, (size_t)N * 3, \
-                      s.sdelta, ptr<float>(c->attr), B, dens, B, N, B, f_spw, s.ge_tmp, s.g_cnode, s.gah, ptr<float>(c->g_sdelta), s.d, \
+                      s.sdelta, ptr<float>(c->ws.attr), B, dens, B, N, B, f_spw, s.ge_tmp, s.g_cnode, s.gah, ptr<float>(c->g_sdelta), s.d, \
                       f_parts, f_bar + (size_t)t * f_groups, f_bar + (size_t)H * f_groups
             if (f_coop)
                 hipLaunchKernelGGL((kmb_step_bwd<true, true>), dim3((unsigned)(f_groups * f_parts)), dim3(64 * KMB_FUSED_WAVES), KMB_COOP_LDS, st, STEP_BWD_ARGS);
@@ -281,8 +281,8 @@ int drp_train_step(drp_ctx* c, const float* states, const float* states_delta, c
         memcpy(pin + lay.nums, particle_nums, (size_t)B * sizeof(int));
     }
     CHK(ensure(c, c->tr_arena, lay.bytes));
-    CHK(ensure(c, c->attr, bn * sizeof(float)));
-    CHK(ensure(c, c->dens, (size_t)B * sizeof(float)));
+    CHK(ensure(c, c->ws.attr, bn * sizeof(float)));
+    CHK(ensure(c, c->ws.dens, (size_t)B * sizeof(float)));
     CHK(ensure(c, c->tape_sdelta, (size_t)H * bn * 3 * sizeof(float)));
     {
         // the unpacking launch IS the upload: it reads the staged batch from the pinned host buffer (device-visible) and leaves
@@ -293,11 +293,11 @@ int drp_train_step(drp_ctx* c, const float* states, const float* states_delta, c
         const size_t total = (size_t)H * bn * 3;
         hipLaunchKernelGGL(kt_unpack_inputs, dim3((unsigned)std::min<size_t>((total + 255) / 256, 1024)), dim3(256), 0, c->stream,
                            reinterpret_cast<const float*>(ar + lay.sdelta), reinterpret_cast<const float*>(ar + lay.attrs),
-                           reinterpret_cast<const float*>(ar + lay.dens), B, H, N, ptr<float>(c->tape_sdelta), ptr<float>(c->attr),
-                           ptr<float>(c->dens), by_kernel ? ptr<const float4>(c->tr_pin) : (const float4*)nullptr,
+                           reinterpret_cast<const float*>(ar + lay.dens), B, H, N, ptr<float>(c->tape_sdelta), ptr<float>(c->ws.attr),
+                           ptr<float>(c->ws.dens), by_kernel ? ptr<const float4>(c->tr_pin) : (const float4*)nullptr,
                            by_kernel ? static_cast<float4*>(c->tr_arena.p) : (float4*)nullptr, by_kernel ? lay.bytes / 16 : (size_t)0);
     }
-    CHK(ensure_step_ws(c, B, N, c->tr_engine));
+    CHK(ensure_step_ws(c, c->ws, B, N, c->tr_engine));
     CHK(ensure(c, c->states, (size_t)H * bn * 3 * sizeof(float)));
     CHK(ensure(c, c->g_state, (size_t)H * bn * 3 * sizeof(float)));
     c->wg_defer_now = false;
@@ -324,7 +324,7 @@ int drp_train_step(drp_ctx* c, const float* states, const float* states_delta, c
         CHK(ensure(c, c->ed_x0, kt * bnk * 8 * sizeof(float)));
     }
     CHK(ensure(c, c->tr_loss, (size_t)H * B * sizeof(double)));
-    c->lastH = H;
+    c->marks.lastH = H;
     double* const parts = reinterpret_cast<double*>(ptr<char>(c->tr_pin) + back_off);
     unsigned* const gave_up = reinterpret_cast<unsigned*>(parts + (size_t)H * B);
     // kmb_step_bwd's barrier among the workgroups of a group gives up after two seconds (k_backward_mfma.h) and sets a flag

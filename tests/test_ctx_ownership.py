@@ -83,3 +83,33 @@ def test_the_owners_are_move_only():
         owner = _body(text, 'struct %s {' % t)
         assert '%s(const %s&) = delete;' % (t, t) in owner and '%s& operator=(const %s&) = delete;' % (t, t) in owner, t
         assert '~%s() { (void)release(); }' % t in owner, t
+
+
+# ---- a step's engine and buffers are arguments (StepArgs); a float64 call swaps one struct (StepWs) -----------------------
+def test_nobody_but_the_owners_assigns_an_owned_pointer():
+    """`x.p = ...` outside DevBuf / PinBuf would make an owner hold memory it did not allocate (a view is a plain pointer)"""
+    for f, text in _sources().items():
+        if f == 'capi_ctx.h':
+            for owner in ('struct DevBuf {', 'struct PinBuf {'):
+                text = text.replace(_body(text, owner), '')
+        hits = [ln.strip() for ln in text.splitlines() if re.search(r'\.p\s*=[^=]', ln)]
+        assert not hits, (f, hits)
+
+
+def test_the_selected_engine_is_written_by_its_two_entry_points_only():
+    core = _sources()['capi_core.h']
+    homes = _body(core, 'int drp_create(int device, drp_ctx** out) {') + _body(core, 'int drp_set_engine(drp_ctx* c, int engine) {')
+    sites = [(f, n, ln) for f, text in _sources().items() for n, ln in enumerate(text.splitlines(), 1) if re.search(r'->engine\s*=[^=]', ln)]
+    assert len(sites) == 3, sites
+    assert all(f == 'capi_core.h' and ln.strip() in homes for f, _, ln in sites), sites
+
+
+def test_ensure_step_ws_and_stepws_name_the_same_fourteen_buffers():
+    ws = _body(_sources()['capi_ctx.h'], 'struct StepWs {')
+    members = [m for decl in re.findall(r'DevBuf\s+([^;]+);', ws) for m in re.findall(r'\w+', decl)]
+    assert len(members) == 14 and len(set(members)) == 14, members
+    named = set(re.findall(r'\bws\.(\w+)', _body(_sources()['capi_pipeline.h'], 'int ensure_step_ws(drp_ctx* c, StepWs& ws,')))
+    assert named == set(members), (sorted(named), sorted(members))
+    # and the float64 calls swap the struct whole: no list of buffers to keep in step
+    scope = _body(_sources()['capi_f64.h'], 'struct F64Scope {')
+    assert scope.count('std::swap(c->ws, c->f64_ws);') == 2 and 'DevBuf' not in scope, scope

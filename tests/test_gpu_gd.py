@@ -384,3 +384,75 @@ def test_the_stage_kernels_against_the_reference(monkeypatch, golden, case):
     np.testing.assert_allclose(r, g[case + '/reward'][:, 0], rtol=2e-5)
     ref_ga = g[case + '/grad_act']
     assert np.abs(ga - ref_ga).max() < 2e-3 * np.abs(ref_ga).max()
+
+
+# ---- a tape forward's engine and lists are run_step's arguments: the context's selection and step workspace stay as they were ----
+ENGINE_NAMES = ['valu', 'mfma', 'split', 'fused', 'lite']
+
+
+@pytest.fixture(scope='module')
+def untaped(golden):
+    """a context that never ran a tape, and the step inputs (3 samples) per particle count"""
+    from dyn_res_pile_manip_amd.engine import Engine
+    eng = Engine(0)
+    eng.load_weights(weights.blob_from_state_dict(golden.weights_seed0), 0.08)
+    eng.set_camera(world2cam_affine(syn.demo_cam_extrinsics()), 24.0, syn.demo_cam_params())
+    inputs, steps = {}, {}
+
+    def step(name, N):
+        if N not in inputs:
+            s0, dens, attr = syn.make_pile(N, 3, seed=N)
+            inputs[N] = (attr, s0, eng.gen_s_delta(s0, syn.sample_pushes(3, 1, seed=N)[:, 0]), dens)
+        if (name, N) not in steps:
+            eng.set_engine(name)
+            steps[name, N] = eng.step(*inputs[N])
+        return inputs[N], steps[name, N]
+    yield step
+    eng.close()
+
+
+def _step_as_on_the_untaped_context(eng, untaped, name, N):
+    from dyn_res_pile_manip_amd import _lib
+    inputs, want = untaped(name, N)
+    assert eng.engine_id == _lib.ENGINES[name]
+    got = eng.step(*inputs)
+    assert np.abs(got - inputs[1]).max() > 0
+    np.testing.assert_array_equal(got, want)
+
+
+@pytest.mark.parametrize('N', [20, 130])
+@pytest.mark.parametrize('name', ENGINE_NAMES)
+def test_a_tape_forward_leaves_the_selected_engine_and_the_step_workspace_alone(ctx, untaped, name, N):
+    """gd_grad writes its tape on the fused or the fp32 matrix engine whatever is selected, its impulses and lists into the
+    tape's slices (N = 20: km_prop<tape> per step and k_graph_rev; N = 130: km_prop3<tape> and the strip graph).  A step on
+    the same context afterwards runs the selected engine in the context's own workspace: the bits of a context that never
+    ran a tape."""
+    s0, dens, attr = syn.make_pile(N, 3, seed=N + 1)
+    obs_goal = syn.goal_distance_image(syn.goal_mask('I'))
+    lo, hi = syn.action_limits()
+    ctx.set_goal(syn.goal_field(obs_goal), syn.goal_coor_strided(obs_goal, 5 * N))
+    ctx.set_engine(name)
+    try:
+        ctx.gd_begin(s0, attr, dens, syn.sample_pushes(6, 2, seed=N), 0.05, lo, hi)
+        r, ga = ctx.gd_grad()[:2]
+        assert np.isfinite(r).all() and np.abs(ga).max() > 0
+        _step_as_on_the_untaped_context(ctx, untaped, name, N)
+    finally:
+        ctx.set_engine('fused')
+
+
+def test_a_training_tape_leaves_the_selected_engine_and_the_step_workspace_alone(golden, untaped):
+    from dyn_res_pile_manip_amd.engine import Engine
+    g = golden.train
+    batch = [g['b2_r5/' + k] for k in ('states', 'states_delta', 'attrs', 'particle_nums', 'particle_dens')]
+    eng = Engine(0)
+    try:
+        eng.load_weights(weights.blob_from_state_dict(golden.weights_seed0), 0.08)
+        eng.set_camera(world2cam_affine(syn.demo_cam_extrinsics()), 24.0, syn.demo_cam_params())
+        eng.set_engine('split')
+        eng.train_begin(batch[0].shape[1] - 1, 1e-3, 0.9)
+        loss, grad = eng.train_step(*batch, mode='grad', want_grad=True)
+        assert np.isfinite(loss) and np.abs(grad).max() > 0
+        _step_as_on_the_untaped_context(eng, untaped, 'split', 20)
+    finally:
+        eng.close()
