@@ -314,6 +314,8 @@ struct drp_ctx {
     DevBuf grad64_ws, grad64_io;    // drp_gd_grad_f64 and drp_train_grad_f64 (capi_grad_f64.h; one-shots that keep nothing between calls): a chunk's tape
                                     // and reverse pass (the trainer: and its samples' gradient accumulators); the batch's inputs and results
 
+    DevBuf ch_io;                   // drp_cloud_chamfer (capi_chamfer.h; a one-shot that keeps nothing between calls): its inputs and results
+
     // re-packing after an optimiser step on the device (k_train.h): gather maps of the plain packers, pinned copy of the blob
     DevBuf map_valu, map_mfma, map_mfma_bwd;
     bool repack_maps_ready = false;

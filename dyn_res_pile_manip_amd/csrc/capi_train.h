@@ -5,9 +5,10 @@
 namespace {
 #define TR_GRAD_PAD ((W_TOTAL + 63) & ~63)      // tr_grad: the gradient blob, then (from here) kmb_step_bwd's barrier counters
 // the batch as uploaded (drp_train_step): states [B][H+1][N][3] | impulses [B][H][N][3] | attributes [B][H+1][N] | densities [B]
-// | particle counts [B] (ints), every block 16-byte aligned
-struct TrArena { size_t states, sdelta, attrs, dens, nums, bytes; };
-TrArena tr_layout(int B, int H, int N) {
+// | particle counts [B] (ints), every block 16-byte aligned; drp_train_step_untracked (M > 0): behind them the target clouds
+// [B][H][M][3] | their counts [B][H] (ints) -- with M = 0 the layout, and so the one copy, is drp_train_step's
+struct TrArena { size_t states, sdelta, attrs, dens, nums, targets, tnums, bytes; };
+TrArena tr_layout(int B, int H, int N, int M = 0) {
     auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
     TrArena a{};
     a.states = 0;
@@ -16,14 +17,28 @@ TrArena tr_layout(int B, int H, int N) {
     a.dens = up(a.attrs + (size_t)B * (H + 1) * N * sizeof(float));
     a.nums = up(a.dens + (size_t)B * sizeof(float));
     a.bytes = up(a.nums + (size_t)B * sizeof(int));
+    if (M > 0) {
+        a.targets = a.bytes;
+        a.tnums = up(a.targets + (size_t)B * H * M * 3 * sizeof(float));
+        a.bytes = up(a.tnums + (size_t)B * H * sizeof(int));
+    }
     return a;
 }
 const float* tr_given(const drp_ctx* c) { return static_cast<const float*>(c->tr_arena.p); }
 const int* tr_nums(const drp_ctx* c, int B, int N) {
     return reinterpret_cast<const int*>(static_cast<const char*>(c->tr_arena.p) + tr_layout(B, c->tr_nroll, N).nums);
 }
+// what seeds the reverse pass: the tracked loss (kt_mse_grad against the given next states) or the Chamfer loss against
+// untracked target clouds (k_chamfer.h); the targets as the HOST gave them (the entry point stages them behind the batch)
+enum { TR_LOSS_MSE = 0, TR_LOSS_CHAMFER = 1 };
+struct TrLoss {
+    int kind = TR_LOSS_MSE;
+    const float* targets = nullptr;         // [B][H][M][3]
+    const int32_t* target_nums = nullptr;   // [B][H]
+    int M = 0;
+};
 // forward over n_rollout steps (+ loss), optionally the backward pass with weight gradients
-int train_forward_backward(drp_ctx* c, int B, int N, bool backward) {
+int train_forward_backward(drp_ctx* c, int B, int N, bool backward, const TrLoss& lk) {
     const int H = c->tr_nroll;
     const size_t bn = (size_t)B * N, bn64 = bn * 64, bnk = bn * DRP_K;
     const size_t hstride = (size_t)H * N * 3;                 // predicted states [B][H][N][3]
@@ -49,9 +64,26 @@ int train_forward_backward(drp_ctx* c, int B, int N, bool backward) {
         CHK(run_tape_forward(c, c->tr_engine, B, N, H, f));
     }
     // the loss of every step and d loss / d s_pred_t (train/train_gnn_dyn.py:184-186, :203) in one launch
-    hipLaunchKernelGGL(kt_mse_grad, dim3(B, H), dim3(256), 0, st, states, hstride, given + (size_t)N * 3, in_stride,
-                       nums, N, scale, g_state, loss, backward ? ptr<float>(c->tr_grad) : (float*)nullptr,
-                       (size_t)TR_GRAD_PAD + (size_t)H * c->n_cu + 1);      // the gradient blob with kmb_step_bwd's counters behind it
+    if (lk.kind == TR_LOSS_MSE) {
+        hipLaunchKernelGGL(kt_mse_grad, dim3(B, H), dim3(256), 0, st, states, hstride, given + (size_t)N * 3, in_stride,
+                           nums, N, scale, g_state, loss, backward ? ptr<float>(c->tr_grad) : (float*)nullptr,
+                           (size_t)TR_GRAD_PAD + (size_t)H * c->n_cu + 1);      // the gradient blob with kmb_step_bwd's counters behind it
+    } else {
+        // the same slot of the stream, the same outputs and the same zero-fill: step t of the predictions against step t of the
+        // staged target clouds
+        const TrArena lay = tr_layout(B, H, N, lk.M);
+        const char* ar = static_cast<const char*>(c->tr_arena.p);
+        KcArgs a{};
+        a.pred = states; a.p_bstride = hstride; a.p_tstride = (size_t)N * 3;
+        a.tgt = reinterpret_cast<const float*>(ar + lay.targets); a.q_bstride = (size_t)H * lk.M * 3; a.q_tstride = (size_t)lk.M * 3;
+        a.n_p = nums;
+        a.n_q = reinterpret_cast<const int*>(ar + lay.tnums); a.nq_bstride = H; a.nq_tstride = 1;
+        a.N = N; a.M = lk.M; a.scale = scale;
+        a.grad = g_state; a.terms = loss;
+        a.zero = backward ? ptr<float>(c->tr_grad) : (float*)nullptr;
+        a.n_zero = (size_t)TR_GRAD_PAD + (size_t)H * c->n_cu + 1;
+        hipLaunchKernelGGL((kc_chamfer<true>), dim3(B, H), dim3(KC_THREADS), 0, st, a);
+    }
     HIPCHK(c, hipGetLastError());
     if (!backward) return DRP_OK;
 
@@ -243,9 +275,11 @@ int drp_train_begin(drp_ctx* c, int n_rollout, double lr, double beta1) {
     return DRP_OK;
 }
 
-int drp_train_step(drp_ctx* c, const float* states, const float* states_delta, const float* attrs,
-                   const int32_t* particle_nums, const float* particle_dens, int B, int N, int mode, double* loss_out,
-                   float* grad_out) {
+namespace {
+// drp_train_step and drp_train_step_untracked: one body, the loss kind and the targets in `lk`
+int train_step_body(drp_ctx* c, const float* states, const float* states_delta, const float* attrs,
+                    const int32_t* particle_nums, const float* particle_dens, int B, int N, const TrLoss& lk, int mode,
+                    double* loss_out, float* grad_out) {
     if (!c || !c->tr_on) return fail(c, DRP_ESTATE, "drp_train_begin not called");
     CHK(check_bn(c, B, N));
     if (!states || !states_delta || !attrs || !particle_nums || !particle_dens) return fail(c, DRP_EINVAL, "null argument");
@@ -253,6 +287,14 @@ int drp_train_step(drp_ctx* c, const float* states, const float* states_delta, c
     for (int b = 0; b < B; ++b)
         if (particle_nums[b] <= 0 || particle_nums[b] > N)
             return fail(c, DRP_EINVAL, "particle_nums[%d]=%d outside 1..%d", b, particle_nums[b], N);
+    if (lk.kind == TR_LOSS_CHAMFER) {
+        if (!lk.targets || !lk.target_nums) return fail(c, DRP_EINVAL, "null argument");
+        if (lk.M <= 0 || lk.M > KC_MAX_POINTS) return fail(c, DRP_EINVAL, "bad target size M=%d (1..%d)", lk.M, KC_MAX_POINTS);
+        for (int e = 0; e < B * c->tr_nroll; ++e)
+            if (lk.target_nums[e] <= 0 || lk.target_nums[e] > lk.M)
+                return fail(c, DRP_EINVAL, "target_nums[%d][%d]=%d outside 1..%d", e / c->tr_nroll, e % c->tr_nroll,
+                            lk.target_nums[e], lk.M);
+    }
     HIPCHK(c, hipSetDevice(c->device));
     end_sessions(c);
     {
@@ -264,7 +306,7 @@ int drp_train_step(drp_ctx* c, const float* states, const float* states_delta, c
     const size_t bn = (size_t)B * N, bn64 = bn * 64, bnk = bn * DRP_K;
     const bool backward = mode != DRP_TRAIN_EVAL;
     // the batch in one copy: packed into pinned staging in the caller's layouts, unpacked by one launch (kt_unpack_inputs)
-    const TrArena lay = tr_layout(B, H, N);
+    const TrArena lay = tr_layout(B, H, N, lk.kind == TR_LOSS_CHAMFER ? lk.M : 0);
     // behind the batch: what comes BACK after the one wait -- the loss terms [H][B] and the give-up flag of kmb_step_bwd's
     // barrier (pinned: the copies are asynchronous, nothing on the way touches pageable memory or this frame)
     const size_t back_off = lay.bytes, back_bytes = (size_t)H * B * sizeof(double) + 16;
@@ -279,6 +321,10 @@ int drp_train_step(drp_ctx* c, const float* states, const float* states_delta, c
         memcpy(pin + lay.attrs, attrs, (size_t)B * (H + 1) * N * sizeof(float));
         memcpy(pin + lay.dens, particle_dens, (size_t)B * sizeof(float));
         memcpy(pin + lay.nums, particle_nums, (size_t)B * sizeof(int));
+        if (lk.kind == TR_LOSS_CHAMFER) {
+            memcpy(pin + lay.targets, lk.targets, (size_t)B * H * lk.M * 3 * sizeof(float));
+            memcpy(pin + lay.tnums, lk.target_nums, (size_t)B * H * sizeof(int));
+        }
     }
     CHK(ensure(c, c->tr_arena, lay.bytes));
     CHK(ensure(c, c->ws.attr, bn * sizeof(float)));
@@ -336,7 +382,7 @@ int drp_train_step(drp_ctx* c, const float* states, const float* states_delta, c
     for (int attempt = 0; ; ++attempt) {
         c->wg_defer_now = defer_batch;
         c->wg_jobs.clear();
-        CHK(train_forward_backward(c, B, N, backward));
+        CHK(train_forward_backward(c, B, N, backward, lk));
         const int f_spw = (B + c->n_cu - 1) / c->n_cu, f_groups = (B + f_spw - 1) / f_spw;
         const unsigned* const flag_dev = reinterpret_cast<const unsigned*>(ptr<float>(c->tr_grad) + TR_GRAD_PAD + (size_t)H * f_groups);
         *gave_up = 0;
@@ -393,6 +439,21 @@ int drp_train_step(drp_ctx* c, const float* states, const float* states_delta, c
         *loss_out = total;
     }
     return DRP_OK;
+}
+}  // namespace
+
+int drp_train_step(drp_ctx* c, const float* states, const float* states_delta, const float* attrs,
+                   const int32_t* particle_nums, const float* particle_dens, int B, int N, int mode, double* loss_out,
+                   float* grad_out) {
+    return train_step_body(c, states, states_delta, attrs, particle_nums, particle_dens, B, N, TrLoss{}, mode, loss_out, grad_out);
+}
+
+int drp_train_step_untracked(drp_ctx* c, const float* states, const float* states_delta, const float* attrs,
+                             const int32_t* particle_nums, const float* particle_dens, int B, int N, const float* targets,
+                             const int32_t* target_nums, int M, int mode, double* loss_out, float* grad_out) {
+    TrLoss lk;
+    lk.kind = TR_LOSS_CHAMFER; lk.targets = targets; lk.target_nums = target_nums; lk.M = M;
+    return train_step_body(c, states, states_delta, attrs, particle_nums, particle_dens, B, N, lk, mode, loss_out, grad_out);
 }
 
 int drp_train_set_lr(drp_ctx* c, double lr) {

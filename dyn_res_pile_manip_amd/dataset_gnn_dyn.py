@@ -215,6 +215,50 @@ class ParticleDataset(object):
         return batch
 
 
+def drop_correspondence(sample, rng, keep=(0.6, 1.0)):
+    """A tracked sample (the 6-tuple of ParticleDataset[idx]) -> an untracked one: the same six fields, then `targets`, a list of
+    n_rollout clouds.  Target t is a random subset of the rows of states[t + 1] in random order; its size is drawn uniformly
+    from keep x n (at least one row).  What a pile re-sampled after every push, or a depth camera, gives: points of the next
+    state without the particle they belong to (train_gnn_dyn.collate_untracked, train(loss='chamfer')).  rng: a
+    numpy.random.Generator."""
+    states = np.asarray(sample[0])
+    n = int(sample[3])
+    targets = []
+    for t in range(1, states.shape[0]):
+        m = int(np.clip(int(round(rng.uniform(keep[0], keep[1]) * n)), 1, n))
+        targets.append(np.ascontiguousarray(states[t, :n][rng.permutation(n)[:m]], dtype=np.float32))
+    return tuple(sample[:6]) + (targets,)
+
+
+class UntrackedLoader(object):
+    """A loader of collated tracked batches (DeviceLoader) -> untracked ones: every sample of every batch goes through
+    drop_correspondence (one numpy Generator, in sample order), the batch through collate_untracked.  reseed: every pass starts
+    from the seed again (a validation set that stays the same from epoch to epoch)."""
+
+    def __init__(self, loader, seed=0, keep=(0.6, 1.0), reseed=False):
+        self.loader = loader
+        self.seed = seed
+        self.rng = np.random.default_rng(seed)
+        self.keep = keep
+        self.reseed = bool(reseed)
+
+    def __len__(self):
+        return len(self.loader)
+
+    def __iter__(self):
+        from .train_gnn_dyn import collate_untracked
+        if self.reseed:
+            self.rng = np.random.default_rng(self.seed)
+        for batch in self.loader:
+            states, sdelta, attrs, nums, dens, imgs = [batch[i] for i in range(6)]
+            data = []
+            for b, n in enumerate(np.asarray(nums)):
+                n = int(n)
+                data.append(drop_correspondence((states[b][:, :n], sdelta[b][:, :n], attrs[b][:, :n], n, dens[b],
+                                                 None if imgs is None else imgs[b]), self.rng, self.keep))
+            yield collate_untracked(data)
+
+
 class _Indices(object):
     def __init__(self, n):
         self.n = n

@@ -626,6 +626,59 @@ class Engine(object):
                                          L.TRAIN_MODES[mode], ctypes.byref(loss), None if grad is None else _fp(grad)))
         return loss.value, grad
 
+    def train_step_untracked(self, states, states_delta, attrs, particle_nums, particle_dens, targets, target_nums,
+                             mode='update', want_grad=False):
+        """train_step with each step's loss taken against an untracked cloud (include/drp.h: drp_train_step_untracked): targets
+        [B, n_rollout, M, 3] with target_nums [B, n_rollout] real rows; of `states` only step 0 is read -> (loss, gradient blob
+        or None)."""
+        states, states_delta, attrs = _f32(states), _f32(states_delta), _f32(attrs)
+        dens = _f32(particle_dens)
+        nums = np.ascontiguousarray(particle_nums, dtype=np.int32)
+        targets = _f32(targets)
+        tnums = np.ascontiguousarray(target_nums, dtype=np.int32)
+        B, T1, N, _ = states.shape
+        assert T1 == self._n_rollout + 1 and states_delta.shape == (B, T1 - 1, N, 3)
+        assert attrs.shape == (B, T1, N) and nums.shape == (B,) and dens.shape == (B,)
+        assert targets.ndim == 4 and targets.shape[:2] == (B, T1 - 1) and targets.shape[3] == 3 and tnums.shape == (B, T1 - 1)
+        M = targets.shape[2]
+        loss = ctypes.c_double()
+        grad = np.empty((38403,), np.float32) if (want_grad and mode != 'eval') else None
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        self._ck(self.lib.drp_train_step_untracked(self.h, _fp(states), _fp(states_delta), _fp(attrs), nums.ctypes.data_as(i32p),
+                                                   _fp(dens), B, N, _fp(targets), tnums.ctypes.data_as(i32p), int(M),
+                                                   L.TRAIN_MODES[mode], ctypes.byref(loss), None if grad is None else _fp(grad)))
+        return loss.value, grad
+
+    # ---- the Chamfer metric of two cloud batches (include/drp.h: drp_cloud_chamfer) ----------------------------------
+    def cloud_chamfer(self, p, q, n_p=None, n_q=None, want_grad=False, want_nn=False):
+        """Symmetric squared Chamfer distance of p [B, N, 3] (n_p [B] real rows, default all) and q [B, M, 3] (n_q) ->
+        {'fwd', 'bwd', 'total' [B] float64[, 'grad' [B, N, 3] = d total / d p][, 'nn_pq' [B, N], 'nn_qp' [B, M]: each row's nearest
+        row of the other cloud, -1 on padding]}.  A single cloud pair may be given as [N, 3], [M, 3].  A one-shot: it needs no
+        weights and ends no session."""
+        p, q = _f32(p), _f32(q)
+        if p.ndim == 2 and q.ndim == 2:
+            p, q = p[None], q[None]
+        assert p.ndim == 3 and q.ndim == 3 and p.shape[2] == 3 and q.shape[2] == 3 and p.shape[0] == q.shape[0]
+        B, N, M = p.shape[0], p.shape[1], q.shape[1]
+        n_p = np.full((B,), N, np.int32) if n_p is None else np.ascontiguousarray(n_p, dtype=np.int32).reshape(-1)
+        n_q = np.full((B,), M, np.int32) if n_q is None else np.ascontiguousarray(n_q, dtype=np.int32).reshape(-1)
+        assert n_p.shape == (B,) and n_q.shape == (B,)
+        terms = np.empty((B, 2), np.float64)
+        grad = np.empty((B, N, 3), np.float32) if want_grad else None
+        nn_pq = np.empty((B, N), np.int32) if want_nn else None
+        nn_qp = np.empty((B, M), np.int32) if want_nn else None
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        self._ck(self.lib.drp_cloud_chamfer(self.h, _fp(p), n_p.ctypes.data_as(i32p), _fp(q), n_q.ctypes.data_as(i32p), int(B), int(N),
+                                            int(M), _dp(terms), _fp(grad) if want_grad else None,
+                                            nn_pq.ctypes.data_as(i32p) if want_nn else None,
+                                            nn_qp.ctypes.data_as(i32p) if want_nn else None))
+        out = {'fwd': terms[:, 0].copy(), 'bwd': terms[:, 1].copy(), 'total': terms[:, 0] + terms[:, 1]}
+        if want_grad:
+            out['grad'] = grad
+        if want_nn:
+            out['nn_pq'], out['nn_qp'] = nn_pq, nn_qp
+        return out
+
     # ---- the float64 yardstick of the trainer's gradients (include/drp.h: drp_train_grad_f64) ------------------------
     def train_grad_f64(self, states, states_delta, attrs, particle_nums, particle_dens, want_state=False):
         """What train_step(mode='grad') computes, in float64 on the device -> (loss, loss_terms [n_rollout, B], gradient blob

@@ -1,6 +1,7 @@
 """Host mirror of the reference's training script body (`train/train_gnn_dyn.py`), row f4.
 
   collate_fn(data)                     :20-45   variable particle counts -> zero-padded batch
+  collate_untracked(data)              the same, plus each sample's per-step target clouds (no counterpart: loss='chamfer')
   DeviceAdam(model, lr, betas)         :128-131 torch.optim.Adam(model.parameters(), ...) on the device
   run_batch(model, optimizer, data, phase)      :159-210 the loop body for one batch
   train(config, datasets, ...)         :134-246 epochs over 'train' / 'valid' phases, best-model tracking
@@ -54,6 +55,23 @@ def collate_fn(data):
     return batch
 
 
+def collate_untracked(data):
+    """collate_fn for untracked samples (dataset_gnn_dyn.drop_correspondence: the 6-tuple, then a list of n_rollout target clouds
+    [m_t, 3]): the six fields as collate_fn gives them, then targets [B, H, M, 3] zero-padded to the largest cloud and
+    target_nums [B, H] int32."""
+    batch = collate_fn(data)
+    B, H = len(data), len(data[0][6])
+    counts = np.array([[np.asarray(c).shape[0] for c in d[6]] for d in data], dtype=np.int64).reshape(B, H)
+    flat = counts.reshape(-1)
+    owner = np.repeat(np.arange(B * H), flat)                    # (sample, step) of every packed target row
+    slot = np.arange(flat.sum()) - (np.cumsum(flat) - flat)[owner]
+    targets = np.zeros((B * H, int(counts.max()), 3), dtype=np.float32)
+    targets[owner, slot] = np.concatenate([_np(c).reshape(-1, 3) for d in data for c in d[6]], axis=0)
+    out = PaddedBatch(tuple(batch) + (targets.reshape(B, H, -1, 3), counts.astype(np.int32)))
+    out.offsets = batch.offsets
+    return out
+
+
 class DeviceAdam(object):
     """torch.optim.Adam(model.parameters(), lr=lr, betas=(beta1, 0.999)) whose state lives in the
     model's engine (train/train_gnn_dyn.py:128-131)."""
@@ -70,8 +88,15 @@ class DeviceAdam(object):
         self.model.engine.train_set_lr(lr)
 
 
-def run_batch(model, optimizer, data, phase='train', n_rollout=None):
-    """The loop body at train/train_gnn_dyn.py:159-210 -> loss (python float, what loss.item() is there)."""
+LOSSES = ('mse', 'chamfer')
+
+
+def run_batch(model, optimizer, data, phase='train', n_rollout=None, loss='mse'):
+    """The loop body at train/train_gnn_dyn.py:159-210 -> loss (python float, what loss.item() is there).  loss='chamfer': `data`
+    is collate_untracked's (targets and target_nums behind the six fields) and each step's term is the Chamfer distance to its
+    target cloud (Engine.train_step_untracked)."""
+    if loss not in LOSSES:
+        raise ValueError('loss must be one of %s, got %r' % (LOSSES, loss))
     states, states_delta, attrs, particle_nums, particle_dens = [data[i] for i in range(5)]
     states = _np(states)
     B, length, n_obj, _ = states.shape
@@ -81,6 +106,10 @@ def run_batch(model, optimizer, data, phase='train', n_rollout=None):
     if hasattr(model, '_claim'):
         model._claim()                                  # models share the process's context: this one's weights in
         model._device_ahead = model._device_ahead or mode == 'update'
+    if loss == 'chamfer':
+        value, _ = model.engine.train_step_untracked(states, _np(states_delta), _np(attrs), _np(particle_nums, np.int32),
+                                                     _np(particle_dens), _np(data[6]), _np(data[7], np.int32), mode=mode)
+        return value
     loss, _ = model.engine.train_step(states, _np(states_delta), _np(attrs), _np(particle_nums, np.int32),
                                       _np(particle_dens), mode=mode)
     return loss
@@ -108,12 +137,20 @@ def probe_batch(model, data):
                                              _np(particle_dens))
 
 
-def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=None, first_epoch=0, grad_probe_every=0):
+def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=None, first_epoch=0, grad_probe_every=0,
+          loss='mse'):
     """train/train_gnn_dyn.py:134-246 without the file I/O: `dataloaders` = {'train': iterable of
     collated batches, 'valid': ...}.  Returns {'best_valid_loss', 'history': [(epoch, phase, rmse)]}.
     ckp(epoch, i, model): called after training batch i when i % ckp_per_iter == 0 (:217-218); first_epoch: the epoch
     a resumed run starts from (:136).  grad_probe_every = k > 0: every k-th training batch (i % k == 0) is probed before its
-    update (probe_batch); the worst tensor's rel goes to the history as (epoch, 'grad_probe', rel) and to the log."""
+    update (probe_batch); the worst tensor's rel goes to the history as (epoch, 'grad_probe', rel) and to the log.
+    loss='chamfer': the batches are collate_untracked's and every step's term is the Chamfer distance to its target cloud; the
+    float64 yardstick on the device is MSE-only, so grad_probe_every > 0 is refused with it."""
+    if loss not in LOSSES:
+        raise ValueError('loss must be one of %s, got %r' % (LOSSES, loss))
+    if loss == 'chamfer' and grad_probe_every > 0:
+        raise ValueError('grad_probe_every needs loss=\'mse\': the float64 yardstick of the gradients is MSE-only')
+    loss_kind = loss
     tc = config['train']
     n_rollout = tc['n_rollout']
     assert tc['n_history'] == 1
@@ -131,7 +168,7 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
                     if log is not None:
                         log('grad_probe [%d][%d] worst %s rel %.3e (%s tape), loss diff %.3e' % (epoch, i, pr['worst'], pr['rel'],
                                                                                                pr['tape'], pr['loss_diff']))
-                loss = run_batch(model, optimizer, data, phase, n_rollout)
+                loss = run_batch(model, optimizer, data, phase, n_rollout, loss=loss_kind)
                 meter.update(loss, _np(data[0]).shape[0])
                 if log is not None and i % tc['log_per_iter'] == 0:
                     log('%s [%d][%d] LR: %.6f, Loss: %.6f (%.6f)' % (phase, epoch, i, optimizer.param_groups[0]['lr'],
@@ -167,18 +204,22 @@ def set_seed(seed):
     random.seed(seed)
 
 
-def main(config, data_root=None, train_dir=None, cam=None, chunk=64, threads=8, n_epoch=None, engine=None, grad_probe_every=0):
+def main(config, data_root=None, train_dir=None, cam=None, chunk=64, threads=8, n_epoch=None, engine=None, grad_probe_every=0,
+         loss='mse'):
     """The file-level part of train/train_gnn_dyn.py:train() (:45-130, :196-228): seed, the log directory with config.yaml
     and log.txt, the 'train' / 'valid' ParticleDatasets and their DeviceLoaders, a fresh model (torch.nn.Linear's default
     initialisation) or the resumed checkpoint, net_epoch_%d_iter_%d.pth every ckp_per_iter training batches and
     net_best.pth, all in the state_dict layout PropNetDiffDenModel.load_state_dict reads.  cam = (cam_params,
     cam_extrinsic), by default the demo camera (synthetic.py; FleX is not available).  Returns train()'s result and
-    the directory."""
+    the directory.  loss='chamfer': the recorded episodes' correspondence is dropped (dataset_gnn_dyn.drop_correspondence on
+    every sample, seeded by train.random_seed) and the model is trained on the Chamfer distance to the untracked clouds."""
     import time
     import yaml
     from . import synthetic, weights
-    from .dataset_gnn_dyn import DeviceLoader, ParticleDataset
+    from .dataset_gnn_dyn import DeviceLoader, ParticleDataset, UntrackedLoader
     from .gnn_dyn import PropNetDiffDenModel
+    if loss == 'chamfer' and grad_probe_every > 0:
+        raise ValueError('grad_probe_every needs loss=\'mse\': the float64 yardstick of the gradients is MSE-only')
     tc = config['train']
     resume = tc['particle'].get('resume', {'active': False, 'epoch': 0, 'iter': 0})
     if cam is None:
@@ -195,6 +236,9 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=64, threads=8, 
     datasets = {ph: ParticleDataset(data_root, config, ph, cam, engine=engine) for ph in ('train', 'valid')}
     loaders = {ph: DeviceLoader(datasets[ph], tc['batch_size'], shuffle=(ph == 'train'), chunk=chunk, threads=threads)
                for ph in ('train', 'valid')}
+    if loss == 'chamfer':
+        loaders = {ph: UntrackedLoader(loaders[ph], seed=tc['random_seed'] + k, reseed=(ph == 'valid'))
+                   for k, ph in enumerate(('train', 'valid'))}
     model = PropNetDiffDenModel(config, engine=engine)
     if resume['active']:
         path = os.path.join(train_dir, 'net_epoch_%d_iter_%d.pth' % (resume['epoch'], resume['iter']))
@@ -215,7 +259,7 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=64, threads=8, 
 
         result = train(config, model, loaders, n_epoch=n_epoch, log=log, on_best=on_best, ckp=ckp,
                        first_epoch=resume['epoch'] if resume['active'] and resume['epoch'] > 0 else 0,
-                       grad_probe_every=grad_probe_every)
+                       grad_probe_every=grad_probe_every, loss=loss)
         for epoch, phase, rmse in result['history']:
             if phase == 'grad_probe':                   # logged when it was taken
                 continue
@@ -238,6 +282,8 @@ def _cli(argv=None):
     ap.add_argument('--threads', type=int, default=8, help='decoding threads (at most 16)')
     ap.add_argument('--grad-probe-every', type=int, default=0,
                     help='hold every k-th training batch\'s gradients against float64 before its update (0: never)')
+    ap.add_argument('--loss', choices=LOSSES, default='mse',
+                    help='chamfer: drop the recorded correspondence and train on the Chamfer distance to the untracked clouds')
     a = ap.parse_args(argv)
     config = default_config()
     if a.config:
@@ -248,7 +294,7 @@ def _cli(argv=None):
     if a.n_timestep is not None:
         config['dataset']['n_timestep'] = a.n_timestep
     result, d = main(config, a.data_root, a.train_dir, chunk=a.chunk, threads=a.threads, n_epoch=a.epochs,
-                     grad_probe_every=a.grad_probe_every)
+                     grad_probe_every=a.grad_probe_every, loss=a.loss)
     print('best valid loss %.6f, checkpoints in %s' % (np.sqrt(result['best_valid_loss']), d))
 
 

@@ -239,6 +239,20 @@ int drp_train_begin(drp_ctx* ctx, int n_rollout, double lr, double beta1);
 int drp_train_step(drp_ctx* ctx, const float* states, const float* states_delta, const float* attrs,
                    const int32_t* particle_nums, const float* particle_dens, int B, int N, int mode,
                    double* loss_out, float* grad_out);
+/* drp_train_step with the loss of each step taken against an UNTRACKED cloud: same arguments, then the targets.  Row i of a
+ * target is not particle i of the prediction (a pile re-sampled by FPS after every push, env/flex_env.py:1020,1093; a depth
+ * camera's cloud), so the term of (step t, sample b) is the symmetric squared Chamfer distance of drp_cloud_chamfer below between
+ * s_pred_t[b, :n_b] and targets[b, t, :target_nums[b, t]], (fwd + bwd) / (n_rollout B), summed step-major as drp_train_step's;
+ * the arg-mins are constants of the derivative.  Of states [B, n_rollout+1, N, 3] only step 0 is read (the layout is
+ * drp_train_step's); the impulses are data, as there: with n_rollout = 1 and Engine.gen_s_delta on the observed cloud this is
+ * exact for real untracked data, longer rollouts serve recorded episodes whose correspondence is dropped.  targets
+ * [B, n_rollout, M, 3], target_nums [B, n_rollout].  Everything behind the loss gradient -- reverse pass, weight gradients, Adam,
+ * re-packing -- is drp_train_step's.  DRP_ESTATE without drp_train_begin; DRP_EINVAL for a null argument, a count outside 1..N
+ * or 1..M, M outside 1..4096. */
+int drp_train_step_untracked(drp_ctx* ctx, const float* states, const float* states_delta, const float* attrs,
+                             const int32_t* particle_nums, const float* particle_dens, int B, int N,
+                             const float* targets /*[B][H][M][3]*/, const int32_t* target_nums /*[B][H]*/, int M,
+                             int mode, double* loss_out, float* grad_out);
 int drp_train_set_lr(drp_ctx* ctx, double lr);
 /* model.state_dict() (train/train_gnn_dyn.py:226,244): the current weights, drp_load_weights layout */
 int drp_get_weights(drp_ctx* ctx, float* blob_out, size_t n_floats);
@@ -554,6 +568,22 @@ int drp_gd_grad_f64(drp_ctx* ctx, const float* s0, const float* attr, const floa
 int drp_train_grad_f64(drp_ctx* ctx, const float* states, const float* states_delta, const float* attrs,
                        const int32_t* particle_nums, const float* particle_dens, int B, int N, int n_rollout,
                        double* loss_out, double* loss_terms_out, double* grad_out, double* grad_state_out);
+
+/* ---- symmetric squared Chamfer distance of two padded cloud batches and its gradient; no counterpart in the reference
+ * (env/flex_rewards.py:9 imports pytorch3d's and never uses it).  p [B][N][3] with n_p[b] real rows, q [B][M][3] with n_q[b];
+ * rows beyond a count are padding: never read as points, gradient exactly 0, neighbour -1.
+ *   a(i) = argmin_j |p_i - q_j|^2  j < n_q (lowest j on a tie)      c(j) = argmin_i |q_j - p_i|^2  i < n_p (lowest i on a tie)
+ *   fwd = 1/(3 n_p) sum_i |p_i - q_a(i)|^2                          bwd = 1/(3 n_q) sum_j |q_j - p_c(j)|^2
+ *   d (fwd + bwd) / d p_i = 2/(3 n_p) (p_i - q_a(i)) + 2/(3 n_q) sum_{j: c(j) = i} (p_i - q_j)       (arg-mins constant)
+ * The 1/3 is the per-coordinate mean of F.mse_loss: where the nearest neighbour is the true partner, fwd is the tracked loss's
+ * MSE term.  Squared distances in fp32 from fp32 differences, the sums in double, no atomics: the same bits from run to run and
+ * for a sample alone or inside any batch.  A one-shot with buffers of its own: needs no weights, ends no drp_mpc_* / drp_gd_* /
+ * training session, leaves the selected engine, drp_last_dispatch and the trainer's state alone.  DRP_EINVAL: a null argument
+ * (the last three outputs are nullable), a count outside 1..N or 1..M, N or M outside 1..4096. */
+int drp_cloud_chamfer(drp_ctx* ctx, const float* p, const int32_t* n_p, const float* q, const int32_t* n_q,
+                      int B, int N, int M, double* terms_out /*[B][2]: fwd, bwd*/,
+                      float* grad_p_out /*[B][N][3], nullable; scale = 1*/,
+                      int32_t* nn_pq_out /*[B][N], nullable*/, int32_t* nn_qp_out /*[B][M], nullable*/);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,9 @@
 """Time one training iteration (train/train_gnn_dyn.py:159-210; batch_size 4, n_rollout 5 as
-config/train/gnn_dyn.yaml) on the device, next to the dense torch-autograd oracle on the host."""
+config/train/gnn_dyn.yaml) on the device, next to the dense torch-autograd oracle on the host.
+
+  python tools/train_timing.py [shape index [iterations]]
+  python tools/train_timing.py --loss chamfer    a Chamfer update (train_step_untracked) against an MSE update of the same shape,
+                                                 interleaved on one context: B = 4 and 32, N = M = 300, n_rollout = 5"""
 import sys
 import time
 
@@ -16,6 +20,10 @@ eng.load_weights(weights.blob_from_state_dict(sd), 0.08)
 W = {k: np.asarray(v) for k, v in sd.items()}
 rng = np.random.default_rng(0)
 SHAPES = ((4, [300, 240, 150, 280]), (4, [1000, 800, 900, 600]), (32, [300] * 32))
+CHAMFER = '--loss' in sys.argv and sys.argv[sys.argv.index('--loss') + 1] == 'chamfer'
+if CHAMFER:
+    sys.argv = sys.argv[:1]
+    SHAPES = ((4, [300] * 4), (32, [300] * 32))
 if len(sys.argv) > 1:                      # one shape only (profiling): its index
     SHAPES = (SHAPES[int(sys.argv[1])],)
 ITERS = int(sys.argv[2]) if len(sys.argv) > 2 else 10
@@ -33,6 +41,27 @@ for B, nums in SHAPES:
         sdelta[b, :, :n] = 0.004 * rng.standard_normal((H, n, 3)).astype(np.float32)
     pn = np.asarray(nums, np.int32)
     eng.train_begin(H, 1e-3, 0.9)
+    if CHAMFER:
+        # the next states with their rows shuffled: M = N, every row a target
+        targets = np.stack([np.stack([states[b, t + 1][rng.permutation(N)] for t in range(H)]) for b in range(B)])
+        tn = np.full((B, H), N, np.int32)
+        steps = {'mse': lambda: eng.train_step(states, sdelta, attrs, pn, dens, mode='update'),
+                 'chamfer': lambda: eng.train_step_untracked(states, sdelta, attrs, pn, dens, targets, tn, mode='update')}
+        for k in steps:
+            steps[k](), steps[k]()
+        took = {'mse': [], 'chamfer': []}
+        for rep in range(6):                                        # interleaved blocks; the median of each
+            for k in ('mse', 'chamfer'):
+                eng.sync()
+                t0 = time.perf_counter()
+                for _ in range(ITERS):
+                    steps[k]()
+                eng.sync()
+                took[k].append((time.perf_counter() - t0) / ITERS * 1e3)
+        print('B=%d N=M=%d n_rollout=%d: update with the MSE loss %.3f ms (blocks %.3f .. %.3f), with the Chamfer loss %.3f ms '
+              '(%.3f .. %.3f)' % (B, N, H, np.median(took['mse']), min(took['mse']), max(took['mse']),
+                                  np.median(took['chamfer']), min(took['chamfer']), max(took['chamfer'])), flush=True)
+        continue
     for _ in range(2):
         eng.train_step(states, sdelta, attrs, pn, dens, mode='update')
     eng.sync()
