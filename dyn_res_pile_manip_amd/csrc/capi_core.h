@@ -13,6 +13,7 @@ int drp_create(int device, drp_ctx** out) {
     if (e != hipSuccess) return fail(nullptr, DRP_EHIP, "hipSetDevice: %s", hipGetErrorString(e));
     std::unique_ptr<drp_ctx> c(new drp_ctx());      // a failure exit below destroys it, its stream included
     c->device = device;
+    c->wgrad.reset(new WgradQueue(c.get()));
     e = hipStreamCreateWithFlags(&c->stream.s, hipStreamNonBlocking);
     if (e != hipSuccess) return fail(nullptr, DRP_EHIP, "hipStreamCreate: %s", hipGetErrorString(e));
     hipDeviceProp_t prop;

@@ -167,6 +167,7 @@ RcclApi* rccl_api() {
     return api.handle ? &api : nullptr;
 }
 
+struct WgradQueue;                  // capi_pipeline.h: its methods use the context
 double now_s() {
     timespec ts;
     clock_gettime(CLOCK_MONOTONIC, &ts);
@@ -198,7 +199,6 @@ struct drp_ctx {
     int n_cu = 256;
     DispatchPolicy pol;             // every threshold and switch that decides which kernel runs (dispatch.h; policy_from_env)
     bool comm_always = false;       // DRP_COMM_ALWAYS=1: a one-rank communicator still goes through ncclAllGather (bench.py --force-comm)
-    double* tr_loss_host = nullptr; // drp_train_step: pinned host memory the loss kernel stores its terms to (null: c->tr_loss)
     bool train_copy_upload = false; // DRP_TRAIN_COPY_UPLOAD=1: the training batch goes up by a copy on the stream instead of inside kt_unpack_inputs
     bool debug_force_giveup = false; // DRP_DEBUG_FORCE_GIVEUP=1 (tests): drp_train_step's first pass ends as if kmb_step_bwd's barrier had timed out
     // the mean in-degree the last lists of a shape had (k_deg_stat, every few launches): sum | rows << 24 | N << 48 in host memory
@@ -241,14 +241,11 @@ struct drp_ctx {
     double comm_init_timeout_s = 300.0;  // DRP_COMM_INIT_TIMEOUT_S: ncclCommInitRank (every rank must arrive)
 
     // gradient-descent planner state
-    int gd_engine = DRP_ENGINE_FUSED, tr_engine = DRP_ENGINE_FUSED;   // which engine writes the tape (pick_tape_engine)
+    int gd_engine = DRP_ENGINE_FUSED;        // which engine writes the session's tape (pick_tape_engine)
     bool gd_on = false;
     int gd_nb = 0, gd_N = 0, gd_B = 0, gd_H = 0, gd_iter = 0;
     PinBuf gd_pin[DRP_GD_SLOTS];             // drp_gd_step_async: pinned host copies [B rewards | B*H*4 pushes] of the iterations in flight,
     Event gd_ev[DRP_GD_SLOTS];               //   written by the iteration's own kernels (kb_reward, k_adam): no copy on the stream
-    float* gd_host_rewards = nullptr;        // where the iteration being enqueued writes them (null: device buffers only)
-    float* gd_host_actions = nullptr;
-    KbAdam gd_adam = KbAdam{};               // gd_iteration: the optimiser step rides on the last kb_sdelta launch (act == null: gradients only)
     bool gd_pending[DRP_GD_SLOTS] = {};
     PinBuf mpc_pin[2];                       // drp_mpc_fetch_async: [B*H*4 pushes | B final rewards] of two iterations in flight
     Event mpc_ev[2];
@@ -270,14 +267,9 @@ struct drp_ctx {
     int tr_nroll = 0, tr_iter = 0;
     double tr_lr = 1e-3, tr_beta1 = 0.9;
     std::vector<float> w_host;
-    std::vector<WgradJob> wg_jobs;  // weight-gradient jobs waiting for the next flush_wgrad
-    // DEFERRED weight gradients (training, DRP_NO_WGRAD_DEFER=1 turns it off): every operand of an iteration's jobs keeps a
-    // buffer of its own (per rollout step, per propagation step), the jobs queue up for the whole backward pass and go out
-    // in a handful of launches at its end (flush_wgrad_all) instead of 25 pairs in between
-    bool wgrad_defer = true, wg_defer_now = false;
-    DevBuf wg_jobs_dev, wg_idx_dev;
-    std::vector<unsigned char> wg_uploaded;     // what wg_jobs_dev / wg_idx_dev hold (re-uploaded when the iteration's jobs change)
-    DevBuf tr_part, tr_grad, tr_m, tr_v, tr_loss, agg_hist, tr_hact, tr_gh, tr_gpe, tr_a1n,
+    std::unique_ptr<WgradQueue> wgrad;      // the weight-gradient jobs of a backward pass and their buffers (capi_pipeline.h; from drp_create on)
+    bool wgrad_defer = true;        // DRP_NO_WGRAD_DEFER=1 turns the deferred weight gradients off
+    DevBuf tr_grad, tr_m, tr_v, tr_loss, agg_hist, tr_hact, tr_gh, tr_gpe, tr_a1n,
         tr_gh1, tr_xn, ed_re, ed_a2, ed_a1, ed_x0, ed_gce, ed_g3, ed_g2, ed_g1;
 
     // goal pre-processing (row f3)

@@ -14,7 +14,10 @@ void launch_edge_encode_mfma(drp_ctx* c, const float* s_prev, int prev_mod, size
                        ptr<float>(c->w_mfma_bwd), s_prev, prev_mod, prev_stride, ptr<float>(c->ws.attr), nb, ptr<float>(c->ws.dens), nb, idx,
                        cnt, gah, mht, bn, N, B, gpos_edge, dump);
 }
-int gd_forward_backward(drp_ctx* c) {
+// what one pass of the session does beside the gradients: the optimiser step that rides on the last kb_sdelta launch (a null
+// adam.act: gradients only) and where kb_reward also stores the rewards (pinned host memory; null: the device buffer only)
+struct GdPass { KbAdam adam = KbAdam{}; float* host_rewards = nullptr; };
+int gd_forward_backward(drp_ctx* c, const GdPass& pass) {
     const int nb = c->gd_nb, N = c->gd_N, B = c->gd_B, H = c->gd_H;
     const size_t bn = (size_t)B * N;
     const size_t hstride = (size_t)H * N * 3;
@@ -50,7 +53,7 @@ int gd_forward_backward(drp_ctx* c) {
         c->dv(DV_BWD_REWARD);
         hipLaunchKernelGGL(kb_reward, dim3(B), dim3(256), KB_REWARD_LDS(N), st, states + (size_t)(H - 1) * N * 3, hstride,
                            N, ptr<float>(c->goal_field), c->goal_h, c->goal_w, ptr<float>(c->goal_coor), c->goal_m, c->cam,
-                           1, g_state + (size_t)(H - 1) * bn * 3, (size_t)N * 3, ptr<float>(c->rewards), c->gd_host_rewards);
+                           1, g_state + (size_t)(H - 1) * bn * 3, (size_t)N * 3, ptr<float>(c->rewards), pass.host_rewards);
     }
     for (int t = H - 1; t >= 0; --t) {
         const float* s_prev = (t == 0) ? ptr<float>(c->ws.s_in) : states + (size_t)(t - 1) * N * 3;
@@ -107,7 +110,7 @@ int gd_forward_backward(drp_ctx* c) {
         { ProbeScope ps(c, KC_BWD_PUSH);
         hipLaunchKernelGGL(kb_sdelta, dim3(B), dim3(256), 0, st, s_prev, prev_mod, prev_stride,
                            ptr<float>(c->actions) + (size_t)t * 4, (size_t)H * 4, ptr<float>(c->g_sdelta), N, c->cam,
-                           ptr<float>(c->g_act) + (size_t)t * 4, (size_t)H * 4, g_prev, (size_t)N * 3, t == 0 ? c->gd_adam : KbAdam{});
+                           ptr<float>(c->g_act) + (size_t)t * 4, (size_t)H * 4, g_prev, (size_t)N * 3, t == 0 ? pass.adam : KbAdam{});
         }
     }
     HIPCHK(c, hipGetLastError());
@@ -162,7 +165,8 @@ int drp_gd_begin(drp_ctx* c, const float* s0, const float* attr, const float* de
 int drp_gd_grad(drp_ctx* c, float* rewards_out, float* grad_act_out, float* grad_state_out) {
     if (!c || !c->gd_on) return fail(c, DRP_ESTATE, "drp_gd_begin not called");
     HIPCHK(c, hipSetDevice(c->device));
-    CHK(gd_forward_backward(c));
+    DrainOnError drain(c);
+    CHK(gd_forward_backward(c, GdPass{}));
     const size_t bn = (size_t)c->gd_B * c->gd_N;
     if (rewards_out) CHK(d2h(c, rewards_out, c->rewards.p, (size_t)c->gd_B * sizeof(float)));
     if (grad_act_out) CHK(d2h(c, grad_act_out, c->g_act.p, (size_t)c->gd_B * c->gd_H * 4 * sizeof(float)));
@@ -174,26 +178,26 @@ int drp_gd_grad(drp_ctx* c, float* rewards_out, float* grad_act_out, float* grad
                                        ptr<float>(c->g_state) + (size_t)t * bn * 3, row, row, c->gd_B,
                                        hipMemcpyDeviceToHost, c->stream));
     }
-    return drp_sync(c);
+    CHK(drp_sync(c));
+    return drain.ok();
 }
 
 namespace {
 // one iteration on the stream: forward, backward, Adam, clip -- the optimiser step of a row in the kb_sdelta launch that
-// completes the row's gradient (rollout step 0's, the last of the backward pass): one launch fewer per iteration
-int gd_iteration(drp_ctx* c) {
+// completes the row's gradient (rollout step 0's, the last of the backward pass): one launch fewer per iteration.
+// host_rewards / host_actions (pinned; null for none): where the iteration's kernels also store its rewards and updated pushes
+int gd_iteration(drp_ctx* c, float* host_rewards, float* host_actions) {
     // torch.optim.Adam: step_size = lr / (1 - beta1^t), denom = sqrt(v) / sqrt(1 - beta2^t) + eps
     const double it = (double)(c->gd_iter + 1);
     const double bc1 = 1.0 - pow(0.9, it), bc2 = 1.0 - pow(0.999, it);
-    KbAdam a{};
-    a.act = ptr<float>(c->actions); a.m = ptr<float>(c->adam_m); a.v = ptr<float>(c->adam_v); a.act_copy = c->gd_host_actions;
+    GdPass pass{KbAdam{}, host_rewards};
+    KbAdam& a = pass.adam;
+    a.act = ptr<float>(c->actions); a.m = ptr<float>(c->adam_m); a.v = ptr<float>(c->adam_v); a.act_copy = host_actions;
     a.n_row = c->gd_H * 4;
     a.step_size = (float)(c->gd_lr / bc1); a.bc2_sqrt = (float)sqrt(bc2); a.b1 = 0.9f;
     a.lo = make_float4(c->gd_lo[0], c->gd_lo[1], c->gd_lo[2], c->gd_lo[3]);
     a.hi = make_float4(c->gd_hi[0], c->gd_hi[1], c->gd_hi[2], c->gd_hi[3]);
-    c->gd_adam = a;
-    const int rc = gd_forward_backward(c);
-    c->gd_adam = KbAdam{};
-    CHK(rc);
+    CHK(gd_forward_backward(c, pass));
     c->gd_iter += 1;
     HIPCHK(c, hipGetLastError());
     return DRP_OK;
@@ -203,12 +207,13 @@ int gd_iteration(drp_ctx* c) {
 int drp_gd_step(drp_ctx* c, float* rewards_out) {
     if (!c || !c->gd_on) return fail(c, DRP_ESTATE, "drp_gd_begin not called");
     HIPCHK(c, hipSetDevice(c->device));
-    CHK(gd_iteration(c));
+    DrainOnError drain(c);
+    CHK(gd_iteration(c, nullptr, nullptr));
     if (rewards_out) {
         CHK(d2h(c, rewards_out, c->rewards.p, (size_t)c->gd_B * sizeof(float)));
-        return drp_sync(c);
+        CHK(drp_sync(c));
     }
-    return DRP_OK;
+    return drain.ok();
 }
 
 // The planner's loop needs every iteration's rewards and updated pushes on the host (per-column bookkeeping,
@@ -229,14 +234,11 @@ int drp_gd_step_async(drp_ctx* c, int slot) {
     }
     // the iteration's own kernels write the slot (pinned host memory is device-visible): kb_reward the rewards, k_adam
     // the updated pushes -- two copies fewer on the stream per iteration (they were 27 of 197 us at 20 particles)
-    c->gd_host_rewards = ptr<float>(c->gd_pin[slot]);
-    c->gd_host_actions = ptr<float>(c->gd_pin[slot]) + nr;
-    const int rc_it = gd_iteration(c);
-    c->gd_host_rewards = c->gd_host_actions = nullptr;
-    CHK(rc_it);
+    DrainOnError drain(c);                  // (an exit that leaves gd_pending[slot] false leaves nothing writing the slot either)
+    CHK(gd_iteration(c, ptr<float>(c->gd_pin[slot]), ptr<float>(c->gd_pin[slot]) + nr));
     HIPCHK(c, hipEventRecord(c->gd_ev[slot].ev, c->stream));
     c->gd_pending[slot] = true;
-    return DRP_OK;
+    return drain.ok();
 }
 
 int drp_gd_wait(drp_ctx* c, int slot, float* rewards_out, float* actions_out) {

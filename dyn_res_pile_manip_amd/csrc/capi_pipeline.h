@@ -752,101 +752,109 @@ int need(drp_ctx* c, bool weights, bool cam, bool goal) {
     return DRP_OK;
 }
 
-// Weight-gradient jobs are queued and go out together (flush_wgrad): one pair of launches for all the jobs whose
-// inputs exist at that point of the stream.  flush_wgrad must run before a kernel overwrites a queued job's g or x.
-void flush_wgrad(drp_ctx* c) {
-    const int n = (int)c->wg_jobs.size();
-    if (n == 0 || c->wg_defer_now) return;
-    WgradJobs J{};
-    int max_blocks = 1;
-    for (int q = 0; q < n; ++q) {
-        J.j[q] = c->wg_jobs[q];
-        J.j[q].part = static_cast<float*>(c->tr_part.p) + (size_t)q * KT_WGRAD_MAX_BLOCKS * 66 * 64;
-        if (J.j[q].blocks > max_blocks) max_blocks = J.j[q].blocks;
+// Weight-gradient jobs are queued and go out together (flush): one pair of launches for all the jobs whose inputs exist at
+// that point of the stream.  flush() must run before a kernel overwrites a queued job's g or x.
+// DEFERRED weight gradients (training, DRP_NO_WGRAD_DEFER=1 turns it off): every operand of an iteration's jobs keeps a
+// buffer of its own (per rollout step, per propagation step), the jobs queue up for the whole backward pass and go out
+// in a handful of launches at its end (flush_all) instead of 25 pairs in between.  The mode is fixed for a pass by begin().
+struct WgradQueue {
+    drp_ctx* const c;
+    std::vector<WgradJob> wg_jobs;              // waiting for the next flush
+    bool defer = false;
+    DevBuf wg_jobs_dev, wg_idx_dev;             // flush_all's jobs and lists on the device
+    std::vector<unsigned char> wg_uploaded;     // what they hold (re-uploaded when the iteration's jobs change)
+    DevBuf tr_part;                             // the jobs' partial sums
+    explicit WgradQueue(drp_ctx* ctx) : c(ctx) {}
+    void begin(bool defer_pass) { wg_jobs.clear(); defer = defer_pass; }
+    template <int IN>
+    void push(const float* g, int ldg, const float* x, int ldx, long M, float* dW, int lane_stride, int k_stride, float* db,
+              float* dwd, const float* dens, int dens_mod, long rows_per_sample) {
+        long blocks = (M + 63) / 64;
+        if (blocks > KT_WGRAD_MAX_BLOCKS) blocks = KT_WGRAD_MAX_BLOCKS;
+        if (blocks < 1) blocks = 1;
+        if ((int)wg_jobs.size() == KT_WGRAD_MAX_JOBS) flush();
+        WgradJob q{};
+        q.g = g; q.x = x; q.dW = dW; q.db = db; q.dwd = dwd; q.dens = dens; q.part = nullptr;
+        q.M = M; q.rows_per_sample = rows_per_sample;
+        q.ldg = ldg; q.ldx = ldx; q.lane_stride = lane_stride; q.k_stride = k_stride; q.dens_mod = dens_mod; q.in = IN;
+        q.blocks = (int)blocks;
+        wg_jobs.push_back(q);
     }
-    c->dv(c->pol.wgrad_mfma ? DV_WGRAD_MFMA : DV_WGRAD_VALU);
-    if (c->pol.wgrad_mfma)
-        hipLaunchKernelGGL(kt_wgrad_mfma_multi, dim3((unsigned)max_blocks, (unsigned)n), dim3(256), KT_WGRAD_MULTI_LDS, c->stream, J);
-    else
-        hipLaunchKernelGGL(kt_wgrad_multi, dim3((unsigned)max_blocks, (unsigned)n), dim3(256), KT_WGRAD_MULTI_LDS, c->stream, J);
-    hipLaunchKernelGGL(kt_wgrad_reduce_multi, dim3(66, (unsigned)n), dim3(256), 0, c->stream, J);
-    c->wg_jobs.clear();
-}
+    // the queued jobs now -- unless the pass defers them: then they wait for flush_all
+    void flush() {
+        const int n = (int)wg_jobs.size();
+        if (n == 0 || defer) return;
+        WgradJobs J{};
+        int max_blocks = 1;
+        for (int q = 0; q < n; ++q) {
+            J.j[q] = wg_jobs[q];
+            J.j[q].part = static_cast<float*>(tr_part.p) + (size_t)q * KT_WGRAD_MAX_BLOCKS * 66 * 64;
+            if (J.j[q].blocks > max_blocks) max_blocks = J.j[q].blocks;
+        }
+        c->dv(c->pol.wgrad_mfma ? DV_WGRAD_MFMA : DV_WGRAD_VALU);
+        if (c->pol.wgrad_mfma)
+            hipLaunchKernelGGL(kt_wgrad_mfma_multi, dim3((unsigned)max_blocks, (unsigned)n), dim3(256), KT_WGRAD_MULTI_LDS, c->stream, J);
+        else
+            hipLaunchKernelGGL(kt_wgrad_multi, dim3((unsigned)max_blocks, (unsigned)n), dim3(256), KT_WGRAD_MULTI_LDS, c->stream, J);
+        hipLaunchKernelGGL(kt_wgrad_reduce_multi, dim3(66, (unsigned)n), dim3(256), 0, c->stream, J);
+        wg_jobs.clear();
+    }
+    // The deferred jobs of a whole backward pass, as planned (dispatch.h: plan_wgrad_lists).  Jobs of one size go through one
+    // launch (blockIdx.y walks that size's slice of `order`); then ONE reduction launch in which a block owns a target dW and
+    // adds its jobs' sums in queue order -- what the in-between flushes did launch after launch, so the gradients keep their bits.
+    int flush_all() {
+        const int n = (int)wg_jobs.size();
+        if (n == 0) return DRP_OK;
+        std::vector<int> blocks(n);
+        std::vector<const void*> target(n);
+        for (int q = 0; q < n; ++q) { blocks[q] = wg_jobs[q].blocks; target[q] = wg_jobs[q].dW; }
+        const WgradListPlan k = plan_wgrad_lists(blocks, target);
+        CHK(ensure(c, tr_part, std::max(k.part_floats, (size_t)KT_WGRAD_MAX_JOBS * KT_WGRAD_MAX_BLOCKS * 66 * 64) * sizeof(float)));
+        for (int q = 0; q < n; ++q) wg_jobs[q].part = static_cast<float*>(tr_part.p) + k.part_off[q];
+        // upload when anything changed (the same shape queues the same jobs iteration after iteration)
+        const size_t jb = (size_t)n * sizeof(WgradJob), ib = k.idx.size() * sizeof(int);
+        std::vector<unsigned char> img(jb + ib);
+        memcpy(img.data(), wg_jobs.data(), jb);
+        memcpy(img.data() + jb, k.idx.data(), ib);
+        if (img != wg_uploaded) {
+            wg_uploaded.swap(img);                  // the copies' source stays alive in the queue
+            CHK(h2d(c, wg_jobs_dev, wg_uploaded.data(), jb));
+            CHK(h2d(c, wg_idx_dev, wg_uploaded.data() + jb, ib));
+        }
+        c->dv(DV_WGRAD_DEFERRED);
+        c->dv(c->pol.wgrad_mfma ? DV_WGRAD_MFMA : DV_WGRAD_VALU);
+        const WgradJob* jd = static_cast<const WgradJob*>(wg_jobs_dev.p);
+        const int* od = static_cast<const int*>(wg_idx_dev.p);
+        for (int a = 0; a < n;) {
+            int b = a;
+            while (b < n && blocks[k.order[b]] == blocks[k.order[a]]) ++b;
+            const dim3 grid((unsigned)blocks[k.order[a]], (unsigned)(b - a));
+            if (c->pol.wgrad_mfma) hipLaunchKernelGGL(kt_wgrad_mfma_list, grid, dim3(256), KT_WGRAD_MULTI_LDS, c->stream, jd, od, a);
+            else hipLaunchKernelGGL(kt_wgrad_list, grid, dim3(256), KT_WGRAD_MULTI_LDS, c->stream, jd, od, a);
+            a = b;
+        }
+        hipLaunchKernelGGL(kt_wgrad_reduce_lists, dim3(66, (unsigned)k.n_targets), dim3(256), 0, c->stream, jd, od + n, od + n + k.n_targets + 1);
+        wg_jobs.clear();
+        HIPCHK(c, hipGetLastError());
+        return DRP_OK;
+    }
+};
 
-// The deferred jobs of a whole backward pass.  Jobs of one size go through one launch (blockIdx.y walks that size's
-// slice of `order`); then ONE reduction launch in which a block owns a target dW and adds its jobs' sums in queue order
-// -- what the in-between flushes did launch after launch, so the gradients keep their bits.
-int flush_wgrad_all(drp_ctx* c) {
-    const int n = (int)c->wg_jobs.size();
-    c->wg_defer_now = false;
-    if (n == 0) return DRP_OK;
-    // partial sums: one slab per job
-    size_t part_floats = 0;
-    std::vector<size_t> part_off(n);
-    for (int q = 0; q < n; ++q) { part_off[q] = part_floats; part_floats += (size_t)c->wg_jobs[q].blocks * 66 * 64; }
-    CHK(ensure(c, c->tr_part, std::max(part_floats, (size_t)KT_WGRAD_MAX_JOBS * KT_WGRAD_MAX_BLOCKS * 66 * 64) * sizeof(float)));
-    for (int q = 0; q < n; ++q) c->wg_jobs[q].part = static_cast<float*>(c->tr_part.p) + part_off[q];
-    // launch order: by size; reduction lists: by target, in queue order
-    std::vector<int> order(n);
-    for (int q = 0; q < n; ++q) order[q] = q;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return c->wg_jobs[a].blocks > c->wg_jobs[b].blocks; });
-    std::vector<float*> targets;
-    std::vector<std::vector<int>> lists;
-    for (int q = 0; q < n; ++q) {
-        size_t k = 0;
-        while (k < targets.size() && targets[k] != c->wg_jobs[q].dW) ++k;
-        if (k == targets.size()) { targets.push_back(c->wg_jobs[q].dW); lists.emplace_back(); }
-        lists[k].push_back(q);
+// Kernels of the planner's and the trainer's entry points read and write pinned host memory (the staged batch, the results' slots).
+// Constructed before the first such launch and disarmed by the DRP_OK return (ok()), this waits for the stream on every other way
+// out: no call returns with work of its own in flight.  The caller still sees the first failure's text, not the wait's.
+struct DrainOnError {
+    drp_ctx* c;
+    bool armed = true;
+    explicit DrainOnError(drp_ctx* ctx) : c(ctx) {}
+    ~DrainOnError() {
+        if (!armed) return;
+        std::string first = std::move(c->err);
+        (void)guarded_wait(c, nullptr);
+        c->err = std::move(first);
     }
-    const int nt = (int)targets.size();
-    std::vector<int> idx;                      // order[n] | tgt_off[nt + 1] | tgt_jobs[n]
-    idx.insert(idx.end(), order.begin(), order.end());
-    int off = 0;
-    for (int k = 0; k < nt; ++k) { idx.push_back(off); off += (int)lists[k].size(); }
-    idx.push_back(off);
-    for (int k = 0; k < nt; ++k) idx.insert(idx.end(), lists[k].begin(), lists[k].end());
-    // upload when anything changed (the same shape queues the same jobs iteration after iteration)
-    const size_t jb = (size_t)n * sizeof(WgradJob), ib = idx.size() * sizeof(int);
-    std::vector<unsigned char> img(jb + ib);
-    memcpy(img.data(), c->wg_jobs.data(), jb);
-    memcpy(img.data() + jb, idx.data(), ib);
-    if (img != c->wg_uploaded) {
-        c->wg_uploaded.swap(img);               // the copies' source stays alive in the context
-        CHK(h2d(c, c->wg_jobs_dev, c->wg_uploaded.data(), jb));
-        CHK(h2d(c, c->wg_idx_dev, c->wg_uploaded.data() + jb, ib));
-    }
-    c->dv(DV_WGRAD_DEFERRED);
-    c->dv(c->pol.wgrad_mfma ? DV_WGRAD_MFMA : DV_WGRAD_VALU);
-    const WgradJob* jd = static_cast<const WgradJob*>(c->wg_jobs_dev.p);
-    const int* od = static_cast<const int*>(c->wg_idx_dev.p);
-    for (int a = 0; a < n;) {
-        int b = a;
-        while (b < n && c->wg_jobs[order[b]].blocks == c->wg_jobs[order[a]].blocks) ++b;
-        const dim3 grid((unsigned)c->wg_jobs[order[a]].blocks, (unsigned)(b - a));
-        if (c->pol.wgrad_mfma) hipLaunchKernelGGL(kt_wgrad_mfma_list, grid, dim3(256), KT_WGRAD_MULTI_LDS, c->stream, jd, od, a);
-        else hipLaunchKernelGGL(kt_wgrad_list, grid, dim3(256), KT_WGRAD_MULTI_LDS, c->stream, jd, od, a);
-        a = b;
-    }
-    hipLaunchKernelGGL(kt_wgrad_reduce_lists, dim3(66, (unsigned)nt), dim3(256), 0, c->stream, jd, od + n, od + n + nt + 1);
-    c->wg_jobs.clear();
-    HIPCHK(c, hipGetLastError());
-    return DRP_OK;
-}
-
-template <int IN>
-void launch_wgrad(drp_ctx* c, const float* g, int ldg, const float* x, int ldx, long M, float* dW, int lane_stride,
-                  int k_stride, float* db, float* dwd, const float* dens, int dens_mod, long rows_per_sample) {
-    long blocks = (M + 63) / 64;
-    if (blocks > KT_WGRAD_MAX_BLOCKS) blocks = KT_WGRAD_MAX_BLOCKS;
-    if (blocks < 1) blocks = 1;
-    if ((int)c->wg_jobs.size() == KT_WGRAD_MAX_JOBS && !c->wg_defer_now) flush_wgrad(c);
-    WgradJob q{};
-    q.g = g; q.x = x; q.dW = dW; q.db = db; q.dwd = dwd; q.dens = dens; q.part = nullptr;
-    q.M = M; q.rows_per_sample = rows_per_sample;
-    q.ldg = ldg; q.ldx = ldx; q.lane_stride = lane_stride; q.k_stride = k_stride; q.dens_mod = dens_mod; q.in = IN;
-    q.blocks = (int)blocks;
-    c->wg_jobs.push_back(q);
-}
+    int ok() { armed = false; return DRP_OK; }
+};
 
 // ---- reverse mode, shared by the gradient-descent planner (capi_gd.h) and the trainer (capi_train.h) ------------------
 
@@ -946,36 +954,36 @@ struct BwdStep {
 // the predictor; per propagation step p = 2, 1, 0 behind its update and behind its edge terms; behind the last update;
 // behind the particle encoder
 struct NodeWgrad {
-    drp_ctx* c;
+    WgradQueue& wq;
     float* G;                       // the gradient blob
     const float* aht;               // the step's aggregated edge effects [3][B*N][64]
     const float* dens;
     void predictor(const BwdStep& s) const {
         const size_t bn = (size_t)s.B * s.N;
-        launch_wgrad<64>(c, s.d.gh, 64, s.eht + 3 * bn * 64, 64, (long)bn, G + W_PR0_W, 64, 1, G + W_PR0_B, nullptr, nullptr, 1, 1);
-        launch_wgrad<3>(c, s.d.hact, 64, s.g_out, 3, (long)bn, G + W_PR1_W, 1, 64, nullptr, nullptr, nullptr, 1, 1);
+        wq.push<64>(s.d.gh, 64, s.eht + 3 * bn * 64, 64, (long)bn, G + W_PR0_W, 64, 1, G + W_PR0_B, nullptr, nullptr, 1, 1);
+        wq.push<3>(s.d.hact, 64, s.g_out, 3, (long)bn, G + W_PR1_W, 1, 64, nullptr, nullptr, nullptr, 1, 1);
     }
     void update(const BwdStep& s, int p) const {       // particle propagator, aggregate columns
         const size_t bn = (size_t)s.B * s.N;
-        launch_wgrad<64>(c, s.d.ge[DRP_PSTEP - 1 - p], 64, aht + (size_t)p * bn * 64, 64, (long)bn, G + W_PP_W + 64, 129, 1,
-                         nullptr, nullptr, nullptr, 1, 1);
+        wq.push<64>(s.d.ge[DRP_PSTEP - 1 - p], 64, aht + (size_t)p * bn * 64, 64, (long)bn, G + W_PP_W + 64, 129, 1,
+                        nullptr, nullptr, nullptr, 1, 1);
     }
     void edge_terms(const BwdStep& s, int p) const {   // relation propagator, receiver and sender columns
         const size_t bn = (size_t)s.B * s.N;
-        launch_wgrad<64>(c, s.d.gp[p], 128, s.eht + (size_t)p * bn * 64, 64, (long)bn, G + W_RP_W + 64, 193, 1,
-                         nullptr, nullptr, nullptr, 1, 1);
-        launch_wgrad<64>(c, s.d.gp[p] + 64, 128, s.eht + (size_t)p * bn * 64, 64, (long)bn, G + W_RP_W + 128, 193, 1,
-                         nullptr, nullptr, nullptr, 1, 1);
+        wq.push<64>(s.d.gp[p], 128, s.eht + (size_t)p * bn * 64, 64, (long)bn, G + W_RP_W + 64, 193, 1,
+                        nullptr, nullptr, nullptr, 1, 1);
+        wq.push<64>(s.d.gp[p] + 64, 128, s.eht + (size_t)p * bn * 64, 64, (long)bn, G + W_RP_W + 128, 193, 1,
+                        nullptr, nullptr, nullptr, 1, 1);
     }
     void cnode(const BwdStep& s) const {               // particle propagator, encoder columns + density column + bias
         const size_t bn = (size_t)s.B * s.N;
-        launch_wgrad<64>(c, s.g_cnode, 64, s.eht, 64, (long)bn, G + W_PP_W, 129, 1, G + W_PP_B, G + W_PP_W + 128, dens, s.B,
-                         (long)s.N);
+        wq.push<64>(s.g_cnode, 64, s.eht, 64, (long)bn, G + W_PP_W, 129, 1, G + W_PP_B, G + W_PP_W + 128, dens, s.B,
+                        (long)s.N);
     }
     void encoder(const BwdStep& s) const {             // particle encoder
         const size_t bn = (size_t)s.B * s.N;
-        launch_wgrad<64>(c, s.d.gpe, 64, s.d.a1n, 64, (long)bn, G + W_PE2_W, 64, 1, G + W_PE2_B, nullptr, nullptr, 1, 1);
-        launch_wgrad<5>(c, s.d.gh1, 64, s.d.xn, 8, (long)bn, G + W_PE0_W, 5, 1, G + W_PE0_B, nullptr, nullptr, 1, 1);
+        wq.push<64>(s.d.gpe, 64, s.d.a1n, 64, (long)bn, G + W_PE2_W, 64, 1, G + W_PE2_B, nullptr, nullptr, 1, 1);
+        wq.push<5>(s.d.gh1, 64, s.d.xn, 8, (long)bn, G + W_PE0_W, 5, 1, G + W_PE0_B, nullptr, nullptr, 1, 1);
     }
 };
 
@@ -1008,7 +1016,7 @@ void launch_node_stages(drp_ctx* c, const BwdStep& s, dim3 egrid, int chunks, co
         }
         if (wg) {
             wg->edge_terms(s, p);
-            flush_wgrad(c);                              // (not deferred:) before the next kernel overwrites g_eff (and, next step, g_proj)
+            wg->wq.flush();                              // (not deferred:) before the next kernel overwrites g_eff (and, next step, g_proj)
         }
         ProbeScope ps(c, KC_BWD_NODE);
         if (p > 0)
@@ -1025,7 +1033,7 @@ void launch_node_stages(drp_ctx* c, const BwdStep& s, dim3 egrid, int chunks, co
     }
     if (wg) {
         wg->encoder(s);
-        flush_wgrad(c);
+        wg->wq.flush();
     }
 }
 

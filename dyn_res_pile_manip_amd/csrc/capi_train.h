@@ -25,8 +25,8 @@ TrArena tr_layout(int B, int H, int N, int M = 0) {
     return a;
 }
 const float* tr_given(const drp_ctx* c) { return static_cast<const float*>(c->tr_arena.p); }
-const int* tr_nums(const drp_ctx* c, int B, int N) {
-    return reinterpret_cast<const int*>(static_cast<const char*>(c->tr_arena.p) + tr_layout(B, c->tr_nroll, N).nums);
+const int* tr_nums(const drp_ctx* c, const TrArena& lay) {
+    return reinterpret_cast<const int*>(static_cast<const char*>(c->tr_arena.p) + lay.nums);
 }
 // what seeds the reverse pass: the tracked loss (kt_mse_grad against the given next states) or the Chamfer loss against
 // untracked target clouds (k_chamfer.h); the targets as the HOST gave them (the entry point stages them behind the batch)
@@ -37,23 +37,36 @@ struct TrLoss {
     const int32_t* target_nums = nullptr;   // [B][H]
     int M = 0;
 };
+// one pass over a staged batch: everything train_forward_backward reads beside the shapes and the session
+struct TrainPass {
+    int engine = DRP_ENGINE_FUSED;  // which engine writes the tape (pick_tape_engine)
+    bool backward = false;          // false: the forward pass and the loss alone
+    bool defer = false;             // the weight gradients wait for the end of the pass (and the dumps have a buffer per step)
+    double* loss_terms = nullptr;   // [H][B], where the loss kernel stores: c->tr_loss, or pinned host memory the caller reads
+    TrArena lay{};                  // the batch in c->tr_arena
+    TrLoss lk;
+};
 // forward over n_rollout steps (+ loss), optionally the backward pass with weight gradients
-int train_forward_backward(drp_ctx* c, int B, int N, bool backward, const TrLoss& lk) {
+int train_forward_backward(drp_ctx* c, int B, int N, const TrainPass& tp) {
     const int H = c->tr_nroll;
+    const bool backward = tp.backward, defer = tp.defer;
+    const TrLoss& lk = tp.lk;
+    WgradQueue& wq = *c->wgrad;
+    wq.begin(defer);
     const size_t bn = (size_t)B * N, bn64 = bn * 64, bnk = bn * DRP_K;
     const size_t hstride = (size_t)H * N * 3;                 // predicted states [B][H][N][3]
     const size_t in_stride = (size_t)(H + 1) * N * 3;         // given states     [B][H+1][N][3]
     hipStream_t st = c->stream;
     float* states = ptr<float>(c->states);
     const float* given = tr_given(c);
-    const int* nums = tr_nums(c, B, N);
+    const int* nums = tr_nums(c, tp.lay);
     float* g_state = ptr<float>(c->g_state);
-    double* loss = c->tr_loss_host ? c->tr_loss_host : ptr<double>(c->tr_loss);      // pinned host memory: the terms land where the caller reads them
+    double* loss = tp.loss_terms;
     const float scale = 1.0f / (float)(H * B);
     {
         const float* cself = nullptr;
         const uint8_t* cself_ok = nullptr;
-        CHK(prepare_cself(c, B, N, B, &cself, &cself_ok, c->tr_engine));
+        CHK(prepare_cself(c, B, N, B, &cself, &cself_ok, tp.engine));
         TapeFwd f{};
         f.s0 = given; f.s0_mod = B; f.s0_stride = in_stride;
         f.mod = B;
@@ -61,7 +74,7 @@ int train_forward_backward(drp_ctx* c, int B, int N, bool backward, const TrLoss
         f.padded = true;                // collate_fn pads with zero rows: coincident particles
         f.tape = backward; f.agg_hist = true;
         f.cself = cself; f.cself_ok = cself_ok;
-        CHK(run_tape_forward(c, c->tr_engine, B, N, H, f));
+        CHK(run_tape_forward(c, tp.engine, B, N, H, f));
     }
     // the loss of every step and d loss / d s_pred_t (train/train_gnn_dyn.py:184-186, :203) in one launch
     if (lk.kind == TR_LOSS_MSE) {
@@ -71,7 +84,7 @@ int train_forward_backward(drp_ctx* c, int B, int N, bool backward, const TrLoss
     } else {
         // the same slot of the stream, the same outputs and the same zero-fill: step t of the predictions against step t of the
         // staged target clouds
-        const TrArena lay = tr_layout(B, H, N, lk.M);
+        const TrArena& lay = tp.lay;
         const char* ar = static_cast<const char*>(c->tr_arena.p);
         KcArgs a{};
         a.pred = states; a.p_bstride = hstride; a.p_tstride = (size_t)N * 3;
@@ -100,7 +113,6 @@ int train_forward_backward(drp_ctx* c, int B, int N, bool backward, const TrLoss
     launch_reverse_lists(c, ptr<int16_t>(c->tape_idx), ptr<uint8_t>(c->tape_cnt), N, B * H, nums, B);
     // deferred weight gradients: what a job reads keeps a buffer per rollout step t (g_eff and g_proj: per propagation step
     // too; slot 0 of g_eff is the transient copy the predictor writes and the particle encoder reads)
-    const bool defer = c->wg_defer_now;
     const size_t per_t = defer ? 1 : 0;
     // the node stages of a rollout step in ONE launch (kmb_step_bwd<dump>) or a launch per stage (dispatch.h: plan_train_backward)
     const TrainBwdPlan k = plan_train_backward(c->pol, c->n_cu, B, N, defer);
@@ -135,7 +147,7 @@ int train_forward_backward(drp_ctx* c, int B, int N, bool backward, const TrLoss
         }
         s.d.gpe = ptr<float>(c->tr_gpe) + tt * bn64; s.d.a1n = ptr<float>(c->tr_a1n) + tt * bn64;
         s.d.gh1 = ptr<float>(c->tr_gh1) + tt * bn64; s.d.xn = ptr<float>(c->tr_xn) + tt * bn * 8;
-        const NodeWgrad wg{c, G, ptr<float>(c->agg_hist) + (size_t)t * 3 * bn64, dens};
+        const NodeWgrad wg{wq, G, ptr<float>(c->agg_hist) + (size_t)t * 3 * bn64, dens};
         if (fused) {
             // everything between the loss gradient and the relation encoder's backward in ONE launch (kmb_step_bwd<DUMP>): the
             // operands of the weight gradients are its dumps; the jobs in the stage kernels' queue order
@@ -168,17 +180,17 @@ int train_forward_backward(drp_ctx* c, int B, int N, bool backward, const TrLoss
         if (g_prev != nullptr)
             hipLaunchKernelGGL(kb_gather_pos, dim3((N + 255) / 256, B), dim3(256), 0, st, ptr<float>(c->gpos_edge),
                                s.rev_off, s.rev, N, g_prev, (size_t)N * 3, s.cnt, (const float*)g_out);
-        launch_wgrad<64>(c, ed.gce, 64, ed.re, 64, (long)bnk, G + W_RP_W, 193, 1, G + W_RP_B, G + W_RP_W + 192, dens, B,
-                         (long)N * DRP_K);
-        launch_wgrad<64>(c, ed.g3, 64, ed.a2, 64, (long)bnk, G + W_RE4_W, 64, 1, G + W_RE4_B, nullptr, nullptr, 1, 1);
-        launch_wgrad<64>(c, ed.g2, 64, ed.a1, 64, (long)bnk, G + W_RE2_W, 64, 1, G + W_RE2_B, nullptr, nullptr, 1, 1);
-        launch_wgrad<6>(c, ed.g1, 64, ed.x0, 8, (long)bnk, G + W_RE0_W, 6, 1, G + W_RE0_B, nullptr, nullptr, 1, 1);
-        flush_wgrad(c);                                  // the next rollout step rewrites the dumps these jobs read
+        wq.push<64>(ed.gce, 64, ed.re, 64, (long)bnk, G + W_RP_W, 193, 1, G + W_RP_B, G + W_RP_W + 192, dens, B,
+                    (long)N * DRP_K);
+        wq.push<64>(ed.g3, 64, ed.a2, 64, (long)bnk, G + W_RE4_W, 64, 1, G + W_RE4_B, nullptr, nullptr, 1, 1);
+        wq.push<64>(ed.g2, 64, ed.a1, 64, (long)bnk, G + W_RE2_W, 64, 1, G + W_RE2_B, nullptr, nullptr, 1, 1);
+        wq.push<6>(ed.g1, 64, ed.x0, 8, (long)bnk, G + W_RE0_W, 6, 1, G + W_RE0_B, nullptr, nullptr, 1, 1);
+        wq.flush();                                  // the next rollout step rewrites the dumps these jobs read
     }
-    flush_wgrad(c);
+    wq.flush();
     // bias of the predictor's last layer: the column sums of every step's d loss / d s_pred (all final by now), one launch
     hipLaunchKernelGGL(kt_colsum3, dim3(1), dim3(1024), 0, st, g_state, (long)(H * bn), G + W_PR1_B);
-    if (defer) CHK(flush_wgrad_all(c));
+    if (defer) CHK(wq.flush_all());
     HIPCHK(c, hipGetLastError());
     return DRP_OK;
 }
@@ -264,7 +276,7 @@ int drp_train_begin(drp_ctx* c, int n_rollout, double lr, double beta1) {
     CHK(ensure(c, c->tr_grad, ((size_t)TR_GRAD_PAD + (size_t)n_rollout * c->n_cu + 1) * sizeof(float)));
     CHK(ensure(c, c->tr_m, (size_t)W_TOTAL * sizeof(float)));
     CHK(ensure(c, c->tr_v, (size_t)W_TOTAL * sizeof(float)));
-    CHK(ensure(c, c->tr_part, (size_t)KT_WGRAD_MAX_JOBS * KT_WGRAD_MAX_BLOCKS * 66 * 64 * sizeof(float)));
+    CHK(ensure(c, c->wgrad->tr_part, (size_t)KT_WGRAD_MAX_JOBS * KT_WGRAD_MAX_BLOCKS * 66 * 64 * sizeof(float)));
     HIPCHK(c, hipMemsetAsync(c->tr_m.p, 0, (size_t)W_TOTAL * sizeof(float), c->stream));
     HIPCHK(c, hipMemsetAsync(c->tr_v.p, 0, (size_t)W_TOTAL * sizeof(float), c->stream));
     CHK(guarded_wait(c, nullptr));
@@ -276,10 +288,9 @@ int drp_train_begin(drp_ctx* c, int n_rollout, double lr, double beta1) {
 }
 
 namespace {
-// drp_train_step and drp_train_step_untracked: one body, the loss kind and the targets in `lk`
-int train_step_body(drp_ctx* c, const float* states, const float* states_delta, const float* attrs,
-                    const int32_t* particle_nums, const float* particle_dens, int B, int N, const TrLoss& lk, int mode,
-                    double* loss_out, float* grad_out) {
+// ---- drp_train_step and drp_train_step_untracked: one body (train_step_body), the loss kind and the targets in `lk` ----
+int train_check_args(drp_ctx* c, const float* states, const float* states_delta, const float* attrs, const int32_t* particle_nums,
+                     const float* particle_dens, int B, int N, const TrLoss& lk, int mode) {
     if (!c || !c->tr_on) return fail(c, DRP_ESTATE, "drp_train_begin not called");
     CHK(check_bn(c, B, N));
     if (!states || !states_delta || !attrs || !particle_nums || !particle_dens) return fail(c, DRP_EINVAL, "null argument");
@@ -295,67 +306,30 @@ int train_step_body(drp_ctx* c, const float* states, const float* states_delta, 
                 return fail(c, DRP_EINVAL, "target_nums[%d][%d]=%d outside 1..%d", e / c->tr_nroll, e % c->tr_nroll,
                             lk.target_nums[e], lk.M);
     }
-    HIPCHK(c, hipSetDevice(c->device));
-    end_sessions(c);
-    {
-        float amax = 0.0f;                                    // a_cur = attrs[:, 0]
-        for (int b = 0; b < B; ++b) amax = fmaxf(amax, max_abs(attrs + (size_t)b * (c->tr_nroll + 1) * N, (size_t)N));
-        CHK(pick_tape_engine(c, amax, max_abs(particle_dens, (size_t)B), max_abs(states_delta, (size_t)B * c->tr_nroll * N * 3), &c->tr_engine));
-    }
+    return DRP_OK;
+}
+
+// every buffer of the step at its size, and whether the weight gradients of its backward pass are deferred (tp.defer)
+int train_ensure_workspace(drp_ctx* c, int B, int N, TrainPass& tp) {
     const int H = c->tr_nroll;
     const size_t bn = (size_t)B * N, bn64 = bn * 64, bnk = bn * DRP_K;
-    const bool backward = mode != DRP_TRAIN_EVAL;
-    // the batch in one copy: packed into pinned staging in the caller's layouts, unpacked by one launch (kt_unpack_inputs)
-    const TrArena lay = tr_layout(B, H, N, lk.kind == TR_LOSS_CHAMFER ? lk.M : 0);
-    // behind the batch: what comes BACK after the one wait -- the loss terms [H][B] and the give-up flag of kmb_step_bwd's
-    // barrier (pinned: the copies are asynchronous, nothing on the way touches pageable memory or this frame)
-    const size_t back_off = lay.bytes, back_bytes = (size_t)H * B * sizeof(double) + 16;
-    // kernels read and write this buffer directly: nothing of an earlier call (one that returned on an error before its
-    // wait, say) may still be in flight when it goes
-    if (c->tr_pin.p && c->tr_pin.cap < lay.bytes + back_bytes) (void)hipStreamSynchronize(c->stream);
-    CHK(ensure_pinned(c, c->tr_pin, lay.bytes + back_bytes));
-    {
-        char* pin = ptr<char>(c->tr_pin);
-        memcpy(pin + lay.states, states, (size_t)B * (H + 1) * N * 3 * sizeof(float));
-        memcpy(pin + lay.sdelta, states_delta, (size_t)B * H * N * 3 * sizeof(float));
-        memcpy(pin + lay.attrs, attrs, (size_t)B * (H + 1) * N * sizeof(float));
-        memcpy(pin + lay.dens, particle_dens, (size_t)B * sizeof(float));
-        memcpy(pin + lay.nums, particle_nums, (size_t)B * sizeof(int));
-        if (lk.kind == TR_LOSS_CHAMFER) {
-            memcpy(pin + lay.targets, lk.targets, (size_t)B * H * lk.M * 3 * sizeof(float));
-            memcpy(pin + lay.tnums, lk.target_nums, (size_t)B * H * sizeof(int));
-        }
-    }
-    CHK(ensure(c, c->tr_arena, lay.bytes));
+    // behind the batch in tr_pin: what comes BACK after the one wait -- the loss terms [H][B] and the give-up flag of kmb_step_bwd's
+    // barrier (pinned: the copies are asynchronous, nothing on the way touches pageable memory or the caller's frame)
+    // kernels read and write tr_pin directly; no wait before it goes: every earlier call has waited for or drained its work (DrainOnError)
+    CHK(ensure_pinned(c, c->tr_pin, tp.lay.bytes + (size_t)H * B * sizeof(double) + 16));
+    CHK(ensure(c, c->tr_arena, tp.lay.bytes));
     CHK(ensure(c, c->ws.attr, bn * sizeof(float)));
     CHK(ensure(c, c->ws.dens, (size_t)B * sizeof(float)));
     CHK(ensure(c, c->tape_sdelta, (size_t)H * bn * 3 * sizeof(float)));
-    {
-        // the unpacking launch IS the upload: it reads the staged batch from the pinned host buffer (device-visible) and leaves
-        // the arena copy for the kernels that read the given states; DRP_TRAIN_COPY_UPLOAD=1: a copy on the stream first
-        const bool by_kernel = !c->train_copy_upload;
-        if (!by_kernel) CHK(h2d(c, c->tr_arena, c->tr_pin.p, lay.bytes));
-        const char* ar = by_kernel ? ptr<const char>(c->tr_pin) : static_cast<const char*>(c->tr_arena.p);
-        const size_t total = (size_t)H * bn * 3;
-        hipLaunchKernelGGL(kt_unpack_inputs, dim3((unsigned)std::min<size_t>((total + 255) / 256, 1024)), dim3(256), 0, c->stream,
-                           reinterpret_cast<const float*>(ar + lay.sdelta), reinterpret_cast<const float*>(ar + lay.attrs),
-                           reinterpret_cast<const float*>(ar + lay.dens), B, H, N, ptr<float>(c->tape_sdelta), ptr<float>(c->ws.attr),
-                           ptr<float>(c->ws.dens), by_kernel ? ptr<const float4>(c->tr_pin) : (const float4*)nullptr,
-                           by_kernel ? static_cast<float4*>(c->tr_arena.p) : (float4*)nullptr, by_kernel ? lay.bytes / 16 : (size_t)0);
-    }
-    CHK(ensure_step_ws(c, c->ws, B, N, c->tr_engine));
+    CHK(ensure_step_ws(c, c->ws, B, N, tp.engine));
     CHK(ensure(c, c->states, (size_t)H * bn * 3 * sizeof(float)));
     CHK(ensure(c, c->g_state, (size_t)H * bn * 3 * sizeof(float)));
-    c->wg_defer_now = false;
-    c->wg_jobs.clear();
-    bool defer_batch = false;               // re-armed before every pass of the step (flush_wgrad_all clears wg_defer_now)
-    if (backward) {
+    tp.defer = false;
+    if (tp.backward) {
         // deferred weight gradients keep every job's operands until the end of the backward pass: H copies of the node-level
         // dumps (3 H + 1 of g_eff, 3 H of g_proj) and of the relation encoder's dumps -- 0.24 GB per rollout step at 32 x 300
         const size_t keep_bytes = (size_t)H * (16 * bn64 + 7 * bnk * 64 + bnk * 8 + bn * 8) * sizeof(float);
-        const bool defer = c->wgrad_defer && keep_bytes <= ((size_t)8 << 30);
-        c->wg_defer_now = defer;
-        defer_batch = defer;
+        const bool defer = tp.defer = c->wgrad_defer && keep_bytes <= ((size_t)8 << 30);
         const size_t kt = defer ? (size_t)H : 1;
         CHK(ensure_tape(c, B, N, H, H));
         CHK(ensure(c, c->agg_hist, (size_t)H * 3 * bn64 * sizeof(float)));
@@ -370,75 +344,130 @@ int train_step_body(drp_ctx* c, const float* states, const float* states_delta, 
         CHK(ensure(c, c->ed_x0, kt * bnk * 8 * sizeof(float)));
     }
     CHK(ensure(c, c->tr_loss, (size_t)H * B * sizeof(double)));
+    return DRP_OK;
+}
+
+// the batch in one copy: packed into pinned staging in the caller's layouts, unpacked by one launch (kt_unpack_inputs)
+int train_stage_batch(drp_ctx* c, const float* states, const float* states_delta, const float* attrs, const int32_t* particle_nums,
+                      const float* particle_dens, int B, int N, const TrainPass& tp) {
+    const int H = c->tr_nroll;
+    const TrArena& lay = tp.lay;
+    char* pin = ptr<char>(c->tr_pin);
+    memcpy(pin + lay.states, states, (size_t)B * (H + 1) * N * 3 * sizeof(float));
+    memcpy(pin + lay.sdelta, states_delta, (size_t)B * H * N * 3 * sizeof(float));
+    memcpy(pin + lay.attrs, attrs, (size_t)B * (H + 1) * N * sizeof(float));
+    memcpy(pin + lay.dens, particle_dens, (size_t)B * sizeof(float));
+    memcpy(pin + lay.nums, particle_nums, (size_t)B * sizeof(int));
+    if (tp.lk.kind == TR_LOSS_CHAMFER) {
+        memcpy(pin + lay.targets, tp.lk.targets, (size_t)B * H * tp.lk.M * 3 * sizeof(float));
+        memcpy(pin + lay.tnums, tp.lk.target_nums, (size_t)B * H * sizeof(int));
+    }
+    // the unpacking launch IS the upload: it reads the staged batch from the pinned host buffer (device-visible) and leaves
+    // the arena copy for the kernels that read the given states; DRP_TRAIN_COPY_UPLOAD=1: a copy on the stream first
+    const bool by_kernel = !c->train_copy_upload;
+    if (!by_kernel) CHK(h2d(c, c->tr_arena, c->tr_pin.p, lay.bytes));
+    const char* ar = by_kernel ? ptr<const char>(c->tr_pin) : static_cast<const char*>(c->tr_arena.p);
+    const size_t total = (size_t)H * B * N * 3;
+    hipLaunchKernelGGL(kt_unpack_inputs, dim3((unsigned)std::min<size_t>((total + 255) / 256, 1024)), dim3(256), 0, c->stream,
+                       reinterpret_cast<const float*>(ar + lay.sdelta), reinterpret_cast<const float*>(ar + lay.attrs),
+                       reinterpret_cast<const float*>(ar + lay.dens), B, H, N, ptr<float>(c->tape_sdelta), ptr<float>(c->ws.attr),
+                       ptr<float>(c->ws.dens), by_kernel ? ptr<const float4>(c->tr_pin) : (const float4*)nullptr,
+                       by_kernel ? static_cast<float4*>(c->tr_arena.p) : (float4*)nullptr, by_kernel ? lay.bytes / 16 : (size_t)0);
+    return DRP_OK;
+}
+
+// One pass over the staged batch, the optimiser step, the re-pack, the wait.  `back`: the loss terms [H][B] and the give-up flag
+// in tr_pin; *gave_up: kmb_step_bwd's barrier among the workgroups of a group gave up after two seconds (k_backward_mfma.h)
+// and set the flag behind its counters -- the gradient of such a pass is partial.  The optimiser step reads the flag ON THE
+// DEVICE and moves nothing when it is set (k_adam's `skip`); the iteration count advances only once it has come back clear.
+int train_attempt(drp_ctx* c, int B, int N, const TrainPass& tp, int mode, bool want_loss, float* grad_out, double* back, bool* gave_up) {
+    const int H = c->tr_nroll;
+    unsigned* const flag_host = reinterpret_cast<unsigned*>(back + (size_t)H * B);
+    CHK(train_forward_backward(c, B, N, tp));
+    const int f_spw = (B + c->n_cu - 1) / c->n_cu, f_groups = (B + f_spw - 1) / f_spw;
+    const unsigned* const flag_dev = reinterpret_cast<const unsigned*>(ptr<float>(c->tr_grad) + TR_GRAD_PAD + (size_t)H * f_groups);
+    *flag_host = 0;
+    // update iterations end WITHOUT a copy on the stream: the loss terms are stored to pinned host memory by the loss kernel,
+    // the optimiser step writes the updated blob and the barrier's flag there, kt_repack_split the range shift -- a copy
+    // engine's transfer between kernels costs tens of microseconds of hand-over (tools/train_trace.sh)
+    const bool direct = mode == DRP_TRAIN_UPDATE && c->repack_device && !c->train_copy_upload;
+    if (c->debug_force_giveup && tp.backward) {        // tests: the flag as a timed-out barrier would leave it, once
+        HIPCHK(c, hipMemsetAsync(const_cast<unsigned*>(flag_dev), 1, sizeof(unsigned), c->stream));
+        c->debug_force_giveup = false;
+    }
+    if (want_loss && tp.loss_terms != back) CHK(d2h(c, back, c->tr_loss.p, (size_t)H * B * sizeof(double)));
+    if (grad_out && tp.backward) CHK(d2h(c, grad_out, c->tr_grad.p, (size_t)W_TOTAL * sizeof(float)));
+    if (tp.backward && !direct) CHK(d2h(c, flag_host, flag_dev, sizeof(unsigned)));
+    bool repacked = false;
+    if (mode == DRP_TRAIN_UPDATE) {
+        const long iter = c->tr_iter + 1;
+        const double bc1 = 1.0 - pow(c->tr_beta1, (double)iter), bc2 = 1.0 - pow(0.999, (double)iter);
+        const float inf = __builtin_inff();
+        if (direct) CHK(ensure_repack_maps(c));          // (allocates w_pin)
+        hipLaunchKernelGGL(k_adam, dim3((W_TOTAL + 255) / 256), dim3(256), 0, c->stream, ptr<float>(c->w_raw),
+                           ptr<float>(c->tr_grad), ptr<float>(c->tr_m), ptr<float>(c->tr_v), (int)W_TOTAL,
+                           (float)(c->tr_lr / bc1), (float)sqrt(bc2), make_float4(-inf, -inf, -inf, -inf),
+                           make_float4(inf, inf, inf, inf), (float)c->tr_beta1, direct ? ptr<float>(c->w_pin) : (float*)nullptr, flag_dev,
+                           direct ? flag_host : (unsigned*)nullptr);
+        if (hipGetLastError() != hipSuccess) return fail(c, DRP_EHIP, "k_adam launch");
+        c->f64_w_valid = false;           // the float64 copy is of the old blob: the next *_f64 call widens the new one
+        // the engines read packed copies of the weights: rebuild them from the blob (unchanged if the step was skipped)
+        if (c->repack_device) {
+            CHK(repack_on_device(c, direct));
+            repacked = true;
+        } else {
+            std::vector<float> blob((size_t)W_TOTAL);
+            CHK(d2h(c, blob.data(), c->w_raw.p, (size_t)W_TOTAL * sizeof(float)));
+            CHK(guarded_wait(c, nullptr));
+            CHK(install_weights(c, blob));
+        }
+    }
+    CHK(drp_sync(c));
+    *gave_up = *flag_host != 0;
+    if (repacked && !*gave_up) CHK(finish_repack(c));      // (a skipped step wrote no blob: the weights are what they were)
+    if (!*gave_up && mode == DRP_TRAIN_UPDATE) c->tr_iter += 1;
+    return DRP_OK;
+}
+
+int train_step_body(drp_ctx* c, const float* states, const float* states_delta, const float* attrs,
+                    const int32_t* particle_nums, const float* particle_dens, int B, int N, const TrLoss& lk, int mode,
+                    double* loss_out, float* grad_out) {
+    CHK(train_check_args(c, states, states_delta, attrs, particle_nums, particle_dens, B, N, lk, mode));
+    HIPCHK(c, hipSetDevice(c->device));
+    end_sessions(c);
+    const int H = c->tr_nroll;
+    TrainPass tp;
+    {
+        float amax = 0.0f;                                    // a_cur = attrs[:, 0]
+        for (int b = 0; b < B; ++b) amax = fmaxf(amax, max_abs(attrs + (size_t)b * (H + 1) * N, (size_t)N));
+        CHK(pick_tape_engine(c, amax, max_abs(particle_dens, (size_t)B), max_abs(states_delta, (size_t)B * H * N * 3), &tp.engine));
+    }
+    tp.backward = mode != DRP_TRAIN_EVAL;
+    tp.lay = tr_layout(B, H, N, lk.kind == TR_LOSS_CHAMFER ? lk.M : 0);
+    tp.lk = lk;
+    CHK(train_ensure_workspace(c, B, N, tp));
     c->marks.lastH = H;
-    double* const parts = reinterpret_cast<double*>(ptr<char>(c->tr_pin) + back_off);
-    unsigned* const gave_up = reinterpret_cast<unsigned*>(parts + (size_t)H * B);
-    // kmb_step_bwd's barrier among the workgroups of a group gives up after two seconds (k_backward_mfma.h) and sets a flag
-    // behind its counters; the gradient of such a pass is partial.  The optimiser step reads the flag ON THE DEVICE and moves
-    // nothing when it is set (k_adam's `skip`), the iteration count advances only once the flag has come back clear, and the
-    // step runs again with one workgroup per group (no barrier to wait at) -- for the rest of the context's life.
-    c->tr_loss_host = (loss_out && !c->train_copy_upload) ? parts : nullptr;
-    struct LossHostReset { drp_ctx* c; ~LossHostReset() { c->tr_loss_host = nullptr; } } loss_host_reset{c};
-    for (int attempt = 0; ; ++attempt) {
-        c->wg_defer_now = defer_batch;
-        c->wg_jobs.clear();
-        CHK(train_forward_backward(c, B, N, backward, lk));
-        const int f_spw = (B + c->n_cu - 1) / c->n_cu, f_groups = (B + f_spw - 1) / f_spw;
-        const unsigned* const flag_dev = reinterpret_cast<const unsigned*>(ptr<float>(c->tr_grad) + TR_GRAD_PAD + (size_t)H * f_groups);
-        *gave_up = 0;
-        // update iterations end WITHOUT a copy on the stream: the loss terms are stored to pinned host memory by the loss kernel,
-        // the optimiser step writes the updated blob and the barrier's flag there, kt_repack_split the range shift -- a copy
-        // engine's transfer between kernels costs tens of microseconds of hand-over (tools/train_trace.sh)
-        const bool direct = mode == DRP_TRAIN_UPDATE && c->repack_device && !c->train_copy_upload;
-        if (c->debug_force_giveup && attempt == 0 && backward) {        // tests: the flag as a timed-out barrier would leave it, once
-            HIPCHK(c, hipMemsetAsync(const_cast<unsigned*>(flag_dev), 1, sizeof(unsigned), c->stream));
-            c->debug_force_giveup = false;
-        }
-        if (loss_out && !c->tr_loss_host) CHK(d2h(c, parts, c->tr_loss.p, (size_t)H * B * sizeof(double)));
-        if (grad_out && backward) CHK(d2h(c, grad_out, c->tr_grad.p, (size_t)W_TOTAL * sizeof(float)));
-        if (backward && !direct) CHK(d2h(c, gave_up, flag_dev, sizeof(unsigned)));
-        bool repacked = false;
-        if (mode == DRP_TRAIN_UPDATE) {
-            const long iter = c->tr_iter + 1;
-            const double bc1 = 1.0 - pow(c->tr_beta1, (double)iter), bc2 = 1.0 - pow(0.999, (double)iter);
-            const float inf = __builtin_inff();
-            if (direct) CHK(ensure_repack_maps(c));          // (allocates w_pin)
-            hipLaunchKernelGGL(k_adam, dim3((W_TOTAL + 255) / 256), dim3(256), 0, c->stream, ptr<float>(c->w_raw),
-                               ptr<float>(c->tr_grad), ptr<float>(c->tr_m), ptr<float>(c->tr_v), (int)W_TOTAL,
-                               (float)(c->tr_lr / bc1), (float)sqrt(bc2), make_float4(-inf, -inf, -inf, -inf),
-                               make_float4(inf, inf, inf, inf), (float)c->tr_beta1, direct ? ptr<float>(c->w_pin) : (float*)nullptr, flag_dev,
-                               direct ? gave_up : (unsigned*)nullptr);
-            if (hipGetLastError() != hipSuccess) { (void)drp_sync(c); return fail(c, DRP_EHIP, "k_adam launch"); }
-            c->f64_w_valid = false;           // the float64 copy is of the old blob: the next *_f64 call widens the new one
-            // the engines read packed copies of the weights: rebuild them from the blob (unchanged if the step was skipped)
-            if (c->repack_device) {
-                const int rc = repack_on_device(c, direct);
-                if (rc != DRP_OK) { (void)drp_sync(c); return rc; }
-                repacked = true;
-            } else {
-                std::vector<float> blob((size_t)W_TOTAL);
-                CHK(d2h(c, blob.data(), c->w_raw.p, (size_t)W_TOTAL * sizeof(float)));
-                CHK(guarded_wait(c, nullptr));
-                CHK(install_weights(c, blob));
-            }
-        }
-        CHK(drp_sync(c));
-        if (repacked && !*gave_up) CHK(finish_repack(c));      // (a skipped step wrote no blob: the weights are what they were)
-        if (!*gave_up) {
-            if (mode == DRP_TRAIN_UPDATE) c->tr_iter += 1;
-            break;
-        }
-        if (attempt > 0 || c->pol.train_parts == 1)
-            return fail(c, DRP_EHIP, "kmb_step_bwd: a workgroup waited two seconds for the others of its group, with one workgroup per group too");
+    double* const back = reinterpret_cast<double*>(ptr<char>(c->tr_pin) + tp.lay.bytes);
+    tp.loss_terms = (loss_out && !c->train_copy_upload) ? back : ptr<double>(c->tr_loss);   // pinned: the terms land where this call reads them
+    DrainOnError drain(c);
+    CHK(train_stage_batch(c, states, states_delta, attrs, particle_nums, particle_dens, B, N, tp));
+    // a pass whose barrier gave up runs again with one workgroup per group (no barrier to wait at) -- for the rest of the
+    // context's life
+    bool gave_up = false;
+    CHK(train_attempt(c, B, N, tp, mode, loss_out != nullptr, grad_out, back, &gave_up));
+    if (gave_up && c->pol.train_parts != 1) {
         c->pol.train_parts = 1;                     // the device is shared or masked: the groups' workgroups are not all resident
         c->dv(DV_TRAIN_BARRIER_RETRY);
+        CHK(train_attempt(c, B, N, tp, mode, loss_out != nullptr, grad_out, back, &gave_up));
     }
+    if (gave_up)
+        return fail(c, DRP_EHIP, "kmb_step_bwd: a workgroup waited two seconds for the others of its group, with one workgroup per group too");
     if (loss_out) {
         double total = 0.0;                     // fixed order: step-major, then sample
-        for (size_t q = 0; q < (size_t)H * B; ++q) total += parts[q];
+        for (size_t q = 0; q < (size_t)H * B; ++q) total += back[q];
         *loss_out = total;
     }
-    return DRP_OK;
+    return drain.ok();
 }
 }  // namespace
 

@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <initializer_list>
+#include <vector>
 
 namespace dispatch {
 
@@ -658,6 +659,42 @@ inline TrainBwdPlan plan_train_backward(const DispatchPolicy& p, int n_cu, int B
         // L2 round trips per tile and phase: 27 us against 6); many: a tile per wave, the waves hide each other's latency
         k.coop = p.train_coop >= 0 ? p.train_coop != 0 : (group_tiles + k.parts - 1) / k.parts <= 2 * COOP_SLOTS;
     }
+    return k;
+}
+
+// ---- the deferred weight gradients of a whole backward pass (capi_pipeline.h: WgradQueue::flush_all) ----------------------
+// Job q is `blocks[q]` workgroups adding into target `target[q]` (any identity: the address of its dW).  A slab of partial
+// sums per job; jobs of one size through one launch, the larger first (stable: queue order among equals); one reduction
+// block per target, targets in first-seen order, each adding its jobs' sums in queue order.
+struct WgradListPlan {
+    std::vector<size_t> part_off;   // [n]: where job q's slab starts, in floats
+    size_t part_floats = 0;
+    std::vector<int> order;         // [n]: the jobs in launch order
+    int n_targets = 0;
+    std::vector<int> idx;           // what the kernels read: order[n] | tgt_off[n_targets + 1] | tgt_jobs[n]
+};
+inline WgradListPlan plan_wgrad_lists(const std::vector<int>& blocks, const std::vector<const void*>& target) {
+    const int n = (int)blocks.size();
+    WgradListPlan k;
+    k.part_off.resize(n);
+    for (int q = 0; q < n; ++q) { k.part_off[q] = k.part_floats; k.part_floats += (size_t)blocks[q] * 66 * 64; }
+    k.order.resize(n);
+    for (int q = 0; q < n; ++q) k.order[q] = q;
+    std::stable_sort(k.order.begin(), k.order.end(), [&](int a, int b) { return blocks[a] > blocks[b]; });
+    std::vector<const void*> targets;
+    std::vector<std::vector<int>> lists;
+    for (int q = 0; q < n; ++q) {
+        size_t t = 0;
+        while (t < targets.size() && targets[t] != target[q]) ++t;
+        if (t == targets.size()) { targets.push_back(target[q]); lists.emplace_back(); }
+        lists[t].push_back(q);
+    }
+    k.n_targets = (int)targets.size();
+    k.idx = k.order;
+    int off = 0;
+    for (const std::vector<int>& l : lists) { k.idx.push_back(off); off += (int)l.size(); }
+    k.idx.push_back(off);
+    for (const std::vector<int>& l : lists) k.idx.insert(k.idx.end(), l.begin(), l.end());
     return k;
 }
 

@@ -6,6 +6,9 @@
 //   dispatch_dump cache n_cu          N B nb step-cached rollout-cached, for N = 1 ... 300 and a set of batches
 //   dispatch_dump policy              every policy field, from the environment
 //   dispatch_dump env                 the names of the environment table
+//   dispatch_dump wgrad b0 t0 b1 t1 ...       the deferred weight gradients' lists (plan_wgrad_lists) for jobs of b_q blocks adding
+//                                     into target t_q: the lines part_off, part_floats, order, n_targets, idx
+#include <cstdint>
 #include <cstring>
 #include <set>
 #include <string>
@@ -101,6 +104,21 @@ int main(int argc, char** argv) {
         int n = 0;
         const EnvSwitch* t = env_switches(&n);
         for (int q = 0; q < n; ++q) printf("%s\n", t[q].name);
+    } else if (mode == "wgrad" && argc >= 4 && argc % 2 == 0) {
+        std::vector<int> blocks;
+        std::vector<const void*> target;
+        for (int q = 2; q < argc; q += 2) {
+            blocks.push_back(atoi(argv[q]));
+            target.push_back(reinterpret_cast<const void*>((uintptr_t)atol(argv[q + 1])));
+        }
+        const WgradListPlan k = plan_wgrad_lists(blocks, target);
+        printf("part_off");
+        for (size_t v : k.part_off) printf(" %zu", v);
+        printf("\npart_floats %zu\norder", k.part_floats);
+        for (int v : k.order) printf(" %d", v);
+        printf("\nn_targets %d\nidx", k.n_targets);
+        for (int v : k.idx) printf(" %d", v);
+        printf("\n");
     } else {
         return 2;
     }

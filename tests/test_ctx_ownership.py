@@ -113,3 +113,34 @@ def test_ensure_step_ws_and_stepws_name_the_same_fourteen_buffers():
     # and the float64 calls swap the struct whole: no list of buffers to keep in step
     scope = _body(_sources()['capi_f64.h'], 'struct F64Scope {')
     assert scope.count('std::swap(c->ws, c->f64_ws);') == 2 and 'DevBuf' not in scope, scope
+
+
+# ---- a gradient pass takes its outputs as arguments (GdPass, TrainPass); the weight-gradient queue is one struct; one guard drains ----
+def test_no_gradient_pass_patches_the_context():
+    for gone in ('gd_adam', 'gd_host_rewards', 'gd_host_actions', 'tr_loss_host', 'tr_engine', 'wg_defer_now', 'LossHostReset'):
+        assert not _sites(gone), (gone, _sites(gone)[:3])
+
+
+def test_the_weight_gradient_queue_keeps_its_state_to_itself():
+    for needle in ('wg_jobs', 'wg_uploaded', 'wg_jobs_dev', 'wg_idx_dev'):
+        _only_inside(needle, 'capi_pipeline.h', 'struct WgradQueue {')
+
+
+def test_the_guard_stands_before_the_first_launch_and_no_exit_drains_by_hand():
+    """DrainOnError (capi_pipeline.h) waits for the stream on every exit but the DRP_OK one: constructed before anything is
+    launched, disarmed by the last return"""
+    train, gd = _sources()['capi_train.h'], _sources()['capi_gd.h']
+    launch = r'hipLaunchKernelGGL|gd_iteration\(|gd_forward_backward\(|train_stage_batch\(|train_attempt\(|train_forward_backward\('
+    for text, head in ((train, 'int train_step_body(drp_ctx* c,'), (gd, 'int drp_gd_grad(drp_ctx* c,'),
+                       (gd, 'int drp_gd_step(drp_ctx* c,'), (gd, 'int drp_gd_step_async(drp_ctx* c,')):
+        body = _body(text, head)
+        guard = body.index('DrainOnError drain(c);')
+        launches = [m.start() for m in re.finditer(launch, body)]
+        assert launches and guard < min(launches), head
+        assert body.count('drain.ok()') == 1 and body.rstrip('} \n').endswith('return drain.ok();'), head
+    # what train_step_body calls before its guard launches nothing; the staging and the attempts come behind it
+    for head in ('int train_check_args(drp_ctx* c,', 'int train_ensure_workspace(drp_ctx* c,'):
+        assert 'hipLaunchKernelGGL' not in _body(train, head), head
+    for head in ('int train_stage_batch(drp_ctx* c,', 'int train_attempt(drp_ctx* c,'):
+        assert 'hipLaunchKernelGGL' in _body(train, head), head
+    assert '(void)drp_sync(c); return' not in train

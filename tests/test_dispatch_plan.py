@@ -123,3 +123,36 @@ def test_the_documented_switches_are_the_tables(dump):
         doc |= set(re.findall(r'DRP_[A-Z0-9_]+', r.split('|')[1]))
     assert doc - NOT_DISPATCH == set(dump('env'))
     assert NOT_DISPATCH <= doc
+
+
+def wgrad_grid():
+    """(blocks, target id) per job: 25 jobs per rollout step is what the trainer queues; block counts all equal, strictly
+    decreasing and with ties (the stable order must show); targets all distinct, all equal and interleaved (queue order within a
+    target must show)"""
+    for n in (1, 2, 24, 25, 75):
+        for blocks in ([7] * n, [n + 3 - q for q in range(n)], [(3, 16, 3, 1, 16)[q % 5] for q in range(n)]):
+            for targets in ([100 + q for q in range(n)], [5] * n, [(9, 4, 9, 2)[q % 4] + 10 * (q % 25 // 12) for q in range(n)]):
+                yield list(zip(blocks, targets))
+
+
+def wgrad_lists(jobs):
+    """csrc/dispatch.h plan_wgrad_lists, restated"""
+    n, blocks = len(jobs), [b for b, _ in jobs]
+    part_off = [66 * 64 * sum(blocks[:q]) for q in range(n)]
+    order = sorted(range(n), key=lambda q: -blocks[q])                  # (sorted is stable)
+    seen = list(dict.fromkeys(t for _, t in jobs))                      # first-seen order
+    lists = [[q for q in range(n) if jobs[q][1] == t] for t in seen]
+    tgt_off = [sum(len(l) for l in lists[:k]) for k in range(len(seen) + 1)]
+    return part_off, 66 * 64 * sum(blocks), order, len(seen), order + tgt_off + [q for l in lists for q in l]
+
+
+def test_the_deferred_weight_gradients_lists(dump):
+    cases = list(wgrad_grid())
+    assert len(cases) == 45
+    for jobs in cases:
+        got = {l.split()[0]: [int(v) for v in l.split()[1:]] for l in dump('wgrad', *[v for job in jobs for v in job])}
+        part_off, part_floats, order, n_targets, idx = wgrad_lists(jobs)
+        assert got == dict(part_off=part_off, part_floats=[part_floats], order=order, n_targets=[n_targets], idx=idx), jobs
+    # the stable order and the queue order within a target, spelled out once: ties keep their queue order
+    got = dump('wgrad', 3, 9, 16, 4, 3, 9, 1, 2, 16, 4)
+    assert got[2] == 'order 1 4 0 2 3' and got[3] == 'n_targets 3' and got[4] == 'idx 1 4 0 2 3 0 2 4 5 0 2 1 4 3'

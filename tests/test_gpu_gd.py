@@ -360,6 +360,39 @@ def test_pipelined_iterations_equal_the_blocking_ones(ctx, golden):
         np.testing.assert_array_equal(a, want[i][1])
 
 
+@pytest.mark.parametrize('N', [20, 70])
+def test_a_blocking_gradient_between_an_async_step_and_its_wait(ctx, N):
+    """A pass's outputs are its arguments (csrc/capi_gd.h: GdPass): drp_gd_grad issued while an iteration's slot is still
+    pending is a gradients-only pass -- no optimiser step, no store to the slot.  Horizon 2 (the t > 0 branch and the Adam
+    step on the t == 0 launch both run), one tile of 32 rows and three with the last ragged: step, gradient, wait against
+    step, wait, gradient, bit for bit."""
+    B, H = 4, 2
+    s0, dens, attr = syn.make_pile(N, 1, seed=N)
+    obs_goal = syn.goal_distance_image(syn.goal_mask('I'))
+    ctx.set_goal(syn.goal_field(obs_goal), syn.goal_coor_strided(obs_goal, 5 * N))
+    lo, hi = syn.action_limits()
+    acts = np.stack([syn.nominal_pushes(H, seed=50 + i) for i in range(B)]).astype(np.float32)
+    acts[:, 0] = [-3.5, 0.3, 2.5, -0.2]           # through the pile: every row has a gradient
+    acts[:, 0, 1] += 0.1 * np.arange(B)
+    args = (s0, attr, dens, acts, 0.05, lo, hi)
+    ctx.gd_begin(*args)
+    ctx.gd_step_async(0)
+    grad_a = ctx.gd_grad(want_state_grad=True)
+    wait_a = ctx.gd_wait(0)
+    after_a = ctx.gd_actions()
+    ctx.gd_begin(*args)
+    ctx.gd_step_async(0)
+    wait_b = ctx.gd_wait(0)
+    grad_b = ctx.gd_grad(want_state_grad=True)
+    after_b = ctx.gd_actions()
+    for a, b in zip(wait_a + grad_a, wait_b + grad_b):
+        np.testing.assert_array_equal(a, b)
+    assert np.isfinite(grad_a[1]).all() and (np.abs(grad_a[1]).sum((1, 2)) > 0).all()
+    assert not np.array_equal(wait_a[1], acts)                      # the step moved the pushes ...
+    np.testing.assert_array_equal(after_a, wait_a[1])               # ... and the gradient pass did not
+    np.testing.assert_array_equal(after_b, wait_b[1])
+
+
 @pytest.mark.parametrize('case', ['h1', 'h2'])
 def test_the_stage_kernels_against_the_reference(monkeypatch, golden, case):
     """The planner's reverse-mode node stages a launch per stage (kmb_predict, kmb_node_step, kb_edge_terms, kmb_node_encode),

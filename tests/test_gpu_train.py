@@ -131,6 +131,42 @@ def test_tiny_and_unpadded_batches(golden):
     model.engine.close()
 
 
+def test_a_refused_step_between_two_updates_changes_nothing(golden):
+    """drp_train_step refuses a batch whose particle_nums[0] is 0 (DRP_EINVAL) before it stages or launches anything: the update
+    after it has the loss and leaves the weights of a run that never made the refused call, bit for bit.  Two samples of 40
+    rows with 40 and 23 particles, two rollout steps."""
+    from dyn_res_pile_manip_amd._lib import DrpError
+    nums, T = np.array([40, 23], np.int32), 2
+    B, N = len(nums), int(nums.max())
+    rng = np.random.default_rng(0)
+    states = np.zeros((B, T + 1, N, 3), np.float32)
+    sdelta = np.zeros((B, T, N, 3), np.float32)
+    attrs = np.zeros((B, T + 1, N), np.float32)
+    dens = np.array([300.0, 350.0], np.float32)
+    for b, n in enumerate(nums):
+        s, _, _ = syn.make_pile(int(n), 1, seed=5 + b, kind='blob')
+        for t in range(T + 1):
+            states[b, t, :n] = s[0] * 0.3 + 0.002 * t * rng.standard_normal((n, 3)).astype(np.float32) + [0, 0, 0.52]
+        sdelta[b, :, :n] = 0.004 * rng.standard_normal((T, n, 3)).astype(np.float32)
+    bad = nums.copy()
+    bad[0] = 0
+    runs = []
+    for refuse in (True, False):
+        model = _model(golden)
+        eng = model.engine
+        eng.train_begin(T, 1e-3, 0.9)
+        first = eng.train_step(states, sdelta, attrs, nums, dens, mode='update')[0]
+        if refuse:
+            with pytest.raises(DrpError, match=r'particle_nums\[0\]=0'):
+                eng.train_step(states, sdelta, attrs, bad, dens, mode='update')
+        second = eng.train_step(states, sdelta, attrs, nums, dens, mode='update')[0]
+        runs.append((first, second, eng.get_weights().copy()))
+        eng.close()
+    assert runs[0][0] == runs[1][0] and runs[0][1] == runs[1][1] and runs[0][1] != runs[0][0]
+    np.testing.assert_array_equal(runs[0][2], runs[1][2])
+    assert np.abs(runs[0][2] - weights.blob_from_state_dict(golden.weights_seed0)).max() > 0
+
+
 def test_checkpoint_round_trip_is_a_torch_state_dict(golden, tmp_path):
     """train/train_gnn_dyn.py:214-215,226: `torch.save(model.state_dict(), path)` must write what torch's
     `load_state_dict` accepts -- tensors under the reference's keys and shapes -- and what this package's own
