@@ -100,6 +100,9 @@ SIGNATURES = {
     'drp_train_step_untracked': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.POINTER(ctypes.c_int32),
                                                 c_float_p, ctypes.c_int, ctypes.c_int, c_float_p, ctypes.POINTER(ctypes.c_int32),
                                                 ctypes.c_int, ctypes.c_int, c_double_p, c_float_p]),
+    'drp_train_step_actions': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.POINTER(ctypes.c_int32),
+                                              c_float_p, ctypes.c_int, ctypes.c_int, c_float_p, ctypes.POINTER(ctypes.c_int32),
+                                              ctypes.c_int, ctypes.c_int, c_double_p, c_float_p]),
     'drp_train_set_lr': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double]),
     'drp_get_weights': (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_size_t]),
     'drp_depth2fgpcd': (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int,
@@ -173,6 +176,9 @@ SIGNATURES = {
                                        ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p]),
     'drp_train_grad_f64': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.POINTER(ctypes.c_int32), c_float_p,
                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p]),
+    'drp_train_grad_f64_actions': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.POINTER(ctypes.c_int32),
+                                                  c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p,
+                                                  c_double_p, c_double_p]),
     'drp_cloud_chamfer': (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.POINTER(ctypes.c_int32), c_float_p,
                                          ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_float_p,
                                          ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),

@@ -174,6 +174,10 @@ long drp_debug_fetch(drp_ctx* c, const char* name, void* out, size_t out_bytes) 
     else if (!strcmp(name, "w_split6_bwd")) { b = &c->w_split6_bwd; bytes = (size_t)SB6_TOTAL * 16; }
     else if (!strcmp(name, "rev_off")) { b = &c->rev_off; bytes = (size_t)c->marks.lastB * (c->marks.lastN + 1) * 4; }
     else if (!strcmp(name, "rev")) { b = &c->rev; bytes = bn * DRP_K * 4; }
+    // the last training step's predicted states, sample-major [B][H][N][3], and impulses, step-major [H][B][N][3] (tests: the
+    // padded rows of drp_train_step_actions)
+    else if (!strcmp(name, "train_states")) { b = &c->states; bytes = (size_t)c->marks.lastH * bn * 3 * 4; }
+    else if (!strcmp(name, "train_sdelta")) { b = &c->tape_sdelta; bytes = (size_t)c->marks.lastH * bn * 3 * 4; }
     // the resolution regressor's post-activation taps of its last forward (NHWC [B][H][W][C] for the convolutions)
     else if (!strncmp(name, "rgr_c", 5) && name[5] >= '1' && name[5] <= '5' && !name[6]) {
         b = &c->rgr_a[name[5] - '1']; bytes = rgr_conv_out_floats(name[5] - '1', c->rgr_lastB) * 4;

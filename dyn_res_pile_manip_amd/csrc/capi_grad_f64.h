@@ -274,7 +274,8 @@ struct Tr64Ws {
 
 // the batch on the device: the caller's arrays, a_cur = attrs[:, 0] gathered, then the results
 struct Tr64Io {
-    const float *states, *sdelta, *attr, *dens;
+    const float *states, *sdelta, *attr, *dens;     // sdelta: the impulses [B][H][N][3], or with `actions` the pushes [B][H][4]
+    bool actions;
     const int* nums;
     double *terms, *total;          // [H][B], [W_TOTAL]
 };
@@ -287,10 +288,14 @@ int tr64_chunk(drp_ctx* c, const Tr64Ws& k, const Tr64Io& io, int b0, int bc, in
     const float* attr = io.attr + (size_t)b0 * N;
     const float* dens = io.dens + b0;
     hipLaunchKernelGGL(kt64_init_state, lin3, dim3(256), 0, st, io.states, b0, N, H, (long)(pn * 3), k.tape.state);
-    // ---- forward: the impulse is data
+    // ---- forward: the impulse is data, or the batch's push on the step's own input (padded rows zero)
     CHK(f64_tape_forward(c, k.tape, bc, N, H, attr, dens, true, [&](int t, const F64Tape& s) {
-        hipLaunchKernelGGL(kt64_stage_step, lin3, dim3(256), 0, st, s.state, io.sdelta, b0, N, H, t, (long)(pn * 3), s.sd,
-                           ptr<float>(c->ws.s_in), ptr<float>(c->ws.s_delta));
+        if (io.actions)
+            hipLaunchKernelGGL(kt64_sdelta_actions, dim3(bc), dim3(256), 0, st, s.state, io.sdelta, io.nums, b0, N, H, t, c->cam, s.sd,
+                               ptr<float>(c->ws.s_in), ptr<float>(c->ws.s_delta));
+        else
+            hipLaunchKernelGGL(kt64_stage_step, lin3, dim3(256), 0, st, s.state, io.sdelta, b0, N, H, t, (long)(pn * 3), s.sd,
+                               ptr<float>(c->ws.s_in), ptr<float>(c->ws.s_delta));
     }));
     // ---- every step's loss term and its seed of the reverse pass; the samples' accumulators start at zero
     hipLaunchKernelGGL(kt64_mse, dim3(bc, H), dim3(256), 0, st, k.tape.state, io.states, io.nums, b0, bc, B, N, H, io.terms, k.rev.g_state);
@@ -305,6 +310,9 @@ int tr64_chunk(drp_ctx* c, const Tr64Ws& k, const Tr64Io& io, int b0, int bc, in
         if (t > 0)
             hipLaunchKernelGGL(kt64_state_bwd, dim3((unsigned)((pn + 255) / 256)), dim3(256), 0, st, g_out, k.rev.g_diff, s.cnt,
                                k.rev.rev_off, k.rev.rev, N, bc * N, k.rev.g_state + (size_t)(t - 1) * pn * 3);
+        if (t > 0 && io.actions)            // the push's share, on top of that sum
+            hipLaunchKernelGGL(kt64_push_bwd, dim3(bc), dim3(256), 0, st, s.state, io.sdelta, io.nums, b0, N, H, t, c->cam, k.rev.g_sd,
+                               k.rev.g_state + (size_t)(t - 1) * pn * 3);
         HIPCHK(c, hipGetLastError());
     }
     hipLaunchKernelGGL(kt64_total, dim3((W_TOTAL + 255) / 256), dim3(256), 0, st, k.wg.acc, bc, io.total);
@@ -353,16 +361,20 @@ int drp_gd_grad_f64(drp_ctx* c, const float* s0, const float* attr, const float*
     return guarded_wait(c, nullptr);        // (the upload's host block lives until here)
 }
 
-int drp_train_grad_f64(drp_ctx* c, const float* states, const float* states_delta, const float* attrs, const int32_t* particle_nums,
-                       const float* particle_dens, int B, int N, int n_rollout, double* loss_out, double* loss_terms_out,
-                       double* grad_out, double* grad_state_out) {
-    CHK(need(c, true, false, false));
+namespace {
+// drp_train_grad_f64 and drp_train_grad_f64_actions: one body; `impulses` is states_delta [B][H][N][3], or with `actions` the
+// pushes [B][H][4]
+int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, bool actions, const float* attrs,
+                        const int32_t* particle_nums, const float* particle_dens, int B, int N, int n_rollout, double* loss_out,
+                        double* loss_terms_out, double* grad_out, double* grad_state_out) {
+    CHK(need(c, true, actions, false));
     CHK(check_bn(c, B, N));
-    if (!states || !states_delta || !attrs || !particle_nums || !particle_dens) return fail(c, DRP_EINVAL, "null argument");
+    if (!states || !impulses || !attrs || !particle_nums || !particle_dens) return fail(c, DRP_EINVAL, "null argument");
     if (n_rollout < 1 || n_rollout > 64) return fail(c, DRP_EINVAL, "bad n_rollout=%d", n_rollout);
     for (int b = 0; b < B; ++b)
         if (particle_nums[b] <= 0 || particle_nums[b] > N)
             return fail(c, DRP_EINVAL, "particle_nums[%d]=%d outside 1..%d", b, particle_nums[b], N);
+    if (actions) CHK(check_pushes(c, impulses, B, n_rollout));
     HIPCHK(c, hipSetDevice(c->device));
     F64Scope scope(c);
     if (!c->f64_w_valid) CHK(f64_refresh_weights(c));
@@ -374,10 +386,10 @@ int drp_train_grad_f64(drp_ctx* c, const float* states, const float* states_delt
     CHK(f64_size_chunks(c, B, N, ((size_t)1 << 24) / ((size_t)N * DRP_K), bytes_of, &Bc));
     k.carve(c->grad64_ws.p, Bc, (size_t)N, (size_t)H);
     // the whole batch's inputs in one upload: states | impulses | attrs[:, 0] | densities | particle counts, then the results
-    const size_t n_st = (size_t)B * (H + 1) * N * 3, n_sd = (size_t)B * H * N * 3, n_at = (size_t)B * N;
+    const size_t n_st = (size_t)B * (H + 1) * N * 3, n_sd = actions ? (size_t)B * H * 4 : (size_t)B * H * N * 3, n_at = (size_t)B * N;
     std::vector<float> host(n_st + n_sd + n_at + (size_t)B + (size_t)B);
     memcpy(host.data(), states, n_st * sizeof(float));
-    memcpy(host.data() + n_st, states_delta, n_sd * sizeof(float));
+    memcpy(host.data() + n_st, impulses, n_sd * sizeof(float));
     for (int b = 0; b < B; ++b) memcpy(host.data() + n_st + n_sd + (size_t)b * N, attrs + (size_t)b * (H + 1) * N, (size_t)N * sizeof(float));
     memcpy(host.data() + n_st + n_sd + n_at, particle_dens, (size_t)B * sizeof(float));
     memcpy(host.data() + n_st + n_sd + n_at + B, particle_nums, (size_t)B * sizeof(int32_t));
@@ -386,6 +398,7 @@ int drp_train_grad_f64(drp_ctx* c, const float* states, const float* states_delt
     CHK(f64_upload_batch(c, host, n_terms + (size_t)W_TOTAL, &io.terms));
     io.states = ptr<float>(c->grad64_io); io.sdelta = io.states + n_st; io.attr = io.sdelta + n_sd; io.dens = io.attr + n_at;
     io.nums = reinterpret_cast<const int*>(io.dens + B);
+    io.actions = actions;
     io.total = io.terms + n_terms;
     HIPCHK(c, hipMemsetAsync(io.total, 0, (size_t)W_TOTAL * sizeof(double), c->stream));
     for (int b0 = 0; b0 < B; b0 += (int)Bc)
@@ -401,4 +414,19 @@ int drp_train_grad_f64(drp_ctx* c, const float* states, const float* states_delt
         *loss_out = total;
     }
     return DRP_OK;
+}
+}  // namespace
+
+int drp_train_grad_f64(drp_ctx* c, const float* states, const float* states_delta, const float* attrs, const int32_t* particle_nums,
+                       const float* particle_dens, int B, int N, int n_rollout, double* loss_out, double* loss_terms_out,
+                       double* grad_out, double* grad_state_out) {
+    return train_grad_f64_body(c, states, states_delta, false, attrs, particle_nums, particle_dens, B, N, n_rollout, loss_out,
+                               loss_terms_out, grad_out, grad_state_out);
+}
+
+int drp_train_grad_f64_actions(drp_ctx* c, const float* states, const float* actions, const float* attrs,
+                               const int32_t* particle_nums, const float* particle_dens, int B, int N, int n_rollout,
+                               double* loss_out, double* loss_terms_out, double* grad_out, double* grad_state_out) {
+    return train_grad_f64_body(c, states, actions, true, attrs, particle_nums, particle_dens, B, N, n_rollout, loss_out,
+                               loss_terms_out, grad_out, grad_state_out);
 }

@@ -882,6 +882,8 @@ struct TapeFwd {
     const float* s0; int s0_mod; size_t s0_stride;   // the first step's input; the later steps read the step before's output
     int mod;                                         // attributes and densities: sample b reads row b % mod
     const float* actions;                            // [B][H][4], or null: the impulses are data, already in tape_sdelta
+    const float* masked_actions = nullptr;           // the trainer's pushes [B][H][4] (with `actions` null): a launch ahead of each step
+    const int* nums = nullptr;                       //   writes tape_sdelta's slice from the step's input, zeros on rows >= nums[b]
     bool padded;
     bool tape;                                       // false: the forward pass alone
     bool agg_hist;
@@ -906,6 +908,9 @@ int run_tape_forward(drp_ctx* c, int engine, int B, int N, int H, const TapeFwd&
         a.padded = f.padded;
         a.rev_off = f.rev_off; a.rev = f.rev; a.rev_built = f.rev_built;
         a.s_delta = ptr<float>(c->tape_sdelta) + (size_t)t * bn * 3;
+        if (f.masked_actions)           // the step itself reads the slice as it reads data impulses: the graph kernels' push path knows no padding
+            hipLaunchKernelGGL(kt_sdelta_actions, dim3(B), dim3(256), 0, c->stream, a.s_prev, a.prev_stride, f.masked_actions + (size_t)t * 4,
+                               (size_t)H * 4, f.nums, N, a.s_delta, c->cam);
         if (f.tape) {
             a.nbr_idx = ptr<int16_t>(c->tape_idx) + (size_t)t * bn * DRP_K;
             a.nbr_cnt = ptr<uint8_t>(c->tape_cnt) + (size_t)t * bn;
@@ -1098,6 +1103,14 @@ float push_len_bound(const drp_ctx* c, const float* actions, size_t n) {
         if (v > l2 || v != v) l2 = (v != v) ? INFINITY : v;
     }
     return fro * sqrtf(l2) / c->cam.gs;
+}
+// the trainer's pushes [B][H][4] (drp_train_step_actions, drp_train_grad_f64_actions): one of zero length, or of none, is refused
+// (train_host.h: first_bad_push)
+int check_pushes(drp_ctx* c, const float* actions, int B, int H) {
+    float len = 0.0f;
+    const long e = first_bad_push(c->cam.m, c->cam.gs, actions, (size_t)B * H, &len);
+    if (e >= 0) return fail(c, DRP_EINVAL, "actions[%d][%d]: a push of length %g", (int)(e / H), (int)(e % H), (double)len);
+    return DRP_OK;
 }
 // engine: the one the caller runs (the gradient-descent planner's and the trainer's forward pass write their tape with the
 // fused one whatever drp_set_engine chose)

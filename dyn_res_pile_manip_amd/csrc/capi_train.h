@@ -4,26 +4,7 @@
 // ---- training on the same kernels (row f4) ------------------------------------------------------
 namespace {
 #define TR_GRAD_PAD ((W_TOTAL + 63) & ~63)      // tr_grad: the gradient blob, then (from here) kmb_step_bwd's barrier counters
-// the batch as uploaded (drp_train_step): states [B][H+1][N][3] | impulses [B][H][N][3] | attributes [B][H+1][N] | densities [B]
-// | particle counts [B] (ints), every block 16-byte aligned; drp_train_step_untracked (M > 0): behind them the target clouds
-// [B][H][M][3] | their counts [B][H] (ints) -- with M = 0 the layout, and so the one copy, is drp_train_step's
-struct TrArena { size_t states, sdelta, attrs, dens, nums, targets, tnums, bytes; };
-TrArena tr_layout(int B, int H, int N, int M = 0) {
-    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    TrArena a{};
-    a.states = 0;
-    a.sdelta = up(a.states + (size_t)B * (H + 1) * N * 3 * sizeof(float));
-    a.attrs = up(a.sdelta + (size_t)B * H * N * 3 * sizeof(float));
-    a.dens = up(a.attrs + (size_t)B * (H + 1) * N * sizeof(float));
-    a.nums = up(a.dens + (size_t)B * sizeof(float));
-    a.bytes = up(a.nums + (size_t)B * sizeof(int));
-    if (M > 0) {
-        a.targets = a.bytes;
-        a.tnums = up(a.targets + (size_t)B * H * M * 3 * sizeof(float));
-        a.bytes = up(a.tnums + (size_t)B * H * sizeof(int));
-    }
-    return a;
-}
+// (train_host.h: TrArena / tr_layout, where the blocks of a staged batch lie)
 const float* tr_given(const drp_ctx* c) { return static_cast<const float*>(c->tr_arena.p); }
 const int* tr_nums(const drp_ctx* c, const TrArena& lay) {
     return reinterpret_cast<const int*>(static_cast<const char*>(c->tr_arena.p) + lay.nums);
@@ -45,6 +26,8 @@ struct TrainPass {
     double* loss_terms = nullptr;   // [H][B], where the loss kernel stores: c->tr_loss, or pinned host memory the caller reads
     TrArena lay{};                  // the batch in c->tr_arena
     TrLoss lk;
+    bool actions = false;           // the impulse source: false, data (lay.sdelta holds [B][H][N][3]); true, the pushes there
+                                    // ([B][H][4]) evaluated on the state each step reads (kt_sdelta_actions, kb_sdelta_pos)
 };
 // forward over n_rollout steps (+ loss), optionally the backward pass with weight gradients
 int train_forward_backward(drp_ctx* c, int B, int N, const TrainPass& tp) {
@@ -60,6 +43,7 @@ int train_forward_backward(drp_ctx* c, int B, int N, const TrainPass& tp) {
     float* states = ptr<float>(c->states);
     const float* given = tr_given(c);
     const int* nums = tr_nums(c, tp.lay);
+    const float* acts = tp.actions ? reinterpret_cast<const float*>(static_cast<const char*>(c->tr_arena.p) + tp.lay.sdelta) : nullptr;
     float* g_state = ptr<float>(c->g_state);
     double* loss = tp.loss_terms;
     const float scale = 1.0f / (float)(H * B);
@@ -71,6 +55,8 @@ int train_forward_backward(drp_ctx* c, int B, int N, const TrainPass& tp) {
         f.s0 = given; f.s0_mod = B; f.s0_stride = in_stride;
         f.mod = B;
         f.actions = nullptr;            // this step's impulses are data (train/train_gnn_dyn.py:181): the step-major copy kt_unpack_inputs left
+        f.masked_actions = acts;        //   -- or the batch's pushes on the step's own input, written there ahead of each step
+        f.nums = nums;
         f.padded = true;                // collate_fn pads with zero rows: coincident particles
         f.tape = backward; f.agg_hist = true;
         f.cself = cself; f.cself_ok = cself_ok;
@@ -109,8 +95,10 @@ int train_forward_backward(drp_ctx* c, int B, int N, const TrainPass& tp) {
     const dim3 egrid((unsigned)(B * chunks16));
     const float* dens = ptr<float>(c->ws.dens);
     // the reversed lists of ALL rollout steps in one launch (the tape holds every step's lists; a training batch is a handful
-    // of workgroups per step)
-    launch_reverse_lists(c, ptr<int16_t>(c->tape_idx), ptr<uint8_t>(c->tape_cnt), N, B * H, nums, B);
+    // of workgroups per step).  Data impulses: padded receivers are left out, their gradient is identically zero while no zero
+    // row neighbours a real one.  With pushes every receiver is listed, as in the GD planner: the pass stays exact where a pile
+    // lies around the camera-frame origin and a zero row is a real row's sender (d loss / d s_pred of that zero row is not zero)
+    launch_reverse_lists(c, ptr<int16_t>(c->tape_idx), ptr<uint8_t>(c->tape_cnt), N, B * H, acts != nullptr ? nullptr : nums, B);
     // deferred weight gradients: what a job reads keeps a buffer per rollout step t (g_eff and g_proj: per propagation step
     // too; slot 0 of g_eff is the transient copy the predictor writes and the particle encoder reads)
     const size_t per_t = defer ? 1 : 0;
@@ -180,6 +168,10 @@ int train_forward_backward(drp_ctx* c, int B, int N, const TrainPass& tp) {
         if (g_prev != nullptr)
             hipLaunchKernelGGL(kb_gather_pos, dim3((N + 255) / 256, B), dim3(256), 0, st, ptr<float>(c->gpos_edge),
                                s.rev_off, s.rev, N, g_prev, (size_t)N * 3, s.cnt, (const float*)g_out);
+        // the push's share, last: the impulse of this step was evaluated on s_pred_{t-1} (c->g_sdelta: the node stages' d / d impulse)
+        if (g_prev != nullptr && acts != nullptr)
+            hipLaunchKernelGGL(kb_sdelta_pos, dim3(B), dim3(256), 0, st, s_prev, prev_stride, acts + (size_t)t * 4, (size_t)H * 4,
+                               ptr<float>(c->g_sdelta), nums, N, c->cam, g_prev, (size_t)N * 3);
         wq.push<64>(ed.gce, 64, ed.re, 64, (long)bnk, G + W_RP_W, 193, 1, G + W_RP_B, G + W_RP_W + 192, dens, B,
                     (long)N * DRP_K);
         wq.push<64>(ed.g3, 64, ed.a2, 64, (long)bnk, G + W_RE4_W, 64, 1, G + W_RE4_B, nullptr, nullptr, 1, 1);
@@ -289,11 +281,18 @@ int drp_train_begin(drp_ctx* c, int n_rollout, double lr, double beta1) {
 
 namespace {
 // ---- drp_train_step and drp_train_step_untracked: one body (train_step_body), the loss kind and the targets in `lk` ----
-int train_check_args(drp_ctx* c, const float* states, const float* states_delta, const float* attrs, const int32_t* particle_nums,
-                     const float* particle_dens, int B, int N, const TrLoss& lk, int mode) {
+// `impulses`: states_delta [B][H][N][3], or with `actions` the pushes [B][H][4]
+int train_check_args(drp_ctx* c, const float* states, const float* impulses, bool actions, const float* attrs,
+                     const int32_t* particle_nums, const float* particle_dens, int B, int N, const TrLoss& lk, int mode) {
     if (!c || !c->tr_on) return fail(c, DRP_ESTATE, "drp_train_begin not called");
     CHK(check_bn(c, B, N));
-    if (!states || !states_delta || !attrs || !particle_nums || !particle_dens) return fail(c, DRP_EINVAL, "null argument");
+    if (!states || !impulses || !attrs || !particle_nums || !particle_dens) return fail(c, DRP_EINVAL, "null argument");
+    if (actions) {
+        if (!c->have_cam) return fail(c, DRP_ESTATE, "camera not set (drp_set_camera)");
+        // a zero-length push is 0 / 0 in every impulse (planners.py:240) and from there in every weight; the dataset path
+        // refuses such a push too (dataset_gnn_dyn.py:148-153)
+        CHK(check_pushes(c, impulses, B, c->tr_nroll));
+    }
     if (mode < DRP_TRAIN_EVAL || mode > DRP_TRAIN_UPDATE) return fail(c, DRP_EINVAL, "bad mode %d", mode);
     for (int b = 0; b < B; ++b)
         if (particle_nums[b] <= 0 || particle_nums[b] > N)
@@ -348,13 +347,13 @@ int train_ensure_workspace(drp_ctx* c, int B, int N, TrainPass& tp) {
 }
 
 // the batch in one copy: packed into pinned staging in the caller's layouts, unpacked by one launch (kt_unpack_inputs)
-int train_stage_batch(drp_ctx* c, const float* states, const float* states_delta, const float* attrs, const int32_t* particle_nums,
+int train_stage_batch(drp_ctx* c, const float* states, const float* impulses, const float* attrs, const int32_t* particle_nums,
                       const float* particle_dens, int B, int N, const TrainPass& tp) {
     const int H = c->tr_nroll;
     const TrArena& lay = tp.lay;
     char* pin = ptr<char>(c->tr_pin);
     memcpy(pin + lay.states, states, (size_t)B * (H + 1) * N * 3 * sizeof(float));
-    memcpy(pin + lay.sdelta, states_delta, (size_t)B * H * N * 3 * sizeof(float));
+    memcpy(pin + lay.sdelta, impulses, tr_impulse_bytes(B, H, N, tp.actions));
     memcpy(pin + lay.attrs, attrs, (size_t)B * (H + 1) * N * sizeof(float));
     memcpy(pin + lay.dens, particle_dens, (size_t)B * sizeof(float));
     memcpy(pin + lay.nums, particle_nums, (size_t)B * sizeof(int));
@@ -369,7 +368,8 @@ int train_stage_batch(drp_ctx* c, const float* states, const float* states_delta
     const char* ar = by_kernel ? ptr<const char>(c->tr_pin) : static_cast<const char*>(c->tr_arena.p);
     const size_t total = (size_t)H * B * N * 3;
     hipLaunchKernelGGL(kt_unpack_inputs, dim3((unsigned)std::min<size_t>((total + 255) / 256, 1024)), dim3(256), 0, c->stream,
-                       reinterpret_cast<const float*>(ar + lay.sdelta), reinterpret_cast<const float*>(ar + lay.attrs),
+                       tp.actions ? (const float*)nullptr : reinterpret_cast<const float*>(ar + lay.sdelta),
+                       reinterpret_cast<const float*>(ar + lay.attrs),
                        reinterpret_cast<const float*>(ar + lay.dens), B, H, N, ptr<float>(c->tape_sdelta), ptr<float>(c->ws.attr),
                        ptr<float>(c->ws.dens), by_kernel ? ptr<const float4>(c->tr_pin) : (const float4*)nullptr,
                        by_kernel ? static_cast<float4*>(c->tr_arena.p) : (float4*)nullptr, by_kernel ? lay.bytes / 16 : (size_t)0);
@@ -429,10 +429,10 @@ int train_attempt(drp_ctx* c, int B, int N, const TrainPass& tp, int mode, bool 
     return DRP_OK;
 }
 
-int train_step_body(drp_ctx* c, const float* states, const float* states_delta, const float* attrs,
+int train_step_body(drp_ctx* c, const float* states, const float* impulses, bool actions, const float* attrs,
                     const int32_t* particle_nums, const float* particle_dens, int B, int N, const TrLoss& lk, int mode,
                     double* loss_out, float* grad_out) {
-    CHK(train_check_args(c, states, states_delta, attrs, particle_nums, particle_dens, B, N, lk, mode));
+    CHK(train_check_args(c, states, impulses, actions, attrs, particle_nums, particle_dens, B, N, lk, mode));
     HIPCHK(c, hipSetDevice(c->device));
     end_sessions(c);
     const int H = c->tr_nroll;
@@ -440,17 +440,20 @@ int train_step_body(drp_ctx* c, const float* states, const float* states_delta, 
     {
         float amax = 0.0f;                                    // a_cur = attrs[:, 0]
         for (int b = 0; b < B; ++b) amax = fmaxf(amax, max_abs(attrs + (size_t)b * (H + 1) * N, (size_t)N));
-        CHK(pick_tape_engine(c, amax, max_abs(particle_dens, (size_t)B), max_abs(states_delta, (size_t)B * H * N * 3), &tp.engine));
+        // the largest impulse: the data's, or what the pushes can cause on any state
+        const float sd_max = actions ? push_len_bound(c, impulses, (size_t)B * H) : max_abs(impulses, (size_t)B * H * N * 3);
+        CHK(pick_tape_engine(c, amax, max_abs(particle_dens, (size_t)B), sd_max, &tp.engine));
     }
     tp.backward = mode != DRP_TRAIN_EVAL;
-    tp.lay = tr_layout(B, H, N, lk.kind == TR_LOSS_CHAMFER ? lk.M : 0);
+    tp.lay = tr_layout(B, H, N, lk.kind == TR_LOSS_CHAMFER ? lk.M : 0, actions);
     tp.lk = lk;
+    tp.actions = actions;
     CHK(train_ensure_workspace(c, B, N, tp));
     c->marks.lastH = H;
     double* const back = reinterpret_cast<double*>(ptr<char>(c->tr_pin) + tp.lay.bytes);
     tp.loss_terms = (loss_out && !c->train_copy_upload) ? back : ptr<double>(c->tr_loss);   // pinned: the terms land where this call reads them
     DrainOnError drain(c);
-    CHK(train_stage_batch(c, states, states_delta, attrs, particle_nums, particle_dens, B, N, tp));
+    CHK(train_stage_batch(c, states, impulses, attrs, particle_nums, particle_dens, B, N, tp));
     // a pass whose barrier gave up runs again with one workgroup per group (no barrier to wait at) -- for the rest of the
     // context's life
     bool gave_up = false;
@@ -474,7 +477,7 @@ int train_step_body(drp_ctx* c, const float* states, const float* states_delta, 
 int drp_train_step(drp_ctx* c, const float* states, const float* states_delta, const float* attrs,
                    const int32_t* particle_nums, const float* particle_dens, int B, int N, int mode, double* loss_out,
                    float* grad_out) {
-    return train_step_body(c, states, states_delta, attrs, particle_nums, particle_dens, B, N, TrLoss{}, mode, loss_out, grad_out);
+    return train_step_body(c, states, states_delta, false, attrs, particle_nums, particle_dens, B, N, TrLoss{}, mode, loss_out, grad_out);
 }
 
 int drp_train_step_untracked(drp_ctx* c, const float* states, const float* states_delta, const float* attrs,
@@ -482,7 +485,18 @@ int drp_train_step_untracked(drp_ctx* c, const float* states, const float* state
                              const int32_t* target_nums, int M, int mode, double* loss_out, float* grad_out) {
     TrLoss lk;
     lk.kind = TR_LOSS_CHAMFER; lk.targets = targets; lk.target_nums = target_nums; lk.M = M;
-    return train_step_body(c, states, states_delta, attrs, particle_nums, particle_dens, B, N, lk, mode, loss_out, grad_out);
+    return train_step_body(c, states, states_delta, false, attrs, particle_nums, particle_dens, B, N, lk, mode, loss_out, grad_out);
+}
+
+// the same body with each step's impulse evaluated from the batch's pushes on the state the step reads (TrainPass::actions)
+int drp_train_step_actions(drp_ctx* c, const float* states, const float* actions, const float* attrs, const int32_t* particle_nums,
+                           const float* particle_dens, int B, int N, const float* targets, const int32_t* target_nums, int M,
+                           int mode, double* loss_out, float* grad_out) {
+    TrLoss lk;
+    if (targets != nullptr || target_nums != nullptr || M != 0) {
+        lk.kind = TR_LOSS_CHAMFER; lk.targets = targets; lk.target_nums = target_nums; lk.M = M;
+    }
+    return train_step_body(c, states, actions, true, attrs, particle_nums, particle_dens, B, N, lk, mode, loss_out, grad_out);
 }
 
 int drp_train_set_lr(drp_ctx* c, double lr) {

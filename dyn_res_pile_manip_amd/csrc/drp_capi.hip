@@ -52,6 +52,7 @@
 #include "k_prop_inst.h"       // km_prop / km_prop3 / km_rollout: declared here, instantiated in inst_*.hip
 
 #include "dispatch.h"          // host-only: policy, variant flags, plan functions
+#include "train_host.h"        // host-only: the trainer's staged-batch layout and push check
 #include "capi_ctx.h"
 #include "capi_pipeline.h"
 

@@ -381,6 +381,58 @@ kb_sdelta(const float* __restrict__ s_cur, int s_mod, size_t s_stride, const flo
     }
 }
 
+// kb_sdelta's position share alone, for the trainer's pushes (drp_train_step_actions: the pushes are data, d / d actions is no
+// output): g_pos[b, n, 0:3] += J_pos^T g_s_delta[n] on the real rows n < nums[b]; padded rows (collate_fn's zero rows, whose
+// impulse kt_sdelta_actions sets to zero) receive nothing.  The same expressions as kb_sdelta's directions 4..6: the push's
+// frame is a constant here, the hard mask a constant of the derivative (push_hard on push_frame's values: the forward's decision
+// on every row, also within an ulp of u = 0 or u = L), the soft mask and both projections differentiated.
+// One thread per element, no atomics.
+__global__ void __launch_bounds__(256)
+kb_sdelta_pos(const float* __restrict__ s_cur, size_t s_stride, const float* __restrict__ actions, size_t act_stride,
+              const float* __restrict__ g_sdelta, const int* __restrict__ nums, int N, DrpCam cam, float* __restrict__ g_pos,
+              size_t gpos_stride) {
+    typedef Dual<3> D;
+    const int b = blockIdx.x;
+    const int nb = min(max(nums[b], 0), N);
+    const float* act = actions + (size_t)b * act_stride;
+    const float* s = s_cur + (size_t)b * s_stride;
+    const float* gs = g_sdelta + (size_t)b * N * 3;
+    float sc[3], ec[3];
+    const float igs = 1.0f / cam.gs;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const float m0 = cam.m[r * 4 + 0], m2 = cam.m[r * 4 + 2], m3 = cam.m[r * 4 + 3];
+        sc[r] = (m0 * act[0] - m2 * act[1] + m3) * igs;
+        ec[r] = (m0 * act[2] - m2 * act[3] + m3) * igs;
+    }
+    const float vx = ec[0] - sc[0], vy = ec[1] - sc[1], vz = ec[2] - sc[2];
+    const float len = sqrtf(vx * vx + vy * vy + vz * vz);
+    const D dx = dconst<3>(vx / len), dy = dconst<3>(vy / len), dz = dconst<3>(vz / len);
+    const PushFrame fwd = push_frame(cam, act);       // kt_sdelta_actions' frame: the hard mask is decided on its values
+    for (int n = threadIdx.x; n < nb; n += blockDim.x) {
+        D px = dconst<3>(s[n * 3 + 0]), py = dconst<3>(s[n * 3 + 1]), pz = dconst<3>(s[n * 3 + 2]);
+        px.d[0] = 1.0f; py.d[1] = 1.0f; pz.d[2] = 1.0f;
+        const D rx = px - dconst<3>(sc[0]), ry = py - dconst<3>(sc[1]);
+        if (!push_hard(fwd, s[n * 3 + 0], s[n * 3 + 1], s[n * 3 + 2])) continue;    // hard mask (constant), as the forward took it
+        const D v = ry * dx - rx * dy;
+        D pen = dconst<3>(0.0f);
+        const float lo = -DRP_PUSHER_W - v.v, hi = v.v - DRP_PUSHER_W;
+        if (lo > 0.0f && lo >= hi) pen = dconst<3>(-DRP_PUSHER_W) - v;
+        else if (hi > 0.0f) pen = v - dconst<3>(DRP_PUSHER_W);
+        const float e = expf(-pen.v / DRP_SOFT_SCALE);
+        D soft = dconst<3>(e);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) soft.d[c] = -e * pen.d[c] / DRP_SOFT_SCALE;
+        const D te = (dconst<3>(ec[0]) - px) * dx + (dconst<3>(ec[1]) - py) * dy + (dconst<3>(ec[2]) - pz) * dz;
+        const D base = te * soft;
+        const D ox = base * dx, oy = base * dy, oz = base * dz;
+        const float g0 = gs[n * 3 + 0], g1 = gs[n * 3 + 1], g2 = gs[n * 3 + 2];
+        float* gp = g_pos + (size_t)b * gpos_stride + (size_t)n * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) gp[c] += g0 * ox.d[c] + g1 * oy.d[c] + g2 * oz.d[c];
+    }
+}
+
 // what the weight-gradient pass of the training path needs from kmb_edge_encode, per edge slot
 // (row = (b*N + i)*10 + k; every slot is written, padded ones with zero gradients)
 struct KbEdgeDump {

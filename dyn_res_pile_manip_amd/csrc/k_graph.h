@@ -44,13 +44,20 @@ __device__ __forceinline__ PushFrame push_frame(const DrpCam& c, const float* ac
     return f;
 }
 
+// gen_s_delta's hard mask of a row (planners.py:248), push_delta's one decision: a reverse pass that treats it as a constant of
+// the derivative (kb_sdelta_pos) takes it from here, so that it is the forward's on every row
+__device__ __forceinline__ bool push_hard(const PushFrame& f, float px, float py, float pz) {
+    float rx = px - f.sx, ry = py - f.sy, rz = pz - f.sz;
+    float u = __fadd_rn(__fadd_rn(__fmul_rn(rx, f.dx), __fmul_rn(ry, f.dy)), __fmul_rn(rz, f.dz));
+    return u < f.len && u > 0.0f;
+}
+
 __device__ __forceinline__ void push_delta(const PushFrame& f, float px, float py, float pz,
                                            float& ox, float& oy, float& oz) {
     // ortho = (-dir_y, dir_x, 0): planners.py:242
     float rx = px - f.sx, ry = py - f.sy, rz = pz - f.sz;
     float v = __fadd_rn(__fadd_rn(__fmul_rn(rx, -f.dy), __fmul_rn(ry, f.dx)), __fmul_rn(rz, 0.0f));
-    float u = __fadd_rn(__fadd_rn(__fmul_rn(rx, f.dx), __fmul_rn(ry, f.dy)), __fmul_rn(rz, f.dz));
-    float hard = (u < f.len && u > 0.0f) ? 1.0f : 0.0f;                       // :248
+    float hard = push_hard(f, px, py, pz) ? 1.0f : 0.0f;                      // :248
     float soft = fmaxf(fmaxf(-DRP_PUSHER_W - v, 0.0f), fmaxf(v - DRP_PUSHER_W, 0.0f));  // :249-250
     soft = expf(__fdiv_rn(-soft, DRP_SOFT_SCALE));                            // :251
     float tx = f.ex - px, ty = f.ey - py, tz = f.ez - pz;

@@ -9,6 +9,7 @@
 // workgroup in HBM, added up by a second launch in a fixed order (no atomics: deterministic).
 #pragma once
 #include "drp_common.h"
+#include "k_graph.h"
 #include "k_mlp_split.h"
 
 // d loss / d s_pred_t and the loss itself, every rollout step in one launch (grid B x H; blockIdx.y = t: the states of
@@ -65,12 +66,34 @@ kt_unpack_inputs(const float* __restrict__ sdelta_in /* [B][H][N][3] */, const f
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
         const size_t bt = e / n3, r = e - bt * n3;
         const int b = (int)(bt / H), t = (int)(bt - (size_t)b * H);
-        sdelta_out[((size_t)t * B + b) * n3 + r] = sdelta_in[e];
+        if (sdelta_in != nullptr) sdelta_out[((size_t)t * B + b) * n3 + r] = sdelta_in[e];     // (null: kt_sdelta_actions writes the slices)
         if (e < (size_t)B * N) {
             const int ab = (int)(e / N), ai = (int)(e - (size_t)ab * N);
             attr_out[e] = attrs_in[(size_t)ab * (H + 1) * N + ai];
         }
         if (e < (size_t)B) dens_out[e] = dens_in[e];
+    }
+}
+
+// The impulses of one rollout step from the batch's pushes, on the state the step actually reads (drp_train_step_actions;
+// planners.py:211-257 at s_cur): row n < particle_nums[b] gets gen_s_delta(s_cur[b], action[b])[n] -- k_sdelta's push_frame and
+// push_delta, so the bits of drp_gen_s_delta -- and the padded rows +0.0f, what collate_fn's zero rows carry as data.  The
+// mask is the point: a push over the camera-frame origin would move the zero rows.  grid B; s_cur and actions strided per
+// sample; s_delta [B][N][3] (the tape's slice of the step).
+__global__ void __launch_bounds__(256)
+kt_sdelta_actions(const float* __restrict__ s_cur, size_t s_stride, const float* __restrict__ actions, size_t act_stride,
+                  const int* __restrict__ particle_nums, int N, float* __restrict__ s_delta, DrpCam cam) {
+    const int b = blockIdx.x;
+    const int nb = min(max(particle_nums[b], 0), N);
+    const PushFrame f = push_frame(cam, actions + (size_t)b * act_stride);
+    const float* s = s_cur + (size_t)b * s_stride;
+    float* o = s_delta + (size_t)b * N * 3;
+    for (int i = threadIdx.x; i < N; i += blockDim.x) {
+        float x = 0.0f, y = 0.0f, z = 0.0f;
+        if (i < nb) push_delta(f, s[i * 3 + 0], s[i * 3 + 1], s[i * 3 + 2], x, y, z);
+        o[i * 3 + 0] = x;
+        o[i * 3 + 1] = y;
+        o[i * 3 + 2] = z;
     }
 }
 

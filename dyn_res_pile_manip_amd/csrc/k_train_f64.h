@@ -38,6 +38,27 @@ __global__ __launch_bounds__(256) void kt64_stage_step(const double* __restrict_
     s32[i] = (float)s_t[i];
 }
 
+// step t's impulse from the batch's pushes (drp_train_grad_f64_actions): kg_sdelta on the chunk's state with the padding mask --
+// row n < nums[b0 + b] gets gen_s_delta(s_t[b], act[b0 + b, t])[n] in double, the padded rows zero -- and the fp32 roundings the
+// graph build reads.  grid = samples of the chunk; act: the batch's pushes [B][H][4]
+__global__ __launch_bounds__(256) void kt64_sdelta_actions(const double* __restrict__ s_t, const float* __restrict__ act,
+                                                           const int* __restrict__ nums, int b0, int N, int H, int t, DrpCam cam,
+                                                           double* __restrict__ sd_t, float* __restrict__ s32, float* __restrict__ sd32) {
+    const int b = blockIdx.x;
+    const float* ab = act + ((size_t)(b0 + b) * H + t) * 4;
+    const double a[4] = {(double)ab[0], (double)ab[1], (double)ab[2], (double)ab[3]};
+    const KgFrame<double> f = kg_frame<double>(cam, a);
+    const int nb = min(max(nums[b0 + b], 0), N);
+    for (int n = threadIdx.x; n < N; n += blockDim.x) {
+        const size_t o = ((size_t)b * N + n) * 3;
+        const double p[3] = {s_t[o], s_t[o + 1], s_t[o + 2]};
+        double out[3] = {0.0, 0.0, 0.0};
+        if (n < nb) kg_push<double>(f, p, out);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { sd_t[o + k] = out[k]; s32[o + k] = (float)p[k]; sd32[o + k] = (float)out[k]; }
+    }
+}
+
 // the loss term of (sample b, step t) = mse(s_pred[b, :n_b], s_nxt[b, :n_b]) / (H B) and its seed of the reverse pass,
 // 2 (s_pred - s_nxt) / (3 n_b H B) on real rows, 0 on padded rows.  grid (bc, H); s_pred: the tape's states [H+1][bc*N,3]
 // (slice t + 1), s_nxt: the caller's states [B][H+1][N][3] (fp32, widened exactly), loss [H][B], seed [H][bc*N,3].
@@ -83,6 +104,31 @@ __global__ __launch_bounds__(256) void kt64_state_bwd(const double* __restrict__
 #pragma unroll
     for (int k = 0; k < 3; ++k)
         g_prev[i * 3 + k] = kg_state_share(g_prev[i * 3 + k] + g_out[i * 3 + k], g_diff, cnt, rev_off, rev, N, (size_t)b, n, k);
+}
+
+// the push's share on top of kt64_state_bwd's sum (drp_train_grad_f64_actions; kg_sdelta_bwd's position part with the padding
+// mask): g_prev[b, n] += J_pos^T g_sd[b, n] on rows n < nums[b0 + b]; the hard mask a constant of the derivative, the soft mask
+// and both projections differentiated (directions 4..6 of KgDual); padded rows receive nothing
+__global__ __launch_bounds__(256) void kt64_push_bwd(const double* __restrict__ s_t, const float* __restrict__ act,
+                                                     const int* __restrict__ nums, int b0, int N, int H, int t, DrpCam cam,
+                                                     const double* __restrict__ g_sd, double* __restrict__ g_prev) {
+    const int b = blockIdx.x;
+    const float* ab = act + ((size_t)(b0 + b) * H + t) * 4;
+    KgDual a[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a[k] = KgDual((double)ab[k]);
+    const KgFrame<KgDual> f = kg_frame<KgDual>(cam, a);
+    const int nb = min(max(nums[b0 + b], 0), N);
+    for (int n = threadIdx.x; n < nb; n += blockDim.x) {
+        const size_t i = (size_t)b * N + n;
+        KgDual p[3], out[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { p[k] = KgDual(s_t[i * 3 + k]); p[k].d[4 + k] = 1.0; }
+        if (!kg_push<KgDual>(f, p, out)) continue;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            g_prev[i * 3 + k] += g_sd[i * 3] * out[0].d[4 + k] + g_sd[i * 3 + 1] * out[1].d[4 + k] + g_sd[i * 3 + 2] * out[2].d[4 + k];
+    }
 }
 
 // ---- the operands of a 64-wide layer's weight gradient ------------------------------------------------------------------

@@ -1,0 +1,57 @@
+// train_host.h -- the trainer's entry points' host arithmetic that touches no device: where a staged batch's blocks lie, and which
+// pushes a call refuses.  Plain C++ (no HIP header), so that tools/train_host_check.cpp builds it alone under the host
+// sanitizers; drp_capi.hip includes it ahead of the C ABI's sections.
+#pragma once
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+
+// the batch as uploaded (drp_train_step): states [B][H+1][N][3] | impulses [B][H][N][3] | attributes [B][H+1][N] | densities [B]
+// | particle counts [B] (ints), every block 16-byte aligned; drp_train_step_untracked (M > 0): behind them the target clouds
+// [B][H][M][3] | their counts [B][H] (ints) -- with M = 0 the layout, and so the one copy, is drp_train_step's;
+// drp_train_step_actions (`actions`): the pushes [B][H][4] where the impulses are, everything behind them moving up
+struct TrArena { size_t states, sdelta, attrs, dens, nums, targets, tnums, bytes; };
+// the impulse block: what train_stage_batch copies to TrArena::sdelta
+inline size_t tr_impulse_bytes(int B, int H, int N, bool actions) {
+    return (actions ? (size_t)B * H * 4 : (size_t)B * H * N * 3) * sizeof(float);
+}
+inline TrArena tr_layout(int B, int H, int N, int M = 0, bool actions = false) {
+    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    TrArena a{};
+    a.states = 0;
+    a.sdelta = up(a.states + (size_t)B * (H + 1) * N * 3 * sizeof(float));
+    a.attrs = up(a.sdelta + tr_impulse_bytes(B, H, N, actions));
+    a.dens = up(a.attrs + (size_t)B * (H + 1) * N * sizeof(float));
+    a.nums = up(a.dens + (size_t)B * sizeof(float));
+    a.bytes = up(a.nums + (size_t)B * sizeof(int));
+    if (M > 0) {
+        a.targets = a.bytes;
+        a.tnums = up(a.targets + (size_t)B * H * M * 3 * sizeof(float));
+        a.bytes = up(a.tnums + (size_t)B * H * sizeof(int));
+    }
+    return a;
+}
+
+// the length of a push (sx, sy, ex, ey) in the camera frame, with push_frame's operations (k_graph.h: the same fmaf chain,
+// division and sum, no contraction); m: the 3x4 world -> camera map, gs: global_scale
+inline float push_len_host(const float* m, float gs, const float* act) {
+#pragma clang fp contract(off)
+    float p[2][3];
+    for (int e = 0; e < 2; ++e)
+        for (int r = 0; r < 3; ++r)
+            p[e][r] = fmaf(m[r * 4 + 2], -act[e * 2 + 1], fmaf(m[r * 4 + 1], 0.0f, fmaf(m[r * 4 + 0], act[e * 2], m[r * 4 + 3]))) / gs;
+    const float vx = p[1][0] - p[0][0], vy = p[1][1] - p[0][1], vz = p[1][2] - p[0][2];
+    return sqrtf(vx * vx + vy * vy + vz * vz);
+}
+// the first of n pushes [n][4] whose length is zero, infinite or no number -- what would put 0 / 0 into every impulse of its step
+// (planners.py:240) and from there into every weight -- or -1; *len_out: that length
+inline long first_bad_push(const float* m, float gs, const float* actions, size_t n, float* len_out) {
+    for (size_t e = 0; e < n; ++e) {
+        const float len = push_len_host(m, gs, actions + e * 4);
+        if (!(len > 0.0f) || len == INFINITY) {
+            *len_out = len;
+            return (long)e;
+        }
+    }
+    return -1;
+}

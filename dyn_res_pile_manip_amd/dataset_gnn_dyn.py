@@ -152,7 +152,8 @@ class ParticleDataset(object):
 
     def load(self, idx):
         """The files of sample idx, decoded (thread-safe, no random draw): depth uint16, its foreground count, the T
-        particle frames [T, n, 4] float32, the T-1 push frames [T-1, 10], colour images (load_color) or None."""
+        particle frames [T, n, 4] float32, the T-1 push frames [T-1, 10], the raw pushes [T-1, 4] (sx, sy, ex, ey as pickled),
+        colour images (load_color) or None."""
         ep, t0 = self.locate(idx)
         T = self.n_his + self.n_roll
         with open(self._path(ep, 'actions.p'), 'rb') as fp:
@@ -169,7 +170,9 @@ class ParticleDataset(object):
             for i in range(t0, t0 + T):
                 color[i - t0] = read_color(self._path(ep, '%d_color.png' % i))
         return {'episode': ep, 'depth': depth, 'n_fg': count_fg(depth, self.global_scale),
-                'particles': np.stack(frames).astype(np.float32, copy=False), 'push': push, 'color': color}
+                'particles': np.stack(frames).astype(np.float32, copy=False), 'push': push,
+                'actions': np.asarray([actions[i] for i in range(t0, t0 + T - 1)], dtype=np.float64).reshape(T - 1, 4),
+                'color': color}
 
     @staticmethod
     def draw(sample):
@@ -212,6 +215,7 @@ class ParticleDataset(object):
         batch = PaddedBatch((states, sdelta, np.zeros((B, T, n_max), np.float32), counts.astype(np.int32),
                              np.asarray([d[0] for d in draws], dtype=np.float32), imgs))
         batch.offsets = np.concatenate([[0], np.cumsum(counts.astype(np.int64))])
+        batch.actions = np.stack([s['actions'] for s in samples]).astype(np.float32)
         return batch
 
 
@@ -256,7 +260,7 @@ class UntrackedLoader(object):
                 n = int(n)
                 data.append(drop_correspondence((states[b][:, :n], sdelta[b][:, :n], attrs[b][:, :n], n, dens[b],
                                                  None if imgs is None else imgs[b]), self.rng, self.keep))
-            yield collate_untracked(data)
+            yield collate_untracked(data, actions=getattr(batch, 'actions', None))
 
 
 class _Indices(object):
@@ -307,6 +311,7 @@ class DeviceLoader(object):
         chunks = [order[k:k + self.chunk] for k in range(0, len(order), self.chunk)]
         ds = self.dataset
         done = []                    # per-sample tuples, in sample order
+        done_act = []                # their raw pushes [T-1, 4]: attached to the collated batch (collate_fn's tuple is the reference's)
         bi = 0
         with ThreadPoolExecutor(max_workers=self.threads) as pool:
             pending = [pool.submit(ds.load, i) for i in chunks[0]] if chunks else []
@@ -320,8 +325,11 @@ class DeviceLoader(object):
                     n = int(counts[j])
                     done.append((states[j, :, :n], sdelta[j, :, :n], np.zeros((T, n), np.float32), n, draws[j][0],
                                  s['color']))
+                    done_act.append(s['actions'])
                 while bi < len(batches) and len(done) >= len(batches[bi]):
                     nb = len(batches[bi])
-                    yield collate_fn(done[:nb])
-                    done = done[nb:]
+                    out = collate_fn(done[:nb])
+                    out.actions = np.stack(done_act[:nb]).astype(np.float32)
+                    yield out
+                    done, done_act = done[nb:], done_act[nb:]
                     bi += 1

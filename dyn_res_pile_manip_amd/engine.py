@@ -649,6 +649,34 @@ class Engine(object):
                                                    L.TRAIN_MODES[mode], ctypes.byref(loss), None if grad is None else _fp(grad)))
         return loss.value, grad
 
+    def train_step_actions(self, states, actions, attrs, particle_nums, particle_dens, targets=None, target_nums=None,
+                           mode='update', want_grad=False):
+        """train_step (targets None: the tracked MSE) or train_step_untracked (targets [B, n_rollout, M, 3], target_nums
+        [B, n_rollout]: the Chamfer loss) with every step's impulse computed from `actions` [B, n_rollout, 4] = (sx, sy, ex, ey) on
+        the state the step reads -- states[:, 0], then the model's own predictions -- zero on padded rows, and the push's
+        position share in the backward pass (include/drp.h: drp_train_step_actions).  Needs set_camera -> (loss, gradient blob or
+        None)."""
+        states, actions, attrs = _f32(states), _f32(actions), _f32(attrs)
+        dens = _f32(particle_dens)
+        nums = np.ascontiguousarray(particle_nums, dtype=np.int32)
+        B, T1, N, _ = states.shape
+        assert T1 == self._n_rollout + 1 and actions.shape == (B, T1 - 1, 4)
+        assert attrs.shape == (B, T1, N) and nums.shape == (B,) and dens.shape == (B,)
+        assert (targets is None) == (target_nums is None)
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        tp, tnp, M = None, None, 0
+        if targets is not None:
+            targets = _f32(targets)
+            tnums = np.ascontiguousarray(target_nums, dtype=np.int32)
+            assert targets.ndim == 4 and targets.shape[:2] == (B, T1 - 1) and targets.shape[3] == 3 and tnums.shape == (B, T1 - 1)
+            tp, tnp, M = _fp(targets), tnums.ctypes.data_as(i32p), targets.shape[2]
+        loss = ctypes.c_double()
+        grad = np.empty((38403,), np.float32) if (want_grad and mode != 'eval') else None
+        self._ck(self.lib.drp_train_step_actions(self.h, _fp(states), _fp(actions), _fp(attrs), nums.ctypes.data_as(i32p), _fp(dens),
+                                                 B, N, tp, tnp, int(M), L.TRAIN_MODES[mode], ctypes.byref(loss),
+                                                 None if grad is None else _fp(grad)))
+        return loss.value, grad
+
     # ---- the Chamfer metric of two cloud batches (include/drp.h: drp_cloud_chamfer) ----------------------------------
     def cloud_chamfer(self, p, q, n_p=None, n_q=None, want_grad=False, want_nn=False):
         """Symmetric squared Chamfer distance of p [B, N, 3] (n_p [B] real rows, default all) and q [B, M, 3] (n_q) ->
@@ -702,19 +730,47 @@ class Engine(object):
                                              ctypes.byref(loss), _dp(terms), _dp(grad), _dp(gs) if want_state else None))
         return (loss.value, terms, grad, gs) if want_state else (loss.value, terms, grad)
 
-    def train_gradient_probe(self, states, states_delta, attrs, particle_nums, particle_dens):
+    def train_grad_f64_actions(self, states, actions, attrs, particle_nums, particle_dens, want_state=False):
+        """train_grad_f64 with the pushes `actions` [B, n_rollout, 4] in place of states_delta: what
+        train_step_actions(mode='grad') computes with the MSE loss, in float64 on the device (include/drp.h:
+        drp_train_grad_f64_actions).  Needs set_camera; the same returns and the same one-shot contract."""
+        states, actions, attrs = _f32(states), _f32(actions), _f32(attrs)
+        dens = _f32(particle_dens)
+        nums = np.ascontiguousarray(particle_nums, dtype=np.int32)
+        B, T1, N, _ = states.shape
+        H = T1 - 1
+        assert actions.shape == (B, H, 4) and attrs.shape == (B, T1, N) and nums.shape == (B,) and dens.shape == (B,)
+        loss = ctypes.c_double()
+        terms = np.empty((H, B), np.float64)
+        grad = np.empty((38403,), np.float64)
+        gs = np.empty((B, H, N, 3), np.float64) if want_state else None
+        self._ck(self.lib.drp_train_grad_f64_actions(self.h, _fp(states), _fp(actions), _fp(attrs),
+                                                     nums.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _fp(dens), int(B), int(N),
+                                                     int(H), ctypes.byref(loss), _dp(terms), _dp(grad),
+                                                     _dp(gs) if want_state else None))
+        return (loss.value, terms, grad, gs) if want_state else (loss.value, terms, grad)
+
+    def train_gradient_probe(self, states, states_delta, attrs, particle_nums, particle_dens, actions=None):
         """The gradients the trainer consumes, held against float64: train_step(mode='grad', want_grad=True) on whatever tape the
         selection gives, then train_grad_f64 on the same batch -> {'tensors': {state_dict key: {'max_abs_err', 'max_abs_ref',
         'rel' = err / max(ref, 1e-300)}}, 'worst': the key of the largest rel, 'rel': that rel, 'loss32', 'loss64', 'loss_diff',
         'tape': 'fused' | 'mfma'}.  Needs train_begin, like train_step; it changes no weight, Adam moment or iteration count, so a
         following train_step(mode='update') is what it would have been.  Like train_step it ends a running planner session, and
-        it resets the dispatch marks: last_dispatch() afterwards names this call's kernels."""
+        it resets the dispatch marks: last_dispatch() afterwards names this call's kernels.  With `actions` [B, n_rollout, 4]
+        (states_delta is then ignored and may be None) the pair is train_step_actions and train_grad_f64_actions: the impulses
+        from the pushes on the predicted state, the MSE loss."""
         from .weights import STATE_DICT_KEYS
         self.dispatch_reset()
-        loss32, g32 = self.train_step(states, states_delta, attrs, particle_nums, particle_dens, mode='grad', want_grad=True)
+        if actions is not None:
+            loss32, g32 = self.train_step_actions(states, actions, attrs, particle_nums, particle_dens, mode='grad', want_grad=True)
+        else:
+            loss32, g32 = self.train_step(states, states_delta, attrs, particle_nums, particle_dens, mode='grad', want_grad=True)
         # the fp32 matrix engine's tape is the only user of k_aggregate_tape (pick_tape_engine: selected, or after a range refusal)
         tape = 'mfma' if 'k_aggregate_tape' in self.last_dispatch() else 'fused'
-        loss64, _, g64 = self.train_grad_f64(states, states_delta, attrs, particle_nums, particle_dens)
+        if actions is not None:
+            loss64, _, g64 = self.train_grad_f64_actions(states, actions, attrs, particle_nums, particle_dens)
+        else:
+            loss64, _, g64 = self.train_grad_f64(states, states_delta, attrs, particle_nums, particle_dens)
         tensors, off, worst = {}, 0, None
         for key, shape in STATE_DICT_KEYS:
             n = int(np.prod(shape))

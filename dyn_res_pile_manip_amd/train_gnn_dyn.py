@@ -28,6 +28,8 @@ class PaddedBatch(tuple):
     """What `collate_fn` returns: the reference's 6-tuple (states, states_delta, attr, particle_num,
     particle_den, color_imgs), plus the ragged layout it was built from."""
     offsets = None          # [B+1] running particle offset of each sample in the concatenated cloud
+    actions = None          # [B, n_rollout, 4] float32, the raw pushes (sx, sy, ex, ey) of the samples' steps where the loader has
+                            # them (dataset_gnn_dyn.get_batch / DeviceLoader): what impulses='actions' trains on
 
 
 def collate_fn(data):
@@ -55,10 +57,10 @@ def collate_fn(data):
     return batch
 
 
-def collate_untracked(data):
+def collate_untracked(data, actions=None):
     """collate_fn for untracked samples (dataset_gnn_dyn.drop_correspondence: the 6-tuple, then a list of n_rollout target clouds
     [m_t, 3]): the six fields as collate_fn gives them, then targets [B, H, M, 3] zero-padded to the largest cloud and
-    target_nums [B, H] int32."""
+    target_nums [B, H] int32.  actions: the samples' pushes [B, H, 4], carried through as `.actions`."""
     batch = collate_fn(data)
     B, H = len(data), len(data[0][6])
     counts = np.array([[np.asarray(c).shape[0] for c in d[6]] for d in data], dtype=np.int64).reshape(B, H)
@@ -69,6 +71,8 @@ def collate_untracked(data):
     targets[owner, slot] = np.concatenate([_np(c).reshape(-1, 3) for d in data for c in d[6]], axis=0)
     out = PaddedBatch(tuple(batch) + (targets.reshape(B, H, -1, 3), counts.astype(np.int32)))
     out.offsets = batch.offsets
+    if actions is not None:
+        out.actions = np.asarray(actions, dtype=np.float32).reshape(B, H, 4)
     return out
 
 
@@ -89,15 +93,30 @@ class DeviceAdam(object):
 
 
 LOSSES = ('mse', 'chamfer')
+IMPULSES = ('data', 'actions')
 
 
-def run_batch(model, optimizer, data, phase='train', n_rollout=None, loss='mse'):
+def batch_actions(data):
+    """the pushes [B, n_rollout, 4] a loader attached to a collated batch (impulses='actions')"""
+    actions = getattr(data, 'actions', None)
+    if actions is None:
+        raise ValueError('impulses=\'actions\' needs a batch with .actions [B, n_rollout, 4] (ParticleDataset.get_batch, DeviceLoader, '
+                         'UntrackedLoader attach it)')
+    return _np(actions)
+
+
+def run_batch(model, optimizer, data, phase='train', n_rollout=None, loss='mse', impulses='data'):
     """The loop body at train/train_gnn_dyn.py:159-210 -> loss (python float, what loss.item() is there).  loss='chamfer': `data`
     is collate_untracked's (targets and target_nums behind the six fields) and each step's term is the Chamfer distance to its
-    target cloud (Engine.train_step_untracked)."""
+    target cloud (Engine.train_step_untracked).  impulses='actions': every step's impulse is computed from the batch's pushes
+    (`data.actions`) on the state the step reads instead of taken from states_delta (Engine.train_step_actions; the engine's
+    camera must be set)."""
     if loss not in LOSSES:
         raise ValueError('loss must be one of %s, got %r' % (LOSSES, loss))
+    if impulses not in IMPULSES:
+        raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
     states, states_delta, attrs, particle_nums, particle_dens = [data[i] for i in range(5)]
+    actions = batch_actions(data) if impulses == 'actions' else None
     states = _np(states)
     B, length, n_obj, _ = states.shape
     if n_rollout is not None:
@@ -106,6 +125,12 @@ def run_batch(model, optimizer, data, phase='train', n_rollout=None, loss='mse')
     if hasattr(model, '_claim'):
         model._claim()                                  # models share the process's context: this one's weights in
         model._device_ahead = model._device_ahead or mode == 'update'
+    if impulses == 'actions':
+        chamfer = loss == 'chamfer'
+        value, _ = model.engine.train_step_actions(states, actions, _np(attrs), _np(particle_nums, np.int32),
+                                                   _np(particle_dens), _np(data[6]) if chamfer else None,
+                                                   _np(data[7], np.int32) if chamfer else None, mode=mode)
+        return value
     if loss == 'chamfer':
         value, _ = model.engine.train_step_untracked(states, _np(states_delta), _np(attrs), _np(particle_nums, np.int32),
                                                      _np(particle_dens), _np(data[6]), _np(data[7], np.int32), mode=mode)
@@ -127,27 +152,31 @@ class AverageMeter(object):
         self.avg = self.sum / self.count
 
 
-def probe_batch(model, data):
+def probe_batch(model, data, impulses='data'):
     """Engine.train_gradient_probe on a collated batch: the trainer's fp32 gradients against the float64 evaluation of the same
     batch on the device; weights, Adam state and iteration count are untouched"""
     states, states_delta, attrs, particle_nums, particle_dens = [data[i] for i in range(5)]
     if hasattr(model, '_claim'):
         model._claim()
     return model.engine.train_gradient_probe(_np(states), _np(states_delta), _np(attrs), _np(particle_nums, np.int32),
-                                             _np(particle_dens))
+                                             _np(particle_dens), actions=batch_actions(data) if impulses == 'actions' else None)
 
 
 def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=None, first_epoch=0, grad_probe_every=0,
-          loss='mse'):
+          loss='mse', impulses='data'):
     """train/train_gnn_dyn.py:134-246 without the file I/O: `dataloaders` = {'train': iterable of
     collated batches, 'valid': ...}.  Returns {'best_valid_loss', 'history': [(epoch, phase, rmse)]}.
     ckp(epoch, i, model): called after training batch i when i % ckp_per_iter == 0 (:217-218); first_epoch: the epoch
     a resumed run starts from (:136).  grad_probe_every = k > 0: every k-th training batch (i % k == 0) is probed before its
     update (probe_batch); the worst tensor's rel goes to the history as (epoch, 'grad_probe', rel) and to the log.
     loss='chamfer': the batches are collate_untracked's and every step's term is the Chamfer distance to its target cloud; the
-    float64 yardstick on the device is MSE-only, so grad_probe_every > 0 is refused with it."""
+    float64 yardstick on the device is MSE-only, so grad_probe_every > 0 is refused with it.  impulses='actions': the batches
+    carry `.actions` and the model is trained through the push (run_batch); with real untracked data this is what makes
+    n_rollout > 1 meaningful.  The engine's camera must be set (main does it)."""
     if loss not in LOSSES:
         raise ValueError('loss must be one of %s, got %r' % (LOSSES, loss))
+    if impulses not in IMPULSES:
+        raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
     if loss == 'chamfer' and grad_probe_every > 0:
         raise ValueError('grad_probe_every needs loss=\'mse\': the float64 yardstick of the gradients is MSE-only')
     loss_kind = loss
@@ -163,12 +192,12 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
             meter = AverageMeter()
             for i, data in enumerate(dataloaders[phase]):
                 if grad_probe_every > 0 and phase == 'train' and i % grad_probe_every == 0:
-                    pr = probe_batch(model, data)
+                    pr = probe_batch(model, data, impulses)
                     history.append((epoch, 'grad_probe', float(pr['rel'])))
                     if log is not None:
                         log('grad_probe [%d][%d] worst %s rel %.3e (%s tape), loss diff %.3e' % (epoch, i, pr['worst'], pr['rel'],
                                                                                                pr['tape'], pr['loss_diff']))
-                loss = run_batch(model, optimizer, data, phase, n_rollout, loss=loss_kind)
+                loss = run_batch(model, optimizer, data, phase, n_rollout, loss=loss_kind, impulses=impulses)
                 meter.update(loss, _np(data[0]).shape[0])
                 if log is not None and i % tc['log_per_iter'] == 0:
                     log('%s [%d][%d] LR: %.6f, Loss: %.6f (%.6f)' % (phase, epoch, i, optimizer.param_groups[0]['lr'],
@@ -205,14 +234,16 @@ def set_seed(seed):
 
 
 def main(config, data_root=None, train_dir=None, cam=None, chunk=64, threads=8, n_epoch=None, engine=None, grad_probe_every=0,
-         loss='mse'):
+         loss='mse', impulses='data'):
     """The file-level part of train/train_gnn_dyn.py:train() (:45-130, :196-228): seed, the log directory with config.yaml
     and log.txt, the 'train' / 'valid' ParticleDatasets and their DeviceLoaders, a fresh model (torch.nn.Linear's default
     initialisation) or the resumed checkpoint, net_epoch_%d_iter_%d.pth every ckp_per_iter training batches and
     net_best.pth, all in the state_dict layout PropNetDiffDenModel.load_state_dict reads.  cam = (cam_params,
     cam_extrinsic), by default the demo camera (synthetic.py; FleX is not available).  Returns train()'s result and
     the directory.  loss='chamfer': the recorded episodes' correspondence is dropped (dataset_gnn_dyn.drop_correspondence on
-    every sample, seeded by train.random_seed) and the model is trained on the Chamfer distance to the untracked clouds."""
+    every sample, seeded by train.random_seed) and the model is trained on the Chamfer distance to the untracked clouds.
+    impulses='actions': the engine's camera is set from the dataset's extrinsics and global_scale and every step's impulse comes
+    from the recorded push on the state the step reads (train)."""
     import time
     import yaml
     from . import synthetic, weights
@@ -240,6 +271,10 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=64, threads=8, 
         loaders = {ph: UntrackedLoader(loaders[ph], seed=tc['random_seed'] + k, reseed=(ph == 'valid'))
                    for k, ph in enumerate(('train', 'valid'))}
     model = PropNetDiffDenModel(config, engine=engine)
+    if impulses == 'actions':
+        from .planners import world2cam_affine
+        gs = float(config['dataset']['global_scale'])
+        model.engine.set_camera(world2cam_affine(np.asarray(cam[1], dtype=np.float64)), gs, cam[0])
     if resume['active']:
         path = os.path.join(train_dir, 'net_epoch_%d_iter_%d.pth' % (resume['epoch'], resume['iter']))
         model.load_state_dict(weights.state_dict_from_blob(weights.load_checkpoint(path)))
@@ -259,7 +294,7 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=64, threads=8, 
 
         result = train(config, model, loaders, n_epoch=n_epoch, log=log, on_best=on_best, ckp=ckp,
                        first_epoch=resume['epoch'] if resume['active'] and resume['epoch'] > 0 else 0,
-                       grad_probe_every=grad_probe_every, loss=loss)
+                       grad_probe_every=grad_probe_every, loss=loss, impulses=impulses)
         for epoch, phase, rmse in result['history']:
             if phase == 'grad_probe':                   # logged when it was taken
                 continue
@@ -284,6 +319,8 @@ def _cli(argv=None):
                     help='hold every k-th training batch\'s gradients against float64 before its update (0: never)')
     ap.add_argument('--loss', choices=LOSSES, default='mse',
                     help='chamfer: drop the recorded correspondence and train on the Chamfer distance to the untracked clouds')
+    ap.add_argument('--impulses', choices=IMPULSES, default='data',
+                    help='actions: compute every step\'s impulse from the recorded push on the state the model predicted')
     a = ap.parse_args(argv)
     config = default_config()
     if a.config:
@@ -294,7 +331,7 @@ def _cli(argv=None):
     if a.n_timestep is not None:
         config['dataset']['n_timestep'] = a.n_timestep
     result, d = main(config, a.data_root, a.train_dir, chunk=a.chunk, threads=a.threads, n_epoch=a.epochs,
-                     grad_probe_every=a.grad_probe_every, loss=a.loss)
+                     grad_probe_every=a.grad_probe_every, loss=a.loss, impulses=a.impulses)
     print('best valid loss %.6f, checkpoints in %s' % (np.sqrt(result['best_valid_loss']), d))
 
 

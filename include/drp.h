@@ -253,6 +253,27 @@ int drp_train_step_untracked(drp_ctx* ctx, const float* states, const float* sta
                              const int32_t* particle_nums, const float* particle_dens, int B, int N,
                              const float* targets /*[B][H][M][3]*/, const int32_t* target_nums /*[B][H]*/, int M,
                              int mode, double* loss_out, float* grad_out);
+/* drp_train_step (targets == NULL, M == 0: the tracked MSE) or drp_train_step_untracked (otherwise: the Chamfer loss) with every
+ * step's impulse computed from the batch's pushes ON THE STATE THE STEP READS, as every consumer of the trained model does:
+ * train/train_gnn_dyn.py:159-189 with states_delta[:, t] replaced by planners.py:211-257 evaluated at s_cur.  actions
+ * [B, n_rollout, 4] = (sx, sy, ex, ey) in world units, the planner's convention, through the camera of drp_set_camera.
+ *   forward   s_cur_0 = states[:, 0], s_cur_t = s_pred_{t-1}; row n < particle_nums[b] of step t's impulse is
+ *             gen_s_delta(s_cur_t[b], actions[b, t])[n] with the arithmetic (and on those rows the bits) of drp_gen_s_delta; rows
+ *             n >= particle_nums[b] get +0.0f, what collate_fn's padding carries as data -- they still join the graph.
+ *   backward  for t > 0 and real rows d loss / d s_pred_{t-1}[b, n] += J_pos^T g_s_delta_t[b, n]: the hard mask 0 < u < L is a
+ *             constant of the derivative, the soft mask and both projections are differentiated (as drp_gd_grad); padded rows
+ *             receive nothing.  Per element the order is fixed -- loss seed, residual share, relation-encoder share, push share
+ *             -- and nothing is atomic: two runs give the same bits.  d loss / d actions is no output: the pushes are data.
+ * Loss, weight gradients, Adam, re-packing and the one wait are drp_train_step's; with n_rollout = 1 the result has the bits of
+ * drp_train_step fed drp_gen_s_delta's impulses with the padded rows zeroed.  The tape engine's range check takes the pushes'
+ * length bound where drp_train_step takes max |states_delta|.  DRP_ESTATE without drp_train_begin or without a camera;
+ * DRP_EINVAL for a null argument (actions included), a push of zero length in the camera frame (0 / 0 in every impulse, and
+ * from there in every weight; the dataset path refuses such a push too), and whatever drp_train_step(_untracked) refuses.  A
+ * refused call leaves the context as it was. */
+int drp_train_step_actions(drp_ctx* ctx, const float* states, const float* actions /*[B][H][4]*/, const float* attrs,
+                           const int32_t* particle_nums, const float* particle_dens, int B, int N,
+                           const float* targets /*[B][H][M][3] or NULL*/, const int32_t* target_nums /*[B][H] or NULL*/, int M,
+                           int mode, double* loss_out, float* grad_out);
 int drp_train_set_lr(drp_ctx* ctx, double lr);
 /* model.state_dict() (train/train_gnn_dyn.py:226,244): the current weights, drp_load_weights layout */
 int drp_get_weights(drp_ctx* ctx, float* blob_out, size_t n_floats);
@@ -568,6 +589,15 @@ int drp_gd_grad_f64(drp_ctx* ctx, const float* s0, const float* attr, const floa
 int drp_train_grad_f64(drp_ctx* ctx, const float* states, const float* states_delta, const float* attrs,
                        const int32_t* particle_nums, const float* particle_dens, int B, int N, int n_rollout,
                        double* loss_out, double* loss_terms_out, double* grad_out, double* grad_state_out);
+/* drp_train_grad_f64 with actions [B, n_rollout, 4] in place of states_delta: the yardstick of drp_train_step_actions' gradients
+ * with the MSE loss (train/train_gnn_dyn.py:159-189 with planners.py:211-257 evaluated at s_cur, in double).  Step t's impulse is
+ * drp_gd_grad_f64's gen_s_delta on the double state, zero on rows n >= particle_nums[b]; for t > 0 the push's position share
+ * (hard mask constant, soft mask and projections differentiated) joins d loss / d s_pred_{t-1} on real rows.  Everything else,
+ * the one-shot contract included, is drp_train_grad_f64's.  DRP_ESTATE also without a camera; DRP_EINVAL also for a push of
+ * zero length. */
+int drp_train_grad_f64_actions(drp_ctx* ctx, const float* states, const float* actions, const float* attrs,
+                               const int32_t* particle_nums, const float* particle_dens, int B, int N, int n_rollout,
+                               double* loss_out, double* loss_terms_out, double* grad_out, double* grad_state_out);
 
 /* ---- symmetric squared Chamfer distance of two padded cloud batches and its gradient; no counterpart in the reference
  * (env/flex_rewards.py:9 imports pytorch3d's and never uses it).  p [B][N][3] with n_p[b] real rows, q [B][M][3] with n_q[b];

@@ -1,0 +1,129 @@
+// Host-code hygiene of the trainer's entry points (csrc/train_host.h): where the blocks of a staged batch lie, with data impulses,
+// with pushes and with target clouds, and which pushes a call refuses.  A stand-alone program for the host sanitizers:
+//
+//   hipcc -x hip --offload-arch=gfx950 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
+//         tools/train_host_check.cpp -o build/train_host_check && build/train_host_check
+//   (or any C++17 compiler: c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all ...)
+//
+// It stages batches as train_stage_batch does -- the same copies, to the offsets tr_layout gives, into a heap block of exactly
+// TrArena::bytes -- so a block that overlaps the next one or runs past the end is the sanitizer's finding; the offsets are held
+// to the documented layout as well.  No device is touched.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <limits>
+#include <vector>
+
+#include "../dyn_res_pile_manip_amd/csrc/train_host.h"
+
+static int failures = 0;
+#define EXPECT(cond)                                                         \
+    do {                                                                     \
+        if (!(cond)) {                                                       \
+            std::printf("FAILED line %d: %s\n", __LINE__, #cond);            \
+            ++failures;                                                      \
+        }                                                                    \
+    } while (0)
+
+static void stage(int B, int H, int N, int M, bool actions) {
+    const TrArena lay = tr_layout(B, H, N, M, actions);
+    const size_t n_st = (size_t)B * (H + 1) * N * 3, n_imp = actions ? (size_t)B * H * 4 : (size_t)B * H * N * 3;
+    const size_t n_at = (size_t)B * (H + 1) * N, n_tg = (size_t)B * H * M * 3;
+    std::vector<float> states(n_st, 1.0f), imp(n_imp, 2.0f), attrs(n_at, 3.0f), dens(B, 4.0f), targets(n_tg, 6.0f);
+    std::vector<int32_t> nums(B, 5), tnums((size_t)B * H, 7);
+    // every block starts on 16 bytes, in the documented order, and ends before the next one starts
+    const size_t off[] = {lay.states, lay.sdelta, lay.attrs, lay.dens, lay.nums, M > 0 ? lay.targets : lay.bytes,
+                          M > 0 ? lay.tnums : lay.bytes, lay.bytes};
+    const size_t len[] = {n_st * 4, n_imp * 4, n_at * 4, (size_t)B * 4, (size_t)B * 4, n_tg * 4, M > 0 ? (size_t)B * H * 4 : 0};
+    for (int k = 0; k < 7; ++k) {
+        EXPECT(off[k] % 16 == 0);
+        EXPECT(off[k] + len[k] <= off[k + 1]);
+        EXPECT(off[k + 1] - (off[k] + len[k]) < 16);             // no more than the alignment between two blocks
+    }
+    EXPECT(tr_impulse_bytes(B, H, N, actions) == n_imp * 4);
+    if (!actions && M == 0) {                                    // the existing call's layout, restated from its description
+        auto up = [](size_t v) { return (v + 15) / 16 * 16; };
+        size_t at = up(n_st * 4);
+        EXPECT(lay.sdelta == at);
+        at = up(at + (size_t)B * H * N * 3 * 4);
+        EXPECT(lay.attrs == at);
+        at = up(at + n_at * 4);
+        EXPECT(lay.dens == at);
+        at = up(at + (size_t)B * 4);
+        EXPECT(lay.nums == at);
+        EXPECT(lay.bytes == up(at + (size_t)B * 4));
+    }
+    if (actions) {                                               // the pushes shrink the impulse block: nothing else moves ahead of it
+        const TrArena data = tr_layout(B, H, N, M, false);
+        EXPECT(lay.states == data.states && lay.sdelta == data.sdelta);
+        EXPECT(lay.bytes <= data.bytes);
+    }
+    // train_stage_batch's copies into a block of exactly lay.bytes
+    char* pin = static_cast<char*>(std::malloc(lay.bytes));
+    std::memset(pin, 0xff, lay.bytes);
+    std::memcpy(pin + lay.states, states.data(), n_st * sizeof(float));
+    std::memcpy(pin + lay.sdelta, imp.data(), tr_impulse_bytes(B, H, N, actions));
+    std::memcpy(pin + lay.attrs, attrs.data(), n_at * sizeof(float));
+    std::memcpy(pin + lay.dens, dens.data(), (size_t)B * sizeof(float));
+    std::memcpy(pin + lay.nums, nums.data(), (size_t)B * sizeof(int));
+    if (M > 0) {
+        std::memcpy(pin + lay.targets, targets.data(), n_tg * sizeof(float));
+        std::memcpy(pin + lay.tnums, tnums.data(), (size_t)B * H * sizeof(int));
+    }
+    // read back as the kernels address it: no copy overwrote another block
+    auto f = [&](size_t o, size_t i) { float v; std::memcpy(&v, pin + o + i * 4, 4); return v; };
+    auto n = [&](size_t o, size_t i) { int32_t v; std::memcpy(&v, pin + o + i * 4, 4); return v; };
+    EXPECT(f(lay.states, 0) == 1.0f && f(lay.states, n_st - 1) == 1.0f);
+    EXPECT(f(lay.sdelta, 0) == 2.0f && f(lay.sdelta, n_imp - 1) == 2.0f);
+    EXPECT(f(lay.attrs, 0) == 3.0f && f(lay.attrs, n_at - 1) == 3.0f);
+    EXPECT(f(lay.dens, 0) == 4.0f && f(lay.dens, B - 1) == 4.0f);
+    EXPECT(n(lay.nums, 0) == 5 && n(lay.nums, B - 1) == 5);
+    if (M > 0) {
+        EXPECT(f(lay.targets, 0) == 6.0f && f(lay.targets, n_tg - 1) == 6.0f);
+        EXPECT(n(lay.tnums, 0) == 7 && n(lay.tnums, (size_t)B * H - 1) == 7);
+    }
+    std::free(pin);
+}
+
+int main() {
+    // odd sizes (no block a multiple of 16 bytes), one sample, the reference's batch, a large one
+    const int shapes[][4] = {{1, 1, 1, 0}, {1, 1, 5, 3}, {3, 3, 24, 0}, {3, 3, 23, 17}, {2, 5, 11, 0}, {4, 5, 300, 0}, {4, 5, 300, 300},
+                             {7, 2, 301, 299}, {32, 5, 300, 0}, {2, 64, 9, 1}};
+    for (const auto& s : shapes)
+        for (int actions = 0; actions < 2; ++actions) stage(s[0], s[1], s[2], s[3], actions != 0);
+
+    // the push check, with the demo camera's map (x, z, -y + 18 scaled by 1 / 24: a camera that looks straight down)
+    const float m[12] = {1, 0, 0, 0, 0, 0, 1, 0, 0, -1, 0, 18};
+    const float gs = 24.0f;
+    const float inf = std::numeric_limits<float>::infinity(), nan = std::numeric_limits<float>::quiet_NaN();
+    float len = -1.0f;
+    {
+        const int B = 3, H = 4;
+        std::vector<float> acts((size_t)B * H * 4);
+        for (int e = 0; e < B * H; ++e) {
+            acts[e * 4 + 0] = -3.0f + 0.1f * e; acts[e * 4 + 1] = 0.5f; acts[e * 4 + 2] = 3.0f; acts[e * 4 + 3] = -0.25f * e;
+        }
+        EXPECT(first_bad_push(m, gs, acts.data(), acts.size() / 4, &len) == -1 && len == -1.0f);
+        EXPECT(std::fabs(push_len_host(m, gs, acts.data()) - std::sqrt(36.0f + 0.25f) / 24.0f) < 1e-6f);
+        std::vector<float> bad = acts;                           // a zero-length push in the middle of the batch
+        bad[(1 * H + 1) * 4 + 2] = bad[(1 * H + 1) * 4 + 0];
+        bad[(1 * H + 1) * 4 + 3] = bad[(1 * H + 1) * 4 + 1];
+        EXPECT(first_bad_push(m, gs, bad.data(), bad.size() / 4, &len) == 1 * H + 1 && len == 0.0f);
+        bad = acts;                                              // the last one: the loop reads every push and no further
+        bad[bad.size() - 1] = nan;
+        EXPECT(first_bad_push(m, gs, bad.data(), bad.size() / 4, &len) == B * H - 1 && len != len);
+        bad = acts;
+        bad[0] = inf;
+        EXPECT(first_bad_push(m, gs, bad.data(), bad.size() / 4, &len) == 0);
+        bad = acts;
+        bad[2] = 3e38f; bad[0] = -3e38f;                         // a finite push whose length overflows
+        EXPECT(first_bad_push(m, gs, bad.data(), bad.size() / 4, &len) == 0 && len == inf);
+        EXPECT(first_bad_push(m, gs, acts.data(), 0, &len) == -1);
+    }
+    {
+        const float denormal[4] = {0.0f, 0.0f, 1e-30f, 0.0f};   // its square underflows: the length is zero as push_frame computes it
+        EXPECT(first_bad_push(m, gs, denormal, 1, &len) == 0 && len == 0.0f);
+    }
+    std::printf(failures ? "%d checks FAILED\n" : "train_host_check: all checks passed\n", failures);
+    return failures ? 1 : 0;
+}

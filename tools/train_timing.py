@@ -3,7 +3,12 @@ config/train/gnn_dyn.yaml) on the device, next to the dense torch-autograd oracl
 
   python tools/train_timing.py [shape index [iterations]]
   python tools/train_timing.py --loss chamfer    a Chamfer update (train_step_untracked) against an MSE update of the same shape,
-                                                 interleaved on one context: B = 4 and 32, N = M = 300, n_rollout = 5"""
+                                                 interleaved on one context: B = 4 and 32, N = M = 300, n_rollout = 5
+  python tools/train_timing.py --impulses actions [iterations]
+                                                 an update through the push (train_step_actions: random pushes that cross the
+                                                 pile) against an update on data impulses, interleaved on one context, at the
+                                                 reference's batch (4 x <= 300 particles, n_rollout = 5); `--impulses data` is
+                                                 the default run"""
 import sys
 import time
 
@@ -24,6 +29,18 @@ CHAMFER = '--loss' in sys.argv and sys.argv[sys.argv.index('--loss') + 1] == 'ch
 if CHAMFER:
     sys.argv = sys.argv[:1]
     SHAPES = ((4, [300] * 4), (32, [300] * 32))
+ACTIONS = False
+if '--impulses' in sys.argv:
+    at = sys.argv.index('--impulses')
+    if sys.argv[at + 1] not in ('data', 'actions'):
+        raise SystemExit('--impulses data | actions')
+    ACTIONS = sys.argv[at + 1] == 'actions'
+    del sys.argv[at:at + 2]
+if ACTIONS:
+    from dyn_res_pile_manip_amd.planners import world2cam_affine
+    eng.set_camera(world2cam_affine(syn.demo_cam_extrinsics()), 24.0, syn.demo_cam_params())
+    SHAPES = SHAPES[:1]
+    sys.argv.insert(1, '0')
 if len(sys.argv) > 1:                      # one shape only (profiling): its index
     SHAPES = (SHAPES[int(sys.argv[1])],)
 ITERS = int(sys.argv[2]) if len(sys.argv) > 2 else 10
@@ -61,6 +78,27 @@ for B, nums in SHAPES:
         print('B=%d N=M=%d n_rollout=%d: update with the MSE loss %.3f ms (blocks %.3f .. %.3f), with the Chamfer loss %.3f ms '
               '(%.3f .. %.3f)' % (B, N, H, np.median(took['mse']), min(took['mse']), max(took['mse']),
                                   np.median(took['chamfer']), min(took['chamfer']), max(took['chamfer'])), flush=True)
+        continue
+    if ACTIONS:
+        acts = np.stack([np.stack([syn.pushes_through(states[b, t, :n][None], seed=10 * b + t)[0] for t in range(H)])
+                         for b, n in enumerate(nums)])
+        steps = {'data': lambda: eng.train_step(states, sdelta, attrs, pn, dens, mode='update'),
+                 'actions': lambda: eng.train_step_actions(states, acts, attrs, pn, dens, mode='update')}
+        for k in steps:
+            steps[k](), steps[k]()
+        took = {'data': [], 'actions': []}
+        for rep in range(6):                                        # interleaved blocks; the median of each
+            for k in ('data', 'actions'):
+                eng.sync()
+                t0 = time.perf_counter()
+                for _ in range(ITERS):
+                    loss, _ = steps[k]()
+                    assert np.isfinite(loss), (k, loss)
+                eng.sync()
+                took[k].append((time.perf_counter() - t0) / ITERS * 1e3)
+        print('B=%d N<=%d n_rollout=%d: update on data impulses %.3f ms (blocks %.3f .. %.3f), through the push %.3f ms '
+              '(%.3f .. %.3f)' % (B, N, H, np.median(took['data']), min(took['data']), max(took['data']),
+                                  np.median(took['actions']), min(took['actions']), max(took['actions'])), flush=True)
         continue
     for _ in range(2):
         eng.train_step(states, sdelta, attrs, pn, dens, mode='update')
