@@ -55,7 +55,7 @@ SIGNATURES = {
     'drp_set_engine': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'drp_device_info': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t,
                                        ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_size_t)]),
-    'drp_load_weights': (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_size_t, ctypes.c_float]),
+    'drp_load_weights': (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_size_t, ctypes.c_double]),
     'drp_set_camera': (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_float, c_float_p]),
     'drp_set_goal': (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int, ctypes.c_int,
                                     c_float_p, ctypes.c_int]),

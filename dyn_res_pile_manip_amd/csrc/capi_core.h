@@ -99,7 +99,7 @@ int drp_device_info(drp_ctx* c, char* name, size_t name_len, int* n_cu, size_t* 
     return DRP_OK;
 }
 
-int drp_load_weights(drp_ctx* c, const float* blob, size_t n_floats, float adj_thresh) {
+int drp_load_weights(drp_ctx* c, const float* blob, size_t n_floats, double adj_thresh) {
     if (!c || !blob) return DRP_EINVAL;
     if (n_floats != (size_t)W_TOTAL)
         return fail(c, DRP_EINVAL, "weight blob has %zu floats, expected %d", n_floats, (int)W_TOTAL);
@@ -126,9 +126,9 @@ int drp_load_weights(drp_ctx* c, const float* blob, size_t n_floats, float adj_t
     CHK(guarded_wait(c, nullptr));
     c->w_host.assign(blob, blob + n_floats);
     c->adj_thresh = adj_thresh;
-    // threshold = adj_thresh * adj_thresh in Python doubles, then an fp32 scalar
-    // (model/gnn_dyn.py:229,236)
-    c->thr = (float)((double)adj_thresh * (double)adj_thresh);
+    // threshold = adj_thresh * adj_thresh in Python doubles, then an fp32 scalar (model/gnn_dyn.py:229,236): the radius
+    // arrives as the double it is there -- squaring its fp32 rounding gives another threshold at 0.05, 0.1, 0.7
+    c->thr = (float)(adj_thresh * adj_thresh);
     c->have_weights = true;
     return DRP_OK;
 }

@@ -209,7 +209,8 @@ struct drp_ctx {
 
     // model constants
     bool have_weights = false, have_cam = false, have_goal = false;
-    float adj_thresh = 0.08f, thr = 0.0064f;
+    double adj_thresh = 0.08;       // the radius as the caller gave it (a Python float): the threshold squares THIS value
+    float thr = 0.0064f;
     SplitRange re_range{};          // range shift 2^k of the split relation encoder and the bound it rests on
     float re_scale = 1.0f, re_inv = 1.0f;
     bool re_ok = true;

@@ -178,6 +178,12 @@ long drp_debug_fetch(drp_ctx* c, const char* name, void* out, size_t out_bytes) 
     // padded rows of drp_train_step_actions)
     else if (!strcmp(name, "train_states")) { b = &c->states; bytes = (size_t)c->marks.lastH * bn * 3 * 4; }
     else if (!strcmp(name, "train_sdelta")) { b = &c->tape_sdelta; bytes = (size_t)c->marks.lastH * bn * 3 * 4; }
+    // the last taped pass's neighbour lists of every step, step-major [H][B][N][10] / [H][B][N] (tests: the reversed lists of a
+    // training batch, whose rev_off / rev hold lastH sets [H][B][N+1] / [H][B][N*10]: "train_rev_off", "train_rev")
+    else if (!strcmp(name, "train_nbr_idx")) { b = &c->tape_idx; bytes = (size_t)c->marks.lastH * bn * DRP_K * 2; }
+    else if (!strcmp(name, "train_nbr_cnt")) { b = &c->tape_cnt; bytes = (size_t)c->marks.lastH * bn; }
+    else if (!strcmp(name, "train_rev_off")) { b = &c->rev_off; bytes = (size_t)c->marks.lastH * c->marks.lastB * (c->marks.lastN + 1) * 4; }
+    else if (!strcmp(name, "train_rev")) { b = &c->rev; bytes = (size_t)c->marks.lastH * bn * DRP_K * 4; }
     // the resolution regressor's post-activation taps of its last forward (NHWC [B][H][W][C] for the convolutions)
     else if (!strncmp(name, "rgr_c", 5) && name[5] >= '1' && name[5] <= '5' && !name[6]) {
         b = &c->rgr_a[name[5] - '1']; bytes = rgr_conv_out_floats(name[5] - '1', c->rgr_lastB) * 4;

@@ -1116,7 +1116,7 @@ int check_pushes(drp_ctx* c, const float* actions, int B, int H) {
 // fused one whatever drp_set_engine chose)
 int range_check(drp_ctx* c, int engine, float max_attr, float max_dens, float max_sdelta) {
     if (!engine_is_fused(engine) && engine != DRP_ENGINE_SPLIT) return DRP_OK;
-    const double A = max_attr, dm = max_dens / DRP_DENS_SCALE, D = (double)c->adj_thresh + 2.0 * max_sdelta;
+    const double A = max_attr, dm = max_dens / DRP_DENS_SCALE, D = c->adj_thresh + 2.0 * max_sdelta;
     const SplitRange& r = c->re_range;
     if (!c->re_ok)
         return fail(c, DRP_ERANGE, "weights outside the range of the split-fp16 relation encoder (largest |w| %g, activation "

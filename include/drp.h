@@ -85,8 +85,11 @@ int drp_device_info(drp_ctx* ctx, char* name, size_t name_len, int* n_cu, size_t
 /* PropNetDiffDenModel.load_state_dict (visualize_mpc.py:36-41): the 38 403 floats of
  * the state_dict, concatenated in its own key order, torch Linear
  * layout [out,in].  adj_thresh = config train.particle.adj_thresh
- * (model/gnn_dyn.py:206). */
-int drp_load_weights(drp_ctx* ctx, const float* blob, size_t n_floats, float adj_thresh);
+ * (model/gnn_dyn.py:206), as the double the config holds: the radius test compares
+ * against (float)(adj_thresh * adj_thresh), the product taken in doubles as Python takes
+ * it (model/gnn_dyn.py:229) -- squaring the radius's fp32 rounding instead moves the
+ * threshold by an ulp at 0.05, 0.1 and 0.7. */
+int drp_load_weights(drp_ctx* ctx, const float* blob, size_t n_floats, double adj_thresh);
 
 /* PlannerGD.world2cam (planners.py:192-209): m34 = first three rows of
  * inv(inv(cam_extrinsic) diag(1,-1,-1,1)) in fp32, global_scale from the config;

@@ -1,13 +1,19 @@
-"""Fuzz the three neighbour-list kernels against each other: plain sweep (k_graph), x strips (k_graph_strips),
-two-dimensional cells (k_graph_cells, forced for every size, random band height and first halo) -- random particle
-counts, batch sizes (so that the rounded-up grids of spread_item() have idle workgroups), pile shapes (uniform, blob,
-a line along x, a line along y, clusters of coincident particles, lattice = exact distance ties), scales and radii.
-Lists must agree bit for bit.   python tools/fuzz_graph.py [cases] [seed]"""
+"""Fuzz the three neighbour-list kernels against the host oracle (oracle/propnet_sparse.build_neighbours) and against each
+other: plain sweep (k_graph), x strips (k_graph_strips), two-dimensional cells (k_graph_cells, forced for every size, random
+band height and first halo) -- random particle counts, batch sizes (so that the rounded-up grids of spread_item() have idle
+workgroups), pile shapes (uniform, blob, a line along x, a line along y -- tests/_graph_edge_cases.py's --, clusters of
+coincident particles, lattice = exact distance ties), scales and radii (0.05 and 0.1 among them: the radii whose threshold
+differs when the fp32 rounding of the radius is squared).  Lists must agree bit for bit.  The suite's own edge cases (pairs an
+ulp from the radius, strip and band boundaries) are tests/test_gpu_graph_edges.py.   python tools/fuzz_graph.py [cases] [seed]"""
 import os, sys
 import numpy as np
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import _graph_edge_cases as edge_cases
 from dyn_res_pile_manip_amd import synthetic as syn, weights
 from dyn_res_pile_manip_amd.planners import world2cam_affine
+from oracle import propnet_sparse as osp
 
 
 def engine(env, radius):
@@ -22,16 +28,14 @@ def engine(env, radius):
 
 
 def pile(rng, N, kind):
+    if kind in ('xline', 'yline'):
+        return edge_cases.line_pile(rng, N, 0 if kind == 'xline' else 1)
     s = np.empty((N, 3), np.float64)
     if kind == 'uniform':
         s[:, :2] = rng.uniform(-0.2, 0.2, (N, 2))
     elif kind == 'blob':
         r = 0.12 * np.sqrt(rng.uniform(0, 1, N)); th = rng.uniform(0, 2 * np.pi, N)
         s[:, 0] = r * np.cos(th); s[:, 1] = r * np.sin(th)
-    elif kind == 'xline':
-        s[:, 0] = rng.uniform(-0.3, 0.3, N); s[:, 1] = rng.normal(0, 0.003, N)
-    elif kind == 'yline':
-        s[:, 1] = rng.uniform(-0.3, 0.3, N); s[:, 0] = rng.normal(0, 0.003, N)
     elif kind == 'dupes':
         c = rng.uniform(-0.2, 0.2, (max(N // 12, 1), 2))
         s[:, :2] = c[rng.integers(0, len(c), N)]
@@ -53,23 +57,22 @@ for c in range(cases):
     B = int(rng.integers(1, 12))
     kind = str(rng.choice(['uniform', 'blob', 'xline', 'yline', 'dupes', 'lattice']))
     scale = float(rng.choice([0.3, 1.0, 1.0, 2.5]))
-    radius = float(rng.choice([0.02, 0.08, 0.08, 0.3]))
+    radius = float(rng.choice([0.02, 0.05, 0.08, 0.08, 0.1, 0.3]))
     hb = float(rng.choice([0.02, 0.035, 0.05, 0.09, 0.2, 0.7]))
     halo = float(rng.choice([0.005, 0.02, 0.04, 0.1]))
     s = np.stack([pile(rng, N, kind) for _ in range(B)]).astype(np.float32)
     s[..., :2] *= scale
     sd = np.zeros_like(s) if kind in ('dupes', 'lattice') else (0.004 * rng.standard_normal(s.shape)).astype(np.float32)
-    ref = None
+    oidx, ocnt = osp.build_neighbours(s, sd, radius)
+    ref = (oidx.astype(np.int16), ocnt.astype(np.uint8))
     for name, env in (('plain', {'DRP_NO_GRAPH_STRIPS': '1'}), ('strips', {'DRP_NO_GRAPH_CELLS': '1'}),
                       ('cells', {'DRP_GRAPH_CELLS_MIN_N': '1', 'DRP_GRAPH_CELLS_HB': repr(hb), 'DRP_GRAPH_CELLS_HALO': repr(halo)})):
         e = engine(env, radius)
         idx, cnt = e.build_graph(s, sd)
         e.close()
-        if ref is None:
-            ref = (idx, cnt)
-        elif not (np.array_equal(idx, ref[0]) and np.array_equal(cnt, ref[1])):
+        if not (np.array_equal(idx, ref[0]) and np.array_equal(cnt, ref[1])):
             bad += 1
-            print('MISMATCH %s: case %d N=%d B=%d %s scale=%g radius=%g hb=%g halo=%g: %d rows differ' %
+            print('MISMATCH %s against the oracle: case %d N=%d B=%d %s scale=%g radius=%g hb=%g halo=%g: %d rows differ' %
                   (name, c, N, B, kind, scale, radius, hb, halo, int((idx != ref[0]).any(-1).sum())))
 print('%d cases, %d mismatches' % (cases, bad))
 sys.exit(1 if bad else 0)
