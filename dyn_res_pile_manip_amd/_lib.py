@@ -64,6 +64,11 @@ SIGNATURES = {
     'drp_set_goal_image': (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_int, ctypes.c_int, c_float_p, c_float_p,
                                           ctypes.POINTER(ctypes.c_int)]),
+    'drp_set_goal_scenes': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_float_p, ctypes.c_int, ctypes.c_int, c_float_p,
+                                           ctypes.POINTER(ctypes.c_int32), ctypes.c_int]),
+    'drp_set_goal_image_scenes': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_int, ctypes.c_int, c_float_p, c_float_p,
+                                                 ctypes.POINTER(ctypes.c_int32)]),
     'drp_gen_s_delta': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_int,
                                        ctypes.c_int, c_float_p]),
     'drp_build_graph': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_int,
@@ -77,6 +82,11 @@ SIGNATURES = {
                                    c_float_p]),
     'drp_reward': (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int, ctypes.c_int,
                                   ctypes.c_int, c_float_p]),
+    'drp_reward_scenes': (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_int, c_float_p]),
+    'drp_mpc_begin_scenes': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(MpcParams), ctypes.c_int, c_float_p,
+                                            c_float_p, c_float_p, c_double_p, ctypes.POINTER(ctypes.c_uint64)]),
+    'drp_mpc_stats_scenes': (ctypes.c_int, [ctypes.c_void_p, c_double_p]),
     'drp_mpc_begin': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(MpcParams), c_float_p,
                                      c_float_p, c_float_p, c_double_p]),
     'drp_mpc_sample': (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_uint64]),
@@ -122,6 +132,9 @@ SIGNATURES = {
                                     ctypes.POINTER(ctypes.c_int)]),
     'drp_gd_begin': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.c_int, ctypes.c_int,
                                     c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_float_p, c_float_p]),
+    'drp_gd_begin_scenes': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_float_p, c_float_p, c_float_p, ctypes.c_int,
+                                           ctypes.c_int, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_float_p,
+                                           c_float_p]),
     'drp_gd_grad': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p]),
     'drp_gd_step': (ctypes.c_int, [ctypes.c_void_p, c_float_p]),
     'drp_gd_get': (ctypes.c_int, [ctypes.c_void_p, c_float_p]),
@@ -188,6 +201,7 @@ _lib = None
 
 
 DRP_ERANGE = -6
+MAX_SCENES = 64             # DRP_MAX_SCENES
 
 
 class DrpError(RuntimeError):

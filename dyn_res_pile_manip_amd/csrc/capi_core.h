@@ -36,6 +36,7 @@ int drp_create(int device, drp_ctx** out) {
         hipFuncSetAttribute((const void*)k_graph_strips_q<GRAPH_THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
         hipFuncSetAttribute((const void*)k_graph_strips_q<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
         hipFuncSetAttribute((const void*)kb_reward, hipFuncAttributeMaxDynamicSharedMemorySize, (int)KB_REWARD_LDS(4096)) != hipSuccess ||
+        hipFuncSetAttribute((const void*)kb_reward_scenes, hipFuncAttributeMaxDynamicSharedMemorySize, (int)KB_REWARD_LDS(4096)) != hipSuccess ||
         hipFuncSetAttribute((const void*)kb_reverse_lists<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)KB_REV_LDS(KB_REV_LDS_MAX_N, 1)) != hipSuccess ||
         hipFuncSetAttribute((const void*)kb_reverse_lists<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)KB_REV_LDS(KB_REV_LDS_MAX_N, 1)) != hipSuccess ||
         hipFuncSetAttribute((const void*)k_aggregate_lds, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -153,6 +154,28 @@ int drp_set_goal(drp_ctx* c, const float* field, int h, int w, const float* goal
     return DRP_OK;
 }
 
+// A new table ends the sessions that read the old one (their kernels take the table's shape at every launch).
+static void end_scene_sessions(drp_ctx* c) {
+    if (c->mpc_on && c->mpc_S > 0) { c->mpc_on = false; c->mpc_pending[0] = c->mpc_pending[1] = false; }
+    if (c->gd_on && c->gd_S > 0) { c->gd_on = false; for (int q = 0; q < DRP_GD_SLOTS; ++q) c->gd_pending[q] = false; }
+}
+
+int drp_set_goal_scenes(drp_ctx* c, int S, const float* fields, int h, int w, const float* goal_coor, const int32_t* m, int m_max) {
+    if (!c || !fields || !goal_coor || !m || h <= 0 || w <= 0 || m_max <= 0) return fail(c, DRP_EINVAL, "bad goal table");
+    if (S < 1 || S > DRP_MAX_SCENES) return fail(c, DRP_EINVAL, "%d scenes outside 1..%d", S, DRP_MAX_SCENES);
+    for (int k = 0; k < S; ++k)
+        if (m[k] < 1 || m[k] > m_max) return fail(c, DRP_EINVAL, "scene %d has %d goal pixels, outside 1..m_max=%d", k, (int)m[k], m_max);
+    HIPCHK(c, hipSetDevice(c->device));
+    end_scene_sessions(c);
+    c->gt_S = 0;
+    CHK(h2d(c, c->gt_fields, fields, (size_t)S * h * w * sizeof(float)));
+    CHK(h2d(c, c->gt_coor, goal_coor, (size_t)S * m_max * 2 * sizeof(float)));
+    CHK(h2d(c, c->gt_m, m, (size_t)S * sizeof(int32_t)));
+    CHK(guarded_wait(c, nullptr));
+    c->gt_S = S; c->gt_h = h; c->gt_w = w; c->gt_m_max = m_max;
+    return DRP_OK;
+}
+
 int drp_gen_s_delta(drp_ctx* c, const float* s_cur, const float* action, int B, int N, float* out) {
     CHK(need(c, false, true, false));
     CHK(check_bn(c, B, N));
@@ -265,6 +288,22 @@ int drp_reward(drp_ctx* c, const float* state, int Bp, int N, int normalize, flo
     CHK(h2d(c, c->ws.s_out, state, (size_t)Bp * N * 3 * sizeof(float)));
     CHK(ensure(c, c->scratch, (size_t)Bp * sizeof(float)));
     CHK(run_reward(c, ptr<float>(c->ws.s_out), (size_t)N * 3, Bp, N, normalize, ptr<float>(c->scratch)));
+    CHK(d2h(c, reward_out, c->scratch.p, (size_t)Bp * sizeof(float)));
+    return drp_sync(c);
+}
+
+int drp_reward_scenes(drp_ctx* c, const float* state, const int32_t* scene, int Bp, int N, int normalize, float* reward_out) {
+    CHK(need(c, false, true, false));
+    if (c->gt_S <= 0) return fail(c, DRP_ESTATE, "no goal table installed (drp_set_goal_scenes)");
+    CHK(check_bn(c, Bp, N));
+    if (!state || !scene || !reward_out) return fail(c, DRP_EINVAL, "null buffer");
+    for (int r = 0; r < Bp; ++r)
+        if (scene[r] < 0 || scene[r] >= c->gt_S) return fail(c, DRP_EINVAL, "row %d names scene %d, outside the table's 0..%d", r, (int)scene[r], c->gt_S - 1);
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(h2d(c, c->ws.s_out, state, (size_t)Bp * N * 3 * sizeof(float)));
+    CHK(h2d(c, c->gt_rows, scene, (size_t)Bp * sizeof(int32_t)));
+    CHK(ensure(c, c->scratch, (size_t)Bp * sizeof(float)));
+    CHK(run_reward(c, ptr<float>(c->ws.s_out), (size_t)N * 3, Bp, N, normalize, ptr<float>(c->scratch), c->gt_S, 1, 1, ptr<int>(c->gt_rows)));
     CHK(d2h(c, reward_out, c->scratch.p, (size_t)Bp * sizeof(float)));
     return drp_sync(c);
 }

@@ -220,6 +220,10 @@ struct drp_ctx {
     DevBuf goal_field, goal_coor, cself;
     unsigned cself_tag = 0;         // bumped by every prepare_cself: who filled c->cself last
     int goal_h = 0, goal_w = 0, goal_m = 0;
+    // the goal table of multi-scene sessions (drp_set_goal_scenes / drp_set_goal_image_scenes): gt_S goals of one image size,
+    // fields [S][h][w], pixels [S][m_max][2] with counts gt_m [S]; gt_S = 0: none installed.  The single goal above is another thing.
+    DevBuf gt_fields, gt_coor, gt_m, gt_rows, scene_seeds;
+    int gt_S = 0, gt_h = 0, gt_w = 0, gt_m_max = 0;
 
     // workspaces: a step's engine and buffers are run_step's arguments (StepArgs); `ws` is what the selected engine's calls pass
     StepWs ws;
@@ -233,6 +237,7 @@ struct drp_ctx {
     const uint8_t* mpc_cself_ok = nullptr;
     float sess_attr_max = 0.0f, sess_dens_max = 0.0f;   // of the running MPC session (range check of later uploads)
     drp_mpc_params mpc{};
+    int mpc_S = 0;                  // scenes of the running session (drp_mpc_begin_scenes); 0: a single-scene session on the single goal
     DevBuf nominal, noise, partials, gathered, stats, elite, elite_all, xchg;
     int n_ranks = 1, rank = 0;
     ncclComm_t comm = nullptr;
@@ -245,6 +250,7 @@ struct drp_ctx {
     int gd_engine = DRP_ENGINE_FUSED;        // which engine writes the session's tape (pick_tape_engine)
     bool gd_on = false;
     int gd_nb = 0, gd_N = 0, gd_B = 0, gd_H = 0, gd_iter = 0;
+    int gd_S = 0, gd_scene_nb = 0;           // drp_gd_begin_scenes: scenes and columns per scene (gd_nb = gd_S * gd_scene_nb); 0: the single goal
     PinBuf gd_pin[DRP_GD_SLOTS];             // drp_gd_step_async: pinned host copies [B rewards | B*H*4 pushes] of the iterations in flight,
     Event gd_ev[DRP_GD_SLOTS];               //   written by the iteration's own kernels (kb_reward, k_adam): no copy on the stream
     bool gd_pending[DRP_GD_SLOTS] = {};

@@ -51,9 +51,15 @@ int gd_forward_backward(drp_ctx* c, const GdPass& pass) {
     {
         ProbeScope ps(c, KC_BWD_REWARD);
         c->dv(DV_BWD_REWARD);
-        hipLaunchKernelGGL(kb_reward, dim3(B), dim3(256), KB_REWARD_LDS(N), st, states + (size_t)(H - 1) * N * 3, hstride,
-                           N, ptr<float>(c->goal_field), c->goal_h, c->goal_w, ptr<float>(c->goal_coor), c->goal_m, c->cam,
-                           1, g_state + (size_t)(H - 1) * bn * 3, (size_t)N * 3, ptr<float>(c->rewards), pass.host_rewards);
+        if (c->gd_S > 0) {          // a goal per row: row r belongs to scene (r / gd_scene_nb) % gd_S (drp_gd_begin_scenes)
+            hipLaunchKernelGGL(kb_reward_scenes, dim3(B), dim3(256), KB_REWARD_LDS(N), st, states + (size_t)(H - 1) * N * 3, hstride,
+                               N, goal_table(c, c->gd_scene_nb, 1), c->gt_h, c->gt_w, c->cam,
+                               1, g_state + (size_t)(H - 1) * bn * 3, (size_t)N * 3, ptr<float>(c->rewards), pass.host_rewards);
+        } else {
+            hipLaunchKernelGGL(kb_reward, dim3(B), dim3(256), KB_REWARD_LDS(N), st, states + (size_t)(H - 1) * N * 3, hstride,
+                               N, ptr<float>(c->goal_field), c->goal_h, c->goal_w, ptr<float>(c->goal_coor), c->goal_m, c->cam,
+                               1, g_state + (size_t)(H - 1) * bn * 3, (size_t)N * 3, ptr<float>(c->rewards), pass.host_rewards);
+        }
     }
     for (int t = H - 1; t >= 0; --t) {
         const float* s_prev = (t == 0) ? ptr<float>(c->ws.s_in) : states + (size_t)(t - 1) * N * 3;
@@ -118,13 +124,13 @@ int gd_forward_backward(drp_ctx* c, const GdPass& pass) {
 }
 }  // namespace
 
-int drp_gd_begin(drp_ctx* c, const float* s0, const float* attr, const float* dens, int nb, int N,
-                 const float* actions, int B, int H, double lr, const float act_lo[4], const float act_hi[4]) {
-    CHK(need(c, true, true, true));
+// S = 0: drp_gd_begin (the single goal).  S >= 1: drp_gd_begin_scenes -- nb is then S * (columns per scene)
+static int gd_begin_common(drp_ctx* c, int S, const float* s0, const float* attr, const float* dens, int nb, int N,
+                           const float* actions, int B, int H, double lr, const float act_lo[4], const float act_hi[4]) {
     CHK(check_bn(c, B, N));
     if (!s0 || !attr || !dens || !actions || !act_lo || !act_hi) return fail(c, DRP_EINVAL, "null argument");
     if (H < 1 || H > 64) return fail(c, DRP_EINVAL, "bad horizon H=%d", H);
-    if (nb <= 0 || B % nb != 0) return fail(c, DRP_EINVAL, "B must be a multiple of n_batch");
+    if (nb <= 0 || B % nb != 0) return fail(c, DRP_EINVAL, S > 0 ? "B must be a multiple of S * n_batch" : "B must be a multiple of n_batch");
     HIPCHK(c, hipSetDevice(c->device));
     {
         // Adam moves the pushes, the clip keeps them in the box: bound by the box's diagonals and by the initial pushes
@@ -151,6 +157,7 @@ int drp_gd_begin(drp_ctx* c, const float* s0, const float* attr, const float* de
     HIPCHK(c, hipMemsetAsync(c->adam_m.p, 0, (size_t)B * H * 4 * sizeof(float), c->stream));
     HIPCHK(c, hipMemsetAsync(c->adam_v.p, 0, (size_t)B * H * 4 * sizeof(float), c->stream));
     CHK(guarded_wait(c, nullptr));
+    c->gd_S = S; c->gd_scene_nb = S > 0 ? nb / S : 0;
     c->gd_nb = nb; c->gd_N = N; c->gd_B = B; c->gd_H = H; c->gd_iter = 0; c->gd_lr = lr;
     for (int q = 0; q < DRP_GD_SLOTS; ++q) c->gd_pending[q] = false;           // a new problem drops what the last one left in flight
     c->gd_cself_tag = 0;
@@ -160,6 +167,22 @@ int drp_gd_begin(drp_ctx* c, const float* s0, const float* attr, const float* de
     c->gd_on = true;
     c->mpc_on = false;
     return DRP_OK;
+}
+
+int drp_gd_begin(drp_ctx* c, const float* s0, const float* attr, const float* dens, int nb, int N,
+                 const float* actions, int B, int H, double lr, const float act_lo[4], const float act_hi[4]) {
+    CHK(need(c, true, true, true));
+    return gd_begin_common(c, 0, s0, attr, dens, nb, N, actions, B, H, lr, act_lo, act_hi);
+}
+
+int drp_gd_begin_scenes(drp_ctx* c, int S, const float* s0, const float* attr, const float* dens, int nb, int N,
+                        const float* actions, int B, int H, double lr, const float act_lo[4], const float act_hi[4]) {
+    CHK(need(c, true, true, false));
+    if (S < 1 || S > DRP_MAX_SCENES) return fail(c, DRP_EINVAL, "%d scenes outside 1..%d", S, DRP_MAX_SCENES);
+    if (c->gt_S <= 0) return fail(c, DRP_ESTATE, "no goal table installed (drp_set_goal_scenes)");
+    if (c->gt_S != S) return fail(c, DRP_EINVAL, "a session of %d scenes on a goal table of %d", S, c->gt_S);
+    if (nb <= 0 || nb > 0x7fffffff / S) return fail(c, DRP_EINVAL, "bad n_batch %d", nb);
+    return gd_begin_common(c, S, s0, attr, dens, S * nb, N, actions, B, H, lr, act_lo, act_hi);
 }
 
 int drp_gd_grad(drp_ctx* c, float* rewards_out, float* grad_act_out, float* grad_state_out) {

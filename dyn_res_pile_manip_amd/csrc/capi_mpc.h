@@ -2,15 +2,20 @@
 // Here: the device-resident sampling planner (drp_mpc_*: sampler, rollout, softmax and elite updates, the one RCCL all-gather) and drp_fps.
 
 // ---- sampling MPC -------------------------------------------------------------------------
-int drp_mpc_begin(drp_ctx* c, const drp_mpc_params* p, const float* s0, const float* attr,
-                  const float* dens, const double* nominal) {
-    CHK(need(c, true, true, true));
-    if (!p || !s0 || !attr || !dens || !nominal) return fail(c, DRP_EINVAL, "null argument");
+// S = 0: drp_mpc_begin (one scene, the single goal).  S >= 1: drp_mpc_begin_scenes -- S * nb start columns, S nominal
+// sequences, S keys; row = (sample * S + scene) * nb + column, so the rollout sees a plain session of S * nb columns.
+static inline int mpc_scenes(const drp_ctx* c) { return c->mpc_S > 0 ? c->mpc_S : 1; }
+static inline int mpc_rows(const drp_ctx* c) { return c->mpc.n_sample * mpc_scenes(c) * c->mpc.n_batch; }
+
+static int mpc_begin_common(drp_ctx* c, const drp_mpc_params* p, int S, const float* s0, const float* attr,
+                            const float* dens, const double* nominal, const uint64_t* seeds) {
+    const int Sn = S > 0 ? S : 1;
     if (p->n_batch <= 0 || p->n_sample <= 0 || p->n_look_ahead <= 0 || p->n_look_ahead > 64)
         return fail(c, DRP_EINVAL, "bad mpc shape");
     if (p->noise_type < DRP_NOISE_NORMAL || p->noise_type > DRP_NOISE_TOTAL_RAND)
         return fail(c, DRP_EINVAL, "bad noise_type %d", p->noise_type);
-    const int nb = p->n_batch, N = p->n_particles, H = p->n_look_ahead, B = p->n_sample * nb;
+    if ((long long)p->n_sample * Sn * p->n_batch > 0x7fffffffLL) return fail(c, DRP_EINVAL, "bad mpc shape");
+    const int nb = p->n_batch * Sn, N = p->n_particles, H = p->n_look_ahead, B = p->n_sample * nb;
     CHK(check_bn(c, B, N));
     HIPCHK(c, hipSetDevice(c->device));
     {
@@ -22,14 +27,17 @@ int drp_mpc_begin(drp_ctx* c, const drp_mpc_params* p, const float* s0, const fl
         CHK(range_check(c, c->engine, c->sess_attr_max, c->sess_dens_max, push_len_bound(c, box, 2)));
     }
     c->mpc = *p;
+    c->mpc_S = S;
+    c->mpc_on = false;              // until everything below has gone through
+    if (seeds) CHK(h2d(c, c->scene_seeds, seeds, (size_t)Sn * sizeof(uint64_t)));
     CHK(h2d(c, c->ws.s_in, s0, (size_t)nb * N * 3 * sizeof(float)));
     CHK(h2d(c, c->ws.attr, attr, (size_t)nb * N * sizeof(float)));
     CHK(h2d(c, c->ws.dens, dens, (size_t)nb * sizeof(float)));
-    CHK(h2d(c, c->nominal, nominal, (size_t)H * 4 * sizeof(double)));
+    CHK(h2d(c, c->nominal, nominal, (size_t)Sn * H * 4 * sizeof(double)));
     CHK(ensure(c, c->actions, (size_t)B * H * 4 * sizeof(float)));
-    CHK(ensure(c, c->partials, (size_t)(6 + 4 * H) * sizeof(double)));
+    CHK(ensure(c, c->partials, (size_t)Sn * (6 + 4 * H) * sizeof(double)));
     CHK(ensure(c, c->gathered, (size_t)(6 + 4 * H) * sizeof(double) * (size_t)(c->n_ranks > 0 ? c->n_ranks : 1)));
-    CHK(ensure(c, c->stats, 8 * sizeof(double)));
+    CHK(ensure(c, c->stats, (size_t)Sn * 8 * sizeof(double)));
     CHK(ensure_step_ws(c, c->ws, B, N));
     CHK(ensure(c, c->states, (size_t)B * H * N * 3 * sizeof(float)));
     CHK(ensure(c, c->rewards, (size_t)B * H * sizeof(float)));
@@ -42,21 +50,46 @@ int drp_mpc_begin(drp_ctx* c, const drp_mpc_params* p, const float* s0, const fl
     return DRP_OK;
 }
 
+int drp_mpc_begin(drp_ctx* c, const drp_mpc_params* p, const float* s0, const float* attr,
+                  const float* dens, const double* nominal) {
+    CHK(need(c, true, true, true));
+    if (!p || !s0 || !attr || !dens || !nominal) return fail(c, DRP_EINVAL, "null argument");
+    return mpc_begin_common(c, p, 0, s0, attr, dens, nominal, nullptr);
+}
+
+int drp_mpc_begin_scenes(drp_ctx* c, const drp_mpc_params* p, int S, const float* s0, const float* attr,
+                         const float* dens, const double* nominal, const uint64_t* seeds) {
+    CHK(need(c, true, true, false));
+    if (!p || !s0 || !attr || !dens || !nominal || !seeds) return fail(c, DRP_EINVAL, "null argument");
+    if (S < 1 || S > DRP_MAX_SCENES) return fail(c, DRP_EINVAL, "%d scenes outside 1..%d", S, DRP_MAX_SCENES);
+    if (c->gt_S <= 0) return fail(c, DRP_ESTATE, "no goal table installed (drp_set_goal_scenes)");
+    if (c->gt_S != S) return fail(c, DRP_EINVAL, "a session of %d scenes on a goal table of %d", S, c->gt_S);
+    return mpc_begin_common(c, p, S, s0, attr, dens, nominal, seeds);
+}
+
+// what a multi-scene session cannot do: the host-transport and sharding forms
+static int no_scene_sharding(drp_ctx* c, const char* what) {
+    if (c->mpc_S > 1) return fail(c, DRP_ESTATE, "%s: a session of %d scenes cannot be sharded (one context plans all its samples)", what, c->mpc_S);
+    return DRP_OK;
+}
+static bool mpc_gathers(const drp_ctx* c) { return c->comm && (c->n_ranks > 1 || (c->comm_always && c->mpc_S <= 1)); }
+
 int drp_mpc_sample(drp_ctx* c, const float* noise, uint64_t iteration) {
     if (!c || !c->mpc_on) return fail(c, DRP_ESTATE, "drp_mpc_begin not called");
     HIPCHK(c, hipSetDevice(c->device));
     const drp_mpc_params& p = c->mpc;
     const float* dnoise = nullptr;
     if (noise) {
-        CHK(h2d(c, c->noise, noise, (size_t)p.n_sample * p.n_look_ahead * 4 * sizeof(float)));
+        CHK(h2d(c, c->noise, noise, (size_t)mpc_scenes(c) * p.n_sample * p.n_look_ahead * 4 * sizeof(float)));
         dnoise = ptr<float>(c->noise);
     }
     ProbeScope ps(c, KC_MPPI);
-    hipLaunchKernelGGL(k_mppi_sample, dim3((4 * p.n_sample + 255) / 256), dim3(256), 0, c->stream,
+    hipLaunchKernelGGL(k_mppi_sample, dim3((4 * p.n_sample + 255) / 256, mpc_scenes(c)), dim3(256), 0, c->stream,
                        ptr<double>(c->nominal), dnoise, p.n_sample, p.n_batch, p.n_look_ahead, p.sigma,
                        p.beta_filter, make_float4(p.act_lo[0], p.act_lo[1], p.act_lo[2], p.act_lo[3]),
                        make_float4(p.act_hi[0], p.act_hi[1], p.act_hi[2], p.act_hi[3]), p.seed,
-                       p.sample_offset, iteration, p.noise_type, ptr<float>(c->actions));
+                       p.sample_offset, iteration, p.noise_type, ptr<float>(c->actions),
+                       c->mpc_S > 0 ? ptr<uint64_t>(c->scene_seeds) : (const uint64_t*)nullptr);
     HIPCHK(c, hipGetLastError());
     return DRP_OK;
 }
@@ -67,8 +100,8 @@ int drp_mpc_set_actions(drp_ctx* c, const float* actions) {
     if (!actions) return fail(c, DRP_EINVAL, "null actions");
     const drp_mpc_params& p = c->mpc;
     CHK(range_check(c, c->engine, c->sess_attr_max, c->sess_dens_max,
-                    push_len_bound(c, actions, (size_t)p.n_sample * p.n_batch * p.n_look_ahead)));
-    CHK(h2d(c, c->actions, actions, (size_t)p.n_sample * p.n_batch * p.n_look_ahead * 4 * sizeof(float)));
+                    push_len_bound(c, actions, (size_t)mpc_rows(c) * p.n_look_ahead)));
+    CHK(h2d(c, c->actions, actions, (size_t)mpc_rows(c) * p.n_look_ahead * 4 * sizeof(float)));
     return DRP_OK;
 }
 
@@ -76,23 +109,24 @@ int drp_mpc_rollout(drp_ctx* c, int reward_all_steps) {
     if (!c || !c->mpc_on) return fail(c, DRP_ESTATE, "drp_mpc_begin not called");
     HIPCHK(c, hipSetDevice(c->device));
     const drp_mpc_params& p = c->mpc;
-    return run_rollout(c, p.n_batch, p.n_particles, p.n_sample * p.n_batch, p.n_look_ahead,
-                       reward_all_steps != 0, reward_all_steps == 0, true);
+    return run_rollout(c, p.n_batch * mpc_scenes(c), p.n_particles, mpc_rows(c), p.n_look_ahead,
+                       reward_all_steps != 0, reward_all_steps == 0, true, c->mpc_S, p.n_batch);
 }
 
-static int launch_partials(drp_ctx* c, double* out) {
+static int launch_partials(drp_ctx* c, double* out, int scene_stride = 0) {
     const drp_mpc_params& p = c->mpc;
     const int H = p.n_look_ahead;
     ProbeScope ps(c, KC_MPPI);
-    hipLaunchKernelGGL(k_mppi_partials, dim3(4 * H + 1), dim3(256), 0, c->stream,
+    hipLaunchKernelGGL(k_mppi_partials, dim3(4 * H + 1, mpc_scenes(c)), dim3(256), 0, c->stream,
                        ptr<float>(c->rewards) + (H - 1), H, ptr<float>(c->actions), p.n_sample, p.n_batch,
-                       H, p.reward_weight, p.sample_offset, out);
+                       H, p.reward_weight, p.sample_offset, out, scene_stride > 0 ? scene_stride : 6 + 4 * H);
     HIPCHK(c, hipGetLastError());
     return DRP_OK;
 }
 
 int drp_mpc_partials(drp_ctx* c, double* out) {
     if (!c || !c->mpc_on) return fail(c, DRP_ESTATE, "drp_mpc_begin not called");
+    CHK(no_scene_sharding(c, "drp_mpc_partials"));
     HIPCHK(c, hipSetDevice(c->device));
     CHK(launch_partials(c, ptr<double>(c->partials)));
     if (out) {
@@ -102,19 +136,20 @@ int drp_mpc_partials(drp_ctx* c, double* out) {
     return DRP_OK;
 }
 
-static int launch_update(drp_ctx* c, const double* dev_partials, int n_ranks, int rank_stride = 0) {
+static int launch_update(drp_ctx* c, const double* dev_partials, int n_ranks, int rank_stride = 0, int scene_stride = 0) {
     const drp_mpc_params& p = c->mpc;
     ProbeScope ps(c, KC_MPPI);
     c->dv(DV_MPPI_SOFTMAX);
-    hipLaunchKernelGGL(k_mppi_update, dim3(1), dim3(128), 0, c->stream, dev_partials, n_ranks,
+    hipLaunchKernelGGL(k_mppi_update, dim3(1, mpc_scenes(c)), dim3(128), 0, c->stream, dev_partials, n_ranks,
                        rank_stride > 0 ? rank_stride : 6 + 4 * p.n_look_ahead, p.n_look_ahead, (double)p.n_sample * (double)n_ranks, ptr<double>(c->nominal),
-                       ptr<double>(c->stats));
+                       ptr<double>(c->stats), scene_stride > 0 ? scene_stride : 6 + 4 * p.n_look_ahead);
     HIPCHK(c, hipGetLastError());
     return DRP_OK;
 }
 
 int drp_mpc_update(drp_ctx* c, const double* partials, int n_ranks, double* nominal_out) {
     if (!c || !c->mpc_on) return fail(c, DRP_ESTATE, "drp_mpc_begin not called");
+    CHK(no_scene_sharding(c, "drp_mpc_update"));
     HIPCHK(c, hipSetDevice(c->device));
     if (!partials || n_ranks <= 0) return fail(c, DRP_EINVAL, "bad partials");
     const size_t rec = (size_t)(6 + 4 * c->mpc.n_look_ahead) * sizeof(double);
@@ -131,9 +166,10 @@ int drp_mpc_update_device(drp_ctx* c) {
     if (!c || !c->mpc_on) return fail(c, DRP_ESTATE, "drp_mpc_begin not called");
     HIPCHK(c, hipSetDevice(c->device));
     if (c->comm_failed) return comm_failed_error(c);
+    if (c->comm && c->n_ranks > 1) CHK(no_scene_sharding(c, "drp_mpc_update_device with a communicator of several ranks"));
     CHK(launch_partials(c, ptr<double>(c->partials)));
     const int rec = 6 + 4 * c->mpc.n_look_ahead;
-    if (c->comm && (c->n_ranks > 1 || c->comm_always)) {
+    if (mpc_gathers(c)) {
         CHK(ensure(c, c->gathered, (size_t)rec * sizeof(double) * c->n_ranks));
         RcclApi* R = rccl_api();
         ncclResult_t r = R->AllGather(c->partials.p, c->gathered.p, rec, ncclDouble, c->comm, c->stream);
@@ -154,7 +190,7 @@ static int elite_check(drp_ctx* c, int k) {
 
 static int pow2_at_least(int n) { int p = 1; while (p < n) p <<= 1; return p; }
 
-static int launch_elite_local(drp_ctx* c, int k, double* out) {
+static int launch_elite_local(drp_ctx* c, int k, double* out, int scene_stride = 0) {
     const drp_mpc_params& p = c->mpc;
     const int H = p.n_look_ahead;
     // sort path while keys + indices + positions of 2^m >= n_sample entries fit in LDS; k dependent rounds otherwise
@@ -163,13 +199,13 @@ static int launch_elite_local(drp_ctx* c, int k, double* out) {
     if (lds > 150 * 1024 || k > n2) { n2 = 0; lds = (size_t)p.n_sample * 16 + (size_t)k * 4; }
     ProbeScope ps(c, KC_MPPI);
     c->dv(n2 ? DV_ELITE_SORT : DV_ELITE_ROUNDS);
-    hipLaunchKernelGGL(k_elite_local, dim3(1), dim3(256), lds, c->stream, ptr<float>(c->rewards) + (H - 1), H,
-                       ptr<float>(c->actions), p.n_sample, p.n_batch, H, k, p.sample_offset, n2, out);
+    hipLaunchKernelGGL(k_elite_local, dim3(1, mpc_scenes(c)), dim3(256), lds, c->stream, ptr<float>(c->rewards) + (H - 1), H,
+                       ptr<float>(c->actions), p.n_sample, p.n_batch, H, k, p.sample_offset, n2, out, scene_stride);
     HIPCHK(c, hipGetLastError());
     return DRP_OK;
 }
 
-static int launch_elite_update(drp_ctx* c, const double* dev_records, int n_ranks, int k, int rank_stride = 0) {
+static int launch_elite_update(drp_ctx* c, const double* dev_records, int n_ranks, int k, int rank_stride = 0, int scene_stride = 0) {
     const int HJ = 4 * c->mpc.n_look_ahead, total = n_ranks * k;
     if (rank_stride <= 0) rank_stride = k * (2 + HJ);
     int n2 = pow2_at_least(total);
@@ -182,14 +218,15 @@ static int launch_elite_update(drp_ctx* c, const double* dev_records, int n_rank
         if (lds > 150 * 1024) return fail(c, DRP_EINVAL, "too many elite records (%d ranks x %d, horizon %d)", n_ranks, k, c->mpc.n_look_ahead);
     }
     ProbeScope ps(c, KC_MPPI);
-    hipLaunchKernelGGL(k_elite_update, dim3(1), dim3(256), lds, c->stream, dev_records, n_ranks, rank_stride, k, c->mpc.n_look_ahead, n2,
-                       ptr<double>(c->nominal), ptr<double>(c->stats) + 6);
+    hipLaunchKernelGGL(k_elite_update, dim3(1, mpc_scenes(c)), dim3(256), lds, c->stream, dev_records, n_ranks, rank_stride, k, c->mpc.n_look_ahead, n2,
+                       ptr<double>(c->nominal), ptr<double>(c->stats) + 6, scene_stride);
     HIPCHK(c, hipGetLastError());
     return DRP_OK;
 }
 
 int drp_mpc_elite(drp_ctx* c, int k, double* out) {
     CHK(elite_check(c, k));
+    CHK(no_scene_sharding(c, "drp_mpc_elite"));
     HIPCHK(c, hipSetDevice(c->device));
     CHK(ensure(c, c->elite, (size_t)k * (2 + 4 * c->mpc.n_look_ahead) * sizeof(double)));
     CHK(launch_elite_local(c, k, ptr<double>(c->elite)));
@@ -202,6 +239,7 @@ int drp_mpc_elite(drp_ctx* c, int k, double* out) {
 
 int drp_mpc_update_elite(drp_ctx* c, const double* records, int n_ranks, int k, double* nominal_out) {
     CHK(elite_check(c, k));
+    CHK(no_scene_sharding(c, "drp_mpc_update_elite"));
     HIPCHK(c, hipSetDevice(c->device));
     if (!records || n_ranks <= 0) return fail(c, DRP_EINVAL, "bad elite records");
     const size_t bytes = (size_t)n_ranks * k * (2 + 4 * c->mpc.n_look_ahead) * sizeof(double);
@@ -223,14 +261,16 @@ int drp_mpc_update_elite_device(drp_ctx* c, int k) {
     // two combine kernels (the softmax combine supplies mean / std / max / argmax; its nominal is then replaced
     // by the elite mean).
     if (c->comm_failed) return comm_failed_error(c);
+    if (c->comm && c->n_ranks > 1) CHK(no_scene_sharding(c, "drp_mpc_update_elite_device with a communicator of several ranks"));
+    // (a multi-scene session: one such message per scene, side by side, combined per scene)
     const int H = c->mpc.n_look_ahead, rec_s = 6 + 4 * H, rec_e = k * (2 + 4 * H), msg = rec_s + rec_e;
-    CHK(ensure(c, c->elite, (size_t)msg * sizeof(double)));
+    CHK(ensure(c, c->elite, (size_t)mpc_scenes(c) * msg * sizeof(double)));
     double* mine = ptr<double>(c->elite);
-    CHK(launch_partials(c, mine));
-    CHK(launch_elite_local(c, k, mine + rec_s));
+    CHK(launch_partials(c, mine, msg));
+    CHK(launch_elite_local(c, k, mine + rec_s, msg));
     const double* all = mine;
     int n_ranks = 1;
-    if (c->comm && (c->n_ranks > 1 || c->comm_always)) {
+    if (mpc_gathers(c)) {
         CHK(ensure(c, c->elite_all, (size_t)msg * sizeof(double) * c->n_ranks));
         RcclApi* R = rccl_api();
         ncclResult_t r = R->AllGather(c->elite.p, c->elite_all.p, msg, ncclDouble, c->comm, c->stream);
@@ -238,8 +278,8 @@ int drp_mpc_update_elite_device(drp_ctx* c, int k) {
         all = ptr<double>(c->elite_all);
         n_ranks = c->n_ranks;
     }
-    CHK(launch_update(c, all, n_ranks, msg));
-    return launch_elite_update(c, all + rec_s, n_ranks, k, msg);
+    CHK(launch_update(c, all, n_ranks, msg, msg));
+    return launch_elite_update(c, all + rec_s, n_ranks, k, msg, msg);
 }
 
 int drp_mpc_get(drp_ctx* c, float* actions, float* rewards, float* rewards_all, float* states,
@@ -247,14 +287,23 @@ int drp_mpc_get(drp_ctx* c, float* actions, float* rewards, float* rewards_all, 
     if (!c || !c->mpc_on) return fail(c, DRP_ESTATE, "drp_mpc_begin not called");
     HIPCHK(c, hipSetDevice(c->device));
     const drp_mpc_params& p = c->mpc;
-    const int H = p.n_look_ahead, B = p.n_sample * p.n_batch, N = p.n_particles;
+    const int H = p.n_look_ahead, B = mpc_rows(c), N = p.n_particles;
     if (actions) CHK(d2h(c, actions, c->actions.p, (size_t)B * H * 4 * sizeof(float)));
     if (rewards)
         HIPCHK(c, hipMemcpy2DAsync(rewards, sizeof(float), ptr<float>(c->rewards) + (H - 1),
                                    H * sizeof(float), sizeof(float), B, hipMemcpyDeviceToHost, c->stream));
     if (rewards_all) CHK(d2h(c, rewards_all, c->rewards.p, (size_t)B * H * sizeof(float)));
     if (states) CHK(d2h(c, states, c->states.p, (size_t)B * H * N * 3 * sizeof(float)));
-    if (nominal) CHK(d2h(c, nominal, c->nominal.p, (size_t)H * 4 * sizeof(double)));
+    if (nominal) CHK(d2h(c, nominal, c->nominal.p, (size_t)mpc_scenes(c) * H * 4 * sizeof(double)));
+    return drp_sync(c);
+}
+
+int drp_mpc_stats_scenes(drp_ctx* c, double* stats_out) {
+    if (!c || !c->mpc_on) return fail(c, DRP_ESTATE, "drp_mpc_begin not called");
+    if (!stats_out) return fail(c, DRP_EINVAL, "null buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpy2DAsync(stats_out, 6 * sizeof(double), c->stats.p, 8 * sizeof(double), 6 * sizeof(double), (size_t)mpc_scenes(c),
+                               hipMemcpyDeviceToHost, c->stream));
     return drp_sync(c);
 }
 
@@ -267,7 +316,7 @@ int drp_mpc_fetch_async(drp_ctx* c, int slot) {
     if (c->mpc_pending[slot]) return fail(c, DRP_ESTATE, "slot %d holds an iteration nobody has waited for", slot);
     HIPCHK(c, hipSetDevice(c->device));
     const drp_mpc_params& p = c->mpc;
-    const int H = p.n_look_ahead, B = p.n_sample * p.n_batch;
+    const int H = p.n_look_ahead, B = mpc_rows(c);
     const size_t na = (size_t)B * H * 4, nr = (size_t)B;
     for (int q = 0; q < 2; ++q) {
         // a slot's block goes only while nothing is in flight: the copies of a pending iteration land in it
@@ -291,7 +340,7 @@ int drp_mpc_wait(drp_ctx* c, int slot, float* actions, float* rewards) {
     c->mpc_pending[slot] = false;
     CHK(guarded_wait(c, c->mpc_ev[slot].ev));
     const drp_mpc_params& p = c->mpc;
-    const size_t na = (size_t)p.n_sample * p.n_batch * p.n_look_ahead * 4, nr = (size_t)p.n_sample * p.n_batch;
+    const size_t na = (size_t)mpc_rows(c) * p.n_look_ahead * 4, nr = (size_t)mpc_rows(c);
     if (actions) memcpy(actions, c->mpc_pin[slot].p, na * sizeof(float));
     if (rewards) memcpy(rewards, ptr<float>(c->mpc_pin[slot]) + na, nr * sizeof(float));
     return DRP_OK;

@@ -590,10 +590,28 @@ int run_step(drp_ctx* c, const StepArgs& a) {
     return DRP_OK;
 }
 
+// the installed goal table as the scene kernels take it: rows of the session layout (nb columns per scene, `div` rows per
+// sample row), or an explicit scene per row
+GoalTable goal_table(const drp_ctx* c, int nb, int div, const int* scene_of_row = nullptr) {
+    GoalTable t{};
+    t.fields = static_cast<const float*>(c->gt_fields.p); t.coor = static_cast<const float*>(c->gt_coor.p);
+    t.m = static_cast<const int*>(c->gt_m.p); t.scene_of_row = scene_of_row;
+    t.field_stride = (size_t)c->gt_h * c->gt_w; t.m_max = c->gt_m_max; t.S = c->gt_S; t.nb = nb > 0 ? nb : 1; t.div = div > 0 ? div : 1;
+    return t;
+}
+
+// scenes > 0: a goal per row from the goal table (k_reward_scenes; scene_nb columns per scene, div rows per sample row, or
+// scene_of_row); else the single goal
 int run_reward(drp_ctx* c, const float* state, size_t row_stride, int rows, int N, int normalize,
-               float* out) {
+               float* out, int scenes = 0, int scene_nb = 1, int div = 1, const int* scene_of_row = nullptr) {
     ProbeScope ps(c, KC_REWARD);
     c->dv(DV_REWARD);
+    if (scenes > 0) {
+        hipLaunchKernelGGL(k_reward_scenes, dim3(rows), dim3(256), (2 * ((N + 3) & ~3) + 8) * sizeof(float), c->stream, state,
+                           row_stride, N, goal_table(c, scene_nb, div, scene_of_row), c->gt_h, c->gt_w, c->cam, normalize, out);
+        HIPCHK(c, hipGetLastError());
+        return DRP_OK;
+    }
     hipLaunchKernelGGL(k_reward, dim3(rows), dim3(256), (2 * ((N + 3) & ~3) + 8) * sizeof(float), c->stream, state,
                        row_stride, N, ptr<float>(c->goal_field), c->goal_h, c->goal_w,
                        ptr<float>(c->goal_coor), c->goal_m, c->cam, normalize, out);
@@ -621,7 +639,9 @@ int prepare_cself(drp_ctx* c, int attr_mod, int N, int B, const float** cself, c
     return DRP_OK;
 }
 
-int run_rollout(drp_ctx* c, int nb, int N, int B, int H, bool reward_all, bool reward_last, bool session = false) {
+// scenes > 0 (a multi-scene session): nb = scenes * scene_nb columns, and the rewards read the goal of the row's scene
+int run_rollout(drp_ctx* c, int nb, int N, int B, int H, bool reward_all, bool reward_last, bool session = false,
+                int scenes = 0, int scene_nb = 1) {
     CHK(ensure_step_ws(c, c->ws, B, N));
     CHK(ensure(c, c->states, (size_t)B * H * N * 3 * sizeof(float)));
     CHK(ensure(c, c->rewards, (size_t)B * H * sizeof(float)));
@@ -706,11 +726,11 @@ int run_rollout(drp_ctx* c, int nb, int N, int B, int H, bool reward_all, bool r
     }
     if (reward_all) {
         // rows = B*H consecutive [N,3] blocks
-        CHK(run_reward(c, states, (size_t)N * 3, B * H, N, 1, ptr<float>(c->rewards)));
+        CHK(run_reward(c, states, (size_t)N * 3, B * H, N, 1, ptr<float>(c->rewards), scenes, scene_nb, H));
     } else if (reward_last) {
         // only the last step's state of every sample; written at rewards[b*H + H-1]
         CHK(ensure(c, c->scratch, (size_t)B * sizeof(float)));
-        CHK(run_reward(c, states + (size_t)(H - 1) * N * 3, hstride, B, N, 1, ptr<float>(c->scratch)));
+        CHK(run_reward(c, states + (size_t)(H - 1) * N * 3, hstride, B, N, 1, ptr<float>(c->scratch), scenes, scene_nb, 1));
         HIPCHK(c, hipMemcpy2DAsync(ptr<float>(c->rewards) + (H - 1), H * sizeof(float), c->scratch.p,
                                    sizeof(float), sizeof(float), B, hipMemcpyDeviceToDevice, c->stream));
     }

@@ -274,11 +274,11 @@ int drp_distance_transform(drp_ctx* c, const uint8_t* src, int h, int w, int mod
     return drp_sync(c);
 }
 
-int drp_set_goal_image(drp_ctx* c, const float* obs_goal, int h, int w, int mode, int max_goal_pts, int fps_init,
-                       float* field_out, float* goal_coor_out, int* m_out) {
-    if (!c || !obs_goal) return fail(c, DRP_EINVAL, "null argument");
-    if (h <= 0 || w <= 0 || max_goal_pts <= 0) return fail(c, DRP_EINVAL, "bad goal image arguments");
-    HIPCHK(c, hipSetDevice(c->device));
+// One goal image -> its field and its goal pixel subsample, on the device.  field_dst / coor_dst null: into the context's single
+// goal (grown as needed); else into the caller's device memory (a slot of the goal table: h * w floats, max_goal_pts * 2 floats).
+// Enqueued and waited for; *m_res = the number of goal pixels kept.  The context's goal state is the caller's to update.
+static int goal_image_build(drp_ctx* c, const float* obs_goal, int h, int w, int mode, int max_goal_pts, int fps_init,
+                            float* field_dst, float* coor_dst, float* field_out, float* goal_coor_out, int* m_res) {
     hipStream_t st = c->stream;
     const size_t npix = (size_t)h * w;
     const unsigned eb = (unsigned)((npix + 255) / 256);
@@ -314,22 +314,70 @@ int drp_set_goal_image(drp_ctx* c, const float* obs_goal, int h, int w, int mode
         hipLaunchKernelGGL(k_fps_reg<2>, dim3(1), dim3(FPS_WIDE_THREADS), 0, st, ptr<float>(c->gl_pix), count, m, fps_init, chosen, md);
     else
         hipLaunchKernelGGL(k_fps<2>, dim3(1), dim3(1024), 0, st, ptr<float>(c->gl_pix), count, m, fps_init, fdist, chosen, md);
-    CHK(ensure(c, c->goal_coor, (size_t)m * 2 * sizeof(float)));
+    if (!coor_dst) {
+        CHK(ensure(c, c->goal_coor, (size_t)m * 2 * sizeof(float)));
+        coor_dst = ptr<float>(c->goal_coor);
+    }
     hipLaunchKernelGGL(k_goal_gather, dim3((m + 255) / 256), dim3(256), 0, st, ptr<float>(c->gl_pix), chosen, m,
-                       ptr<float>(c->goal_coor));
+                       coor_dst);
     // the field
     CHK(goal_stage_dt(c, ptr<uint8_t>(c->gl_seg), h, w, mode));
-    CHK(ensure(c, c->goal_field, npix * sizeof(float)));
+    if (!field_dst) {
+        CHK(ensure(c, c->goal_field, npix * sizeof(float)));
+        field_dst = ptr<float>(c->goal_field);
+    }
     hipLaunchKernelGGL(k_goal_sub, dim3(eb), dim3(256), 0, st, ptr<float>(c->gl_goal), ptr<float>(c->gl_dist), npix,
-                       ptr<float>(c->goal_field), bmin);
+                       field_dst, bmin);
     hipLaunchKernelGGL(k_goal_min, dim3(1), dim3(1024), 0, st, bmin, (int)eb, bmin + eb);
-    hipLaunchKernelGGL(k_goal_shift, dim3(eb), dim3(256), 0, st, ptr<float>(c->goal_field), npix, bmin + eb);
+    hipLaunchKernelGGL(k_goal_shift, dim3(eb), dim3(256), 0, st, field_dst, npix, bmin + eb);
     HIPCHK(c, hipGetLastError());
-    if (field_out) CHK(d2h(c, field_out, c->goal_field.p, npix * sizeof(float)));
-    if (goal_coor_out) CHK(d2h(c, goal_coor_out, c->goal_coor.p, (size_t)m * 2 * sizeof(float)));
+    if (field_out) CHK(d2h(c, field_out, field_dst, npix * sizeof(float)));
+    if (goal_coor_out) CHK(d2h(c, goal_coor_out, coor_dst, (size_t)m * 2 * sizeof(float)));
     CHK(guarded_wait(c, nullptr));
+    *m_res = m;
+    return DRP_OK;
+}
+
+int drp_set_goal_image(drp_ctx* c, const float* obs_goal, int h, int w, int mode, int max_goal_pts, int fps_init,
+                       float* field_out, float* goal_coor_out, int* m_out) {
+    if (!c || !obs_goal) return fail(c, DRP_EINVAL, "null argument");
+    if (h <= 0 || w <= 0 || max_goal_pts <= 0) return fail(c, DRP_EINVAL, "bad goal image arguments");
+    HIPCHK(c, hipSetDevice(c->device));
+    int m = 0;
+    CHK(goal_image_build(c, obs_goal, h, w, mode, max_goal_pts, fps_init, nullptr, nullptr, field_out, goal_coor_out, &m));
     if (m_out) *m_out = m;
     c->goal_h = h; c->goal_w = w; c->goal_m = m;
     c->have_goal = true;
+    return DRP_OK;
+}
+
+// The S-scene form: the single-scene device path once per scene, into slot s of a NEW table that replaces the installed one
+// only when every scene has gone through (an image without goal pixels leaves the context as it was).
+int drp_set_goal_image_scenes(drp_ctx* c, int S, const float* obs_goals, int h, int w, int mode, int max_goal_pts, int fps_init,
+                              float* field_out, float* goal_coor_out, int32_t* m_out) {
+    if (!c || !obs_goals) return fail(c, DRP_EINVAL, "null argument");
+    if (h <= 0 || w <= 0 || max_goal_pts <= 0) return fail(c, DRP_EINVAL, "bad goal image arguments");
+    if (S < 1 || S > DRP_MAX_SCENES) return fail(c, DRP_EINVAL, "%d scenes outside 1..%d", S, DRP_MAX_SCENES);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t npix = (size_t)h * w;
+    DevBuf nf, nc, nm;
+    CHK(ensure(c, nf, (size_t)S * npix * sizeof(float)));
+    CHK(ensure(c, nc, (size_t)S * max_goal_pts * 2 * sizeof(float)));
+    std::vector<int32_t> m((size_t)S, 0);
+    for (int k = 0; k < S; ++k) {
+        int mk = 0;
+        const int rc = goal_image_build(c, obs_goals + (size_t)k * npix, h, w, mode, max_goal_pts, fps_init,
+                                        static_cast<float*>(nf.p) + (size_t)k * npix, static_cast<float*>(nc.p) + (size_t)k * max_goal_pts * 2,
+                                        field_out ? field_out + (size_t)k * npix : nullptr,
+                                        goal_coor_out ? goal_coor_out + (size_t)k * max_goal_pts * 2 : nullptr, &mk);
+        if (rc != DRP_OK) { c->err = "scene " + std::to_string(k) + ": " + c->err; return rc; }
+        m[(size_t)k] = mk;
+    }
+    CHK(h2d(c, nm, m.data(), (size_t)S * sizeof(int32_t)));
+    CHK(guarded_wait(c, nullptr));
+    end_scene_sessions(c);
+    c->gt_fields = std::move(nf); c->gt_coor = std::move(nc); c->gt_m = std::move(nm);
+    c->gt_S = S; c->gt_h = h; c->gt_w = w; c->gt_m_max = max_goal_pts;
+    if (m_out) memcpy(m_out, m.data(), (size_t)S * sizeof(int32_t));
     return DRP_OK;
 }

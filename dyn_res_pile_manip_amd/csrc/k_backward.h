@@ -45,10 +45,12 @@ __device__ __forceinline__ KbRange kb_range(int N, int chunks) {
 // reward_out (nullable): the reward itself too, in k_reward's arithmetic and reduction order (the same bits) --
 // the planner's iteration then needs one launch for the reward and its gradient instead of two.
 #define KB_REWARD_LDS(N) ((size_t)(2 * (N) + 8) * sizeof(float) + (size_t)(2 * (N)) * sizeof(long long))
-__global__ void __launch_bounds__(256)
-kb_reward(const float* __restrict__ state, size_t row_stride, int N, const float* __restrict__ G, int Hh, int Ww,
-          const float* __restrict__ goal_coor, int M, DrpCam cam, int normalize, float* __restrict__ g_state,
-          size_t g_stride, float* __restrict__ reward_out, float* __restrict__ reward_copy = nullptr /* pinned host memory */) {
+// one state row `s` against one goal, gradient to `g`: the workgroup's whole work (kb_reward and kb_reward_scenes differ in
+// where G, goal_coor and M come from, in nothing else)
+__device__ __forceinline__ void kb_reward_row(const float* __restrict__ s, int N, const float* __restrict__ G, int Hh, int Ww,
+                                              const float* __restrict__ goal_coor, int M, const DrpCam& cam, int normalize,
+                                              float* __restrict__ g, float* __restrict__ reward_out,
+                                              float* __restrict__ reward_copy) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* px = lds;
     float* py = lds + N;
@@ -60,7 +62,6 @@ kb_reward(const float* __restrict__ state, size_t row_stride, int N, const float
     long long* gx = reinterpret_cast<long long*>(lds + 2 * N);
     long long* gy = gx + N;
     const float FIX = 1099511627776.0f, UNFIX = 1.0f / 1099511627776.0f;
-    const float* s = state + (size_t)blockIdx.x * row_stride;
     const float scale = normalize ? 1.0f / (float)N : 1.0f;
     for (int n = threadIdx.x; n < N; n += blockDim.x) {
         const float x = s[n * 3 + 0], y = s[n * 3 + 1], z = s[n * 3 + 2];
@@ -117,7 +118,6 @@ kb_reward(const float* __restrict__ state, size_t row_stride, int N, const float
         atomicAdd(reinterpret_cast<unsigned long long*>(&gy[arg]), (unsigned long long)__float2ll_rn(-scale * (qy - py[arg]) / dist * FIX));
     }
     __syncthreads();
-    float* g = g_state + (size_t)blockIdx.x * g_stride;
     for (int n = threadIdx.x; n < N; n += blockDim.x) {
         const float x = s[n * 3 + 0], y = s[n * 3 + 1], z = s[n * 3 + 2];
         const float gxn = (float)((double)gx[n] * (double)UNFIX), gyn = (float)((double)gy[n] * (double)UNFIX);
@@ -135,6 +135,25 @@ kb_reward(const float* __restrict__ state, size_t row_stride, int N, const float
             if (reward_copy != nullptr) reward_copy[blockIdx.x] = -r;
         }
     }
+}
+
+__global__ void __launch_bounds__(256)
+kb_reward(const float* __restrict__ state, size_t row_stride, int N, const float* __restrict__ G, int Hh, int Ww,
+          const float* __restrict__ goal_coor, int M, DrpCam cam, int normalize, float* __restrict__ g_state,
+          size_t g_stride, float* __restrict__ reward_out, float* __restrict__ reward_copy = nullptr /* pinned host memory */) {
+    kb_reward_row(state + (size_t)blockIdx.x * row_stride, N, G, Hh, Ww, goal_coor, M, cam, normalize,
+                  g_state + (size_t)blockIdx.x * g_stride, reward_out, reward_copy);
+}
+
+// the same with a goal per row (k_reward.h: GoalTable): row r reads the field, the pixels and the pixel count of scene(r)
+__global__ void __launch_bounds__(256)
+kb_reward_scenes(const float* __restrict__ state, size_t row_stride, int N, GoalTable gt, int Hh, int Ww, DrpCam cam,
+                 int normalize, float* __restrict__ g_state, size_t g_stride, float* __restrict__ reward_out,
+                 float* __restrict__ reward_copy /* pinned host memory, nullable */) {
+    const int sc = goal_scene(gt, (int)blockIdx.x);
+    kb_reward_row(state + (size_t)blockIdx.x * row_stride, N, gt.fields + (size_t)sc * gt.field_stride, Hh, Ww,
+                  gt.coor + (size_t)sc * gt.m_max * 2, gt.m[sc], cam, normalize, g_state + (size_t)blockIdx.x * g_stride,
+                  reward_out, reward_copy);
 }
 
 // ---- reversed neighbour lists: for every sender j the edge slots (i*10 + k) it feeds, ascending --

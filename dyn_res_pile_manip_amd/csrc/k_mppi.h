@@ -45,15 +45,22 @@ __device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& n0, fl
 //          else [n_sample,H,4] draws from the host (standard normal / U(-1,1) / U[0,1) by noise_type).
 //   noise_type (planners.py:116-135,169-175): 0 'normal' N(0, sigma); 1 'uniform' U(-sigma, sigma);
 //          2 'total_rand': no residual, the push is drawn uniformly from the clip box.
+// A multi-scene session launches gridDim.y = S: block row `sc` samples scene sc from its own nominal [sc][H][4], its own
+// key scene_seeds[sc] (the counter is a single-scene session's: the same draws) or its own host draws [sc][n_sample][H][4],
+// into the rows (sample * S + sc) * n_batch + batch.  gridDim.y = 1 and null scene_seeds is the single-scene launch.
 __global__ void k_mppi_sample(const double* __restrict__ nominal, const float* __restrict__ noise,
                               int n_sample, int n_batch, int H, double sigma, double beta, float4 lo,
                               float4 hi, uint64_t seed, uint64_t sample_offset, uint64_t iteration,
-                              int noise_type, float* __restrict__ actions) {
+                              int noise_type, float* __restrict__ actions, const uint64_t* __restrict__ scene_seeds = nullptr) {
     // four threads per sample, one per push component: the temporal filter runs along t only (the four lanes of a
     // sample evaluate the same Philox block -- one block yields the draws of all four components)
     const int tid = blockIdx.x * blockDim.x + threadIdx.x;
     const int s = tid >> 2, c = tid & 3;
     if (s >= n_sample) return;
+    const int sc = blockIdx.y, S = gridDim.y;
+    if (scene_seeds != nullptr) seed = scene_seeds[sc];
+    nominal += (size_t)sc * H * 4;
+    if (noise != nullptr) noise += (size_t)sc * n_sample * H * 4;
     const float lo_[4] = {lo.x, lo.y, lo.z, lo.w}, hi_[4] = {hi.x, hi.y, hi.z, hi.w};
     const double lc = (double)lo_[c], hc = (double)hi_[c];
     double resid = 0.0;
@@ -80,7 +87,7 @@ __global__ void k_mppi_sample(const double* __restrict__ nominal, const float* _
         a = fmin(fmax(a, lc), hc);
         if (noise_type == 2) a = lc + (double)n * (hc - lc);
         for (int j = 0; j < n_batch; ++j)
-            actions[(((size_t)s * n_batch + j) * H + t) * 4 + c] = (float)a;
+            actions[((((size_t)s * S + sc) * n_batch + j) * H + t) * 4 + c] = (float)a;
     }
 }
 
@@ -111,17 +118,21 @@ __device__ __forceinline__ double block_max_d(double v, double* red) {
 //   [2+4H] sum r   [3+4H] sum r^2   [4+4H] max r   [5+4H] argmax (global sample index)
 // r_s = mean over the n_batch columns of the sample's final-step reward.
 // grid = 4H + 1 blocks of 256 threads; block j < 4H reduces A[j], the last block the rest.
+// gridDim.y = S scenes (1: a single-scene session): block row sc reduces the samples of scene sc alone -- rows
+// (sample * S + sc) * n_batch + column -- into out + sc * scene_stride, in the order a single-scene session reduces them.
 __global__ void __launch_bounds__(256)
 k_mppi_partials(const float* __restrict__ reward, int reward_stride, const float* __restrict__ actions,
                 int n_sample, int n_batch, int H, double lambda, uint64_t sample_offset,
-                double* __restrict__ out) {
+                double* __restrict__ out, int scene_stride = 0) {
     __shared__ double red[4];
     const int j = blockIdx.x;
     const int HJ = 4 * H;
+    const int sc = blockIdx.y, S = gridDim.y;
+    out += (size_t)sc * scene_stride;
     double mloc = -__builtin_inf();
     for (int s = threadIdx.x; s < n_sample; s += blockDim.x) {
         double r = 0.0;
-        for (int c = 0; c < n_batch; ++c) r += (double)reward[((size_t)s * n_batch + c) * reward_stride];
+        for (int c = 0; c < n_batch; ++c) r += (double)reward[(((size_t)s * S + sc) * n_batch + c) * reward_stride];
         r /= (double)n_batch;
         mloc = fmax(mloc, lambda * r);
     }
@@ -131,11 +142,11 @@ k_mppi_partials(const float* __restrict__ reward, int reward_stride, const float
     int amax = 0;
     for (int s = threadIdx.x; s < n_sample; s += blockDim.x) {
         double r = 0.0;
-        for (int c = 0; c < n_batch; ++c) r += (double)reward[((size_t)s * n_batch + c) * reward_stride];
+        for (int c = 0; c < n_batch; ++c) r += (double)reward[(((size_t)s * S + sc) * n_batch + c) * reward_stride];
         r /= (double)n_batch;
         const double w = exp(lambda * r - m);
         if (j < HJ) {
-            acc0 += w * (double)actions[((size_t)s * n_batch) * HJ + j];
+            acc0 += w * (double)actions[(((size_t)s * S + sc) * n_batch) * HJ + j];
         } else {
             acc0 += w;
             acc1 += r;
@@ -168,10 +179,15 @@ k_mppi_partials(const float* __restrict__ reward, int reward_stride, const float
 // starts at partials + g * rank_stride (>= 6 + 4H doubles: the elite form of the exchange packs a rank's
 // statistics record and its elite block into one all-gathered message).
 //   stats_out: [0] mean r  [1] unbiased std r  [2] max r  [3] argmax  [4] Z  [5] m
+// gridDim.y = S scenes: block row sc combines scene sc's records (partials + sc * scene_stride) into nominal[sc][H][4] and
+// stats_out[sc][8].
 __global__ void k_mppi_update(const double* __restrict__ partials, int n_ranks, int rank_stride, int H,
                               double n_sample_total, double* __restrict__ nominal,
-                              double* __restrict__ stats_out) {
+                              double* __restrict__ stats_out, int scene_stride = 0) {
     const int HJ = 4 * H, REC = rank_stride;
+    partials += (size_t)blockIdx.y * scene_stride;
+    nominal += (size_t)blockIdx.y * HJ;
+    stats_out += (size_t)blockIdx.y * 8;
     double m = -__builtin_inf();
     for (int g = 0; g < n_ranks; ++g) m = fmax(m, partials[(size_t)g * REC]);
     double Z = 0.0;
@@ -286,8 +302,10 @@ __device__ __forceinline__ void block_sort_best_first(double* key, double* idx, 
 __global__ void __launch_bounds__(256)
 k_elite_local(const float* __restrict__ reward, int reward_stride, const float* __restrict__ actions,
               int n_sample, int n_batch, int H, int k, uint64_t sample_offset, int n2 /* 2^m >= n_sample: sort path; 0: k rounds */,
-              double* __restrict__ out) {
+              double* __restrict__ out, int scene_stride = 0 /* gridDim.y = S scenes: scene sc's records at out + sc * scene_stride */) {
     extern __shared__ __attribute__((aligned(16))) double el_lds[];
+    const int sc = blockIdx.y, S = gridDim.y;
+    out += (size_t)sc * scene_stride;
     const int cap = n2 > 0 ? n2 : n_sample;
     double* key = el_lds;
     double* idx = key + cap;
@@ -295,7 +313,7 @@ k_elite_local(const float* __restrict__ reward, int reward_stride, const float* 
     const int HJ = 4 * H, REC = 2 + HJ;
     for (int s = threadIdx.x; s < n_sample; s += blockDim.x) {
         double r = 0.0;
-        for (int c = 0; c < n_batch; ++c) r += (double)reward[((size_t)s * n_batch + c) * reward_stride];
+        for (int c = 0; c < n_batch; ++c) r += (double)reward[(((size_t)s * S + sc) * n_batch + c) * reward_stride];
         key[s] = r / (double)n_batch;
         idx[s] = (double)s + (double)sample_offset;
     }
@@ -315,7 +333,7 @@ k_elite_local(const float* __restrict__ reward, int reward_stride, const float* 
         for (int t = threadIdx.x; t < k * HJ; t += blockDim.x) {
             const int e = t / HJ, j = t - e * HJ;
             const bool ok = e < n2 && idx[e] >= 0.0 && key[e] == key[e];
-            out[(size_t)e * REC + 2 + j] = ok ? (double)actions[((size_t)src[e] * n_batch) * HJ + j] : 0.0;
+            out[(size_t)e * REC + 2 + j] = ok ? (double)actions[(((size_t)src[e] * S + sc) * n_batch) * HJ + j] : 0.0;
         }
         return;
     }
@@ -327,7 +345,7 @@ k_elite_local(const float* __restrict__ reward, int reward_stride, const float* 
         const int s = pick[e];
         double r = 0.0;
         if (s >= 0) {
-            for (int c = 0; c < n_batch; ++c) r += (double)reward[((size_t)s * n_batch + c) * reward_stride];
+            for (int c = 0; c < n_batch; ++c) r += (double)reward[(((size_t)s * S + sc) * n_batch + c) * reward_stride];
             r /= (double)n_batch;
         }
         out[(size_t)e * REC] = (s >= 0) ? r : -__builtin_inf();
@@ -335,7 +353,7 @@ k_elite_local(const float* __restrict__ reward, int reward_stride, const float* 
     }
     for (int t = threadIdx.x; t < k * HJ; t += blockDim.x) {       // all picks' sequences at once
         const int e = t / HJ, j = t - e * HJ, s = pick[e];
-        out[(size_t)e * REC + 2 + j] = (s >= 0) ? (double)actions[((size_t)s * n_batch) * HJ + j] : 0.0;
+        out[(size_t)e * REC + 2 + j] = (s >= 0) ? (double)actions[(((size_t)s * S + sc) * n_batch) * HJ + j] : 0.0;
     }
 }
 
@@ -344,9 +362,13 @@ k_elite_local(const float* __restrict__ reward, int reward_stride, const float* 
 // elite_out: [0] elite size, [1] worst elite reward.  dynamic LDS: max(2 * n_ranks * k, k * 4H) doubles + k ints
 __global__ void __launch_bounds__(256)
 k_elite_update(const double* __restrict__ recs, int n_ranks, int rank_stride, int k, int H, int n2 /* 2^m >= n_ranks * k: sort path; 0: k rounds */,
-               double* __restrict__ nominal, double* __restrict__ elite_out) {
+               double* __restrict__ nominal, double* __restrict__ elite_out,
+               int scene_stride = 0 /* gridDim.y = S scenes: scene sc's records at recs + sc * scene_stride, its nominal [sc][H][4], its elite_out [sc][8] */) {
     extern __shared__ __attribute__((aligned(16))) double el_lds[];
     const int HJ = 4 * H, REC = 2 + HJ, total = n_ranks * k;
+    recs += (size_t)blockIdx.y * scene_stride;
+    nominal += (size_t)blockIdx.y * HJ;
+    if (elite_out != nullptr) elite_out += (size_t)blockIdx.y * 8;
     auto rec_at = [&](int q) { return recs + (size_t)(q / k) * rank_stride + (size_t)(q % k) * REC; };
     double* key = el_lds;
     double* idx = key + (n2 > 0 ? n2 : total);

@@ -23,17 +23,33 @@ __device__ __forceinline__ float block_sum_256(float v, float* red /* >= 4 float
     return t;
 }
 
-// state row r lives at state + r * row_stride (floats); reward_out[r].
-__global__ void __launch_bounds__(256)
-k_reward(const float* __restrict__ state, size_t row_stride, int N, const float* __restrict__ G,
-         int Hh, int Ww, const float* __restrict__ goal_coor, int M, DrpCam cam, int normalize,
-         float* __restrict__ reward_out) {
+// The goal table of a multi-scene session (capi_ctx.h: gt_*): S goals of one image size.  Scene k's field is
+// fields + k * field_stride, its pixels coor + k * m_max * 2 (the first m[k] of them; what lies behind is never read).
+// The scene of row r: scene_of_row[r] when given (drp_reward_scenes), else ((r / div) / nb) % S -- the session layout
+// row = (sample * S + scene) * nb + column (planners.py:661-662 with S * nb columns), div = rows per sample row
+// (H when every step of a rollout is rewarded, 1 otherwise).
+struct GoalTable {
+    const float* fields;
+    const float* coor;
+    const int* m;
+    const int* scene_of_row;
+    size_t field_stride;
+    int m_max, S, nb, div;
+};
+__device__ __forceinline__ int goal_scene(const GoalTable& t, int row) {
+    return t.scene_of_row ? t.scene_of_row[row] : ((row / t.div) / t.nb) % t.S;
+}
+
+// one state row `s` against one goal: the workgroup's whole work (k_reward and k_reward_scenes differ in where G,
+// goal_coor and M come from, in nothing else)
+__device__ __forceinline__ void reward_row(const float* __restrict__ s, int N, const float* __restrict__ G,
+                                           int Hh, int Ww, const float* __restrict__ goal_coor, int M, const DrpCam& cam,
+                                           int normalize, float* __restrict__ reward_out) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int Na = (N + 3) & ~3;                     // py and the reduction scratch stay 16-B aligned
     float* px = lds;
     float* py = lds + Na;
     float* red = lds + 2 * Na;
-    const float* s = state + (size_t)blockIdx.x * row_stride;
     float r1 = 0.0f;
     for (int n = threadIdx.x; n < N; n += blockDim.x) {
         const float x = s[n * 3 + 0], y = s[n * 3 + 1], z = s[n * 3 + 2];
@@ -84,4 +100,21 @@ k_reward(const float* __restrict__ state, size_t row_stride, int N, const float*
         if (normalize) r = __fdiv_rn(r, (float)N);
         reward_out[blockIdx.x] = -r;
     }
+}
+
+// state row r lives at state + r * row_stride (floats); reward_out[r].
+__global__ void __launch_bounds__(256)
+k_reward(const float* __restrict__ state, size_t row_stride, int N, const float* __restrict__ G,
+         int Hh, int Ww, const float* __restrict__ goal_coor, int M, DrpCam cam, int normalize,
+         float* __restrict__ reward_out) {
+    reward_row(state + (size_t)blockIdx.x * row_stride, N, G, Hh, Ww, goal_coor, M, cam, normalize, reward_out);
+}
+
+// the same with a goal per row: the workgroup of row r reads the field, the pixels and the pixel count of scene(r)
+__global__ void __launch_bounds__(256)
+k_reward_scenes(const float* __restrict__ state, size_t row_stride, int N, GoalTable gt, int Hh, int Ww, DrpCam cam,
+                int normalize, float* __restrict__ reward_out) {
+    const int sc = goal_scene(gt, (int)blockIdx.x);
+    reward_row(state + (size_t)blockIdx.x * row_stride, N, gt.fields + (size_t)sc * gt.field_stride, Hh, Ww,
+               gt.coor + (size_t)sc * gt.m_max * 2, gt.m[sc], cam, normalize, reward_out);
 }

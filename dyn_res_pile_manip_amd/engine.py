@@ -22,6 +22,41 @@ def _dp(a):
     return a.ctypes.data_as(L.c_double_p)
 
 
+# ---- the row layout of a multi-scene session (include/drp.h: drp_mpc_begin_scenes; pure numpy, no device, no library) --------
+def scene_rows(S, n_units, nb):
+    """Rows of every scene in a session of S scenes x n_units samples (or trajectories) x nb columns -> int64 [S, n_units * nb]:
+    scene s's rows in the order a single-scene session numbers them (unit * nb + column).  The layout is planners.py:661-662
+    with S * nb columns: row = (unit * S + scene) * nb + column, so scene(row) = (row // nb) % S and row % (S * nb) is the
+    start column."""
+    S, n_units, nb = int(S), int(n_units), int(nb)
+    if S < 1 or n_units < 1 or nb < 1:
+        raise ValueError('scene_rows needs S, n_units, nb >= 1, got %d, %d, %d' % (S, n_units, nb))
+    u = np.arange(n_units, dtype=np.int64)[None, :, None]
+    k = np.arange(S, dtype=np.int64)[:, None, None]
+    c = np.arange(nb, dtype=np.int64)[None, None, :]
+    return ((u * S + k) * nb + c).reshape(S, n_units * nb)
+
+
+def interleave_scenes(per_scene, nb):
+    """S per-scene arrays [n_units * nb, ...] (a sequence, or an array [S, n_units * nb, ...]) -> the session's array
+    [n_units * S * nb, ...] (scene_rows' layout)."""
+    a = np.asarray(per_scene)
+    if a.ndim < 2 or a.shape[1] % int(nb) != 0:
+        raise ValueError('interleave_scenes needs [S, n_units * nb, ...] with nb = %d, got %s' % (int(nb), a.shape))
+    S, rows = a.shape[0], a.shape[1]
+    out = np.empty((S * rows,) + a.shape[2:], a.dtype)
+    out[scene_rows(S, rows // int(nb), nb).reshape(-1)] = a.reshape((S * rows,) + a.shape[2:])
+    return out
+
+
+def split_scenes(session, S, nb):
+    """The inverse of interleave_scenes: a session array [n_units * S * nb, ...] -> [S, n_units * nb, ...]."""
+    a = np.asarray(session)
+    if a.ndim < 1 or a.shape[0] % (int(S) * int(nb)) != 0:
+        raise ValueError('split_scenes needs [n_units * S * nb, ...] with S = %d, nb = %d, got %s' % (int(S), int(nb), a.shape))
+    return a[scene_rows(S, a.shape[0] // (int(S) * int(nb)), nb)]
+
+
 _DEFAULT = {}
 
 
@@ -354,6 +389,60 @@ class Engine(object):
         self._have_goal = True
         return field, coor[:m.value].copy()
 
+    # ---- the goal table of multi-scene sessions (include/drp.h: drp_set_goal_scenes) ------------------------------------
+    scene_rows = staticmethod(scene_rows)
+    interleave_scenes = staticmethod(interleave_scenes)
+    split_scenes = staticmethod(split_scenes)
+
+    def set_goal_scenes(self, fields, goal_coor, m=None):
+        """S goals of one image size beside the single goal: fields [S,h,w]; goal_coor either a sequence of S arrays [m_s,2]
+        (padded here to the longest) or an array [S,m_max,2] with the counts m [S]."""
+        fields = _f32(fields)
+        assert fields.ndim == 3
+        S = fields.shape[0]
+        if m is None:
+            parts = [_f32(g) for g in goal_coor]
+            assert len(parts) == S and all(g.ndim == 2 and g.shape[1] == 2 for g in parts)
+            m = np.array([g.shape[0] for g in parts], np.int32)
+            coor = np.zeros((S, max(int(m.max()) if S else 0, 1), 2), np.float32)
+            for k, g in enumerate(parts):
+                coor[k, :g.shape[0]] = g
+        else:
+            coor = _f32(goal_coor)
+            m = np.ascontiguousarray(m, dtype=np.int32).reshape(-1)
+            assert coor.ndim == 3 and coor.shape[0] == S and coor.shape[2] == 2 and m.shape == (S,)
+        self._ck(self.lib.drp_set_goal_scenes(self.h, int(S), _fp(fields), fields.shape[1], fields.shape[2], _fp(coor),
+                                              m.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), coor.shape[1]))
+        self._goal_scenes = int(S)
+
+    def set_goal_image_scenes(self, obs_goals, max_goal_pts, fps_init=0, mode='cv5', want=False):
+        """set_goal_image for S goal distance images [S,h,w] into the goal table: slot s gets the bits set_goal_image gives for
+        obs_goals[s].  -> the counts m [S]; want=True: (fields [S,h,w], [goal_coor_s [m_s,2] for every scene])."""
+        g = _f32(obs_goals)
+        assert g.ndim == 3
+        S = g.shape[0]
+        m = np.zeros(max(S, 1), np.int32)
+        field = np.empty(g.shape, np.float32) if want else None
+        coor = np.empty((S, int(max_goal_pts), 2), np.float32) if want else None
+        self._ck(self.lib.drp_set_goal_image_scenes(self.h, int(S), _fp(g), g.shape[1], g.shape[2], L.DIST_TRANSFORMS[mode],
+                                                    int(max_goal_pts), int(fps_init), _fp(field) if want else None,
+                                                    _fp(coor) if want else None, m.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+        self._goal_scenes = int(S)
+        if not want:
+            return m[:S].copy()
+        return field, [coor[k, :m[k]].copy() for k in range(S)]
+
+    def reward_scenes(self, state, scene, normalize=True):
+        """reward() with a goal per row: state [Bp,N,3], scene [Bp] indices into the goal table -> [Bp]"""
+        state = _f32(state)
+        Bp, N, _ = state.shape
+        scene = np.ascontiguousarray(scene, dtype=np.int32).reshape(-1)
+        assert scene.shape == (Bp,)
+        out = np.empty((Bp,), dtype=np.float32)
+        self._ck(self.lib.drp_reward_scenes(self.h, _fp(state), scene.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), Bp, N,
+                                            int(bool(normalize)), _fp(out)))
+        return out
+
     # ---- single operations --------------------------------------------------------
     def gen_s_delta(self, s_cur, action):
         s_cur, action = _f32(s_cur), _f32(action)
@@ -524,16 +613,54 @@ class Engine(object):
         p.noise_type, p.reserved = L.NOISE_TYPES[noise_type], 0
         self._ranged(lambda: self.lib.drp_mpc_begin(self.h, ctypes.byref(p), _fp(s0), _fp(attr), _fp(dens), _dp(nominal)))
         self.H, self.nb, self.N, self.ns = H, nb, N, int(n_sample)
+        self.S = 0
+
+    S = 0       # scenes of the running sampling session (mpc_begin_scenes); 0: a single-scene session
+
+    def mpc_begin_scenes(self, s0, attr, dens, nominal, n_sample, sigma, beta_filter, reward_weight,
+                         act_lo, act_hi, seeds, sample_offset=0, noise_type='normal'):
+        """mpc_begin over S scenes on the installed goal table (include/drp.h: drp_mpc_begin_scenes): s0 [S,nb,N,3], attr
+        [S,nb,N], dens [S,nb], nominal [S,H,4], seeds [S]; n_sample is per scene.  The session calls then move
+        n_sample * S * nb rows in scene_rows' layout, nominals [S,H,4], host noise [S,n_sample,H,4].  The range check is taken
+        over all scenes: one scene out of range refuses the whole session (auto_engine: moves all of it to the fp32 engine)."""
+        s0, attr, dens = _f32(s0), _f32(attr), _f32(dens)
+        nominal = np.ascontiguousarray(nominal, dtype=np.float64)
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64).reshape(-1)
+        assert s0.ndim == 4 and nominal.ndim == 3
+        S, nb, N, _ = s0.shape
+        H = nominal.shape[1]
+        assert attr.shape == (S, nb, N) and dens.shape == (S, nb) and nominal.shape == (S, H, 4) and seeds.shape == (S,)
+        p = L.MpcParams()
+        p.n_batch, p.n_particles, p.n_sample, p.n_look_ahead = nb, N, int(n_sample), H
+        p.sigma, p.beta_filter, p.reward_weight = float(sigma), float(beta_filter), float(reward_weight)
+        for i in range(4):
+            p.act_lo[i] = float(act_lo[i])
+            p.act_hi[i] = float(act_hi[i])
+        p.seed, p.sample_offset = 0, int(sample_offset)
+        p.noise_type, p.reserved = L.NOISE_TYPES[noise_type], 0
+        self._ranged(lambda: self.lib.drp_mpc_begin_scenes(self.h, ctypes.byref(p), int(S), _fp(s0), _fp(attr), _fp(dens),
+                                                           _dp(nominal), seeds.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+        self.H, self.nb, self.N, self.ns = H, nb, N, int(n_sample)
+        self.S = int(S)
+
+    def _mpc_rows(self):
+        return self.ns * max(self.S, 1) * self.nb
+
+    def mpc_stats_scenes(self):
+        """the last update's statistics of every scene (one entry for a single-scene session), each as mpc_stats() gives them"""
+        out = np.empty((max(self.S, 1), 6), dtype=np.float64)
+        self._ck(self.lib.drp_mpc_stats_scenes(self.h, _dp(out)))
+        return [{'mean': o[0], 'std': o[1], 'max': o[2], 'argmax': int(o[3]), 'Z': o[4], 'm': o[5]} for o in out]
 
     def mpc_sample(self, iteration, noise=None):
         if noise is not None:
             noise = _f32(noise)
-            assert noise.shape == (self.ns, self.H, 4)
+            assert noise.shape == ((self.S, self.ns, self.H, 4) if self.S else (self.ns, self.H, 4))
         self._ranged(lambda: self.lib.drp_mpc_sample(self.h, _fp(noise) if noise is not None else None, int(iteration)))
 
     def mpc_set_actions(self, actions):
         actions = _f32(actions)
-        assert actions.shape == (self.ns * self.nb, self.H, 4)
+        assert actions.shape == (self._mpc_rows(), self.H, 4)
         self._ranged(lambda: self.lib.drp_mpc_set_actions(self.h, _fp(actions)))
 
     def mpc_rollout(self, reward_all_steps=False):
@@ -569,12 +696,12 @@ class Engine(object):
         self._ck(self.lib.drp_mpc_update_elite_device(self.h, int(k)))
 
     def mpc_get(self, actions=False, rewards=False, rewards_all=False, states=False, nominal=False):
-        B = self.ns * self.nb
+        B = self._mpc_rows()
         a = np.empty((B, self.H, 4), np.float32) if actions else None
         r = np.empty((B,), np.float32) if rewards else None
         ra = np.empty((B, self.H), np.float32) if rewards_all else None
         s = np.empty((B, self.H, self.N, 3), np.float32) if states else None
-        n = np.empty((self.H, 4), np.float64) if nominal else None
+        n = np.empty(((self.S, self.H, 4) if self.S else (self.H, 4)), np.float64) if nominal else None
         self._ck(self.lib.drp_mpc_get(self.h, _fp(a) if actions else None, _fp(r) if rewards else None,
                                       _fp(ra) if rewards_all else None, _fp(s) if states else None,
                                       _dp(n) if nominal else None))
@@ -585,7 +712,7 @@ class Engine(object):
         self._ck(self.lib.drp_mpc_fetch_async(self.h, int(slot)))
 
     def mpc_wait(self, slot):
-        B = self.ns * self.nb
+        B = self._mpc_rows()
         a = np.empty((B, self.H, 4), np.float32)
         r = np.empty((B,), np.float32)
         self._ck(self.lib.drp_mpc_wait(self.h, int(slot), _fp(a), _fp(r)))
@@ -937,6 +1064,20 @@ class Engine(object):
         lo, hi = _f32(act_lo), _f32(act_hi)
         self._ck(self.lib.drp_gd_begin(self.h, _fp(s0), _fp(attr), _fp(dens), nb, N, _fp(actions), B, H,
                                        float(lr), _fp(lo), _fp(hi)))
+        self._gd = (B, H, N)
+
+    def gd_begin_scenes(self, s0, attr, dens, actions, lr, act_lo, act_hi):
+        """gd_begin over S scenes on the installed goal table (include/drp.h: drp_gd_begin_scenes): s0 [S,nb,N,3], attr [S,nb,N],
+        dens [S,nb], actions [B,H,4] in scene_rows' layout (B a multiple of S * nb).  gd_grad, gd_step, gd_step_async / gd_wait
+        and gd_actions then run as in a single-scene session."""
+        s0, attr, dens, actions = _f32(s0), _f32(attr), _f32(dens), _f32(actions)
+        assert s0.ndim == 4
+        S, nb, N, _ = s0.shape
+        B, H, _ = actions.shape
+        assert attr.shape == (S, nb, N) and dens.shape == (S, nb)
+        lo, hi = _f32(act_lo), _f32(act_hi)
+        self._ck(self.lib.drp_gd_begin_scenes(self.h, int(S), _fp(s0), _fp(attr), _fp(dens), nb, N, _fp(actions), B, H,
+                                              float(lr), _fp(lo), _fp(hi)))
         self._gd = (B, H, N)
 
     def gd_grad(self, want_state_grad=False):

@@ -43,6 +43,17 @@ def gd_iteration_count(n_update_iter, time_lim_ms, particle_num):
     return min(int(n_update_iter), bound)
 
 
+def _vote(max_reward_traj_idx, max_reward, best_actions):
+    """planners.py:773-781: the most frequent best-trajectory index over the columns wins, ties -> the column with the highest
+    reward; -> that column's best pushes [1,H,4]."""
+    idx_best_act = int(np.argmax(np.bincount(max_reward_traj_idx)))
+    idx_best_sample, best_r = -1, -np.inf
+    for j in range(len(max_reward_traj_idx)):
+        if idx_best_act == max_reward_traj_idx[j] and max_reward[j] > best_r:
+            idx_best_sample, best_r = j, max_reward[j]
+    return best_actions[idx_best_sample][None]
+
+
 def world2cam_affine(cam_extrinsic):
     """planners.py:197-203: rows 0..2 of inv(inv(cam_ext) diag(1,-1,-1,1)), built in
     float64 and cast to fp32 as the reference does."""
@@ -124,6 +135,36 @@ class PlannerGD(Planner):
         if self._goal_key is None or key[1:] != self._goal_key[1:] or key[0] is not self._goal_key[0]:
             eng.set_goal(flex_rewards.goal_field(g, eng), gc)
             self._goal_key = key
+
+    def _set_goal_scenes(self, eng, obs_goals, goal_coor=None, max_goal_pts=None, goal_keys=None):
+        """_set_goal for the goal table of a multi-scene call: S goal images [S,h,w] (and, optionally, the caller's goal pixels,
+        a sequence of S arrays [m_s,2]), installed once per content -- or per tuple of names `goal_keys`.  The single goal
+        and its cache are not touched.  -> True when the installed table was re-used."""
+        import hashlib
+        from . import flex_rewards
+        mode = flex_rewards.DIST_TRANSFORM
+        was = getattr(self, '_goal_scenes_key', None)
+        if goal_keys is not None and goal_coor is None:
+            key = (eng, mode, ('named', tuple(goal_keys)), None, int(max_goal_pts))
+        else:
+            g = np.ascontiguousarray(obs_goals, dtype=np.float32)
+            dig = hashlib.blake2b(g.tobytes(), digest_size=16)
+            if goal_coor is not None:
+                for gc in goal_coor:
+                    gc = np.ascontiguousarray(_to_np(gc)[0], dtype=np.float32)
+                    dig.update(repr(gc.shape).encode())
+                    dig.update(gc.tobytes())
+            key = (eng, mode, g.shape, dig.digest(), None if goal_coor is not None else int(max_goal_pts))
+        if was is not None and key[1:] == was[1:] and key[0] is was[0]:
+            return True
+        g = np.ascontiguousarray(obs_goals, dtype=np.float32)
+        if goal_coor is None:
+            eng.set_goal_image_scenes(g, max_goal_pts, 0, mode)
+        else:
+            fields, _ = eng.set_goal_image_scenes(g, 1, 0, mode, want=True)
+            eng.set_goal_scenes(fields, [np.ascontiguousarray(_to_np(gc)[0], dtype=np.float32) for gc in goal_coor])
+        self._goal_scenes_key = key
+        return False
 
     def _clip_box(self, cvx_l=0):
         """planners.py:151-167: the clip box of convex region `cvx_l`."""
@@ -466,15 +507,7 @@ class PlannerGD(Planner):
             max_reward_traj_idx[:] = mi
             best_actions_of_samples[:] = acts.reshape(n_batch, H, self.action_dim)
 
-        # planners.py:773-781: vote = most frequent best-trajectory index over the columns,
-        # ties -> the column with the highest reward
-        counts = np.bincount(max_reward_traj_idx)
-        idx_best_act = int(np.argmax(counts))
-        idx_best_sample, best_r = -1, -np.inf
-        for j in range(n_batch):
-            if idx_best_act == max_reward_traj_idx[j] and max_reward[j] > best_r:
-                idx_best_sample, best_r = j, max_reward[j]
-        best_seq = best_actions_of_samples[idx_best_sample][None]       # [1,H,4]
+        best_seq = _vote(max_reward_traj_idx, max_reward, best_actions_of_samples)       # [1,H,4]
 
         obs_seq_best, reward_best, next_r = None, None, None
         t_best = time.perf_counter()
@@ -502,6 +535,200 @@ class PlannerGD(Planner):
                           'goal_time': goal_time, 'goal_cached': goal_cached,
                           'best_rollout_time': (time.perf_counter() - t_best) * 1e3},
                 'iter_num': i}
+
+    def trajectory_optimization_ptcl_multi_scene(self, state_cur_np, state_param, attr_cur_np, obs_goals, model_dy, act_seq,
+                                                 act_label_seq, n_sample, n_look_ahead, n_update_iter, action_lower_lim,
+                                                 action_upper_lim, use_gpu=True, rollout_best_action_sequence=True,
+                                                 reward_params=None, funnel_dist=None, distractor_df_fn=None, gd_loop=1,
+                                                 time_lim=float('inf'), goal_coor=None, seeds=None, comm=None,
+                                                 noise_type='normal', wallclock_limit=False, goal_keys=None):
+        """trajectory_optimization_ptcl_multi_traj for S scenes in ONE session (include/drp.h: drp_mpc_begin_scenes,
+        drp_gd_begin_scenes): state_cur_np [S,nb,N,3], state_param [S,nb], attr_cur_np [S,nb,N], obs_goals [S,h,w], act_seq
+        [S,H,traj_num,4]; every other argument is shared by the scenes.  -> a list of S dicts; dict s is what the
+        single-scene method returns for scene s alone with seed = seeds[s] (every key but the wall-clock entries of `times`,
+        which are the whole call's).  mpc_type 'GD', 'MPPI' and 'CEM'.
+
+          goal_coor   a sequence of S arrays [m_s,2]: the caller's goal pixels of every scene;
+          goal_keys   the caller's names of the S goal images (the installed table is re-used while they stay the same);
+          seeds       [S] keys of the device sampler (default: drawn from numpy's global generator, scene 0 first).
+
+        One session means one range check: one scene whose attributes or densities leave the split-fp16 range moves all the
+        scenes to the fp32 engine.  comm, wallclock_limit=True and distractor_df_fn are refused: a multi-scene session
+        is neither sharded nor stopped by the clock."""
+        from .engine import interleave_scenes, split_scenes
+        if distractor_df_fn is not None:
+            raise NotImplementedError('distractor rewards are unused on the live path')
+        if comm is not None:
+            raise NotImplementedError('a multi-scene session cannot be sharded over ranks')
+        if wallclock_limit:
+            raise NotImplementedError('a multi-scene session has no wall-clock break: its scenes would stop together')
+        assert type(state_cur_np) == np.ndarray and state_cur_np.ndim == 4 and state_cur_np.shape[3] == 3
+        S, n_batch, N, _ = state_cur_np.shape
+        assert state_param.shape == (S, n_batch) and attr_cur_np.shape == (S, n_batch, N)
+        assert type(obs_goals) == np.ndarray and obs_goals.ndim == 3 and obs_goals.shape[0] == S
+        assert type(act_seq) == np.ndarray and act_seq.ndim == 4 and act_seq.shape[0] == S
+        assert act_seq.shape[1] == n_look_ahead and act_label_seq.shape[-1] == n_look_ahead
+        assert goal_coor is None or len(goal_coor) == S
+        start = time.time()
+        self.particle_num = N
+        H = n_look_ahead
+        traj_num = int(act_seq.shape[2])
+        eng = self._bind(model_dy)
+        self._eng = eng
+        mpc_type = self.config['mpc'].get('mpc_type', 'MPPI')
+
+        t_goal = time.time()
+        goal_cached = self._set_goal_scenes(eng, obs_goals, goal_coor, max_goal_pts=N * 5, goal_keys=goal_keys)
+        if not goal_cached:
+            eng.sync()
+        goal_time = time.time() - t_goal
+
+        lo, hi = self._clip_box(0)
+        cfg = self.config['mpc']
+        if noise_type == 'uniform':
+            sigma = 2.0 * self.global_scale / 12.0                  # planners.py:124
+        else:
+            sigma = cfg['sigma'] * self.global_scale / 12.0         # planners.py:116
+        if seeds is None:
+            seeds = [int(np.random.randint(0, 2 ** 31 - 1)) for _ in range(S)]
+        seeds = [int(v) for v in seeds]
+        assert len(seeds) == S
+
+        n_it_cap = int(n_update_iter) * int(gd_loop)
+
+        class Book(object):
+            """one scene's bookkeeping (planners.py:721-727,736-738), as the single-scene method keeps it"""
+            def __init__(bk):
+                bk.max_reward = -np.inf * np.ones(n_batch, dtype=np.float32)
+                bk.max_reward_traj_idx = np.zeros(n_batch, dtype=np.int64)
+                bk.best_actions = np.zeros((n_batch, H, self.action_dim), dtype=np.float32)
+                bk.rew_mean = np.zeros((1, n_it_cap), dtype=np.float32)
+                bk.rew_std = np.zeros((1, n_it_cap), dtype=np.float32)
+
+            def aggregate(bk, it, rewards, actions, ns):
+                r = rewards.reshape(ns, n_batch)
+                cur_max, idx = r.max(0), r.argmax(0)                         # first maximum, as torch.max
+                acts = actions.reshape(ns, n_batch, H, self.action_dim)[idx, np.arange(n_batch)]
+                better = np.asarray(cur_max) > bk.max_reward                  # strictly, per column (planners.py:724)
+                bk.max_reward[better] = np.asarray(cur_max)[better]
+                bk.max_reward_traj_idx[better] = np.asarray(idx)[better]
+                bk.best_actions[better] = np.asarray(acts)[better]
+                if it < n_it_cap:
+                    bk.rew_mean[0, it] = r[:, 0].mean()
+                    bk.rew_std[0, it] = r[:, 0].std(ddof=1) if ns > 1 else 0.0
+
+        books = [Book() for _ in range(S)]
+        rollout_time = 0.0
+        optim_time = 0.0
+        # every scene's candidates as the single-scene method lays them out, [traj * nb, H, 4], then interleaved by scene
+        cand = np.stack([np.repeat(act_seq[k].transpose(1, 0, 2), n_batch, axis=0) for k in range(S)]).astype(np.float32)
+
+        def aggregate_all(it, rewards, actions, ns):
+            r, a = split_scenes(rewards, S, n_batch), split_scenes(actions, S, n_batch)
+            for k in range(S):
+                books[k].aggregate(it, r[k], a[k], ns)
+            return r, a
+
+        i = 0
+        if mpc_type == 'GD':
+            assert n_sample == traj_num, 'GD optimises the traj_num given trajectories (n_sample == traj_num)'
+            n_iter = gd_iteration_count(n_update_iter, time_lim, N)
+            if n_iter < 1:
+                raise ValueError('time_lim %.3g ms admits no iteration at %d particles (%d ms each, planners.py:25-28)'
+                                 % (time_lim, N, particle_num_to_iter_time(N)))
+            eng.gd_begin_scenes(state_cur_np, attr_cur_np, state_param, interleave_scenes(cand, n_batch), cfg['gd']['lr'], lo, hi)
+            reward_seqs = np.zeros((S, cand.shape[1]), np.float32)
+            act_seqs_last = cand
+            t0 = time.perf_counter()
+            enqueued = 0
+            for i in range(n_iter):
+                before = act_seqs_last
+                while enqueued < n_iter and enqueued <= i + GD_AHEAD:
+                    eng.gd_step_async(enqueued % GD_SLOTS)
+                    enqueued += 1
+                rew, acts = eng.gd_wait(i % GD_SLOTS)
+                # the rewards belong to the pushes before the update
+                reward_seqs = split_scenes(rew, S, n_batch)
+                act_seqs_last = split_scenes(acts, S, n_batch)
+                for k in range(S):
+                    books[k].aggregate(i, reward_seqs[k], before[k], traj_num)
+            optim_time += (time.perf_counter() - t0) * 1e3
+            nominal = [None] * S
+        else:
+            n_iter = int(n_update_iter)
+            mp = dict(sigma=sigma, beta_filter=cfg['mppi']['beta_filter'], reward_weight=cfg['mppi']['reward_weight'],
+                      act_lo=lo, act_hi=hi, seeds=seeds, noise_type=noise_type)
+            # iteration 0: every scene's traj_num candidates are scored
+            eng.mpc_begin_scenes(state_cur_np, attr_cur_np, state_param, act_seq[:, :, 0, :], n_sample=traj_num, **mp)
+            eng.mpc_set_actions(interleave_scenes(cand, n_batch))
+            t0 = time.perf_counter()
+            eng.mpc_rollout(False)
+            got = eng.mpc_get(rewards=True)
+            rollout_time += (time.perf_counter() - t0) * 1e3
+            reward_seqs = split_scenes(got['rewards'], S, n_batch).copy()
+            for k in range(S):
+                books[k].aggregate(0, reward_seqs[k], cand[k], traj_num)
+            act_seqs_last = cand
+            nominal = np.stack([act_seq[k][:, int(np.argmax(reward_seqs[k].reshape(traj_num, n_batch).mean(1))), :]
+                                for k in range(S)]).astype(np.float64)
+            if n_iter > 1:
+                eng.mpc_begin_scenes(state_cur_np, attr_cur_np, state_param, nominal, n_sample=int(n_sample), **mp)
+            k_elite = int(cfg.get('cem', {}).get('n_elite', max(1, n_sample // 10)))
+
+            def enqueue(it):
+                eng.mpc_sample(it)
+                eng.mpc_rollout(False)
+                if mpc_type == 'CEM':
+                    eng.mpc_update_elite_device(k_elite)   # elite update (not in the reference)
+                else:
+                    eng.mpc_update_device()
+                eng.mpc_fetch_async(it & 1)
+
+            t0 = time.perf_counter()
+            if n_iter > 1:
+                enqueue(1)
+            for i in range(1, n_iter):
+                if i + 1 < n_iter:
+                    enqueue(i + 1)
+                got = eng.mpc_wait(i & 1)
+                reward_seqs, act_seqs_last = aggregate_all(i, got['rewards'], got['actions'], int(n_sample))
+            optim_time += (time.perf_counter() - t0) * 1e3
+            if n_iter > 1:
+                nominal = eng.mpc_get(nominal=True)['nominal']
+            nominal = list(nominal)
+
+        out = []
+        t_best = time.perf_counter()
+        for k in range(S):
+            bk = books[k]
+            best_seq = _vote(bk.max_reward_traj_idx, bk.max_reward, bk.best_actions)       # [1,H,4]
+            obs_seq_best, reward_best, next_r = None, None, None
+            if rollout_best_action_sequence:
+                # planners.py:821-851: B=1 re-rollout of the winner on the scene's column 0 + all-step reward on the scene's goal
+                states, _ = eng.rollout(state_cur_np[k, 0:1], attr_cur_np[k, 0:1], state_param[k, 0:1], best_seq,
+                                        want_states=True, want_reward=False)
+                rew = eng.reward_scenes(states[0], np.full(H, k, np.int32))
+                obs_seq_best = states[0]
+                next_r = rew[:, None]                                    # [H,1]
+                reward_best = rew[-1:].copy()                            # [1]
+            ns_last = reward_seqs[k].shape[0] // n_batch
+            out.append({'action_sequence': best_seq[0],
+                        'action_full': act_seqs_last[k][:, 0, :],
+                        'reward_full': reward_seqs[k].reshape(ns_last, n_batch)[:, 0],
+                        'observation_sequence': obs_seq_best,
+                        'observation_distractor_sequence': None,
+                        'reward': reward_best,
+                        'next_r': next_r,
+                        'rew_mean': bk.rew_mean,
+                        'rew_std': bk.rew_std,
+                        'nominal_sequence': nominal[k],
+                        'iter_num': i})
+        times = {'total_time': time.time() - start, 'rollout_time': rollout_time, 'optim_time': optim_time,
+                 'goal_time': goal_time, 'goal_cached': goal_cached,
+                 'best_rollout_time': (time.perf_counter() - t_best) * 1e3}
+        for d in out:
+            d['times'] = dict(times)
+        return out
 
 
 def fps_np(pcd, particle_num, init_idx=-1):

@@ -121,6 +121,25 @@ int drp_distance_transform(drp_ctx* ctx, const uint8_t* src, int h, int w, int m
 int drp_set_goal_image(drp_ctx* ctx, const float* obs_goal, int h, int w, int mode, int max_goal_pts,
                        int fps_init, float* field_out, float* goal_coor_out, int* m_out);
 
+/* ---- the goal table of multi-scene sessions ----------------------------------------------------
+ * A context can hold, beside its single goal, S goals of one image size (1 <= S <= DRP_MAX_SCENES): the constants of
+ * config_reward_ptcl (env/flex_rewards.py:156-214) once per scene.  fields [S][h][w]; goal_coor [S][m_max][2] = (col,row)
+ * with per-scene counts m [S], 1 <= m[s] <= m_max: what lies behind a scene's m[s] pixels is never read.  The table serves
+ * drp_reward_scenes, drp_mpc_begin_scenes and drp_gd_begin_scenes; the single goal of drp_set_goal / drp_set_goal_image is
+ * another thing: installing either leaves the other as it was.  Installing a table ends a running multi-scene session (its
+ * next call returns DRP_ESTATE; begin again).  DRP_EINVAL for S outside the range or a count outside 1..m_max: the context
+ * is then as it was.
+ * The float64 yardsticks, training and the rewards of the one-shot rollout read the single goal only. */
+#define DRP_MAX_SCENES 64
+int drp_set_goal_scenes(drp_ctx* ctx, int S, const float* fields, int h, int w, const float* goal_coor, const int32_t* m,
+                        int m_max);
+/* The S-scene form of the goal-image call above: obs_goals [S][h][w]; slot s of the table receives the bits that call
+ * produces for obs_goals[s] (the same device path, once per scene), m_max = max_goal_pts.  field_out [S][h][w] /
+ * goal_coor_out [S][max_goal_pts][2] (the first m_out[s] rows of slot s) / m_out [S] are optional copies.  An image that the
+ * single-scene call refuses is refused here, with its scene named, and the installed table stays. */
+int drp_set_goal_image_scenes(drp_ctx* ctx, int S, const float* obs_goals, int h, int w, int mode, int max_goal_pts,
+                              int fps_init, float* field_out, float* goal_coor_out, int32_t* m_out);
+
 /* ---- single operations on host buffers (unit parity with the reference) --------
  * These stage their inputs in the buffers the drp_mpc_* / drp_gd_* sessions keep their state in: calling one of
  * them ends a running session (its next call returns DRP_ESTATE; begin again). */
@@ -154,6 +173,11 @@ int drp_rollout(drp_ctx* ctx, const float* s0, const float* attr, const float* d
 /* config_reward_ptcl (env/flex_rewards.py:156-214) downstream of the distance
  * transform.  state [Bp,N,3] -> reward [Bp]. */
 int drp_reward(drp_ctx* ctx, const float* state, int Bp, int N, int normalize, float* reward_out);
+/* The same with a goal per row: row r is scored against scene[r] of the goal table (env/flex_rewards.py:156-214 with that
+ * scene's constants) and gets the bits the call above gives with that scene's goal installed alone.  scene [Bp] int32.
+ * DRP_ESTATE without a table, DRP_EINVAL for an index outside 0..S-1.  Ends no session. */
+int drp_reward_scenes(drp_ctx* ctx, const float* state, const int32_t* scene, int Bp, int N, int normalize,
+                      float* reward_out);
 
 /* ---- device-resident sampling MPC (MPPI) ------------------------------------------
  * One iteration = sample_action_sequences (planners.py:69-190) -> ptcl_model_rollout
@@ -181,6 +205,29 @@ typedef struct drp_mpc_params {
 
 int drp_mpc_begin(drp_ctx* ctx, const drp_mpc_params* p, const float* s0, const float* attr,
                   const float* dens, const double* nominal /* [H,4] */);
+/* A session over S scenes (1 <= S <= DRP_MAX_SCENES, the S of the installed goal table): S piles, S goals, S nominal
+ * sequences, planned in one rollout batch.  p is shared by all scenes (shapes, sigma, beta_filter, reward_weight, clip box,
+ * noise type, sample_offset); p->n_sample is PER SCENE; p->seed is ignored for seeds [S].  s0 [S * nb][N][3], attr
+ * [S * nb][N], dens [S * nb] (scene-major: scene s owns columns s * nb .. s * nb + nb - 1), nominal [S][H][4].
+ * Rows follow planners.py:661-662 with S * nb columns:
+ *     row = (sample * S + scene) * nb + column,   scene(row) = (row / nb) % S,   B = n_sample * S * nb
+ * so the rollout is the one of a single-scene session of S * nb columns, and a row's reward reads its scene's goal.
+ * Every session call then acts on all scenes: drp_mpc_sample draws scene s from nominal[s] with the Philox key seeds[s] and
+ * a single-scene session's counter (the same draws; host noise is [S][n_sample][H][4]); drp_mpc_set_actions, drp_mpc_get,
+ * drp_mpc_fetch_async / drp_mpc_wait move B rows and [S][H][4] nominals; drp_mpc_update_device and
+ * drp_mpc_update_elite_device run one softmax combine / elite selection per scene over that scene's samples, in a
+ * single-scene session's reduction order: scene s's nominal and statistics are the doubles of a single-scene session with
+ * seed = seeds[s].  Sample indices are per scene, 0 .. n_sample - 1 plus sample_offset.
+ * The range check (DRP_ERANGE) is taken once per session over ALL scenes' attributes and densities and the clip box: one
+ * out-of-range scene refuses -- or, with the host mirror's fallback, moves to the fp32 matrix engine -- the whole session.
+ * Sharded multi-scene planning is out of scope: with S > 1 the partials / update / elite / update_elite calls (the
+ * host-transport forms) and the two device updates with a communicator of more than one rank return DRP_ESTATE.
+ * DRP_ESTATE without a goal table; DRP_EINVAL for S out of range or a table of another S. */
+int drp_mpc_begin_scenes(drp_ctx* ctx, const drp_mpc_params* p, int S, const float* s0, const float* attr,
+                         const float* dens, const double* nominal /* [S][H][4] */, const uint64_t* seeds /* [S] */);
+/* the statistics of the last update, per scene: [S][6] = mean r, unbiased std r, max r, argmax (sample index within the
+ * scene, plus sample_offset), Z, m.  S = 1 for a single-scene session. */
+int drp_mpc_stats_scenes(drp_ctx* ctx, double* stats_out /* [S][6] */);
 /* noise: NULL -> device Philox draws; else host [n_sample,H,4] draws: standard normal (DRP_NOISE_NORMAL),
  * U(-1,1) (DRP_NOISE_UNIFORM) or U[0,1) (DRP_NOISE_TOTAL_RAND). */
 int drp_mpc_sample(drp_ctx* ctx, const float* noise, uint64_t iteration);
@@ -355,6 +402,16 @@ int drp_gd_get(drp_ctx* ctx, float* actions_out);
 #define DRP_GD_SLOTS 8
 int drp_gd_step_async(drp_ctx* ctx, int slot);
 int drp_gd_wait(drp_ctx* ctx, int slot, float* rewards_out, float* actions_out);
+/* The same session over S scenes (the S of the installed goal table): s0 [S * nb][N][3], attr [S * nb][N], dens [S * nb],
+ * scene-major; B a multiple of S * nb; row r belongs to scene (r / nb) % S (planners.py:661-662 with S * nb columns) and its
+ * reward and the reward's gradient read that scene's goal (env/flex_rewards.py:156-214).  Rows are independent Adam problems,
+ * so nothing is combined per scene: the five session calls above then run as they do in a single-scene session, on either
+ * tape, and a row's rewards, gradients and pushes are the bits of a single-scene session on its scene.  The tape's engine
+ * is picked once from all scenes' attributes, densities and pushes.  DRP_ESTATE without a goal table; DRP_EINVAL for S out
+ * of range, a table of another S, or B no multiple of S * nb.  Sharding the rows of a multi-scene session over ranks is out
+ * of scope, as for the sampling sessions. */
+int drp_gd_begin_scenes(drp_ctx* ctx, int S, const float* s0, const float* attr, const float* dens, int nb, int N,
+                        const float* actions, int B, int H, double lr, const float act_lo[4], const float act_hi[4]);
 
 /* ---- multi-GPU (RCCL over xGMI) ------------------------------------------------------
  * The library does not link librccl: the first of these calls binds, at run time, $DRP_RCCL_LIB, else the librccl that
