@@ -195,6 +195,14 @@ SIGNATURES = {
     'drp_cloud_chamfer': (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.POINTER(ctypes.c_int32), c_float_p,
                                          ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_float_p,
                                          ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    'drp_train_grad_f64_untracked': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p,
+                                                    ctypes.POINTER(ctypes.c_int32), c_float_p, ctypes.c_int, ctypes.c_int,
+                                                    ctypes.c_int, c_float_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int,
+                                                    c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    'drp_cloud_chamfer_f64': (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.POINTER(ctypes.c_int32), c_float_p,
+                                             ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p,
+                                             c_double_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                             c_double_p]),
 }
 
 _lib = None

@@ -314,6 +314,7 @@ struct drp_ctx {
                                     // and reverse pass (the trainer: and its samples' gradient accumulators); the batch's inputs and results
 
     DevBuf ch_io;                   // drp_cloud_chamfer (capi_chamfer.h; a one-shot that keeps nothing between calls): its inputs and results
+    DevBuf ch64_io;                 // drp_cloud_chamfer_f64: the same, in a buffer of its own
 
     // re-packing after an optimiser step on the device (k_train.h): gather maps of the plain packers, pinned copy of the blob
     DevBuf map_valu, map_mfma, map_mfma_bwd;

@@ -3,7 +3,9 @@
 // engines' gradient, row y2) and the training loop body (drp_train_grad_f64, the yardstick of drp_train_step's gradients, row
 // y3) -- on ONE tape and ONE reverse pass (kernels: k_prop_f64.h forward, k_gd_f64.h backward; k_train_f64.h loss and weight
 // gradients).  They differ in where a step's impulse comes from (the push, or data), in the loss that seeds the reverse pass, in
-// the tail of a reverse step, and in the trainer's weight-gradient launches in between (F64Wgrad).  Like the one-step calls of
+// the tail of a reverse step, and in the trainer's weight-gradient launches in between (F64Wgrad).  drp_train_grad_f64_untracked is the
+// trainer's body with the Chamfer loss of k_chamfer_f64.h as the seed (row u1's yardstick); everything behind the seed is the
+// same code.  Like the one-step calls of
 // capi_f64.h they are no engine and no session: they work in buffers of their own under F64Scope, keep nothing between calls
 // and leave the context -- the trainer's Adam state included -- as they found it.
 
@@ -277,7 +279,11 @@ struct Tr64Io {
     const float *states, *sdelta, *attr, *dens;     // sdelta: the impulses [B][H][N][3], or with `actions` the pushes [B][H][4]
     bool actions;
     const int* nums;
+    const float* targets;           // the Chamfer loss (M > 0): the target clouds [B][H][M][3] and their counts [B][H]; else null
+    const int* tnums;
+    int M;
     double *terms, *total;          // [H][B], [W_TOTAL]
+    double* margin;                 // the Chamfer loss: [H][B], every (step, sample)'s smallest arg-min margin
 };
 
 // forward with tape, loss, reverse pass with weight gradients of the samples [b0, b0 + bc): launches and the state gradient's copy
@@ -298,7 +304,21 @@ int tr64_chunk(drp_ctx* c, const Tr64Ws& k, const Tr64Io& io, int b0, int bc, in
                                ptr<float>(c->ws.s_in), ptr<float>(c->ws.s_delta));
     }));
     // ---- every step's loss term and its seed of the reverse pass; the samples' accumulators start at zero
-    hipLaunchKernelGGL(kt64_mse, dim3(bc, H), dim3(256), 0, st, k.tape.state, io.states, io.nums, b0, bc, B, N, H, io.terms, k.rev.g_state);
+    if (io.M == 0) {
+        hipLaunchKernelGGL(kt64_mse, dim3(bc, H), dim3(256), 0, st, k.tape.state, io.states, io.nums, b0, bc, B, N, H, io.terms, k.rev.g_state);
+    } else {
+        // the same slot of the stream and the same outputs: slice t + 1 of the tape's states against step t of the target clouds,
+        // the arg-mins taken here in double
+        Kc64Args a{};
+        a.p64 = k.tape.state + pn * 3; a.p_bstride = (size_t)N * 3; a.p_tstride = pn * 3;
+        a.tgt = io.targets; a.q_bstride = (size_t)H * io.M * 3; a.q_tstride = (size_t)io.M * 3;
+        a.n_p = io.nums;
+        a.n_q = io.tnums; a.nq_bstride = H; a.nq_tstride = 1;
+        a.b_off = b0; a.B = B; a.N = N; a.M = io.M;
+        a.scale = 1.0 / ((double)H * (double)B);
+        a.grad = k.rev.g_state; a.terms = io.terms; a.margin = io.margin;
+        hipLaunchKernelGGL((kc64_chamfer<true>), dim3(bc, H), dim3(KC64_THREADS), 0, st, a);
+    }
     HIPCHK(c, hipMemsetAsync(k.wg.acc, 0, (size_t)bc * W_TOTAL * sizeof(double), st));
     F64Wgrad wg = k.wg;
     wg.st = st; wg.bc = bc; wg.N = N; wg.dens = dens;
@@ -362,11 +382,19 @@ int drp_gd_grad_f64(drp_ctx* c, const float* s0, const float* attr, const float*
 }
 
 namespace {
-// drp_train_grad_f64 and drp_train_grad_f64_actions: one body; `impulses` is states_delta [B][H][N][3], or with `actions` the
-// pushes [B][H][4]
+// what seeds the reverse pass: the tracked MSE, or the Chamfer loss against untracked target clouds (k_chamfer_f64.h)
+struct Tr64Loss {
+    bool chamfer = false;
+    const float* targets = nullptr;         // [B][H][M][3]
+    const int32_t* target_nums = nullptr;   // [B][H]
+    int M = 0;
+    double* margin_out = nullptr;           // [H][B], nullable
+};
+// drp_train_grad_f64, drp_train_grad_f64_actions and drp_train_grad_f64_untracked: one body; `impulses` is states_delta
+// [B][H][N][3], or with `actions` the pushes [B][H][4]; the loss kind and the targets in `lk`
 int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, bool actions, const float* attrs,
-                        const int32_t* particle_nums, const float* particle_dens, int B, int N, int n_rollout, double* loss_out,
-                        double* loss_terms_out, double* grad_out, double* grad_state_out) {
+                        const int32_t* particle_nums, const float* particle_dens, int B, int N, int n_rollout, const Tr64Loss& lk,
+                        double* loss_out, double* loss_terms_out, double* grad_out, double* grad_state_out) {
     CHK(need(c, true, actions, false));
     CHK(check_bn(c, B, N));
     if (!states || !impulses || !attrs || !particle_nums || !particle_dens) return fail(c, DRP_EINVAL, "null argument");
@@ -374,6 +402,14 @@ int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, 
     for (int b = 0; b < B; ++b)
         if (particle_nums[b] <= 0 || particle_nums[b] > N)
             return fail(c, DRP_EINVAL, "particle_nums[%d]=%d outside 1..%d", b, particle_nums[b], N);
+    if (lk.chamfer) {
+        if (!lk.targets || !lk.target_nums) return fail(c, DRP_EINVAL, "null argument");
+        if (lk.M <= 0 || lk.M > KC64_MAX_POINTS) return fail(c, DRP_EINVAL, "bad shape M=%d (1..%d)", lk.M, KC64_MAX_POINTS);
+        for (int e = 0; e < B * n_rollout; ++e)
+            if (lk.target_nums[e] <= 0 || lk.target_nums[e] > lk.M)
+                return fail(c, DRP_EINVAL, "target_nums[%d][%d]=%d outside 1..%d", e / n_rollout, e % n_rollout, lk.target_nums[e],
+                            lk.M);
+    }
     if (actions) CHK(check_pushes(c, impulses, B, n_rollout));
     HIPCHK(c, hipSetDevice(c->device));
     F64Scope scope(c);
@@ -385,27 +421,40 @@ int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, 
     size_t Bc;
     CHK(f64_size_chunks(c, B, N, ((size_t)1 << 24) / ((size_t)N * DRP_K), bytes_of, &Bc));
     k.carve(c->grad64_ws.p, Bc, (size_t)N, (size_t)H);
-    // the whole batch's inputs in one upload: states | impulses | attrs[:, 0] | densities | particle counts, then the results
-    const size_t n_st = (size_t)B * (H + 1) * N * 3, n_sd = actions ? (size_t)B * H * 4 : (size_t)B * H * N * 3, n_at = (size_t)B * N;
-    std::vector<float> host(n_st + n_sd + n_at + (size_t)B + (size_t)B);
-    memcpy(host.data(), states, n_st * sizeof(float));
-    memcpy(host.data() + n_st, impulses, n_sd * sizeof(float));
-    for (int b = 0; b < B; ++b) memcpy(host.data() + n_st + n_sd + (size_t)b * N, attrs + (size_t)b * (H + 1) * N, (size_t)N * sizeof(float));
-    memcpy(host.data() + n_st + n_sd + n_at, particle_dens, (size_t)B * sizeof(float));
-    memcpy(host.data() + n_st + n_sd + n_at + B, particle_nums, (size_t)B * sizeof(int32_t));
+    // the whole batch's inputs in one upload (train_host.h: tr64_layout): states | impulses | attrs[:, 0] | densities | particle
+    // counts [| target clouds | their counts], then the results: terms | total [| margins]
+    const int M = lk.chamfer ? lk.M : 0;
+    const Tr64Arena lay = tr64_layout(B, H, N, M, actions);
+    std::vector<float> host(lay.words);
+    memcpy(host.data() + lay.states, states, (lay.sdelta - lay.states) * sizeof(float));
+    memcpy(host.data() + lay.sdelta, impulses, (lay.attr - lay.sdelta) * sizeof(float));
+    for (int b = 0; b < B; ++b) memcpy(host.data() + lay.attr + (size_t)b * N, attrs + (size_t)b * (H + 1) * N, (size_t)N * sizeof(float));
+    memcpy(host.data() + lay.dens, particle_dens, (size_t)B * sizeof(float));
+    memcpy(host.data() + lay.nums, particle_nums, (size_t)B * sizeof(int32_t));
+    if (M > 0) {
+        memcpy(host.data() + lay.targets, lk.targets, (size_t)B * H * M * 3 * sizeof(float));
+        memcpy(host.data() + lay.tnums, lk.target_nums, (size_t)B * H * sizeof(int32_t));
+    }
     const size_t n_terms = (size_t)H * B;
     Tr64Io io{};
-    CHK(f64_upload_batch(c, host, n_terms + (size_t)W_TOTAL, &io.terms));
-    io.states = ptr<float>(c->grad64_io); io.sdelta = io.states + n_st; io.attr = io.sdelta + n_sd; io.dens = io.attr + n_at;
-    io.nums = reinterpret_cast<const int*>(io.dens + B);
+    CHK(f64_upload_batch(c, host, n_terms + (size_t)W_TOTAL + (M > 0 ? n_terms : 0), &io.terms));
+    io.states = ptr<float>(c->grad64_io); io.sdelta = io.states + lay.sdelta; io.attr = io.states + lay.attr; io.dens = io.states + lay.dens;
+    io.nums = reinterpret_cast<const int*>(io.states + lay.nums);
     io.actions = actions;
+    io.M = M;
     io.total = io.terms + n_terms;
+    if (M > 0) {
+        io.targets = io.states + lay.targets;
+        io.tnums = reinterpret_cast<const int*>(io.states + lay.tnums);
+        io.margin = io.total + W_TOTAL;
+    }
     HIPCHK(c, hipMemsetAsync(io.total, 0, (size_t)W_TOTAL * sizeof(double), c->stream));
     for (int b0 = 0; b0 < B; b0 += (int)Bc)
         CHK(tr64_chunk(c, k, io, b0, std::min((int)Bc, B - b0), N, B, H, grad_state_out));
     std::vector<double> terms(n_terms);
     CHK(d2h(c, terms.data(), io.terms, n_terms * sizeof(double)));
     if (grad_out) CHK(d2h(c, grad_out, io.total, (size_t)W_TOTAL * sizeof(double)));
+    if (M > 0 && lk.margin_out) CHK(d2h(c, lk.margin_out, io.margin, n_terms * sizeof(double)));
     CHK(guarded_wait(c, nullptr));          // (the upload's host block lives until here)
     if (loss_terms_out) memcpy(loss_terms_out, terms.data(), n_terms * sizeof(double));
     if (loss_out) {
@@ -420,13 +469,26 @@ int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, 
 int drp_train_grad_f64(drp_ctx* c, const float* states, const float* states_delta, const float* attrs, const int32_t* particle_nums,
                        const float* particle_dens, int B, int N, int n_rollout, double* loss_out, double* loss_terms_out,
                        double* grad_out, double* grad_state_out) {
-    return train_grad_f64_body(c, states, states_delta, false, attrs, particle_nums, particle_dens, B, N, n_rollout, loss_out,
-                               loss_terms_out, grad_out, grad_state_out);
+    return train_grad_f64_body(c, states, states_delta, false, attrs, particle_nums, particle_dens, B, N, n_rollout, Tr64Loss{},
+                               loss_out, loss_terms_out, grad_out, grad_state_out);
 }
 
 int drp_train_grad_f64_actions(drp_ctx* c, const float* states, const float* actions, const float* attrs,
                                const int32_t* particle_nums, const float* particle_dens, int B, int N, int n_rollout,
                                double* loss_out, double* loss_terms_out, double* grad_out, double* grad_state_out) {
-    return train_grad_f64_body(c, states, actions, true, attrs, particle_nums, particle_dens, B, N, n_rollout, loss_out,
+    return train_grad_f64_body(c, states, actions, true, attrs, particle_nums, particle_dens, B, N, n_rollout, Tr64Loss{}, loss_out,
                                loss_terms_out, grad_out, grad_state_out);
+}
+
+int drp_train_grad_f64_untracked(drp_ctx* c, const float* states, const float* states_delta, const float* actions,
+                                 const float* attrs, const int32_t* particle_nums, const float* particle_dens, int B, int N,
+                                 int n_rollout, const float* targets, const int32_t* target_nums, int M, double* loss_out,
+                                 double* loss_terms_out, double* grad_out, double* grad_state_out, double* margin_out) {
+    if (!c) return DRP_EINVAL;
+    if ((states_delta != nullptr) == (actions != nullptr))
+        return fail(c, DRP_EINVAL, "exactly one of states_delta and actions must be given");
+    Tr64Loss lk;
+    lk.chamfer = true; lk.targets = targets; lk.target_nums = target_nums; lk.M = M; lk.margin_out = margin_out;
+    return train_grad_f64_body(c, states, actions != nullptr ? actions : states_delta, actions != nullptr, attrs, particle_nums,
+                               particle_dens, B, N, n_rollout, lk, loss_out, loss_terms_out, grad_out, grad_state_out);
 }

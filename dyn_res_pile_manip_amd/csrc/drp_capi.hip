@@ -49,6 +49,7 @@
 #include "k_gd_f64.h"
 #include "k_train_f64.h"
 #include "k_chamfer.h"
+#include "k_chamfer_f64.h"
 #include "k_prop_inst.h"       // km_prop / km_prop3 / km_rollout: declared here, instantiated in inst_*.hip
 
 #include "dispatch.h"          // host-only: policy, variant flags, plan functions

@@ -32,6 +32,27 @@ inline TrArena tr_layout(int B, int H, int N, int M = 0, bool actions = false) {
     return a;
 }
 
+// the batch as the float64 yardsticks upload it (capi_grad_f64.h: train_grad_f64_body), in 4-byte words, packed: states
+// [B][H+1][N][3] | impulses [B][H][N][3] (`actions`: the pushes [B][H][4]) | attrs[:, 0] [B][N] | densities [B] | particle counts
+// [B] (ints); drp_train_grad_f64_untracked (M > 0): behind them the target clouds [B][H][M][3] | their counts [B][H] (ints) --
+// with M = 0 the layout, and so the one copy, is drp_train_grad_f64's
+struct Tr64Arena { size_t states, sdelta, attr, dens, nums, targets, tnums, words; };
+inline Tr64Arena tr64_layout(int B, int H, int N, int M = 0, bool actions = false) {
+    Tr64Arena a{};
+    a.states = 0;
+    a.sdelta = a.states + (size_t)B * (H + 1) * N * 3;
+    a.attr = a.sdelta + tr_impulse_bytes(B, H, N, actions) / sizeof(float);
+    a.dens = a.attr + (size_t)B * N;
+    a.nums = a.dens + (size_t)B;
+    a.words = a.nums + (size_t)B;
+    a.targets = a.tnums = a.words;
+    if (M > 0) {
+        a.tnums = a.targets + (size_t)B * H * M * 3;
+        a.words = a.tnums + (size_t)B * H;
+    }
+    return a;
+}
+
 // the length of a push (sx, sy, ex, ey) in the camera frame, with push_frame's operations (k_graph.h: the same fmaf chain,
 // division and sum, no contraction); m: the 3x4 world -> camera map, gs: global_scale
 inline float push_len_host(const float* m, float gs, const float* act) {

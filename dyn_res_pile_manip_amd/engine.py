@@ -834,6 +834,35 @@ class Engine(object):
             out['nn_pq'], out['nn_qp'] = nn_pq, nn_qp
         return out
 
+    def cloud_chamfer_f64(self, p, q, n_p=None, n_q=None, want_grad=False, want_nn=False):
+        """cloud_chamfer in float64 on the device (include/drp.h: drp_cloud_chamfer_f64): the same dict with 'grad' as float64,
+        plus 'margin' [B, 2] -- per sample the smallest (second-best - best) squared distance over its arg-mins, p -> q then
+        q -> p: 0 for a duplicate of a winner, inf where the other cloud has one row."""
+        p, q = _f32(p), _f32(q)
+        if p.ndim == 2 and q.ndim == 2:
+            p, q = p[None], q[None]
+        assert p.ndim == 3 and q.ndim == 3 and p.shape[2] == 3 and q.shape[2] == 3 and p.shape[0] == q.shape[0]
+        B, N, M = p.shape[0], p.shape[1], q.shape[1]
+        n_p = np.full((B,), N, np.int32) if n_p is None else np.ascontiguousarray(n_p, dtype=np.int32).reshape(-1)
+        n_q = np.full((B,), M, np.int32) if n_q is None else np.ascontiguousarray(n_q, dtype=np.int32).reshape(-1)
+        assert n_p.shape == (B,) and n_q.shape == (B,)
+        terms = np.empty((B, 2), np.float64)
+        margin = np.empty((B, 2), np.float64)
+        grad = np.empty((B, N, 3), np.float64) if want_grad else None
+        nn_pq = np.empty((B, N), np.int32) if want_nn else None
+        nn_qp = np.empty((B, M), np.int32) if want_nn else None
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        self._ck(self.lib.drp_cloud_chamfer_f64(self.h, _fp(p), n_p.ctypes.data_as(i32p), _fp(q), n_q.ctypes.data_as(i32p), int(B),
+                                                int(N), int(M), _dp(terms), _dp(grad) if want_grad else None,
+                                                nn_pq.ctypes.data_as(i32p) if want_nn else None,
+                                                nn_qp.ctypes.data_as(i32p) if want_nn else None, _dp(margin)))
+        out = {'fwd': terms[:, 0].copy(), 'bwd': terms[:, 1].copy(), 'total': terms[:, 0] + terms[:, 1], 'margin': margin}
+        if want_grad:
+            out['grad'] = grad
+        if want_nn:
+            out['nn_pq'], out['nn_qp'] = nn_pq, nn_qp
+        return out
+
     # ---- the float64 yardstick of the trainer's gradients (include/drp.h: drp_train_grad_f64) ------------------------
     def train_grad_f64(self, states, states_delta, attrs, particle_nums, particle_dens, want_state=False):
         """What train_step(mode='grad') computes, in float64 on the device -> (loss, loss_terms [n_rollout, B], gradient blob
@@ -877,7 +906,41 @@ class Engine(object):
                                                      _dp(gs) if want_state else None))
         return (loss.value, terms, grad, gs) if want_state else (loss.value, terms, grad)
 
-    def train_gradient_probe(self, states, states_delta, attrs, particle_nums, particle_dens, actions=None):
+    def train_grad_f64_untracked(self, states, states_delta, attrs, particle_nums, particle_dens, targets, target_nums,
+                                 actions=None, want_state=False):
+        """train_grad_f64 (actions None) or train_grad_f64_actions (actions [B, n_rollout, 4]; states_delta is then ignored and
+        may be None) with the Chamfer loss against targets [B, n_rollout, M, 3] / target_nums [B, n_rollout]: what
+        train_step_untracked / train_step_actions(targets=...) compute with mode='grad', in float64 on the device (include/drp.h:
+        drp_train_grad_f64_untracked) -> (loss, loss_terms [n_rollout, B], gradient blob [38403], margin [n_rollout, B][, d loss /
+        d every step's predicted state [B, n_rollout, N, 3]]).  margin: per (step, sample) the smallest (second-best - best)
+        squared distance over its float64 arg-mins -- how close the nearest partner flip is.  The same one-shot contract."""
+        states, attrs = _f32(states), _f32(attrs)
+        imp = _f32(actions) if actions is not None else _f32(states_delta)
+        dens = _f32(particle_dens)
+        nums = np.ascontiguousarray(particle_nums, dtype=np.int32)
+        targets = _f32(targets)
+        tnums = np.ascontiguousarray(target_nums, dtype=np.int32)
+        B, T1, N, _ = states.shape
+        H = T1 - 1
+        assert imp.shape == ((B, H, 4) if actions is not None else (B, H, N, 3))
+        assert attrs.shape == (B, T1, N) and nums.shape == (B,) and dens.shape == (B,)
+        assert targets.ndim == 4 and targets.shape[:2] == (B, H) and targets.shape[3] == 3 and tnums.shape == (B, H)
+        M = targets.shape[2]
+        loss = ctypes.c_double()
+        terms = np.empty((H, B), np.float64)
+        margin = np.empty((H, B), np.float64)
+        grad = np.empty((38403,), np.float64)
+        gs = np.empty((B, H, N, 3), np.float64) if want_state else None
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        self._ck(self.lib.drp_train_grad_f64_untracked(self.h, _fp(states), None if actions is not None else _fp(imp),
+                                                       _fp(imp) if actions is not None else None, _fp(attrs),
+                                                       nums.ctypes.data_as(i32p), _fp(dens), int(B), int(N), int(H), _fp(targets),
+                                                       tnums.ctypes.data_as(i32p), int(M), ctypes.byref(loss), _dp(terms), _dp(grad),
+                                                       _dp(gs) if want_state else None, _dp(margin)))
+        return (loss.value, terms, grad, margin, gs) if want_state else (loss.value, terms, grad, margin)
+
+    def train_gradient_probe(self, states, states_delta, attrs, particle_nums, particle_dens, actions=None, targets=None,
+                             target_nums=None):
         """The gradients the trainer consumes, held against float64: train_step(mode='grad', want_grad=True) on whatever tape the
         selection gives, then train_grad_f64 on the same batch -> {'tensors': {state_dict key: {'max_abs_err', 'max_abs_ref',
         'rel' = err / max(ref, 1e-300)}}, 'worst': the key of the largest rel, 'rel': that rel, 'loss32', 'loss64', 'loss_diff',
@@ -885,16 +948,32 @@ class Engine(object):
         following train_step(mode='update') is what it would have been.  Like train_step it ends a running planner session, and
         it resets the dispatch marks: last_dispatch() afterwards names this call's kernels.  With `actions` [B, n_rollout, 4]
         (states_delta is then ignored and may be None) the pair is train_step_actions and train_grad_f64_actions: the impulses
-        from the pushes on the predicted state, the MSE loss."""
+        from the pushes on the predicted state, the MSE loss.  With `targets` [B, n_rollout, M, 3] and `target_nums`
+        [B, n_rollout] the loss is the Chamfer distance to the untracked clouds: the pair is train_step_untracked (or
+        train_step_actions with targets) and train_grad_f64_untracked, and the dict also has 'loss_kind': 'chamfer' and
+        'min_margin', the smallest arg-min margin of the float64 evaluation over the batch (squared distance).  The float64 side
+        takes its own arg-mins: where min_margin is as small as the fp32 drift of a predicted state allows a nearest partner to
+        flip, a finding may be that flip -- a discrete change of the gradient -- and no arithmetic error."""
         from .weights import STATE_DICT_KEYS
+        assert (targets is None) == (target_nums is None)
+        chamfer = targets is not None
         self.dispatch_reset()
         if actions is not None:
-            loss32, g32 = self.train_step_actions(states, actions, attrs, particle_nums, particle_dens, mode='grad', want_grad=True)
+            loss32, g32 = self.train_step_actions(states, actions, attrs, particle_nums, particle_dens, targets, target_nums,
+                                                  mode='grad', want_grad=True)
+        elif chamfer:
+            loss32, g32 = self.train_step_untracked(states, states_delta, attrs, particle_nums, particle_dens, targets, target_nums,
+                                                    mode='grad', want_grad=True)
         else:
             loss32, g32 = self.train_step(states, states_delta, attrs, particle_nums, particle_dens, mode='grad', want_grad=True)
         # the fp32 matrix engine's tape is the only user of k_aggregate_tape (pick_tape_engine: selected, or after a range refusal)
         tape = 'mfma' if 'k_aggregate_tape' in self.last_dispatch() else 'fused'
-        if actions is not None:
+        min_margin = None
+        if chamfer:
+            loss64, _, g64, margin = self.train_grad_f64_untracked(states, states_delta, attrs, particle_nums, particle_dens, targets,
+                                                                   target_nums, actions=actions)
+            min_margin = float(margin.min())
+        elif actions is not None:
             loss64, _, g64 = self.train_grad_f64_actions(states, actions, attrs, particle_nums, particle_dens)
         else:
             loss64, _, g64 = self.train_grad_f64(states, states_delta, attrs, particle_nums, particle_dens)
@@ -908,8 +987,11 @@ class Engine(object):
             if worst is None or tensors[key]['rel'] > tensors[worst]['rel']:
                 worst = key
             off += n
-        return {'tensors': tensors, 'worst': worst, 'rel': tensors[worst]['rel'], 'loss32': loss32, 'loss64': loss64,
-                'loss_diff': abs(loss32 - loss64), 'tape': tape}
+        out = {'tensors': tensors, 'worst': worst, 'rel': tensors[worst]['rel'], 'loss32': loss32, 'loss64': loss64,
+               'loss_diff': abs(loss32 - loss64), 'tape': tape}
+        if chamfer:
+            out['loss_kind'], out['min_margin'] = 'chamfer', min_margin
+        return out
 
     def train_set_lr(self, lr):
         self._ck(self.lib.drp_train_set_lr(self.h, float(lr)))

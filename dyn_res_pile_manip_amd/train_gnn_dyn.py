@@ -152,34 +152,55 @@ class AverageMeter(object):
         self.avg = self.sum / self.count
 
 
-def probe_batch(model, data, impulses='data'):
+def probe_batch(model, data, impulses='data', loss='mse'):
     """Engine.train_gradient_probe on a collated batch: the trainer's fp32 gradients against the float64 evaluation of the same
-    batch on the device; weights, Adam state and iteration count are untouched"""
+    batch on the device; weights, Adam state and iteration count are untouched.  loss='chamfer': `data` is collate_untracked's
+    and the result also has 'min_margin' (Engine.train_gradient_probe)"""
+    if loss not in LOSSES:
+        raise ValueError('loss must be one of %s, got %r' % (LOSSES, loss))
+    if impulses not in IMPULSES:
+        raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
     states, states_delta, attrs, particle_nums, particle_dens = [data[i] for i in range(5)]
     if hasattr(model, '_claim'):
         model._claim()
-    return model.engine.train_gradient_probe(_np(states), _np(states_delta), _np(attrs), _np(particle_nums, np.int32),
-                                             _np(particle_dens), actions=batch_actions(data) if impulses == 'actions' else None)
+    extra = {}
+    if loss == 'chamfer':
+        extra = {'targets': _np(data[6]), 'target_nums': _np(data[7], np.int32)}
+    return model.engine.train_gradient_probe(_np(states), None if states_delta is None else _np(states_delta), _np(attrs),
+                                             _np(particle_nums, np.int32), _np(particle_dens),
+                                             actions=batch_actions(data) if impulses == 'actions' else None, **extra)
+
+
+def check_probe_options(loss, grad_probe_every, probe_every):
+    """the two probe schedules of train() / main(): grad_probe_every (the MSE yardstick alone) and probe_every (every loss)"""
+    if loss not in LOSSES:
+        raise ValueError('loss must be one of %s, got %r' % (LOSSES, loss))
+    if grad_probe_every > 0 and probe_every > 0:
+        raise ValueError('give grad_probe_every or probe_every, not both')
+    if loss == 'chamfer' and grad_probe_every > 0:
+        raise ValueError('grad_probe_every needs loss=\'mse\': the float64 yardstick of the gradients it pairs with is MSE-only; '
+                         'probe_every probes every loss')
 
 
 def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=None, first_epoch=0, grad_probe_every=0,
-          loss='mse', impulses='data'):
+          loss='mse', impulses='data', probe_every=0):
     """train/train_gnn_dyn.py:134-246 without the file I/O: `dataloaders` = {'train': iterable of
     collated batches, 'valid': ...}.  Returns {'best_valid_loss', 'history': [(epoch, phase, rmse)]}.
     ckp(epoch, i, model): called after training batch i when i % ckp_per_iter == 0 (:217-218); first_epoch: the epoch
     a resumed run starts from (:136).  grad_probe_every = k > 0: every k-th training batch (i % k == 0) is probed before its
     update (probe_batch); the worst tensor's rel goes to the history as (epoch, 'grad_probe', rel) and to the log.
     loss='chamfer': the batches are collate_untracked's and every step's term is the Chamfer distance to its target cloud; the
-    float64 yardstick on the device is MSE-only, so grad_probe_every > 0 is refused with it.  impulses='actions': the batches
+    option grad_probe_every pairs with the MSE yardstick alone, so grad_probe_every > 0 is refused with it.  probe_every = k > 0:
+    grad_probe_every's schedule and history entry for every loss and impulse source (probe_batch with the run's loss; with
+    loss='chamfer' the log line also carries min_margin, the float64 side's smallest arg-min margin); giving both is refused.
+    impulses='actions': the batches
     carry `.actions` and the model is trained through the push (run_batch); with real untracked data this is what makes
     n_rollout > 1 meaningful.  The engine's camera must be set (main does it)."""
-    if loss not in LOSSES:
-        raise ValueError('loss must be one of %s, got %r' % (LOSSES, loss))
+    check_probe_options(loss, grad_probe_every, probe_every)
     if impulses not in IMPULSES:
         raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
-    if loss == 'chamfer' and grad_probe_every > 0:
-        raise ValueError('grad_probe_every needs loss=\'mse\': the float64 yardstick of the gradients is MSE-only')
     loss_kind = loss
+    every = grad_probe_every if grad_probe_every > 0 else probe_every
     tc = config['train']
     n_rollout = tc['n_rollout']
     assert tc['n_history'] == 1
@@ -191,12 +212,13 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
             model.train(phase == 'train')
             meter = AverageMeter()
             for i, data in enumerate(dataloaders[phase]):
-                if grad_probe_every > 0 and phase == 'train' and i % grad_probe_every == 0:
-                    pr = probe_batch(model, data, impulses)
+                if every > 0 and phase == 'train' and i % every == 0:
+                    pr = probe_batch(model, data, impulses, loss_kind)
                     history.append((epoch, 'grad_probe', float(pr['rel'])))
                     if log is not None:
-                        log('grad_probe [%d][%d] worst %s rel %.3e (%s tape), loss diff %.3e' % (epoch, i, pr['worst'], pr['rel'],
-                                                                                               pr['tape'], pr['loss_diff']))
+                        line = 'grad_probe [%d][%d] worst %s rel %.3e (%s tape), loss diff %.3e' % (epoch, i, pr['worst'], pr['rel'],
+                                                                                                  pr['tape'], pr['loss_diff'])
+                        log(line + (', min_margin %.3e' % pr['min_margin'] if loss_kind == 'chamfer' else ''))
                 loss = run_batch(model, optimizer, data, phase, n_rollout, loss=loss_kind, impulses=impulses)
                 meter.update(loss, _np(data[0]).shape[0])
                 if log is not None and i % tc['log_per_iter'] == 0:
@@ -234,7 +256,7 @@ def set_seed(seed):
 
 
 def main(config, data_root=None, train_dir=None, cam=None, chunk=64, threads=8, n_epoch=None, engine=None, grad_probe_every=0,
-         loss='mse', impulses='data'):
+         loss='mse', impulses='data', probe_every=0):
     """The file-level part of train/train_gnn_dyn.py:train() (:45-130, :196-228): seed, the log directory with config.yaml
     and log.txt, the 'train' / 'valid' ParticleDatasets and their DeviceLoaders, a fresh model (torch.nn.Linear's default
     initialisation) or the resumed checkpoint, net_epoch_%d_iter_%d.pth every ckp_per_iter training batches and
@@ -243,14 +265,13 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=64, threads=8, 
     the directory.  loss='chamfer': the recorded episodes' correspondence is dropped (dataset_gnn_dyn.drop_correspondence on
     every sample, seeded by train.random_seed) and the model is trained on the Chamfer distance to the untracked clouds.
     impulses='actions': the engine's camera is set from the dataset's extrinsics and global_scale and every step's impulse comes
-    from the recorded push on the state the step reads (train)."""
+    from the recorded push on the state the step reads (train).  probe_every: train's."""
     import time
     import yaml
     from . import synthetic, weights
     from .dataset_gnn_dyn import DeviceLoader, ParticleDataset, UntrackedLoader
     from .gnn_dyn import PropNetDiffDenModel
-    if loss == 'chamfer' and grad_probe_every > 0:
-        raise ValueError('grad_probe_every needs loss=\'mse\': the float64 yardstick of the gradients is MSE-only')
+    check_probe_options(loss, grad_probe_every, probe_every)
     tc = config['train']
     resume = tc['particle'].get('resume', {'active': False, 'epoch': 0, 'iter': 0})
     if cam is None:
@@ -294,7 +315,7 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=64, threads=8, 
 
         result = train(config, model, loaders, n_epoch=n_epoch, log=log, on_best=on_best, ckp=ckp,
                        first_epoch=resume['epoch'] if resume['active'] and resume['epoch'] > 0 else 0,
-                       grad_probe_every=grad_probe_every, loss=loss, impulses=impulses)
+                       grad_probe_every=grad_probe_every, loss=loss, impulses=impulses, probe_every=probe_every)
         for epoch, phase, rmse in result['history']:
             if phase == 'grad_probe':                   # logged when it was taken
                 continue
@@ -317,6 +338,9 @@ def _cli(argv=None):
     ap.add_argument('--threads', type=int, default=8, help='decoding threads (at most 16)')
     ap.add_argument('--grad-probe-every', type=int, default=0,
                     help='hold every k-th training batch\'s gradients against float64 before its update (0: never)')
+    ap.add_argument('--probe-every', type=int, default=0,
+                    help='the same for every --loss and --impulses; with --loss chamfer the log line carries the float64 side\'s '
+                         'smallest arg-min margin')
     ap.add_argument('--loss', choices=LOSSES, default='mse',
                     help='chamfer: drop the recorded correspondence and train on the Chamfer distance to the untracked clouds')
     ap.add_argument('--impulses', choices=IMPULSES, default='data',
@@ -331,7 +355,7 @@ def _cli(argv=None):
     if a.n_timestep is not None:
         config['dataset']['n_timestep'] = a.n_timestep
     result, d = main(config, a.data_root, a.train_dir, chunk=a.chunk, threads=a.threads, n_epoch=a.epochs,
-                     grad_probe_every=a.grad_probe_every, loss=a.loss, impulses=a.impulses)
+                     grad_probe_every=a.grad_probe_every, loss=a.loss, impulses=a.impulses, probe_every=a.probe_every)
     print('best valid loss %.6f, checkpoints in %s' % (np.sqrt(result['best_valid_loss']), d))
 
 

@@ -654,10 +654,30 @@ int drp_train_grad_f64(drp_ctx* ctx, const float* states, const float* states_de
  * drp_gd_grad_f64's gen_s_delta on the double state, zero on rows n >= particle_nums[b]; for t > 0 the push's position share
  * (hard mask constant, soft mask and projections differentiated) joins d loss / d s_pred_{t-1} on real rows.  Everything else,
  * the one-shot contract included, is drp_train_grad_f64's.  DRP_ESTATE also without a camera; DRP_EINVAL also for a push of
- * zero length. */
+ * zero length.  (The Chamfer loss on the same pushes: drp_train_grad_f64_untracked below.) */
 int drp_train_grad_f64_actions(drp_ctx* ctx, const float* states, const float* actions, const float* attrs,
                                const int32_t* particle_nums, const float* particle_dens, int B, int N, int n_rollout,
                                double* loss_out, double* loss_terms_out, double* grad_out, double* grad_state_out);
+/* drp_train_grad_f64 (states_delta given, actions NULL) or drp_train_grad_f64_actions (actions given, states_delta NULL) with the
+ * Chamfer loss of drp_train_step_untracked in place of the MSE: the yardstick of drp_train_step_untracked's and of
+ * drp_train_step_actions' (with targets) gradients, row u1.  The term of (step t, sample b) is (fwd + bwd) / (n_rollout B) of
+ * drp_cloud_chamfer_f64 below between the DOUBLE prediction s_pred_t[b, :n_b] and targets[b, t, :target_nums[b, t]] widened
+ * exactly; it seeds the reverse pass with its gradient on real rows and +0.0 on padded ones, and everything behind the seed is
+ * drp_train_grad_f64's code.  The arg-mins are taken in double on the double prediction (lowest index on a tie) and are constants
+ * of the derivative: unlike the graph lists, which come from the fp32 build, the fp32 trainer's arg-mins are no input here.  A
+ * near-tie can therefore give the fp32 tape another partner than this call, which moves a gradient by a discrete amount and is
+ * no arithmetic error: margin_out [n_rollout][B] (nullable) is, per (step, sample), the smallest (second-best - best) squared
+ * distance over all its arg-mins of both directions -- 0 for a duplicate of a winner, +inf where every other cloud has one row.
+ * Of states only step 0 is read.  The same bits from run to run and under any workspace cap.  The one-shot contract is
+ * drp_train_grad_f64's; it is no dispatch variant.  Refusals: those of drp_train_grad_f64 / drp_train_grad_f64_actions, and
+ * DRP_EINVAL unless exactly one of states_delta and actions is given, for null targets or target_nums, M outside 1..4096, a
+ * target_nums entry outside 1..M.  A refused call leaves the context usable. */
+int drp_train_grad_f64_untracked(drp_ctx* ctx, const float* states, const float* states_delta /*[B][H][N][3] or NULL*/,
+                                 const float* actions /*[B][H][4] or NULL*/, const float* attrs, const int32_t* particle_nums,
+                                 const float* particle_dens, int B, int N, int n_rollout,
+                                 const float* targets /*[B][H][M][3]*/, const int32_t* target_nums /*[B][H]*/, int M,
+                                 double* loss_out, double* loss_terms_out, double* grad_out, double* grad_state_out,
+                                 double* margin_out /*[H][B], nullable*/);
 
 /* ---- symmetric squared Chamfer distance of two padded cloud batches and its gradient; no counterpart in the reference
  * (env/flex_rewards.py:9 imports pytorch3d's and never uses it).  p [B][N][3] with n_p[b] real rows, q [B][M][3] with n_q[b];
@@ -674,6 +694,16 @@ int drp_cloud_chamfer(drp_ctx* ctx, const float* p, const int32_t* n_p, const fl
                       int B, int N, int M, double* terms_out /*[B][2]: fwd, bwd*/,
                       float* grad_p_out /*[B][N][3], nullable; scale = 1*/,
                       int32_t* nn_pq_out /*[B][N], nullable*/, int32_t* nn_qp_out /*[B][M], nullable*/);
+/* drp_cloud_chamfer in float64, the yardstick of the metric: p and q widened exactly, a squared distance dx*dx + dy*dy + dz*dz
+ * in double in that order without fused multiply-add, the arg-mins taken in double (strict <, lowest index on a tie), sums and
+ * gradient in double in one fixed order, no atomics.  margin_out [B][2] (nullable): the smallest (second-best - best) squared
+ * distance over the real rows' arg-mins, p -> q then q -> p; 0 exactly for a duplicate of a winner, +inf where the other cloud
+ * has one row.  Contract and refusals are drp_cloud_chamfer's; a buffer of its own. */
+int drp_cloud_chamfer_f64(drp_ctx* ctx, const float* p, const int32_t* n_p, const float* q, const int32_t* n_q,
+                          int B, int N, int M, double* terms_out /*[B][2]: fwd, bwd*/,
+                          double* grad_p_out /*[B][N][3], nullable; scale = 1*/,
+                          int32_t* nn_pq_out /*[B][N], nullable*/, int32_t* nn_qp_out /*[B][M], nullable*/,
+                          double* margin_out /*[B][2]: p -> q, q -> p; nullable*/);
 
 #ifdef __cplusplus
 }

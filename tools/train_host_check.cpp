@@ -7,7 +7,10 @@
 //
 // It stages batches as train_stage_batch does -- the same copies, to the offsets tr_layout gives, into a heap block of exactly
 // TrArena::bytes -- so a block that overlaps the next one or runs past the end is the sanitizer's finding; the offsets are held
-// to the documented layout as well.  No device is touched.
+// to the documented layout as well.  The float64 yardsticks' upload (tr64_layout: train_grad_f64_body's one vector, with and
+// without target clouds) is staged the same way.  No device is touched.
+//
+//   train_host_check layout64 B H N M actions     prints tr64_layout's eight fields (4-byte words) and exits
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -85,12 +88,59 @@ static void stage(int B, int H, int N, int M, bool actions) {
     std::free(pin);
 }
 
-int main() {
+// the float64 yardsticks' batch as train_grad_f64_body stages it: one vector of exactly Tr64Arena::words 4-byte words
+static void stage64(int B, int H, int N, int M, bool actions) {
+    const Tr64Arena lay = tr64_layout(B, H, N, M, actions);
+    const size_t n_st = (size_t)B * (H + 1) * N * 3, n_imp = actions ? (size_t)B * H * 4 : (size_t)B * H * N * 3;
+    const size_t n_at_in = (size_t)B * (H + 1) * N, n_tg = (size_t)B * H * M * 3;
+    std::vector<float> states(n_st, 1.0f), imp(n_imp, 2.0f), attrs(n_at_in, 3.0f), dens(B, 4.0f), targets(n_tg, 6.0f);
+    std::vector<int32_t> nums(B, 5), tnums((size_t)B * H, 7);
+    // packed, in the documented order: every block ends where the next one starts
+    const size_t off[] = {lay.states, lay.sdelta, lay.attr, lay.dens, lay.nums, lay.targets, lay.tnums, lay.words};
+    const size_t len[] = {n_st, n_imp, (size_t)B * N, (size_t)B, (size_t)B, n_tg, M > 0 ? (size_t)B * H : 0};
+    for (int k = 0; k < 7; ++k) EXPECT(off[k] + len[k] == off[k + 1]);
+    EXPECT(lay.states == 0);
+    if (M == 0) EXPECT(lay.words == n_st + n_imp + (size_t)B * N + 2 * (size_t)B);      // drp_train_grad_f64's vector, restated
+    // train_grad_f64_body's copies into a block of exactly lay.words words
+    float* host = static_cast<float*>(std::malloc(lay.words * sizeof(float)));
+    std::memset(host, 0xff, lay.words * sizeof(float));
+    std::memcpy(host + lay.states, states.data(), (lay.sdelta - lay.states) * sizeof(float));
+    std::memcpy(host + lay.sdelta, imp.data(), (lay.attr - lay.sdelta) * sizeof(float));
+    for (int b = 0; b < B; ++b) std::memcpy(host + lay.attr + (size_t)b * N, attrs.data() + (size_t)b * (H + 1) * N, (size_t)N * sizeof(float));
+    std::memcpy(host + lay.dens, dens.data(), (size_t)B * sizeof(float));
+    std::memcpy(host + lay.nums, nums.data(), (size_t)B * sizeof(int32_t));
+    if (M > 0) {
+        std::memcpy(host + lay.targets, targets.data(), n_tg * sizeof(float));
+        std::memcpy(host + lay.tnums, tnums.data(), (size_t)B * H * sizeof(int32_t));
+    }
+    auto n = [&](size_t o, size_t i) { int32_t v; std::memcpy(&v, host + o + i, 4); return v; };
+    EXPECT(host[lay.states] == 1.0f && host[lay.sdelta - 1] == 1.0f);
+    EXPECT(host[lay.sdelta] == 2.0f && host[lay.attr - 1] == 2.0f);
+    EXPECT(host[lay.attr] == 3.0f && host[lay.dens - 1] == 3.0f);
+    EXPECT(host[lay.dens] == 4.0f && host[lay.nums - 1] == 4.0f);
+    EXPECT(n(lay.nums, 0) == 5 && n(lay.nums, B - 1) == 5);
+    if (M > 0) {
+        EXPECT(host[lay.targets] == 6.0f && host[lay.tnums - 1] == 6.0f);
+        EXPECT(n(lay.tnums, 0) == 7 && n(lay.tnums, (size_t)B * H - 1) == 7 && lay.tnums + (size_t)B * H == lay.words);
+    }
+    std::free(host);
+}
+
+int main(int argc, char** argv) {
+    if (argc == 7 && std::strcmp(argv[1], "layout64") == 0) {
+        const Tr64Arena a = tr64_layout(std::atoi(argv[2]), std::atoi(argv[3]), std::atoi(argv[4]), std::atoi(argv[5]), std::atoi(argv[6]) != 0);
+        std::printf("%zu %zu %zu %zu %zu %zu %zu %zu\n", a.states, a.sdelta, a.attr, a.dens, a.nums, a.targets, a.tnums, a.words);
+        return 0;
+    }
     // odd sizes (no block a multiple of 16 bytes), one sample, the reference's batch, a large one
     const int shapes[][4] = {{1, 1, 1, 0}, {1, 1, 5, 3}, {3, 3, 24, 0}, {3, 3, 23, 17}, {2, 5, 11, 0}, {4, 5, 300, 0}, {4, 5, 300, 300},
                              {7, 2, 301, 299}, {32, 5, 300, 0}, {2, 64, 9, 1}};
     for (const auto& s : shapes)
-        for (int actions = 0; actions < 2; ++actions) stage(s[0], s[1], s[2], s[3], actions != 0);
+        for (int actions = 0; actions < 2; ++actions) {
+            stage(s[0], s[1], s[2], s[3], actions != 0);
+            stage64(s[0], s[1], s[2], s[3], actions != 0);
+        }
+    stage64(1, 1, 4096, 4096, false);                            // the largest clouds of one (sample, step)
 
     // the push check, with the demo camera's map (x, z, -y + 18 scaled by 1 / 24: a camera that looks straight down)
     const float m[12] = {1, 0, 0, 0, 0, 0, 1, 0, 0, -1, 0, 18};
