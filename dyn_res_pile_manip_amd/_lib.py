@@ -24,7 +24,7 @@ DIST_TRANSFORMS = {'cv5': 0, 'exact': 1}
 RGR_REGRESSOR = 1           # DRP_RGR_REGRESSOR: n_out of the MPCResRgrNoPool head
 RGR_CLASSIFIER = 6          # DRP_RGR_CLASSIFIER: n_out of the MPCResCls head
 RGR_BMAX = 64
-PD_BMAX = 1024              # drp_ptcl_dataset_batch: samples per call
+PD_BMAX = 1024              # drp_ptcl_dataset_batch: samples per call; drp_ptcl_dataset_frames: images (B * T) per call
 PD_CAP = 4096               # particles per sample
 NOISE_TYPES = {'normal': 0, 'uniform': 1, 'total_rand': 2}
 ENGINES = {'valu': ENGINE_VALU, 'mfma': ENGINE_MFMA, 'split': ENGINE_SPLIT, 'fused': ENGINE_FUSED, 'lite': ENGINE_LITE}
@@ -176,6 +176,11 @@ SIGNATURES = {
                                               ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), c_double_p,
                                               ctypes.POINTER(ctypes.c_int32), ctypes.c_int, c_float_p, c_float_p,
                                               ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int)]),
+    'drp_ptcl_dataset_frames': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint16),
+                                               ctypes.c_int, ctypes.c_int, ctypes.c_double, c_double_p, c_double_p,
+                                               ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                               ctypes.POINTER(ctypes.c_int32), ctypes.c_int, c_float_p,
+                                               ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int)]),
     'drp_ptcl_dataset_time': (ctypes.c_int, [ctypes.c_void_p, c_float_p]),
     'drp_forward_f64': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p,
                                        c_int16_p, c_uint8_p, ctypes.c_int, ctypes.c_int, c_double_p]),

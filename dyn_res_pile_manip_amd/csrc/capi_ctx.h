@@ -298,9 +298,11 @@ struct drp_ctx {
     // GNN training batches from recorded episodes (capi_ptcl_dataset.h, row x4): workspaces of its own
     DevBuf pd_in, pd_blk, pd_meta, pd_pcd, pd_dist, pd_chosen, pd_rec, pd_near, pd_out;
     PinBuf pd_pin;                  // pinned staging: the upload arena, then the counts, then the download
-    Event pd_ev[7];                 // stage boundaries of the last drp_ptcl_dataset_batch (drp_ptcl_dataset_time)
+    Event pd_ev[7];                 // stage boundaries of the last drp_ptcl_dataset_batch / _frames (drp_ptcl_dataset_time)
     bool pd_timed = false;
-    int pd_lastB = 0, pd_nmax = 0;  // shapes of the last batch (debug taps)
+    int pd_lastB = 0, pd_nmax = 0;  // shapes of the last batch (debug taps); for a frames call pd_lastB = B * T images
+    int pd_kind = 0;                // whose bytes the shared pd_* buffers hold: 0 nobody's (a call is under way or failed), 1
+                                    // drp_ptcl_dataset_batch ("pd_*" taps), 2 drp_ptcl_dataset_frames ("pdf_*" taps)
 
     // float64 one-step evaluation and the accuracy probe (k_prop_f64.h, capi_f64.h): weights, staging and workspaces of its own,
     // nothing shared with the sessions' state -- a *_f64 call or a probe ends no session

@@ -192,11 +192,19 @@ long drp_debug_fetch(drp_ctx* c, const char* name, void* out, size_t out_bytes) 
     }
     // the GNN dataset's intermediates of its last batch: foreground counts [B] and sampler picks [B][4097] (int32),
     // recentered points [B][n_max][3] (float64), nearest frame-0 particles [B][n_max] (int32)
-    else if (!strcmp(name, "pd_nfg")) {
-        b = &c->pd_meta; part = true; view = ptr<long long>(c->pd_meta) + c->pd_lastB; view_cap = c->pd_meta.cap; bytes = (size_t)c->pd_lastB * 4;
-    } else if (!strcmp(name, "pd_chosen")) { b = &c->pd_chosen; bytes = (size_t)c->pd_lastB * (PD_CAP + 1) * 4; }
-    else if (!strcmp(name, "pd_recenter")) { b = &c->pd_rec; bytes = (size_t)c->pd_lastB * c->pd_nmax * 3 * 8; }
-    else if (!strcmp(name, "pd_nearest")) { b = &c->pd_near; bytes = (size_t)c->pd_lastB * c->pd_nmax * 4; }
+    // (c->pd_kind 1); "pdf_*": the same buffers after a drp_ptcl_dataset_frames (c->pd_kind 2), [B * T] images in (b, t) order.
+    // The two calls share the buffers: a tap of the call that did not run last is not populated
+    else if (!strncmp(name, "pd_", 3) || !strncmp(name, "pdf_", 4)) {
+        const bool frames = name[2] == 'f';
+        const char* what = name + (frames ? 4 : 3);
+        const size_t nb = c->pd_kind == (frames ? 2 : 1) ? (size_t)c->pd_lastB : 0;      // 0: refused below as not populated
+        if (!strcmp(what, "nfg")) {
+            b = &c->pd_meta; part = true; view = ptr<long long>(c->pd_meta) + nb; view_cap = c->pd_meta.cap; bytes = nb * 4;
+        } else if (!strcmp(what, "chosen")) { b = &c->pd_chosen; bytes = nb * (PD_CAP + 1) * 4; }
+        else if (!strcmp(what, "recenter")) { b = &c->pd_rec; bytes = nb * c->pd_nmax * 3 * 8; }
+        else if (!frames && !strcmp(what, "nearest")) { b = &c->pd_near; bytes = nb * c->pd_nmax * 4; }
+        else return fail(c, DRP_EINVAL, "unknown buffer '%s'", name);
+    }
     else return fail(c, DRP_EINVAL, "unknown buffer '%s'", name);
     // a GD session keeps every step's impulses and lists in its tape, not in the step workspace: the last step's
     if (c->gd_on && c->gd_H > 0 && bn == (size_t)c->gd_B * c->gd_N) {

@@ -4,6 +4,9 @@
 //   -> fps_rad (utils.py:438-449) -> recenter in float64 (utils.py:468-477, :101)
 //   -> nearest frame-0 particle (KDTree.query(k=1), :108-109) -> states / states_delta (:114-194)
 //   -> the zero-padded float32 layout of collate_fn (train/train_gnn_dyn.py:20-45).
+// Untracked samples straight from the depth frames (drp_ptcl_dataset_frames): the same chain on every frame of a window.  The
+// count / scan / compact / meta / fps_rad / recenter kernels below index images, not samples, so that call launches them on
+// the B * T images in (b, t) order with radius[b][t] and init_idx[b][t]; only the pack (k_pd_pack_frames) is its own.
 // Everything the reference computes in float64 stays float64, in its evaluation order; no FMA contraction
 // (-ffp-contract=off).  No atomics: every output has one order of evaluation, the same in any batch.
 #pragma once
@@ -208,4 +211,15 @@ k_pd_pack(const int* __restrict__ nearest, const int* __restrict__ counts, int n
     const double te = ((e[0] - P[0]) * dir[0] + (e[1] - P[1]) * dir[1]) + (e[2] - P[2]) * dir[2];
 #pragma unroll
     for (int a = 0; a < 3; ++a) dout[a] = (float)(((te * dir[a]) * lm) * wm);
+}
+
+// clouds [B * T][n_max][3] = the recentered points of every (sample, frame) image rounded once to float32
+// (torch.FloatTensor), +0.0f beyond the image's count.  grid (ceil(n_max/256), B * T)
+__global__ void __launch_bounds__(256)
+k_pd_pack_frames(const double* __restrict__ rec, const int* __restrict__ counts, int n_max, float* __restrict__ clouds) {
+    const int img = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n_max) return;
+    const size_t o = ((size_t)img * n_max + j) * 3;
+    if (j >= counts[img]) { clouds[o] = clouds[o + 1] = clouds[o + 2] = 0.0f; return; }
+    clouds[o] = (float)rec[o]; clouds[o + 1] = (float)rec[o + 1]; clouds[o + 2] = (float)rec[o + 2];
 }

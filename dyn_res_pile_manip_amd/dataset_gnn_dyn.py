@@ -9,6 +9,7 @@ train_gnn_dyn.py.  Same name and arguments, so a script swaps one import:
                                                           particle_den, color_imgs), numpy
   ParticleDataset.get_batch(indices)              collate_fn([ds[i] for i in indices]) in ONE device call
   DeviceLoader(dataset, batch_size, shuffle)      the DataLoader of train/train_gnn_dyn.py:94-100
+  DepthDataset(data_dir, config, phase, cam)      untracked samples from the depth PNGs and actions.p alone (no counterpart)
 
 What the reference computes per sample -- depth2fgpcd, fps_rad (a Python loop over the whole cloud), recenter (a dense
 float64 distance matrix), the KDTree query, the gather and the push formula -- runs in `drp_ptcl_dataset_batch` on the
@@ -20,6 +21,11 @@ Random draws are the reference's calls in its order on numpy's global generator:
 then np.random.randint(n_fg).  Under the same seed the same samples come out.  One deliberate difference: DeviceLoader
 draws from ONE numpy stream in sample order, as DataLoader(num_workers=0) does; the reference's forked workers each draw
 from a copy of the parent's global numpy state.
+
+DepthDataset is the data path of a recorded robot episode, which holds depth images and pushes and no simulator particles: every
+frame of a window goes through depth2fgpcd -> fps_rad -> recenter (`drp_ptcl_dataset_frames`), frame 0 is the state, frames
+1..T-1 are the Chamfer targets.  Its draws per sample: np.random.uniform(15, 6500), then np.random.randint(n_fg_t) for the frames
+t = 0..T-1 in order, so under one seed the first sample's frame-0 cloud is the one ParticleDataset samples.
 """
 import os
 import pickle
@@ -98,6 +104,8 @@ def read_color(path):
 class ParticleDataset(object):
     """dataset/dataset_gnn_dyn.py:27-201 with the per-sample work on the device.  `cam` = (cam_params [fx, fy, cx, cy],
     cam_extrinsic 4x4) as FlexEnv gives them; engine: the context to run on (default: the process's one)."""
+
+    default_chunk = 64           # samples per device call of a DeviceLoader
 
     def __init__(self, data_dir, config, phase, cam, engine=None, load_color=False):
         self.config = config
@@ -190,6 +198,21 @@ class ParticleDataset(object):
             [s['n_fg'] for s in samples], np.stack([s['push'] for s in samples]),
             episode=[s['episode'] for s in samples])
 
+    def tuples(self, samples, draws):
+        """one device call -> the per-sample tuples of __getitem__ (views of the call's outputs), in order"""
+        states, sdelta, counts = self.run(samples, draws)
+        T = states.shape[1]
+        return [(states[j, :, :int(counts[j])], sdelta[j, :, :int(counts[j])], np.zeros((T, int(counts[j])), np.float32),
+                 int(counts[j]), draws[j][0], s['color']) for j, s in enumerate(samples)]
+
+    @staticmethod
+    def collate(data, actions):
+        """per-sample tuples and their raw pushes [T-1, 4] -> the batch a loader yields (collate_fn's tuple is the reference's:
+        the pushes are attached)"""
+        out = collate_fn(data)
+        out.actions = np.stack(actions).astype(np.float32)
+        return out
+
     def __getitem__(self, idx):
         sample = self.load(idx)
         den, init = self.draw(sample)
@@ -217,6 +240,94 @@ class ParticleDataset(object):
         batch.offsets = np.concatenate([[0], np.cumsum(counts.astype(np.int64))])
         batch.actions = np.stack([s['actions'] for s in samples]).astype(np.float32)
         return batch
+
+
+class DepthDataset(ParticleDataset):
+    """Untracked training samples straight from recorded depth frames: the phases, `__len__` and `locate` of ParticleDataset, but
+    a sample is read from the T = n_his + n_rollout depth PNGs of its window and actions.p alone -- no `*_particles.npy`, no
+    colour image.  Every frame becomes a cloud by the reference's own chain depth2fgpcd -> fps_rad -> recenter
+    (dataset/dataset_gnn_dyn.py:97-101) on the device (Engine.ptcl_dataset_frames): frame 0 at radius 1/sqrt(den), the frames
+    after it, the Chamfer targets, at 1/sqrt(den * target_den_scale).  Batches are collate_untracked's and carry
+    `depth_only = True`: there are no recorded impulses, so they train with loss='chamfer', impulses='actions' only."""
+
+    default_chunk = 16           # 16 samples x 6 frames at 720 x 720 upload 100 MB and hold 0.4 GB of clouds on the device
+
+    def __init__(self, data_dir, config, phase, cam, engine=None, target_den_scale=1.0):
+        ParticleDataset.__init__(self, data_dir, config, phase, cam, engine=engine)
+        if not (float(target_den_scale) > 0.0 and np.isfinite(target_den_scale)):
+            raise ValueError('target_den_scale must be positive and finite, got %r' % (target_den_scale,))
+        self.target_den_scale = float(target_den_scale)
+
+    def load(self, idx):
+        """The files of sample idx, decoded (thread-safe, no random draw): the T depth frames uint16 [T, h, w], their
+        foreground counts [T], the raw pushes [T-1, 4]."""
+        ep, t0 = self.locate(idx)
+        T = self.n_his + self.n_roll
+        with open(self._path(ep, 'actions.p'), 'rb') as fp:
+            actions = pickle.load(fp)
+        depth = np.stack([read_depth(self._path(ep, '%d_depth.png' % i)) for i in range(t0, t0 + T)])
+        return {'episode': ep, 'depth': depth, 'n_fg': [count_fg(d, self.global_scale) for d in depth],
+                'actions': np.asarray([actions[i] for i in range(t0, t0 + T - 1)], dtype=np.float64).reshape(T - 1, 4),
+                'color': None}
+
+    @staticmethod
+    def draw(sample):
+        """the draws of one loaded sample: particle_den as ParticleDataset.draw, then every frame's sampler start in frame
+        order -> (den, [init_0 .. init_T-1]).  A frame without foreground draws no start (the device refuses it)."""
+        den = np.random.uniform(PARTICLE_DEN_MIN, PARTICLE_DEN_MAX)
+        return den, [np.random.randint(n) if n > 0 else 0 for n in sample['n_fg']]
+
+    def radii(self, den, T):
+        """fps_rad's radius of every frame of a sample: [T] float64"""
+        r = np.full((T,), 1 / np.sqrt(den * self.target_den_scale), np.float64)
+        r[0] = 1 / np.sqrt(den)
+        return r
+
+    def run(self, samples, draws):
+        """one device call for loaded samples and their draws -> (clouds [B,T,n_max,3], counts [B,T])"""
+        depth = np.stack([s['depth'] for s in samples])
+        return self.engine.ptcl_dataset_frames(
+            depth, self.global_scale, self.cam_params, np.stack([self.radii(d[0], depth.shape[1]) for d in draws]),
+            [d[1] for d in draws], [s['n_fg'] for s in samples], episode=[s['episode'] for s in samples])
+
+    def tuples(self, samples, draws):
+        """one device call -> the per-sample tuples of __getitem__ (copies), in order"""
+        clouds, counts = self.run(samples, draws)
+        T = clouds.shape[1]
+        out = []
+        for j in range(len(samples)):
+            n = int(counts[j, 0])
+            states = np.zeros((T, n, 3), np.float32)
+            states[0] = clouds[j, 0, :n]
+            out.append((states, np.zeros((T - 1, n, 3), np.float32), np.zeros((T, n), np.float32), n, draws[j][0], None,
+                        [clouds[j, t, :int(counts[j, t])].copy() for t in range(1, T)]))
+        return out
+
+    @staticmethod
+    def collate(data, actions):
+        from .train_gnn_dyn import collate_untracked
+        out = collate_untracked(data, actions=np.stack(actions))
+        out.depth_only = True
+        return out
+
+    def __getitem__(self, idx):
+        """-> (states [T, n, 3] with step 0 filled, states_delta zeros, attrs zeros, n, particle_den, None, targets: the T-1
+        clouds [m_t, 3] of the frames after the first): what collate_untracked takes"""
+        sample = self.load(idx)
+        return self.tuples([sample], [self.draw(sample)])[0]
+
+    def get_batch(self, indices, pool=None):
+        """collate_untracked([self[i] for i in indices]) from the same numpy state, in one device call, with the raw pushes as
+        `.actions` and `depth_only = True`; `pool`: an executor for the decoding."""
+        indices = [int(i) for i in indices]
+        if not indices:
+            raise ValueError('get_batch needs at least one index')
+        T = self.n_his + self.n_roll
+        if len(indices) * T > 1024:
+            raise ValueError('get_batch takes at most 1024 frames per call, got %d samples of %d' % (len(indices), T))
+        samples = list(pool.map(self.load, indices)) if pool is not None else [self.load(i) for i in indices]
+        draws = [self.draw(s) for s in samples]
+        return self.collate(self.tuples(samples, draws), [s['actions'] for s in samples])
 
 
 def drop_correspondence(sample, rng, keep=(0.6, 1.0)):
@@ -279,11 +390,14 @@ class DeviceLoader(object):
     The sample order is torch's: a DataLoader over the indices (RandomSampler / SequentialSampler) consumes torch's
     generator exactly as the reference's does.  `chunk` samples go to the device per call (fps_rad runs one workgroup per
     sample: a chunk fills the CUs) and come back as batches of batch_size; the chunk size does not change the output.
-    Decoding runs on `threads` (at most 16) threads, one chunk ahead of the device."""
+    Decoding runs on `threads` (at most 16) threads, one chunk ahead of the device.  chunk None: the dataset's default_chunk
+    (ParticleDataset 64; DepthDataset, whose samples are T images each, 16).  A DepthDataset's batches are collate_untracked's."""
 
-    def __init__(self, dataset, batch_size, shuffle=False, chunk=64, threads=8, drop_last=False):
+    def __init__(self, dataset, batch_size, shuffle=False, chunk=None, threads=8, drop_last=False):
         if int(batch_size) < 1:
             raise ValueError('batch_size must be >= 1, got %r' % (batch_size,))
+        if chunk is None:
+            chunk = dataset.default_chunk
         if int(chunk) < 1 or int(chunk) > 1024:
             raise ValueError('chunk must be in 1..1024, got %r' % (chunk,))
         if int(threads) < 1 or int(threads) > MAX_THREADS:
@@ -311,7 +425,7 @@ class DeviceLoader(object):
         chunks = [order[k:k + self.chunk] for k in range(0, len(order), self.chunk)]
         ds = self.dataset
         done = []                    # per-sample tuples, in sample order
-        done_act = []                # their raw pushes [T-1, 4]: attached to the collated batch (collate_fn's tuple is the reference's)
+        done_act = []                # their raw pushes [T-1, 4]: attached to the collated batch
         bi = 0
         with ThreadPoolExecutor(max_workers=self.threads) as pool:
             pending = [pool.submit(ds.load, i) for i in chunks[0]] if chunks else []
@@ -319,17 +433,10 @@ class DeviceLoader(object):
                 samples = [f.result() for f in pending]
                 pending = [pool.submit(ds.load, i) for i in chunks[k + 1]] if k + 1 < len(chunks) else []
                 draws = [ds.draw(s) for s in samples]
-                states, sdelta, counts = ds.run(samples, draws)
-                T = states.shape[1]
-                for j, s in enumerate(samples):
-                    n = int(counts[j])
-                    done.append((states[j, :, :n], sdelta[j, :, :n], np.zeros((T, n), np.float32), n, draws[j][0],
-                                 s['color']))
-                    done_act.append(s['actions'])
+                done.extend(ds.tuples(samples, draws))
+                done_act.extend(s['actions'] for s in samples)
                 while bi < len(batches) and len(done) >= len(batches[bi]):
                     nb = len(batches[bi])
-                    out = collate_fn(done[:nb])
-                    out.actions = np.stack(done_act[:nb]).astype(np.float32)
-                    yield out
+                    yield ds.collate(done[:nb], done_act[:nb])
                     done, done_act = done[nb:], done_act[nb:]
                     bi += 1

@@ -1123,8 +1123,47 @@ class Engine(object):
         return (states[:B * T * nm * 3].reshape(B, T, nm, 3), sdelta[:B * (T - 1) * nm * 3].reshape(B, T - 1, nm, 3),
                 counts)
 
+    def ptcl_dataset_frames(self, depth, global_scale, cam_params, radius, init_idx, n_fg, episode=None, n_cap=L.PD_CAP):
+        """depth2fgpcd -> fps_rad -> recenter on every frame of B windows of T depth frames (drp_ptcl_dataset_frames): untracked
+        training samples without a particle file.  depth [B,T,h,w] uint16; radius, init_idx, n_fg [B,T] (fps_rad's radius, the
+        sampler's start and the host's foreground count of every frame); B * T <= 1024.
+        -> (clouds [B,T,n_max,3] f32, +0.0 beyond each count; counts [B,T] int32)"""
+        depth = np.ascontiguousarray(depth, dtype=np.uint16)
+        if depth.ndim != 4:
+            raise ValueError('depth must be [B, T, h, w], got %s' % (depth.shape,))
+        B, T, h, w = depth.shape
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        radius, init, nfg = _f64(radius), i32(init_idx), i32(n_fg)
+        for name, a in (('radius', radius), ('init_idx', init), ('n_fg', nfg)):
+            if a.shape != (B, T):
+                raise ValueError('%s must be [B, T] = %s, got %s' % (name, (B, T), a.shape))
+        ep = None if episode is None else i32(episode).reshape(B)
+        cam = _f64(cam_params).reshape(4)
+        n_cap = int(n_cap)
+        # np.empty: only the pages the call writes (B * T * n_max * 3 floats) are ever touched
+        clouds = np.empty((B * T * max(n_cap, 0) * 3,), np.float32)
+        counts = np.empty((B, T), np.int32)
+        n_max = ctypes.c_int()
+        self._pdf_shape = (0, 0, 0)
+        self._ck(self.lib.drp_ptcl_dataset_frames(
+            self.h, B, T, depth.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)), h, w, float(global_scale), _dp(cam),
+            _dp(radius), ip(init), ip(nfg), None if ep is None else ip(ep), n_cap, _fp(clouds), ip(counts),
+            ctypes.byref(n_max)))
+        nm = n_max.value
+        self._pdf_shape = (B, T, nm)
+        return clouds[:B * T * nm * 3].reshape(B, T, nm, 3), counts
+
+    def ptcl_dataset_frames_tap(self, name):
+        """intermediates of the last ptcl_dataset_frames: 'nfg' [B,T], 'chosen' [B,T,4097], 'recenter' [B,T,n_max,3] float64.
+        Refused (DrpError) when a ptcl_dataset_batch has run since: the two calls share their buffers"""
+        B, T, nm = getattr(self, '_pdf_shape', (0, 0, 0))
+        shape, dt = {'nfg': ((B, T), np.int32), 'chosen': ((B, T, L.PD_CAP + 1), np.int32),
+                     'recenter': ((B, T, nm, 3), np.float64)}[name]
+        return self.debug_fetch('pdf_' + name, shape, dt)
+
     def ptcl_dataset_time(self):
-        """device ms of the last ptcl_dataset_batch by stage: {'upload', 'compaction', 'fps_rad', 'recenter', 'track_pack',
+        """device ms of the last ptcl_dataset_batch / ptcl_dataset_frames (there 'track_pack' is the pack alone) by stage: {'upload', 'compaction', 'fps_rad', 'recenter', 'track_pack',
         'download'}"""
         ms = np.empty((6,), np.float32)
         self._ck(self.lib.drp_ptcl_dataset_time(self.h, _fp(ms)))

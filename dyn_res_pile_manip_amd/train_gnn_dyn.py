@@ -30,6 +30,8 @@ class PaddedBatch(tuple):
     offsets = None          # [B+1] running particle offset of each sample in the concatenated cloud
     actions = None          # [B, n_rollout, 4] float32, the raw pushes (sx, sy, ex, ey) of the samples' steps where the loader has
                             # them (dataset_gnn_dyn.get_batch / DeviceLoader): what impulses='actions' trains on
+    depth_only = False      # True: the batch comes from depth frames alone (dataset_gnn_dyn.DepthDataset): states has only step 0
+                            # and states_delta is zeros, so it trains with loss='chamfer', impulses='actions' and nothing else
 
 
 def collate_fn(data):
@@ -94,6 +96,30 @@ class DeviceAdam(object):
 
 LOSSES = ('mse', 'chamfer')
 IMPULSES = ('data', 'actions')
+DATA = ('particles', 'depth')
+
+
+def check_depth_only(data, loss, impulses):
+    """a batch made from depth frames alone has no tracked targets and no recorded impulses: anything but the Chamfer loss through
+    the push would train on zeros"""
+    if getattr(data, 'depth_only', False) and not (loss == 'chamfer' and impulses == 'actions'):
+        raise ValueError('a depth-only batch (DepthDataset) holds no tracked states and no impulses: it needs loss=\'chamfer\' and '
+                         'impulses=\'actions\', got loss=%r, impulses=%r' % (loss, impulses))
+
+
+def resolve_data_options(data, loss, impulses):
+    """main()'s / the command line's data, loss and impulses -> (loss, impulses).  None = not given: 'mse' and 'data' for
+    data='particles'; data='depth' implies 'chamfer' and 'actions' and refuses anything else."""
+    if data not in DATA:
+        raise ValueError('data must be one of %s, got %r' % (DATA, data))
+    if data == 'depth':
+        if loss not in (None, 'chamfer'):
+            raise ValueError('data=\'depth\' trains on untracked clouds: loss=%r contradicts the loss=\'chamfer\' it implies' % (loss,))
+        if impulses not in (None, 'actions'):
+            raise ValueError('data=\'depth\' has no recorded impulses: impulses=%r contradicts the impulses=\'actions\' it implies'
+                             % (impulses,))
+        return 'chamfer', 'actions'
+    return 'mse' if loss is None else loss, 'data' if impulses is None else impulses
 
 
 def batch_actions(data):
@@ -108,13 +134,15 @@ def batch_actions(data):
 def run_batch(model, optimizer, data, phase='train', n_rollout=None, loss='mse', impulses='data'):
     """The loop body at train/train_gnn_dyn.py:159-210 -> loss (python float, what loss.item() is there).  loss='chamfer': `data`
     is collate_untracked's (targets and target_nums behind the six fields) and each step's term is the Chamfer distance to its
-    target cloud (Engine.train_step_untracked).  impulses='actions': every step's impulse is computed from the batch's pushes
+    target cloud (Engine.train_step_untracked).  A batch marked depth_only (DepthDataset) is refused (ValueError) unless
+    loss='chamfer' and impulses='actions'.  impulses='actions': every step's impulse is computed from the batch's pushes
     (`data.actions`) on the state the step reads instead of taken from states_delta (Engine.train_step_actions; the engine's
     camera must be set)."""
     if loss not in LOSSES:
         raise ValueError('loss must be one of %s, got %r' % (LOSSES, loss))
     if impulses not in IMPULSES:
         raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
+    check_depth_only(data, loss, impulses)
     states, states_delta, attrs, particle_nums, particle_dens = [data[i] for i in range(5)]
     actions = batch_actions(data) if impulses == 'actions' else None
     states = _np(states)
@@ -160,6 +188,7 @@ def probe_batch(model, data, impulses='data', loss='mse'):
         raise ValueError('loss must be one of %s, got %r' % (LOSSES, loss))
     if impulses not in IMPULSES:
         raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
+    check_depth_only(data, loss, impulses)
     states, states_delta, attrs, particle_nums, particle_dens = [data[i] for i in range(5)]
     if hasattr(model, '_claim'):
         model._claim()
@@ -255,8 +284,8 @@ def set_seed(seed):
     random.seed(seed)
 
 
-def main(config, data_root=None, train_dir=None, cam=None, chunk=64, threads=8, n_epoch=None, engine=None, grad_probe_every=0,
-         loss='mse', impulses='data', probe_every=0):
+def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8, n_epoch=None, engine=None, grad_probe_every=0,
+         loss=None, impulses=None, probe_every=0, data='particles', target_den_scale=1.0):
     """The file-level part of train/train_gnn_dyn.py:train() (:45-130, :196-228): seed, the log directory with config.yaml
     and log.txt, the 'train' / 'valid' ParticleDatasets and their DeviceLoaders, a fresh model (torch.nn.Linear's default
     initialisation) or the resumed checkpoint, net_epoch_%d_iter_%d.pth every ckp_per_iter training batches and
@@ -265,12 +294,17 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=64, threads=8, 
     the directory.  loss='chamfer': the recorded episodes' correspondence is dropped (dataset_gnn_dyn.drop_correspondence on
     every sample, seeded by train.random_seed) and the model is trained on the Chamfer distance to the untracked clouds.
     impulses='actions': the engine's camera is set from the dataset's extrinsics and global_scale and every step's impulse comes
-    from the recorded push on the state the step reads (train).  probe_every: train's."""
+    from the recorded push on the state the step reads (train).  probe_every: train's.
+    data='depth': the episodes need only their depth PNGs and actions.p (a recorded robot episode): the datasets are
+    DepthDatasets (every frame of a window sampled from its depth image on the device, the later frames at target_den_scale
+    times the state's density), which implies loss='chamfer' and impulses='actions'; a contradicting value is refused.  loss /
+    impulses None: 'mse' / 'data', or what data implies.  chunk None: the dataset's default (64 samples; 16 for data='depth')."""
     import time
     import yaml
     from . import synthetic, weights
-    from .dataset_gnn_dyn import DeviceLoader, ParticleDataset, UntrackedLoader
+    from .dataset_gnn_dyn import DepthDataset, DeviceLoader, ParticleDataset, UntrackedLoader
     from .gnn_dyn import PropNetDiffDenModel
+    loss, impulses = resolve_data_options(data, loss, impulses)
     check_probe_options(loss, grad_probe_every, probe_every)
     tc = config['train']
     resume = tc['particle'].get('resume', {'active': False, 'epoch': 0, 'iter': 0})
@@ -285,10 +319,14 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=64, threads=8, 
         yaml.safe_dump(config, f)
     log_name = 'log.txt' if not resume['active'] else 'log_resume_epoch_%d_iter_%d.txt' % (resume['epoch'], resume['iter'])
     data_root = data_root if data_root is not None else tc['data_root']
-    datasets = {ph: ParticleDataset(data_root, config, ph, cam, engine=engine) for ph in ('train', 'valid')}
+    if data == 'depth':
+        datasets = {ph: DepthDataset(data_root, config, ph, cam, engine=engine, target_den_scale=target_den_scale)
+                    for ph in ('train', 'valid')}
+    else:
+        datasets = {ph: ParticleDataset(data_root, config, ph, cam, engine=engine) for ph in ('train', 'valid')}
     loaders = {ph: DeviceLoader(datasets[ph], tc['batch_size'], shuffle=(ph == 'train'), chunk=chunk, threads=threads)
                for ph in ('train', 'valid')}
-    if loss == 'chamfer':
+    if loss == 'chamfer' and data != 'depth':
         loaders = {ph: UntrackedLoader(loaders[ph], seed=tc['random_seed'] + k, reseed=(ph == 'valid'))
                    for k, ph in enumerate(('train', 'valid'))}
     model = PropNetDiffDenModel(config, engine=engine)
@@ -334,18 +372,27 @@ def _cli(argv=None):
     ap.add_argument('--n-episode', type=int, help='override dataset.n_episode')
     ap.add_argument('--n-timestep', type=int, help='override dataset.n_timestep')
     ap.add_argument('--epochs', type=int, help='override train.n_epoch')
-    ap.add_argument('--chunk', type=int, default=64, help='samples per device call')
+    ap.add_argument('--chunk', type=int, default=None, help='samples per device call (default 64; 16 with --data depth)')
     ap.add_argument('--threads', type=int, default=8, help='decoding threads (at most 16)')
     ap.add_argument('--grad-probe-every', type=int, default=0,
                     help='hold every k-th training batch\'s gradients against float64 before its update (0: never)')
     ap.add_argument('--probe-every', type=int, default=0,
                     help='the same for every --loss and --impulses; with --loss chamfer the log line carries the float64 side\'s '
                          'smallest arg-min margin')
-    ap.add_argument('--loss', choices=LOSSES, default='mse',
-                    help='chamfer: drop the recorded correspondence and train on the Chamfer distance to the untracked clouds')
-    ap.add_argument('--impulses', choices=IMPULSES, default='data',
-                    help='actions: compute every step\'s impulse from the recorded push on the state the model predicted')
+    ap.add_argument('--data', choices=DATA, default='particles',
+                    help='depth: episodes of depth PNGs and actions.p alone; every frame of a window is sampled from its depth '
+                         'image on the device.  Implies --loss chamfer --impulses actions')
+    ap.add_argument('--target-den-scale', type=float, default=1.0,
+                    help='--data depth: the target frames are sampled at this multiple of the state\'s particle density')
+    ap.add_argument('--loss', choices=LOSSES, default=None,
+                    help='(default mse) chamfer: drop the recorded correspondence and train on the Chamfer distance to the untracked clouds')
+    ap.add_argument('--impulses', choices=IMPULSES, default=None,
+                    help='(default data) actions: compute every step\'s impulse from the recorded push on the state the model predicted')
     a = ap.parse_args(argv)
+    try:
+        resolve_data_options(a.data, a.loss, a.impulses)
+    except ValueError as e:
+        ap.error(str(e))
     config = default_config()
     if a.config:
         with open(a.config) as f:
@@ -355,7 +402,8 @@ def _cli(argv=None):
     if a.n_timestep is not None:
         config['dataset']['n_timestep'] = a.n_timestep
     result, d = main(config, a.data_root, a.train_dir, chunk=a.chunk, threads=a.threads, n_epoch=a.epochs,
-                     grad_probe_every=a.grad_probe_every, loss=a.loss, impulses=a.impulses, probe_every=a.probe_every)
+                     grad_probe_every=a.grad_probe_every, loss=a.loss, impulses=a.impulses, probe_every=a.probe_every,
+                     data=a.data, target_den_scale=a.target_den_scale)
     print('best valid loss %.6f, checkpoints in %s' % (np.sqrt(result['best_valid_loss']), d))
 
 

@@ -521,8 +521,30 @@ int drp_ptcl_dataset_batch(drp_ctx* ctx, int B, const uint16_t* depth, int h, in
                            const double T_cam[16], int T, const int32_t* n_ptcl, const float* particles, const double* radius,
                            const int32_t* init_idx, const int32_t* n_fg_host, const double* push, const int32_t* episode,
                            int n_cap, float* states_out, float* sdelta_out, int32_t* counts_out, int* n_max_out);
-/* Device time of the last completed drp_ptcl_dataset_batch by stage (HIP events): ms_out [6] = upload | compaction |
- * fps_rad | recenter | track + pack | download.  DRP_ESTATE before the first. */
+/* Untracked samples straight from recorded depth frames (row x4 / u1): the chain depth PNG / (global_scale * 1000.0) ->
+ * depth2fgpcd -> fps_rad -> recenter (dataset/dataset_gnn_dyn.py:97-101, utils.py:491-506, 438-449, 468-477) on EVERY frame of B
+ * windows of T frames, T >= 1 and 1 <= B * T <= 1024 images per call; no particle file is involved.  Frame 0 of a window is
+ * the state a Chamfer + actions training step starts from, frames 1..T-1 are its target clouds, each with its own count.
+ * Inputs: depth [B][T][h][w] uint16, cam [fx, fy, cx, cy]; per (sample, frame): radius[b][t] (fps_rad's; recenter uses r =
+ * min(0.02, 0.5 * radius[b][t])), init_idx[b][t] = the sampler's start (numpy's randint(n_fg)), n_fg_host[b][t] = the foreground
+ * count the host drew it from (the device's must agree); episode [B] (nullable) = the episode numbers errors name.  Outputs:
+ * clouds [B][T][n_max][3] float32 = each recentered float64 point rounded once, +0.0f beyond counts_out[b][t] (room for n_cap
+ * particle slots per frame); *n_max_out = the largest count of the call.  float64 in the reference's evaluation order, no
+ * atomics: frame t of a window has the bits a T = 1 call on that frame has, frame 0 those of drp_ptcl_dataset_batch's sampler
+ * and recenter on the same sample and draws.  DRP_EINVAL (the context stays usable; the message names episode and frame) for a
+ * null argument or bad shapes, B * T out of range, a non-positive or non-finite radius, a frame without foreground, a host
+ * count that disagrees, a start outside its cloud, a frame that reaches 4096 particles, n_max > n_cap.
+ * Memory: the upload is 2 * B * T * h * w bytes (pinned staging and its device copy), the clouds and the sampler's distances
+ * 32 * sum(n_fg) bytes: about 1.6 GB of device memory for 64 samples x 6 frames at 720 x 720 with 90 k foreground pixels --
+ * hence the image limit.  Workspaces: drp_ptcl_dataset_batch's (the two calls share them and one pinned staging block for
+ * both directions); nothing of the PropNet weights, a training / planning session, the regressor or drp_obs2ptcl is touched.
+ * One wait after the sampler (the counts), one at the end. */
+int drp_ptcl_dataset_frames(drp_ctx* ctx, int B, int T, const uint16_t* depth, int h, int w, double global_scale,
+                            const double cam[4], const double* radius, const int32_t* init_idx, const int32_t* n_fg_host,
+                            const int32_t* episode, int n_cap, float* clouds_out, int32_t* counts_out, int* n_max_out);
+/* Device time of the last completed drp_ptcl_dataset_batch or drp_ptcl_dataset_frames, whichever completed last, by stage (HIP
+ * events): ms_out [6] = upload | compaction | fps_rad | recenter | track + pack (frames: the pack alone) | download.
+ * DRP_ESTATE before the first. */
 int drp_ptcl_dataset_time(drp_ctx* ctx, float* ms_out);
 
 /* ---- measurement / debugging ----------------------------------------------------- */
@@ -566,7 +588,10 @@ int drp_debug_stall(drp_ctx* ctx, int ms);
  * "w_valu","w_mfma","w_mfma_bwd","w_split","w_split6"; the resolution regressor's post-activation taps of its last forward
  * "rgr_c1".."rgr_c5" (NHWC [B][H][W][C]) and "rgr_f1".."rgr_f4" ([B][features]); the last drp_ptcl_dataset_batch's
  * "pd_nfg" ([B] int32), "pd_chosen" ([B][4097] int32), "pd_recenter" ([B][n_max][3] float64), "pd_nearest" ([B][n_max]
- * int32) (byte sizes: the returned value). returns bytes. */
+ * int32); the last drp_ptcl_dataset_frames's "pdf_nfg" ([B][T] int32), "pdf_chosen" ([B][T][4097] int32), "pdf_recenter"
+ * ([B][T][n_max][3] float64).  The two dataset calls share their buffers: a "pd_*" tap after a frames call, or a "pdf_*" tap
+ * after a batch call, is DRP_ESTATE (not populated), never the other call's bytes. (byte sizes: the returned value). returns
+ * bytes. */
 long drp_debug_fetch(drp_ctx* ctx, const char* name, void* out, size_t out_bytes);
 
 /* ---- the float64 yardstick: one step evaluated in double on the device, and a probe that holds an engine against it ----

@@ -7,6 +7,14 @@ Reports (medians of --reps):
     B = 4 / 64 / 256, particle_den drawn as the reference draws it (uniform 15 .. 6500);
   - host decoding per sample (depth PNG, particle files, actions.p, push frames) on one thread and on --threads;
   - DeviceLoader's samples/s at batch 4, chunk 64, against what the device trainer consumes (UPDATE steps at batch 4).
+
+  python tools/dataset_timing.py --frames [--episodes 4] [--threads 8] [--reps 5]
+
+The untracked path from depth frames alone (drp_ptcl_dataset_frames, DepthDataset; T = 6 frames per sample):
+  - per-stage device time of one call (the fifth stage is the pack alone) at B = 4 / 16 / 64 samples = 24 / 96 / 384 images;
+  - host decoding per sample (T depth PNGs, actions.p) on one thread and on --threads;
+  - DeviceLoader's samples/s at batch 4, chunk 16, against what a Chamfer + actions UPDATE step consumes on the same batches
+    (tools/train_timing.py times that step on synthetic piles).
 """
 import argparse
 import os
@@ -25,7 +33,10 @@ def main():
     ap.add_argument('--episodes', type=int, default=4)
     ap.add_argument('--threads', type=int, default=8)
     ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--frames', action='store_true', help='time drp_ptcl_dataset_frames / DepthDataset instead')
     a = ap.parse_args()
+    if a.frames:
+        return frames(a)
     import __graft_entry__ as g
     g.build()
     from concurrent.futures import ThreadPoolExecutor
@@ -93,6 +104,85 @@ def main():
                 k += 1
         dt = time.perf_counter() - t0
         print('trainer at batch 4: %.2f ms per step = %.0f samples/s' % (dt / k * 1e3, 4 * k / dt))
+    eng.close()
+
+
+def frames(a):
+    import __graft_entry__ as g
+    g.build()
+    from concurrent.futures import ThreadPoolExecutor
+    import torch
+    from dyn_res_pile_manip_amd import synthetic, weights
+    from dyn_res_pile_manip_amd.dataset_gnn_dyn import DepthDataset, DeviceLoader
+    from dyn_res_pile_manip_amd.engine import Engine
+    from dyn_res_pile_manip_amd.planners import world2cam_affine
+    from dyn_res_pile_manip_amd.train_gnn_dyn import default_config
+    eng = Engine(0)
+    print('device: %s' % eng.device_info()['name'])
+    cfg = default_config()
+    cfg['dataset'].update(n_episode=a.episodes, n_timestep=10)
+    cfg['train']['train_valid_ratio'] = 1.0
+    with tempfile.TemporaryDirectory() as d:
+        t0 = time.perf_counter()
+        synthetic.write_episodes(d, a.episodes, 10, seed=0)
+        for ep in os.listdir(d):                       # what a recorded robot episode holds: depth PNGs and actions.p
+            for f in os.listdir(os.path.join(d, ep)):
+                if f.endswith('_particles.npy') or f.endswith('_color.png'):
+                    os.remove(os.path.join(d, ep, f))
+        cam = (synthetic.demo_cam_params(), synthetic.demo_cam_extrinsics())
+        ds = DepthDataset(d, cfg, 'train', cam, engine=eng)
+        T = ds.n_his + ds.n_roll
+        print('%d episodes, %d samples of %d frames (written in %.1f s)' % (a.episodes, len(ds), T, time.perf_counter() - t0))
+        samples = [ds.load(i) for i in range(len(ds))]
+        fg = [n for s in samples for n in s['n_fg']]
+        print('foreground points per frame: %d .. %d' % (min(fg), max(fg)))
+        np.random.seed(0)
+        stages = ('upload', 'compaction', 'fps_rad', 'recenter', 'track_pack', 'download')
+        for B in (4, 16, 64):
+            rows, walls, nmax = [], [], []
+            for r in range(a.reps + 1):
+                batch = [samples[(r * B + j) % len(samples)] for j in range(B)]
+                draws = [ds.draw(s) for s in batch]
+                t0 = time.perf_counter()
+                _, cnt = ds.run(batch, draws)
+                wall = time.perf_counter() - t0
+                if r == 0:
+                    continue                       # first call: allocations
+                rows.append([eng.ptcl_dataset_time()[k] for k in stages])
+                walls.append(wall * 1e3)
+                nmax.append(int(cnt.max()))
+            med = np.median(np.array(rows), axis=0)
+            print('B=%3d x T=%d device ms: %s | sum %.2f | call wall %.2f ms | max particles %d' % (
+                B, T, ' '.join('%s %.3f' % (k if k != 'track_pack' else 'pack', v) for k, v in zip(stages, med)), med.sum(),
+                np.median(walls), max(nmax)))
+        for threads in (1, a.threads):
+            n = 32
+            with ThreadPoolExecutor(max_workers=threads) as pool:
+                t0 = time.perf_counter()
+                list(pool.map(ds.load, [i % len(ds) for i in range(n)]))
+                dt = time.perf_counter() - t0
+            print('host decode: %.2f ms per sample (%d PNGs) on %d thread(s)' % (dt / n * 1e3, T, threads))
+        np.random.seed(0)
+        torch.manual_seed(0)
+        loader = DeviceLoader(ds, 4, shuffle=True, threads=a.threads)
+        t0 = time.perf_counter()
+        batches = list(loader)
+        dt = time.perf_counter() - t0
+        print('DeviceLoader batch 4, chunk %d, %d threads: %.1f samples/s' % (loader.chunk, a.threads, len(ds) / dt))
+        eng.load_weights(weights.blob_from_state_dict(weights.random_state_dict(seed=0, predictor_scale=1.0)), 0.08)
+        eng.set_camera(world2cam_affine(np.asarray(cam[1], dtype=np.float64)), float(cfg['dataset']['global_scale']), cam[0])
+        eng.train_begin(T - 1, 1e-3, 0.9)
+        step = lambda b: eng.train_step_actions(b[0], b.actions, b[2], b[3], b[4], b[6], b[7], mode='update')
+        for b in batches[:2]:
+            step(b)
+        t0 = time.perf_counter()
+        k = 0
+        for _ in range(5):
+            for b in batches:
+                step(b)
+                k += 1
+        dt = time.perf_counter() - t0
+        print('Chamfer + actions trainer at batch 4: %.2f ms per step = %.0f samples/s' % (dt / k * 1e3, 4 * k / dt))
     eng.close()
 
 
