@@ -102,11 +102,15 @@ def make_elite_records(rewards, act_seqs, k, sample_offset=0):
 
 
 def combine_elite_records(records, k):
-    """[n_ranks, k, 2+4H] -> nominal [H,4] (mean of the k best of all records), elite size, worst elite reward."""
+    """[n_ranks, k, 2+4H] -> nominal [H,4] (mean of the k best of all records), elite size, worst elite reward.
+    As k_elite_update: padding (index < 0) and NaN rewards are no candidates; fewer than k candidates give a smaller elite;
+    none at all gives (None, 0, 0.0) -- the device leaves its nominal as it was."""
     rec = np.asarray(records, dtype=np.float64)
     rec = rec.reshape(-1, rec.shape[-1])
-    rec = rec[rec[:, 1] >= 0.0]
+    rec = rec[(rec[:, 1] >= 0.0) & ~np.isnan(rec[:, 0])]
     order = np.lexsort((rec[:, 1], -rec[:, 0]))[:k]
+    if len(order) == 0:
+        return None, 0, 0.0
     H = (rec.shape[1] - 2) // 4
     el = rec[order]
     return el[:, 2:].mean(0).reshape(H, 4), len(order), float(el[-1, 0])

@@ -194,7 +194,7 @@ typedef struct drp_mpc_params {
     double reward_weight; /* mpc.mppi.reward_weight (planners.py:553) */
     float act_lo[4];      /* clip box (planners.py:152-155) */
     float act_hi[4];
-    uint64_t seed;        /* Philox key */
+    uint64_t seed;        /* Philox key: the stream below */
     uint64_t sample_offset; /* first global sample index of this rank (Philox counter) */
     int noise_type;       /* DRP_NOISE_*: the sampler's noise_type argument (planners.py:75,116-135,169-175) */
     int reserved;         /* 0 */
@@ -229,7 +229,23 @@ int drp_mpc_begin_scenes(drp_ctx* ctx, const drp_mpc_params* p, int S, const flo
  * scene, plus sample_offset), Z, m.  S = 1 for a single-scene session. */
 int drp_mpc_stats_scenes(drp_ctx* ctx, double* stats_out /* [S][6] */);
 /* noise: NULL -> device Philox draws; else host [n_sample,H,4] draws: standard normal (DRP_NOISE_NORMAL),
- * U(-1,1) (DRP_NOISE_UNIFORM) or U[0,1) (DRP_NOISE_TOTAL_RAND). */
+ * U(-1,1) (DRP_NOISE_UNIFORM) or U[0,1) (DRP_NOISE_TOTAL_RAND).
+ * The device's stream is a contract (sharding rests on it: a shard of a job draws what the whole job draws), restated on
+ * the host in tests/_philox_ref.py and held to it by tests/test_gpu_sampler.py:
+ *   block    w[0..3] = Philox4x32-10 (Random123: multipliers D2511F53 / CD9E8D57, key increments 9E3779B9 / BB67AE85)
+ *            key     (seed & 0xffffffff, seed >> 32)              -- a scene of a multi-scene session: seeds[scene]
+ *            counter (gs & 0xffffffff, gs >> 32, t, iteration & 0xffffffff),   gs = sample_offset + sample (mod 2^64),
+ *                    t = 0 .. H-1 the step: one block per (global sample, step); `iteration` enters modulo 2^32
+ *   uniform  component c = 0..3 of the push reads w[c]:  u = (w[c] >> 8) * 2^-24 in [0, 1), 24 bits, exact;
+ *            DRP_NOISE_UNIFORM draws 2u - 1, DRP_NOISE_TOTAL_RAND u
+ *   normal   components 0, 1 read the pair (a, b) = (w[0], w[1]), components 2, 3 the pair (w[2], w[3]) (Box-Muller):
+ *            u1 = ((float)a + 1) * 2^-32 in (0, 1],  u2 = (float)b * 2^-32,  r = sqrt(-2 ln u1) <= 6.66,
+ *            even component r cos(2 pi u2), odd component r sin(2 pi u2) -- float32, round to nearest: the uniforms are the
+ *            restatement's bits, a normal is within a few float32 ulps of r of the float64 evaluation on the same u1, u2
+ *            (the bound: DESIGN.md section 2, row a12)
+ *   filter   per component, in float64:  resid = beta (sigma n) + resid (1 - beta),  push = clip(nominal[t] + resid) (TOTAL_RAND:
+ *            act_lo + n (act_hi - act_lo)), rounded to float32 -- the restatement's bits for device and host draws alike;
+ *            every column of a sample gets the sample's push. */
 int drp_mpc_sample(drp_ctx* ctx, const float* noise, uint64_t iteration);
 int drp_mpc_set_actions(drp_ctx* ctx, const float* actions /* [B,H,4] */);
 int drp_mpc_rollout(drp_ctx* ctx, int reward_all_steps);
