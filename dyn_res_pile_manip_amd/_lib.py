@@ -20,6 +20,8 @@ ENGINE_SPLIT = 2
 ENGINE_FUSED = 3
 ENGINE_LITE = 4             # opt-in reduced products on the fused engine's kernels (include/drp.h: DRP_ENGINE_LITE)
 TRAIN_MODES = {'eval': 0, 'grad': 1, 'update': 2}
+LOSS_KINDS = {'chamfer': 1, 'match': 2, 'chamfer+match': 3}     # DRP_LOSS_*: drp_train_step_loss
+MATCH_MAX_POINTS = 1024     # KA_MAX_POINTS: the largest cloud of a matching
 DIST_TRANSFORMS = {'cv5': 0, 'exact': 1}
 RGR_REGRESSOR = 1           # DRP_RGR_REGRESSOR: n_out of the MPCResRgrNoPool head
 RGR_CLASSIFIER = 6          # DRP_RGR_CLASSIFIER: n_out of the MPCResCls head
@@ -208,6 +210,13 @@ SIGNATURES = {
                                              ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p,
                                              c_double_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
                                              c_double_p]),
+    'drp_cloud_match': (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.POINTER(ctypes.c_int32), c_float_p,
+                                       ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_float_p,
+                                       ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), c_double_p]),
+    'drp_train_step_loss': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p,
+                                           ctypes.POINTER(ctypes.c_int32), c_float_p, ctypes.c_int, ctypes.c_int, c_float_p,
+                                           ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
+                                           ctypes.POINTER(ctypes.c_double), c_float_p, ctypes.POINTER(ctypes.c_int32)]),
 }
 
 _lib = None

@@ -39,7 +39,10 @@ int drp_cloud_chamfer(drp_ctx* c, const float* p, const int32_t* n_p, const floa
     a.terms = reinterpret_cast<double*>(io + o_terms);
     a.nn_pq = nn_pq_out ? reinterpret_cast<int*>(io + o_pq) : nullptr;
     a.nn_qp = nn_qp_out ? reinterpret_cast<int*>(io + o_qp) : nullptr;
-    hipLaunchKernelGGL((kc_chamfer<false>), dim3(B, 1), dim3(KC_THREADS), 0, c->stream, a);
+    {
+        ProbeScope ps(c, KC_LOSS);
+        hipLaunchKernelGGL((kc_chamfer<false>), dim3(B, 1), dim3(KC_THREADS), 0, c->stream, a);
+    }
     if (hipGetLastError() != hipSuccess) { (void)drp_sync(c); return fail(c, DRP_EHIP, "kc_chamfer launch"); }   // (the staging vector is still being read)
     int rc = d2h(c, terms_out, io + o_terms, (size_t)B * 2 * sizeof(double));
     if (rc == DRP_OK && grad_p_out) rc = d2h(c, grad_p_out, io + o_grad, bn * 3 * sizeof(float));

@@ -7,10 +7,10 @@ std::string g_create_error;
 
 enum KClass { KC_GRAPH = 0, KC_NODE_ENCODE, KC_EDGE_ENCODE, KC_PROJECT, KC_AGGREGATE, KC_UPDATE,
               KC_PREDICT, KC_REWARD, KC_MPPI, KC_PROP, KC_TAPE_COPY, KC_BWD_REWARD, KC_BWD_LISTS, KC_BWD_NODE, KC_BWD_EDGE,
-              KC_BWD_PUSH, KC_OPT, KC_COUNT };
+              KC_BWD_PUSH, KC_OPT, KC_LOSS, KC_COUNT };
 const char* const kclass_names[KC_COUNT] = {"graph", "node_encode", "edge_encode", "project",
                                             "aggregate", "update", "predict", "reward", "mppi", "prop",
-                                            "tape_copy", "bwd_reward", "bwd_lists", "bwd_node", "bwd_edge", "bwd_push", "opt"};
+                                            "tape_copy", "bwd_reward", "bwd_lists", "bwd_node", "bwd_edge", "bwd_push", "opt", "loss"};
 
 // the variant names (DispatchVariant, dv_name), the dispatch policy and the plan functions: host-only, csrc/dispatch.h
 using namespace dispatch;
@@ -317,6 +317,8 @@ struct drp_ctx {
 
     DevBuf ch_io;                   // drp_cloud_chamfer (capi_chamfer.h; a one-shot that keeps nothing between calls): its inputs and results
     DevBuf ch64_io;                 // drp_cloud_chamfer_f64: the same, in a buffer of its own
+    DevBuf ma_io;                   // drp_cloud_match (capi_match.h): the same, in a buffer of its own
+    DevBuf tr_match;                // drp_train_step_loss: the partner of every predicted row [H][B][N] (ka_match<true>)
 
     // re-packing after an optimiser step on the device (k_train.h): gather maps of the plain packers, pinned copy of the blob
     DevBuf map_valu, map_mfma, map_mfma_bwd;

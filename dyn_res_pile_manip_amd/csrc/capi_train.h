@@ -10,13 +10,18 @@ const int* tr_nums(const drp_ctx* c, const TrArena& lay) {
     return reinterpret_cast<const int*>(static_cast<const char*>(c->tr_arena.p) + lay.nums);
 }
 // what seeds the reverse pass: the tracked loss (kt_mse_grad against the given next states) or the Chamfer loss against
-// untracked target clouds (k_chamfer.h); the targets as the HOST gave them (the entry point stages them behind the batch)
-enum { TR_LOSS_MSE = 0, TR_LOSS_CHAMFER = 1 };
+// untracked target clouds (k_chamfer.h), the one-to-one matching loss against them (k_match.h), or the two mixed; the targets as
+// the HOST gave them (the entry point stages them behind the batch).  The kinds beyond the MSE are include/drp.h's DRP_LOSS_*
+enum { TR_LOSS_MSE = 0, TR_LOSS_CHAMFER = DRP_LOSS_CHAMFER, TR_LOSS_MATCH = DRP_LOSS_MATCH, TR_LOSS_CHAMFER_MATCH = DRP_LOSS_CHAMFER_MATCH };
 struct TrLoss {
     int kind = TR_LOSS_MSE;
     const float* targets = nullptr;         // [B][H][M][3]
     const int32_t* target_nums = nullptr;   // [B][H]
     int M = 0;
+    double match_weight = 0.0;              // TR_LOSS_CHAMFER_MATCH: (1 - w) Chamfer + w matching
+    int32_t* match_out = nullptr;           // the caller's [H][B][N], nullable: every predicted row's partner (kinds with a matching)
+    bool chamfer() const { return kind == TR_LOSS_CHAMFER || kind == TR_LOSS_CHAMFER_MATCH; }
+    bool match() const { return kind == TR_LOSS_MATCH || kind == TR_LOSS_CHAMFER_MATCH; }
 };
 // one pass over a staged batch: everything train_forward_backward reads beside the shapes and the session
 struct TrainPass {
@@ -72,16 +77,37 @@ int train_forward_backward(drp_ctx* c, int B, int N, const TrainPass& tp) {
         // staged target clouds
         const TrArena& lay = tp.lay;
         const char* ar = static_cast<const char*>(c->tr_arena.p);
-        KcArgs a{};
-        a.pred = states; a.p_bstride = hstride; a.p_tstride = (size_t)N * 3;
-        a.tgt = reinterpret_cast<const float*>(ar + lay.targets); a.q_bstride = (size_t)H * lk.M * 3; a.q_tstride = (size_t)lk.M * 3;
-        a.n_p = nums;
-        a.n_q = reinterpret_cast<const int*>(ar + lay.tnums); a.nq_bstride = H; a.nq_tstride = 1;
-        a.N = N; a.M = lk.M; a.scale = scale;
-        a.grad = g_state; a.terms = loss;
-        a.zero = backward ? ptr<float>(c->tr_grad) : (float*)nullptr;
-        a.n_zero = (size_t)TR_GRAD_PAD + (size_t)H * c->n_cu + 1;
-        hipLaunchKernelGGL((kc_chamfer<true>), dim3(B, H), dim3(KC_THREADS), 0, st, a);
+        float* const zero = backward ? ptr<float>(c->tr_grad) : (float*)nullptr;
+        const size_t n_zero = (size_t)TR_GRAD_PAD + (size_t)H * c->n_cu + 1;
+        if (lk.chamfer()) {
+            KcArgs a{};
+            a.pred = states; a.p_bstride = hstride; a.p_tstride = (size_t)N * 3;
+            a.tgt = reinterpret_cast<const float*>(ar + lay.targets); a.q_bstride = (size_t)H * lk.M * 3; a.q_tstride = (size_t)lk.M * 3;
+            a.n_p = nums;
+            a.n_q = reinterpret_cast<const int*>(ar + lay.tnums); a.nq_bstride = H; a.nq_tstride = 1;
+            a.N = N; a.M = lk.M;
+            a.scale = scale;               // (the mix too: the matching kernel weighs what this one leaves, in double)
+            a.grad = g_state; a.terms = loss;
+            a.zero = zero; a.n_zero = n_zero;
+            hipLaunchKernelGGL((kc_chamfer<true>), dim3(B, H), dim3(KC_THREADS), 0, st, a);
+        }
+        if (lk.match()) {
+            // alone: the Chamfer kernel's outputs and zero-fill; in the mix: behind it in the stream, turning the gradient and the
+            // terms it finds into (1 - w) x them + its own share -- one writer per element, so the sum's order is fixed, and
+            // the Chamfer share is (1 - w) x the bits of a Chamfer-only step whatever w is
+            KaArgs a{};
+            a.pred = states; a.p_bstride = hstride; a.p_tstride = (size_t)N * 3;
+            a.tgt = reinterpret_cast<const float*>(ar + lay.targets); a.q_bstride = (size_t)H * lk.M * 3; a.q_tstride = (size_t)lk.M * 3;
+            a.n_p = nums;
+            a.n_q = reinterpret_cast<const int*>(ar + lay.tnums); a.nq_bstride = H; a.nq_tstride = 1;
+            a.N = N; a.M = lk.M;
+            a.scale = lk.chamfer() ? (double)scale * lk.match_weight : (double)scale;
+            a.keep = lk.chamfer() ? 1.0 - lk.match_weight : 0.0;
+            a.grad = g_state; a.terms = loss;
+            a.match_pq = ptr<int>(c->tr_match);
+            a.zero = lk.chamfer() ? (float*)nullptr : zero; a.n_zero = n_zero;
+            ka_launch<true>(dim3(B, H), st, a);
+        }
     }
     HIPCHK(c, hipGetLastError());
     if (!backward) return DRP_OK;
@@ -297,9 +323,15 @@ int train_check_args(drp_ctx* c, const float* states, const float* impulses, boo
     for (int b = 0; b < B; ++b)
         if (particle_nums[b] <= 0 || particle_nums[b] > N)
             return fail(c, DRP_EINVAL, "particle_nums[%d]=%d outside 1..%d", b, particle_nums[b], N);
-    if (lk.kind == TR_LOSS_CHAMFER) {
+    if (lk.kind != TR_LOSS_MSE) {
         if (!lk.targets || !lk.target_nums) return fail(c, DRP_EINVAL, "null argument");
         if (lk.M <= 0 || lk.M > KC_MAX_POINTS) return fail(c, DRP_EINVAL, "bad target size M=%d (1..%d)", lk.M, KC_MAX_POINTS);
+        if (lk.match()) {
+            if (N > KA_MAX_POINTS || lk.M > KA_MAX_POINTS)
+                return fail(c, DRP_EINVAL, "a matching loss takes clouds of 1..%d points: N=%d M=%d", KA_MAX_POINTS, N, lk.M);
+            if (lk.kind == TR_LOSS_CHAMFER_MATCH && !(lk.match_weight > 0.0 && lk.match_weight < 1.0))
+                return fail(c, DRP_EINVAL, "match_weight %g outside (0, 1)", lk.match_weight);
+        }
         for (int e = 0; e < B * c->tr_nroll; ++e)
             if (lk.target_nums[e] <= 0 || lk.target_nums[e] > lk.M)
                 return fail(c, DRP_EINVAL, "target_nums[%d][%d]=%d outside 1..%d", e / c->tr_nroll, e % c->tr_nroll,
@@ -343,6 +375,7 @@ int train_ensure_workspace(drp_ctx* c, int B, int N, TrainPass& tp) {
         CHK(ensure(c, c->ed_x0, kt * bnk * 8 * sizeof(float)));
     }
     CHK(ensure(c, c->tr_loss, (size_t)H * B * sizeof(double)));
+    if (tp.lk.match()) CHK(ensure(c, c->tr_match, (size_t)H * bn * sizeof(int)));
     return DRP_OK;
 }
 
@@ -357,7 +390,7 @@ int train_stage_batch(drp_ctx* c, const float* states, const float* impulses, co
     memcpy(pin + lay.attrs, attrs, (size_t)B * (H + 1) * N * sizeof(float));
     memcpy(pin + lay.dens, particle_dens, (size_t)B * sizeof(float));
     memcpy(pin + lay.nums, particle_nums, (size_t)B * sizeof(int));
-    if (tp.lk.kind == TR_LOSS_CHAMFER) {
+    if (tp.lk.kind != TR_LOSS_MSE) {
         memcpy(pin + lay.targets, tp.lk.targets, (size_t)B * H * tp.lk.M * 3 * sizeof(float));
         memcpy(pin + lay.tnums, tp.lk.target_nums, (size_t)B * H * sizeof(int));
     }
@@ -397,6 +430,7 @@ int train_attempt(drp_ctx* c, int B, int N, const TrainPass& tp, int mode, bool 
     }
     if (want_loss && tp.loss_terms != back) CHK(d2h(c, back, c->tr_loss.p, (size_t)H * B * sizeof(double)));
     if (grad_out && tp.backward) CHK(d2h(c, grad_out, c->tr_grad.p, (size_t)W_TOTAL * sizeof(float)));
+    if (tp.lk.match_out && tp.lk.match()) CHK(d2h(c, tp.lk.match_out, c->tr_match.p, (size_t)H * B * N * sizeof(int)));
     if (tp.backward && !direct) CHK(d2h(c, flag_host, flag_dev, sizeof(unsigned)));
     bool repacked = false;
     if (mode == DRP_TRAIN_UPDATE) {
@@ -445,7 +479,7 @@ int train_step_body(drp_ctx* c, const float* states, const float* impulses, bool
         CHK(pick_tape_engine(c, amax, max_abs(particle_dens, (size_t)B), sd_max, &tp.engine));
     }
     tp.backward = mode != DRP_TRAIN_EVAL;
-    tp.lay = tr_layout(B, H, N, lk.kind == TR_LOSS_CHAMFER ? lk.M : 0, actions);
+    tp.lay = tr_layout(B, H, N, lk.kind != TR_LOSS_MSE ? lk.M : 0, actions);
     tp.lk = lk;
     tp.actions = actions;
     CHK(train_ensure_workspace(c, B, N, tp));
@@ -497,6 +531,25 @@ int drp_train_step_actions(drp_ctx* c, const float* states, const float* actions
         lk.kind = TR_LOSS_CHAMFER; lk.targets = targets; lk.target_nums = target_nums; lk.M = M;
     }
     return train_step_body(c, states, actions, true, attrs, particle_nums, particle_dens, B, N, lk, mode, loss_out, grad_out);
+}
+
+// drp_train_step_untracked / drp_train_step_actions with the loss kind and the mix's weight as arguments: the same body, two more
+// fields of TrLoss
+int drp_train_step_loss(drp_ctx* c, const float* states, const float* states_delta, const float* actions, const float* attrs,
+                        const int32_t* particle_nums, const float* particle_dens, int B, int N, const float* targets,
+                        const int32_t* target_nums, int M, int loss_kind, double match_weight, int mode, double* loss_out,
+                        float* grad_out, int32_t* match_out) {
+    if (!c) return DRP_EINVAL;
+    if ((states_delta != nullptr) == (actions != nullptr))
+        return fail(c, DRP_EINVAL, "exactly one of states_delta and actions must be given");
+    if (loss_kind != DRP_LOSS_CHAMFER && loss_kind != DRP_LOSS_MATCH && loss_kind != DRP_LOSS_CHAMFER_MATCH)
+        return fail(c, DRP_EINVAL, "bad loss_kind %d", loss_kind);
+    TrLoss lk;
+    lk.kind = loss_kind; lk.targets = targets; lk.target_nums = target_nums; lk.M = M;
+    lk.match_weight = match_weight; lk.match_out = match_out;
+    const bool by_actions = actions != nullptr;
+    return train_step_body(c, states, by_actions ? actions : states_delta, by_actions, attrs, particle_nums, particle_dens, B, N, lk,
+                           mode, loss_out, grad_out);
 }
 
 int drp_train_set_lr(drp_ctx* c, double lr) {

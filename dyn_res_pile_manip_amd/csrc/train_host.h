@@ -53,6 +53,37 @@ inline Tr64Arena tr64_layout(int B, int H, int N, int M = 0, bool actions = fals
     return a;
 }
 
+// drp_cloud_match's one buffer (capi_match.h), every block 16-byte aligned.  Up: p [B][N][3] | q [B][M][3] | n_p [B] | n_q [B]
+// (ints); down, behind `in_bytes`: terms [B] (doubles) | gradient [B][N][3] | partner of every row of p [B][N] | of q [B][M]
+// (ints) | duals [B][N + M] (doubles)
+struct CmLayout { size_t pts_p, pts_q, n_p, n_q, in_bytes, terms, grad, pq, qp, dual, bytes; };
+inline CmLayout cm_layout(int B, int N, int M) {
+    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t bn = (size_t)B * N, bm = (size_t)B * M;
+    CmLayout a{};
+    a.pts_p = 0;
+    a.pts_q = up(a.pts_p + bn * 3 * sizeof(float));
+    a.n_p = up(a.pts_q + bm * 3 * sizeof(float));
+    a.n_q = up(a.n_p + (size_t)B * sizeof(int32_t));
+    a.in_bytes = up(a.n_q + (size_t)B * sizeof(int32_t));
+    a.terms = a.in_bytes;
+    a.grad = up(a.terms + (size_t)B * sizeof(double));
+    a.pq = up(a.grad + bn * 3 * sizeof(float));
+    a.qp = up(a.pq + bn * sizeof(int32_t));
+    a.dual = up(a.qp + bm * sizeof(int32_t));
+    a.bytes = up(a.dual + (bn + bm) * sizeof(double));
+    return a;
+}
+// the first of the real rows' coordinates of a padded cloud batch [B][N][3] that is infinite or no number, as b * N + row, or -1
+// (the padding is never read as points: rubbish there is allowed)
+inline long first_nonfinite_row(const float* x, const int32_t* counts, int B, int N) {
+    for (int b = 0; b < B; ++b)
+        for (int i = 0; i < counts[b] && i < N; ++i)
+            for (int d = 0; d < 3; ++d)
+                if (!std::isfinite(x[((size_t)b * N + i) * 3 + d])) return (long)b * N + i;
+    return -1;
+}
+
 // the length of a push (sx, sy, ex, ey) in the camera frame, with push_frame's operations (k_graph.h: the same fmaf chain,
 // division and sum, no contraction); m: the 3x4 world -> camera map, gs: global_scale
 inline float push_len_host(const float* m, float gs, const float* act) {

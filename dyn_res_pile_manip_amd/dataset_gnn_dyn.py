@@ -345,6 +345,29 @@ def drop_correspondence(sample, rng, keep=(0.6, 1.0)):
     return tuple(sample[:6]) + (targets,)
 
 
+def track_clouds(engine, clouds, counts):
+    """The bridge from untracked clouds back to the tracked tools: clouds [T, N, 3] (the frames of one untracked window, padded)
+    with counts [T] real rows each -> perms [T, n] int64 with clouds[t, perms[t, i]] the row of frame t that is particle i of
+    frame 0 (perms[0] = arange(n)).  Consecutive frames are paired by Engine.cloud_match, the one-to-one matching at the least
+    total squared distance, all T - 1 pairs in one call, and the partners are chained; clouds[t, perms[t]] is then a tracked
+    window that loss='mse' and train_grad_f64 can read.  A window whose counts are not all equal has rows without a partner and
+    is refused (ValueError)."""
+    clouds = np.ascontiguousarray(clouds, dtype=np.float32)
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    if clouds.ndim != 3 or clouds.shape[2] != 3 or counts.shape[0] != clouds.shape[0]:
+        raise ValueError('clouds must be [T, N, 3] with one count per frame, got %s and %d counts' % (clouds.shape, counts.shape[0]))
+    if clouds.shape[0] < 1 or (counts != counts[0]).any():
+        raise ValueError('a window is tracked only where all its counts are equal, got %s' % (counts.tolist(),))
+    n = int(counts[0])
+    perms = np.empty((clouds.shape[0], n), np.int64)
+    perms[0] = np.arange(n)
+    if clouds.shape[0] > 1:
+        out = engine.cloud_match(clouds[:-1], clouds[1:], counts[:-1], counts[1:], want_match=True)
+        for t in range(1, clouds.shape[0]):
+            perms[t] = out['match_pq'][t - 1][perms[t - 1]]
+    return perms
+
+
 class UntrackedLoader(object):
     """A loader of collated tracked batches (DeviceLoader) -> untracked ones: every sample of every batch goes through
     drop_correspondence (one numpy Generator, in sample order), the batch through collate_untracked.  reseed: every pass starts

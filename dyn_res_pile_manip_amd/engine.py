@@ -834,6 +834,79 @@ class Engine(object):
             out['nn_pq'], out['nn_qp'] = nn_pq, nn_qp
         return out
 
+    # ---- the one-to-one matching distance of two cloud batches (include/drp.h: drp_cloud_match) --------------------------
+    def cloud_match(self, p, q, n_p=None, n_q=None, want_grad=False, want_match=False, want_dual=False):
+        """Matching (earth mover's) distance of p [B, N, 3] (n_p [B] real rows, default all) and q [B, M, 3] (n_q): every row of
+        the smaller cloud paired with a distinct row of the larger one at the least total squared distance ->
+        {'match' [B] float64 = sum over the pairs / (3 r), 'r' [B] = min(n_p, n_q)[, 'grad' [B, N, 3] = d match / d p][, 'match_pq'
+        [B, N], 'match_qp' [B, M]: each row's partner, -1 for unmatched rows and padding][, 'u' [B, N], 'v' [B, M]: the duals of
+        p's and q's rows, float64]}.  A single cloud pair may be given as [N, 3], [M, 3].  At most 1024 points per cloud.  A
+        one-shot: it needs no weights and ends no session."""
+        p, q = _f32(p), _f32(q)
+        if p.ndim == 2 and q.ndim == 2:
+            p, q = p[None], q[None]
+        assert p.ndim == 3 and q.ndim == 3 and p.shape[2] == 3 and q.shape[2] == 3 and p.shape[0] == q.shape[0]
+        B, N, M = p.shape[0], p.shape[1], q.shape[1]
+        n_p = np.full((B,), N, np.int32) if n_p is None else np.ascontiguousarray(n_p, dtype=np.int32).reshape(-1)
+        n_q = np.full((B,), M, np.int32) if n_q is None else np.ascontiguousarray(n_q, dtype=np.int32).reshape(-1)
+        assert n_p.shape == (B,) and n_q.shape == (B,)
+        terms = np.empty((B,), np.float64)
+        grad = np.empty((B, N, 3), np.float32) if want_grad else None
+        m_pq = np.empty((B, N), np.int32) if want_match else None
+        m_qp = np.empty((B, M), np.int32) if want_match else None
+        dual = np.empty((B, N + M), np.float64) if want_dual else None
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        self._ck(self.lib.drp_cloud_match(self.h, _fp(p), n_p.ctypes.data_as(i32p), _fp(q), n_q.ctypes.data_as(i32p), int(B), int(N),
+                                          int(M), _dp(terms), _fp(grad) if want_grad else None,
+                                          m_pq.ctypes.data_as(i32p) if want_match else None,
+                                          m_qp.ctypes.data_as(i32p) if want_match else None, _dp(dual) if want_dual else None))
+        out = {'match': terms, 'r': np.minimum(n_p, n_q)}
+        if want_grad:
+            out['grad'] = grad
+        if want_match:
+            out['match_pq'], out['match_qp'] = m_pq, m_qp
+        if want_dual:
+            out['u'], out['v'] = dual[:, :N].copy(), dual[:, N:].copy()
+        return out
+
+    def train_step_loss(self, states, attrs, particle_nums, particle_dens, targets, target_nums, states_delta=None, actions=None,
+                        loss='match', match_weight=0.5, mode='update', want_grad=False, want_match=False):
+        """train_step_untracked (states_delta [B, n_rollout, N, 3]) or train_step_actions (actions [B, n_rollout, 4]) -- exactly
+        one of the two -- with the loss chosen by name (include/drp.h: drp_train_step_loss): 'chamfer', 'match' (the one-to-one
+        matching term of cloud_match) or 'chamfer+match' = (1 - match_weight) chamfer + match_weight match -> (loss, gradient blob
+        or None[, match [n_rollout, B, N]: every predicted row's partner in its target, -1 for unmatched rows and padding])."""
+        if loss not in L.LOSS_KINDS:
+            raise ValueError('loss must be one of %s' % (tuple(L.LOSS_KINDS),))
+        if (states_delta is None) == (actions is None):
+            raise ValueError('exactly one of states_delta and actions must be given')
+        states, attrs = _f32(states), _f32(attrs)
+        dens = _f32(particle_dens)
+        nums = np.ascontiguousarray(particle_nums, dtype=np.int32)
+        targets = _f32(targets)
+        tnums = np.ascontiguousarray(target_nums, dtype=np.int32)
+        B, T1, N, _ = states.shape
+        assert T1 == self._n_rollout + 1
+        if states_delta is not None:
+            states_delta = _f32(states_delta)
+            assert states_delta.shape == (B, T1 - 1, N, 3)
+        else:
+            actions = _f32(actions)
+            assert actions.shape == (B, T1 - 1, 4)
+        assert attrs.shape == (B, T1, N) and nums.shape == (B,) and dens.shape == (B,)
+        assert targets.ndim == 4 and targets.shape[:2] == (B, T1 - 1) and targets.shape[3] == 3 and tnums.shape == (B, T1 - 1)
+        M = targets.shape[2]
+        out_loss = ctypes.c_double()
+        grad = np.empty((38403,), np.float32) if (want_grad and mode != 'eval') else None
+        match = np.full((T1 - 1, B, N), -1, np.int32) if (want_match and loss != 'chamfer') else None
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        self._ck(self.lib.drp_train_step_loss(self.h, _fp(states), _fp(states_delta) if states_delta is not None else None,
+                                              _fp(actions) if actions is not None else None, _fp(attrs), nums.ctypes.data_as(i32p),
+                                              _fp(dens), B, N, _fp(targets), tnums.ctypes.data_as(i32p), int(M), L.LOSS_KINDS[loss],
+                                              float(match_weight), L.TRAIN_MODES[mode], ctypes.byref(out_loss),
+                                              None if grad is None else _fp(grad),
+                                              None if match is None else match.ctypes.data_as(i32p)))
+        return (out_loss.value, grad, match) if want_match else (out_loss.value, grad)
+
     def cloud_chamfer_f64(self, p, q, n_p=None, n_q=None, want_grad=False, want_nn=False):
         """cloud_chamfer in float64 on the device (include/drp.h: drp_cloud_chamfer_f64): the same dict with 'grad' as float64,
         plus 'margin' [B, 2] -- per sample the smallest (second-best - best) squared distance over its arg-mins, p -> q then

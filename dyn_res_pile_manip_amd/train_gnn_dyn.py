@@ -95,30 +95,48 @@ class DeviceAdam(object):
 
 
 LOSSES = ('mse', 'chamfer')
+# the one-to-one matching loss of Engine.cloud_match and its mix with the Chamfer distance (Engine.train_step_loss): they train as
+# 'chamfer' does, on collate_untracked's batches, but have no float64 yardstick yet, so the probe options refuse them
+MATCH_LOSSES = ('match', 'chamfer+match')
+UNTRACKED_LOSSES = ('chamfer',) + MATCH_LOSSES
 IMPULSES = ('data', 'actions')
 DATA = ('particles', 'depth')
+
+
+def check_loss(loss, match_weight=0.5):
+    if loss not in LOSSES + MATCH_LOSSES:
+        raise ValueError('loss must be one of %s or %s, got %r' % (LOSSES, MATCH_LOSSES, loss))
+    if loss == 'chamfer+match' and not 0.0 < float(match_weight) < 1.0:
+        raise ValueError('match_weight must lie in (0, 1), got %r' % (match_weight,))
+
+
+def refuse_match_probe(loss):
+    if loss in MATCH_LOSSES:
+        raise ValueError('there is no float64 yardstick for the matching loss yet: loss=%r cannot be probed '
+                         '(probe_every, grad_probe_every, probe_batch)' % (loss,))
 
 
 def check_depth_only(data, loss, impulses):
     """a batch made from depth frames alone has no tracked targets and no recorded impulses: anything but the Chamfer loss through
     the push would train on zeros"""
-    if getattr(data, 'depth_only', False) and not (loss == 'chamfer' and impulses == 'actions'):
-        raise ValueError('a depth-only batch (DepthDataset) holds no tracked states and no impulses: it needs loss=\'chamfer\' and '
-                         'impulses=\'actions\', got loss=%r, impulses=%r' % (loss, impulses))
+    if getattr(data, 'depth_only', False) and not (loss in UNTRACKED_LOSSES and impulses == 'actions'):
+        raise ValueError('a depth-only batch (DepthDataset) holds no tracked states and no impulses: it needs loss=\'chamfer\' (or '
+                         'one of %s) and impulses=\'actions\', got loss=%r, impulses=%r' % (MATCH_LOSSES, loss, impulses))
 
 
 def resolve_data_options(data, loss, impulses):
     """main()'s / the command line's data, loss and impulses -> (loss, impulses).  None = not given: 'mse' and 'data' for
-    data='particles'; data='depth' implies 'chamfer' and 'actions' and refuses anything else."""
+    data='particles'; data='depth' implies 'chamfer' and 'actions'; it takes a MATCH_LOSSES member in place of 'chamfer' and
+    refuses anything else."""
     if data not in DATA:
         raise ValueError('data must be one of %s, got %r' % (DATA, data))
     if data == 'depth':
-        if loss not in (None, 'chamfer'):
+        if loss not in (None,) + UNTRACKED_LOSSES:
             raise ValueError('data=\'depth\' trains on untracked clouds: loss=%r contradicts the loss=\'chamfer\' it implies' % (loss,))
         if impulses not in (None, 'actions'):
             raise ValueError('data=\'depth\' has no recorded impulses: impulses=%r contradicts the impulses=\'actions\' it implies'
                              % (impulses,))
-        return 'chamfer', 'actions'
+        return 'chamfer' if loss is None else loss, 'actions'
     return 'mse' if loss is None else loss, 'data' if impulses is None else impulses
 
 
@@ -131,15 +149,16 @@ def batch_actions(data):
     return _np(actions)
 
 
-def run_batch(model, optimizer, data, phase='train', n_rollout=None, loss='mse', impulses='data'):
+def run_batch(model, optimizer, data, phase='train', n_rollout=None, loss='mse', impulses='data', match_weight=0.5):
     """The loop body at train/train_gnn_dyn.py:159-210 -> loss (python float, what loss.item() is there).  loss='chamfer': `data`
     is collate_untracked's (targets and target_nums behind the six fields) and each step's term is the Chamfer distance to its
     target cloud (Engine.train_step_untracked).  A batch marked depth_only (DepthDataset) is refused (ValueError) unless
     loss='chamfer' and impulses='actions'.  impulses='actions': every step's impulse is computed from the batch's pushes
     (`data.actions`) on the state the step reads instead of taken from states_delta (Engine.train_step_actions; the engine's
-    camera must be set)."""
-    if loss not in LOSSES:
-        raise ValueError('loss must be one of %s, got %r' % (LOSSES, loss))
+    camera must be set).  loss='match' / 'chamfer+match' (MATCH_LOSSES): collate_untracked's batches as for 'chamfer', each step's
+    term the one-to-one matching distance to its target cloud, or (1 - match_weight) Chamfer + match_weight matching, with either
+    impulse source (Engine.train_step_loss)."""
+    check_loss(loss, match_weight)
     if impulses not in IMPULSES:
         raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
     check_depth_only(data, loss, impulses)
@@ -153,6 +172,11 @@ def run_batch(model, optimizer, data, phase='train', n_rollout=None, loss='mse',
     if hasattr(model, '_claim'):
         model._claim()                                  # models share the process's context: this one's weights in
         model._device_ahead = model._device_ahead or mode == 'update'
+    if loss in MATCH_LOSSES:
+        value, _ = model.engine.train_step_loss(states, _np(attrs), _np(particle_nums, np.int32), _np(particle_dens), _np(data[6]),
+                                                _np(data[7], np.int32), states_delta=None if actions is not None else _np(states_delta),
+                                                actions=actions, loss=loss, match_weight=match_weight, mode=mode)
+        return value
     if impulses == 'actions':
         chamfer = loss == 'chamfer'
         value, _ = model.engine.train_step_actions(states, actions, _np(attrs), _np(particle_nums, np.int32),
@@ -183,9 +207,9 @@ class AverageMeter(object):
 def probe_batch(model, data, impulses='data', loss='mse'):
     """Engine.train_gradient_probe on a collated batch: the trainer's fp32 gradients against the float64 evaluation of the same
     batch on the device; weights, Adam state and iteration count are untouched.  loss='chamfer': `data` is collate_untracked's
-    and the result also has 'min_margin' (Engine.train_gradient_probe)"""
-    if loss not in LOSSES:
-        raise ValueError('loss must be one of %s, got %r' % (LOSSES, loss))
+    and the result also has 'min_margin' (Engine.train_gradient_probe).  A MATCH_LOSSES member is refused: no yardstick yet."""
+    check_loss(loss)
+    refuse_match_probe(loss)
     if impulses not in IMPULSES:
         raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
     check_depth_only(data, loss, impulses)
@@ -201,9 +225,11 @@ def probe_batch(model, data, impulses='data', loss='mse'):
 
 
 def check_probe_options(loss, grad_probe_every, probe_every):
-    """the two probe schedules of train() / main(): grad_probe_every (the MSE yardstick alone) and probe_every (every loss)"""
-    if loss not in LOSSES:
-        raise ValueError('loss must be one of %s, got %r' % (LOSSES, loss))
+    """the two probe schedules of train() / main(): grad_probe_every (the MSE yardstick alone) and probe_every (every loss of
+    LOSSES; the matching losses have no float64 yardstick yet and refuse both)"""
+    check_loss(loss)
+    if grad_probe_every > 0 or probe_every > 0:
+        refuse_match_probe(loss)
     if grad_probe_every > 0 and probe_every > 0:
         raise ValueError('give grad_probe_every or probe_every, not both')
     if loss == 'chamfer' and grad_probe_every > 0:
@@ -212,7 +238,7 @@ def check_probe_options(loss, grad_probe_every, probe_every):
 
 
 def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=None, first_epoch=0, grad_probe_every=0,
-          loss='mse', impulses='data', probe_every=0):
+          loss='mse', impulses='data', probe_every=0, match_weight=0.5):
     """train/train_gnn_dyn.py:134-246 without the file I/O: `dataloaders` = {'train': iterable of
     collated batches, 'valid': ...}.  Returns {'best_valid_loss', 'history': [(epoch, phase, rmse)]}.
     ckp(epoch, i, model): called after training batch i when i % ckp_per_iter == 0 (:217-218); first_epoch: the epoch
@@ -224,8 +250,10 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
     loss='chamfer' the log line also carries min_margin, the float64 side's smallest arg-min margin); giving both is refused.
     impulses='actions': the batches
     carry `.actions` and the model is trained through the push (run_batch); with real untracked data this is what makes
-    n_rollout > 1 meaningful.  The engine's camera must be set (main does it)."""
+    n_rollout > 1 meaningful.  The engine's camera must be set (main does it).  loss in MATCH_LOSSES: run_batch's matching loss
+    with match_weight; both probe options are refused with it."""
     check_probe_options(loss, grad_probe_every, probe_every)
+    check_loss(loss, match_weight)
     if impulses not in IMPULSES:
         raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
     loss_kind = loss
@@ -248,7 +276,7 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
                         line = 'grad_probe [%d][%d] worst %s rel %.3e (%s tape), loss diff %.3e' % (epoch, i, pr['worst'], pr['rel'],
                                                                                                   pr['tape'], pr['loss_diff'])
                         log(line + (', min_margin %.3e' % pr['min_margin'] if loss_kind == 'chamfer' else ''))
-                loss = run_batch(model, optimizer, data, phase, n_rollout, loss=loss_kind, impulses=impulses)
+                loss = run_batch(model, optimizer, data, phase, n_rollout, loss=loss_kind, impulses=impulses, match_weight=match_weight)
                 meter.update(loss, _np(data[0]).shape[0])
                 if log is not None and i % tc['log_per_iter'] == 0:
                     log('%s [%d][%d] LR: %.6f, Loss: %.6f (%.6f)' % (phase, epoch, i, optimizer.param_groups[0]['lr'],
@@ -285,7 +313,7 @@ def set_seed(seed):
 
 
 def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8, n_epoch=None, engine=None, grad_probe_every=0,
-         loss=None, impulses=None, probe_every=0, data='particles', target_den_scale=1.0):
+         loss=None, impulses=None, probe_every=0, data='particles', target_den_scale=1.0, match_weight=0.5):
     """The file-level part of train/train_gnn_dyn.py:train() (:45-130, :196-228): seed, the log directory with config.yaml
     and log.txt, the 'train' / 'valid' ParticleDatasets and their DeviceLoaders, a fresh model (torch.nn.Linear's default
     initialisation) or the resumed checkpoint, net_epoch_%d_iter_%d.pth every ckp_per_iter training batches and
@@ -298,7 +326,8 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
     data='depth': the episodes need only their depth PNGs and actions.p (a recorded robot episode): the datasets are
     DepthDatasets (every frame of a window sampled from its depth image on the device, the later frames at target_den_scale
     times the state's density), which implies loss='chamfer' and impulses='actions'; a contradicting value is refused.  loss /
-    impulses None: 'mse' / 'data', or what data implies.  chunk None: the dataset's default (64 samples; 16 for data='depth')."""
+    impulses None: 'mse' / 'data', or what data implies.  loss in MATCH_LOSSES (with match_weight for the mix): as 'chamfer', on
+    particles or depth.  chunk None: the dataset's default (64 samples; 16 for data='depth')."""
     import time
     import yaml
     from . import synthetic, weights
@@ -306,6 +335,7 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
     from .gnn_dyn import PropNetDiffDenModel
     loss, impulses = resolve_data_options(data, loss, impulses)
     check_probe_options(loss, grad_probe_every, probe_every)
+    check_loss(loss, match_weight)
     tc = config['train']
     resume = tc['particle'].get('resume', {'active': False, 'epoch': 0, 'iter': 0})
     if cam is None:
@@ -326,7 +356,7 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
         datasets = {ph: ParticleDataset(data_root, config, ph, cam, engine=engine) for ph in ('train', 'valid')}
     loaders = {ph: DeviceLoader(datasets[ph], tc['batch_size'], shuffle=(ph == 'train'), chunk=chunk, threads=threads)
                for ph in ('train', 'valid')}
-    if loss == 'chamfer' and data != 'depth':
+    if loss in UNTRACKED_LOSSES and data != 'depth':
         loaders = {ph: UntrackedLoader(loaders[ph], seed=tc['random_seed'] + k, reseed=(ph == 'valid'))
                    for k, ph in enumerate(('train', 'valid'))}
     model = PropNetDiffDenModel(config, engine=engine)
@@ -353,7 +383,8 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
 
         result = train(config, model, loaders, n_epoch=n_epoch, log=log, on_best=on_best, ckp=ckp,
                        first_epoch=resume['epoch'] if resume['active'] and resume['epoch'] > 0 else 0,
-                       grad_probe_every=grad_probe_every, loss=loss, impulses=impulses, probe_every=probe_every)
+                       grad_probe_every=grad_probe_every, loss=loss, impulses=impulses, probe_every=probe_every,
+                       match_weight=match_weight)
         for epoch, phase, rmse in result['history']:
             if phase == 'grad_probe':                   # logged when it was taken
                 continue
@@ -384,13 +415,16 @@ def _cli(argv=None):
                          'image on the device.  Implies --loss chamfer --impulses actions')
     ap.add_argument('--target-den-scale', type=float, default=1.0,
                     help='--data depth: the target frames are sampled at this multiple of the state\'s particle density')
-    ap.add_argument('--loss', choices=LOSSES, default=None,
-                    help='(default mse) chamfer: drop the recorded correspondence and train on the Chamfer distance to the untracked clouds')
+    ap.add_argument('--loss', choices=LOSSES + MATCH_LOSSES, default=None,
+                    help='(default mse) chamfer: drop the recorded correspondence and train on the Chamfer distance to the untracked '
+                         'clouds; match: on the one-to-one matching distance to them; chamfer+match: on their mix (--match-weight)')
+    ap.add_argument('--match-weight', type=float, default=0.5,
+                    help='--loss chamfer+match: (1 - w) Chamfer + w matching, w in (0, 1)')
     ap.add_argument('--impulses', choices=IMPULSES, default=None,
                     help='(default data) actions: compute every step\'s impulse from the recorded push on the state the model predicted')
     a = ap.parse_args(argv)
     try:
-        resolve_data_options(a.data, a.loss, a.impulses)
+        check_loss(resolve_data_options(a.data, a.loss, a.impulses)[0], a.match_weight)
     except ValueError as e:
         ap.error(str(e))
     config = default_config()
@@ -403,7 +437,7 @@ def _cli(argv=None):
         config['dataset']['n_timestep'] = a.n_timestep
     result, d = main(config, a.data_root, a.train_dir, chunk=a.chunk, threads=a.threads, n_epoch=a.epochs,
                      grad_probe_every=a.grad_probe_every, loss=a.loss, impulses=a.impulses, probe_every=a.probe_every,
-                     data=a.data, target_den_scale=a.target_den_scale)
+                     data=a.data, target_den_scale=a.target_den_scale, match_weight=a.match_weight)
     print('best valid loss %.6f, checkpoints in %s' % (np.sqrt(result['best_valid_loss']), d))
 
 

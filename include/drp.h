@@ -566,7 +566,8 @@ int drp_ptcl_dataset_time(drp_ctx* ctx, float* ms_out);
 /* ---- measurement / debugging ----------------------------------------------------- */
 /* HIP-event timing of one kernel class on the context's stream.  name: "graph",
  * "node_encode", "edge_encode", "project", "aggregate", "update", "predict", "reward",
- * "mppi", "prop" (the fused propagation-step kernel of DRP_ENGINE_FUSED / _LITE).  drp_probe_read returns total ms and launches since drp_probe_begin. */
+ * "mppi", "prop" (the fused propagation-step kernel of DRP_ENGINE_FUSED / _LITE), "loss" (the stand-alone metrics' kernel:
+ * drp_cloud_chamfer, drp_cloud_match).  drp_probe_read returns total ms and launches since drp_probe_begin. */
 int drp_probe_begin(drp_ctx* ctx, const char* kernel_class);
 int drp_probe_read(drp_ctx* ctx, double* total_ms, long* launches);
 /* What the propagation kernels (km_prop, km_prop3, km_rollout) EXECUTED since drp_probe_begin(ctx, "prop+work") -- the "prop"
@@ -745,6 +746,54 @@ int drp_cloud_chamfer_f64(drp_ctx* ctx, const float* p, const int32_t* n_p, cons
                           double* grad_p_out /*[B][N][3], nullable; scale = 1*/,
                           int32_t* nn_pq_out /*[B][N], nullable*/, int32_t* nn_qp_out /*[B][M], nullable*/,
                           double* margin_out /*[B][2]: p -> q, q -> p; nullable*/);
+
+/* ---- one-to-one matching (earth mover's) distance of two padded cloud batches and its gradient: what the Chamfer
+ * distance is blind to -- any number of predicted rows may share one nearest target there, here every row of the smaller cloud
+ * has a partner of its own.  p, q, the counts and the padding as drp_cloud_chamfer; r = min(n_p, n_q).
+ *   C[i][j] = |p_i - q_j|^2 in fp32, formed as drp_cloud_chamfer forms it (fp32 differences, dx*dx + dy*dy + dz*dz, no fma)
+ *   sigma   = the matching of every row of the SMALLER cloud to a distinct row of the larger one that minimises sum C (the
+ *             rectangular linear assignment problem; the exact optimum by shortest augmenting paths with duals, shortest
+ *             distances and reduced costs in double -- no epsilon)
+ *   match   = sum_pairs |p_i - q_j|^2 / (3 r), each pair's squared fp32 differences summed in double.  With n_p = n_q and the
+ *             matching the tracked correspondence this is the tracked loss's MSE term.
+ *   d match / d p_i = 2 (p_i - q_sigma(i)) / (3 r) for a matched row; +0.0 exactly for a row left unmatched (n_p > n_q) and for
+ *             padding.  sigma is a constant of the derivative.
+ * Deterministic: rows of the smaller cloud (p's where n_p = n_q) are inserted in ascending index, among equal shortest reduced
+ * costs the lowest column index wins, nothing is atomic -- the same bits from run to run and for a sample alone or inside any
+ * batch.  match_pq_out [B][N] / match_qp_out [B][M]: the partner's index, -1 for unmatched rows and padding.  dual_out
+ * [B][N + M]: the duals of p's rows, then of q's (0 on padding): u_i + v_j <= C[i][j], equal on matched pairs, 0 on the larger
+ * cloud's unmatched rows, sum u + sum v = sum_pairs C.  N and M are at most 1024 (the work is r^2 dependent steps of c / 64
+ * each); the kernel's loops are counted by r and c alone, whatever the values.  Contract as drp_cloud_chamfer: a one-shot in a
+ * buffer of its own that needs no weights, ends no session and leaves the engine, drp_last_dispatch and the trainer alone.
+ * DRP_EINVAL: a null argument (every output but terms_out is nullable), a count outside 1..N or 1..M, N or M outside 1..1024, a
+ * real row that is not finite. */
+int drp_cloud_match(drp_ctx* ctx, const float* p, const int32_t* n_p, const float* q, const int32_t* n_q,
+                    int B, int N, int M, double* terms_out /*[B]*/, float* grad_p_out /*[B][N][3], nullable*/,
+                    int32_t* match_pq_out /*[B][N], nullable*/, int32_t* match_qp_out /*[B][M], nullable*/,
+                    double* dual_out /*[B][N+M], nullable*/);
+
+/* The loop body of train/train_gnn_dyn.py:159-189 with the loss of each step chosen by argument: drp_train_step_untracked
+ * (states_delta given, actions NULL) or drp_train_step_actions (actions given, states_delta NULL) -- exactly one of the two --
+ * against targets [B][H][M][3] with target_nums [B][H], and
+ *   DRP_LOSS_CHAMFER        the Chamfer term: the bits of drp_train_step_untracked / drp_train_step_actions
+ *   DRP_LOSS_MATCH          the matching term of drp_cloud_match between s_pred_t[b, :n_b] and targets[b, t, :target_nums[b, t]],
+ *                           / (n_rollout B)
+ *   DRP_LOSS_CHAMFER_MATCH  (1 - w) (fwd + bwd) + w match with w = match_weight in (0, 1): the Chamfer kernel runs first and leaves
+ *                           a Chamfer-only step's terms and state gradient, the matching kernel behind it in the stream turns
+ *                           each into (1 - w) x it + its own share, in double, rounded once: one writer per element, a fixed
+ *                           order, and the loss is (1 - w) x the Chamfer call's + w x the matching call's to double rounding
+ * match_weight is read by the mix only.  match_out [H][B][N] (nullable; kinds with a matching): the partner in the target of every
+ * predicted row, per (step, sample), -1 for an unmatched row and padding.  Everything behind the loss gradient is
+ * drp_train_step's; it is no dispatch variant.  A diverged model's non-finite prediction ends in a NaN loss after the same
+ * number of steps.  Refusals (the context stays as it was): those of the call it generalises; N or M above 1024 with a matching;
+ * match_weight outside (0, 1) for the mix; both or neither of states_delta and actions; another loss_kind. */
+#define DRP_LOSS_CHAMFER 1
+#define DRP_LOSS_MATCH 2
+#define DRP_LOSS_CHAMFER_MATCH 3
+int drp_train_step_loss(drp_ctx* ctx, const float* states, const float* states_delta /*or NULL*/, const float* actions /*or NULL*/,
+                        const float* attrs, const int32_t* particle_nums, const float* particle_dens, int B, int N,
+                        const float* targets /*[B][H][M][3]*/, const int32_t* target_nums /*[B][H]*/, int M, int loss_kind,
+                        double match_weight, int mode, double* loss_out, float* grad_out, int32_t* match_out /*[H][B][N], nullable*/);
 
 #ifdef __cplusplus
 }

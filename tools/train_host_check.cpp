@@ -8,7 +8,8 @@
 // It stages batches as train_stage_batch does -- the same copies, to the offsets tr_layout gives, into a heap block of exactly
 // TrArena::bytes -- so a block that overlaps the next one or runs past the end is the sanitizer's finding; the offsets are held
 // to the documented layout as well.  The float64 yardsticks' upload (tr64_layout: train_grad_f64_body's one vector, with and
-// without target clouds) is staged the same way.  No device is touched.
+// without target clouds) is staged the same way, and so is drp_cloud_match's buffer (cm_layout: the inputs staged, every output
+// block written in full), with the check that refuses a real row that is no number.  No device is touched.
 //
 //   train_host_check layout64 B H N M actions     prints tr64_layout's eight fields (4-byte words) and exits
 #include <cstdio>
@@ -126,6 +127,40 @@ static void stage64(int B, int H, int N, int M, bool actions) {
     std::free(host);
 }
 
+// drp_cloud_match's buffer as capi_match.h uses it: the inputs copied into a vector of exactly CmLayout::in_bytes, every output
+// block written in full inside a block of exactly CmLayout::bytes
+static void stage_match(int B, int N, int M) {
+    const CmLayout lay = cm_layout(B, N, M);
+    const size_t bn = (size_t)B * N, bm = (size_t)B * M;
+    const size_t off[] = {lay.pts_p, lay.pts_q, lay.n_p, lay.n_q, lay.terms, lay.grad, lay.pq, lay.qp, lay.dual, lay.bytes};
+    const size_t len[] = {bn * 12, bm * 12, (size_t)B * 4, (size_t)B * 4, (size_t)B * 8, bn * 12, bn * 4, bm * 4, (bn + bm) * 8};
+    for (int k = 0; k < 9; ++k) {
+        EXPECT(off[k] % 16 == 0);
+        EXPECT(off[k] + len[k] <= off[k + 1]);
+        EXPECT(off[k + 1] - (off[k] + len[k]) < 16);
+    }
+    EXPECT(lay.pts_p == 0 && lay.terms == lay.in_bytes);
+    std::vector<float> p(bn * 3, 1.0f), q(bm * 3, 2.0f);
+    std::vector<int32_t> n_p(B, N), n_q(B, M);
+    std::vector<char> stage(lay.in_bytes);
+    std::memcpy(stage.data() + lay.pts_p, p.data(), bn * 3 * sizeof(float));
+    std::memcpy(stage.data() + lay.pts_q, q.data(), bm * 3 * sizeof(float));
+    std::memcpy(stage.data() + lay.n_p, n_p.data(), (size_t)B * sizeof(int32_t));
+    std::memcpy(stage.data() + lay.n_q, n_q.data(), (size_t)B * sizeof(int32_t));
+    char* io = static_cast<char*>(std::malloc(lay.bytes));
+    std::memcpy(io, stage.data(), lay.in_bytes);
+    for (int k = 4; k < 9; ++k) std::memset(io + off[k], k, len[k]);       // the kernel's stores, block by block
+    float f; int32_t n;
+    std::memcpy(&f, io + lay.pts_p + (bn * 3 - 1) * 4, 4);
+    EXPECT(f == 1.0f);
+    std::memcpy(&f, io + lay.pts_q + (bm * 3 - 1) * 4, 4);
+    EXPECT(f == 2.0f);
+    std::memcpy(&n, io + lay.n_q + (size_t)(B - 1) * 4, 4);
+    EXPECT(n == M);
+    for (int k = 4; k < 9; ++k) EXPECT(io[off[k]] == k && io[off[k] + len[k] - 1] == k);
+    std::free(io);
+}
+
 int main(int argc, char** argv) {
     if (argc == 7 && std::strcmp(argv[1], "layout64") == 0) {
         const Tr64Arena a = tr64_layout(std::atoi(argv[2]), std::atoi(argv[3]), std::atoi(argv[4]), std::atoi(argv[5]), std::atoi(argv[6]) != 0);
@@ -141,6 +176,26 @@ int main(int argc, char** argv) {
             stage64(s[0], s[1], s[2], s[3], actions != 0);
         }
     stage64(1, 1, 4096, 4096, false);                            // the largest clouds of one (sample, step)
+    const int mshapes[][3] = {{1, 1, 1}, {1, 5, 3}, {3, 7, 9}, {2, 65, 64}, {1, 1024, 1024}, {5, 1024, 1}, {4, 300, 257}};
+    for (const auto& s : mshapes) stage_match(s[0], s[1], s[2]);
+    {
+        // the finiteness check reads the real rows only, every one of them, and no further
+        const float inf32 = std::numeric_limits<float>::infinity(), nan32 = std::numeric_limits<float>::quiet_NaN();
+        const int B = 2, N = 3;
+        const int32_t counts[2] = {2, 3};
+        float* x = static_cast<float*>(std::malloc((size_t)B * N * 3 * sizeof(float)));     // exactly [B][N][3]
+        for (int e = 0; e < B * N * 3; ++e) x[e] = 0.25f * e;
+        EXPECT(first_nonfinite_row(x, counts, B, N) == -1);
+        x[2 * 3 + 1] = nan32;                                    // sample 0's padding row
+        EXPECT(first_nonfinite_row(x, counts, B, N) == -1);
+        x[(1 * N + 2) * 3 + 2] = inf32;                          // the last coordinate of the last real row
+        EXPECT(first_nonfinite_row(x, counts, B, N) == 1 * N + 2);
+        x[1 * 3 + 0] = nan32;
+        EXPECT(first_nonfinite_row(x, counts, B, N) == 1);
+        const int32_t over[2] = {7, 3};                          // a count beyond N is read up to N (the entry point refuses it first)
+        EXPECT(first_nonfinite_row(x, over, B, N) == 1);
+        std::free(x);
+    }
 
     // the push check, with the demo camera's map (x, z, -y + 18 scaled by 1 / 24: a camera that looks straight down)
     const float m[12] = {1, 0, 0, 0, 0, 0, 1, 0, 0, -1, 0, 18};
