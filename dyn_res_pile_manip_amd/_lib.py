@@ -33,6 +33,7 @@ ENGINES = {'valu': ENGINE_VALU, 'mfma': ENGINE_MFMA, 'split': ENGINE_SPLIT, 'fus
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
 c_double_p = ctypes.POINTER(ctypes.c_double)
+c_int32_p = ctypes.POINTER(ctypes.c_int32)
 c_int16_p = ctypes.POINTER(ctypes.c_int16)
 c_uint8_p = ctypes.POINTER(ctypes.c_uint8)
 
@@ -107,14 +108,13 @@ SIGNATURES = {
     'drp_fps': (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                ctypes.POINTER(ctypes.c_int32), c_float_p]),
     'drp_train_begin': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_double]),
-    'drp_train_step': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.POINTER(ctypes.c_int32),
-                                      c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_float_p]),
-    'drp_train_step_untracked': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.POINTER(ctypes.c_int32),
-                                                c_float_p, ctypes.c_int, ctypes.c_int, c_float_p, ctypes.POINTER(ctypes.c_int32),
-                                                ctypes.c_int, ctypes.c_int, c_double_p, c_float_p]),
-    'drp_train_step_actions': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.POINTER(ctypes.c_int32),
-                                              c_float_p, ctypes.c_int, ctypes.c_int, c_float_p, ctypes.POINTER(ctypes.c_int32),
-                                              ctypes.c_int, ctypes.c_int, c_double_p, c_float_p]),
+    'drp_train_step': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_int32_p, c_float_p, ctypes.c_int,
+                                      ctypes.c_int, ctypes.c_int, c_double_p, c_float_p]),
+    'drp_train_step_untracked': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_int32_p, c_float_p,
+                                                ctypes.c_int, ctypes.c_int, c_float_p, c_int32_p, ctypes.c_int, ctypes.c_int,
+                                                c_double_p, c_float_p]),
+    'drp_train_step_actions': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_int32_p, c_float_p, ctypes.c_int,
+                                              ctypes.c_int, c_float_p, c_int32_p, ctypes.c_int, ctypes.c_int, c_double_p, c_float_p]),
     'drp_train_set_lr': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double]),
     'drp_get_weights': (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_size_t]),
     'drp_depth2fgpcd': (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int,
@@ -194,29 +194,23 @@ SIGNATURES = {
                                           ctypes.c_int, ctypes.c_int, c_double_p]),
     'drp_gd_grad_f64': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.c_int, ctypes.c_int, c_float_p,
                                        ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p]),
-    'drp_train_grad_f64': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.POINTER(ctypes.c_int32), c_float_p,
-                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p]),
-    'drp_train_grad_f64_actions': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.POINTER(ctypes.c_int32),
-                                                  c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p,
-                                                  c_double_p, c_double_p]),
-    'drp_cloud_chamfer': (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.POINTER(ctypes.c_int32), c_float_p,
-                                         ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_float_p,
-                                         ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
-    'drp_train_grad_f64_untracked': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p,
-                                                    ctypes.POINTER(ctypes.c_int32), c_float_p, ctypes.c_int, ctypes.c_int,
-                                                    ctypes.c_int, c_float_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int,
-                                                    c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
-    'drp_cloud_chamfer_f64': (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.POINTER(ctypes.c_int32), c_float_p,
-                                             ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p,
-                                             c_double_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
-                                             c_double_p]),
-    'drp_cloud_match': (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.POINTER(ctypes.c_int32), c_float_p,
-                                       ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_float_p,
-                                       ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), c_double_p]),
-    'drp_train_step_loss': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p,
-                                           ctypes.POINTER(ctypes.c_int32), c_float_p, ctypes.c_int, ctypes.c_int, c_float_p,
-                                           ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
-                                           ctypes.POINTER(ctypes.c_double), c_float_p, ctypes.POINTER(ctypes.c_int32)]),
+    'drp_train_grad_f64': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_int32_p, c_float_p, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p]),
+    'drp_train_grad_f64_actions': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_int32_p, c_float_p,
+                                                  ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p,
+                                                  c_double_p]),
+    'drp_cloud_chamfer': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_int32_p, c_float_p, c_int32_p, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_int, c_double_p, c_float_p, c_int32_p, c_int32_p]),
+    'drp_train_grad_f64_untracked': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, c_int32_p,
+                                                    c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_float_p, c_int32_p,
+                                                    ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    'drp_cloud_chamfer_f64': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_int32_p, c_float_p, c_int32_p, ctypes.c_int,
+                                             ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_int32_p, c_int32_p, c_double_p]),
+    'drp_cloud_match': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_int32_p, c_float_p, c_int32_p, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_int, c_double_p, c_float_p, c_int32_p, c_int32_p, c_double_p]),
+    'drp_train_step_loss': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, c_int32_p, c_float_p,
+                                           ctypes.c_int, ctypes.c_int, c_float_p, c_int32_p, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_double, ctypes.c_int, c_double_p, c_float_p, c_int32_p]),
 }
 
 _lib = None

@@ -315,9 +315,8 @@ struct drp_ctx {
     DevBuf grad64_ws, grad64_io;    // drp_gd_grad_f64 and drp_train_grad_f64 (capi_grad_f64.h; one-shots that keep nothing between calls): a chunk's tape
                                     // and reverse pass (the trainer: and its samples' gradient accumulators); the batch's inputs and results
 
-    DevBuf ch_io;                   // drp_cloud_chamfer (capi_chamfer.h; a one-shot that keeps nothing between calls): its inputs and results
-    DevBuf ch64_io;                 // drp_cloud_chamfer_f64: the same, in a buffer of its own
-    DevBuf ma_io;                   // drp_cloud_match (capi_match.h): the same, in a buffer of its own
+    DevBuf cloud_io;                // drp_cloud_chamfer, drp_cloud_chamfer_f64, drp_cloud_match (capi_pipeline.h: cloud_begin; one-shots that
+                                    // end in a wait and keep nothing between calls): the running call's inputs and results
     DevBuf tr_match;                // drp_train_step_loss: the partner of every predicted row [H][B][N] (ka_match<true>)
 
     // re-packing after an optimiser step on the device (k_train.h): gather maps of the plain packers, pinned copy of the blob

@@ -310,11 +310,9 @@ int tr64_chunk(drp_ctx* c, const Tr64Ws& k, const Tr64Io& io, int b0, int bc, in
         // the same slot of the stream and the same outputs: slice t + 1 of the tape's states against step t of the target clouds,
         // the arg-mins taken here in double
         Kc64Args a{};
-        a.p64 = k.tape.state + pn * 3; a.p_bstride = (size_t)N * 3; a.p_tstride = pn * 3;
-        a.tgt = io.targets; a.q_bstride = (size_t)H * io.M * 3; a.q_tstride = (size_t)io.M * 3;
-        a.n_p = io.nums;
-        a.n_q = io.tnums; a.nq_bstride = H; a.nq_tstride = 1;
-        a.b_off = b0; a.B = B; a.N = N; a.M = io.M;
+        a.cp = tr_cloud_pair((size_t)N * 3, pn * 3, io.nums, io.targets, io.tnums, H, N, io.M);
+        a.p64 = k.tape.state + pn * 3;
+        a.b_off = b0; a.B = B;
         a.scale = 1.0 / ((double)H * (double)B);
         a.grad = k.rev.g_state; a.terms = io.terms; a.margin = io.margin;
         hipLaunchKernelGGL((kc64_chamfer<true>), dim3(bc, H), dim3(KC64_THREADS), 0, st, a);
@@ -382,33 +380,21 @@ int drp_gd_grad_f64(drp_ctx* c, const float* s0, const float* attr, const float*
 }
 
 namespace {
-// what seeds the reverse pass: the tracked MSE, or the Chamfer loss against untracked target clouds (k_chamfer_f64.h)
-struct Tr64Loss {
-    bool chamfer = false;
-    const float* targets = nullptr;         // [B][H][M][3]
-    const int32_t* target_nums = nullptr;   // [B][H]
-    int M = 0;
-    double* margin_out = nullptr;           // [H][B], nullable
-};
 // drp_train_grad_f64, drp_train_grad_f64_actions and drp_train_grad_f64_untracked: one body; `impulses` is states_delta
-// [B][H][N][3], or with `actions` the pushes [B][H][4]; the loss kind and the targets in `lk`
+// [B][H][N][3], or with `actions` the pushes [B][H][4]; the loss kind and the targets in `lk` (capi_train.h: TrLoss) -- the tracked
+// MSE, or the Chamfer loss against untracked target clouds (k_chamfer_f64.h); the matching kinds have no yardstick
 int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, bool actions, const float* attrs,
-                        const int32_t* particle_nums, const float* particle_dens, int B, int N, int n_rollout, const Tr64Loss& lk,
+                        const int32_t* particle_nums, const float* particle_dens, int B, int N, int n_rollout, const TrLoss& lk,
                         double* loss_out, double* loss_terms_out, double* grad_out, double* grad_state_out) {
     CHK(need(c, true, actions, false));
+    if (lk.match()) return fail(c, DRP_EINVAL, "no float64 yardstick for loss kind %d", lk.kind);
     CHK(check_bn(c, B, N));
     if (!states || !impulses || !attrs || !particle_nums || !particle_dens) return fail(c, DRP_EINVAL, "null argument");
     if (n_rollout < 1 || n_rollout > 64) return fail(c, DRP_EINVAL, "bad n_rollout=%d", n_rollout);
-    for (int b = 0; b < B; ++b)
-        if (particle_nums[b] <= 0 || particle_nums[b] > N)
-            return fail(c, DRP_EINVAL, "particle_nums[%d]=%d outside 1..%d", b, particle_nums[b], N);
-    if (lk.chamfer) {
-        if (!lk.targets || !lk.target_nums) return fail(c, DRP_EINVAL, "null argument");
-        if (lk.M <= 0 || lk.M > KC64_MAX_POINTS) return fail(c, DRP_EINVAL, "bad shape M=%d (1..%d)", lk.M, KC64_MAX_POINTS);
-        for (int e = 0; e < B * n_rollout; ++e)
-            if (lk.target_nums[e] <= 0 || lk.target_nums[e] > lk.M)
-                return fail(c, DRP_EINVAL, "target_nums[%d][%d]=%d outside 1..%d", e / n_rollout, e % n_rollout, lk.target_nums[e],
-                            lk.M);
+    CHK(check_particle_nums(c, particle_nums, B, N));
+    if (lk.chamfer()) {
+        CHK(check_target_clouds(c, lk, KC64_MAX_POINTS, "shape"));
+        CHK(check_target_nums(c, lk, B, n_rollout));
     }
     if (actions) CHK(check_pushes(c, impulses, B, n_rollout));
     HIPCHK(c, hipSetDevice(c->device));
@@ -423,7 +409,7 @@ int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, 
     k.carve(c->grad64_ws.p, Bc, (size_t)N, (size_t)H);
     // the whole batch's inputs in one upload (train_host.h: tr64_layout): states | impulses | attrs[:, 0] | densities | particle
     // counts [| target clouds | their counts], then the results: terms | total [| margins]
-    const int M = lk.chamfer ? lk.M : 0;
+    const int M = lk.chamfer() ? lk.M : 0;
     const Tr64Arena lay = tr64_layout(B, H, N, M, actions);
     std::vector<float> host(lay.words);
     memcpy(host.data() + lay.states, states, (lay.sdelta - lay.states) * sizeof(float));
@@ -469,14 +455,14 @@ int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, 
 int drp_train_grad_f64(drp_ctx* c, const float* states, const float* states_delta, const float* attrs, const int32_t* particle_nums,
                        const float* particle_dens, int B, int N, int n_rollout, double* loss_out, double* loss_terms_out,
                        double* grad_out, double* grad_state_out) {
-    return train_grad_f64_body(c, states, states_delta, false, attrs, particle_nums, particle_dens, B, N, n_rollout, Tr64Loss{},
+    return train_grad_f64_body(c, states, states_delta, false, attrs, particle_nums, particle_dens, B, N, n_rollout, TrLoss{},
                                loss_out, loss_terms_out, grad_out, grad_state_out);
 }
 
 int drp_train_grad_f64_actions(drp_ctx* c, const float* states, const float* actions, const float* attrs,
                                const int32_t* particle_nums, const float* particle_dens, int B, int N, int n_rollout,
                                double* loss_out, double* loss_terms_out, double* grad_out, double* grad_state_out) {
-    return train_grad_f64_body(c, states, actions, true, attrs, particle_nums, particle_dens, B, N, n_rollout, Tr64Loss{}, loss_out,
+    return train_grad_f64_body(c, states, actions, true, attrs, particle_nums, particle_dens, B, N, n_rollout, TrLoss{}, loss_out,
                                loss_terms_out, grad_out, grad_state_out);
 }
 
@@ -487,8 +473,8 @@ int drp_train_grad_f64_untracked(drp_ctx* c, const float* states, const float* s
     if (!c) return DRP_EINVAL;
     if ((states_delta != nullptr) == (actions != nullptr))
         return fail(c, DRP_EINVAL, "exactly one of states_delta and actions must be given");
-    Tr64Loss lk;
-    lk.chamfer = true; lk.targets = targets; lk.target_nums = target_nums; lk.M = M; lk.margin_out = margin_out;
+    TrLoss lk = TrLoss::against(TR_LOSS_CHAMFER, targets, target_nums, M);
+    lk.margin_out = margin_out;
     return train_grad_f64_body(c, states, actions != nullptr ? actions : states_delta, actions != nullptr, attrs, particle_nums,
                                particle_dens, B, N, n_rollout, lk, loss_out, loss_terms_out, grad_out, grad_state_out);
 }

@@ -1,5 +1,5 @@
 // capi_pipeline.h -- a section of the C ABI's translation unit (textually included by drp_capi.hip, which has the order of the sections).
-// Here: internal helpers and pipelines: guarded waits, probes, the graph build, one predict_one_step on every engine (run_step), reward, rollouts (run_rollout), weight packing, deferred weight gradients, the range check.
+// Here: internal helpers and pipelines: guarded waits, probes, the graph build, one predict_one_step on every engine (run_step), reward, rollouts (run_rollout), weight packing, deferred weight gradients, the range check, what a one-shot on two clouds does around its launch.
 
 namespace {
 
@@ -1188,6 +1188,68 @@ int f64_refresh_weights(drp_ctx* c) {
 int check_bn(drp_ctx* c, int B, int N) {
     if (B <= 0 || N <= 0 || N > 4096) return fail(c, DRP_EINVAL, "bad shape B=%d N=%d (N <= 4096)", B, N);
     return DRP_OK;
+}
+
+// ---- a one-shot on two clouds: checks, staging, copies back --------------------------------------------------------------
+// One buffer for the three of them (c->cloud_io; train_host.h: CloudLayout): every call ends in a wait, keeps nothing, and reads
+// back only blocks its own kernel wrote.  No weights, no session begun or ended, nothing of the engine, the dispatch marks or the
+// trainer touched.
+
+// the arguments every one of them refuses, in this order; n_cap: the cap on N beyond check_bn's (0: none), `what`: the caps' suffix
+int cloud_check(drp_ctx* c, const float* p, const int32_t* n_p, const float* q, const int32_t* n_q, int B, int N, int M,
+                const double* terms_out, int n_cap, int m_cap, const char* what) {
+    if (!c) return DRP_EINVAL;
+    CHK(check_bn(c, B, N));
+    if (n_cap > 0 && N > n_cap) return fail(c, DRP_EINVAL, "bad shape N=%d (1..%d%s)", N, n_cap, what);
+    if (M <= 0 || M > m_cap) return fail(c, DRP_EINVAL, "bad shape M=%d (1..%d%s)", M, m_cap, what);
+    if (!p || !n_p || !q || !n_q || !terms_out) return fail(c, DRP_EINVAL, "null argument");
+    for (int b = 0; b < B; ++b) {
+        if (n_p[b] <= 0 || n_p[b] > N) return fail(c, DRP_EINVAL, "n_p[%d]=%d outside 1..%d", b, n_p[b], N);
+        if (n_q[b] <= 0 || n_q[b] > M) return fail(c, DRP_EINVAL, "n_q[%d]=%d outside 1..%d", b, n_q[b], M);
+    }
+    return DRP_OK;
+}
+
+struct CloudCall {
+    CloudLayout lay{};
+    void* const* outs = nullptr;    // the caller's arrays, one per block of lay.out (null: not asked for)
+    std::vector<char> stage;        // the inputs as uploaded: read until cloud_finish's wait
+    char* io = nullptr;             // c->cloud_io
+    CloudPair cp{};                 // the pair on the device, step strides 0
+    const float* p_dev = nullptr;   // p's rows there
+    // block k on the device for the kernel to write, null where the caller did not ask for it
+    template <typename T>
+    T* out(int k) const { return outs[k] ? reinterpret_cast<T*>(io + lay.out[k]) : nullptr; }
+};
+// the inputs staged and on their way up, the view filled
+int cloud_begin(drp_ctx* c, CloudCall& k, const CloudLayout& lay, void* const* outs, const float* p, const int32_t* n_p,
+                const float* q, const int32_t* n_q, int B, int N, int M) {
+    HIPCHK(c, hipSetDevice(c->device));
+    k.lay = lay; k.outs = outs;
+    CHK(ensure(c, c->cloud_io, lay.bytes));
+    k.stage.resize(lay.in_bytes);
+    memcpy(k.stage.data() + lay.pts_p, p, (size_t)B * N * 3 * sizeof(float));
+    memcpy(k.stage.data() + lay.pts_q, q, (size_t)B * M * 3 * sizeof(float));
+    memcpy(k.stage.data() + lay.n_p, n_p, (size_t)B * sizeof(int));
+    memcpy(k.stage.data() + lay.n_q, n_q, (size_t)B * sizeof(int));
+    CHK(h2d(c, c->cloud_io, k.stage.data(), lay.in_bytes));
+    k.io = ptr<char>(c->cloud_io);
+    k.p_dev = reinterpret_cast<const float*>(k.io + lay.pts_p);
+    k.cp.p_bstride = (size_t)N * 3; k.cp.p_tstride = 0;
+    k.cp.q = reinterpret_cast<const float*>(k.io + lay.pts_q); k.cp.q_bstride = (size_t)M * 3; k.cp.q_tstride = 0;
+    k.cp.n_p = reinterpret_cast<const int*>(k.io + lay.n_p);
+    k.cp.n_q = reinterpret_cast<const int*>(k.io + lay.n_q); k.cp.nq_bstride = 1; k.cp.nq_tstride = 0;
+    k.cp.N = N; k.cp.M = M;
+    return DRP_OK;
+}
+// behind the launch of `kernel`: every block asked for comes back, then the wait
+int cloud_finish(drp_ctx* c, const CloudCall& k, const char* kernel) {
+    if (hipGetLastError() != hipSuccess) { (void)drp_sync(c); return fail(c, DRP_EHIP, "%s launch", kernel); }   // (the staging vector is still being read)
+    int rc = DRP_OK;
+    for (int b = 0; b < k.lay.n_out; ++b)
+        if (rc == DRP_OK && k.outs[b]) rc = d2h(c, k.outs[b], k.io + k.lay.out[b], k.lay.out_bytes[b]);
+    const int rw = guarded_wait(c, nullptr);            // also on an error above: the staging vector goes out of scope
+    return rc != DRP_OK ? rc : rw;
 }
 
 }  // namespace

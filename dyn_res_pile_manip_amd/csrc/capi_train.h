@@ -11,7 +11,8 @@ const int* tr_nums(const drp_ctx* c, const TrArena& lay) {
 }
 // what seeds the reverse pass: the tracked loss (kt_mse_grad against the given next states) or the Chamfer loss against
 // untracked target clouds (k_chamfer.h), the one-to-one matching loss against them (k_match.h), or the two mixed; the targets as
-// the HOST gave them (the entry point stages them behind the batch).  The kinds beyond the MSE are include/drp.h's DRP_LOSS_*
+// the HOST gave them (the entry point stages them behind the batch).  The kinds beyond the MSE are include/drp.h's DRP_LOSS_*.
+// The float64 yardstick (capi_grad_f64.h) reads the same description; it has the MSE and the Chamfer loss
 enum { TR_LOSS_MSE = 0, TR_LOSS_CHAMFER = DRP_LOSS_CHAMFER, TR_LOSS_MATCH = DRP_LOSS_MATCH, TR_LOSS_CHAMFER_MATCH = DRP_LOSS_CHAMFER_MATCH };
 struct TrLoss {
     int kind = TR_LOSS_MSE;
@@ -20,9 +21,45 @@ struct TrLoss {
     int M = 0;
     double match_weight = 0.0;              // TR_LOSS_CHAMFER_MATCH: (1 - w) Chamfer + w matching
     int32_t* match_out = nullptr;           // the caller's [H][B][N], nullable: every predicted row's partner (kinds with a matching)
+    double* margin_out = nullptr;           // float64 only: the caller's [H][B], nullable (kc64_chamfer's arg-min margins)
     bool chamfer() const { return kind == TR_LOSS_CHAMFER || kind == TR_LOSS_CHAMFER_MATCH; }
     bool match() const { return kind == TR_LOSS_MATCH || kind == TR_LOSS_CHAMFER_MATCH; }
+    static TrLoss against(int kind, const float* targets, const int32_t* target_nums, int M) {
+        TrLoss lk;
+        lk.kind = kind; lk.targets = targets; lk.target_nums = target_nums; lk.M = M;
+        return lk;
+    }
 };
+// ---- the checks both trainers make of a batch and its loss; each body calls them where its own order of refusals has them ----
+int check_particle_nums(drp_ctx* c, const int32_t* particle_nums, int B, int N) {
+    for (int b = 0; b < B; ++b)
+        if (particle_nums[b] <= 0 || particle_nums[b] > N)
+            return fail(c, DRP_EINVAL, "particle_nums[%d]=%d outside 1..%d", b, particle_nums[b], N);
+    return DRP_OK;
+}
+// the target clouds are there and no larger than the loss kernel's `m_cap` (`what`: the caller's word for M) ...
+int check_target_clouds(drp_ctx* c, const TrLoss& lk, int m_cap, const char* what) {
+    if (!lk.targets || !lk.target_nums) return fail(c, DRP_EINVAL, "null argument");
+    if (lk.M <= 0 || lk.M > m_cap) return fail(c, DRP_EINVAL, "bad %s M=%d (1..%d)", what, lk.M, m_cap);
+    return DRP_OK;
+}
+// ... and every (sample, step) has 1..M real rows
+int check_target_nums(drp_ctx* c, const TrLoss& lk, int B, int H) {
+    for (int e = 0; e < B * H; ++e)
+        if (lk.target_nums[e] <= 0 || lk.target_nums[e] > lk.M)
+            return fail(c, DRP_EINVAL, "target_nums[%d][%d]=%d outside 1..%d", e / H, e % H, lk.target_nums[e], lk.M);
+    return DRP_OK;
+}
+// step t of the predictions (p's strides) against step t of the target clouds [B][H][M][3] and their counts [B][H] as staged
+CloudPair tr_cloud_pair(size_t p_bstride, size_t p_tstride, const int* nums, const float* targets, const int* tnums, int H, int N, int M) {
+    CloudPair cp{};
+    cp.p_bstride = p_bstride; cp.p_tstride = p_tstride;
+    cp.q = targets; cp.q_bstride = (size_t)H * M * 3; cp.q_tstride = (size_t)M * 3;
+    cp.n_p = nums;
+    cp.n_q = tnums; cp.nq_bstride = H; cp.nq_tstride = 1;
+    cp.N = N; cp.M = M;
+    return cp;
+}
 // one pass over a staged batch: everything train_forward_backward reads beside the shapes and the session
 struct TrainPass {
     int engine = DRP_ENGINE_FUSED;  // which engine writes the tape (pick_tape_engine)
@@ -79,13 +116,11 @@ int train_forward_backward(drp_ctx* c, int B, int N, const TrainPass& tp) {
         const char* ar = static_cast<const char*>(c->tr_arena.p);
         float* const zero = backward ? ptr<float>(c->tr_grad) : (float*)nullptr;
         const size_t n_zero = (size_t)TR_GRAD_PAD + (size_t)H * c->n_cu + 1;
+        const CloudPair cp = tr_cloud_pair(hstride, (size_t)N * 3, nums, reinterpret_cast<const float*>(ar + lay.targets),
+                                           reinterpret_cast<const int*>(ar + lay.tnums), H, N, lk.M);
         if (lk.chamfer()) {
             KcArgs a{};
-            a.pred = states; a.p_bstride = hstride; a.p_tstride = (size_t)N * 3;
-            a.tgt = reinterpret_cast<const float*>(ar + lay.targets); a.q_bstride = (size_t)H * lk.M * 3; a.q_tstride = (size_t)lk.M * 3;
-            a.n_p = nums;
-            a.n_q = reinterpret_cast<const int*>(ar + lay.tnums); a.nq_bstride = H; a.nq_tstride = 1;
-            a.N = N; a.M = lk.M;
+            a.cp = cp; a.pred = states;
             a.scale = scale;               // (the mix too: the matching kernel weighs what this one leaves, in double)
             a.grad = g_state; a.terms = loss;
             a.zero = zero; a.n_zero = n_zero;
@@ -96,11 +131,7 @@ int train_forward_backward(drp_ctx* c, int B, int N, const TrainPass& tp) {
             // terms it finds into (1 - w) x them + its own share -- one writer per element, so the sum's order is fixed, and
             // the Chamfer share is (1 - w) x the bits of a Chamfer-only step whatever w is
             KaArgs a{};
-            a.pred = states; a.p_bstride = hstride; a.p_tstride = (size_t)N * 3;
-            a.tgt = reinterpret_cast<const float*>(ar + lay.targets); a.q_bstride = (size_t)H * lk.M * 3; a.q_tstride = (size_t)lk.M * 3;
-            a.n_p = nums;
-            a.n_q = reinterpret_cast<const int*>(ar + lay.tnums); a.nq_bstride = H; a.nq_tstride = 1;
-            a.N = N; a.M = lk.M;
+            a.cp = cp; a.pred = states;
             a.scale = lk.chamfer() ? (double)scale * lk.match_weight : (double)scale;
             a.keep = lk.chamfer() ? 1.0 - lk.match_weight : 0.0;
             a.grad = g_state; a.terms = loss;
@@ -320,22 +351,16 @@ int train_check_args(drp_ctx* c, const float* states, const float* impulses, boo
         CHK(check_pushes(c, impulses, B, c->tr_nroll));
     }
     if (mode < DRP_TRAIN_EVAL || mode > DRP_TRAIN_UPDATE) return fail(c, DRP_EINVAL, "bad mode %d", mode);
-    for (int b = 0; b < B; ++b)
-        if (particle_nums[b] <= 0 || particle_nums[b] > N)
-            return fail(c, DRP_EINVAL, "particle_nums[%d]=%d outside 1..%d", b, particle_nums[b], N);
+    CHK(check_particle_nums(c, particle_nums, B, N));
     if (lk.kind != TR_LOSS_MSE) {
-        if (!lk.targets || !lk.target_nums) return fail(c, DRP_EINVAL, "null argument");
-        if (lk.M <= 0 || lk.M > KC_MAX_POINTS) return fail(c, DRP_EINVAL, "bad target size M=%d (1..%d)", lk.M, KC_MAX_POINTS);
+        CHK(check_target_clouds(c, lk, KC_MAX_POINTS, "target size"));
         if (lk.match()) {
             if (N > KA_MAX_POINTS || lk.M > KA_MAX_POINTS)
                 return fail(c, DRP_EINVAL, "a matching loss takes clouds of 1..%d points: N=%d M=%d", KA_MAX_POINTS, N, lk.M);
             if (lk.kind == TR_LOSS_CHAMFER_MATCH && !(lk.match_weight > 0.0 && lk.match_weight < 1.0))
                 return fail(c, DRP_EINVAL, "match_weight %g outside (0, 1)", lk.match_weight);
         }
-        for (int e = 0; e < B * c->tr_nroll; ++e)
-            if (lk.target_nums[e] <= 0 || lk.target_nums[e] > lk.M)
-                return fail(c, DRP_EINVAL, "target_nums[%d][%d]=%d outside 1..%d", e / c->tr_nroll, e % c->tr_nroll,
-                            lk.target_nums[e], lk.M);
+        CHK(check_target_nums(c, lk, B, c->tr_nroll));
     }
     return DRP_OK;
 }
@@ -517,19 +542,16 @@ int drp_train_step(drp_ctx* c, const float* states, const float* states_delta, c
 int drp_train_step_untracked(drp_ctx* c, const float* states, const float* states_delta, const float* attrs,
                              const int32_t* particle_nums, const float* particle_dens, int B, int N, const float* targets,
                              const int32_t* target_nums, int M, int mode, double* loss_out, float* grad_out) {
-    TrLoss lk;
-    lk.kind = TR_LOSS_CHAMFER; lk.targets = targets; lk.target_nums = target_nums; lk.M = M;
-    return train_step_body(c, states, states_delta, false, attrs, particle_nums, particle_dens, B, N, lk, mode, loss_out, grad_out);
+    return train_step_body(c, states, states_delta, false, attrs, particle_nums, particle_dens, B, N,
+                           TrLoss::against(TR_LOSS_CHAMFER, targets, target_nums, M), mode, loss_out, grad_out);
 }
 
 // the same body with each step's impulse evaluated from the batch's pushes on the state the step reads (TrainPass::actions)
 int drp_train_step_actions(drp_ctx* c, const float* states, const float* actions, const float* attrs, const int32_t* particle_nums,
                            const float* particle_dens, int B, int N, const float* targets, const int32_t* target_nums, int M,
                            int mode, double* loss_out, float* grad_out) {
-    TrLoss lk;
-    if (targets != nullptr || target_nums != nullptr || M != 0) {
-        lk.kind = TR_LOSS_CHAMFER; lk.targets = targets; lk.target_nums = target_nums; lk.M = M;
-    }
+    const bool untracked = targets != nullptr || target_nums != nullptr || M != 0;
+    const TrLoss lk = untracked ? TrLoss::against(TR_LOSS_CHAMFER, targets, target_nums, M) : TrLoss{};
     return train_step_body(c, states, actions, true, attrs, particle_nums, particle_dens, B, N, lk, mode, loss_out, grad_out);
 }
 
@@ -544,8 +566,7 @@ int drp_train_step_loss(drp_ctx* c, const float* states, const float* states_del
         return fail(c, DRP_EINVAL, "exactly one of states_delta and actions must be given");
     if (loss_kind != DRP_LOSS_CHAMFER && loss_kind != DRP_LOSS_MATCH && loss_kind != DRP_LOSS_CHAMFER_MATCH)
         return fail(c, DRP_EINVAL, "bad loss_kind %d", loss_kind);
-    TrLoss lk;
-    lk.kind = loss_kind; lk.targets = targets; lk.target_nums = target_nums; lk.M = M;
+    TrLoss lk = TrLoss::against(loss_kind, targets, target_nums, M);
     lk.match_weight = match_weight; lk.match_out = match_out;
     const bool by_actions = actions != nullptr;
     return train_step_body(c, states, by_actions ? actions : states_delta, by_actions, attrs, particle_nums, particle_dens, B, N, lk,

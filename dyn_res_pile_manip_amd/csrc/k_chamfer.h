@@ -11,18 +11,15 @@
 // No atomics: c(.) stays in LDS and every i walks it in ascending j, adding (p_i - q_j) for its own entries -- the same bits
 // from run to run, and for a sample alone or inside any batch (nothing depends on B, on the padding or on another sample).
 #pragma once
-#include "drp_common.h"
+#include "k_cloud_pair.h"
 
 #define KC_THREADS 256
 #define KC_TILE 1024            // points of the other cloud per LDS tile (float4 each: 16 KB)
 #define KC_MAX_POINTS 4096      // check_bn's limit: c(.) of a whole cloud stays in LDS (16 KB)
 
 struct KcArgs {
-    const float* pred; size_t p_bstride, p_tstride;      // [.][.][N][3]: sample b, step t at pred + b * p_bstride + t * p_tstride
-    const float* tgt; size_t q_bstride, q_tstride;      // [.][.][M][3]
-    const int* n_p;                                     // [B]
-    const int* n_q; int nq_bstride, nq_tstride;         // n_q[b * nq_bstride + t * nq_tstride]
-    int N, M;
+    const float* pred;          // p's rows (cp's strides)
+    CloudPair cp;
     float scale;
     float* grad;                // TRAIN: [H][B][N][3], every row written (padded rows 0); else [B][N][3], nullable
     double* terms;              // TRAIN: [H][B], scale (fwd + bwd); else [B][2]: fwd, bwd
@@ -72,14 +69,11 @@ __global__ void __launch_bounds__(KC_THREADS) kc_chamfer(KcArgs A) {
     __shared__ int s_c[KC_MAX_POINTS];
     __shared__ double s_w[4];
     const int b = blockIdx.x, t = blockIdx.y, B = gridDim.x;
-    const int N = A.N, M = A.M;
-    if (TRAIN && A.zero != nullptr)
-        for (size_t e = ((size_t)t * B + b) * KC_THREADS + threadIdx.x; e < A.n_zero; e += (size_t)gridDim.x * gridDim.y * KC_THREADS)
-            A.zero[e] = 0.0f;
-    const int np = min(max(A.n_p[b], 0), N);                // the entry points refuse counts outside 1..N, 1..M
-    const int nq = min(max(A.n_q[(size_t)b * A.nq_bstride + (size_t)t * A.nq_tstride], 0), min(M, KC_MAX_POINTS));
-    const float* p = A.pred + (size_t)b * A.p_bstride + (size_t)t * A.p_tstride;
-    const float* q = A.tgt + (size_t)b * A.q_bstride + (size_t)t * A.q_tstride;
+    const int N = A.cp.N, M = A.cp.M;
+    if (TRAIN) train_zero_fill(A.zero, A.n_zero, KC_THREADS);
+    const int np = A.cp.count_p(b, KC_MAX_POINTS), nq = A.cp.count_q(b, t, KC_MAX_POINTS);
+    const float* p = A.cp.p_rows(A.pred, b, t);
+    const float* q = A.cp.q_rows(b, t);
     const size_t slot = (size_t)t * B + b;
     float* g = A.grad != nullptr ? A.grad + slot * N * 3 : nullptr;
     int* nn_pq = (!TRAIN && A.nn_pq != nullptr) ? A.nn_pq + slot * N : nullptr;

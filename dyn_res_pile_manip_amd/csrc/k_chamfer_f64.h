@@ -18,7 +18,7 @@
 // ascending row, then lanes by xor-shuffle, then the four waves in order.  No atomics: the same bits from run to run, for a
 // sample alone or in any batch, and in any chunk of a batch.
 #pragma once
-#include "drp_common.h"
+#include "k_cloud_pair.h"
 
 #define KC64_THREADS 256
 #define KC64_TILE 1024          // points of the other cloud per LDS tile (four doubles each: 32 KB)
@@ -27,14 +27,10 @@
 struct Kc64Pt { double x, y, z, w; };
 
 struct Kc64Args {
-    const double* p64; const float* p32;                // TRAIN: p64; else p32.  [.][.][N][3]: (b, t) at + b * p_bstride + t * p_tstride
-    size_t p_bstride, p_tstride;
-    const float* tgt; size_t q_bstride, q_tstride;      // [.][.][M][3]: sample b_off + b
-    const int* n_p;                                     // [B]: sample b_off + b
-    const int* n_q; int nq_bstride, nq_tstride;         // n_q[(b_off + b) * nq_bstride + t * nq_tstride]
+    const double* p64; const float* p32;                // p's rows (cp's strides): TRAIN: p64, the chunk's; else p32
+    CloudPair cp;               // q and the counts are the batch's: sample b_off + b
     int b_off;                  // TRAIN: the chunk's first sample (p and grad are the chunk's, everything else the batch's)
     int B;                      // TRAIN: samples of the batch (the stride of terms and margin)
-    int N, M;
     double scale;
     double* grad;               // TRAIN: [H][gridDim.x][N][3], every row written (padded rows +0.0); else [B][N][3], nullable
     double* terms;              // TRAIN: [H][B], scale (fwd + bwd); else [B][2]: fwd, bwd
@@ -95,12 +91,11 @@ __device__ __forceinline__ double kc64_block_min(double v, double* s_w) {
 template <bool TRAIN, typename P>
 __device__ __forceinline__ void kc64_body(const Kc64Args& A, const P* __restrict__ p_all, Kc64Pt* s_tile, int* s_c, double* s_w) {
     const int b = blockIdx.x, t = blockIdx.y, nb = gridDim.x;
-    const int N = A.N, M = A.M;
+    const int N = A.cp.N, M = A.cp.M;
     const int bb = A.b_off + b;                             // the sample in the batch's arrays
-    const int np = min(max(A.n_p[bb], 0), min(N, KC64_MAX_POINTS));     // the entry points refuse counts outside 1..N, 1..M
-    const int nq = min(max(A.n_q[(size_t)bb * A.nq_bstride + (size_t)t * A.nq_tstride], 0), min(M, KC64_MAX_POINTS));
-    const P* p = p_all + (size_t)b * A.p_bstride + (size_t)t * A.p_tstride;
-    const float* q = A.tgt + (size_t)bb * A.q_bstride + (size_t)t * A.q_tstride;
+    const int np = A.cp.count_p(bb, KC64_MAX_POINTS), nq = A.cp.count_q(bb, t, KC64_MAX_POINTS);
+    const P* p = A.cp.p_rows(p_all, b, t);
+    const float* q = A.cp.q_rows(bb, t);
     const size_t slot = (size_t)t * nb + b;                 // of the launch's own outputs
     double* g = A.grad != nullptr ? A.grad + slot * N * 3 : nullptr;
     int* nn_pq = (!TRAIN && A.nn_pq != nullptr) ? A.nn_pq + slot * N : nullptr;

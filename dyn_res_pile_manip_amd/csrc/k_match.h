@@ -23,18 +23,15 @@
 // comparisons false, the search then takes the lowest unscanned columns with the inserted row as predecessor, the matching stays
 // one-to-one and the term comes out NaN or inf -- after the same number of steps.
 #pragma once
-#include "drp_common.h"
+#include "k_cloud_pair.h"
 
 #define KA_THREADS 64
 #define KA_MAX_POINTS 1024      // per cloud: the work is O(r^2) dependent steps of O(c / 64) each
 #define KA_CPL (KA_MAX_POINTS / 64)
 
 struct KaArgs {
-    const float* pred; size_t p_bstride, p_tstride;      // [.][.][N][3]: sample b, step t at pred + b * p_bstride + t * p_tstride
-    const float* tgt; size_t q_bstride, q_tstride;      // [.][.][M][3]
-    const int* n_p;                                     // [B]
-    const int* n_q; int nq_bstride, nq_tstride;         // n_q[b * nq_bstride + t * nq_tstride]
-    int N, M;
+    const float* pred;          // p's rows (cp's strides)
+    CloudPair cp;
     double scale;
     double keep;                // TRAIN, the mix: kc_chamfer<true> ran before with the whole Chamfer term -- grad and terms become
                                 // keep * (what is there) + this kernel's share, one rounding per element; 0: they are written
@@ -57,14 +54,11 @@ __global__ void __launch_bounds__(KA_THREADS) ka_match(KaArgs A) {
     __shared__ int s_pred[KA_MAX_POINTS];       // column -> the row its shortest path comes through
     const int b = blockIdx.x, t = blockIdx.y, B = gridDim.x;
     const int lane = threadIdx.x;
-    const int N = A.N, M = A.M;
-    if (TRAIN && A.zero != nullptr)
-        for (size_t e = ((size_t)t * B + b) * KA_THREADS + lane; e < A.n_zero; e += (size_t)gridDim.x * gridDim.y * KA_THREADS)
-            A.zero[e] = 0.0f;
-    const int np = min(max(A.n_p[b], 0), min(N, 64 * CPL));             // the entry points refuse counts outside 1..N, 1..M
-    const int nq = min(max(A.n_q[(size_t)b * A.nq_bstride + (size_t)t * A.nq_tstride], 0), min(M, 64 * CPL));
-    const float* p = A.pred + (size_t)b * A.p_bstride + (size_t)t * A.p_tstride;
-    const float* q = A.tgt + (size_t)b * A.q_bstride + (size_t)t * A.q_tstride;
+    const int N = A.cp.N, M = A.cp.M;
+    if (TRAIN) train_zero_fill(A.zero, A.n_zero, KA_THREADS);
+    const int np = A.cp.count_p(b, 64 * CPL), nq = A.cp.count_q(b, t, 64 * CPL);
+    const float* p = A.cp.p_rows(A.pred, b, t);
+    const float* q = A.cp.q_rows(b, t);
     const size_t slot = (size_t)t * B + b;
     float* g = A.grad != nullptr ? A.grad + slot * N * 3 : nullptr;
     int* m_pq = A.match_pq != nullptr ? A.match_pq + slot * N : nullptr;
@@ -225,7 +219,7 @@ __global__ void __launch_bounds__(KA_THREADS) ka_match(KaArgs A) {
 // one wavefront per problem on grid (B, H); the instantiation by the larger padded size (the entry points hold N, M <= KA_MAX_POINTS)
 template <bool TRAIN>
 inline void ka_launch(dim3 grid, hipStream_t st, const KaArgs& a) {
-    const int c = a.N > a.M ? a.N : a.M;
+    const int c = a.cp.N > a.cp.M ? a.cp.N : a.cp.M;
     if (c <= 64) hipLaunchKernelGGL((ka_match<TRAIN, 1>), grid, dim3(KA_THREADS), 0, st, a);
     else if (c <= 128) hipLaunchKernelGGL((ka_match<TRAIN, 2>), grid, dim3(KA_THREADS), 0, st, a);
     else if (c <= 256) hipLaunchKernelGGL((ka_match<TRAIN, 4>), grid, dim3(KA_THREADS), 0, st, a);

@@ -8,7 +8,7 @@
 // lane (v_readlane), waves stride over the rows, partial sums meet in LDS, then one partial per
 // workgroup in HBM, added up by a second launch in a fixed order (no atomics: deterministic).
 #pragma once
-#include "drp_common.h"
+#include "k_cloud_pair.h"
 #include "k_graph.h"
 #include "k_mlp_split.h"
 
@@ -21,10 +21,7 @@ kt_mse_grad(const float* __restrict__ s_pred, size_t pred_stride, const float* _
             double* __restrict__ loss /* [H][B] */, float* __restrict__ zero /* nullable */, size_t n_zero) {
     __shared__ double s_w[4];
     const int b = blockIdx.x, t = blockIdx.y, B = gridDim.x;
-    // with a backward pass to follow: the gradient blob (and the counters behind it) start at zero -- here instead of a
-    // memset of their own (two fill launches)
-    if (zero != nullptr)
-        for (size_t e = ((size_t)t * B + b) * 256 + threadIdx.x; e < n_zero; e += (size_t)gridDim.x * gridDim.y * 256) zero[e] = 0.0f;
+    train_zero_fill(zero, n_zero, 256);
     const int nb = particle_nums[b];
     const float* p = s_pred + (size_t)b * pred_stride + (size_t)t * N * 3;
     const float* q = s_nxt + (size_t)b * nxt_stride + (size_t)t * N * 3;

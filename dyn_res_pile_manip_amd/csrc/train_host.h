@@ -53,26 +53,44 @@ inline Tr64Arena tr64_layout(int B, int H, int N, int M = 0, bool actions = fals
     return a;
 }
 
-// drp_cloud_match's one buffer (capi_match.h), every block 16-byte aligned.  Up: p [B][N][3] | q [B][M][3] | n_p [B] | n_q [B]
-// (ints); down, behind `in_bytes`: terms [B] (doubles) | gradient [B][N][3] | partner of every row of p [B][N] | of q [B][M]
-// (ints) | duals [B][N + M] (doubles)
-struct CmLayout { size_t pts_p, pts_q, n_p, n_q, in_bytes, terms, grad, pq, qp, dual, bytes; };
-inline CmLayout cm_layout(int B, int N, int M) {
+// The one buffer of a one-shot on two clouds (capi_pipeline.h: cloud_begin), every block 16-byte aligned.  Up: p [B][N][3] |
+// q [B][M][3] | n_p [B] | n_q [B] (ints); down, behind `in_bytes`: the call's n_out output blocks out[k] of out_bytes[k] each
+#define CLOUD_MAX_OUT 5
+struct CloudLayout { size_t pts_p, pts_q, n_p, n_q, in_bytes, out[CLOUD_MAX_OUT], out_bytes[CLOUD_MAX_OUT], bytes; int n_out; };
+inline CloudLayout cloud_layout(int B, int N, int M, const size_t (&out_bytes)[CLOUD_MAX_OUT]) {
     auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t bn = (size_t)B * N, bm = (size_t)B * M;
-    CmLayout a{};
+    CloudLayout a{};
     a.pts_p = 0;
-    a.pts_q = up(a.pts_p + bn * 3 * sizeof(float));
-    a.n_p = up(a.pts_q + bm * 3 * sizeof(float));
+    a.pts_q = up(a.pts_p + (size_t)B * N * 3 * sizeof(float));
+    a.n_p = up(a.pts_q + (size_t)B * M * 3 * sizeof(float));
     a.n_q = up(a.n_p + (size_t)B * sizeof(int32_t));
-    a.in_bytes = up(a.n_q + (size_t)B * sizeof(int32_t));
-    a.terms = a.in_bytes;
-    a.grad = up(a.terms + (size_t)B * sizeof(double));
-    a.pq = up(a.grad + bn * 3 * sizeof(float));
-    a.qp = up(a.pq + bn * sizeof(int32_t));
-    a.dual = up(a.qp + bm * sizeof(int32_t));
-    a.bytes = up(a.dual + (bn + bm) * sizeof(double));
+    a.bytes = a.in_bytes = up(a.n_q + (size_t)B * sizeof(int32_t));
+    for (int k = 0; k < CLOUD_MAX_OUT && out_bytes[k] > 0; ++k) {
+        a.out[k] = a.bytes;
+        a.out_bytes[k] = out_bytes[k];
+        a.bytes = up(a.bytes + out_bytes[k]);
+        a.n_out = k + 1;
+    }
     return a;
+}
+// the three callers' output blocks, with bn = B N, bm = B M.  drp_cloud_chamfer: terms [B][2] (doubles) | gradient [B][N][3] |
+// a(.) [B][N] | c(.) [B][M] (ints)
+inline CloudLayout chamfer_layout(int B, int N, int M) {
+    const size_t bn = (size_t)B * N, bm = (size_t)B * M;
+    return cloud_layout(B, N, M, {(size_t)B * 2 * sizeof(double), bn * 3 * sizeof(float), bn * sizeof(int32_t), bm * sizeof(int32_t), 0});
+}
+// drp_cloud_chamfer_f64: terms [B][2] | margins [B][2] | gradient [B][N][3] (doubles) | a(.) [B][N] | c(.) [B][M] (ints)
+inline CloudLayout chamfer64_layout(int B, int N, int M) {
+    const size_t bn = (size_t)B * N, bm = (size_t)B * M;
+    return cloud_layout(B, N, M, {(size_t)B * 2 * sizeof(double), (size_t)B * 2 * sizeof(double), bn * 3 * sizeof(double),
+                                  bn * sizeof(int32_t), bm * sizeof(int32_t)});
+}
+// drp_cloud_match: terms [B] (doubles) | gradient [B][N][3] | partner of every row of p [B][N] | of q [B][M] (ints) | duals
+// [B][N + M] (doubles)
+inline CloudLayout cm_layout(int B, int N, int M) {
+    const size_t bn = (size_t)B * N, bm = (size_t)B * M;
+    return cloud_layout(B, N, M, {(size_t)B * sizeof(double), bn * 3 * sizeof(float), bn * sizeof(int32_t), bm * sizeof(int32_t),
+                                  (bn + bm) * sizeof(double)});
 }
 // the first of the real rows' coordinates of a padded cloud batch [B][N][3] that is infinite or no number, as b * N + row, or -1
 // (the padding is never read as points: rubbish there is allowed)

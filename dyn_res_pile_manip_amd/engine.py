@@ -22,6 +22,19 @@ def _dp(a):
     return a.ctypes.data_as(L.c_double_p)
 
 
+def _i32(x):
+    return np.ascontiguousarray(x, dtype=np.int32)
+
+
+def _ip(a):
+    return a.ctypes.data_as(L.c_int32_p)
+
+
+def _opt(f, a):
+    """f(a), or None for an argument that is not given"""
+    return None if a is None else f(a)
+
+
 # ---- the row layout of a multi-scene session (include/drp.h: drp_mpc_begin_scenes; pure numpy, no device, no library) --------
 def scene_rows(S, n_units, nb):
     """Rows of every scene in a session of S scenes x n_units samples (or trajectories) x nb columns -> int64 [S, n_units * nb]:
@@ -738,43 +751,64 @@ class Engine(object):
         self._ck(self.lib.drp_train_begin(self.h, int(n_rollout), float(lr), float(beta1)))
         self._n_rollout = int(n_rollout)
 
+    def _train_batch(self, states, impulses, attrs, particle_nums, particle_dens, targets, target_nums, by_actions, need_begin):
+        """A training batch as every trainer entry point takes it: contiguous float32 / int32 arrays, their shapes held to one
+        another.  impulses: states_delta [B, H, N, 3], or with by_actions the pushes [B, H, 4]; targets / target_nums: None, or
+        [B, H, M, 3] / [B, H].  need_begin: H is train_begin's n_rollout; else it is read from `states`, and a batch with an empty
+        axis goes on for the C ABI to refuse -> (the arrays, (B, N, H, M), their ctypes pointers), arrays and pointers in the order
+        of the arguments; M = 0 and None for targets that are not there."""
+        arrays = (_f32(states), _f32(impulses), _f32(attrs), _i32(particle_nums), _f32(particle_dens),
+                  _opt(_f32, targets), _opt(_i32, target_nums))
+        states, imp, attrs, nums, dens, targets, tnums = arrays
+        B, T1, N = states.shape[:3] if states.ndim == 4 else (0, 1, 0)
+        H, M = T1 - 1, 0
+        assert not need_begin or (states.ndim == 4 and T1 == self._n_rollout + 1)
+        if need_begin or (B > 0 and N > 0 and H > 0):
+            assert states.shape == (B, T1, N, 3) and imp.shape == ((B, H, 4) if by_actions else (B, H, N, 3))
+            assert attrs.shape == (B, T1, N) and nums.shape == (B,) and dens.shape == (B,)
+        assert (targets is None) == (tnums is None)
+        if targets is not None:
+            assert targets.ndim == 4 and targets.shape[:2] == (B, H) and targets.shape[3] == 3 and tnums.shape == (B, H)
+            M = targets.shape[2]
+        ptrs = (_fp(states), _fp(imp), _fp(attrs), _ip(nums), _fp(dens), _opt(_fp, targets), _opt(_ip, tnums))
+        return arrays, (int(B), int(N), int(H), int(M)), ptrs
+
+    def _train_step32(self, states, states_delta, actions, attrs, particle_nums, particle_dens, targets, target_nums, mode,
+                      want_grad, loss=None, match_weight=0.5, want_match=False):
+        """One fp32 trainer call -> (loss, gradient blob or None, match or None).  The C function by what is given: `loss` (a key
+        of L.LOSS_KINDS): drp_train_step_loss; else `actions`: drp_train_step_actions; else `targets`: drp_train_step_untracked;
+        else drp_train_step."""
+        by_actions = actions is not None
+        keep, (B, N, H, M), (ps, pi, pa, pn, pd, pt, ptn) = self._train_batch(
+            states, actions if by_actions else states_delta, attrs, particle_nums, particle_dens, targets, target_nums, by_actions, True)
+        out = ctypes.c_double()
+        grad = np.empty((L.DRP_N_WEIGHTS,), np.float32) if (want_grad and mode != 'eval') else None
+        match = np.full((H, B, N), -1, np.int32) if (want_match and loss != 'chamfer') else None
+        tail = (L.TRAIN_MODES[mode], ctypes.byref(out), _opt(_fp, grad))
+        if loss is not None:
+            rc = self.lib.drp_train_step_loss(self.h, ps, None if by_actions else pi, pi if by_actions else None, pa, pn, pd, B, N,
+                                              pt, ptn, M, L.LOSS_KINDS[loss], float(match_weight), *tail, _opt(_ip, match))
+        elif by_actions:
+            rc = self.lib.drp_train_step_actions(self.h, ps, pi, pa, pn, pd, B, N, pt, ptn, M, *tail)
+        elif targets is not None:
+            rc = self.lib.drp_train_step_untracked(self.h, ps, pi, pa, pn, pd, B, N, pt, ptn, M, *tail)
+        else:
+            rc = self.lib.drp_train_step(self.h, ps, pi, pa, pn, pd, B, N, *tail)
+        self._ck(rc)
+        return out.value, grad, match
+
     def train_step(self, states, states_delta, attrs, particle_nums, particle_dens, mode='update', want_grad=False):
         """One body of the loop at train/train_gnn_dyn.py:159-210 -> (loss, gradient blob or None)."""
-        states, states_delta, attrs = _f32(states), _f32(states_delta), _f32(attrs)
-        dens = _f32(particle_dens)
-        nums = np.ascontiguousarray(particle_nums, dtype=np.int32)
-        B, T1, N, _ = states.shape
-        assert T1 == self._n_rollout + 1 and states_delta.shape == (B, T1 - 1, N, 3)
-        assert attrs.shape == (B, T1, N) and nums.shape == (B,) and dens.shape == (B,)
-        loss = ctypes.c_double()
-        grad = np.empty((38403,), np.float32) if (want_grad and mode != 'eval') else None
-        self._ck(self.lib.drp_train_step(self.h, _fp(states), _fp(states_delta), _fp(attrs),
-                                         nums.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _fp(dens), B, N,
-                                         L.TRAIN_MODES[mode], ctypes.byref(loss), None if grad is None else _fp(grad)))
-        return loss.value, grad
+        return self._train_step32(states, states_delta, None, attrs, particle_nums, particle_dens, None, None, mode, want_grad)[:2]
 
     def train_step_untracked(self, states, states_delta, attrs, particle_nums, particle_dens, targets, target_nums,
                              mode='update', want_grad=False):
         """train_step with each step's loss taken against an untracked cloud (include/drp.h: drp_train_step_untracked): targets
         [B, n_rollout, M, 3] with target_nums [B, n_rollout] real rows; of `states` only step 0 is read -> (loss, gradient blob
         or None)."""
-        states, states_delta, attrs = _f32(states), _f32(states_delta), _f32(attrs)
-        dens = _f32(particle_dens)
-        nums = np.ascontiguousarray(particle_nums, dtype=np.int32)
-        targets = _f32(targets)
-        tnums = np.ascontiguousarray(target_nums, dtype=np.int32)
-        B, T1, N, _ = states.shape
-        assert T1 == self._n_rollout + 1 and states_delta.shape == (B, T1 - 1, N, 3)
-        assert attrs.shape == (B, T1, N) and nums.shape == (B,) and dens.shape == (B,)
-        assert targets.ndim == 4 and targets.shape[:2] == (B, T1 - 1) and targets.shape[3] == 3 and tnums.shape == (B, T1 - 1)
-        M = targets.shape[2]
-        loss = ctypes.c_double()
-        grad = np.empty((38403,), np.float32) if (want_grad and mode != 'eval') else None
-        i32p = ctypes.POINTER(ctypes.c_int32)
-        self._ck(self.lib.drp_train_step_untracked(self.h, _fp(states), _fp(states_delta), _fp(attrs), nums.ctypes.data_as(i32p),
-                                                   _fp(dens), B, N, _fp(targets), tnums.ctypes.data_as(i32p), int(M),
-                                                   L.TRAIN_MODES[mode], ctypes.byref(loss), None if grad is None else _fp(grad)))
-        return loss.value, grad
+        assert targets is not None and target_nums is not None
+        return self._train_step32(states, states_delta, None, attrs, particle_nums, particle_dens, targets, target_nums, mode,
+                                  want_grad)[:2]
 
     def train_step_actions(self, states, actions, attrs, particle_nums, particle_dens, targets=None, target_nums=None,
                            mode='update', want_grad=False):
@@ -783,91 +817,8 @@ class Engine(object):
         the state the step reads -- states[:, 0], then the model's own predictions -- zero on padded rows, and the push's
         position share in the backward pass (include/drp.h: drp_train_step_actions).  Needs set_camera -> (loss, gradient blob or
         None)."""
-        states, actions, attrs = _f32(states), _f32(actions), _f32(attrs)
-        dens = _f32(particle_dens)
-        nums = np.ascontiguousarray(particle_nums, dtype=np.int32)
-        B, T1, N, _ = states.shape
-        assert T1 == self._n_rollout + 1 and actions.shape == (B, T1 - 1, 4)
-        assert attrs.shape == (B, T1, N) and nums.shape == (B,) and dens.shape == (B,)
-        assert (targets is None) == (target_nums is None)
-        i32p = ctypes.POINTER(ctypes.c_int32)
-        tp, tnp, M = None, None, 0
-        if targets is not None:
-            targets = _f32(targets)
-            tnums = np.ascontiguousarray(target_nums, dtype=np.int32)
-            assert targets.ndim == 4 and targets.shape[:2] == (B, T1 - 1) and targets.shape[3] == 3 and tnums.shape == (B, T1 - 1)
-            tp, tnp, M = _fp(targets), tnums.ctypes.data_as(i32p), targets.shape[2]
-        loss = ctypes.c_double()
-        grad = np.empty((38403,), np.float32) if (want_grad and mode != 'eval') else None
-        self._ck(self.lib.drp_train_step_actions(self.h, _fp(states), _fp(actions), _fp(attrs), nums.ctypes.data_as(i32p), _fp(dens),
-                                                 B, N, tp, tnp, int(M), L.TRAIN_MODES[mode], ctypes.byref(loss),
-                                                 None if grad is None else _fp(grad)))
-        return loss.value, grad
-
-    # ---- the Chamfer metric of two cloud batches (include/drp.h: drp_cloud_chamfer) ----------------------------------
-    def cloud_chamfer(self, p, q, n_p=None, n_q=None, want_grad=False, want_nn=False):
-        """Symmetric squared Chamfer distance of p [B, N, 3] (n_p [B] real rows, default all) and q [B, M, 3] (n_q) ->
-        {'fwd', 'bwd', 'total' [B] float64[, 'grad' [B, N, 3] = d total / d p][, 'nn_pq' [B, N], 'nn_qp' [B, M]: each row's nearest
-        row of the other cloud, -1 on padding]}.  A single cloud pair may be given as [N, 3], [M, 3].  A one-shot: it needs no
-        weights and ends no session."""
-        p, q = _f32(p), _f32(q)
-        if p.ndim == 2 and q.ndim == 2:
-            p, q = p[None], q[None]
-        assert p.ndim == 3 and q.ndim == 3 and p.shape[2] == 3 and q.shape[2] == 3 and p.shape[0] == q.shape[0]
-        B, N, M = p.shape[0], p.shape[1], q.shape[1]
-        n_p = np.full((B,), N, np.int32) if n_p is None else np.ascontiguousarray(n_p, dtype=np.int32).reshape(-1)
-        n_q = np.full((B,), M, np.int32) if n_q is None else np.ascontiguousarray(n_q, dtype=np.int32).reshape(-1)
-        assert n_p.shape == (B,) and n_q.shape == (B,)
-        terms = np.empty((B, 2), np.float64)
-        grad = np.empty((B, N, 3), np.float32) if want_grad else None
-        nn_pq = np.empty((B, N), np.int32) if want_nn else None
-        nn_qp = np.empty((B, M), np.int32) if want_nn else None
-        i32p = ctypes.POINTER(ctypes.c_int32)
-        self._ck(self.lib.drp_cloud_chamfer(self.h, _fp(p), n_p.ctypes.data_as(i32p), _fp(q), n_q.ctypes.data_as(i32p), int(B), int(N),
-                                            int(M), _dp(terms), _fp(grad) if want_grad else None,
-                                            nn_pq.ctypes.data_as(i32p) if want_nn else None,
-                                            nn_qp.ctypes.data_as(i32p) if want_nn else None))
-        out = {'fwd': terms[:, 0].copy(), 'bwd': terms[:, 1].copy(), 'total': terms[:, 0] + terms[:, 1]}
-        if want_grad:
-            out['grad'] = grad
-        if want_nn:
-            out['nn_pq'], out['nn_qp'] = nn_pq, nn_qp
-        return out
-
-    # ---- the one-to-one matching distance of two cloud batches (include/drp.h: drp_cloud_match) --------------------------
-    def cloud_match(self, p, q, n_p=None, n_q=None, want_grad=False, want_match=False, want_dual=False):
-        """Matching (earth mover's) distance of p [B, N, 3] (n_p [B] real rows, default all) and q [B, M, 3] (n_q): every row of
-        the smaller cloud paired with a distinct row of the larger one at the least total squared distance ->
-        {'match' [B] float64 = sum over the pairs / (3 r), 'r' [B] = min(n_p, n_q)[, 'grad' [B, N, 3] = d match / d p][, 'match_pq'
-        [B, N], 'match_qp' [B, M]: each row's partner, -1 for unmatched rows and padding][, 'u' [B, N], 'v' [B, M]: the duals of
-        p's and q's rows, float64]}.  A single cloud pair may be given as [N, 3], [M, 3].  At most 1024 points per cloud.  A
-        one-shot: it needs no weights and ends no session."""
-        p, q = _f32(p), _f32(q)
-        if p.ndim == 2 and q.ndim == 2:
-            p, q = p[None], q[None]
-        assert p.ndim == 3 and q.ndim == 3 and p.shape[2] == 3 and q.shape[2] == 3 and p.shape[0] == q.shape[0]
-        B, N, M = p.shape[0], p.shape[1], q.shape[1]
-        n_p = np.full((B,), N, np.int32) if n_p is None else np.ascontiguousarray(n_p, dtype=np.int32).reshape(-1)
-        n_q = np.full((B,), M, np.int32) if n_q is None else np.ascontiguousarray(n_q, dtype=np.int32).reshape(-1)
-        assert n_p.shape == (B,) and n_q.shape == (B,)
-        terms = np.empty((B,), np.float64)
-        grad = np.empty((B, N, 3), np.float32) if want_grad else None
-        m_pq = np.empty((B, N), np.int32) if want_match else None
-        m_qp = np.empty((B, M), np.int32) if want_match else None
-        dual = np.empty((B, N + M), np.float64) if want_dual else None
-        i32p = ctypes.POINTER(ctypes.c_int32)
-        self._ck(self.lib.drp_cloud_match(self.h, _fp(p), n_p.ctypes.data_as(i32p), _fp(q), n_q.ctypes.data_as(i32p), int(B), int(N),
-                                          int(M), _dp(terms), _fp(grad) if want_grad else None,
-                                          m_pq.ctypes.data_as(i32p) if want_match else None,
-                                          m_qp.ctypes.data_as(i32p) if want_match else None, _dp(dual) if want_dual else None))
-        out = {'match': terms, 'r': np.minimum(n_p, n_q)}
-        if want_grad:
-            out['grad'] = grad
-        if want_match:
-            out['match_pq'], out['match_qp'] = m_pq, m_qp
-        if want_dual:
-            out['u'], out['v'] = dual[:, :N].copy(), dual[:, N:].copy()
-        return out
+        return self._train_step32(states, None, _f32(actions), attrs, particle_nums, particle_dens, targets, target_nums, mode,
+                                  want_grad)[:2]
 
     def train_step_loss(self, states, attrs, particle_nums, particle_dens, targets, target_nums, states_delta=None, actions=None,
                         loss='match', match_weight=0.5, mode='update', want_grad=False, want_match=False):
@@ -879,56 +830,81 @@ class Engine(object):
             raise ValueError('loss must be one of %s' % (tuple(L.LOSS_KINDS),))
         if (states_delta is None) == (actions is None):
             raise ValueError('exactly one of states_delta and actions must be given')
-        states, attrs = _f32(states), _f32(attrs)
-        dens = _f32(particle_dens)
-        nums = np.ascontiguousarray(particle_nums, dtype=np.int32)
-        targets = _f32(targets)
-        tnums = np.ascontiguousarray(target_nums, dtype=np.int32)
-        B, T1, N, _ = states.shape
-        assert T1 == self._n_rollout + 1
-        if states_delta is not None:
-            states_delta = _f32(states_delta)
-            assert states_delta.shape == (B, T1 - 1, N, 3)
-        else:
-            actions = _f32(actions)
-            assert actions.shape == (B, T1 - 1, 4)
-        assert attrs.shape == (B, T1, N) and nums.shape == (B,) and dens.shape == (B,)
-        assert targets.ndim == 4 and targets.shape[:2] == (B, T1 - 1) and targets.shape[3] == 3 and tnums.shape == (B, T1 - 1)
-        M = targets.shape[2]
-        out_loss = ctypes.c_double()
-        grad = np.empty((38403,), np.float32) if (want_grad and mode != 'eval') else None
-        match = np.full((T1 - 1, B, N), -1, np.int32) if (want_match and loss != 'chamfer') else None
-        i32p = ctypes.POINTER(ctypes.c_int32)
-        self._ck(self.lib.drp_train_step_loss(self.h, _fp(states), _fp(states_delta) if states_delta is not None else None,
-                                              _fp(actions) if actions is not None else None, _fp(attrs), nums.ctypes.data_as(i32p),
-                                              _fp(dens), B, N, _fp(targets), tnums.ctypes.data_as(i32p), int(M), L.LOSS_KINDS[loss],
-                                              float(match_weight), L.TRAIN_MODES[mode], ctypes.byref(out_loss),
-                                              None if grad is None else _fp(grad),
-                                              None if match is None else match.ctypes.data_as(i32p)))
-        return (out_loss.value, grad, match) if want_match else (out_loss.value, grad)
+        assert targets is not None and target_nums is not None
+        out = self._train_step32(states, states_delta, actions, attrs, particle_nums, particle_dens, targets, target_nums, mode,
+                                 want_grad, loss, match_weight, want_match)
+        return out if want_match else out[:2]
 
-    def cloud_chamfer_f64(self, p, q, n_p=None, n_q=None, want_grad=False, want_nn=False):
-        """cloud_chamfer in float64 on the device (include/drp.h: drp_cloud_chamfer_f64): the same dict with 'grad' as float64,
-        plus 'margin' [B, 2] -- per sample the smallest (second-best - best) squared distance over its arg-mins, p -> q then
-        q -> p: 0 for a duplicate of a winner, inf where the other cloud has one row."""
+    # ---- one-shots on two cloud batches (include/drp.h: drp_cloud_chamfer, drp_cloud_chamfer_f64, drp_cloud_match) ---------
+    @staticmethod
+    def _cloud_pair(p, q, n_p, n_q):
+        """p [B, N, 3] and q [B, M, 3] (or one pair as [N, 3], [M, 3]) with their real rows n_p, n_q [B] (None: all) as the one-shots
+        take them -> (p, q, n_p, n_q, B, N, M)."""
         p, q = _f32(p), _f32(q)
         if p.ndim == 2 and q.ndim == 2:
             p, q = p[None], q[None]
         assert p.ndim == 3 and q.ndim == 3 and p.shape[2] == 3 and q.shape[2] == 3 and p.shape[0] == q.shape[0]
         B, N, M = p.shape[0], p.shape[1], q.shape[1]
-        n_p = np.full((B,), N, np.int32) if n_p is None else np.ascontiguousarray(n_p, dtype=np.int32).reshape(-1)
-        n_q = np.full((B,), M, np.int32) if n_q is None else np.ascontiguousarray(n_q, dtype=np.int32).reshape(-1)
+        n_p = np.full((B,), N, np.int32) if n_p is None else _i32(n_p).reshape(-1)
+        n_q = np.full((B,), M, np.int32) if n_q is None else _i32(n_q).reshape(-1)
         assert n_p.shape == (B,) and n_q.shape == (B,)
+        return p, q, n_p, n_q, int(B), int(N), int(M)
+
+    def cloud_chamfer(self, p, q, n_p=None, n_q=None, want_grad=False, want_nn=False):
+        """Symmetric squared Chamfer distance of p [B, N, 3] (n_p [B] real rows, default all) and q [B, M, 3] (n_q) ->
+        {'fwd', 'bwd', 'total' [B] float64[, 'grad' [B, N, 3] = d total / d p][, 'nn_pq' [B, N], 'nn_qp' [B, M]: each row's nearest
+        row of the other cloud, -1 on padding]}.  A single cloud pair may be given as [N, 3], [M, 3].  A one-shot: it needs no
+        weights and ends no session."""
+        p, q, n_p, n_q, B, N, M = self._cloud_pair(p, q, n_p, n_q)
+        terms = np.empty((B, 2), np.float64)
+        grad = np.empty((B, N, 3), np.float32) if want_grad else None
+        nn_pq = np.empty((B, N), np.int32) if want_nn else None
+        nn_qp = np.empty((B, M), np.int32) if want_nn else None
+        self._ck(self.lib.drp_cloud_chamfer(self.h, _fp(p), _ip(n_p), _fp(q), _ip(n_q), B, N, M, _dp(terms), _opt(_fp, grad),
+                                            _opt(_ip, nn_pq), _opt(_ip, nn_qp)))
+        out = {'fwd': terms[:, 0].copy(), 'bwd': terms[:, 1].copy(), 'total': terms[:, 0] + terms[:, 1]}
+        if want_grad:
+            out['grad'] = grad
+        if want_nn:
+            out['nn_pq'], out['nn_qp'] = nn_pq, nn_qp
+        return out
+
+    def cloud_match(self, p, q, n_p=None, n_q=None, want_grad=False, want_match=False, want_dual=False):
+        """Matching (earth mover's) distance of p [B, N, 3] (n_p [B] real rows, default all) and q [B, M, 3] (n_q): every row of
+        the smaller cloud paired with a distinct row of the larger one at the least total squared distance ->
+        {'match' [B] float64 = sum over the pairs / (3 r), 'r' [B] = min(n_p, n_q)[, 'grad' [B, N, 3] = d match / d p][, 'match_pq'
+        [B, N], 'match_qp' [B, M]: each row's partner, -1 for unmatched rows and padding][, 'u' [B, N], 'v' [B, M]: the duals of
+        p's and q's rows, float64]}.  A single cloud pair may be given as [N, 3], [M, 3].  At most 1024 points per cloud.  A
+        one-shot: it needs no weights and ends no session."""
+        p, q, n_p, n_q, B, N, M = self._cloud_pair(p, q, n_p, n_q)
+        terms = np.empty((B,), np.float64)
+        grad = np.empty((B, N, 3), np.float32) if want_grad else None
+        m_pq = np.empty((B, N), np.int32) if want_match else None
+        m_qp = np.empty((B, M), np.int32) if want_match else None
+        dual = np.empty((B, N + M), np.float64) if want_dual else None
+        self._ck(self.lib.drp_cloud_match(self.h, _fp(p), _ip(n_p), _fp(q), _ip(n_q), B, N, M, _dp(terms), _opt(_fp, grad),
+                                          _opt(_ip, m_pq), _opt(_ip, m_qp), _opt(_dp, dual)))
+        out = {'match': terms, 'r': np.minimum(n_p, n_q)}
+        if want_grad:
+            out['grad'] = grad
+        if want_match:
+            out['match_pq'], out['match_qp'] = m_pq, m_qp
+        if want_dual:
+            out['u'], out['v'] = dual[:, :N].copy(), dual[:, N:].copy()
+        return out
+
+    def cloud_chamfer_f64(self, p, q, n_p=None, n_q=None, want_grad=False, want_nn=False):
+        """cloud_chamfer in float64 on the device (include/drp.h: drp_cloud_chamfer_f64): the same dict with 'grad' as float64,
+        plus 'margin' [B, 2] -- per sample the smallest (second-best - best) squared distance over its arg-mins, p -> q then
+        q -> p: 0 for a duplicate of a winner, inf where the other cloud has one row."""
+        p, q, n_p, n_q, B, N, M = self._cloud_pair(p, q, n_p, n_q)
         terms = np.empty((B, 2), np.float64)
         margin = np.empty((B, 2), np.float64)
         grad = np.empty((B, N, 3), np.float64) if want_grad else None
         nn_pq = np.empty((B, N), np.int32) if want_nn else None
         nn_qp = np.empty((B, M), np.int32) if want_nn else None
-        i32p = ctypes.POINTER(ctypes.c_int32)
-        self._ck(self.lib.drp_cloud_chamfer_f64(self.h, _fp(p), n_p.ctypes.data_as(i32p), _fp(q), n_q.ctypes.data_as(i32p), int(B),
-                                                int(N), int(M), _dp(terms), _dp(grad) if want_grad else None,
-                                                nn_pq.ctypes.data_as(i32p) if want_nn else None,
-                                                nn_qp.ctypes.data_as(i32p) if want_nn else None, _dp(margin)))
+        self._ck(self.lib.drp_cloud_chamfer_f64(self.h, _fp(p), _ip(n_p), _fp(q), _ip(n_q), B, N, M, _dp(terms), _opt(_dp, grad),
+                                                _opt(_ip, nn_pq), _opt(_ip, nn_qp), _dp(margin)))
         out = {'fwd': terms[:, 0].copy(), 'bwd': terms[:, 1].copy(), 'total': terms[:, 0] + terms[:, 1], 'margin': margin}
         if want_grad:
             out['grad'] = grad
@@ -937,47 +913,44 @@ class Engine(object):
         return out
 
     # ---- the float64 yardstick of the trainer's gradients (include/drp.h: drp_train_grad_f64) ------------------------
+    def _train_grad64(self, states, states_delta, actions, attrs, particle_nums, particle_dens, targets, target_nums, want_state):
+        """One float64 trainer call -> (loss, terms [H, B], gradient blob, margin [H, B] or None, state gradient or None).  The C
+        function by what is given: `targets`: drp_train_grad_f64_untracked; else `actions`: drp_train_grad_f64_actions; else
+        drp_train_grad_f64."""
+        by_actions = actions is not None
+        keep, (B, N, H, M), (ps, pi, pa, pn, pd, pt, ptn) = self._train_batch(
+            states, actions if by_actions else states_delta, attrs, particle_nums, particle_dens, targets, target_nums, by_actions, False)
+        loss = ctypes.c_double()
+        terms = np.empty((max(H, 0), B), np.float64)
+        margin = np.empty((H, B), np.float64) if targets is not None else None
+        grad = np.empty((L.DRP_N_WEIGHTS,), np.float64)
+        gs = np.empty((B, max(H, 0), N, 3), np.float64) if want_state else None
+        tail = (ctypes.byref(loss), _dp(terms), _dp(grad), _opt(_dp, gs))
+        if targets is not None:
+            rc = self.lib.drp_train_grad_f64_untracked(self.h, ps, None if by_actions else pi, pi if by_actions else None, pa, pn, pd,
+                                                       B, N, H, pt, ptn, M, *tail, _dp(margin))
+        else:
+            fn = self.lib.drp_train_grad_f64_actions if by_actions else self.lib.drp_train_grad_f64
+            rc = fn(self.h, ps, pi, pa, pn, pd, B, N, H, *tail)
+        self._ck(rc)
+        return loss.value, terms, grad, margin, gs
+
     def train_grad_f64(self, states, states_delta, attrs, particle_nums, particle_dens, want_state=False):
         """What train_step(mode='grad') computes, in float64 on the device -> (loss, loss_terms [n_rollout, B], gradient blob
         [38403] in state_dict order[, d loss / d every step's predicted state [B, n_rollout, N, 3]]) as float64.  n_rollout is
         read from the arrays.  A one-shot call in buffers of its own: no train_begin needed; it ends no session and leaves the
         trainer's Adam state, the selected engine, last_dispatch() and the float64 taps as they were."""
-        states, states_delta, attrs = _f32(states), _f32(states_delta), _f32(attrs)
-        dens = _f32(particle_dens)
-        nums = np.ascontiguousarray(particle_nums, dtype=np.int32)
-        B, T1, N = (states.shape[0], states.shape[1], states.shape[2]) if states.ndim == 4 else (0, 1, 0)
-        H = T1 - 1
-        if B > 0 and N > 0 and H > 0:
-            assert states.shape == (B, T1, N, 3) and states_delta.shape == (B, H, N, 3)
-            assert attrs.shape == (B, T1, N) and nums.shape == (B,) and dens.shape == (B,)
-        loss = ctypes.c_double()
-        terms = np.empty((max(H, 0), max(B, 0)), np.float64)
-        grad = np.empty((38403,), np.float64)
-        gs = np.empty((max(B, 0), max(H, 0), max(N, 0), 3), np.float64) if want_state else None
-        self._ck(self.lib.drp_train_grad_f64(self.h, _fp(states), _fp(states_delta), _fp(attrs),
-                                             nums.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _fp(dens), int(B), int(N), int(H),
-                                             ctypes.byref(loss), _dp(terms), _dp(grad), _dp(gs) if want_state else None))
-        return (loss.value, terms, grad, gs) if want_state else (loss.value, terms, grad)
+        loss, terms, grad, _, gs = self._train_grad64(states, states_delta, None, attrs, particle_nums, particle_dens, None, None,
+                                                      want_state)
+        return (loss, terms, grad, gs) if want_state else (loss, terms, grad)
 
     def train_grad_f64_actions(self, states, actions, attrs, particle_nums, particle_dens, want_state=False):
         """train_grad_f64 with the pushes `actions` [B, n_rollout, 4] in place of states_delta: what
         train_step_actions(mode='grad') computes with the MSE loss, in float64 on the device (include/drp.h:
         drp_train_grad_f64_actions).  Needs set_camera; the same returns and the same one-shot contract."""
-        states, actions, attrs = _f32(states), _f32(actions), _f32(attrs)
-        dens = _f32(particle_dens)
-        nums = np.ascontiguousarray(particle_nums, dtype=np.int32)
-        B, T1, N, _ = states.shape
-        H = T1 - 1
-        assert actions.shape == (B, H, 4) and attrs.shape == (B, T1, N) and nums.shape == (B,) and dens.shape == (B,)
-        loss = ctypes.c_double()
-        terms = np.empty((H, B), np.float64)
-        grad = np.empty((38403,), np.float64)
-        gs = np.empty((B, H, N, 3), np.float64) if want_state else None
-        self._ck(self.lib.drp_train_grad_f64_actions(self.h, _fp(states), _fp(actions), _fp(attrs),
-                                                     nums.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _fp(dens), int(B), int(N),
-                                                     int(H), ctypes.byref(loss), _dp(terms), _dp(grad),
-                                                     _dp(gs) if want_state else None))
-        return (loss.value, terms, grad, gs) if want_state else (loss.value, terms, grad)
+        loss, terms, grad, _, gs = self._train_grad64(states, None, _f32(actions), attrs, particle_nums, particle_dens, None, None,
+                                                      want_state)
+        return (loss, terms, grad, gs) if want_state else (loss, terms, grad)
 
     def train_grad_f64_untracked(self, states, states_delta, attrs, particle_nums, particle_dens, targets, target_nums,
                                  actions=None, want_state=False):
@@ -987,30 +960,10 @@ class Engine(object):
         drp_train_grad_f64_untracked) -> (loss, loss_terms [n_rollout, B], gradient blob [38403], margin [n_rollout, B][, d loss /
         d every step's predicted state [B, n_rollout, N, 3]]).  margin: per (step, sample) the smallest (second-best - best)
         squared distance over its float64 arg-mins -- how close the nearest partner flip is.  The same one-shot contract."""
-        states, attrs = _f32(states), _f32(attrs)
-        imp = _f32(actions) if actions is not None else _f32(states_delta)
-        dens = _f32(particle_dens)
-        nums = np.ascontiguousarray(particle_nums, dtype=np.int32)
-        targets = _f32(targets)
-        tnums = np.ascontiguousarray(target_nums, dtype=np.int32)
-        B, T1, N, _ = states.shape
-        H = T1 - 1
-        assert imp.shape == ((B, H, 4) if actions is not None else (B, H, N, 3))
-        assert attrs.shape == (B, T1, N) and nums.shape == (B,) and dens.shape == (B,)
-        assert targets.ndim == 4 and targets.shape[:2] == (B, H) and targets.shape[3] == 3 and tnums.shape == (B, H)
-        M = targets.shape[2]
-        loss = ctypes.c_double()
-        terms = np.empty((H, B), np.float64)
-        margin = np.empty((H, B), np.float64)
-        grad = np.empty((38403,), np.float64)
-        gs = np.empty((B, H, N, 3), np.float64) if want_state else None
-        i32p = ctypes.POINTER(ctypes.c_int32)
-        self._ck(self.lib.drp_train_grad_f64_untracked(self.h, _fp(states), None if actions is not None else _fp(imp),
-                                                       _fp(imp) if actions is not None else None, _fp(attrs),
-                                                       nums.ctypes.data_as(i32p), _fp(dens), int(B), int(N), int(H), _fp(targets),
-                                                       tnums.ctypes.data_as(i32p), int(M), ctypes.byref(loss), _dp(terms), _dp(grad),
-                                                       _dp(gs) if want_state else None, _dp(margin)))
-        return (loss.value, terms, grad, margin, gs) if want_state else (loss.value, terms, grad, margin)
+        assert targets is not None and target_nums is not None
+        loss, terms, grad, margin, gs = self._train_grad64(states, states_delta, actions, attrs, particle_nums, particle_dens,
+                                                           targets, target_nums, want_state)
+        return (loss, terms, grad, margin, gs) if want_state else (loss, terms, grad, margin)
 
     def train_gradient_probe(self, states, states_delta, attrs, particle_nums, particle_dens, actions=None, targets=None,
                              target_nums=None):
@@ -1031,25 +984,12 @@ class Engine(object):
         assert (targets is None) == (target_nums is None)
         chamfer = targets is not None
         self.dispatch_reset()
-        if actions is not None:
-            loss32, g32 = self.train_step_actions(states, actions, attrs, particle_nums, particle_dens, targets, target_nums,
-                                                  mode='grad', want_grad=True)
-        elif chamfer:
-            loss32, g32 = self.train_step_untracked(states, states_delta, attrs, particle_nums, particle_dens, targets, target_nums,
-                                                    mode='grad', want_grad=True)
-        else:
-            loss32, g32 = self.train_step(states, states_delta, attrs, particle_nums, particle_dens, mode='grad', want_grad=True)
+        loss32, g32, _ = self._train_step32(states, states_delta, actions, attrs, particle_nums, particle_dens, targets, target_nums,
+                                            'grad', True)
         # the fp32 matrix engine's tape is the only user of k_aggregate_tape (pick_tape_engine: selected, or after a range refusal)
         tape = 'mfma' if 'k_aggregate_tape' in self.last_dispatch() else 'fused'
-        min_margin = None
-        if chamfer:
-            loss64, _, g64, margin = self.train_grad_f64_untracked(states, states_delta, attrs, particle_nums, particle_dens, targets,
-                                                                   target_nums, actions=actions)
-            min_margin = float(margin.min())
-        elif actions is not None:
-            loss64, _, g64 = self.train_grad_f64_actions(states, actions, attrs, particle_nums, particle_dens)
-        else:
-            loss64, _, g64 = self.train_grad_f64(states, states_delta, attrs, particle_nums, particle_dens)
+        loss64, _, g64, margin, _ = self._train_grad64(states, states_delta, actions, attrs, particle_nums, particle_dens, targets,
+                                                       target_nums, False)
         tensors, off, worst = {}, 0, None
         for key, shape in STATE_DICT_KEYS:
             n = int(np.prod(shape))
@@ -1063,14 +1003,14 @@ class Engine(object):
         out = {'tensors': tensors, 'worst': worst, 'rel': tensors[worst]['rel'], 'loss32': loss32, 'loss64': loss64,
                'loss_diff': abs(loss32 - loss64), 'tape': tape}
         if chamfer:
-            out['loss_kind'], out['min_margin'] = 'chamfer', min_margin
+            out['loss_kind'], out['min_margin'] = 'chamfer', float(margin.min())
         return out
 
     def train_set_lr(self, lr):
         self._ck(self.lib.drp_train_set_lr(self.h, float(lr)))
 
     def get_weights(self):
-        blob = np.empty((38403,), np.float32)
+        blob = np.empty((L.DRP_N_WEIGHTS,), np.float32)
         self._ck(self.lib.drp_get_weights(self.h, _fp(blob), blob.size))
         return blob
 

@@ -729,7 +729,8 @@ int drp_train_grad_f64_untracked(drp_ctx* ctx, const float* states, const float*
  *   d (fwd + bwd) / d p_i = 2/(3 n_p) (p_i - q_a(i)) + 2/(3 n_q) sum_{j: c(j) = i} (p_i - q_j)       (arg-mins constant)
  * The 1/3 is the per-coordinate mean of F.mse_loss: where the nearest neighbour is the true partner, fwd is the tracked loss's
  * MSE term.  Squared distances in fp32 from fp32 differences, the sums in double, no atomics: the same bits from run to run and
- * for a sample alone or inside any batch.  A one-shot with buffers of its own: needs no weights, ends no drp_mpc_* / drp_gd_* /
+ * for a sample alone or inside any batch.  A one-shot (the three drp_cloud_* calls share one buffer; each ends in a wait and
+ * keeps nothing between calls): needs no weights, ends no drp_mpc_* / drp_gd_* /
  * training session, leaves the selected engine, drp_last_dispatch and the trainer's state alone.  DRP_EINVAL: a null argument
  * (the last three outputs are nullable), a count outside 1..N or 1..M, N or M outside 1..4096. */
 int drp_cloud_chamfer(drp_ctx* ctx, const float* p, const int32_t* n_p, const float* q, const int32_t* n_q,
@@ -740,7 +741,7 @@ int drp_cloud_chamfer(drp_ctx* ctx, const float* p, const int32_t* n_p, const fl
  * in double in that order without fused multiply-add, the arg-mins taken in double (strict <, lowest index on a tie), sums and
  * gradient in double in one fixed order, no atomics.  margin_out [B][2] (nullable): the smallest (second-best - best) squared
  * distance over the real rows' arg-mins, p -> q then q -> p; 0 exactly for a duplicate of a winner, +inf where the other cloud
- * has one row.  Contract and refusals are drp_cloud_chamfer's; a buffer of its own. */
+ * has one row.  Contract and refusals are drp_cloud_chamfer's. */
 int drp_cloud_chamfer_f64(drp_ctx* ctx, const float* p, const int32_t* n_p, const float* q, const int32_t* n_q,
                           int B, int N, int M, double* terms_out /*[B][2]: fwd, bwd*/,
                           double* grad_p_out /*[B][N][3], nullable; scale = 1*/,
@@ -763,8 +764,8 @@ int drp_cloud_chamfer_f64(drp_ctx* ctx, const float* p, const int32_t* n_p, cons
  * batch.  match_pq_out [B][N] / match_qp_out [B][M]: the partner's index, -1 for unmatched rows and padding.  dual_out
  * [B][N + M]: the duals of p's rows, then of q's (0 on padding): u_i + v_j <= C[i][j], equal on matched pairs, 0 on the larger
  * cloud's unmatched rows, sum u + sum v = sum_pairs C.  N and M are at most 1024 (the work is r^2 dependent steps of c / 64
- * each); the kernel's loops are counted by r and c alone, whatever the values.  Contract as drp_cloud_chamfer: a one-shot in a
- * buffer of its own that needs no weights, ends no session and leaves the engine, drp_last_dispatch and the trainer alone.
+ * each); the kernel's loops are counted by r and c alone, whatever the values.  Contract as drp_cloud_chamfer: a one-shot
+ * that needs no weights, ends no session and leaves the engine, drp_last_dispatch and the trainer alone.
  * DRP_EINVAL: a null argument (every output but terms_out is nullable), a count outside 1..N or 1..M, N or M outside 1..1024, a
  * real row that is not finite. */
 int drp_cloud_match(drp_ctx* ctx, const float* p, const int32_t* n_p, const float* q, const int32_t* n_q,

@@ -245,3 +245,28 @@ def test_an_adam_trajectory_survives_calls(golden):
         e.close()
     assert runs[0][0] == runs[1][0]
     np.testing.assert_array_equal(runs[0][1], runs[1][1])
+
+
+def test_the_three_one_shots_share_one_buffer(eng):
+    """drp_cloud_chamfer, drp_cloud_match and drp_cloud_chamfer_f64 stage into one device buffer (c->cloud_io): interleaved on one
+    context, every output asked for, each call returns the bytes it returns as the first call of a fresh context.  A large call
+    before a small one (stale bytes behind a shrunk layout), a small one before a large one (the buffer grows), and 65 against 64
+    rows (the matching kernel's lane-stripe edge, the float64 kernel's first partial chunk); every case has a sample whose
+    counts lie below the padding."""
+    big, small, edge = U.chamfer_case((70, 130, 70, 130), 3), U.chamfer_case((5, 3, 5, 3), 2), U.chamfer_case((65, 60, 65, 64), 1)
+    for p, q, n_p, n_q in (big, small, edge):
+        assert (n_p < p.shape[1]).any() or (n_q < q.shape[1]).any()
+    chamfer = lambda e, c: e.cloud_chamfer(*c, want_grad=True, want_nn=True)
+    match = lambda e, c: e.cloud_match(*c, want_grad=True, want_match=True, want_dual=True)
+    chamfer64 = lambda e, c: e.cloud_chamfer_f64(*c, want_grad=True, want_nn=True)
+    for n, (call, case) in enumerate(((chamfer, big), (match, small), (chamfer64, edge), (chamfer, small), (match, big))):
+        got = call(eng, case)
+        fresh_eng = Engine(0)
+        try:
+            fresh = call(fresh_eng, case)
+        finally:
+            fresh_eng.close()
+        assert sorted(got) == sorted(fresh)
+        for k in fresh:
+            assert got[k].dtype == fresh[k].dtype and got[k].shape == fresh[k].shape
+            assert got[k].tobytes() == fresh[k].tobytes(), 'call %d, %s' % (n, k)

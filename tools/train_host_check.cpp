@@ -8,8 +8,10 @@
 // It stages batches as train_stage_batch does -- the same copies, to the offsets tr_layout gives, into a heap block of exactly
 // TrArena::bytes -- so a block that overlaps the next one or runs past the end is the sanitizer's finding; the offsets are held
 // to the documented layout as well.  The float64 yardsticks' upload (tr64_layout: train_grad_f64_body's one vector, with and
-// without target clouds) is staged the same way, and so is drp_cloud_match's buffer (cm_layout: the inputs staged, every output
-// block written in full), with the check that refuses a real row that is no number.  No device is touched.
+// without target clouds) is staged the same way, and so is the one buffer of the three one-shots on two clouds (cloud_layout with
+// cm_layout's, chamfer_layout's and chamfer64_layout's blocks: the inputs staged, every output block written in full; the two
+// Chamfer layouts held to offset chains written out by hand here, an independent restatement), with the check
+// that refuses a real row that is no number.  No device is touched.
 //
 //   train_host_check layout64 B H N M actions     prints tr64_layout's eight fields (4-byte words) and exits
 #include <cstdio>
@@ -127,19 +129,27 @@ static void stage64(int B, int H, int N, int M, bool actions) {
     std::free(host);
 }
 
-// drp_cloud_match's buffer as capi_match.h uses it: the inputs copied into a vector of exactly CmLayout::in_bytes, every output
-// block written in full inside a block of exactly CmLayout::bytes
-static void stage_match(int B, int N, int M) {
-    const CmLayout lay = cm_layout(B, N, M);
+// a one-shot's buffer as cloud_begin and the kernel use it (capi_pipeline.h): the inputs copied into a vector of exactly
+// CloudLayout::in_bytes, every output block written in full inside a block of exactly CloudLayout::bytes; len: the n_out blocks'
+// sizes, restated by the caller
+static void stage_cloud(const CloudLayout& lay, int B, int N, int M, int n_out, const size_t* out_len) {
     const size_t bn = (size_t)B * N, bm = (size_t)B * M;
-    const size_t off[] = {lay.pts_p, lay.pts_q, lay.n_p, lay.n_q, lay.terms, lay.grad, lay.pq, lay.qp, lay.dual, lay.bytes};
-    const size_t len[] = {bn * 12, bm * 12, (size_t)B * 4, (size_t)B * 4, (size_t)B * 8, bn * 12, bn * 4, bm * 4, (bn + bm) * 8};
-    for (int k = 0; k < 9; ++k) {
+    EXPECT(lay.n_out == n_out);
+    size_t off[4 + CLOUD_MAX_OUT + 1] = {lay.pts_p, lay.pts_q, lay.n_p, lay.n_q};
+    size_t len[4 + CLOUD_MAX_OUT] = {bn * 12, bm * 12, (size_t)B * 4, (size_t)B * 4};
+    for (int k = 0; k < n_out; ++k) {
+        off[4 + k] = lay.out[k];
+        len[4 + k] = out_len[k];
+        EXPECT(lay.out_bytes[k] == out_len[k]);
+    }
+    const int nb = 4 + n_out;
+    off[nb] = lay.bytes;
+    for (int k = 0; k < nb; ++k) {
         EXPECT(off[k] % 16 == 0);
-        EXPECT(off[k] + len[k] <= off[k + 1]);
+        EXPECT(off[k] + len[k] <= off[k + 1]);                   // no block overlaps the next
         EXPECT(off[k + 1] - (off[k] + len[k]) < 16);
     }
-    EXPECT(lay.pts_p == 0 && lay.terms == lay.in_bytes);
+    EXPECT(lay.pts_p == 0 && lay.out[0] == lay.in_bytes);
     std::vector<float> p(bn * 3, 1.0f), q(bm * 3, 2.0f);
     std::vector<int32_t> n_p(B, N), n_q(B, M);
     std::vector<char> stage(lay.in_bytes);
@@ -149,7 +159,7 @@ static void stage_match(int B, int N, int M) {
     std::memcpy(stage.data() + lay.n_q, n_q.data(), (size_t)B * sizeof(int32_t));
     char* io = static_cast<char*>(std::malloc(lay.bytes));
     std::memcpy(io, stage.data(), lay.in_bytes);
-    for (int k = 4; k < 9; ++k) std::memset(io + off[k], k, len[k]);       // the kernel's stores, block by block
+    for (int k = 4; k < nb; ++k) std::memset(io + off[k], k, len[k]);      // the kernel's stores, block by block
     float f; int32_t n;
     std::memcpy(&f, io + lay.pts_p + (bn * 3 - 1) * 4, 4);
     EXPECT(f == 1.0f);
@@ -157,8 +167,40 @@ static void stage_match(int B, int N, int M) {
     EXPECT(f == 2.0f);
     std::memcpy(&n, io + lay.n_q + (size_t)(B - 1) * 4, 4);
     EXPECT(n == M);
-    for (int k = 4; k < 9; ++k) EXPECT(io[off[k]] == k && io[off[k] + len[k] - 1] == k);
+    for (int k = 4; k < nb; ++k) EXPECT(io[off[k]] == k && io[off[k] + len[k] - 1] == k);
     std::free(io);
+}
+static void stage_match(int B, int N, int M) {
+    const size_t bn = (size_t)B * N, bm = (size_t)B * M;
+    const size_t len[] = {(size_t)B * 8, bn * 12, bn * 4, bm * 4, (bn + bm) * 8};
+    stage_cloud(cm_layout(B, N, M), B, N, M, 5, len);
+}
+// drp_cloud_chamfer's and drp_cloud_chamfer_f64's layouts against their offset chains written out block by block (the yardstick
+// of cloud_layout: the offsets a call's kernel and copies have always used), then staged like the matching's
+static void stage_chamfer(int B, int N, int M) {
+    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t bn = (size_t)B * N, bm = (size_t)B * M;
+    const size_t o_p = 0, o_q = up(o_p + bn * 3 * sizeof(float)), o_np = up(o_q + bm * 3 * sizeof(float)),
+                 o_nq = up(o_np + (size_t)B * sizeof(int)), in_bytes = up(o_nq + (size_t)B * sizeof(int));
+    {
+        const size_t o_terms = in_bytes, o_grad = up(o_terms + (size_t)B * 2 * sizeof(double)), o_pq = up(o_grad + bn * 3 * sizeof(float)),
+                     o_qp = up(o_pq + bn * sizeof(int)), bytes = up(o_qp + bm * sizeof(int));
+        const CloudLayout lay = chamfer_layout(B, N, M);
+        EXPECT(lay.pts_p == o_p && lay.pts_q == o_q && lay.n_p == o_np && lay.n_q == o_nq && lay.in_bytes == in_bytes);
+        EXPECT(lay.out[0] == o_terms && lay.out[1] == o_grad && lay.out[2] == o_pq && lay.out[3] == o_qp && lay.bytes == bytes);
+        const size_t len[] = {(size_t)B * 16, bn * 12, bn * 4, bm * 4};
+        stage_cloud(lay, B, N, M, 4, len);
+    }
+    {
+        const size_t o_terms = in_bytes, o_mar = up(o_terms + (size_t)B * 2 * sizeof(double)), o_grad = up(o_mar + (size_t)B * 2 * sizeof(double)),
+                     o_pq = up(o_grad + bn * 3 * sizeof(double)), o_qp = up(o_pq + bn * sizeof(int)), bytes = up(o_qp + bm * sizeof(int));
+        const CloudLayout lay = chamfer64_layout(B, N, M);
+        EXPECT(lay.pts_p == o_p && lay.pts_q == o_q && lay.n_p == o_np && lay.n_q == o_nq && lay.in_bytes == in_bytes);
+        EXPECT(lay.out[0] == o_terms && lay.out[1] == o_mar && lay.out[2] == o_grad && lay.out[3] == o_pq && lay.out[4] == o_qp &&
+               lay.bytes == bytes);
+        const size_t len[] = {(size_t)B * 16, (size_t)B * 16, bn * 24, bn * 4, bm * 4};
+        stage_cloud(lay, B, N, M, 5, len);
+    }
 }
 
 int main(int argc, char** argv) {
@@ -178,6 +220,8 @@ int main(int argc, char** argv) {
     stage64(1, 1, 4096, 4096, false);                            // the largest clouds of one (sample, step)
     const int mshapes[][3] = {{1, 1, 1}, {1, 5, 3}, {3, 7, 9}, {2, 65, 64}, {1, 1024, 1024}, {5, 1024, 1}, {4, 300, 257}};
     for (const auto& s : mshapes) stage_match(s[0], s[1], s[2]);
+    const int cshapes[][3] = {{1, 1, 1}, {2, 5, 3}, {3, 70, 130}, {1, 4096, 4096}};
+    for (const auto& s : cshapes) stage_chamfer(s[0], s[1], s[2]);
     {
         // the finiteness check reads the real rows only, every one of them, and no further
         const float inf32 = std::numeric_limits<float>::infinity(), nan32 = std::numeric_limits<float>::quiet_NaN();
