@@ -55,6 +55,7 @@
 
 #include "dispatch.h"          // host-only: policy, variant flags, plan functions
 #include "train_host.h"        // host-only: the trainer's staged-batch layout and push check
+#include "ptcl_dataset_host.h" // host-only: the dataset calls' upload arena and per-image checks
 #include "capi_ctx.h"
 #include "capi_pipeline.h"
 

@@ -222,16 +222,24 @@ class ParticleDataset(object):
         return (states[0, :, :n].copy(), sdelta[0, :, :n].copy(), np.zeros((T, n), np.float32), n, den,
                 sample['color'])
 
-    def get_batch(self, indices, pool=None):
-        """collate_fn([self[i] for i in indices]) (train/train_gnn_dyn.py:20-45) from the same numpy state, in one
-        device call; `pool`: an executor for the decoding."""
+    def check_limit(self, n):
+        """refuses more samples than one device call takes"""
+        if n > 1024:
+            raise ValueError('get_batch takes at most 1024 samples per call, got %d' % n)
+
+    def load_and_draw(self, indices, pool=None):
+        """the samples of a get_batch, decoded (through `pool` if given), and their draws in sample order"""
         indices = [int(i) for i in indices]
         if not indices:
             raise ValueError('get_batch needs at least one index')
-        if len(indices) > 1024:
-            raise ValueError('get_batch takes at most 1024 samples per call, got %d' % len(indices))
+        self.check_limit(len(indices))
         samples = list(pool.map(self.load, indices)) if pool is not None else [self.load(i) for i in indices]
-        draws = [self.draw(s) for s in samples]
+        return samples, [self.draw(s) for s in samples]
+
+    def get_batch(self, indices, pool=None):
+        """collate_fn([self[i] for i in indices]) (train/train_gnn_dyn.py:20-45) from the same numpy state, in one
+        device call; `pool`: an executor for the decoding."""
+        samples, draws = self.load_and_draw(indices, pool)
         states, sdelta, counts = self.run(samples, draws)
         B, T, n_max, _ = states.shape
         imgs = None if samples[0]['color'] is None else np.stack([s['color'] for s in samples]).astype(np.float32)
@@ -269,6 +277,11 @@ class DepthDataset(ParticleDataset):
         return {'episode': ep, 'depth': depth, 'n_fg': [count_fg(d, self.global_scale) for d in depth],
                 'actions': np.asarray([actions[i] for i in range(t0, t0 + T - 1)], dtype=np.float64).reshape(T - 1, 4),
                 'color': None}
+
+    def check_limit(self, n):
+        T = self.n_his + self.n_roll
+        if n * T > 1024:
+            raise ValueError('get_batch takes at most 1024 frames per call, got %d samples of %d' % (n, T))
 
     @staticmethod
     def draw(sample):
@@ -319,14 +332,7 @@ class DepthDataset(ParticleDataset):
     def get_batch(self, indices, pool=None):
         """collate_untracked([self[i] for i in indices]) from the same numpy state, in one device call, with the raw pushes as
         `.actions` and `depth_only = True`; `pool`: an executor for the decoding."""
-        indices = [int(i) for i in indices]
-        if not indices:
-            raise ValueError('get_batch needs at least one index')
-        T = self.n_his + self.n_roll
-        if len(indices) * T > 1024:
-            raise ValueError('get_batch takes at most 1024 frames per call, got %d samples of %d' % (len(indices), T))
-        samples = list(pool.map(self.load, indices)) if pool is not None else [self.load(i) for i in indices]
-        draws = [self.draw(s) for s in samples]
+        samples, draws = self.load_and_draw(indices, pool)
         return self.collate(self.tuples(samples, draws), [s['actions'] for s in samples])
 
 

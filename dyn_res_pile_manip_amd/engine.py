@@ -1,5 +1,6 @@
 """numpy-facing wrapper of one C-ABI context (one GPU, one HIP stream)."""
 import ctypes
+import types
 
 import numpy as np
 
@@ -1096,18 +1097,45 @@ class Engine(object):
         return out, r, (nfg.value, nd.value)
 
     # ---- GNN training batches from recorded episodes (row x4) ------------
+    def _pd_args(self, depth, names, radius, init_idx, n_fg, episode, cam_params, n_cap, rows):
+        """what the two dataset calls marshal alike: depth [*lead, h, w] uint16 with lead = (B,) or (B, T) as `names` says; radius,
+        init_idx, n_fg per image, [*lead]; episode [B] or None; cam [4]; per entry r of rows an output of prod(lead) * r * n_cap
+        * 3 floats (np.empty: only the pages the call writes are ever touched); counts [*lead]; n_max"""
+        a = types.SimpleNamespace()
+        a.depth = np.ascontiguousarray(depth, dtype=np.uint16)
+        if a.depth.ndim != len(names) + 2:
+            raise ValueError('depth must be [%s, h, w], got %s' % (', '.join(names), a.depth.shape))
+        a.lead, (a.h, a.w) = a.depth.shape[:-2], a.depth.shape[-2:]
+        a.radius, a.init, a.nfg = _f64(radius), _i32(init_idx), _i32(n_fg)
+        if len(a.lead) == 1:                # one image per sample: [B], [B, 1], ... alike
+            a.radius, a.init, a.nfg = a.radius.reshape(a.lead), a.init.reshape(a.lead), a.nfg.reshape(a.lead)
+        for name, x in (('radius', a.radius), ('init_idx', a.init), ('n_fg', a.nfg)):
+            if x.shape != a.lead:
+                raise ValueError('%s must be [%s] = %s, got %s' % (name, ', '.join(names), a.lead, x.shape))
+        a.ep = None if episode is None else _i32(episode).reshape(a.lead[0])
+        a.cam = _f64(cam_params).reshape(4)
+        n_cap, n_img = int(n_cap), int(np.prod(a.lead))
+        a.outs = [np.empty((n_img * r * max(n_cap, 0) * 3,), np.float32) for r in rows]
+        a.counts = np.empty(a.lead, np.int32)
+        a.n_max = ctypes.c_int()
+        # the three argument runs the two C calls share
+        a.image = (a.depth.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)), a.h, a.w)
+        a.per_image = (_dp(a.radius), _ip(a.init), _ip(a.nfg))
+        a.tail = (None if a.ep is None else _ip(a.ep), n_cap) + tuple(_fp(o) for o in a.outs) + (_ip(a.counts), ctypes.byref(a.n_max))
+        return a
+
     def ptcl_dataset_batch(self, depth, global_scale, cam_params, T_cam, particles, radius, init_idx, n_fg, push,
                            episode=None, n_cap=L.PD_CAP):
         """ParticleDataset.__getitem__ for B samples on the device, collated (drp_ptcl_dataset_batch).
         depth [B,h,w] uint16; T_cam [4,4] = inv(opencv_T_world); particles: B arrays [T,n_ptcl_b,4] float32; radius [B]
         = 1/sqrt(den); init_idx [B]; n_fg [B] host foreground counts; push [B,T-1,10] float64.
         -> (states [B,T,n_max,3] f32, states_delta [B,T-1,n_max,3] f32, counts [B] int32)"""
-        depth = np.ascontiguousarray(depth, dtype=np.uint16)
-        B, h, w = depth.shape
         parts = [np.ascontiguousarray(p, dtype=np.float32) for p in particles]
+        T = parts[0].shape[0]
+        a = self._pd_args(depth, ('B',), radius, init_idx, n_fg, episode, cam_params, n_cap, (T, T - 1))
+        B, = a.lead
         if len(parts) != B:
             raise ValueError('%d particle arrays for %d depth images' % (len(parts), B))
-        T = parts[0].shape[0]
         for p in parts:
             if p.ndim != 3 or p.shape[0] != T or p.shape[2] != 4:
                 raise ValueError('particles must be [T, n, 4] with one T for the batch, got %s' % (p.shape,))
@@ -1116,68 +1144,46 @@ class Engine(object):
         push = _f64(push)
         if push.shape != (B, T - 1, 10):
             raise ValueError('push must be [B, T-1, 10] = %s, got %s' % ((B, T - 1, 10), push.shape))
-        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-        ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
-        radius, init, nfg = _f64(radius).reshape(B), i32(init_idx).reshape(B), i32(n_fg).reshape(B)
-        ep = None if episode is None else i32(episode).reshape(B)
-        Tm, cam = _f64(T_cam).reshape(16), _f64(cam_params).reshape(4)
-        n_cap = int(n_cap)
-        # np.empty: only the pages the call writes (B * T * n_max * 3 floats) are ever touched
-        states = np.empty((B * T * n_cap * 3,), np.float32)
-        sdelta = np.empty((B * (T - 1) * n_cap * 3,), np.float32)
-        counts = np.empty((B,), np.int32)
-        n_max = ctypes.c_int()
+        Tm = _f64(T_cam).reshape(16)
         self._ck(self.lib.drp_ptcl_dataset_batch(
-            self.h, B, depth.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)), h, w, float(global_scale), _dp(cam), _dp(Tm),
-            T, ip(n_ptcl), _fp(flat), _dp(radius), ip(init), ip(nfg), _dp(push), None if ep is None else ip(ep), n_cap,
-            _fp(states), _fp(sdelta), ip(counts), ctypes.byref(n_max)))
-        nm = n_max.value
+            self.h, B, *a.image, float(global_scale), _dp(a.cam), _dp(Tm), T, _ip(n_ptcl), _fp(flat), *a.per_image, _dp(push),
+            *a.tail))
+        nm = a.n_max.value
         self._pd_shape = (B, nm)
+        states, sdelta = a.outs
         return (states[:B * T * nm * 3].reshape(B, T, nm, 3), sdelta[:B * (T - 1) * nm * 3].reshape(B, T - 1, nm, 3),
-                counts)
+                a.counts)
 
     def ptcl_dataset_frames(self, depth, global_scale, cam_params, radius, init_idx, n_fg, episode=None, n_cap=L.PD_CAP):
         """depth2fgpcd -> fps_rad -> recenter on every frame of B windows of T depth frames (drp_ptcl_dataset_frames): untracked
         training samples without a particle file.  depth [B,T,h,w] uint16; radius, init_idx, n_fg [B,T] (fps_rad's radius, the
         sampler's start and the host's foreground count of every frame); B * T <= 1024.
         -> (clouds [B,T,n_max,3] f32, +0.0 beyond each count; counts [B,T] int32)"""
-        depth = np.ascontiguousarray(depth, dtype=np.uint16)
-        if depth.ndim != 4:
-            raise ValueError('depth must be [B, T, h, w], got %s' % (depth.shape,))
-        B, T, h, w = depth.shape
-        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-        ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
-        radius, init, nfg = _f64(radius), i32(init_idx), i32(n_fg)
-        for name, a in (('radius', radius), ('init_idx', init), ('n_fg', nfg)):
-            if a.shape != (B, T):
-                raise ValueError('%s must be [B, T] = %s, got %s' % (name, (B, T), a.shape))
-        ep = None if episode is None else i32(episode).reshape(B)
-        cam = _f64(cam_params).reshape(4)
-        n_cap = int(n_cap)
-        # np.empty: only the pages the call writes (B * T * n_max * 3 floats) are ever touched
-        clouds = np.empty((B * T * max(n_cap, 0) * 3,), np.float32)
-        counts = np.empty((B, T), np.int32)
-        n_max = ctypes.c_int()
+        a = self._pd_args(depth, ('B', 'T'), radius, init_idx, n_fg, episode, cam_params, n_cap, (1,))
+        B, T = a.lead
         self._pdf_shape = (0, 0, 0)
-        self._ck(self.lib.drp_ptcl_dataset_frames(
-            self.h, B, T, depth.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)), h, w, float(global_scale), _dp(cam),
-            _dp(radius), ip(init), ip(nfg), None if ep is None else ip(ep), n_cap, _fp(clouds), ip(counts),
-            ctypes.byref(n_max)))
-        nm = n_max.value
+        self._ck(self.lib.drp_ptcl_dataset_frames(self.h, B, T, *a.image, float(global_scale), _dp(a.cam), *a.per_image, *a.tail))
+        nm = a.n_max.value
         self._pdf_shape = (B, T, nm)
-        return clouds[:B * T * nm * 3].reshape(B, T, nm, 3), counts
+        return a.outs[0][:B * T * nm * 3].reshape(B, T, nm, 3), a.counts
+
+    def _pd_tap(self, prefix, names, lead, nm, name):
+        """one of the intermediates `names` of the last dataset call over images [*lead]: the debug tap prefix + name"""
+        if name not in names:
+            raise KeyError(name)
+        shape, dt = {'nfg': ((), np.int32), 'chosen': ((L.PD_CAP + 1,), np.int32), 'recenter': ((nm, 3), np.float64),
+                     'nearest': ((nm,), np.int32)}[name]
+        return self.debug_fetch(prefix + name, tuple(lead) + shape, dt)
 
     def ptcl_dataset_frames_tap(self, name):
         """intermediates of the last ptcl_dataset_frames: 'nfg' [B,T], 'chosen' [B,T,4097], 'recenter' [B,T,n_max,3] float64.
         Refused (DrpError) when a ptcl_dataset_batch has run since: the two calls share their buffers"""
         B, T, nm = getattr(self, '_pdf_shape', (0, 0, 0))
-        shape, dt = {'nfg': ((B, T), np.int32), 'chosen': ((B, T, L.PD_CAP + 1), np.int32),
-                     'recenter': ((B, T, nm, 3), np.float64)}[name]
-        return self.debug_fetch('pdf_' + name, shape, dt)
+        return self._pd_tap('pdf_', ('nfg', 'chosen', 'recenter'), (B, T), nm, name)
 
     def ptcl_dataset_time(self):
-        """device ms of the last ptcl_dataset_batch / ptcl_dataset_frames (there 'track_pack' is the pack alone) by stage: {'upload', 'compaction', 'fps_rad', 'recenter', 'track_pack',
-        'download'}"""
+        """device ms of the last ptcl_dataset_batch / ptcl_dataset_frames by stage: {'upload', 'compaction', 'fps_rad', 'recenter',
+        'track_pack', 'download'}; after a ptcl_dataset_frames 'track_pack' is the pack alone"""
         ms = np.empty((6,), np.float32)
         self._ck(self.lib.drp_ptcl_dataset_time(self.h, _fp(ms)))
         return dict(zip(('upload', 'compaction', 'fps_rad', 'recenter', 'track_pack', 'download'), ms.tolist()))
@@ -1186,9 +1192,7 @@ class Engine(object):
         """intermediates of the last ptcl_dataset_batch: 'nfg' [B], 'chosen' [B,4097], 'recenter' [B,n_max,3] float64,
         'nearest' [B,n_max]"""
         B, nm = getattr(self, '_pd_shape', (0, 0))
-        shape, dt = {'nfg': ((B,), np.int32), 'chosen': ((B, L.PD_CAP + 1), np.int32),
-                     'recenter': ((B, nm, 3), np.float64), 'nearest': ((B, nm), np.int32)}[name]
-        return self.debug_fetch('pd_' + name, shape, dt)
+        return self._pd_tap('pd_', ('nfg', 'chosen', 'recenter', 'nearest'), (B,), nm, name)
 
     # ---- gradient-descent planner ---------------------------------------
     def gd_begin(self, s0, attr, dens, actions, lr, act_lo, act_hi):

@@ -215,3 +215,12 @@ def test_data_depth_flag_logic(tmp_path):
         with pytest.raises(SystemExit) as ei:
             TG._cli(argv)
         assert ei.value.code == 2
+
+
+def test_the_dataset_calls_host_arithmetic_passes_its_check_program(tmp_path):
+    """csrc/ptcl_dataset_host.h (arena layout, per-image checks) is plain C++: tools/ptcl_dataset_host_check.cpp built for the host"""
+    import subprocess
+    import __graft_entry__ as g
+    exe = str(tmp_path / 'ptcl_dataset_host_check')
+    subprocess.check_call([g.HIPCC, '-x', 'c++', '-std=c++17', '-O1', os.path.join(ROOT, 'tools', 'ptcl_dataset_host_check.cpp'), '-o', exe])
+    assert 'all checks passed' in subprocess.check_output([exe]).decode()

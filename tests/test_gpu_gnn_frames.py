@@ -357,6 +357,66 @@ def test_refusals_name_episode_and_frame_and_leave_the_context_usable(eng):
     _bits(again[1], good[1])
 
 
+def _at(a, idx, v):
+    a = np.array(a)
+    a[idx] = v
+    return a
+
+
+def _refused_then_good(call, good, cases):
+    """every input of `cases` carries two faults: (overrides, what the message says, what it does not say); after each refusal a
+    good call gives the bits of the good call made before it"""
+    from dyn_res_pile_manip_amd import _lib
+    for kw, says, silent in cases:
+        with pytest.raises(_lib.DrpError) as ei:
+            call(**kw)
+        msg = str(ei.value)
+        assert 'drp error -1:' in msg and all(s in msg for s in says) and silent not in msg, (kw, msg)
+        for x, y in zip(call(), good):
+            _bits(x, y)
+
+
+def test_batch_call_names_the_first_of_two_faults(eng):
+    # B = 2, T = 2: five particles per frame, T_cam identity, unit in-plane pushes
+    n_fg = [500, 640]
+    rng = np.random.default_rng(3)
+    push = np.zeros((2, 1, 10))
+    push[..., 6] = push[..., 9] = 1.0
+    base = dict(depth=np.stack([_crafted(n, 200 + b) for b, n in enumerate(n_fg)]), global_scale=24, cam_params=SMALL_CAM,
+                T_cam=np.eye(4), particles=[rng.normal(size=(2, 5, 4)).astype(np.float32) for _ in range(2)], radius=[0.05, 0.07],
+                init_idx=[3, 639], n_fg=n_fg, push=push, episode=[41, 57])
+    call = lambda **kw: eng.ptcl_dataset_batch(**dict(base, **kw))
+    good = call()
+    assert good[0].shape[:2] == (2, 2) and good[2].min() > 1
+    _refused_then_good(call, good, [
+        # within a sample: the radius before the pushes
+        (dict(radius=_at(base['radius'], 0, np.inf), push=_at(push, (0, 0, 9), 0.0)), ('bad fps radius', 'episode 41:'), 'push'),
+        # across samples: sample 0's last check before sample 1's first
+        (dict(push=_at(push, (0, 0, 8), 0.5), init_idx=_at(base['init_idx'], 1, -1)), ('leaves the table plane', 'episode 41:'),
+         'sampler start'),
+        # behind the counts wait: the host's count before the start
+        (dict(n_fg=_at(n_fg, 1, 639), init_idx=_at(base['init_idx'], 1, 640)), ('foreground pixels on the host', 'episode 57:'),
+         'sampler start'),
+    ])
+
+
+def test_frames_call_names_the_first_of_two_faults(eng):
+    n_fg = np.array([[500, 300, 640], [64, 900, 1100]])             # B = 2, T = 3
+    base = dict(depth=np.stack([np.stack([_crafted(n, 100 + 10 * b + t) for t, n in enumerate(row)]) for b, row in enumerate(n_fg)]),
+                global_scale=24, cam_params=SMALL_CAM, radius=np.array([[0.05, 0.07, 0.04], [0.1, 0.03, 0.06]]),
+                init_idx=np.array([[3, 299, 0], [63, 10, 555]]), n_fg=n_fg, episode=[41, 57])
+    call = lambda **kw: eng.ptcl_dataset_frames(**dict(base, **kw))
+    good = call()
+    _refused_then_good(call, good, [
+        # within an image: the start before the radius
+        (dict(init_idx=_at(base['init_idx'], (0, 1), -1), radius=_at(base['radius'], (0, 1), 0.0)),
+         ('sampler start', 'episode 41 frame 1:'), 'radius'),
+        # across images in (b, t) order: the last check of (0, 2) before the radius of (1, 0)
+        (dict(radius=_at(base['radius'], (1, 0), np.nan), n_fg=_at(n_fg, (0, 2), 40 * 33 + 1)),
+         ('host foreground count', 'episode 41 frame 2:'), 'radius'),
+    ])
+
+
 # ---- 7: isolation ----------------------------------------------------------------------------------------------------------
 def test_isolation_from_training_extraction_and_the_batch_call(tracked_episodes, episodes, eng):
     from dyn_res_pile_manip_amd import _lib, synthetic as syn, weights

@@ -28,6 +28,32 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+STAGES = ('upload', 'compaction', 'fps_rad', 'recenter', 'track_pack', 'download')
+
+
+def tracked_step(eng, cam, cfg, T):
+    eng.train_begin(5, 1e-3, 0.9)
+    return lambda b: eng.train_step(*b[:5], mode='update')
+
+
+def depth_step(eng, cam, cfg, T):
+    from dyn_res_pile_manip_amd.planners import world2cam_affine
+    eng.set_camera(world2cam_affine(np.asarray(cam[1], dtype=np.float64)), float(cfg['dataset']['global_scale']), cam[0])
+    eng.train_begin(T - 1, 1e-3, 0.9)
+    return lambda b: eng.train_step_actions(b[0], b.actions, b[2], b[3], b[4], b[6], b[7], mode='update')
+
+
+# per mode: the dataset class, the batch sizes, the fifth stage's label, the files a sample does not have, the trainer step; then
+# what its printed lines say differently (T: frames per sample)
+MODES = {
+    False: dict(cls='ParticleDataset', sizes=(4, 64, 256), label='track_pack', strip=(), step=tracked_step, trainer='trainer',
+                of_T='', per='sample', x_T='', decode_n=48, pngs='', rate='%.0f'),
+    True: dict(cls='DepthDataset', sizes=(4, 16, 64), label='pack', strip=('_particles.npy', '_color.png'), step=depth_step,
+               trainer='Chamfer + actions trainer', of_T=' of %(T)d frames', per='frame', x_T=' x T=%(T)d', decode_n=32,
+               pngs=' (%(T)d PNGs)', rate='%.1f'),
+}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--episodes', type=int, default=4)
@@ -35,87 +61,13 @@ def main():
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--frames', action='store_true', help='time drp_ptcl_dataset_frames / DepthDataset instead')
     a = ap.parse_args()
-    if a.frames:
-        return frames(a)
-    import __graft_entry__ as g
-    g.build()
-    from concurrent.futures import ThreadPoolExecutor
-    from dyn_res_pile_manip_amd import synthetic
-    from dyn_res_pile_manip_amd.dataset_gnn_dyn import DeviceLoader, ParticleDataset
-    from dyn_res_pile_manip_amd.engine import Engine
-    from dyn_res_pile_manip_amd.train_gnn_dyn import default_config
-    eng = Engine(0)
-    print('device: %s' % eng.device_info()['name'])
-    cfg = default_config()
-    cfg['dataset'].update(n_episode=a.episodes, n_timestep=10)
-    cfg['train']['train_valid_ratio'] = 1.0
-    with tempfile.TemporaryDirectory() as d:
-        t0 = time.perf_counter()
-        synthetic.write_episodes(d, a.episodes, 10, seed=0)
-        cam = (synthetic.demo_cam_params(), synthetic.demo_cam_extrinsics())
-        ds = ParticleDataset(d, cfg, 'train', cam, engine=eng)
-        print('%d episodes, %d samples (written in %.1f s)' % (a.episodes, len(ds), time.perf_counter() - t0))
-        samples = [ds.load(i) for i in range(len(ds))]
-        print('foreground points per sample: %d .. %d' % (min(s['n_fg'] for s in samples), max(s['n_fg'] for s in samples)))
-        np.random.seed(0)
-        stages = ('upload', 'compaction', 'fps_rad', 'recenter', 'track_pack', 'download')
-        for B in (4, 64, 256):
-            rows, walls, nmax = [], [], []
-            for r in range(a.reps + 1):
-                batch = [samples[(r * B + j) % len(samples)] for j in range(B)]
-                draws = [ds.draw(s) for s in batch]
-                t0 = time.perf_counter()
-                st, _, cnt = ds.run(batch, draws)
-                wall = time.perf_counter() - t0
-                if r == 0:
-                    continue                       # first call: allocations
-                rows.append([ds.engine.ptcl_dataset_time()[k] for k in stages])
-                walls.append(wall * 1e3)
-                nmax.append(int(cnt.max()))
-            med = np.median(np.array(rows), axis=0)
-            print('B=%3d device ms: %s | sum %.2f | call wall %.2f ms | max particles %d' % (
-                B, ' '.join('%s %.3f' % (k, v) for k, v in zip(stages, med)), med.sum(), np.median(walls),
-                max(nmax)))
-        for threads in (1, a.threads):
-            n = 48
-            with ThreadPoolExecutor(max_workers=threads) as pool:
-                t0 = time.perf_counter()
-                list(pool.map(ds.load, [i % len(ds) for i in range(n)]))
-                dt = time.perf_counter() - t0
-            print('host decode: %.2f ms per sample on %d thread(s)' % (dt / n * 1e3, threads))
-        np.random.seed(0)
-        import torch
-        torch.manual_seed(0)
-        loader = DeviceLoader(ds, 4, shuffle=True, chunk=64, threads=a.threads)
-        t0 = time.perf_counter()
-        batches = list(loader)
-        dt = time.perf_counter() - t0
-        print('DeviceLoader batch 4, chunk 64, %d threads: %.0f samples/s' % (a.threads, len(ds) / dt))
-        from dyn_res_pile_manip_amd import weights
-        eng.load_weights(weights.blob_from_state_dict(weights.random_state_dict(seed=0, predictor_scale=1.0)), 0.08)
-        eng.train_begin(5, 1e-3, 0.9)
-        for b in batches[:2]:
-            eng.train_step(*b[:5], mode='update')
-        t0 = time.perf_counter()
-        k = 0
-        for _ in range(5):
-            for b in batches:
-                eng.train_step(*b[:5], mode='update')
-                k += 1
-        dt = time.perf_counter() - t0
-        print('trainer at batch 4: %.2f ms per step = %.0f samples/s' % (dt / k * 1e3, 4 * k / dt))
-    eng.close()
-
-
-def frames(a):
+    m = MODES[a.frames]
     import __graft_entry__ as g
     g.build()
     from concurrent.futures import ThreadPoolExecutor
     import torch
-    from dyn_res_pile_manip_amd import synthetic, weights
-    from dyn_res_pile_manip_amd.dataset_gnn_dyn import DepthDataset, DeviceLoader
+    from dyn_res_pile_manip_amd import dataset_gnn_dyn, synthetic, weights
     from dyn_res_pile_manip_amd.engine import Engine
-    from dyn_res_pile_manip_amd.planners import world2cam_affine
     from dyn_res_pile_manip_amd.train_gnn_dyn import default_config
     eng = Engine(0)
     print('device: %s' % eng.device_info()['name'])
@@ -125,54 +77,52 @@ def frames(a):
     with tempfile.TemporaryDirectory() as d:
         t0 = time.perf_counter()
         synthetic.write_episodes(d, a.episodes, 10, seed=0)
-        for ep in os.listdir(d):                       # what a recorded robot episode holds: depth PNGs and actions.p
+        for ep in os.listdir(d):                       # --frames: what a recorded robot episode holds, depth PNGs and actions.p
             for f in os.listdir(os.path.join(d, ep)):
-                if f.endswith('_particles.npy') or f.endswith('_color.png'):
+                if m['strip'] and f.endswith(m['strip']):
                     os.remove(os.path.join(d, ep, f))
         cam = (synthetic.demo_cam_params(), synthetic.demo_cam_extrinsics())
-        ds = DepthDataset(d, cfg, 'train', cam, engine=eng)
+        ds = getattr(dataset_gnn_dyn, m['cls'])(d, cfg, 'train', cam, engine=eng)
         T = ds.n_his + ds.n_roll
-        print('%d episodes, %d samples of %d frames (written in %.1f s)' % (a.episodes, len(ds), T, time.perf_counter() - t0))
+        fill = lambda text: text % {'T': T}
+        print('%d episodes, %d samples%s (written in %.1f s)' % (a.episodes, len(ds), fill(m['of_T']), time.perf_counter() - t0))
         samples = [ds.load(i) for i in range(len(ds))]
-        fg = [n for s in samples for n in s['n_fg']]
-        print('foreground points per frame: %d .. %d' % (min(fg), max(fg)))
+        fg = np.concatenate([np.atleast_1d(s['n_fg']) for s in samples])
+        print('foreground points per %s: %d .. %d' % (m['per'], fg.min(), fg.max()))
         np.random.seed(0)
-        stages = ('upload', 'compaction', 'fps_rad', 'recenter', 'track_pack', 'download')
-        for B in (4, 16, 64):
+        for B in m['sizes']:
             rows, walls, nmax = [], [], []
             for r in range(a.reps + 1):
                 batch = [samples[(r * B + j) % len(samples)] for j in range(B)]
                 draws = [ds.draw(s) for s in batch]
                 t0 = time.perf_counter()
-                _, cnt = ds.run(batch, draws)
+                cnt = ds.run(batch, draws)[-1]
                 wall = time.perf_counter() - t0
                 if r == 0:
                     continue                       # first call: allocations
-                rows.append([eng.ptcl_dataset_time()[k] for k in stages])
+                rows.append([eng.ptcl_dataset_time()[k] for k in STAGES])
                 walls.append(wall * 1e3)
                 nmax.append(int(cnt.max()))
             med = np.median(np.array(rows), axis=0)
-            print('B=%3d x T=%d device ms: %s | sum %.2f | call wall %.2f ms | max particles %d' % (
-                B, T, ' '.join('%s %.3f' % (k if k != 'track_pack' else 'pack', v) for k, v in zip(stages, med)), med.sum(),
-                np.median(walls), max(nmax)))
+            print('B=%3d%s device ms: %s | sum %.2f | call wall %.2f ms | max particles %d' % (
+                B, fill(m['x_T']), ' '.join('%s %.3f' % (k if k != 'track_pack' else m['label'], v) for k, v in zip(STAGES, med)),
+                med.sum(), np.median(walls), max(nmax)))
         for threads in (1, a.threads):
-            n = 32
+            n = m['decode_n']
             with ThreadPoolExecutor(max_workers=threads) as pool:
                 t0 = time.perf_counter()
                 list(pool.map(ds.load, [i % len(ds) for i in range(n)]))
                 dt = time.perf_counter() - t0
-            print('host decode: %.2f ms per sample (%d PNGs) on %d thread(s)' % (dt / n * 1e3, T, threads))
+            print('host decode: %.2f ms per sample%s on %d thread(s)' % (dt / n * 1e3, fill(m['pngs']), threads))
         np.random.seed(0)
         torch.manual_seed(0)
-        loader = DeviceLoader(ds, 4, shuffle=True, threads=a.threads)
+        loader = dataset_gnn_dyn.DeviceLoader(ds, 4, shuffle=True, threads=a.threads)
         t0 = time.perf_counter()
         batches = list(loader)
         dt = time.perf_counter() - t0
-        print('DeviceLoader batch 4, chunk %d, %d threads: %.1f samples/s' % (loader.chunk, a.threads, len(ds) / dt))
+        print(('DeviceLoader batch 4, chunk %%d, %%d threads: %s samples/s' % m['rate']) % (loader.chunk, a.threads, len(ds) / dt))
         eng.load_weights(weights.blob_from_state_dict(weights.random_state_dict(seed=0, predictor_scale=1.0)), 0.08)
-        eng.set_camera(world2cam_affine(np.asarray(cam[1], dtype=np.float64)), float(cfg['dataset']['global_scale']), cam[0])
-        eng.train_begin(T - 1, 1e-3, 0.9)
-        step = lambda b: eng.train_step_actions(b[0], b.actions, b[2], b[3], b[4], b[6], b[7], mode='update')
+        step = m['step'](eng, cam, cfg, T)
         for b in batches[:2]:
             step(b)
         t0 = time.perf_counter()
@@ -182,7 +132,7 @@ def frames(a):
                 step(b)
                 k += 1
         dt = time.perf_counter() - t0
-        print('Chamfer + actions trainer at batch 4: %.2f ms per step = %.0f samples/s' % (dt / k * 1e3, 4 * k / dt))
+        print('%s at batch 4: %.2f ms per step = %.0f samples/s' % (m['trainer'], dt / k * 1e3, 4 * k / dt))
     eng.close()
 
 
