@@ -22,6 +22,7 @@ ENGINE_LITE = 4             # opt-in reduced products on the fused engine's kern
 TRAIN_MODES = {'eval': 0, 'grad': 1, 'update': 2}
 LOSS_KINDS = {'chamfer': 1, 'match': 2, 'chamfer+match': 3}     # DRP_LOSS_*: drp_train_step_loss
 MATCH_MAX_POINTS = 1024     # KA_MAX_POINTS: the largest cloud of a matching
+TRANSPORT_MAX_ITERS = 1000  # DRP_TRANSPORT_MAX_ITERS: the most sweeps of drp_cloud_transport / drp_train_step_transport
 DIST_TRANSFORMS = {'cv5': 0, 'exact': 1}
 RGR_REGRESSOR = 1           # DRP_RGR_REGRESSOR: n_out of the MPCResRgrNoPool head
 RGR_CLASSIFIER = 6          # DRP_RGR_CLASSIFIER: n_out of the MPCResCls head
@@ -211,6 +212,11 @@ SIGNATURES = {
     'drp_train_step_loss': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, c_int32_p, c_float_p,
                                            ctypes.c_int, ctypes.c_int, c_float_p, c_int32_p, ctypes.c_int, ctypes.c_int,
                                            ctypes.c_double, ctypes.c_int, c_double_p, c_float_p, c_int32_p]),
+    'drp_cloud_transport': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_int32_p, c_float_p, c_int32_p, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, c_float_p, c_double_p, c_double_p]),
+    'drp_train_step_transport': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, c_int32_p, c_float_p,
+                                                ctypes.c_int, ctypes.c_int, c_float_p, c_int32_p, ctypes.c_int, c_double_p,
+                                                ctypes.c_int, ctypes.c_int, c_double_p, c_float_p, c_double_p]),
 }
 
 _lib = None

@@ -12,8 +12,11 @@ const int* tr_nums(const drp_ctx* c, const TrArena& lay) {
 // what seeds the reverse pass: the tracked loss (kt_mse_grad against the given next states) or the Chamfer loss against
 // untracked target clouds (k_chamfer.h), the one-to-one matching loss against them (k_match.h), or the two mixed; the targets as
 // the HOST gave them (the entry point stages them behind the batch).  The kinds beyond the MSE are include/drp.h's DRP_LOSS_*.
-// The float64 yardstick (capi_grad_f64.h) reads the same description; it has the MSE and the Chamfer loss
-enum { TR_LOSS_MSE = 0, TR_LOSS_CHAMFER = DRP_LOSS_CHAMFER, TR_LOSS_MATCH = DRP_LOSS_MATCH, TR_LOSS_CHAMFER_MATCH = DRP_LOSS_CHAMFER_MATCH };
+// The float64 yardstick (capi_grad_f64.h) reads the same description; it has the MSE and the Chamfer loss.
+// TR_LOSS_TRANSPORT (k_transport.h) is internal: drp_train_step_transport's, no loss_kind of drp_train_step_loss
+enum { TR_LOSS_MSE = 0, TR_LOSS_CHAMFER = DRP_LOSS_CHAMFER, TR_LOSS_MATCH = DRP_LOSS_MATCH, TR_LOSS_CHAMFER_MATCH = DRP_LOSS_CHAMFER_MATCH,
+       TR_LOSS_TRANSPORT = 4 };
+static_assert(KT_MAX_ITERS == DRP_TRANSPORT_MAX_ITERS, "include/drp.h states the kernel's cap");
 struct TrLoss {
     int kind = TR_LOSS_MSE;
     const float* targets = nullptr;         // [B][H][M][3]
@@ -22,6 +25,10 @@ struct TrLoss {
     double match_weight = 0.0;              // TR_LOSS_CHAMFER_MATCH: (1 - w) Chamfer + w matching
     int32_t* match_out = nullptr;           // the caller's [H][B][N], nullable: every predicted row's partner (kinds with a matching)
     double* margin_out = nullptr;           // float64 only: the caller's [H][B], nullable (kc64_chamfer's arg-min margins)
+    const double* eps = nullptr;            // TR_LOSS_TRANSPORT: the caller's [B], the regularisation of every step of a sample
+    int iters = 0;                          // TR_LOSS_TRANSPORT: the sweeps
+    double* col_err_out = nullptr;          // TR_LOSS_TRANSPORT: the caller's [H][B], nullable
+    bool transport() const { return kind == TR_LOSS_TRANSPORT; }
     bool chamfer() const { return kind == TR_LOSS_CHAMFER || kind == TR_LOSS_CHAMFER_MATCH; }
     bool match() const { return kind == TR_LOSS_MATCH || kind == TR_LOSS_CHAMFER_MATCH; }
     static TrLoss against(int kind, const float* targets, const int32_t* target_nums, int M) {
@@ -48,6 +55,14 @@ int check_target_nums(drp_ctx* c, const TrLoss& lk, int B, int H) {
     for (int e = 0; e < B * H; ++e)
         if (lk.target_nums[e] <= 0 || lk.target_nums[e] > lk.M)
             return fail(c, DRP_EINVAL, "target_nums[%d][%d]=%d outside 1..%d", e / H, e % H, lk.target_nums[e], lk.M);
+    return DRP_OK;
+}
+// eps [B] and iters as drp_cloud_transport and drp_train_step_transport refuse them
+int check_transport_params(drp_ctx* c, const double* eps, int B, int iters) {
+    if (!eps) return fail(c, DRP_EINVAL, "null argument");
+    const int bad = first_bad_eps(eps, B);
+    if (bad >= 0) return fail(c, DRP_EINVAL, "eps[%d]=%g is not a positive finite number", bad, eps[bad]);
+    if (iters < 1 || iters > KT_MAX_ITERS) return fail(c, DRP_EINVAL, "iters=%d outside 1..%d", iters, KT_MAX_ITERS);
     return DRP_OK;
 }
 // step t of the predictions (p's strides) against step t of the target clouds [B][H][M][3] and their counts [B][H] as staged
@@ -138,6 +153,17 @@ int train_forward_backward(drp_ctx* c, int B, int N, const TrainPass& tp) {
             a.match_pq = ptr<int>(c->tr_match);
             a.zero = lk.chamfer() ? (float*)nullptr : zero; a.n_zero = n_zero;
             ka_launch<true>(dim3(B, H), st, a);
+        }
+        if (lk.transport()) {
+            // the Chamfer kernel's outputs and zero-fill; eps [B] lies behind the staged batch, col_err [H][B] behind the terms
+            KtArgs a{};
+            a.cp = cp; a.pred = states;
+            a.eps = reinterpret_cast<const double*>(ar + lay.eps); a.iters = lk.iters;
+            a.scale = (double)scale;
+            a.grad = g_state; a.terms = loss;
+            a.col_err = lk.col_err_out != nullptr ? ptr<double>(c->tr_loss) + (size_t)H * B : (double*)nullptr;
+            a.zero = zero; a.n_zero = n_zero;
+            hipLaunchKernelGGL((kt_transport<true>), dim3(B, H), dim3(KT_THREADS), 0, st, a);
         }
     }
     HIPCHK(c, hipGetLastError());
@@ -360,6 +386,11 @@ int train_check_args(drp_ctx* c, const float* states, const float* impulses, boo
             if (lk.kind == TR_LOSS_CHAMFER_MATCH && !(lk.match_weight > 0.0 && lk.match_weight < 1.0))
                 return fail(c, DRP_EINVAL, "match_weight %g outside (0, 1)", lk.match_weight);
         }
+        if (lk.transport()) {
+            if (N > KT_MAX_POINTS || lk.M > KT_MAX_POINTS)
+                return fail(c, DRP_EINVAL, "the transport loss takes clouds of 1..%d points: N=%d M=%d", KT_MAX_POINTS, N, lk.M);
+            CHK(check_transport_params(c, lk.eps, B, lk.iters));
+        }
         CHK(check_target_nums(c, lk, B, c->tr_nroll));
     }
     return DRP_OK;
@@ -399,7 +430,7 @@ int train_ensure_workspace(drp_ctx* c, int B, int N, TrainPass& tp) {
         for (DevBuf* b : edge64) CHK(ensure(c, *b, kt * bnk * 64 * sizeof(float)));
         CHK(ensure(c, c->ed_x0, kt * bnk * 8 * sizeof(float)));
     }
-    CHK(ensure(c, c->tr_loss, (size_t)H * B * sizeof(double)));
+    CHK(ensure(c, c->tr_loss, (size_t)H * B * sizeof(double) * (tp.lk.transport() ? 2 : 1)));    // (the transport loss: col_err behind the terms)
     if (tp.lk.match()) CHK(ensure(c, c->tr_match, (size_t)H * bn * sizeof(int)));
     return DRP_OK;
 }
@@ -419,6 +450,7 @@ int train_stage_batch(drp_ctx* c, const float* states, const float* impulses, co
         memcpy(pin + lay.targets, tp.lk.targets, (size_t)B * H * tp.lk.M * 3 * sizeof(float));
         memcpy(pin + lay.tnums, tp.lk.target_nums, (size_t)B * H * sizeof(int));
     }
+    if (tp.lk.transport()) memcpy(pin + lay.eps, tp.lk.eps, (size_t)B * sizeof(double));
     // the unpacking launch IS the upload: it reads the staged batch from the pinned host buffer (device-visible) and leaves
     // the arena copy for the kernels that read the given states; DRP_TRAIN_COPY_UPLOAD=1: a copy on the stream first
     const bool by_kernel = !c->train_copy_upload;
@@ -456,6 +488,8 @@ int train_attempt(drp_ctx* c, int B, int N, const TrainPass& tp, int mode, bool 
     if (want_loss && tp.loss_terms != back) CHK(d2h(c, back, c->tr_loss.p, (size_t)H * B * sizeof(double)));
     if (grad_out && tp.backward) CHK(d2h(c, grad_out, c->tr_grad.p, (size_t)W_TOTAL * sizeof(float)));
     if (tp.lk.match_out && tp.lk.match()) CHK(d2h(c, tp.lk.match_out, c->tr_match.p, (size_t)H * B * N * sizeof(int)));
+    if (tp.lk.col_err_out && tp.lk.transport())
+        CHK(d2h(c, tp.lk.col_err_out, ptr<double>(c->tr_loss) + (size_t)H * B, (size_t)H * B * sizeof(double)));
     if (tp.backward && !direct) CHK(d2h(c, flag_host, flag_dev, sizeof(unsigned)));
     bool repacked = false;
     if (mode == DRP_TRAIN_UPDATE) {
@@ -504,7 +538,7 @@ int train_step_body(drp_ctx* c, const float* states, const float* impulses, bool
         CHK(pick_tape_engine(c, amax, max_abs(particle_dens, (size_t)B), sd_max, &tp.engine));
     }
     tp.backward = mode != DRP_TRAIN_EVAL;
-    tp.lay = tr_layout(B, H, N, lk.kind != TR_LOSS_MSE ? lk.M : 0, actions);
+    tp.lay = tr_layout(B, H, N, lk.kind != TR_LOSS_MSE ? lk.M : 0, actions, lk.transport());
     tp.lk = lk;
     tp.actions = actions;
     CHK(train_ensure_workspace(c, B, N, tp));

@@ -9,13 +9,14 @@
 // the batch as uploaded (drp_train_step): states [B][H+1][N][3] | impulses [B][H][N][3] | attributes [B][H+1][N] | densities [B]
 // | particle counts [B] (ints), every block 16-byte aligned; drp_train_step_untracked (M > 0): behind them the target clouds
 // [B][H][M][3] | their counts [B][H] (ints) -- with M = 0 the layout, and so the one copy, is drp_train_step's;
-// drp_train_step_actions (`actions`): the pushes [B][H][4] where the impulses are, everything behind them moving up
-struct TrArena { size_t states, sdelta, attrs, dens, nums, targets, tnums, bytes; };
+// drp_train_step_actions (`actions`): the pushes [B][H][4] where the impulses are, everything behind them moving up;
+// drp_train_step_transport (`eps`): behind everything the regularisation strengths [B] (doubles)
+struct TrArena { size_t states, sdelta, attrs, dens, nums, targets, tnums, bytes, eps; };
 // the impulse block: what train_stage_batch copies to TrArena::sdelta
 inline size_t tr_impulse_bytes(int B, int H, int N, bool actions) {
     return (actions ? (size_t)B * H * 4 : (size_t)B * H * N * 3) * sizeof(float);
 }
-inline TrArena tr_layout(int B, int H, int N, int M = 0, bool actions = false) {
+inline TrArena tr_layout(int B, int H, int N, int M = 0, bool actions = false, bool eps = false) {
     auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
     TrArena a{};
     a.states = 0;
@@ -28,6 +29,10 @@ inline TrArena tr_layout(int B, int H, int N, int M = 0, bool actions = false) {
         a.targets = a.bytes;
         a.tnums = up(a.targets + (size_t)B * H * M * 3 * sizeof(float));
         a.bytes = up(a.tnums + (size_t)B * H * sizeof(int));
+    }
+    if (eps) {
+        a.eps = a.bytes;
+        a.bytes = up(a.eps + (size_t)B * sizeof(double));
     }
     return a;
 }
@@ -91,6 +96,19 @@ inline CloudLayout cm_layout(int B, int N, int M) {
     const size_t bn = (size_t)B * N, bm = (size_t)B * M;
     return cloud_layout(B, N, M, {(size_t)B * sizeof(double), bn * 3 * sizeof(float), bn * sizeof(int32_t), bm * sizeof(int32_t),
                                   (bn + bm) * sizeof(double)});
+}
+// drp_cloud_transport: terms [B] (doubles) | gradient [B][N][3] | duals [B][N + M] | col_err [B] (doubles) | eps [B] (doubles): the
+// last block goes UP behind cloud_begin's copy and is never read back
+inline CloudLayout transport_layout(int B, int N, int M) {
+    const size_t bn = (size_t)B * N, bm = (size_t)B * M;
+    return cloud_layout(B, N, M, {(size_t)B * sizeof(double), bn * 3 * sizeof(float), (bn + bm) * sizeof(double),
+                                  (size_t)B * sizeof(double), (size_t)B * sizeof(double)});
+}
+// the first of the B regularisation strengths that is zero, negative, infinite or no number, or -1
+inline int first_bad_eps(const double* eps, int B) {
+    for (int b = 0; b < B; ++b)
+        if (!(eps[b] > 0.0) || !std::isfinite(eps[b])) return b;
+    return -1;
 }
 // the first of the real rows' coordinates of a padded cloud batch [B][N][3] that is infinite or no number, as b * N + row, or -1
 // (the padding is never read as points: rubbish there is allowed)

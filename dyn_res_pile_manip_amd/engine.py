@@ -894,6 +894,54 @@ class Engine(object):
             out['u'], out['v'] = dual[:, :N].copy(), dual[:, N:].copy()
         return out
 
+    def cloud_transport(self, p, q, n_p=None, n_q=None, eps=None, iters=None, want_grad=False, want_dual=False, want_col_err=False):
+        """Entropy-regularised optimal-transport distance of p [B, N, 3] (n_p [B] real rows, default all; mass 1 / n_p each) and
+        q [B, M, 3] (n_q; mass 1 / n_q each) after `iters` log-domain Sinkhorn sweeps with eps (a number or [B], in
+        squared-distance units; both are required) -> {'transport' [B] float64 = sum_ij P_ij |p_i - q_j|^2 / 3[, 'grad' [B, N, 3] =
+        d transport / d p with the plan P held fixed: non-zero on every real row whatever the counts][, 'f' [B, N], 'g' [B, M]: the
+        duals, float64, 0 on padding][, 'col_err' [B]: sum_j |sum_i P_ij - 1 / n_q|, what the sweeps left of the column
+        marginals]} (include/drp.h: drp_cloud_transport).  A single cloud pair may be given as [N, 3], [M, 3].  At most 1024
+        points per cloud.  A one-shot: it needs no weights and ends no session."""
+        if eps is None or iters is None:
+            raise ValueError('cloud_transport needs eps (squared-distance units) and iters')
+        p, q, n_p, n_q, B, N, M = self._cloud_pair(p, q, n_p, n_q)
+        eps = np.ascontiguousarray(np.broadcast_to(np.asarray(eps, np.float64).reshape(-1), (B,)))
+        terms = np.empty((B,), np.float64)
+        grad = np.empty((B, N, 3), np.float32) if want_grad else None
+        dual = np.empty((B, N + M), np.float64) if want_dual else None
+        col_err = np.empty((B,), np.float64) if want_col_err else None
+        self._ck(self.lib.drp_cloud_transport(self.h, _fp(p), _ip(n_p), _fp(q), _ip(n_q), B, N, M, _dp(eps), int(iters), _dp(terms),
+                                              _opt(_fp, grad), _opt(_dp, dual), _opt(_dp, col_err)))
+        out = {'transport': terms}
+        if want_grad:
+            out['grad'] = grad
+        if want_dual:
+            out['f'], out['g'] = dual[:, :N].copy(), dual[:, N:].copy()
+        if want_col_err:
+            out['col_err'] = col_err
+        return out
+
+    def train_step_transport(self, states, attrs, particle_nums, particle_dens, targets, target_nums, eps, iters, states_delta=None,
+                             actions=None, mode='update', want_grad=False, want_col_err=False):
+        """train_step_loss with each step's term the transport distance of cloud_transport between the predicted state and its
+        target cloud (include/drp.h: drp_train_step_transport): eps [B] (or a number) per sample, iters sweeps; states_delta
+        [B, n_rollout, N, 3] or actions [B, n_rollout, 4] -- exactly one of the two -> (loss, gradient blob or None[, col_err
+        [n_rollout, B]: every problem's column-marginal violation])."""
+        if (states_delta is None) == (actions is None):
+            raise ValueError('exactly one of states_delta and actions must be given')
+        assert targets is not None and target_nums is not None
+        by_actions = actions is not None
+        keep, (B, N, H, M), (ps, pi, pa, pn, pd, pt, ptn) = self._train_batch(
+            states, _f32(actions) if by_actions else states_delta, attrs, particle_nums, particle_dens, targets, target_nums, by_actions, True)
+        eps = np.ascontiguousarray(np.broadcast_to(np.asarray(eps, np.float64).reshape(-1), (B,)))
+        out = ctypes.c_double()
+        grad = np.empty((L.DRP_N_WEIGHTS,), np.float32) if (want_grad and mode != 'eval') else None
+        col_err = np.empty((H, B), np.float64) if want_col_err else None
+        self._ck(self.lib.drp_train_step_transport(self.h, ps, None if by_actions else pi, pi if by_actions else None, pa, pn, pd, B, N,
+                                                   pt, ptn, M, _dp(eps), int(iters), L.TRAIN_MODES[mode], ctypes.byref(out),
+                                                   _opt(_fp, grad), _opt(_dp, col_err)))
+        return (out.value, grad, col_err) if want_col_err else (out.value, grad)
+
     def cloud_chamfer_f64(self, p, q, n_p=None, n_q=None, want_grad=False, want_nn=False):
         """cloud_chamfer in float64 on the device (include/drp.h: drp_cloud_chamfer_f64): the same dict with 'grad' as float64,
         plus 'margin' [B, 2] -- per sample the smallest (second-best - best) squared distance over its arg-mins, p -> q then

@@ -98,20 +98,41 @@ LOSSES = ('mse', 'chamfer')
 # the one-to-one matching loss of Engine.cloud_match and its mix with the Chamfer distance (Engine.train_step_loss): they train as
 # 'chamfer' does, on collate_untracked's batches, but have no float64 yardstick yet, so the probe options refuse them
 MATCH_LOSSES = ('match', 'chamfer+match')
-UNTRACKED_LOSSES = ('chamfer',) + MATCH_LOSSES
+# the entropy-regularised transport loss of Engine.cloud_transport (Engine.train_step_transport): fractional masses, so clouds of
+# unequal counts share mass and every real row has a gradient.  It trains as the matching losses do and, like them, has no
+# float64 yardstick: the probe options refuse it with their message
+TRANSPORT_LOSSES = ('transport',)
+UNTRACKED_LOSSES = ('chamfer',) + MATCH_LOSSES + TRANSPORT_LOSSES
 IMPULSES = ('data', 'actions')
 DATA = ('particles', 'depth')
+# eps_b = transport_eps_scale / particle_dens[b]: 1 / den is the squared fps_rad sampling radius, so scale 1 blurs the plan over
+# one particle spacing -- a definition, not a tuned value
+TRANSPORT_EPS_SCALE = 1.0
+# the smallest of {10, 20, 50, 100, 200} at which the host reference's col_err is at most 1 % of the total mass on every case of
+# tests/_untracked_ref.chamfer_cases() at scale 1 (DESIGN.md 9 has the table)
+TRANSPORT_ITERS = 50
+from ._lib import TRANSPORT_MAX_ITERS  # noqa: E402  (include/drp.h: DRP_TRANSPORT_MAX_ITERS)
 
 
-def check_loss(loss, match_weight=0.5):
-    if loss not in LOSSES + MATCH_LOSSES:
-        raise ValueError('loss must be one of %s or %s, got %r' % (LOSSES, MATCH_LOSSES, loss))
+def check_loss(loss, match_weight=0.5, transport_eps_scale=TRANSPORT_EPS_SCALE, transport_iters=TRANSPORT_ITERS):
+    if loss not in LOSSES + MATCH_LOSSES + TRANSPORT_LOSSES:
+        raise ValueError('loss must be one of %s or %s or %s, got %r' % (LOSSES, MATCH_LOSSES, TRANSPORT_LOSSES, loss))
     if loss == 'chamfer+match' and not 0.0 < float(match_weight) < 1.0:
         raise ValueError('match_weight must lie in (0, 1), got %r' % (match_weight,))
+    if loss in TRANSPORT_LOSSES:
+        if not 0.0 < float(transport_eps_scale) < float('inf'):
+            raise ValueError('transport_eps_scale must be a positive finite number, got %r' % (transport_eps_scale,))
+        if int(transport_iters) != transport_iters or not 1 <= int(transport_iters) <= TRANSPORT_MAX_ITERS:
+            raise ValueError('transport_iters must be an integer in 1..%d, got %r' % (TRANSPORT_MAX_ITERS, transport_iters))
+
+
+def transport_eps(particle_dens, transport_eps_scale=TRANSPORT_EPS_SCALE):
+    """every sample's regularisation strength, float64 [B]: transport_eps_scale / particle_dens[b]"""
+    return float(transport_eps_scale) / np.asarray(particle_dens, np.float64).reshape(-1)
 
 
 def refuse_match_probe(loss):
-    if loss in MATCH_LOSSES:
+    if loss in MATCH_LOSSES + TRANSPORT_LOSSES:
         raise ValueError('there is no float64 yardstick for the matching loss yet: loss=%r cannot be probed '
                          '(probe_every, grad_probe_every, probe_batch)' % (loss,))
 
@@ -149,7 +170,8 @@ def batch_actions(data):
     return _np(actions)
 
 
-def run_batch(model, optimizer, data, phase='train', n_rollout=None, loss='mse', impulses='data', match_weight=0.5):
+def run_batch(model, optimizer, data, phase='train', n_rollout=None, loss='mse', impulses='data', match_weight=0.5,
+              transport_eps_scale=TRANSPORT_EPS_SCALE, transport_iters=TRANSPORT_ITERS):
     """The loop body at train/train_gnn_dyn.py:159-210 -> loss (python float, what loss.item() is there).  loss='chamfer': `data`
     is collate_untracked's (targets and target_nums behind the six fields) and each step's term is the Chamfer distance to its
     target cloud (Engine.train_step_untracked).  A batch marked depth_only (DepthDataset) is refused (ValueError) unless
@@ -157,8 +179,10 @@ def run_batch(model, optimizer, data, phase='train', n_rollout=None, loss='mse',
     (`data.actions`) on the state the step reads instead of taken from states_delta (Engine.train_step_actions; the engine's
     camera must be set).  loss='match' / 'chamfer+match' (MATCH_LOSSES): collate_untracked's batches as for 'chamfer', each step's
     term the one-to-one matching distance to its target cloud, or (1 - match_weight) Chamfer + match_weight matching, with either
-    impulse source (Engine.train_step_loss)."""
-    check_loss(loss, match_weight)
+    impulse source (Engine.train_step_loss).  loss='transport' (TRANSPORT_LOSSES): the same batches and impulse sources, each
+    step's term the entropy-regularised transport distance to its target cloud after transport_iters sweeps with
+    eps_b = transport_eps_scale / particle_dens[b] (Engine.train_step_transport)."""
+    check_loss(loss, match_weight, transport_eps_scale, transport_iters)
     if impulses not in IMPULSES:
         raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
     check_depth_only(data, loss, impulses)
@@ -176,6 +200,13 @@ def run_batch(model, optimizer, data, phase='train', n_rollout=None, loss='mse',
         value, _ = model.engine.train_step_loss(states, _np(attrs), _np(particle_nums, np.int32), _np(particle_dens), _np(data[6]),
                                                 _np(data[7], np.int32), states_delta=None if actions is not None else _np(states_delta),
                                                 actions=actions, loss=loss, match_weight=match_weight, mode=mode)
+        return value
+    if loss in TRANSPORT_LOSSES:
+        dens = _np(particle_dens)
+        value, _ = model.engine.train_step_transport(states, _np(attrs), _np(particle_nums, np.int32), dens, _np(data[6]),
+                                                     _np(data[7], np.int32), transport_eps(dens, transport_eps_scale),
+                                                     int(transport_iters), states_delta=None if actions is not None else _np(states_delta),
+                                                     actions=actions, mode=mode)
         return value
     if impulses == 'actions':
         chamfer = loss == 'chamfer'
@@ -238,7 +269,8 @@ def check_probe_options(loss, grad_probe_every, probe_every):
 
 
 def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=None, first_epoch=0, grad_probe_every=0,
-          loss='mse', impulses='data', probe_every=0, match_weight=0.5):
+          loss='mse', impulses='data', probe_every=0, match_weight=0.5, transport_eps_scale=TRANSPORT_EPS_SCALE,
+          transport_iters=TRANSPORT_ITERS):
     """train/train_gnn_dyn.py:134-246 without the file I/O: `dataloaders` = {'train': iterable of
     collated batches, 'valid': ...}.  Returns {'best_valid_loss', 'history': [(epoch, phase, rmse)]}.
     ckp(epoch, i, model): called after training batch i when i % ckp_per_iter == 0 (:217-218); first_epoch: the epoch
@@ -251,9 +283,10 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
     impulses='actions': the batches
     carry `.actions` and the model is trained through the push (run_batch); with real untracked data this is what makes
     n_rollout > 1 meaningful.  The engine's camera must be set (main does it).  loss in MATCH_LOSSES: run_batch's matching loss
-    with match_weight; both probe options are refused with it."""
+    with match_weight; both probe options are refused with it.  loss in TRANSPORT_LOSSES: run_batch's transport loss with
+    transport_eps_scale and transport_iters; the probe options are refused with it too."""
     check_probe_options(loss, grad_probe_every, probe_every)
-    check_loss(loss, match_weight)
+    check_loss(loss, match_weight, transport_eps_scale, transport_iters)
     if impulses not in IMPULSES:
         raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
     loss_kind = loss
@@ -276,7 +309,8 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
                         line = 'grad_probe [%d][%d] worst %s rel %.3e (%s tape), loss diff %.3e' % (epoch, i, pr['worst'], pr['rel'],
                                                                                                   pr['tape'], pr['loss_diff'])
                         log(line + (', min_margin %.3e' % pr['min_margin'] if loss_kind == 'chamfer' else ''))
-                loss = run_batch(model, optimizer, data, phase, n_rollout, loss=loss_kind, impulses=impulses, match_weight=match_weight)
+                loss = run_batch(model, optimizer, data, phase, n_rollout, loss=loss_kind, impulses=impulses, match_weight=match_weight,
+                                 transport_eps_scale=transport_eps_scale, transport_iters=transport_iters)
                 meter.update(loss, _np(data[0]).shape[0])
                 if log is not None and i % tc['log_per_iter'] == 0:
                     log('%s [%d][%d] LR: %.6f, Loss: %.6f (%.6f)' % (phase, epoch, i, optimizer.param_groups[0]['lr'],
@@ -313,7 +347,8 @@ def set_seed(seed):
 
 
 def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8, n_epoch=None, engine=None, grad_probe_every=0,
-         loss=None, impulses=None, probe_every=0, data='particles', target_den_scale=1.0, match_weight=0.5):
+         loss=None, impulses=None, probe_every=0, data='particles', target_den_scale=1.0, match_weight=0.5,
+         transport_eps_scale=TRANSPORT_EPS_SCALE, transport_iters=TRANSPORT_ITERS):
     """The file-level part of train/train_gnn_dyn.py:train() (:45-130, :196-228): seed, the log directory with config.yaml
     and log.txt, the 'train' / 'valid' ParticleDatasets and their DeviceLoaders, a fresh model (torch.nn.Linear's default
     initialisation) or the resumed checkpoint, net_epoch_%d_iter_%d.pth every ckp_per_iter training batches and
@@ -327,7 +362,8 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
     DepthDatasets (every frame of a window sampled from its depth image on the device, the later frames at target_den_scale
     times the state's density), which implies loss='chamfer' and impulses='actions'; a contradicting value is refused.  loss /
     impulses None: 'mse' / 'data', or what data implies.  loss in MATCH_LOSSES (with match_weight for the mix): as 'chamfer', on
-    particles or depth.  chunk None: the dataset's default (64 samples; 16 for data='depth')."""
+    particles or depth; loss in TRANSPORT_LOSSES (with transport_eps_scale and transport_iters) likewise.  chunk None: the
+    dataset's default (64 samples; 16 for data='depth')."""
     import time
     import yaml
     from . import synthetic, weights
@@ -335,7 +371,7 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
     from .gnn_dyn import PropNetDiffDenModel
     loss, impulses = resolve_data_options(data, loss, impulses)
     check_probe_options(loss, grad_probe_every, probe_every)
-    check_loss(loss, match_weight)
+    check_loss(loss, match_weight, transport_eps_scale, transport_iters)
     tc = config['train']
     resume = tc['particle'].get('resume', {'active': False, 'epoch': 0, 'iter': 0})
     if cam is None:
@@ -384,7 +420,7 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
         result = train(config, model, loaders, n_epoch=n_epoch, log=log, on_best=on_best, ckp=ckp,
                        first_epoch=resume['epoch'] if resume['active'] and resume['epoch'] > 0 else 0,
                        grad_probe_every=grad_probe_every, loss=loss, impulses=impulses, probe_every=probe_every,
-                       match_weight=match_weight)
+                       match_weight=match_weight, transport_eps_scale=transport_eps_scale, transport_iters=transport_iters)
         for epoch, phase, rmse in result['history']:
             if phase == 'grad_probe':                   # logged when it was taken
                 continue
@@ -415,16 +451,21 @@ def _cli(argv=None):
                          'image on the device.  Implies --loss chamfer --impulses actions')
     ap.add_argument('--target-den-scale', type=float, default=1.0,
                     help='--data depth: the target frames are sampled at this multiple of the state\'s particle density')
-    ap.add_argument('--loss', choices=LOSSES + MATCH_LOSSES, default=None,
+    ap.add_argument('--loss', choices=LOSSES + MATCH_LOSSES + TRANSPORT_LOSSES, default=None,
                     help='(default mse) chamfer: drop the recorded correspondence and train on the Chamfer distance to the untracked '
-                         'clouds; match: on the one-to-one matching distance to them; chamfer+match: on their mix (--match-weight)')
+                         'clouds; match: on the one-to-one matching distance to them; chamfer+match: on their mix (--match-weight); '
+                         'transport: on the entropy-regularised transport distance to them (--transport-eps-scale, --transport-iters)')
     ap.add_argument('--match-weight', type=float, default=0.5,
                     help='--loss chamfer+match: (1 - w) Chamfer + w matching, w in (0, 1)')
+    ap.add_argument('--transport-eps-scale', type=float, default=TRANSPORT_EPS_SCALE,
+                    help='--loss transport: eps = scale / particle density per sample (1: the plan blurs over one particle spacing)')
+    ap.add_argument('--transport-iters', type=int, default=TRANSPORT_ITERS,
+                    help='--loss transport: Sinkhorn sweeps per problem, 1..%d' % TRANSPORT_MAX_ITERS)
     ap.add_argument('--impulses', choices=IMPULSES, default=None,
                     help='(default data) actions: compute every step\'s impulse from the recorded push on the state the model predicted')
     a = ap.parse_args(argv)
     try:
-        check_loss(resolve_data_options(a.data, a.loss, a.impulses)[0], a.match_weight)
+        check_loss(resolve_data_options(a.data, a.loss, a.impulses)[0], a.match_weight, a.transport_eps_scale, a.transport_iters)
     except ValueError as e:
         ap.error(str(e))
     config = default_config()
@@ -437,7 +478,8 @@ def _cli(argv=None):
         config['dataset']['n_timestep'] = a.n_timestep
     result, d = main(config, a.data_root, a.train_dir, chunk=a.chunk, threads=a.threads, n_epoch=a.epochs,
                      grad_probe_every=a.grad_probe_every, loss=a.loss, impulses=a.impulses, probe_every=a.probe_every,
-                     data=a.data, target_den_scale=a.target_den_scale, match_weight=a.match_weight)
+                     data=a.data, target_den_scale=a.target_den_scale, match_weight=a.match_weight,
+                     transport_eps_scale=a.transport_eps_scale, transport_iters=a.transport_iters)
     print('best valid loss %.6f, checkpoints in %s' % (np.sqrt(result['best_valid_loss']), d))
 
 

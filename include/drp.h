@@ -567,7 +567,7 @@ int drp_ptcl_dataset_time(drp_ctx* ctx, float* ms_out);
 /* HIP-event timing of one kernel class on the context's stream.  name: "graph",
  * "node_encode", "edge_encode", "project", "aggregate", "update", "predict", "reward",
  * "mppi", "prop" (the fused propagation-step kernel of DRP_ENGINE_FUSED / _LITE), "loss" (the stand-alone metrics' kernel:
- * drp_cloud_chamfer, drp_cloud_match).  drp_probe_read returns total ms and launches since drp_probe_begin. */
+ * drp_cloud_chamfer, drp_cloud_match, drp_cloud_transport).  drp_probe_read returns total ms and launches since drp_probe_begin. */
 int drp_probe_begin(drp_ctx* ctx, const char* kernel_class);
 int drp_probe_read(drp_ctx* ctx, double* total_ms, long* launches);
 /* What the propagation kernels (km_prop, km_prop3, km_rollout) EXECUTED since drp_probe_begin(ctx, "prop+work") -- the "prop"
@@ -795,6 +795,55 @@ int drp_train_step_loss(drp_ctx* ctx, const float* states, const float* states_d
                         const float* attrs, const int32_t* particle_nums, const float* particle_dens, int B, int N,
                         const float* targets /*[B][H][M][3]*/, const int32_t* target_nums /*[B][H]*/, int M, int loss_kind,
                         double match_weight, int mode, double* loss_out, float* grad_out, int32_t* match_out /*[H][B][N], nullable*/);
+
+/* ---- entropy-regularised optimal-transport distance of two padded cloud batches and its gradient: transport with
+ * fractional masses, where clouds of unequal counts share mass instead of leaving rows unmatched.  The inputs are a prediction p
+ * with n_p real rows and a target q with n_q real rows; padding is as for drp_cloud_chamfer.
+ *   Cost.        C[i][j] is the fp32 squared distance exactly as kc_chamfer forms it: fp32 differences, dx*dx + dy*dy + dz*dz,
+ *                no fma.  It is widened to double exactly.  Everything after it is double.
+ *   Masses.      a_i = 1/n_p, b_j = 1/n_q.
+ *   Parameters.  eps = eps[b] > 0 is in squared-distance units, per sample.  K = iters satisfies 1 <= K <= KT_MAX_ITERS
+ *                (DRP_TRANSPORT_MAX_ITERS).
+ *   Sweeps.      f = 0.  For k = 1 .. K, first g_j = -eps LSE_i((f_i - C_ij)/eps + log a_i), then
+ *                f_i = -eps LSE_j((g_j - C_ij)/eps + log b_j).  LSE is max-shifted.  Its terms are added in a fixed order that
+ *                DESIGN.md 9 states (ascending index within each of the lanes that share a sum, then an xor butterfly over
+ *                those lanes).  The last update is f's, so the plan P_ij = a_i b_j exp((f_i + g_j - C_ij)/eps) has row sums a_i
+ *                to rounding.  Every predicted particle's whole mass is placed.
+ *   Term.        transport = sum_ij P_ij C_ij / 3.  This is the same /3 as match.  With equal counts and eps -> 0 it tends to
+ *                the match term.
+ *   Gradient.    d/dp_i = scale sum_j P_ij 2 (p_i - q_j) / 3.  P is a constant of the derivative, as sigma is for match.  The
+ *                differences are the fp32 ones.  The sum is in double and is rounded once to fp32.  The gradient is +0.0 exactly
+ *                on padding.
+ *   col_err.     col_err = sum_j |sum_i P_ij - b_j| is the column-marginal violation that K sweeps leave.  It is the caller's
+ *                certificate that K was enough.  It is an output, not a stopping rule.
+ *   Fixed work.  The loops are counted by K, n_p and n_q alone.  No value prolongs them.
+ *   Non-finite input.  The stand-alone call refuses a non-finite real row on the host.  In the trainer a non-finite prediction
+ *                ends in a NaN loss after the same number of steps.
+ *   Determinism. No atomics.  The bits are the same from run to run.  They are the same for a sample alone or inside any batch.
+ *                They do not depend on the padded N and M, only on the counts.
+ * dual_out [B][N + M]: f then g, 0 on padding.  N and M are at most 1024 (the work is K n_p n_q exponentials).  Contract as
+ * drp_cloud_match: a one-shot that needs no weights, ends no session, is no dispatch variant and leaves drp_last_dispatch and the
+ * trainer alone; it counts under the "loss" kernel class of drp_probe_begin.
+ * DRP_EINVAL (the context stays usable): a null argument (every output but terms_out is nullable), a count outside 1..N or 1..M, N
+ * or M outside 1..1024, eps[b] not finite or <= 0, iters outside 1..DRP_TRANSPORT_MAX_ITERS, a real row that is not finite. */
+#define DRP_TRANSPORT_MAX_ITERS 1000
+int drp_cloud_transport(drp_ctx* ctx, const float* p, const int32_t* n_p, const float* q, const int32_t* n_q,
+                        int B, int N, int M, const double* eps /*[B]*/, int iters, double* terms_out /*[B]*/,
+                        float* grad_p_out /*[B][N][3], nullable*/, double* dual_out /*[B][N+M]: f then g, nullable*/,
+                        double* col_err_out /*[B], nullable*/);
+
+/* drp_train_step_loss's body with the transport term of drp_cloud_transport between s_pred_t[b, :n_b] and
+ * targets[b, t, :target_nums[b, t]] as each step's loss, / (n_rollout B); eps [B] (per sample, every step of it) and iters as
+ * there.  states_delta or actions: exactly one of the two.  The transport kernel is launched where the Chamfer kernel is and
+ * writes the same state gradient, loss terms and zero-fill; everything behind the loss gradient is drp_train_step's; it is no
+ * dispatch variant.  col_err_out [H][B] (nullable): every problem's col_err.  A call of its own because drp_train_step_loss has no
+ * room for eps and iters: that call's accepted kinds stay 1..3.  Refusals (the context stays as it was): those of
+ * drp_train_step_loss; N or M above 1024; a null eps, eps[b] not finite or <= 0; iters outside 1..DRP_TRANSPORT_MAX_ITERS. */
+int drp_train_step_transport(drp_ctx* ctx, const float* states, const float* states_delta /*or NULL*/, const float* actions /*or NULL*/,
+                             const float* attrs, const int32_t* particle_nums, const float* particle_dens, int B, int N,
+                             const float* targets /*[B][H][M][3]*/, const int32_t* target_nums /*[B][H]*/, int M,
+                             const double* eps /*[B]*/, int iters, int mode, double* loss_out, float* grad_out,
+                             double* col_err_out /*[H][B], nullable*/);
 
 #ifdef __cplusplus
 }

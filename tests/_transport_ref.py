@@ -1,0 +1,161 @@
+"""TEST INFRASTRUCTURE of the entropy-regularised transport loss (drp_cloud_transport, drp_train_step_transport;
+csrc/k_transport.h): include/drp.h's definition in numpy float64, operation for operation.
+
+  sinkhorn64(C, eps, K)            the K sweeps on a cost matrix -> (f, g): f = 0, then K times g's update and f's, each a
+                                   max-shifted log-sum-exp whose terms are added in ascending index
+  plan64(C, f, g, eps)             P_ij = a_i b_j exp((f_i + g_j - C_ij) / eps)
+  transport64(p, q, n_p, n_q, eps, K)   term, gradient, duals and col_err of a padded batch, on cost32 of tests/_match_ref.py
+
+The device adds the same terms in another fixed order; every other operation is the same IEEE double operation
+in the same order, and exp and log are each library's own."""
+import numpy as np
+
+from _match_ref import cost32
+
+# the options' defaults as the issue defines them (dyn_res_pile_manip_amd.train_gnn_dyn holds the same values)
+EPS_SCALE = 1.0
+ITERS_CANDIDATES = (10, 20, 50, 100, 200)
+COL_ERR_MAX = 0.01              # of the total mass 1
+
+
+def _lse_rows(X):
+    """max-shifted log-sum-exp along axis 0, the terms added in ascending index -> [columns]"""
+    m = X.max(axis=0)
+    s = np.zeros(X.shape[1])
+    for i in range(X.shape[0]):
+        s += np.exp(X[i] - m)
+    return m + np.log(s)
+
+
+def sinkhorn64(C, eps, K):
+    C = np.asarray(C, np.float64)
+    n, m = C.shape
+    log_a, log_b = np.log(1.0 / n), np.log(1.0 / m)
+    f, g = np.zeros(n), np.zeros(m)
+    for _ in range(int(K)):
+        g = -eps * _lse_rows((f[:, None] - C) / eps + log_a)
+        f = -eps * _lse_rows((g[:, None] - C.T) / eps + log_b)
+    return f, g
+
+
+def plan64(C, f, g, eps):
+    C = np.asarray(C, np.float64)
+    n, m = C.shape
+    return ((1.0 / n) * (1.0 / m)) * np.exp((f[:, None] + g[None, :] - C) / eps)
+
+
+def col_err64(P):
+    return float(np.abs(P.sum(axis=0) - 1.0 / P.shape[1]).sum())
+
+
+def pair64(p, q, eps, K, scale=1.0, p64=None):
+    """one pair of real rows -> (term, grad [n, 3] float64 before the fp32 rounding, f, g, col_err, P).  p64: the point the term is
+    differentiated at where it is not the float32 p (central differences): the cost and the differences are then float64"""
+    if p64 is None:
+        C = cost32(p, q).astype(np.float64)
+        d = (np.asarray(p, np.float32)[:, None, :] - np.asarray(q, np.float32)[None, :, :]).astype(np.float64)
+    else:
+        d = np.asarray(p64, np.float64)[:, None, :] - np.asarray(q, np.float64)[None, :, :]
+        C = d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2]
+    f, g = sinkhorn64(C, eps, K)
+    P = plan64(C, f, g, eps)
+    term = scale * ((P * C).sum() / 3.0)
+    grad = (2.0 * scale / 3.0) * (P[:, :, None] * d).sum(axis=1)
+    return term, grad, f, g, col_err64(P), P
+
+
+def transport64(p, q, n_p, n_q, eps, K, scale=1.0):
+    """p [B, N, 3], q [B, M, 3] float32 with n_p, n_q real rows, eps a number or [B] -> {'transport' [B], 'grad' [B, N, 3] float64
+    (+0.0 on padding), 'f' [B, N], 'g' [B, M] (0 on padding), 'col_err' [B], 'row_err' [B]: max_i |sum_j P_ij - a_i| / a_i}"""
+    p, q = np.asarray(p, np.float32), np.asarray(q, np.float32)
+    B, N, M = p.shape[0], p.shape[1], q.shape[1]
+    eps = np.broadcast_to(np.asarray(eps, np.float64).reshape(-1), (B,))
+    out = {'transport': np.zeros(B), 'grad': np.zeros((B, N, 3)), 'f': np.zeros((B, N)), 'g': np.zeros((B, M)),
+           'col_err': np.zeros(B), 'row_err': np.zeros(B)}
+    for b in range(B):
+        n, m = int(n_p[b]), int(n_q[b])
+        term, grad, f, g, ce, P = pair64(p[b, :n], q[b, :m], float(eps[b]), K, scale)
+        out['transport'][b], out['col_err'][b] = term, ce
+        out['grad'][b, :n], out['f'][b, :n], out['g'][b, :m] = grad, f, g
+        out['row_err'][b] = float(np.abs(P.sum(axis=1) * n - 1.0).max())
+    return out
+
+
+# ---- the trainer ---------------------------------------------------------------------------------------------------------
+def train_transport64(W, states, states_delta, attrs, particle_nums, particle_dens, targets, target_nums, plans, actions=None,
+                      adj_thresh=0.08):
+    """tests/_match_ref.py's train_match64 loop (actions [B, H, 4] given: tests/_train_actions_ref.py's impulses in place of
+    states_delta) with the term of (step t, sample b) replaced by sum_ij P_ij |p_i - q_j|^2 / (3 n_rollout B), P = plans[t][b]
+    [n_b, m_bt] a constant of the derivative as in the kernel -> (loss, terms [H, B], {key: gradient}, d loss / d predicted
+    states [B, H, N, 3])"""
+    import torch
+    from oracle.propnet_dense import adjacency
+    from _f64_grad_ref import _d, step, weights64
+    from _f64_train_ref import PARAMS
+    W = dict((k, v.clone().requires_grad_(True)) for k, v in weights64(W).items())
+    st, at, dens = _d(states), _d(attrs), _d(particle_dens)
+    if actions is None:
+        sd_all = _d(states_delta)
+    else:
+        import _train_actions_ref as A
+        ac = _d(actions)
+    tg = _d(targets)
+    nums = [int(n) for n in np.asarray(particle_nums)]
+    tnums = np.asarray(target_nums)
+    B, T1, N, _ = st.shape
+    H = T1 - 1
+    s_cur, a_cur = st[:, 0], at[:, 0]
+    terms, preds = [], []
+    for t in range(H):
+        sd = sd_all[:, t] if actions is None else A.impulses64(s_cur, ac[:, t], nums)
+        adj, _ = adjacency(s_cur.detach().float(), sd.detach().float(), adj_thresh)
+        s_pred = step(W, a_cur, s_cur, sd, dens, adj.double())
+        s_pred.retain_grad()
+        preds.append(s_pred)
+        row = []
+        for b in range(B):
+            n, m = nums[b], int(tnums[b, t])
+            d = s_pred[b, :n, None, :] - tg[b, t, None, :m, :]
+            row.append((torch.from_numpy(np.asarray(plans[t][b], np.float64)) * (d ** 2).sum(-1)).sum() / 3.0 / (H * B))
+        terms.append(torch.stack(row))
+        s_cur = s_pred
+    terms = torch.stack(terms)
+    loss = terms.sum()
+    loss.backward()
+    grads = dict((k, W[k].grad.numpy().copy()) for k in PARAMS)
+    g_state = np.stack([p.grad.numpy() if p.grad is not None else np.zeros((B, N, 3)) for p in preds], 1)
+    return float(loss.item()), terms.detach().numpy(), grads, g_state
+
+
+TRAIN_NUMS, TRAIN_H, TRAIN_M = (9, 6), 2, 12
+TRAIN_TARGET_NUMS = ((12, 7), (5, 10))      # per sample and step: above and below the sample's own count
+TRAIN_SEED = 90
+
+
+def train_batch():
+    """B = 2, H = 2, N = 9 (counts 9 and 6), M = 12 with ragged target counts on both sides of the predictions' -> (states, states_delta,
+    actions, attrs, particle_nums, particle_dens, targets, target_nums): tests/_train_actions_ref.py's synthetic piles and pushes,
+    the recorded impulses those pushes cause on the recorded states, and targets re-sampled from the recorded next states (rows
+    drawn with replacement, moved by _untracked_ref.JITTER)"""
+    import _train_actions_ref as A
+    import _untracked_ref as U
+    states, actions, attrs, nums, dens = A.synthetic_batch(list(TRAIN_NUMS), TRAIN_H, TRAIN_SEED)
+    B, N = len(TRAIN_NUMS), max(TRAIN_NUMS)
+    sdelta = np.zeros((B, TRAIN_H, N, 3), np.float32)
+    targets = np.zeros((B, TRAIN_H, TRAIN_M, 3), np.float32)
+    tnums = np.asarray(TRAIN_TARGET_NUMS, np.int32)
+    rng = np.random.default_rng(TRAIN_SEED)
+    for b, n in enumerate(TRAIN_NUMS):
+        for t in range(TRAIN_H):
+            sdelta[b, t, :n] = A._sd32(states[b, t, :n], actions[b, t])
+            m = int(tnums[b, t])
+            rows = states[b, t + 1, :n][rng.integers(0, n, m)]
+            targets[b, t, :m] = (rows + U.JITTER * rng.standard_normal((m, 3))).astype(np.float32)
+    return states, sdelta, actions, attrs, nums, dens, targets, tnums
+
+
+def case_eps(n_p, n_q, scale=EPS_SCALE):
+    """the regularisation of a tests/_untracked_ref.chamfer_case sample: its clouds fill a cube of side 0.02 max(n_p, n_q)^(1/3),
+    so their density is that of the denser cloud, 1 / 0.02^2 per unit area of a layer: eps = scale x 0.02^2, the squared spacing
+    -- what transport_eps_scale / particle_dens is for a pile sampled at fps_rad's radius"""
+    return np.full((len(np.atleast_1d(n_p)),), scale * 0.02 ** 2)

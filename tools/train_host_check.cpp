@@ -11,7 +11,8 @@
 // without target clouds) is staged the same way, and so is the one buffer of the three one-shots on two clouds (cloud_layout with
 // cm_layout's, chamfer_layout's and chamfer64_layout's blocks: the inputs staged, every output block written in full; the two
 // Chamfer layouts held to offset chains written out by hand here, an independent restatement), with the check
-// that refuses a real row that is no number.  No device is touched.
+// that refuses a real row that is no number.  The transport loss: transport_layout's blocks staged like the matching's, the
+// eps block behind a training batch (tr_layout with `eps`), and the check of the regularisation strengths.  No device is touched.
 //
 //   train_host_check layout64 B H N M actions     prints tr64_layout's eight fields (4-byte words) and exits
 #include <cstdio>
@@ -175,6 +176,29 @@ static void stage_match(int B, int N, int M) {
     const size_t len[] = {(size_t)B * 8, bn * 12, bn * 4, bm * 4, (bn + bm) * 8};
     stage_cloud(cm_layout(B, N, M), B, N, M, 5, len);
 }
+// drp_cloud_transport: four output blocks and eps [B] as a fifth, which the entry point copies up behind the inputs
+static void stage_transport(int B, int N, int M) {
+    const size_t bn = (size_t)B * N, bm = (size_t)B * M;
+    const size_t len[] = {(size_t)B * 8, bn * 12, (bn + bm) * 8, (size_t)B * 8, (size_t)B * 8};
+    stage_cloud(transport_layout(B, N, M), B, N, M, 5, len);
+}
+// drp_train_step_transport's batch: eps [B] (doubles) behind everything else, the other blocks where they were
+static void stage_eps(int B, int H, int N, int M, bool actions) {
+    const TrArena lay = tr_layout(B, H, N, M, actions, true), plain = tr_layout(B, H, N, M, actions);
+    EXPECT(lay.states == plain.states && lay.sdelta == plain.sdelta && lay.attrs == plain.attrs && lay.dens == plain.dens &&
+           lay.nums == plain.nums && lay.targets == plain.targets && lay.tnums == plain.tnums);
+    EXPECT(lay.eps == plain.bytes && lay.eps % 16 == 0);
+    EXPECT(lay.eps + (size_t)B * 8 <= lay.bytes && lay.bytes - (lay.eps + (size_t)B * 8) < 16 && lay.bytes % 16 == 0);
+    std::vector<double> eps(B, 0.5);
+    char* pin = static_cast<char*>(std::malloc(lay.bytes));
+    std::memset(pin, 0xff, lay.bytes);
+    std::memcpy(pin + lay.eps, eps.data(), (size_t)B * sizeof(double));
+    double last;
+    std::memcpy(&last, pin + lay.eps + (size_t)(B - 1) * 8, 8);
+    EXPECT(last == 0.5);
+    std::free(pin);
+}
+
 // drp_cloud_chamfer's and drp_cloud_chamfer_f64's layouts against their offset chains written out block by block (the yardstick
 // of cloud_layout: the offsets a call's kernel and copies have always used), then staged like the matching's
 static void stage_chamfer(int B, int N, int M) {
@@ -219,7 +243,29 @@ int main(int argc, char** argv) {
         }
     stage64(1, 1, 4096, 4096, false);                            // the largest clouds of one (sample, step)
     const int mshapes[][3] = {{1, 1, 1}, {1, 5, 3}, {3, 7, 9}, {2, 65, 64}, {1, 1024, 1024}, {5, 1024, 1}, {4, 300, 257}};
-    for (const auto& s : mshapes) stage_match(s[0], s[1], s[2]);
+    for (const auto& s : mshapes) {
+        stage_match(s[0], s[1], s[2]);
+        stage_transport(s[0], s[1], s[2]);
+    }
+    for (const auto& s : shapes)
+        for (int actions = 0; actions < 2; ++actions)
+            if (s[3] > 0) stage_eps(s[0], s[1], s[2], s[3], actions != 0);
+    {
+        // the regularisation strengths: every one read, none beyond the B-th
+        const double inf64 = std::numeric_limits<double>::infinity(), nan64 = std::numeric_limits<double>::quiet_NaN();
+        double* eps = static_cast<double*>(std::malloc(3 * sizeof(double)));                 // exactly [B]
+        eps[0] = 4e-4; eps[1] = 1e-300; eps[2] = 7.0;
+        EXPECT(first_bad_eps(eps, 3) == -1);
+        eps[2] = 0.0;
+        EXPECT(first_bad_eps(eps, 3) == 2 && first_bad_eps(eps, 2) == -1);
+        eps[2] = -4e-4;
+        EXPECT(first_bad_eps(eps, 3) == 2);
+        eps[2] = inf64;
+        EXPECT(first_bad_eps(eps, 3) == 2);
+        eps[2] = 1.0; eps[0] = nan64;
+        EXPECT(first_bad_eps(eps, 3) == 0);
+        std::free(eps);
+    }
     const int cshapes[][3] = {{1, 1, 1}, {2, 5, 3}, {3, 70, 130}, {1, 4096, 4096}};
     for (const auto& s : cshapes) stage_chamfer(s[0], s[1], s[2]);
     {
