@@ -342,5 +342,6 @@ struct drp_ctx {
     unsigned long long* work_ptr() const { return (marks.probe_cls == KC_PROP && probe_count) ? static_cast<unsigned long long*>(probe_work.p) : nullptr; }
     std::vector<Event> probe_ev;
     size_t probe_used = 0;
+    long probe_prop_kernels = 0;    // kernel launches inside the regions of the "prop" probe (drp_probe_prop_launches)
 };
 

@@ -33,6 +33,7 @@ int drp_probe_begin(drp_ctx* c, const char* kernel_class) {
     if (!c) return DRP_EINVAL;
     c->marks.probe_cls = -1;
     c->probe_used = 0;
+    c->probe_prop_kernels = 0;
     c->probe_count = false;
     c->work_lite = c->work_full = false;
     if (!kernel_class || !*kernel_class) return DRP_OK;
@@ -74,6 +75,12 @@ int drp_probe_work(drp_ctx* c, unsigned long long out[8]) {
         out[6] += sh[(size_t)q * PROP_WORK_STRIDE + PROP_WORK_CLK_CYCLES];
         out[7] += sh[(size_t)q * PROP_WORK_STRIDE + PROP_WORK_CLK_TICKS];
     }
+    return DRP_OK;
+}
+
+int drp_probe_prop_launches(drp_ctx* c, long* kernels) {
+    if (!c || !kernels) return fail(c, DRP_EINVAL, "null argument");
+    *kernels = c->marks.probe_cls == KC_PROP ? c->probe_prop_kernels : 0;
     return DRP_OK;
 }
 

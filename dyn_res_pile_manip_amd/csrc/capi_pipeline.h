@@ -183,6 +183,7 @@ struct ProbeScope {
         }
         (void)hipEventRecord(c->probe_ev[c->probe_used++].ev, c->stream);
     }
+    void launched() { if (on) ++c->probe_prop_kernels; }      // a kernel of the "prop" class inside this region
 };
 
 int ensure_step_ws(drp_ctx* c, StepWs& ws, int B, int N, int engine = -1) {
@@ -456,6 +457,7 @@ int run_step_mfma(drp_ctx* c, const StepArgs& a, const StepPlan& k) {
                                    tape ? a.mask_hist + ro * DRP_K * 2 : (unsigned*)nullptr,
                                    (tape && a.agg_hist) ? a.agg_hist + ro * 64 : (float*)nullptr, c->re_scale, c->re_inv,
                                    (c->pol.prop3_order ? 1 : 0), ptr<float4>(c->ws.ecache), b.ec_stride, wk, tape ? (size_t)B * N : (size_t)0);
+                ps.launched();
             }
         }
         for (int p = 0; p < DRP_PSTEP && !k.prop3; ++p) {
@@ -469,6 +471,7 @@ int run_step_mfma(drp_ctx* c, const StepArgs& a, const StepPlan& k) {
                                tape ? a.mask_hist + (size_t)p * B * N * DRP_K * 2 : (unsigned*)nullptr,
                                (tape && a.agg_hist) ? a.agg_hist + (size_t)p * bn64 : (float*)nullptr,
                                c->re_scale, c->re_inv, k.spread, wk);
+            ps.launched();
             float* tmp = pa; pa = pb; pb = tmp;
         }
         return DRP_OK;
@@ -704,6 +707,7 @@ int run_rollout(drp_ctx* c, int nb, int N, int B, int H, bool reward_all, bool r
             const Block b = k.blocks.block(q);
             hipLaunchKernelGGL(prop_tables().of(k.flags(b)), dim3((unsigned)b.grid), dim3(64 * PROP_WAVES), KM_ROLLOUT_LDS,
                                c->stream, ptr<RolloutArgs>(c->roll_args) + q);
+            ps.launched();
         }
         HIPCHK(c, hipGetLastError());
         note_degrees(c, ptr<uint8_t>(c->ws.nbr_cnt), k.spw, N, B);           // the last step's lists

@@ -225,11 +225,13 @@ struct DispatchPolicy {
     // + 3 %, but 1 024 x 150 - 12 % and x 200 - 5 %: one sample of 129 ... 224 particles leaves three to one of a workgroup's
     // eight waves without a tile.  So: up to ecache_max_n = 128 particles (two samples of up to 128 fill the eight tiles), and
     // ecache_full_n = 225 ... 256 (one sample, eight tiles).  The TAPE's launches (gradient-descent planner, trainer) write one
-    // history buffer over the whole batch and are not split: their cache covers the whole batch, which pays up to
-    // ecache_tape_max_n = 40 particles at the planner's 1 500 rows (50 particles: 0.398 ms per iteration recomputing, 0.42 cached).
+    // history buffer over the whole batch and are cut into the same blocks (the kernel takes the buffer's slot stride: hist_rows;
+    // tests/test_gpu_tape_blocks.py); the cache pays up to ecache_tape_max_n = 40 particles at the planner's 1 500 rows, one launch
+    // (50 particles: 0.398 ms per iteration recomputing, 0.42 cached).
     int ecache_max_mb = 192;
-    int ecache_hard_max_mb = 4096;  // a cached launch that cannot be split (the tape's: 1 500 x 40 rows are 150 MB) and would need more recomputes:
-                                    // 1.6 million rows -- no caller of the reference comes near; the one place where the batch decides the kernel
+    int ecache_hard_max_mb = 4096;  // DRP_ECACHE_HARD_MAX_MB: a cached batch whose first launch would need more (batch columns no block is a multiple
+                                    // of: 1.6 million rows in one launch) recomputes instead, in one launch -- no caller of the reference comes
+                                    // near; the one place where the batch decides the kernel
     int ecache_max_n = 128, ecache_full_n = 225, ecache_tape_max_n = 40;
     int graph_q4 = 1;               // DRP_GRAPH_Q4=0 / 1 / 2: four threads per receiver in the plain neighbour sweep -- never / for a handful
                                     // of samples (fewer workgroups than half the CUs) / whenever the plain sweep is chosen
@@ -282,6 +284,8 @@ inline const EnvSwitch* env_switches(int* count) {
         DRP_SW_B("DRP_NO_GRAPH_REV", OFF_IF_SET, graph_rev, "the reversed lists always in a launch of their own"),
         DRP_SW_B("DRP_REV_GLOBAL", ON_IF_SET, rev_global_only, "reversed lists built in global memory"),
         DRP_SW_I("DRP_ECACHE_MAX_MB", ecache_max_mb, 0, INT_MAX, nullptr, "0: the edge-chain cache is never used"),
+        DRP_SW_I("DRP_ECACHE_HARD_MAX_MB", ecache_hard_max_mb, 0, INT_MAX, nullptr,
+                 "a cached batch whose first launch needs a cache buffer above this many MB recomputes instead, in one launch"),
         DRP_SW_I("DRP_ECACHE_MAX_N", ecache_max_n, 0, INT_MAX, ecache_max_n_also, "cached up to this many particles; also: no 225 ... 256 range (ecache_full_n = 257)"),
         DRP_SW_I("DRP_ECACHE_TAPE_MAX_N", ecache_tape_max_n, 0, INT_MAX, nullptr, "the tape's launches cached up to this many particles"),
     };

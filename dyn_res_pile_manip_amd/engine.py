@@ -1348,6 +1348,13 @@ class Engine(object):
         self._ck(self.lib.drp_probe_read(self.h, ctypes.byref(ms), ctypes.byref(n)))
         return ms.value, n.value
 
+    def probe_prop_launches(self):
+        """Kernel launches inside the regions of the 'prop' probe since probe_begin: probe_read counts regions, and a region
+        covers one launch per block of a batch that is cut (include/drp.h: drp_probe_prop_launches)."""
+        n = ctypes.c_long()
+        self._ck(self.lib.drp_probe_prop_launches(self.h, ctypes.byref(n)))
+        return n.value
+
     def probe_work(self):
         """What the propagation kernels executed since probe_begin('prop'), counted by the kernels (include/drp.h)."""
         out = (ctypes.c_ulonglong * 8)()

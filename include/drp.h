@@ -570,6 +570,10 @@ int drp_ptcl_dataset_time(drp_ctx* ctx, float* ms_out);
  * drp_cloud_chamfer, drp_cloud_match, drp_cloud_transport).  drp_probe_read returns total ms and launches since drp_probe_begin. */
 int drp_probe_begin(drp_ctx* ctx, const char* kernel_class);
 int drp_probe_read(drp_ctx* ctx, double* total_ms, long* launches);
+/* Kernel launches inside the timed regions of the "prop" / "prop+work" probe since drp_probe_begin.  drp_probe_read's `launches`
+ * counts regions, and a region of the whole-sample kernels covers one launch per block of samples (csrc/dispatch.h: cut_blocks):
+ * a batch that is cut into blocks shows here.  Reading does not reset the count; 0 while another class is probed. */
+int drp_probe_prop_launches(drp_ctx* ctx, long* kernels);
 /* What the propagation kernels (km_prop, km_prop3, km_rollout) EXECUTED since drp_probe_begin(ctx, "prop+work") -- the "prop"
  * probe with the kernels' own counters switched on (two atomic adds per tile: they cost the 300-particle launch 8 %, so a
  * timed region runs under the plain "prop" probe and the counters over an iteration of their own): out[0] slot iterations that ran the relation

@@ -4,6 +4,9 @@
 //                                     the plans give, policy from the environment
 //   dispatch_dump pair spw N B [sum rows n]      paired tiles?  (no statistic given: unknown)
 //   dispatch_dump cache n_cu          N B nb step-cached rollout-cached, for N = 1 ... 300 and a set of batches
+//   dispatch_dump blocks n_cu B N nb H tape    how km_prop3's launches of every rollout step t < H of a gd / rollout call are cut
+//                                     (plan_step; tape: 0 / 1): per step a line "step t prop3 cache n chunk cache_bytes" and a line
+//                                     "block q b_off Bc spw grid pair cache ec_stride cache_bytes" per launch
 //   dispatch_dump policy              every policy field, from the environment
 //   dispatch_dump env                 the names of the environment table
 //   dispatch_dump wgrad b0 t0 b1 t1 ...       the deferred weight gradients' lists (plan_wgrad_lists) for jobs of b_q blocks adding
@@ -90,6 +93,20 @@ int main(int argc, char** argv) {
                     const RolloutPlan r = plan_rollout(p, n_cu, ENGINE_FUSED, B, N, nb, false, DegStat{});
                     printf("%d %d %d %d %d\n", N, B, nb, k.prop3 ? (k.blocks.cache ? 1 : 0) : -1, r.one_launch ? (r.blocks.cache ? 1 : 0) : -1);
                 }
+    } else if (mode == "blocks" && argc == 8) {
+        const int n_cu = atoi(argv[2]), B = atoi(argv[3]), N = atoi(argv[4]), nb = atoi(argv[5]), H = atoi(argv[6]);
+        const bool tape = atoi(argv[7]) != 0;
+        for (int t = 0; t < H; ++t) {
+            StepShape s;
+            s.B = B; s.N = N; s.tape = tape; s.has_actions = true; s.wants_rev = tape && H == 1;
+            s.prev_mod = t == 0 ? nb : B; s.attr_mod = nb; s.dens_mod = nb;
+            const StepPlan k = plan_step(p, n_cu, s);
+            printf("step %d %d %d %d %ld %zu\n", t, k.prop3 ? 1 : 0, k.blocks.cache ? 1 : 0, k.blocks.n, k.blocks.chunk, k.blocks.cache_bytes);
+            for (int q = 0; k.prop3 && q < k.blocks.n; ++q) {
+                const Block b = k.blocks.block(q);
+                printf("block %d %ld %d %d %d %d %d %zu %zu\n", q, b.b_off, b.Bc, b.spw, b.grid, b.pair ? 1 : 0, b.cache, b.ec_stride, b.cache_bytes);
+            }
+        }
     } else if (mode == "policy") {
 #define FIELD(NAME) printf(#NAME "=%g\n", (double)p.NAME)
         FIELD(agg_global_only); FIELD(rev_global_only); FIELD(self_const); FIELD(prop3); FIELD(prop3_min_b); FIELD(prop3_min_tiles);

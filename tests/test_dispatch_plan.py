@@ -1,7 +1,8 @@
 """CPU: csrc/dispatch.h is pure host code.  tests/dispatch_dump.cpp is compiled against it with the host compiler alone
 (-Wall -Werror, no HIP header in reach) and asked what the library would launch: the same names as the built library reported on
 a GPU (tests/dispatch_table.txt), the pairing rule on both sides of its threshold, the sharding contract of the edge-chain cache
-(DESIGN.md 9), the environment table field by field, and DESIGN_NOTES.md 9c's list of switches."""
+(DESIGN.md 9), the tape's launches cut into blocks and the cache-size fallback, the environment table field by field, and
+DESIGN_NOTES.md 9c's list of switches."""
 import os
 import re
 import shutil
@@ -34,7 +35,7 @@ EFFECTS = {
     'DRP_NO_GRAPH_ENCODE': ('1', dict(graph_encode=0)), 'DRP_TRAIN_FUSED': ('1', dict(train_fused=1)),
     'DRP_NO_GRAPH_REV': ('1', dict(graph_rev=0)), 'DRP_REV_GLOBAL': ('1', dict(rev_global_only=1)),
     'DRP_ECACHE_MAX_MB': ('-3', dict(ecache_max_mb=0)), 'DRP_ECACHE_MAX_N': ('64', dict(ecache_max_n=64, ecache_full_n=257)),
-    'DRP_ECACHE_TAPE_MAX_N': ('50', dict(ecache_tape_max_n=50)),
+    'DRP_ECACHE_TAPE_MAX_N': ('50', dict(ecache_tape_max_n=50)), 'DRP_ECACHE_HARD_MAX_MB': ('-2', dict(ecache_hard_max_mb=0)),
 }
 
 
@@ -100,6 +101,58 @@ def test_the_cache_decision_is_a_function_of_the_pile_size_alone(dump):
     for N in range(1, 301):
         kinds = set().union(*(seen.get((N, k), set()) for k in ('step', 'rollout')))
         assert kinds == {1 if (N <= 128 or 225 <= N <= 256) else 0}, N
+
+
+def blocks_of(dump, B, N, nb, H, tape=1, env=None):
+    """the 'blocks' mode, parsed: per rollout step (prop3, cache, n, chunk, cache_bytes, [block dicts])"""
+    steps = []
+    for line in dump('blocks', 256, B, N, nb, H, tape, env=env):
+        f = line.split()
+        if f[0] == 'step':
+            steps.append(dict(prop3=int(f[2]), cache=int(f[3]), n=int(f[4]), chunk=int(f[5]), cache_bytes=int(f[6]), blocks=[]))
+        else:
+            names = ('q', 'b_off', 'Bc', 'spw', 'grid', 'pair', 'cache', 'ec_stride', 'cache_bytes')
+            steps[-1]['blocks'].append(dict(zip(names, map(int, f[1:]))))
+    assert len(steps) == H and all(len(s['blocks']) == s['n'] for s in steps)
+    return steps
+
+
+def test_the_tape_is_cut_into_blocks_and_falls_back_by_the_cache_size(dump):
+    """The tape's launches (gradient-descent planner, trainer) at 256 CUs: 40 particles are 7 samples = 280 rows per workgroup,
+    1792 samples per launch (1770 in whole multiples of 30 batch columns).  Both rollout steps of a call are cut alike: the first
+    reads the start state by batch column, the others a state per sample."""
+    tile_bytes = 10 * 512 * 16                                      # K x EC_UNITS float4 per unpaired tile of 32 receivers
+    for nb, chunk, grid0, tail in ((1, 1792, 256, 8), (30, 1770, 253, 30)):
+        steps = blocks_of(dump, 1800, 40, nb, 2)
+        assert steps[0] == steps[1]
+        s = steps[0]
+        assert (s['prop3'], s['cache'], s['n'], s['chunk']) == (1, 1, 2, chunk) and chunk % nb == 0
+        first, second = s['blocks']
+        assert first == dict(q=0, b_off=0, Bc=chunk, spw=7, grid=grid0, pair=0, cache=1, ec_stride=9 * 10 * 512,
+                             cache_bytes=grid0 * 9 * tile_bytes)
+        # the tail: a sample per workgroup, 40 rows as three paired tiles of 16 (5 x 512 float4 each), rows kept in registers
+        assert second == dict(q=1, b_off=chunk, Bc=tail, spw=1, grid=tail, pair=1, cache=2, ec_stride=3 * 5 * 512,
+                              cache_bytes=tail * 3 * 5 * 512 * 16)
+        assert s['cache_bytes'] == first['cache_bytes'] >= second['cache_bytes']          # the buffer is the first block's
+    # two equal blocks; one launch at exactly a block; 41 particles are never cached on the tape
+    s = blocks_of(dump, 3584, 40, 1, 2)[1]
+    assert s['n'] == 2 and s['blocks'][1] == dict(s['blocks'][0], q=1, b_off=1792)
+    s = blocks_of(dump, 1792, 40, 1, 2)[0]
+    assert (s['cache'], s['n'], s['chunk'], s['blocks'][0]['Bc'], s['blocks'][0]['cache']) == (1, 1, 1792, 1792, 1)
+    for B in (8, 1800, 8192):
+        s = blocks_of(dump, B, 41, 1, 1)[0]
+        assert (s['prop3'], s['cache'], s['n'], s['chunk'], s['cache_bytes']) == (1, 0, 1, B, 0) and s['blocks'][0]['cache'] == 0
+    # the fallback: the first launch's 178 MB are above 1 MB, the whole batch recomputes in one launch
+    for nb in (1, 30):
+        for s in blocks_of(dump, 1800, 40, nb, 2, env={'DRP_ECACHE_HARD_MAX_MB': '1'}):
+            assert (s['prop3'], s['cache'], s['n'], s['chunk'], s['cache_bytes']) == (1, 0, 1, 1800, 0)
+            assert s['blocks'] == [dict(q=0, b_off=0, Bc=1800, spw=8, grid=225, pair=0, cache=0, ec_stride=s['blocks'][0]['ec_stride'],
+                                        cache_bytes=0)]
+    # ... and a limit the first launch fits under changes nothing
+    assert blocks_of(dump, 1800, 40, 30, 2, env={'DRP_ECACHE_HARD_MAX_MB': '178'}) == blocks_of(dump, 1800, 40, 30, 2)
+    assert blocks_of(dump, 1800, 40, 30, 2, env={'DRP_ECACHE_HARD_MAX_MB': '177'})[0]['cache'] == 0
+    # the forward launches of the same shape are cut the same way (held on a GPU by test_edge_cache_against_the_oracle)
+    assert [b['Bc'] for b in blocks_of(dump, 1800, 40, 30, 1, tape=0)[0]['blocks']] == [1770, 30]
 
 
 def test_the_environment_table_field_by_field(dump):

@@ -181,6 +181,10 @@ def main():
     # the trainer's node stages: one launch up to n_cu / 4 tiles of 32 rows
     for nums in ([256] * (n_cu // 32), [256] * (n_cu // 32 + 1)):
         r.train('fused', nums, 1)
+    # the tape in more than one km_prop3 launch: 40 particles are cached on the tape, seven samples to a workgroup and launch --
+    # one block of whole multiples of the 30 batch columns and a tail of one multiple; a block and seven samples for the trainer
+    r.gd('fused', n_cu * 7 // 30 * 30 + 30, 40, 30, 2)
+    r.train('fused', [40] * (n_cu * 7 + 7), 1)
     sys.stdout.write('\n'.join(r.lines) + '\n')
 
 
