@@ -218,6 +218,12 @@ SIGNATURES = {
     'drp_train_step_transport': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, c_int32_p, c_float_p,
                                                 ctypes.c_int, ctypes.c_int, c_float_p, c_int32_p, ctypes.c_int, c_double_p,
                                                 ctypes.c_int, ctypes.c_int, c_double_p, c_float_p, c_double_p]),
+    'drp_cloud_divergence': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_int32_p, c_float_p, c_int32_p, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, c_float_p, c_double_p, c_double_p,
+                                            c_double_p]),
+    'drp_train_step_divergence': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, c_int32_p, c_float_p,
+                                                 ctypes.c_int, ctypes.c_int, c_float_p, c_int32_p, ctypes.c_int, c_double_p,
+                                                 ctypes.c_int, ctypes.c_int, c_double_p, c_float_p, c_double_p, c_double_p]),
 }
 
 _lib = None

@@ -1,0 +1,49 @@
+// capi_divergence.h -- a section of the C ABI's translation unit (textually included by drp_capi.hip, which has the order of the sections).
+// Here: the stand-alone Sinkhorn divergence of two padded cloud batches (k_divergence.h), and the trainer's entry point for it
+// (capi_train.h: train_step_body with the TR_LOSS_DIVERGENCE kind, check_transport_params).
+
+// A one-shot on two clouds (capi_pipeline.h: cloud_check, cloud_begin, cloud_finish; train_host.h: divergence_layout)
+int drp_cloud_divergence(drp_ctx* c, const float* p, const int32_t* n_p, const float* q, const int32_t* n_q, int B, int N, int M,
+                         const double* eps, int iters, double* terms_out, float* grad_p_out, double* dual_out, double* col_err_out,
+                         double* self_err_out) {
+    CHK(cloud_check(c, p, n_p, q, n_q, B, N, M, terms_out, KT_MAX_POINTS, KT_MAX_POINTS, " for a divergence"));
+    CHK(check_transport_params(c, eps, B, iters));
+    // as drp_cloud_transport: the kernels end after the same number of steps whatever they read
+    long bad = first_nonfinite_row(p, n_p, B, N);
+    if (bad >= 0) return fail(c, DRP_EINVAL, "p[%ld][%ld] is not finite", bad / N, bad % N);
+    bad = first_nonfinite_row(q, n_q, B, M);
+    if (bad >= 0) return fail(c, DRP_EINVAL, "q[%ld][%ld] is not finite", bad / M, bad % M);
+    void* const outs[] = {terms_out, grad_p_out, dual_out, col_err_out, self_err_out};
+    const DivLayout lay = divergence_layout(B, N, M);
+    CloudCall k;
+    CHK(cloud_begin(c, k, lay.cloud, outs, p, n_p, q, n_q, B, N, M));
+    double* const eps_dev = reinterpret_cast<double*>(k.io + lay.eps);
+    HIPCHK(c, hipMemcpyAsync(eps_dev, eps, (size_t)B * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    KdArgs a{};
+    a.cp = k.cp; a.pred = k.p_dev; a.eps = eps_dev; a.iters = iters; a.scale = 1.0;
+    a.vals = reinterpret_cast<double*>(k.io + lay.vals);
+    a.grad = k.out<float>(1);
+    a.gsum = a.grad != nullptr ? reinterpret_cast<double*>(k.io + lay.gsum) : nullptr;
+    a.terms = k.out<double>(0); a.dual = k.out<double>(2); a.col_err = k.out<double>(3); a.self_err = k.out<double>(4);
+    {
+        ProbeScope ps(c, KC_LOSS);
+        hipLaunchKernelGGL(kd_sweeps, dim3(B, 1, 3), dim3(KT_THREADS), 0, c->stream, a);
+        hipLaunchKernelGGL((kd_combine<false>), dim3(B, 1), dim3(KD_COMBINE_THREADS), 0, c->stream, a);
+    }
+    return cloud_finish(c, k, "kd_sweeps");
+}
+
+// drp_train_step_transport's body with the divergence as each step's term: one more certificate
+int drp_train_step_divergence(drp_ctx* c, const float* states, const float* states_delta, const float* actions, const float* attrs,
+                              const int32_t* particle_nums, const float* particle_dens, int B, int N, const float* targets,
+                              const int32_t* target_nums, int M, const double* eps, int iters, int mode, double* loss_out,
+                              float* grad_out, double* col_err_out, double* self_err_out) {
+    if (!c) return DRP_EINVAL;
+    if ((states_delta != nullptr) == (actions != nullptr))
+        return fail(c, DRP_EINVAL, "exactly one of states_delta and actions must be given");
+    TrLoss lk = TrLoss::against(TR_LOSS_DIVERGENCE, targets, target_nums, M);
+    lk.eps = eps; lk.iters = iters; lk.col_err_out = col_err_out; lk.self_err_out = self_err_out;
+    const bool by_actions = actions != nullptr;
+    return train_step_body(c, states, by_actions ? actions : states_delta, by_actions, attrs, particle_nums, particle_dens, B, N, lk,
+                           mode, loss_out, grad_out);
+}

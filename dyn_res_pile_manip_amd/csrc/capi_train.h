@@ -13,9 +13,10 @@ const int* tr_nums(const drp_ctx* c, const TrArena& lay) {
 // untracked target clouds (k_chamfer.h), the one-to-one matching loss against them (k_match.h), or the two mixed; the targets as
 // the HOST gave them (the entry point stages them behind the batch).  The kinds beyond the MSE are include/drp.h's DRP_LOSS_*.
 // The float64 yardstick (capi_grad_f64.h) reads the same description; it has the MSE and the Chamfer loss.
-// TR_LOSS_TRANSPORT (k_transport.h) is internal: drp_train_step_transport's, no loss_kind of drp_train_step_loss
+// TR_LOSS_TRANSPORT (k_transport.h) is internal: drp_train_step_transport's, no loss_kind of drp_train_step_loss; so is
+// TR_LOSS_DIVERGENCE (k_divergence.h), drp_train_step_divergence's
 enum { TR_LOSS_MSE = 0, TR_LOSS_CHAMFER = DRP_LOSS_CHAMFER, TR_LOSS_MATCH = DRP_LOSS_MATCH, TR_LOSS_CHAMFER_MATCH = DRP_LOSS_CHAMFER_MATCH,
-       TR_LOSS_TRANSPORT = 4 };
+       TR_LOSS_TRANSPORT = 4, TR_LOSS_DIVERGENCE = 5 };
 static_assert(KT_MAX_ITERS == DRP_TRANSPORT_MAX_ITERS, "include/drp.h states the kernel's cap");
 struct TrLoss {
     int kind = TR_LOSS_MSE;
@@ -25,10 +26,13 @@ struct TrLoss {
     double match_weight = 0.0;              // TR_LOSS_CHAMFER_MATCH: (1 - w) Chamfer + w matching
     int32_t* match_out = nullptr;           // the caller's [H][B][N], nullable: every predicted row's partner (kinds with a matching)
     double* margin_out = nullptr;           // float64 only: the caller's [H][B], nullable (kc64_chamfer's arg-min margins)
-    const double* eps = nullptr;            // TR_LOSS_TRANSPORT: the caller's [B], the regularisation of every step of a sample
-    int iters = 0;                          // TR_LOSS_TRANSPORT: the sweeps
-    double* col_err_out = nullptr;          // TR_LOSS_TRANSPORT: the caller's [H][B], nullable
+    const double* eps = nullptr;            // TR_LOSS_TRANSPORT, _DIVERGENCE: the caller's [B], the regularisation of every step of a sample
+    int iters = 0;                          // TR_LOSS_TRANSPORT, _DIVERGENCE: the sweeps
+    double* col_err_out = nullptr;          // TR_LOSS_TRANSPORT, _DIVERGENCE: the caller's [H][B], nullable
+    double* self_err_out = nullptr;         // TR_LOSS_DIVERGENCE: the caller's [H][B][2], nullable
     bool transport() const { return kind == TR_LOSS_TRANSPORT; }
+    bool divergence() const { return kind == TR_LOSS_DIVERGENCE; }
+    bool sinkhorn() const { return transport() || divergence(); }      // eps and iters, the kernels' caps and col_err
     bool chamfer() const { return kind == TR_LOSS_CHAMFER || kind == TR_LOSS_CHAMFER_MATCH; }
     bool match() const { return kind == TR_LOSS_MATCH || kind == TR_LOSS_CHAMFER_MATCH; }
     static TrLoss against(int kind, const float* targets, const int32_t* target_nums, int M) {
@@ -164,6 +168,23 @@ int train_forward_backward(drp_ctx* c, int B, int N, const TrainPass& tp) {
             a.col_err = lk.col_err_out != nullptr ? ptr<double>(c->tr_loss) + (size_t)H * B : (double*)nullptr;
             a.zero = zero; a.n_zero = n_zero;
             hipLaunchKernelGGL((kt_transport<true>), dim3(B, H), dim3(KT_THREADS), 0, st, a);
+        }
+        if (lk.divergence()) {
+            // the same outputs; the certificates and the two kernels' scratch lie behind the terms (train_host.h:
+            // tr_div_loss_layout); kd_combine does the zero-fill, on the grid the other loss kernels do it on
+            const TrDivLoss dl = tr_div_loss_layout(B, H, N);
+            double* const d = ptr<double>(c->tr_loss);
+            KdArgs a{};
+            a.cp = cp; a.pred = states;
+            a.eps = reinterpret_cast<const double*>(ar + lay.eps); a.iters = lk.iters;
+            a.scale = (double)scale;
+            a.vals = d + dl.vals; a.gsum = d + dl.gsum;
+            a.grad = g_state; a.terms = loss;
+            a.col_err = lk.col_err_out != nullptr ? d + dl.col_err : (double*)nullptr;
+            a.self_err = lk.self_err_out != nullptr ? d + dl.self_err : (double*)nullptr;
+            a.zero = zero; a.n_zero = n_zero;
+            hipLaunchKernelGGL(kd_sweeps, dim3(B, H, 3), dim3(KT_THREADS), 0, st, a);
+            hipLaunchKernelGGL((kd_combine<true>), dim3(B, H), dim3(KD_COMBINE_THREADS), 0, st, a);
         }
     }
     HIPCHK(c, hipGetLastError());
@@ -386,9 +407,10 @@ int train_check_args(drp_ctx* c, const float* states, const float* impulses, boo
             if (lk.kind == TR_LOSS_CHAMFER_MATCH && !(lk.match_weight > 0.0 && lk.match_weight < 1.0))
                 return fail(c, DRP_EINVAL, "match_weight %g outside (0, 1)", lk.match_weight);
         }
-        if (lk.transport()) {
+        if (lk.sinkhorn()) {
             if (N > KT_MAX_POINTS || lk.M > KT_MAX_POINTS)
-                return fail(c, DRP_EINVAL, "the transport loss takes clouds of 1..%d points: N=%d M=%d", KT_MAX_POINTS, N, lk.M);
+                return fail(c, DRP_EINVAL, "the %s takes clouds of 1..%d points: N=%d M=%d",
+                            lk.divergence() ? "Sinkhorn divergence" : "transport loss", KT_MAX_POINTS, N, lk.M);
             CHK(check_transport_params(c, lk.eps, B, lk.iters));
         }
         CHK(check_target_nums(c, lk, B, c->tr_nroll));
@@ -430,7 +452,9 @@ int train_ensure_workspace(drp_ctx* c, int B, int N, TrainPass& tp) {
         for (DevBuf* b : edge64) CHK(ensure(c, *b, kt * bnk * 64 * sizeof(float)));
         CHK(ensure(c, c->ed_x0, kt * bnk * 8 * sizeof(float)));
     }
-    CHK(ensure(c, c->tr_loss, (size_t)H * B * sizeof(double) * (tp.lk.transport() ? 2 : 1)));    // (the transport loss: col_err behind the terms)
+    // (the transport loss: col_err behind the terms; the divergence: its certificates and scratch, tr_div_loss_layout)
+    CHK(ensure(c, c->tr_loss, tp.lk.divergence() ? tr_div_loss_layout(B, H, N).count * sizeof(double)
+                                                 : (size_t)H * B * sizeof(double) * (tp.lk.transport() ? 2 : 1)));
     if (tp.lk.match()) CHK(ensure(c, c->tr_match, (size_t)H * bn * sizeof(int)));
     return DRP_OK;
 }
@@ -450,7 +474,7 @@ int train_stage_batch(drp_ctx* c, const float* states, const float* impulses, co
         memcpy(pin + lay.targets, tp.lk.targets, (size_t)B * H * tp.lk.M * 3 * sizeof(float));
         memcpy(pin + lay.tnums, tp.lk.target_nums, (size_t)B * H * sizeof(int));
     }
-    if (tp.lk.transport()) memcpy(pin + lay.eps, tp.lk.eps, (size_t)B * sizeof(double));
+    if (tp.lk.sinkhorn()) memcpy(pin + lay.eps, tp.lk.eps, (size_t)B * sizeof(double));
     // the unpacking launch IS the upload: it reads the staged batch from the pinned host buffer (device-visible) and leaves
     // the arena copy for the kernels that read the given states; DRP_TRAIN_COPY_UPLOAD=1: a copy on the stream first
     const bool by_kernel = !c->train_copy_upload;
@@ -490,6 +514,11 @@ int train_attempt(drp_ctx* c, int B, int N, const TrainPass& tp, int mode, bool 
     if (tp.lk.match_out && tp.lk.match()) CHK(d2h(c, tp.lk.match_out, c->tr_match.p, (size_t)H * B * N * sizeof(int)));
     if (tp.lk.col_err_out && tp.lk.transport())
         CHK(d2h(c, tp.lk.col_err_out, ptr<double>(c->tr_loss) + (size_t)H * B, (size_t)H * B * sizeof(double)));
+    if (tp.lk.divergence()) {
+        const TrDivLoss dl = tr_div_loss_layout(B, H, N);
+        if (tp.lk.col_err_out) CHK(d2h(c, tp.lk.col_err_out, ptr<double>(c->tr_loss) + dl.col_err, (size_t)H * B * sizeof(double)));
+        if (tp.lk.self_err_out) CHK(d2h(c, tp.lk.self_err_out, ptr<double>(c->tr_loss) + dl.self_err, (size_t)H * B * 2 * sizeof(double)));
+    }
     if (tp.backward && !direct) CHK(d2h(c, flag_host, flag_dev, sizeof(unsigned)));
     bool repacked = false;
     if (mode == DRP_TRAIN_UPDATE) {
@@ -538,7 +567,7 @@ int train_step_body(drp_ctx* c, const float* states, const float* impulses, bool
         CHK(pick_tape_engine(c, amax, max_abs(particle_dens, (size_t)B), sd_max, &tp.engine));
     }
     tp.backward = mode != DRP_TRAIN_EVAL;
-    tp.lay = tr_layout(B, H, N, lk.kind != TR_LOSS_MSE ? lk.M : 0, actions, lk.transport());
+    tp.lay = tr_layout(B, H, N, lk.kind != TR_LOSS_MSE ? lk.M : 0, actions, lk.sinkhorn());
     tp.lk = lk;
     tp.actions = actions;
     CHK(train_ensure_workspace(c, B, N, tp));

@@ -52,6 +52,7 @@
 #include "k_chamfer_f64.h"
 #include "k_match.h"
 #include "k_transport.h"
+#include "k_divergence.h"
 #include "k_prop_inst.h"       // km_prop / km_prop3 / km_rollout: declared here, instantiated in inst_*.hip
 
 #include "dispatch.h"          // host-only: policy, variant flags, plan functions
@@ -70,6 +71,7 @@ extern "C" {
 #include "capi_chamfer.h"
 #include "capi_match.h"
 #include "capi_transport.h"
+#include "capi_divergence.h"
 #include "capi_comm.h"
 #include "capi_rgr.h"
 #include "capi_rgr_train.h"

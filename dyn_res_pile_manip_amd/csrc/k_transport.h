@@ -74,7 +74,9 @@ __device__ __forceinline__ double kt_group_sum(double v, int lp) {
     return v;
 }
 
-// out_dual[j] = -eps LSE_i((in_dual[i] - C_ij) / eps + log_mass) for every j < n_out; the caller's barrier is behind it
+// out_dual[j] = -eps LSE_i((in_dual[i] - C_ij) / eps + log_mass) for every j < n_out; the caller's barrier is behind it.
+// AVERAGE (k_divergence.h's self problems, both clouds the same one): out_dual[j] = (in_dual[j] + that) / 2
+template <bool AVERAGE = false>
 __device__ __forceinline__ void kt_half_sweep(const float4* out_pts, int n_out, const float4* in_pts, int n_in, const double* in_dual,
                                               double* out_dual, double eps, double log_mass) {
     const int lp = kt_parts(n_out, n_in), parts = 1 << lp, items = n_out << lp;
@@ -98,7 +100,10 @@ __device__ __forceinline__ void kt_half_sweep(const float4* out_pts, int n_out, 
             sum += exp(x - m);
         }
         sum = kt_group_sum(sum, lp);
-        if (live && s == 0) out_dual[j] = -eps * (m + log(sum));
+        if (live && s == 0) {
+            const double v = -eps * (m + log(sum));
+            out_dual[j] = AVERAGE ? 0.5 * (in_dual[j] + v) : v;
+        }
     }
 }
 

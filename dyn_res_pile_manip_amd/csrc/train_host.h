@@ -10,7 +10,7 @@
 // | particle counts [B] (ints), every block 16-byte aligned; drp_train_step_untracked (M > 0): behind them the target clouds
 // [B][H][M][3] | their counts [B][H] (ints) -- with M = 0 the layout, and so the one copy, is drp_train_step's;
 // drp_train_step_actions (`actions`): the pushes [B][H][4] where the impulses are, everything behind them moving up;
-// drp_train_step_transport (`eps`): behind everything the regularisation strengths [B] (doubles)
+// drp_train_step_transport, drp_train_step_divergence (`eps`): behind everything the regularisation strengths [B] (doubles)
 struct TrArena { size_t states, sdelta, attrs, dens, nums, targets, tnums, bytes, eps; };
 // the impulse block: what train_stage_batch copies to TrArena::sdelta
 inline size_t tr_impulse_bytes(int B, int H, int N, bool actions) {
@@ -103,6 +103,36 @@ inline CloudLayout transport_layout(int B, int N, int M) {
     const size_t bn = (size_t)B * N, bm = (size_t)B * M;
     return cloud_layout(B, N, M, {(size_t)B * sizeof(double), bn * 3 * sizeof(float), (bn + bm) * sizeof(double),
                                   (size_t)B * sizeof(double), (size_t)B * sizeof(double)});
+}
+// drp_cloud_divergence: terms [B] (doubles) | gradient [B][N][3] | duals [B][2N + 2M] | col_err [B] | self_err [B][2] (doubles) come
+// back; behind them, never read back: eps [B] (doubles, UP behind cloud_begin's copy) | the kernels' scratch: the value sums
+// [3][B] | the gradient sums [2][B][N][3] (doubles)
+struct DivLayout { CloudLayout cloud; size_t eps, vals, gsum; };
+inline DivLayout divergence_layout(int B, int N, int M) {
+    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t bn = (size_t)B * N, bm = (size_t)B * M;
+    DivLayout a{};
+    a.cloud = cloud_layout(B, N, M, {(size_t)B * sizeof(double), bn * 3 * sizeof(float), 2 * (bn + bm) * sizeof(double),
+                                     (size_t)B * sizeof(double), (size_t)B * 2 * sizeof(double)});
+    a.eps = a.cloud.bytes;
+    a.vals = up(a.eps + (size_t)B * sizeof(double));
+    a.gsum = up(a.vals + (size_t)3 * B * sizeof(double));
+    a.cloud.bytes = up(a.gsum + 2 * bn * 3 * sizeof(double));
+    return a;
+}
+// drp_train_step_divergence's device doubles (c->tr_loss), in doubles: terms [H][B] | col_err [H][B] | self_err [H][B][2] | the
+// value sums [3][H][B] | the gradient sums [2][H][B][N][3]
+struct TrDivLoss { size_t terms, col_err, self_err, vals, gsum, count; };
+inline TrDivLoss tr_div_loss_layout(int B, int H, int N) {
+    const size_t hb = (size_t)H * B;
+    TrDivLoss a{};
+    a.terms = 0;
+    a.col_err = a.terms + hb;
+    a.self_err = a.col_err + hb;
+    a.vals = a.self_err + 2 * hb;
+    a.gsum = a.vals + 3 * hb;
+    a.count = a.gsum + 2 * hb * N * 3;
+    return a;
 }
 // the first of the B regularisation strengths that is zero, negative, infinite or no number, or -1
 inline int first_bad_eps(const double* eps, int B) {

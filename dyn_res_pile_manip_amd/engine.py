@@ -942,6 +942,60 @@ class Engine(object):
                                                    _opt(_fp, grad), _opt(_dp, col_err)))
         return (out.value, grad, col_err) if want_col_err else (out.value, grad)
 
+    def cloud_divergence(self, p, q, n_p=None, n_q=None, eps=None, iters=None, want_grad=False, want_dual=False, want_col_err=False,
+                         want_self_err=False):
+        """Sinkhorn divergence of p [B, N, 3] and q [B, M, 3] (arguments as cloud_transport's; eps and iters are required):
+        cloud_transport's loss with its entropic bias taken out, OT(p, q) - OT(p, p) / 2 - OT(q, q) / 2 on the dual values, zero
+        only for equal clouds -> {'divergence' [B] float64 (not clamped: rounding can leave it a hair below zero at p ~ q)[, 'grad'
+        [B, N, 3] = d divergence / d p with the cross plan and p's self plan held fixed: non-zero on every real row whatever the
+        counts, and zero where transport's is not, at p == q][, 'f' [B, N], 'g' [B, M], 'h_p' [B, N], 'h_q' [B, M]: the duals of
+        the cross problem and of the two self problems, float64, 0 on padding][, 'col_err' [B] as cloud_transport's][, 'self_err'
+        [B, 2]: sum_i |sum_j S_ij - mass| of p's and of q's self plan]} (include/drp.h: drp_cloud_divergence).  At most 1024
+        points per cloud.  A one-shot: it needs no weights and ends no session."""
+        if eps is None or iters is None:
+            raise ValueError('cloud_divergence needs eps (squared-distance units) and iters')
+        p, q, n_p, n_q, B, N, M = self._cloud_pair(p, q, n_p, n_q)
+        eps = np.ascontiguousarray(np.broadcast_to(np.asarray(eps, np.float64).reshape(-1), (B,)))
+        terms = np.empty((B,), np.float64)
+        grad = np.empty((B, N, 3), np.float32) if want_grad else None
+        dual = np.empty((B, 2 * (N + M)), np.float64) if want_dual else None
+        col_err = np.empty((B,), np.float64) if want_col_err else None
+        self_err = np.empty((B, 2), np.float64) if want_self_err else None
+        self._ck(self.lib.drp_cloud_divergence(self.h, _fp(p), _ip(n_p), _fp(q), _ip(n_q), B, N, M, _dp(eps), int(iters), _dp(terms),
+                                               _opt(_fp, grad), _opt(_dp, dual), _opt(_dp, col_err), _opt(_dp, self_err)))
+        out = {'divergence': terms}
+        if want_grad:
+            out['grad'] = grad
+        if want_dual:
+            out['f'], out['g'] = dual[:, :N].copy(), dual[:, N:N + M].copy()
+            out['h_p'], out['h_q'] = dual[:, N + M:2 * N + M].copy(), dual[:, 2 * N + M:].copy()
+        if want_col_err:
+            out['col_err'] = col_err
+        if want_self_err:
+            out['self_err'] = self_err
+        return out
+
+    def train_step_divergence(self, states, attrs, particle_nums, particle_dens, targets, target_nums, eps, iters, states_delta=None,
+                              actions=None, mode='update', want_grad=False, want_err=False):
+        """train_step_transport with each step's term the Sinkhorn divergence of cloud_divergence (include/drp.h:
+        drp_train_step_divergence): the same arguments -> (loss, gradient blob or None[, col_err [n_rollout, B], self_err
+        [n_rollout, B, 2]: every problem's certificates])."""
+        if (states_delta is None) == (actions is None):
+            raise ValueError('exactly one of states_delta and actions must be given')
+        assert targets is not None and target_nums is not None
+        by_actions = actions is not None
+        keep, (B, N, H, M), (ps, pi, pa, pn, pd, pt, ptn) = self._train_batch(
+            states, _f32(actions) if by_actions else states_delta, attrs, particle_nums, particle_dens, targets, target_nums, by_actions, True)
+        eps = np.ascontiguousarray(np.broadcast_to(np.asarray(eps, np.float64).reshape(-1), (B,)))
+        out = ctypes.c_double()
+        grad = np.empty((L.DRP_N_WEIGHTS,), np.float32) if (want_grad and mode != 'eval') else None
+        col_err = np.empty((H, B), np.float64) if want_err else None
+        self_err = np.empty((H, B, 2), np.float64) if want_err else None
+        self._ck(self.lib.drp_train_step_divergence(self.h, ps, None if by_actions else pi, pi if by_actions else None, pa, pn, pd, B, N,
+                                                    pt, ptn, M, _dp(eps), int(iters), L.TRAIN_MODES[mode], ctypes.byref(out),
+                                                    _opt(_fp, grad), _opt(_dp, col_err), _opt(_dp, self_err)))
+        return (out.value, grad, col_err, self_err) if want_err else (out.value, grad)
+
     def cloud_chamfer_f64(self, p, q, n_p=None, n_q=None, want_grad=False, want_nn=False):
         """cloud_chamfer in float64 on the device (include/drp.h: drp_cloud_chamfer_f64): the same dict with 'grad' as float64,
         plus 'margin' [B, 2] -- per sample the smallest (second-best - best) squared distance over its arg-mins, p -> q then

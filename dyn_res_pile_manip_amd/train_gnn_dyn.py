@@ -103,6 +103,11 @@ MATCH_LOSSES = ('match', 'chamfer+match')
 # float64 yardstick: the probe options refuse it with their message
 TRANSPORT_LOSSES = ('transport',)
 UNTRACKED_LOSSES = ('chamfer',) + MATCH_LOSSES + TRANSPORT_LOSSES
+# the Sinkhorn divergence of Engine.cloud_divergence (Engine.train_step_divergence): the transport loss with its entropic bias
+# taken out -- its minimum over the prediction is the target cloud, not a shrunken copy of it -- and the loss to use on depth
+# data.  It trains on the batches UNTRACKED_LOSSES train on, takes the transport loss's two options, and like it has no float64
+# yardstick.  A tuple of its own: the four above are pinned by tests as they are
+DIVERGENCE_LOSSES = ('sinkhorn',)
 IMPULSES = ('data', 'actions')
 DATA = ('particles', 'depth')
 # eps_b = transport_eps_scale / particle_dens[b]: 1 / den is the squared fps_rad sampling radius, so scale 1 blurs the plan over
@@ -115,11 +120,11 @@ from ._lib import TRANSPORT_MAX_ITERS  # noqa: E402  (include/drp.h: DRP_TRANSPO
 
 
 def check_loss(loss, match_weight=0.5, transport_eps_scale=TRANSPORT_EPS_SCALE, transport_iters=TRANSPORT_ITERS):
-    if loss not in LOSSES + MATCH_LOSSES + TRANSPORT_LOSSES:
-        raise ValueError('loss must be one of %s or %s or %s, got %r' % (LOSSES, MATCH_LOSSES, TRANSPORT_LOSSES, loss))
+    if loss not in LOSSES + MATCH_LOSSES + TRANSPORT_LOSSES + DIVERGENCE_LOSSES:
+        raise ValueError('loss must be one of %s or %s or %s or %s, got %r' % (LOSSES, MATCH_LOSSES, TRANSPORT_LOSSES, DIVERGENCE_LOSSES, loss))
     if loss == 'chamfer+match' and not 0.0 < float(match_weight) < 1.0:
         raise ValueError('match_weight must lie in (0, 1), got %r' % (match_weight,))
-    if loss in TRANSPORT_LOSSES:
+    if loss in TRANSPORT_LOSSES + DIVERGENCE_LOSSES:
         if not 0.0 < float(transport_eps_scale) < float('inf'):
             raise ValueError('transport_eps_scale must be a positive finite number, got %r' % (transport_eps_scale,))
         if int(transport_iters) != transport_iters or not 1 <= int(transport_iters) <= TRANSPORT_MAX_ITERS:
@@ -132,7 +137,7 @@ def transport_eps(particle_dens, transport_eps_scale=TRANSPORT_EPS_SCALE):
 
 
 def refuse_match_probe(loss):
-    if loss in MATCH_LOSSES + TRANSPORT_LOSSES:
+    if loss in MATCH_LOSSES + TRANSPORT_LOSSES + DIVERGENCE_LOSSES:
         raise ValueError('there is no float64 yardstick for the matching loss yet: loss=%r cannot be probed '
                          '(probe_every, grad_probe_every, probe_batch)' % (loss,))
 
@@ -140,19 +145,20 @@ def refuse_match_probe(loss):
 def check_depth_only(data, loss, impulses):
     """a batch made from depth frames alone has no tracked targets and no recorded impulses: anything but the Chamfer loss through
     the push would train on zeros"""
-    if getattr(data, 'depth_only', False) and not (loss in UNTRACKED_LOSSES and impulses == 'actions'):
+    if getattr(data, 'depth_only', False) and not (loss in UNTRACKED_LOSSES + DIVERGENCE_LOSSES and impulses == 'actions'):
         raise ValueError('a depth-only batch (DepthDataset) holds no tracked states and no impulses: it needs loss=\'chamfer\' (or '
-                         'one of %s) and impulses=\'actions\', got loss=%r, impulses=%r' % (MATCH_LOSSES, loss, impulses))
+                         'one of %s) and impulses=\'actions\', got loss=%r, impulses=%r'
+                         % (MATCH_LOSSES + TRANSPORT_LOSSES + DIVERGENCE_LOSSES, loss, impulses))
 
 
 def resolve_data_options(data, loss, impulses):
     """main()'s / the command line's data, loss and impulses -> (loss, impulses).  None = not given: 'mse' and 'data' for
-    data='particles'; data='depth' implies 'chamfer' and 'actions'; it takes a MATCH_LOSSES member in place of 'chamfer' and
-    refuses anything else."""
+    data='particles'; data='depth' implies 'chamfer' and 'actions'; it takes a member of MATCH_LOSSES, TRANSPORT_LOSSES or
+    DIVERGENCE_LOSSES in place of 'chamfer' and refuses anything else."""
     if data not in DATA:
         raise ValueError('data must be one of %s, got %r' % (DATA, data))
     if data == 'depth':
-        if loss not in (None,) + UNTRACKED_LOSSES:
+        if loss not in (None,) + UNTRACKED_LOSSES + DIVERGENCE_LOSSES:
             raise ValueError('data=\'depth\' trains on untracked clouds: loss=%r contradicts the loss=\'chamfer\' it implies' % (loss,))
         if impulses not in (None, 'actions'):
             raise ValueError('data=\'depth\' has no recorded impulses: impulses=%r contradicts the impulses=\'actions\' it implies'
@@ -181,7 +187,8 @@ def run_batch(model, optimizer, data, phase='train', n_rollout=None, loss='mse',
     term the one-to-one matching distance to its target cloud, or (1 - match_weight) Chamfer + match_weight matching, with either
     impulse source (Engine.train_step_loss).  loss='transport' (TRANSPORT_LOSSES): the same batches and impulse sources, each
     step's term the entropy-regularised transport distance to its target cloud after transport_iters sweeps with
-    eps_b = transport_eps_scale / particle_dens[b] (Engine.train_step_transport)."""
+    eps_b = transport_eps_scale / particle_dens[b] (Engine.train_step_transport).  loss='sinkhorn' (DIVERGENCE_LOSSES): the same
+    again with the Sinkhorn divergence as each step's term, under the same two options (Engine.train_step_divergence)."""
     check_loss(loss, match_weight, transport_eps_scale, transport_iters)
     if impulses not in IMPULSES:
         raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
@@ -201,12 +208,12 @@ def run_batch(model, optimizer, data, phase='train', n_rollout=None, loss='mse',
                                                 _np(data[7], np.int32), states_delta=None if actions is not None else _np(states_delta),
                                                 actions=actions, loss=loss, match_weight=match_weight, mode=mode)
         return value
-    if loss in TRANSPORT_LOSSES:
+    if loss in TRANSPORT_LOSSES + DIVERGENCE_LOSSES:
         dens = _np(particle_dens)
-        value, _ = model.engine.train_step_transport(states, _np(attrs), _np(particle_nums, np.int32), dens, _np(data[6]),
-                                                     _np(data[7], np.int32), transport_eps(dens, transport_eps_scale),
-                                                     int(transport_iters), states_delta=None if actions is not None else _np(states_delta),
-                                                     actions=actions, mode=mode)
+        step = model.engine.train_step_transport if loss in TRANSPORT_LOSSES else model.engine.train_step_divergence
+        value = step(states, _np(attrs), _np(particle_nums, np.int32), dens, _np(data[6]), _np(data[7], np.int32),
+                     transport_eps(dens, transport_eps_scale), int(transport_iters),
+                     states_delta=None if actions is not None else _np(states_delta), actions=actions, mode=mode)[0]
         return value
     if impulses == 'actions':
         chamfer = loss == 'chamfer'
@@ -238,7 +245,8 @@ class AverageMeter(object):
 def probe_batch(model, data, impulses='data', loss='mse'):
     """Engine.train_gradient_probe on a collated batch: the trainer's fp32 gradients against the float64 evaluation of the same
     batch on the device; weights, Adam state and iteration count are untouched.  loss='chamfer': `data` is collate_untracked's
-    and the result also has 'min_margin' (Engine.train_gradient_probe).  A MATCH_LOSSES member is refused: no yardstick yet."""
+    and the result also has 'min_margin' (Engine.train_gradient_probe).  A member of MATCH_LOSSES, TRANSPORT_LOSSES or
+    DIVERGENCE_LOSSES is refused: no yardstick yet."""
     check_loss(loss)
     refuse_match_probe(loss)
     if impulses not in IMPULSES:
@@ -284,7 +292,8 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
     carry `.actions` and the model is trained through the push (run_batch); with real untracked data this is what makes
     n_rollout > 1 meaningful.  The engine's camera must be set (main does it).  loss in MATCH_LOSSES: run_batch's matching loss
     with match_weight; both probe options are refused with it.  loss in TRANSPORT_LOSSES: run_batch's transport loss with
-    transport_eps_scale and transport_iters; the probe options are refused with it too."""
+    transport_eps_scale and transport_iters; the probe options are refused with it too.  loss in DIVERGENCE_LOSSES: the same
+    with run_batch's Sinkhorn divergence."""
     check_probe_options(loss, grad_probe_every, probe_every)
     check_loss(loss, match_weight, transport_eps_scale, transport_iters)
     if impulses not in IMPULSES:
@@ -362,7 +371,7 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
     DepthDatasets (every frame of a window sampled from its depth image on the device, the later frames at target_den_scale
     times the state's density), which implies loss='chamfer' and impulses='actions'; a contradicting value is refused.  loss /
     impulses None: 'mse' / 'data', or what data implies.  loss in MATCH_LOSSES (with match_weight for the mix): as 'chamfer', on
-    particles or depth; loss in TRANSPORT_LOSSES (with transport_eps_scale and transport_iters) likewise.  chunk None: the
+    particles or depth; loss in TRANSPORT_LOSSES or DIVERGENCE_LOSSES (with transport_eps_scale and transport_iters) likewise.  chunk None: the
     dataset's default (64 samples; 16 for data='depth')."""
     import time
     import yaml
@@ -392,7 +401,7 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
         datasets = {ph: ParticleDataset(data_root, config, ph, cam, engine=engine) for ph in ('train', 'valid')}
     loaders = {ph: DeviceLoader(datasets[ph], tc['batch_size'], shuffle=(ph == 'train'), chunk=chunk, threads=threads)
                for ph in ('train', 'valid')}
-    if loss in UNTRACKED_LOSSES and data != 'depth':
+    if loss in UNTRACKED_LOSSES + DIVERGENCE_LOSSES and data != 'depth':
         loaders = {ph: UntrackedLoader(loaders[ph], seed=tc['random_seed'] + k, reseed=(ph == 'valid'))
                    for k, ph in enumerate(('train', 'valid'))}
     model = PropNetDiffDenModel(config, engine=engine)
@@ -451,16 +460,18 @@ def _cli(argv=None):
                          'image on the device.  Implies --loss chamfer --impulses actions')
     ap.add_argument('--target-den-scale', type=float, default=1.0,
                     help='--data depth: the target frames are sampled at this multiple of the state\'s particle density')
-    ap.add_argument('--loss', choices=LOSSES + MATCH_LOSSES + TRANSPORT_LOSSES, default=None,
+    ap.add_argument('--loss', choices=LOSSES + MATCH_LOSSES + TRANSPORT_LOSSES + DIVERGENCE_LOSSES, default=None,
                     help='(default mse) chamfer: drop the recorded correspondence and train on the Chamfer distance to the untracked '
                          'clouds; match: on the one-to-one matching distance to them; chamfer+match: on their mix (--match-weight); '
-                         'transport: on the entropy-regularised transport distance to them (--transport-eps-scale, --transport-iters)')
+                         'transport: on the entropy-regularised transport distance to them (--transport-eps-scale, --transport-iters); '
+                         'sinkhorn: on the Sinkhorn divergence to them, the transport distance without its pull inward (the same two '
+                         'options): the one for depth data')
     ap.add_argument('--match-weight', type=float, default=0.5,
                     help='--loss chamfer+match: (1 - w) Chamfer + w matching, w in (0, 1)')
     ap.add_argument('--transport-eps-scale', type=float, default=TRANSPORT_EPS_SCALE,
-                    help='--loss transport: eps = scale / particle density per sample (1: the plan blurs over one particle spacing)')
+                    help='--loss transport, sinkhorn: eps = scale / particle density per sample (1: the plan blurs over one particle spacing)')
     ap.add_argument('--transport-iters', type=int, default=TRANSPORT_ITERS,
-                    help='--loss transport: Sinkhorn sweeps per problem, 1..%d' % TRANSPORT_MAX_ITERS)
+                    help='--loss transport, sinkhorn: Sinkhorn sweeps per problem, 1..%d' % TRANSPORT_MAX_ITERS)
     ap.add_argument('--impulses', choices=IMPULSES, default=None,
                     help='(default data) actions: compute every step\'s impulse from the recorded push on the state the model predicted')
     a = ap.parse_args(argv)

@@ -567,7 +567,7 @@ int drp_ptcl_dataset_time(drp_ctx* ctx, float* ms_out);
 /* HIP-event timing of one kernel class on the context's stream.  name: "graph",
  * "node_encode", "edge_encode", "project", "aggregate", "update", "predict", "reward",
  * "mppi", "prop" (the fused propagation-step kernel of DRP_ENGINE_FUSED / _LITE), "loss" (the stand-alone metrics' kernel:
- * drp_cloud_chamfer, drp_cloud_match, drp_cloud_transport).  drp_probe_read returns total ms and launches since drp_probe_begin. */
+ * drp_cloud_chamfer, drp_cloud_match, drp_cloud_transport, drp_cloud_divergence).  drp_probe_read returns total ms and launches since drp_probe_begin. */
 int drp_probe_begin(drp_ctx* ctx, const char* kernel_class);
 int drp_probe_read(drp_ctx* ctx, double* total_ms, long* launches);
 /* Kernel launches inside the timed regions of the "prop" / "prop+work" probe since drp_probe_begin.  drp_probe_read's `launches`
@@ -848,6 +848,50 @@ int drp_train_step_transport(drp_ctx* ctx, const float* states, const float* sta
                              const float* targets /*[B][H][M][3]*/, const int32_t* target_nums /*[B][H]*/, int M,
                              const double* eps /*[B]*/, int iters, int mode, double* loss_out, float* grad_out,
                              double* col_err_out /*[H][B], nullable*/);
+
+/* ---- Sinkhorn divergence of two padded cloud batches and its gradient: drp_cloud_transport's loss with its
+ * entropic bias taken out.  An entropy-regularised plan blurs every particle's mass over its neighbours, so the cloud that
+ * minimises the transport term over p is a shrunken copy of q: at p == q the transport gradient is not zero, and descent on it
+ * pulls a pile inward.  tests/test_divergence_host.py measures both on the float64 definition (a jittered 0.02 grid, eps = 0.02^2,
+ * K = 50): at p == q, 40 points, the transport gradient's largest component is 1.0e-4, a seventh of the 7.1e-4 of two unrelated
+ * clouds, where the divergence's is 1.2e-8 and its value -9e-14 against a transport term of 1.1e-4; 200 steps of descent from
+ * p = q shrink a 64-point pile's radius of gyration by 4.3 % under transport and move it by 2e-7 of itself under the divergence.
+ * The divergence
+ *       S(p, q) = OT(p, q) - OT(p, p) / 2 - OT(q, q) / 2     on the dual values
+ * is non-negative, zero only for equal clouds, sees density and gives every real row a gradient for any pair of counts.  Per
+ * problem (one sample at one rollout step), with n_p and n_q real rows, a = 1/n_p, b = 1/n_q, eps = eps[b] > 0, K = iters:
+ *   Cross problem.  Exactly drp_cloud_transport's cost and sweeps: f = 0, then K times g's update and f's.
+ *                P_ij = a b exp((f_i + g_j - C_ij)/eps).
+ *   Self problem of a cloud x with n rows and mass m = 1/n.  h = 0.  K times, for every j:
+ *                h_j <- (h_j + (-eps LSE_i((h_i - C^xx_ij)/eps + log m))) / 2.  Every h_i on the right is the previous sweep's
+ *                value (Jacobi form, two arrays).  LSE is max-shifted as in the cross problem.
+ *                S_ij = m^2 exp((h_i + h_j - C^xx_ij)/eps) is symmetric by construction.
+ *   Value.       divergence = scale (sum_i a f_i + sum_j b g_j - sum_i a h^p_i - sum_j b h^q_j) / 3.  This is the dual form, not
+ *                sum P C: the non-negativity holds for it, and the gradient below is its gradient at convergence.  It is not
+ *                clamped: rounding or too few sweeps can leave it a hair below zero at p ~ q.
+ *   Gradient.    d/dp_i = (2 scale / 3) (sum_j P_ij (p_i - q_j) - sum_j S^p_ij (p_i - p_j)).  P and S are constants of the
+ *                derivative.  The differences are fp32 and widened, both sums are in double, and their difference is rounded
+ *                once to fp32.  Padding rows get +0.0.  The q-q problem contributes to the value only.
+ *   Certificates.  col_err as drp_cloud_transport's.  self_err = [sum_i |sum_j S^p_ij - a|, sum_j |sum_i S^q_ij - b|].  Outputs,
+ *                not stopping rules.
+ *   Fixed work, non-finite input, determinism.  As drp_cloud_transport: the loops are counted by K, n_p and n_q alone; no
+ *                atomics, one summation order; the bits depend on the two counts, not on the padded N and M, on B or on the
+ *                neighbouring samples.
+ * dual_out [B][2N + 2M]: f, g, h^p, h^q, 0 on padding.  Contract and refusals as drp_cloud_transport (every output but
+ * terms_out is nullable); it counts under the "loss" kernel class of drp_probe_begin.  There is no float64 yardstick for it: the
+ * trainer's probe options refuse it as they refuse the matching and the transport loss. */
+int drp_cloud_divergence(drp_ctx* ctx, const float* p, const int32_t* n_p, const float* q, const int32_t* n_q,
+                         int B, int N, int M, const double* eps /*[B]*/, int iters, double* terms_out /*[B]*/,
+                         float* grad_p_out /*[B][N][3], nullable*/, double* dual_out /*[B][2N+2M]: f, g, h_p, h_q, nullable*/,
+                         double* col_err_out /*[B], nullable*/, double* self_err_out /*[B][2], nullable*/);
+
+/* drp_train_step_transport with the divergence of drp_cloud_divergence as each step's term: the same arguments, refusals and
+ * contract, plus self_err_out [H][B][2] (nullable): every problem's self_err. */
+int drp_train_step_divergence(drp_ctx* ctx, const float* states, const float* states_delta /*or NULL*/, const float* actions /*or NULL*/,
+                              const float* attrs, const int32_t* particle_nums, const float* particle_dens, int B, int N,
+                              const float* targets /*[B][H][M][3]*/, const int32_t* target_nums /*[B][H]*/, int M,
+                              const double* eps /*[B]*/, int iters, int mode, double* loss_out, float* grad_out,
+                              double* col_err_out /*[H][B], nullable*/, double* self_err_out /*[H][B][2], nullable*/);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,9 @@
 // cm_layout's, chamfer_layout's and chamfer64_layout's blocks: the inputs staged, every output block written in full; the two
 // Chamfer layouts held to offset chains written out by hand here, an independent restatement), with the check
 // that refuses a real row that is no number.  The transport loss: transport_layout's blocks staged like the matching's, the
-// eps block behind a training batch (tr_layout with `eps`), and the check of the regularisation strengths.  No device is touched.
+// eps block behind a training batch (tr_layout with `eps`), and the check of the regularisation strengths.  The Sinkhorn divergence:
+// divergence_layout's five blocks that come back staged the same way, eps and the kernels' scratch behind them written in full
+// inside a block of exactly its `bytes`, and the trainer's doubles (tr_div_loss_layout) likewise.  No device is touched.
 //
 //   train_host_check layout64 B H N M actions     prints tr64_layout's eight fields (4-byte words) and exits
 #include <cstdio>
@@ -182,6 +184,45 @@ static void stage_transport(int B, int N, int M) {
     const size_t len[] = {(size_t)B * 8, bn * 12, (bn + bm) * 8, (size_t)B * 8, (size_t)B * 8};
     stage_cloud(transport_layout(B, N, M), B, N, M, 5, len);
 }
+// drp_cloud_divergence: five output blocks as a one-shot's; behind them eps [B], the value sums [3][B] and the gradient sums
+// [2][B][N][3], which the kernels write and nothing reads back
+static void stage_divergence(int B, int N, int M) {
+    const size_t bn = (size_t)B * N, bm = (size_t)B * M;
+    const DivLayout lay = divergence_layout(B, N, M);
+    const size_t len[] = {(size_t)B * 8, bn * 12, 2 * (bn + bm) * 8, (size_t)B * 8, (size_t)B * 16};
+    CloudLayout back = lay.cloud;
+    back.bytes = lay.eps;                                            // what comes back ends where eps starts
+    stage_cloud(back, B, N, M, 5, len);
+    const size_t off[] = {lay.eps, lay.vals, lay.gsum, lay.cloud.bytes};
+    const size_t xlen[] = {(size_t)B * 8, (size_t)3 * B * 8, 2 * bn * 3 * 8};
+    char* io = static_cast<char*>(std::malloc(lay.cloud.bytes));
+    for (int k = 0; k < 3; ++k) {
+        EXPECT(off[k] % 16 == 0);
+        EXPECT(off[k] + xlen[k] <= off[k + 1] && off[k + 1] - (off[k] + xlen[k]) < 16);
+        std::memset(io + off[k], k + 1, xlen[k]);
+    }
+    for (int k = 0; k < 3; ++k) EXPECT(io[off[k]] == k + 1 && io[off[k] + xlen[k] - 1] == k + 1);
+    // the last row's last gradient sum of the second problem set, where kd_sweeps' p-p block of the last sample stores it
+    double* gsum = reinterpret_cast<double*>(io + lay.gsum);
+    gsum[((size_t)B + (B - 1)) * N * 3 + (size_t)(N - 1) * 3 + 2] = 1.0;
+    reinterpret_cast<double*>(io + lay.vals)[2 * (size_t)B + (B - 1)] = 1.0;
+    std::free(io);
+}
+// drp_train_step_divergence's doubles on the device: the terms, the certificates and the kernels' scratch, packed, in doubles
+static void stage_div_loss(int B, int H, int N) {
+    const TrDivLoss dl = tr_div_loss_layout(B, H, N);
+    const size_t hb = (size_t)H * B;
+    const size_t off[] = {dl.terms, dl.col_err, dl.self_err, dl.vals, dl.gsum, dl.count};
+    const size_t len[] = {hb, hb, 2 * hb, 3 * hb, 2 * hb * N * 3};
+    EXPECT(dl.terms == 0 && dl.col_err == hb);                       // the transport loss's two blocks where they were
+    double* d = static_cast<double*>(std::malloc(dl.count * sizeof(double)));
+    for (int k = 0; k < 5; ++k) {
+        EXPECT(off[k] + len[k] == off[k + 1]);
+        for (size_t e = 0; e < len[k]; ++e) d[off[k] + e] = (double)k;
+    }
+    for (int k = 0; k < 5; ++k) EXPECT(d[off[k]] == (double)k && d[off[k + 1] - 1] == (double)k);
+    std::free(d);
+}
 // drp_train_step_transport's batch: eps [B] (doubles) behind everything else, the other blocks where they were
 static void stage_eps(int B, int H, int N, int M, bool actions) {
     const TrArena lay = tr_layout(B, H, N, M, actions, true), plain = tr_layout(B, H, N, M, actions);
@@ -246,7 +287,10 @@ int main(int argc, char** argv) {
     for (const auto& s : mshapes) {
         stage_match(s[0], s[1], s[2]);
         stage_transport(s[0], s[1], s[2]);
+        stage_divergence(s[0], s[1], s[2]);
     }
+    const int dshapes[][3] = {{1, 1, 1}, {2, 2, 9}, {4, 5, 100}, {3, 1, 1024}};
+    for (const auto& s : dshapes) stage_div_loss(s[0], s[1], s[2]);
     for (const auto& s : shapes)
         for (int actions = 0; actions < 2; ++actions)
             if (s[3] > 0) stage_eps(s[0], s[1], s[2], s[3], actions != 0);

@@ -9,6 +9,9 @@
 (b) a whole mode='update' step at 4 x 5 x 100 (B x n_rollout x N = M) under 'chamfer', 'match' and 'transport', interleaved on one
     context: host time of the call (it returns when the step is complete on the device), the median of 6 blocks of 10 after
     warm-up, as tools/match_timing.py measures its steps.
+(c) python tools/transport_timing.py --divergence [output file] -> profiles/divergence_timing.txt: the Sinkhorn divergence
+    (csrc/k_divergence.h: kd_sweeps and kd_combine, one timed region) beside kt_transport on the same clouds, 20 problems at
+    100 x 100 and 300 x 300, measured as (a); and a whole update at 4 x 5 x 100 under 'transport' and 'sinkhorn', measured as (b).
 Each measurement runs in a child process of its own under a time limit (a stuck step ends there, and nothing follows it)."""
 import subprocess
 import sys
@@ -18,6 +21,7 @@ sys.path.insert(0, '.')
 import numpy as np
 
 SIZES = ((20, 20), (50, 50), (100, 100), (300, 300), (100, 130))
+DIVERGENCE_SIZES = (100, 300)
 PROBLEMS = 20
 STEP_LIMIT_S = 120
 SPACING = 0.02
@@ -61,7 +65,36 @@ def kernel_times(n, m):
              med['kt_transport'] / med['kc_chamfer'], med['kt_transport'] / med['ka_match'], col_err), flush=True)
 
 
-def update_times():
+def divergence_kernel_times(n, m):
+    from dyn_res_pile_manip_amd import train_gnn_dyn as TG
+    from dyn_res_pile_manip_amd.engine import Engine
+    eng = Engine(0)
+    p, q = clouds(n, m, 7 * n + m)
+    eps, K = TG.TRANSPORT_EPS_SCALE * SPACING ** 2, TG.TRANSPORT_ITERS
+    calls = (('kt_transport', lambda: eng.cloud_transport(p, q, eps=eps, iters=K, want_grad=True)),
+             ('kd_sweeps + kd_combine', lambda: eng.cloud_divergence(p, q, eps=eps, iters=K, want_grad=True)))
+    for _ in range(3):
+        for _, call in calls:
+            call()
+    took = dict((name, []) for name, _ in calls)
+    for _ in range(21):
+        for name, call in calls:
+            eng.probe_begin('loss')
+            call()
+            ms, launches = eng.probe_read()
+            assert launches == 1
+            took[name].append(ms)
+    eng.probe_begin(None)
+    self_err = float(eng.cloud_divergence(p, q, eps=eps, iters=K, want_self_err=True)['self_err'].max())
+    eng.close()
+    med = dict((name, float(np.median(took[name]))) for name in took)
+    print('%d problems of %d x %d, K = %d: %s; the divergence = %.2f x kt_transport; self_err at most %.1e'
+          % (PROBLEMS, n, m, K, ', '.join('%s %.4f ms (%.4f .. %.4f)' % (name, med[name], min(took[name]), max(took[name]))
+                                          for name, _ in calls),
+             med['kd_sweeps + kd_combine'] / med['kt_transport'], self_err), flush=True)
+
+
+def update_times(kinds=('chamfer', 'match', 'transport')):
     from dyn_res_pile_manip_amd import synthetic as syn, train_gnn_dyn as TG, weights
     from dyn_res_pile_manip_amd.engine import Engine
     eng = Engine(0)
@@ -82,11 +115,12 @@ def update_times():
     tn = np.full((B, H), N, np.int32)
     eps, K = TG.transport_eps(dens), TG.TRANSPORT_ITERS
     eng.train_begin(H, 1e-3, 0.9)
-    kinds = ('chamfer', 'match', 'transport')
 
     def step(k):
         if k == 'transport':
             return eng.train_step_transport(states, attrs, pn, dens, targets, tn, eps, K, states_delta=sdelta, mode='update')
+        if k == 'sinkhorn':
+            return eng.train_step_divergence(states, attrs, pn, dens, targets, tn, eps, K, states_delta=sdelta, mode='update')
         return eng.train_step_loss(states, attrs, pn, dens, targets, tn, states_delta=sdelta, loss=k, mode='update')
     for k in kinds:
         step(k), step(k)
@@ -104,8 +138,11 @@ def update_times():
     med = dict((k, float(np.median(took[k]))) for k in kinds)
     print('update at B=%d n_rollout=%d N=M=%d, K = %d: %s' % (B, H, N, K, ', '.join("'%s' %.3f ms (blocks %.3f .. %.3f)"
           % (k, med[k], min(took[k]), max(took[k])) for k in kinds)), flush=True)
-    print("a 'transport' update costs %.2f 'chamfer' updates and %.2f 'match' updates"
-          % (med['transport'] / med['chamfer'], med['transport'] / med['match']), flush=True)
+    if 'sinkhorn' in kinds:
+        print("a 'sinkhorn' update costs %.2f 'transport' updates" % (med['sinkhorn'] / med['transport'],), flush=True)
+    else:
+        print("a 'transport' update costs %.2f 'chamfer' updates and %.2f 'match' updates"
+              % (med['transport'] / med['chamfer'], med['transport'] / med['match']), flush=True)
 
 
 if __name__ == '__main__':
@@ -113,11 +150,20 @@ if __name__ == '__main__':
         kernel_times(int(sys.argv[2]), int(sys.argv[3]))
     elif len(sys.argv) > 1 and sys.argv[1] == '--update':
         update_times()
+    elif len(sys.argv) > 1 and sys.argv[1] == '--divergence-kernel':
+        divergence_kernel_times(int(sys.argv[2]), int(sys.argv[3]))
+    elif len(sys.argv) > 1 and sys.argv[1] == '--divergence-update':
+        update_times(('transport', 'sinkhorn'))
     else:
-        out = sys.argv[1] if len(sys.argv) > 1 else 'profiles/transport_timing.txt'
+        divergence = len(sys.argv) > 1 and sys.argv[1] == '--divergence'
+        rest = sys.argv[2:] if divergence else sys.argv[1:]
+        out = rest[0] if rest else ('profiles/divergence_timing.txt' if divergence else 'profiles/transport_timing.txt')
         lines = ['tools/transport_timing.py: device time of the loss kernels by HIP events (median of 21 interleaved launches, min ..',
                  'max), and host time of whole update steps (median of 6 interleaved blocks of 10); one MI355X', '']
         jobs = [['--kernel', str(n), str(m)] for n, m in SIZES] + [['--update']]
+        if divergence:
+            lines[0] = lines[0].replace('tools/transport_timing.py:', 'tools/transport_timing.py --divergence:')
+            jobs = [['--divergence-kernel', str(n), str(n)] for n in DIVERGENCE_SIZES] + [['--divergence-update']]
         for job in jobs:
             r = subprocess.run(['timeout', '-k', '10', str(STEP_LIMIT_S), sys.executable, __file__] + job, stdout=subprocess.PIPE,
                                stderr=subprocess.STDOUT, universal_newlines=True)
