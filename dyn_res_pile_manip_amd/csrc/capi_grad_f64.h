@@ -5,7 +5,8 @@
 // gradients).  They differ in where a step's impulse comes from (the push, or data), in the loss that seeds the reverse pass, in
 // the tail of a reverse step, and in the trainer's weight-gradient launches in between (F64Wgrad).  drp_train_grad_f64_untracked is the
 // trainer's body with the Chamfer loss of k_chamfer_f64.h as the seed (row u1's yardstick); everything behind the seed is the
-// same code.  Like the one-step calls of
+// same code, and drp_train_grad_f64_divergence (capi_divergence_f64.h) is it with the Sinkhorn divergence of k_divergence_f64.h
+// (row u4).  Like the one-step calls of
 // capi_f64.h they are no engine and no session: they work in buffers of their own under F64Scope, keep nothing between calls
 // and leave the context -- the trainer's Adam state included -- as they found it.
 
@@ -262,7 +263,8 @@ struct Tr64Ws {
     F64Tape tape;
     F64Rev rev;
     F64Wgrad wg;
-    size_t carve(void* base, size_t bc, size_t N, size_t H) {                   // -> its bytes
+    double *div_vals, *div_gsum;    // the Sinkhorn divergence (`div`): kd64_sweeps' scratch, [3][H][bc] and [2][H][bc][N][3]
+    size_t carve(void* base, size_t bc, size_t N, size_t H, bool div = false) {  // -> its bytes
         F64Carver a{static_cast<char*>(base)};
         const size_t pn = bc * N, en = pn * DRP_K;
         tape.carve(a, pn, H);
@@ -270,6 +272,7 @@ struct Tr64Ws {
         a.take(wg.pr_h, pn * 64); a.take(wg.pr_gh, pn * 64); a.take(wg.pe_h, pn * 64); a.take(wg.pe_gh, pn * 64); a.take(wg.pe_in, pn * 5);
         a.take(wg.re_h1, en * 64); a.take(wg.re_h2, en * 64); a.take(wg.re_g1, en * 64); a.take(wg.re_g2, en * 64); a.take(wg.re_in, en * 6);
         a.take(wg.acc, bc * (size_t)W_TOTAL);
+        a.take(div_vals, div ? 3 * H * bc : 0); a.take(div_gsum, div ? 2 * H * pn * 3 : 0);
         return a.off;
     }
 };
@@ -284,6 +287,9 @@ struct Tr64Io {
     int M;
     double *terms, *total;          // [H][B], [W_TOTAL]
     double* margin;                 // the Chamfer loss: [H][B], every (step, sample)'s smallest arg-min margin
+    const double* eps;              // the Sinkhorn divergence (non-null): the regularisation strengths [B], with `iters` sweeps,
+    int iters;                      //   against the same targets; its certificates behind the total: col_err [H][B], self_err [H][B][2]
+    double *col_err, *self_err;
 };
 
 // forward with tape, loss, reverse pass with weight gradients of the samples [b0, b0 + bc): launches and the state gradient's copy
@@ -304,7 +310,19 @@ int tr64_chunk(drp_ctx* c, const Tr64Ws& k, const Tr64Io& io, int b0, int bc, in
                                ptr<float>(c->ws.s_in), ptr<float>(c->ws.s_delta));
     }));
     // ---- every step's loss term and its seed of the reverse pass; the samples' accumulators start at zero
-    if (io.M == 0) {
+    if (io.eps != nullptr) {
+        // the same slot of the stream and the same outputs: the plans from the tape's own double states (k_divergence_f64.h)
+        Kd64Args a{};
+        a.cp = tr_cloud_pair((size_t)N * 3, pn * 3, io.nums, io.targets, io.tnums, H, N, io.M);
+        a.pred = k.tape.state + pn * 3;
+        a.b_off = b0; a.B = B;
+        a.eps = io.eps; a.iters = io.iters;
+        a.scale = 1.0 / ((double)H * (double)B);
+        a.vals = k.div_vals; a.gsum = k.div_gsum;
+        a.grad = k.rev.g_state; a.terms = io.terms; a.col_err = io.col_err; a.self_err = io.self_err;
+        hipLaunchKernelGGL(kd64_sweeps, dim3(bc, H, 3), dim3(KT_THREADS), 0, st, a);
+        hipLaunchKernelGGL(kd64_combine, dim3(bc, H), dim3(KD_COMBINE_THREADS), 0, st, a);
+    } else if (io.M == 0) {
         hipLaunchKernelGGL(kt64_mse, dim3(bc, H), dim3(256), 0, st, k.tape.state, io.states, io.nums, b0, bc, B, N, H, io.terms, k.rev.g_state);
     } else {
         // the same slot of the stream and the same outputs: slice t + 1 of the tape's states against step t of the target clouds,
@@ -382,12 +400,13 @@ int drp_gd_grad_f64(drp_ctx* c, const float* s0, const float* attr, const float*
 namespace {
 // drp_train_grad_f64, drp_train_grad_f64_actions and drp_train_grad_f64_untracked: one body; `impulses` is states_delta
 // [B][H][N][3], or with `actions` the pushes [B][H][4]; the loss kind and the targets in `lk` (capi_train.h: TrLoss) -- the tracked
-// MSE, or the Chamfer loss against untracked target clouds (k_chamfer_f64.h); the matching kinds have no yardstick
+// MSE, the Chamfer loss against untracked target clouds (k_chamfer_f64.h), or the Sinkhorn divergence to them
+// (k_divergence_f64.h); the matching kinds and the transport loss have no yardstick
 int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, bool actions, const float* attrs,
                         const int32_t* particle_nums, const float* particle_dens, int B, int N, int n_rollout, const TrLoss& lk,
                         double* loss_out, double* loss_terms_out, double* grad_out, double* grad_state_out) {
     CHK(need(c, true, actions, false));
-    if (lk.match()) return fail(c, DRP_EINVAL, "no float64 yardstick for loss kind %d", lk.kind);
+    if (lk.match() || lk.transport()) return fail(c, DRP_EINVAL, "no float64 yardstick for loss kind %d", lk.kind);
     CHK(check_bn(c, B, N));
     if (!states || !impulses || !attrs || !particle_nums || !particle_dens) return fail(c, DRP_EINVAL, "null argument");
     if (n_rollout < 1 || n_rollout > 64) return fail(c, DRP_EINVAL, "bad n_rollout=%d", n_rollout);
@@ -396,6 +415,12 @@ int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, 
         CHK(check_target_clouds(c, lk, KC64_MAX_POINTS, "shape"));
         CHK(check_target_nums(c, lk, B, n_rollout));
     }
+    if (lk.divergence()) {
+        CHK(check_target_clouds(c, lk, KT_MAX_POINTS, "shape"));
+        if (N > KT_MAX_POINTS) return fail(c, DRP_EINVAL, "the Sinkhorn divergence takes at most %d points per cloud (N=%d)", KT_MAX_POINTS, N);
+        CHK(check_target_nums(c, lk, B, n_rollout));
+        CHK(check_transport_params(c, lk.eps, B, lk.iters));
+    }
     if (actions) CHK(check_pushes(c, impulses, B, n_rollout));
     HIPCHK(c, hipSetDevice(c->device));
     F64Scope scope(c);
@@ -403,14 +428,15 @@ int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, 
     const int H = n_rollout;
     // samples per chunk: tape, reverse pass, weight gradients' operands and accumulators together
     Tr64Ws k{};
-    auto bytes_of = [&](size_t bc) { return k.carve(nullptr, bc, (size_t)N, (size_t)H); };
+    const bool div = lk.divergence();
+    auto bytes_of = [&](size_t bc) { return k.carve(nullptr, bc, (size_t)N, (size_t)H, div); };
     size_t Bc;
     CHK(f64_size_chunks(c, B, N, ((size_t)1 << 24) / ((size_t)N * DRP_K), bytes_of, &Bc));
-    k.carve(c->grad64_ws.p, Bc, (size_t)N, (size_t)H);
+    k.carve(c->grad64_ws.p, Bc, (size_t)N, (size_t)H, div);
     // the whole batch's inputs in one upload (train_host.h: tr64_layout): states | impulses | attrs[:, 0] | densities | particle
-    // counts [| target clouds | their counts], then the results: terms | total [| margins]
-    const int M = lk.chamfer() ? lk.M : 0;
-    const Tr64Arena lay = tr64_layout(B, H, N, M, actions);
+    // counts [| target clouds | their counts] [| eps], then the results: terms | total [| margins] [| col_err | self_err]
+    const int M = lk.chamfer() || div ? lk.M : 0;
+    const Tr64Arena lay = tr64_layout(B, H, N, M, actions, div);
     std::vector<float> host(lay.words);
     memcpy(host.data() + lay.states, states, (lay.sdelta - lay.states) * sizeof(float));
     memcpy(host.data() + lay.sdelta, impulses, (lay.attr - lay.sdelta) * sizeof(float));
@@ -421,9 +447,10 @@ int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, 
         memcpy(host.data() + lay.targets, lk.targets, (size_t)B * H * M * 3 * sizeof(float));
         memcpy(host.data() + lay.tnums, lk.target_nums, (size_t)B * H * sizeof(int32_t));
     }
+    if (div) memcpy(host.data() + lay.eps, lk.eps, (size_t)B * sizeof(double));
     const size_t n_terms = (size_t)H * B;
     Tr64Io io{};
-    CHK(f64_upload_batch(c, host, n_terms + (size_t)W_TOTAL + (M > 0 ? n_terms : 0), &io.terms));
+    CHK(f64_upload_batch(c, host, n_terms + (size_t)W_TOTAL + (div ? 3 * n_terms : M > 0 ? n_terms : 0), &io.terms));
     io.states = ptr<float>(c->grad64_io); io.sdelta = io.states + lay.sdelta; io.attr = io.states + lay.attr; io.dens = io.states + lay.dens;
     io.nums = reinterpret_cast<const int*>(io.states + lay.nums);
     io.actions = actions;
@@ -432,7 +459,12 @@ int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, 
     if (M > 0) {
         io.targets = io.states + lay.targets;
         io.tnums = reinterpret_cast<const int*>(io.states + lay.tnums);
-        io.margin = io.total + W_TOTAL;
+        if (div) {
+            io.eps = reinterpret_cast<const double*>(io.states + lay.eps); io.iters = lk.iters;
+            io.col_err = io.total + W_TOTAL; io.self_err = io.col_err + n_terms;
+        } else {
+            io.margin = io.total + W_TOTAL;
+        }
     }
     HIPCHK(c, hipMemsetAsync(io.total, 0, (size_t)W_TOTAL * sizeof(double), c->stream));
     for (int b0 = 0; b0 < B; b0 += (int)Bc)
@@ -440,7 +472,9 @@ int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, 
     std::vector<double> terms(n_terms);
     CHK(d2h(c, terms.data(), io.terms, n_terms * sizeof(double)));
     if (grad_out) CHK(d2h(c, grad_out, io.total, (size_t)W_TOTAL * sizeof(double)));
-    if (M > 0 && lk.margin_out) CHK(d2h(c, lk.margin_out, io.margin, n_terms * sizeof(double)));
+    if (io.margin && lk.margin_out) CHK(d2h(c, lk.margin_out, io.margin, n_terms * sizeof(double)));
+    if (div && lk.col_err_out) CHK(d2h(c, lk.col_err_out, io.col_err, n_terms * sizeof(double)));
+    if (div && lk.self_err_out) CHK(d2h(c, lk.self_err_out, io.self_err, 2 * n_terms * sizeof(double)));
     CHK(guarded_wait(c, nullptr));          // (the upload's host block lives until here)
     if (loss_terms_out) memcpy(loss_terms_out, terms.data(), n_terms * sizeof(double));
     if (loss_out) {

@@ -1199,8 +1199,8 @@ int check_bn(drp_ctx* c, int B, int N) {
 // back only blocks its own kernel wrote.  No weights, no session begun or ended, nothing of the engine, the dispatch marks or the
 // trainer touched.
 
-// the arguments every one of them refuses, in this order; n_cap: the cap on N beyond check_bn's (0: none), `what`: the caps' suffix
-int cloud_check(drp_ctx* c, const float* p, const int32_t* n_p, const float* q, const int32_t* n_q, int B, int N, int M,
+// the arguments every one of them refuses, in this order (p: floats, or drp_cloud_divergence_f64's doubles); n_cap: the cap on N beyond check_bn's (0: none), `what`: the caps' suffix
+int cloud_check(drp_ctx* c, const void* p, const int32_t* n_p, const float* q, const int32_t* n_q, int B, int N, int M,
                 const double* terms_out, int n_cap, int m_cap, const char* what) {
     if (!c) return DRP_EINVAL;
     CHK(check_bn(c, B, N));

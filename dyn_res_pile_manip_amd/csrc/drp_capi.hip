@@ -53,6 +53,7 @@
 #include "k_match.h"
 #include "k_transport.h"
 #include "k_divergence.h"
+#include "k_divergence_f64.h"
 #include "k_prop_inst.h"       // km_prop / km_prop3 / km_rollout: declared here, instantiated in inst_*.hip
 
 #include "dispatch.h"          // host-only: policy, variant flags, plan functions
@@ -78,6 +79,7 @@ extern "C" {
 #include "capi_ptcl_dataset.h"
 #include "capi_f64.h"
 #include "capi_grad_f64.h"
+#include "capi_divergence_f64.h"
 #include "capi_debug.h"
 
 }  // extern "C"

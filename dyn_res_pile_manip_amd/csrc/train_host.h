@@ -40,9 +40,11 @@ inline TrArena tr_layout(int B, int H, int N, int M = 0, bool actions = false, b
 // the batch as the float64 yardsticks upload it (capi_grad_f64.h: train_grad_f64_body), in 4-byte words, packed: states
 // [B][H+1][N][3] | impulses [B][H][N][3] (`actions`: the pushes [B][H][4]) | attrs[:, 0] [B][N] | densities [B] | particle counts
 // [B] (ints); drp_train_grad_f64_untracked (M > 0): behind them the target clouds [B][H][M][3] | their counts [B][H] (ints) --
-// with M = 0 the layout, and so the one copy, is drp_train_grad_f64's
-struct Tr64Arena { size_t states, sdelta, attr, dens, nums, targets, tnums, words; };
-inline Tr64Arena tr64_layout(int B, int H, int N, int M = 0, bool actions = false) {
+// with M = 0 the layout, and so the one copy, is drp_train_grad_f64's; drp_train_grad_f64_divergence (`eps`): behind everything
+// the regularisation strengths [B] (doubles, two words each) on the next even word -- the vector's base is 256-byte aligned on
+// the device, so an even word is an 8-byte boundary -- and nothing ahead of them moves
+struct Tr64Arena { size_t states, sdelta, attr, dens, nums, targets, tnums, words, eps; };
+inline Tr64Arena tr64_layout(int B, int H, int N, int M = 0, bool actions = false, bool eps = false) {
     Tr64Arena a{};
     a.states = 0;
     a.sdelta = a.states + (size_t)B * (H + 1) * N * 3;
@@ -54,6 +56,10 @@ inline Tr64Arena tr64_layout(int B, int H, int N, int M = 0, bool actions = fals
     if (M > 0) {
         a.tnums = a.targets + (size_t)B * H * M * 3;
         a.words = a.tnums + (size_t)B * H;
+    }
+    if (eps) {
+        a.eps = (a.words + 1) & ~(size_t)1;
+        a.words = a.eps + 2 * (size_t)B;
     }
     return a;
 }
@@ -120,6 +126,33 @@ inline DivLayout divergence_layout(int B, int N, int M) {
     a.cloud.bytes = up(a.gsum + 2 * bn * 3 * sizeof(double));
     return a;
 }
+// drp_cloud_divergence_f64: p is the caller's doubles, so the buffer is its own (not cloud_begin's).  Up, in one copy: p [B][N][3]
+// (doubles) | eps [B] (doubles) | q [B][M][3] | n_p [B] | n_q [B] (ints); down, behind `in_bytes`: terms [B] | gradient [B][N][3] |
+// duals [B][2N + 2M] | col_err [B] | self_err [B][2] (out[0..5), doubles all); behind them, never read back, the kernels' scratch:
+// the value sums [3][B] | the gradient sums [2][B][N][3].  Every block 16-byte aligned
+struct Div64Layout { size_t pts_p, eps, pts_q, n_p, n_q, in_bytes, out[5], out_bytes[5], vals, gsum, bytes; };
+inline Div64Layout divergence64_layout(int B, int N, int M) {
+    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t bn = (size_t)B * N, bm = (size_t)B * M;
+    Div64Layout a{};
+    a.pts_p = 0;
+    a.eps = up(a.pts_p + bn * 3 * sizeof(double));
+    a.pts_q = up(a.eps + (size_t)B * sizeof(double));
+    a.n_p = up(a.pts_q + bm * 3 * sizeof(float));
+    a.n_q = up(a.n_p + (size_t)B * sizeof(int32_t));
+    a.bytes = a.in_bytes = up(a.n_q + (size_t)B * sizeof(int32_t));
+    const size_t ob[5] = {(size_t)B * sizeof(double), bn * 3 * sizeof(double), 2 * (bn + bm) * sizeof(double), (size_t)B * sizeof(double),
+                          (size_t)B * 2 * sizeof(double)};
+    for (int k = 0; k < 5; ++k) {
+        a.out[k] = a.bytes;
+        a.out_bytes[k] = ob[k];
+        a.bytes = up(a.bytes + ob[k]);
+    }
+    a.vals = a.bytes;
+    a.gsum = up(a.vals + (size_t)3 * B * sizeof(double));
+    a.bytes = up(a.gsum + 2 * bn * 3 * sizeof(double));
+    return a;
+}
 // drp_train_step_divergence's device doubles (c->tr_loss), in doubles: terms [H][B] | col_err [H][B] | self_err [H][B][2] | the
 // value sums [3][H][B] | the gradient sums [2][H][B][N][3]
 struct TrDivLoss { size_t terms, col_err, self_err, vals, gsum, count; };
@@ -141,8 +174,9 @@ inline int first_bad_eps(const double* eps, int B) {
     return -1;
 }
 // the first of the real rows' coordinates of a padded cloud batch [B][N][3] that is infinite or no number, as b * N + row, or -1
-// (the padding is never read as points: rubbish there is allowed)
-inline long first_nonfinite_row(const float* x, const int32_t* counts, int B, int N) {
+// (the padding is never read as points: rubbish there is allowed); T: float, or drp_cloud_divergence_f64's double
+template <typename T>
+inline long first_nonfinite_row(const T* x, const int32_t* counts, int B, int N) {
     for (int b = 0; b < B; ++b)
         for (int i = 0; i < counts[b] && i < N; ++i)
             for (int d = 0; d < 3; ++d)

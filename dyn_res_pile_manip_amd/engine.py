@@ -1015,6 +1015,39 @@ class Engine(object):
             out['nn_pq'], out['nn_qp'] = nn_pq, nn_qp
         return out
 
+    def cloud_divergence_f64(self, p, q, n_p=None, n_q=None, eps=None, iters=None, want_grad=False, want_dual=False,
+                             want_col_err=False, want_self_err=False):
+        """cloud_divergence with nothing in fp32, on the device (include/drp.h: drp_cloud_divergence_f64): p is taken as float64
+        [B, N, 3] -- every bit of it enters the costs, as the float64 tape's predicted state does in train_grad_f64_divergence --
+        q as float32 widened exactly; costs and differences are double, and 'grad' is float64, never rounded to fp32.  The same
+        arguments, dict, limits (1024 points per cloud) and one-shot contract."""
+        if eps is None or iters is None:
+            raise ValueError('cloud_divergence_f64 needs eps (squared-distance units) and iters')
+        p64, q = _f64(p), _f32(q)
+        if p64.ndim == 2 and q.ndim == 2:
+            p64, q = p64[None], q[None]
+        _, q, n_p, n_q, B, N, M = self._cloud_pair(np.empty(p64.shape, np.float32), q, n_p, n_q)     # (the shapes' checks)
+        eps = np.ascontiguousarray(np.broadcast_to(np.asarray(eps, np.float64).reshape(-1), (B,)))
+        terms = np.empty((B,), np.float64)
+        grad = np.empty((B, N, 3), np.float64) if want_grad else None
+        dual = np.empty((B, 2 * (N + M)), np.float64) if want_dual else None
+        col_err = np.empty((B,), np.float64) if want_col_err else None
+        self_err = np.empty((B, 2), np.float64) if want_self_err else None
+        self._ck(self.lib.drp_cloud_divergence_f64(self.h, _dp(p64), _ip(n_p), _fp(q), _ip(n_q), B, N, M, _dp(eps), int(iters),
+                                                   _dp(terms), _opt(_dp, grad), _opt(_dp, dual), _opt(_dp, col_err),
+                                                   _opt(_dp, self_err)))
+        out = {'divergence': terms}
+        if want_grad:
+            out['grad'] = grad
+        if want_dual:
+            out['f'], out['g'] = dual[:, :N].copy(), dual[:, N:N + M].copy()
+            out['h_p'], out['h_q'] = dual[:, N + M:2 * N + M].copy(), dual[:, 2 * N + M:].copy()
+        if want_col_err:
+            out['col_err'] = col_err
+        if want_self_err:
+            out['self_err'] = self_err
+        return out
+
     # ---- the float64 yardstick of the trainer's gradients (include/drp.h: drp_train_grad_f64) ------------------------
     def _train_grad64(self, states, states_delta, actions, attrs, particle_nums, particle_dens, targets, target_nums, want_state):
         """One float64 trainer call -> (loss, terms [H, B], gradient blob, margin [H, B] or None, state gradient or None).  The C
@@ -1068,8 +1101,33 @@ class Engine(object):
                                                            targets, target_nums, want_state)
         return (loss, terms, grad, margin, gs) if want_state else (loss, terms, grad, margin)
 
+    def train_grad_f64_divergence(self, states, states_delta, attrs, particle_nums, particle_dens, targets, target_nums, eps, iters,
+                                  actions=None, want_state=False, want_err=False):
+        """train_grad_f64_untracked with the Sinkhorn divergence in place of the Chamfer loss: what
+        train_step_divergence(mode='grad') computes, in float64 on the device (include/drp.h: drp_train_grad_f64_divergence).
+        eps [B] (or a number) and iters as train_step_divergence's; actions [B, n_rollout, 4] in place of states_delta (then
+        ignored, may be None).  The plans of every step are formed from the float64 prediction itself -> (loss, loss_terms
+        [n_rollout, B], gradient blob [38403][, d loss / d every step's predicted state [B, n_rollout, N, 3]][, col_err
+        [n_rollout, B], self_err [n_rollout, B, 2]: every problem's certificates]).  The same one-shot contract."""
+        assert targets is not None and target_nums is not None
+        by_actions = actions is not None
+        keep, (B, N, H, M), (ps, pi, pa, pn, pd, pt, ptn) = self._train_batch(
+            states, _f32(actions) if by_actions else states_delta, attrs, particle_nums, particle_dens, targets, target_nums,
+            by_actions, False)
+        eps = np.ascontiguousarray(np.broadcast_to(np.asarray(eps, np.float64).reshape(-1), (max(B, 1),)))
+        loss = ctypes.c_double()
+        terms = np.empty((max(H, 0), B), np.float64)
+        grad = np.empty((L.DRP_N_WEIGHTS,), np.float64)
+        gs = np.empty((B, max(H, 0), N, 3), np.float64) if want_state else None
+        col_err = np.empty((max(H, 0), B), np.float64) if want_err else None
+        self_err = np.empty((max(H, 0), B, 2), np.float64) if want_err else None
+        self._ck(self.lib.drp_train_grad_f64_divergence(self.h, ps, None if by_actions else pi, pi if by_actions else None, pa, pn, pd,
+                                                        B, N, H, pt, ptn, M, _dp(eps), int(iters), ctypes.byref(loss), _dp(terms),
+                                                        _dp(grad), _opt(_dp, gs), _opt(_dp, col_err), _opt(_dp, self_err)))
+        return (loss.value, terms, grad) + ((gs,) if want_state else ()) + ((col_err, self_err) if want_err else ())
+
     def train_gradient_probe(self, states, states_delta, attrs, particle_nums, particle_dens, actions=None, targets=None,
-                             target_nums=None):
+                             target_nums=None, eps=None, iters=None):
         """The gradients the trainer consumes, held against float64: train_step(mode='grad', want_grad=True) on whatever tape the
         selection gives, then train_grad_f64 on the same batch -> {'tensors': {state_dict key: {'max_abs_err', 'max_abs_ref',
         'rel' = err / max(ref, 1e-300)}}, 'worst': the key of the largest rel, 'rel': that rel, 'loss32', 'loss64', 'loss_diff',
@@ -1082,17 +1140,33 @@ class Engine(object):
         train_step_actions with targets) and train_grad_f64_untracked, and the dict also has 'loss_kind': 'chamfer' and
         'min_margin', the smallest arg-min margin of the float64 evaluation over the batch (squared distance).  The float64 side
         takes its own arg-mins: where min_margin is as small as the fp32 drift of a predicted state allows a nearest partner to
-        flip, a finding may be that flip -- a discrete change of the gradient -- and no arithmetic error."""
+        flip, a finding may be that flip -- a discrete change of the gradient -- and no arithmetic error.  With `eps` [B] (or a
+        number) and `iters` given beside the targets the loss is the Sinkhorn divergence to them: the pair is
+        train_step_divergence(mode='grad') and train_grad_f64_divergence, and the dict has 'loss_kind': 'sinkhorn', 'col_err' and
+        'self_err' -- the float64 side's largest certificates over the batch -- in place of 'min_margin'.  The float64 side forms
+        its own plans from its own predicted states."""
         from .weights import STATE_DICT_KEYS
         assert (targets is None) == (target_nums is None)
-        chamfer = targets is not None
+        assert (eps is None) == (iters is None) and (eps is None or targets is not None)
+        sinkhorn = eps is not None
+        chamfer = targets is not None and not sinkhorn
         self.dispatch_reset()
-        loss32, g32, _ = self._train_step32(states, states_delta, actions, attrs, particle_nums, particle_dens, targets, target_nums,
-                                            'grad', True)
+        if sinkhorn:
+            sd = None if actions is not None else states_delta
+            loss32, g32 = self.train_step_divergence(states, attrs, particle_nums, particle_dens, targets, target_nums, eps, iters,
+                                                     states_delta=sd, actions=actions, mode='grad', want_grad=True)
+        else:
+            loss32, g32, _ = self._train_step32(states, states_delta, actions, attrs, particle_nums, particle_dens, targets,
+                                                target_nums, 'grad', True)
         # the fp32 matrix engine's tape is the only user of k_aggregate_tape (pick_tape_engine: selected, or after a range refusal)
         tape = 'mfma' if 'k_aggregate_tape' in self.last_dispatch() else 'fused'
-        loss64, _, g64, margin, _ = self._train_grad64(states, states_delta, actions, attrs, particle_nums, particle_dens, targets,
-                                                       target_nums, False)
+        if sinkhorn:
+            loss64, _, g64, col_err, self_err = self.train_grad_f64_divergence(
+                states, states_delta, attrs, particle_nums, particle_dens, targets, target_nums, eps, iters, actions=actions,
+                want_err=True)
+        else:
+            loss64, _, g64, margin, _ = self._train_grad64(states, states_delta, actions, attrs, particle_nums, particle_dens,
+                                                           targets, target_nums, False)
         tensors, off, worst = {}, 0, None
         for key, shape in STATE_DICT_KEYS:
             n = int(np.prod(shape))
@@ -1107,6 +1181,8 @@ class Engine(object):
                'loss_diff': abs(loss32 - loss64), 'tape': tape}
         if chamfer:
             out['loss_kind'], out['min_margin'] = 'chamfer', float(margin.min())
+        if sinkhorn:
+            out['loss_kind'], out['col_err'], out['self_err'] = 'sinkhorn', float(col_err.max()), float(self_err.max())
         return out
 
     def train_set_lr(self, lr):

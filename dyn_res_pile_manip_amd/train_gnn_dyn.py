@@ -105,8 +105,10 @@ TRANSPORT_LOSSES = ('transport',)
 UNTRACKED_LOSSES = ('chamfer',) + MATCH_LOSSES + TRANSPORT_LOSSES
 # the Sinkhorn divergence of Engine.cloud_divergence (Engine.train_step_divergence): the transport loss with its entropic bias
 # taken out -- its minimum over the prediction is the target cloud, not a shrunken copy of it -- and the loss to use on depth
-# data.  It trains on the batches UNTRACKED_LOSSES train on, takes the transport loss's two options, and like it has no float64
-# yardstick.  A tuple of its own: the four above are pinned by tests as they are
+# data.  It trains on the batches UNTRACKED_LOSSES train on and takes the transport loss's two options.  The three older probe
+# options refuse it as they refuse the transport loss (their refusals are pinned by tests); its float64 yardstick
+# (Engine.train_grad_f64_divergence) is reached through an option of its own, sinkhorn_probe_every / probe_batch_sinkhorn.  A
+# tuple of its own: the four above are pinned by tests as they are
 DIVERGENCE_LOSSES = ('sinkhorn',)
 IMPULSES = ('data', 'actions')
 DATA = ('particles', 'depth')
@@ -263,6 +265,43 @@ def probe_batch(model, data, impulses='data', loss='mse'):
                                              actions=batch_actions(data) if impulses == 'actions' else None, **extra)
 
 
+def probe_batch_sinkhorn(model, data, impulses='data', transport_eps_scale=TRANSPORT_EPS_SCALE, transport_iters=TRANSPORT_ITERS):
+    """Engine.train_gradient_probe with the Sinkhorn divergence on a collate_untracked batch: train_step_divergence(mode='grad')
+    against Engine.train_grad_f64_divergence on the same batch, eps and sweeps as run_batch(loss='sinkhorn') takes them; the
+    result has 'loss_kind': 'sinkhorn' and the float64 side's largest 'col_err' and 'self_err'.  Weights, Adam state and
+    iteration count are untouched.  It works on depth_only batches with impulses='actions'.  probe_batch itself still refuses
+    the loss: its refusal is pinned by tests/test_divergence_host.py and tests/test_gpu_train_divergence.py, and folding this
+    call into probe_batch / probe_every waits for a change of those tests."""
+    loss = DIVERGENCE_LOSSES[0]
+    check_loss(loss, 0.5, transport_eps_scale, transport_iters)
+    if impulses not in IMPULSES:
+        raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
+    check_depth_only(data, loss, impulses)
+    states, states_delta, attrs, particle_nums, particle_dens = [data[i] for i in range(5)]
+    if hasattr(model, '_claim'):
+        model._claim()
+    by_actions = impulses == 'actions'
+    dens = _np(particle_dens)
+    return model.engine.train_gradient_probe(_np(states), None if (by_actions or states_delta is None) else _np(states_delta),
+                                             _np(attrs), _np(particle_nums, np.int32), dens,
+                                             actions=batch_actions(data) if by_actions else None, targets=_np(data[6]),
+                                             target_nums=_np(data[7], np.int32), eps=transport_eps(dens, transport_eps_scale),
+                                             iters=int(transport_iters))
+
+
+def check_sinkhorn_probe_option(loss, sinkhorn_probe_every, grad_probe_every=0, probe_every=0):
+    """sinkhorn_probe_every of train() / main(): the probe schedule of DIVERGENCE_LOSSES alone, and no companion of the two older
+    schedules (check_probe_options has refused those for this loss already)"""
+    if int(sinkhorn_probe_every) != sinkhorn_probe_every or sinkhorn_probe_every < 0:
+        raise ValueError('sinkhorn_probe_every must be a non-negative integer, got %r' % (sinkhorn_probe_every,))
+    if sinkhorn_probe_every > 0:
+        if grad_probe_every > 0 or probe_every > 0:
+            raise ValueError('give sinkhorn_probe_every alone, not with grad_probe_every or probe_every')
+        if loss not in DIVERGENCE_LOSSES:
+            raise ValueError('sinkhorn_probe_every needs a loss of %s, got %r: probe_every probes the losses of %s'
+                             % (DIVERGENCE_LOSSES, loss, LOSSES))
+
+
 def check_probe_options(loss, grad_probe_every, probe_every):
     """the two probe schedules of train() / main(): grad_probe_every (the MSE yardstick alone) and probe_every (every loss of
     LOSSES; the matching losses have no float64 yardstick yet and refuse both)"""
@@ -278,7 +317,7 @@ def check_probe_options(loss, grad_probe_every, probe_every):
 
 def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=None, first_epoch=0, grad_probe_every=0,
           loss='mse', impulses='data', probe_every=0, match_weight=0.5, transport_eps_scale=TRANSPORT_EPS_SCALE,
-          transport_iters=TRANSPORT_ITERS):
+          transport_iters=TRANSPORT_ITERS, sinkhorn_probe_every=0):
     """train/train_gnn_dyn.py:134-246 without the file I/O: `dataloaders` = {'train': iterable of
     collated batches, 'valid': ...}.  Returns {'best_valid_loss', 'history': [(epoch, phase, rmse)]}.
     ckp(epoch, i, model): called after training batch i when i % ckp_per_iter == 0 (:217-218); first_epoch: the epoch
@@ -293,13 +332,18 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
     n_rollout > 1 meaningful.  The engine's camera must be set (main does it).  loss in MATCH_LOSSES: run_batch's matching loss
     with match_weight; both probe options are refused with it.  loss in TRANSPORT_LOSSES: run_batch's transport loss with
     transport_eps_scale and transport_iters; the probe options are refused with it too.  loss in DIVERGENCE_LOSSES: the same
-    with run_batch's Sinkhorn divergence."""
+    with run_batch's Sinkhorn divergence.  sinkhorn_probe_every = k > 0: probe_every's schedule and history entry for a loss in
+    DIVERGENCE_LOSSES (probe_batch_sinkhorn with the run's transport_eps_scale and transport_iters); the log line also carries
+    col_err and self_err, the float64 side's largest certificates.  It is refused with any other loss and together with either
+    older probe option, which keep refusing this loss: folding it into probe_every waits for a change of the tests that pin
+    those refusals."""
     check_probe_options(loss, grad_probe_every, probe_every)
+    check_sinkhorn_probe_option(loss, sinkhorn_probe_every, grad_probe_every, probe_every)
     check_loss(loss, match_weight, transport_eps_scale, transport_iters)
     if impulses not in IMPULSES:
         raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
     loss_kind = loss
-    every = grad_probe_every if grad_probe_every > 0 else probe_every
+    every = grad_probe_every if grad_probe_every > 0 else probe_every if probe_every > 0 else sinkhorn_probe_every
     tc = config['train']
     n_rollout = tc['n_rollout']
     assert tc['n_history'] == 1
@@ -312,11 +356,16 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
             meter = AverageMeter()
             for i, data in enumerate(dataloaders[phase]):
                 if every > 0 and phase == 'train' and i % every == 0:
-                    pr = probe_batch(model, data, impulses, loss_kind)
+                    if sinkhorn_probe_every > 0:
+                        pr = probe_batch_sinkhorn(model, data, impulses, transport_eps_scale, transport_iters)
+                    else:
+                        pr = probe_batch(model, data, impulses, loss_kind)
                     history.append((epoch, 'grad_probe', float(pr['rel'])))
                     if log is not None:
                         line = 'grad_probe [%d][%d] worst %s rel %.3e (%s tape), loss diff %.3e' % (epoch, i, pr['worst'], pr['rel'],
                                                                                                   pr['tape'], pr['loss_diff'])
+                        if sinkhorn_probe_every > 0:
+                            line += ', col_err %.3e, self_err %.3e' % (pr['col_err'], pr['self_err'])
                         log(line + (', min_margin %.3e' % pr['min_margin'] if loss_kind == 'chamfer' else ''))
                 loss = run_batch(model, optimizer, data, phase, n_rollout, loss=loss_kind, impulses=impulses, match_weight=match_weight,
                                  transport_eps_scale=transport_eps_scale, transport_iters=transport_iters)
@@ -357,7 +406,7 @@ def set_seed(seed):
 
 def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8, n_epoch=None, engine=None, grad_probe_every=0,
          loss=None, impulses=None, probe_every=0, data='particles', target_den_scale=1.0, match_weight=0.5,
-         transport_eps_scale=TRANSPORT_EPS_SCALE, transport_iters=TRANSPORT_ITERS):
+         transport_eps_scale=TRANSPORT_EPS_SCALE, transport_iters=TRANSPORT_ITERS, sinkhorn_probe_every=0):
     """The file-level part of train/train_gnn_dyn.py:train() (:45-130, :196-228): seed, the log directory with config.yaml
     and log.txt, the 'train' / 'valid' ParticleDatasets and their DeviceLoaders, a fresh model (torch.nn.Linear's default
     initialisation) or the resumed checkpoint, net_epoch_%d_iter_%d.pth every ckp_per_iter training batches and
@@ -366,7 +415,7 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
     the directory.  loss='chamfer': the recorded episodes' correspondence is dropped (dataset_gnn_dyn.drop_correspondence on
     every sample, seeded by train.random_seed) and the model is trained on the Chamfer distance to the untracked clouds.
     impulses='actions': the engine's camera is set from the dataset's extrinsics and global_scale and every step's impulse comes
-    from the recorded push on the state the step reads (train).  probe_every: train's.
+    from the recorded push on the state the step reads (train).  probe_every, sinkhorn_probe_every: train's.
     data='depth': the episodes need only their depth PNGs and actions.p (a recorded robot episode): the datasets are
     DepthDatasets (every frame of a window sampled from its depth image on the device, the later frames at target_den_scale
     times the state's density), which implies loss='chamfer' and impulses='actions'; a contradicting value is refused.  loss /
@@ -380,6 +429,7 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
     from .gnn_dyn import PropNetDiffDenModel
     loss, impulses = resolve_data_options(data, loss, impulses)
     check_probe_options(loss, grad_probe_every, probe_every)
+    check_sinkhorn_probe_option(loss, sinkhorn_probe_every, grad_probe_every, probe_every)
     check_loss(loss, match_weight, transport_eps_scale, transport_iters)
     tc = config['train']
     resume = tc['particle'].get('resume', {'active': False, 'epoch': 0, 'iter': 0})
@@ -429,7 +479,8 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
         result = train(config, model, loaders, n_epoch=n_epoch, log=log, on_best=on_best, ckp=ckp,
                        first_epoch=resume['epoch'] if resume['active'] and resume['epoch'] > 0 else 0,
                        grad_probe_every=grad_probe_every, loss=loss, impulses=impulses, probe_every=probe_every,
-                       match_weight=match_weight, transport_eps_scale=transport_eps_scale, transport_iters=transport_iters)
+                       match_weight=match_weight, transport_eps_scale=transport_eps_scale, transport_iters=transport_iters,
+                       sinkhorn_probe_every=sinkhorn_probe_every)
         for epoch, phase, rmse in result['history']:
             if phase == 'grad_probe':                   # logged when it was taken
                 continue
@@ -455,6 +506,9 @@ def _cli(argv=None):
     ap.add_argument('--probe-every', type=int, default=0,
                     help='the same for every --loss and --impulses; with --loss chamfer the log line carries the float64 side\'s '
                          'smallest arg-min margin')
+    ap.add_argument('--sinkhorn-probe-every', type=int, default=0,
+                    help='--loss sinkhorn: hold every k-th training batch\'s gradients against the float64 Sinkhorn divergence before '
+                         'its update; the log line carries the float64 side\'s largest col_err and self_err (not with the two options above)')
     ap.add_argument('--data', choices=DATA, default='particles',
                     help='depth: episodes of depth PNGs and actions.p alone; every frame of a window is sampled from its depth '
                          'image on the device.  Implies --loss chamfer --impulses actions')
@@ -490,7 +544,8 @@ def _cli(argv=None):
     result, d = main(config, a.data_root, a.train_dir, chunk=a.chunk, threads=a.threads, n_epoch=a.epochs,
                      grad_probe_every=a.grad_probe_every, loss=a.loss, impulses=a.impulses, probe_every=a.probe_every,
                      data=a.data, target_den_scale=a.target_den_scale, match_weight=a.match_weight,
-                     transport_eps_scale=a.transport_eps_scale, transport_iters=a.transport_iters)
+                     transport_eps_scale=a.transport_eps_scale, transport_iters=a.transport_iters,
+                     sinkhorn_probe_every=a.sinkhorn_probe_every)
     print('best valid loss %.6f, checkpoints in %s' % (np.sqrt(result['best_valid_loss']), d))
 
 

@@ -567,7 +567,7 @@ int drp_ptcl_dataset_time(drp_ctx* ctx, float* ms_out);
 /* HIP-event timing of one kernel class on the context's stream.  name: "graph",
  * "node_encode", "edge_encode", "project", "aggregate", "update", "predict", "reward",
  * "mppi", "prop" (the fused propagation-step kernel of DRP_ENGINE_FUSED / _LITE), "loss" (the stand-alone metrics' kernel:
- * drp_cloud_chamfer, drp_cloud_match, drp_cloud_transport, drp_cloud_divergence).  drp_probe_read returns total ms and launches since drp_probe_begin. */
+ * drp_cloud_chamfer, drp_cloud_match, drp_cloud_transport, drp_cloud_divergence, drp_cloud_divergence_f64).  drp_probe_read returns total ms and launches since drp_probe_begin. */
 int drp_probe_begin(drp_ctx* ctx, const char* kernel_class);
 int drp_probe_read(drp_ctx* ctx, double* total_ms, long* launches);
 /* Kernel launches inside the timed regions of the "prop" / "prop+work" probe since drp_probe_begin.  drp_probe_read's `launches`
@@ -878,8 +878,8 @@ int drp_train_step_transport(drp_ctx* ctx, const float* states, const float* sta
  *                atomics, one summation order; the bits depend on the two counts, not on the padded N and M, on B or on the
  *                neighbouring samples.
  * dual_out [B][2N + 2M]: f, g, h^p, h^q, 0 on padding.  Contract and refusals as drp_cloud_transport (every output but
- * terms_out is nullable); it counts under the "loss" kernel class of drp_probe_begin.  There is no float64 yardstick for it: the
- * trainer's probe options refuse it as they refuse the matching and the transport loss. */
+ * terms_out is nullable); it counts under the "loss" kernel class of drp_probe_begin.  Its float64 yardstick is
+ * drp_cloud_divergence_f64 / drp_train_grad_f64_divergence below. */
 int drp_cloud_divergence(drp_ctx* ctx, const float* p, const int32_t* n_p, const float* q, const int32_t* n_q,
                          int B, int N, int M, const double* eps /*[B]*/, int iters, double* terms_out /*[B]*/,
                          float* grad_p_out /*[B][N][3], nullable*/, double* dual_out /*[B][2N+2M]: f, g, h_p, h_q, nullable*/,
@@ -892,6 +892,42 @@ int drp_train_step_divergence(drp_ctx* ctx, const float* states, const float* st
                               const float* targets /*[B][H][M][3]*/, const int32_t* target_nums /*[B][H]*/, int M,
                               const double* eps /*[B]*/, int iters, int mode, double* loss_out, float* grad_out,
                               double* col_err_out /*[H][B], nullable*/, double* self_err_out /*[H][B][2], nullable*/);
+
+/* ---- the float64 yardstick of the Sinkhorn divergence (csrc/k_divergence_f64.h).  drp_cloud_divergence's definition with nothing
+ * in fp32: p is DOUBLE [B][N][3] -- on purpose: the call runs the instantiation the trainer's yardstick runs on the float64
+ * tape's predicted state -- q the caller's floats widened exactly; every cost, of p - q, p - p and q - q, is dx*dx + dy*dy + dz*dz
+ * in double in that order on double differences (no fused multiply-add); the gradient (2 scale / 3) (sum_j P_ij (p_i - q_j) -
+ * sum_j S^p_ij (p_i - p_j)) is written as double with no rounding to fp32, +0.0 on padding; the value is the dual form, not
+ * clamped.  Sweeps, (output, part) mapping, summation orders, fixed work and determinism are drp_cloud_divergence's: the bits
+ * depend on the two counts alone.  The same one-shot contract: no weights needed, no session ended, every output but terms_out
+ * nullable, a refused call leaves the context usable.  Refusals as drp_cloud_divergence, on the host: N or M above 1024 points
+ * (DRP_EINVAL), counts outside 1..N / 1..M, eps not positive and finite, iters outside 1..DRP_TRANSPORT_MAX_ITERS, a real row
+ * that is not finite.  It is no dispatch variant; like drp_cloud_divergence it counts under the "loss" kernel class of
+ * drp_probe_begin (one timed region around its two kernels). */
+int drp_cloud_divergence_f64(drp_ctx* ctx, const double* p /*[B][N][3]*/, const int32_t* n_p, const float* q, const int32_t* n_q,
+                             int B, int N, int M, const double* eps /*[B]*/, int iters, double* terms_out /*[B]*/,
+                             double* grad_p_out /*[B][N][3], nullable*/, double* dual_out /*[B][2N+2M]: f, g, h_p, h_q, nullable*/,
+                             double* col_err_out /*[B], nullable*/, double* self_err_out /*[B][2], nullable*/);
+
+/* drp_train_grad_f64_untracked with the Sinkhorn divergence of drp_train_step_divergence in place of the Chamfer loss: the
+ * yardstick of drp_train_step_divergence's gradients, row u4.  The term of (step t, sample b) is drp_cloud_divergence_f64's value
+ * / (n_rollout B) between the DOUBLE prediction s_pred_t[b, :n_b] and targets[b, t, :target_nums[b, t]] with eps[b] and iters
+ * sweeps; it seeds the reverse pass with that call's gradient (the cross plan and the prediction's self plan constants of the
+ * derivative) on real rows and +0.0 on padded ones, and everything behind the seed is drp_train_grad_f64's code.  The plans are
+ * formed HERE from the double prediction: the fp32 trainer's plans are no input, so the difference of the two gradients includes
+ * what the fp32 state's drift does to exp(. / eps).  col_err_out [n_rollout][B] and self_err_out [n_rollout][B][2] (nullable):
+ * every problem's certificates.  Exactly one of states_delta and actions; of states only step 0 is read.  The same bits from run
+ * to run and under any workspace cap.  The one-shot contract is drp_train_grad_f64's: no drp_train_begin; the Adam state, the
+ * selected engine, the dispatch marks and the float64 taps are untouched.  Refusals: those of drp_train_grad_f64_untracked, and
+ * DRP_EINVAL for N or M above 1024 and for eps / iters as drp_cloud_transport refuses them.  The transport loss and the matching
+ * losses have no float64 yardstick. */
+int drp_train_grad_f64_divergence(drp_ctx* ctx, const float* states, const float* states_delta /*[B][H][N][3] or NULL*/,
+                                  const float* actions /*[B][H][4] or NULL*/, const float* attrs, const int32_t* particle_nums,
+                                  const float* particle_dens, int B, int N, int n_rollout,
+                                  const float* targets /*[B][H][M][3]*/, const int32_t* target_nums /*[B][H]*/, int M,
+                                  const double* eps /*[B]*/, int iters, double* loss_out, double* loss_terms_out, double* grad_out,
+                                  double* grad_state_out, double* col_err_out /*[H][B], nullable*/,
+                                  double* self_err_out /*[H][B][2], nullable*/);
 
 #ifdef __cplusplus
 }

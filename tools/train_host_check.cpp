@@ -14,7 +14,10 @@
 // that refuses a real row that is no number.  The transport loss: transport_layout's blocks staged like the matching's, the
 // eps block behind a training batch (tr_layout with `eps`), and the check of the regularisation strengths.  The Sinkhorn divergence:
 // divergence_layout's five blocks that come back staged the same way, eps and the kernels' scratch behind them written in full
-// inside a block of exactly its `bytes`, and the trainer's doubles (tr_div_loss_layout) likewise.  No device is touched.
+// inside a block of exactly its `bytes`, and the trainer's doubles (tr_div_loss_layout) likewise.  Its float64 yardstick: eps [B]
+// (doubles) behind the float64 upload on an even word (tr64_layout with `eps`), nothing ahead of it moved, and
+// drp_cloud_divergence_f64's buffer of its own (divergence64_layout: p as doubles), every block written in full; the finiteness
+// check on double rows.  No device is touched.
 //
 //   train_host_check layout64 B H N M actions     prints tr64_layout's eight fields (4-byte words) and exits
 #include <cstdio>
@@ -130,6 +133,68 @@ static void stage64(int B, int H, int N, int M, bool actions) {
         EXPECT(n(lay.tnums, 0) == 7 && n(lay.tnums, (size_t)B * H - 1) == 7 && lay.tnums + (size_t)B * H == lay.words);
     }
     std::free(host);
+}
+
+// drp_train_grad_f64_divergence's upload: eps [B] (doubles) behind everything else on an 8-byte boundary of a vector whose base is
+// aligned, the other blocks where they were
+static void stage64_eps(int B, int H, int N, int M, bool actions) {
+    const Tr64Arena lay = tr64_layout(B, H, N, M, actions, true), plain = tr64_layout(B, H, N, M, actions);
+    EXPECT(lay.states == plain.states && lay.sdelta == plain.sdelta && lay.attr == plain.attr && lay.dens == plain.dens &&
+           lay.nums == plain.nums && lay.targets == plain.targets && lay.tnums == plain.tnums);
+    EXPECT(lay.eps % 2 == 0 && lay.eps >= plain.words && lay.eps - plain.words < 2);
+    EXPECT(lay.words == lay.eps + 2 * (size_t)B);
+    EXPECT(plain.eps == 0);
+    std::vector<double> eps(B, 0.5);
+    float* host = static_cast<float*>(std::malloc(lay.words * sizeof(float)));      // (malloc aligns to 16: the device buffer to 256)
+    std::memset(host, 0xff, lay.words * sizeof(float));
+    std::memcpy(host + lay.eps, eps.data(), (size_t)B * sizeof(double));
+    EXPECT(reinterpret_cast<uintptr_t>(host + lay.eps) % sizeof(double) == 0);
+    const double* as_kernel = reinterpret_cast<const double*>(host + lay.eps);       // as kd64_sweeps addresses it
+    EXPECT(as_kernel[0] == 0.5 && as_kernel[B - 1] == 0.5);
+    std::free(host);
+}
+
+// drp_cloud_divergence_f64's buffer: the inputs (p as doubles, eps among them) staged into a vector of exactly in_bytes, the five
+// blocks that come back and the kernels' scratch written in full inside a block of exactly `bytes`
+static void stage_divergence64(int B, int N, int M) {
+    const size_t bn = (size_t)B * N, bm = (size_t)B * M;
+    const Div64Layout lay = divergence64_layout(B, N, M);
+    const size_t off[] = {lay.pts_p, lay.eps, lay.pts_q, lay.n_p, lay.n_q, lay.out[0], lay.out[1], lay.out[2], lay.out[3], lay.out[4],
+                          lay.vals, lay.gsum, lay.bytes};
+    const size_t len[] = {bn * 24, (size_t)B * 8, bm * 12, (size_t)B * 4, (size_t)B * 4, (size_t)B * 8, bn * 24, 2 * (bn + bm) * 8,
+                          (size_t)B * 8, (size_t)B * 16, (size_t)3 * B * 8, 2 * bn * 24};
+    for (int k = 0; k < 12; ++k) {
+        EXPECT(off[k] % 16 == 0);
+        EXPECT(off[k] + len[k] <= off[k + 1] && off[k + 1] - (off[k] + len[k]) < 16);
+        if (k >= 5 && k < 10) EXPECT(lay.out_bytes[k - 5] == len[k]);
+    }
+    EXPECT(lay.pts_p == 0 && lay.out[0] == lay.in_bytes);
+    std::vector<double> p(bn * 3, 1.0), eps(B, 0.5);
+    std::vector<float> q(bm * 3, 2.0f);
+    std::vector<int32_t> n_p(B, N), n_q(B, M);
+    std::vector<char> stage(lay.in_bytes);
+    std::memcpy(stage.data() + lay.pts_p, p.data(), bn * 3 * sizeof(double));
+    std::memcpy(stage.data() + lay.eps, eps.data(), (size_t)B * sizeof(double));
+    std::memcpy(stage.data() + lay.pts_q, q.data(), bm * 3 * sizeof(float));
+    std::memcpy(stage.data() + lay.n_p, n_p.data(), (size_t)B * sizeof(int32_t));
+    std::memcpy(stage.data() + lay.n_q, n_q.data(), (size_t)B * sizeof(int32_t));
+    char* io = static_cast<char*>(std::malloc(lay.bytes));
+    std::memcpy(io, stage.data(), lay.in_bytes);
+    for (int k = 5; k < 12; ++k) std::memset(io + off[k], k, len[k]);          // the kernels' stores, block by block
+    double d; float f; int32_t n;
+    std::memcpy(&d, io + lay.pts_p + (bn * 3 - 1) * 8, 8);
+    EXPECT(d == 1.0);
+    std::memcpy(&d, io + lay.eps + (size_t)(B - 1) * 8, 8);
+    EXPECT(d == 0.5);
+    std::memcpy(&f, io + lay.pts_q + (bm * 3 - 1) * 4, 4);
+    EXPECT(f == 2.0f);
+    std::memcpy(&n, io + lay.n_q + (size_t)(B - 1) * 4, 4);
+    EXPECT(n == M);
+    for (int k = 5; k < 12; ++k) EXPECT(io[off[k]] == k && io[off[k] + len[k] - 1] == k);
+    // the last row's last gradient sum of the second problem set and the last value sum, where kd64_sweeps stores them
+    reinterpret_cast<double*>(io + lay.gsum)[((size_t)B + (B - 1)) * N * 3 + (size_t)(N - 1) * 3 + 2] = 1.0;
+    reinterpret_cast<double*>(io + lay.vals)[2 * (size_t)B + (B - 1)] = 1.0;
+    std::free(io);
 }
 
 // a one-shot's buffer as cloud_begin and the kernel use it (capi_pipeline.h): the inputs copied into a vector of exactly
@@ -281,6 +346,7 @@ int main(int argc, char** argv) {
         for (int actions = 0; actions < 2; ++actions) {
             stage(s[0], s[1], s[2], s[3], actions != 0);
             stage64(s[0], s[1], s[2], s[3], actions != 0);
+            if (s[3] > 0) stage64_eps(s[0], s[1], s[2], s[3], actions != 0);
         }
     stage64(1, 1, 4096, 4096, false);                            // the largest clouds of one (sample, step)
     const int mshapes[][3] = {{1, 1, 1}, {1, 5, 3}, {3, 7, 9}, {2, 65, 64}, {1, 1024, 1024}, {5, 1024, 1}, {4, 300, 257}};
@@ -288,6 +354,7 @@ int main(int argc, char** argv) {
         stage_match(s[0], s[1], s[2]);
         stage_transport(s[0], s[1], s[2]);
         stage_divergence(s[0], s[1], s[2]);
+        stage_divergence64(s[0], s[1], s[2]);
     }
     const int dshapes[][3] = {{1, 1, 1}, {2, 2, 9}, {4, 5, 100}, {3, 1, 1024}};
     for (const auto& s : dshapes) stage_div_loss(s[0], s[1], s[2]);
@@ -329,6 +396,16 @@ int main(int argc, char** argv) {
         const int32_t over[2] = {7, 3};                          // a count beyond N is read up to N (the entry point refuses it first)
         EXPECT(first_nonfinite_row(x, over, B, N) == 1);
         std::free(x);
+        // the same on double rows (drp_cloud_divergence_f64's p)
+        const double inf64 = std::numeric_limits<double>::infinity(), nan64 = std::numeric_limits<double>::quiet_NaN();
+        double* y = static_cast<double*>(std::malloc((size_t)B * N * 3 * sizeof(double)));
+        for (int e = 0; e < B * N * 3; ++e) y[e] = 0.25 * e + 1e-12;
+        EXPECT(first_nonfinite_row(y, counts, B, N) == -1);
+        y[2 * 3 + 1] = nan64;                                    // sample 0's padding row
+        EXPECT(first_nonfinite_row(y, counts, B, N) == -1);
+        y[(1 * N + 2) * 3 + 2] = inf64;
+        EXPECT(first_nonfinite_row(y, counts, B, N) == 1 * N + 2);
+        std::free(y);
     }
 
     // the push check, with the demo camera's map (x, z, -y + 18 scaled by 1 / 24: a camera that looks straight down)

@@ -12,6 +12,9 @@
 (c) python tools/transport_timing.py --divergence [output file] -> profiles/divergence_timing.txt: the Sinkhorn divergence
     (csrc/k_divergence.h: kd_sweeps and kd_combine, one timed region) beside kt_transport on the same clouds, 20 problems at
     100 x 100 and 300 x 300, measured as (a); and a whole update at 4 x 5 x 100 under 'transport' and 'sinkhorn', measured as (b).
+(d) python tools/transport_timing.py --divergence-f64 [output file] -> profiles/divergence_f64_timing.txt: the float64 yardstick
+    (csrc/k_divergence_f64.h: kd64_sweeps and kd64_combine, one timed region) beside kd_sweeps + kd_combine on the same clouds
+    (p widened exactly), 20 problems at 100 x 100 and 300 x 300, measured as (a).  A yardstick's cost, not an engine's.
 Each measurement runs in a child process of its own under a time limit (a stuck step ends there, and nothing follows it)."""
 import subprocess
 import sys
@@ -94,6 +97,35 @@ def divergence_kernel_times(n, m):
              med['kd_sweeps + kd_combine'] / med['kt_transport'], self_err), flush=True)
 
 
+def divergence_f64_kernel_times(n, m):
+    from dyn_res_pile_manip_amd import train_gnn_dyn as TG
+    from dyn_res_pile_manip_amd.engine import Engine
+    eng = Engine(0)
+    p, q = clouds(n, m, 7 * n + m)
+    p64 = p.astype(np.float64)
+    eps, K = TG.TRANSPORT_EPS_SCALE * SPACING ** 2, TG.TRANSPORT_ITERS
+    calls = (('kd_sweeps + kd_combine', lambda: eng.cloud_divergence(p, q, eps=eps, iters=K, want_grad=True)),
+             ('kd64_sweeps + kd64_combine', lambda: eng.cloud_divergence_f64(p64, q, eps=eps, iters=K, want_grad=True)))
+    for _ in range(3):
+        for _, call in calls:
+            call()
+    took = dict((name, []) for name, _ in calls)
+    for _ in range(21):
+        for name, call in calls:
+            eng.probe_begin('loss')
+            call()
+            ms, launches = eng.probe_read()
+            assert launches == 1
+            took[name].append(ms)
+    eng.probe_begin(None)
+    eng.close()
+    med = dict((name, float(np.median(took[name]))) for name in took)
+    print('%d problems of %d x %d, K = %d: %s; the float64 yardstick = %.2f x the fp32-cost kernels'
+          % (PROBLEMS, n, m, K, ', '.join('%s %.4f ms (%.4f .. %.4f)' % (name, med[name], min(took[name]), max(took[name]))
+                                          for name, _ in calls),
+             med['kd64_sweeps + kd64_combine'] / med['kd_sweeps + kd_combine']), flush=True)
+
+
 def update_times(kinds=('chamfer', 'match', 'transport')):
     from dyn_res_pile_manip_amd import synthetic as syn, train_gnn_dyn as TG, weights
     from dyn_res_pile_manip_amd.engine import Engine
@@ -154,16 +186,23 @@ if __name__ == '__main__':
         divergence_kernel_times(int(sys.argv[2]), int(sys.argv[3]))
     elif len(sys.argv) > 1 and sys.argv[1] == '--divergence-update':
         update_times(('transport', 'sinkhorn'))
+    elif len(sys.argv) > 1 and sys.argv[1] == '--divergence-f64-kernel':
+        divergence_f64_kernel_times(int(sys.argv[2]), int(sys.argv[3]))
     else:
         divergence = len(sys.argv) > 1 and sys.argv[1] == '--divergence'
-        rest = sys.argv[2:] if divergence else sys.argv[1:]
-        out = rest[0] if rest else ('profiles/divergence_timing.txt' if divergence else 'profiles/transport_timing.txt')
+        f64 = len(sys.argv) > 1 and sys.argv[1] == '--divergence-f64'
+        rest = sys.argv[2:] if divergence or f64 else sys.argv[1:]
+        out = rest[0] if rest else ('profiles/divergence_timing.txt' if divergence else
+                                    'profiles/divergence_f64_timing.txt' if f64 else 'profiles/transport_timing.txt')
         lines = ['tools/transport_timing.py: device time of the loss kernels by HIP events (median of 21 interleaved launches, min ..',
                  'max), and host time of whole update steps (median of 6 interleaved blocks of 10); one MI355X', '']
         jobs = [['--kernel', str(n), str(m)] for n, m in SIZES] + [['--update']]
         if divergence:
             lines[0] = lines[0].replace('tools/transport_timing.py:', 'tools/transport_timing.py --divergence:')
             jobs = [['--divergence-kernel', str(n), str(n)] for n in DIVERGENCE_SIZES] + [['--divergence-update']]
+        if f64:
+            lines[0] = lines[0].replace('tools/transport_timing.py:', 'tools/transport_timing.py --divergence-f64:')
+            jobs = [['--divergence-f64-kernel', str(n), str(n)] for n in DIVERGENCE_SIZES]
         for job in jobs:
             r = subprocess.run(['timeout', '-k', '10', str(STEP_LIMIT_S), sys.executable, __file__] + job, stdout=subprocess.PIPE,
                                stderr=subprocess.STDOUT, universal_newlines=True)
