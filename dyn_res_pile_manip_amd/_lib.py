@@ -21,6 +21,7 @@ ENGINE_FUSED = 3
 ENGINE_LITE = 4             # opt-in reduced products on the fused engine's kernels (include/drp.h: DRP_ENGINE_LITE)
 TRAIN_MODES = {'eval': 0, 'grad': 1, 'update': 2}
 LOSS_KINDS = {'chamfer': 1, 'match': 2, 'chamfer+match': 3}     # DRP_LOSS_*: drp_train_step_loss
+MATCH_LOSSES = ('match', 'chamfer+match')   # the kinds with a matching: drp_train_grad_f64_match's
 MATCH_MAX_POINTS = 1024     # KA_MAX_POINTS: the largest cloud of a matching
 TRANSPORT_MAX_ITERS = 1000  # DRP_TRANSPORT_MAX_ITERS: the most sweeps of drp_cloud_transport / drp_train_step_transport
 DIST_TRANSFORMS = {'cv5': 0, 'exact': 1}
@@ -231,6 +232,13 @@ SIGNATURES = {
                                                      c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_float_p, c_int32_p,
                                                      ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, c_double_p, c_double_p,
                                                      c_double_p, c_double_p, c_double_p]),
+    'drp_cloud_match_f64': (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_int32_p, c_float_p, c_int32_p, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int, c_int32_p, c_double_p, c_double_p, c_int32_p, c_int32_p, c_double_p,
+                                           c_double_p]),
+    'drp_train_grad_f64_match': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, c_int32_p, c_float_p,
+                                                ctypes.c_int, ctypes.c_int, ctypes.c_int, c_float_p, c_int32_p, ctypes.c_int,
+                                                ctypes.c_int, ctypes.c_double, c_int32_p, c_double_p, c_double_p, c_double_p,
+                                                c_double_p, c_int32_p, c_double_p, c_double_p]),
 }
 
 _lib = None

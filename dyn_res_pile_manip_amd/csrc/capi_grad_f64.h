@@ -6,7 +6,8 @@
 // the tail of a reverse step, and in the trainer's weight-gradient launches in between (F64Wgrad).  drp_train_grad_f64_untracked is the
 // trainer's body with the Chamfer loss of k_chamfer_f64.h as the seed (row u1's yardstick); everything behind the seed is the
 // same code, and drp_train_grad_f64_divergence (capi_divergence_f64.h) is it with the Sinkhorn divergence of k_divergence_f64.h
-// (row u4).  Like the one-step calls of
+// (row u4), drp_train_grad_f64_match (capi_match_f64.h) with the matching term of k_match_f64.h or its mix with the Chamfer term
+// (row u2).  Like the one-step calls of
 // capi_f64.h they are no engine and no session: they work in buffers of their own under F64Scope, keep nothing between calls
 // and leave the context -- the trainer's Adam state included -- as they found it.
 
@@ -258,6 +259,18 @@ int gd64_chunk(drp_ctx* c, const Gd64Ws& k, int b0, int bc, int nb, int N, int H
 }
 
 // ---- the trainer's gradients --------------------------------------------------------------------------------------------
+// ka64_match on grid (samples, steps): its dynamic LDS at the cap is above what a function may use unasked, so the context sets
+// the function's attribute once, at first use
+int ka64_run(drp_ctx* c, dim3 grid, const Ka64Args& a) {
+    if (!c->ka64_ready) {
+        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&ka64_match), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)KA64_LDS(KA_MAX_POINTS)));
+        c->ka64_ready = true;
+    }
+    ka64_launch(grid, c->stream, a);
+    return DRP_OK;
+}
+
 // a chunk's workspace: the shared parts, then the weight gradients' operands and accumulators (wg's; the chunk fills in the rest)
 struct Tr64Ws {
     F64Tape tape;
@@ -290,7 +303,25 @@ struct Tr64Io {
     const double* eps;              // the Sinkhorn divergence (non-null): the regularisation strengths [B], with `iters` sweeps,
     int iters;                      //   against the same targets; its certificates behind the total: col_err [H][B], self_err [H][B][2]
     double *col_err, *self_err;
+    int match_kind;                 // the matching losses (TR_LOSS_MATCH, TR_LOSS_CHAMFER_MATCH; else 0) against the same targets:
+    double match_weight;            //   the mix's weight; the caller's pairs [H][B][N] (nullable: the kernel's own optimum); behind
+    const int* match_in;            //   the margins the costs [H][B][2] and the optimum's partners [H][B][N]
+    double* cost;
+    int* match_out;
 };
+
+// the matching kernel's arguments for a chunk: p, the seed and its padding are the chunk's, everything else the batch's (b_off)
+Ka64Args tr64_match_args(const Tr64Ws& k, const Tr64Io& io, int b0, int bc, int N, int B, int H, double scale, double keep) {
+    Ka64Args a{};
+    const size_t pn = (size_t)bc * N;
+    a.cp = tr_cloud_pair((size_t)N * 3, pn * 3, io.nums, io.targets, io.tnums, H, N, io.M);
+    a.pred = k.tape.state + pn * 3;
+    a.b_off = b0; a.B = B;
+    a.scale = scale; a.keep = keep;
+    a.match_in = io.match_in;
+    a.grad = k.rev.g_state; a.terms = io.terms; a.match_pq = io.match_out; a.cost = io.cost;
+    return a;
+}
 
 // forward with tape, loss, reverse pass with weight gradients of the samples [b0, b0 + bc): launches and the state gradient's copy
 int tr64_chunk(drp_ctx* c, const Tr64Ws& k, const Tr64Io& io, int b0, int bc, int N, int B, int H, double* grad_state_out) {
@@ -322,6 +353,10 @@ int tr64_chunk(drp_ctx* c, const Tr64Ws& k, const Tr64Io& io, int b0, int bc, in
         a.grad = k.rev.g_state; a.terms = io.terms; a.col_err = io.col_err; a.self_err = io.self_err;
         hipLaunchKernelGGL(kd64_sweeps, dim3(bc, H, 3), dim3(KT_THREADS), 0, st, a);
         hipLaunchKernelGGL(kd64_combine, dim3(bc, H), dim3(KD_COMBINE_THREADS), 0, st, a);
+    } else if (io.match_kind == TR_LOSS_MATCH) {
+        // the same slot of the stream and the same outputs: the assignment solved here in double on the tape's own double states
+        // (k_match_f64.h), the term and the seed on io.match_in's pairs where the caller gave them
+        CHK(ka64_run(c, dim3(bc, H), tr64_match_args(k, io, b0, bc, N, B, H, 1.0 / ((double)H * (double)B), 0.0)));
     } else if (io.M == 0) {
         hipLaunchKernelGGL(kt64_mse, dim3(bc, H), dim3(256), 0, st, k.tape.state, io.states, io.nums, b0, bc, B, N, H, io.terms, k.rev.g_state);
     } else {
@@ -334,6 +369,10 @@ int tr64_chunk(drp_ctx* c, const Tr64Ws& k, const Tr64Io& io, int b0, int bc, in
         a.scale = 1.0 / ((double)H * (double)B);
         a.grad = k.rev.g_state; a.terms = io.terms; a.margin = io.margin;
         hipLaunchKernelGGL((kc64_chamfer<true>), dim3(bc, H), dim3(KC64_THREADS), 0, st, a);
+        // the mix: behind a Chamfer-only step's terms and seed the matching kernel turns each element into (1 - w) x it + w x its
+        // own share, in double: one writer per element, stream order (the fp32 trainer's scheme)
+        if (io.match_kind == TR_LOSS_CHAMFER_MATCH)
+            CHK(ka64_run(c, dim3(bc, H), tr64_match_args(k, io, b0, bc, N, B, H, a.scale * io.match_weight, 1.0 - io.match_weight)));
     }
     HIPCHK(c, hipMemsetAsync(k.wg.acc, 0, (size_t)bc * W_TOTAL * sizeof(double), st));
     F64Wgrad wg = k.wg;
@@ -398,23 +437,42 @@ int drp_gd_grad_f64(drp_ctx* c, const float* s0, const float* attr, const float*
 }
 
 namespace {
+// what drp_train_step_loss refuses of a matching loss's sizes and weight
+int check_match_loss(drp_ctx* c, const TrLoss& lk, int N) {
+    if (N > KA_MAX_POINTS || lk.M > KA_MAX_POINTS)
+        return fail(c, DRP_EINVAL, "a matching loss takes clouds of 1..%d points: N=%d M=%d", KA_MAX_POINTS, N, lk.M);
+    if (lk.kind == TR_LOSS_CHAMFER_MATCH && !(lk.match_weight > 0.0 && lk.match_weight < 1.0))
+        return fail(c, DRP_EINVAL, "match_weight %g outside (0, 1)", lk.match_weight);
+    return DRP_OK;
+}
 // drp_train_grad_f64, drp_train_grad_f64_actions and drp_train_grad_f64_untracked: one body; `impulses` is states_delta
 // [B][H][N][3], or with `actions` the pushes [B][H][4]; the loss kind and the targets in `lk` (capi_train.h: TrLoss) -- the tracked
 // MSE, the Chamfer loss against untracked target clouds (k_chamfer_f64.h), or the Sinkhorn divergence to them
-// (k_divergence_f64.h); the matching kinds and the transport loss have no yardstick
+// (k_divergence_f64.h), or the matching kinds (k_match_f64.h: the matching term, or its mix with the Chamfer term); the transport
+// loss has no yardstick
 int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, bool actions, const float* attrs,
                         const int32_t* particle_nums, const float* particle_dens, int B, int N, int n_rollout, const TrLoss& lk,
                         double* loss_out, double* loss_terms_out, double* grad_out, double* grad_state_out) {
     CHK(need(c, true, actions, false));
-    if (lk.match() || lk.transport()) return fail(c, DRP_EINVAL, "no float64 yardstick for loss kind %d", lk.kind);
+    if (lk.transport()) return fail(c, DRP_EINVAL, "no float64 yardstick for loss kind %d", lk.kind);
     CHK(check_bn(c, B, N));
     if (!states || !impulses || !attrs || !particle_nums || !particle_dens) return fail(c, DRP_EINVAL, "null argument");
     if (n_rollout < 1 || n_rollout > 64) return fail(c, DRP_EINVAL, "bad n_rollout=%d", n_rollout);
     CHK(check_particle_nums(c, particle_nums, B, N));
-    if (lk.chamfer()) {
-        CHK(check_target_clouds(c, lk, KC64_MAX_POINTS, "shape"));
+    if (lk.chamfer() || lk.match()) {
+        CHK(check_target_clouds(c, lk, lk.chamfer() ? KC64_MAX_POINTS : KA_MAX_POINTS, "shape"));
+        if (lk.match()) CHK(check_match_loss(c, lk, N));
         CHK(check_target_nums(c, lk, B, n_rollout));
     }
+    if (lk.match() && lk.match_in)          // [H][B][N]: drp_train_step_loss's match_out layout
+        for (int t = 0; t < n_rollout; ++t)
+            for (int b = 0; b < B; ++b) {
+                int row;
+                const int why = check_matching(lk.match_in + ((size_t)t * B + b) * N, particle_nums[b],
+                                               lk.target_nums[(size_t)b * n_rollout + t], N, &row);
+                if (why != MATCH_OK)
+                    return fail(c, DRP_EINVAL, "match_in: sample %d step %d row %d %s", b, t, row, matching_fault(why));
+            }
     if (lk.divergence()) {
         CHK(check_target_clouds(c, lk, KT_MAX_POINTS, "shape"));
         if (N > KT_MAX_POINTS) return fail(c, DRP_EINVAL, "the Sinkhorn divergence takes at most %d points per cloud (N=%d)", KT_MAX_POINTS, N);
@@ -434,9 +492,11 @@ int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, 
     CHK(f64_size_chunks(c, B, N, ((size_t)1 << 24) / ((size_t)N * DRP_K), bytes_of, &Bc));
     k.carve(c->grad64_ws.p, Bc, (size_t)N, (size_t)H, div);
     // the whole batch's inputs in one upload (train_host.h: tr64_layout): states | impulses | attrs[:, 0] | densities | particle
-    // counts [| target clouds | their counts] [| eps], then the results: terms | total [| margins] [| col_err | self_err]
-    const int M = lk.chamfer() || div ? lk.M : 0;
-    const Tr64Arena lay = tr64_layout(B, H, N, M, actions, div);
+    // counts [| target clouds | their counts] [| eps] [| the caller's matching], then the results: terms | total [| margins]
+    // [| col_err | self_err] [| the matching's costs | its optimum's partners]
+    const bool match = lk.match();
+    const int M = lk.chamfer() || div || match ? lk.M : 0;
+    const Tr64Arena lay = tr64_layout(B, H, N, M, actions, div, match && lk.match_in != nullptr);
     std::vector<float> host(lay.words);
     memcpy(host.data() + lay.states, states, (lay.sdelta - lay.states) * sizeof(float));
     memcpy(host.data() + lay.sdelta, impulses, (lay.attr - lay.sdelta) * sizeof(float));
@@ -448,9 +508,12 @@ int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, 
         memcpy(host.data() + lay.tnums, lk.target_nums, (size_t)B * H * sizeof(int32_t));
     }
     if (div) memcpy(host.data() + lay.eps, lk.eps, (size_t)B * sizeof(double));
+    if (match && lk.match_in) memcpy(host.data() + lay.match_in, lk.match_in, (size_t)H * B * N * sizeof(int32_t));
     const size_t n_terms = (size_t)H * B;
+    // the matching kinds: behind the margins the costs [H][B][2], then the optimum's partners [H][B][N] (ints, two to a double)
+    const size_t n_match = match ? 2 * n_terms + (n_terms * N + 1) / 2 : 0;
     Tr64Io io{};
-    CHK(f64_upload_batch(c, host, n_terms + (size_t)W_TOTAL + (div ? 3 * n_terms : M > 0 ? n_terms : 0), &io.terms));
+    CHK(f64_upload_batch(c, host, n_terms + (size_t)W_TOTAL + (div ? 3 * n_terms : M > 0 ? n_terms : 0) + n_match, &io.terms));
     io.states = ptr<float>(c->grad64_io); io.sdelta = io.states + lay.sdelta; io.attr = io.states + lay.attr; io.dens = io.states + lay.dens;
     io.nums = reinterpret_cast<const int*>(io.states + lay.nums);
     io.actions = actions;
@@ -465,6 +528,12 @@ int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, 
         } else {
             io.margin = io.total + W_TOTAL;
         }
+        if (match) {
+            io.match_kind = lk.kind; io.match_weight = lk.match_weight;
+            io.match_in = lk.match_in ? reinterpret_cast<const int*>(io.states + lay.match_in) : nullptr;
+            io.cost = io.margin + n_terms;
+            io.match_out = reinterpret_cast<int*>(io.cost + 2 * n_terms);
+        }
     }
     HIPCHK(c, hipMemsetAsync(io.total, 0, (size_t)W_TOTAL * sizeof(double), c->stream));
     for (int b0 = 0; b0 < B; b0 += (int)Bc)
@@ -472,7 +541,9 @@ int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, 
     std::vector<double> terms(n_terms);
     CHK(d2h(c, terms.data(), io.terms, n_terms * sizeof(double)));
     if (grad_out) CHK(d2h(c, grad_out, io.total, (size_t)W_TOTAL * sizeof(double)));
-    if (io.margin && lk.margin_out) CHK(d2h(c, lk.margin_out, io.margin, n_terms * sizeof(double)));
+    if (io.margin && lk.margin_out && lk.chamfer()) CHK(d2h(c, lk.margin_out, io.margin, n_terms * sizeof(double)));
+    if (match && lk.cost_out) CHK(d2h(c, lk.cost_out, io.cost, 2 * n_terms * sizeof(double)));
+    if (match && lk.match_out) CHK(d2h(c, lk.match_out, io.match_out, n_terms * N * sizeof(int32_t)));
     if (div && lk.col_err_out) CHK(d2h(c, lk.col_err_out, io.col_err, n_terms * sizeof(double)));
     if (div && lk.self_err_out) CHK(d2h(c, lk.self_err_out, io.self_err, 2 * n_terms * sizeof(double)));
     CHK(guarded_wait(c, nullptr));          // (the upload's host block lives until here)

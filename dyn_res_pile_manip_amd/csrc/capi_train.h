@@ -12,7 +12,7 @@ const int* tr_nums(const drp_ctx* c, const TrArena& lay) {
 // what seeds the reverse pass: the tracked loss (kt_mse_grad against the given next states) or the Chamfer loss against
 // untracked target clouds (k_chamfer.h), the one-to-one matching loss against them (k_match.h), or the two mixed; the targets as
 // the HOST gave them (the entry point stages them behind the batch).  The kinds beyond the MSE are include/drp.h's DRP_LOSS_*.
-// The float64 yardstick (capi_grad_f64.h) reads the same description; it has the MSE and the Chamfer loss.
+// The float64 yardstick (capi_grad_f64.h) reads the same description; it has every kind but the transport loss.
 // TR_LOSS_TRANSPORT (k_transport.h) is internal: drp_train_step_transport's, no loss_kind of drp_train_step_loss; so is
 // TR_LOSS_DIVERGENCE (k_divergence.h), drp_train_step_divergence's
 enum { TR_LOSS_MSE = 0, TR_LOSS_CHAMFER = DRP_LOSS_CHAMFER, TR_LOSS_MATCH = DRP_LOSS_MATCH, TR_LOSS_CHAMFER_MATCH = DRP_LOSS_CHAMFER_MATCH,
@@ -25,6 +25,8 @@ struct TrLoss {
     int M = 0;
     double match_weight = 0.0;              // TR_LOSS_CHAMFER_MATCH: (1 - w) Chamfer + w matching
     int32_t* match_out = nullptr;           // the caller's [H][B][N], nullable: every predicted row's partner (kinds with a matching)
+    const int32_t* match_in = nullptr;      // float64 only: the caller's [H][B][N], nullable: the pairs of the term and the seed
+    double* cost_out = nullptr;             // float64 only: the caller's [H][B][2], nullable (ka64_match's costs)
     double* margin_out = nullptr;           // float64 only: the caller's [H][B], nullable (kc64_chamfer's arg-min margins)
     const double* eps = nullptr;            // TR_LOSS_TRANSPORT, _DIVERGENCE: the caller's [B], the regularisation of every step of a sample
     int iters = 0;                          // TR_LOSS_TRANSPORT, _DIVERGENCE: the sweeps

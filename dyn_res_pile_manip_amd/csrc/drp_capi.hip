@@ -51,6 +51,7 @@
 #include "k_chamfer.h"
 #include "k_chamfer_f64.h"
 #include "k_match.h"
+#include "k_match_f64.h"
 #include "k_transport.h"
 #include "k_divergence.h"
 #include "k_divergence_f64.h"
@@ -80,6 +81,7 @@ extern "C" {
 #include "capi_f64.h"
 #include "capi_grad_f64.h"
 #include "capi_divergence_f64.h"
+#include "capi_match_f64.h"
 #include "capi_debug.h"
 
 }  // extern "C"

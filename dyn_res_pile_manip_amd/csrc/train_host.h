@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 // the batch as uploaded (drp_train_step): states [B][H+1][N][3] | impulses [B][H][N][3] | attributes [B][H+1][N] | densities [B]
 // | particle counts [B] (ints), every block 16-byte aligned; drp_train_step_untracked (M > 0): behind them the target clouds
@@ -42,9 +43,10 @@ inline TrArena tr_layout(int B, int H, int N, int M = 0, bool actions = false, b
 // [B] (ints); drp_train_grad_f64_untracked (M > 0): behind them the target clouds [B][H][M][3] | their counts [B][H] (ints) --
 // with M = 0 the layout, and so the one copy, is drp_train_grad_f64's; drp_train_grad_f64_divergence (`eps`): behind everything
 // the regularisation strengths [B] (doubles, two words each) on the next even word -- the vector's base is 256-byte aligned on
-// the device, so an even word is an 8-byte boundary -- and nothing ahead of them moves
-struct Tr64Arena { size_t states, sdelta, attr, dens, nums, targets, tnums, words, eps; };
-inline Tr64Arena tr64_layout(int B, int H, int N, int M = 0, bool actions = false, bool eps = false) {
+// the device, so an even word is an 8-byte boundary -- and nothing ahead of them moves; drp_train_grad_f64_match with a matching
+// of the caller's (`match_in`): behind everything the partners [H][B][N] (ints), nothing ahead of them moving either
+struct Tr64Arena { size_t states, sdelta, attr, dens, nums, targets, tnums, words, eps, match_in; };
+inline Tr64Arena tr64_layout(int B, int H, int N, int M = 0, bool actions = false, bool eps = false, bool match_in = false) {
     Tr64Arena a{};
     a.states = 0;
     a.sdelta = a.states + (size_t)B * (H + 1) * N * 3;
@@ -60,6 +62,10 @@ inline Tr64Arena tr64_layout(int B, int H, int N, int M = 0, bool actions = fals
     if (eps) {
         a.eps = (a.words + 1) & ~(size_t)1;
         a.words = a.eps + 2 * (size_t)B;
+    }
+    if (match_in) {
+        a.match_in = a.words;
+        a.words = a.match_in + (size_t)H * B * N;
     }
     return a;
 }
@@ -153,6 +159,59 @@ inline Div64Layout divergence64_layout(int B, int N, int M) {
     a.bytes = up(a.gsum + 2 * bn * 3 * sizeof(double));
     return a;
 }
+// drp_cloud_match_f64: p is the caller's doubles, so the buffer is its own too.  Up, in one copy: p [B][N][3] (doubles) | q [B][M][3]
+// | n_p [B] | n_q [B] | with `match_in` the caller's partners [B][N] (ints); down, behind `in_bytes`: terms [B] | gradient [B][N][3]
+// (doubles) | partner of every row of p [B][N] | of q [B][M] (ints) | duals [B][N + M] | costs [B][2] (doubles) (out[0..6)).  Every
+// block 16-byte aligned
+struct Match64Layout { size_t pts_p, pts_q, n_p, n_q, match_in, in_bytes, out[6], out_bytes[6], bytes; };
+inline Match64Layout match64_layout(int B, int N, int M, bool match_in) {
+    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t bn = (size_t)B * N, bm = (size_t)B * M;
+    Match64Layout a{};
+    a.pts_p = 0;
+    a.pts_q = up(a.pts_p + bn * 3 * sizeof(double));
+    a.n_p = up(a.pts_q + bm * 3 * sizeof(float));
+    a.n_q = up(a.n_p + (size_t)B * sizeof(int32_t));
+    a.match_in = up(a.n_q + (size_t)B * sizeof(int32_t));
+    a.bytes = a.in_bytes = match_in ? up(a.match_in + bn * sizeof(int32_t)) : a.match_in;
+    const size_t ob[6] = {(size_t)B * sizeof(double), bn * 3 * sizeof(double), bn * sizeof(int32_t), bm * sizeof(int32_t),
+                          (bn + bm) * sizeof(double), (size_t)B * 2 * sizeof(double)};
+    for (int k = 0; k < 6; ++k) {
+        a.out[k] = a.bytes;
+        a.out_bytes[k] = ob[k];
+        a.bytes = up(a.bytes + ob[k]);
+    }
+    return a;
+}
+// A matching given by the caller (drp_cloud_match_f64, drp_train_grad_f64_match): match [N] has the partner in q of every row of p,
+// or -1.  It must be a one-to-one matching of exactly r = min(n_p, n_q) of p's n_p real rows into 0..n_q-1 with no partner on a
+// padded row -> MATCH_OK, or what is wrong with *row_out, the first row at fault (MATCH_FEW: the first real row without a partner)
+enum { MATCH_OK = 0, MATCH_RANGE = 1, MATCH_DUP = 2, MATCH_PAD = 3, MATCH_FEW = 4 };
+inline int check_matching(const int32_t* match, int n_p, int n_q, int N, int* row_out) {
+    std::vector<char> taken((size_t)(n_q > 0 ? n_q : 0), 0);
+    const int r = n_p < n_q ? n_p : n_q;
+    int pairs = 0, first_free = -1;
+    for (int i = 0; i < N; ++i) {
+        const int32_t j = match[i];
+        *row_out = i;
+        if (j < -1 || j >= n_q) return MATCH_RANGE;
+        if (j < 0) {
+            if (i < n_p && first_free < 0) first_free = i;
+            continue;
+        }
+        if (i >= n_p) return MATCH_PAD;
+        if (taken[(size_t)j]) return MATCH_DUP;
+        taken[(size_t)j] = 1;
+        ++pairs;
+    }
+    *row_out = first_free;
+    return pairs == r ? MATCH_OK : MATCH_FEW;
+}
+inline const char* matching_fault(int why) {
+    return why == MATCH_RANGE ? "has a partner out of range" : why == MATCH_DUP ? "has a partner another row has"
+         : why == MATCH_PAD ? "is padding and has a partner" : "has no partner: too few pairs";
+}
+
 // drp_train_step_divergence's device doubles (c->tr_loss), in doubles: terms [H][B] | col_err [H][B] | self_err [H][B][2] | the
 // value sums [3][H][B] | the gradient sums [2][H][B][N][3]
 struct TrDivLoss { size_t terms, col_err, self_err, vals, gsum, count; };

@@ -1048,6 +1048,37 @@ class Engine(object):
             out['self_err'] = self_err
         return out
 
+    def cloud_match_f64(self, p, q, n_p=None, n_q=None, match_in=None, want_grad=False, want_match=False, want_dual=False):
+        """cloud_match with nothing in fp32, on the device (include/drp.h: drp_cloud_match_f64): p is taken as float64 [B, N, 3]
+        -- every bit of it enters the costs, as the float64 tape's predicted state does in train_grad_f64_match -- q as float32
+        widened exactly; the assignment is solved on double costs -> cloud_match's dict with 'grad' as float64, plus 'cost' [B]
+        (sum of the squared distances over the pairs the term used) and 'opt_cost' [B] (over the optimum's pairs).  match_in
+        [B, N] (every row of p's partner, -1 for none): 'match' and 'grad' are taken on these pairs; 'match_pq', 'match_qp', 'u',
+        'v' and 'opt_cost' are the solver's own optimum all the same, and cost >= opt_cost says how far from it the given pairs
+        are.  The same limits (1024 points per cloud) and one-shot contract."""
+        p64, q = _f64(p), _f32(q)
+        if p64.ndim == 2 and q.ndim == 2:
+            p64, q = p64[None], q[None]
+        _, q, n_p, n_q, B, N, M = self._cloud_pair(np.empty(p64.shape, np.float32), q, n_p, n_q)     # (the shapes' checks)
+        if match_in is not None:
+            match_in = _i32(match_in).reshape(B, N)
+        terms = np.empty((B,), np.float64)
+        grad = np.empty((B, N, 3), np.float64) if want_grad else None
+        m_pq = np.empty((B, N), np.int32) if want_match else None
+        m_qp = np.empty((B, M), np.int32) if want_match else None
+        dual = np.empty((B, N + M), np.float64) if want_dual else None
+        cost = np.empty((B, 2), np.float64)
+        self._ck(self.lib.drp_cloud_match_f64(self.h, _dp(p64), _ip(n_p), _fp(q), _ip(n_q), B, N, M, _opt(_ip, match_in), _dp(terms),
+                                              _opt(_dp, grad), _opt(_ip, m_pq), _opt(_ip, m_qp), _opt(_dp, dual), _dp(cost)))
+        out = {'match': terms, 'r': np.minimum(n_p, n_q), 'cost': cost[:, 0].copy(), 'opt_cost': cost[:, 1].copy()}
+        if want_grad:
+            out['grad'] = grad
+        if want_match:
+            out['match_pq'], out['match_qp'] = m_pq, m_qp
+        if want_dual:
+            out['u'], out['v'] = dual[:, :N].copy(), dual[:, N:].copy()
+        return out
+
     # ---- the float64 yardstick of the trainer's gradients (include/drp.h: drp_train_grad_f64) ------------------------
     def _train_grad64(self, states, states_delta, actions, attrs, particle_nums, particle_dens, targets, target_nums, want_state):
         """One float64 trainer call -> (loss, terms [H, B], gradient blob, margin [H, B] or None, state gradient or None).  The C
@@ -1126,8 +1157,43 @@ class Engine(object):
                                                         _dp(grad), _opt(_dp, gs), _opt(_dp, col_err), _opt(_dp, self_err)))
         return (loss.value, terms, grad) + ((gs,) if want_state else ()) + ((col_err, self_err) if want_err else ())
 
+    def train_grad_f64_match(self, states, states_delta, attrs, particle_nums, particle_dens, targets, target_nums, loss='match',
+                             match_weight=0.5, actions=None, match_in=None, want_state=False, want_info=False):
+        """train_grad_f64_untracked with a matching loss in place of the Chamfer loss: what train_step_loss(mode='grad') computes
+        for loss 'match' or 'chamfer+match' (match_weight: the mix's), in float64 on the device (include/drp.h:
+        drp_train_grad_f64_match).  actions [B, n_rollout, 4] in place of states_delta (then ignored, may be None).  match_in
+        [n_rollout, B, N] (train_step_loss's match): every term and the seed of the reverse pass are taken on these pairs, so that
+        the difference from the fp32 gradient is arithmetic on the same pairs; None: on the float64 side's own optimum, solved on
+        its double prediction -> (loss, loss_terms [n_rollout, B], gradient blob [38403][, d loss / d every step's predicted state
+        [B, n_rollout, N, 3]][, info = {'match' [n_rollout, B, N]: the float64 optimum's partners, 'cost', 'opt_cost'
+        [n_rollout, B]: the sum of squared distances over the pairs used and over the optimum's, 'chamfer_margin' [n_rollout, B]:
+        the mix's Chamfer arg-min margins, None for 'match'}]).  The same one-shot contract."""
+        if loss not in L.MATCH_LOSSES:
+            raise ValueError('loss must be one of %s' % (L.MATCH_LOSSES,))
+        assert targets is not None and target_nums is not None
+        by_actions = actions is not None
+        keep, (B, N, H, M), (ps, pi, pa, pn, pd, pt, ptn) = self._train_batch(
+            states, _f32(actions) if by_actions else states_delta, attrs, particle_nums, particle_dens, targets, target_nums,
+            by_actions, False)
+        if match_in is not None:
+            match_in = _i32(match_in).reshape(max(H, 0), B, N)
+        out = ctypes.c_double()
+        terms = np.empty((max(H, 0), B), np.float64)
+        grad = np.empty((L.DRP_N_WEIGHTS,), np.float64)
+        gs = np.empty((B, max(H, 0), N, 3), np.float64) if want_state else None
+        match = np.full((max(H, 0), B, N), -1, np.int32) if want_info else None
+        cost = np.empty((max(H, 0), B, 2), np.float64) if want_info else None
+        margin = np.empty((max(H, 0), B), np.float64) if (want_info and loss != 'match') else None
+        self._ck(self.lib.drp_train_grad_f64_match(self.h, ps, None if by_actions else pi, pi if by_actions else None, pa, pn, pd,
+                                                   B, N, H, pt, ptn, M, L.LOSS_KINDS[loss], float(match_weight),
+                                                   _opt(_ip, match_in), ctypes.byref(out), _dp(terms), _dp(grad), _opt(_dp, gs),
+                                                   _opt(_ip, match), _opt(_dp, cost), _opt(_dp, margin)))
+        info = {'match': match, 'cost': cost[..., 0].copy(), 'opt_cost': cost[..., 1].copy(),
+                'chamfer_margin': margin} if want_info else None
+        return (out.value, terms, grad) + ((gs,) if want_state else ()) + ((info,) if want_info else ())
+
     def train_gradient_probe(self, states, states_delta, attrs, particle_nums, particle_dens, actions=None, targets=None,
-                             target_nums=None, eps=None, iters=None):
+                             target_nums=None, eps=None, iters=None, loss=None, match_weight=0.5):
         """The gradients the trainer consumes, held against float64: train_step(mode='grad', want_grad=True) on whatever tape the
         selection gives, then train_grad_f64 on the same batch -> {'tensors': {state_dict key: {'max_abs_err', 'max_abs_ref',
         'rel' = err / max(ref, 1e-300)}}, 'worst': the key of the largest rel, 'rel': that rel, 'loss32', 'loss64', 'loss_diff',
@@ -1144,14 +1210,29 @@ class Engine(object):
         number) and `iters` given beside the targets the loss is the Sinkhorn divergence to them: the pair is
         train_step_divergence(mode='grad') and train_grad_f64_divergence, and the dict has 'loss_kind': 'sinkhorn', 'col_err' and
         'self_err' -- the float64 side's largest certificates over the batch -- in place of 'min_margin'.  The float64 side forms
-        its own plans from its own predicted states."""
+        its own plans from its own predicted states.  With `loss` 'match' or 'chamfer+match' (match_weight: the mix's) beside
+        the targets the pair is train_step_loss(mode='grad', want_match=True) and train_grad_f64_match(match_in=the fp32 side's
+        partners): 'rel' and 'tensors' are then ARITHMETIC error on the same pairs, whatever the fp32 tape's drift did to the
+        assignment.  What it did is reported beside them, from the same float64 call, which solves the assignment on its own
+        double prediction all the same: 'loss_kind'; 'flipped', the number of (step, sample) problems whose float64 optimum
+        differs from the fp32 side's partners, and 'rows_flipped', the rows that differ; 'cost_gap', the largest (cost - opt_cost)
+        / opt_cost -- how far from optimal, in double, the fp32 side's matching is; for the mix 'min_margin' as for Chamfer.  Only
+        where flipped > 0, a second float64 call on its own matching gives 'rel_own': what the disagreement costs in the
+        gradient.  loss=None is the call without these two keywords."""
         from .weights import STATE_DICT_KEYS
         assert (targets is None) == (target_nums is None)
         assert (eps is None) == (iters is None) and (eps is None or targets is not None)
+        if loss is not None and (loss not in L.MATCH_LOSSES or targets is None or eps is not None):
+            raise ValueError('loss= takes one of %s, with targets and without eps' % (L.MATCH_LOSSES,))
+        matching = loss is not None
         sinkhorn = eps is not None
-        chamfer = targets is not None and not sinkhorn
+        chamfer = targets is not None and not sinkhorn and not matching
         self.dispatch_reset()
-        if sinkhorn:
+        if matching:
+            sd = None if actions is not None else states_delta
+            loss32, g32, match32 = self._train_step32(states, sd, actions, attrs, particle_nums, particle_dens, targets,
+                                                      target_nums, 'grad', True, loss, match_weight, True)
+        elif sinkhorn:
             sd = None if actions is not None else states_delta
             loss32, g32 = self.train_step_divergence(states, attrs, particle_nums, particle_dens, targets, target_nums, eps, iters,
                                                      states_delta=sd, actions=actions, mode='grad', want_grad=True)
@@ -1160,29 +1241,50 @@ class Engine(object):
                                                 target_nums, 'grad', True)
         # the fp32 matrix engine's tape is the only user of k_aggregate_tape (pick_tape_engine: selected, or after a range refusal)
         tape = 'mfma' if 'k_aggregate_tape' in self.last_dispatch() else 'fused'
-        if sinkhorn:
+        if matching:
+            loss64, _, g64, info = self.train_grad_f64_match(states, states_delta, attrs, particle_nums, particle_dens, targets,
+                                                             target_nums, loss, match_weight, actions=actions, match_in=match32,
+                                                             want_info=True)
+        elif sinkhorn:
             loss64, _, g64, col_err, self_err = self.train_grad_f64_divergence(
                 states, states_delta, attrs, particle_nums, particle_dens, targets, target_nums, eps, iters, actions=actions,
                 want_err=True)
         else:
             loss64, _, g64, margin, _ = self._train_grad64(states, states_delta, actions, attrs, particle_nums, particle_dens,
                                                            targets, target_nums, False)
-        tensors, off, worst = {}, 0, None
-        for key, shape in STATE_DICT_KEYS:
-            n = int(np.prod(shape))
-            err = np.abs(g32[off:off + n].astype(np.float64) - g64[off:off + n])
-            err = float(np.where(np.isnan(err), np.inf, err).max())
-            ref = float(np.abs(g64[off:off + n]).max())
-            tensors[key] = {'max_abs_err': err, 'max_abs_ref': ref, 'rel': err / max(ref, 1e-300)}
-            if worst is None or tensors[key]['rel'] > tensors[worst]['rel']:
-                worst = key
-            off += n
+
+        def compare(g64):
+            tensors, off, worst = {}, 0, None
+            for key, shape in STATE_DICT_KEYS:
+                n = int(np.prod(shape))
+                err = np.abs(g32[off:off + n].astype(np.float64) - g64[off:off + n])
+                err = float(np.where(np.isnan(err), np.inf, err).max())
+                ref = float(np.abs(g64[off:off + n]).max())
+                tensors[key] = {'max_abs_err': err, 'max_abs_ref': ref, 'rel': err / max(ref, 1e-300)}
+                if worst is None or tensors[key]['rel'] > tensors[worst]['rel']:
+                    worst = key
+                off += n
+            return tensors, worst
+
+        tensors, worst = compare(g64)
         out = {'tensors': tensors, 'worst': worst, 'rel': tensors[worst]['rel'], 'loss32': loss32, 'loss64': loss64,
                'loss_diff': abs(loss32 - loss64), 'tape': tape}
         if chamfer:
             out['loss_kind'], out['min_margin'] = 'chamfer', float(margin.min())
         if sinkhorn:
             out['loss_kind'], out['col_err'], out['self_err'] = 'sinkhorn', float(col_err.max()), float(self_err.max())
+        if matching:
+            differ = info['match'] != match32
+            out['loss_kind'] = loss
+            out['flipped'], out['rows_flipped'] = int(differ.any(axis=2).sum()), int(differ.sum())
+            out['cost_gap'] = float(((info['cost'] - info['opt_cost']) / np.maximum(info['opt_cost'], 1e-300)).max())
+            if info['chamfer_margin'] is not None:
+                out['min_margin'] = float(info['chamfer_margin'].min())
+            if out['flipped'] > 0:
+                own = self.train_grad_f64_match(states, states_delta, attrs, particle_nums, particle_dens, targets, target_nums,
+                                                loss, match_weight, actions=actions)
+                t_own, w_own = compare(own[2])
+                out['rel_own'] = t_own[w_own]['rel']
         return out
 
     def train_set_lr(self, lr):

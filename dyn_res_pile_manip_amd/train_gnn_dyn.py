@@ -96,7 +96,9 @@ class DeviceAdam(object):
 
 LOSSES = ('mse', 'chamfer')
 # the one-to-one matching loss of Engine.cloud_match and its mix with the Chamfer distance (Engine.train_step_loss): they train as
-# 'chamfer' does, on collate_untracked's batches, but have no float64 yardstick yet, so the probe options refuse them
+# 'chamfer' does, on collate_untracked's batches.  The three older probe options refuse them (their refusals are pinned by
+# tests); their float64 yardstick (Engine.train_grad_f64_match) is reached through an option of its own, match_probe_every /
+# probe_batch_match
 MATCH_LOSSES = ('match', 'chamfer+match')
 # the entropy-regularised transport loss of Engine.cloud_transport (Engine.train_step_transport): fractional masses, so clouds of
 # unequal counts share mass and every real row has a gradient.  It trains as the matching losses do and, like them, has no
@@ -289,6 +291,42 @@ def probe_batch_sinkhorn(model, data, impulses='data', transport_eps_scale=TRANS
                                              iters=int(transport_iters))
 
 
+def probe_batch_match(model, data, impulses='data', loss='match', match_weight=0.5):
+    """Engine.train_gradient_probe with a matching loss (a member of MATCH_LOSSES; match_weight: the mix's) on a
+    collate_untracked batch: train_step_loss(mode='grad') against Engine.train_grad_f64_match on the fp32 side's own partners, so
+    that 'rel' is arithmetic error on the same pairs; the result also has 'loss_kind', 'flipped', 'rows_flipped', 'cost_gap' --
+    what the fp32 tape's drift did to the assignment -- and, only where a partner flipped, 'rel_own'.  Weights, Adam state and
+    iteration count are untouched.  It works on depth_only batches with impulses='actions'.  probe_batch itself still refuses
+    these losses: its refusal is pinned by tests/test_match_host.py and tests/test_gpu_train_match.py."""
+    if loss not in MATCH_LOSSES:
+        raise ValueError('probe_batch_match needs a loss of %s, got %r' % (MATCH_LOSSES, loss))
+    check_loss(loss, match_weight)
+    if impulses not in IMPULSES:
+        raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
+    check_depth_only(data, loss, impulses)
+    states, states_delta, attrs, particle_nums, particle_dens = [data[i] for i in range(5)]
+    if hasattr(model, '_claim'):
+        model._claim()
+    by_actions = impulses == 'actions'
+    return model.engine.train_gradient_probe(_np(states), None if (by_actions or states_delta is None) else _np(states_delta),
+                                             _np(attrs), _np(particle_nums, np.int32), _np(particle_dens),
+                                             actions=batch_actions(data) if by_actions else None, targets=_np(data[6]),
+                                             target_nums=_np(data[7], np.int32), loss=loss, match_weight=float(match_weight))
+
+
+def check_match_probe_option(loss, match_probe_every, grad_probe_every=0, probe_every=0, sinkhorn_probe_every=0):
+    """match_probe_every of train() / main(): the probe schedule of MATCH_LOSSES alone, and no companion of the three other
+    schedules (check_probe_options has refused the two older ones for these losses already)"""
+    if int(match_probe_every) != match_probe_every or match_probe_every < 0:
+        raise ValueError('match_probe_every must be a non-negative integer, got %r' % (match_probe_every,))
+    if match_probe_every > 0:
+        if grad_probe_every > 0 or probe_every > 0 or sinkhorn_probe_every > 0:
+            raise ValueError('give match_probe_every alone, not with grad_probe_every, probe_every or sinkhorn_probe_every')
+        if loss not in MATCH_LOSSES:
+            raise ValueError('match_probe_every needs a loss of %s, got %r: probe_every probes the losses of %s'
+                             % (MATCH_LOSSES, loss, LOSSES))
+
+
 def check_sinkhorn_probe_option(loss, sinkhorn_probe_every, grad_probe_every=0, probe_every=0):
     """sinkhorn_probe_every of train() / main(): the probe schedule of DIVERGENCE_LOSSES alone, and no companion of the two older
     schedules (check_probe_options has refused those for this loss already)"""
@@ -317,7 +355,7 @@ def check_probe_options(loss, grad_probe_every, probe_every):
 
 def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=None, first_epoch=0, grad_probe_every=0,
           loss='mse', impulses='data', probe_every=0, match_weight=0.5, transport_eps_scale=TRANSPORT_EPS_SCALE,
-          transport_iters=TRANSPORT_ITERS, sinkhorn_probe_every=0):
+          transport_iters=TRANSPORT_ITERS, sinkhorn_probe_every=0, match_probe_every=0):
     """train/train_gnn_dyn.py:134-246 without the file I/O: `dataloaders` = {'train': iterable of
     collated batches, 'valid': ...}.  Returns {'best_valid_loss', 'history': [(epoch, phase, rmse)]}.
     ckp(epoch, i, model): called after training batch i when i % ckp_per_iter == 0 (:217-218); first_epoch: the epoch
@@ -336,14 +374,17 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
     DIVERGENCE_LOSSES (probe_batch_sinkhorn with the run's transport_eps_scale and transport_iters); the log line also carries
     col_err and self_err, the float64 side's largest certificates.  It is refused with any other loss and together with either
     older probe option, which keep refusing this loss: folding it into probe_every waits for a change of the tests that pin
-    those refusals."""
+    those refusals.  match_probe_every = k > 0: the same for a loss in MATCH_LOSSES (probe_batch_match with the run's
+    match_weight); the log line also carries flipped and cost_gap -- the problems whose float64 optimum differs from the fp32
+    side's partners, and how far from optimal in double those are -- and, where a partner flipped, rel_own."""
     check_probe_options(loss, grad_probe_every, probe_every)
     check_sinkhorn_probe_option(loss, sinkhorn_probe_every, grad_probe_every, probe_every)
+    check_match_probe_option(loss, match_probe_every, grad_probe_every, probe_every, sinkhorn_probe_every)
     check_loss(loss, match_weight, transport_eps_scale, transport_iters)
     if impulses not in IMPULSES:
         raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
     loss_kind = loss
-    every = grad_probe_every if grad_probe_every > 0 else probe_every if probe_every > 0 else sinkhorn_probe_every
+    every = max(grad_probe_every, probe_every, sinkhorn_probe_every, match_probe_every)     # (at most one of them is given)
     tc = config['train']
     n_rollout = tc['n_rollout']
     assert tc['n_history'] == 1
@@ -358,6 +399,8 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
                 if every > 0 and phase == 'train' and i % every == 0:
                     if sinkhorn_probe_every > 0:
                         pr = probe_batch_sinkhorn(model, data, impulses, transport_eps_scale, transport_iters)
+                    elif match_probe_every > 0:
+                        pr = probe_batch_match(model, data, impulses, loss_kind, match_weight)
                     else:
                         pr = probe_batch(model, data, impulses, loss_kind)
                     history.append((epoch, 'grad_probe', float(pr['rel'])))
@@ -366,6 +409,9 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
                                                                                                   pr['tape'], pr['loss_diff'])
                         if sinkhorn_probe_every > 0:
                             line += ', col_err %.3e, self_err %.3e' % (pr['col_err'], pr['self_err'])
+                        if match_probe_every > 0:
+                            line += ', flipped %d, cost_gap %.3e' % (pr['flipped'], pr['cost_gap'])
+                            line += ', rel_own %.3e' % pr['rel_own'] if 'rel_own' in pr else ''
                         log(line + (', min_margin %.3e' % pr['min_margin'] if loss_kind == 'chamfer' else ''))
                 loss = run_batch(model, optimizer, data, phase, n_rollout, loss=loss_kind, impulses=impulses, match_weight=match_weight,
                                  transport_eps_scale=transport_eps_scale, transport_iters=transport_iters)
@@ -406,7 +452,7 @@ def set_seed(seed):
 
 def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8, n_epoch=None, engine=None, grad_probe_every=0,
          loss=None, impulses=None, probe_every=0, data='particles', target_den_scale=1.0, match_weight=0.5,
-         transport_eps_scale=TRANSPORT_EPS_SCALE, transport_iters=TRANSPORT_ITERS, sinkhorn_probe_every=0):
+         transport_eps_scale=TRANSPORT_EPS_SCALE, transport_iters=TRANSPORT_ITERS, sinkhorn_probe_every=0, match_probe_every=0):
     """The file-level part of train/train_gnn_dyn.py:train() (:45-130, :196-228): seed, the log directory with config.yaml
     and log.txt, the 'train' / 'valid' ParticleDatasets and their DeviceLoaders, a fresh model (torch.nn.Linear's default
     initialisation) or the resumed checkpoint, net_epoch_%d_iter_%d.pth every ckp_per_iter training batches and
@@ -415,7 +461,7 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
     the directory.  loss='chamfer': the recorded episodes' correspondence is dropped (dataset_gnn_dyn.drop_correspondence on
     every sample, seeded by train.random_seed) and the model is trained on the Chamfer distance to the untracked clouds.
     impulses='actions': the engine's camera is set from the dataset's extrinsics and global_scale and every step's impulse comes
-    from the recorded push on the state the step reads (train).  probe_every, sinkhorn_probe_every: train's.
+    from the recorded push on the state the step reads (train).  probe_every, sinkhorn_probe_every, match_probe_every: train's.
     data='depth': the episodes need only their depth PNGs and actions.p (a recorded robot episode): the datasets are
     DepthDatasets (every frame of a window sampled from its depth image on the device, the later frames at target_den_scale
     times the state's density), which implies loss='chamfer' and impulses='actions'; a contradicting value is refused.  loss /
@@ -430,6 +476,7 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
     loss, impulses = resolve_data_options(data, loss, impulses)
     check_probe_options(loss, grad_probe_every, probe_every)
     check_sinkhorn_probe_option(loss, sinkhorn_probe_every, grad_probe_every, probe_every)
+    check_match_probe_option(loss, match_probe_every, grad_probe_every, probe_every, sinkhorn_probe_every)
     check_loss(loss, match_weight, transport_eps_scale, transport_iters)
     tc = config['train']
     resume = tc['particle'].get('resume', {'active': False, 'epoch': 0, 'iter': 0})
@@ -480,7 +527,7 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
                        first_epoch=resume['epoch'] if resume['active'] and resume['epoch'] > 0 else 0,
                        grad_probe_every=grad_probe_every, loss=loss, impulses=impulses, probe_every=probe_every,
                        match_weight=match_weight, transport_eps_scale=transport_eps_scale, transport_iters=transport_iters,
-                       sinkhorn_probe_every=sinkhorn_probe_every)
+                       sinkhorn_probe_every=sinkhorn_probe_every, match_probe_every=match_probe_every)
         for epoch, phase, rmse in result['history']:
             if phase == 'grad_probe':                   # logged when it was taken
                 continue
@@ -509,6 +556,10 @@ def _cli(argv=None):
     ap.add_argument('--sinkhorn-probe-every', type=int, default=0,
                     help='--loss sinkhorn: hold every k-th training batch\'s gradients against the float64 Sinkhorn divergence before '
                          'its update; the log line carries the float64 side\'s largest col_err and self_err (not with the two options above)')
+    ap.add_argument('--match-probe-every', type=int, default=0,
+                    help='--loss match, chamfer+match: hold every k-th training batch\'s gradients against the float64 matching loss on '
+                         'the same pairs before its update; the log line carries the problems whose float64 optimum differs (flipped) '
+                         'and the fp32 matching\'s distance from it (cost_gap) (not with the three options above)')
     ap.add_argument('--data', choices=DATA, default='particles',
                     help='depth: episodes of depth PNGs and actions.p alone; every frame of a window is sampled from its depth '
                          'image on the device.  Implies --loss chamfer --impulses actions')
@@ -545,7 +596,7 @@ def _cli(argv=None):
                      grad_probe_every=a.grad_probe_every, loss=a.loss, impulses=a.impulses, probe_every=a.probe_every,
                      data=a.data, target_den_scale=a.target_den_scale, match_weight=a.match_weight,
                      transport_eps_scale=a.transport_eps_scale, transport_iters=a.transport_iters,
-                     sinkhorn_probe_every=a.sinkhorn_probe_every)
+                     sinkhorn_probe_every=a.sinkhorn_probe_every, match_probe_every=a.match_probe_every)
     print('best valid loss %.6f, checkpoints in %s' % (np.sqrt(result['best_valid_loss']), d))
 
 

@@ -567,7 +567,7 @@ int drp_ptcl_dataset_time(drp_ctx* ctx, float* ms_out);
 /* HIP-event timing of one kernel class on the context's stream.  name: "graph",
  * "node_encode", "edge_encode", "project", "aggregate", "update", "predict", "reward",
  * "mppi", "prop" (the fused propagation-step kernel of DRP_ENGINE_FUSED / _LITE), "loss" (the stand-alone metrics' kernel:
- * drp_cloud_chamfer, drp_cloud_match, drp_cloud_transport, drp_cloud_divergence, drp_cloud_divergence_f64).  drp_probe_read returns total ms and launches since drp_probe_begin. */
+ * drp_cloud_chamfer, drp_cloud_match, drp_cloud_transport, drp_cloud_divergence, drp_cloud_divergence_f64, drp_cloud_match_f64).  drp_probe_read returns total ms and launches since drp_probe_begin. */
 int drp_probe_begin(drp_ctx* ctx, const char* kernel_class);
 int drp_probe_read(drp_ctx* ctx, double* total_ms, long* launches);
 /* Kernel launches inside the timed regions of the "prop" / "prop+work" probe since drp_probe_begin.  drp_probe_read's `launches`
@@ -919,8 +919,8 @@ int drp_cloud_divergence_f64(drp_ctx* ctx, const double* p /*[B][N][3]*/, const 
  * every problem's certificates.  Exactly one of states_delta and actions; of states only step 0 is read.  The same bits from run
  * to run and under any workspace cap.  The one-shot contract is drp_train_grad_f64's: no drp_train_begin; the Adam state, the
  * selected engine, the dispatch marks and the float64 taps are untouched.  Refusals: those of drp_train_grad_f64_untracked, and
- * DRP_EINVAL for N or M above 1024 and for eps / iters as drp_cloud_transport refuses them.  The transport loss and the matching
- * losses have no float64 yardstick. */
+ * DRP_EINVAL for N or M above 1024 and for eps / iters as drp_cloud_transport refuses them.  The matching losses' yardstick is
+ * drp_train_grad_f64_match below; the transport loss has none. */
 int drp_train_grad_f64_divergence(drp_ctx* ctx, const float* states, const float* states_delta /*[B][H][N][3] or NULL*/,
                                   const float* actions /*[B][H][4] or NULL*/, const float* attrs, const int32_t* particle_nums,
                                   const float* particle_dens, int B, int N, int n_rollout,
@@ -928,6 +928,61 @@ int drp_train_grad_f64_divergence(drp_ctx* ctx, const float* states, const float
                                   const double* eps /*[B]*/, int iters, double* loss_out, double* loss_terms_out, double* grad_out,
                                   double* grad_state_out, double* col_err_out /*[H][B], nullable*/,
                                   double* self_err_out /*[H][B][2], nullable*/);
+
+/* ---- the float64 yardstick of the matching losses (csrc/k_match_f64.h).  drp_cloud_match's definition with nothing in fp32: p
+ * is DOUBLE [B][N][3] -- on purpose: the call runs the kernel the trainer's yardstick runs on the float64 tape's predicted state --
+ * q the caller's floats widened where they are loaded; C[i][j] = dx*dx + dy*dy + dz*dz in double, in that order, on double
+ * differences (no fused multiply-add).  The solver is drp_cloud_match's: shortest augmenting paths with duals, rows of the smaller
+ * cloud (p's where the counts are equal) inserted in ascending index, the lowest column index among equal shortest reduced
+ * costs; u, v, shortest distances and reduced costs double; no atomics; every loop counted by r and c alone.  One wavefront per
+ * problem, column j on lane j & 63 whatever the sizes: the bits depend on the two counts and the values alone, not on N, M, B, the
+ * padding or the samples around.
+ *   terms_out [B]       sum_pairs |p_i - q_sigma(i)|^2 / (3 r) on double differences, summed in ascending row index of p
+ *   grad_p_out          2 (p_i - q_sigma(i)) / (3 r) on matched rows, +0.0 exactly on unmatched rows and padding; double
+ *   match_pq_out, match_qp_out   the OPTIMUM's partners, -1 on unmatched rows and padding
+ *   dual_out [B][N+M]   the optimum's duals u then v, 0 on padding and on the larger cloud's unmatched rows
+ *   cost_out [B][2]     sum C over the pairs the term used, then over the optimum's pairs
+ * match_in [B][N] (nullable): a matching given by the caller -- the partner in q of every row of p, -1 for none.  The term and
+ * the gradient are then taken on the caller's pairs; the solver runs all the same and its own optimum goes to match_pq_out,
+ * match_qp_out, dual_out and cost_out[.][1].  With match_in NULL the two costs are equal; otherwise the first is never below the
+ * second.  The one-shot contract of drp_cloud_match: no weights needed, no session ended, the engine, drp_last_dispatch and the
+ * trainer left alone; it counts under the "loss" kernel class of drp_probe_begin.
+ * DRP_EINVAL (the context stays usable): what drp_cloud_match refuses (a null argument -- every output but terms_out is nullable
+ * --, a count outside 1..N or 1..M, N or M outside 1..1024, a real row of p or q that is not finite), and a match_in that is no
+ * one-to-one matching of exactly r = min(n_p, n_q) real rows into 0..n_q-1 or has a partner on a padded row (the message names
+ * sample, step and row). */
+int drp_cloud_match_f64(drp_ctx* ctx, const double* p /*[B][N][3]*/, const int32_t* n_p, const float* q, const int32_t* n_q,
+                        int B, int N, int M, const int32_t* match_in /*[B][N], nullable*/, double* terms_out /*[B]*/,
+                        double* grad_p_out /*[B][N][3], nullable*/, int32_t* match_pq_out /*[B][N], nullable*/,
+                        int32_t* match_qp_out /*[B][M], nullable*/, double* dual_out /*[B][N+M], nullable*/,
+                        double* cost_out /*[B][2], nullable*/);
+
+/* drp_train_grad_f64_untracked with a matching loss of drp_train_step_loss in place of the Chamfer loss: the yardstick of that
+ * call's gradients for loss_kind DRP_LOSS_MATCH and DRP_LOSS_CHAMFER_MATCH (another kind: DRP_EINVAL), row u2.  The term of
+ * (step t, sample b) is drp_cloud_match_f64's / (n_rollout B) between the DOUBLE prediction s_pred_t[b, :n_b] and
+ * targets[b, t, :target_nums[b, t]]; it seeds the reverse pass with that call's gradient, and everything behind the seed is
+ * drp_train_grad_f64's code.  The mix: the float64 Chamfer kernel runs first and leaves a Chamfer-only step's terms and seed, the
+ * matching kernel behind it in the stream turns each element into (1 - w) x it + w x its own share, in double -- one writer
+ * per element, stream order, drp_train_step_loss's scheme.
+ * match_in [n_rollout][B][N] (nullable; drp_train_step_loss's match_out layout): the pairs of every term and seed, as
+ * drp_cloud_match_f64's match_in.  With the fp32 trainer's partners given here, the difference of the two calls' gradients is
+ * arithmetic error on the SAME pairs -- a partner that the fp32 tape's drift of about 1e-6 of a spacing flipped is no part of it.
+ * The assignment is solved in double all the same: match_out [n_rollout][B][N] (nullable) is the float64 side's own optimum,
+ * cost_out [n_rollout][B][2] (nullable) sum C over the pairs used, then over the optimum's -- equal with match_in NULL, the first
+ * never below the second otherwise --, margin_out [n_rollout][B] (nullable; written for the mix only) the Chamfer arg-min margins
+ * of drp_train_grad_f64_untracked.  Exactly one of states_delta and actions; of states only step 0 is read.  The same bits from
+ * run to run and under any workspace cap.  The one-shot contract of drp_train_grad_f64_untracked.  Refusals (DRP_EINVAL, the
+ * context stays usable): those of drp_train_grad_f64_untracked and of drp_train_step_loss -- N or M above 1024, match_weight
+ * outside (0, 1) for the mix (it is read by the mix only) --, another loss_kind, and a match_in as drp_cloud_match_f64 refuses it.
+ * The transport loss has no float64 yardstick. */
+int drp_train_grad_f64_match(drp_ctx* ctx, const float* states, const float* states_delta /*[B][H][N][3] or NULL*/,
+                             const float* actions /*[B][H][4] or NULL*/, const float* attrs, const int32_t* particle_nums,
+                             const float* particle_dens, int B, int N, int n_rollout,
+                             const float* targets /*[B][H][M][3]*/, const int32_t* target_nums /*[B][H]*/, int M, int loss_kind,
+                             double match_weight, const int32_t* match_in /*[H][B][N], nullable*/, double* loss_out,
+                             double* loss_terms_out, double* grad_out, double* grad_state_out,
+                             int32_t* match_out /*[H][B][N], nullable*/, double* cost_out /*[H][B][2], nullable*/,
+                             double* margin_out /*[H][B], nullable*/);
 
 #ifdef __cplusplus
 }

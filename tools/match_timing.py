@@ -7,7 +7,12 @@
 (b) a whole mode='update' step at 4 x 5 x 100 (B x n_rollout x N = M) under 'chamfer', 'match' and 'chamfer+match', interleaved
     on one context: host time of the call (it returns when the step is complete on the device), the median of 6 blocks of 10
     after warm-up, as tools/train_timing.py measures its steps.
-Each measurement runs in a child process of its own under a time limit (a stuck step ends there, and nothing follows it)."""
+Each measurement runs in a child process of its own under a time limit (a stuck step ends there, and nothing follows it).
+
+  python tools/match_timing.py --f64 [output file]  -> profiles/match_f64_timing.txt
+
+(c) the float64 yardstick's kernel (csrc/k_match_f64.h: ka64_match) beside ka_match on the same clouds, p widened exactly, at (a)'s
+    sizes: the same events and counts, the two kernels' launches interleaved.  A yardstick's cost: recorded, no condition."""
 import subprocess
 import sys
 import time
@@ -49,6 +54,31 @@ def kernel_times(n, m):
     eng.close()
     print('%d problems of %d x %d: ka_match %.4f ms (%.4f .. %.4f), kc_chamfer %.4f ms (%.4f .. %.4f): %.1f x'
           % ((PROBLEMS, n, m) + out['ka_match'] + out['kc_chamfer'] + (out['ka_match'][0] / out['kc_chamfer'][0],)), flush=True)
+
+
+def f64_kernel_times(n, m):
+    from dyn_res_pile_manip_amd.engine import Engine
+    eng = Engine(0)
+    p, q = clouds(n, m, 7 * n + m)
+    p64 = p.astype(np.float64)                                      # widened exactly: the two kernels solve the same clouds
+    calls = (('ka_match', lambda: eng.cloud_match(p, q, want_grad=True)),
+             ('ka64_match', lambda: eng.cloud_match_f64(p64, q, want_grad=True)))
+    for _, call in calls:
+        for _ in range(3):
+            call()
+    took = dict((name, []) for name, _ in calls)
+    for _ in range(21):                                             # interleaved
+        for name, call in calls:
+            eng.probe_begin('loss')
+            call()
+            ms, launches = eng.probe_read()
+            assert launches == 1
+            took[name].append(ms)
+    eng.probe_begin(None)
+    eng.close()
+    out = dict((k, (float(np.median(v)), min(v), max(v))) for k, v in took.items())
+    print('%d problems of %d x %d: ka64_match %.4f ms (%.4f .. %.4f), ka_match %.4f ms (%.4f .. %.4f): %.2f x'
+          % ((PROBLEMS, n, m) + out['ka64_match'] + out['ka_match'] + (out['ka64_match'][0] / out['ka_match'][0],)), flush=True)
 
 
 def update_times():
@@ -96,13 +126,22 @@ def update_times():
 if __name__ == '__main__':
     if len(sys.argv) > 1 and sys.argv[1] == '--kernel':
         kernel_times(int(sys.argv[2]), int(sys.argv[3]))
+    elif len(sys.argv) > 1 and sys.argv[1] == '--f64-kernel':
+        f64_kernel_times(int(sys.argv[2]), int(sys.argv[3]))
     elif len(sys.argv) > 1 and sys.argv[1] == '--update':
         update_times()
     else:
-        out = sys.argv[1] if len(sys.argv) > 1 else 'profiles/match_timing.txt'
-        lines = ['tools/match_timing.py: device time of the loss kernels by HIP events (median of 21 launches, min .. max), and host',
-                 'time of whole update steps (median of 6 interleaved blocks of 10); one MI355X', '']
-        jobs = [['--kernel', str(n), str(m)] for n, m in SIZES] + [['--update']]
+        f64 = len(sys.argv) > 1 and sys.argv[1] == '--f64'
+        rest = sys.argv[2:] if f64 else sys.argv[1:]
+        out = rest[0] if rest else ('profiles/match_f64_timing.txt' if f64 else 'profiles/match_timing.txt')
+        if f64:
+            lines = ['tools/match_timing.py --f64: device time of the float64 assignment kernel beside the fp32 one on the same clouds, by',
+                     'HIP events (median of 21 interleaved launches, min .. max); one MI355X', '']
+            jobs = [['--f64-kernel', str(n), str(m)] for n, m in SIZES]
+        else:
+            lines = ['tools/match_timing.py: device time of the loss kernels by HIP events (median of 21 launches, min .. max), and host',
+                     'time of whole update steps (median of 6 interleaved blocks of 10); one MI355X', '']
+            jobs = [['--kernel', str(n), str(m)] for n, m in SIZES] + [['--update']]
         for job in jobs:
             r = subprocess.run(['timeout', '-k', '10', str(STEP_LIMIT_S), sys.executable, __file__] + job, stdout=subprocess.PIPE,
                                stderr=subprocess.STDOUT, universal_newlines=True)

@@ -17,7 +17,9 @@
 // inside a block of exactly its `bytes`, and the trainer's doubles (tr_div_loss_layout) likewise.  Its float64 yardstick: eps [B]
 // (doubles) behind the float64 upload on an even word (tr64_layout with `eps`), nothing ahead of it moved, and
 // drp_cloud_divergence_f64's buffer of its own (divergence64_layout: p as doubles), every block written in full; the finiteness
-// check on double rows.  No device is touched.
+// check on double rows.  The matching losses' float64 yardstick: the caller's partners [H][B][N] behind the float64 upload
+// (tr64_layout with `match_in`), drp_cloud_match_f64's buffer of its own (match64_layout, with and without match_in), and the
+// check of a matching given by the caller (check_matching) on arrays of exactly [N].  No device is touched.
 //
 //   train_host_check layout64 B H N M actions     prints tr64_layout's eight fields (4-byte words) and exits
 #include <cstdio>
@@ -197,6 +199,87 @@ static void stage_divergence64(int B, int N, int M) {
     std::free(io);
 }
 
+// drp_train_grad_f64_match's upload: the caller's partners [H][B][N] (ints) behind everything else, the other blocks where they were
+static void stage64_match(int B, int H, int N, int M, bool actions) {
+    const Tr64Arena lay = tr64_layout(B, H, N, M, actions, false, true), plain = tr64_layout(B, H, N, M, actions);
+    EXPECT(lay.states == plain.states && lay.sdelta == plain.sdelta && lay.attr == plain.attr && lay.dens == plain.dens &&
+           lay.nums == plain.nums && lay.targets == plain.targets && lay.tnums == plain.tnums);
+    EXPECT(lay.match_in == plain.words && lay.words == lay.match_in + (size_t)H * B * N && plain.match_in == 0);
+    std::vector<int32_t> match((size_t)H * B * N, 7);
+    float* host = static_cast<float*>(std::malloc(lay.words * sizeof(float)));
+    std::memset(host, 0xff, lay.words * sizeof(float));
+    std::memcpy(host + lay.match_in, match.data(), match.size() * sizeof(int32_t));
+    const int* as_kernel = reinterpret_cast<const int*>(host + lay.match_in);          // as ka64_match addresses it
+    EXPECT(as_kernel[0] == 7 && as_kernel[((size_t)(H - 1) * B + (B - 1)) * N + (N - 1)] == 7);
+    std::free(host);
+}
+
+// drp_cloud_match_f64's buffer: the inputs (p as doubles, the caller's partners last and optional) staged into a vector of exactly
+// in_bytes, the six blocks that come back written in full inside a block of exactly `bytes`
+static void stage_match64(int B, int N, int M, bool match_in) {
+    const size_t bn = (size_t)B * N, bm = (size_t)B * M;
+    const Match64Layout lay = match64_layout(B, N, M, match_in);
+    const size_t off[] = {lay.pts_p, lay.pts_q, lay.n_p, lay.n_q, lay.match_in, lay.out[0], lay.out[1], lay.out[2], lay.out[3],
+                          lay.out[4], lay.out[5], lay.bytes};
+    const size_t len[] = {bn * 24, bm * 12, (size_t)B * 4, (size_t)B * 4, match_in ? bn * 4 : 0, (size_t)B * 8, bn * 24, bn * 4, bm * 4,
+                          (bn + bm) * 8, (size_t)B * 16};
+    for (int k = 0; k < 11; ++k) {
+        EXPECT(off[k] % 16 == 0);
+        EXPECT(off[k] + len[k] <= off[k + 1] && off[k + 1] - (off[k] + len[k]) < 16);
+        if (k >= 5) EXPECT(lay.out_bytes[k - 5] == len[k]);
+    }
+    EXPECT(lay.pts_p == 0 && lay.out[0] == lay.in_bytes);
+    std::vector<double> p(bn * 3, 1.0);
+    std::vector<float> q(bm * 3, 2.0f);
+    std::vector<int32_t> n_p(B, N), n_q(B, M), match(bn, 3);
+    std::vector<char> stage(lay.in_bytes);
+    std::memcpy(stage.data() + lay.pts_p, p.data(), bn * 3 * sizeof(double));
+    std::memcpy(stage.data() + lay.pts_q, q.data(), bm * 3 * sizeof(float));
+    std::memcpy(stage.data() + lay.n_p, n_p.data(), (size_t)B * sizeof(int32_t));
+    std::memcpy(stage.data() + lay.n_q, n_q.data(), (size_t)B * sizeof(int32_t));
+    if (match_in) std::memcpy(stage.data() + lay.match_in, match.data(), bn * sizeof(int32_t));
+    char* io = static_cast<char*>(std::malloc(lay.bytes));
+    std::memcpy(io, stage.data(), lay.in_bytes);
+    for (int k = 5; k < 11; ++k) std::memset(io + off[k], k, len[k]);          // the kernel's stores, block by block
+    double d; int32_t n;
+    std::memcpy(&d, io + lay.pts_p + (bn * 3 - 1) * 8, 8);
+    EXPECT(d == 1.0);
+    std::memcpy(&n, io + lay.n_q + (size_t)(B - 1) * 4, 4);
+    EXPECT(n == M);
+    if (match_in) {
+        std::memcpy(&n, io + lay.match_in + (bn - 1) * 4, 4);
+        EXPECT(n == 3);
+    }
+    for (int k = 5; k < 11; ++k) EXPECT(io[off[k]] == k && io[off[k] + len[k] - 1] == k);
+    std::free(io);
+}
+
+// a matching given by the caller, on a heap array of exactly [N]: what check_matching accepts and what it refuses, with the row
+static void check_matchings() {
+    const int N = 6;
+    int32_t* m = static_cast<int32_t*>(std::malloc(N * sizeof(int32_t)));
+    int row = -7;
+    auto set = [&](int a, int b, int c, int d, int e, int f) { m[0] = a; m[1] = b; m[2] = c; m[3] = d; m[4] = e; m[5] = f; };
+    set(2, 0, 1, 3, -1, -1);                                     // n_p = 4 rows into n_q = 5: every real row matched
+    EXPECT(check_matching(m, 4, 5, N, &row) == MATCH_OK);
+    set(-1, 0, -1, 1, 2, -1);                                    // n_p = 5 rows, n_q = 3: r = 3 pairs, two real rows left out
+    EXPECT(check_matching(m, 5, 3, N, &row) == MATCH_OK);
+    set(2, 0, 2, 3, -1, -1);                                     // a partner two rows have
+    EXPECT(check_matching(m, 4, 5, N, &row) == MATCH_DUP && row == 2);
+    set(2, 0, 5, 3, -1, -1);                                     // out of range: n_q = 5
+    EXPECT(check_matching(m, 4, 5, N, &row) == MATCH_RANGE && row == 2);
+    set(2, 0, 1, -2, -1, -1);                                    // below -1
+    EXPECT(check_matching(m, 4, 5, N, &row) == MATCH_RANGE && row == 3);
+    set(2, -1, 1, 3, -1, -1);                                    // too few pairs: row 1 has none
+    EXPECT(check_matching(m, 4, 5, N, &row) == MATCH_FEW && row == 1);
+    set(2, 0, 1, 3, -1, 4);                                      // a partner on the last padded row
+    EXPECT(check_matching(m, 4, 5, N, &row) == MATCH_PAD && row == 5);
+    set(0, -1, -1, -1, -1, -1);                                  // one row each
+    EXPECT(check_matching(m, 1, 1, N, &row) == MATCH_OK);
+    EXPECT(check_matching(m, 1, 1, 1, &row) == MATCH_OK);        // N = 1: one element read
+    std::free(m);
+}
+
 // a one-shot's buffer as cloud_begin and the kernel use it (capi_pipeline.h): the inputs copied into a vector of exactly
 // CloudLayout::in_bytes, every output block written in full inside a block of exactly CloudLayout::bytes; len: the n_out blocks'
 // sizes, restated by the caller
@@ -347,6 +430,7 @@ int main(int argc, char** argv) {
             stage(s[0], s[1], s[2], s[3], actions != 0);
             stage64(s[0], s[1], s[2], s[3], actions != 0);
             if (s[3] > 0) stage64_eps(s[0], s[1], s[2], s[3], actions != 0);
+            if (s[3] > 0) stage64_match(s[0], s[1], s[2], s[3], actions != 0);
         }
     stage64(1, 1, 4096, 4096, false);                            // the largest clouds of one (sample, step)
     const int mshapes[][3] = {{1, 1, 1}, {1, 5, 3}, {3, 7, 9}, {2, 65, 64}, {1, 1024, 1024}, {5, 1024, 1}, {4, 300, 257}};
@@ -355,7 +439,10 @@ int main(int argc, char** argv) {
         stage_transport(s[0], s[1], s[2]);
         stage_divergence(s[0], s[1], s[2]);
         stage_divergence64(s[0], s[1], s[2]);
+        stage_match64(s[0], s[1], s[2], false);
+        stage_match64(s[0], s[1], s[2], true);
     }
+    check_matchings();
     const int dshapes[][3] = {{1, 1, 1}, {2, 2, 9}, {4, 5, 100}, {3, 1, 1024}};
     for (const auto& s : dshapes) stage_div_loss(s[0], s[1], s[2]);
     for (const auto& s : shapes)
