@@ -33,6 +33,69 @@ int drp_cloud_divergence(drp_ctx* c, const float* p, const int32_t* n_p, const f
     return cloud_finish(c, k, "kd_sweeps");
 }
 
+// drp_cloud_divergence with a reach and a target mass per sample (k_divergence.h: kd_sweeps_unbalanced; train_host.h:
+// divergence_unbalanced_layout).  The checks are drp_cloud_divergence's, in its order, then the two new arrays'
+int drp_cloud_divergence_unbalanced(drp_ctx* c, const float* p, const int32_t* n_p, const float* q, const int32_t* n_q, int B, int N, int M,
+                                    const double* eps, const double* rho, const double* mass_q, int iters, double* terms_out,
+                                    float* grad_p_out, double* dual_out, double* col_err_out, double* self_err_out,
+                                    double* transported_out) {
+    CHK(cloud_check(c, p, n_p, q, n_q, B, N, M, terms_out, KT_MAX_POINTS, KT_MAX_POINTS, " for a divergence"));
+    CHK(check_transport_params(c, eps, B, iters));
+    CHK(check_reach_params(c, eps, rho, mass_q, B, 1));
+    long bad = first_nonfinite_row(p, n_p, B, N);
+    if (bad >= 0) return fail(c, DRP_EINVAL, "p[%ld][%ld] is not finite", bad / N, bad % N);
+    bad = first_nonfinite_row(q, n_q, B, M);
+    if (bad >= 0) return fail(c, DRP_EINVAL, "q[%ld][%ld] is not finite", bad / M, bad % M);
+    void* const outs[] = {terms_out, grad_p_out, dual_out, col_err_out, self_err_out};
+    const DivUnbalancedLayout lay = divergence_unbalanced_layout(B, N, M);
+    CloudCall k;
+    CHK(cloud_begin(c, k, lay.cloud, outs, p, n_p, q, n_q, B, N, M));
+    // eps | rho | mass_q lie side by side: one staging vector, one copy (read until cloud_finish's wait)
+    std::vector<double> up((size_t)3 * B);
+    memcpy(up.data(), eps, (size_t)B * sizeof(double));
+    memcpy(up.data() + B, rho, (size_t)B * sizeof(double));
+    memcpy(up.data() + 2 * (size_t)B, mass_q, (size_t)B * sizeof(double));
+    if (hipMemcpyAsync(k.io + lay.eps, up.data(), up.size() * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+        (void)drp_sync(c);                                  // (cloud_begin's staging vector is still being read)
+        return fail(c, DRP_EHIP, "hipMemcpyAsync of eps, rho and mass_q");
+    }
+    KdArgs a{};
+    a.cp = k.cp; a.pred = k.p_dev; a.eps = reinterpret_cast<double*>(k.io + lay.eps); a.iters = iters; a.scale = 1.0;
+    a.rho = reinterpret_cast<double*>(k.io + lay.rho); a.mass_q = reinterpret_cast<double*>(k.io + lay.mass_q);
+    a.vals = reinterpret_cast<double*>(k.io + lay.vals);
+    a.grad = k.out<float>(1);
+    a.gsum = a.grad != nullptr ? reinterpret_cast<double*>(k.io + lay.gsum) : nullptr;
+    a.terms = k.out<double>(0); a.dual = k.out<double>(2); a.col_err = k.out<double>(3); a.self_err = k.out<double>(4);
+    a.transported = transported_out != nullptr ? reinterpret_cast<double*>(k.io + lay.transported) : nullptr;
+    {
+        ProbeScope ps(c, KC_LOSS);
+        hipLaunchKernelGGL(kd_sweeps_unbalanced, dim3(B, 1, 3), dim3(KT_THREADS), 0, c->stream, a);
+        hipLaunchKernelGGL((kd_combine<false, true>), dim3(B, 1), dim3(KD_COMBINE_THREADS), 0, c->stream, a);
+    }
+    int rc = DRP_OK;
+    if (transported_out != nullptr) rc = d2h(c, transported_out, k.io + lay.transported, (size_t)B * sizeof(double));
+    const int rf = cloud_finish(c, k, "kd_sweeps_unbalanced");      // the wait, also behind an error above
+    return rc != DRP_OK ? rc : rf;
+}
+
+// drp_train_step_divergence with the reaches and the targets' masses in TrLoss: train_step_body launches the unbalanced kernels
+int drp_train_step_divergence_unbalanced(drp_ctx* c, const float* states, const float* states_delta, const float* actions,
+                                         const float* attrs, const int32_t* particle_nums, const float* particle_dens, int B, int N,
+                                         const float* targets, const int32_t* target_nums, int M, const double* eps, const double* rho,
+                                         const double* mass_q, int iters, int mode, double* loss_out, float* grad_out,
+                                         double* col_err_out, double* self_err_out, double* transported_out) {
+    if (!c) return DRP_EINVAL;
+    if ((states_delta != nullptr) == (actions != nullptr))
+        return fail(c, DRP_EINVAL, "exactly one of states_delta and actions must be given");
+    if (!rho || !mass_q) return fail(c, DRP_EINVAL, "null argument");
+    TrLoss lk = TrLoss::against(TR_LOSS_DIVERGENCE, targets, target_nums, M);
+    lk.eps = eps; lk.iters = iters; lk.col_err_out = col_err_out; lk.self_err_out = self_err_out;
+    lk.rho = rho; lk.mass_q = mass_q; lk.transported_out = transported_out;
+    const bool by_actions = actions != nullptr;
+    return train_step_body(c, states, by_actions ? actions : states_delta, by_actions, attrs, particle_nums, particle_dens, B, N, lk,
+                           mode, loss_out, grad_out);
+}
+
 // drp_train_step_transport's body with the divergence as each step's term: one more certificate
 int drp_train_step_divergence(drp_ctx* c, const float* states, const float* states_delta, const float* actions, const float* attrs,
                               const int32_t* particle_nums, const float* particle_dens, int B, int N, const float* targets,

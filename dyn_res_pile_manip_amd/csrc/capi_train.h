@@ -32,6 +32,10 @@ struct TrLoss {
     int iters = 0;                          // TR_LOSS_TRANSPORT, _DIVERGENCE: the sweeps
     double* col_err_out = nullptr;          // TR_LOSS_TRANSPORT, _DIVERGENCE: the caller's [H][B], nullable
     double* self_err_out = nullptr;         // TR_LOSS_DIVERGENCE: the caller's [H][B][2], nullable
+    const double* rho = nullptr;            // TR_LOSS_DIVERGENCE, non-null: the unbalanced divergence -- the caller's reaches [B] ...
+    const double* mass_q = nullptr;         //   ... and the targets' total masses [H][B] (both or neither)
+    double* transported_out = nullptr;      //   ... and the caller's [H][B], nullable
+    bool unbalanced() const { return kind == TR_LOSS_DIVERGENCE && rho != nullptr; }
     bool transport() const { return kind == TR_LOSS_TRANSPORT; }
     bool divergence() const { return kind == TR_LOSS_DIVERGENCE; }
     bool sinkhorn() const { return transport() || divergence(); }      // eps and iters, the kernels' caps and col_err
@@ -69,6 +73,26 @@ int check_transport_params(drp_ctx* c, const double* eps, int B, int iters) {
     const int bad = first_bad_eps(eps, B);
     if (bad >= 0) return fail(c, DRP_EINVAL, "eps[%d]=%g is not a positive finite number", bad, eps[bad]);
     if (iters < 1 || iters > KT_MAX_ITERS) return fail(c, DRP_EINVAL, "iters=%d outside 1..%d", iters, KT_MAX_ITERS);
+    return DRP_OK;
+}
+// rho [B] and mass_q [n_steps][B] as drp_cloud_divergence_unbalanced (n_steps = 1) and drp_train_step_divergence_unbalanced
+// refuse them (train_host.h: check_reach); behind check_transport_params: eps is positive and finite
+int check_reach_params(drp_ctx* c, const double* eps, const double* rho, const double* mass_q, int B, int n_steps) {
+    if (!rho || !mass_q) return fail(c, DRP_EINVAL, "null argument");
+    for (int t = 0; t < n_steps; ++t)
+        for (int b = 0; b < B; ++b) {
+            const double w = mass_q[(size_t)t * B + b];
+            switch (check_reach(eps[b], rho[b], w)) {
+            case REACH_RHO:
+                return fail(c, DRP_EINVAL, "rho[%d]=%g is neither +inf nor a finite number of at least eps[%d]/1024 = %g", b, rho[b], b,
+                            eps[b] * KD_MIN_REACH_PER_EPS);
+            case REACH_MASS:
+                return fail(c, DRP_EINVAL, "mass_q[%d][%d]=%g outside %g..%g", t, b, w, KD_MIN_MASS, KD_MAX_MASS);
+            case REACH_INF_MASS:
+                return fail(c, DRP_EINVAL, "mass_q[%d][%d]=%g with rho[%d]=+inf: balanced transport needs equal masses (mass_q = 1)", t, b, w, b);
+            default: break;
+            }
+        }
     return DRP_OK;
 }
 // step t of the predictions (p's strides) against step t of the target clouds [B][H][M][3] and their counts [B][H] as staged
@@ -174,7 +198,8 @@ int train_forward_backward(drp_ctx* c, int B, int N, const TrainPass& tp) {
         if (lk.divergence()) {
             // the same outputs; the certificates and the two kernels' scratch lie behind the terms (train_host.h:
             // tr_div_loss_layout); kd_combine does the zero-fill, on the grid the other loss kernels do it on
-            const TrDivLoss dl = tr_div_loss_layout(B, H, N);
+            const bool unbalanced = lk.unbalanced();
+            const TrDivLoss dl = tr_div_loss_layout(B, H, N, unbalanced);
             double* const d = ptr<double>(c->tr_loss);
             KdArgs a{};
             a.cp = cp; a.pred = states;
@@ -185,8 +210,17 @@ int train_forward_backward(drp_ctx* c, int B, int N, const TrainPass& tp) {
             a.col_err = lk.col_err_out != nullptr ? d + dl.col_err : (double*)nullptr;
             a.self_err = lk.self_err_out != nullptr ? d + dl.self_err : (double*)nullptr;
             a.zero = zero; a.n_zero = n_zero;
-            hipLaunchKernelGGL(kd_sweeps, dim3(B, H, 3), dim3(KT_THREADS), 0, st, a);
-            hipLaunchKernelGGL((kd_combine<true>), dim3(B, H), dim3(KD_COMBINE_THREADS), 0, st, a);
+            if (unbalanced) {
+                // the reaches [B] and the targets' masses [H][B] lie behind eps; transported behind the scratch
+                a.rho = reinterpret_cast<const double*>(ar + lay.rho);
+                a.mass_q = reinterpret_cast<const double*>(ar + lay.mass_q);
+                a.transported = lk.transported_out != nullptr ? d + dl.transported : (double*)nullptr;
+                hipLaunchKernelGGL(kd_sweeps_unbalanced, dim3(B, H, 3), dim3(KT_THREADS), 0, st, a);
+                hipLaunchKernelGGL((kd_combine<true, true>), dim3(B, H), dim3(KD_COMBINE_THREADS), 0, st, a);
+            } else {
+                hipLaunchKernelGGL(kd_sweeps, dim3(B, H, 3), dim3(KT_THREADS), 0, st, a);
+                hipLaunchKernelGGL((kd_combine<true>), dim3(B, H), dim3(KD_COMBINE_THREADS), 0, st, a);
+            }
         }
     }
     HIPCHK(c, hipGetLastError());
@@ -414,6 +448,7 @@ int train_check_args(drp_ctx* c, const float* states, const float* impulses, boo
                 return fail(c, DRP_EINVAL, "the %s takes clouds of 1..%d points: N=%d M=%d",
                             lk.divergence() ? "Sinkhorn divergence" : "transport loss", KT_MAX_POINTS, N, lk.M);
             CHK(check_transport_params(c, lk.eps, B, lk.iters));
+            if (lk.unbalanced()) CHK(check_reach_params(c, lk.eps, lk.rho, lk.mass_q, B, c->tr_nroll));
         }
         CHK(check_target_nums(c, lk, B, c->tr_nroll));
     }
@@ -455,7 +490,7 @@ int train_ensure_workspace(drp_ctx* c, int B, int N, TrainPass& tp) {
         CHK(ensure(c, c->ed_x0, kt * bnk * 8 * sizeof(float)));
     }
     // (the transport loss: col_err behind the terms; the divergence: its certificates and scratch, tr_div_loss_layout)
-    CHK(ensure(c, c->tr_loss, tp.lk.divergence() ? tr_div_loss_layout(B, H, N).count * sizeof(double)
+    CHK(ensure(c, c->tr_loss, tp.lk.divergence() ? tr_div_loss_layout(B, H, N, tp.lk.unbalanced()).count * sizeof(double)
                                                  : (size_t)H * B * sizeof(double) * (tp.lk.transport() ? 2 : 1)));
     if (tp.lk.match()) CHK(ensure(c, c->tr_match, (size_t)H * bn * sizeof(int)));
     return DRP_OK;
@@ -477,6 +512,10 @@ int train_stage_batch(drp_ctx* c, const float* states, const float* impulses, co
         memcpy(pin + lay.tnums, tp.lk.target_nums, (size_t)B * H * sizeof(int));
     }
     if (tp.lk.sinkhorn()) memcpy(pin + lay.eps, tp.lk.eps, (size_t)B * sizeof(double));
+    if (tp.lk.unbalanced()) {
+        memcpy(pin + lay.rho, tp.lk.rho, (size_t)B * sizeof(double));
+        memcpy(pin + lay.mass_q, tp.lk.mass_q, (size_t)H * B * sizeof(double));
+    }
     // the unpacking launch IS the upload: it reads the staged batch from the pinned host buffer (device-visible) and leaves
     // the arena copy for the kernels that read the given states; DRP_TRAIN_COPY_UPLOAD=1: a copy on the stream first
     const bool by_kernel = !c->train_copy_upload;
@@ -517,9 +556,11 @@ int train_attempt(drp_ctx* c, int B, int N, const TrainPass& tp, int mode, bool 
     if (tp.lk.col_err_out && tp.lk.transport())
         CHK(d2h(c, tp.lk.col_err_out, ptr<double>(c->tr_loss) + (size_t)H * B, (size_t)H * B * sizeof(double)));
     if (tp.lk.divergence()) {
-        const TrDivLoss dl = tr_div_loss_layout(B, H, N);
+        const TrDivLoss dl = tr_div_loss_layout(B, H, N, tp.lk.unbalanced());
         if (tp.lk.col_err_out) CHK(d2h(c, tp.lk.col_err_out, ptr<double>(c->tr_loss) + dl.col_err, (size_t)H * B * sizeof(double)));
         if (tp.lk.self_err_out) CHK(d2h(c, tp.lk.self_err_out, ptr<double>(c->tr_loss) + dl.self_err, (size_t)H * B * 2 * sizeof(double)));
+        if (tp.lk.unbalanced() && tp.lk.transported_out)
+            CHK(d2h(c, tp.lk.transported_out, ptr<double>(c->tr_loss) + dl.transported, (size_t)H * B * sizeof(double)));
     }
     if (tp.backward && !direct) CHK(d2h(c, flag_host, flag_dev, sizeof(unsigned)));
     bool repacked = false;
@@ -569,7 +610,7 @@ int train_step_body(drp_ctx* c, const float* states, const float* impulses, bool
         CHK(pick_tape_engine(c, amax, max_abs(particle_dens, (size_t)B), sd_max, &tp.engine));
     }
     tp.backward = mode != DRP_TRAIN_EVAL;
-    tp.lay = tr_layout(B, H, N, lk.kind != TR_LOSS_MSE ? lk.M : 0, actions, lk.sinkhorn());
+    tp.lay = tr_layout(B, H, N, lk.kind != TR_LOSS_MSE ? lk.M : 0, actions, lk.sinkhorn(), lk.unbalanced());
     tp.lk = lk;
     tp.actions = actions;
     CHK(train_ensure_workspace(c, B, N, tp));

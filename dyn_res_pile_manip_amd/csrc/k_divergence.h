@@ -19,6 +19,15 @@
 // padding, the term, and in the trainer the zero-fill of the gradient blob (train_zero_fill: this launch alone does it, on the
 // grid the other loss kernels do it on).  The duals and the certificates are each written by the one block that owns them.
 // No atomics, one summation order fixed by the counts, no value prolongs a loop (k_transport.h).
+// UNBALANCED (kd_sweeps_unbalanced, kd_combine<., true>; include/drp.h: drp_cloud_divergence_unbalanced).  Each marginal is held
+// by a KL penalty of weight rho (the reach, in eps's unit) in place of the hard constraint, and the target cloud carries total
+// mass w: a = 1 / n_p, b = w / n_q, lambda = rho / (rho + eps).  Every sweep's soft minimum is multiplied by lambda (kt_half_sweep's
+// DAMPED: one multiply per output), the self problems' mass is the cloud's own, and
+//   divergence = scale (rho + eps / 2) (sum_i a (expm1(-h^p_i / rho) - expm1(-f_i / rho)) + sum_j b (expm1(-h^q_j / rho) - expm1(-g_j / rho))) / 3
+//   col_err    = sum_j |sum_i P_ij - b exp(-g_j / rho)|;  self_err likewise against m exp(-h / rho);  the gradient's expression is the same
+//   transported = sum_i a exp(-f_i / rho): the plan's total mass (its rows sum to a exp(-f_i / rho) exactly behind f's update)
+// rho = +inf (with w = 1): lambda = 1 and the balanced value -- x 1.0 and exp(-0) are exact, so every output has the balanced
+// kernel's bits.  Same LDS, same grid, same loops: the sums of the value are kt_block_sum's as the duals' are.
 #pragma once
 #include "k_transport.h"
 
@@ -30,7 +39,7 @@ struct KdArgs {
     const double* eps;          // [B]
     int iters;
     double scale;
-    double* vals;               // scratch [3][H][B]: sum a f + sum b g | sum a h^p | sum b h^q
+    double* vals;               // scratch [3][H][B]: sum a f + sum b g | sum a h^p | sum b h^q  (unbalanced: of -expm1(-. / rho))
     double* gsum;               // scratch [2][H][B][N][3]: sum_j P_ij (p_i - q_j) | sum_j S^p_ij (p_i - p_j), real rows; null: no gradient
     float* grad;                // [H][B][N][3], every row written (padded rows 0); null with gsum
     double* terms;              // [H][B]
@@ -38,11 +47,41 @@ struct KdArgs {
     double* col_err;            // [H][B], nullable: the pass over the columns runs only where it is asked for
     double* self_err;           // [H][B][2], nullable
     float* zero; size_t n_zero; // the trainer, nullable: filled with 0 by kd_combine<true>
+    const double* rho;          // unbalanced: [B], the reach (+inf: balanced); else null
+    const double* mass_q;       // unbalanced: [H][B], the target cloud's total mass w; else null
+    double* transported;        // unbalanced: [H][B], nullable
 };
 
+// what the relaxation adds to a block: the reach, its damping factor and whether it is the balanced limit
+struct KdReach {
+    double rho, lambda;
+    bool balanced;
+};
+__device__ __forceinline__ KdReach kd_reach(double rho, double eps) {
+    KdReach r;
+    r.rho = rho;
+    r.balanced = rho == (double)__builtin_inff();
+    r.lambda = r.balanced ? 1.0 : rho / (rho + eps);
+    return r;
+}
+// a dual's share of the value: the dual itself, or with a finite reach -expm1(-dual / rho) (kd_combine multiplies by rho + eps / 2)
+template <bool UNBAL>
+__device__ __forceinline__ double kd_value_term(double dual, const KdReach& r) {
+    if (UNBAL && !r.balanced) return -expm1(-dual / r.rho);
+    return dual;
+}
+// what a row (column) of a plan sums to at the fixed point: the mass, or with a finite reach what the penalty leaves of it
+template <bool UNBAL>
+__device__ __forceinline__ double kd_marginal(double mass, double dual, const KdReach& r) {
+    if (UNBAL) return mass * exp(-dual / r.rho);
+    return mass;
+}
+
 // z = 0: the cross problem -- kt_transport's sweeps; behind them the duals' sum, the plan's rows against q, col_err
+template <bool UNBAL>
 __device__ __forceinline__ void kd_cross(const KdArgs& A, float4* s_p, float4* s_q, double* s_f, double* s_g, double* s_w, const float* p,
-                                         const float* q, int np, int nq, bool empty, int iters, double eps, size_t slot) {
+                                         const float* q, int np, int nq, bool empty, int iters, double eps, size_t slot, const KdReach& R,
+                                         double w) {
     const int tid = threadIdx.x;
     const int N = A.cp.N, M = A.cp.M;
     for (int e = tid; e < np; e += KT_THREADS) {
@@ -54,21 +93,28 @@ __device__ __forceinline__ void kd_cross(const KdArgs& A, float4* s_p, float4* s
         s_g[e] = 0.0;
     }
     __syncthreads();
-    const double mass_p = empty ? 0.0 : 1.0 / (double)np, mass_q = empty ? 0.0 : 1.0 / (double)nq;
+    const double mass_p = empty ? 0.0 : 1.0 / (double)np, mass_q = empty ? 0.0 : (UNBAL ? w : 1.0) / (double)nq;
     const double log_a = log(mass_p), log_b = log(mass_q);
     for (int k = 0; k < iters; ++k) {
-        kt_half_sweep(s_q, nq, s_p, np, s_f, s_g, eps, log_a);
+        kt_half_sweep<false, UNBAL>(s_q, nq, s_p, np, s_f, s_g, eps, log_a, R.lambda);
         __syncthreads();
-        kt_half_sweep(s_p, np, s_q, nq, s_g, s_f, eps, log_b);
+        kt_half_sweep<false, UNBAL>(s_p, np, s_q, nq, s_g, s_f, eps, log_b, R.lambda);
         __syncthreads();
     }
     double acc = 0.0;
     if (!empty) {
-        for (int e = tid; e < np; e += KT_THREADS) acc += mass_p * s_f[e];
-        for (int e = tid; e < nq; e += KT_THREADS) acc += mass_q * s_g[e];
+        for (int e = tid; e < np; e += KT_THREADS) acc += mass_p * kd_value_term<UNBAL>(s_f[e], R);
+        for (int e = tid; e < nq; e += KT_THREADS) acc += mass_q * kd_value_term<UNBAL>(s_g[e], R);
     }
     const double total = kt_block_sum(acc, s_w);
     if (tid == 0) A.vals[slot] = total;
+    if (UNBAL && A.transported != nullptr) {
+        double moved = 0.0;
+        if (!empty)
+            for (int e = tid; e < np; e += KT_THREADS) moved += kd_marginal<UNBAL>(mass_p, s_f[e], R);
+        const double sum = kt_block_sum(moved, s_w);
+        if (tid == 0) A.transported[slot] = sum;
+    }
     if (A.dual != nullptr) {
         double* dual = A.dual + slot * (2 * ((size_t)N + M));
         for (int e = tid; e < N; e += KT_THREADS) dual[e] = (!empty && e < np) ? s_f[e] : 0.0;
@@ -108,7 +154,7 @@ __device__ __forceinline__ void kd_cross(const KdArgs& A, float4* s_p, float4* s
             double col = 0.0;
             for (int i = s; i < np; i += parts) col += ab * exp((s_f[i] + gj - (double)kt_cost(s_p[i], o)) / eps);
             col = kt_group_sum(col, lp);
-            if (live && s == 0) err += fabs(col - mass_q);
+            if (live && s == 0) err += fabs(col - kd_marginal<UNBAL>(mass_q, gj, R));
         }
         const double sum = kt_block_sum(err, s_w);
         if (tid == 0) A.col_err[slot] = sum;
@@ -117,27 +163,29 @@ __device__ __forceinline__ void kd_cross(const KdArgs& A, float4* s_p, float4* s
 
 // z = 1 (x = p) and 2 (x = q): the self problem of one cloud of n rows (row length `len` in the padded batch) -- the averaged
 // Jacobi sweeps between h0 and h1; behind them h's sum, the symmetric plan's rows against x itself (the gradient's second sum:
-// p's only) and self_err
+// p's only) and self_err.  total_mass: the cloud's (1, or the unbalanced target's w)
+template <bool UNBAL>
 __device__ __forceinline__ void kd_self(const KdArgs& A, float4* s_x, double* h0, double* h1, double* s_w, const float* x, int n, int len,
-                                        bool empty, int iters, double eps, size_t slot, size_t slots, int which, double* dual) {
+                                        bool empty, int iters, double eps, size_t slot, size_t slots, int which, double* dual,
+                                        const KdReach& R, double total_mass) {
     const int tid = threadIdx.x;
     for (int e = tid; e < n; e += KT_THREADS) {
         s_x[e] = make_float4(x[(size_t)e * 3], x[(size_t)e * 3 + 1], x[(size_t)e * 3 + 2], 0.0f);
         h0[e] = 0.0;
     }
     __syncthreads();
-    const double mass = empty ? 0.0 : 1.0 / (double)n;
+    const double mass = empty ? 0.0 : (UNBAL ? total_mass : 1.0) / (double)n;
     const double log_m = log(mass);
     double* cur = h0;
     double* nxt = h1;
     for (int k = 0; k < iters; ++k) {
-        kt_half_sweep<true>(s_x, n, s_x, n, cur, nxt, eps, log_m);
+        kt_half_sweep<true, UNBAL>(s_x, n, s_x, n, cur, nxt, eps, log_m, R.lambda);
         __syncthreads();
         double* const sw = cur; cur = nxt; nxt = sw;
     }
     double acc = 0.0;
     if (!empty)
-        for (int e = tid; e < n; e += KT_THREADS) acc += mass * cur[e];
+        for (int e = tid; e < n; e += KT_THREADS) acc += mass * kd_value_term<UNBAL>(cur[e], R);
     const double total = kt_block_sum(acc, s_w);
     if (tid == 0) A.vals[(size_t)(1 + which) * slots + slot] = total;
     if (dual != nullptr)
@@ -165,7 +213,7 @@ __device__ __forceinline__ void kd_self(const KdArgs& A, float4* s_x, double* h0
         row = kt_group_sum(row, lp);
         if (gs != nullptr) { sx = kt_group_sum(sx, lp); sy = kt_group_sum(sy, lp); sz = kt_group_sum(sz, lp); }
         if (live && s == 0) {
-            err += fabs(row - mass);
+            err += fabs(row - kd_marginal<UNBAL>(mass, hi, R));
             if (gs != nullptr) { gs[(size_t)i * 3] = sx; gs[(size_t)i * 3 + 1] = sy; gs[(size_t)i * 3 + 2] = sz; }
         }
     }
@@ -175,7 +223,8 @@ __device__ __forceinline__ void kd_self(const KdArgs& A, float4* s_x, double* h0
     }
 }
 
-__global__ void __launch_bounds__(KT_THREADS) kd_sweeps(KdArgs A) {
+template <bool UNBAL>
+__device__ __forceinline__ void kd_sweeps_body(const KdArgs& A) {
     __shared__ float4 s_p[KT_MAX_POINTS];       // cross: p; self: the cloud
     __shared__ float4 s_q[KT_MAX_POINTS];       // cross: q
     __shared__ double s_f[KT_MAX_POINTS];       // cross: f; self: h of the even sweeps
@@ -190,14 +239,23 @@ __global__ void __launch_bounds__(KT_THREADS) kd_sweeps(KdArgs A) {
     const bool empty = np == 0 || nq == 0;              // (the entry points refuse it)
     const int iters = empty ? 0 : min(max(A.iters, 0), KT_MAX_ITERS);
     const double eps = A.eps[b];
+    KdReach R{};
+    double w = 1.0;
+    if (UNBAL) {
+        R = kd_reach(A.rho[b], eps);
+        w = A.mass_q[slot];
+    }
     double* dual = A.dual != nullptr ? A.dual + slot * (2 * ((size_t)N + M)) : nullptr;
-    if (z == 0) kd_cross(A, s_p, s_q, s_f, s_g, s_w, p, q, np, nq, empty, iters, eps, slot);
-    else if (z == 1) kd_self(A, s_p, s_f, s_g, s_w, p, np, N, empty, iters, eps, slot, slots, 0, dual != nullptr ? dual + N + M : nullptr);
-    else kd_self(A, s_p, s_f, s_g, s_w, q, nq, M, empty, iters, eps, slot, slots, 1, dual != nullptr ? dual + 2 * (size_t)N + M : nullptr);
+    if (z == 0) kd_cross<UNBAL>(A, s_p, s_q, s_f, s_g, s_w, p, q, np, nq, empty, iters, eps, slot, R, w);
+    else if (z == 1) kd_self<UNBAL>(A, s_p, s_f, s_g, s_w, p, np, N, empty, iters, eps, slot, slots, 0, dual != nullptr ? dual + N + M : nullptr, R, 1.0);
+    else kd_self<UNBAL>(A, s_p, s_f, s_g, s_w, q, nq, M, empty, iters, eps, slot, slots, 1, dual != nullptr ? dual + 2 * (size_t)N + M : nullptr, R, w);
 }
 
+__global__ void __launch_bounds__(KT_THREADS) kd_sweeps(KdArgs A) { kd_sweeps_body<false>(A); }
+__global__ void __launch_bounds__(KT_THREADS) kd_sweeps_unbalanced(KdArgs A) { kd_sweeps_body<true>(A); }
+
 // behind kd_sweeps in the stream: what needs more than one block's results
-template <bool TRAIN>
+template <bool TRAIN, bool UNBAL = false>
 __global__ void __launch_bounds__(KD_COMBINE_THREADS) kd_combine(KdArgs A) {
     const int b = blockIdx.x, t = blockIdx.y, B = gridDim.x;
     const int tid = threadIdx.x;
@@ -214,5 +272,10 @@ __global__ void __launch_bounds__(KD_COMBINE_THREADS) kd_combine(KdArgs A) {
         const int real = (empty ? 0 : np) * 3;
         for (int e = tid; e < N * 3; e += KD_COMBINE_THREADS) g[e] = e < real ? (float)(gscale * (cross[e] - self[e])) : 0.0f;     // rounded once
     }
-    if (tid == 0) A.terms[slot] = A.scale * ((A.vals[slot] - A.vals[slots + slot] - A.vals[2 * slots + slot]) / 3.0);
+    if (tid == 0) {
+        const double sum = A.vals[slot] - A.vals[slots + slot] - A.vals[2 * slots + slot];
+        const KdReach R = UNBAL ? kd_reach(A.rho[b], A.eps[b]) : KdReach{};
+        if (UNBAL && !R.balanced) A.terms[slot] = A.scale * (((R.rho + 0.5 * A.eps[b]) * sum) / 3.0);
+        else A.terms[slot] = A.scale * (sum / 3.0);
+    }
 }

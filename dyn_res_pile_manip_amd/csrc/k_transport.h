@@ -76,9 +76,10 @@ __device__ __forceinline__ double kt_group_sum(double v, int lp) {
 
 // out_dual[j] = -eps LSE_i((in_dual[i] - C_ij) / eps + log_mass) for every j < n_out; the caller's barrier is behind it.
 // AVERAGE (k_divergence.h's self problems, both clouds the same one): out_dual[j] = (in_dual[j] + that) / 2
-template <bool AVERAGE = false>
+// DAMPED (k_divergence.h's unbalanced problems): `that` is lambda x the soft minimum -- one multiply per output, nothing per term
+template <bool AVERAGE = false, bool DAMPED = false>
 __device__ __forceinline__ void kt_half_sweep(const float4* out_pts, int n_out, const float4* in_pts, int n_in, const double* in_dual,
-                                              double* out_dual, double eps, double log_mass) {
+                                              double* out_dual, double eps, double log_mass, double lambda = 1.0) {
     const int lp = kt_parts(n_out, n_in), parts = 1 << lp, items = n_out << lp;
     const double ninf = -(double)__builtin_inff();
     for (int e0 = 0; e0 < items; e0 += KT_THREADS) {
@@ -101,7 +102,8 @@ __device__ __forceinline__ void kt_half_sweep(const float4* out_pts, int n_out, 
         }
         sum = kt_group_sum(sum, lp);
         if (live && s == 0) {
-            const double v = -eps * (m + log(sum));
+            const double u = -eps * (m + log(sum));
+            const double v = DAMPED ? lambda * u : u;
             out_dual[j] = AVERAGE ? 0.5 * (in_dual[j] + v) : v;
         }
     }

@@ -11,13 +11,14 @@
 // | particle counts [B] (ints), every block 16-byte aligned; drp_train_step_untracked (M > 0): behind them the target clouds
 // [B][H][M][3] | their counts [B][H] (ints) -- with M = 0 the layout, and so the one copy, is drp_train_step's;
 // drp_train_step_actions (`actions`): the pushes [B][H][4] where the impulses are, everything behind them moving up;
-// drp_train_step_transport, drp_train_step_divergence (`eps`): behind everything the regularisation strengths [B] (doubles)
-struct TrArena { size_t states, sdelta, attrs, dens, nums, targets, tnums, bytes, eps; };
+// drp_train_step_transport, drp_train_step_divergence (`eps`): behind everything the regularisation strengths [B] (doubles);
+// drp_train_step_divergence_unbalanced (`reach`, with `eps`): behind those the reaches [B] | the targets' masses [H][B] (doubles)
+struct TrArena { size_t states, sdelta, attrs, dens, nums, targets, tnums, bytes, eps, rho, mass_q; };
 // the impulse block: what train_stage_batch copies to TrArena::sdelta
 inline size_t tr_impulse_bytes(int B, int H, int N, bool actions) {
     return (actions ? (size_t)B * H * 4 : (size_t)B * H * N * 3) * sizeof(float);
 }
-inline TrArena tr_layout(int B, int H, int N, int M = 0, bool actions = false, bool eps = false) {
+inline TrArena tr_layout(int B, int H, int N, int M = 0, bool actions = false, bool eps = false, bool reach = false) {
     auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
     TrArena a{};
     a.states = 0;
@@ -34,6 +35,11 @@ inline TrArena tr_layout(int B, int H, int N, int M = 0, bool actions = false, b
     if (eps) {
         a.eps = a.bytes;
         a.bytes = up(a.eps + (size_t)B * sizeof(double));
+    }
+    if (eps && reach) {
+        a.rho = a.bytes;
+        a.mass_q = up(a.rho + (size_t)B * sizeof(double));
+        a.bytes = up(a.mass_q + (size_t)H * B * sizeof(double));
     }
     return a;
 }
@@ -132,6 +138,23 @@ inline DivLayout divergence_layout(int B, int N, int M) {
     a.cloud.bytes = up(a.gsum + 2 * bn * 3 * sizeof(double));
     return a;
 }
+// drp_cloud_divergence_unbalanced: divergence_layout's blocks; behind them eps [B] | rho [B] | mass_q [B] (doubles, UP in one copy
+// behind cloud_begin's) | the same scratch | transported [B] (doubles, comes back by a copy of its own: a sixth output)
+struct DivUnbalancedLayout { CloudLayout cloud; size_t eps, rho, mass_q, vals, gsum, transported; };
+inline DivUnbalancedLayout divergence_unbalanced_layout(int B, int N, int M) {
+    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t bn = (size_t)B * N;
+    DivUnbalancedLayout a{};
+    a.cloud = divergence_layout(B, N, M).cloud;
+    a.eps = divergence_layout(B, N, M).eps;
+    a.rho = a.eps + (size_t)B * sizeof(double);
+    a.mass_q = a.rho + (size_t)B * sizeof(double);
+    a.vals = up(a.mass_q + (size_t)B * sizeof(double));
+    a.gsum = up(a.vals + (size_t)3 * B * sizeof(double));
+    a.transported = up(a.gsum + 2 * bn * 3 * sizeof(double));
+    a.cloud.bytes = up(a.transported + (size_t)B * sizeof(double));
+    return a;
+}
 // drp_cloud_divergence_f64: p is the caller's doubles, so the buffer is its own (not cloud_begin's).  Up, in one copy: p [B][N][3]
 // (doubles) | eps [B] (doubles) | q [B][M][3] | n_p [B] | n_q [B] (ints); down, behind `in_bytes`: terms [B] | gradient [B][N][3] |
 // duals [B][2N + 2M] | col_err [B] | self_err [B][2] (out[0..5), doubles all); behind them, never read back, the kernels' scratch:
@@ -213,9 +236,10 @@ inline const char* matching_fault(int why) {
 }
 
 // drp_train_step_divergence's device doubles (c->tr_loss), in doubles: terms [H][B] | col_err [H][B] | self_err [H][B][2] | the
-// value sums [3][H][B] | the gradient sums [2][H][B][N][3]
-struct TrDivLoss { size_t terms, col_err, self_err, vals, gsum, count; };
-inline TrDivLoss tr_div_loss_layout(int B, int H, int N) {
+// value sums [3][H][B] | the gradient sums [2][H][B][N][3]; drp_train_step_divergence_unbalanced (`unbalanced`): behind them
+// transported [H][B]
+struct TrDivLoss { size_t terms, col_err, self_err, vals, gsum, count, transported; };
+inline TrDivLoss tr_div_loss_layout(int B, int H, int N, bool unbalanced = false) {
     const size_t hb = (size_t)H * B;
     TrDivLoss a{};
     a.terms = 0;
@@ -224,6 +248,10 @@ inline TrDivLoss tr_div_loss_layout(int B, int H, int N) {
     a.vals = a.self_err + 2 * hb;
     a.gsum = a.vals + 3 * hb;
     a.count = a.gsum + 2 * hb * N * 3;
+    if (unbalanced) {
+        a.transported = a.count;
+        a.count = a.transported + hb;
+    }
     return a;
 }
 // the first of the B regularisation strengths that is zero, negative, infinite or no number, or -1
@@ -231,6 +259,19 @@ inline int first_bad_eps(const double* eps, int B) {
     for (int b = 0; b < B; ++b)
         if (!(eps[b] > 0.0) || !std::isfinite(eps[b])) return b;
     return -1;
+}
+// the unbalanced divergence's reach and target mass of one problem (include/drp.h: drp_cloud_divergence_unbalanced): 0 where it
+// is served, else what is refused
+enum { REACH_OK = 0, REACH_RHO = 1, REACH_MASS = 2, REACH_INF_MASS = 3 };
+#define KD_MIN_REACH_PER_EPS (1.0 / 1024.0)
+#define KD_MIN_MASS 0.125
+#define KD_MAX_MASS 8.0
+inline int check_reach(double eps, double rho, double mass_q) {
+    const bool inf = rho == INFINITY;
+    if (!inf && !(std::isfinite(rho) && rho >= eps * KD_MIN_REACH_PER_EPS)) return REACH_RHO;      // (NaN, <= 0 and -inf too)
+    if (!(mass_q >= KD_MIN_MASS && mass_q <= KD_MAX_MASS)) return REACH_MASS;
+    if (inf && mass_q != 1.0) return REACH_INF_MASS;
+    return REACH_OK;
 }
 // the first of the real rows' coordinates of a padded cloud batch [B][N][3] that is infinite or no number, as b * N + row, or -1
 // (the padding is never read as points: rubbish there is allowed); T: float, or drp_cloud_divergence_f64's double

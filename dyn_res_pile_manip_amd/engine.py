@@ -943,7 +943,7 @@ class Engine(object):
         return (out.value, grad, col_err) if want_col_err else (out.value, grad)
 
     def cloud_divergence(self, p, q, n_p=None, n_q=None, eps=None, iters=None, want_grad=False, want_dual=False, want_col_err=False,
-                         want_self_err=False):
+                         want_self_err=False, reach=None, mass_q=None, want_transported=False):
         """Sinkhorn divergence of p [B, N, 3] and q [B, M, 3] (arguments as cloud_transport's; eps and iters are required):
         cloud_transport's loss with its entropic bias taken out, OT(p, q) - OT(p, p) / 2 - OT(q, q) / 2 on the dual values, zero
         only for equal clouds -> {'divergence' [B] float64 (not clamped: rounding can leave it a hair below zero at p ~ q)[, 'grad'
@@ -951,9 +951,15 @@ class Engine(object):
         counts, and zero where transport's is not, at p == q][, 'f' [B, N], 'g' [B, M], 'h_p' [B, N], 'h_q' [B, M]: the duals of
         the cross problem and of the two self problems, float64, 0 on padding][, 'col_err' [B] as cloud_transport's][, 'self_err'
         [B, 2]: sum_i |sum_j S_ij - mass| of p's and of q's self plan]} (include/drp.h: drp_cloud_divergence).  At most 1024
-        points per cloud.  A one-shot: it needs no weights and ends no session."""
+        points per cloud.  A one-shot: it needs no weights and ends no session.
+        reach (a number or [B], in eps's unit; np.inf: balanced) makes it the UNBALANCED divergence for a pile seen partly
+        (include/drp.h: drp_cloud_divergence_unbalanced): mass further than about sqrt(reach) from the other cloud is given up
+        instead of moved.  mass_q (a number or [B], default 1, within [1/8, 8]): q's total mass against p's 1 -- n_q / n_p is
+        equal mass per point.  want_transported: + 'transported' [B], the plan's total mass.  reach=None is the call above."""
         if eps is None or iters is None:
             raise ValueError('cloud_divergence needs eps (squared-distance units) and iters')
+        if reach is None and (mass_q is not None or want_transported):
+            raise ValueError('mass_q and want_transported belong to the unbalanced divergence: give reach')
         p, q, n_p, n_q, B, N, M = self._cloud_pair(p, q, n_p, n_q)
         eps = np.ascontiguousarray(np.broadcast_to(np.asarray(eps, np.float64).reshape(-1), (B,)))
         terms = np.empty((B,), np.float64)
@@ -961,9 +967,19 @@ class Engine(object):
         dual = np.empty((B, 2 * (N + M)), np.float64) if want_dual else None
         col_err = np.empty((B,), np.float64) if want_col_err else None
         self_err = np.empty((B, 2), np.float64) if want_self_err else None
-        self._ck(self.lib.drp_cloud_divergence(self.h, _fp(p), _ip(n_p), _fp(q), _ip(n_q), B, N, M, _dp(eps), int(iters), _dp(terms),
-                                               _opt(_fp, grad), _opt(_dp, dual), _opt(_dp, col_err), _opt(_dp, self_err)))
+        if reach is None:
+            self._ck(self.lib.drp_cloud_divergence(self.h, _fp(p), _ip(n_p), _fp(q), _ip(n_q), B, N, M, _dp(eps), int(iters), _dp(terms),
+                                                   _opt(_fp, grad), _opt(_dp, dual), _opt(_dp, col_err), _opt(_dp, self_err)))
+        else:
+            rho = np.ascontiguousarray(np.broadcast_to(np.asarray(reach, np.float64).reshape(-1), (B,)))
+            w = np.ascontiguousarray(np.broadcast_to(np.asarray(1.0 if mass_q is None else mass_q, np.float64).reshape(-1), (B,)))
+            moved = np.empty((B,), np.float64) if want_transported else None
+            self._ck(self.lib.drp_cloud_divergence_unbalanced(self.h, _fp(p), _ip(n_p), _fp(q), _ip(n_q), B, N, M, _dp(eps), _dp(rho),
+                                                              _dp(w), int(iters), _dp(terms), _opt(_fp, grad), _opt(_dp, dual),
+                                                              _opt(_dp, col_err), _opt(_dp, self_err), _opt(_dp, moved)))
         out = {'divergence': terms}
+        if want_transported:
+            out['transported'] = moved
         if want_grad:
             out['grad'] = grad
         if want_dual:
@@ -976,12 +992,16 @@ class Engine(object):
         return out
 
     def train_step_divergence(self, states, attrs, particle_nums, particle_dens, targets, target_nums, eps, iters, states_delta=None,
-                              actions=None, mode='update', want_grad=False, want_err=False):
+                              actions=None, mode='update', want_grad=False, want_err=False, reach=None, mass_q=None):
         """train_step_transport with each step's term the Sinkhorn divergence of cloud_divergence (include/drp.h:
         drp_train_step_divergence): the same arguments -> (loss, gradient blob or None[, col_err [n_rollout, B], self_err
-        [n_rollout, B, 2]: every problem's certificates])."""
+        [n_rollout, B, 2]: every problem's certificates]).  reach (a number or [B]) and mass_q (a number, [B] or [n_rollout, B];
+        default 1): cloud_divergence's unbalanced divergence as each step's term (drp_train_step_divergence_unbalanced); want_err
+        then also returns transported [n_rollout, B].  reach=None is the call above."""
         if (states_delta is None) == (actions is None):
             raise ValueError('exactly one of states_delta and actions must be given')
+        if reach is None and mass_q is not None:
+            raise ValueError('mass_q belongs to the unbalanced divergence: give reach')
         assert targets is not None and target_nums is not None
         by_actions = actions is not None
         keep, (B, N, H, M), (ps, pi, pa, pn, pd, pt, ptn) = self._train_batch(
@@ -991,6 +1011,15 @@ class Engine(object):
         grad = np.empty((L.DRP_N_WEIGHTS,), np.float32) if (want_grad and mode != 'eval') else None
         col_err = np.empty((H, B), np.float64) if want_err else None
         self_err = np.empty((H, B, 2), np.float64) if want_err else None
+        if reach is not None:
+            rho = np.ascontiguousarray(np.broadcast_to(np.asarray(reach, np.float64).reshape(-1), (B,)))
+            w = np.ascontiguousarray(np.broadcast_to(np.asarray(1.0 if mass_q is None else mass_q, np.float64), (H, B)))
+            moved = np.empty((H, B), np.float64) if want_err else None
+            self._ck(self.lib.drp_train_step_divergence_unbalanced(
+                self.h, ps, None if by_actions else pi, pi if by_actions else None, pa, pn, pd, B, N, pt, ptn, M, _dp(eps), _dp(rho),
+                _dp(w), int(iters), L.TRAIN_MODES[mode], ctypes.byref(out), _opt(_fp, grad), _opt(_dp, col_err), _opt(_dp, self_err),
+                _opt(_dp, moved)))
+            return (out.value, grad, col_err, self_err, moved) if want_err else (out.value, grad)
         self._ck(self.lib.drp_train_step_divergence(self.h, ps, None if by_actions else pi, pi if by_actions else None, pa, pn, pd, B, N,
                                                     pt, ptn, M, _dp(eps), int(iters), L.TRAIN_MODES[mode], ctypes.byref(out),
                                                     _opt(_fp, grad), _opt(_dp, col_err), _opt(_dp, self_err)))

@@ -135,6 +135,57 @@ def check_loss(loss, match_weight=0.5, transport_eps_scale=TRANSPORT_EPS_SCALE, 
             raise ValueError('transport_iters must be an integer in 1..%d, got %r' % (TRANSPORT_MAX_ITERS, transport_iters))
 
 
+# the unbalanced Sinkhorn divergence (Engine.train_step_divergence(reach=...)): for a pile seen partly.  sinkhorn_reach_scale r:
+# rho_b = r / particle_dens[b], transport_eps_scale's unit, so r = 4 is a reach of two particle spacings; None: balanced.
+# sinkhorn_mass: the target cloud's total mass against the prediction's 1 -- 'unit': 1; 'count': target_nums[b, t] /
+# particle_nums[b], equal mass per point, right when the targets are sampled at the particles' spacing (target_den_scale == 1)
+SINKHORN_MASSES = ('unit', 'count')
+SINKHORN_MIN_REACH_PER_EPS = 1.0 / 1024.0       # include/drp.h: rho >= eps / 1024
+SINKHORN_MASS_RANGE = (0.125, 8.0)              # include/drp.h: 1/8 <= mass_q <= 8
+
+
+def check_sinkhorn_options(loss, sinkhorn_reach_scale=None, sinkhorn_mass='unit', sinkhorn_probe_every=0,
+                           transport_eps_scale=TRANSPORT_EPS_SCALE):
+    """sinkhorn_reach_scale and sinkhorn_mass of run_batch() / train() / main(): DIVERGENCE_LOSSES' alone; 'count' needs a reach
+    (balanced transport between unequal masses has no plan); the float64 yardstick has no unbalanced variant, so
+    sinkhorn_probe_every is refused with a reach -- refused, not skipped"""
+    if sinkhorn_mass not in SINKHORN_MASSES:
+        raise ValueError('sinkhorn_mass must be one of %s, got %r' % (SINKHORN_MASSES, sinkhorn_mass))
+    if sinkhorn_reach_scale is None:
+        if sinkhorn_mass != 'unit':
+            raise ValueError('sinkhorn_mass=%r needs sinkhorn_reach_scale: balanced transport between unequal masses has no plan'
+                             % (sinkhorn_mass,))
+        return
+    if loss not in DIVERGENCE_LOSSES:
+        raise ValueError('sinkhorn_reach_scale and sinkhorn_mass need a loss of %s, got %r' % (DIVERGENCE_LOSSES, loss))
+    r = float(sinkhorn_reach_scale)
+    if not (r == float('inf') or (0.0 < r < float('inf') and r >= float(transport_eps_scale) * SINKHORN_MIN_REACH_PER_EPS)):
+        raise ValueError('sinkhorn_reach_scale must be inf or a positive finite number of at least transport_eps_scale / 1024, got %r'
+                         % (sinkhorn_reach_scale,))
+    if r == float('inf') and sinkhorn_mass != 'unit':
+        raise ValueError('sinkhorn_mass=%r needs a finite sinkhorn_reach_scale: balanced transport between unequal masses has no plan'
+                         % (sinkhorn_mass,))
+    if sinkhorn_probe_every > 0:
+        raise ValueError('sinkhorn_probe_every: there is no float64 yardstick for the unbalanced divergence yet '
+                         '(sinkhorn_reach_scale=%r)' % (sinkhorn_reach_scale,))
+
+
+def sinkhorn_reach(particle_dens, sinkhorn_reach_scale):
+    """every sample's reach, float64 [B]: sinkhorn_reach_scale / particle_dens[b]"""
+    return float(sinkhorn_reach_scale) / np.asarray(particle_dens, np.float64).reshape(-1)
+
+
+def sinkhorn_mass_q(sinkhorn_mass, particle_nums, target_nums):
+    """the target clouds' total masses, float64 [n_rollout, B], from particle_nums [B] and target_nums [B, n_rollout]"""
+    tn = np.asarray(target_nums, np.float64)
+    if sinkhorn_mass == 'unit':
+        return np.ones(tn.T.shape)
+    w = np.ascontiguousarray((tn / np.asarray(particle_nums, np.float64).reshape(-1, 1)).T)
+    if not ((w >= SINKHORN_MASS_RANGE[0]) & (w <= SINKHORN_MASS_RANGE[1])).all():
+        raise ValueError('sinkhorn_mass=\'count\': a target cloud has less than 1/8 or more than 8 times its prediction\'s points')
+    return w
+
+
 def transport_eps(particle_dens, transport_eps_scale=TRANSPORT_EPS_SCALE):
     """every sample's regularisation strength, float64 [B]: transport_eps_scale / particle_dens[b]"""
     return float(transport_eps_scale) / np.asarray(particle_dens, np.float64).reshape(-1)
@@ -181,7 +232,8 @@ def batch_actions(data):
 
 
 def run_batch(model, optimizer, data, phase='train', n_rollout=None, loss='mse', impulses='data', match_weight=0.5,
-              transport_eps_scale=TRANSPORT_EPS_SCALE, transport_iters=TRANSPORT_ITERS):
+              transport_eps_scale=TRANSPORT_EPS_SCALE, transport_iters=TRANSPORT_ITERS, sinkhorn_reach_scale=None,
+              sinkhorn_mass='unit', stats=None):
     """The loop body at train/train_gnn_dyn.py:159-210 -> loss (python float, what loss.item() is there).  loss='chamfer': `data`
     is collate_untracked's (targets and target_nums behind the six fields) and each step's term is the Chamfer distance to its
     target cloud (Engine.train_step_untracked).  A batch marked depth_only (DepthDataset) is refused (ValueError) unless
@@ -192,8 +244,12 @@ def run_batch(model, optimizer, data, phase='train', n_rollout=None, loss='mse',
     impulse source (Engine.train_step_loss).  loss='transport' (TRANSPORT_LOSSES): the same batches and impulse sources, each
     step's term the entropy-regularised transport distance to its target cloud after transport_iters sweeps with
     eps_b = transport_eps_scale / particle_dens[b] (Engine.train_step_transport).  loss='sinkhorn' (DIVERGENCE_LOSSES): the same
-    again with the Sinkhorn divergence as each step's term, under the same two options (Engine.train_step_divergence)."""
+    again with the Sinkhorn divergence as each step's term, under the same two options (Engine.train_step_divergence).
+    sinkhorn_reach_scale (not None) and sinkhorn_mass: the unbalanced divergence with rho_b = sinkhorn_reach_scale /
+    particle_dens[b] and the targets' masses of sinkhorn_mass_q (check_sinkhorn_options); `stats`, a dict, then receives
+    'transported': the mean over the batch's problems of the share of the predicted mass the plan pairs with something."""
     check_loss(loss, match_weight, transport_eps_scale, transport_iters)
+    check_sinkhorn_options(loss, sinkhorn_reach_scale, sinkhorn_mass, 0, transport_eps_scale)
     if impulses not in IMPULSES:
         raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
     check_depth_only(data, loss, impulses)
@@ -214,6 +270,16 @@ def run_batch(model, optimizer, data, phase='train', n_rollout=None, loss='mse',
         return value
     if loss in TRANSPORT_LOSSES + DIVERGENCE_LOSSES:
         dens = _np(particle_dens)
+        if sinkhorn_reach_scale is not None:
+            nums, tnums = _np(particle_nums, np.int32), _np(data[7], np.int32)
+            out = model.engine.train_step_divergence(
+                states, _np(attrs), nums, dens, _np(data[6]), tnums, transport_eps(dens, transport_eps_scale), int(transport_iters),
+                states_delta=None if actions is not None else _np(states_delta), actions=actions, mode=mode,
+                reach=sinkhorn_reach(dens, sinkhorn_reach_scale), mass_q=sinkhorn_mass_q(sinkhorn_mass, nums, tnums),
+                want_err=stats is not None)
+            if stats is not None:
+                stats['transported'] = float(out[4].mean())
+            return out[0]
         step = model.engine.train_step_transport if loss in TRANSPORT_LOSSES else model.engine.train_step_divergence
         value = step(states, _np(attrs), _np(particle_nums, np.int32), dens, _np(data[6]), _np(data[7], np.int32),
                      transport_eps(dens, transport_eps_scale), int(transport_iters),
@@ -355,7 +421,8 @@ def check_probe_options(loss, grad_probe_every, probe_every):
 
 def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=None, first_epoch=0, grad_probe_every=0,
           loss='mse', impulses='data', probe_every=0, match_weight=0.5, transport_eps_scale=TRANSPORT_EPS_SCALE,
-          transport_iters=TRANSPORT_ITERS, sinkhorn_probe_every=0, match_probe_every=0):
+          transport_iters=TRANSPORT_ITERS, sinkhorn_probe_every=0, match_probe_every=0, sinkhorn_reach_scale=None,
+          sinkhorn_mass='unit'):
     """train/train_gnn_dyn.py:134-246 without the file I/O: `dataloaders` = {'train': iterable of
     collated batches, 'valid': ...}.  Returns {'best_valid_loss', 'history': [(epoch, phase, rmse)]}.
     ckp(epoch, i, model): called after training batch i when i % ckp_per_iter == 0 (:217-218); first_epoch: the epoch
@@ -376,11 +443,15 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
     older probe option, which keep refusing this loss: folding it into probe_every waits for a change of the tests that pin
     those refusals.  match_probe_every = k > 0: the same for a loss in MATCH_LOSSES (probe_batch_match with the run's
     match_weight); the log line also carries flipped and cost_gap -- the problems whose float64 optimum differs from the fp32
-    side's partners, and how far from optimal in double those are -- and, where a partner flipped, rel_own."""
+    side's partners, and how far from optimal in double those are -- and, where a partner flipped, rel_own.
+    sinkhorn_reach_scale, sinkhorn_mass: run_batch's unbalanced divergence (check_sinkhorn_options: a loss in DIVERGENCE_LOSSES
+    alone, 'count' only with a reach, no sinkhorn_probe_every beside a reach); the training log line then carries the batch's
+    mean transported."""
     check_probe_options(loss, grad_probe_every, probe_every)
     check_sinkhorn_probe_option(loss, sinkhorn_probe_every, grad_probe_every, probe_every)
     check_match_probe_option(loss, match_probe_every, grad_probe_every, probe_every, sinkhorn_probe_every)
     check_loss(loss, match_weight, transport_eps_scale, transport_iters)
+    check_sinkhorn_options(loss, sinkhorn_reach_scale, sinkhorn_mass, sinkhorn_probe_every, transport_eps_scale)
     if impulses not in IMPULSES:
         raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
     loss_kind = loss
@@ -413,12 +484,16 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
                             line += ', flipped %d, cost_gap %.3e' % (pr['flipped'], pr['cost_gap'])
                             line += ', rel_own %.3e' % pr['rel_own'] if 'rel_own' in pr else ''
                         log(line + (', min_margin %.3e' % pr['min_margin'] if loss_kind == 'chamfer' else ''))
+                logged = log is not None and i % tc['log_per_iter'] == 0
+                stats = {} if logged and sinkhorn_reach_scale is not None else None
                 loss = run_batch(model, optimizer, data, phase, n_rollout, loss=loss_kind, impulses=impulses, match_weight=match_weight,
-                                 transport_eps_scale=transport_eps_scale, transport_iters=transport_iters)
+                                 transport_eps_scale=transport_eps_scale, transport_iters=transport_iters,
+                                 sinkhorn_reach_scale=sinkhorn_reach_scale, sinkhorn_mass=sinkhorn_mass, stats=stats)
                 meter.update(loss, _np(data[0]).shape[0])
-                if log is not None and i % tc['log_per_iter'] == 0:
+                if logged:
                     log('%s [%d][%d] LR: %.6f, Loss: %.6f (%.6f)' % (phase, epoch, i, optimizer.param_groups[0]['lr'],
-                                                                      np.sqrt(loss), np.sqrt(meter.avg)))
+                                                                      np.sqrt(loss), np.sqrt(meter.avg))
+                        + (', transported %.4f' % stats['transported'] if stats is not None else ''))
                 if ckp is not None and phase == 'train' and i % tc['ckp_per_iter'] == 0:
                     ckp(epoch, i, model)
             history.append((epoch, phase, float(np.sqrt(meter.avg))))
@@ -452,7 +527,8 @@ def set_seed(seed):
 
 def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8, n_epoch=None, engine=None, grad_probe_every=0,
          loss=None, impulses=None, probe_every=0, data='particles', target_den_scale=1.0, match_weight=0.5,
-         transport_eps_scale=TRANSPORT_EPS_SCALE, transport_iters=TRANSPORT_ITERS, sinkhorn_probe_every=0, match_probe_every=0):
+         transport_eps_scale=TRANSPORT_EPS_SCALE, transport_iters=TRANSPORT_ITERS, sinkhorn_probe_every=0, match_probe_every=0,
+         sinkhorn_reach_scale=None, sinkhorn_mass='unit'):
     """The file-level part of train/train_gnn_dyn.py:train() (:45-130, :196-228): seed, the log directory with config.yaml
     and log.txt, the 'train' / 'valid' ParticleDatasets and their DeviceLoaders, a fresh model (torch.nn.Linear's default
     initialisation) or the resumed checkpoint, net_epoch_%d_iter_%d.pth every ckp_per_iter training batches and
@@ -467,7 +543,7 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
     times the state's density), which implies loss='chamfer' and impulses='actions'; a contradicting value is refused.  loss /
     impulses None: 'mse' / 'data', or what data implies.  loss in MATCH_LOSSES (with match_weight for the mix): as 'chamfer', on
     particles or depth; loss in TRANSPORT_LOSSES or DIVERGENCE_LOSSES (with transport_eps_scale and transport_iters) likewise.  chunk None: the
-    dataset's default (64 samples; 16 for data='depth')."""
+    dataset's default (64 samples; 16 for data='depth').  sinkhorn_reach_scale, sinkhorn_mass: train's."""
     import time
     import yaml
     from . import synthetic, weights
@@ -478,6 +554,7 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
     check_sinkhorn_probe_option(loss, sinkhorn_probe_every, grad_probe_every, probe_every)
     check_match_probe_option(loss, match_probe_every, grad_probe_every, probe_every, sinkhorn_probe_every)
     check_loss(loss, match_weight, transport_eps_scale, transport_iters)
+    check_sinkhorn_options(loss, sinkhorn_reach_scale, sinkhorn_mass, sinkhorn_probe_every, transport_eps_scale)
     tc = config['train']
     resume = tc['particle'].get('resume', {'active': False, 'epoch': 0, 'iter': 0})
     if cam is None:
@@ -527,7 +604,8 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
                        first_epoch=resume['epoch'] if resume['active'] and resume['epoch'] > 0 else 0,
                        grad_probe_every=grad_probe_every, loss=loss, impulses=impulses, probe_every=probe_every,
                        match_weight=match_weight, transport_eps_scale=transport_eps_scale, transport_iters=transport_iters,
-                       sinkhorn_probe_every=sinkhorn_probe_every, match_probe_every=match_probe_every)
+                       sinkhorn_probe_every=sinkhorn_probe_every, match_probe_every=match_probe_every,
+                       sinkhorn_reach_scale=sinkhorn_reach_scale, sinkhorn_mass=sinkhorn_mass)
         for epoch, phase, rmse in result['history']:
             if phase == 'grad_probe':                   # logged when it was taken
                 continue
@@ -577,11 +655,20 @@ def _cli(argv=None):
                     help='--loss transport, sinkhorn: eps = scale / particle density per sample (1: the plan blurs over one particle spacing)')
     ap.add_argument('--transport-iters', type=int, default=TRANSPORT_ITERS,
                     help='--loss transport, sinkhorn: Sinkhorn sweeps per problem, 1..%d' % TRANSPORT_MAX_ITERS)
+    ap.add_argument('--sinkhorn-reach-scale', type=float, default=None,
+                    help='--loss sinkhorn: the unbalanced divergence for a pile seen partly, reach = scale / particle density per sample '
+                         '(the unit of --transport-eps-scale: 4 is a reach of two particle spacings); mass further than that from the '
+                         'other cloud is given up, not moved (default: balanced)')
+    ap.add_argument('--sinkhorn-mass', choices=SINKHORN_MASSES, default='unit',
+                    help='--sinkhorn-reach-scale: the target cloud\'s total mass against the prediction\'s 1 -- unit: 1; count: its '
+                         'point count over the prediction\'s, equal mass per point (targets sampled at the particles\' spacing)')
     ap.add_argument('--impulses', choices=IMPULSES, default=None,
                     help='(default data) actions: compute every step\'s impulse from the recorded push on the state the model predicted')
     a = ap.parse_args(argv)
     try:
         check_loss(resolve_data_options(a.data, a.loss, a.impulses)[0], a.match_weight, a.transport_eps_scale, a.transport_iters)
+        check_sinkhorn_options(resolve_data_options(a.data, a.loss, a.impulses)[0], a.sinkhorn_reach_scale, a.sinkhorn_mass,
+                               a.sinkhorn_probe_every, a.transport_eps_scale)
     except ValueError as e:
         ap.error(str(e))
     config = default_config()
@@ -596,7 +683,8 @@ def _cli(argv=None):
                      grad_probe_every=a.grad_probe_every, loss=a.loss, impulses=a.impulses, probe_every=a.probe_every,
                      data=a.data, target_den_scale=a.target_den_scale, match_weight=a.match_weight,
                      transport_eps_scale=a.transport_eps_scale, transport_iters=a.transport_iters,
-                     sinkhorn_probe_every=a.sinkhorn_probe_every, match_probe_every=a.match_probe_every)
+                     sinkhorn_probe_every=a.sinkhorn_probe_every, match_probe_every=a.match_probe_every,
+                     sinkhorn_reach_scale=a.sinkhorn_reach_scale, sinkhorn_mass=a.sinkhorn_mass)
     print('best valid loss %.6f, checkpoints in %s' % (np.sqrt(result['best_valid_loss']), d))
 
 

@@ -567,7 +567,7 @@ int drp_ptcl_dataset_time(drp_ctx* ctx, float* ms_out);
 /* HIP-event timing of one kernel class on the context's stream.  name: "graph",
  * "node_encode", "edge_encode", "project", "aggregate", "update", "predict", "reward",
  * "mppi", "prop" (the fused propagation-step kernel of DRP_ENGINE_FUSED / _LITE), "loss" (the stand-alone metrics' kernel:
- * drp_cloud_chamfer, drp_cloud_match, drp_cloud_transport, drp_cloud_divergence, drp_cloud_divergence_f64, drp_cloud_match_f64).  drp_probe_read returns total ms and launches since drp_probe_begin. */
+ * drp_cloud_chamfer, drp_cloud_match, drp_cloud_transport, drp_cloud_divergence, drp_cloud_divergence_unbalanced, drp_cloud_divergence_f64, drp_cloud_match_f64).  drp_probe_read returns total ms and launches since drp_probe_begin. */
 int drp_probe_begin(drp_ctx* ctx, const char* kernel_class);
 int drp_probe_read(drp_ctx* ctx, double* total_ms, long* launches);
 /* Kernel launches inside the timed regions of the "prop" / "prop+work" probe since drp_probe_begin.  drp_probe_read's `launches`
@@ -892,6 +892,49 @@ int drp_train_step_divergence(drp_ctx* ctx, const float* states, const float* st
                               const float* targets /*[B][H][M][3]*/, const int32_t* target_nums /*[B][H]*/, int M,
                               const double* eps /*[B]*/, int iters, int mode, double* loss_out, float* grad_out,
                               double* col_err_out /*[H][B], nullable*/, double* self_err_out /*[H][B][2], nullable*/);
+
+/* ---- Unbalanced Sinkhorn divergence (csrc/k_divergence.h: kd_sweeps_unbalanced): drp_cloud_divergence for a pile
+ * seen partly.  The balanced plan must place every predicted particle's mass on the observed cloud, so a particle whose
+ * counterpart was not observed is pulled hardest.  Here each marginal is held by a KL penalty in place of the hard constraint
+ * (Sejourne et al. 2019): mass further than about sqrt(rho) from the other cloud is given up, not moved.  Two more quantities per
+ * problem: the reach rho = rho[b] > 0, in squared-distance units like eps, and the target cloud's total mass w = mass_q[b] > 0.
+ * a = 1/n_p per predicted row (total 1), b = w/n_q per target row (total w), lambda = rho / (rho + eps).  Notation as above.
+ *   Cross problem.  f = 0.  K times: g_j <- lambda (-eps LSE_i((f_i - C_ij)/eps + log a)), then
+ *                f_i <- lambda (-eps LSE_j((g_j - C_ij)/eps + log b)).  P_ij = a b exp((f_i + g_j - C_ij)/eps).
+ *   Self problem of a cloud with per-row mass m (a for p, b for q).  h = 0.  K times, Jacobi on the previous sweep's h:
+ *                h_j <- (h_j + lambda (-eps LSE_i((h_i - C_ij)/eps + log m))) / 2.  S_ij = m^2 exp((h_i + h_j - C_ij)/eps).
+ *   Value.       scale (rho + eps/2) [sum_i a (expm1(-h^p_i/rho) - expm1(-f_i/rho)) + sum_j b (expm1(-h^q_j/rho) - expm1(-g_j/rho))] / 3,
+ *                not clamped.  At the fixed point this is OT_rho(p,q) - OT_rho(p,p)/2 - OT_rho(q,q)/2 + (eps/2)(1 - w)^2: every
+ *                term in the masses cancels.  expm1 because the two exponentials cancel for large rho; the limit for
+ *                rho -> inf is the balanced value.  Summed as -expm1(-f/rho) and -expm1(-g/rho) in the cross problem's order, less
+ *                the two self problems' sums, times (rho + eps/2).
+ *   Gradient.    The balanced expression with these P and S^p: the cost enters the relaxed problem through <P, C> alone.
+ *   Certificates.  col_err = sum_j |sum_i P_ij - b exp(-g_j/rho)| (the row identity sum_j P_ij = a exp(-f_i/rho) holds exactly
+ *                behind f's update).  self_err = [sum_i |sum_j S^p_ij - a exp(-h^p_i/rho)|, sum_j |sum_i S^q_ij - b exp(-h^q_j/rho)|].
+ *                transported = sum_i a exp(-f_i/rho): the plan's total mass, the share of the predicted pile the loss pairs
+ *                with something; 1 when balanced.
+ *   rho = +inf   is allowed and means lambda = 1, the balanced value and certificates.  It requires w == 1 exactly (balanced
+ *                transport between unequal masses has no plan); every output then has drp_cloud_divergence's bits.
+ * Refused with DRP_EINVAL and a message, on the host, before any launch: everything drp_cloud_divergence refuses; rho or mass_q
+ * NULL; rho[b] not (finite with rho[b] >= eps[b]/1024, or +inf) -- below that f/rho means nothing but "no transport";
+ * mass_q[b] outside [1/8, 8]; mass_q[b] != 1 with rho[b] = +inf.  Same grid, LDS and fixed work as drp_cloud_divergence; no
+ * float64 yardstick yet. */
+int drp_cloud_divergence_unbalanced(drp_ctx* ctx, const float* p, const int32_t* n_p, const float* q, const int32_t* n_q,
+                                    int B, int N, int M, const double* eps /*[B]*/, const double* rho /*[B]*/,
+                                    const double* mass_q /*[B]*/, int iters, double* terms_out /*[B]*/,
+                                    float* grad_p_out /*[B][N][3], nullable*/, double* dual_out /*[B][2N+2M]: f, g, h_p, h_q, nullable*/,
+                                    double* col_err_out /*[B], nullable*/, double* self_err_out /*[B][2], nullable*/,
+                                    double* transported_out /*[B], nullable*/);
+
+/* drp_train_step_divergence with drp_cloud_divergence_unbalanced as each step's term: rho [B] per sample, mass_q [H][B] per
+ * problem (step-major, as the certificates), transported_out [H][B] (nullable).  The same refusals on top of that call's. */
+int drp_train_step_divergence_unbalanced(drp_ctx* ctx, const float* states, const float* states_delta /*or NULL*/,
+                                         const float* actions /*or NULL*/, const float* attrs, const int32_t* particle_nums,
+                                         const float* particle_dens, int B, int N, const float* targets /*[B][H][M][3]*/,
+                                         const int32_t* target_nums /*[B][H]*/, int M, const double* eps /*[B]*/,
+                                         const double* rho /*[B]*/, const double* mass_q /*[H][B]*/, int iters, int mode,
+                                         double* loss_out, float* grad_out, double* col_err_out /*[H][B], nullable*/,
+                                         double* self_err_out /*[H][B][2], nullable*/, double* transported_out /*[H][B], nullable*/);
 
 /* ---- the float64 yardstick of the Sinkhorn divergence (csrc/k_divergence_f64.h).  drp_cloud_divergence's definition with nothing
  * in fp32: p is DOUBLE [B][N][3] -- on purpose: the call runs the instantiation the trainer's yardstick runs on the float64

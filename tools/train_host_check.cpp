@@ -19,7 +19,11 @@
 // drp_cloud_divergence_f64's buffer of its own (divergence64_layout: p as doubles), every block written in full; the finiteness
 // check on double rows.  The matching losses' float64 yardstick: the caller's partners [H][B][N] behind the float64 upload
 // (tr64_layout with `match_in`), drp_cloud_match_f64's buffer of its own (match64_layout, with and without match_in), and the
-// check of a matching given by the caller (check_matching) on arrays of exactly [N].  No device is touched.
+// check of a matching given by the caller (check_matching) on arrays of exactly [N].  The unbalanced Sinkhorn divergence:
+// divergence_unbalanced_layout (eps | rho | mass_q side by side, the scratch, transported, inside a block of exactly its `bytes`,
+// the five blocks that come back where divergence_layout has them), the trainer's rho [B] | mass_q [H][B] behind eps (tr_layout
+// with `reach`) and transported behind its doubles (tr_div_loss_layout with `unbalanced`), nothing ahead of them moved, and the
+// check of a reach and a target mass (check_reach) at the edges of its ranges.  No device is touched.
 //
 //   train_host_check layout64 B H N M actions     prints tr64_layout's eight fields (4-byte words) and exits
 #include <cstdio>
@@ -371,6 +375,71 @@ static void stage_div_loss(int B, int H, int N) {
     for (int k = 0; k < 5; ++k) EXPECT(d[off[k]] == (double)k && d[off[k + 1] - 1] == (double)k);
     std::free(d);
 }
+// drp_cloud_divergence_unbalanced: divergence_layout's five blocks where they were; behind them eps | rho | mass_q [B] each, side
+// by side (one copy up), the same scratch, then transported [B], all inside a block of exactly `bytes`
+static void stage_divergence_unbalanced(int B, int N, int M) {
+    const size_t bn = (size_t)B * N;
+    const DivUnbalancedLayout lay = divergence_unbalanced_layout(B, N, M);
+    const DivLayout plain = divergence_layout(B, N, M);
+    for (int k = 0; k < CLOUD_MAX_OUT; ++k) EXPECT(lay.cloud.out[k] == plain.cloud.out[k] && lay.cloud.out_bytes[k] == plain.cloud.out_bytes[k]);
+    EXPECT(lay.cloud.in_bytes == plain.cloud.in_bytes && lay.cloud.n_out == plain.cloud.n_out && lay.eps == plain.eps);
+    EXPECT(lay.rho == lay.eps + (size_t)B * 8 && lay.mass_q == lay.rho + (size_t)B * 8);
+    const size_t off[] = {lay.eps, lay.vals, lay.gsum, lay.transported, lay.cloud.bytes};
+    const size_t xlen[] = {(size_t)3 * B * 8, (size_t)3 * B * 8, 2 * bn * 3 * 8, (size_t)B * 8};
+    char* io = static_cast<char*>(std::malloc(lay.cloud.bytes));
+    for (int k = 0; k < 4; ++k) {
+        EXPECT(off[k] % 16 == 0);
+        EXPECT(off[k] + xlen[k] <= off[k + 1] && off[k + 1] - (off[k] + xlen[k]) < 16);
+        std::memset(io + off[k], k + 1, xlen[k]);
+    }
+    for (int k = 0; k < 4; ++k) EXPECT(io[off[k]] == k + 1 && io[off[k] + xlen[k] - 1] == k + 1);
+    reinterpret_cast<double*>(io + lay.transported)[B - 1] = 1.0;
+    reinterpret_cast<double*>(io + lay.mass_q)[B - 1] = 1.0;
+    std::free(io);
+}
+// drp_train_step_divergence_unbalanced: the balanced step's doubles where they were, transported [H][B] behind them; and its batch:
+// rho [B] | mass_q [H][B] behind eps, nothing ahead of them moved
+static void stage_div_unbalanced_train(int B, int H, int N, int M, bool actions) {
+    const TrDivLoss dl = tr_div_loss_layout(B, H, N, true), plain = tr_div_loss_layout(B, H, N);
+    const size_t hb = (size_t)H * B;
+    EXPECT(dl.terms == plain.terms && dl.col_err == plain.col_err && dl.self_err == plain.self_err && dl.vals == plain.vals &&
+           dl.gsum == plain.gsum);
+    EXPECT(dl.transported == plain.count && dl.count == dl.transported + hb && plain.transported == 0);
+    double* d = static_cast<double*>(std::malloc(dl.count * sizeof(double)));
+    for (size_t e = 0; e < hb; ++e) d[dl.transported + e] = 1.0;
+    EXPECT(d[dl.count - 1] == 1.0);
+    std::free(d);
+    const TrArena lay = tr_layout(B, H, N, M, actions, true, true), bal = tr_layout(B, H, N, M, actions, true);
+    EXPECT(lay.states == bal.states && lay.sdelta == bal.sdelta && lay.attrs == bal.attrs && lay.dens == bal.dens && lay.nums == bal.nums &&
+           lay.targets == bal.targets && lay.tnums == bal.tnums && lay.eps == bal.eps);
+    EXPECT(lay.rho == bal.bytes && lay.rho % 16 == 0 && lay.mass_q % 16 == 0 && lay.bytes % 16 == 0);
+    EXPECT(lay.rho + (size_t)B * 8 <= lay.mass_q && lay.mass_q - (lay.rho + (size_t)B * 8) < 16);
+    EXPECT(lay.mass_q + hb * 8 <= lay.bytes && lay.bytes - (lay.mass_q + hb * 8) < 16);
+    EXPECT(tr_layout(B, H, N, M, actions, false, true).bytes == tr_layout(B, H, N, M, actions).bytes);     // a reach without eps: nothing
+    std::vector<double> rho(B, 0.5), w(hb, 2.0);
+    char* pin = static_cast<char*>(std::malloc(lay.bytes));
+    std::memset(pin, 0xff, lay.bytes);
+    std::memcpy(pin + lay.rho, rho.data(), (size_t)B * sizeof(double));
+    std::memcpy(pin + lay.mass_q, w.data(), hb * sizeof(double));
+    double last;
+    std::memcpy(&last, pin + lay.mass_q + (hb - 1) * 8, 8);
+    EXPECT(last == 2.0);
+    std::memcpy(&last, pin + lay.rho + (size_t)(B - 1) * 8, 8);
+    EXPECT(last == 0.5);
+    std::free(pin);
+}
+// the reach and the target mass a problem of the unbalanced divergence is served with (check_reach)
+static void check_reaches() {
+    const double inf64 = std::numeric_limits<double>::infinity(), nan64 = std::numeric_limits<double>::quiet_NaN();
+    const double eps = 4e-4;
+    EXPECT(check_reach(eps, 4 * eps, 1.0) == REACH_OK && check_reach(eps, eps / 1024, 0.125) == REACH_OK);
+    EXPECT(check_reach(eps, 4 * eps, 8.0) == REACH_OK && check_reach(eps, inf64, 1.0) == REACH_OK);
+    EXPECT(check_reach(eps, 0.0, 1.0) == REACH_RHO && check_reach(eps, -eps, 1.0) == REACH_RHO && check_reach(eps, nan64, 1.0) == REACH_RHO);
+    EXPECT(check_reach(eps, -inf64, 1.0) == REACH_RHO && check_reach(eps, eps / 1025, 1.0) == REACH_RHO);
+    EXPECT(check_reach(eps, 4 * eps, 0.1249) == REACH_MASS && check_reach(eps, 4 * eps, 8.001) == REACH_MASS);
+    EXPECT(check_reach(eps, 4 * eps, nan64) == REACH_MASS && check_reach(eps, 4 * eps, 0.0) == REACH_MASS && check_reach(eps, inf64, nan64) == REACH_MASS);
+    EXPECT(check_reach(eps, inf64, 0.6) == REACH_INF_MASS && check_reach(eps, inf64, 8.0) == REACH_INF_MASS);
+}
 // drp_train_step_transport's batch: eps [B] (doubles) behind everything else, the other blocks where they were
 static void stage_eps(int B, int H, int N, int M, bool actions) {
     const TrArena lay = tr_layout(B, H, N, M, actions, true), plain = tr_layout(B, H, N, M, actions);
@@ -438,6 +507,7 @@ int main(int argc, char** argv) {
         stage_match(s[0], s[1], s[2]);
         stage_transport(s[0], s[1], s[2]);
         stage_divergence(s[0], s[1], s[2]);
+        stage_divergence_unbalanced(s[0], s[1], s[2]);
         stage_divergence64(s[0], s[1], s[2]);
         stage_match64(s[0], s[1], s[2], false);
         stage_match64(s[0], s[1], s[2], true);
@@ -447,7 +517,11 @@ int main(int argc, char** argv) {
     for (const auto& s : dshapes) stage_div_loss(s[0], s[1], s[2]);
     for (const auto& s : shapes)
         for (int actions = 0; actions < 2; ++actions)
-            if (s[3] > 0) stage_eps(s[0], s[1], s[2], s[3], actions != 0);
+            if (s[3] > 0) {
+                stage_eps(s[0], s[1], s[2], s[3], actions != 0);
+                stage_div_unbalanced_train(s[0], s[1], s[2], s[3], actions != 0);
+            }
+    check_reaches();
     {
         // the regularisation strengths: every one read, none beyond the B-th
         const double inf64 = std::numeric_limits<double>::infinity(), nan64 = std::numeric_limits<double>::quiet_NaN();

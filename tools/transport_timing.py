@@ -15,6 +15,10 @@
 (d) python tools/transport_timing.py --divergence-f64 [output file] -> profiles/divergence_f64_timing.txt: the float64 yardstick
     (csrc/k_divergence_f64.h: kd64_sweeps and kd64_combine, one timed region) beside kd_sweeps + kd_combine on the same clouds
     (p widened exactly), 20 problems at 100 x 100 and 300 x 300, measured as (a).  A yardstick's cost, not an engine's.
+(e) python tools/transport_timing.py --unbalanced [output file] -> profiles/divergence_unbalanced_timing.txt: the unbalanced
+    divergence (kd_sweeps_unbalanced and kd_combine, one timed region; rho = 4 eps) beside the balanced kernels, interleaved on
+    one context on the same clouds, 20 problems at 100 x 100 and 300 x 300, measured as (a); and a whole update at 4 x 5 x 100
+    under 'sinkhorn' with and without a reach, measured as (b).
 Each measurement runs in a child process of its own under a time limit (a stuck step ends there, and nothing follows it)."""
 import subprocess
 import sys
@@ -126,6 +130,39 @@ def divergence_f64_kernel_times(n, m):
              med['kd64_sweeps + kd64_combine'] / med['kd_sweeps + kd_combine']), flush=True)
 
 
+UNBALANCED_REACH_PER_EPS = 4.0      # a reach of two particle spacings
+
+
+def unbalanced_kernel_times(n, m):
+    from dyn_res_pile_manip_amd import train_gnn_dyn as TG
+    from dyn_res_pile_manip_amd.engine import Engine
+    eng = Engine(0)
+    p, q = clouds(n, m, 7 * n + m)
+    eps, K = TG.TRANSPORT_EPS_SCALE * SPACING ** 2, TG.TRANSPORT_ITERS
+    rho = UNBALANCED_REACH_PER_EPS * eps
+    calls = (('kd_sweeps + kd_combine', lambda: eng.cloud_divergence(p, q, eps=eps, iters=K, want_grad=True)),
+             ('kd_sweeps_unbalanced + kd_combine', lambda: eng.cloud_divergence(p, q, eps=eps, iters=K, want_grad=True, reach=rho)))
+    for _ in range(3):
+        for _, call in calls:
+            call()
+    took = dict((name, []) for name, _ in calls)
+    for _ in range(21):
+        for name, call in calls:
+            eng.probe_begin('loss')
+            call()
+            ms, launches = eng.probe_read()
+            assert launches == 1
+            took[name].append(ms)
+    eng.probe_begin(None)
+    moved = eng.cloud_divergence(p, q, eps=eps, iters=K, reach=rho, want_transported=True)['transported']
+    eng.close()
+    med = dict((name, float(np.median(took[name]))) for name in took)
+    print('%d problems of %d x %d, K = %d, rho = %g eps: %s; unbalanced = %.3f x balanced; transported %.3f .. %.3f'
+          % (PROBLEMS, n, m, K, UNBALANCED_REACH_PER_EPS,
+             ', '.join('%s %.4f ms (%.4f .. %.4f)' % (name, med[name], min(took[name]), max(took[name])) for name, _ in calls),
+             med['kd_sweeps_unbalanced + kd_combine'] / med['kd_sweeps + kd_combine'], moved.min(), moved.max()), flush=True)
+
+
 def update_times(kinds=('chamfer', 'match', 'transport')):
     from dyn_res_pile_manip_amd import synthetic as syn, train_gnn_dyn as TG, weights
     from dyn_res_pile_manip_amd.engine import Engine
@@ -153,6 +190,9 @@ def update_times(kinds=('chamfer', 'match', 'transport')):
             return eng.train_step_transport(states, attrs, pn, dens, targets, tn, eps, K, states_delta=sdelta, mode='update')
         if k == 'sinkhorn':
             return eng.train_step_divergence(states, attrs, pn, dens, targets, tn, eps, K, states_delta=sdelta, mode='update')
+        if k == 'sinkhorn, reach':
+            return eng.train_step_divergence(states, attrs, pn, dens, targets, tn, eps, K, states_delta=sdelta, mode='update',
+                                             reach=UNBALANCED_REACH_PER_EPS * eps)
         return eng.train_step_loss(states, attrs, pn, dens, targets, tn, states_delta=sdelta, loss=k, mode='update')
     for k in kinds:
         step(k), step(k)
@@ -170,7 +210,9 @@ def update_times(kinds=('chamfer', 'match', 'transport')):
     med = dict((k, float(np.median(took[k]))) for k in kinds)
     print('update at B=%d n_rollout=%d N=M=%d, K = %d: %s' % (B, H, N, K, ', '.join("'%s' %.3f ms (blocks %.3f .. %.3f)"
           % (k, med[k], min(took[k]), max(took[k])) for k in kinds)), flush=True)
-    if 'sinkhorn' in kinds:
+    if 'sinkhorn, reach' in kinds:
+        print("a 'sinkhorn' update with a reach costs %.3f balanced ones" % (med['sinkhorn, reach'] / med['sinkhorn'],), flush=True)
+    elif 'sinkhorn' in kinds:
         print("a 'sinkhorn' update costs %.2f 'transport' updates" % (med['sinkhorn'] / med['transport'],), flush=True)
     else:
         print("a 'transport' update costs %.2f 'chamfer' updates and %.2f 'match' updates"
@@ -188,12 +230,18 @@ if __name__ == '__main__':
         update_times(('transport', 'sinkhorn'))
     elif len(sys.argv) > 1 and sys.argv[1] == '--divergence-f64-kernel':
         divergence_f64_kernel_times(int(sys.argv[2]), int(sys.argv[3]))
+    elif len(sys.argv) > 1 and sys.argv[1] == '--unbalanced-kernel':
+        unbalanced_kernel_times(int(sys.argv[2]), int(sys.argv[3]))
+    elif len(sys.argv) > 1 and sys.argv[1] == '--unbalanced-update':
+        update_times(('sinkhorn', 'sinkhorn, reach'))
     else:
         divergence = len(sys.argv) > 1 and sys.argv[1] == '--divergence'
         f64 = len(sys.argv) > 1 and sys.argv[1] == '--divergence-f64'
-        rest = sys.argv[2:] if divergence or f64 else sys.argv[1:]
+        unbalanced = len(sys.argv) > 1 and sys.argv[1] == '--unbalanced'
+        rest = sys.argv[2:] if divergence or f64 or unbalanced else sys.argv[1:]
         out = rest[0] if rest else ('profiles/divergence_timing.txt' if divergence else
-                                    'profiles/divergence_f64_timing.txt' if f64 else 'profiles/transport_timing.txt')
+                                    'profiles/divergence_f64_timing.txt' if f64 else
+                                    'profiles/divergence_unbalanced_timing.txt' if unbalanced else 'profiles/transport_timing.txt')
         lines = ['tools/transport_timing.py: device time of the loss kernels by HIP events (median of 21 interleaved launches, min ..',
                  'max), and host time of whole update steps (median of 6 interleaved blocks of 10); one MI355X', '']
         jobs = [['--kernel', str(n), str(m)] for n, m in SIZES] + [['--update']]
@@ -203,6 +251,9 @@ if __name__ == '__main__':
         if f64:
             lines[0] = lines[0].replace('tools/transport_timing.py:', 'tools/transport_timing.py --divergence-f64:')
             jobs = [['--divergence-f64-kernel', str(n), str(n)] for n in DIVERGENCE_SIZES]
+        if unbalanced:
+            lines[0] = lines[0].replace('tools/transport_timing.py:', 'tools/transport_timing.py --unbalanced:')
+            jobs = [['--unbalanced-kernel', str(n), str(n)] for n in DIVERGENCE_SIZES] + [['--unbalanced-update']]
         for job in jobs:
             r = subprocess.run(['timeout', '-k', '10', str(STEP_LIMIT_S), sys.executable, __file__] + job, stdout=subprocess.PIPE,
                                stderr=subprocess.STDOUT, universal_newlines=True)
@@ -210,5 +261,15 @@ if __name__ == '__main__':
             if r.returncode != 0:
                 raise SystemExit('step %s ended with status %d: nothing further is started' % (job, r.returncode))
             lines += [ln for ln in r.stdout.splitlines() if 'problems of' in ln or 'update' in ln]
+        if unbalanced:
+            # the balanced kernels in this run against the figures profiles/divergence_timing.txt recorded for them: a templating
+            # that leaked into the balanced path shows here
+            import re
+            pat = re.compile(r'(\d+ x \d+), K = \d+.*?kd_sweeps \+ kd_combine ([0-9.]+) ms')
+            now = dict(m.groups() for m in map(pat.search, lines) if m)
+            with open('profiles/divergence_timing.txt') as f:
+                then = dict(m.groups() for m in map(pat.search, f) if m)
+            lines.append('kd_sweeps + kd_combine in this run against profiles/divergence_timing.txt: ' + ', '.join(
+                '%s %s against %s ms (%.3f x)' % (k, now[k], then[k], float(now[k]) / float(then[k])) for k in now if k in then))
         with open(out, 'w') as f:
             f.write('\n'.join(lines) + '\n')
