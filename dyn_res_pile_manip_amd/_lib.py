@@ -235,6 +235,14 @@ SIGNATURES = {
     'drp_cloud_divergence_f64': (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_int32_p, c_float_p, c_int32_p, ctypes.c_int,
                                                 ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, c_double_p,
                                                 c_double_p, c_double_p, c_double_p]),
+    'drp_cloud_divergence_unbalanced_f64': (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_int32_p, c_float_p, c_int32_p, ctypes.c_int,
+                                                           ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p, ctypes.c_int,
+                                                           c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    'drp_train_grad_f64_divergence_unbalanced': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, c_int32_p,
+                                                                c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_float_p,
+                                                                c_int32_p, ctypes.c_int, c_double_p, c_double_p, c_double_p,
+                                                                ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p,
+                                                                c_double_p, c_double_p, c_double_p]),
     'drp_train_grad_f64_divergence': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, c_int32_p,
                                                      c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_float_p, c_int32_p,
                                                      ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, c_double_p, c_double_p,

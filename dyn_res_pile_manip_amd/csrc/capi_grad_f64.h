@@ -303,6 +303,8 @@ struct Tr64Io {
     const double* eps;              // the Sinkhorn divergence (non-null): the regularisation strengths [B], with `iters` sweeps,
     int iters;                      //   against the same targets; its certificates behind the total: col_err [H][B], self_err [H][B][2]
     double *col_err, *self_err;
+    const double *rho, *mass_q;     // the unbalanced divergence (non-null): the reaches [B] and the targets' masses [H][B] of the
+    double* transported;            //   BATCH (the kernels index them by b_off + b), and behind self_err transported [H][B]
     int match_kind;                 // the matching losses (TR_LOSS_MATCH, TR_LOSS_CHAMFER_MATCH; else 0) against the same targets:
     double match_weight;            //   the mix's weight; the caller's pairs [H][B][N] (nullable: the kernel's own optimum); behind
     const int* match_in;            //   the margins the costs [H][B][2] and the optimum's partners [H][B][N]
@@ -351,8 +353,14 @@ int tr64_chunk(drp_ctx* c, const Tr64Ws& k, const Tr64Io& io, int b0, int bc, in
         a.scale = 1.0 / ((double)H * (double)B);
         a.vals = k.div_vals; a.gsum = k.div_gsum;
         a.grad = k.rev.g_state; a.terms = io.terms; a.col_err = io.col_err; a.self_err = io.self_err;
-        hipLaunchKernelGGL(kd64_sweeps, dim3(bc, H, 3), dim3(KT_THREADS), 0, st, a);
-        hipLaunchKernelGGL(kd64_combine, dim3(bc, H), dim3(KD_COMBINE_THREADS), 0, st, a);
+        if (io.rho != nullptr) {
+            a.rho = io.rho; a.mass_q = io.mass_q; a.transported = io.transported;
+            hipLaunchKernelGGL(kd64_sweeps_unbalanced, dim3(bc, H, 3), dim3(KT_THREADS), 0, st, a);
+            hipLaunchKernelGGL(kd64_combine_unbalanced, dim3(bc, H), dim3(KD_COMBINE_THREADS), 0, st, a);
+        } else {
+            hipLaunchKernelGGL(kd64_sweeps, dim3(bc, H, 3), dim3(KT_THREADS), 0, st, a);
+            hipLaunchKernelGGL(kd64_combine, dim3(bc, H), dim3(KD_COMBINE_THREADS), 0, st, a);
+        }
     } else if (io.match_kind == TR_LOSS_MATCH) {
         // the same slot of the stream and the same outputs: the assignment solved here in double on the tape's own double states
         // (k_match_f64.h), the term and the seed on io.match_in's pairs where the caller gave them
@@ -478,6 +486,7 @@ int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, 
         if (N > KT_MAX_POINTS) return fail(c, DRP_EINVAL, "the Sinkhorn divergence takes at most %d points per cloud (N=%d)", KT_MAX_POINTS, N);
         CHK(check_target_nums(c, lk, B, n_rollout));
         CHK(check_transport_params(c, lk.eps, B, lk.iters));
+        if (lk.unbalanced()) CHK(check_reach_params(c, lk.eps, lk.rho, lk.mass_q, B, n_rollout));
     }
     if (actions) CHK(check_pushes(c, impulses, B, n_rollout));
     HIPCHK(c, hipSetDevice(c->device));
@@ -486,17 +495,17 @@ int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, 
     const int H = n_rollout;
     // samples per chunk: tape, reverse pass, weight gradients' operands and accumulators together
     Tr64Ws k{};
-    const bool div = lk.divergence();
+    const bool div = lk.divergence(), reach = lk.unbalanced();
     auto bytes_of = [&](size_t bc) { return k.carve(nullptr, bc, (size_t)N, (size_t)H, div); };
     size_t Bc;
     CHK(f64_size_chunks(c, B, N, ((size_t)1 << 24) / ((size_t)N * DRP_K), bytes_of, &Bc));
     k.carve(c->grad64_ws.p, Bc, (size_t)N, (size_t)H, div);
     // the whole batch's inputs in one upload (train_host.h: tr64_layout): states | impulses | attrs[:, 0] | densities | particle
-    // counts [| target clouds | their counts] [| eps] [| the caller's matching], then the results: terms | total [| margins]
-    // [| col_err | self_err] [| the matching's costs | its optimum's partners]
+    // counts [| target clouds | their counts] [| eps [| rho | mass_q]] [| the caller's matching], then the results: terms | total
+    // [| margins] [| col_err | self_err [| transported]] [| the matching's costs | its optimum's partners]
     const bool match = lk.match();
     const int M = lk.chamfer() || div || match ? lk.M : 0;
-    const Tr64Arena lay = tr64_layout(B, H, N, M, actions, div, match && lk.match_in != nullptr);
+    const Tr64Arena lay = tr64_layout(B, H, N, M, actions, div, match && lk.match_in != nullptr, reach);
     std::vector<float> host(lay.words);
     memcpy(host.data() + lay.states, states, (lay.sdelta - lay.states) * sizeof(float));
     memcpy(host.data() + lay.sdelta, impulses, (lay.attr - lay.sdelta) * sizeof(float));
@@ -508,12 +517,16 @@ int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, 
         memcpy(host.data() + lay.tnums, lk.target_nums, (size_t)B * H * sizeof(int32_t));
     }
     if (div) memcpy(host.data() + lay.eps, lk.eps, (size_t)B * sizeof(double));
+    if (reach) {
+        memcpy(host.data() + lay.rho, lk.rho, (size_t)B * sizeof(double));
+        memcpy(host.data() + lay.mass_q, lk.mass_q, (size_t)H * B * sizeof(double));
+    }
     if (match && lk.match_in) memcpy(host.data() + lay.match_in, lk.match_in, (size_t)H * B * N * sizeof(int32_t));
     const size_t n_terms = (size_t)H * B;
     // the matching kinds: behind the margins the costs [H][B][2], then the optimum's partners [H][B][N] (ints, two to a double)
     const size_t n_match = match ? 2 * n_terms + (n_terms * N + 1) / 2 : 0;
     Tr64Io io{};
-    CHK(f64_upload_batch(c, host, n_terms + (size_t)W_TOTAL + (div ? 3 * n_terms : M > 0 ? n_terms : 0) + n_match, &io.terms));
+    CHK(f64_upload_batch(c, host, n_terms + (size_t)W_TOTAL + (div ? (reach ? 4 : 3) * n_terms : M > 0 ? n_terms : 0) + n_match, &io.terms));
     io.states = ptr<float>(c->grad64_io); io.sdelta = io.states + lay.sdelta; io.attr = io.states + lay.attr; io.dens = io.states + lay.dens;
     io.nums = reinterpret_cast<const int*>(io.states + lay.nums);
     io.actions = actions;
@@ -525,6 +538,11 @@ int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, 
         if (div) {
             io.eps = reinterpret_cast<const double*>(io.states + lay.eps); io.iters = lk.iters;
             io.col_err = io.total + W_TOTAL; io.self_err = io.col_err + n_terms;
+            if (reach) {
+                io.rho = reinterpret_cast<const double*>(io.states + lay.rho);
+                io.mass_q = reinterpret_cast<const double*>(io.states + lay.mass_q);
+                io.transported = io.self_err + 2 * n_terms;
+            }
         } else {
             io.margin = io.total + W_TOTAL;
         }
@@ -546,6 +564,7 @@ int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, 
     if (match && lk.match_out) CHK(d2h(c, lk.match_out, io.match_out, n_terms * N * sizeof(int32_t)));
     if (div && lk.col_err_out) CHK(d2h(c, lk.col_err_out, io.col_err, n_terms * sizeof(double)));
     if (div && lk.self_err_out) CHK(d2h(c, lk.self_err_out, io.self_err, 2 * n_terms * sizeof(double)));
+    if (reach && lk.transported_out) CHK(d2h(c, lk.transported_out, io.transported, n_terms * sizeof(double)));
     CHK(guarded_wait(c, nullptr));          // (the upload's host block lives until here)
     if (loss_terms_out) memcpy(loss_terms_out, terms.data(), n_terms * sizeof(double));
     if (loss_out) {

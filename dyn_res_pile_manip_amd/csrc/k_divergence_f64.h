@@ -19,6 +19,13 @@
 // cloud, the fp32 call's limit.
 // CHUNKS.  The trainer runs samples [b_off, b_off + gridDim.x) of a batch of B: p, the gradient and the two scratch buffers are
 // the chunk's; q, the counts, eps, the terms and the certificates are the batch's (as Kc64Args).
+// UNBALANCED (kd64_sweeps_unbalanced, kd64_combine_unbalanced; include/drp.h: drp_cloud_divergence_unbalanced_f64).  k_divergence.h's
+// relaxation, by its method: the same bodies instantiated a second time with UNBAL.  lambda = rho / (rho + eps) multiplies every
+// sweep's soft minimum (kd64_half_sweep's DAMPED), the self problems use the cloud's own mass (a = 1 / n_p, b = w / n_q), the value
+// sums are of -expm1(-dual / rho) and kd64_combine_unbalanced multiplies by rho + eps / 2, the certificates compare against
+// mass exp(-dual / rho), and transported = sum_i a exp(-f_i / rho) is one more output.  kd_reach, kd_value_term and kd_marginal are
+// k_divergence.h's: double already.  rho, mass_q and transported are the BATCH's ([B], [H][B], [H][B]: bb and oslot below, never
+// the chunk's slot).  rho = +inf with w = 1: x 1.0 and exp(-0) are exact, so every output has the balanced kernels' bits.
 #pragma once
 #include "k_divergence.h"
 
@@ -50,12 +57,16 @@ struct Kd64Args {
     double* dual;               // [gridDim.x][2N + 2M]: f, g, h^p, h^q (0 on padding), nullable; the one-shot only
     double* col_err;            // [H][B], nullable
     double* self_err;           // [H][B][2], nullable
+    const double* rho;          // unbalanced: [B], the reach (+inf: balanced), the batch's; else null
+    const double* mass_q;       // unbalanced: [H][B], the target cloud's total mass w, the batch's; else null
+    double* transported;        // unbalanced: [H][B], the batch's, nullable
 };
 
-// kt_half_sweep on double costs: out_dual[j] = -eps LSE_i((in_dual[i] - C_ij) / eps + log_mass) for every j < n_out; AVERAGE as there
-template <bool AVERAGE, typename OV, typename IV>
+// kt_half_sweep on double costs: out_dual[j] = -eps LSE_i((in_dual[i] - C_ij) / eps + log_mass) for every j < n_out; AVERAGE and
+// DAMPED (lambda x the soft minimum: one multiply per output) as there
+template <bool AVERAGE, bool DAMPED, typename OV, typename IV>
 __device__ __forceinline__ void kd64_half_sweep(const OV out_pts, int n_out, const IV in_pts, int n_in, const double* in_dual,
-                                                double* out_dual, double eps, double log_mass) {
+                                                double* out_dual, double eps, double log_mass, double lambda) {
     const int lp = kt_parts(n_out, n_in), parts = 1 << lp, items = n_out << lp;
     const double ninf = -(double)__builtin_inff();
     for (int e0 = 0; e0 < items; e0 += KT_THREADS) {
@@ -85,17 +96,20 @@ __device__ __forceinline__ void kd64_half_sweep(const OV out_pts, int n_out, con
         }
         sum = kt_group_sum(sum, lp);
         if (live && s == 0) {
-            const double v = -eps * (m + log(sum));
+            const double u = -eps * (m + log(sum));
+            const double v = DAMPED ? lambda * u : u;
             out_dual[j] = AVERAGE ? 0.5 * (in_dual[j] + v) : v;
         }
     }
 }
 
 // The plan w exp((d_out_i + d_in_j - C_ij) / eps) row by row of the `out` cloud: with gs the row's sum_j plan_ij (out_i - in_j)
-// into gs[i][3]; returns this thread's share of sum_i |sum_j plan_ij - target| (the rows it owns).  n_out = 0: nothing runs.
-template <typename OV, typename IV>
+// into gs[i][3]; returns this thread's share of sum_i |sum_j plan_ij - target| (the rows it owns), the target the row's mass or
+// with UNBAL what the penalty leaves of it (kd_marginal).  n_out = 0: nothing runs.
+template <bool UNBAL, typename OV, typename IV>
 __device__ __forceinline__ double kd64_plan_rows(const OV out_pts, int n_out, const IV in_pts, int n_in, const double* d_out,
-                                                 const double* d_in, double w, double eps, double target, double* gs) {
+                                                 const double* d_in, double w, double eps, double target, const KdReach& R,
+                                                 double* gs) {
     double err = 0.0;
     const int lp = kt_parts(n_out, n_in), parts = 1 << lp, items = n_out << lp;
     for (int e0 = 0; e0 < items; e0 += KT_THREADS) {
@@ -118,7 +132,7 @@ __device__ __forceinline__ double kd64_plan_rows(const OV out_pts, int n_out, co
         row = kt_group_sum(row, lp);
         if (gs != nullptr) { sx = kt_group_sum(sx, lp); sy = kt_group_sum(sy, lp); sz = kt_group_sum(sz, lp); }
         if (live && s == 0) {
-            err += fabs(row - target);
+            err += fabs(row - kd_marginal<UNBAL>(target, di, R));
             if (gs != nullptr) { gs[(size_t)i * 3] = sx; gs[(size_t)i * 3 + 1] = sy; gs[(size_t)i * 3 + 2] = sz; }
         }
     }
@@ -126,39 +140,40 @@ __device__ __forceinline__ double kd64_plan_rows(const OV out_pts, int n_out, co
 }
 
 // the self problem of one cloud already in LDS: the averaged Jacobi sweeps between h0 and h1, h's sum, the symmetric plan's rows
-// against the cloud itself (gs: p's only) and self_err
-template <typename V>
+// against the cloud itself (gs: p's only) and self_err.  total_mass: the cloud's (1, or the unbalanced target's w)
+template <bool UNBAL, typename V>
 __device__ __forceinline__ void kd64_self(const V pts, int n, int len, bool empty, int iters, double eps, double* h0, double* h1,
                                           double* s_w, double* val_out, double* dual /* nullable */, double* gs /* nullable */,
-                                          double* err_out /* nullable */) {
+                                          double* err_out /* nullable */, const KdReach& R, double total_mass) {
     const int tid = threadIdx.x;
     for (int e = tid; e < n; e += KT_THREADS) h0[e] = 0.0;
     __syncthreads();
-    const double mass = empty ? 0.0 : 1.0 / (double)n;
+    const double mass = empty ? 0.0 : (UNBAL ? total_mass : 1.0) / (double)n;
     const double log_m = log(mass);
     double* cur = h0;
     double* nxt = h1;
     for (int k = 0; k < iters; ++k) {
-        kd64_half_sweep<true>(pts, n, pts, n, cur, nxt, eps, log_m);
+        kd64_half_sweep<true, UNBAL>(pts, n, pts, n, cur, nxt, eps, log_m, R.lambda);
         __syncthreads();
         double* const sw = cur; cur = nxt; nxt = sw;
     }
     double acc = 0.0;
     if (!empty)
-        for (int e = tid; e < n; e += KT_THREADS) acc += mass * cur[e];
+        for (int e = tid; e < n; e += KT_THREADS) acc += mass * kd_value_term<UNBAL>(cur[e], R);
     const double total = kt_block_sum(acc, s_w);
     if (tid == 0) *val_out = total;
     if (dual != nullptr)
         for (int e = tid; e < len; e += KT_THREADS) dual[e] = (!empty && e < n) ? cur[e] : 0.0;
     if (gs == nullptr && err_out == nullptr) return;
-    const double err = kd64_plan_rows(pts, empty ? 0 : n, pts, n, cur, cur, mass * mass, eps, mass, gs);
+    const double err = kd64_plan_rows<UNBAL>(pts, empty ? 0 : n, pts, n, cur, cur, mass * mass, eps, mass, R, gs);
     if (err_out != nullptr) {
         const double sum = kt_block_sum(err, s_w);
         if (tid == 0) *err_out = sum;
     }
 }
 
-__global__ void __launch_bounds__(KT_THREADS) kd64_sweeps(Kd64Args A) {
+template <bool UNBAL>
+__device__ __forceinline__ void kd64_sweeps_body(const Kd64Args& A) {
     __shared__ double s_px[KT_MAX_POINTS];      // p, by coordinate (cross and p-p)
     __shared__ double s_py[KT_MAX_POINTS];
     __shared__ double s_pz[KT_MAX_POINTS];
@@ -178,6 +193,12 @@ __global__ void __launch_bounds__(KT_THREADS) kd64_sweeps(Kd64Args A) {
     const bool empty = np == 0 || nq == 0;                  // (the entry points refuse it)
     const int iters = empty ? 0 : min(max(A.iters, 0), KT_MAX_ITERS);
     const double eps = A.eps[bb];
+    KdReach R{};
+    double w = 1.0;
+    if (UNBAL) {
+        R = kd_reach(A.rho[bb], eps);
+        w = A.mass_q[oslot];
+    }
     double* dual = A.dual != nullptr ? A.dual + slot * (2 * ((size_t)N + M)) : nullptr;
     const Kd64PtsD P{s_px, s_py, s_pz};
     const Kd64PtsF Q{s_q};
@@ -186,50 +207,62 @@ __global__ void __launch_bounds__(KT_THREADS) kd64_sweeps(Kd64Args A) {
     if (z != 1)
         for (int e = tid; e < nq; e += KT_THREADS) s_q[e] = make_float4(q[(size_t)e * 3], q[(size_t)e * 3 + 1], q[(size_t)e * 3 + 2], 0.0f);
     if (z == 1) {
-        kd64_self(P, np, N, empty, iters, eps, s_f, s_g, s_w, A.vals + slots + slot, dual != nullptr ? dual + N + M : nullptr,
-                  A.gsum != nullptr ? A.gsum + (slots + slot) * N * 3 : nullptr, A.self_err != nullptr ? A.self_err + oslot * 2 : nullptr);
+        kd64_self<UNBAL>(P, np, N, empty, iters, eps, s_f, s_g, s_w, A.vals + slots + slot, dual != nullptr ? dual + N + M : nullptr,
+                         A.gsum != nullptr ? A.gsum + (slots + slot) * N * 3 : nullptr, A.self_err != nullptr ? A.self_err + oslot * 2 : nullptr,
+                         R, 1.0);
         return;
     }
     if (z == 2) {
-        kd64_self(Q, nq, M, empty, iters, eps, s_f, s_g, s_w, A.vals + 2 * slots + slot,
-                  dual != nullptr ? dual + 2 * (size_t)N + M : nullptr, (double*)nullptr,
-                  A.self_err != nullptr ? A.self_err + oslot * 2 + 1 : nullptr);
+        kd64_self<UNBAL>(Q, nq, M, empty, iters, eps, s_f, s_g, s_w, A.vals + 2 * slots + slot,
+                         dual != nullptr ? dual + 2 * (size_t)N + M : nullptr, (double*)nullptr,
+                         A.self_err != nullptr ? A.self_err + oslot * 2 + 1 : nullptr, R, w);
         return;
     }
     // z = 0: the cross problem -- kt_transport's sweeps; behind them the duals' sum, the plan's rows against q, col_err
     for (int e = tid; e < np; e += KT_THREADS) s_f[e] = 0.0;
     for (int e = tid; e < nq; e += KT_THREADS) s_g[e] = 0.0;
     __syncthreads();
-    const double mass_p = empty ? 0.0 : 1.0 / (double)np, mass_q = empty ? 0.0 : 1.0 / (double)nq;
+    const double mass_p = empty ? 0.0 : 1.0 / (double)np, mass_q = empty ? 0.0 : (UNBAL ? w : 1.0) / (double)nq;
     const double log_a = log(mass_p), log_b = log(mass_q);
     for (int k = 0; k < iters; ++k) {
-        kd64_half_sweep<false>(Q, nq, P, np, s_f, s_g, eps, log_a);
+        kd64_half_sweep<false, UNBAL>(Q, nq, P, np, s_f, s_g, eps, log_a, R.lambda);
         __syncthreads();
-        kd64_half_sweep<false>(P, np, Q, nq, s_g, s_f, eps, log_b);
+        kd64_half_sweep<false, UNBAL>(P, np, Q, nq, s_g, s_f, eps, log_b, R.lambda);
         __syncthreads();
     }
     double acc = 0.0;
     if (!empty) {
-        for (int e = tid; e < np; e += KT_THREADS) acc += mass_p * s_f[e];
-        for (int e = tid; e < nq; e += KT_THREADS) acc += mass_q * s_g[e];
+        for (int e = tid; e < np; e += KT_THREADS) acc += mass_p * kd_value_term<UNBAL>(s_f[e], R);
+        for (int e = tid; e < nq; e += KT_THREADS) acc += mass_q * kd_value_term<UNBAL>(s_g[e], R);
     }
     const double total = kt_block_sum(acc, s_w);
     if (tid == 0) A.vals[slot] = total;
+    if (UNBAL && A.transported != nullptr) {
+        double moved = 0.0;
+        if (!empty)
+            for (int e = tid; e < np; e += KT_THREADS) moved += kd_marginal<UNBAL>(mass_p, s_f[e], R);
+        const double sum = kt_block_sum(moved, s_w);
+        if (tid == 0) A.transported[oslot] = sum;
+    }
     if (dual != nullptr) {
         for (int e = tid; e < N; e += KT_THREADS) dual[e] = (!empty && e < np) ? s_f[e] : 0.0;
         for (int e = tid; e < M; e += KT_THREADS) dual[(size_t)N + e] = (!empty && e < nq) ? s_g[e] : 0.0;
     }
     const double ab = mass_p * mass_q;
-    if (A.gsum != nullptr) (void)kd64_plan_rows(P, empty ? 0 : np, Q, nq, s_f, s_g, ab, eps, mass_p, A.gsum + slot * N * 3);
+    if (A.gsum != nullptr) (void)kd64_plan_rows<UNBAL>(P, empty ? 0 : np, Q, nq, s_f, s_g, ab, eps, mass_p, R, A.gsum + slot * N * 3);
     if (A.col_err != nullptr) {
-        const double err = kd64_plan_rows(Q, empty ? 0 : nq, P, np, s_g, s_f, ab, eps, mass_q, (double*)nullptr);
+        const double err = kd64_plan_rows<UNBAL>(Q, empty ? 0 : nq, P, np, s_g, s_f, ab, eps, mass_q, R, (double*)nullptr);
         const double sum = kt_block_sum(err, s_w);
         if (tid == 0) A.col_err[oslot] = sum;
     }
 }
 
+__global__ void __launch_bounds__(KT_THREADS) kd64_sweeps(Kd64Args A) { kd64_sweeps_body<false>(A); }
+__global__ void __launch_bounds__(KT_THREADS) kd64_sweeps_unbalanced(Kd64Args A) { kd64_sweeps_body<true>(A); }
+
 // behind kd64_sweeps in the stream, grid (samples, H): the gradient from the two sums, the zero padding, the term
-__global__ void __launch_bounds__(KD_COMBINE_THREADS) kd64_combine(Kd64Args A) {
+template <bool UNBAL>
+__device__ __forceinline__ void kd64_combine_body(const Kd64Args& A) {
     const int b = blockIdx.x, t = blockIdx.y, nb = gridDim.x;
     const int tid = threadIdx.x;
     const int N = A.cp.N;
@@ -245,5 +278,12 @@ __global__ void __launch_bounds__(KD_COMBINE_THREADS) kd64_combine(Kd64Args A) {
         const int real = (empty ? 0 : np) * 3;
         for (int e = tid; e < N * 3; e += KD_COMBINE_THREADS) g[e] = e < real ? gscale * (cross[e] - self[e]) : 0.0;
     }
-    if (tid == 0) A.terms[(size_t)t * A.B + bb] = A.scale * ((A.vals[slot] - A.vals[slots + slot] - A.vals[2 * slots + slot]) / 3.0);
+    if (tid == 0) {
+        const double sum = A.vals[slot] - A.vals[slots + slot] - A.vals[2 * slots + slot];
+        const KdReach R = UNBAL ? kd_reach(A.rho[bb], A.eps[bb]) : KdReach{};
+        if (UNBAL && !R.balanced) A.terms[(size_t)t * A.B + bb] = A.scale * (((R.rho + 0.5 * A.eps[bb]) * sum) / 3.0);
+        else A.terms[(size_t)t * A.B + bb] = A.scale * (sum / 3.0);
+    }
 }
+__global__ void __launch_bounds__(KD_COMBINE_THREADS) kd64_combine(Kd64Args A) { kd64_combine_body<false>(A); }
+__global__ void __launch_bounds__(KD_COMBINE_THREADS) kd64_combine_unbalanced(Kd64Args A) { kd64_combine_body<true>(A); }

@@ -49,10 +49,12 @@ inline TrArena tr_layout(int B, int H, int N, int M = 0, bool actions = false, b
 // [B] (ints); drp_train_grad_f64_untracked (M > 0): behind them the target clouds [B][H][M][3] | their counts [B][H] (ints) --
 // with M = 0 the layout, and so the one copy, is drp_train_grad_f64's; drp_train_grad_f64_divergence (`eps`): behind everything
 // the regularisation strengths [B] (doubles, two words each) on the next even word -- the vector's base is 256-byte aligned on
-// the device, so an even word is an 8-byte boundary -- and nothing ahead of them moves; drp_train_grad_f64_match with a matching
+// the device, so an even word is an 8-byte boundary -- and nothing ahead of them moves; drp_train_grad_f64_divergence_unbalanced
+// (`reach`, with `eps`): behind eps the reaches [B] | the targets' masses [H][B] (doubles too); drp_train_grad_f64_match with a matching
 // of the caller's (`match_in`): behind everything the partners [H][B][N] (ints), nothing ahead of them moving either
-struct Tr64Arena { size_t states, sdelta, attr, dens, nums, targets, tnums, words, eps, match_in; };
-inline Tr64Arena tr64_layout(int B, int H, int N, int M = 0, bool actions = false, bool eps = false, bool match_in = false) {
+struct Tr64Arena { size_t states, sdelta, attr, dens, nums, targets, tnums, words, eps, match_in, rho, mass_q; };
+inline Tr64Arena tr64_layout(int B, int H, int N, int M = 0, bool actions = false, bool eps = false, bool match_in = false,
+                             bool reach = false) {
     Tr64Arena a{};
     a.states = 0;
     a.sdelta = a.states + (size_t)B * (H + 1) * N * 3;
@@ -68,6 +70,11 @@ inline Tr64Arena tr64_layout(int B, int H, int N, int M = 0, bool actions = fals
     if (eps) {
         a.eps = (a.words + 1) & ~(size_t)1;
         a.words = a.eps + 2 * (size_t)B;
+    }
+    if (eps && reach) {
+        a.rho = a.words;
+        a.mass_q = a.rho + 2 * (size_t)B;
+        a.words = a.mass_q + 2 * (size_t)H * B;
     }
     if (match_in) {
         a.match_in = a.words;
@@ -158,15 +165,22 @@ inline DivUnbalancedLayout divergence_unbalanced_layout(int B, int N, int M) {
 // drp_cloud_divergence_f64: p is the caller's doubles, so the buffer is its own (not cloud_begin's).  Up, in one copy: p [B][N][3]
 // (doubles) | eps [B] (doubles) | q [B][M][3] | n_p [B] | n_q [B] (ints); down, behind `in_bytes`: terms [B] | gradient [B][N][3] |
 // duals [B][2N + 2M] | col_err [B] | self_err [B][2] (out[0..5), doubles all); behind them, never read back, the kernels' scratch:
-// the value sums [3][B] | the gradient sums [2][B][N][3].  Every block 16-byte aligned
-struct Div64Layout { size_t pts_p, eps, pts_q, n_p, n_q, in_bytes, out[5], out_bytes[5], vals, gsum, bytes; };
-inline Div64Layout divergence64_layout(int B, int N, int M) {
+// the value sums [3][B] | the gradient sums [2][B][N][3].  Every block 16-byte aligned.  drp_cloud_divergence_unbalanced_f64
+// (`reach`): rho [B] | mass_q [B] (doubles) go up between eps and q, and transported [B] (doubles) lies behind the scratch and comes
+// back by a copy of its own, a sixth output; without `reach` no block moves
+struct Div64Layout { size_t pts_p, eps, pts_q, n_p, n_q, in_bytes, out[5], out_bytes[5], vals, gsum, bytes, rho, mass_q, transported; };
+inline Div64Layout divergence64_layout(int B, int N, int M, bool reach = false) {
     auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t bn = (size_t)B * N, bm = (size_t)B * M;
     Div64Layout a{};
     a.pts_p = 0;
     a.eps = up(a.pts_p + bn * 3 * sizeof(double));
     a.pts_q = up(a.eps + (size_t)B * sizeof(double));
+    if (reach) {
+        a.rho = a.pts_q;
+        a.mass_q = up(a.rho + (size_t)B * sizeof(double));
+        a.pts_q = up(a.mass_q + (size_t)B * sizeof(double));
+    }
     a.n_p = up(a.pts_q + bm * 3 * sizeof(float));
     a.n_q = up(a.n_p + (size_t)B * sizeof(int32_t));
     a.bytes = a.in_bytes = up(a.n_q + (size_t)B * sizeof(int32_t));
@@ -180,6 +194,10 @@ inline Div64Layout divergence64_layout(int B, int N, int M) {
     a.vals = a.bytes;
     a.gsum = up(a.vals + (size_t)3 * B * sizeof(double));
     a.bytes = up(a.gsum + 2 * bn * 3 * sizeof(double));
+    if (reach) {
+        a.transported = a.bytes;
+        a.bytes = up(a.transported + (size_t)B * sizeof(double));
+    }
     return a;
 }
 // drp_cloud_match_f64: p is the caller's doubles, so the buffer is its own too.  Up, in one copy: p [B][N][3] (doubles) | q [B][M][3]

@@ -1045,13 +1045,17 @@ class Engine(object):
         return out
 
     def cloud_divergence_f64(self, p, q, n_p=None, n_q=None, eps=None, iters=None, want_grad=False, want_dual=False,
-                             want_col_err=False, want_self_err=False):
+                             want_col_err=False, want_self_err=False, reach=None, mass_q=None, want_transported=False):
         """cloud_divergence with nothing in fp32, on the device (include/drp.h: drp_cloud_divergence_f64): p is taken as float64
         [B, N, 3] -- every bit of it enters the costs, as the float64 tape's predicted state does in train_grad_f64_divergence --
         q as float32 widened exactly; costs and differences are double, and 'grad' is float64, never rounded to fp32.  The same
-        arguments, dict, limits (1024 points per cloud) and one-shot contract."""
+        arguments, dict, limits (1024 points per cloud) and one-shot contract.  reach, mass_q and want_transported as
+        cloud_divergence's: the unbalanced divergence's yardstick (include/drp.h: drp_cloud_divergence_unbalanced_f64); reach=None
+        is the call above."""
         if eps is None or iters is None:
             raise ValueError('cloud_divergence_f64 needs eps (squared-distance units) and iters')
+        if reach is None and (mass_q is not None or want_transported):
+            raise ValueError('mass_q and want_transported belong to the unbalanced divergence: give reach')
         p64, q = _f64(p), _f32(q)
         if p64.ndim == 2 and q.ndim == 2:
             p64, q = p64[None], q[None]
@@ -1062,10 +1066,21 @@ class Engine(object):
         dual = np.empty((B, 2 * (N + M)), np.float64) if want_dual else None
         col_err = np.empty((B,), np.float64) if want_col_err else None
         self_err = np.empty((B, 2), np.float64) if want_self_err else None
-        self._ck(self.lib.drp_cloud_divergence_f64(self.h, _dp(p64), _ip(n_p), _fp(q), _ip(n_q), B, N, M, _dp(eps), int(iters),
-                                                   _dp(terms), _opt(_dp, grad), _opt(_dp, dual), _opt(_dp, col_err),
-                                                   _opt(_dp, self_err)))
+        if reach is None:
+            self._ck(self.lib.drp_cloud_divergence_f64(self.h, _dp(p64), _ip(n_p), _fp(q), _ip(n_q), B, N, M, _dp(eps), int(iters),
+                                                       _dp(terms), _opt(_dp, grad), _opt(_dp, dual), _opt(_dp, col_err),
+                                                       _opt(_dp, self_err)))
+        else:
+            rho = np.ascontiguousarray(np.broadcast_to(np.asarray(reach, np.float64).reshape(-1), (B,)))
+            w = np.ascontiguousarray(np.broadcast_to(np.asarray(1.0 if mass_q is None else mass_q, np.float64).reshape(-1), (B,)))
+            moved = np.empty((B,), np.float64) if want_transported else None
+            self._ck(self.lib.drp_cloud_divergence_unbalanced_f64(self.h, _dp(p64), _ip(n_p), _fp(q), _ip(n_q), B, N, M, _dp(eps),
+                                                                  _dp(rho), _dp(w), int(iters), _dp(terms), _opt(_dp, grad),
+                                                                  _opt(_dp, dual), _opt(_dp, col_err), _opt(_dp, self_err),
+                                                                  _opt(_dp, moved)))
         out = {'divergence': terms}
+        if want_transported:
+            out['transported'] = moved
         if want_grad:
             out['grad'] = grad
         if want_dual:
@@ -1162,13 +1177,18 @@ class Engine(object):
         return (loss, terms, grad, margin, gs) if want_state else (loss, terms, grad, margin)
 
     def train_grad_f64_divergence(self, states, states_delta, attrs, particle_nums, particle_dens, targets, target_nums, eps, iters,
-                                  actions=None, want_state=False, want_err=False):
+                                  actions=None, want_state=False, want_err=False, reach=None, mass_q=None):
         """train_grad_f64_untracked with the Sinkhorn divergence in place of the Chamfer loss: what
         train_step_divergence(mode='grad') computes, in float64 on the device (include/drp.h: drp_train_grad_f64_divergence).
         eps [B] (or a number) and iters as train_step_divergence's; actions [B, n_rollout, 4] in place of states_delta (then
         ignored, may be None).  The plans of every step are formed from the float64 prediction itself -> (loss, loss_terms
         [n_rollout, B], gradient blob [38403][, d loss / d every step's predicted state [B, n_rollout, N, 3]][, col_err
-        [n_rollout, B], self_err [n_rollout, B, 2]: every problem's certificates]).  The same one-shot contract."""
+        [n_rollout, B], self_err [n_rollout, B, 2]: every problem's certificates]).  The same one-shot contract.  reach (a number
+        or [B]) and mass_q (a number, [B] or [n_rollout, B]; default 1) as train_step_divergence's: the unbalanced divergence as
+        each step's term (drp_train_grad_f64_divergence_unbalanced); want_err then also returns transported [n_rollout, B].
+        reach=None is the call above."""
+        if reach is None and mass_q is not None:
+            raise ValueError('mass_q belongs to the unbalanced divergence: give reach')
         assert targets is not None and target_nums is not None
         by_actions = actions is not None
         keep, (B, N, H, M), (ps, pi, pa, pn, pd, pt, ptn) = self._train_batch(
@@ -1181,6 +1201,15 @@ class Engine(object):
         gs = np.empty((B, max(H, 0), N, 3), np.float64) if want_state else None
         col_err = np.empty((max(H, 0), B), np.float64) if want_err else None
         self_err = np.empty((max(H, 0), B, 2), np.float64) if want_err else None
+        if reach is not None:
+            rho = np.ascontiguousarray(np.broadcast_to(np.asarray(reach, np.float64).reshape(-1), (max(B, 1),)))
+            w = np.ascontiguousarray(np.broadcast_to(np.asarray(1.0 if mass_q is None else mass_q, np.float64), (max(H, 1), max(B, 1))))
+            moved = np.empty((max(H, 0), B), np.float64) if want_err else None
+            self._ck(self.lib.drp_train_grad_f64_divergence_unbalanced(
+                self.h, ps, None if by_actions else pi, pi if by_actions else None, pa, pn, pd, B, N, H, pt, ptn, M, _dp(eps), _dp(rho),
+                _dp(w), int(iters), ctypes.byref(loss), _dp(terms), _dp(grad), _opt(_dp, gs), _opt(_dp, col_err), _opt(_dp, self_err),
+                _opt(_dp, moved)))
+            return (loss.value, terms, grad) + ((gs,) if want_state else ()) + ((col_err, self_err, moved) if want_err else ())
         self._ck(self.lib.drp_train_grad_f64_divergence(self.h, ps, None if by_actions else pi, pi if by_actions else None, pa, pn, pd,
                                                         B, N, H, pt, ptn, M, _dp(eps), int(iters), ctypes.byref(loss), _dp(terms),
                                                         _dp(grad), _opt(_dp, gs), _opt(_dp, col_err), _opt(_dp, self_err)))
@@ -1222,7 +1251,7 @@ class Engine(object):
         return (out.value, terms, grad) + ((gs,) if want_state else ()) + ((info,) if want_info else ())
 
     def train_gradient_probe(self, states, states_delta, attrs, particle_nums, particle_dens, actions=None, targets=None,
-                             target_nums=None, eps=None, iters=None, loss=None, match_weight=0.5):
+                             target_nums=None, eps=None, iters=None, loss=None, match_weight=0.5, reach=None, mass_q=None):
         """The gradients the trainer consumes, held against float64: train_step(mode='grad', want_grad=True) on whatever tape the
         selection gives, then train_grad_f64 on the same batch -> {'tensors': {state_dict key: {'max_abs_err', 'max_abs_ref',
         'rel' = err / max(ref, 1e-300)}}, 'worst': the key of the largest rel, 'rel': that rel, 'loss32', 'loss64', 'loss_diff',
@@ -1247,8 +1276,17 @@ class Engine(object):
         differs from the fp32 side's partners, and 'rows_flipped', the rows that differ; 'cost_gap', the largest (cost - opt_cost)
         / opt_cost -- how far from optimal, in double, the fp32 side's matching is; for the mix 'min_margin' as for Chamfer.  Only
         where flipped > 0, a second float64 call on its own matching gives 'rel_own': what the disagreement costs in the
-        gradient.  loss=None is the call without these two keywords."""
+        gradient.  loss=None is the call without these two keywords.  With `reach` (a number or [B]) and `mass_q` (a number,
+        [B] or [n_rollout, B]; default 1) beside eps and iters the loss is the UNBALANCED divergence: the pair is
+        train_step_divergence(reach=, mass_q=, mode='grad', want_err=True) and train_grad_f64_divergence(reach=, mass_q=), and the
+        'sinkhorn' dict also has 'reach': True, 'transported' -- the float64 side's smallest transported share over the batch --
+        and 'transported_diff', the largest |fp32 side - float64 side| of a problem's share: whether the tape's drift changed what
+        the loss gives up.  reach=None is the call without these two keywords."""
         from .weights import STATE_DICT_KEYS
+        if reach is not None and (eps is None or loss is not None):
+            raise ValueError('reach= belongs to the Sinkhorn divergence: give eps and iters, and no loss=')
+        if reach is None and mass_q is not None:
+            raise ValueError('mass_q belongs to the unbalanced divergence: give reach')
         assert (targets is None) == (target_nums is None)
         assert (eps is None) == (iters is None) and (eps is None or targets is not None)
         if loss is not None and (loss not in L.MATCH_LOSSES or targets is None or eps is not None):
@@ -1261,6 +1299,11 @@ class Engine(object):
             sd = None if actions is not None else states_delta
             loss32, g32, match32 = self._train_step32(states, sd, actions, attrs, particle_nums, particle_dens, targets,
                                                       target_nums, 'grad', True, loss, match_weight, True)
+        elif sinkhorn and reach is not None:
+            sd = None if actions is not None else states_delta
+            loss32, g32, _, _, moved32 = self.train_step_divergence(
+                states, attrs, particle_nums, particle_dens, targets, target_nums, eps, iters, states_delta=sd, actions=actions,
+                mode='grad', want_grad=True, want_err=True, reach=reach, mass_q=mass_q)
         elif sinkhorn:
             sd = None if actions is not None else states_delta
             loss32, g32 = self.train_step_divergence(states, attrs, particle_nums, particle_dens, targets, target_nums, eps, iters,
@@ -1274,6 +1317,10 @@ class Engine(object):
             loss64, _, g64, info = self.train_grad_f64_match(states, states_delta, attrs, particle_nums, particle_dens, targets,
                                                              target_nums, loss, match_weight, actions=actions, match_in=match32,
                                                              want_info=True)
+        elif sinkhorn and reach is not None:
+            loss64, _, g64, col_err, self_err, moved64 = self.train_grad_f64_divergence(
+                states, states_delta, attrs, particle_nums, particle_dens, targets, target_nums, eps, iters, actions=actions,
+                want_err=True, reach=reach, mass_q=mass_q)
         elif sinkhorn:
             loss64, _, g64, col_err, self_err = self.train_grad_f64_divergence(
                 states, states_delta, attrs, particle_nums, particle_dens, targets, target_nums, eps, iters, actions=actions,
@@ -1302,6 +1349,9 @@ class Engine(object):
             out['loss_kind'], out['min_margin'] = 'chamfer', float(margin.min())
         if sinkhorn:
             out['loss_kind'], out['col_err'], out['self_err'] = 'sinkhorn', float(col_err.max()), float(self_err.max())
+            if reach is not None:
+                out['reach'], out['transported'] = True, float(moved64.min())
+                out['transported_diff'] = float(np.abs(moved32 - moved64).max())
         if matching:
             differ = info['match'] != match32
             out['loss_kind'] = loss

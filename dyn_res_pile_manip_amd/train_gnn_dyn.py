@@ -138,7 +138,9 @@ def check_loss(loss, match_weight=0.5, transport_eps_scale=TRANSPORT_EPS_SCALE, 
 # the unbalanced Sinkhorn divergence (Engine.train_step_divergence(reach=...)): for a pile seen partly.  sinkhorn_reach_scale r:
 # rho_b = r / particle_dens[b], transport_eps_scale's unit, so r = 4 is a reach of two particle spacings; None: balanced.
 # sinkhorn_mass: the target cloud's total mass against the prediction's 1 -- 'unit': 1; 'count': target_nums[b, t] /
-# particle_nums[b], equal mass per point, right when the targets are sampled at the particles' spacing (target_den_scale == 1)
+# particle_nums[b], equal mass per point, right when the targets are sampled at the particles' spacing (target_den_scale == 1).
+# Its float64 yardstick (Engine.train_grad_f64_divergence(reach=...)) is reached through sinkhorn_reach_probe_every;
+# sinkhorn_probe_every keeps refusing a reach (tests/test_divergence_unbalanced_host.py pins that)
 SINKHORN_MASSES = ('unit', 'count')
 SINKHORN_MIN_REACH_PER_EPS = 1.0 / 1024.0       # include/drp.h: rho >= eps / 1024
 SINKHORN_MASS_RANGE = (0.125, 8.0)              # include/drp.h: 1/8 <= mass_q <= 8
@@ -147,8 +149,8 @@ SINKHORN_MASS_RANGE = (0.125, 8.0)              # include/drp.h: 1/8 <= mass_q <
 def check_sinkhorn_options(loss, sinkhorn_reach_scale=None, sinkhorn_mass='unit', sinkhorn_probe_every=0,
                            transport_eps_scale=TRANSPORT_EPS_SCALE):
     """sinkhorn_reach_scale and sinkhorn_mass of run_batch() / train() / main(): DIVERGENCE_LOSSES' alone; 'count' needs a reach
-    (balanced transport between unequal masses has no plan); the float64 yardstick has no unbalanced variant, so
-    sinkhorn_probe_every is refused with a reach -- refused, not skipped"""
+    (balanced transport between unequal masses has no plan); sinkhorn_probe_every probes the balanced divergence and
+    is refused with a reach -- refused, not skipped (a test pins it); sinkhorn_reach_probe_every probes the unbalanced one"""
     if sinkhorn_mass not in SINKHORN_MASSES:
         raise ValueError('sinkhorn_mass must be one of %s, got %r' % (SINKHORN_MASSES, sinkhorn_mass))
     if sinkhorn_reach_scale is None:
@@ -166,8 +168,8 @@ def check_sinkhorn_options(loss, sinkhorn_reach_scale=None, sinkhorn_mass='unit'
         raise ValueError('sinkhorn_mass=%r needs a finite sinkhorn_reach_scale: balanced transport between unequal masses has no plan'
                          % (sinkhorn_mass,))
     if sinkhorn_probe_every > 0:
-        raise ValueError('sinkhorn_probe_every: there is no float64 yardstick for the unbalanced divergence yet '
-                         '(sinkhorn_reach_scale=%r)' % (sinkhorn_reach_scale,))
+        raise ValueError('sinkhorn_probe_every: there is no float64 yardstick for the unbalanced divergence yet under this option '
+                         '(sinkhorn_reach_scale=%r): sinkhorn_reach_probe_every reaches it' % (sinkhorn_reach_scale,))
 
 
 def sinkhorn_reach(particle_dens, sinkhorn_reach_scale):
@@ -333,15 +335,20 @@ def probe_batch(model, data, impulses='data', loss='mse'):
                                              actions=batch_actions(data) if impulses == 'actions' else None, **extra)
 
 
-def probe_batch_sinkhorn(model, data, impulses='data', transport_eps_scale=TRANSPORT_EPS_SCALE, transport_iters=TRANSPORT_ITERS):
+def probe_batch_sinkhorn(model, data, impulses='data', transport_eps_scale=TRANSPORT_EPS_SCALE, transport_iters=TRANSPORT_ITERS,
+                         sinkhorn_reach_scale=None, sinkhorn_mass='unit'):
     """Engine.train_gradient_probe with the Sinkhorn divergence on a collate_untracked batch: train_step_divergence(mode='grad')
     against Engine.train_grad_f64_divergence on the same batch, eps and sweeps as run_batch(loss='sinkhorn') takes them; the
     result has 'loss_kind': 'sinkhorn' and the float64 side's largest 'col_err' and 'self_err'.  Weights, Adam state and
     iteration count are untouched.  It works on depth_only batches with impulses='actions'.  probe_batch itself still refuses
     the loss: its refusal is pinned by tests/test_divergence_host.py and tests/test_gpu_train_divergence.py, and folding this
-    call into probe_batch / probe_every waits for a change of those tests."""
+    call into probe_batch / probe_every waits for a change of those tests.  sinkhorn_reach_scale (not None) and sinkhorn_mass:
+    the unbalanced divergence as run_batch takes it -- the reaches of sinkhorn_reach and the targets' masses of sinkhorn_mass_q
+    -- against Engine.train_grad_f64_divergence(reach=, mass_q=); the result then also has 'reach': True, 'transported' and
+    'transported_diff'."""
     loss = DIVERGENCE_LOSSES[0]
     check_loss(loss, 0.5, transport_eps_scale, transport_iters)
+    check_sinkhorn_options(loss, sinkhorn_reach_scale, sinkhorn_mass, 0, transport_eps_scale)
     if impulses not in IMPULSES:
         raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
     check_depth_only(data, loss, impulses)
@@ -350,11 +357,15 @@ def probe_batch_sinkhorn(model, data, impulses='data', transport_eps_scale=TRANS
         model._claim()
     by_actions = impulses == 'actions'
     dens = _np(particle_dens)
+    nums, tnums = _np(particle_nums, np.int32), _np(data[7], np.int32)
+    extra = {}
+    if sinkhorn_reach_scale is not None:
+        extra = {'reach': sinkhorn_reach(dens, sinkhorn_reach_scale), 'mass_q': sinkhorn_mass_q(sinkhorn_mass, nums, tnums)}
     return model.engine.train_gradient_probe(_np(states), None if (by_actions or states_delta is None) else _np(states_delta),
-                                             _np(attrs), _np(particle_nums, np.int32), dens,
+                                             _np(attrs), nums, dens,
                                              actions=batch_actions(data) if by_actions else None, targets=_np(data[6]),
-                                             target_nums=_np(data[7], np.int32), eps=transport_eps(dens, transport_eps_scale),
-                                             iters=int(transport_iters))
+                                             target_nums=tnums, eps=transport_eps(dens, transport_eps_scale),
+                                             iters=int(transport_iters), **extra)
 
 
 def probe_batch_match(model, data, impulses='data', loss='match', match_weight=0.5):
@@ -406,6 +417,25 @@ def check_sinkhorn_probe_option(loss, sinkhorn_probe_every, grad_probe_every=0, 
                              % (DIVERGENCE_LOSSES, loss, LOSSES))
 
 
+def check_sinkhorn_reach_probe_option(loss, sinkhorn_reach_probe_every, sinkhorn_reach_scale=None, grad_probe_every=0, probe_every=0,
+                                      sinkhorn_probe_every=0, match_probe_every=0):
+    """sinkhorn_reach_probe_every of train() / main(): the probe schedule of DIVERGENCE_LOSSES with a reach alone, and no
+    companion of the four other schedules (sinkhorn_probe_every keeps refusing a reach: tests/test_divergence_unbalanced_host.py
+    pins that)"""
+    if int(sinkhorn_reach_probe_every) != sinkhorn_reach_probe_every or sinkhorn_reach_probe_every < 0:
+        raise ValueError('sinkhorn_reach_probe_every must be a non-negative integer, got %r' % (sinkhorn_reach_probe_every,))
+    if sinkhorn_reach_probe_every > 0:
+        if grad_probe_every > 0 or probe_every > 0 or sinkhorn_probe_every > 0 or match_probe_every > 0:
+            raise ValueError('give sinkhorn_reach_probe_every alone, not with grad_probe_every, probe_every, sinkhorn_probe_every or '
+                             'match_probe_every')
+        if loss not in DIVERGENCE_LOSSES:
+            raise ValueError('sinkhorn_reach_probe_every needs a loss of %s, got %r: probe_every probes the losses of %s'
+                             % (DIVERGENCE_LOSSES, loss, LOSSES))
+        if sinkhorn_reach_scale is None:
+            raise ValueError('sinkhorn_reach_probe_every needs sinkhorn_reach_scale: sinkhorn_probe_every probes the balanced '
+                             'divergence')
+
+
 def check_probe_options(loss, grad_probe_every, probe_every):
     """the two probe schedules of train() / main(): grad_probe_every (the MSE yardstick alone) and probe_every (every loss of
     LOSSES; the matching losses have no float64 yardstick yet and refuse both)"""
@@ -422,7 +452,7 @@ def check_probe_options(loss, grad_probe_every, probe_every):
 def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=None, first_epoch=0, grad_probe_every=0,
           loss='mse', impulses='data', probe_every=0, match_weight=0.5, transport_eps_scale=TRANSPORT_EPS_SCALE,
           transport_iters=TRANSPORT_ITERS, sinkhorn_probe_every=0, match_probe_every=0, sinkhorn_reach_scale=None,
-          sinkhorn_mass='unit'):
+          sinkhorn_mass='unit', sinkhorn_reach_probe_every=0):
     """train/train_gnn_dyn.py:134-246 without the file I/O: `dataloaders` = {'train': iterable of
     collated batches, 'valid': ...}.  Returns {'best_valid_loss', 'history': [(epoch, phase, rmse)]}.
     ckp(epoch, i, model): called after training batch i when i % ckp_per_iter == 0 (:217-218); first_epoch: the epoch
@@ -446,16 +476,22 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
     side's partners, and how far from optimal in double those are -- and, where a partner flipped, rel_own.
     sinkhorn_reach_scale, sinkhorn_mass: run_batch's unbalanced divergence (check_sinkhorn_options: a loss in DIVERGENCE_LOSSES
     alone, 'count' only with a reach, no sinkhorn_probe_every beside a reach); the training log line then carries the batch's
-    mean transported."""
+    mean transported.  sinkhorn_reach_probe_every = k > 0: probe_every's schedule and history entry for a loss in
+    DIVERGENCE_LOSSES with a reach (probe_batch_sinkhorn with the run's sinkhorn_reach_scale and sinkhorn_mass); the log line
+    carries col_err, self_err, the float64 side's smallest transported and transported_diff.  It is refused without a reach,
+    with any other loss and beside any of the four other probe options (check_sinkhorn_reach_probe_option)."""
     check_probe_options(loss, grad_probe_every, probe_every)
     check_sinkhorn_probe_option(loss, sinkhorn_probe_every, grad_probe_every, probe_every)
     check_match_probe_option(loss, match_probe_every, grad_probe_every, probe_every, sinkhorn_probe_every)
+    check_sinkhorn_reach_probe_option(loss, sinkhorn_reach_probe_every, sinkhorn_reach_scale, grad_probe_every, probe_every,
+                                      sinkhorn_probe_every, match_probe_every)
     check_loss(loss, match_weight, transport_eps_scale, transport_iters)
     check_sinkhorn_options(loss, sinkhorn_reach_scale, sinkhorn_mass, sinkhorn_probe_every, transport_eps_scale)
     if impulses not in IMPULSES:
         raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
     loss_kind = loss
-    every = max(grad_probe_every, probe_every, sinkhorn_probe_every, match_probe_every)     # (at most one of them is given)
+    every = max(grad_probe_every, probe_every, sinkhorn_probe_every, match_probe_every,
+                sinkhorn_reach_probe_every)                                                 # (at most one of them is given)
     tc = config['train']
     n_rollout = tc['n_rollout']
     assert tc['n_history'] == 1
@@ -468,7 +504,10 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
             meter = AverageMeter()
             for i, data in enumerate(dataloaders[phase]):
                 if every > 0 and phase == 'train' and i % every == 0:
-                    if sinkhorn_probe_every > 0:
+                    if sinkhorn_reach_probe_every > 0:
+                        pr = probe_batch_sinkhorn(model, data, impulses, transport_eps_scale, transport_iters, sinkhorn_reach_scale,
+                                                  sinkhorn_mass)
+                    elif sinkhorn_probe_every > 0:
                         pr = probe_batch_sinkhorn(model, data, impulses, transport_eps_scale, transport_iters)
                     elif match_probe_every > 0:
                         pr = probe_batch_match(model, data, impulses, loss_kind, match_weight)
@@ -478,8 +517,10 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
                     if log is not None:
                         line = 'grad_probe [%d][%d] worst %s rel %.3e (%s tape), loss diff %.3e' % (epoch, i, pr['worst'], pr['rel'],
                                                                                                   pr['tape'], pr['loss_diff'])
-                        if sinkhorn_probe_every > 0:
+                        if sinkhorn_probe_every > 0 or sinkhorn_reach_probe_every > 0:
                             line += ', col_err %.3e, self_err %.3e' % (pr['col_err'], pr['self_err'])
+                        if sinkhorn_reach_probe_every > 0:
+                            line += ', transported %.4f, transported_diff %.3e' % (pr['transported'], pr['transported_diff'])
                         if match_probe_every > 0:
                             line += ', flipped %d, cost_gap %.3e' % (pr['flipped'], pr['cost_gap'])
                             line += ', rel_own %.3e' % pr['rel_own'] if 'rel_own' in pr else ''
@@ -528,7 +569,7 @@ def set_seed(seed):
 def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8, n_epoch=None, engine=None, grad_probe_every=0,
          loss=None, impulses=None, probe_every=0, data='particles', target_den_scale=1.0, match_weight=0.5,
          transport_eps_scale=TRANSPORT_EPS_SCALE, transport_iters=TRANSPORT_ITERS, sinkhorn_probe_every=0, match_probe_every=0,
-         sinkhorn_reach_scale=None, sinkhorn_mass='unit'):
+         sinkhorn_reach_scale=None, sinkhorn_mass='unit', sinkhorn_reach_probe_every=0):
     """The file-level part of train/train_gnn_dyn.py:train() (:45-130, :196-228): seed, the log directory with config.yaml
     and log.txt, the 'train' / 'valid' ParticleDatasets and their DeviceLoaders, a fresh model (torch.nn.Linear's default
     initialisation) or the resumed checkpoint, net_epoch_%d_iter_%d.pth every ckp_per_iter training batches and
@@ -543,7 +584,7 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
     times the state's density), which implies loss='chamfer' and impulses='actions'; a contradicting value is refused.  loss /
     impulses None: 'mse' / 'data', or what data implies.  loss in MATCH_LOSSES (with match_weight for the mix): as 'chamfer', on
     particles or depth; loss in TRANSPORT_LOSSES or DIVERGENCE_LOSSES (with transport_eps_scale and transport_iters) likewise.  chunk None: the
-    dataset's default (64 samples; 16 for data='depth').  sinkhorn_reach_scale, sinkhorn_mass: train's."""
+    dataset's default (64 samples; 16 for data='depth').  sinkhorn_reach_scale, sinkhorn_mass, sinkhorn_reach_probe_every: train's."""
     import time
     import yaml
     from . import synthetic, weights
@@ -553,6 +594,8 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
     check_probe_options(loss, grad_probe_every, probe_every)
     check_sinkhorn_probe_option(loss, sinkhorn_probe_every, grad_probe_every, probe_every)
     check_match_probe_option(loss, match_probe_every, grad_probe_every, probe_every, sinkhorn_probe_every)
+    check_sinkhorn_reach_probe_option(loss, sinkhorn_reach_probe_every, sinkhorn_reach_scale, grad_probe_every, probe_every,
+                                      sinkhorn_probe_every, match_probe_every)
     check_loss(loss, match_weight, transport_eps_scale, transport_iters)
     check_sinkhorn_options(loss, sinkhorn_reach_scale, sinkhorn_mass, sinkhorn_probe_every, transport_eps_scale)
     tc = config['train']
@@ -605,7 +648,8 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
                        grad_probe_every=grad_probe_every, loss=loss, impulses=impulses, probe_every=probe_every,
                        match_weight=match_weight, transport_eps_scale=transport_eps_scale, transport_iters=transport_iters,
                        sinkhorn_probe_every=sinkhorn_probe_every, match_probe_every=match_probe_every,
-                       sinkhorn_reach_scale=sinkhorn_reach_scale, sinkhorn_mass=sinkhorn_mass)
+                       sinkhorn_reach_scale=sinkhorn_reach_scale, sinkhorn_mass=sinkhorn_mass,
+                       sinkhorn_reach_probe_every=sinkhorn_reach_probe_every)
         for epoch, phase, rmse in result['history']:
             if phase == 'grad_probe':                   # logged when it was taken
                 continue
@@ -638,6 +682,10 @@ def _cli(argv=None):
                     help='--loss match, chamfer+match: hold every k-th training batch\'s gradients against the float64 matching loss on '
                          'the same pairs before its update; the log line carries the problems whose float64 optimum differs (flipped) '
                          'and the fp32 matching\'s distance from it (cost_gap) (not with the three options above)')
+    ap.add_argument('--sinkhorn-reach-probe-every', type=int, default=0,
+                    help='--loss sinkhorn --sinkhorn-reach-scale r: hold every k-th training batch\'s gradients against the float64 '
+                         'unbalanced divergence before its update; the log line also carries the float64 side\'s smallest transported '
+                         'share and its largest difference from the fp32 side\'s (not with the four options above)')
     ap.add_argument('--data', choices=DATA, default='particles',
                     help='depth: episodes of depth PNGs and actions.p alone; every frame of a window is sampled from its depth '
                          'image on the device.  Implies --loss chamfer --impulses actions')
@@ -669,6 +717,9 @@ def _cli(argv=None):
         check_loss(resolve_data_options(a.data, a.loss, a.impulses)[0], a.match_weight, a.transport_eps_scale, a.transport_iters)
         check_sinkhorn_options(resolve_data_options(a.data, a.loss, a.impulses)[0], a.sinkhorn_reach_scale, a.sinkhorn_mass,
                                a.sinkhorn_probe_every, a.transport_eps_scale)
+        check_sinkhorn_reach_probe_option(resolve_data_options(a.data, a.loss, a.impulses)[0], a.sinkhorn_reach_probe_every,
+                                          a.sinkhorn_reach_scale, a.grad_probe_every, a.probe_every, a.sinkhorn_probe_every,
+                                          a.match_probe_every)
     except ValueError as e:
         ap.error(str(e))
     config = default_config()
@@ -684,7 +735,8 @@ def _cli(argv=None):
                      data=a.data, target_den_scale=a.target_den_scale, match_weight=a.match_weight,
                      transport_eps_scale=a.transport_eps_scale, transport_iters=a.transport_iters,
                      sinkhorn_probe_every=a.sinkhorn_probe_every, match_probe_every=a.match_probe_every,
-                     sinkhorn_reach_scale=a.sinkhorn_reach_scale, sinkhorn_mass=a.sinkhorn_mass)
+                     sinkhorn_reach_scale=a.sinkhorn_reach_scale, sinkhorn_mass=a.sinkhorn_mass,
+                     sinkhorn_reach_probe_every=a.sinkhorn_reach_probe_every)
     print('best valid loss %.6f, checkpoints in %s' % (np.sqrt(result['best_valid_loss']), d))
 
 

@@ -567,7 +567,7 @@ int drp_ptcl_dataset_time(drp_ctx* ctx, float* ms_out);
 /* HIP-event timing of one kernel class on the context's stream.  name: "graph",
  * "node_encode", "edge_encode", "project", "aggregate", "update", "predict", "reward",
  * "mppi", "prop" (the fused propagation-step kernel of DRP_ENGINE_FUSED / _LITE), "loss" (the stand-alone metrics' kernel:
- * drp_cloud_chamfer, drp_cloud_match, drp_cloud_transport, drp_cloud_divergence, drp_cloud_divergence_unbalanced, drp_cloud_divergence_f64, drp_cloud_match_f64).  drp_probe_read returns total ms and launches since drp_probe_begin. */
+ * drp_cloud_chamfer, drp_cloud_match, drp_cloud_transport, drp_cloud_divergence, drp_cloud_divergence_unbalanced, drp_cloud_divergence_f64, drp_cloud_divergence_unbalanced_f64, drp_cloud_match_f64).  drp_probe_read returns total ms and launches since drp_probe_begin. */
 int drp_probe_begin(drp_ctx* ctx, const char* kernel_class);
 int drp_probe_read(drp_ctx* ctx, double* total_ms, long* launches);
 /* Kernel launches inside the timed regions of the "prop" / "prop+work" probe since drp_probe_begin.  drp_probe_read's `launches`
@@ -917,8 +917,8 @@ int drp_train_step_divergence(drp_ctx* ctx, const float* states, const float* st
  *                transport between unequal masses has no plan); every output then has drp_cloud_divergence's bits.
  * Refused with DRP_EINVAL and a message, on the host, before any launch: everything drp_cloud_divergence refuses; rho or mass_q
  * NULL; rho[b] not (finite with rho[b] >= eps[b]/1024, or +inf) -- below that f/rho means nothing but "no transport";
- * mass_q[b] outside [1/8, 8]; mass_q[b] != 1 with rho[b] = +inf.  Same grid, LDS and fixed work as drp_cloud_divergence; no
- * float64 yardstick yet. */
+ * mass_q[b] outside [1/8, 8]; mass_q[b] != 1 with rho[b] = +inf.  Same grid, LDS and fixed work as drp_cloud_divergence.  The
+ * float64 yardstick is drp_cloud_divergence_unbalanced_f64 / drp_train_grad_f64_divergence_unbalanced below. */
 int drp_cloud_divergence_unbalanced(drp_ctx* ctx, const float* p, const int32_t* n_p, const float* q, const int32_t* n_q,
                                     int B, int N, int M, const double* eps /*[B]*/, const double* rho /*[B]*/,
                                     const double* mass_q /*[B]*/, int iters, double* terms_out /*[B]*/,
@@ -971,6 +971,36 @@ int drp_train_grad_f64_divergence(drp_ctx* ctx, const float* states, const float
                                   const double* eps /*[B]*/, int iters, double* loss_out, double* loss_terms_out, double* grad_out,
                                   double* grad_state_out, double* col_err_out /*[H][B], nullable*/,
                                   double* self_err_out /*[H][B][2], nullable*/);
+
+/* ---- the float64 yardstick of the unbalanced Sinkhorn divergence (csrc/k_divergence_f64.h: kd64_sweeps_unbalanced,
+ * kd64_combine_unbalanced).  drp_cloud_divergence_unbalanced's definition -- sweeps damped by lambda, the clouds' own masses, the
+ * expm1 value times (rho + eps/2), the certificates against mass exp(-dual/rho), transported -- with drp_cloud_divergence_f64's
+ * arithmetic: p DOUBLE, q widened exactly, double costs on double differences, the gradient written as double, +0.0 on padding.
+ * rho [B], mass_q [B], transported_out [B] (nullable).  The contract and the launches are drp_cloud_divergence_f64's (grid, LDS,
+ * fixed work, bits a function of the counts alone, the "loss" kernel class); rho[b] = +inf with mass_q[b] = 1 returns
+ * drp_cloud_divergence_f64's bits on every output and transported = sum_i a.  Refused on the host, before any launch: everything
+ * drp_cloud_divergence_f64 refuses and everything drp_cloud_divergence_unbalanced refuses of rho and mass_q; the context stays
+ * usable. */
+int drp_cloud_divergence_unbalanced_f64(drp_ctx* ctx, const double* p /*[B][N][3]*/, const int32_t* n_p, const float* q,
+                                        const int32_t* n_q, int B, int N, int M, const double* eps /*[B]*/, const double* rho /*[B]*/,
+                                        const double* mass_q /*[B]*/, int iters, double* terms_out /*[B]*/,
+                                        double* grad_p_out /*[B][N][3], nullable*/,
+                                        double* dual_out /*[B][2N+2M]: f, g, h_p, h_q, nullable*/, double* col_err_out /*[B], nullable*/,
+                                        double* self_err_out /*[B][2], nullable*/, double* transported_out /*[B], nullable*/);
+
+/* drp_train_grad_f64_divergence with drp_cloud_divergence_unbalanced_f64 as each step's term: the yardstick of
+ * drp_train_step_divergence_unbalanced's gradients.  rho [B] per sample, mass_q [n_rollout][B] per problem (step-major, as the
+ * certificates), transported_out [n_rollout][B] (nullable).  The three arrays belong to the batch: the bits are the same under
+ * any workspace cap.  The same refusals as drp_train_grad_f64_divergence, and rho / mass_q as
+ * drp_train_step_divergence_unbalanced refuses them. */
+int drp_train_grad_f64_divergence_unbalanced(drp_ctx* ctx, const float* states, const float* states_delta /*[B][H][N][3] or NULL*/,
+                                             const float* actions /*[B][H][4] or NULL*/, const float* attrs,
+                                             const int32_t* particle_nums, const float* particle_dens, int B, int N, int n_rollout,
+                                             const float* targets /*[B][H][M][3]*/, const int32_t* target_nums /*[B][H]*/, int M,
+                                             const double* eps /*[B]*/, const double* rho /*[B]*/, const double* mass_q /*[H][B]*/,
+                                             int iters, double* loss_out, double* loss_terms_out, double* grad_out,
+                                             double* grad_state_out, double* col_err_out /*[H][B], nullable*/,
+                                             double* self_err_out /*[H][B][2], nullable*/, double* transported_out /*[H][B], nullable*/);
 
 /* ---- the float64 yardstick of the matching losses (csrc/k_match_f64.h).  drp_cloud_match's definition with nothing in fp32: p
  * is DOUBLE [B][N][3] -- on purpose: the call runs the kernel the trainer's yardstick runs on the float64 tape's predicted state --

@@ -23,7 +23,10 @@
 // divergence_unbalanced_layout (eps | rho | mass_q side by side, the scratch, transported, inside a block of exactly its `bytes`,
 // the five blocks that come back where divergence_layout has them), the trainer's rho [B] | mass_q [H][B] behind eps (tr_layout
 // with `reach`) and transported behind its doubles (tr_div_loss_layout with `unbalanced`), nothing ahead of them moved, and the
-// check of a reach and a target mass (check_reach) at the edges of its ranges.  No device is touched.
+// check of a reach and a target mass (check_reach) at the edges of its ranges.  Its float64 yardstick: rho [B] | mass_q [H][B]
+// (doubles) behind eps in the float64 upload (tr64_layout with `reach`), and drp_cloud_divergence_unbalanced_f64's buffer
+// (divergence64_layout with `reach`: rho | mass_q between eps and q, transported behind the scratch), nothing else moved
+// relative to one another.  No device is touched.
 //
 //   train_host_check layout64 B H N M actions     prints tr64_layout's eight fields (4-byte words) and exits
 #include <cstdio>
@@ -200,6 +203,74 @@ static void stage_divergence64(int B, int N, int M) {
     // the last row's last gradient sum of the second problem set and the last value sum, where kd64_sweeps stores them
     reinterpret_cast<double*>(io + lay.gsum)[((size_t)B + (B - 1)) * N * 3 + (size_t)(N - 1) * 3 + 2] = 1.0;
     reinterpret_cast<double*>(io + lay.vals)[2 * (size_t)B + (B - 1)] = 1.0;
+    std::free(io);
+}
+
+// drp_train_grad_f64_divergence_unbalanced's upload: rho [B] | mass_q [H][B] (doubles) behind eps, 8-byte aligned, everything ahead
+// of them where it was; both written and read back as the kernels address them, in a block of exactly `words`
+static void stage64_reach(int B, int H, int N, int M, bool actions) {
+    const Tr64Arena lay = tr64_layout(B, H, N, M, actions, true, false, true), plain = tr64_layout(B, H, N, M, actions, true);
+    EXPECT(lay.states == plain.states && lay.sdelta == plain.sdelta && lay.attr == plain.attr && lay.dens == plain.dens &&
+           lay.nums == plain.nums && lay.targets == plain.targets && lay.tnums == plain.tnums && lay.eps == plain.eps);
+    EXPECT(lay.rho == plain.words && lay.rho % 2 == 0);
+    EXPECT(lay.mass_q == lay.rho + 2 * (size_t)B && lay.words == lay.mass_q + 2 * (size_t)H * B);
+    EXPECT(plain.rho == 0 && plain.mass_q == 0);
+    EXPECT(tr64_layout(B, H, N, M, actions, false, false, true).words == tr64_layout(B, H, N, M, actions).words);  // (no reach without eps)
+    std::vector<double> rho(B, 0.25), w((size_t)H * B, 1.5);
+    float* host = static_cast<float*>(std::malloc(lay.words * sizeof(float)));
+    std::memset(host, 0xff, lay.words * sizeof(float));
+    std::memcpy(host + lay.rho, rho.data(), (size_t)B * sizeof(double));
+    std::memcpy(host + lay.mass_q, w.data(), (size_t)H * B * sizeof(double));
+    EXPECT(reinterpret_cast<uintptr_t>(host + lay.rho) % sizeof(double) == 0);
+    const double* r = reinterpret_cast<const double*>(host + lay.rho);               // as kd64_sweeps_unbalanced addresses them
+    const double* m = reinterpret_cast<const double*>(host + lay.mass_q);
+    EXPECT(r[0] == 0.25 && r[B - 1] == 0.25 && m[0] == 1.5 && m[(size_t)(H - 1) * B + (B - 1)] == 1.5);
+    std::free(host);
+}
+
+// drp_cloud_divergence_unbalanced_f64's buffer: divergence64_layout's with rho | mass_q between eps and q and transported behind
+// the scratch; every block staged or written in full inside a block of exactly `bytes`
+static void stage_divergence64_reach(int B, int N, int M) {
+    const size_t bn = (size_t)B * N, bm = (size_t)B * M;
+    const Div64Layout lay = divergence64_layout(B, N, M, true), plain = divergence64_layout(B, N, M);
+    const size_t off[] = {lay.pts_p, lay.eps, lay.rho, lay.mass_q, lay.pts_q, lay.n_p, lay.n_q, lay.out[0], lay.out[1], lay.out[2],
+                          lay.out[3], lay.out[4], lay.vals, lay.gsum, lay.transported, lay.bytes};
+    const size_t len[] = {bn * 24, (size_t)B * 8, (size_t)B * 8, (size_t)B * 8, bm * 12, (size_t)B * 4, (size_t)B * 4, (size_t)B * 8,
+                          bn * 24, 2 * (bn + bm) * 8, (size_t)B * 8, (size_t)B * 16, (size_t)3 * B * 8, 2 * bn * 24, (size_t)B * 8};
+    for (int k = 0; k < 15; ++k) {
+        EXPECT(off[k] % 16 == 0);
+        EXPECT(off[k] + len[k] <= off[k + 1] && off[k + 1] - (off[k] + len[k]) < 16);
+        if (k >= 7 && k < 12) EXPECT(lay.out_bytes[k - 7] == len[k]);
+    }
+    EXPECT(lay.pts_p == 0 && lay.eps == plain.eps && lay.out[0] == lay.in_bytes);
+    EXPECT(plain.rho == 0 && plain.mass_q == 0 && plain.transported == 0);
+    std::vector<double> p(bn * 3, 1.0), eps(B, 0.5), rho(B, 0.25), w(B, 1.5);
+    std::vector<float> q(bm * 3, 2.0f);
+    std::vector<int32_t> n_p(B, N), n_q(B, M);
+    std::vector<char> stage(lay.in_bytes);
+    std::memcpy(stage.data() + lay.pts_p, p.data(), bn * 3 * sizeof(double));
+    std::memcpy(stage.data() + lay.eps, eps.data(), (size_t)B * sizeof(double));
+    std::memcpy(stage.data() + lay.rho, rho.data(), (size_t)B * sizeof(double));
+    std::memcpy(stage.data() + lay.mass_q, w.data(), (size_t)B * sizeof(double));
+    std::memcpy(stage.data() + lay.pts_q, q.data(), bm * 3 * sizeof(float));
+    std::memcpy(stage.data() + lay.n_p, n_p.data(), (size_t)B * sizeof(int32_t));
+    std::memcpy(stage.data() + lay.n_q, n_q.data(), (size_t)B * sizeof(int32_t));
+    char* io = static_cast<char*>(std::malloc(lay.bytes));
+    std::memcpy(io, stage.data(), lay.in_bytes);
+    for (int k = 7; k < 15; ++k) std::memset(io + off[k], k, len[k]);          // the kernels' stores, block by block
+    double d; float f; int32_t n;
+    std::memcpy(&d, io + lay.eps + (size_t)(B - 1) * 8, 8);
+    EXPECT(d == 0.5);
+    std::memcpy(&d, io + lay.rho + (size_t)(B - 1) * 8, 8);
+    EXPECT(d == 0.25);
+    std::memcpy(&d, io + lay.mass_q + (size_t)(B - 1) * 8, 8);
+    EXPECT(d == 1.5);
+    std::memcpy(&f, io + lay.pts_q + (bm * 3 - 1) * 4, 4);
+    EXPECT(f == 2.0f);
+    std::memcpy(&n, io + lay.n_q + (size_t)(B - 1) * 4, 4);
+    EXPECT(n == M);
+    for (int k = 7; k < 15; ++k) EXPECT(io[off[k]] == k && io[off[k] + len[k] - 1] == k);
+    reinterpret_cast<double*>(io + lay.transported)[B - 1] = 1.0;              // where kd64_sweeps_unbalanced stores the last one
     std::free(io);
 }
 
@@ -500,6 +571,7 @@ int main(int argc, char** argv) {
             stage64(s[0], s[1], s[2], s[3], actions != 0);
             if (s[3] > 0) stage64_eps(s[0], s[1], s[2], s[3], actions != 0);
             if (s[3] > 0) stage64_match(s[0], s[1], s[2], s[3], actions != 0);
+            if (s[3] > 0) stage64_reach(s[0], s[1], s[2], s[3], actions != 0);
         }
     stage64(1, 1, 4096, 4096, false);                            // the largest clouds of one (sample, step)
     const int mshapes[][3] = {{1, 1, 1}, {1, 5, 3}, {3, 7, 9}, {2, 65, 64}, {1, 1024, 1024}, {5, 1024, 1}, {4, 300, 257}};
@@ -509,6 +581,7 @@ int main(int argc, char** argv) {
         stage_divergence(s[0], s[1], s[2]);
         stage_divergence_unbalanced(s[0], s[1], s[2]);
         stage_divergence64(s[0], s[1], s[2]);
+        stage_divergence64_reach(s[0], s[1], s[2]);
         stage_match64(s[0], s[1], s[2], false);
         stage_match64(s[0], s[1], s[2], true);
     }
