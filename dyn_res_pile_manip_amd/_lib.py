@@ -214,6 +214,14 @@ SIGNATURES = {
     'drp_train_step_loss': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, c_int32_p, c_float_p,
                                            ctypes.c_int, ctypes.c_int, c_float_p, c_int32_p, ctypes.c_int, ctypes.c_int,
                                            ctypes.c_double, ctypes.c_int, c_double_p, c_float_p, c_int32_p]),
+    'drp_train_predict': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, c_int32_p, c_float_p,
+                                         ctypes.c_int, ctypes.c_int, c_float_p]),
+    'drp_train_step_seeded': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, c_int32_p, c_float_p,
+                                             ctypes.c_int, ctypes.c_int, c_float_p, ctypes.c_int, c_float_p]),
+    'drp_train_predict_f64': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, c_int32_p, c_float_p,
+                                             ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p]),
+    'drp_train_grad_f64_seeded': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, c_int32_p, c_float_p,
+                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p]),
     'drp_cloud_transport': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_int32_p, c_float_p, c_int32_p, ctypes.c_int, ctypes.c_int,
                                            ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, c_float_p, c_double_p, c_double_p]),
     'drp_train_step_transport': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, c_int32_p, c_float_p,

@@ -185,6 +185,9 @@ long drp_debug_fetch(drp_ctx* c, const char* name, void* out, size_t out_bytes) 
     // padded rows of drp_train_step_actions)
     else if (!strcmp(name, "train_states")) { b = &c->states; bytes = (size_t)c->marks.lastH * bn * 3 * 4; }
     else if (!strcmp(name, "train_sdelta")) { b = &c->tape_sdelta; bytes = (size_t)c->marks.lastH * bn * 3 * 4; }
+    // d loss / d s_pred as the last trainer call's loss kernel left it, step-major [H][B][N][3]: the loss's own seed after
+    // DRP_TRAIN_EVAL, which runs no reverse pass over it (a reverse pass adds every later step's share below the last step's slice)
+    else if (!strcmp(name, "train_seed")) { b = &c->g_state; bytes = (size_t)c->marks.lastH * bn * 3 * 4; }
     // the last taped pass's neighbour lists of every step, step-major [H][B][N][10] / [H][B][N] (tests: the reversed lists of a
     // training batch, whose rev_off / rev hold lastH sets [H][B][N+1] / [H][B][N*10]: "train_rev_off", "train_rev")
     else if (!strcmp(name, "train_nbr_idx")) { b = &c->tape_idx; bytes = (size_t)c->marks.lastH * bn * DRP_K * 2; }

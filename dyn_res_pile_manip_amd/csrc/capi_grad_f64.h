@@ -310,6 +310,8 @@ struct Tr64Io {
     const int* match_in;            //   the margins the costs [H][B][2] and the optimum's partners [H][B][N]
     double* cost;
     int* match_out;
+    const double* seed;             // TR_LOSS_GIVEN (non-null): the caller's seed of the BATCH [B][H][N][3] in the loss kernel's place
+    bool predict;                   // the forward alone: the chunk's predictions to the caller, no loss, nothing reversed
 };
 
 // the matching kernel's arguments for a chunk: p, the seed and its padding are the chunk's, everything else the batch's (b_off)
@@ -326,6 +328,7 @@ Ka64Args tr64_match_args(const Tr64Ws& k, const Tr64Io& io, int b0, int bc, int 
 }
 
 // forward with tape, loss, reverse pass with weight gradients of the samples [b0, b0 + bc): launches and the state gradient's copy
+// (io.predict: grad_state_out receives the predictions [B][H][N][3] instead -- the tape's slices 1..H lie as the seed does)
 int tr64_chunk(drp_ctx* c, const Tr64Ws& k, const Tr64Io& io, int b0, int bc, int N, int B, int H, double* grad_state_out) {
     hipStream_t st = c->stream;
     const size_t pn = (size_t)bc * N;
@@ -342,8 +345,12 @@ int tr64_chunk(drp_ctx* c, const Tr64Ws& k, const Tr64Io& io, int b0, int bc, in
             hipLaunchKernelGGL(kt64_stage_step, lin3, dim3(256), 0, st, s.state, io.sdelta, b0, N, H, t, (long)(pn * 3), s.sd,
                                ptr<float>(c->ws.s_in), ptr<float>(c->ws.s_delta));
     }));
+    if (io.predict) return f64_copy_state_grad(c, k.tape.state + pn * 3, b0, bc, N, H, grad_state_out);
     // ---- every step's loss term and its seed of the reverse pass; the samples' accumulators start at zero
-    if (io.eps != nullptr) {
+    if (io.seed != nullptr) {
+        // the same slot of the stream and the same seed buffer: the caller's seed at the chunk's sample offset, no term
+        hipLaunchKernelGGL(k64_seed_given, dim3(bc, H), dim3(256), 0, st, io.seed, io.nums, b0, bc, N, H, k.rev.g_state);
+    } else if (io.eps != nullptr) {
         // the same slot of the stream and the same outputs: the plans from the tape's own double states (k_divergence_f64.h)
         Kd64Args a{};
         a.cp = tr_cloud_pair((size_t)N * 3, pn * 3, io.nums, io.targets, io.tnums, H, N, io.M);
@@ -460,7 +467,8 @@ int check_match_loss(drp_ctx* c, const TrLoss& lk, int N) {
 // loss has no yardstick
 int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, bool actions, const float* attrs,
                         const int32_t* particle_nums, const float* particle_dens, int B, int N, int n_rollout, const TrLoss& lk,
-                        double* loss_out, double* loss_terms_out, double* grad_out, double* grad_state_out) {
+                        double* loss_out, double* loss_terms_out, double* grad_out, double* grad_state_out,
+                        double* pred_out = nullptr /* drp_train_predict_f64: the forward alone, every step's prediction [B][H][N][3] */) {
     CHK(need(c, true, actions, false));
     if (lk.transport()) return fail(c, DRP_EINVAL, "no float64 yardstick for loss kind %d", lk.kind);
     CHK(check_bn(c, B, N));
@@ -489,6 +497,13 @@ int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, 
         if (lk.unbalanced()) CHK(check_reach_params(c, lk.eps, lk.rho, lk.mass_q, B, n_rollout));
     }
     if (actions) CHK(check_pushes(c, impulses, B, n_rollout));
+    if (lk.given()) {
+        if (!lk.seed64) return fail(c, DRP_EINVAL, "null argument");
+        const long bad = first_bad_seed(lk.seed64, particle_nums, B, n_rollout, N);
+        if (bad >= 0)
+            return fail(c, DRP_EINVAL, "seed: sample %d step %d row %d is not finite", (int)(bad / N / n_rollout),
+                        (int)(bad / N % n_rollout), (int)(bad % N));
+    }
     HIPCHK(c, hipSetDevice(c->device));
     F64Scope scope(c);
     if (!c->f64_w_valid) CHK(f64_refresh_weights(c));
@@ -505,7 +520,7 @@ int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, 
     // [| margins] [| col_err | self_err [| transported]] [| the matching's costs | its optimum's partners]
     const bool match = lk.match();
     const int M = lk.chamfer() || div || match ? lk.M : 0;
-    const Tr64Arena lay = tr64_layout(B, H, N, M, actions, div, match && lk.match_in != nullptr, reach);
+    const Tr64Arena lay = tr64_layout(B, H, N, M, actions, div, match && lk.match_in != nullptr, reach, lk.given());
     std::vector<float> host(lay.words);
     memcpy(host.data() + lay.states, states, (lay.sdelta - lay.states) * sizeof(float));
     memcpy(host.data() + lay.sdelta, impulses, (lay.attr - lay.sdelta) * sizeof(float));
@@ -522,6 +537,7 @@ int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, 
         memcpy(host.data() + lay.mass_q, lk.mass_q, (size_t)H * B * sizeof(double));
     }
     if (match && lk.match_in) memcpy(host.data() + lay.match_in, lk.match_in, (size_t)H * B * N * sizeof(int32_t));
+    if (lk.given()) memcpy(host.data() + lay.seed, lk.seed64, (size_t)B * H * N * 3 * sizeof(double));
     const size_t n_terms = (size_t)H * B;
     // the matching kinds: behind the margins the costs [H][B][2], then the optimum's partners [H][B][N] (ints, two to a double)
     const size_t n_match = match ? 2 * n_terms + (n_terms * N + 1) / 2 : 0;
@@ -532,6 +548,8 @@ int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, 
     io.actions = actions;
     io.M = M;
     io.total = io.terms + n_terms;
+    if (lk.given()) io.seed = reinterpret_cast<const double*>(io.states + lay.seed);
+    io.predict = pred_out != nullptr;
     if (M > 0) {
         io.targets = io.states + lay.targets;
         io.tnums = reinterpret_cast<const int*>(io.states + lay.tnums);
@@ -555,9 +573,10 @@ int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, 
     }
     HIPCHK(c, hipMemsetAsync(io.total, 0, (size_t)W_TOTAL * sizeof(double), c->stream));
     for (int b0 = 0; b0 < B; b0 += (int)Bc)
-        CHK(tr64_chunk(c, k, io, b0, std::min((int)Bc, B - b0), N, B, H, grad_state_out));
+        CHK(tr64_chunk(c, k, io, b0, std::min((int)Bc, B - b0), N, B, H, io.predict ? pred_out : grad_state_out));
+    if (io.predict) return guarded_wait(c, nullptr);        // (the upload's host block lives until here)
     std::vector<double> terms(n_terms);
-    CHK(d2h(c, terms.data(), io.terms, n_terms * sizeof(double)));
+    if (!lk.given()) CHK(d2h(c, terms.data(), io.terms, n_terms * sizeof(double)));      // (a given seed has no terms: none were written)
     if (grad_out) CHK(d2h(c, grad_out, io.total, (size_t)W_TOTAL * sizeof(double)));
     if (io.margin && lk.margin_out && lk.chamfer()) CHK(d2h(c, lk.margin_out, io.margin, n_terms * sizeof(double)));
     if (match && lk.cost_out) CHK(d2h(c, lk.cost_out, io.cost, 2 * n_terms * sizeof(double)));
@@ -581,6 +600,30 @@ int drp_train_grad_f64(drp_ctx* c, const float* states, const float* states_delt
                        double* grad_out, double* grad_state_out) {
     return train_grad_f64_body(c, states, states_delta, false, attrs, particle_nums, particle_dens, B, N, n_rollout, TrLoss{},
                                loss_out, loss_terms_out, grad_out, grad_state_out);
+}
+
+// the float64 forward alone, and the reverse pass from a seed of the caller's: train_grad_f64_body with TR_LOSS_GIVEN
+int drp_train_predict_f64(drp_ctx* c, const float* states, const float* states_delta, const float* actions, const float* attrs,
+                          const int32_t* particle_nums, const float* particle_dens, int B, int N, int n_rollout,
+                          double* states_pred_out) {
+    if (!c) return DRP_EINVAL;
+    if ((states_delta != nullptr) == (actions != nullptr))
+        return fail(c, DRP_EINVAL, "exactly one of states_delta and actions must be given");
+    if (!states_pred_out) return fail(c, DRP_EINVAL, "null argument");
+    return train_grad_f64_body(c, states, actions != nullptr ? actions : states_delta, actions != nullptr, attrs, particle_nums,
+                               particle_dens, B, N, n_rollout, TrLoss{}, nullptr, nullptr, nullptr, nullptr, states_pred_out);
+}
+
+int drp_train_grad_f64_seeded(drp_ctx* c, const float* states, const float* states_delta, const float* actions, const float* attrs,
+                              const int32_t* particle_nums, const float* particle_dens, int B, int N, int n_rollout,
+                              const double* seed, double* grad_out, double* grad_state_out) {
+    if (!c) return DRP_EINVAL;
+    if ((states_delta != nullptr) == (actions != nullptr))
+        return fail(c, DRP_EINVAL, "exactly one of states_delta and actions must be given");
+    TrLoss lk;
+    lk.kind = TR_LOSS_GIVEN; lk.seed64 = seed;
+    return train_grad_f64_body(c, states, actions != nullptr ? actions : states_delta, actions != nullptr, attrs, particle_nums,
+                               particle_dens, B, N, n_rollout, lk, nullptr, nullptr, grad_out, grad_state_out);
 }
 
 int drp_train_grad_f64_actions(drp_ctx* c, const float* states, const float* actions, const float* attrs,

@@ -14,9 +14,10 @@ const int* tr_nums(const drp_ctx* c, const TrArena& lay) {
 // the HOST gave them (the entry point stages them behind the batch).  The kinds beyond the MSE are include/drp.h's DRP_LOSS_*.
 // The float64 yardstick (capi_grad_f64.h) reads the same description; it has every kind but the transport loss.
 // TR_LOSS_TRANSPORT (k_transport.h) is internal: drp_train_step_transport's, no loss_kind of drp_train_step_loss; so is
-// TR_LOSS_DIVERGENCE (k_divergence.h), drp_train_step_divergence's
+// TR_LOSS_DIVERGENCE (k_divergence.h), drp_train_step_divergence's, and TR_LOSS_GIVEN: no loss at all but the CALLER's d loss / d
+// s_pred as the seed (drp_train_step_seeded, drp_train_grad_f64_seeded; kt_seed_given, k64_seed_given)
 enum { TR_LOSS_MSE = 0, TR_LOSS_CHAMFER = DRP_LOSS_CHAMFER, TR_LOSS_MATCH = DRP_LOSS_MATCH, TR_LOSS_CHAMFER_MATCH = DRP_LOSS_CHAMFER_MATCH,
-       TR_LOSS_TRANSPORT = 4, TR_LOSS_DIVERGENCE = 5 };
+       TR_LOSS_TRANSPORT = 4, TR_LOSS_DIVERGENCE = 5, TR_LOSS_GIVEN = 6 };
 static_assert(KT_MAX_ITERS == DRP_TRANSPORT_MAX_ITERS, "include/drp.h states the kernel's cap");
 struct TrLoss {
     int kind = TR_LOSS_MSE;
@@ -35,6 +36,10 @@ struct TrLoss {
     const double* rho = nullptr;            // TR_LOSS_DIVERGENCE, non-null: the unbalanced divergence -- the caller's reaches [B] ...
     const double* mass_q = nullptr;         //   ... and the targets' total masses [H][B] (both or neither)
     double* transported_out = nullptr;      //   ... and the caller's [H][B], nullable
+    const float* seed = nullptr;            // TR_LOSS_GIVEN: the caller's d loss / d s_pred [B][H][N][3] ...
+    const double* seed64 = nullptr;         //   ... float64: the same in double
+    bool given() const { return kind == TR_LOSS_GIVEN; }
+    bool targeted() const { return kind != TR_LOSS_MSE && kind != TR_LOSS_GIVEN; }     // a loss against target clouds
     bool unbalanced() const { return kind == TR_LOSS_DIVERGENCE && rho != nullptr; }
     bool transport() const { return kind == TR_LOSS_TRANSPORT; }
     bool divergence() const { return kind == TR_LOSS_DIVERGENCE; }
@@ -109,6 +114,8 @@ CloudPair tr_cloud_pair(size_t p_bstride, size_t p_tstride, const int* nums, con
 struct TrainPass {
     int engine = DRP_ENGINE_FUSED;  // which engine writes the tape (pick_tape_engine)
     bool backward = false;          // false: the forward pass and the loss alone
+    bool predict = false;           // with `backward`: the pass ends behind its forward -- the one a backward pass would follow, tape
+                                    //   and all (drp_train_predict) -- with no loss kernel and nothing reversed
     bool defer = false;             // the weight gradients wait for the end of the pass (and the dumps have a buffer per step)
     double* loss_terms = nullptr;   // [H][B], where the loss kernel stores: c->tr_loss, or pinned host memory the caller reads
     TrArena lay{};                  // the batch in c->tr_arena
@@ -149,8 +156,17 @@ int train_forward_backward(drp_ctx* c, int B, int N, const TrainPass& tp) {
         f.cself = cself; f.cself_ok = cself_ok;
         CHK(run_tape_forward(c, tp.engine, B, N, H, f));
     }
+    if (tp.predict) {
+        HIPCHK(c, hipGetLastError());
+        return DRP_OK;
+    }
     // the loss of every step and d loss / d s_pred_t (train/train_gnn_dyn.py:184-186, :203) in one launch
-    if (lk.kind == TR_LOSS_MSE) {
+    if (lk.given()) {
+        // the same slot of the stream, the same seed buffer and the same zero-fill: the caller's seed as staged behind the batch
+        hipLaunchKernelGGL(kt_seed_given, dim3(B, H), dim3(256), 0, st,
+                           reinterpret_cast<const float*>(static_cast<const char*>(c->tr_arena.p) + tp.lay.seed), nums, N, g_state,
+                           backward ? ptr<float>(c->tr_grad) : (float*)nullptr, (size_t)TR_GRAD_PAD + (size_t)H * c->n_cu + 1);
+    } else if (lk.kind == TR_LOSS_MSE) {
         hipLaunchKernelGGL(kt_mse_grad, dim3(B, H), dim3(256), 0, st, states, hstride, given + (size_t)N * 3, in_stride,
                            nums, N, scale, g_state, loss, backward ? ptr<float>(c->tr_grad) : (float*)nullptr,
                            (size_t)TR_GRAD_PAD + (size_t)H * c->n_cu + 1);      // the gradient blob with kmb_step_bwd's counters behind it
@@ -435,7 +451,17 @@ int train_check_args(drp_ctx* c, const float* states, const float* impulses, boo
     }
     if (mode < DRP_TRAIN_EVAL || mode > DRP_TRAIN_UPDATE) return fail(c, DRP_EINVAL, "bad mode %d", mode);
     CHK(check_particle_nums(c, particle_nums, B, N));
-    if (lk.kind != TR_LOSS_MSE) {
+    if (lk.given()) {
+        // the caller's seed: there, for a reverse pass, and a number on every real row
+        if (!lk.seed) return fail(c, DRP_EINVAL, "null argument");
+        if (mode == DRP_TRAIN_EVAL)
+            return fail(c, DRP_EINVAL, "drp_train_step_seeded runs a reverse pass (DRP_TRAIN_GRAD, DRP_TRAIN_UPDATE): the forward alone is drp_train_predict");
+        const int H = c->tr_nroll;
+        const long bad = first_bad_seed(lk.seed, particle_nums, B, H, N);
+        if (bad >= 0)
+            return fail(c, DRP_EINVAL, "seed: sample %d step %d row %d is not finite", (int)(bad / N / H), (int)(bad / N % H), (int)(bad % N));
+    }
+    if (lk.targeted()) {
         CHK(check_target_clouds(c, lk, KC_MAX_POINTS, "target size"));
         if (lk.match()) {
             if (N > KA_MAX_POINTS || lk.M > KA_MAX_POINTS)
@@ -507,7 +533,8 @@ int train_stage_batch(drp_ctx* c, const float* states, const float* impulses, co
     memcpy(pin + lay.attrs, attrs, (size_t)B * (H + 1) * N * sizeof(float));
     memcpy(pin + lay.dens, particle_dens, (size_t)B * sizeof(float));
     memcpy(pin + lay.nums, particle_nums, (size_t)B * sizeof(int));
-    if (tp.lk.kind != TR_LOSS_MSE) {
+    if (tp.lk.given()) memcpy(pin + lay.seed, tp.lk.seed, (size_t)B * H * N * 3 * sizeof(float));
+    if (tp.lk.targeted()) {
         memcpy(pin + lay.targets, tp.lk.targets, (size_t)B * H * tp.lk.M * 3 * sizeof(float));
         memcpy(pin + lay.tnums, tp.lk.target_nums, (size_t)B * H * sizeof(int));
     }
@@ -596,7 +623,7 @@ int train_attempt(drp_ctx* c, int B, int N, const TrainPass& tp, int mode, bool 
 
 int train_step_body(drp_ctx* c, const float* states, const float* impulses, bool actions, const float* attrs,
                     const int32_t* particle_nums, const float* particle_dens, int B, int N, const TrLoss& lk, int mode,
-                    double* loss_out, float* grad_out) {
+                    double* loss_out, float* grad_out, float* pred_out = nullptr /* drp_train_predict: the forward alone */) {
     CHK(train_check_args(c, states, impulses, actions, attrs, particle_nums, particle_dens, B, N, lk, mode));
     HIPCHK(c, hipSetDevice(c->device));
     end_sessions(c);
@@ -610,7 +637,8 @@ int train_step_body(drp_ctx* c, const float* states, const float* impulses, bool
         CHK(pick_tape_engine(c, amax, max_abs(particle_dens, (size_t)B), sd_max, &tp.engine));
     }
     tp.backward = mode != DRP_TRAIN_EVAL;
-    tp.lay = tr_layout(B, H, N, lk.kind != TR_LOSS_MSE ? lk.M : 0, actions, lk.sinkhorn(), lk.unbalanced());
+    tp.predict = pred_out != nullptr;
+    tp.lay = tr_layout(B, H, N, lk.targeted() ? lk.M : 0, actions, lk.sinkhorn(), lk.unbalanced(), lk.given());
     tp.lk = lk;
     tp.actions = actions;
     CHK(train_ensure_workspace(c, B, N, tp));
@@ -619,10 +647,17 @@ int train_step_body(drp_ctx* c, const float* states, const float* impulses, bool
     tp.loss_terms = (loss_out && !c->train_copy_upload) ? back : ptr<double>(c->tr_loss);   // pinned: the terms land where this call reads them
     DrainOnError drain(c);
     CHK(train_stage_batch(c, states, impulses, attrs, particle_nums, particle_dens, B, N, tp));
-    // a pass whose barrier gave up runs again with one workgroup per group (no barrier to wait at) -- for the rest of the
-    // context's life
     bool gave_up = false;
-    CHK(train_attempt(c, B, N, tp, mode, loss_out != nullptr, grad_out, back, &gave_up));
+    if (tp.predict) {
+        // the forward a DRP_TRAIN_GRAD pass runs, then the predicted states as they lie, [B][H][N][3]; nothing else happens
+        CHK(train_forward_backward(c, B, N, tp));
+        CHK(d2h(c, pred_out, c->states.p, (size_t)B * H * N * 3 * sizeof(float)));
+        CHK(drp_sync(c));
+    } else {
+        // a pass whose barrier gave up runs again with one workgroup per group (no barrier to wait at) -- for the rest of the
+        // context's life
+        CHK(train_attempt(c, B, N, tp, mode, loss_out != nullptr, grad_out, back, &gave_up));
+    }
     if (gave_up && c->pol.train_parts != 1) {
         c->pol.train_parts = 1;                     // the device is shared or masked: the groups' workgroups are not all resident
         c->dv(DV_TRAIN_BARRIER_RETRY);
@@ -677,6 +712,33 @@ int drp_train_step_loss(drp_ctx* c, const float* states, const float* states_del
     const bool by_actions = actions != nullptr;
     return train_step_body(c, states, by_actions ? actions : states_delta, by_actions, attrs, particle_nums, particle_dens, B, N, lk,
                            mode, loss_out, grad_out);
+}
+
+// the forward of a DRP_TRAIN_GRAD pass alone -- the tape engine, the tape, the padded mode -- and every step's prediction out
+int drp_train_predict(drp_ctx* c, const float* states, const float* states_delta, const float* actions, const float* attrs,
+                      const int32_t* particle_nums, const float* particle_dens, int B, int N, float* states_pred_out) {
+    if (!c) return DRP_EINVAL;
+    if ((states_delta != nullptr) == (actions != nullptr))
+        return fail(c, DRP_EINVAL, "exactly one of states_delta and actions must be given");
+    if (!states_pred_out) return fail(c, DRP_EINVAL, "null argument");
+    const bool by_actions = actions != nullptr;
+    return train_step_body(c, states, by_actions ? actions : states_delta, by_actions, attrs, particle_nums, particle_dens, B, N,
+                           TrLoss{}, DRP_TRAIN_GRAD, nullptr, nullptr, states_pred_out);
+}
+
+// the same body with the caller's d loss / d s_pred in the loss kernel's place (TR_LOSS_GIVEN): everything behind the seed is
+// train_forward_backward's and train_attempt's
+int drp_train_step_seeded(drp_ctx* c, const float* states, const float* states_delta, const float* actions, const float* attrs,
+                          const int32_t* particle_nums, const float* particle_dens, int B, int N, const float* seed, int mode,
+                          float* grad_out) {
+    if (!c) return DRP_EINVAL;
+    if ((states_delta != nullptr) == (actions != nullptr))
+        return fail(c, DRP_EINVAL, "exactly one of states_delta and actions must be given");
+    TrLoss lk;
+    lk.kind = TR_LOSS_GIVEN; lk.seed = seed;
+    const bool by_actions = actions != nullptr;
+    return train_step_body(c, states, by_actions ? actions : states_delta, by_actions, attrs, particle_nums, particle_dens, B, N, lk,
+                           mode, nullptr, grad_out);
 }
 
 int drp_train_set_lr(drp_ctx* c, double lr) {

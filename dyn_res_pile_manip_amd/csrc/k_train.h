@@ -44,6 +44,36 @@ kt_mse_grad(const float* __restrict__ s_pred, size_t pred_stride, const float* _
     if (threadIdx.x == 0) loss[(size_t)t * B + b] = (s_w[0] + s_w[1] + s_w[2] + s_w[3]) * (double)inv;   // one slot per (step, sample)
 }
 
+// d loss / d s_pred_t as the CALLER gives it (drp_train_step_seeded), in kt_mse_grad's slot of the stream and on its grid B x H:
+// the staged seed [B][H][N][3] (the caller's layout, train_host.h: TrArena::seed) to g_out [H][B][N][3], real rows bit for bit,
+// +0.0f on rows n >= particle_nums[b] whatever lies there (selected, never multiplied: a NaN in the padding stays there), and
+// the zero-fill of the gradient blob behind it as every loss kernel does.  No loss term: the value is the caller's.  Where N * 3
+// is a multiple of four, both slices start on 16 bytes (the block and g_out do) and the copy is float4s.
+__global__ void __launch_bounds__(256)
+kt_seed_given(const float* __restrict__ seed /* [B][H][N][3] */, const int* __restrict__ particle_nums, int N,
+              float* __restrict__ g_out /* [H][B][N][3] */, float* __restrict__ zero /* nullable */, size_t n_zero) {
+    const int b = blockIdx.x, t = blockIdx.y, B = gridDim.x, H = gridDim.y;
+    train_zero_fill(zero, n_zero, 256);
+    const int n3 = N * 3, real = min(max(particle_nums[b], 0), N) * 3;
+    const float* s = seed + ((size_t)b * H + t) * n3;
+    float* g = g_out + ((size_t)t * B + b) * n3;
+    if ((n3 & 3) == 0) {
+        const float4* s4 = reinterpret_cast<const float4*>(s);
+        float4* g4 = reinterpret_cast<float4*>(g);
+        for (int i = threadIdx.x; i < n3 / 4; i += 256) {
+            float4 v = s4[i];
+            const int e = i * 4;
+            v.x = e + 0 < real ? v.x : 0.0f;
+            v.y = e + 1 < real ? v.y : 0.0f;
+            v.z = e + 2 < real ? v.z : 0.0f;
+            v.w = e + 3 < real ? v.w : 0.0f;
+            g4[i] = v;
+        }
+    } else {
+        for (int i = threadIdx.x; i < n3; i += 256) g[i] = i < real ? s[i] : 0.0f;
+    }
+}
+
 // A training batch arrives as ONE copy (pinned staging -> arena: states | impulses | attributes | densities | particle counts,
 // the caller's layouts).  The states and the counts are read where they land; this launch puts the rest where the step
 // kernels expect it: the impulses step-major ([H][B][N][3]: a step's slice is the s_delta of that step, and the tape's),

@@ -92,6 +92,30 @@ __global__ __launch_bounds__(256) void kt64_mse(const double* __restrict__ state
     }
 }
 
+// the seed of the reverse pass as the CALLER gives it (drp_train_grad_f64_seeded), in kt64_mse's slot and on its grid (bc, H): the
+// batch's seed [B][H][N][3] (doubles, the caller's layout) at the chunk's sample offset b0 to seed_out [H][bc*N,3], real rows bit
+// for bit, +0.0 on rows n >= nums[b0 + b] whatever lies there.  No loss term.  Where N * 3 is even both slices start on 16 bytes
+// and the copy is double2s.
+__global__ __launch_bounds__(256) void k64_seed_given(const double* __restrict__ seed_in, const int* __restrict__ nums, int b0, int bc,
+                                                      int N, int H, double* __restrict__ seed_out) {
+    const int b = blockIdx.x, t = blockIdx.y;
+    const int n3 = N * 3, real = min(max(nums[b0 + b], 0), N) * 3;
+    const double* s = seed_in + ((size_t)(b0 + b) * H + t) * n3;
+    double* g = seed_out + ((size_t)t * bc + b) * n3;
+    if ((n3 & 1) == 0) {
+        const double2* s2 = reinterpret_cast<const double2*>(s);
+        double2* g2 = reinterpret_cast<double2*>(g);
+        for (int i = threadIdx.x; i < n3 / 2; i += 256) {
+            double2 v = s2[i];
+            v.x = i * 2 + 0 < real ? v.x : 0.0;
+            v.y = i * 2 + 1 < real ? v.y : 0.0;
+            g2[i] = v;
+        }
+    } else {
+        for (int i = threadIdx.x; i < n3; i += 256) g[i] = i < real ? s[i] : 0.0;
+    }
+}
+
 // d loss / d s_pred_{t-1} += the step's share: the + s_cur of the output, then the relation encoder's (kg_state_share).
 // g_prev holds the MSE's seed of step t - 1 when this runs.
 __global__ __launch_bounds__(256) void kt64_state_bwd(const double* __restrict__ g_out, const double* __restrict__ g_diff,

@@ -12,13 +12,16 @@
 // [B][H][M][3] | their counts [B][H] (ints) -- with M = 0 the layout, and so the one copy, is drp_train_step's;
 // drp_train_step_actions (`actions`): the pushes [B][H][4] where the impulses are, everything behind them moving up;
 // drp_train_step_transport, drp_train_step_divergence (`eps`): behind everything the regularisation strengths [B] (doubles);
-// drp_train_step_divergence_unbalanced (`reach`, with `eps`): behind those the reaches [B] | the targets' masses [H][B] (doubles)
-struct TrArena { size_t states, sdelta, attrs, dens, nums, targets, tnums, bytes, eps, rho, mass_q; };
+// drp_train_step_divergence_unbalanced (`reach`, with `eps`): behind those the reaches [B] | the targets' masses [H][B] (doubles);
+// drp_train_step_seeded (`seed`): behind everything the caller's d loss / d s_pred [B][H][N][3] (floats, the caller's layout) -- a
+// call without it takes zero bytes for it, and nothing ahead of it moves
+struct TrArena { size_t states, sdelta, attrs, dens, nums, targets, tnums, bytes, eps, rho, mass_q, seed; };
 // the impulse block: what train_stage_batch copies to TrArena::sdelta
 inline size_t tr_impulse_bytes(int B, int H, int N, bool actions) {
     return (actions ? (size_t)B * H * 4 : (size_t)B * H * N * 3) * sizeof(float);
 }
-inline TrArena tr_layout(int B, int H, int N, int M = 0, bool actions = false, bool eps = false, bool reach = false) {
+inline TrArena tr_layout(int B, int H, int N, int M = 0, bool actions = false, bool eps = false, bool reach = false,
+                         bool seed = false) {
     auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
     TrArena a{};
     a.states = 0;
@@ -41,6 +44,10 @@ inline TrArena tr_layout(int B, int H, int N, int M = 0, bool actions = false, b
         a.mass_q = up(a.rho + (size_t)B * sizeof(double));
         a.bytes = up(a.mass_q + (size_t)H * B * sizeof(double));
     }
+    if (seed) {
+        a.seed = a.bytes;
+        a.bytes = up(a.seed + (size_t)B * H * N * 3 * sizeof(float));
+    }
     return a;
 }
 
@@ -51,10 +58,12 @@ inline TrArena tr_layout(int B, int H, int N, int M = 0, bool actions = false, b
 // the regularisation strengths [B] (doubles, two words each) on the next even word -- the vector's base is 256-byte aligned on
 // the device, so an even word is an 8-byte boundary -- and nothing ahead of them moves; drp_train_grad_f64_divergence_unbalanced
 // (`reach`, with `eps`): behind eps the reaches [B] | the targets' masses [H][B] (doubles too); drp_train_grad_f64_match with a matching
-// of the caller's (`match_in`): behind everything the partners [H][B][N] (ints), nothing ahead of them moving either
-struct Tr64Arena { size_t states, sdelta, attr, dens, nums, targets, tnums, words, eps, match_in, rho, mass_q; };
+// of the caller's (`match_in`): behind everything the partners [H][B][N] (ints), nothing ahead of them moving either;
+// drp_train_grad_f64_seeded (`seed`): behind everything the caller's d loss / d s_pred [B][H][N][3] (doubles, two words each) on
+// the next multiple of four words -- a 16-byte boundary on the device --, nothing ahead of it moving
+struct Tr64Arena { size_t states, sdelta, attr, dens, nums, targets, tnums, words, eps, match_in, rho, mass_q, seed; };
 inline Tr64Arena tr64_layout(int B, int H, int N, int M = 0, bool actions = false, bool eps = false, bool match_in = false,
-                             bool reach = false) {
+                             bool reach = false, bool seed = false) {
     Tr64Arena a{};
     a.states = 0;
     a.sdelta = a.states + (size_t)B * (H + 1) * N * 3;
@@ -79,6 +88,10 @@ inline Tr64Arena tr64_layout(int B, int H, int N, int M = 0, bool actions = fals
     if (match_in) {
         a.match_in = a.words;
         a.words = a.match_in + (size_t)H * B * N;
+    }
+    if (seed) {
+        a.seed = (a.words + 3) & ~(size_t)3;
+        a.words = a.seed + 2 * (size_t)B * H * N * 3;
     }
     return a;
 }
@@ -276,6 +289,18 @@ inline TrDivLoss tr_div_loss_layout(int B, int H, int N, bool unbalanced = false
 inline int first_bad_eps(const double* eps, int B) {
     for (int b = 0; b < B; ++b)
         if (!(eps[b] > 0.0) || !std::isfinite(eps[b])) return b;
+    return -1;
+}
+// the first coordinate of a seed [B][H][N][3] (drp_train_step_seeded's d loss / d s_pred, the caller's layout) on a real row -- row
+// n < counts[b] of every step -- that is infinite or no number, as (b * H + t) * N + row, or -1 (the padded rows are never read as
+// numbers: rubbish there is allowed); T: float, or drp_train_grad_f64_seeded's double
+template <typename T>
+inline long first_bad_seed(const T* seed, const int32_t* counts, int B, int H, int N) {
+    for (int b = 0; b < B; ++b)
+        for (int t = 0; t < H; ++t)
+            for (int i = 0; i < counts[b] && i < N; ++i)
+                for (int d = 0; d < 3; ++d)
+                    if (!std::isfinite(seed[(((size_t)b * H + t) * N + i) * 3 + d])) return ((long)b * H + t) * N + i;
     return -1;
 }
 // the unbalanced divergence's reach and target mass of one problem (include/drp.h: drp_cloud_divergence_unbalanced): 0 where it

@@ -836,6 +836,62 @@ class Engine(object):
                                  want_grad, loss, match_weight, want_match)
         return out if want_match else out[:2]
 
+    # ---- training on a loss of the caller's (include/drp.h: drp_train_predict, drp_train_step_seeded) ----------------------
+    def _seeded_batch(self, states, states_delta, actions, attrs, particle_nums, particle_dens, need_begin):
+        """the batch of the four seeded calls: exactly one impulse source -> (_train_batch's arrays, (B, N, H), the C arguments up
+        to N)"""
+        if (states_delta is None) == (actions is None):
+            raise ValueError('exactly one of states_delta and actions must be given')
+        by_actions = actions is not None
+        keep, (B, N, H, _), (ps, pi, pa, pn, pd, _, _) = self._train_batch(
+            states, _f32(actions) if by_actions else states_delta, attrs, particle_nums, particle_dens, None, None, by_actions,
+            need_begin)
+        return keep, (B, N, H), (self.h, ps, None if by_actions else pi, pi if by_actions else None, pa, pn, pd, B, N)
+
+    def train_predict(self, states, attrs, particle_nums, particle_dens, states_delta=None, actions=None):
+        """What the training forward predicts: every step's state [B, n_rollout, N, 3] float32, from the forward exactly as
+        train_step_seeded (and train_step(mode='grad')) runs it -- on real rows the bits of that call's own forward (include/drp.h:
+        drp_train_predict).  states_delta [B, n_rollout, N, 3] or actions [B, n_rollout, 4] -- exactly one of the two.  Rows
+        n >= particle_nums[b] come back as the forward leaves them.  Needs train_begin; changes no weight, Adam moment or
+        iteration count."""
+        keep, (B, N, H), args = self._seeded_batch(states, states_delta, actions, attrs, particle_nums, particle_dens, True)
+        pred = np.empty((B, H, N, 3), np.float32)
+        self._ck(self.lib.drp_train_predict(*args, _fp(pred)))
+        return pred
+
+    def train_step_seeded(self, states, attrs, particle_nums, particle_dens, seed, states_delta=None, actions=None, mode='update',
+                          want_grad=False):
+        """train_step with the reverse pass seeded by the caller: seed [B, n_rollout, N, 3], seed[b, t, n] = d loss / d
+        s_pred_t[b, n], complete (no 1 / (n_rollout B), no 1 / (3 n_b) is applied); rows n >= particle_nums[b] are ignored
+        (include/drp.h: drp_train_step_seeded).  mode 'grad' or 'update' -> the gradient blob, or None."""
+        keep, (B, N, H), args = self._seeded_batch(states, states_delta, actions, attrs, particle_nums, particle_dens, True)
+        seed = _f32(seed)
+        assert seed.shape == (B, H, N, 3)
+        grad = np.empty((L.DRP_N_WEIGHTS,), np.float32) if want_grad else None
+        self._ck(self.lib.drp_train_step_seeded(*args, _fp(seed), L.TRAIN_MODES[mode], _opt(_fp, grad)))
+        return grad
+
+    def train_step_custom(self, loss_fn, states, attrs, particle_nums, particle_dens, states_delta=None, actions=None,
+                          mode='update', want_grad=False, context=None):
+        """One training step on a loss that is a Python function: loss_fn(pred, context) -> (value, grad), a pure function of
+        pred [B, n_rollout, N, 3] (train_predict's; it must work on float32 and float64 arrays alike), grad = d value / d pred in
+        pred's shape; context: whatever the caller passes through.  mode='eval': train_predict and loss_fn, the gradient dropped;
+        else train_predict, loss_fn, train_step_seeded -- the forward runs twice, and being deterministic gives the same bits
+        both times, so the gradient is taken at the right point -> (loss, gradient blob or None).  (losses.py: worked examples,
+        and torch_loss for a loss written in torch.)"""
+        if mode not in L.TRAIN_MODES:
+            raise ValueError('mode must be one of %s' % (tuple(L.TRAIN_MODES),))
+        pred = self.train_predict(states, attrs, particle_nums, particle_dens, states_delta=states_delta, actions=actions)
+        value, seed = loss_fn(pred, context)
+        if mode == 'eval':
+            return float(value), None
+        seed = np.asarray(seed)
+        if seed.shape != pred.shape:
+            raise ValueError('loss_fn must return a gradient of pred\'s shape %s, got %s' % (pred.shape, seed.shape))
+        grad = self.train_step_seeded(states, attrs, particle_nums, particle_dens, seed, states_delta=states_delta, actions=actions,
+                                      mode=mode, want_grad=want_grad)
+        return float(value), grad
+
     # ---- one-shots on two cloud batches (include/drp.h: drp_cloud_chamfer, drp_cloud_chamfer_f64, drp_cloud_match) ---------
     @staticmethod
     def _cloud_pair(p, q, n_p, n_q):
@@ -1249,6 +1305,65 @@ class Engine(object):
         info = {'match': match, 'cost': cost[..., 0].copy(), 'opt_cost': cost[..., 1].copy(),
                 'chamfer_margin': margin} if want_info else None
         return (out.value, terms, grad) + ((gs,) if want_state else ()) + ((info,) if want_info else ())
+
+    def train_predict_f64(self, states, attrs, particle_nums, particle_dens, states_delta=None, actions=None):
+        """train_predict in float64 on the device: every step's predicted state [B, n_rollout, N, 3] float64 of train_grad_f64's
+        forward (include/drp.h: drp_train_predict_f64).  n_rollout is read from the arrays; train_grad_f64's one-shot contract."""
+        keep, (B, N, H), args = self._seeded_batch(states, states_delta, actions, attrs, particle_nums, particle_dens, False)
+        pred = np.empty((B, max(H, 0), N, 3), np.float64)
+        self._ck(self.lib.drp_train_predict_f64(*args, H, _dp(pred)))
+        return pred
+
+    def train_grad_f64_seeded(self, states, attrs, particle_nums, particle_dens, seed, states_delta=None, actions=None,
+                              want_state=False):
+        """What train_step_seeded(mode='grad') computes, in float64 on the device: seed [B, n_rollout, N, 3] float64 = d loss / d
+        every step's predicted state, complete; padded rows ignored (include/drp.h: drp_train_grad_f64_seeded) -> (gradient blob
+        [38403][, d loss / d every step's predicted state with the later steps' shares, [B, n_rollout, N, 3]]) as float64.
+        train_grad_f64's one-shot contract."""
+        keep, (B, N, H), args = self._seeded_batch(states, states_delta, actions, attrs, particle_nums, particle_dens, False)
+        seed = _f64(seed)
+        assert seed.shape == (B, H, N, 3)
+        grad = np.empty((L.DRP_N_WEIGHTS,), np.float64)
+        gs = np.empty((B, max(H, 0), N, 3), np.float64) if want_state else None
+        self._ck(self.lib.drp_train_grad_f64_seeded(*args, H, _dp(seed), _dp(grad), _opt(_dp, gs)))
+        return (grad, gs) if want_state else (grad,)
+
+    def train_gradient_probe_custom(self, loss_fn, states, attrs, particle_nums, particle_dens, states_delta=None, actions=None,
+                                    context=None):
+        """train_gradient_probe for a loss of the caller's (train_step_custom's loss_fn): the fp32 pair -- train_predict, loss_fn,
+        train_step_seeded(mode='grad') -- held against the float64 pair -- train_predict_f64, loss_fn, train_grad_f64_seeded -- on
+        the same batch -> train_gradient_probe's dict ('tensors', 'worst', 'rel', 'loss32', 'loss64', 'loss_diff', 'tape') with
+        'loss_kind': 'custom' and 'seed_rel' = max |seed32 - seed64| / max |seed64|: how far the loss's own gradient moves under
+        the fp32 drift of the prediction -- the loss's conditioning, as opposed to the tape's arithmetic.  Needs train_begin; it
+        changes no weight, Adam moment or iteration count; like train_gradient_probe it ends a running planner session and
+        resets the dispatch marks."""
+        from .weights import STATE_DICT_KEYS
+        kw = {'states_delta': states_delta, 'actions': actions}
+        self.dispatch_reset()
+        pred32 = self.train_predict(states, attrs, particle_nums, particle_dens, **kw)
+        loss32, seed32 = loss_fn(pred32, context)
+        g32 = self.train_step_seeded(states, attrs, particle_nums, particle_dens, seed32, mode='grad', want_grad=True, **kw)
+        tape = 'mfma' if 'k_aggregate_tape' in self.last_dispatch() else 'fused'
+        pred64 = self.train_predict_f64(states, attrs, particle_nums, particle_dens, **kw)
+        loss64, seed64 = loss_fn(pred64, context)
+        g64, = self.train_grad_f64_seeded(states, attrs, particle_nums, particle_dens, seed64, **kw)
+        loss32, loss64 = float(loss32), float(loss64)
+        tensors, off, worst = {}, 0, None
+        for key, shape in STATE_DICT_KEYS:
+            n = int(np.prod(shape))
+            err = np.abs(g32[off:off + n].astype(np.float64) - g64[off:off + n])
+            err = float(np.where(np.isnan(err), np.inf, err).max())
+            ref = float(np.abs(g64[off:off + n]).max())
+            tensors[key] = {'max_abs_err': err, 'max_abs_ref': ref, 'rel': err / max(ref, 1e-300)}
+            if worst is None or tensors[key]['rel'] > tensors[worst]['rel']:
+                worst = key
+            off += n
+        real = np.arange(pred32.shape[2])[None, :] < _i32(particle_nums).reshape(-1, 1)          # [B, N]
+        s32 = np.where(real[:, None, :, None], np.asarray(seed32, np.float64), 0.0)
+        s64 = np.where(real[:, None, :, None], np.asarray(seed64, np.float64), 0.0)
+        return {'tensors': tensors, 'worst': worst, 'rel': tensors[worst]['rel'], 'loss32': loss32, 'loss64': loss64,
+                'loss_diff': abs(loss32 - loss64), 'tape': tape, 'loss_kind': 'custom',
+                'seed_rel': float(np.abs(s32 - s64).max() / max(np.abs(s64).max(), 1e-300))}
 
     def train_gradient_probe(self, states, states_delta, attrs, particle_nums, particle_dens, actions=None, targets=None,
                              target_nums=None, eps=None, iters=None, loss=None, match_weight=0.5, reach=None, mass_q=None):

@@ -124,6 +124,8 @@ from ._lib import TRANSPORT_MAX_ITERS  # noqa: E402  (include/drp.h: DRP_TRANSPO
 
 
 def check_loss(loss, match_weight=0.5, transport_eps_scale=TRANSPORT_EPS_SCALE, transport_iters=TRANSPORT_ITERS):
+    if callable(loss):                      # a loss of the caller's (Engine.train_step_custom): no option above is its
+        return
     if loss not in LOSSES + MATCH_LOSSES + TRANSPORT_LOSSES + DIVERGENCE_LOSSES:
         raise ValueError('loss must be one of %s or %s or %s or %s, got %r' % (LOSSES, MATCH_LOSSES, TRANSPORT_LOSSES, DIVERGENCE_LOSSES, loss))
     if loss == 'chamfer+match' and not 0.0 < float(match_weight) < 1.0:
@@ -193,6 +195,32 @@ def transport_eps(particle_dens, transport_eps_scale=TRANSPORT_EPS_SCALE):
     return float(transport_eps_scale) / np.asarray(particle_dens, np.float64).reshape(-1)
 
 
+def refuse_custom_probe(loss, option):
+    """the five older probe options hold a built-in loss against its own float64 yardstick: a callable loss has none of those"""
+    if callable(loss):
+        raise ValueError('%s probes the built-in losses: a callable loss (%s) is probed through custom_probe_every'
+                         % (option, getattr(loss, '__name__', repr(loss))))
+
+
+def check_custom_probe_option(loss, custom_probe_every, grad_probe_every=0, probe_every=0, sinkhorn_probe_every=0, match_probe_every=0,
+                              sinkhorn_reach_probe_every=0):
+    """custom_probe_every of train() / main(): the probe schedule of a callable loss alone (probe_batch_custom), and no companion of
+    the five other schedules -- each of which refuses a callable loss, naming it"""
+    for option, every in (('grad_probe_every', grad_probe_every), ('probe_every', probe_every),
+                          ('sinkhorn_probe_every', sinkhorn_probe_every), ('match_probe_every', match_probe_every),
+                          ('sinkhorn_reach_probe_every', sinkhorn_reach_probe_every)):
+        if every > 0:
+            refuse_custom_probe(loss, option)
+    if int(custom_probe_every) != custom_probe_every or custom_probe_every < 0:
+        raise ValueError('custom_probe_every must be a non-negative integer, got %r' % (custom_probe_every,))
+    if custom_probe_every > 0:
+        if grad_probe_every > 0 or probe_every > 0 or sinkhorn_probe_every > 0 or match_probe_every > 0 or sinkhorn_reach_probe_every > 0:
+            raise ValueError('give custom_probe_every alone, not with grad_probe_every, probe_every, sinkhorn_probe_every, '
+                             'match_probe_every or sinkhorn_reach_probe_every')
+        if not callable(loss):
+            raise ValueError('custom_probe_every needs a callable loss, got %r: probe_every probes the losses of %s' % (loss, LOSSES))
+
+
 def refuse_match_probe(loss):
     if loss in MATCH_LOSSES + TRANSPORT_LOSSES + DIVERGENCE_LOSSES:
         raise ValueError('there is no float64 yardstick for the matching loss yet: loss=%r cannot be probed '
@@ -202,6 +230,8 @@ def refuse_match_probe(loss):
 def check_depth_only(data, loss, impulses):
     """a batch made from depth frames alone has no tracked targets and no recorded impulses: anything but the Chamfer loss through
     the push would train on zeros"""
+    if getattr(data, 'depth_only', False) and callable(loss) and impulses == 'actions':
+        return                              # a loss of the caller's: what it reads of the batch is its own affair
     if getattr(data, 'depth_only', False) and not (loss in UNTRACKED_LOSSES + DIVERGENCE_LOSSES and impulses == 'actions'):
         raise ValueError('a depth-only batch (DepthDataset) holds no tracked states and no impulses: it needs loss=\'chamfer\' (or '
                          'one of %s) and impulses=\'actions\', got loss=%r, impulses=%r'
@@ -215,6 +245,11 @@ def resolve_data_options(data, loss, impulses):
     if data not in DATA:
         raise ValueError('data must be one of %s, got %r' % (DATA, data))
     if data == 'depth':
+        if callable(loss):
+            if impulses not in (None, 'actions'):
+                raise ValueError('data=\'depth\' has no recorded impulses: impulses=%r contradicts the impulses=\'actions\' it implies'
+                                 % (impulses,))
+            return loss, 'actions'
         if loss not in (None,) + UNTRACKED_LOSSES + DIVERGENCE_LOSSES:
             raise ValueError('data=\'depth\' trains on untracked clouds: loss=%r contradicts the loss=\'chamfer\' it implies' % (loss,))
         if impulses not in (None, 'actions'):
@@ -249,7 +284,9 @@ def run_batch(model, optimizer, data, phase='train', n_rollout=None, loss='mse',
     again with the Sinkhorn divergence as each step's term, under the same two options (Engine.train_step_divergence).
     sinkhorn_reach_scale (not None) and sinkhorn_mass: the unbalanced divergence with rho_b = sinkhorn_reach_scale /
     particle_dens[b] and the targets' masses of sinkhorn_mass_q (check_sinkhorn_options); `stats`, a dict, then receives
-    'transported': the mean over the batch's problems of the share of the predicted mass the plan pairs with something."""
+    'transported': the mean over the batch's problems of the share of the predicted mass the plan pairs with something.
+    A CALLABLE loss: loss(pred, context) -> (value, d value / d pred) of losses.py, trained through Engine.train_step_custom
+    with `data` itself as the context, on either impulse source and, with impulses='actions', on depth_only batches too."""
     check_loss(loss, match_weight, transport_eps_scale, transport_iters)
     check_sinkhorn_options(loss, sinkhorn_reach_scale, sinkhorn_mass, 0, transport_eps_scale)
     if impulses not in IMPULSES:
@@ -265,6 +302,11 @@ def run_batch(model, optimizer, data, phase='train', n_rollout=None, loss='mse',
     if hasattr(model, '_claim'):
         model._claim()                                  # models share the process's context: this one's weights in
         model._device_ahead = model._device_ahead or mode == 'update'
+    if callable(loss):
+        value, _ = model.engine.train_step_custom(loss, states, _np(attrs), _np(particle_nums, np.int32), _np(particle_dens),
+                                                  states_delta=None if actions is not None else _np(states_delta), actions=actions,
+                                                  mode=mode, context=data)
+        return value
     if loss in MATCH_LOSSES:
         value, _ = model.engine.train_step_loss(states, _np(attrs), _np(particle_nums, np.int32), _np(particle_dens), _np(data[6]),
                                                 _np(data[7], np.int32), states_delta=None if actions is not None else _np(states_delta),
@@ -335,6 +377,24 @@ def probe_batch(model, data, impulses='data', loss='mse'):
                                              actions=batch_actions(data) if impulses == 'actions' else None, **extra)
 
 
+def probe_batch_custom(model, data, loss, impulses='data'):
+    """Engine.train_gradient_probe_custom on a collated batch with a callable loss, `data` itself as its context: the fp32 pair
+    (train_predict, the loss, train_step_seeded) against the float64 pair; the result has 'loss_kind': 'custom' and 'seed_rel',
+    the share of a finding that is the loss's own conditioning.  Weights, Adam state and iteration count are untouched."""
+    if not callable(loss):
+        raise ValueError('probe_batch_custom needs a callable loss, got %r' % (loss,))
+    if impulses not in IMPULSES:
+        raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
+    check_depth_only(data, loss, impulses)
+    states, states_delta, attrs, particle_nums, particle_dens = [data[i] for i in range(5)]
+    if hasattr(model, '_claim'):
+        model._claim()
+    by_actions = impulses == 'actions'
+    return model.engine.train_gradient_probe_custom(loss, _np(states), _np(attrs), _np(particle_nums, np.int32), _np(particle_dens),
+                                                    states_delta=None if by_actions else _np(states_delta),
+                                                    actions=batch_actions(data) if by_actions else None, context=data)
+
+
 def probe_batch_sinkhorn(model, data, impulses='data', transport_eps_scale=TRANSPORT_EPS_SCALE, transport_iters=TRANSPORT_ITERS,
                          sinkhorn_reach_scale=None, sinkhorn_mass='unit'):
     """Engine.train_gradient_probe with the Sinkhorn divergence on a collate_untracked batch: train_step_divergence(mode='grad')
@@ -397,6 +457,7 @@ def check_match_probe_option(loss, match_probe_every, grad_probe_every=0, probe_
     if int(match_probe_every) != match_probe_every or match_probe_every < 0:
         raise ValueError('match_probe_every must be a non-negative integer, got %r' % (match_probe_every,))
     if match_probe_every > 0:
+        refuse_custom_probe(loss, 'match_probe_every')
         if grad_probe_every > 0 or probe_every > 0 or sinkhorn_probe_every > 0:
             raise ValueError('give match_probe_every alone, not with grad_probe_every, probe_every or sinkhorn_probe_every')
         if loss not in MATCH_LOSSES:
@@ -410,6 +471,7 @@ def check_sinkhorn_probe_option(loss, sinkhorn_probe_every, grad_probe_every=0, 
     if int(sinkhorn_probe_every) != sinkhorn_probe_every or sinkhorn_probe_every < 0:
         raise ValueError('sinkhorn_probe_every must be a non-negative integer, got %r' % (sinkhorn_probe_every,))
     if sinkhorn_probe_every > 0:
+        refuse_custom_probe(loss, 'sinkhorn_probe_every')
         if grad_probe_every > 0 or probe_every > 0:
             raise ValueError('give sinkhorn_probe_every alone, not with grad_probe_every or probe_every')
         if loss not in DIVERGENCE_LOSSES:
@@ -425,6 +487,7 @@ def check_sinkhorn_reach_probe_option(loss, sinkhorn_reach_probe_every, sinkhorn
     if int(sinkhorn_reach_probe_every) != sinkhorn_reach_probe_every or sinkhorn_reach_probe_every < 0:
         raise ValueError('sinkhorn_reach_probe_every must be a non-negative integer, got %r' % (sinkhorn_reach_probe_every,))
     if sinkhorn_reach_probe_every > 0:
+        refuse_custom_probe(loss, 'sinkhorn_reach_probe_every')
         if grad_probe_every > 0 or probe_every > 0 or sinkhorn_probe_every > 0 or match_probe_every > 0:
             raise ValueError('give sinkhorn_reach_probe_every alone, not with grad_probe_every, probe_every, sinkhorn_probe_every or '
                              'match_probe_every')
@@ -440,6 +503,9 @@ def check_probe_options(loss, grad_probe_every, probe_every):
     """the two probe schedules of train() / main(): grad_probe_every (the MSE yardstick alone) and probe_every (every loss of
     LOSSES; the matching losses have no float64 yardstick yet and refuse both)"""
     check_loss(loss)
+    for option, every in (('grad_probe_every', grad_probe_every), ('probe_every', probe_every)):
+        if every > 0:
+            refuse_custom_probe(loss, option)
     if grad_probe_every > 0 or probe_every > 0:
         refuse_match_probe(loss)
     if grad_probe_every > 0 and probe_every > 0:
@@ -452,7 +518,7 @@ def check_probe_options(loss, grad_probe_every, probe_every):
 def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=None, first_epoch=0, grad_probe_every=0,
           loss='mse', impulses='data', probe_every=0, match_weight=0.5, transport_eps_scale=TRANSPORT_EPS_SCALE,
           transport_iters=TRANSPORT_ITERS, sinkhorn_probe_every=0, match_probe_every=0, sinkhorn_reach_scale=None,
-          sinkhorn_mass='unit', sinkhorn_reach_probe_every=0):
+          sinkhorn_mass='unit', sinkhorn_reach_probe_every=0, custom_probe_every=0):
     """train/train_gnn_dyn.py:134-246 without the file I/O: `dataloaders` = {'train': iterable of
     collated batches, 'valid': ...}.  Returns {'best_valid_loss', 'history': [(epoch, phase, rmse)]}.
     ckp(epoch, i, model): called after training batch i when i % ckp_per_iter == 0 (:217-218); first_epoch: the epoch
@@ -479,7 +545,12 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
     mean transported.  sinkhorn_reach_probe_every = k > 0: probe_every's schedule and history entry for a loss in
     DIVERGENCE_LOSSES with a reach (probe_batch_sinkhorn with the run's sinkhorn_reach_scale and sinkhorn_mass); the log line
     carries col_err, self_err, the float64 side's smallest transported and transported_diff.  It is refused without a reach,
-    with any other loss and beside any of the four other probe options (check_sinkhorn_reach_probe_option)."""
+    with any other loss and beside any of the four other probe options (check_sinkhorn_reach_probe_option).  A CALLABLE loss:
+    run_batch's loss of the caller's, every batch its own context; the five probe options above refuse it, naming it.
+    custom_probe_every = k > 0: probe_every's schedule and history entry for a callable loss (probe_batch_custom); the log line
+    also carries seed_rel.  It is refused with a string loss and beside any other probe option (check_custom_probe_option)."""
+    check_custom_probe_option(loss, custom_probe_every, grad_probe_every, probe_every, sinkhorn_probe_every, match_probe_every,
+                              sinkhorn_reach_probe_every)
     check_probe_options(loss, grad_probe_every, probe_every)
     check_sinkhorn_probe_option(loss, sinkhorn_probe_every, grad_probe_every, probe_every)
     check_match_probe_option(loss, match_probe_every, grad_probe_every, probe_every, sinkhorn_probe_every)
@@ -491,7 +562,7 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
         raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
     loss_kind = loss
     every = max(grad_probe_every, probe_every, sinkhorn_probe_every, match_probe_every,
-                sinkhorn_reach_probe_every)                                                 # (at most one of them is given)
+                sinkhorn_reach_probe_every, custom_probe_every)                                               # (at most one of them is given)
     tc = config['train']
     n_rollout = tc['n_rollout']
     assert tc['n_history'] == 1
@@ -504,7 +575,9 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
             meter = AverageMeter()
             for i, data in enumerate(dataloaders[phase]):
                 if every > 0 and phase == 'train' and i % every == 0:
-                    if sinkhorn_reach_probe_every > 0:
+                    if custom_probe_every > 0:
+                        pr = probe_batch_custom(model, data, loss_kind, impulses)
+                    elif sinkhorn_reach_probe_every > 0:
                         pr = probe_batch_sinkhorn(model, data, impulses, transport_eps_scale, transport_iters, sinkhorn_reach_scale,
                                                   sinkhorn_mass)
                     elif sinkhorn_probe_every > 0:
@@ -521,6 +594,8 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
                             line += ', col_err %.3e, self_err %.3e' % (pr['col_err'], pr['self_err'])
                         if sinkhorn_reach_probe_every > 0:
                             line += ', transported %.4f, transported_diff %.3e' % (pr['transported'], pr['transported_diff'])
+                        if custom_probe_every > 0:
+                            line += ', seed_rel %.3e' % pr['seed_rel']
                         if match_probe_every > 0:
                             line += ', flipped %d, cost_gap %.3e' % (pr['flipped'], pr['cost_gap'])
                             line += ', rel_own %.3e' % pr['rel_own'] if 'rel_own' in pr else ''
@@ -569,7 +644,7 @@ def set_seed(seed):
 def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8, n_epoch=None, engine=None, grad_probe_every=0,
          loss=None, impulses=None, probe_every=0, data='particles', target_den_scale=1.0, match_weight=0.5,
          transport_eps_scale=TRANSPORT_EPS_SCALE, transport_iters=TRANSPORT_ITERS, sinkhorn_probe_every=0, match_probe_every=0,
-         sinkhorn_reach_scale=None, sinkhorn_mass='unit', sinkhorn_reach_probe_every=0):
+         sinkhorn_reach_scale=None, sinkhorn_mass='unit', sinkhorn_reach_probe_every=0, custom_probe_every=0):
     """The file-level part of train/train_gnn_dyn.py:train() (:45-130, :196-228): seed, the log directory with config.yaml
     and log.txt, the 'train' / 'valid' ParticleDatasets and their DeviceLoaders, a fresh model (torch.nn.Linear's default
     initialisation) or the resumed checkpoint, net_epoch_%d_iter_%d.pth every ckp_per_iter training batches and
@@ -584,13 +659,16 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
     times the state's density), which implies loss='chamfer' and impulses='actions'; a contradicting value is refused.  loss /
     impulses None: 'mse' / 'data', or what data implies.  loss in MATCH_LOSSES (with match_weight for the mix): as 'chamfer', on
     particles or depth; loss in TRANSPORT_LOSSES or DIVERGENCE_LOSSES (with transport_eps_scale and transport_iters) likewise.  chunk None: the
-    dataset's default (64 samples; 16 for data='depth').  sinkhorn_reach_scale, sinkhorn_mass, sinkhorn_reach_probe_every: train's."""
+    dataset's default (64 samples; 16 for data='depth').  sinkhorn_reach_scale, sinkhorn_mass, sinkhorn_reach_probe_every: train's.
+    A callable loss and custom_probe_every: train's (tracked batches, or with data='depth' the depth batches through the push)."""
     import time
     import yaml
     from . import synthetic, weights
     from .dataset_gnn_dyn import DepthDataset, DeviceLoader, ParticleDataset, UntrackedLoader
     from .gnn_dyn import PropNetDiffDenModel
     loss, impulses = resolve_data_options(data, loss, impulses)
+    check_custom_probe_option(loss, custom_probe_every, grad_probe_every, probe_every, sinkhorn_probe_every, match_probe_every,
+                              sinkhorn_reach_probe_every)
     check_probe_options(loss, grad_probe_every, probe_every)
     check_sinkhorn_probe_option(loss, sinkhorn_probe_every, grad_probe_every, probe_every)
     check_match_probe_option(loss, match_probe_every, grad_probe_every, probe_every, sinkhorn_probe_every)
@@ -649,12 +727,26 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
                        match_weight=match_weight, transport_eps_scale=transport_eps_scale, transport_iters=transport_iters,
                        sinkhorn_probe_every=sinkhorn_probe_every, match_probe_every=match_probe_every,
                        sinkhorn_reach_scale=sinkhorn_reach_scale, sinkhorn_mass=sinkhorn_mass,
-                       sinkhorn_reach_probe_every=sinkhorn_reach_probe_every)
+                       sinkhorn_reach_probe_every=sinkhorn_reach_probe_every, custom_probe_every=custom_probe_every)
         for epoch, phase, rmse in result['history']:
             if phase == 'grad_probe':                   # logged when it was taken
                 continue
             log('%s [%d] Loss: %.6f' % (phase, epoch, rmse))
     return result, train_dir
+
+
+def load_loss_fn(spec):
+    """--loss-fn's 'package.module:attribute' -> the callable it names (importlib); anything else is refused"""
+    import importlib
+    module, sep, attribute = str(spec).partition(':')
+    if not sep or not module or not attribute:
+        raise ValueError('loss_fn must be given as package.module:attribute, got %r' % (spec,))
+    fn = importlib.import_module(module)
+    for part in attribute.split('.'):
+        fn = getattr(fn, part)
+    if not callable(fn):
+        raise ValueError('loss_fn %r is not callable (%r)' % (spec, type(fn).__name__))
+    return fn
 
 
 def _cli(argv=None):
@@ -697,6 +789,13 @@ def _cli(argv=None):
                          'transport: on the entropy-regularised transport distance to them (--transport-eps-scale, --transport-iters); '
                          'sinkhorn: on the Sinkhorn divergence to them, the transport distance without its pull inward (the same two '
                          'options): the one for depth data')
+    ap.add_argument('--loss-fn', default=None, metavar='package.module:attribute',
+                    help='train on a loss of your own instead of --loss: a function loss(pred, context) -> (value, gradient) as in '
+                         'dyn_res_pile_manip_amd.losses (e.g. dyn_res_pile_manip_amd.losses:pseudo_huber_loss); context is the batch')
+    ap.add_argument('--custom-probe-every', type=int, default=0,
+                    help='--loss-fn: hold every k-th training batch\'s gradients against the float64 evaluation of the same loss before '
+                         'its update; the log line carries seed_rel, the loss\'s own sensitivity to the fp32 prediction (not with the '
+                         'five options above)')
     ap.add_argument('--match-weight', type=float, default=0.5,
                     help='--loss chamfer+match: (1 - w) Chamfer + w matching, w in (0, 1)')
     ap.add_argument('--transport-eps-scale', type=float, default=TRANSPORT_EPS_SCALE,
@@ -713,7 +812,13 @@ def _cli(argv=None):
     ap.add_argument('--impulses', choices=IMPULSES, default=None,
                     help='(default data) actions: compute every step\'s impulse from the recorded push on the state the model predicted')
     a = ap.parse_args(argv)
+    if a.loss is not None and a.loss_fn is not None:
+        ap.error('give --loss or --loss-fn, not both')
     try:
+        if a.loss_fn is not None:
+            a.loss = load_loss_fn(a.loss_fn)
+        check_custom_probe_option(a.loss, a.custom_probe_every, a.grad_probe_every, a.probe_every, a.sinkhorn_probe_every,
+                                  a.match_probe_every, a.sinkhorn_reach_probe_every)
         check_loss(resolve_data_options(a.data, a.loss, a.impulses)[0], a.match_weight, a.transport_eps_scale, a.transport_iters)
         check_sinkhorn_options(resolve_data_options(a.data, a.loss, a.impulses)[0], a.sinkhorn_reach_scale, a.sinkhorn_mass,
                                a.sinkhorn_probe_every, a.transport_eps_scale)
@@ -736,7 +841,7 @@ def _cli(argv=None):
                      transport_eps_scale=a.transport_eps_scale, transport_iters=a.transport_iters,
                      sinkhorn_probe_every=a.sinkhorn_probe_every, match_probe_every=a.match_probe_every,
                      sinkhorn_reach_scale=a.sinkhorn_reach_scale, sinkhorn_mass=a.sinkhorn_mass,
-                     sinkhorn_reach_probe_every=a.sinkhorn_reach_probe_every)
+                     sinkhorn_reach_probe_every=a.sinkhorn_reach_probe_every, custom_probe_every=a.custom_probe_every)
     print('best valid loss %.6f, checkpoints in %s' % (np.sqrt(result['best_valid_loss']), d))
 
 

@@ -611,8 +611,11 @@ int drp_debug_stall(drp_ctx* ctx, int ms);
  * "pd_nfg" ([B] int32), "pd_chosen" ([B][4097] int32), "pd_recenter" ([B][n_max][3] float64), "pd_nearest" ([B][n_max]
  * int32); the last drp_ptcl_dataset_frames's "pdf_nfg" ([B][T] int32), "pdf_chosen" ([B][T][4097] int32), "pdf_recenter"
  * ([B][T][n_max][3] float64).  The two dataset calls share their buffers: a "pd_*" tap after a frames call, or a "pdf_*" tap
- * after a batch call, is DRP_ESTATE (not populated), never the other call's bytes. (byte sizes: the returned value). returns
- * bytes. */
+ * after a batch call, is DRP_ESTATE (not populated), never the other call's bytes.  The last trainer call's "train_states"
+ * ([B][H][N][3] float32, the predicted states), "train_sdelta" ([H][B][N][3], the impulses) and "train_seed" ([H][B][N][3]
+ * float32: d loss / d s_pred as the call's loss kernel left it -- the loss's own seed after a call with DRP_TRAIN_EVAL, which runs
+ * no reverse pass over it; a reverse pass adds the later steps' shares to every slice but the last).  (byte sizes: the returned
+ * value). returns bytes. */
 long drp_debug_fetch(drp_ctx* ctx, const char* name, void* out, size_t out_bytes);
 
 /* ---- the float64 yardstick: one step evaluated in double on the device, and a probe that holds an engine against it ----
@@ -1056,6 +1059,52 @@ int drp_train_grad_f64_match(drp_ctx* ctx, const float* states, const float* sta
                              double* loss_terms_out, double* grad_out, double* grad_state_out,
                              int32_t* match_out /*[H][B][N], nullable*/, double* cost_out /*[H][B][2], nullable*/,
                              double* margin_out /*[H][B], nullable*/);
+
+/* ---- training on a loss of the CALLER's: every step's prediction out, d loss / d s_pred in -------------------------------------
+ * In drp_train_step every loss kernel does three things: it writes d loss / d s_pred_t of every step, the loss terms, and it
+ * zero-fills the gradient blob.  These two calls open that seam, statelessly: the first returns what the training forward
+ * predicts, the second runs the same forward again and seeds the reverse pass with an array of the caller's.  The forward is
+ * deterministic, so the second call's predictions are the bits the first returned and the seed is the gradient at the right
+ * point; the price is one forward more per update.  The batch arguments and their refusals are drp_train_step_loss's: exactly one
+ * of states_delta and actions, actions needs a camera and refuses a push of zero length.
+ *
+ * drp_train_predict: the forward EXACTLY as drp_train_step_seeded (and drp_train_step with DRP_TRAIN_GRAD) runs it -- the tape
+ * engine of the same selection, the tape written, zero-padded rows joining the graph -- and states_pred_out [B][n_rollout][N][3]:
+ * on rows n < particle_nums[b] the bits of that call's own forward.  (The DRP_TRAIN_EVAL forward runs without the tape and is
+ * promised nothing here.)  Rows n >= particle_nums[b] come back as the forward leaves them and are no part of the contract.
+ * Needs drp_train_begin (n_rollout is its); changes no weight, no Adam moment and no iteration count.
+ *
+ * drp_train_step_seeded: seed [B][n_rollout][N][3], seed[b, t, n, :] = d loss / d s_pred_t[b, n], COMPLETE -- the library applies
+ * no 1 / (n_rollout B) and no 1 / (3 n_b).  Rows n >= particle_nums[b] of the seed are never read as numbers: the reverse pass
+ * sees +0.0 there whatever they hold.  Everything behind the seed -- the reverse pass, the push's position share with actions, the
+ * weight gradients, Adam, re-packing, the one wait -- is drp_train_step's own code; fed drp_train_step's own seed, 2 (s_pred -
+ * s_nxt) / (3 n_b n_rollout B) formed with its fp32 operations from drp_train_predict's output, grad_out has the bits of
+ * drp_train_step's.  mode DRP_TRAIN_GRAD or DRP_TRAIN_UPDATE.  There is no loss argument: the value is the caller's.  No dispatch
+ * variant of its own.  Refusals: DRP_ESTATE without drp_train_begin (or, with actions, without a camera); DRP_EINVAL for a null
+ * argument, both or neither impulse source, a count outside 1..N, a value on a real row of the seed that is infinite or no number
+ * (the message names sample, step and row), DRP_TRAIN_EVAL (the forward alone is drp_train_predict).  A refused call leaves the
+ * context as it was. */
+int drp_train_predict(drp_ctx* ctx, const float* states, const float* states_delta /*[B][H][N][3] or NULL*/,
+                      const float* actions /*[B][H][4] or NULL*/, const float* attrs, const int32_t* particle_nums,
+                      const float* particle_dens, int B, int N, float* states_pred_out /*[B][H][N][3]*/);
+int drp_train_step_seeded(drp_ctx* ctx, const float* states, const float* states_delta /*[B][H][N][3] or NULL*/,
+                          const float* actions /*[B][H][4] or NULL*/, const float* attrs, const int32_t* particle_nums,
+                          const float* particle_dens, int B, int N, const float* seed /*[B][H][N][3]*/, int mode,
+                          float* grad_out /*nullable*/);
+/* The same pair in float64, on drp_train_grad_f64's tape and reverse pass: the yardstick of the two calls above.  The forward of
+ * both is drp_train_grad_f64's; states_pred_out and seed are doubles [B][n_rollout][N][3]; grad_out [38 403] (nullable) and
+ * grad_state_out [B][n_rollout][N][3] (nullable) as drp_train_grad_f64's.  The seed is sliced per chunk of samples; the outputs are
+ * the same bits from run to run and under any workspace cap.  The one-shot contract of drp_train_grad_f64: no drp_train_begin
+ * needed, buffers of their own, the engine, the sessions, the Adam state, the dispatch marks and the float64 taps untouched.
+ * Refusals (DRP_EINVAL): those of drp_train_grad_f64_untracked's batch arguments, a null seed or output, a value on a real row of
+ * the seed that is infinite or no number. */
+int drp_train_predict_f64(drp_ctx* ctx, const float* states, const float* states_delta /*[B][H][N][3] or NULL*/,
+                          const float* actions /*[B][H][4] or NULL*/, const float* attrs, const int32_t* particle_nums,
+                          const float* particle_dens, int B, int N, int n_rollout, double* states_pred_out /*[B][H][N][3]*/);
+int drp_train_grad_f64_seeded(drp_ctx* ctx, const float* states, const float* states_delta /*[B][H][N][3] or NULL*/,
+                              const float* actions /*[B][H][4] or NULL*/, const float* attrs, const int32_t* particle_nums,
+                              const float* particle_dens, int B, int N, int n_rollout, const double* seed /*[B][H][N][3]*/,
+                              double* grad_out, double* grad_state_out);
 
 #ifdef __cplusplus
 }

@@ -26,9 +26,14 @@
 // check of a reach and a target mass (check_reach) at the edges of its ranges.  Its float64 yardstick: rho [B] | mass_q [H][B]
 // (doubles) behind eps in the float64 upload (tr64_layout with `reach`), and drp_cloud_divergence_unbalanced_f64's buffer
 // (divergence64_layout with `reach`: rho | mass_q between eps and q, transported behind the scratch), nothing else moved
-// relative to one another.  No device is touched.
+// relative to one another.  The seeded step: the caller's d loss / d s_pred [B][H][N][3] behind a training batch (tr_layout with
+// `seed`: floats, 16-byte aligned) and behind the float64 upload (tr64_layout with `seed`: doubles on a multiple of four words),
+// staged as train_stage_batch and train_grad_f64_body stage them and read back as kt_seed_given and k64_seed_given address them,
+// nothing ahead of either moved and a call without a seed taking no byte for it; and the scan that refuses a real row of a seed
+// that is no number (first_bad_seed) on arrays of exactly [B][H][N][3].  No device is touched.
 //
 //   train_host_check layout64 B H N M actions     prints tr64_layout's eight fields (4-byte words) and exits
+//   train_host_check layout B H N M actions eps reach seed     prints tr_layout's twelve fields (bytes) and exits
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -528,6 +533,70 @@ static void stage_eps(int B, int H, int N, int M, bool actions) {
     std::free(pin);
 }
 
+// drp_train_step_seeded's batch: the seed [B][H][N][3] (floats) behind everything else, the other blocks where they were, with every
+// combination of the older blocks; drp_train_grad_f64_seeded's upload: the same in doubles behind the float64 batch
+static void stage_seed(int B, int H, int N, int M, bool actions) {
+    const size_t n_seed = (size_t)B * H * N * 3;
+    for (int eps = 0; eps < 2; ++eps)
+        for (int reach = 0; reach < 2; ++reach) {
+            const TrArena lay = tr_layout(B, H, N, M, actions, eps != 0, reach != 0, true), plain = tr_layout(B, H, N, M, actions, eps != 0, reach != 0);
+            EXPECT(lay.states == plain.states && lay.sdelta == plain.sdelta && lay.attrs == plain.attrs && lay.dens == plain.dens &&
+                   lay.nums == plain.nums && lay.targets == plain.targets && lay.tnums == plain.tnums && lay.eps == plain.eps &&
+                   lay.rho == plain.rho && lay.mass_q == plain.mass_q);
+            EXPECT(plain.seed == 0 && lay.seed == plain.bytes && lay.seed % 16 == 0 && lay.bytes % 16 == 0);
+            EXPECT(lay.seed + n_seed * 4 <= lay.bytes && lay.bytes - (lay.seed + n_seed * 4) < 16);
+        }
+    const TrArena lay = tr_layout(B, H, N, M, actions, false, false, true);
+    std::vector<float> seed(n_seed);
+    for (size_t e = 0; e < n_seed; ++e) seed[e] = (float)(e % 1021);
+    char* pin = static_cast<char*>(std::malloc(lay.bytes));
+    std::memset(pin, 0xff, lay.bytes);
+    std::memcpy(pin + lay.seed, seed.data(), n_seed * sizeof(float));           // train_stage_batch's copy
+    // as kt_seed_given addresses it: sample b, step t at ((b H + t) N) 3 floats, the last element of the last slice included
+    const float* as_kernel = reinterpret_cast<const float*>(pin + lay.seed);
+    const size_t last = ((size_t)(B - 1) * H + (H - 1)) * N * 3 + (size_t)N * 3 - 1;
+    EXPECT(last == n_seed - 1 && as_kernel[0] == 0.0f && as_kernel[last] == (float)(last % 1021));
+    if ((N * 3) % 4 == 0) EXPECT((lay.seed + ((size_t)(B - 1) * H + (H - 1)) * N * 3 * 4) % 16 == 0);      // its float4 path's premise
+    std::free(pin);
+
+    const Tr64Arena l64 = tr64_layout(B, H, N, M, actions, false, false, false, true), p64 = tr64_layout(B, H, N, M, actions);
+    EXPECT(l64.states == p64.states && l64.sdelta == p64.sdelta && l64.attr == p64.attr && l64.dens == p64.dens && l64.nums == p64.nums &&
+           l64.targets == p64.targets && l64.tnums == p64.tnums);
+    EXPECT(p64.seed == 0 && l64.seed % 4 == 0 && l64.seed >= p64.words && l64.seed - p64.words < 4 && l64.words == l64.seed + 2 * n_seed);
+    std::vector<double> seed64(n_seed, 0.5);
+    seed64[n_seed - 1] = 0.25;
+    float* host = static_cast<float*>(std::malloc(l64.words * sizeof(float)));
+    std::memset(host, 0xff, l64.words * sizeof(float));
+    std::memcpy(host + l64.seed, seed64.data(), n_seed * sizeof(double));       // train_grad_f64_body's copy
+    EXPECT(reinterpret_cast<uintptr_t>(host + l64.seed) % 16 == 0);              // (malloc aligns to 16: the device buffer to 256)
+    const double* k64 = reinterpret_cast<const double*>(host + l64.seed);        // as k64_seed_given addresses it
+    EXPECT(k64[0] == 0.5 && k64[last] == 0.25);
+    std::free(host);
+}
+// the scan of a seed's real rows: every one of them read, in every step, and nothing of the padding
+template <typename T>
+static void check_seeds() {
+    const T inf = std::numeric_limits<T>::infinity(), nan = std::numeric_limits<T>::quiet_NaN();
+    const int B = 2, H = 3, N = 4;
+    const int32_t counts[2] = {2, 4};
+    const size_t n = (size_t)B * H * N * 3;
+    T* x = static_cast<T*>(std::malloc(n * sizeof(T)));                           // exactly [B][H][N][3]
+    for (size_t e = 0; e < n; ++e) x[e] = (T)0.125 * (T)e;
+    EXPECT(first_bad_seed(x, counts, B, H, N) == -1);
+    for (int t = 0; t < H; ++t) x[((size_t)(0 * H + t) * N + 2) * 3 + 1] = nan;       // sample 0's padding, every step
+    x[((size_t)(0 * H + 2) * N + 3) * 3 + 2] = inf;
+    EXPECT(first_bad_seed(x, counts, B, H, N) == -1);
+    x[n - 1] = inf;                                                                 // the last coordinate of the last real row
+    EXPECT(first_bad_seed(x, counts, B, H, N) == ((long)1 * H + 2) * N + 3);
+    x[((size_t)(1 * H + 0) * N + 0) * 3 + 0] = nan;                                 // an earlier one wins
+    EXPECT(first_bad_seed(x, counts, B, H, N) == ((long)1 * H + 0) * N + 0);
+    x[((size_t)(0 * H + 1) * N + 1) * 3 + 2] = -inf;
+    EXPECT(first_bad_seed(x, counts, B, H, N) == ((long)0 * H + 1) * N + 1);
+    const int32_t over[2] = {9, 4};                                                 // a count beyond N is read up to N
+    EXPECT(first_bad_seed(x, over, B, H, N) == ((long)0 * H + 0) * N + 2);
+    std::free(x);
+}
+
 // drp_cloud_chamfer's and drp_cloud_chamfer_f64's layouts against their offset chains written out block by block (the yardstick
 // of cloud_layout: the offsets a call's kernel and copies have always used), then staged like the matching's
 static void stage_chamfer(int B, int N, int M) {
@@ -562,6 +631,13 @@ int main(int argc, char** argv) {
         std::printf("%zu %zu %zu %zu %zu %zu %zu %zu\n", a.states, a.sdelta, a.attr, a.dens, a.nums, a.targets, a.tnums, a.words);
         return 0;
     }
+    if (argc == 10 && std::strcmp(argv[1], "layout") == 0) {
+        const TrArena a = tr_layout(std::atoi(argv[2]), std::atoi(argv[3]), std::atoi(argv[4]), std::atoi(argv[5]), std::atoi(argv[6]) != 0,
+                                    std::atoi(argv[7]) != 0, std::atoi(argv[8]) != 0, std::atoi(argv[9]) != 0);
+        std::printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", a.states, a.sdelta, a.attrs, a.dens, a.nums, a.targets, a.tnums,
+                    a.bytes, a.eps, a.rho, a.mass_q, a.seed);
+        return 0;
+    }
     // odd sizes (no block a multiple of 16 bytes), one sample, the reference's batch, a large one
     const int shapes[][4] = {{1, 1, 1, 0}, {1, 1, 5, 3}, {3, 3, 24, 0}, {3, 3, 23, 17}, {2, 5, 11, 0}, {4, 5, 300, 0}, {4, 5, 300, 300},
                              {7, 2, 301, 299}, {32, 5, 300, 0}, {2, 64, 9, 1}};
@@ -569,6 +645,7 @@ int main(int argc, char** argv) {
         for (int actions = 0; actions < 2; ++actions) {
             stage(s[0], s[1], s[2], s[3], actions != 0);
             stage64(s[0], s[1], s[2], s[3], actions != 0);
+            stage_seed(s[0], s[1], s[2], s[3], actions != 0);
             if (s[3] > 0) stage64_eps(s[0], s[1], s[2], s[3], actions != 0);
             if (s[3] > 0) stage64_match(s[0], s[1], s[2], s[3], actions != 0);
             if (s[3] > 0) stage64_reach(s[0], s[1], s[2], s[3], actions != 0);
@@ -595,6 +672,8 @@ int main(int argc, char** argv) {
                 stage_div_unbalanced_train(s[0], s[1], s[2], s[3], actions != 0);
             }
     check_reaches();
+    check_seeds<float>();
+    check_seeds<double>();
     {
         // the regularisation strengths: every one read, none beyond the B-th
         const double inf64 = std::numeric_limits<double>::infinity(), nan64 = std::numeric_limits<double>::quiet_NaN();
