@@ -97,11 +97,10 @@ int drp_train_grad_f64_divergence(drp_ctx* c, const float* states, const float* 
                                   double* loss_out, double* loss_terms_out, double* grad_out, double* grad_state_out,
                                   double* col_err_out, double* self_err_out) {
     if (!c) return DRP_EINVAL;
-    if ((states_delta != nullptr) == (actions != nullptr))
-        return fail(c, DRP_EINVAL, "exactly one of states_delta and actions must be given");
-    TrLoss lk = TrLoss::against(TR_LOSS_DIVERGENCE, targets, target_nums, M);
-    lk.eps = eps; lk.iters = iters; lk.col_err_out = col_err_out; lk.self_err_out = self_err_out;
-    return train_grad_f64_body(c, states, actions != nullptr ? actions : states_delta, actions != nullptr, attrs, particle_nums,
+    ImpulseSource src;
+    CHK(impulse_source(c, states_delta, actions, src));
+    TrLoss lk = TrLoss::sinkhorn(TR_LOSS_DIVERGENCE, targets, target_nums, M, eps, iters, col_err_out, self_err_out);
+    return train_grad_f64_body(c, states, src.impulses, src.by_actions, attrs, particle_nums,
                                particle_dens, B, N, n_rollout, lk, loss_out, loss_terms_out, grad_out, grad_state_out);
 }
 
@@ -113,12 +112,11 @@ int drp_train_grad_f64_divergence_unbalanced(drp_ctx* c, const float* states, co
                                              double* grad_out, double* grad_state_out, double* col_err_out, double* self_err_out,
                                              double* transported_out) {
     if (!c) return DRP_EINVAL;
-    if ((states_delta != nullptr) == (actions != nullptr))
-        return fail(c, DRP_EINVAL, "exactly one of states_delta and actions must be given");
+    ImpulseSource src;
+    CHK(impulse_source(c, states_delta, actions, src));
     if (!rho || !mass_q) return fail(c, DRP_EINVAL, "null argument");
-    TrLoss lk = TrLoss::against(TR_LOSS_DIVERGENCE, targets, target_nums, M);
-    lk.eps = eps; lk.iters = iters; lk.col_err_out = col_err_out; lk.self_err_out = self_err_out;
+    TrLoss lk = TrLoss::sinkhorn(TR_LOSS_DIVERGENCE, targets, target_nums, M, eps, iters, col_err_out, self_err_out);
     lk.rho = rho; lk.mass_q = mass_q; lk.transported_out = transported_out;
-    return train_grad_f64_body(c, states, actions != nullptr ? actions : states_delta, actions != nullptr, attrs, particle_nums,
+    return train_grad_f64_body(c, states, src.impulses, src.by_actions, attrs, particle_nums,
                                particle_dens, B, N, n_rollout, lk, loss_out, loss_terms_out, grad_out, grad_state_out);
 }

@@ -607,10 +607,10 @@ int drp_train_predict_f64(drp_ctx* c, const float* states, const float* states_d
                           const int32_t* particle_nums, const float* particle_dens, int B, int N, int n_rollout,
                           double* states_pred_out) {
     if (!c) return DRP_EINVAL;
-    if ((states_delta != nullptr) == (actions != nullptr))
-        return fail(c, DRP_EINVAL, "exactly one of states_delta and actions must be given");
+    ImpulseSource src;
+    CHK(impulse_source(c, states_delta, actions, src));
     if (!states_pred_out) return fail(c, DRP_EINVAL, "null argument");
-    return train_grad_f64_body(c, states, actions != nullptr ? actions : states_delta, actions != nullptr, attrs, particle_nums,
+    return train_grad_f64_body(c, states, src.impulses, src.by_actions, attrs, particle_nums,
                                particle_dens, B, N, n_rollout, TrLoss{}, nullptr, nullptr, nullptr, nullptr, states_pred_out);
 }
 
@@ -618,11 +618,11 @@ int drp_train_grad_f64_seeded(drp_ctx* c, const float* states, const float* stat
                               const int32_t* particle_nums, const float* particle_dens, int B, int N, int n_rollout,
                               const double* seed, double* grad_out, double* grad_state_out) {
     if (!c) return DRP_EINVAL;
-    if ((states_delta != nullptr) == (actions != nullptr))
-        return fail(c, DRP_EINVAL, "exactly one of states_delta and actions must be given");
+    ImpulseSource src;
+    CHK(impulse_source(c, states_delta, actions, src));
     TrLoss lk;
     lk.kind = TR_LOSS_GIVEN; lk.seed64 = seed;
-    return train_grad_f64_body(c, states, actions != nullptr ? actions : states_delta, actions != nullptr, attrs, particle_nums,
+    return train_grad_f64_body(c, states, src.impulses, src.by_actions, attrs, particle_nums,
                                particle_dens, B, N, n_rollout, lk, nullptr, nullptr, grad_out, grad_state_out);
 }
 
@@ -638,10 +638,10 @@ int drp_train_grad_f64_untracked(drp_ctx* c, const float* states, const float* s
                                  int n_rollout, const float* targets, const int32_t* target_nums, int M, double* loss_out,
                                  double* loss_terms_out, double* grad_out, double* grad_state_out, double* margin_out) {
     if (!c) return DRP_EINVAL;
-    if ((states_delta != nullptr) == (actions != nullptr))
-        return fail(c, DRP_EINVAL, "exactly one of states_delta and actions must be given");
+    ImpulseSource src;
+    CHK(impulse_source(c, states_delta, actions, src));
     TrLoss lk = TrLoss::against(TR_LOSS_CHAMFER, targets, target_nums, M);
     lk.margin_out = margin_out;
-    return train_grad_f64_body(c, states, actions != nullptr ? actions : states_delta, actions != nullptr, attrs, particle_nums,
+    return train_grad_f64_body(c, states, src.impulses, src.by_actions, attrs, particle_nums,
                                particle_dens, B, N, n_rollout, lk, loss_out, loss_terms_out, grad_out, grad_state_out);
 }

@@ -68,11 +68,11 @@ int drp_train_grad_f64_match(drp_ctx* c, const float* states, const float* state
     if (!c) return DRP_EINVAL;
     if (loss_kind != DRP_LOSS_MATCH && loss_kind != DRP_LOSS_CHAMFER_MATCH)
         return fail(c, DRP_EINVAL, "bad loss_kind=%d (the matching kinds: %d, %d)", loss_kind, DRP_LOSS_MATCH, DRP_LOSS_CHAMFER_MATCH);
-    if ((states_delta != nullptr) == (actions != nullptr))
-        return fail(c, DRP_EINVAL, "exactly one of states_delta and actions must be given");
+    ImpulseSource src;
+    CHK(impulse_source(c, states_delta, actions, src));
     TrLoss lk = TrLoss::against(loss_kind, targets, target_nums, M);
     lk.match_weight = match_weight; lk.match_in = match_in; lk.match_out = match_out; lk.cost_out = cost_out;
     lk.margin_out = margin_out;
-    return train_grad_f64_body(c, states, actions != nullptr ? actions : states_delta, actions != nullptr, attrs, particle_nums,
+    return train_grad_f64_body(c, states, src.impulses, src.by_actions, attrs, particle_nums,
                                particle_dens, B, N, n_rollout, lk, loss_out, loss_terms_out, grad_out, grad_state_out);
 }

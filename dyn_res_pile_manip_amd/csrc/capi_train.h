@@ -51,7 +51,23 @@ struct TrLoss {
         lk.kind = kind; lk.targets = targets; lk.target_nums = target_nums; lk.M = M;
         return lk;
     }
+    // the transport loss and the divergence: `against` with the sweeps' arguments and the certificates' outputs (nullable)
+    static TrLoss sinkhorn(int kind, const float* targets, const int32_t* target_nums, int M, const double* eps, int iters,
+                           double* col_err_out, double* self_err_out = nullptr) {
+        TrLoss lk = against(kind, targets, target_nums, M);
+        lk.eps = eps; lk.iters = iters; lk.col_err_out = col_err_out; lk.self_err_out = self_err_out;
+        return lk;
+    }
 };
+// The impulse source of an entry point that takes both pointers: exactly one of states_delta and actions is given
+struct ImpulseSource { const float* impulses; bool by_actions; };
+int impulse_source(drp_ctx* c, const float* states_delta, const float* actions, ImpulseSource& src) {
+    if ((states_delta != nullptr) == (actions != nullptr))
+        return fail(c, DRP_EINVAL, "exactly one of states_delta and actions must be given");
+    src.by_actions = actions != nullptr;
+    src.impulses = src.by_actions ? actions : states_delta;
+    return DRP_OK;
+}
 // ---- the checks both trainers make of a batch and its loss; each body calls them where its own order of refusals has them ----
 int check_particle_nums(drp_ctx* c, const int32_t* particle_nums, int B, int N) {
     for (int b = 0; b < B; ++b)
@@ -703,14 +719,13 @@ int drp_train_step_loss(drp_ctx* c, const float* states, const float* states_del
                         const int32_t* target_nums, int M, int loss_kind, double match_weight, int mode, double* loss_out,
                         float* grad_out, int32_t* match_out) {
     if (!c) return DRP_EINVAL;
-    if ((states_delta != nullptr) == (actions != nullptr))
-        return fail(c, DRP_EINVAL, "exactly one of states_delta and actions must be given");
+    ImpulseSource src;
+    CHK(impulse_source(c, states_delta, actions, src));
     if (loss_kind != DRP_LOSS_CHAMFER && loss_kind != DRP_LOSS_MATCH && loss_kind != DRP_LOSS_CHAMFER_MATCH)
         return fail(c, DRP_EINVAL, "bad loss_kind %d", loss_kind);
     TrLoss lk = TrLoss::against(loss_kind, targets, target_nums, M);
     lk.match_weight = match_weight; lk.match_out = match_out;
-    const bool by_actions = actions != nullptr;
-    return train_step_body(c, states, by_actions ? actions : states_delta, by_actions, attrs, particle_nums, particle_dens, B, N, lk,
+    return train_step_body(c, states, src.impulses, src.by_actions, attrs, particle_nums, particle_dens, B, N, lk,
                            mode, loss_out, grad_out);
 }
 
@@ -718,11 +733,10 @@ int drp_train_step_loss(drp_ctx* c, const float* states, const float* states_del
 int drp_train_predict(drp_ctx* c, const float* states, const float* states_delta, const float* actions, const float* attrs,
                       const int32_t* particle_nums, const float* particle_dens, int B, int N, float* states_pred_out) {
     if (!c) return DRP_EINVAL;
-    if ((states_delta != nullptr) == (actions != nullptr))
-        return fail(c, DRP_EINVAL, "exactly one of states_delta and actions must be given");
+    ImpulseSource src;
+    CHK(impulse_source(c, states_delta, actions, src));
     if (!states_pred_out) return fail(c, DRP_EINVAL, "null argument");
-    const bool by_actions = actions != nullptr;
-    return train_step_body(c, states, by_actions ? actions : states_delta, by_actions, attrs, particle_nums, particle_dens, B, N,
+    return train_step_body(c, states, src.impulses, src.by_actions, attrs, particle_nums, particle_dens, B, N,
                            TrLoss{}, DRP_TRAIN_GRAD, nullptr, nullptr, states_pred_out);
 }
 
@@ -732,12 +746,11 @@ int drp_train_step_seeded(drp_ctx* c, const float* states, const float* states_d
                           const int32_t* particle_nums, const float* particle_dens, int B, int N, const float* seed, int mode,
                           float* grad_out) {
     if (!c) return DRP_EINVAL;
-    if ((states_delta != nullptr) == (actions != nullptr))
-        return fail(c, DRP_EINVAL, "exactly one of states_delta and actions must be given");
+    ImpulseSource src;
+    CHK(impulse_source(c, states_delta, actions, src));
     TrLoss lk;
     lk.kind = TR_LOSS_GIVEN; lk.seed = seed;
-    const bool by_actions = actions != nullptr;
-    return train_step_body(c, states, by_actions ? actions : states_delta, by_actions, attrs, particle_nums, particle_dens, B, N, lk,
+    return train_step_body(c, states, src.impulses, src.by_actions, attrs, particle_nums, particle_dens, B, N, lk,
                            mode, nullptr, grad_out);
 }
 

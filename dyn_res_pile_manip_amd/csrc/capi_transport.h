@@ -33,11 +33,9 @@ int drp_train_step_transport(drp_ctx* c, const float* states, const float* state
                              const int32_t* target_nums, int M, const double* eps, int iters, int mode, double* loss_out,
                              float* grad_out, double* col_err_out) {
     if (!c) return DRP_EINVAL;
-    if ((states_delta != nullptr) == (actions != nullptr))
-        return fail(c, DRP_EINVAL, "exactly one of states_delta and actions must be given");
-    TrLoss lk = TrLoss::against(TR_LOSS_TRANSPORT, targets, target_nums, M);
-    lk.eps = eps; lk.iters = iters; lk.col_err_out = col_err_out;
-    const bool by_actions = actions != nullptr;
-    return train_step_body(c, states, by_actions ? actions : states_delta, by_actions, attrs, particle_nums, particle_dens, B, N, lk,
+    ImpulseSource src;
+    CHK(impulse_source(c, states_delta, actions, src));
+    const TrLoss lk = TrLoss::sinkhorn(TR_LOSS_TRANSPORT, targets, target_nums, M, eps, iters, col_err_out);
+    return train_step_body(c, states, src.impulses, src.by_actions, attrs, particle_nums, particle_dens, B, N, lk,
                            mode, loss_out, grad_out);
 }

@@ -144,35 +144,29 @@ inline CloudLayout transport_layout(int B, int N, int M) {
 }
 // drp_cloud_divergence: terms [B] (doubles) | gradient [B][N][3] | duals [B][2N + 2M] | col_err [B] | self_err [B][2] (doubles) come
 // back; behind them, never read back: eps [B] (doubles, UP behind cloud_begin's copy) | the kernels' scratch: the value sums
-// [3][B] | the gradient sums [2][B][N][3] (doubles)
-struct DivLayout { CloudLayout cloud; size_t eps, vals, gsum; };
-inline DivLayout divergence_layout(int B, int N, int M) {
+// [3][B] | the gradient sums [2][B][N][3] (doubles).  drp_cloud_divergence_unbalanced (`reach`): rho [B] | mass_q [B] (doubles) lie
+// side by side with eps -- the three go UP in one copy -- ahead of the scratch, and transported [B] (doubles, comes back by a copy
+// of its own: a sixth output) behind it; the five blocks that come back and eps stay where they are without it
+struct DivLayout { CloudLayout cloud; size_t eps, rho, mass_q, vals, gsum, transported; };
+inline DivLayout divergence_layout(int B, int N, int M, bool reach = false) {
     auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t bn = (size_t)B * N, bm = (size_t)B * M;
+    const size_t bn = (size_t)B * N, bm = (size_t)B * M, b8 = (size_t)B * sizeof(double);
     DivLayout a{};
-    a.cloud = cloud_layout(B, N, M, {(size_t)B * sizeof(double), bn * 3 * sizeof(float), 2 * (bn + bm) * sizeof(double),
-                                     (size_t)B * sizeof(double), (size_t)B * 2 * sizeof(double)});
+    a.cloud = cloud_layout(B, N, M, {b8, bn * 3 * sizeof(float), 2 * (bn + bm) * sizeof(double), b8, 2 * b8});
     a.eps = a.cloud.bytes;
-    a.vals = up(a.eps + (size_t)B * sizeof(double));
-    a.gsum = up(a.vals + (size_t)3 * B * sizeof(double));
+    size_t end = a.eps + b8;
+    if (reach) {
+        a.rho = end;
+        a.mass_q = a.rho + b8;
+        end = a.mass_q + b8;
+    }
+    a.vals = up(end);
+    a.gsum = up(a.vals + 3 * b8);
     a.cloud.bytes = up(a.gsum + 2 * bn * 3 * sizeof(double));
-    return a;
-}
-// drp_cloud_divergence_unbalanced: divergence_layout's blocks; behind them eps [B] | rho [B] | mass_q [B] (doubles, UP in one copy
-// behind cloud_begin's) | the same scratch | transported [B] (doubles, comes back by a copy of its own: a sixth output)
-struct DivUnbalancedLayout { CloudLayout cloud; size_t eps, rho, mass_q, vals, gsum, transported; };
-inline DivUnbalancedLayout divergence_unbalanced_layout(int B, int N, int M) {
-    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t bn = (size_t)B * N;
-    DivUnbalancedLayout a{};
-    a.cloud = divergence_layout(B, N, M).cloud;
-    a.eps = divergence_layout(B, N, M).eps;
-    a.rho = a.eps + (size_t)B * sizeof(double);
-    a.mass_q = a.rho + (size_t)B * sizeof(double);
-    a.vals = up(a.mass_q + (size_t)B * sizeof(double));
-    a.gsum = up(a.vals + (size_t)3 * B * sizeof(double));
-    a.transported = up(a.gsum + 2 * bn * 3 * sizeof(double));
-    a.cloud.bytes = up(a.transported + (size_t)B * sizeof(double));
+    if (reach) {
+        a.transported = a.cloud.bytes;
+        a.cloud.bytes = up(a.transported + b8);
+    }
     return a;
 }
 // drp_cloud_divergence_f64: p is the caller's doubles, so the buffer is its own (not cloud_begin's).  Up, in one copy: p [B][N][3]

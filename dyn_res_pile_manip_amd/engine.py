@@ -36,6 +36,55 @@ def _opt(f, a):
     return None if a is None else f(a)
 
 
+_POINTERS = {np.dtype(np.float32): _fp, np.dtype(np.float64): _dp, np.dtype(np.int32): _ip}
+
+
+def _ptr(a):
+    """an array's ctypes pointer by its dtype; None and plain numbers pass through"""
+    return _POINTERS[a.dtype](a) if isinstance(a, np.ndarray) else a
+
+
+def _per_sample(x, B):
+    """a number or [B] -> float64 [B] (eps, reach)"""
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(x, np.float64).reshape(-1), (B,)))
+
+
+def _per_step(x, H, B):
+    """a number, [B] or [H, B] -> float64 [H, B] (mass_q)"""
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(x, np.float64), (H, B)))
+
+
+def _impulses(states_delta, actions, exactly_one=True):
+    """a trainer call's impulse source -> (by_actions, the array _train_batch takes for it); exactly_one: giving both or neither
+    is refused (the float64 calls ignore states_delta beside actions instead)"""
+    if exactly_one and (states_delta is None) == (actions is None):
+        raise ValueError('exactly one of states_delta and actions must be given')
+    by_actions = actions is not None
+    return by_actions, _f32(actions) if by_actions else states_delta
+
+
+def _source_args(by_actions, impulses):
+    """the C ABI's (states_delta, actions) argument pair"""
+    return (None, impulses) if by_actions else (impulses, None)
+
+
+def _compare_blobs(g32, g64):
+    """an fp32 gradient blob against its float64 yardstick, per tensor -> ({state_dict key: {'max_abs_err', 'max_abs_ref', 'rel' =
+    err / max(ref, 1e-300)}}, the key of the largest rel); NaN counts as +inf"""
+    from .weights import STATE_DICT_KEYS
+    tensors, off, worst = {}, 0, None
+    for key, shape in STATE_DICT_KEYS:
+        n = int(np.prod(shape))
+        err = np.abs(g32[off:off + n].astype(np.float64) - g64[off:off + n])
+        err = float(np.where(np.isnan(err), np.inf, err).max())
+        ref = float(np.abs(g64[off:off + n]).max())
+        tensors[key] = {'max_abs_err': err, 'max_abs_ref': ref, 'rel': err / max(ref, 1e-300)}
+        if worst is None or tensors[key]['rel'] > tensors[worst]['rel']:
+            worst = key
+        off += n
+    return tensors, worst
+
+
 # ---- the row layout of a multi-scene session (include/drp.h: drp_mpc_begin_scenes; pure numpy, no device, no library) --------
 def scene_rows(S, n_units, nb):
     """Rows of every scene in a session of S scenes x n_units samples (or trajectories) x nb columns -> int64 [S, n_units * nb]:
@@ -787,8 +836,8 @@ class Engine(object):
         match = np.full((H, B, N), -1, np.int32) if (want_match and loss != 'chamfer') else None
         tail = (L.TRAIN_MODES[mode], ctypes.byref(out), _opt(_fp, grad))
         if loss is not None:
-            rc = self.lib.drp_train_step_loss(self.h, ps, None if by_actions else pi, pi if by_actions else None, pa, pn, pd, B, N,
-                                              pt, ptn, M, L.LOSS_KINDS[loss], float(match_weight), *tail, _opt(_ip, match))
+            rc = self.lib.drp_train_step_loss(self.h, ps, *_source_args(by_actions, pi), pa, pn, pd, B, N, pt, ptn, M,
+                                              L.LOSS_KINDS[loss], float(match_weight), *tail, _opt(_ip, match))
         elif by_actions:
             rc = self.lib.drp_train_step_actions(self.h, ps, pi, pa, pn, pd, B, N, pt, ptn, M, *tail)
         elif targets is not None:
@@ -829,8 +878,7 @@ class Engine(object):
         or None[, match [n_rollout, B, N]: every predicted row's partner in its target, -1 for unmatched rows and padding])."""
         if loss not in L.LOSS_KINDS:
             raise ValueError('loss must be one of %s' % (tuple(L.LOSS_KINDS),))
-        if (states_delta is None) == (actions is None):
-            raise ValueError('exactly one of states_delta and actions must be given')
+        _impulses(states_delta, actions)
         assert targets is not None and target_nums is not None
         out = self._train_step32(states, states_delta, actions, attrs, particle_nums, particle_dens, targets, target_nums, mode,
                                  want_grad, loss, match_weight, want_match)
@@ -840,13 +888,10 @@ class Engine(object):
     def _seeded_batch(self, states, states_delta, actions, attrs, particle_nums, particle_dens, need_begin):
         """the batch of the four seeded calls: exactly one impulse source -> (_train_batch's arrays, (B, N, H), the C arguments up
         to N)"""
-        if (states_delta is None) == (actions is None):
-            raise ValueError('exactly one of states_delta and actions must be given')
-        by_actions = actions is not None
+        by_actions, imp = _impulses(states_delta, actions)
         keep, (B, N, H, _), (ps, pi, pa, pn, pd, _, _) = self._train_batch(
-            states, _f32(actions) if by_actions else states_delta, attrs, particle_nums, particle_dens, None, None, by_actions,
-            need_begin)
-        return keep, (B, N, H), (self.h, ps, None if by_actions else pi, pi if by_actions else None, pa, pn, pd, B, N)
+            states, imp, attrs, particle_nums, particle_dens, None, None, by_actions, need_begin)
+        return keep, (B, N, H), (self.h, ps, *_source_args(by_actions, pi), pa, pn, pd, B, N)
 
     def train_predict(self, states, attrs, particle_nums, particle_dens, states_delta=None, actions=None):
         """What the training forward predicts: every step's state [B, n_rollout, N, 3] float32, from the forward exactly as
@@ -892,12 +937,12 @@ class Engine(object):
                                       mode=mode, want_grad=want_grad)
         return float(value), grad
 
-    # ---- one-shots on two cloud batches (include/drp.h: drp_cloud_chamfer, drp_cloud_chamfer_f64, drp_cloud_match) ---------
+    # ---- one-shots on two cloud batches (include/drp.h: drp_cloud_chamfer, drp_cloud_match, drp_cloud_divergence and their _f64) ----
     @staticmethod
-    def _cloud_pair(p, q, n_p, n_q):
+    def _cloud_pair(p, q, n_p, n_q, dtype=np.float32):
         """p [B, N, 3] and q [B, M, 3] (or one pair as [N, 3], [M, 3]) with their real rows n_p, n_q [B] (None: all) as the one-shots
-        take them -> (p, q, n_p, n_q, B, N, M)."""
-        p, q = _f32(p), _f32(q)
+        take them -> (p, q, n_p, n_q, B, N, M); dtype: p's -- float64 for the yardsticks that take p as doubles."""
+        p, q = np.ascontiguousarray(p, dtype=dtype), _f32(q)
         if p.ndim == 2 and q.ndim == 2:
             p, q = p[None], q[None]
         assert p.ndim == 3 and q.ndim == 3 and p.shape[2] == 3 and q.shape[2] == 3 and p.shape[0] == q.shape[0]
@@ -907,23 +952,64 @@ class Engine(object):
         assert n_p.shape == (B,) and n_q.shape == (B,)
         return p, q, n_p, n_q, int(B), int(N), int(M)
 
+    def _cloud_call(self, fn, pair, middle, outs):
+        """A one-shot's C call on _cloud_pair's tuple: `middle` goes between M and the outputs, `outs` are the output arrays, None
+        for one that is not wanted; the pointers by each array's dtype"""
+        p, q, n_p, n_q, B, N, M = pair
+        self._ck(fn(self.h, _ptr(p), _ip(n_p), _fp(q), _ip(n_q), B, N, M, *map(_ptr, middle), *map(_ptr, outs)))
+
+    def _cloud_chamfer(self, dtype, p, q, n_p, n_q, want_grad, want_nn):
+        """cloud_chamfer (dtype float32) and cloud_chamfer_f64 (float64: the gradient's type, and the margins; p stays float32)"""
+        f64 = dtype is np.float64
+        pair = self._cloud_pair(p, q, n_p, n_q)
+        B, N, M = pair[4:]
+        terms = np.empty((B, 2), np.float64)
+        grad = np.empty((B, N, 3), dtype) if want_grad else None
+        nn_pq = np.empty((B, N), np.int32) if want_nn else None
+        nn_qp = np.empty((B, M), np.int32) if want_nn else None
+        margin = np.empty((B, 2), np.float64) if f64 else None
+        self._cloud_call(self.lib.drp_cloud_chamfer_f64 if f64 else self.lib.drp_cloud_chamfer, pair, (),
+                         (terms, grad, nn_pq, nn_qp) + ((margin,) if f64 else ()))
+        out = {'fwd': terms[:, 0].copy(), 'bwd': terms[:, 1].copy(), 'total': terms[:, 0] + terms[:, 1]}
+        if f64:
+            out['margin'] = margin
+        if want_grad:
+            out['grad'] = grad
+        if want_nn:
+            out['nn_pq'], out['nn_qp'] = nn_pq, nn_qp
+        return out
+
     def cloud_chamfer(self, p, q, n_p=None, n_q=None, want_grad=False, want_nn=False):
         """Symmetric squared Chamfer distance of p [B, N, 3] (n_p [B] real rows, default all) and q [B, M, 3] (n_q) ->
         {'fwd', 'bwd', 'total' [B] float64[, 'grad' [B, N, 3] = d total / d p][, 'nn_pq' [B, N], 'nn_qp' [B, M]: each row's nearest
         row of the other cloud, -1 on padding]}.  A single cloud pair may be given as [N, 3], [M, 3].  A one-shot: it needs no
         weights and ends no session."""
-        p, q, n_p, n_q, B, N, M = self._cloud_pair(p, q, n_p, n_q)
-        terms = np.empty((B, 2), np.float64)
-        grad = np.empty((B, N, 3), np.float32) if want_grad else None
-        nn_pq = np.empty((B, N), np.int32) if want_nn else None
-        nn_qp = np.empty((B, M), np.int32) if want_nn else None
-        self._ck(self.lib.drp_cloud_chamfer(self.h, _fp(p), _ip(n_p), _fp(q), _ip(n_q), B, N, M, _dp(terms), _opt(_fp, grad),
-                                            _opt(_ip, nn_pq), _opt(_ip, nn_qp)))
-        out = {'fwd': terms[:, 0].copy(), 'bwd': terms[:, 1].copy(), 'total': terms[:, 0] + terms[:, 1]}
+        return self._cloud_chamfer(np.float32, p, q, n_p, n_q, want_grad, want_nn)
+
+    def _cloud_match(self, dtype, p, q, n_p, n_q, match_in, want_grad, want_match, want_dual):
+        """cloud_match (dtype float32) and cloud_match_f64 (float64: p's and the gradient's type, match_in and the two costs)"""
+        f64 = dtype is np.float64
+        pair = self._cloud_pair(p, q, n_p, n_q, dtype)
+        n_p, n_q, B, N, M = pair[2:]
+        if match_in is not None:
+            match_in = _i32(match_in).reshape(B, N)
+        terms = np.empty((B,), np.float64)
+        grad = np.empty((B, N, 3), dtype) if want_grad else None
+        m_pq = np.empty((B, N), np.int32) if want_match else None
+        m_qp = np.empty((B, M), np.int32) if want_match else None
+        dual = np.empty((B, N + M), np.float64) if want_dual else None
+        cost = np.empty((B, 2), np.float64) if f64 else None
+        self._cloud_call(self.lib.drp_cloud_match_f64 if f64 else self.lib.drp_cloud_match, pair, (match_in,) if f64 else (),
+                         (terms, grad, m_pq, m_qp, dual) + ((cost,) if f64 else ()))
+        out = {'match': terms, 'r': np.minimum(n_p, n_q)}
+        if f64:
+            out['cost'], out['opt_cost'] = cost[:, 0].copy(), cost[:, 1].copy()
         if want_grad:
             out['grad'] = grad
-        if want_nn:
-            out['nn_pq'], out['nn_qp'] = nn_pq, nn_qp
+        if want_match:
+            out['match_pq'], out['match_qp'] = m_pq, m_qp
+        if want_dual:
+            out['u'], out['v'] = dual[:, :N].copy(), dual[:, N:].copy()
         return out
 
     def cloud_match(self, p, q, n_p=None, n_q=None, want_grad=False, want_match=False, want_dual=False):
@@ -933,22 +1019,7 @@ class Engine(object):
         [B, N], 'match_qp' [B, M]: each row's partner, -1 for unmatched rows and padding][, 'u' [B, N], 'v' [B, M]: the duals of
         p's and q's rows, float64]}.  A single cloud pair may be given as [N, 3], [M, 3].  At most 1024 points per cloud.  A
         one-shot: it needs no weights and ends no session."""
-        p, q, n_p, n_q, B, N, M = self._cloud_pair(p, q, n_p, n_q)
-        terms = np.empty((B,), np.float64)
-        grad = np.empty((B, N, 3), np.float32) if want_grad else None
-        m_pq = np.empty((B, N), np.int32) if want_match else None
-        m_qp = np.empty((B, M), np.int32) if want_match else None
-        dual = np.empty((B, N + M), np.float64) if want_dual else None
-        self._ck(self.lib.drp_cloud_match(self.h, _fp(p), _ip(n_p), _fp(q), _ip(n_q), B, N, M, _dp(terms), _opt(_fp, grad),
-                                          _opt(_ip, m_pq), _opt(_ip, m_qp), _opt(_dp, dual)))
-        out = {'match': terms, 'r': np.minimum(n_p, n_q)}
-        if want_grad:
-            out['grad'] = grad
-        if want_match:
-            out['match_pq'], out['match_qp'] = m_pq, m_qp
-        if want_dual:
-            out['u'], out['v'] = dual[:, :N].copy(), dual[:, N:].copy()
-        return out
+        return self._cloud_match(np.float32, p, q, n_p, n_q, None, want_grad, want_match, want_dual)
 
     def cloud_transport(self, p, q, n_p=None, n_q=None, eps=None, iters=None, want_grad=False, want_dual=False, want_col_err=False):
         """Entropy-regularised optimal-transport distance of p [B, N, 3] (n_p [B] real rows, default all; mass 1 / n_p each) and
@@ -960,14 +1031,13 @@ class Engine(object):
         points per cloud.  A one-shot: it needs no weights and ends no session."""
         if eps is None or iters is None:
             raise ValueError('cloud_transport needs eps (squared-distance units) and iters')
-        p, q, n_p, n_q, B, N, M = self._cloud_pair(p, q, n_p, n_q)
-        eps = np.ascontiguousarray(np.broadcast_to(np.asarray(eps, np.float64).reshape(-1), (B,)))
+        pair = self._cloud_pair(p, q, n_p, n_q)
+        B, N, M = pair[4:]
         terms = np.empty((B,), np.float64)
         grad = np.empty((B, N, 3), np.float32) if want_grad else None
         dual = np.empty((B, N + M), np.float64) if want_dual else None
         col_err = np.empty((B,), np.float64) if want_col_err else None
-        self._ck(self.lib.drp_cloud_transport(self.h, _fp(p), _ip(n_p), _fp(q), _ip(n_q), B, N, M, _dp(eps), int(iters), _dp(terms),
-                                              _opt(_fp, grad), _opt(_dp, dual), _opt(_dp, col_err)))
+        self._cloud_call(self.lib.drp_cloud_transport, pair, (_per_sample(eps, B), int(iters)), (terms, grad, dual, col_err))
         out = {'transport': terms}
         if want_grad:
             out['grad'] = grad
@@ -977,26 +1047,70 @@ class Engine(object):
             out['col_err'] = col_err
         return out
 
+    def _train_targeted32(self, fn, by_actions, impulses, states, attrs, particle_nums, particle_dens, targets, target_nums, mode,
+                          want_grad, extra):
+        """An fp32 trainer call whose loss takes arguments of its own (drp_train_step_transport, drp_train_step_divergence,
+        drp_train_step_divergence_unbalanced).  by_actions, impulses: _impulses'.  extra(H, B) -> (the C arguments between M and
+        mode, the outputs behind grad_out -- None for one that is not wanted), arrays as numpy arrays -> (loss, gradient blob or
+        None) + the outputs."""
+        assert targets is not None and target_nums is not None
+        keep, (B, N, H, M), (ps, pi, pa, pn, pd, pt, ptn) = self._train_batch(
+            states, impulses, attrs, particle_nums, particle_dens, targets, target_nums, by_actions, True)
+        args, outs = extra(H, B)
+        loss = ctypes.c_double()
+        grad = np.empty((L.DRP_N_WEIGHTS,), np.float32) if (want_grad and mode != 'eval') else None
+        self._ck(fn(self.h, ps, *_source_args(by_actions, pi), pa, pn, pd, B, N, pt, ptn, M, *map(_ptr, args), L.TRAIN_MODES[mode],
+                    ctypes.byref(loss), _ptr(grad), *map(_ptr, outs)))
+        return (loss.value, grad) + tuple(outs)
+
     def train_step_transport(self, states, attrs, particle_nums, particle_dens, targets, target_nums, eps, iters, states_delta=None,
                              actions=None, mode='update', want_grad=False, want_col_err=False):
         """train_step_loss with each step's term the transport distance of cloud_transport between the predicted state and its
         target cloud (include/drp.h: drp_train_step_transport): eps [B] (or a number) per sample, iters sweeps; states_delta
         [B, n_rollout, N, 3] or actions [B, n_rollout, 4] -- exactly one of the two -> (loss, gradient blob or None[, col_err
         [n_rollout, B]: every problem's column-marginal violation])."""
-        if (states_delta is None) == (actions is None):
-            raise ValueError('exactly one of states_delta and actions must be given')
-        assert targets is not None and target_nums is not None
-        by_actions = actions is not None
-        keep, (B, N, H, M), (ps, pi, pa, pn, pd, pt, ptn) = self._train_batch(
-            states, _f32(actions) if by_actions else states_delta, attrs, particle_nums, particle_dens, targets, target_nums, by_actions, True)
-        eps = np.ascontiguousarray(np.broadcast_to(np.asarray(eps, np.float64).reshape(-1), (B,)))
-        out = ctypes.c_double()
-        grad = np.empty((L.DRP_N_WEIGHTS,), np.float32) if (want_grad and mode != 'eval') else None
-        col_err = np.empty((H, B), np.float64) if want_col_err else None
-        self._ck(self.lib.drp_train_step_transport(self.h, ps, None if by_actions else pi, pi if by_actions else None, pa, pn, pd, B, N,
-                                                   pt, ptn, M, _dp(eps), int(iters), L.TRAIN_MODES[mode], ctypes.byref(out),
-                                                   _opt(_fp, grad), _opt(_dp, col_err)))
-        return (out.value, grad, col_err) if want_col_err else (out.value, grad)
+        by_actions, imp = _impulses(states_delta, actions)
+        out = self._train_targeted32(
+            self.lib.drp_train_step_transport, by_actions, imp, states, attrs, particle_nums, particle_dens, targets, target_nums,
+            mode, want_grad, lambda H, B: ((_per_sample(eps, B), int(iters)), (np.empty((H, B)) if want_col_err else None,)))
+        return out if want_col_err else out[:2]
+
+    def _cloud_divergence(self, name, dtype, p, q, n_p, n_q, eps, iters, want_grad, want_dual, want_col_err, want_self_err, reach,
+                          mass_q, want_transported):
+        """cloud_divergence (dtype float32) and cloud_divergence_f64 (float64: p's and the gradient's type); the balanced and the
+        unbalanced call differ in their trailing arguments alone"""
+        if eps is None or iters is None:
+            raise ValueError('%s needs eps (squared-distance units) and iters' % name)
+        if reach is None and (mass_q is not None or want_transported):
+            raise ValueError('mass_q and want_transported belong to the unbalanced divergence: give reach')
+        pair = self._cloud_pair(p, q, n_p, n_q, dtype)
+        B, N, M = pair[4:]
+        middle = (_per_sample(eps, B),)
+        terms = np.empty((B,), np.float64)
+        grad = np.empty((B, N, 3), dtype) if want_grad else None
+        dual = np.empty((B, 2 * (N + M)), np.float64) if want_dual else None
+        col_err = np.empty((B,), np.float64) if want_col_err else None
+        self_err = np.empty((B, 2), np.float64) if want_self_err else None
+        outs = (terms, grad, dual, col_err, self_err)
+        if reach is not None:
+            middle += (_per_sample(reach, B), _per_sample(1.0 if mass_q is None else mass_q, B))
+            moved = np.empty((B,), np.float64) if want_transported else None
+            outs += (moved,)
+        fn = 'drp_cloud_divergence' + ('' if reach is None else '_unbalanced') + ('_f64' if dtype is np.float64 else '')
+        self._cloud_call(getattr(self.lib, fn), pair, middle + (int(iters),), outs)
+        out = {'divergence': terms}
+        if want_transported:
+            out['transported'] = moved
+        if want_grad:
+            out['grad'] = grad
+        if want_dual:
+            out['f'], out['g'] = dual[:, :N].copy(), dual[:, N:N + M].copy()
+            out['h_p'], out['h_q'] = dual[:, N + M:2 * N + M].copy(), dual[:, 2 * N + M:].copy()
+        if want_col_err:
+            out['col_err'] = col_err
+        if want_self_err:
+            out['self_err'] = self_err
+        return out
 
     def cloud_divergence(self, p, q, n_p=None, n_q=None, eps=None, iters=None, want_grad=False, want_dual=False, want_col_err=False,
                          want_self_err=False, reach=None, mass_q=None, want_transported=False):
@@ -1012,40 +1126,23 @@ class Engine(object):
         (include/drp.h: drp_cloud_divergence_unbalanced): mass further than about sqrt(reach) from the other cloud is given up
         instead of moved.  mass_q (a number or [B], default 1, within [1/8, 8]): q's total mass against p's 1 -- n_q / n_p is
         equal mass per point.  want_transported: + 'transported' [B], the plan's total mass.  reach=None is the call above."""
-        if eps is None or iters is None:
-            raise ValueError('cloud_divergence needs eps (squared-distance units) and iters')
-        if reach is None and (mass_q is not None or want_transported):
-            raise ValueError('mass_q and want_transported belong to the unbalanced divergence: give reach')
-        p, q, n_p, n_q, B, N, M = self._cloud_pair(p, q, n_p, n_q)
-        eps = np.ascontiguousarray(np.broadcast_to(np.asarray(eps, np.float64).reshape(-1), (B,)))
-        terms = np.empty((B,), np.float64)
-        grad = np.empty((B, N, 3), np.float32) if want_grad else None
-        dual = np.empty((B, 2 * (N + M)), np.float64) if want_dual else None
-        col_err = np.empty((B,), np.float64) if want_col_err else None
-        self_err = np.empty((B, 2), np.float64) if want_self_err else None
-        if reach is None:
-            self._ck(self.lib.drp_cloud_divergence(self.h, _fp(p), _ip(n_p), _fp(q), _ip(n_q), B, N, M, _dp(eps), int(iters), _dp(terms),
-                                                   _opt(_fp, grad), _opt(_dp, dual), _opt(_dp, col_err), _opt(_dp, self_err)))
-        else:
-            rho = np.ascontiguousarray(np.broadcast_to(np.asarray(reach, np.float64).reshape(-1), (B,)))
-            w = np.ascontiguousarray(np.broadcast_to(np.asarray(1.0 if mass_q is None else mass_q, np.float64).reshape(-1), (B,)))
-            moved = np.empty((B,), np.float64) if want_transported else None
-            self._ck(self.lib.drp_cloud_divergence_unbalanced(self.h, _fp(p), _ip(n_p), _fp(q), _ip(n_q), B, N, M, _dp(eps), _dp(rho),
-                                                              _dp(w), int(iters), _dp(terms), _opt(_fp, grad), _opt(_dp, dual),
-                                                              _opt(_dp, col_err), _opt(_dp, self_err), _opt(_dp, moved)))
-        out = {'divergence': terms}
-        if want_transported:
-            out['transported'] = moved
-        if want_grad:
-            out['grad'] = grad
-        if want_dual:
-            out['f'], out['g'] = dual[:, :N].copy(), dual[:, N:N + M].copy()
-            out['h_p'], out['h_q'] = dual[:, N + M:2 * N + M].copy(), dual[:, 2 * N + M:].copy()
-        if want_col_err:
-            out['col_err'] = col_err
-        if want_self_err:
-            out['self_err'] = self_err
-        return out
+        return self._cloud_divergence('cloud_divergence', np.float32, p, q, n_p, n_q, eps, iters, want_grad, want_dual, want_col_err,
+                                      want_self_err, reach, mass_q, want_transported)
+
+    @staticmethod
+    def _divergence_extra(eps, iters, reach, mass_q, want_err, floor=0):
+        """_train_targeted32's / _train_targeted64's `extra` of the divergence: eps [B][, reach [B], mass_q [H, B]], iters, and
+        col_err [H, B], self_err [H, B, 2][, transported [H, B]] where wanted; floor: the least length the inputs are broadcast to
+        (the float64 calls hand an empty batch on for the C ABI to refuse)"""
+        def extra(H, B):
+            Hi, Bi = max(H, floor), max(B, floor)
+            args = (_per_sample(eps, Bi),)
+            shapes = ((H, B), (H, B, 2))
+            if reach is not None:
+                args += (_per_sample(reach, Bi), _per_step(1.0 if mass_q is None else mass_q, Hi, Bi))
+                shapes += ((H, B),)
+            return args + (int(iters),), tuple(np.empty(s, np.float64) if want_err else None for s in shapes)
+        return extra
 
     def train_step_divergence(self, states, attrs, particle_nums, particle_dens, targets, target_nums, eps, iters, states_delta=None,
                               actions=None, mode='update', want_grad=False, want_err=False, reach=None, mass_q=None):
@@ -1054,51 +1151,19 @@ class Engine(object):
         [n_rollout, B, 2]: every problem's certificates]).  reach (a number or [B]) and mass_q (a number, [B] or [n_rollout, B];
         default 1): cloud_divergence's unbalanced divergence as each step's term (drp_train_step_divergence_unbalanced); want_err
         then also returns transported [n_rollout, B].  reach=None is the call above."""
-        if (states_delta is None) == (actions is None):
-            raise ValueError('exactly one of states_delta and actions must be given')
+        by_actions, imp = _impulses(states_delta, actions)
         if reach is None and mass_q is not None:
             raise ValueError('mass_q belongs to the unbalanced divergence: give reach')
-        assert targets is not None and target_nums is not None
-        by_actions = actions is not None
-        keep, (B, N, H, M), (ps, pi, pa, pn, pd, pt, ptn) = self._train_batch(
-            states, _f32(actions) if by_actions else states_delta, attrs, particle_nums, particle_dens, targets, target_nums, by_actions, True)
-        eps = np.ascontiguousarray(np.broadcast_to(np.asarray(eps, np.float64).reshape(-1), (B,)))
-        out = ctypes.c_double()
-        grad = np.empty((L.DRP_N_WEIGHTS,), np.float32) if (want_grad and mode != 'eval') else None
-        col_err = np.empty((H, B), np.float64) if want_err else None
-        self_err = np.empty((H, B, 2), np.float64) if want_err else None
-        if reach is not None:
-            rho = np.ascontiguousarray(np.broadcast_to(np.asarray(reach, np.float64).reshape(-1), (B,)))
-            w = np.ascontiguousarray(np.broadcast_to(np.asarray(1.0 if mass_q is None else mass_q, np.float64), (H, B)))
-            moved = np.empty((H, B), np.float64) if want_err else None
-            self._ck(self.lib.drp_train_step_divergence_unbalanced(
-                self.h, ps, None if by_actions else pi, pi if by_actions else None, pa, pn, pd, B, N, pt, ptn, M, _dp(eps), _dp(rho),
-                _dp(w), int(iters), L.TRAIN_MODES[mode], ctypes.byref(out), _opt(_fp, grad), _opt(_dp, col_err), _opt(_dp, self_err),
-                _opt(_dp, moved)))
-            return (out.value, grad, col_err, self_err, moved) if want_err else (out.value, grad)
-        self._ck(self.lib.drp_train_step_divergence(self.h, ps, None if by_actions else pi, pi if by_actions else None, pa, pn, pd, B, N,
-                                                    pt, ptn, M, _dp(eps), int(iters), L.TRAIN_MODES[mode], ctypes.byref(out),
-                                                    _opt(_fp, grad), _opt(_dp, col_err), _opt(_dp, self_err)))
-        return (out.value, grad, col_err, self_err) if want_err else (out.value, grad)
+        fn = self.lib.drp_train_step_divergence if reach is None else self.lib.drp_train_step_divergence_unbalanced
+        out = self._train_targeted32(fn, by_actions, imp, states, attrs, particle_nums, particle_dens, targets, target_nums, mode,
+                                     want_grad, self._divergence_extra(eps, iters, reach, mass_q, want_err))
+        return out if want_err else out[:2]
 
     def cloud_chamfer_f64(self, p, q, n_p=None, n_q=None, want_grad=False, want_nn=False):
         """cloud_chamfer in float64 on the device (include/drp.h: drp_cloud_chamfer_f64): the same dict with 'grad' as float64,
         plus 'margin' [B, 2] -- per sample the smallest (second-best - best) squared distance over its arg-mins, p -> q then
         q -> p: 0 for a duplicate of a winner, inf where the other cloud has one row."""
-        p, q, n_p, n_q, B, N, M = self._cloud_pair(p, q, n_p, n_q)
-        terms = np.empty((B, 2), np.float64)
-        margin = np.empty((B, 2), np.float64)
-        grad = np.empty((B, N, 3), np.float64) if want_grad else None
-        nn_pq = np.empty((B, N), np.int32) if want_nn else None
-        nn_qp = np.empty((B, M), np.int32) if want_nn else None
-        self._ck(self.lib.drp_cloud_chamfer_f64(self.h, _fp(p), _ip(n_p), _fp(q), _ip(n_q), B, N, M, _dp(terms), _opt(_dp, grad),
-                                                _opt(_ip, nn_pq), _opt(_ip, nn_qp), _dp(margin)))
-        out = {'fwd': terms[:, 0].copy(), 'bwd': terms[:, 1].copy(), 'total': terms[:, 0] + terms[:, 1], 'margin': margin}
-        if want_grad:
-            out['grad'] = grad
-        if want_nn:
-            out['nn_pq'], out['nn_qp'] = nn_pq, nn_qp
-        return out
+        return self._cloud_chamfer(np.float64, p, q, n_p, n_q, want_grad, want_nn)
 
     def cloud_divergence_f64(self, p, q, n_p=None, n_q=None, eps=None, iters=None, want_grad=False, want_dual=False,
                              want_col_err=False, want_self_err=False, reach=None, mass_q=None, want_transported=False):
@@ -1106,47 +1171,9 @@ class Engine(object):
         [B, N, 3] -- every bit of it enters the costs, as the float64 tape's predicted state does in train_grad_f64_divergence --
         q as float32 widened exactly; costs and differences are double, and 'grad' is float64, never rounded to fp32.  The same
         arguments, dict, limits (1024 points per cloud) and one-shot contract.  reach, mass_q and want_transported as
-        cloud_divergence's: the unbalanced divergence's yardstick (include/drp.h: drp_cloud_divergence_unbalanced_f64); reach=None
-        is the call above."""
-        if eps is None or iters is None:
-            raise ValueError('cloud_divergence_f64 needs eps (squared-distance units) and iters')
-        if reach is None and (mass_q is not None or want_transported):
-            raise ValueError('mass_q and want_transported belong to the unbalanced divergence: give reach')
-        p64, q = _f64(p), _f32(q)
-        if p64.ndim == 2 and q.ndim == 2:
-            p64, q = p64[None], q[None]
-        _, q, n_p, n_q, B, N, M = self._cloud_pair(np.empty(p64.shape, np.float32), q, n_p, n_q)     # (the shapes' checks)
-        eps = np.ascontiguousarray(np.broadcast_to(np.asarray(eps, np.float64).reshape(-1), (B,)))
-        terms = np.empty((B,), np.float64)
-        grad = np.empty((B, N, 3), np.float64) if want_grad else None
-        dual = np.empty((B, 2 * (N + M)), np.float64) if want_dual else None
-        col_err = np.empty((B,), np.float64) if want_col_err else None
-        self_err = np.empty((B, 2), np.float64) if want_self_err else None
-        if reach is None:
-            self._ck(self.lib.drp_cloud_divergence_f64(self.h, _dp(p64), _ip(n_p), _fp(q), _ip(n_q), B, N, M, _dp(eps), int(iters),
-                                                       _dp(terms), _opt(_dp, grad), _opt(_dp, dual), _opt(_dp, col_err),
-                                                       _opt(_dp, self_err)))
-        else:
-            rho = np.ascontiguousarray(np.broadcast_to(np.asarray(reach, np.float64).reshape(-1), (B,)))
-            w = np.ascontiguousarray(np.broadcast_to(np.asarray(1.0 if mass_q is None else mass_q, np.float64).reshape(-1), (B,)))
-            moved = np.empty((B,), np.float64) if want_transported else None
-            self._ck(self.lib.drp_cloud_divergence_unbalanced_f64(self.h, _dp(p64), _ip(n_p), _fp(q), _ip(n_q), B, N, M, _dp(eps),
-                                                                  _dp(rho), _dp(w), int(iters), _dp(terms), _opt(_dp, grad),
-                                                                  _opt(_dp, dual), _opt(_dp, col_err), _opt(_dp, self_err),
-                                                                  _opt(_dp, moved)))
-        out = {'divergence': terms}
-        if want_transported:
-            out['transported'] = moved
-        if want_grad:
-            out['grad'] = grad
-        if want_dual:
-            out['f'], out['g'] = dual[:, :N].copy(), dual[:, N:N + M].copy()
-            out['h_p'], out['h_q'] = dual[:, N + M:2 * N + M].copy(), dual[:, 2 * N + M:].copy()
-        if want_col_err:
-            out['col_err'] = col_err
-        if want_self_err:
-            out['self_err'] = self_err
-        return out
+        cloud_divergence's: the unbalanced divergence's yardstick (include/drp.h: drp_cloud_divergence_unbalanced_f64)."""
+        return self._cloud_divergence('cloud_divergence_f64', np.float64, p, q, n_p, n_q, eps, iters, want_grad, want_dual,
+                                      want_col_err, want_self_err, reach, mass_q, want_transported)
 
     def cloud_match_f64(self, p, q, n_p=None, n_q=None, match_in=None, want_grad=False, want_match=False, want_dual=False):
         """cloud_match with nothing in fp32, on the device (include/drp.h: drp_cloud_match_f64): p is taken as float64 [B, N, 3]
@@ -1156,28 +1183,7 @@ class Engine(object):
         [B, N] (every row of p's partner, -1 for none): 'match' and 'grad' are taken on these pairs; 'match_pq', 'match_qp', 'u',
         'v' and 'opt_cost' are the solver's own optimum all the same, and cost >= opt_cost says how far from it the given pairs
         are.  The same limits (1024 points per cloud) and one-shot contract."""
-        p64, q = _f64(p), _f32(q)
-        if p64.ndim == 2 and q.ndim == 2:
-            p64, q = p64[None], q[None]
-        _, q, n_p, n_q, B, N, M = self._cloud_pair(np.empty(p64.shape, np.float32), q, n_p, n_q)     # (the shapes' checks)
-        if match_in is not None:
-            match_in = _i32(match_in).reshape(B, N)
-        terms = np.empty((B,), np.float64)
-        grad = np.empty((B, N, 3), np.float64) if want_grad else None
-        m_pq = np.empty((B, N), np.int32) if want_match else None
-        m_qp = np.empty((B, M), np.int32) if want_match else None
-        dual = np.empty((B, N + M), np.float64) if want_dual else None
-        cost = np.empty((B, 2), np.float64)
-        self._ck(self.lib.drp_cloud_match_f64(self.h, _dp(p64), _ip(n_p), _fp(q), _ip(n_q), B, N, M, _opt(_ip, match_in), _dp(terms),
-                                              _opt(_dp, grad), _opt(_ip, m_pq), _opt(_ip, m_qp), _opt(_dp, dual), _dp(cost)))
-        out = {'match': terms, 'r': np.minimum(n_p, n_q), 'cost': cost[:, 0].copy(), 'opt_cost': cost[:, 1].copy()}
-        if want_grad:
-            out['grad'] = grad
-        if want_match:
-            out['match_pq'], out['match_qp'] = m_pq, m_qp
-        if want_dual:
-            out['u'], out['v'] = dual[:, :N].copy(), dual[:, N:].copy()
-        return out
+        return self._cloud_match(np.float64, p, q, n_p, n_q, match_in, want_grad, want_match, want_dual)
 
     # ---- the float64 yardstick of the trainer's gradients (include/drp.h: drp_train_grad_f64) ------------------------
     def _train_grad64(self, states, states_delta, actions, attrs, particle_nums, particle_dens, targets, target_nums, want_state):
@@ -1194,8 +1200,8 @@ class Engine(object):
         gs = np.empty((B, max(H, 0), N, 3), np.float64) if want_state else None
         tail = (ctypes.byref(loss), _dp(terms), _dp(grad), _opt(_dp, gs))
         if targets is not None:
-            rc = self.lib.drp_train_grad_f64_untracked(self.h, ps, None if by_actions else pi, pi if by_actions else None, pa, pn, pd,
-                                                       B, N, H, pt, ptn, M, *tail, _dp(margin))
+            rc = self.lib.drp_train_grad_f64_untracked(self.h, ps, *_source_args(by_actions, pi), pa, pn, pd, B, N, H, pt, ptn, M,
+                                                       *tail, _dp(margin))
         else:
             fn = self.lib.drp_train_grad_f64_actions if by_actions else self.lib.drp_train_grad_f64
             rc = fn(self.h, ps, pi, pa, pn, pd, B, N, H, *tail)
@@ -1232,6 +1238,24 @@ class Engine(object):
                                                            targets, target_nums, want_state)
         return (loss, terms, grad, margin, gs) if want_state else (loss, terms, grad, margin)
 
+    def _train_targeted64(self, fn, states, states_delta, actions, attrs, particle_nums, particle_dens, targets, target_nums,
+                          want_state, extra):
+        """_train_targeted32's float64 counterpart (drp_train_grad_f64_divergence, drp_train_grad_f64_divergence_unbalanced,
+        drp_train_grad_f64_match): n_rollout is read from the arrays, states_delta is ignored beside actions, and extra(H, B, N)'s
+        outputs go behind grad_state_out -> ((loss, loss_terms [H, B], gradient blob[, state gradient]), the outputs)."""
+        assert targets is not None and target_nums is not None
+        by_actions, imp = _impulses(states_delta, actions, exactly_one=False)
+        keep, (B, N, H, M), (ps, pi, pa, pn, pd, pt, ptn) = self._train_batch(
+            states, imp, attrs, particle_nums, particle_dens, targets, target_nums, by_actions, False)
+        args, outs = extra(max(H, 0), B, N)
+        loss = ctypes.c_double()
+        terms = np.empty((max(H, 0), B), np.float64)
+        grad = np.empty((L.DRP_N_WEIGHTS,), np.float64)
+        gs = np.empty((B, max(H, 0), N, 3), np.float64) if want_state else None
+        self._ck(fn(self.h, ps, *_source_args(by_actions, pi), pa, pn, pd, B, N, H, pt, ptn, M, *map(_ptr, args), ctypes.byref(loss),
+                    _dp(terms), _dp(grad), _ptr(gs), *map(_ptr, outs)))
+        return (loss.value, terms, grad) + ((gs,) if want_state else ()), tuple(outs)
+
     def train_grad_f64_divergence(self, states, states_delta, attrs, particle_nums, particle_dens, targets, target_nums, eps, iters,
                                   actions=None, want_state=False, want_err=False, reach=None, mass_q=None):
         """train_grad_f64_untracked with the Sinkhorn divergence in place of the Chamfer loss: what
@@ -1245,31 +1269,11 @@ class Engine(object):
         reach=None is the call above."""
         if reach is None and mass_q is not None:
             raise ValueError('mass_q belongs to the unbalanced divergence: give reach')
-        assert targets is not None and target_nums is not None
-        by_actions = actions is not None
-        keep, (B, N, H, M), (ps, pi, pa, pn, pd, pt, ptn) = self._train_batch(
-            states, _f32(actions) if by_actions else states_delta, attrs, particle_nums, particle_dens, targets, target_nums,
-            by_actions, False)
-        eps = np.ascontiguousarray(np.broadcast_to(np.asarray(eps, np.float64).reshape(-1), (max(B, 1),)))
-        loss = ctypes.c_double()
-        terms = np.empty((max(H, 0), B), np.float64)
-        grad = np.empty((L.DRP_N_WEIGHTS,), np.float64)
-        gs = np.empty((B, max(H, 0), N, 3), np.float64) if want_state else None
-        col_err = np.empty((max(H, 0), B), np.float64) if want_err else None
-        self_err = np.empty((max(H, 0), B, 2), np.float64) if want_err else None
-        if reach is not None:
-            rho = np.ascontiguousarray(np.broadcast_to(np.asarray(reach, np.float64).reshape(-1), (max(B, 1),)))
-            w = np.ascontiguousarray(np.broadcast_to(np.asarray(1.0 if mass_q is None else mass_q, np.float64), (max(H, 1), max(B, 1))))
-            moved = np.empty((max(H, 0), B), np.float64) if want_err else None
-            self._ck(self.lib.drp_train_grad_f64_divergence_unbalanced(
-                self.h, ps, None if by_actions else pi, pi if by_actions else None, pa, pn, pd, B, N, H, pt, ptn, M, _dp(eps), _dp(rho),
-                _dp(w), int(iters), ctypes.byref(loss), _dp(terms), _dp(grad), _opt(_dp, gs), _opt(_dp, col_err), _opt(_dp, self_err),
-                _opt(_dp, moved)))
-            return (loss.value, terms, grad) + ((gs,) if want_state else ()) + ((col_err, self_err, moved) if want_err else ())
-        self._ck(self.lib.drp_train_grad_f64_divergence(self.h, ps, None if by_actions else pi, pi if by_actions else None, pa, pn, pd,
-                                                        B, N, H, pt, ptn, M, _dp(eps), int(iters), ctypes.byref(loss), _dp(terms),
-                                                        _dp(grad), _opt(_dp, gs), _opt(_dp, col_err), _opt(_dp, self_err)))
-        return (loss.value, terms, grad) + ((gs,) if want_state else ()) + ((col_err, self_err) if want_err else ())
+        fn = self.lib.drp_train_grad_f64_divergence if reach is None else self.lib.drp_train_grad_f64_divergence_unbalanced
+        extra = self._divergence_extra(eps, iters, reach, mass_q, want_err, floor=1)
+        out, errs = self._train_targeted64(fn, states, states_delta, actions, attrs, particle_nums, particle_dens, targets, target_nums,
+                                           want_state, lambda H, B, N: extra(H, B))
+        return out + (errs if want_err else ())
 
     def train_grad_f64_match(self, states, states_delta, attrs, particle_nums, particle_dens, targets, target_nums, loss='match',
                              match_weight=0.5, actions=None, match_in=None, want_state=False, want_info=False):
@@ -1284,27 +1288,18 @@ class Engine(object):
         the mix's Chamfer arg-min margins, None for 'match'}]).  The same one-shot contract."""
         if loss not in L.MATCH_LOSSES:
             raise ValueError('loss must be one of %s' % (L.MATCH_LOSSES,))
-        assert targets is not None and target_nums is not None
-        by_actions = actions is not None
-        keep, (B, N, H, M), (ps, pi, pa, pn, pd, pt, ptn) = self._train_batch(
-            states, _f32(actions) if by_actions else states_delta, attrs, particle_nums, particle_dens, targets, target_nums,
-            by_actions, False)
-        if match_in is not None:
-            match_in = _i32(match_in).reshape(max(H, 0), B, N)
-        out = ctypes.c_double()
-        terms = np.empty((max(H, 0), B), np.float64)
-        grad = np.empty((L.DRP_N_WEIGHTS,), np.float64)
-        gs = np.empty((B, max(H, 0), N, 3), np.float64) if want_state else None
-        match = np.full((max(H, 0), B, N), -1, np.int32) if want_info else None
-        cost = np.empty((max(H, 0), B, 2), np.float64) if want_info else None
-        margin = np.empty((max(H, 0), B), np.float64) if (want_info and loss != 'match') else None
-        self._ck(self.lib.drp_train_grad_f64_match(self.h, ps, None if by_actions else pi, pi if by_actions else None, pa, pn, pd,
-                                                   B, N, H, pt, ptn, M, L.LOSS_KINDS[loss], float(match_weight),
-                                                   _opt(_ip, match_in), ctypes.byref(out), _dp(terms), _dp(grad), _opt(_dp, gs),
-                                                   _opt(_ip, match), _opt(_dp, cost), _opt(_dp, margin)))
+
+        def extra(H, B, N):
+            given = None if match_in is None else _i32(match_in).reshape(H, B, N)
+            match = np.full((H, B, N), -1, np.int32) if want_info else None
+            cost = np.empty((H, B, 2), np.float64) if want_info else None
+            margin = np.empty((H, B), np.float64) if (want_info and loss != 'match') else None
+            return (L.LOSS_KINDS[loss], float(match_weight), given), (match, cost, margin)
+        out, (match, cost, margin) = self._train_targeted64(self.lib.drp_train_grad_f64_match, states, states_delta, actions, attrs,
+                                                            particle_nums, particle_dens, targets, target_nums, want_state, extra)
         info = {'match': match, 'cost': cost[..., 0].copy(), 'opt_cost': cost[..., 1].copy(),
                 'chamfer_margin': margin} if want_info else None
-        return (out.value, terms, grad) + ((gs,) if want_state else ()) + ((info,) if want_info else ())
+        return out + ((info,) if want_info else ())
 
     def train_predict_f64(self, states, attrs, particle_nums, particle_dens, states_delta=None, actions=None):
         """train_predict in float64 on the device: every step's predicted state [B, n_rollout, N, 3] float64 of train_grad_f64's
@@ -1337,7 +1332,6 @@ class Engine(object):
         the fp32 drift of the prediction -- the loss's conditioning, as opposed to the tape's arithmetic.  Needs train_begin; it
         changes no weight, Adam moment or iteration count; like train_gradient_probe it ends a running planner session and
         resets the dispatch marks."""
-        from .weights import STATE_DICT_KEYS
         kw = {'states_delta': states_delta, 'actions': actions}
         self.dispatch_reset()
         pred32 = self.train_predict(states, attrs, particle_nums, particle_dens, **kw)
@@ -1348,16 +1342,7 @@ class Engine(object):
         loss64, seed64 = loss_fn(pred64, context)
         g64, = self.train_grad_f64_seeded(states, attrs, particle_nums, particle_dens, seed64, **kw)
         loss32, loss64 = float(loss32), float(loss64)
-        tensors, off, worst = {}, 0, None
-        for key, shape in STATE_DICT_KEYS:
-            n = int(np.prod(shape))
-            err = np.abs(g32[off:off + n].astype(np.float64) - g64[off:off + n])
-            err = float(np.where(np.isnan(err), np.inf, err).max())
-            ref = float(np.abs(g64[off:off + n]).max())
-            tensors[key] = {'max_abs_err': err, 'max_abs_ref': ref, 'rel': err / max(ref, 1e-300)}
-            if worst is None or tensors[key]['rel'] > tensors[worst]['rel']:
-                worst = key
-            off += n
+        tensors, worst = _compare_blobs(g32, g64)
         real = np.arange(pred32.shape[2])[None, :] < _i32(particle_nums).reshape(-1, 1)          # [B, N]
         s32 = np.where(real[:, None, :, None], np.asarray(seed32, np.float64), 0.0)
         s64 = np.where(real[:, None, :, None], np.asarray(seed64, np.float64), 0.0)
@@ -1397,7 +1382,6 @@ class Engine(object):
         'sinkhorn' dict also has 'reach': True, 'transported' -- the float64 side's smallest transported share over the batch --
         and 'transported_diff', the largest |fp32 side - float64 side| of a problem's share: whether the tape's drift changed what
         the loss gives up.  reach=None is the call without these two keywords."""
-        from .weights import STATE_DICT_KEYS
         if reach is not None and (eps is None or loss is not None):
             raise ValueError('reach= belongs to the Sinkhorn divergence: give eps and iters, and no loss=')
         if reach is None and mass_q is not None:
@@ -1406,68 +1390,33 @@ class Engine(object):
         assert (eps is None) == (iters is None) and (eps is None or targets is not None)
         if loss is not None and (loss not in L.MATCH_LOSSES or targets is None or eps is not None):
             raise ValueError('loss= takes one of %s, with targets and without eps' % (L.MATCH_LOSSES,))
-        matching = loss is not None
-        sinkhorn = eps is not None
-        chamfer = targets is not None and not sinkhorn and not matching
+        # the batch as the fp32 calls take it (one impulse source) and as the float64 calls do (states_delta ignored beside actions)
+        five32 = (states, None if actions is not None else states_delta, actions, attrs, particle_nums, particle_dens)
+        six = (states, attrs, particle_nums, particle_dens, targets, target_nums)
+        seven64 = (states, states_delta, attrs, particle_nums, particle_dens, targets, target_nums)
         self.dispatch_reset()
-        if matching:
-            sd = None if actions is not None else states_delta
-            loss32, g32, match32 = self._train_step32(states, sd, actions, attrs, particle_nums, particle_dens, targets,
-                                                      target_nums, 'grad', True, loss, match_weight, True)
-        elif sinkhorn and reach is not None:
-            sd = None if actions is not None else states_delta
-            loss32, g32, _, _, moved32 = self.train_step_divergence(
-                states, attrs, particle_nums, particle_dens, targets, target_nums, eps, iters, states_delta=sd, actions=actions,
-                mode='grad', want_grad=True, want_err=True, reach=reach, mass_q=mass_q)
-        elif sinkhorn:
-            sd = None if actions is not None else states_delta
-            loss32, g32 = self.train_step_divergence(states, attrs, particle_nums, particle_dens, targets, target_nums, eps, iters,
-                                                     states_delta=sd, actions=actions, mode='grad', want_grad=True)
+        # each loss: the fp32 call -> (loss32, g32, the rest); the float64 call on the rest -> (loss64, terms, g64, the rest)
+        if loss is not None:
+            run32 = lambda: self._train_step32(*five32, targets, target_nums, 'grad', True, loss, match_weight, True)
+            run64 = lambda match32: self.train_grad_f64_match(*seven64, loss, match_weight, actions=actions, match_in=match32,
+                                                              want_info=True)
+        elif eps is not None:
+            more = {} if reach is None else {'reach': reach, 'mass_q': mass_q}
+            run32 = lambda: self.train_step_divergence(*six, eps, iters, states_delta=five32[1], actions=actions, mode='grad',
+                                                       want_grad=True, want_err=reach is not None, **more)
+            run64 = lambda *_: self.train_grad_f64_divergence(*seven64, eps, iters, actions=actions, want_err=True, **more)
         else:
-            loss32, g32, _ = self._train_step32(states, states_delta, actions, attrs, particle_nums, particle_dens, targets,
-                                                target_nums, 'grad', True)
+            run32 = lambda: self._train_step32(states, states_delta, actions, *five32[3:], targets, target_nums, 'grad', True)
+            run64 = lambda _: self._train_grad64(states, states_delta, actions, *five32[3:], targets, target_nums, False)[:4]
+        loss32, g32, *rest32 = run32()
         # the fp32 matrix engine's tape is the only user of k_aggregate_tape (pick_tape_engine: selected, or after a range refusal)
         tape = 'mfma' if 'k_aggregate_tape' in self.last_dispatch() else 'fused'
-        if matching:
-            loss64, _, g64, info = self.train_grad_f64_match(states, states_delta, attrs, particle_nums, particle_dens, targets,
-                                                             target_nums, loss, match_weight, actions=actions, match_in=match32,
-                                                             want_info=True)
-        elif sinkhorn and reach is not None:
-            loss64, _, g64, col_err, self_err, moved64 = self.train_grad_f64_divergence(
-                states, states_delta, attrs, particle_nums, particle_dens, targets, target_nums, eps, iters, actions=actions,
-                want_err=True, reach=reach, mass_q=mass_q)
-        elif sinkhorn:
-            loss64, _, g64, col_err, self_err = self.train_grad_f64_divergence(
-                states, states_delta, attrs, particle_nums, particle_dens, targets, target_nums, eps, iters, actions=actions,
-                want_err=True)
-        else:
-            loss64, _, g64, margin, _ = self._train_grad64(states, states_delta, actions, attrs, particle_nums, particle_dens,
-                                                           targets, target_nums, False)
-
-        def compare(g64):
-            tensors, off, worst = {}, 0, None
-            for key, shape in STATE_DICT_KEYS:
-                n = int(np.prod(shape))
-                err = np.abs(g32[off:off + n].astype(np.float64) - g64[off:off + n])
-                err = float(np.where(np.isnan(err), np.inf, err).max())
-                ref = float(np.abs(g64[off:off + n]).max())
-                tensors[key] = {'max_abs_err': err, 'max_abs_ref': ref, 'rel': err / max(ref, 1e-300)}
-                if worst is None or tensors[key]['rel'] > tensors[worst]['rel']:
-                    worst = key
-                off += n
-            return tensors, worst
-
-        tensors, worst = compare(g64)
+        loss64, _, g64, *rest64 = run64(*rest32)
+        tensors, worst = _compare_blobs(g32, g64)
         out = {'tensors': tensors, 'worst': worst, 'rel': tensors[worst]['rel'], 'loss32': loss32, 'loss64': loss64,
                'loss_diff': abs(loss32 - loss64), 'tape': tape}
-        if chamfer:
-            out['loss_kind'], out['min_margin'] = 'chamfer', float(margin.min())
-        if sinkhorn:
-            out['loss_kind'], out['col_err'], out['self_err'] = 'sinkhorn', float(col_err.max()), float(self_err.max())
-            if reach is not None:
-                out['reach'], out['transported'] = True, float(moved64.min())
-                out['transported_diff'] = float(np.abs(moved32 - moved64).max())
-        if matching:
+        if loss is not None:
+            match32, info = rest32[0], rest64[0]
             differ = info['match'] != match32
             out['loss_kind'] = loss
             out['flipped'], out['rows_flipped'] = int(differ.any(axis=2).sum()), int(differ.sum())
@@ -1475,10 +1424,16 @@ class Engine(object):
             if info['chamfer_margin'] is not None:
                 out['min_margin'] = float(info['chamfer_margin'].min())
             if out['flipped'] > 0:
-                own = self.train_grad_f64_match(states, states_delta, attrs, particle_nums, particle_dens, targets, target_nums,
-                                                loss, match_weight, actions=actions)
-                t_own, w_own = compare(own[2])
+                own = self.train_grad_f64_match(*seven64, loss, match_weight, actions=actions)
+                t_own, w_own = _compare_blobs(g32, own[2])
                 out['rel_own'] = t_own[w_own]['rel']
+        elif eps is not None:
+            out['loss_kind'], out['col_err'], out['self_err'] = 'sinkhorn', float(rest64[0].max()), float(rest64[1].max())
+            if reach is not None:
+                out['reach'], out['transported'] = True, float(rest64[2].min())
+                out['transported_diff'] = float(np.abs(rest32[2] - rest64[2]).max())
+        elif targets is not None:
+            out['loss_kind'], out['min_margin'] = 'chamfer', float(rest64[0].min())
         return out
 
     def train_set_lr(self, lr):

@@ -13,6 +13,7 @@ in `drp_train_step` on the MI355X; nothing here computes on the host.  Data load
 (`dataset/dataset_gnn_dyn.py`: depth PNGs, pickled actions) is outside the path: `datasets`
 is any pair of iterables of samples shaped like `ParticleDataset.__getitem__`'s return.
 """
+import collections
 import os
 
 import numpy as np
@@ -202,23 +203,36 @@ def refuse_custom_probe(loss, option):
                          % (option, getattr(loss, '__name__', repr(loss))))
 
 
+def _check_schedule(row, loss, every, sinkhorn_reach_scale=None):
+    """One probe schedule of train() / main() by its row of SCHEDULES; every: {option: its value} for the row's own option and
+    its companions.  The schedule is a non-negative integer; given (> 0), it refuses a loss that is not the row's -- a callable
+    one by name, for a built-in row --, any companion beside it, and a missing reach where the row needs one."""
+    k = every[row.option]
+    if int(k) != k or k < 0:
+        raise ValueError('%s must be a non-negative integer, got %r' % (row.option, k))
+    if k > 0:
+        if row.losses is not None:
+            refuse_custom_probe(loss, row.option)
+        if any(every[c] > 0 for c in row.companions):
+            raise ValueError('give %s alone, not with %s or %s' % (row.option, ', '.join(row.companions[:-1]), row.companions[-1]))
+        if not callable(loss) if row.losses is None else loss not in row.losses:
+            raise ValueError('%s needs %s, got %r: probe_every probes the losses of %s'
+                             % (row.option, 'a callable loss' if row.losses is None else 'a loss of %s' % (row.losses,), loss, LOSSES))
+        if row.needs_reach and sinkhorn_reach_scale is None:
+            raise ValueError('%s needs sinkhorn_reach_scale: sinkhorn_probe_every probes the balanced divergence' % row.option)
+
+
 def check_custom_probe_option(loss, custom_probe_every, grad_probe_every=0, probe_every=0, sinkhorn_probe_every=0, match_probe_every=0,
                               sinkhorn_reach_probe_every=0):
     """custom_probe_every of train() / main(): the probe schedule of a callable loss alone (probe_batch_custom), and no companion of
     the five other schedules -- each of which refuses a callable loss, naming it"""
-    for option, every in (('grad_probe_every', grad_probe_every), ('probe_every', probe_every),
-                          ('sinkhorn_probe_every', sinkhorn_probe_every), ('match_probe_every', match_probe_every),
-                          ('sinkhorn_reach_probe_every', sinkhorn_reach_probe_every)):
-        if every > 0:
+    row = SCHEDULES['custom_probe_every']
+    every = dict(zip(row.companions, (grad_probe_every, probe_every, sinkhorn_probe_every, match_probe_every,
+                                      sinkhorn_reach_probe_every)), custom_probe_every=custom_probe_every)
+    for option in row.companions:
+        if every[option] > 0:
             refuse_custom_probe(loss, option)
-    if int(custom_probe_every) != custom_probe_every or custom_probe_every < 0:
-        raise ValueError('custom_probe_every must be a non-negative integer, got %r' % (custom_probe_every,))
-    if custom_probe_every > 0:
-        if grad_probe_every > 0 or probe_every > 0 or sinkhorn_probe_every > 0 or match_probe_every > 0 or sinkhorn_reach_probe_every > 0:
-            raise ValueError('give custom_probe_every alone, not with grad_probe_every, probe_every, sinkhorn_probe_every, '
-                             'match_probe_every or sinkhorn_reach_probe_every')
-        if not callable(loss):
-            raise ValueError('custom_probe_every needs a callable loss, got %r: probe_every probes the losses of %s' % (loss, LOSSES))
+    _check_schedule(row, loss, every)
 
 
 def refuse_match_probe(loss):
@@ -268,6 +282,51 @@ def batch_actions(data):
     return _np(actions)
 
 
+class _LossSpec(object):
+    """A run's loss and its options, checked once (check_loss, check_sinkhorn_options): what run_batch, the probe_batch*
+    functions and train() read instead of carrying the six values each."""
+
+    def __init__(self, loss, match_weight=0.5, transport_eps_scale=TRANSPORT_EPS_SCALE, transport_iters=TRANSPORT_ITERS,
+                 sinkhorn_reach_scale=None, sinkhorn_mass='unit', sinkhorn_probe_every=0):
+        check_loss(loss, match_weight, transport_eps_scale, transport_iters)
+        check_sinkhorn_options(loss, sinkhorn_reach_scale, sinkhorn_mass, sinkhorn_probe_every, transport_eps_scale)
+        self.loss, self.match_weight, self.eps_scale, self.iters = loss, match_weight, transport_eps_scale, transport_iters
+        self.reach_scale, self.mass = sinkhorn_reach_scale, sinkhorn_mass
+
+    def eps(self, b):
+        return transport_eps(b.dens, self.eps_scale)
+
+    def reach_args(self, b):
+        """the unbalanced divergence's keywords of the engine's calls on a batch; none without a reach"""
+        if self.reach_scale is None:
+            return {}
+        return {'reach': sinkhorn_reach(b.dens, self.reach_scale), 'mass_q': sinkhorn_mass_q(self.mass, b.nums, b.tnums)}
+
+
+class _Batch(object):
+    """A collated batch as the engine's trainer calls take it, for a loss and an impulse source (both checked against the
+    batch): states, states_delta (None where the batch has none), attrs, nums, dens; actions for impulses='actions', else None;
+    sd: states_delta, None beside actions; targets, tnums for a loss that trains on target clouds, else None.  The model's
+    weights are claimed for the context (models share the process's)."""
+
+    def __init__(self, model, data, loss, impulses):
+        if impulses not in IMPULSES:
+            raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
+        check_depth_only(data, loss, impulses)
+        self.actions = batch_actions(data) if impulses == 'actions' else None
+        self.states, self.attrs, self.nums, self.dens = _np(data[0]), _np(data[2]), _np(data[3], np.int32), _np(data[4])
+        self.states_delta = None if data[1] is None else _np(data[1])
+        self.sd = None if self.actions is not None else self.states_delta
+        untracked = not callable(loss) and loss in UNTRACKED_LOSSES + DIVERGENCE_LOSSES
+        self.targets, self.tnums = (_np(data[6]), _np(data[7], np.int32)) if untracked else (None, None)
+        if hasattr(model, '_claim'):
+            model._claim()
+
+    def probe(self, model, states_delta, **kw):
+        return model.engine.train_gradient_probe(self.states, states_delta, self.attrs, self.nums, self.dens, actions=self.actions,
+                                                 **kw)
+
+
 def run_batch(model, optimizer, data, phase='train', n_rollout=None, loss='mse', impulses='data', match_weight=0.5,
               transport_eps_scale=TRANSPORT_EPS_SCALE, transport_iters=TRANSPORT_ITERS, sinkhorn_reach_scale=None,
               sinkhorn_mass='unit', stats=None):
@@ -287,61 +346,32 @@ def run_batch(model, optimizer, data, phase='train', n_rollout=None, loss='mse',
     'transported': the mean over the batch's problems of the share of the predicted mass the plan pairs with something.
     A CALLABLE loss: loss(pred, context) -> (value, d value / d pred) of losses.py, trained through Engine.train_step_custom
     with `data` itself as the context, on either impulse source and, with impulses='actions', on depth_only batches too."""
-    check_loss(loss, match_weight, transport_eps_scale, transport_iters)
-    check_sinkhorn_options(loss, sinkhorn_reach_scale, sinkhorn_mass, 0, transport_eps_scale)
-    if impulses not in IMPULSES:
-        raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
-    check_depth_only(data, loss, impulses)
-    states, states_delta, attrs, particle_nums, particle_dens = [data[i] for i in range(5)]
-    actions = batch_actions(data) if impulses == 'actions' else None
-    states = _np(states)
-    B, length, n_obj, _ = states.shape
-    if n_rollout is not None:
-        assert length == n_rollout + 1                  # :166 (n_history = 1)
+    spec = _LossSpec(loss, match_weight, transport_eps_scale, transport_iters, sinkhorn_reach_scale, sinkhorn_mass)
     mode = 'update' if phase == 'train' else 'eval'
+    b = _Batch(model, data, loss, impulses)
+    if n_rollout is not None:
+        assert b.states.shape[1] == n_rollout + 1       # :166 (n_history = 1)
     if hasattr(model, '_claim'):
-        model._claim()                                  # models share the process's context: this one's weights in
         model._device_ahead = model._device_ahead or mode == 'update'
+    engine, four, source = model.engine, (b.states, b.attrs, b.nums, b.dens), {'states_delta': b.sd, 'actions': b.actions}
     if callable(loss):
-        value, _ = model.engine.train_step_custom(loss, states, _np(attrs), _np(particle_nums, np.int32), _np(particle_dens),
-                                                  states_delta=None if actions is not None else _np(states_delta), actions=actions,
-                                                  mode=mode, context=data)
-        return value
+        return engine.train_step_custom(loss, *four, mode=mode, context=data, **source)[0]
     if loss in MATCH_LOSSES:
-        value, _ = model.engine.train_step_loss(states, _np(attrs), _np(particle_nums, np.int32), _np(particle_dens), _np(data[6]),
-                                                _np(data[7], np.int32), states_delta=None if actions is not None else _np(states_delta),
-                                                actions=actions, loss=loss, match_weight=match_weight, mode=mode)
-        return value
+        return engine.train_step_loss(*four, b.targets, b.tnums, loss=loss, match_weight=match_weight, mode=mode, **source)[0]
     if loss in TRANSPORT_LOSSES + DIVERGENCE_LOSSES:
-        dens = _np(particle_dens)
-        if sinkhorn_reach_scale is not None:
-            nums, tnums = _np(particle_nums, np.int32), _np(data[7], np.int32)
-            out = model.engine.train_step_divergence(
-                states, _np(attrs), nums, dens, _np(data[6]), tnums, transport_eps(dens, transport_eps_scale), int(transport_iters),
-                states_delta=None if actions is not None else _np(states_delta), actions=actions, mode=mode,
-                reach=sinkhorn_reach(dens, sinkhorn_reach_scale), mass_q=sinkhorn_mass_q(sinkhorn_mass, nums, tnums),
-                want_err=stats is not None)
-            if stats is not None:
-                stats['transported'] = float(out[4].mean())
-            return out[0]
-        step = model.engine.train_step_transport if loss in TRANSPORT_LOSSES else model.engine.train_step_divergence
-        value = step(states, _np(attrs), _np(particle_nums, np.int32), dens, _np(data[6]), _np(data[7], np.int32),
-                     transport_eps(dens, transport_eps_scale), int(transport_iters),
-                     states_delta=None if actions is not None else _np(states_delta), actions=actions, mode=mode)[0]
-        return value
-    if impulses == 'actions':
-        chamfer = loss == 'chamfer'
-        value, _ = model.engine.train_step_actions(states, actions, _np(attrs), _np(particle_nums, np.int32),
-                                                   _np(particle_dens), _np(data[6]) if chamfer else None,
-                                                   _np(data[7], np.int32) if chamfer else None, mode=mode)
-        return value
+        step = engine.train_step_transport if loss in TRANSPORT_LOSSES else engine.train_step_divergence
+        reach = spec.reach_args(b)
+        if reach:
+            reach['want_err'] = stats is not None
+        out = step(*four, b.targets, b.tnums, spec.eps(b), int(spec.iters), mode=mode, **source, **reach)
+        if reach and stats is not None:
+            stats['transported'] = float(out[4].mean())
+        return out[0]
+    if b.actions is not None:
+        return engine.train_step_actions(b.states, b.actions, b.attrs, b.nums, b.dens, b.targets, b.tnums, mode=mode)[0]
     if loss == 'chamfer':
-        value, _ = model.engine.train_step_untracked(states, _np(states_delta), _np(attrs), _np(particle_nums, np.int32),
-                                                     _np(particle_dens), _np(data[6]), _np(data[7], np.int32), mode=mode)
-        return value
-    loss, _ = model.engine.train_step(states, _np(states_delta), _np(attrs), _np(particle_nums, np.int32),
-                                      _np(particle_dens), mode=mode)
-    return loss
+        return engine.train_step_untracked(b.states, b.sd, b.attrs, b.nums, b.dens, b.targets, b.tnums, mode=mode)[0]
+    return engine.train_step(b.states, b.sd, b.attrs, b.nums, b.dens, mode=mode)[0]
 
 
 class AverageMeter(object):
@@ -363,18 +393,8 @@ def probe_batch(model, data, impulses='data', loss='mse'):
     DIVERGENCE_LOSSES is refused: no yardstick yet."""
     check_loss(loss)
     refuse_match_probe(loss)
-    if impulses not in IMPULSES:
-        raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
-    check_depth_only(data, loss, impulses)
-    states, states_delta, attrs, particle_nums, particle_dens = [data[i] for i in range(5)]
-    if hasattr(model, '_claim'):
-        model._claim()
-    extra = {}
-    if loss == 'chamfer':
-        extra = {'targets': _np(data[6]), 'target_nums': _np(data[7], np.int32)}
-    return model.engine.train_gradient_probe(_np(states), None if states_delta is None else _np(states_delta), _np(attrs),
-                                             _np(particle_nums, np.int32), _np(particle_dens),
-                                             actions=batch_actions(data) if impulses == 'actions' else None, **extra)
+    b = _Batch(model, data, loss, impulses)
+    return b.probe(model, b.states_delta, **({'targets': b.targets, 'target_nums': b.tnums} if loss == 'chamfer' else {}))
 
 
 def probe_batch_custom(model, data, loss, impulses='data'):
@@ -383,16 +403,9 @@ def probe_batch_custom(model, data, loss, impulses='data'):
     the share of a finding that is the loss's own conditioning.  Weights, Adam state and iteration count are untouched."""
     if not callable(loss):
         raise ValueError('probe_batch_custom needs a callable loss, got %r' % (loss,))
-    if impulses not in IMPULSES:
-        raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
-    check_depth_only(data, loss, impulses)
-    states, states_delta, attrs, particle_nums, particle_dens = [data[i] for i in range(5)]
-    if hasattr(model, '_claim'):
-        model._claim()
-    by_actions = impulses == 'actions'
-    return model.engine.train_gradient_probe_custom(loss, _np(states), _np(attrs), _np(particle_nums, np.int32), _np(particle_dens),
-                                                    states_delta=None if by_actions else _np(states_delta),
-                                                    actions=batch_actions(data) if by_actions else None, context=data)
+    b = _Batch(model, data, loss, impulses)
+    return model.engine.train_gradient_probe_custom(loss, b.states, b.attrs, b.nums, b.dens, states_delta=b.sd, actions=b.actions,
+                                                    context=data)
 
 
 def probe_batch_sinkhorn(model, data, impulses='data', transport_eps_scale=TRANSPORT_EPS_SCALE, transport_iters=TRANSPORT_ITERS,
@@ -406,26 +419,9 @@ def probe_batch_sinkhorn(model, data, impulses='data', transport_eps_scale=TRANS
     the unbalanced divergence as run_batch takes it -- the reaches of sinkhorn_reach and the targets' masses of sinkhorn_mass_q
     -- against Engine.train_grad_f64_divergence(reach=, mass_q=); the result then also has 'reach': True, 'transported' and
     'transported_diff'."""
-    loss = DIVERGENCE_LOSSES[0]
-    check_loss(loss, 0.5, transport_eps_scale, transport_iters)
-    check_sinkhorn_options(loss, sinkhorn_reach_scale, sinkhorn_mass, 0, transport_eps_scale)
-    if impulses not in IMPULSES:
-        raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
-    check_depth_only(data, loss, impulses)
-    states, states_delta, attrs, particle_nums, particle_dens = [data[i] for i in range(5)]
-    if hasattr(model, '_claim'):
-        model._claim()
-    by_actions = impulses == 'actions'
-    dens = _np(particle_dens)
-    nums, tnums = _np(particle_nums, np.int32), _np(data[7], np.int32)
-    extra = {}
-    if sinkhorn_reach_scale is not None:
-        extra = {'reach': sinkhorn_reach(dens, sinkhorn_reach_scale), 'mass_q': sinkhorn_mass_q(sinkhorn_mass, nums, tnums)}
-    return model.engine.train_gradient_probe(_np(states), None if (by_actions or states_delta is None) else _np(states_delta),
-                                             _np(attrs), nums, dens,
-                                             actions=batch_actions(data) if by_actions else None, targets=_np(data[6]),
-                                             target_nums=tnums, eps=transport_eps(dens, transport_eps_scale),
-                                             iters=int(transport_iters), **extra)
+    spec = _LossSpec(DIVERGENCE_LOSSES[0], 0.5, transport_eps_scale, transport_iters, sinkhorn_reach_scale, sinkhorn_mass)
+    b = _Batch(model, data, spec.loss, impulses)
+    return b.probe(model, b.sd, targets=b.targets, target_nums=b.tnums, eps=spec.eps(b), iters=int(spec.iters), **spec.reach_args(b))
 
 
 def probe_batch_match(model, data, impulses='data', loss='match', match_weight=0.5):
@@ -438,45 +434,63 @@ def probe_batch_match(model, data, impulses='data', loss='match', match_weight=0
     if loss not in MATCH_LOSSES:
         raise ValueError('probe_batch_match needs a loss of %s, got %r' % (MATCH_LOSSES, loss))
     check_loss(loss, match_weight)
-    if impulses not in IMPULSES:
-        raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
-    check_depth_only(data, loss, impulses)
-    states, states_delta, attrs, particle_nums, particle_dens = [data[i] for i in range(5)]
-    if hasattr(model, '_claim'):
-        model._claim()
-    by_actions = impulses == 'actions'
-    return model.engine.train_gradient_probe(_np(states), None if (by_actions or states_delta is None) else _np(states_delta),
-                                             _np(attrs), _np(particle_nums, np.int32), _np(particle_dens),
-                                             actions=batch_actions(data) if by_actions else None, targets=_np(data[6]),
-                                             target_nums=_np(data[7], np.int32), loss=loss, match_weight=float(match_weight))
+    b = _Batch(model, data, loss, impulses)
+    return b.probe(model, b.sd, targets=b.targets, target_nums=b.tnums, loss=loss, match_weight=float(match_weight))
+
+
+# The six probe schedules of train() / main(), in the order their checks run.  option: the schedule's name; losses: the losses it
+# probes (None: a callable loss); needs_reach: only beside sinkhorn_reach_scale; companions: the schedules its "give ... alone"
+# refusal names, in the message's order; probe(model, data, impulses, spec) -> the probe's dict; suffix(pr, loss): what the
+# schedule adds to the log line.  The two oldest rows are checked as a pair by check_probe_options, which has their own refusals.
+_Schedule = collections.namedtuple('_Schedule', 'option losses needs_reach companions probe suffix')
+_OLDER = ('grad_probe_every', 'probe_every')
+
+
+def _probe_older(model, data, impulses, spec):
+    return probe_batch(model, data, impulses, spec.loss)
+
+
+def _probe_sinkhorn(model, data, impulses, spec):
+    return probe_batch_sinkhorn(model, data, impulses, spec.eps_scale, spec.iters, spec.reach_scale, spec.mass)
+
+
+def _suffix_older(pr, loss):
+    return ', min_margin %.3e' % pr['min_margin'] if loss == 'chamfer' else ''
+
+
+def _suffix_sinkhorn(pr, loss):
+    return ', col_err %.3e, self_err %.3e' % (pr['col_err'], pr['self_err'])
+
+
+SCHEDULES = collections.OrderedDict((row.option, row) for row in (
+    _Schedule('custom_probe_every', None, False, _OLDER + ('sinkhorn_probe_every', 'match_probe_every', 'sinkhorn_reach_probe_every'),
+              lambda model, data, impulses, spec: probe_batch_custom(model, data, spec.loss, impulses),
+              lambda pr, loss: ', seed_rel %.3e' % pr['seed_rel']),
+    _Schedule('grad_probe_every', ('mse',), False, (), _probe_older, _suffix_older),
+    _Schedule('probe_every', LOSSES, False, (), _probe_older, _suffix_older),
+    _Schedule('sinkhorn_probe_every', DIVERGENCE_LOSSES, False, _OLDER, _probe_sinkhorn, _suffix_sinkhorn),
+    _Schedule('match_probe_every', MATCH_LOSSES, False, _OLDER + ('sinkhorn_probe_every',),
+              lambda model, data, impulses, spec: probe_batch_match(model, data, impulses, spec.loss, spec.match_weight),
+              lambda pr, loss: ', flipped %d, cost_gap %.3e' % (pr['flipped'], pr['cost_gap'])
+              + (', rel_own %.3e' % pr['rel_own'] if 'rel_own' in pr else '')),
+    _Schedule('sinkhorn_reach_probe_every', DIVERGENCE_LOSSES, True, _OLDER + ('sinkhorn_probe_every', 'match_probe_every'),
+              _probe_sinkhorn, lambda pr, loss: _suffix_sinkhorn(pr, loss) + ', transported %.4f, transported_diff %.3e'
+              % (pr['transported'], pr['transported_diff']))))
 
 
 def check_match_probe_option(loss, match_probe_every, grad_probe_every=0, probe_every=0, sinkhorn_probe_every=0):
     """match_probe_every of train() / main(): the probe schedule of MATCH_LOSSES alone, and no companion of the three other
     schedules (check_probe_options has refused the two older ones for these losses already)"""
-    if int(match_probe_every) != match_probe_every or match_probe_every < 0:
-        raise ValueError('match_probe_every must be a non-negative integer, got %r' % (match_probe_every,))
-    if match_probe_every > 0:
-        refuse_custom_probe(loss, 'match_probe_every')
-        if grad_probe_every > 0 or probe_every > 0 or sinkhorn_probe_every > 0:
-            raise ValueError('give match_probe_every alone, not with grad_probe_every, probe_every or sinkhorn_probe_every')
-        if loss not in MATCH_LOSSES:
-            raise ValueError('match_probe_every needs a loss of %s, got %r: probe_every probes the losses of %s'
-                             % (MATCH_LOSSES, loss, LOSSES))
+    _check_schedule(SCHEDULES['match_probe_every'], loss,
+                    {'match_probe_every': match_probe_every, 'grad_probe_every': grad_probe_every, 'probe_every': probe_every,
+                     'sinkhorn_probe_every': sinkhorn_probe_every})
 
 
 def check_sinkhorn_probe_option(loss, sinkhorn_probe_every, grad_probe_every=0, probe_every=0):
     """sinkhorn_probe_every of train() / main(): the probe schedule of DIVERGENCE_LOSSES alone, and no companion of the two older
     schedules (check_probe_options has refused those for this loss already)"""
-    if int(sinkhorn_probe_every) != sinkhorn_probe_every or sinkhorn_probe_every < 0:
-        raise ValueError('sinkhorn_probe_every must be a non-negative integer, got %r' % (sinkhorn_probe_every,))
-    if sinkhorn_probe_every > 0:
-        refuse_custom_probe(loss, 'sinkhorn_probe_every')
-        if grad_probe_every > 0 or probe_every > 0:
-            raise ValueError('give sinkhorn_probe_every alone, not with grad_probe_every or probe_every')
-        if loss not in DIVERGENCE_LOSSES:
-            raise ValueError('sinkhorn_probe_every needs a loss of %s, got %r: probe_every probes the losses of %s'
-                             % (DIVERGENCE_LOSSES, loss, LOSSES))
+    _check_schedule(SCHEDULES['sinkhorn_probe_every'], loss,
+                    {'sinkhorn_probe_every': sinkhorn_probe_every, 'grad_probe_every': grad_probe_every, 'probe_every': probe_every})
 
 
 def check_sinkhorn_reach_probe_option(loss, sinkhorn_reach_probe_every, sinkhorn_reach_scale=None, grad_probe_every=0, probe_every=0,
@@ -484,19 +498,10 @@ def check_sinkhorn_reach_probe_option(loss, sinkhorn_reach_probe_every, sinkhorn
     """sinkhorn_reach_probe_every of train() / main(): the probe schedule of DIVERGENCE_LOSSES with a reach alone, and no
     companion of the four other schedules (sinkhorn_probe_every keeps refusing a reach: tests/test_divergence_unbalanced_host.py
     pins that)"""
-    if int(sinkhorn_reach_probe_every) != sinkhorn_reach_probe_every or sinkhorn_reach_probe_every < 0:
-        raise ValueError('sinkhorn_reach_probe_every must be a non-negative integer, got %r' % (sinkhorn_reach_probe_every,))
-    if sinkhorn_reach_probe_every > 0:
-        refuse_custom_probe(loss, 'sinkhorn_reach_probe_every')
-        if grad_probe_every > 0 or probe_every > 0 or sinkhorn_probe_every > 0 or match_probe_every > 0:
-            raise ValueError('give sinkhorn_reach_probe_every alone, not with grad_probe_every, probe_every, sinkhorn_probe_every or '
-                             'match_probe_every')
-        if loss not in DIVERGENCE_LOSSES:
-            raise ValueError('sinkhorn_reach_probe_every needs a loss of %s, got %r: probe_every probes the losses of %s'
-                             % (DIVERGENCE_LOSSES, loss, LOSSES))
-        if sinkhorn_reach_scale is None:
-            raise ValueError('sinkhorn_reach_probe_every needs sinkhorn_reach_scale: sinkhorn_probe_every probes the balanced '
-                             'divergence')
+    _check_schedule(SCHEDULES['sinkhorn_reach_probe_every'], loss,
+                    {'sinkhorn_reach_probe_every': sinkhorn_reach_probe_every, 'grad_probe_every': grad_probe_every,
+                     'probe_every': probe_every, 'sinkhorn_probe_every': sinkhorn_probe_every, 'match_probe_every': match_probe_every},
+                    sinkhorn_reach_scale)
 
 
 def check_probe_options(loss, grad_probe_every, probe_every):
@@ -513,6 +518,26 @@ def check_probe_options(loss, grad_probe_every, probe_every):
     if loss == 'chamfer' and grad_probe_every > 0:
         raise ValueError('grad_probe_every needs loss=\'mse\': the float64 yardstick of the gradients it pairs with is MSE-only; '
                          'probe_every probes every loss')
+
+
+def check_train_options(loss, every, match_weight=0.5, transport_eps_scale=TRANSPORT_EPS_SCALE, transport_iters=TRANSPORT_ITERS,
+                        sinkhorn_reach_scale=None, sinkhorn_mass='unit', usage_only=False):
+    """Every option check of train() / main(), in the one order that decides which refusal a caller sees when two apply; every:
+    {option: value} over SCHEDULES -> the run's _LossSpec.  usage_only: the command line's part -- what _cli() turns into a
+    usage error before anything is read or written: the loss's own options, then the reach schedule."""
+    def reach_probe():
+        _check_schedule(SCHEDULES['sinkhorn_reach_probe_every'], loss, every, sinkhorn_reach_scale)
+    if not usage_only:
+        check_custom_probe_option(loss, every['custom_probe_every'], *(every[o] for o in SCHEDULES['custom_probe_every'].companions))
+        check_probe_options(loss, every['grad_probe_every'], every['probe_every'])
+        _check_schedule(SCHEDULES['sinkhorn_probe_every'], loss, every)
+        _check_schedule(SCHEDULES['match_probe_every'], loss, every)
+        reach_probe()
+    spec = _LossSpec(loss, match_weight, transport_eps_scale, transport_iters, sinkhorn_reach_scale, sinkhorn_mass,
+                     every['sinkhorn_probe_every'])
+    if usage_only:
+        reach_probe()
+    return spec
 
 
 def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=None, first_epoch=0, grad_probe_every=0,
@@ -549,20 +574,14 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
     run_batch's loss of the caller's, every batch its own context; the five probe options above refuse it, naming it.
     custom_probe_every = k > 0: probe_every's schedule and history entry for a callable loss (probe_batch_custom); the log line
     also carries seed_rel.  It is refused with a string loss and beside any other probe option (check_custom_probe_option)."""
-    check_custom_probe_option(loss, custom_probe_every, grad_probe_every, probe_every, sinkhorn_probe_every, match_probe_every,
-                              sinkhorn_reach_probe_every)
-    check_probe_options(loss, grad_probe_every, probe_every)
-    check_sinkhorn_probe_option(loss, sinkhorn_probe_every, grad_probe_every, probe_every)
-    check_match_probe_option(loss, match_probe_every, grad_probe_every, probe_every, sinkhorn_probe_every)
-    check_sinkhorn_reach_probe_option(loss, sinkhorn_reach_probe_every, sinkhorn_reach_scale, grad_probe_every, probe_every,
-                                      sinkhorn_probe_every, match_probe_every)
-    check_loss(loss, match_weight, transport_eps_scale, transport_iters)
-    check_sinkhorn_options(loss, sinkhorn_reach_scale, sinkhorn_mass, sinkhorn_probe_every, transport_eps_scale)
+    every = {'grad_probe_every': grad_probe_every, 'probe_every': probe_every, 'sinkhorn_probe_every': sinkhorn_probe_every,
+             'match_probe_every': match_probe_every, 'sinkhorn_reach_probe_every': sinkhorn_reach_probe_every,
+             'custom_probe_every': custom_probe_every}
+    spec = check_train_options(loss, every, match_weight, transport_eps_scale, transport_iters, sinkhorn_reach_scale, sinkhorn_mass)
     if impulses not in IMPULSES:
         raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
     loss_kind = loss
-    every = max(grad_probe_every, probe_every, sinkhorn_probe_every, match_probe_every,
-                sinkhorn_reach_probe_every, custom_probe_every)                                               # (at most one of them is given)
+    schedule = next((row for row in SCHEDULES.values() if every[row.option] > 0), None)         # (at most one of them is given)
     tc = config['train']
     n_rollout = tc['n_rollout']
     assert tc['n_history'] == 1
@@ -574,32 +593,12 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
             model.train(phase == 'train')
             meter = AverageMeter()
             for i, data in enumerate(dataloaders[phase]):
-                if every > 0 and phase == 'train' and i % every == 0:
-                    if custom_probe_every > 0:
-                        pr = probe_batch_custom(model, data, loss_kind, impulses)
-                    elif sinkhorn_reach_probe_every > 0:
-                        pr = probe_batch_sinkhorn(model, data, impulses, transport_eps_scale, transport_iters, sinkhorn_reach_scale,
-                                                  sinkhorn_mass)
-                    elif sinkhorn_probe_every > 0:
-                        pr = probe_batch_sinkhorn(model, data, impulses, transport_eps_scale, transport_iters)
-                    elif match_probe_every > 0:
-                        pr = probe_batch_match(model, data, impulses, loss_kind, match_weight)
-                    else:
-                        pr = probe_batch(model, data, impulses, loss_kind)
+                if schedule is not None and phase == 'train' and i % every[schedule.option] == 0:
+                    pr = schedule.probe(model, data, impulses, spec)
                     history.append((epoch, 'grad_probe', float(pr['rel'])))
                     if log is not None:
-                        line = 'grad_probe [%d][%d] worst %s rel %.3e (%s tape), loss diff %.3e' % (epoch, i, pr['worst'], pr['rel'],
-                                                                                                  pr['tape'], pr['loss_diff'])
-                        if sinkhorn_probe_every > 0 or sinkhorn_reach_probe_every > 0:
-                            line += ', col_err %.3e, self_err %.3e' % (pr['col_err'], pr['self_err'])
-                        if sinkhorn_reach_probe_every > 0:
-                            line += ', transported %.4f, transported_diff %.3e' % (pr['transported'], pr['transported_diff'])
-                        if custom_probe_every > 0:
-                            line += ', seed_rel %.3e' % pr['seed_rel']
-                        if match_probe_every > 0:
-                            line += ', flipped %d, cost_gap %.3e' % (pr['flipped'], pr['cost_gap'])
-                            line += ', rel_own %.3e' % pr['rel_own'] if 'rel_own' in pr else ''
-                        log(line + (', min_margin %.3e' % pr['min_margin'] if loss_kind == 'chamfer' else ''))
+                        log('grad_probe [%d][%d] worst %s rel %.3e (%s tape), loss diff %.3e'
+                            % (epoch, i, pr['worst'], pr['rel'], pr['tape'], pr['loss_diff']) + schedule.suffix(pr, loss_kind))
                 logged = log is not None and i % tc['log_per_iter'] == 0
                 stats = {} if logged and sinkhorn_reach_scale is not None else None
                 loss = run_batch(model, optimizer, data, phase, n_rollout, loss=loss_kind, impulses=impulses, match_weight=match_weight,
@@ -667,15 +666,10 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
     from .dataset_gnn_dyn import DepthDataset, DeviceLoader, ParticleDataset, UntrackedLoader
     from .gnn_dyn import PropNetDiffDenModel
     loss, impulses = resolve_data_options(data, loss, impulses)
-    check_custom_probe_option(loss, custom_probe_every, grad_probe_every, probe_every, sinkhorn_probe_every, match_probe_every,
-                              sinkhorn_reach_probe_every)
-    check_probe_options(loss, grad_probe_every, probe_every)
-    check_sinkhorn_probe_option(loss, sinkhorn_probe_every, grad_probe_every, probe_every)
-    check_match_probe_option(loss, match_probe_every, grad_probe_every, probe_every, sinkhorn_probe_every)
-    check_sinkhorn_reach_probe_option(loss, sinkhorn_reach_probe_every, sinkhorn_reach_scale, grad_probe_every, probe_every,
-                                      sinkhorn_probe_every, match_probe_every)
-    check_loss(loss, match_weight, transport_eps_scale, transport_iters)
-    check_sinkhorn_options(loss, sinkhorn_reach_scale, sinkhorn_mass, sinkhorn_probe_every, transport_eps_scale)
+    every = {'grad_probe_every': grad_probe_every, 'probe_every': probe_every, 'sinkhorn_probe_every': sinkhorn_probe_every,
+             'match_probe_every': match_probe_every, 'sinkhorn_reach_probe_every': sinkhorn_reach_probe_every,
+             'custom_probe_every': custom_probe_every}
+    check_train_options(loss, every, match_weight, transport_eps_scale, transport_iters, sinkhorn_reach_scale, sinkhorn_mass)
     tc = config['train']
     resume = tc['particle'].get('resume', {'active': False, 'epoch': 0, 'iter': 0})
     if cam is None:
@@ -723,11 +717,9 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
 
         result = train(config, model, loaders, n_epoch=n_epoch, log=log, on_best=on_best, ckp=ckp,
                        first_epoch=resume['epoch'] if resume['active'] and resume['epoch'] > 0 else 0,
-                       grad_probe_every=grad_probe_every, loss=loss, impulses=impulses, probe_every=probe_every,
-                       match_weight=match_weight, transport_eps_scale=transport_eps_scale, transport_iters=transport_iters,
-                       sinkhorn_probe_every=sinkhorn_probe_every, match_probe_every=match_probe_every,
-                       sinkhorn_reach_scale=sinkhorn_reach_scale, sinkhorn_mass=sinkhorn_mass,
-                       sinkhorn_reach_probe_every=sinkhorn_reach_probe_every, custom_probe_every=custom_probe_every)
+                       loss=loss, impulses=impulses, match_weight=match_weight, transport_eps_scale=transport_eps_scale,
+                       transport_iters=transport_iters, sinkhorn_reach_scale=sinkhorn_reach_scale, sinkhorn_mass=sinkhorn_mass,
+                       **every)
         for epoch, phase, rmse in result['history']:
             if phase == 'grad_probe':                   # logged when it was taken
                 continue
@@ -817,14 +809,11 @@ def _cli(argv=None):
     try:
         if a.loss_fn is not None:
             a.loss = load_loss_fn(a.loss_fn)
-        check_custom_probe_option(a.loss, a.custom_probe_every, a.grad_probe_every, a.probe_every, a.sinkhorn_probe_every,
-                                  a.match_probe_every, a.sinkhorn_reach_probe_every)
-        check_loss(resolve_data_options(a.data, a.loss, a.impulses)[0], a.match_weight, a.transport_eps_scale, a.transport_iters)
-        check_sinkhorn_options(resolve_data_options(a.data, a.loss, a.impulses)[0], a.sinkhorn_reach_scale, a.sinkhorn_mass,
-                               a.sinkhorn_probe_every, a.transport_eps_scale)
-        check_sinkhorn_reach_probe_option(resolve_data_options(a.data, a.loss, a.impulses)[0], a.sinkhorn_reach_probe_every,
-                                          a.sinkhorn_reach_scale, a.grad_probe_every, a.probe_every, a.sinkhorn_probe_every,
-                                          a.match_probe_every)
+        every = {option: getattr(a, option) for option in SCHEDULES}
+        # (the callable's schedule on the loss as given; the rest on what --data makes of it)
+        check_custom_probe_option(a.loss, a.custom_probe_every, *(every[o] for o in SCHEDULES['custom_probe_every'].companions))
+        check_train_options(resolve_data_options(a.data, a.loss, a.impulses)[0], every, a.match_weight, a.transport_eps_scale,
+                            a.transport_iters, a.sinkhorn_reach_scale, a.sinkhorn_mass, usage_only=True)
     except ValueError as e:
         ap.error(str(e))
     config = default_config()
@@ -836,12 +825,9 @@ def _cli(argv=None):
     if a.n_timestep is not None:
         config['dataset']['n_timestep'] = a.n_timestep
     result, d = main(config, a.data_root, a.train_dir, chunk=a.chunk, threads=a.threads, n_epoch=a.epochs,
-                     grad_probe_every=a.grad_probe_every, loss=a.loss, impulses=a.impulses, probe_every=a.probe_every,
-                     data=a.data, target_den_scale=a.target_den_scale, match_weight=a.match_weight,
+                     loss=a.loss, impulses=a.impulses, data=a.data, target_den_scale=a.target_den_scale, match_weight=a.match_weight,
                      transport_eps_scale=a.transport_eps_scale, transport_iters=a.transport_iters,
-                     sinkhorn_probe_every=a.sinkhorn_probe_every, match_probe_every=a.match_probe_every,
-                     sinkhorn_reach_scale=a.sinkhorn_reach_scale, sinkhorn_mass=a.sinkhorn_mass,
-                     sinkhorn_reach_probe_every=a.sinkhorn_reach_probe_every, custom_probe_every=a.custom_probe_every)
+                     sinkhorn_reach_scale=a.sinkhorn_reach_scale, sinkhorn_mass=a.sinkhorn_mass, **every)
     print('best valid loss %.6f, checkpoints in %s' % (np.sqrt(result['best_valid_loss']), d))
 
 

@@ -5,12 +5,21 @@
 Run at two commits on one machine, the two outputs are compared line by line: a refactor of the loss kernels' arguments, of the
 one-shots' staging or of the trainers' entry points moves no line.  Only public methods of Engine are called, so the script runs
 unchanged at either commit.  The cases:
-  one-shots   cloud_chamfer, cloud_chamfer_f64, cloud_match, every optional output, on one context in this order of (B, N, M):
-              (3, 70, 130), (2, 5, 3), (1, 65, 64), (1, 1, 1), (1, 64, 64)
+  one-shots   cloud_chamfer, cloud_chamfer_f64, cloud_match, cloud_match_f64 (its own matching, and match_in = cloud_match's),
+              cloud_transport, cloud_divergence and cloud_divergence_f64 (balanced, and with reach / mass_q / want_transported),
+              every optional output, on one context in this order of (B, N, M): (3, 70, 130), (2, 5, 3), (1, 65, 64), (1, 1, 1),
+              (1, 64, 64); eps is a per-sample array where B > 1 and a number where B = 1
   fp32        the fixture batch b2_r5 (data impulses) and the push batches tiny and mask (tests/_train_actions_ref.py), every loss
-              kind their entry points take; mode='grad' (loss, blob, matches), then two mode='update' steps and get_weights();
-              on the selected tape and with the `mfma` engine selected
-  float64     train_grad_f64 / _actions / _untracked on the same batches: loss, terms, blob, margin"""
+              kind their entry points take -- train_step_transport, train_step_divergence (balanced and with a reach, want_err),
+              train_predict + train_step_seeded and train_step_custom(losses.mse_loss) among them; mode='grad' (loss, blob, the
+              call's other outputs), then two mode='update' steps and get_weights(); on the selected tape and with the `mfma`
+              engine selected
+  float64     train_grad_f64 / _actions / _untracked, train_grad_f64_divergence (both ways), train_grad_f64_match (its own
+              matching, and match_in = the fp32 side's), train_predict_f64 and train_grad_f64_seeded on the same batches: every
+              output
+  probes      train_gradient_probe with no targets, targets, eps / iters, eps / iters / reach, loss='match', 'chamfer+match', and
+              train_gradient_probe_custom, on the same batches: every scalar of the dict by repr in sorted key order, the
+              per-tensor table hashed"""
 import hashlib
 import os
 import sys
@@ -21,11 +30,14 @@ import numpy as np
 
 import _train_actions_ref as A
 import _untracked_ref as U
-from dyn_res_pile_manip_amd import weights
+from dyn_res_pile_manip_amd import losses, weights
 from dyn_res_pile_manip_amd.engine import Engine
 
 ONE_SHOTS = (((70, 130, 70, 130), 3), ((5, 3, 5, 3), 2), ((65, 60, 65, 64), 1), ((1, 1, 1, 1), 1), ((64, 64, 64, 64), 1))
 MIX = 0.3
+EPS = 4e-4                  # the one-shots' regularisation strength: the clouds' squared spacing (tests/_untracked_ref.chamfer_case)
+ITERS = 50
+REACH_PER_EPS = 4.0         # reach = 4 eps, one-shots and trainers alike: two spacings
 
 
 class Golden(object):
@@ -47,13 +59,38 @@ def one_shots():
                           ('cloud_match', eng.cloud_match(*case, want_grad=True, want_match=True, want_dual=True))):
             for k in sorted(out):
                 show('%s B=%d N=%d M=%d %s' % (name, B, shape[2], shape[3], k), out[k])
+        p, q, n_p, n_q = case
+        eps = EPS * (1.0 + 0.5 * np.arange(B)) if B > 1 else EPS
+        mass_q = np.clip(n_q / n_p.astype(np.float64), 0.125, 8.0)
+        want = {'want_grad': True, 'want_dual': True, 'want_col_err': True}
+        div = dict(want, want_self_err=True)
+        reach = dict(div, reach=REACH_PER_EPS * np.asarray(eps), mass_q=mass_q if B > 1 else float(mass_q[0]), want_transported=True)
+        pairs = eng.cloud_match(*case, want_match=True)['match_pq']
+        for name, out in (('cloud_transport', eng.cloud_transport(*case, eps=eps, iters=ITERS, **want)),
+                          ('cloud_divergence', eng.cloud_divergence(*case, eps=eps, iters=ITERS, **div)),
+                          ('cloud_divergence reach', eng.cloud_divergence(*case, eps=eps, iters=ITERS, **reach)),
+                          ('cloud_divergence_f64', eng.cloud_divergence_f64(*case, eps=eps, iters=ITERS, **div)),
+                          ('cloud_divergence_f64 reach', eng.cloud_divergence_f64(*case, eps=eps, iters=ITERS, **reach)),
+                          ('cloud_match_f64', eng.cloud_match_f64(*case, want_grad=True, want_match=True, want_dual=True)),
+                          ('cloud_match_f64 match_in', eng.cloud_match_f64(*case, match_in=pairs, want_grad=True, want_match=True,
+                                                                           want_dual=True))):
+            for k in sorted(out):
+                show('%s B=%d N=%d M=%d %s' % (name, B, shape[2], shape[3], k), out[k])
     eng.close()
 
 
+def sinkhorn_args(five, tnums):
+    """the trainers' eps [B], reach [B] and mass_q [n_rollout, B] of a batch, as train_gnn_dyn forms them at scale 1 and reach 4"""
+    dens, nums = np.asarray(five[4], np.float64).reshape(-1), np.asarray(five[3], np.float64).reshape(-1, 1)
+    eps = 1.0 / dens
+    return eps, REACH_PER_EPS * eps, np.ascontiguousarray(np.clip(np.asarray(tnums, np.float64) / nums, 0.125, 8.0).T)
+
+
 def fp32_steps(golden, name, five, by_actions, targets, tnums):
-    """label -> a step at the given mode, for every loss kind the batch's entry points take"""
+    """label -> a step at the given mode, for every loss kind the batch's entry points take: (loss, blob, further outputs)"""
     states, imp, attrs, nums, dens = five
     imp_kw = {'actions': imp} if by_actions else {'states_delta': imp}
+    eps, reach, mass_q = sinkhorn_args(five, tnums)
     steps = {}
     if by_actions:
         steps['train_step_actions mse'] = lambda e, mode: e.train_step_actions(*five, mode=mode, want_grad=True)
@@ -67,7 +104,33 @@ def fp32_steps(golden, name, five, by_actions, targets, tnums):
         steps['train_step_loss ' + kind] = (lambda e, mode, kind=kind: e.train_step_loss(
             states, attrs, nums, dens, targets, tnums, loss=kind, match_weight=MIX, mode=mode, want_grad=True, want_match=True,
             **imp_kw))
+    six = (states, attrs, nums, dens, targets, tnums)
+    steps['train_step_transport'] = lambda e, mode: e.train_step_transport(*six, eps, ITERS, mode=mode, want_grad=True,
+                                                                           want_col_err=True, **imp_kw)
+    steps['train_step_divergence'] = lambda e, mode: e.train_step_divergence(*six, eps, ITERS, mode=mode, want_grad=True,
+                                                                             want_err=True, **imp_kw)
+    steps['train_step_divergence reach'] = lambda e, mode: e.train_step_divergence(
+        *six, eps, ITERS, mode=mode, want_grad=True, want_err=True, reach=reach, mass_q=mass_q, **imp_kw)
+    steps['train_step_divergence reach scalar'] = lambda e, mode: e.train_step_divergence(
+        *six, float(eps[0]), ITERS, mode=mode, want_grad=True, reach=float(reach[0]), **imp_kw)
+    steps['train_step_custom mse_loss'] = lambda e, mode: e.train_step_custom(losses.mse_loss, states, attrs, nums, dens, mode=mode,
+                                                                              want_grad=True, context=five, **imp_kw)
+
+    def seeded(e, mode):
+        pred = e.train_predict(states, attrs, nums, dens, **imp_kw)
+        value, seed = losses.mse_loss(pred, five)
+        return value, e.train_step_seeded(states, attrs, nums, dens, seed, mode=mode, want_grad=True, **imp_kw), pred
+    steps['train_predict train_step_seeded'] = seeded
     return steps
+
+
+def show_probe(tag, pr):
+    """a probe's dict: every scalar by repr in sorted key order, the per-tensor table hashed"""
+    for k in sorted(pr):
+        if k != 'tensors':
+            print('%s %s = %r' % (tag, k, pr[k]))
+    show(tag + ' tensors', np.array([[pr['tensors'][key][f] for f in ('max_abs_err', 'max_abs_ref', 'rel')]
+                                     for key in sorted(pr['tensors'])], np.float64))
 
 
 def trainers(golden):
@@ -93,6 +156,8 @@ def trainers(golden):
                 show(tag + ' grad blob', out[1])
                 if len(out) > 2 and out[2] is not None:
                     show(tag + ' grad match', out[2])
+                for k in range(3, len(out)):
+                    show(tag + ' grad out %d' % k, out[k])
                 for it in range(2):
                     show(tag + ' update %d loss' % it, np.float64(step(eng, 'update')[0]))
                 show(tag + ' weights', eng.get_weights())
@@ -110,6 +175,43 @@ def trainers(golden):
         for label, out in calls:
             for k, v in zip(('loss', 'terms', 'blob', 'margin'), out):
                 show('%s %s %s' % (name, label, k), np.float64(v) if k == 'loss' else v)
+        # the yardsticks of the targeted losses and of a caller's loss: states_delta positionally (None beside actions)
+        sd, act = (None, imp) if by_actions else (imp, None)
+        imp_kw = {'actions': imp} if by_actions else {'states_delta': imp}
+        seven64 = (states, sd, attrs, nums, dens, targets, tnums)
+        eps, reach, mass_q = sinkhorn_args(five, tnums)
+        eng.train_begin(H, 1e-3, 0.9)
+        match32 = eng.train_step_loss(states, attrs, nums, dens, targets, tnums, loss='match', mode='grad', want_match=True,
+                                      **imp_kw)[2]
+        pred64 = eng.train_predict_f64(states, attrs, nums, dens, **imp_kw)
+        calls = (('train_grad_f64_divergence', eng.train_grad_f64_divergence(*seven64, eps, ITERS, actions=act, want_state=True,
+                                                                             want_err=True)),
+                 ('train_grad_f64_divergence reach', eng.train_grad_f64_divergence(*seven64, eps, ITERS, actions=act, want_state=True,
+                                                                                   want_err=True, reach=reach, mass_q=mass_q)),
+                 ('train_grad_f64_divergence reach scalar', eng.train_grad_f64_divergence(*seven64, float(eps[0]), ITERS, actions=act,
+                                                                                          reach=float(reach[0]))),
+                 ('train_grad_f64_match', eng.train_grad_f64_match(*seven64, actions=act, want_state=True, want_info=True)),
+                 ('train_grad_f64_match mix', eng.train_grad_f64_match(*seven64, 'chamfer+match', MIX, actions=act, want_info=True)),
+                 ('train_grad_f64_match match_in', eng.train_grad_f64_match(*seven64, actions=act, match_in=match32, want_info=True)),
+                 ('train_predict_f64', (pred64,)),
+                 ('train_grad_f64_seeded', eng.train_grad_f64_seeded(states, attrs, nums, dens, losses.mse_loss(pred64, five)[1],
+                                                                     want_state=True, **imp_kw)))
+        for label, out in calls:
+            for k, v in enumerate(out):
+                for key, item in (sorted(v.items()) if isinstance(v, dict) else (('', v),)):
+                    if item is not None:
+                        show('%s %s out %d %s' % (name, label, k, key), item)
+        probes = (('mse', {}), ('chamfer', {'targets': targets, 'target_nums': tnums}),
+                  ('sinkhorn', {'targets': targets, 'target_nums': tnums, 'eps': eps, 'iters': ITERS}),
+                  ('sinkhorn reach', {'targets': targets, 'target_nums': tnums, 'eps': eps, 'iters': ITERS, 'reach': reach,
+                                      'mass_q': mass_q}),
+                  ('match', {'targets': targets, 'target_nums': tnums, 'loss': 'match'}),
+                  ('chamfer+match', {'targets': targets, 'target_nums': tnums, 'loss': 'chamfer+match', 'match_weight': MIX}))
+        for label, kw in probes:
+            show_probe('%s train_gradient_probe %s' % (name, label), eng.train_gradient_probe(states, sd, attrs, nums, dens, actions=act,
+                                                                                              **kw))
+        show_probe('%s train_gradient_probe_custom' % name, eng.train_gradient_probe_custom(losses.mse_loss, states, attrs, nums, dens,
+                                                                                             context=five, **imp_kw))
         eng.close()
 
 

@@ -20,8 +20,8 @@
 // check on double rows.  The matching losses' float64 yardstick: the caller's partners [H][B][N] behind the float64 upload
 // (tr64_layout with `match_in`), drp_cloud_match_f64's buffer of its own (match64_layout, with and without match_in), and the
 // check of a matching given by the caller (check_matching) on arrays of exactly [N].  The unbalanced Sinkhorn divergence:
-// divergence_unbalanced_layout (eps | rho | mass_q side by side, the scratch, transported, inside a block of exactly its `bytes`,
-// the five blocks that come back where divergence_layout has them), the trainer's rho [B] | mass_q [H][B] behind eps (tr_layout
+// divergence_layout with `reach` (eps | rho | mass_q side by side, the scratch, transported, inside a block of exactly its `bytes`,
+// the five blocks that come back where they are without it, no rho or mass_q without it), the trainer's rho [B] | mass_q [H][B] behind eps (tr_layout
 // with `reach`) and transported behind its doubles (tr_div_loss_layout with `unbalanced`), nothing ahead of them moved, and the
 // check of a reach and a target mass (check_reach) at the edges of its ranges.  Its float64 yardstick: rho [B] | mass_q [H][B]
 // (doubles) behind eps in the float64 upload (tr64_layout with `reach`), and drp_cloud_divergence_unbalanced_f64's buffer
@@ -451,12 +451,12 @@ static void stage_div_loss(int B, int H, int N) {
     for (int k = 0; k < 5; ++k) EXPECT(d[off[k]] == (double)k && d[off[k + 1] - 1] == (double)k);
     std::free(d);
 }
-// drp_cloud_divergence_unbalanced: divergence_layout's five blocks where they were; behind them eps | rho | mass_q [B] each, side
+// drp_cloud_divergence_unbalanced (divergence_layout with `reach`): the five blocks where they were; behind them eps | rho | mass_q [B] each, side
 // by side (one copy up), the same scratch, then transported [B], all inside a block of exactly `bytes`
 static void stage_divergence_unbalanced(int B, int N, int M) {
     const size_t bn = (size_t)B * N;
-    const DivUnbalancedLayout lay = divergence_unbalanced_layout(B, N, M);
-    const DivLayout plain = divergence_layout(B, N, M);
+    const DivLayout lay = divergence_layout(B, N, M, true), plain = divergence_layout(B, N, M);
+    EXPECT(plain.rho == 0 && plain.mass_q == 0 && plain.transported == 0 && plain.vals < lay.vals);
     for (int k = 0; k < CLOUD_MAX_OUT; ++k) EXPECT(lay.cloud.out[k] == plain.cloud.out[k] && lay.cloud.out_bytes[k] == plain.cloud.out_bytes[k]);
     EXPECT(lay.cloud.in_bytes == plain.cloud.in_bytes && lay.cloud.n_out == plain.cloud.n_out && lay.eps == plain.eps);
     EXPECT(lay.rho == lay.eps + (size_t)B * 8 && lay.mass_q == lay.rho + (size_t)B * 8);
