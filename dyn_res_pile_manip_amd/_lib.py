@@ -262,6 +262,11 @@ SIGNATURES = {
                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int, c_float_p, c_int32_p, ctypes.c_int,
                                                 ctypes.c_int, ctypes.c_double, c_int32_p, c_double_p, c_double_p, c_double_p,
                                                 c_double_p, c_int32_p, c_double_p, c_double_p]),
+    'drp_train_accumulate': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double]),
+    'drp_train_apply': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, ctypes.c_double, c_double_p, c_double_p,
+                                       ctypes.POINTER(ctypes.c_int), c_float_p]),
+    'drp_train_get_state': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, ctypes.POINTER(ctypes.c_int64)]),
+    'drp_train_set_state': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_int64]),
 }
 
 _lib = None

@@ -131,6 +131,7 @@ int drp_load_weights(drp_ctx* c, const float* blob, size_t n_floats, double adj_
     // arrives as the double it is there -- squaring its fp32 rounding gives another threshold at 0.05, 0.1, 0.7
     c->thr = (float)(adj_thresh * adj_thresh);
     c->have_weights = true;
+    c->tr_grad_fresh = false;             // a gradient taken at the old weights is nothing drp_train_accumulate may add
     return DRP_OK;
 }
 

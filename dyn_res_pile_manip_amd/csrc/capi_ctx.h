@@ -278,6 +278,13 @@ struct drp_ctx {
     bool wgrad_defer = true;        // DRP_NO_WGRAD_DEFER=1 turns the deferred weight gradients off
     DevBuf tr_grad, tr_m, tr_v, tr_loss, agg_hist, tr_hact, tr_gh, tr_gpe, tr_a1n,
         tr_gh1, tr_xn, ed_re, ed_a2, ed_a1, ed_x0, ed_gce, ed_g3, ed_g2, ed_g1;
+    // the optimiser seam (capi_optim.h: drp_train_accumulate, drp_train_apply); allocated by drp_train_begin
+    DevBuf tr_acc;                  // the float64 accumulator [W_TOTAL]
+    DevBuf tr_opt;                  // ko_norm_partial's partials [KO_BLOCKS(W_TOTAL)] doubles, then ko_norm_final's KoStep
+    DevBuf tr_g32;                  // the scaled, clipped gradient the last drp_train_apply stepped on [W_TOTAL]
+    PinBuf opt_pin;                 // pinned: the KoStep of the last drp_train_apply, written by ko_norm_final
+    bool tr_grad_fresh = false;     // tr_grad holds the gradient of a DRP_TRAIN_GRAD pass that returned DRP_OK and has not been accumulated
+    int tr_acc_n = 0;               // passes accumulated since the last drp_train_apply / drp_train_begin
 
     // goal pre-processing (row f3)
     DevBuf gl_goal, gl_seg, gl_tmp, gl_dist, gl_blk, gl_pix, gl_fps;

@@ -430,6 +430,17 @@ int install_weights(drp_ctx* c, const std::vector<float>& blob) {
     std::vector<float> tmp(blob);
     return drp_load_weights(c, tmp.data(), tmp.size(), c->adj_thresh);
 }
+
+// the optimiser seam's buffers (capi_optim.h) at their one size, the accumulator zeroed: launches only, drp_train_begin waits
+int optim_begin(drp_ctx* c) {
+    const size_t n_part = (size_t)KO_BLOCKS((int)W_TOTAL);
+    CHK(ensure(c, c->tr_acc, (size_t)W_TOTAL * sizeof(double)));
+    CHK(ensure(c, c->tr_opt, n_part * sizeof(double) + sizeof(KoStep)));
+    CHK(ensure(c, c->tr_g32, (size_t)W_TOTAL * sizeof(float)));
+    CHK(ensure_pinned(c, c->opt_pin, sizeof(KoStep)));      // one size for the context's life: never replaced
+    HIPCHK(c, hipMemsetAsync(c->tr_acc.p, 0, (size_t)W_TOTAL * sizeof(double), c->stream));
+    return DRP_OK;
+}
 }  // namespace
 
 int drp_train_begin(drp_ctx* c, int n_rollout, double lr, double beta1) {
@@ -443,8 +454,10 @@ int drp_train_begin(drp_ctx* c, int n_rollout, double lr, double beta1) {
     CHK(ensure(c, c->wgrad->tr_part, (size_t)KT_WGRAD_MAX_JOBS * KT_WGRAD_MAX_BLOCKS * 66 * 64 * sizeof(float)));
     HIPCHK(c, hipMemsetAsync(c->tr_m.p, 0, (size_t)W_TOTAL * sizeof(float), c->stream));
     HIPCHK(c, hipMemsetAsync(c->tr_v.p, 0, (size_t)W_TOTAL * sizeof(float), c->stream));
+    CHK(optim_begin(c));                // the optimiser seam's accumulator, zeroed (capi_optim.h)
     CHK(guarded_wait(c, nullptr));
     c->tr_nroll = n_rollout; c->tr_lr = lr; c->tr_beta1 = beta1; c->tr_iter = 0;
+    c->tr_grad_fresh = false; c->tr_acc_n = 0;
     c->tr_on = true;
     c->gd_on = false;
     c->mpc_on = false;
@@ -640,6 +653,7 @@ int train_attempt(drp_ctx* c, int B, int N, const TrainPass& tp, int mode, bool 
 int train_step_body(drp_ctx* c, const float* states, const float* impulses, bool actions, const float* attrs,
                     const int32_t* particle_nums, const float* particle_dens, int B, int N, const TrLoss& lk, int mode,
                     double* loss_out, float* grad_out, float* pred_out = nullptr /* drp_train_predict: the forward alone */) {
+    if (c) c->tr_grad_fresh = false;    // every trainer pass, refused ones included, ends what drp_train_accumulate could take
     CHK(train_check_args(c, states, impulses, actions, attrs, particle_nums, particle_dens, B, N, lk, mode));
     HIPCHK(c, hipSetDevice(c->device));
     end_sessions(c);
@@ -686,6 +700,7 @@ int train_step_body(drp_ctx* c, const float* states, const float* impulses, bool
         for (size_t q = 0; q < (size_t)H * B; ++q) total += back[q];
         *loss_out = total;
     }
+    c->tr_grad_fresh = mode == DRP_TRAIN_GRAD && !tp.predict;       // tr_grad is whole and the weights are where it was taken
     return drain.ok();
 }
 }  // namespace
@@ -719,6 +734,7 @@ int drp_train_step_loss(drp_ctx* c, const float* states, const float* states_del
                         const int32_t* target_nums, int M, int loss_kind, double match_weight, int mode, double* loss_out,
                         float* grad_out, int32_t* match_out) {
     if (!c) return DRP_EINVAL;
+    c->tr_grad_fresh = false;
     ImpulseSource src;
     CHK(impulse_source(c, states_delta, actions, src));
     if (loss_kind != DRP_LOSS_CHAMFER && loss_kind != DRP_LOSS_MATCH && loss_kind != DRP_LOSS_CHAMFER_MATCH)
@@ -733,6 +749,7 @@ int drp_train_step_loss(drp_ctx* c, const float* states, const float* states_del
 int drp_train_predict(drp_ctx* c, const float* states, const float* states_delta, const float* actions, const float* attrs,
                       const int32_t* particle_nums, const float* particle_dens, int B, int N, float* states_pred_out) {
     if (!c) return DRP_EINVAL;
+    c->tr_grad_fresh = false;
     ImpulseSource src;
     CHK(impulse_source(c, states_delta, actions, src));
     if (!states_pred_out) return fail(c, DRP_EINVAL, "null argument");
@@ -746,6 +763,7 @@ int drp_train_step_seeded(drp_ctx* c, const float* states, const float* states_d
                           const int32_t* particle_nums, const float* particle_dens, int B, int N, const float* seed, int mode,
                           float* grad_out) {
     if (!c) return DRP_EINVAL;
+    c->tr_grad_fresh = false;
     ImpulseSource src;
     CHK(impulse_source(c, states_delta, actions, src));
     TrLoss lk;

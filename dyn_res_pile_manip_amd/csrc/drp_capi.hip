@@ -38,6 +38,7 @@
 #include "k_particles.h"
 #include "k_goal.h"
 #include "k_train.h"
+#include "k_optim.h"
 #include "k_mlp_mfma.h"
 #include "k_mlp_split.h"
 #include "k_backward_mfma.h"
@@ -70,6 +71,7 @@ extern "C" {
 #include "capi_prep.h"
 #include "capi_gd.h"
 #include "capi_train.h"
+#include "capi_optim.h"
 #include "capi_chamfer.h"
 #include "capi_match.h"
 #include "capi_transport.h"

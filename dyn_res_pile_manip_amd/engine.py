@@ -1439,6 +1439,37 @@ class Engine(object):
     def train_set_lr(self, lr):
         self._ck(self.lib.drp_train_set_lr(self.h, float(lr)))
 
+    # ---- the optimiser seam behind mode='grad' (include/drp.h: drp_train_accumulate, drp_train_apply) -----------------------
+    def train_accumulate(self, weight=1.0):
+        """Add weight x the gradient of the last trainer pass -- a mode='grad' call of any train_step* method that succeeded -- to
+        the float64 accumulator on the device.  A pass is accumulated once; an integer weight (a sample count) is exact."""
+        self._ck(self.lib.drp_train_accumulate(self.h, float(weight)))
+
+    def train_apply(self, scale=1.0, max_norm=None, want_grad=False):
+        """One Adam step on scale x the accumulated gradient, clipped to the global norm max_norm as torch's clip_grad_norm_ does
+        (None: no clipping); the accumulator is cleared -> {'norm': || scale x accumulator ||_2 before clipping, 'clip': the
+        factor applied (1.0: none), 'applied': False when the norm was not finite and nothing moved, 'grad': the float32 gradient
+        the step was taken on [38403], or None}."""
+        norm, clip, applied = ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
+        grad = np.empty((L.DRP_N_WEIGHTS,), np.float32) if want_grad else None
+        self._ck(self.lib.drp_train_apply(self.h, float(scale), float('inf') if max_norm is None else float(max_norm),
+                                          ctypes.byref(norm), ctypes.byref(clip), ctypes.byref(applied), _opt(_fp, grad)))
+        return {'norm': norm.value, 'clip': clip.value, 'applied': bool(applied.value), 'grad': grad}
+
+    def train_get_state(self):
+        """Adam's state -> (m [38403] float32, v [38403] float32, the steps taken), in get_weights' layout."""
+        m, v = np.empty((L.DRP_N_WEIGHTS,), np.float32), np.empty((L.DRP_N_WEIGHTS,), np.float32)
+        it = ctypes.c_int64()
+        self._ck(self.lib.drp_train_get_state(self.h, _fp(m), _fp(v), ctypes.byref(it)))
+        return m, v, int(it.value)
+
+    def train_set_state(self, m, v, iter):
+        """train_get_state's triple back in (after train_begin): the next update continues where that run stood."""
+        m, v = _f32(m).reshape(-1), _f32(v).reshape(-1)
+        if m.size != L.DRP_N_WEIGHTS or v.size != L.DRP_N_WEIGHTS:
+            raise ValueError('m and v must hold %d floats each' % L.DRP_N_WEIGHTS)
+        self._ck(self.lib.drp_train_set_state(self.h, _fp(m), _fp(v), int(iter)))
+
     def get_weights(self):
         blob = np.empty((L.DRP_N_WEIGHTS,), np.float32)
         self._ck(self.lib.drp_get_weights(self.h, _fp(blob), blob.size))

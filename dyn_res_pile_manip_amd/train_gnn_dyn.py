@@ -94,6 +94,15 @@ class DeviceAdam(object):
         self.param_groups[0]['lr'] = float(lr)
         self.model.engine.train_set_lr(lr)
 
+    def state_dict(self):
+        """Adam's moments and step count as the engine holds them (Engine.train_get_state): {'m', 'v': float32 [38403] in
+        get_weights' layout, 'iter': int} -- with the weights, all a resumed run needs to continue with an uninterrupted one's bits"""
+        m, v, it = self.model.engine.train_get_state()
+        return {'m': m, 'v': v, 'iter': it}
+
+    def load_state_dict(self, state):
+        self.model.engine.train_set_state(state['m'], state['v'], int(state['iter']))
+
 
 LOSSES = ('mse', 'chamfer')
 # the one-to-one matching loss of Engine.cloud_match and its mix with the Chamfer distance (Engine.train_step_loss): they train as
@@ -329,7 +338,7 @@ class _Batch(object):
 
 def run_batch(model, optimizer, data, phase='train', n_rollout=None, loss='mse', impulses='data', match_weight=0.5,
               transport_eps_scale=TRANSPORT_EPS_SCALE, transport_iters=TRANSPORT_ITERS, sinkhorn_reach_scale=None,
-              sinkhorn_mass='unit', stats=None):
+              sinkhorn_mass='unit', stats=None, mode=None):
     """The loop body at train/train_gnn_dyn.py:159-210 -> loss (python float, what loss.item() is there).  loss='chamfer': `data`
     is collate_untracked's (targets and target_nums behind the six fields) and each step's term is the Chamfer distance to its
     target cloud (Engine.train_step_untracked).  A batch marked depth_only (DepthDataset) is refused (ValueError) unless
@@ -345,9 +354,12 @@ def run_batch(model, optimizer, data, phase='train', n_rollout=None, loss='mse',
     particle_dens[b] and the targets' masses of sinkhorn_mass_q (check_sinkhorn_options); `stats`, a dict, then receives
     'transported': the mean over the batch's problems of the share of the predicted mass the plan pairs with something.
     A CALLABLE loss: loss(pred, context) -> (value, d value / d pred) of losses.py, trained through Engine.train_step_custom
-    with `data` itself as the context, on either impulse source and, with impulses='actions', on depth_only batches too."""
+    with `data` itself as the context, on either impulse source and, with impulses='actions', on depth_only batches too.
+    mode (None: 'update' for phase 'train', else 'eval'): 'grad' runs the same call with the weights untouched and the
+    gradient left on the device for Engine.train_accumulate -- train()'s accum_steps / clip_norm path."""
     spec = _LossSpec(loss, match_weight, transport_eps_scale, transport_iters, sinkhorn_reach_scale, sinkhorn_mass)
-    mode = 'update' if phase == 'train' else 'eval'
+    if mode is None:
+        mode = 'update' if phase == 'train' else 'eval'
     b = _Batch(model, data, loss, impulses)
     if n_rollout is not None:
         assert b.states.shape[1] == n_rollout + 1       # :166 (n_history = 1)
@@ -520,11 +532,21 @@ def check_probe_options(loss, grad_probe_every, probe_every):
                          'probe_every probes every loss')
 
 
+def check_optim_options(accum_steps=1, clip_norm=None):
+    """accum_steps and clip_norm of train() / main(): an integer number of batches >= 1 per optimiser step, and None or a positive
+    global-norm bound (inf: measured and logged, never clipped)"""
+    if isinstance(accum_steps, bool) or int(accum_steps) != accum_steps or accum_steps < 1:
+        raise ValueError('accum_steps must be an integer >= 1, got %r' % (accum_steps,))
+    if clip_norm is not None and not float(clip_norm) > 0.0:
+        raise ValueError('clip_norm must be a number > 0 (or None: no clipping), got %r' % (clip_norm,))
+
+
 def check_train_options(loss, every, match_weight=0.5, transport_eps_scale=TRANSPORT_EPS_SCALE, transport_iters=TRANSPORT_ITERS,
-                        sinkhorn_reach_scale=None, sinkhorn_mass='unit', usage_only=False):
+                        sinkhorn_reach_scale=None, sinkhorn_mass='unit', usage_only=False, accum_steps=1, clip_norm=None):
     """Every option check of train() / main(), in the one order that decides which refusal a caller sees when two apply; every:
     {option: value} over SCHEDULES -> the run's _LossSpec.  usage_only: the command line's part -- what _cli() turns into a
-    usage error before anything is read or written: the loss's own options, then the reach schedule."""
+    usage error before anything is read or written: the loss's own options, then the reach schedule.  accum_steps and clip_norm
+    (check_optim_options) come last: every older refusal is seen as before."""
     def reach_probe():
         _check_schedule(SCHEDULES['sinkhorn_reach_probe_every'], loss, every, sinkhorn_reach_scale)
     if not usage_only:
@@ -537,13 +559,15 @@ def check_train_options(loss, every, match_weight=0.5, transport_eps_scale=TRANS
                      every['sinkhorn_probe_every'])
     if usage_only:
         reach_probe()
+    check_optim_options(accum_steps, clip_norm)
     return spec
 
 
 def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=None, first_epoch=0, grad_probe_every=0,
           loss='mse', impulses='data', probe_every=0, match_weight=0.5, transport_eps_scale=TRANSPORT_EPS_SCALE,
           transport_iters=TRANSPORT_ITERS, sinkhorn_probe_every=0, match_probe_every=0, sinkhorn_reach_scale=None,
-          sinkhorn_mass='unit', sinkhorn_reach_probe_every=0, custom_probe_every=0):
+          sinkhorn_mass='unit', sinkhorn_reach_probe_every=0, custom_probe_every=0, accum_steps=1, clip_norm=None,
+          optimizer_state=None, on_optimizer=None):
     """train/train_gnn_dyn.py:134-246 without the file I/O: `dataloaders` = {'train': iterable of
     collated batches, 'valid': ...}.  Returns {'best_valid_loss', 'history': [(epoch, phase, rmse)]}.
     ckp(epoch, i, model): called after training batch i when i % ckp_per_iter == 0 (:217-218); first_epoch: the epoch
@@ -573,11 +597,24 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
     with any other loss and beside any of the four other probe options (check_sinkhorn_reach_probe_option).  A CALLABLE loss:
     run_batch's loss of the caller's, every batch its own context; the five probe options above refuse it, naming it.
     custom_probe_every = k > 0: probe_every's schedule and history entry for a callable loss (probe_batch_custom); the log line
-    also carries seed_rel.  It is refused with a string loss and beside any other probe option (check_custom_probe_option)."""
+    also carries seed_rel.  It is refused with a string loss and beside any other probe option (check_custom_probe_option).
+    accum_steps = k, clip_norm = c (check_optim_options): with the defaults (1, None) the loop is the one above, call for call.
+    Otherwise every training batch runs with mode='grad' on whichever call the run's loss uses (a callable loss included) and its
+    gradient is accumulated on the device with weight B, its sample count (Engine.train_accumulate); after every k batches, and
+    at the end of the phase for a remainder, one Adam step is taken on the sum times 1 / (the group's samples), clipped to the
+    global norm c as torch's clip_grad_norm_ does (Engine.train_apply) -- the gradient of the mean loss over the group's
+    samples.  clip_norm with accum_steps=1 is the same path with groups of one.  The log line of a batch that ends a group
+    gets ', GradNorm %.6f, Clip %.4f' appended (a remainder group, applied behind the phase's last batch, logs a line of its
+    own); an update skipped because its norm was not finite is logged once and counted in the result's 'skipped_updates' (a
+    key the result has on this path only).  The probe schedules run as they do: they probe a batch before its pass.  ckp fires
+    on its schedule even mid-group and then saves the weights as they stood before the open group.  The valid phase and the
+    history's format are untouched.  optimizer_state: a DeviceAdam.state_dict() loaded before the first batch (a resumed run);
+    on_optimizer(epoch, i, optimizer): called right behind every ckp call (main's --save-optimizer)."""
     every = {'grad_probe_every': grad_probe_every, 'probe_every': probe_every, 'sinkhorn_probe_every': sinkhorn_probe_every,
              'match_probe_every': match_probe_every, 'sinkhorn_reach_probe_every': sinkhorn_reach_probe_every,
              'custom_probe_every': custom_probe_every}
-    spec = check_train_options(loss, every, match_weight, transport_eps_scale, transport_iters, sinkhorn_reach_scale, sinkhorn_mass)
+    spec = check_train_options(loss, every, match_weight, transport_eps_scale, transport_iters, sinkhorn_reach_scale, sinkhorn_mass,
+                               accum_steps=accum_steps, clip_norm=clip_norm)
     if impulses not in IMPULSES:
         raise ValueError('impulses must be one of %s, got %r' % (IMPULSES, impulses))
     loss_kind = loss
@@ -586,12 +623,29 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
     n_rollout = tc['n_rollout']
     assert tc['n_history'] == 1
     optimizer = DeviceAdam(model, float(tc['lr']), betas=(tc['adam_beta1'], 0.999), n_rollout=n_rollout)
+    if optimizer_state is not None:
+        optimizer.load_state_dict(optimizer_state)
+    grouped = int(accum_steps) > 1 or clip_norm is not None
+    skipped = [0]
+
+    def apply_group(n_samples, where):
+        """one optimiser step on the open group's accumulated gradient -> the log line's suffix"""
+        out = model.engine.train_apply(scale=1.0 / n_samples, max_norm=clip_norm)
+        if hasattr(model, '_claim'):
+            model._device_ahead = model._device_ahead or out['applied']
+        if not out['applied']:
+            skipped[0] += 1
+            if log is not None:
+                log('train %s update skipped: GradNorm %r is not finite, nothing moved' % (where, out['norm']))
+        return ', GradNorm %.6f, Clip %.4f' % (out['norm'], out['clip'])
+
     best_valid_loss = np.inf
     history = []
     for epoch in range(int(first_epoch), n_epoch if n_epoch is not None else tc['n_epoch']):
         for phase in ('train', 'valid'):
             model.train(phase == 'train')
             meter = AverageMeter()
+            group_batches, group_samples = 0, 0
             for i, data in enumerate(dataloaders[phase]):
                 if schedule is not None and phase == 'train' and i % every[schedule.option] == 0:
                     pr = schedule.probe(model, data, impulses, spec)
@@ -601,22 +655,40 @@ def train(config, model, dataloaders, n_epoch=None, log=None, on_best=None, ckp=
                             % (epoch, i, pr['worst'], pr['rel'], pr['tape'], pr['loss_diff']) + schedule.suffix(pr, loss_kind))
                 logged = log is not None and i % tc['log_per_iter'] == 0
                 stats = {} if logged and sinkhorn_reach_scale is not None else None
+                in_group = grouped and phase == 'train'
                 loss = run_batch(model, optimizer, data, phase, n_rollout, loss=loss_kind, impulses=impulses, match_weight=match_weight,
                                  transport_eps_scale=transport_eps_scale, transport_iters=transport_iters,
-                                 sinkhorn_reach_scale=sinkhorn_reach_scale, sinkhorn_mass=sinkhorn_mass, stats=stats)
+                                 sinkhorn_reach_scale=sinkhorn_reach_scale, sinkhorn_mass=sinkhorn_mass, stats=stats,
+                                 **({'mode': 'grad'} if in_group else {}))
                 meter.update(loss, _np(data[0]).shape[0])
+                applied = ''
+                if in_group:
+                    model.engine.train_accumulate(_np(data[0]).shape[0])
+                    group_batches, group_samples = group_batches + 1, group_samples + _np(data[0]).shape[0]
+                    if group_batches == int(accum_steps):
+                        applied = apply_group(group_samples, '[%d][%d]' % (epoch, i))
+                        group_batches, group_samples = 0, 0
                 if logged:
                     log('%s [%d][%d] LR: %.6f, Loss: %.6f (%.6f)' % (phase, epoch, i, optimizer.param_groups[0]['lr'],
                                                                       np.sqrt(loss), np.sqrt(meter.avg))
-                        + (', transported %.4f' % stats['transported'] if stats is not None else ''))
+                        + (', transported %.4f' % stats['transported'] if stats is not None else '') + applied)
                 if ckp is not None and phase == 'train' and i % tc['ckp_per_iter'] == 0:
                     ckp(epoch, i, model)
+                    if on_optimizer is not None:
+                        on_optimizer(epoch, i, optimizer)
+            if group_batches:                   # the phase's remainder: fewer than accum_steps batches, applied now
+                applied = apply_group(group_samples, '[%d] (the last %d batches)' % (epoch, group_batches))
+                if log is not None:
+                    log('train [%d] the last %d batches applied%s' % (epoch, group_batches, applied))
             history.append((epoch, phase, float(np.sqrt(meter.avg))))
             if phase == 'valid' and meter.avg < best_valid_loss:
                 best_valid_loss = meter.avg
                 if on_best is not None:
                     on_best(model.state_dict())           # torch.save(model.state_dict(), net_best.pth), :244
-    return {'best_valid_loss': float(best_valid_loss), 'history': history}
+    result = {'best_valid_loss': float(best_valid_loss), 'history': history}
+    if grouped:
+        result['skipped_updates'] = skipped[0]
+    return result
 
 
 def default_config():
@@ -643,7 +715,8 @@ def set_seed(seed):
 def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8, n_epoch=None, engine=None, grad_probe_every=0,
          loss=None, impulses=None, probe_every=0, data='particles', target_den_scale=1.0, match_weight=0.5,
          transport_eps_scale=TRANSPORT_EPS_SCALE, transport_iters=TRANSPORT_ITERS, sinkhorn_probe_every=0, match_probe_every=0,
-         sinkhorn_reach_scale=None, sinkhorn_mass='unit', sinkhorn_reach_probe_every=0, custom_probe_every=0):
+         sinkhorn_reach_scale=None, sinkhorn_mass='unit', sinkhorn_reach_probe_every=0, custom_probe_every=0, accum_steps=1,
+         clip_norm=None, save_optimizer=False):
     """The file-level part of train/train_gnn_dyn.py:train() (:45-130, :196-228): seed, the log directory with config.yaml
     and log.txt, the 'train' / 'valid' ParticleDatasets and their DeviceLoaders, a fresh model (torch.nn.Linear's default
     initialisation) or the resumed checkpoint, net_epoch_%d_iter_%d.pth every ckp_per_iter training batches and
@@ -659,7 +732,11 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
     impulses None: 'mse' / 'data', or what data implies.  loss in MATCH_LOSSES (with match_weight for the mix): as 'chamfer', on
     particles or depth; loss in TRANSPORT_LOSSES or DIVERGENCE_LOSSES (with transport_eps_scale and transport_iters) likewise.  chunk None: the
     dataset's default (64 samples; 16 for data='depth').  sinkhorn_reach_scale, sinkhorn_mass, sinkhorn_reach_probe_every: train's.
-    A callable loss and custom_probe_every: train's (tracked batches, or with data='depth' the depth batches through the push)."""
+    A callable loss and custom_probe_every: train's (tracked batches, or with data='depth' the depth batches through the push).
+    accum_steps, clip_norm: train's.  save_optimizer: every net_epoch_%d_iter_%d.pth gets an opt_epoch_%d_iter_%d.npz beside it
+    (DeviceAdam.state_dict(): m, v, iter); off by default, so the files a run writes are what they were.  A resumed run loads the
+    .npz of its checkpoint when it is there (whatever save_optimizer says) and then continues with Adam's moments and step count
+    instead of zeros."""
     import time
     import yaml
     from . import synthetic, weights
@@ -669,7 +746,8 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
     every = {'grad_probe_every': grad_probe_every, 'probe_every': probe_every, 'sinkhorn_probe_every': sinkhorn_probe_every,
              'match_probe_every': match_probe_every, 'sinkhorn_reach_probe_every': sinkhorn_reach_probe_every,
              'custom_probe_every': custom_probe_every}
-    check_train_options(loss, every, match_weight, transport_eps_scale, transport_iters, sinkhorn_reach_scale, sinkhorn_mass)
+    check_train_options(loss, every, match_weight, transport_eps_scale, transport_iters, sinkhorn_reach_scale, sinkhorn_mass,
+                        accum_steps=accum_steps, clip_norm=clip_norm)
     tc = config['train']
     resume = tc['particle'].get('resume', {'active': False, 'epoch': 0, 'iter': 0})
     if cam is None:
@@ -694,6 +772,7 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
         loaders = {ph: UntrackedLoader(loaders[ph], seed=tc['random_seed'] + k, reseed=(ph == 'valid'))
                    for k, ph in enumerate(('train', 'valid'))}
     model = PropNetDiffDenModel(config, engine=engine)
+    optimizer_state = None
     if impulses == 'actions':
         from .planners import world2cam_affine
         gs = float(config['dataset']['global_scale'])
@@ -701,6 +780,10 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
     if resume['active']:
         path = os.path.join(train_dir, 'net_epoch_%d_iter_%d.pth' % (resume['epoch'], resume['iter']))
         model.load_state_dict(weights.state_dict_from_blob(weights.load_checkpoint(path)))
+        opt_path = os.path.join(train_dir, 'opt_epoch_%d_iter_%d.npz' % (resume['epoch'], resume['iter']))
+        if os.path.exists(opt_path):
+            with np.load(opt_path) as z:
+                optimizer_state = {'m': z['m'], 'v': z['v'], 'iter': int(z['iter'])}
     else:
         model.load_state_dict(weights.random_state_dict(seed=tc['random_seed'], predictor_scale=1.0))
     with open(os.path.join(train_dir, log_name), 'w') as log_fout:
@@ -715,11 +798,18 @@ def main(config, data_root=None, train_dir=None, cam=None, chunk=None, threads=8
         def on_best(sd):
             weights.save_checkpoint(sd, os.path.join(train_dir, 'net_best.pth'))
 
+        def on_optimizer(epoch, i, optimizer):
+            np.savez(os.path.join(train_dir, 'opt_epoch_%d_iter_%d.npz' % (epoch, i)), **optimizer.state_dict())
+
+        if optimizer_state is not None:
+            log('resumed Adam\'s state after %d steps (opt_epoch_%d_iter_%d.npz)' % (optimizer_state['iter'], resume['epoch'], resume['iter']))
+
         result = train(config, model, loaders, n_epoch=n_epoch, log=log, on_best=on_best, ckp=ckp,
                        first_epoch=resume['epoch'] if resume['active'] and resume['epoch'] > 0 else 0,
                        loss=loss, impulses=impulses, match_weight=match_weight, transport_eps_scale=transport_eps_scale,
                        transport_iters=transport_iters, sinkhorn_reach_scale=sinkhorn_reach_scale, sinkhorn_mass=sinkhorn_mass,
-                       **every)
+                       accum_steps=accum_steps, clip_norm=clip_norm, optimizer_state=optimizer_state,
+                       on_optimizer=on_optimizer if save_optimizer else None, **every)
         for epoch, phase, rmse in result['history']:
             if phase == 'grad_probe':                   # logged when it was taken
                 continue
@@ -801,6 +891,13 @@ def _cli(argv=None):
     ap.add_argument('--sinkhorn-mass', choices=SINKHORN_MASSES, default='unit',
                     help='--sinkhorn-reach-scale: the target cloud\'s total mass against the prediction\'s 1 -- unit: 1; count: its '
                          'point count over the prediction\'s, equal mass per point (targets sampled at the particles\' spacing)')
+    ap.add_argument('--accum-steps', type=int, default=1, metavar='k',
+                    help='one optimiser step per k training batches, on the gradient of the mean loss over their samples (accumulated '
+                         'in float64 on the device); a remainder is applied at the end of the phase')
+    ap.add_argument('--clip-norm', type=float, default=None, metavar='c',
+                    help='clip every update\'s gradient to the global 2-norm c (torch\'s clip_grad_norm_); the log carries GradNorm and Clip')
+    ap.add_argument('--save-optimizer', action='store_true',
+                    help='write opt_epoch_E_iter_I.npz (Adam\'s m, v, iter) beside every net_epoch_E_iter_I.pth; a resumed run loads it when it is there')
     ap.add_argument('--impulses', choices=IMPULSES, default=None,
                     help='(default data) actions: compute every step\'s impulse from the recorded push on the state the model predicted')
     a = ap.parse_args(argv)
@@ -813,7 +910,8 @@ def _cli(argv=None):
         # (the callable's schedule on the loss as given; the rest on what --data makes of it)
         check_custom_probe_option(a.loss, a.custom_probe_every, *(every[o] for o in SCHEDULES['custom_probe_every'].companions))
         check_train_options(resolve_data_options(a.data, a.loss, a.impulses)[0], every, a.match_weight, a.transport_eps_scale,
-                            a.transport_iters, a.sinkhorn_reach_scale, a.sinkhorn_mass, usage_only=True)
+                            a.transport_iters, a.sinkhorn_reach_scale, a.sinkhorn_mass, usage_only=True, accum_steps=a.accum_steps,
+                            clip_norm=a.clip_norm)
     except ValueError as e:
         ap.error(str(e))
     config = default_config()
@@ -827,7 +925,8 @@ def _cli(argv=None):
     result, d = main(config, a.data_root, a.train_dir, chunk=a.chunk, threads=a.threads, n_epoch=a.epochs,
                      loss=a.loss, impulses=a.impulses, data=a.data, target_den_scale=a.target_den_scale, match_weight=a.match_weight,
                      transport_eps_scale=a.transport_eps_scale, transport_iters=a.transport_iters,
-                     sinkhorn_reach_scale=a.sinkhorn_reach_scale, sinkhorn_mass=a.sinkhorn_mass, **every)
+                     sinkhorn_reach_scale=a.sinkhorn_reach_scale, sinkhorn_mass=a.sinkhorn_mass, accum_steps=a.accum_steps,
+                     clip_norm=a.clip_norm, save_optimizer=a.save_optimizer, **every)
     print('best valid loss %.6f, checkpoints in %s' % (np.sqrt(result['best_valid_loss']), d))
 
 

@@ -1106,6 +1106,44 @@ int drp_train_grad_f64_seeded(drp_ctx* ctx, const float* states, const float* st
                               const float* particle_dens, int B, int N, int n_rollout, const double* seed /*[B][H][N][3]*/,
                               double* grad_out, double* grad_state_out);
 
+/* ---- the optimiser seam: accumulate gradients, clip by global norm, keep Adam's state -----------------------------------------
+ * Every drp_train_step* entry point ends in the same optimiser: one Adam step on that one call's gradient.  With mode
+ * DRP_TRAIN_GRAD each of them leaves its gradient on the device and the weights untouched; these four calls are what comes behind
+ * it, once for all of them.  They change no existing call.  The context keeps a "fresh gradient" mark: a DRP_TRAIN_GRAD pass of
+ * any entry point that returns DRP_OK sets it; drp_train_accumulate clears it, and so does everything that writes the gradient
+ * buffer or ends training -- every drp_train_step* call in any mode (refused ones included), drp_train_predict, drp_train_begin,
+ * drp_train_apply and drp_load_weights.
+ *
+ * drp_train_accumulate: acc[i] += weight * (double)grad[i] over the 38 403 entries of a float64 accumulator on the device, which
+ * drp_train_begin allocates and zeroes; grad is the last pass's gradient where it lies (no host copy, no wait).  A pass can be
+ * accumulated once.  An integer weight up to 2^29 times an fp32 value is exact in double (24 + 29 bits), so an accumulator fed
+ * sample counts is the exact sum of the weighted gradients in call order, rounded once per addition -- what the trainer uses
+ * (weight = B, then scale = 1 / sum B).  DRP_ESTATE without drp_train_begin or without a fresh gradient; DRP_EINVAL for a weight
+ * that is not finite or not > 0.
+ *
+ * drp_train_apply: s0 = scale; norm = || s0 acc ||_2 in double, reduced in a fixed order without atomics (the same bits from run
+ * to run); clip = min(1, max_norm / (norm + 1e-6)), torch's clip_grad_norm_ (max_norm = +inf: no clipping, clip = 1); s = s0 *
+ * clip, one double product; g32[i] = (float)(acc[i] * s); one Adam step on g32 with drp_train_step's arithmetic and bias
+ * corrections; the device re-pack of drp_train_step; the accumulator zeroed and the iteration count advanced.  One host wait; the
+ * norm does not come to the host between the reduction and the Adam launch.  With weight 1, scale 1 and no clipping the weights,
+ * Adam's moments and the iteration count have the bits DRP_TRAIN_UPDATE leaves on the same batch.  A norm that is not finite
+ * (decided on the device) moves nothing: weights, moments, iteration count and packed copies keep their bits, the accumulator is
+ * still cleared, *applied_out = 0 and the call returns DRP_OK.  A step that is applied ends the planner sessions, as every update
+ * does; a skipped one ends none.  norm_out, clip_out, applied_out and grad_out [38 403] (g32, in
+ * drp_get_weights' layout) are nullable.  DRP_ESTATE without drp_train_begin or with nothing accumulated since the last
+ * drp_train_apply / drp_train_begin; DRP_EINVAL for a scale that is not finite or not > 0 and for max_norm NaN or <= 0.  A
+ * refused call leaves the context as it was.
+ *
+ * drp_train_get_state / drp_train_set_state: Adam's m and v (38 403 floats each, drp_get_weights' layout) and the number of
+ * steps taken, so that a resumed run continues with the bits of an uninterrupted one.  The accumulator is no part of the state.
+ * Both need drp_train_begin (DRP_ESTATE); set_state refuses a value that is not finite, a negative v and a negative iter with
+ * DRP_EINVAL and then changes nothing. */
+int drp_train_accumulate(drp_ctx* ctx, double weight);
+int drp_train_apply(drp_ctx* ctx, double scale, double max_norm /* +inf: no clipping */, double* norm_out, double* clip_out,
+                    int* applied_out, float* grad_out /* nullable, 38 403 */);
+int drp_train_get_state(drp_ctx* ctx, float* m_out, float* v_out, int64_t* iter_out);
+int drp_train_set_state(drp_ctx* ctx, const float* m, const float* v, int64_t iter);
+
 #ifdef __cplusplus
 }
 #endif
