@@ -276,6 +276,12 @@ struct drp_ctx {
     std::vector<float> w_host;
     std::unique_ptr<WgradQueue> wgrad;      // the weight-gradient jobs of a backward pass and their buffers (capi_pipeline.h; from drp_create on)
     bool wgrad_defer = true;        // DRP_NO_WGRAD_DEFER=1 turns the deferred weight gradients off
+    bool wgrad_tap_on = false;      // the operands of the last deferred pass still lie where its jobs read them (capi_debug.h:
+                                    // "train_wgrad_*"); set by a trainer pass that returned DRP_OK, cleared by whatever may write them next
+    // INVARIANT of the "train_wgrad_*" taps: whatever writes (or re-allocates) an operand of the deferred weight-gradient jobs --
+    // agg_hist, tr_hact .. tr_xn and ed_* here; eff_hist, g_eff, g_proj, g_cnode, g_state and ws.dens elsewhere in this struct --
+    // clears wgrad_tap_on first.  Today every such writer stages a step through ensure_step_ws (capi_pipeline.h), which clears
+    // it; a new writer that does not go through there must clear it itself.
     DevBuf tr_grad, tr_m, tr_v, tr_loss, agg_hist, tr_hact, tr_gh, tr_gpe, tr_a1n,
         tr_gh1, tr_xn, ed_re, ed_a2, ed_a1, ed_x0, ed_gce, ed_g3, ed_g2, ed_g1;
     // the optimiser seam (capi_optim.h: drp_train_accumulate, drp_train_apply); allocated by drp_train_begin

@@ -154,8 +154,62 @@ int drp_debug_stall(drp_ctx* c, int ms) {
     return DRP_OK;
 }
 
+// The weight-gradient sums of the last trainer pass that deferred them (WgradQueue::flush_all), read-only: `what` is the
+// name behind "train_wgrad_".  "jobs": one record of WGRAD_TAP_FIELDS int64 per job in queue order -- M, in, rows_per_sample,
+// dens_mod, blocks, lane_stride, k_stride, the offsets in floats of dW, db and dwd inside the gradient blob (-1: null), whether
+// the densities are read -- and one more for the kt_colsum3 call (M, and its target as the db offset; in = 3, the rest 0 / -1).
+// No device pointer leaves.  "g:<q>" / "x:<q>": job q's operand rows, dense [M][64] / [M][in] float32 whatever ldg / ldx are;
+// "g:<jobs>": the colsum's [M][3].  "dens": the density vector the jobs read.  Valid while c->wgrad_tap_on (capi_ctx.h).
+constexpr int WGRAD_TAP_FIELDS = 11;
+static long fetch_wgrad_tap(drp_ctx* c, const char* what, const char* name, void* out, size_t out_bytes) {
+    const WgradQueue& wq = *c->wgrad;
+    if (!c->wgrad_tap_on || wq.tap_jobs.empty() || !wq.tap_G)
+        return fail(c, DRP_ESTATE, "buffer '%s' not populated (the last trainer call ran no reverse pass with deferred weight gradients, "
+                                   "or a later call has reused its buffers)", name);
+    const long n = (long)wq.tap_jobs.size();
+    const void* src = nullptr;
+    size_t width = 0, pitch = 0, rows = 0;              // bytes of a dense row, bytes between rows on the device, rows
+    if (!strcmp(what, "jobs")) {
+        const size_t bytes = (size_t)(n + 1) * WGRAD_TAP_FIELDS * sizeof(int64_t);
+        if (out_bytes < bytes) return fail(c, DRP_EINVAL, "buffer '%s' needs %zu bytes", name, bytes);
+        int64_t* r = static_cast<int64_t*>(out);
+        auto off = [&](const float* p) -> int64_t { return p ? (int64_t)(p - wq.tap_G) : -1; };
+        for (long q = 0; q < n; ++q, r += WGRAD_TAP_FIELDS) {
+            const WgradJob& j = wq.tap_jobs[q];
+            r[0] = j.M; r[1] = j.in; r[2] = j.rows_per_sample; r[3] = j.dens_mod; r[4] = j.blocks; r[5] = j.lane_stride; r[6] = j.k_stride;
+            r[7] = off(j.dW); r[8] = off(j.db); r[9] = off(j.dwd); r[10] = (j.dwd && j.dens) ? 1 : 0;
+        }
+        r[0] = wq.tap_cs_M; r[1] = 3; r[2] = 0; r[3] = 0; r[4] = 0; r[5] = 0; r[6] = 0;
+        r[7] = -1; r[8] = (int64_t)W_PR1_B; r[9] = -1; r[10] = 0;
+        return (long)bytes;
+    }
+    if (!strcmp(what, "dens")) { src = wq.tap_dens; width = pitch = (size_t)wq.tap_dens_n * 4; rows = 1; }
+    else if ((what[0] == 'g' || what[0] == 'x') && what[1] == ':' && what[2] >= '0' && what[2] <= '9') {
+        char* end = nullptr;
+        const long q = strtol(what + 2, &end, 10);
+        if (*end || q < 0 || q > n || (q == n && what[0] == 'x'))
+            return fail(c, DRP_EINVAL, "buffer '%s': the last pass queued jobs 0..%ld (and the column sums' rows as g:%ld)", name, n - 1, n);
+        if (q == n) { src = wq.tap_cs_g; width = pitch = 3 * 4; rows = (size_t)wq.tap_cs_M; }
+        else {
+            const WgradJob& j = wq.tap_jobs[q];
+            rows = (size_t)j.M;
+            if (what[0] == 'g') { src = j.g; width = 64 * 4; pitch = (size_t)j.ldg * 4; }
+            else { src = j.x; width = (size_t)j.in * 4; pitch = (size_t)j.ldx * 4; }
+        }
+    } else return fail(c, DRP_EINVAL, "unknown buffer '%s'", name);
+    const size_t bytes = width * rows;
+    if (!src || bytes == 0) return fail(c, DRP_ESTATE, "buffer '%s' not populated", name);
+    if (out_bytes < bytes) return fail(c, DRP_EINVAL, "buffer '%s' needs %zu bytes", name, bytes);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (pitch == width) HIPCHK(c, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, c->stream));
+    else HIPCHK(c, hipMemcpy2DAsync(out, width, src, pitch, width, rows, hipMemcpyDeviceToHost, c->stream));
+    { const int rc = guarded_wait(c, nullptr); if (rc != DRP_OK) return rc; }
+    return (long)bytes;
+}
+
 long drp_debug_fetch(drp_ctx* c, const char* name, void* out, size_t out_bytes) {
     if (!c || !name || !out) return DRP_EINVAL;
+    if (!strncmp(name, "train_wgrad_", 12)) return fetch_wgrad_tap(c, name + 12, name, out, out_bytes);
     const size_t bn = (size_t)c->marks.lastB * c->marks.lastN;
     const DevBuf* b = nullptr;
     bool part = false;              // fetch `view` (a part of a buffer, not owned; view_cap bytes from there on) instead of *b

@@ -84,7 +84,7 @@ int drp_train_step_divergence_unbalanced(drp_ctx* c, const float* states, const 
                                          const double* mass_q, int iters, int mode, double* loss_out, float* grad_out,
                                          double* col_err_out, double* self_err_out, double* transported_out) {
     if (!c) return DRP_EINVAL;
-    c->tr_grad_fresh = false;
+    c->tr_grad_fresh = false; c->wgrad_tap_on = false;
     ImpulseSource src;
     CHK(impulse_source(c, states_delta, actions, src));
     if (!rho || !mass_q) return fail(c, DRP_EINVAL, "null argument");
@@ -100,7 +100,7 @@ int drp_train_step_divergence(drp_ctx* c, const float* states, const float* stat
                               const int32_t* target_nums, int M, const double* eps, int iters, int mode, double* loss_out,
                               float* grad_out, double* col_err_out, double* self_err_out) {
     if (!c) return DRP_EINVAL;
-    c->tr_grad_fresh = false;
+    c->tr_grad_fresh = false; c->wgrad_tap_on = false;
     ImpulseSource src;
     CHK(impulse_source(c, states_delta, actions, src));
     TrLoss lk = TrLoss::sinkhorn(TR_LOSS_DIVERGENCE, targets, target_nums, M, eps, iters, col_err_out, self_err_out);

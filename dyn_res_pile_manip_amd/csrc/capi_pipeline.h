@@ -188,6 +188,8 @@ struct ProbeScope {
 
 int ensure_step_ws(drp_ctx* c, StepWs& ws, int B, int N, int engine = -1) {
     if (engine < 0) engine = c->engine;
+    c->wgrad_tap_on = false;        // every call that stages a step's inputs comes through here: the densities, the tape and the
+                                    // reverse pass's buffers are about to be rewritten (or grown: their contents are gone)
     // (ws.s_in, ws.attr, ws.dens and ws.s_out grow with the upload that fills them, ws.ecache with the plan that wants it)
     const size_t bn = (size_t)B * N;
     CHK(ensure(c, ws.s_delta, bn * 3 * sizeof(float)));
@@ -788,6 +790,11 @@ struct WgradQueue {
     DevBuf wg_jobs_dev, wg_idx_dev;             // flush_all's jobs and lists on the device
     std::vector<unsigned char> wg_uploaded;     // what they hold (re-uploaded when the iteration's jobs change)
     DevBuf tr_part;                             // the jobs' partial sums
+    // read-only tap of the last flush_all (capi_debug.h: "train_wgrad_*", valid while c->wgrad_tap_on): the jobs in queue order,
+    // the one kt_colsum3 call beside them, the gradient blob the targets point into and the densities the jobs read
+    std::vector<WgradJob> tap_jobs;
+    const float* tap_G = nullptr; const float* tap_cs_g = nullptr; const float* tap_dens = nullptr;
+    long tap_cs_M = 0; int tap_dens_n = 0;
     explicit WgradQueue(drp_ctx* ctx) : c(ctx) {}
     void begin(bool defer_pass) { wg_jobs.clear(); defer = defer_pass; }
     template <int IN>
@@ -858,6 +865,7 @@ struct WgradQueue {
             a = b;
         }
         hipLaunchKernelGGL(kt_wgrad_reduce_lists, dim3(66, (unsigned)k.n_targets), dim3(256), 0, c->stream, jd, od + n, od + n + k.n_targets + 1);
+        tap_jobs.swap(wg_jobs);                     // (the tap keeps them; nothing is copied)
         wg_jobs.clear();
         HIPCHK(c, hipGetLastError());
         return DRP_OK;

@@ -354,7 +354,10 @@ int train_forward_backward(drp_ctx* c, int B, int N, const TrainPass& tp) {
     wq.flush();
     // bias of the predictor's last layer: the column sums of every step's d loss / d s_pred (all final by now), one launch
     hipLaunchKernelGGL(kt_colsum3, dim3(1), dim3(1024), 0, st, g_state, (long)(H * bn), G + W_PR1_B);
-    if (defer) CHK(wq.flush_all());
+    if (defer) {
+        CHK(wq.flush_all());
+        wq.tap_G = G; wq.tap_cs_g = g_state; wq.tap_cs_M = (long)(H * bn); wq.tap_dens = dens; wq.tap_dens_n = B;
+    }
     HIPCHK(c, hipGetLastError());
     return DRP_OK;
 }
@@ -654,6 +657,7 @@ int train_step_body(drp_ctx* c, const float* states, const float* impulses, bool
                     const int32_t* particle_nums, const float* particle_dens, int B, int N, const TrLoss& lk, int mode,
                     double* loss_out, float* grad_out, float* pred_out = nullptr /* drp_train_predict: the forward alone */) {
     if (c) c->tr_grad_fresh = false;    // every trainer pass, refused ones included, ends what drp_train_accumulate could take
+    if (c) c->wgrad_tap_on = false;     //   and what the "train_wgrad_*" taps could show
     CHK(train_check_args(c, states, impulses, actions, attrs, particle_nums, particle_dens, B, N, lk, mode));
     HIPCHK(c, hipSetDevice(c->device));
     end_sessions(c);
@@ -701,6 +705,7 @@ int train_step_body(drp_ctx* c, const float* states, const float* impulses, bool
         *loss_out = total;
     }
     c->tr_grad_fresh = mode == DRP_TRAIN_GRAD && !tp.predict;       // tr_grad is whole and the weights are where it was taken
+    c->wgrad_tap_on = tp.backward && tp.defer && !tp.predict;       // every operand of the pass's deferred jobs is still in place
     return drain.ok();
 }
 }  // namespace
@@ -734,7 +739,7 @@ int drp_train_step_loss(drp_ctx* c, const float* states, const float* states_del
                         const int32_t* target_nums, int M, int loss_kind, double match_weight, int mode, double* loss_out,
                         float* grad_out, int32_t* match_out) {
     if (!c) return DRP_EINVAL;
-    c->tr_grad_fresh = false;
+    c->tr_grad_fresh = false; c->wgrad_tap_on = false;       // (a call refused below ends both, as one refused in train_step_body)
     ImpulseSource src;
     CHK(impulse_source(c, states_delta, actions, src));
     if (loss_kind != DRP_LOSS_CHAMFER && loss_kind != DRP_LOSS_MATCH && loss_kind != DRP_LOSS_CHAMFER_MATCH)
@@ -749,7 +754,7 @@ int drp_train_step_loss(drp_ctx* c, const float* states, const float* states_del
 int drp_train_predict(drp_ctx* c, const float* states, const float* states_delta, const float* actions, const float* attrs,
                       const int32_t* particle_nums, const float* particle_dens, int B, int N, float* states_pred_out) {
     if (!c) return DRP_EINVAL;
-    c->tr_grad_fresh = false;
+    c->tr_grad_fresh = false; c->wgrad_tap_on = false;       // (a call refused below ends both, as one refused in train_step_body)
     ImpulseSource src;
     CHK(impulse_source(c, states_delta, actions, src));
     if (!states_pred_out) return fail(c, DRP_EINVAL, "null argument");
@@ -763,7 +768,7 @@ int drp_train_step_seeded(drp_ctx* c, const float* states, const float* states_d
                           const int32_t* particle_nums, const float* particle_dens, int B, int N, const float* seed, int mode,
                           float* grad_out) {
     if (!c) return DRP_EINVAL;
-    c->tr_grad_fresh = false;
+    c->tr_grad_fresh = false; c->wgrad_tap_on = false;       // (a call refused below ends both, as one refused in train_step_body)
     ImpulseSource src;
     CHK(impulse_source(c, states_delta, actions, src));
     TrLoss lk;

@@ -33,7 +33,7 @@ int drp_train_step_transport(drp_ctx* c, const float* states, const float* state
                              const int32_t* target_nums, int M, const double* eps, int iters, int mode, double* loss_out,
                              float* grad_out, double* col_err_out) {
     if (!c) return DRP_EINVAL;
-    c->tr_grad_fresh = false;
+    c->tr_grad_fresh = false; c->wgrad_tap_on = false;
     ImpulseSource src;
     CHK(impulse_source(c, states_delta, actions, src));
     const TrLoss lk = TrLoss::sinkhorn(TR_LOSS_TRANSPORT, targets, target_nums, M, eps, iters, col_err_out);

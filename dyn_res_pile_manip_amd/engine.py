@@ -1807,3 +1807,30 @@ class Engine(object):
         self._ck(self.lib.drp_debug_fetch(self.h, name.encode(), out.ctypes.data_as(ctypes.c_void_p),
                                           out.nbytes))
         return out
+
+    WGRAD_JOB_FIELDS = ('M', 'in', 'rows_per_sample', 'dens_mod', 'blocks', 'lane_stride', 'k_stride', 'dW', 'db', 'dwd', 'dens')
+
+    def train_wgrad_jobs(self):
+        """The weight-gradient sums of the last trainer pass that ran a reverse pass with deferred weight gradients (the debug
+        taps "train_wgrad_*" of include/drp.h): a list of dicts over WGRAD_JOB_FIELDS, the jobs in queue order and the column sums
+        of the predictor's last bias behind them ('dW', 'db', 'dwd': offsets in floats inside the gradient blob, -1 for none;
+        'dens': whether the job reads the densities).  Refused (DrpError) when the last pass did not defer, ran no reverse pass,
+        or a later call has reused its buffers."""
+        nf = len(self.WGRAD_JOB_FIELDS)
+        buf = np.empty((18 * 64 + 1, nf), np.int64)             # the most a pass queues: 18 jobs a rollout step, 64 steps
+        n = self.lib.drp_debug_fetch(self.h, b'train_wgrad_jobs', buf.ctypes.data_as(ctypes.c_void_p), buf.nbytes)
+        self._ck(n)
+        return [dict(zip(self.WGRAD_JOB_FIELDS, (int(v) for v in rec))) for rec in buf[:n // (8 * nf)]]
+
+    def train_wgrad_tap(self):
+        """train_wgrad_jobs() with the rows the sums were taken over -> (jobs, [(g [M,64], x [M,in]) per job, then (g [M,3], None)
+        of the column sums], the densities [dens_mod] the jobs read): everything tests/_wgrad_ref.py reconstructs the gradient
+        blob from, as float32 copies of what lay in device memory."""
+        jobs = self.train_wgrad_jobs()
+        ops = []
+        for q, j in enumerate(jobs[:-1]):
+            ops.append((self.debug_fetch('train_wgrad_g:%d' % q, (j['M'], 64)), self.debug_fetch('train_wgrad_x:%d' % q, (j['M'], j['in']))))
+        ops.append((self.debug_fetch('train_wgrad_g:%d' % (len(jobs) - 1), (jobs[-1]['M'], 3)), None))
+        n_dens = max([j['dens_mod'] for j in jobs[:-1] if j['dens']] or [0])
+        dens = self.debug_fetch('train_wgrad_dens', (n_dens,)) if n_dens else np.zeros((0,), np.float32)
+        return jobs, ops, dens

@@ -614,8 +614,20 @@ int drp_debug_stall(drp_ctx* ctx, int ms);
  * after a batch call, is DRP_ESTATE (not populated), never the other call's bytes.  The last trainer call's "train_states"
  * ([B][H][N][3] float32, the predicted states), "train_sdelta" ([H][B][N][3], the impulses) and "train_seed" ([H][B][N][3]
  * float32: d loss / d s_pred as the call's loss kernel left it -- the loss's own seed after a call with DRP_TRAIN_EVAL, which runs
- * no reverse pass over it; a reverse pass adds the later steps' shares to every slice but the last).  (byte sizes: the returned
- * value). returns bytes. */
+ * no reverse pass over it; a reverse pass adds the later steps' shares to every slice but the last).  The tape's lists of every
+ * step: "train_nbr_idx", "train_nbr_cnt", "train_rev_off", "train_rev".
+ * The weight-gradient sums of the last trainer call that ran a reverse pass with deferred weight gradients (the default), read-only:
+ * "train_wgrad_jobs" -- one record of 11 int64 per job of the pass, in queue order: M, in, rows_per_sample, dens_mod, blocks,
+ * lane_stride, k_stride, the offsets in floats of dW, db and dwd inside the gradient blob (-1: none), whether the densities are read;
+ * then one more record for the column sums of the predictor's last bias (M, in = 3, its target as the db offset; the rest 0 / -1).
+ * dW[lane * lane_stride + k * k_stride] += sum_rows g[row][lane] x[row][k] (k < in), db[lane] += sum_rows g[row][lane],
+ * dwd[lane * lane_stride] += sum_rows g[row][lane] (dens[(row / rows_per_sample) % dens_mod] / 5000 in fp32).  "train_wgrad_g:<q>" and
+ * "train_wgrad_x:<q>" -- job q's operand rows as dense [M][64] / [M][in] float32 (whatever the strides in device memory are); the
+ * column sums' rows [M][3] under "train_wgrad_g:<number of jobs>".  "train_wgrad_dens" -- the densities [dens_mod] the jobs read.
+ * No device pointer leaves.  DRP_ESTATE (not populated) after a pass that did not defer (DRP_NO_WGRAD_DEFER=1, or operands beyond
+ * 8 GB), after DRP_TRAIN_EVAL or drp_train_predict, after a trainer call that failed, and after any later call that stages a step's
+ * inputs (they share the buffers); DRP_EINVAL for an index the pass did not queue.  drp_train_accumulate and drp_train_apply leave
+ * the taps valid.  (byte sizes: the returned value). returns bytes. */
 long drp_debug_fetch(drp_ctx* ctx, const char* name, void* out, size_t out_bytes);
 
 /* ---- the float64 yardstick: one step evaluated in double on the device, and a probe that holds an engine against it ----
