@@ -9,7 +9,7 @@ int drp_cloud_chamfer(drp_ctx* c, const float* p, const int32_t* n_p, const floa
     CloudCall k;
     CHK(cloud_begin(c, k, chamfer_layout(B, N, M), outs, p, n_p, q, n_q, B, N, M));
     KcArgs a{};
-    a.cp = k.cp; a.pred = k.p_dev; a.scale = 1.0f;
+    a.cp = k.cp; a.pred = k.p<float>(); a.scale = 1.0f;
     a.terms = k.out<double>(0); a.grad = k.out<float>(1); a.nn_pq = k.out<int>(2); a.nn_qp = k.out<int>(3);
     {
         ProbeScope ps(c, KC_LOSS);
@@ -26,7 +26,7 @@ int drp_cloud_chamfer_f64(drp_ctx* c, const float* p, const int32_t* n_p, const 
     CloudCall k;
     CHK(cloud_begin(c, k, chamfer64_layout(B, N, M), outs, p, n_p, q, n_q, B, N, M));
     Kc64Args a{};
-    a.cp = k.cp; a.p32 = k.p_dev; a.b_off = 0; a.B = B; a.scale = 1.0;
+    a.cp = k.cp; a.p32 = k.p<float>(); a.b_off = 0; a.B = B; a.scale = 1.0;
     a.terms = k.out<double>(0); a.margin = k.out<double>(1); a.grad = k.out<double>(2); a.nn_pq = k.out<int>(3); a.nn_qp = k.out<int>(4);
     hipLaunchKernelGGL((kc64_chamfer<false>), dim3(B, 1), dim3(KC64_THREADS), 0, c->stream, a);
     return cloud_finish(c, k, "kc64_chamfer");

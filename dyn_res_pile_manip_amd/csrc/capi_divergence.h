@@ -1,14 +1,17 @@
 // capi_divergence.h -- a section of the C ABI's translation unit (textually included by drp_capi.hip, which has the order of the sections).
-// Here: the stand-alone Sinkhorn divergence of two padded cloud batches (k_divergence.h), and the trainer's entry point for it
+// Here: the stand-alone Sinkhorn divergence of two padded cloud batches (k_sinkhorn.h), and the trainer's entry point for it
 // (capi_train.h: train_step_body with the TR_LOSS_DIVERGENCE kind, check_transport_params).
 
-// A one-shot on two clouds (capi_pipeline.h: cloud_check, cloud_begin, cloud_finish; train_host.h: divergence_layout).
-// drp_cloud_divergence_unbalanced (`reach`: rho, mass_q and transported_out are read; k_divergence.h: kd_sweeps_unbalanced) is the same
-// call with the second instantiation of the kernels: one body, as cloud_divergence_f64_body is, so that the two cannot drift apart
+// A one-shot on two clouds (capi_pipeline.h: cloud_check, cloud_begin, cloud_finish; train_host.h: divergence_layout), ONE body
+// behind the four of them so that they cannot drift apart.  T: p's and the gradient's scalar -- float: drp_cloud_divergence and
+// drp_cloud_divergence_unbalanced; double: their float64 yardsticks (capi_divergence_f64.h).  `reach`: rho, mass_q and
+// transported_out are read, and the second instantiation of the kernels runs (k_sinkhorn.h: UNBAL)
 namespace {
-int cloud_divergence_body(drp_ctx* c, const float* p, const int32_t* n_p, const float* q, const int32_t* n_q, int B, int N, int M,
+extern "C++" template <typename T>
+int cloud_divergence_body(drp_ctx* c, const T* p, const int32_t* n_p, const float* q, const int32_t* n_q, int B, int N, int M,
                           const double* eps, bool reach, const double* rho, const double* mass_q, int iters, double* terms_out,
-                          float* grad_p_out, double* dual_out, double* col_err_out, double* self_err_out, double* transported_out) {
+                          T* grad_p_out, double* dual_out, double* col_err_out, double* self_err_out, double* transported_out) {
+    constexpr bool f64 = sizeof(T) == sizeof(double);
     CHK(cloud_check(c, p, n_p, q, n_q, B, N, M, terms_out, KT_MAX_POINTS, KT_MAX_POINTS, " for a divergence"));
     CHK(check_transport_params(c, eps, B, iters));
     if (reach) CHK(check_reach_params(c, eps, rho, mass_q, B, 1));
@@ -18,7 +21,7 @@ int cloud_divergence_body(drp_ctx* c, const float* p, const int32_t* n_p, const 
     bad = first_nonfinite_row(q, n_q, B, M);
     if (bad >= 0) return fail(c, DRP_EINVAL, "q[%ld][%ld] is not finite", bad / M, bad % M);
     void* const outs[] = {terms_out, grad_p_out, dual_out, col_err_out, self_err_out};
-    const DivLayout lay = divergence_layout(B, N, M, reach);
+    const DivLayout lay = divergence_layout(B, N, M, reach, sizeof(T));
     CloudCall k;
     CHK(cloud_begin(c, k, lay.cloud, outs, p, n_p, q, n_q, B, N, M));
     // eps alone goes up from the caller's array; eps | rho | mass_q lie side by side: one staging vector, one copy (read until
@@ -34,10 +37,11 @@ int cloud_divergence_body(drp_ctx* c, const float* p, const int32_t* n_p, const 
         (void)drp_sync(c);                                  // (cloud_begin's staging vector is still being read)
         return fail(c, DRP_EHIP, reach ? "hipMemcpyAsync of eps, rho and mass_q" : "hipMemcpyAsync of eps");
     }
-    KdArgs a{};
-    a.cp = k.cp; a.pred = k.p_dev; a.eps = reinterpret_cast<double*>(k.io + lay.eps); a.iters = iters; a.scale = 1.0;
+    SkArgs<T, T> a{};
+    a.cp = k.cp; a.pred = k.p<T>(); a.b_off = 0; a.B = B;
+    a.eps = reinterpret_cast<double*>(k.io + lay.eps); a.iters = iters; a.scale = 1.0;
     a.vals = reinterpret_cast<double*>(k.io + lay.vals);
-    a.grad = k.out<float>(1);
+    a.grad = k.out<T>(1);
     a.gsum = a.grad != nullptr ? reinterpret_cast<double*>(k.io + lay.gsum) : nullptr;
     a.terms = k.out<double>(0); a.dual = k.out<double>(2); a.col_err = k.out<double>(3); a.self_err = k.out<double>(4);
     const bool moved = reach && transported_out != nullptr;
@@ -45,18 +49,29 @@ int cloud_divergence_body(drp_ctx* c, const float* p, const int32_t* n_p, const 
         a.rho = reinterpret_cast<double*>(k.io + lay.rho); a.mass_q = reinterpret_cast<double*>(k.io + lay.mass_q);
         a.transported = moved ? reinterpret_cast<double*>(k.io + lay.transported) : nullptr;
     }
+    const dim3 sweeps(B, 1, 3), combine(B, 1);
     {
         ProbeScope ps(c, KC_LOSS);
-        if (reach) {
-            hipLaunchKernelGGL(kd_sweeps_unbalanced, dim3(B, 1, 3), dim3(KT_THREADS), 0, c->stream, a);
-            hipLaunchKernelGGL((kd_combine<false, true>), dim3(B, 1), dim3(KD_COMBINE_THREADS), 0, c->stream, a);
+        if constexpr (f64) {
+            if (reach) {
+                hipLaunchKernelGGL(kd64_sweeps_unbalanced, sweeps, dim3(KT_THREADS), 0, c->stream, a);
+                hipLaunchKernelGGL(kd64_combine_unbalanced, combine, dim3(KD_COMBINE_THREADS), 0, c->stream, a);
+            } else {
+                hipLaunchKernelGGL(kd64_sweeps, sweeps, dim3(KT_THREADS), 0, c->stream, a);
+                hipLaunchKernelGGL(kd64_combine, combine, dim3(KD_COMBINE_THREADS), 0, c->stream, a);
+            }
         } else {
-            hipLaunchKernelGGL(kd_sweeps, dim3(B, 1, 3), dim3(KT_THREADS), 0, c->stream, a);
-            hipLaunchKernelGGL((kd_combine<false>), dim3(B, 1), dim3(KD_COMBINE_THREADS), 0, c->stream, a);
+            if (reach) {
+                hipLaunchKernelGGL(kd_sweeps_unbalanced, sweeps, dim3(KT_THREADS), 0, c->stream, a);
+                hipLaunchKernelGGL((kd_combine<false, true>), combine, dim3(KD_COMBINE_THREADS), 0, c->stream, a);
+            } else {
+                hipLaunchKernelGGL(kd_sweeps, sweeps, dim3(KT_THREADS), 0, c->stream, a);
+                hipLaunchKernelGGL((kd_combine<false>), combine, dim3(KD_COMBINE_THREADS), 0, c->stream, a);
+            }
         }
     }
     const int rc = moved ? d2h(c, transported_out, k.io + lay.transported, (size_t)B * sizeof(double)) : DRP_OK;
-    const int rf = cloud_finish(c, k, reach ? "kd_sweeps_unbalanced" : "kd_sweeps");       // the wait, also behind an error above
+    const int rf = cloud_finish(c, k, f64 ? "kd64_sweeps" : reach ? "kd_sweeps_unbalanced" : "kd_sweeps");     // the wait, also behind an error above
     return rc != DRP_OK ? rc : rf;
 }
 }  // namespace

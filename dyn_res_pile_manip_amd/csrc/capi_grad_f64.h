@@ -5,7 +5,7 @@
 // gradients).  They differ in where a step's impulse comes from (the push, or data), in the loss that seeds the reverse pass, in
 // the tail of a reverse step, and in the trainer's weight-gradient launches in between (F64Wgrad).  drp_train_grad_f64_untracked is the
 // trainer's body with the Chamfer loss of k_chamfer_f64.h as the seed (row u1's yardstick); everything behind the seed is the
-// same code, and drp_train_grad_f64_divergence (capi_divergence_f64.h) is it with the Sinkhorn divergence of k_divergence_f64.h
+// same code, and drp_train_grad_f64_divergence (capi_divergence_f64.h) is it with the Sinkhorn divergence of k_sinkhorn.h
 // (row u4), drp_train_grad_f64_match (capi_match_f64.h) with the matching term of k_match_f64.h or its mix with the Chamfer term
 // (row u2).  Like the one-step calls of
 // capi_f64.h they are no engine and no session: they work in buffers of their own under F64Scope, keep nothing between calls
@@ -351,8 +351,8 @@ int tr64_chunk(drp_ctx* c, const Tr64Ws& k, const Tr64Io& io, int b0, int bc, in
         // the same slot of the stream and the same seed buffer: the caller's seed at the chunk's sample offset, no term
         hipLaunchKernelGGL(k64_seed_given, dim3(bc, H), dim3(256), 0, st, io.seed, io.nums, b0, bc, N, H, k.rev.g_state);
     } else if (io.eps != nullptr) {
-        // the same slot of the stream and the same outputs: the plans from the tape's own double states (k_divergence_f64.h)
-        Kd64Args a{};
+        // the same slot of the stream and the same outputs: the plans from the tape's own double states (k_sinkhorn.h)
+        SkArgs64 a{};
         a.cp = tr_cloud_pair((size_t)N * 3, pn * 3, io.nums, io.targets, io.tnums, H, N, io.M);
         a.pred = k.tape.state + pn * 3;
         a.b_off = b0; a.B = B;
@@ -463,7 +463,7 @@ int check_match_loss(drp_ctx* c, const TrLoss& lk, int N) {
 // drp_train_grad_f64, drp_train_grad_f64_actions and drp_train_grad_f64_untracked: one body; `impulses` is states_delta
 // [B][H][N][3], or with `actions` the pushes [B][H][4]; the loss kind and the targets in `lk` (capi_train.h: TrLoss) -- the tracked
 // MSE, the Chamfer loss against untracked target clouds (k_chamfer_f64.h), or the Sinkhorn divergence to them
-// (k_divergence_f64.h), or the matching kinds (k_match_f64.h: the matching term, or its mix with the Chamfer term); the transport
+// (k_sinkhorn.h), or the matching kinds (k_match_f64.h: the matching term, or its mix with the Chamfer term); the transport
 // loss has no yardstick
 int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, bool actions, const float* attrs,
                         const int32_t* particle_nums, const float* particle_dens, int B, int N, int n_rollout, const TrLoss& lk,

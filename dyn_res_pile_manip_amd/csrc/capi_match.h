@@ -15,7 +15,7 @@ int drp_cloud_match(drp_ctx* c, const float* p, const int32_t* n_p, const float*
     CloudCall k;
     CHK(cloud_begin(c, k, cm_layout(B, N, M), outs, p, n_p, q, n_q, B, N, M));
     KaArgs a{};
-    a.cp = k.cp; a.pred = k.p_dev; a.scale = 1.0; a.keep = 0.0;
+    a.cp = k.cp; a.pred = k.p<float>(); a.scale = 1.0; a.keep = 0.0;
     a.terms = k.out<double>(0); a.grad = k.out<float>(1); a.match_pq = k.out<int>(2); a.match_qp = k.out<int>(3); a.dual = k.out<double>(4);
     {
         ProbeScope ps(c, KC_LOSS);

@@ -4,7 +4,8 @@
 // train_grad_f64_body with the TR_LOSS_MATCH and TR_LOSS_CHAMFER_MATCH kinds; ka64_run is declared ahead of it).
 
 // drp_cloud_match's contract with p as doubles and, optionally, the pairs given: the kernel the trainer's yardstick runs.  The
-// buffer is the one-shots' (c->cloud_io) in a layout of its own (train_host.h: match64_layout): p does not fit cloud_begin's floats
+// buffer is the one-shots' (c->cloud_io) in a layout of its own (train_host.h: match64_layout): the caller's partners go up
+// with the inputs and six blocks come back, which cloud_begin's layout has no room for
 int drp_cloud_match_f64(drp_ctx* c, const double* p, const int32_t* n_p, const float* q, const int32_t* n_q, int B, int N, int M,
                         const int32_t* match_in, double* terms_out, double* grad_p_out, int32_t* match_pq_out, int32_t* match_qp_out,
                         double* dual_out, double* cost_out) {

@@ -1228,25 +1228,27 @@ struct CloudCall {
     std::vector<char> stage;        // the inputs as uploaded: read until cloud_finish's wait
     char* io = nullptr;             // c->cloud_io
     CloudPair cp{};                 // the pair on the device, step strides 0
-    const float* p_dev = nullptr;   // p's rows there
+    const void* p_dev = nullptr;    // p's rows there: lay.p_elem bytes an element
+    template <typename T>
+    const T* p() const { return static_cast<const T*>(p_dev); }
     // block k on the device for the kernel to write, null where the caller did not ask for it
     template <typename T>
     T* out(int k) const { return outs[k] ? reinterpret_cast<T*>(io + lay.out[k]) : nullptr; }
 };
 // the inputs staged and on their way up, the view filled
-int cloud_begin(drp_ctx* c, CloudCall& k, const CloudLayout& lay, void* const* outs, const float* p, const int32_t* n_p,
+int cloud_begin(drp_ctx* c, CloudCall& k, const CloudLayout& lay, void* const* outs, const void* p, const int32_t* n_p,
                 const float* q, const int32_t* n_q, int B, int N, int M) {
     HIPCHK(c, hipSetDevice(c->device));
     k.lay = lay; k.outs = outs;
     CHK(ensure(c, c->cloud_io, lay.bytes));
     k.stage.resize(lay.in_bytes);
-    memcpy(k.stage.data() + lay.pts_p, p, (size_t)B * N * 3 * sizeof(float));
+    memcpy(k.stage.data() + lay.pts_p, p, (size_t)B * N * 3 * lay.p_elem);
     memcpy(k.stage.data() + lay.pts_q, q, (size_t)B * M * 3 * sizeof(float));
     memcpy(k.stage.data() + lay.n_p, n_p, (size_t)B * sizeof(int));
     memcpy(k.stage.data() + lay.n_q, n_q, (size_t)B * sizeof(int));
     CHK(h2d(c, c->cloud_io, k.stage.data(), lay.in_bytes));
     k.io = ptr<char>(c->cloud_io);
-    k.p_dev = reinterpret_cast<const float*>(k.io + lay.pts_p);
+    k.p_dev = k.io + lay.pts_p;
     k.cp.p_bstride = (size_t)N * 3; k.cp.p_tstride = 0;
     k.cp.q = reinterpret_cast<const float*>(k.io + lay.pts_q); k.cp.q_bstride = (size_t)M * 3; k.cp.q_tstride = 0;
     k.cp.n_p = reinterpret_cast<const int*>(k.io + lay.n_p);

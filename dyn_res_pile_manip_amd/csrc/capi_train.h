@@ -13,8 +13,8 @@ const int* tr_nums(const drp_ctx* c, const TrArena& lay) {
 // untracked target clouds (k_chamfer.h), the one-to-one matching loss against them (k_match.h), or the two mixed; the targets as
 // the HOST gave them (the entry point stages them behind the batch).  The kinds beyond the MSE are include/drp.h's DRP_LOSS_*.
 // The float64 yardstick (capi_grad_f64.h) reads the same description; it has every kind but the transport loss.
-// TR_LOSS_TRANSPORT (k_transport.h) is internal: drp_train_step_transport's, no loss_kind of drp_train_step_loss; so is
-// TR_LOSS_DIVERGENCE (k_divergence.h), drp_train_step_divergence's, and TR_LOSS_GIVEN: no loss at all but the CALLER's d loss / d
+// TR_LOSS_TRANSPORT (k_sinkhorn.h) is internal: drp_train_step_transport's, no loss_kind of drp_train_step_loss; so is
+// TR_LOSS_DIVERGENCE (k_sinkhorn.h), drp_train_step_divergence's, and TR_LOSS_GIVEN: no loss at all but the CALLER's d loss / d
 // s_pred as the seed (drp_train_step_seeded, drp_train_grad_f64_seeded; kt_seed_given, k64_seed_given)
 enum { TR_LOSS_MSE = 0, TR_LOSS_CHAMFER = DRP_LOSS_CHAMFER, TR_LOSS_MATCH = DRP_LOSS_MATCH, TR_LOSS_CHAMFER_MATCH = DRP_LOSS_CHAMFER_MATCH,
        TR_LOSS_TRANSPORT = 4, TR_LOSS_DIVERGENCE = 5, TR_LOSS_GIVEN = 6 };
@@ -218,8 +218,8 @@ int train_forward_backward(drp_ctx* c, int B, int N, const TrainPass& tp) {
         }
         if (lk.transport()) {
             // the Chamfer kernel's outputs and zero-fill; eps [B] lies behind the staged batch, col_err [H][B] behind the terms
-            KtArgs a{};
-            a.cp = cp; a.pred = states;
+            SkArgs32 a{};
+            a.cp = cp; a.pred = states; a.b_off = 0; a.B = B;
             a.eps = reinterpret_cast<const double*>(ar + lay.eps); a.iters = lk.iters;
             a.scale = (double)scale;
             a.grad = g_state; a.terms = loss;
@@ -233,8 +233,8 @@ int train_forward_backward(drp_ctx* c, int B, int N, const TrainPass& tp) {
             const bool unbalanced = lk.unbalanced();
             const TrDivLoss dl = tr_div_loss_layout(B, H, N, unbalanced);
             double* const d = ptr<double>(c->tr_loss);
-            KdArgs a{};
-            a.cp = cp; a.pred = states;
+            SkArgs32 a{};
+            a.cp = cp; a.pred = states; a.b_off = 0; a.B = B;
             a.eps = reinterpret_cast<const double*>(ar + lay.eps); a.iters = lk.iters;
             a.scale = (double)scale;
             a.vals = d + dl.vals; a.gsum = d + dl.gsum;

@@ -1,5 +1,5 @@
 // capi_transport.h -- a section of the C ABI's translation unit (textually included by drp_capi.hip, which has the order of the sections).
-// Here: the stand-alone entropy-regularised transport distance of two padded cloud batches (k_transport.h), and the trainer's
+// Here: the stand-alone entropy-regularised transport distance of two padded cloud batches (k_sinkhorn.h), and the trainer's
 // entry point for it (capi_train.h: train_step_body with the TR_LOSS_TRANSPORT kind, check_transport_params).
 
 // A one-shot on two clouds (capi_pipeline.h: cloud_check, cloud_begin, cloud_finish; train_host.h: transport_layout)
@@ -17,8 +17,8 @@ int drp_cloud_transport(drp_ctx* c, const float* p, const int32_t* n_p, const fl
     CHK(cloud_begin(c, k, transport_layout(B, N, M), outs, p, n_p, q, n_q, B, N, M));
     double* const eps_dev = reinterpret_cast<double*>(k.io + k.lay.out[4]);
     HIPCHK(c, hipMemcpyAsync(eps_dev, eps, (size_t)B * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    KtArgs a{};
-    a.cp = k.cp; a.pred = k.p_dev; a.eps = eps_dev; a.iters = iters; a.scale = 1.0;
+    SkArgs32 a{};
+    a.cp = k.cp; a.pred = k.p<float>(); a.b_off = 0; a.B = B; a.eps = eps_dev; a.iters = iters; a.scale = 1.0;
     a.terms = k.out<double>(0); a.grad = k.out<float>(1); a.dual = k.out<double>(2); a.col_err = k.out<double>(3);
     {
         ProbeScope ps(c, KC_LOSS);

@@ -53,9 +53,7 @@
 #include "k_chamfer_f64.h"
 #include "k_match.h"
 #include "k_match_f64.h"
-#include "k_transport.h"
-#include "k_divergence.h"
-#include "k_divergence_f64.h"
+#include "k_sinkhorn.h"
 #include "k_prop_inst.h"       // km_prop / km_prop3 / km_rollout: declared here, instantiated in inst_*.hip
 
 #include "dispatch.h"          // host-only: policy, variant flags, plan functions

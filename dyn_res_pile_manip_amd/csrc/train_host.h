@@ -96,15 +96,17 @@ inline Tr64Arena tr64_layout(int B, int H, int N, int M = 0, bool actions = fals
     return a;
 }
 
-// The one buffer of a one-shot on two clouds (capi_pipeline.h: cloud_begin), every block 16-byte aligned.  Up: p [B][N][3] |
-// q [B][M][3] | n_p [B] | n_q [B] (ints); down, behind `in_bytes`: the call's n_out output blocks out[k] of out_bytes[k] each
+// The one buffer of a one-shot on two clouds (capi_pipeline.h: cloud_begin), every block 16-byte aligned.  Up: p [B][N][3]
+// (elements of p_elem bytes: floats, or the float64 divergence's doubles) | q [B][M][3] | n_p [B] | n_q [B] (ints); down, behind
+// `in_bytes`: the call's n_out output blocks out[k] of out_bytes[k] each
 #define CLOUD_MAX_OUT 5
-struct CloudLayout { size_t pts_p, pts_q, n_p, n_q, in_bytes, out[CLOUD_MAX_OUT], out_bytes[CLOUD_MAX_OUT], bytes; int n_out; };
-inline CloudLayout cloud_layout(int B, int N, int M, const size_t (&out_bytes)[CLOUD_MAX_OUT]) {
+struct CloudLayout { size_t p_elem, pts_p, pts_q, n_p, n_q, in_bytes, out[CLOUD_MAX_OUT], out_bytes[CLOUD_MAX_OUT], bytes; int n_out; };
+inline CloudLayout cloud_layout(int B, int N, int M, const size_t (&out_bytes)[CLOUD_MAX_OUT], size_t p_elem = sizeof(float)) {
     auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
     CloudLayout a{};
+    a.p_elem = p_elem;
     a.pts_p = 0;
-    a.pts_q = up(a.pts_p + (size_t)B * N * 3 * sizeof(float));
+    a.pts_q = up(a.pts_p + (size_t)B * N * 3 * p_elem);
     a.n_p = up(a.pts_q + (size_t)B * M * 3 * sizeof(float));
     a.n_q = up(a.n_p + (size_t)B * sizeof(int32_t));
     a.bytes = a.in_bytes = up(a.n_q + (size_t)B * sizeof(int32_t));
@@ -146,13 +148,15 @@ inline CloudLayout transport_layout(int B, int N, int M) {
 // back; behind them, never read back: eps [B] (doubles, UP behind cloud_begin's copy) | the kernels' scratch: the value sums
 // [3][B] | the gradient sums [2][B][N][3] (doubles).  drp_cloud_divergence_unbalanced (`reach`): rho [B] | mass_q [B] (doubles) lie
 // side by side with eps -- the three go UP in one copy -- ahead of the scratch, and transported [B] (doubles, comes back by a copy
-// of its own: a sixth output) behind it; the five blocks that come back and eps stay where they are without it
+// of its own: a sixth output) behind it; the five blocks that come back and eps stay where they are without it.
+// drp_cloud_divergence_f64 and its unbalanced twin: the same blocks with p and the gradient as doubles (p_elem 8).  Every block
+// starts on a multiple of 16 bytes or, within eps | rho | mass_q, of 8: no double is misaligned
 struct DivLayout { CloudLayout cloud; size_t eps, rho, mass_q, vals, gsum, transported; };
-inline DivLayout divergence_layout(int B, int N, int M, bool reach = false) {
+inline DivLayout divergence_layout(int B, int N, int M, bool reach = false, size_t p_elem = sizeof(float)) {
     auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t bn = (size_t)B * N, bm = (size_t)B * M, b8 = (size_t)B * sizeof(double);
     DivLayout a{};
-    a.cloud = cloud_layout(B, N, M, {b8, bn * 3 * sizeof(float), 2 * (bn + bm) * sizeof(double), b8, 2 * b8});
+    a.cloud = cloud_layout(B, N, M, {b8, bn * 3 * p_elem, 2 * (bn + bm) * sizeof(double), b8, 2 * b8}, p_elem);
     a.eps = a.cloud.bytes;
     size_t end = a.eps + b8;
     if (reach) {
@@ -169,45 +173,7 @@ inline DivLayout divergence_layout(int B, int N, int M, bool reach = false) {
     }
     return a;
 }
-// drp_cloud_divergence_f64: p is the caller's doubles, so the buffer is its own (not cloud_begin's).  Up, in one copy: p [B][N][3]
-// (doubles) | eps [B] (doubles) | q [B][M][3] | n_p [B] | n_q [B] (ints); down, behind `in_bytes`: terms [B] | gradient [B][N][3] |
-// duals [B][2N + 2M] | col_err [B] | self_err [B][2] (out[0..5), doubles all); behind them, never read back, the kernels' scratch:
-// the value sums [3][B] | the gradient sums [2][B][N][3].  Every block 16-byte aligned.  drp_cloud_divergence_unbalanced_f64
-// (`reach`): rho [B] | mass_q [B] (doubles) go up between eps and q, and transported [B] (doubles) lies behind the scratch and comes
-// back by a copy of its own, a sixth output; without `reach` no block moves
-struct Div64Layout { size_t pts_p, eps, pts_q, n_p, n_q, in_bytes, out[5], out_bytes[5], vals, gsum, bytes, rho, mass_q, transported; };
-inline Div64Layout divergence64_layout(int B, int N, int M, bool reach = false) {
-    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t bn = (size_t)B * N, bm = (size_t)B * M;
-    Div64Layout a{};
-    a.pts_p = 0;
-    a.eps = up(a.pts_p + bn * 3 * sizeof(double));
-    a.pts_q = up(a.eps + (size_t)B * sizeof(double));
-    if (reach) {
-        a.rho = a.pts_q;
-        a.mass_q = up(a.rho + (size_t)B * sizeof(double));
-        a.pts_q = up(a.mass_q + (size_t)B * sizeof(double));
-    }
-    a.n_p = up(a.pts_q + bm * 3 * sizeof(float));
-    a.n_q = up(a.n_p + (size_t)B * sizeof(int32_t));
-    a.bytes = a.in_bytes = up(a.n_q + (size_t)B * sizeof(int32_t));
-    const size_t ob[5] = {(size_t)B * sizeof(double), bn * 3 * sizeof(double), 2 * (bn + bm) * sizeof(double), (size_t)B * sizeof(double),
-                          (size_t)B * 2 * sizeof(double)};
-    for (int k = 0; k < 5; ++k) {
-        a.out[k] = a.bytes;
-        a.out_bytes[k] = ob[k];
-        a.bytes = up(a.bytes + ob[k]);
-    }
-    a.vals = a.bytes;
-    a.gsum = up(a.vals + (size_t)3 * B * sizeof(double));
-    a.bytes = up(a.gsum + 2 * bn * 3 * sizeof(double));
-    if (reach) {
-        a.transported = a.bytes;
-        a.bytes = up(a.transported + (size_t)B * sizeof(double));
-    }
-    return a;
-}
-// drp_cloud_match_f64: p is the caller's doubles, so the buffer is its own too.  Up, in one copy: p [B][N][3] (doubles) | q [B][M][3]
+// drp_cloud_match_f64: a buffer of its own (an optional sixth input, six outputs: more than CloudLayout holds).  Up, in one copy: p [B][N][3] (doubles) | q [B][M][3]
 // | n_p [B] | n_q [B] | with `match_in` the caller's partners [B][N] (ints); down, behind `in_bytes`: terms [B] | gradient [B][N][3]
 // (doubles) | partner of every row of p [B][N] | of q [B][M] (ints) | duals [B][N + M] | costs [B][2] (doubles) (out[0..6)).  Every
 // block 16-byte aligned

@@ -908,7 +908,7 @@ int drp_train_step_divergence(drp_ctx* ctx, const float* states, const float* st
                               const double* eps /*[B]*/, int iters, int mode, double* loss_out, float* grad_out,
                               double* col_err_out /*[H][B], nullable*/, double* self_err_out /*[H][B][2], nullable*/);
 
-/* ---- Unbalanced Sinkhorn divergence (csrc/k_divergence.h: kd_sweeps_unbalanced): drp_cloud_divergence for a pile
+/* ---- Unbalanced Sinkhorn divergence (csrc/k_sinkhorn.h: kd_sweeps_unbalanced): drp_cloud_divergence for a pile
  * seen partly.  The balanced plan must place every predicted particle's mass on the observed cloud, so a particle whose
  * counterpart was not observed is pulled hardest.  Here each marginal is held by a KL penalty in place of the hard constraint
  * (Sejourne et al. 2019): mass further than about sqrt(rho) from the other cloud is given up, not moved.  Two more quantities per
@@ -951,7 +951,7 @@ int drp_train_step_divergence_unbalanced(drp_ctx* ctx, const float* states, cons
                                          double* loss_out, float* grad_out, double* col_err_out /*[H][B], nullable*/,
                                          double* self_err_out /*[H][B][2], nullable*/, double* transported_out /*[H][B], nullable*/);
 
-/* ---- the float64 yardstick of the Sinkhorn divergence (csrc/k_divergence_f64.h).  drp_cloud_divergence's definition with nothing
+/* ---- the float64 yardstick of the Sinkhorn divergence (csrc/k_sinkhorn.h).  drp_cloud_divergence's definition with nothing
  * in fp32: p is DOUBLE [B][N][3] -- on purpose: the call runs the instantiation the trainer's yardstick runs on the float64
  * tape's predicted state -- q the caller's floats widened exactly; every cost, of p - q, p - p and q - q, is dx*dx + dy*dy + dz*dz
  * in double in that order on double differences (no fused multiply-add); the gradient (2 scale / 3) (sum_j P_ij (p_i - q_j) -
@@ -987,7 +987,7 @@ int drp_train_grad_f64_divergence(drp_ctx* ctx, const float* states, const float
                                   double* grad_state_out, double* col_err_out /*[H][B], nullable*/,
                                   double* self_err_out /*[H][B][2], nullable*/);
 
-/* ---- the float64 yardstick of the unbalanced Sinkhorn divergence (csrc/k_divergence_f64.h: kd64_sweeps_unbalanced,
+/* ---- the float64 yardstick of the unbalanced Sinkhorn divergence (csrc/k_sinkhorn.h: kd64_sweeps_unbalanced,
  * kd64_combine_unbalanced).  drp_cloud_divergence_unbalanced's definition -- sweeps damped by lambda, the clouds' own masses, the
  * expm1 value times (rho + eps/2), the certificates against mass exp(-dual/rho), transported -- with drp_cloud_divergence_f64's
  * arithmetic: p DOUBLE, q widened exactly, double costs on double differences, the gradient written as double, +0.0 on padding.

@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE of the float64 yardstick of the Sinkhorn divergence (drp_cloud_divergence_f64,
-drp_train_grad_f64_divergence; csrc/k_divergence_f64.h): tests/_divergence_ref.py's definition with nothing in fp32 -- its
+drp_train_grad_f64_divergence; csrc/k_sinkhorn.h): tests/_divergence_ref.py's definition with nothing in fp32 -- its
 pair64(None, q, eps, K, p64=p) path, the one its own central differences use: costs and differences in float64 from the float64
 prediction and the float32 targets widened.
 

@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE of the Sinkhorn divergence (drp_cloud_divergence, drp_train_step_divergence; csrc/k_divergence.h):
+"""TEST INFRASTRUCTURE of the Sinkhorn divergence (drp_cloud_divergence, drp_train_step_divergence; csrc/k_sinkhorn.h):
 include/drp.h's definition in numpy float64, operation for operation, on tests/_transport_ref.py's sweeps and plan and
 tests/_match_ref.py's fp32 cost.  The terms of every sum are added in ascending index.
 

@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE of the float64 yardstick of the unbalanced Sinkhorn divergence (drp_cloud_divergence_unbalanced_f64,
-drp_train_grad_f64_divergence_unbalanced; csrc/k_divergence_f64.h: kd64_sweeps_unbalanced): tests/_divergence_unbalanced_ref.py's
+drp_train_grad_f64_divergence_unbalanced; csrc/k_sinkhorn.h: kd64_sweeps_unbalanced): tests/_divergence_unbalanced_ref.py's
 definition with nothing in fp32 -- its pair64(None, q, eps, rho, w, K, p64=p) path: costs and differences in float64 from the
 float64 prediction and the float32 targets widened.
 

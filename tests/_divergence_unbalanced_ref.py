@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE of the unbalanced Sinkhorn divergence (drp_cloud_divergence_unbalanced, drp_train_step_divergence_unbalanced;
-csrc/k_divergence.h: kd_sweeps_unbalanced): include/drp.h's definition in numpy float64, operation for operation, on
+csrc/k_sinkhorn.h: kd_sweeps_unbalanced): include/drp.h's definition in numpy float64, operation for operation, on
 tests/_divergence_ref.py's helpers.  The terms of every sum are added in ascending index.
 
   reach (rho) > 0 in eps's unit, the target's total mass w:  a = 1 / n_p, b = w / n_q, lambda = rho / (rho + eps)

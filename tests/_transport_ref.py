@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE of the entropy-regularised transport loss (drp_cloud_transport, drp_train_step_transport;
-csrc/k_transport.h): include/drp.h's definition in numpy float64, operation for operation.
+csrc/k_sinkhorn.h): include/drp.h's definition in numpy float64, operation for operation.
 
   sinkhorn64(C, eps, K)            the K sweeps on a cost matrix -> (f, g): f = 0, then K times g's update and f's, each a
                                    max-shifted log-sum-exp whose terms are added in ascending index

@@ -1,4 +1,4 @@
-"""GPU: the stand-alone Sinkhorn divergence (drp_cloud_divergence, csrc/k_divergence.h) through ctypes, against include/drp.h's
+"""GPU: the stand-alone Sinkhorn divergence (drp_cloud_divergence, csrc/k_sinkhorn.h) through ctypes, against include/drp.h's
 definition in numpy float64 (tests/_divergence_ref.py) on the kernel's fp32 cost matrices.
 
 Both sides do the same IEEE double operations in the same order; they differ in the order the terms of a sum are added (the

@@ -1,4 +1,4 @@
-"""GPU: the float64 yardstick of the Sinkhorn divergence stand-alone (drp_cloud_divergence_f64, csrc/k_divergence_f64.h) through
+"""GPU: the float64 yardstick of the Sinkhorn divergence stand-alone (drp_cloud_divergence_f64, csrc/k_sinkhorn.h) through
 ctypes, against tests/_divergence_f64_ref.py's divergence64_wide: include/drp.h's definition in numpy float64 with nothing in fp32.
 
 p carries bits no float32 has -- _untracked_ref.chamfer_case's floats plus 1e-9 x a standard normal draw -- as the float64 tape's

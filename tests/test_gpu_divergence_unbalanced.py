@@ -1,4 +1,4 @@
-"""GPU: the unbalanced Sinkhorn divergence (drp_cloud_divergence_unbalanced; csrc/k_divergence.h: kd_sweeps_unbalanced and
+"""GPU: the unbalanced Sinkhorn divergence (drp_cloud_divergence_unbalanced; csrc/k_sinkhorn.h: kd_sweeps_unbalanced and
 kd_combine<false, true>) through ctypes, against include/drp.h's definition in numpy float64
 (tests/_divergence_unbalanced_ref.py) on the kernel's fp32 cost matrices.
 

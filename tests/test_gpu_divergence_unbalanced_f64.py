@@ -1,5 +1,5 @@
 """GPU: the float64 yardstick of the unbalanced Sinkhorn divergence stand-alone (drp_cloud_divergence_unbalanced_f64;
-csrc/k_divergence_f64.h: kd64_sweeps_unbalanced and kd64_combine_unbalanced) through ctypes, against
+csrc/k_sinkhorn.h: kd64_sweeps_unbalanced and kd64_combine_unbalanced) through ctypes, against
 tests/_divergence_unbalanced_f64_ref.py's divergence64_wide: include/drp.h's definition in numpy float64 with nothing in fp32.
 
 p carries bits no float32 has (tests/test_gpu_divergence_f64.py's wide_case), q is float32.  Both sides do the same IEEE double

@@ -1,4 +1,4 @@
-"""GPU: training with the Sinkhorn divergence (drp_train_step_divergence: kd_sweeps and kd_combine<true> of csrc/k_divergence.h
+"""GPU: training with the Sinkhorn divergence (drp_train_step_divergence: kd_sweeps and kd_combine<true> of csrc/k_sinkhorn.h
 where drp_train_step_transport launches kt_transport<true>; everything behind the loss gradient unchanged) through the C ABI, on
 tests/_transport_ref.py's train_batch: B = 2, H = 2, N = 9 (counts 9 and 6), M = 12 (target counts 12, 7 / 5, 10: above and below
 the predictions'), on both tapes and both impulse sources.

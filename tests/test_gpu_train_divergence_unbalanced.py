@@ -1,5 +1,5 @@
 """GPU: training with the unbalanced Sinkhorn divergence (drp_train_step_divergence_unbalanced: kd_sweeps_unbalanced and
-kd_combine<true, true> of csrc/k_divergence.h where drp_train_step_divergence launches the balanced pair; everything behind the
+kd_combine<true, true> of csrc/k_sinkhorn.h where drp_train_step_divergence launches the balanced pair; everything behind the
 loss gradient unchanged) through the C ABI, on tests/_transport_ref.py's train_batch -- B = 2, H = 2, N = 9 (counts 9 and 6),
 M = 12 (target counts 12, 7 / 5, 10) -- on both tapes, both impulse sources, the seed-0 and the trained weights, at
 rho = 4 eps with the targets' masses 1 ('unit') and target_nums / particle_nums ('count').

@@ -1,5 +1,5 @@
 """GPU, row u4: the training loop body with the Sinkhorn divergence in float64 on the device
-(drp_train_grad_f64_divergence: kd64_sweeps and kd64_combine of csrc/k_divergence_f64.h where drp_train_grad_f64 launches kt64_mse,
+(drp_train_grad_f64_divergence: kd64_sweeps and kd64_combine of csrc/k_sinkhorn.h where drp_train_grad_f64 launches kt64_mse,
 everything behind the seed unchanged), the probe that holds the fp32 tapes against it, and the trainer's hook.
 
 The batch is tests/_transport_ref.py's train_batch: B = 2, H = 2, N = 9 (counts 9 and 6), M = 12 with ragged target counts on both

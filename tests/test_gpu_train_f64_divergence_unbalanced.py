@@ -1,5 +1,5 @@
 """GPU: the training loop body with the UNBALANCED Sinkhorn divergence in float64 on the device
-(drp_train_grad_f64_divergence_unbalanced: kd64_sweeps_unbalanced and kd64_combine_unbalanced of csrc/k_divergence_f64.h where
+(drp_train_grad_f64_divergence_unbalanced: kd64_sweeps_unbalanced and kd64_combine_unbalanced of csrc/k_sinkhorn.h where
 drp_train_grad_f64_divergence launches the balanced pair, everything behind the seed unchanged), the probe that holds the fp32
 tapes against it, and the trainer's hook.
 

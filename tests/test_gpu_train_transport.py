@@ -1,4 +1,4 @@
-"""GPU: training with the entropy-regularised transport loss (drp_train_step_transport: kt_transport<true> of csrc/k_transport.h
+"""GPU: training with the entropy-regularised transport loss (drp_train_step_transport: kt_transport<true> of csrc/k_sinkhorn.h
 where drp_train_step_untracked launches kc_chamfer<true>; everything behind the loss gradient unchanged) through the C ABI, at
 B = 2, H = 2, N = 9 (counts 9 and 6), M = 12 (target counts 12, 7 / 5, 10: above and below the predictions') on both tapes and
 both impulse sources (tests/_transport_ref.py: train_batch).

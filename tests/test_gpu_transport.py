@@ -1,4 +1,4 @@
-"""GPU: the stand-alone entropy-regularised transport distance (drp_cloud_transport, csrc/k_transport.h) through ctypes, against
+"""GPU: the stand-alone entropy-regularised transport distance (drp_cloud_transport, csrc/k_sinkhorn.h) through ctypes, against
 include/drp.h's definition in numpy float64 (tests/_transport_ref.py) on the kernel's fp32 cost matrix.
 
 Both sides do the same IEEE double operations in the same order; they differ in the order the terms of a log-sum-exp are added

@@ -8,7 +8,9 @@ unchanged at either commit.  The cases:
   one-shots   cloud_chamfer, cloud_chamfer_f64, cloud_match, cloud_match_f64 (its own matching, and match_in = cloud_match's),
               cloud_transport, cloud_divergence and cloud_divergence_f64 (balanced, and with reach / mass_q / want_transported),
               every optional output, on one context in this order of (B, N, M): (3, 70, 130), (2, 5, 3), (1, 65, 64), (1, 1, 1),
-              (1, 64, 64); eps is a per-sample array where B > 1 and a number where B = 1
+              (1, 64, 64); eps is a per-sample array where B > 1 and a number where B = 1.  Behind them the Sinkhorn calls alone
+              where kt_parts (csrc/k_sinkhorn.h) changes regime: (1, 257, 300) -- one lane an output one way, two the other --,
+              (1, 16, 16) -- 16 outputs x 64 parts, exactly 1024 items -- and (1, 1024, 1024) at iters = 2
   fp32        the fixture batch b2_r5 (data impulses) and the push batches tiny and mask (tests/_train_actions_ref.py), every loss
               kind their entry points take -- train_step_transport, train_step_divergence (balanced and with a reach, want_err),
               train_predict + train_step_seeded and train_step_custom(losses.mse_loss) among them; mode='grad' (loss, blob, the
@@ -34,6 +36,7 @@ from dyn_res_pile_manip_amd import losses, weights
 from dyn_res_pile_manip_amd.engine import Engine
 
 ONE_SHOTS = (((70, 130, 70, 130), 3), ((5, 3, 5, 3), 2), ((65, 60, 65, 64), 1), ((1, 1, 1, 1), 1), ((64, 64, 64, 64), 1))
+PARTS_SHOTS = (((257, 300, 257, 300), 1, None), ((16, 16, 16, 16), 1, None), ((1024, 1024, 1024, 1024), 1, 2))     # iters: None = ITERS
 MIX = 0.3
 EPS = 4e-4                  # the one-shots' regularisation strength: the clouds' squared spacing (tests/_untracked_ref.chamfer_case)
 ITERS = 50
@@ -50,6 +53,23 @@ def show(label, value):
     print('%s %s %s %s' % (hashlib.sha256(a.tobytes()).hexdigest(), label, a.dtype, list(a.shape)))
 
 
+def sinkhorn_shots(eng, case, shape, B, iters):
+    """the five Sinkhorn one-shots on one case, every optional output"""
+    p, q, n_p, n_q = case
+    eps = EPS * (1.0 + 0.5 * np.arange(B)) if B > 1 else EPS
+    mass_q = np.clip(n_q / n_p.astype(np.float64), 0.125, 8.0)
+    want = {'want_grad': True, 'want_dual': True, 'want_col_err': True}
+    div = dict(want, want_self_err=True)
+    reach = dict(div, reach=REACH_PER_EPS * np.asarray(eps), mass_q=mass_q if B > 1 else float(mass_q[0]), want_transported=True)
+    for name, out in (('cloud_transport', eng.cloud_transport(*case, eps=eps, iters=iters, **want)),
+                      ('cloud_divergence', eng.cloud_divergence(*case, eps=eps, iters=iters, **div)),
+                      ('cloud_divergence reach', eng.cloud_divergence(*case, eps=eps, iters=iters, **reach)),
+                      ('cloud_divergence_f64', eng.cloud_divergence_f64(*case, eps=eps, iters=iters, **div)),
+                      ('cloud_divergence_f64 reach', eng.cloud_divergence_f64(*case, eps=eps, iters=iters, **reach))):
+        for k in sorted(out):
+            show('%s B=%d N=%d M=%d iters=%d %s' % (name, B, shape[2], shape[3], iters, k), out[k])
+
+
 def one_shots():
     eng = Engine(0)
     for shape, B in ONE_SHOTS:
@@ -59,23 +79,15 @@ def one_shots():
                           ('cloud_match', eng.cloud_match(*case, want_grad=True, want_match=True, want_dual=True))):
             for k in sorted(out):
                 show('%s B=%d N=%d M=%d %s' % (name, B, shape[2], shape[3], k), out[k])
-        p, q, n_p, n_q = case
-        eps = EPS * (1.0 + 0.5 * np.arange(B)) if B > 1 else EPS
-        mass_q = np.clip(n_q / n_p.astype(np.float64), 0.125, 8.0)
-        want = {'want_grad': True, 'want_dual': True, 'want_col_err': True}
-        div = dict(want, want_self_err=True)
-        reach = dict(div, reach=REACH_PER_EPS * np.asarray(eps), mass_q=mass_q if B > 1 else float(mass_q[0]), want_transported=True)
         pairs = eng.cloud_match(*case, want_match=True)['match_pq']
-        for name, out in (('cloud_transport', eng.cloud_transport(*case, eps=eps, iters=ITERS, **want)),
-                          ('cloud_divergence', eng.cloud_divergence(*case, eps=eps, iters=ITERS, **div)),
-                          ('cloud_divergence reach', eng.cloud_divergence(*case, eps=eps, iters=ITERS, **reach)),
-                          ('cloud_divergence_f64', eng.cloud_divergence_f64(*case, eps=eps, iters=ITERS, **div)),
-                          ('cloud_divergence_f64 reach', eng.cloud_divergence_f64(*case, eps=eps, iters=ITERS, **reach)),
-                          ('cloud_match_f64', eng.cloud_match_f64(*case, want_grad=True, want_match=True, want_dual=True)),
+        sinkhorn_shots(eng, case, shape, B, ITERS)
+        for name, out in (('cloud_match_f64', eng.cloud_match_f64(*case, want_grad=True, want_match=True, want_dual=True)),
                           ('cloud_match_f64 match_in', eng.cloud_match_f64(*case, match_in=pairs, want_grad=True, want_match=True,
                                                                            want_dual=True))):
             for k in sorted(out):
                 show('%s B=%d N=%d M=%d %s' % (name, B, shape[2], shape[3], k), out[k])
+    for shape, B, iters in PARTS_SHOTS:
+        sinkhorn_shots(eng, U.chamfer_case(shape, B), shape, B, iters or ITERS)
     eng.close()
 
 

@@ -16,8 +16,8 @@
 // divergence_layout's five blocks that come back staged the same way, eps and the kernels' scratch behind them written in full
 // inside a block of exactly its `bytes`, and the trainer's doubles (tr_div_loss_layout) likewise.  Its float64 yardstick: eps [B]
 // (doubles) behind the float64 upload on an even word (tr64_layout with `eps`), nothing ahead of it moved, and
-// drp_cloud_divergence_f64's buffer of its own (divergence64_layout: p as doubles), every block written in full; the finiteness
-// check on double rows.  The matching losses' float64 yardstick: the caller's partners [H][B][N] behind the float64 upload
+// drp_cloud_divergence_f64's buffer (divergence_layout with 8-byte elements: p and the gradient as doubles, staged through the same
+// cloud_layout as every one-shot), every block written in full; the finiteness check on double rows.  The matching losses' float64 yardstick: the caller's partners [H][B][N] behind the float64 upload
 // (tr64_layout with `match_in`), drp_cloud_match_f64's buffer of its own (match64_layout, with and without match_in), and the
 // check of a matching given by the caller (check_matching) on arrays of exactly [N].  The unbalanced Sinkhorn divergence:
 // divergence_layout with `reach` (eps | rho | mass_q side by side, the scratch, transported, inside a block of exactly its `bytes`,
@@ -25,8 +25,7 @@
 // with `reach`) and transported behind its doubles (tr_div_loss_layout with `unbalanced`), nothing ahead of them moved, and the
 // check of a reach and a target mass (check_reach) at the edges of its ranges.  Its float64 yardstick: rho [B] | mass_q [H][B]
 // (doubles) behind eps in the float64 upload (tr64_layout with `reach`), and drp_cloud_divergence_unbalanced_f64's buffer
-// (divergence64_layout with `reach`: rho | mass_q between eps and q, transported behind the scratch), nothing else moved
-// relative to one another.  The seeded step: the caller's d loss / d s_pred [B][H][N][3] behind a training batch (tr_layout with
+// (divergence_layout with `reach` and 8-byte elements: the same blocks, every double on a multiple of 8).  The seeded step: the caller's d loss / d s_pred [B][H][N][3] behind a training batch (tr_layout with
 // `seed`: floats, 16-byte aligned) and behind the float64 upload (tr64_layout with `seed`: doubles on a multiple of four words),
 // staged as train_stage_batch and train_grad_f64_body stage them and read back as kt_seed_given and k64_seed_given address them,
 // nothing ahead of either moved and a call without a seed taking no byte for it; and the scan that refuses a real row of a seed
@@ -168,49 +167,6 @@ static void stage64_eps(int B, int H, int N, int M, bool actions) {
     std::free(host);
 }
 
-// drp_cloud_divergence_f64's buffer: the inputs (p as doubles, eps among them) staged into a vector of exactly in_bytes, the five
-// blocks that come back and the kernels' scratch written in full inside a block of exactly `bytes`
-static void stage_divergence64(int B, int N, int M) {
-    const size_t bn = (size_t)B * N, bm = (size_t)B * M;
-    const Div64Layout lay = divergence64_layout(B, N, M);
-    const size_t off[] = {lay.pts_p, lay.eps, lay.pts_q, lay.n_p, lay.n_q, lay.out[0], lay.out[1], lay.out[2], lay.out[3], lay.out[4],
-                          lay.vals, lay.gsum, lay.bytes};
-    const size_t len[] = {bn * 24, (size_t)B * 8, bm * 12, (size_t)B * 4, (size_t)B * 4, (size_t)B * 8, bn * 24, 2 * (bn + bm) * 8,
-                          (size_t)B * 8, (size_t)B * 16, (size_t)3 * B * 8, 2 * bn * 24};
-    for (int k = 0; k < 12; ++k) {
-        EXPECT(off[k] % 16 == 0);
-        EXPECT(off[k] + len[k] <= off[k + 1] && off[k + 1] - (off[k] + len[k]) < 16);
-        if (k >= 5 && k < 10) EXPECT(lay.out_bytes[k - 5] == len[k]);
-    }
-    EXPECT(lay.pts_p == 0 && lay.out[0] == lay.in_bytes);
-    std::vector<double> p(bn * 3, 1.0), eps(B, 0.5);
-    std::vector<float> q(bm * 3, 2.0f);
-    std::vector<int32_t> n_p(B, N), n_q(B, M);
-    std::vector<char> stage(lay.in_bytes);
-    std::memcpy(stage.data() + lay.pts_p, p.data(), bn * 3 * sizeof(double));
-    std::memcpy(stage.data() + lay.eps, eps.data(), (size_t)B * sizeof(double));
-    std::memcpy(stage.data() + lay.pts_q, q.data(), bm * 3 * sizeof(float));
-    std::memcpy(stage.data() + lay.n_p, n_p.data(), (size_t)B * sizeof(int32_t));
-    std::memcpy(stage.data() + lay.n_q, n_q.data(), (size_t)B * sizeof(int32_t));
-    char* io = static_cast<char*>(std::malloc(lay.bytes));
-    std::memcpy(io, stage.data(), lay.in_bytes);
-    for (int k = 5; k < 12; ++k) std::memset(io + off[k], k, len[k]);          // the kernels' stores, block by block
-    double d; float f; int32_t n;
-    std::memcpy(&d, io + lay.pts_p + (bn * 3 - 1) * 8, 8);
-    EXPECT(d == 1.0);
-    std::memcpy(&d, io + lay.eps + (size_t)(B - 1) * 8, 8);
-    EXPECT(d == 0.5);
-    std::memcpy(&f, io + lay.pts_q + (bm * 3 - 1) * 4, 4);
-    EXPECT(f == 2.0f);
-    std::memcpy(&n, io + lay.n_q + (size_t)(B - 1) * 4, 4);
-    EXPECT(n == M);
-    for (int k = 5; k < 12; ++k) EXPECT(io[off[k]] == k && io[off[k] + len[k] - 1] == k);
-    // the last row's last gradient sum of the second problem set and the last value sum, where kd64_sweeps stores them
-    reinterpret_cast<double*>(io + lay.gsum)[((size_t)B + (B - 1)) * N * 3 + (size_t)(N - 1) * 3 + 2] = 1.0;
-    reinterpret_cast<double*>(io + lay.vals)[2 * (size_t)B + (B - 1)] = 1.0;
-    std::free(io);
-}
-
 // drp_train_grad_f64_divergence_unbalanced's upload: rho [B] | mass_q [H][B] (doubles) behind eps, 8-byte aligned, everything ahead
 // of them where it was; both written and read back as the kernels address them, in a block of exactly `words`
 static void stage64_reach(int B, int H, int N, int M, bool actions) {
@@ -231,52 +187,6 @@ static void stage64_reach(int B, int H, int N, int M, bool actions) {
     const double* m = reinterpret_cast<const double*>(host + lay.mass_q);
     EXPECT(r[0] == 0.25 && r[B - 1] == 0.25 && m[0] == 1.5 && m[(size_t)(H - 1) * B + (B - 1)] == 1.5);
     std::free(host);
-}
-
-// drp_cloud_divergence_unbalanced_f64's buffer: divergence64_layout's with rho | mass_q between eps and q and transported behind
-// the scratch; every block staged or written in full inside a block of exactly `bytes`
-static void stage_divergence64_reach(int B, int N, int M) {
-    const size_t bn = (size_t)B * N, bm = (size_t)B * M;
-    const Div64Layout lay = divergence64_layout(B, N, M, true), plain = divergence64_layout(B, N, M);
-    const size_t off[] = {lay.pts_p, lay.eps, lay.rho, lay.mass_q, lay.pts_q, lay.n_p, lay.n_q, lay.out[0], lay.out[1], lay.out[2],
-                          lay.out[3], lay.out[4], lay.vals, lay.gsum, lay.transported, lay.bytes};
-    const size_t len[] = {bn * 24, (size_t)B * 8, (size_t)B * 8, (size_t)B * 8, bm * 12, (size_t)B * 4, (size_t)B * 4, (size_t)B * 8,
-                          bn * 24, 2 * (bn + bm) * 8, (size_t)B * 8, (size_t)B * 16, (size_t)3 * B * 8, 2 * bn * 24, (size_t)B * 8};
-    for (int k = 0; k < 15; ++k) {
-        EXPECT(off[k] % 16 == 0);
-        EXPECT(off[k] + len[k] <= off[k + 1] && off[k + 1] - (off[k] + len[k]) < 16);
-        if (k >= 7 && k < 12) EXPECT(lay.out_bytes[k - 7] == len[k]);
-    }
-    EXPECT(lay.pts_p == 0 && lay.eps == plain.eps && lay.out[0] == lay.in_bytes);
-    EXPECT(plain.rho == 0 && plain.mass_q == 0 && plain.transported == 0);
-    std::vector<double> p(bn * 3, 1.0), eps(B, 0.5), rho(B, 0.25), w(B, 1.5);
-    std::vector<float> q(bm * 3, 2.0f);
-    std::vector<int32_t> n_p(B, N), n_q(B, M);
-    std::vector<char> stage(lay.in_bytes);
-    std::memcpy(stage.data() + lay.pts_p, p.data(), bn * 3 * sizeof(double));
-    std::memcpy(stage.data() + lay.eps, eps.data(), (size_t)B * sizeof(double));
-    std::memcpy(stage.data() + lay.rho, rho.data(), (size_t)B * sizeof(double));
-    std::memcpy(stage.data() + lay.mass_q, w.data(), (size_t)B * sizeof(double));
-    std::memcpy(stage.data() + lay.pts_q, q.data(), bm * 3 * sizeof(float));
-    std::memcpy(stage.data() + lay.n_p, n_p.data(), (size_t)B * sizeof(int32_t));
-    std::memcpy(stage.data() + lay.n_q, n_q.data(), (size_t)B * sizeof(int32_t));
-    char* io = static_cast<char*>(std::malloc(lay.bytes));
-    std::memcpy(io, stage.data(), lay.in_bytes);
-    for (int k = 7; k < 15; ++k) std::memset(io + off[k], k, len[k]);          // the kernels' stores, block by block
-    double d; float f; int32_t n;
-    std::memcpy(&d, io + lay.eps + (size_t)(B - 1) * 8, 8);
-    EXPECT(d == 0.5);
-    std::memcpy(&d, io + lay.rho + (size_t)(B - 1) * 8, 8);
-    EXPECT(d == 0.25);
-    std::memcpy(&d, io + lay.mass_q + (size_t)(B - 1) * 8, 8);
-    EXPECT(d == 1.5);
-    std::memcpy(&f, io + lay.pts_q + (bm * 3 - 1) * 4, 4);
-    EXPECT(f == 2.0f);
-    std::memcpy(&n, io + lay.n_q + (size_t)(B - 1) * 4, 4);
-    EXPECT(n == M);
-    for (int k = 7; k < 15; ++k) EXPECT(io[off[k]] == k && io[off[k] + len[k] - 1] == k);
-    reinterpret_cast<double*>(io + lay.transported)[B - 1] = 1.0;              // where kd64_sweeps_unbalanced stores the last one
-    std::free(io);
 }
 
 // drp_train_grad_f64_match's upload: the caller's partners [H][B][N] (ints) behind everything else, the other blocks where they were
@@ -362,12 +272,13 @@ static void check_matchings() {
 
 // a one-shot's buffer as cloud_begin and the kernel use it (capi_pipeline.h): the inputs copied into a vector of exactly
 // CloudLayout::in_bytes, every output block written in full inside a block of exactly CloudLayout::bytes; len: the n_out blocks'
-// sizes, restated by the caller
-static void stage_cloud(const CloudLayout& lay, int B, int N, int M, int n_out, const size_t* out_len) {
+// sizes, restated by the caller; p_elem: bytes of one of p's elements (floats, or the float64 divergence's doubles)
+static void stage_cloud(const CloudLayout& lay, int B, int N, int M, int n_out, const size_t* out_len, size_t p_elem = 4) {
     const size_t bn = (size_t)B * N, bm = (size_t)B * M;
     EXPECT(lay.n_out == n_out);
     size_t off[4 + CLOUD_MAX_OUT + 1] = {lay.pts_p, lay.pts_q, lay.n_p, lay.n_q};
-    size_t len[4 + CLOUD_MAX_OUT] = {bn * 12, bm * 12, (size_t)B * 4, (size_t)B * 4};
+    size_t len[4 + CLOUD_MAX_OUT] = {bn * 3 * p_elem, bm * 12, (size_t)B * 4, (size_t)B * 4};
+    EXPECT(lay.p_elem == p_elem);
     for (int k = 0; k < n_out; ++k) {
         off[4 + k] = lay.out[k];
         len[4 + k] = out_len[k];
@@ -382,18 +293,24 @@ static void stage_cloud(const CloudLayout& lay, int B, int N, int M, int n_out, 
     }
     EXPECT(lay.pts_p == 0 && lay.out[0] == lay.in_bytes);
     std::vector<float> p(bn * 3, 1.0f), q(bm * 3, 2.0f);
+    std::vector<double> p64(bn * 3, 1.0);
     std::vector<int32_t> n_p(B, N), n_q(B, M);
     std::vector<char> stage(lay.in_bytes);
-    std::memcpy(stage.data() + lay.pts_p, p.data(), bn * 3 * sizeof(float));
+    std::memcpy(stage.data() + lay.pts_p, p_elem == 8 ? (const void*)p64.data() : (const void*)p.data(), bn * 3 * p_elem);     // as cloud_begin does
     std::memcpy(stage.data() + lay.pts_q, q.data(), bm * 3 * sizeof(float));
     std::memcpy(stage.data() + lay.n_p, n_p.data(), (size_t)B * sizeof(int32_t));
     std::memcpy(stage.data() + lay.n_q, n_q.data(), (size_t)B * sizeof(int32_t));
     char* io = static_cast<char*>(std::malloc(lay.bytes));
     std::memcpy(io, stage.data(), lay.in_bytes);
     for (int k = 4; k < nb; ++k) std::memset(io + off[k], k, len[k]);      // the kernel's stores, block by block
-    float f; int32_t n;
-    std::memcpy(&f, io + lay.pts_p + (bn * 3 - 1) * 4, 4);
-    EXPECT(f == 1.0f);
+    float f; double d; int32_t n;
+    if (p_elem == 8) {
+        std::memcpy(&d, io + lay.pts_p + (bn * 3 - 1) * 8, 8);
+        EXPECT(d == 1.0);
+    } else {
+        std::memcpy(&f, io + lay.pts_p + (bn * 3 - 1) * 4, 4);
+        EXPECT(f == 1.0f);
+    }
     std::memcpy(&f, io + lay.pts_q + (bm * 3 - 1) * 4, 4);
     EXPECT(f == 2.0f);
     std::memcpy(&n, io + lay.n_q + (size_t)(B - 1) * 4, 4);
@@ -413,14 +330,14 @@ static void stage_transport(int B, int N, int M) {
     stage_cloud(transport_layout(B, N, M), B, N, M, 5, len);
 }
 // drp_cloud_divergence: five output blocks as a one-shot's; behind them eps [B], the value sums [3][B] and the gradient sums
-// [2][B][N][3], which the kernels write and nothing reads back
-static void stage_divergence(int B, int N, int M) {
+// [2][B][N][3], which the kernels write and nothing reads back.  p_elem 8: drp_cloud_divergence_f64, p and the gradient as doubles
+static void stage_divergence(int B, int N, int M, size_t p_elem) {
     const size_t bn = (size_t)B * N, bm = (size_t)B * M;
-    const DivLayout lay = divergence_layout(B, N, M);
-    const size_t len[] = {(size_t)B * 8, bn * 12, 2 * (bn + bm) * 8, (size_t)B * 8, (size_t)B * 16};
+    const DivLayout lay = divergence_layout(B, N, M, false, p_elem);
+    const size_t len[] = {(size_t)B * 8, bn * 3 * p_elem, 2 * (bn + bm) * 8, (size_t)B * 8, (size_t)B * 16};
     CloudLayout back = lay.cloud;
     back.bytes = lay.eps;                                            // what comes back ends where eps starts
-    stage_cloud(back, B, N, M, 5, len);
+    stage_cloud(back, B, N, M, 5, len, p_elem);
     const size_t off[] = {lay.eps, lay.vals, lay.gsum, lay.cloud.bytes};
     const size_t xlen[] = {(size_t)B * 8, (size_t)3 * B * 8, 2 * bn * 3 * 8};
     char* io = static_cast<char*>(std::malloc(lay.cloud.bytes));
@@ -452,14 +369,16 @@ static void stage_div_loss(int B, int H, int N) {
     std::free(d);
 }
 // drp_cloud_divergence_unbalanced (divergence_layout with `reach`): the five blocks where they were; behind them eps | rho | mass_q [B] each, side
-// by side (one copy up), the same scratch, then transported [B], all inside a block of exactly `bytes`
-static void stage_divergence_unbalanced(int B, int N, int M) {
+// by side (one copy up), the same scratch, then transported [B], all inside a block of exactly `bytes`.  p_elem 8:
+// drp_cloud_divergence_unbalanced_f64
+static void stage_divergence_unbalanced(int B, int N, int M, size_t p_elem) {
     const size_t bn = (size_t)B * N;
-    const DivLayout lay = divergence_layout(B, N, M, true), plain = divergence_layout(B, N, M);
+    const DivLayout lay = divergence_layout(B, N, M, true, p_elem), plain = divergence_layout(B, N, M, false, p_elem);
     EXPECT(plain.rho == 0 && plain.mass_q == 0 && plain.transported == 0 && plain.vals < lay.vals);
     for (int k = 0; k < CLOUD_MAX_OUT; ++k) EXPECT(lay.cloud.out[k] == plain.cloud.out[k] && lay.cloud.out_bytes[k] == plain.cloud.out_bytes[k]);
     EXPECT(lay.cloud.in_bytes == plain.cloud.in_bytes && lay.cloud.n_out == plain.cloud.n_out && lay.eps == plain.eps);
     EXPECT(lay.rho == lay.eps + (size_t)B * 8 && lay.mass_q == lay.rho + (size_t)B * 8);
+    EXPECT(lay.cloud.out[1] % 8 == 0 && lay.rho % 8 == 0 && lay.mass_q % 8 == 0);      // every double on a multiple of 8
     const size_t off[] = {lay.eps, lay.vals, lay.gsum, lay.transported, lay.cloud.bytes};
     const size_t xlen[] = {(size_t)3 * B * 8, (size_t)3 * B * 8, 2 * bn * 3 * 8, (size_t)B * 8};
     char* io = static_cast<char*>(std::malloc(lay.cloud.bytes));
@@ -655,10 +574,10 @@ int main(int argc, char** argv) {
     for (const auto& s : mshapes) {
         stage_match(s[0], s[1], s[2]);
         stage_transport(s[0], s[1], s[2]);
-        stage_divergence(s[0], s[1], s[2]);
-        stage_divergence_unbalanced(s[0], s[1], s[2]);
-        stage_divergence64(s[0], s[1], s[2]);
-        stage_divergence64_reach(s[0], s[1], s[2]);
+        for (size_t p_elem : {sizeof(float), sizeof(double)}) {
+            stage_divergence(s[0], s[1], s[2], p_elem);
+            stage_divergence_unbalanced(s[0], s[1], s[2], p_elem);
+        }
         stage_match64(s[0], s[1], s[2], false);
         stage_match64(s[0], s[1], s[2], true);
     }

@@ -1,4 +1,4 @@
-"""Time the entropy-regularised transport loss (csrc/k_transport.h) next to the Chamfer and the matching loss it stands beside
+"""Time the entropy-regularised transport loss (csrc/k_sinkhorn.h) next to the Chamfer and the matching loss it stands beside
 -> profiles/transport_timing.txt.
 
   python tools/transport_timing.py [output file]
@@ -10,17 +10,17 @@
     context: host time of the call (it returns when the step is complete on the device), the median of 6 blocks of 10 after
     warm-up, as tools/match_timing.py measures its steps.
 (c) python tools/transport_timing.py --divergence [output file] -> profiles/divergence_timing.txt: the Sinkhorn divergence
-    (csrc/k_divergence.h: kd_sweeps and kd_combine, one timed region) beside kt_transport on the same clouds, 20 problems at
+    (csrc/k_sinkhorn.h: kd_sweeps and kd_combine, one timed region) beside kt_transport on the same clouds, 20 problems at
     100 x 100 and 300 x 300, measured as (a); and a whole update at 4 x 5 x 100 under 'transport' and 'sinkhorn', measured as (b).
 (d) python tools/transport_timing.py --divergence-f64 [output file] -> profiles/divergence_f64_timing.txt: the float64 yardstick
-    (csrc/k_divergence_f64.h: kd64_sweeps and kd64_combine, one timed region) beside kd_sweeps + kd_combine on the same clouds
+    (csrc/k_sinkhorn.h: kd64_sweeps and kd64_combine, one timed region) beside kd_sweeps + kd_combine on the same clouds
     (p widened exactly), 20 problems at 100 x 100 and 300 x 300, measured as (a).  A yardstick's cost, not an engine's.
 (e) python tools/transport_timing.py --unbalanced [output file] -> profiles/divergence_unbalanced_timing.txt: the unbalanced
     divergence (kd_sweeps_unbalanced and kd_combine, one timed region; rho = 4 eps) beside the balanced kernels, interleaved on
     one context on the same clouds, 20 problems at 100 x 100 and 300 x 300, measured as (a); and a whole update at 4 x 5 x 100
     under 'sinkhorn' with and without a reach, measured as (b).
 (f) python tools/transport_timing.py --unbalanced --f64 [output file] -> profiles/divergence_unbalanced_f64_timing.txt: the
-    unbalanced float64 yardstick (csrc/k_divergence_f64.h: kd64_sweeps_unbalanced and kd64_combine_unbalanced, one timed region;
+    unbalanced float64 yardstick (csrc/k_sinkhorn.h: kd64_sweeps_unbalanced and kd64_combine_unbalanced, one timed region;
     rho = 4 eps) beside the balanced kd64 pair, interleaved on one context on the same clouds, 20 problems at 100 x 100 and
     300 x 300, measured as (a); and a whole Engine.train_gradient_probe call at 4 x 5 x 100 under 'sinkhorn' with and without a
     reach, measured as (b) in blocks of 3.  With --ab OLD.so NEW.so behind it (libraries as tools/ab.sh takes them: paths from the
