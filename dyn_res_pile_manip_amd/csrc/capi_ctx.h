@@ -330,7 +330,6 @@ struct drp_ctx {
 
     DevBuf cloud_io;                // drp_cloud_chamfer, drp_cloud_chamfer_f64, drp_cloud_match (capi_pipeline.h: cloud_begin; one-shots that
                                     // end in a wait and keep nothing between calls): the running call's inputs and results
-    DevBuf tr_match;                // drp_train_step_loss: the partner of every predicted row [H][B][N] (ka_match<true>)
     bool ka64_ready = false;        // ka64_match's dynamic LDS size is set (capi_match_f64.h: ka64_run, at first use)
 
     // re-packing after an optimiser step on the device (k_train.h): gather maps of the plain packers, pinned copy of the blob

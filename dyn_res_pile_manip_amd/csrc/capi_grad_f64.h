@@ -276,60 +276,95 @@ struct Tr64Ws {
     F64Tape tape;
     F64Rev rev;
     F64Wgrad wg;
-    double *div_vals, *div_gsum;    // the Sinkhorn divergence (`div`): kd64_sweeps' scratch, [3][H][bc] and [2][H][bc][N][3]
-    size_t carve(void* base, size_t bc, size_t N, size_t H, bool div = false) {  // -> its bytes
+    double *div_vals, *div_gsum;    // the Sinkhorn divergence: kd64_sweeps' scratch, the table's two scratch rows at B = bc
+    size_t carve(void* base, size_t bc, size_t N, size_t H, const TrShape& shape) {  // -> its bytes
         F64Carver a{static_cast<char*>(base)};
         const size_t pn = bc * N, en = pn * DRP_K;
+        const TrBlocks t = tr_blocks(shape, (int)bc, (int)H, (int)N, false, true);
         tape.carve(a, pn, H);
         rev.carve(a, bc, N, H, 0);
         a.take(wg.pr_h, pn * 64); a.take(wg.pr_gh, pn * 64); a.take(wg.pe_h, pn * 64); a.take(wg.pe_gh, pn * 64); a.take(wg.pe_in, pn * 5);
         a.take(wg.re_h1, en * 64); a.take(wg.re_h2, en * 64); a.take(wg.re_g1, en * 64); a.take(wg.re_g2, en * 64); a.take(wg.re_in, en * 6);
         a.take(wg.acc, bc * (size_t)W_TOTAL);
-        a.take(div_vals, div ? 3 * H * bc : 0); a.take(div_gsum, div ? 2 * H * pn * 3 : 0);
+        a.take(div_vals, t.count[TRB_VALS]); a.take(div_gsum, t.count[TRB_GSUM]);
         return a.off;
     }
 };
 
-// the batch on the device: the caller's arrays, a_cur = attrs[:, 0] gathered, then the results
+// the batch on the device beside the loss's blocks (train_host.h: TrView): the caller's arrays with a_cur = attrs[:, 0] gathered,
+// and the weight-gradient sums
 struct Tr64Io {
     const float *states, *sdelta, *attr, *dens;     // sdelta: the impulses [B][H][N][3], or with `actions` the pushes [B][H][4]
     bool actions;
     const int* nums;
-    const float* targets;           // the Chamfer loss (M > 0): the target clouds [B][H][M][3] and their counts [B][H]; else null
-    const int* tnums;
-    int M;
-    double *terms, *total;          // [H][B], [W_TOTAL]
-    double* margin;                 // the Chamfer loss: [H][B], every (step, sample)'s smallest arg-min margin
-    const double* eps;              // the Sinkhorn divergence (non-null): the regularisation strengths [B], with `iters` sweeps,
-    int iters;                      //   against the same targets; its certificates behind the total: col_err [H][B], self_err [H][B][2]
-    double *col_err, *self_err;
-    const double *rho, *mass_q;     // the unbalanced divergence (non-null): the reaches [B] and the targets' masses [H][B] of the
-    double* transported;            //   BATCH (the kernels index them by b_off + b), and behind self_err transported [H][B]
-    int match_kind;                 // the matching losses (TR_LOSS_MATCH, TR_LOSS_CHAMFER_MATCH; else 0) against the same targets:
-    double match_weight;            //   the mix's weight; the caller's pairs [H][B][N] (nullable: the kernel's own optimum); behind
-    const int* match_in;            //   the margins the costs [H][B][2] and the optimum's partners [H][B][N]
-    double* cost;
-    int* match_out;
-    const double* seed;             // TR_LOSS_GIVEN (non-null): the caller's seed of the BATCH [B][H][N][3] in the loss kernel's place
+    double* total;                  // [W_TOTAL]
     bool predict;                   // the forward alone: the chunk's predictions to the caller, no loss, nothing reversed
 };
 
-// the matching kernel's arguments for a chunk: p, the seed and its padding are the chunk's, everything else the batch's (b_off)
-Ka64Args tr64_match_args(const Tr64Ws& k, const Tr64Io& io, int b0, int bc, int N, int B, int H, double scale, double keep) {
-    Ka64Args a{};
+// Every step's loss term and its seed of the reverse pass for the samples [b0, b0 + bc): whatever the kind, the same slot of the
+// stream, the same grid (bc, H), the same seed buffer and terms; p and the seed are the chunk's (the tape's own double states),
+// every block of `v` the BATCH's (the kernels index them by b_off + b)
+int tr64_launch_loss(drp_ctx* c, const Tr64Ws& k, const Tr64Io& io, const TrLoss& lk, const TrView& v, int b0, int bc, int N, int B, int H) {
+    hipStream_t st = c->stream;
     const size_t pn = (size_t)bc * N;
-    a.cp = tr_cloud_pair((size_t)N * 3, pn * 3, io.nums, io.targets, io.tnums, H, N, io.M);
-    a.pred = k.tape.state + pn * 3;
-    a.b_off = b0; a.B = B;
-    a.scale = scale; a.keep = keep;
-    a.match_in = io.match_in;
-    a.grad = k.rev.g_state; a.terms = io.terms; a.match_pq = io.match_out; a.cost = io.cost;
-    return a;
+    const double scale = 1.0 / ((double)H * (double)B);
+    const dim3 grid(bc, H);
+    if (lk.given()) {                   // the caller's seed at the chunk's sample offset, no term
+        hipLaunchKernelGGL(k64_seed_given, grid, dim3(256), 0, st, static_cast<const double*>(v.seed), io.nums, b0, bc, N, H, k.rev.g_state);
+        return DRP_OK;
+    }
+    if (lk.kind == TR_LOSS_MSE) {
+        hipLaunchKernelGGL(kt64_mse, grid, dim3(256), 0, st, k.tape.state, io.states, io.nums, b0, bc, B, N, H, v.terms, k.rev.g_state);
+        return DRP_OK;
+    }
+    // slice t + 1 of the tape's states against step t of the target clouds
+    const CloudPair cp = tr_cloud_pair((size_t)N * 3, pn * 3, io.nums, v.targets, v.tnums, H, N, lk.M);
+    if (lk.divergence()) {              // the plans from the tape's own double states (k_sinkhorn.h)
+        SkArgs64 a{};
+        a.cp = cp; a.pred = k.tape.state + pn * 3;
+        a.b_off = b0; a.B = B;
+        a.eps = v.eps; a.iters = lk.iters;
+        a.scale = scale;
+        a.vals = k.div_vals; a.gsum = k.div_gsum;
+        a.grad = k.rev.g_state; a.terms = v.terms; a.col_err = v.col_err; a.self_err = v.self_err;
+        if (lk.unbalanced()) {
+            a.rho = v.rho; a.mass_q = v.mass_q; a.transported = v.transported;
+            hipLaunchKernelGGL(kd64_sweeps_unbalanced, dim3(bc, H, 3), dim3(KT_THREADS), 0, st, a);
+            hipLaunchKernelGGL(kd64_combine_unbalanced, grid, dim3(KD_COMBINE_THREADS), 0, st, a);
+        } else {
+            hipLaunchKernelGGL(kd64_sweeps, dim3(bc, H, 3), dim3(KT_THREADS), 0, st, a);
+            hipLaunchKernelGGL(kd64_combine, grid, dim3(KD_COMBINE_THREADS), 0, st, a);
+        }
+        return DRP_OK;
+    }
+    if (lk.chamfer()) {                 // the arg-mins taken here in double
+        Kc64Args a{};
+        a.cp = cp; a.p64 = k.tape.state + pn * 3;
+        a.b_off = b0; a.B = B;
+        a.scale = scale;
+        a.grad = k.rev.g_state; a.terms = v.terms; a.margin = v.margin;
+        hipLaunchKernelGGL((kc64_chamfer<true>), grid, dim3(KC64_THREADS), 0, st, a);
+    }
+    if (lk.match()) {
+        // the assignment solved here in double (k_match_f64.h), the term and the seed on the caller's pairs where there are any.  The
+        // mix: behind a Chamfer-only step's terms and seed the kernel turns each element into (1 - w) x it + w x its own share, in
+        // double: one writer per element, stream order (the fp32 trainer's scheme)
+        Ka64Args a{};
+        a.cp = cp; a.pred = k.tape.state + pn * 3;
+        a.b_off = b0; a.B = B;
+        a.scale = lk.chamfer() ? scale * lk.match_weight : scale;
+        a.keep = lk.chamfer() ? 1.0 - lk.match_weight : 0.0;
+        a.match_in = v.match_in;
+        a.grad = k.rev.g_state; a.terms = v.terms; a.match_pq = v.match; a.cost = v.cost;
+        CHK(ka64_run(c, grid, a));
+    }
+    return DRP_OK;
 }
 
 // forward with tape, loss, reverse pass with weight gradients of the samples [b0, b0 + bc): launches and the state gradient's copy
 // (io.predict: grad_state_out receives the predictions [B][H][N][3] instead -- the tape's slices 1..H lie as the seed does)
-int tr64_chunk(drp_ctx* c, const Tr64Ws& k, const Tr64Io& io, int b0, int bc, int N, int B, int H, double* grad_state_out) {
+int tr64_chunk(drp_ctx* c, const Tr64Ws& k, const Tr64Io& io, const TrLoss& lk, const TrView& v, int b0, int bc, int N, int B, int H,
+               double* grad_state_out) {
     hipStream_t st = c->stream;
     const size_t pn = (size_t)bc * N;
     const dim3 lin3((unsigned)((pn * 3 + 255) / 256));
@@ -347,48 +382,7 @@ int tr64_chunk(drp_ctx* c, const Tr64Ws& k, const Tr64Io& io, int b0, int bc, in
     }));
     if (io.predict) return f64_copy_state_grad(c, k.tape.state + pn * 3, b0, bc, N, H, grad_state_out);
     // ---- every step's loss term and its seed of the reverse pass; the samples' accumulators start at zero
-    if (io.seed != nullptr) {
-        // the same slot of the stream and the same seed buffer: the caller's seed at the chunk's sample offset, no term
-        hipLaunchKernelGGL(k64_seed_given, dim3(bc, H), dim3(256), 0, st, io.seed, io.nums, b0, bc, N, H, k.rev.g_state);
-    } else if (io.eps != nullptr) {
-        // the same slot of the stream and the same outputs: the plans from the tape's own double states (k_sinkhorn.h)
-        SkArgs64 a{};
-        a.cp = tr_cloud_pair((size_t)N * 3, pn * 3, io.nums, io.targets, io.tnums, H, N, io.M);
-        a.pred = k.tape.state + pn * 3;
-        a.b_off = b0; a.B = B;
-        a.eps = io.eps; a.iters = io.iters;
-        a.scale = 1.0 / ((double)H * (double)B);
-        a.vals = k.div_vals; a.gsum = k.div_gsum;
-        a.grad = k.rev.g_state; a.terms = io.terms; a.col_err = io.col_err; a.self_err = io.self_err;
-        if (io.rho != nullptr) {
-            a.rho = io.rho; a.mass_q = io.mass_q; a.transported = io.transported;
-            hipLaunchKernelGGL(kd64_sweeps_unbalanced, dim3(bc, H, 3), dim3(KT_THREADS), 0, st, a);
-            hipLaunchKernelGGL(kd64_combine_unbalanced, dim3(bc, H), dim3(KD_COMBINE_THREADS), 0, st, a);
-        } else {
-            hipLaunchKernelGGL(kd64_sweeps, dim3(bc, H, 3), dim3(KT_THREADS), 0, st, a);
-            hipLaunchKernelGGL(kd64_combine, dim3(bc, H), dim3(KD_COMBINE_THREADS), 0, st, a);
-        }
-    } else if (io.match_kind == TR_LOSS_MATCH) {
-        // the same slot of the stream and the same outputs: the assignment solved here in double on the tape's own double states
-        // (k_match_f64.h), the term and the seed on io.match_in's pairs where the caller gave them
-        CHK(ka64_run(c, dim3(bc, H), tr64_match_args(k, io, b0, bc, N, B, H, 1.0 / ((double)H * (double)B), 0.0)));
-    } else if (io.M == 0) {
-        hipLaunchKernelGGL(kt64_mse, dim3(bc, H), dim3(256), 0, st, k.tape.state, io.states, io.nums, b0, bc, B, N, H, io.terms, k.rev.g_state);
-    } else {
-        // the same slot of the stream and the same outputs: slice t + 1 of the tape's states against step t of the target clouds,
-        // the arg-mins taken here in double
-        Kc64Args a{};
-        a.cp = tr_cloud_pair((size_t)N * 3, pn * 3, io.nums, io.targets, io.tnums, H, N, io.M);
-        a.p64 = k.tape.state + pn * 3;
-        a.b_off = b0; a.B = B;
-        a.scale = 1.0 / ((double)H * (double)B);
-        a.grad = k.rev.g_state; a.terms = io.terms; a.margin = io.margin;
-        hipLaunchKernelGGL((kc64_chamfer<true>), dim3(bc, H), dim3(KC64_THREADS), 0, st, a);
-        // the mix: behind a Chamfer-only step's terms and seed the matching kernel turns each element into (1 - w) x it + w x its
-        // own share, in double: one writer per element, stream order (the fp32 trainer's scheme)
-        if (io.match_kind == TR_LOSS_CHAMFER_MATCH)
-            CHK(ka64_run(c, dim3(bc, H), tr64_match_args(k, io, b0, bc, N, B, H, a.scale * io.match_weight, 1.0 - io.match_weight)));
-    }
+    CHK(tr64_launch_loss(c, k, io, lk, v, b0, bc, N, B, H));
     HIPCHK(c, hipMemsetAsync(k.wg.acc, 0, (size_t)bc * W_TOTAL * sizeof(double), st));
     F64Wgrad wg = k.wg;
     wg.st = st; wg.bc = bc; wg.N = N; wg.dens = dens;
@@ -452,14 +446,6 @@ int drp_gd_grad_f64(drp_ctx* c, const float* s0, const float* attr, const float*
 }
 
 namespace {
-// what drp_train_step_loss refuses of a matching loss's sizes and weight
-int check_match_loss(drp_ctx* c, const TrLoss& lk, int N) {
-    if (N > KA_MAX_POINTS || lk.M > KA_MAX_POINTS)
-        return fail(c, DRP_EINVAL, "a matching loss takes clouds of 1..%d points: N=%d M=%d", KA_MAX_POINTS, N, lk.M);
-    if (lk.kind == TR_LOSS_CHAMFER_MATCH && !(lk.match_weight > 0.0 && lk.match_weight < 1.0))
-        return fail(c, DRP_EINVAL, "match_weight %g outside (0, 1)", lk.match_weight);
-    return DRP_OK;
-}
 // drp_train_grad_f64, drp_train_grad_f64_actions and drp_train_grad_f64_untracked: one body; `impulses` is states_delta
 // [B][H][N][3], or with `actions` the pushes [B][H][4]; the loss kind and the targets in `lk` (capi_train.h: TrLoss) -- the tracked
 // MSE, the Chamfer loss against untracked target clouds (k_chamfer_f64.h), or the Sinkhorn divergence to them
@@ -510,80 +496,37 @@ int train_grad_f64_body(drp_ctx* c, const float* states, const float* impulses, 
     const int H = n_rollout;
     // samples per chunk: tape, reverse pass, weight gradients' operands and accumulators together
     Tr64Ws k{};
-    const bool div = lk.divergence(), reach = lk.unbalanced();
-    auto bytes_of = [&](size_t bc) { return k.carve(nullptr, bc, (size_t)N, (size_t)H, div); };
+    const TrShape shape = lk.shape();
+    auto bytes_of = [&](size_t bc) { return k.carve(nullptr, bc, (size_t)N, (size_t)H, shape); };
     size_t Bc;
     CHK(f64_size_chunks(c, B, N, ((size_t)1 << 24) / ((size_t)N * DRP_K), bytes_of, &Bc));
-    k.carve(c->grad64_ws.p, Bc, (size_t)N, (size_t)H, div);
-    // the whole batch's inputs in one upload (train_host.h: tr64_layout): states | impulses | attrs[:, 0] | densities | particle
-    // counts [| target clouds | their counts] [| eps [| rho | mass_q]] [| the caller's matching], then the results: terms | total
-    // [| margins] [| col_err | self_err [| transported]] [| the matching's costs | its optimum's partners]
-    const bool match = lk.match();
-    const int M = lk.chamfer() || div || match ? lk.M : 0;
-    const Tr64Arena lay = tr64_layout(B, H, N, M, actions, div, match && lk.match_in != nullptr, reach, lk.given());
-    std::vector<float> host(lay.words);
-    memcpy(host.data() + lay.states, states, (lay.sdelta - lay.states) * sizeof(float));
-    memcpy(host.data() + lay.sdelta, impulses, (lay.attr - lay.sdelta) * sizeof(float));
-    for (int b = 0; b < B; ++b) memcpy(host.data() + lay.attr + (size_t)b * N, attrs + (size_t)b * (H + 1) * N, (size_t)N * sizeof(float));
-    memcpy(host.data() + lay.dens, particle_dens, (size_t)B * sizeof(float));
-    memcpy(host.data() + lay.nums, particle_nums, (size_t)B * sizeof(int32_t));
-    if (M > 0) {
-        memcpy(host.data() + lay.targets, lk.targets, (size_t)B * H * M * 3 * sizeof(float));
-        memcpy(host.data() + lay.tnums, lk.target_nums, (size_t)B * H * sizeof(int32_t));
-    }
-    if (div) memcpy(host.data() + lay.eps, lk.eps, (size_t)B * sizeof(double));
-    if (reach) {
-        memcpy(host.data() + lay.rho, lk.rho, (size_t)B * sizeof(double));
-        memcpy(host.data() + lay.mass_q, lk.mass_q, (size_t)H * B * sizeof(double));
-    }
-    if (match && lk.match_in) memcpy(host.data() + lay.match_in, lk.match_in, (size_t)H * B * N * sizeof(int32_t));
-    if (lk.given()) memcpy(host.data() + lay.seed, lk.seed64, (size_t)B * H * N * 3 * sizeof(double));
-    const size_t n_terms = (size_t)H * B;
-    // the matching kinds: behind the margins the costs [H][B][2], then the optimum's partners [H][B][N] (ints, two to a double)
-    const size_t n_match = match ? 2 * n_terms + (n_terms * N + 1) / 2 : 0;
-    Tr64Io io{};
-    CHK(f64_upload_batch(c, host, n_terms + (size_t)W_TOTAL + (div ? (reach ? 4 : 3) * n_terms : M > 0 ? n_terms : 0) + n_match, &io.terms));
-    io.states = ptr<float>(c->grad64_io); io.sdelta = io.states + lay.sdelta; io.attr = io.states + lay.attr; io.dens = io.states + lay.dens;
-    io.nums = reinterpret_cast<const int*>(io.states + lay.nums);
-    io.actions = actions;
-    io.M = M;
-    io.total = io.terms + n_terms;
-    if (lk.given()) io.seed = reinterpret_cast<const double*>(io.states + lay.seed);
-    io.predict = pred_out != nullptr;
-    if (M > 0) {
-        io.targets = io.states + lay.targets;
-        io.tnums = reinterpret_cast<const int*>(io.states + lay.tnums);
-        if (div) {
-            io.eps = reinterpret_cast<const double*>(io.states + lay.eps); io.iters = lk.iters;
-            io.col_err = io.total + W_TOTAL; io.self_err = io.col_err + n_terms;
-            if (reach) {
-                io.rho = reinterpret_cast<const double*>(io.states + lay.rho);
-                io.mass_q = reinterpret_cast<const double*>(io.states + lay.mass_q);
-                io.transported = io.self_err + 2 * n_terms;
-            }
-        } else {
-            io.margin = io.total + W_TOTAL;
-        }
-        if (match) {
-            io.match_kind = lk.kind; io.match_weight = lk.match_weight;
-            io.match_in = lk.match_in ? reinterpret_cast<const int*>(io.states + lay.match_in) : nullptr;
-            io.cost = io.margin + n_terms;
-            io.match_out = reinterpret_cast<int*>(io.cost + 2 * n_terms);
-        }
-    }
+    k.carve(c->grad64_ws.p, Bc, (size_t)N, (size_t)H, shape);
+    // the whole batch's inputs in one upload and the results behind them (train_host.h: tr_blocks; of the attributes a_cur = attrs[:, 0])
+    const TrBlocks lay = tr_blocks(shape, B, H, N, actions, true);
+    std::vector<float> host(lay.bytes / sizeof(float));
+    char* const up = reinterpret_cast<char*>(host.data());
+    memcpy(up + lay.off[TRB_STATES], states, lay.size(TRB_STATES));
+    memcpy(up + lay.off[TRB_IMPULSES], impulses, lay.size(TRB_IMPULSES));
+    for (int b = 0; b < B; ++b)
+        memcpy(up + lay.off[TRB_ATTRS] + (size_t)b * N * sizeof(float), attrs + (size_t)b * (H + 1) * N, (size_t)N * sizeof(float));
+    memcpy(up + lay.off[TRB_DENS], particle_dens, lay.size(TRB_DENS));
+    memcpy(up + lay.off[TRB_NUMS], particle_nums, lay.size(TRB_NUMS));
+    tr_stage_loss_inputs(up, lay, lk);
+    double* res;
+    CHK(f64_upload_batch(c, host, lay.res_bytes / sizeof(double), &res));
+    const TrView v = tr_view(c->grad64_io.p, res, lay);
+    auto staged = [&](int id) { return reinterpret_cast<const float*>(static_cast<const char*>(c->grad64_io.p) + lay.off[id]); };
+    const Tr64Io io{staged(TRB_STATES), staged(TRB_IMPULSES), staged(TRB_ATTRS), staged(TRB_DENS), actions,
+                    reinterpret_cast<const int*>(staged(TRB_NUMS)), v.total, pred_out != nullptr};
     HIPCHK(c, hipMemsetAsync(io.total, 0, (size_t)W_TOTAL * sizeof(double), c->stream));
     for (int b0 = 0; b0 < B; b0 += (int)Bc)
-        CHK(tr64_chunk(c, k, io, b0, std::min((int)Bc, B - b0), N, B, H, io.predict ? pred_out : grad_state_out));
+        CHK(tr64_chunk(c, k, io, lk, v, b0, std::min((int)Bc, B - b0), N, B, H, io.predict ? pred_out : grad_state_out));
     if (io.predict) return guarded_wait(c, nullptr);        // (the upload's host block lives until here)
+    const size_t n_terms = lay.count[TRB_TERMS];
     std::vector<double> terms(n_terms);
-    if (!lk.given()) CHK(d2h(c, terms.data(), io.terms, n_terms * sizeof(double)));      // (a given seed has no terms: none were written)
+    if (!lk.given()) CHK(d2h(c, terms.data(), v.terms, n_terms * sizeof(double)));      // (a given seed has no terms: none were written)
     if (grad_out) CHK(d2h(c, grad_out, io.total, (size_t)W_TOTAL * sizeof(double)));
-    if (io.margin && lk.margin_out && lk.chamfer()) CHK(d2h(c, lk.margin_out, io.margin, n_terms * sizeof(double)));
-    if (match && lk.cost_out) CHK(d2h(c, lk.cost_out, io.cost, 2 * n_terms * sizeof(double)));
-    if (match && lk.match_out) CHK(d2h(c, lk.match_out, io.match_out, n_terms * N * sizeof(int32_t)));
-    if (div && lk.col_err_out) CHK(d2h(c, lk.col_err_out, io.col_err, n_terms * sizeof(double)));
-    if (div && lk.self_err_out) CHK(d2h(c, lk.self_err_out, io.self_err, 2 * n_terms * sizeof(double)));
-    if (reach && lk.transported_out) CHK(d2h(c, lk.transported_out, io.transported, n_terms * sizeof(double)));
+    CHK(tr_read_results(lay, res, lk, [c](void* dst, const void* src, size_t n) { return d2h(c, dst, src, n); }));
     CHK(guarded_wait(c, nullptr));          // (the upload's host block lives until here)
     if (loss_terms_out) memcpy(loss_terms_out, terms.data(), n_terms * sizeof(double));
     if (loss_out) {

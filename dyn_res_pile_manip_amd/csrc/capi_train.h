@@ -4,61 +4,13 @@
 // ---- training on the same kernels (row f4) ------------------------------------------------------
 namespace {
 #define TR_GRAD_PAD ((W_TOTAL + 63) & ~63)      // tr_grad: the gradient blob, then (from here) kmb_step_bwd's barrier counters
-// (train_host.h: TrArena / tr_layout, where the blocks of a staged batch lie)
-const float* tr_given(const drp_ctx* c) { return static_cast<const float*>(c->tr_arena.p); }
-const int* tr_nums(const drp_ctx* c, const TrArena& lay) {
-    return reinterpret_cast<const int*>(static_cast<const char*>(c->tr_arena.p) + lay.nums);
+// (train_host.h: TrLoss, the description of the loss both trainers read, and tr_blocks, the table of the blocks a call stages in
+// c->tr_arena and brings back from c->tr_loss)
+extern "C++" template <typename T> const T* tr_staged(const drp_ctx* c, const TrBlocks& lay, int id) {
+    return reinterpret_cast<const T*>(static_cast<const char*>(c->tr_arena.p) + lay.off[id]);
 }
-// what seeds the reverse pass: the tracked loss (kt_mse_grad against the given next states) or the Chamfer loss against
-// untracked target clouds (k_chamfer.h), the one-to-one matching loss against them (k_match.h), or the two mixed; the targets as
-// the HOST gave them (the entry point stages them behind the batch).  The kinds beyond the MSE are include/drp.h's DRP_LOSS_*.
-// The float64 yardstick (capi_grad_f64.h) reads the same description; it has every kind but the transport loss.
-// TR_LOSS_TRANSPORT (k_sinkhorn.h) is internal: drp_train_step_transport's, no loss_kind of drp_train_step_loss; so is
-// TR_LOSS_DIVERGENCE (k_sinkhorn.h), drp_train_step_divergence's, and TR_LOSS_GIVEN: no loss at all but the CALLER's d loss / d
-// s_pred as the seed (drp_train_step_seeded, drp_train_grad_f64_seeded; kt_seed_given, k64_seed_given)
-enum { TR_LOSS_MSE = 0, TR_LOSS_CHAMFER = DRP_LOSS_CHAMFER, TR_LOSS_MATCH = DRP_LOSS_MATCH, TR_LOSS_CHAMFER_MATCH = DRP_LOSS_CHAMFER_MATCH,
-       TR_LOSS_TRANSPORT = 4, TR_LOSS_DIVERGENCE = 5, TR_LOSS_GIVEN = 6 };
+static_assert(W_TOTAL == DRP_N_WEIGHTS, "the table's row of the float64 weight-gradient sums");
 static_assert(KT_MAX_ITERS == DRP_TRANSPORT_MAX_ITERS, "include/drp.h states the kernel's cap");
-struct TrLoss {
-    int kind = TR_LOSS_MSE;
-    const float* targets = nullptr;         // [B][H][M][3]
-    const int32_t* target_nums = nullptr;   // [B][H]
-    int M = 0;
-    double match_weight = 0.0;              // TR_LOSS_CHAMFER_MATCH: (1 - w) Chamfer + w matching
-    int32_t* match_out = nullptr;           // the caller's [H][B][N], nullable: every predicted row's partner (kinds with a matching)
-    const int32_t* match_in = nullptr;      // float64 only: the caller's [H][B][N], nullable: the pairs of the term and the seed
-    double* cost_out = nullptr;             // float64 only: the caller's [H][B][2], nullable (ka64_match's costs)
-    double* margin_out = nullptr;           // float64 only: the caller's [H][B], nullable (kc64_chamfer's arg-min margins)
-    const double* eps = nullptr;            // TR_LOSS_TRANSPORT, _DIVERGENCE: the caller's [B], the regularisation of every step of a sample
-    int iters = 0;                          // TR_LOSS_TRANSPORT, _DIVERGENCE: the sweeps
-    double* col_err_out = nullptr;          // TR_LOSS_TRANSPORT, _DIVERGENCE: the caller's [H][B], nullable
-    double* self_err_out = nullptr;         // TR_LOSS_DIVERGENCE: the caller's [H][B][2], nullable
-    const double* rho = nullptr;            // TR_LOSS_DIVERGENCE, non-null: the unbalanced divergence -- the caller's reaches [B] ...
-    const double* mass_q = nullptr;         //   ... and the targets' total masses [H][B] (both or neither)
-    double* transported_out = nullptr;      //   ... and the caller's [H][B], nullable
-    const float* seed = nullptr;            // TR_LOSS_GIVEN: the caller's d loss / d s_pred [B][H][N][3] ...
-    const double* seed64 = nullptr;         //   ... float64: the same in double
-    bool given() const { return kind == TR_LOSS_GIVEN; }
-    bool targeted() const { return kind != TR_LOSS_MSE && kind != TR_LOSS_GIVEN; }     // a loss against target clouds
-    bool unbalanced() const { return kind == TR_LOSS_DIVERGENCE && rho != nullptr; }
-    bool transport() const { return kind == TR_LOSS_TRANSPORT; }
-    bool divergence() const { return kind == TR_LOSS_DIVERGENCE; }
-    bool sinkhorn() const { return transport() || divergence(); }      // eps and iters, the kernels' caps and col_err
-    bool chamfer() const { return kind == TR_LOSS_CHAMFER || kind == TR_LOSS_CHAMFER_MATCH; }
-    bool match() const { return kind == TR_LOSS_MATCH || kind == TR_LOSS_CHAMFER_MATCH; }
-    static TrLoss against(int kind, const float* targets, const int32_t* target_nums, int M) {
-        TrLoss lk;
-        lk.kind = kind; lk.targets = targets; lk.target_nums = target_nums; lk.M = M;
-        return lk;
-    }
-    // the transport loss and the divergence: `against` with the sweeps' arguments and the certificates' outputs (nullable)
-    static TrLoss sinkhorn(int kind, const float* targets, const int32_t* target_nums, int M, const double* eps, int iters,
-                           double* col_err_out, double* self_err_out = nullptr) {
-        TrLoss lk = against(kind, targets, target_nums, M);
-        lk.eps = eps; lk.iters = iters; lk.col_err_out = col_err_out; lk.self_err_out = self_err_out;
-        return lk;
-    }
-};
 // The impulse source of an entry point that takes both pointers: exactly one of states_delta and actions is given
 struct ImpulseSource { const float* impulses; bool by_actions; };
 int impulse_source(drp_ctx* c, const float* states_delta, const float* actions, ImpulseSource& src) {
@@ -86,6 +38,14 @@ int check_target_nums(drp_ctx* c, const TrLoss& lk, int B, int H) {
     for (int e = 0; e < B * H; ++e)
         if (lk.target_nums[e] <= 0 || lk.target_nums[e] > lk.M)
             return fail(c, DRP_EINVAL, "target_nums[%d][%d]=%d outside 1..%d", e / H, e % H, lk.target_nums[e], lk.M);
+    return DRP_OK;
+}
+// a matching loss's sizes and the mix's weight
+int check_match_loss(drp_ctx* c, const TrLoss& lk, int N) {
+    if (N > KA_MAX_POINTS || lk.M > KA_MAX_POINTS)
+        return fail(c, DRP_EINVAL, "a matching loss takes clouds of 1..%d points: N=%d M=%d", KA_MAX_POINTS, N, lk.M);
+    if (lk.kind == TR_LOSS_CHAMFER_MATCH && !(lk.match_weight > 0.0 && lk.match_weight < 1.0))
+        return fail(c, DRP_EINVAL, "match_weight %g outside (0, 1)", lk.match_weight);
     return DRP_OK;
 }
 // eps [B] and iters as drp_cloud_transport and drp_train_step_transport refuse them
@@ -134,16 +94,90 @@ struct TrainPass {
                                     //   and all (drp_train_predict) -- with no loss kernel and nothing reversed
     bool defer = false;             // the weight gradients wait for the end of the pass (and the dumps have a buffer per step)
     double* loss_terms = nullptr;   // [H][B], where the loss kernel stores: c->tr_loss, or pinned host memory the caller reads
-    TrArena lay{};                  // the batch in c->tr_arena
+    TrBlocks lay{};                 // the call's blocks: the batch in c->tr_arena, the results in c->tr_loss (train_host.h)
     TrLoss lk;
-    bool actions = false;           // the impulse source: false, data (lay.sdelta holds [B][H][N][3]); true, the pushes there
+    bool actions = false;           // the impulse source: false, data (the impulse block holds [B][H][N][3]); true, the pushes there
                                     // ([B][H][4]) evaluated on the state each step reads (kt_sdelta_actions, kb_sdelta_pos)
 };
+// The loss of every step and d loss / d s_pred_t (train/train_gnn_dyn.py:184-186, :203): whatever the kind, the same slot of the
+// stream, the same grid (B, H), the same seed buffer and terms, and one kernel that zero-fills the gradient blob with
+// kmb_step_bwd's counters behind it.  `v`: the loss's blocks in the staged batch and in c->tr_loss (train_host.h: tr_view)
+void train_launch_loss(drp_ctx* c, int B, int N, const TrainPass& tp, const TrView& v) {
+    const int H = c->tr_nroll;
+    const TrLoss& lk = tp.lk;
+    hipStream_t st = c->stream;
+    const int* nums = tr_staged<int>(c, tp.lay, TRB_NUMS);
+    float* states = ptr<float>(c->states);
+    float* g_state = ptr<float>(c->g_state);
+    double* loss = tp.loss_terms;
+    const float scale = 1.0f / (float)(H * B);
+    const size_t hstride = (size_t)H * N * 3;                 // predicted states [B][H][N][3]
+    float* const zero = tp.backward ? ptr<float>(c->tr_grad) : (float*)nullptr;
+    const size_t n_zero = (size_t)TR_GRAD_PAD + (size_t)H * c->n_cu + 1;
+    const dim3 grid(B, H);
+    if (lk.given()) {                   // the caller's seed as staged behind the batch
+        hipLaunchKernelGGL(kt_seed_given, grid, dim3(256), 0, st, static_cast<const float*>(v.seed), nums, N, g_state, zero, n_zero);
+        return;
+    }
+    if (lk.kind == TR_LOSS_MSE) {       // against the given next states [B][H+1][N][3]
+        hipLaunchKernelGGL(kt_mse_grad, grid, dim3(256), 0, st, states, hstride, tr_staged<float>(c, tp.lay, TRB_STATES) + (size_t)N * 3,
+                           (size_t)(H + 1) * N * 3, nums, N, scale, g_state, loss, zero, n_zero);
+        return;
+    }
+    // step t of the predictions against step t of the staged target clouds
+    const CloudPair cp = tr_cloud_pair(hstride, (size_t)N * 3, nums, v.targets, v.tnums, H, N, lk.M);
+    if (lk.chamfer()) {
+        KcArgs a{};
+        a.cp = cp; a.pred = states;
+        a.scale = scale;               // (the mix too: the matching kernel weighs what this one leaves, in double)
+        a.grad = g_state; a.terms = loss;
+        a.zero = zero; a.n_zero = n_zero;
+        hipLaunchKernelGGL((kc_chamfer<true>), grid, dim3(KC_THREADS), 0, st, a);
+    }
+    if (lk.match()) {
+        // alone: the Chamfer kernel's outputs and zero-fill; in the mix: behind it in the stream, turning the gradient and the
+        // terms it finds into (1 - w) x them + its own share -- one writer per element, so the sum's order is fixed, and
+        // the Chamfer share is (1 - w) x the bits of a Chamfer-only step whatever w is
+        KaArgs a{};
+        a.cp = cp; a.pred = states;
+        a.scale = lk.chamfer() ? (double)scale * lk.match_weight : (double)scale;
+        a.keep = lk.chamfer() ? 1.0 - lk.match_weight : 0.0;
+        a.grad = g_state; a.terms = loss;
+        a.match_pq = v.match;
+        a.zero = lk.chamfer() ? (float*)nullptr : zero; a.n_zero = n_zero;
+        ka_launch<true>(grid, st, a);
+    }
+    if (lk.sinkhorn()) {
+        // the Chamfer kernel's outputs and zero-fill; a certificate is formed where the caller asked for it
+        SkArgs32 a{};
+        a.cp = cp; a.pred = states; a.b_off = 0; a.B = B;
+        a.eps = v.eps; a.iters = lk.iters;
+        a.scale = (double)scale;
+        a.grad = g_state; a.terms = loss;
+        a.col_err = lk.col_err_out != nullptr ? v.col_err : (double*)nullptr;
+        a.zero = zero; a.n_zero = n_zero;
+        if (lk.transport()) {
+            hipLaunchKernelGGL((kt_transport<true>), grid, dim3(KT_THREADS), 0, st, a);
+            return;
+        }
+        // the divergence: the sweeps leave their sums in the scratch, kd_combine does the zero-fill on the other kernels' grid
+        a.vals = v.vals; a.gsum = v.gsum;
+        a.self_err = lk.self_err_out != nullptr ? v.self_err : (double*)nullptr;
+        if (lk.unbalanced()) {
+            a.rho = v.rho; a.mass_q = v.mass_q;
+            a.transported = lk.transported_out != nullptr ? v.transported : (double*)nullptr;
+            hipLaunchKernelGGL(kd_sweeps_unbalanced, dim3(B, H, 3), dim3(KT_THREADS), 0, st, a);
+            hipLaunchKernelGGL((kd_combine<true, true>), grid, dim3(KD_COMBINE_THREADS), 0, st, a);
+        } else {
+            hipLaunchKernelGGL(kd_sweeps, dim3(B, H, 3), dim3(KT_THREADS), 0, st, a);
+            hipLaunchKernelGGL((kd_combine<true>), grid, dim3(KD_COMBINE_THREADS), 0, st, a);
+        }
+    }
+}
 // forward over n_rollout steps (+ loss), optionally the backward pass with weight gradients
 int train_forward_backward(drp_ctx* c, int B, int N, const TrainPass& tp) {
     const int H = c->tr_nroll;
     const bool backward = tp.backward, defer = tp.defer;
-    const TrLoss& lk = tp.lk;
     WgradQueue& wq = *c->wgrad;
     wq.begin(defer);
     const size_t bn = (size_t)B * N, bn64 = bn * 64, bnk = bn * DRP_K;
@@ -151,12 +185,10 @@ int train_forward_backward(drp_ctx* c, int B, int N, const TrainPass& tp) {
     const size_t in_stride = (size_t)(H + 1) * N * 3;         // given states     [B][H+1][N][3]
     hipStream_t st = c->stream;
     float* states = ptr<float>(c->states);
-    const float* given = tr_given(c);
-    const int* nums = tr_nums(c, tp.lay);
-    const float* acts = tp.actions ? reinterpret_cast<const float*>(static_cast<const char*>(c->tr_arena.p) + tp.lay.sdelta) : nullptr;
+    const float* given = tr_staged<float>(c, tp.lay, TRB_STATES);
+    const int* nums = tr_staged<int>(c, tp.lay, TRB_NUMS);
+    const float* acts = tp.actions ? tr_staged<float>(c, tp.lay, TRB_IMPULSES) : nullptr;
     float* g_state = ptr<float>(c->g_state);
-    double* loss = tp.loss_terms;
-    const float scale = 1.0f / (float)(H * B);
     {
         const float* cself = nullptr;
         const uint8_t* cself_ok = nullptr;
@@ -176,85 +208,7 @@ int train_forward_backward(drp_ctx* c, int B, int N, const TrainPass& tp) {
         HIPCHK(c, hipGetLastError());
         return DRP_OK;
     }
-    // the loss of every step and d loss / d s_pred_t (train/train_gnn_dyn.py:184-186, :203) in one launch
-    if (lk.given()) {
-        // the same slot of the stream, the same seed buffer and the same zero-fill: the caller's seed as staged behind the batch
-        hipLaunchKernelGGL(kt_seed_given, dim3(B, H), dim3(256), 0, st,
-                           reinterpret_cast<const float*>(static_cast<const char*>(c->tr_arena.p) + tp.lay.seed), nums, N, g_state,
-                           backward ? ptr<float>(c->tr_grad) : (float*)nullptr, (size_t)TR_GRAD_PAD + (size_t)H * c->n_cu + 1);
-    } else if (lk.kind == TR_LOSS_MSE) {
-        hipLaunchKernelGGL(kt_mse_grad, dim3(B, H), dim3(256), 0, st, states, hstride, given + (size_t)N * 3, in_stride,
-                           nums, N, scale, g_state, loss, backward ? ptr<float>(c->tr_grad) : (float*)nullptr,
-                           (size_t)TR_GRAD_PAD + (size_t)H * c->n_cu + 1);      // the gradient blob with kmb_step_bwd's counters behind it
-    } else {
-        // the same slot of the stream, the same outputs and the same zero-fill: step t of the predictions against step t of the
-        // staged target clouds
-        const TrArena& lay = tp.lay;
-        const char* ar = static_cast<const char*>(c->tr_arena.p);
-        float* const zero = backward ? ptr<float>(c->tr_grad) : (float*)nullptr;
-        const size_t n_zero = (size_t)TR_GRAD_PAD + (size_t)H * c->n_cu + 1;
-        const CloudPair cp = tr_cloud_pair(hstride, (size_t)N * 3, nums, reinterpret_cast<const float*>(ar + lay.targets),
-                                           reinterpret_cast<const int*>(ar + lay.tnums), H, N, lk.M);
-        if (lk.chamfer()) {
-            KcArgs a{};
-            a.cp = cp; a.pred = states;
-            a.scale = scale;               // (the mix too: the matching kernel weighs what this one leaves, in double)
-            a.grad = g_state; a.terms = loss;
-            a.zero = zero; a.n_zero = n_zero;
-            hipLaunchKernelGGL((kc_chamfer<true>), dim3(B, H), dim3(KC_THREADS), 0, st, a);
-        }
-        if (lk.match()) {
-            // alone: the Chamfer kernel's outputs and zero-fill; in the mix: behind it in the stream, turning the gradient and the
-            // terms it finds into (1 - w) x them + its own share -- one writer per element, so the sum's order is fixed, and
-            // the Chamfer share is (1 - w) x the bits of a Chamfer-only step whatever w is
-            KaArgs a{};
-            a.cp = cp; a.pred = states;
-            a.scale = lk.chamfer() ? (double)scale * lk.match_weight : (double)scale;
-            a.keep = lk.chamfer() ? 1.0 - lk.match_weight : 0.0;
-            a.grad = g_state; a.terms = loss;
-            a.match_pq = ptr<int>(c->tr_match);
-            a.zero = lk.chamfer() ? (float*)nullptr : zero; a.n_zero = n_zero;
-            ka_launch<true>(dim3(B, H), st, a);
-        }
-        if (lk.transport()) {
-            // the Chamfer kernel's outputs and zero-fill; eps [B] lies behind the staged batch, col_err [H][B] behind the terms
-            SkArgs32 a{};
-            a.cp = cp; a.pred = states; a.b_off = 0; a.B = B;
-            a.eps = reinterpret_cast<const double*>(ar + lay.eps); a.iters = lk.iters;
-            a.scale = (double)scale;
-            a.grad = g_state; a.terms = loss;
-            a.col_err = lk.col_err_out != nullptr ? ptr<double>(c->tr_loss) + (size_t)H * B : (double*)nullptr;
-            a.zero = zero; a.n_zero = n_zero;
-            hipLaunchKernelGGL((kt_transport<true>), dim3(B, H), dim3(KT_THREADS), 0, st, a);
-        }
-        if (lk.divergence()) {
-            // the same outputs; the certificates and the two kernels' scratch lie behind the terms (train_host.h:
-            // tr_div_loss_layout); kd_combine does the zero-fill, on the grid the other loss kernels do it on
-            const bool unbalanced = lk.unbalanced();
-            const TrDivLoss dl = tr_div_loss_layout(B, H, N, unbalanced);
-            double* const d = ptr<double>(c->tr_loss);
-            SkArgs32 a{};
-            a.cp = cp; a.pred = states; a.b_off = 0; a.B = B;
-            a.eps = reinterpret_cast<const double*>(ar + lay.eps); a.iters = lk.iters;
-            a.scale = (double)scale;
-            a.vals = d + dl.vals; a.gsum = d + dl.gsum;
-            a.grad = g_state; a.terms = loss;
-            a.col_err = lk.col_err_out != nullptr ? d + dl.col_err : (double*)nullptr;
-            a.self_err = lk.self_err_out != nullptr ? d + dl.self_err : (double*)nullptr;
-            a.zero = zero; a.n_zero = n_zero;
-            if (unbalanced) {
-                // the reaches [B] and the targets' masses [H][B] lie behind eps; transported behind the scratch
-                a.rho = reinterpret_cast<const double*>(ar + lay.rho);
-                a.mass_q = reinterpret_cast<const double*>(ar + lay.mass_q);
-                a.transported = lk.transported_out != nullptr ? d + dl.transported : (double*)nullptr;
-                hipLaunchKernelGGL(kd_sweeps_unbalanced, dim3(B, H, 3), dim3(KT_THREADS), 0, st, a);
-                hipLaunchKernelGGL((kd_combine<true, true>), dim3(B, H), dim3(KD_COMBINE_THREADS), 0, st, a);
-            } else {
-                hipLaunchKernelGGL(kd_sweeps, dim3(B, H, 3), dim3(KT_THREADS), 0, st, a);
-                hipLaunchKernelGGL((kd_combine<true>), dim3(B, H), dim3(KD_COMBINE_THREADS), 0, st, a);
-            }
-        }
-    }
+    train_launch_loss(c, B, N, tp, tr_view(c->tr_arena.p, c->tr_loss.p, tp.lay));
     HIPCHK(c, hipGetLastError());
     if (!backward) return DRP_OK;
 
@@ -495,12 +449,7 @@ int train_check_args(drp_ctx* c, const float* states, const float* impulses, boo
     }
     if (lk.targeted()) {
         CHK(check_target_clouds(c, lk, KC_MAX_POINTS, "target size"));
-        if (lk.match()) {
-            if (N > KA_MAX_POINTS || lk.M > KA_MAX_POINTS)
-                return fail(c, DRP_EINVAL, "a matching loss takes clouds of 1..%d points: N=%d M=%d", KA_MAX_POINTS, N, lk.M);
-            if (lk.kind == TR_LOSS_CHAMFER_MATCH && !(lk.match_weight > 0.0 && lk.match_weight < 1.0))
-                return fail(c, DRP_EINVAL, "match_weight %g outside (0, 1)", lk.match_weight);
-        }
+        if (lk.match()) CHK(check_match_loss(c, lk, N));
         if (lk.sinkhorn()) {
             if (N > KT_MAX_POINTS || lk.M > KT_MAX_POINTS)
                 return fail(c, DRP_EINVAL, "the %s takes clouds of 1..%d points: N=%d M=%d",
@@ -547,10 +496,7 @@ int train_ensure_workspace(drp_ctx* c, int B, int N, TrainPass& tp) {
         for (DevBuf* b : edge64) CHK(ensure(c, *b, kt * bnk * 64 * sizeof(float)));
         CHK(ensure(c, c->ed_x0, kt * bnk * 8 * sizeof(float)));
     }
-    // (the transport loss: col_err behind the terms; the divergence: its certificates and scratch, tr_div_loss_layout)
-    CHK(ensure(c, c->tr_loss, tp.lk.divergence() ? tr_div_loss_layout(B, H, N, tp.lk.unbalanced()).count * sizeof(double)
-                                                 : (size_t)H * B * sizeof(double) * (tp.lk.transport() ? 2 : 1)));
-    if (tp.lk.match()) CHK(ensure(c, c->tr_match, (size_t)H * bn * sizeof(int)));
+    CHK(ensure(c, c->tr_loss, tp.lay.res_bytes));       // the terms, the loss's other results and its scratch (train_host.h)
     return DRP_OK;
 }
 
@@ -558,23 +504,11 @@ int train_ensure_workspace(drp_ctx* c, int B, int N, TrainPass& tp) {
 int train_stage_batch(drp_ctx* c, const float* states, const float* impulses, const float* attrs, const int32_t* particle_nums,
                       const float* particle_dens, int B, int N, const TrainPass& tp) {
     const int H = c->tr_nroll;
-    const TrArena& lay = tp.lay;
+    const TrBlocks& lay = tp.lay;
     char* pin = ptr<char>(c->tr_pin);
-    memcpy(pin + lay.states, states, (size_t)B * (H + 1) * N * 3 * sizeof(float));
-    memcpy(pin + lay.sdelta, impulses, tr_impulse_bytes(B, H, N, tp.actions));
-    memcpy(pin + lay.attrs, attrs, (size_t)B * (H + 1) * N * sizeof(float));
-    memcpy(pin + lay.dens, particle_dens, (size_t)B * sizeof(float));
-    memcpy(pin + lay.nums, particle_nums, (size_t)B * sizeof(int));
-    if (tp.lk.given()) memcpy(pin + lay.seed, tp.lk.seed, (size_t)B * H * N * 3 * sizeof(float));
-    if (tp.lk.targeted()) {
-        memcpy(pin + lay.targets, tp.lk.targets, (size_t)B * H * tp.lk.M * 3 * sizeof(float));
-        memcpy(pin + lay.tnums, tp.lk.target_nums, (size_t)B * H * sizeof(int));
-    }
-    if (tp.lk.sinkhorn()) memcpy(pin + lay.eps, tp.lk.eps, (size_t)B * sizeof(double));
-    if (tp.lk.unbalanced()) {
-        memcpy(pin + lay.rho, tp.lk.rho, (size_t)B * sizeof(double));
-        memcpy(pin + lay.mass_q, tp.lk.mass_q, (size_t)H * B * sizeof(double));
-    }
+    const void* const five[] = {states, impulses, attrs, particle_dens, particle_nums};
+    for (int id = TRB_STATES; id <= TRB_NUMS; ++id) memcpy(pin + lay.off[id], five[id], lay.size(id));
+    tr_stage_loss_inputs(pin, lay, tp.lk);
     // the unpacking launch IS the upload: it reads the staged batch from the pinned host buffer (device-visible) and leaves
     // the arena copy for the kernels that read the given states; DRP_TRAIN_COPY_UPLOAD=1: a copy on the stream first
     const bool by_kernel = !c->train_copy_upload;
@@ -582,9 +516,9 @@ int train_stage_batch(drp_ctx* c, const float* states, const float* impulses, co
     const char* ar = by_kernel ? ptr<const char>(c->tr_pin) : static_cast<const char*>(c->tr_arena.p);
     const size_t total = (size_t)H * B * N * 3;
     hipLaunchKernelGGL(kt_unpack_inputs, dim3((unsigned)std::min<size_t>((total + 255) / 256, 1024)), dim3(256), 0, c->stream,
-                       tp.actions ? (const float*)nullptr : reinterpret_cast<const float*>(ar + lay.sdelta),
-                       reinterpret_cast<const float*>(ar + lay.attrs),
-                       reinterpret_cast<const float*>(ar + lay.dens), B, H, N, ptr<float>(c->tape_sdelta), ptr<float>(c->ws.attr),
+                       tp.actions ? (const float*)nullptr : reinterpret_cast<const float*>(ar + lay.off[TRB_IMPULSES]),
+                       reinterpret_cast<const float*>(ar + lay.off[TRB_ATTRS]),
+                       reinterpret_cast<const float*>(ar + lay.off[TRB_DENS]), B, H, N, ptr<float>(c->tape_sdelta), ptr<float>(c->ws.attr),
                        ptr<float>(c->ws.dens), by_kernel ? ptr<const float4>(c->tr_pin) : (const float4*)nullptr,
                        by_kernel ? static_cast<float4*>(c->tr_arena.p) : (float4*)nullptr, by_kernel ? lay.bytes / 16 : (size_t)0);
     return DRP_OK;
@@ -611,16 +545,7 @@ int train_attempt(drp_ctx* c, int B, int N, const TrainPass& tp, int mode, bool 
     }
     if (want_loss && tp.loss_terms != back) CHK(d2h(c, back, c->tr_loss.p, (size_t)H * B * sizeof(double)));
     if (grad_out && tp.backward) CHK(d2h(c, grad_out, c->tr_grad.p, (size_t)W_TOTAL * sizeof(float)));
-    if (tp.lk.match_out && tp.lk.match()) CHK(d2h(c, tp.lk.match_out, c->tr_match.p, (size_t)H * B * N * sizeof(int)));
-    if (tp.lk.col_err_out && tp.lk.transport())
-        CHK(d2h(c, tp.lk.col_err_out, ptr<double>(c->tr_loss) + (size_t)H * B, (size_t)H * B * sizeof(double)));
-    if (tp.lk.divergence()) {
-        const TrDivLoss dl = tr_div_loss_layout(B, H, N, tp.lk.unbalanced());
-        if (tp.lk.col_err_out) CHK(d2h(c, tp.lk.col_err_out, ptr<double>(c->tr_loss) + dl.col_err, (size_t)H * B * sizeof(double)));
-        if (tp.lk.self_err_out) CHK(d2h(c, tp.lk.self_err_out, ptr<double>(c->tr_loss) + dl.self_err, (size_t)H * B * 2 * sizeof(double)));
-        if (tp.lk.unbalanced() && tp.lk.transported_out)
-            CHK(d2h(c, tp.lk.transported_out, ptr<double>(c->tr_loss) + dl.transported, (size_t)H * B * sizeof(double)));
-    }
+    CHK(tr_read_results(tp.lay, c->tr_loss.p, tp.lk, [c](void* dst, const void* src, size_t n) { return d2h(c, dst, src, n); }));
     if (tp.backward && !direct) CHK(d2h(c, flag_host, flag_dev, sizeof(unsigned)));
     bool repacked = false;
     if (mode == DRP_TRAIN_UPDATE) {
@@ -672,7 +597,7 @@ int train_step_body(drp_ctx* c, const float* states, const float* impulses, bool
     }
     tp.backward = mode != DRP_TRAIN_EVAL;
     tp.predict = pred_out != nullptr;
-    tp.lay = tr_layout(B, H, N, lk.targeted() ? lk.M : 0, actions, lk.sinkhorn(), lk.unbalanced(), lk.given());
+    tp.lay = tr_blocks(lk.shape(), B, H, N, actions, false);
     tp.lk = lk;
     tp.actions = actions;
     CHK(train_ensure_workspace(c, B, N, tp));

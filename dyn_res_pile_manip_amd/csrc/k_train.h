@@ -45,7 +45,7 @@ kt_mse_grad(const float* __restrict__ s_pred, size_t pred_stride, const float* _
 }
 
 // d loss / d s_pred_t as the CALLER gives it (drp_train_step_seeded), in kt_mse_grad's slot of the stream and on its grid B x H:
-// the staged seed [B][H][N][3] (the caller's layout, train_host.h: TrArena::seed) to g_out [H][B][N][3], real rows bit for bit,
+// the staged seed [B][H][N][3] (the caller's layout, train_host.h: the row TRB_SEED) to g_out [H][B][N][3], real rows bit for bit,
 // +0.0f on rows n >= particle_nums[b] whatever lies there (selected, never multiplied: a NaN in the padding stays there), and
 // the zero-fill of the gradient blob behind it as every loss kernel does.  No loss term: the value is the caller's.  Where N * 3
 // is a multiple of four, both slices start on 16 bytes (the block and g_out do) and the copy is float4s.

@@ -1,100 +1,175 @@
-// train_host.h -- the trainer's entry points' host arithmetic that touches no device: where a staged batch's blocks lie, and which
-// pushes a call refuses.  Plain C++ (no HIP header), so that tools/train_host_check.cpp builds it alone under the host
-// sanitizers; drp_capi.hip includes it ahead of the C ABI's sections.
+// train_host.h -- the trainer's entry points' host arithmetic that touches no device: the description of a loss (TrLoss), the table
+// of the blocks a trainer call stages and brings back (tr_blocks) with the one carve, staging copy, readback and device view over
+// it, the one-shots' buffers, and which pushes, seeds, reaches and matchings a call refuses.  Plain C++ (no HIP header), so that
+// tools/train_host_check.cpp builds it alone under the host sanitizers; drp_capi.hip includes it ahead of the C ABI's sections.
 #pragma once
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
-// the batch as uploaded (drp_train_step): states [B][H+1][N][3] | impulses [B][H][N][3] | attributes [B][H+1][N] | densities [B]
-// | particle counts [B] (ints), every block 16-byte aligned; drp_train_step_untracked (M > 0): behind them the target clouds
-// [B][H][M][3] | their counts [B][H] (ints) -- with M = 0 the layout, and so the one copy, is drp_train_step's;
-// drp_train_step_actions (`actions`): the pushes [B][H][4] where the impulses are, everything behind them moving up;
-// drp_train_step_transport, drp_train_step_divergence (`eps`): behind everything the regularisation strengths [B] (doubles);
-// drp_train_step_divergence_unbalanced (`reach`, with `eps`): behind those the reaches [B] | the targets' masses [H][B] (doubles);
-// drp_train_step_seeded (`seed`): behind everything the caller's d loss / d s_pred [B][H][N][3] (floats, the caller's layout) -- a
-// call without it takes zero bytes for it, and nothing ahead of it moves
-struct TrArena { size_t states, sdelta, attrs, dens, nums, targets, tnums, bytes, eps, rho, mass_q, seed; };
-// the impulse block: what train_stage_batch copies to TrArena::sdelta
-inline size_t tr_impulse_bytes(int B, int H, int N, bool actions) {
-    return (actions ? (size_t)B * H * 4 : (size_t)B * H * N * 3) * sizeof(float);
+#include "../../include/drp.h"
+
+// what seeds the reverse pass: the tracked loss (kt_mse_grad against the given next states) or the Chamfer loss against
+// untracked target clouds (k_chamfer.h), the one-to-one matching loss against them (k_match.h), or the two mixed; the targets as
+// the HOST gave them (the entry point stages them behind the batch).  The kinds beyond the MSE are include/drp.h's DRP_LOSS_*.
+// The float64 yardstick (capi_grad_f64.h) reads the same description; it has every kind but the transport loss.
+// TR_LOSS_TRANSPORT (k_sinkhorn.h) is internal: drp_train_step_transport's, no loss_kind of drp_train_step_loss; so is
+// TR_LOSS_DIVERGENCE (k_sinkhorn.h), drp_train_step_divergence's, and TR_LOSS_GIVEN: no loss at all but the CALLER's d loss / d
+// s_pred as the seed (drp_train_step_seeded, drp_train_grad_f64_seeded; kt_seed_given, k64_seed_given)
+enum { TR_LOSS_MSE = 0, TR_LOSS_CHAMFER = DRP_LOSS_CHAMFER, TR_LOSS_MATCH = DRP_LOSS_MATCH, TR_LOSS_CHAMFER_MATCH = DRP_LOSS_CHAMFER_MATCH,
+       TR_LOSS_TRANSPORT = 4, TR_LOSS_DIVERGENCE = 5, TR_LOSS_GIVEN = 6 };
+// the predicates of a loss that decide which blocks a call has (TrLoss::shape; tools/train_host_check.cpp sets them freely)
+struct TrShape { bool targeted, chamfer, match, match_in, sinkhorn, divergence, unbalanced, given; int M; };
+struct TrLoss {
+    int kind = TR_LOSS_MSE;
+    const float* targets = nullptr;         // [B][H][M][3]
+    const int32_t* target_nums = nullptr;   // [B][H]
+    int M = 0;
+    double match_weight = 0.0;              // TR_LOSS_CHAMFER_MATCH: (1 - w) Chamfer + w matching
+    int32_t* match_out = nullptr;           // the caller's [H][B][N], nullable: every predicted row's partner (kinds with a matching)
+    const int32_t* match_in = nullptr;      // float64 only: the caller's [H][B][N], nullable: the pairs of the term and the seed
+    double* cost_out = nullptr;             // float64 only: the caller's [H][B][2], nullable (ka64_match's costs)
+    double* margin_out = nullptr;           // float64 only: the caller's [H][B], nullable (kc64_chamfer's arg-min margins)
+    const double* eps = nullptr;            // TR_LOSS_TRANSPORT, _DIVERGENCE: the caller's [B], the regularisation of every step of a sample
+    int iters = 0;                          // TR_LOSS_TRANSPORT, _DIVERGENCE: the sweeps
+    double* col_err_out = nullptr;          // TR_LOSS_TRANSPORT, _DIVERGENCE: the caller's [H][B], nullable
+    double* self_err_out = nullptr;         // TR_LOSS_DIVERGENCE: the caller's [H][B][2], nullable
+    const double* rho = nullptr;            // TR_LOSS_DIVERGENCE, non-null: the unbalanced divergence -- the caller's reaches [B] ...
+    const double* mass_q = nullptr;         //   ... and the targets' total masses [H][B] (both or neither)
+    double* transported_out = nullptr;      //   ... and the caller's [H][B], nullable
+    const float* seed = nullptr;            // TR_LOSS_GIVEN: the caller's d loss / d s_pred [B][H][N][3] ...
+    const double* seed64 = nullptr;         //   ... float64: the same in double
+    bool given() const { return kind == TR_LOSS_GIVEN; }
+    bool targeted() const { return kind != TR_LOSS_MSE && kind != TR_LOSS_GIVEN; }     // a loss against target clouds
+    bool unbalanced() const { return kind == TR_LOSS_DIVERGENCE && rho != nullptr; }
+    bool transport() const { return kind == TR_LOSS_TRANSPORT; }
+    bool divergence() const { return kind == TR_LOSS_DIVERGENCE; }
+    bool sinkhorn() const { return transport() || divergence(); }      // eps and iters, the kernels' caps and col_err
+    bool chamfer() const { return kind == TR_LOSS_CHAMFER || kind == TR_LOSS_CHAMFER_MATCH; }
+    bool match() const { return kind == TR_LOSS_MATCH || kind == TR_LOSS_CHAMFER_MATCH; }
+    TrShape shape() const {
+        return TrShape{targeted(), chamfer(), match(), match() && match_in != nullptr, sinkhorn(), divergence(), unbalanced(), given(), M};
+    }
+    static TrLoss against(int kind, const float* targets, const int32_t* target_nums, int M) {
+        TrLoss lk;
+        lk.kind = kind; lk.targets = targets; lk.target_nums = target_nums; lk.M = M;
+        return lk;
+    }
+    // the transport loss and the divergence: `against` with the sweeps' arguments and the certificates' outputs (nullable)
+    static TrLoss sinkhorn(int kind, const float* targets, const int32_t* target_nums, int M, const double* eps, int iters,
+                           double* col_err_out, double* self_err_out = nullptr) {
+        TrLoss lk = against(kind, targets, target_nums, M);
+        lk.eps = eps; lk.iters = iters; lk.col_err_out = col_err_out; lk.self_err_out = self_err_out;
+        return lk;
+    }
+};
+
+// ---- the blocks of a trainer call: ONE table for the fp32 trainer (capi_train.h) and its float64 yardstick (capi_grad_f64.h) ----
+// A row is a block: its id, its element size and its count, each count written once, here.  Rows in the order they lie:
+//   the fixed five      states [B][H+1][N][3] | impulses [B][H][N][3] (`actions`: the pushes [B][H][4]) | attributes [B][H+1][N]
+//                       (float64: a_cur = attrs[:, 0] alone, [B][N]) | densities [B] | particle counts [B] (ints)
+//   the loss's inputs   target clouds [B][H][M][3] | their counts [B][H] (targeted) | eps [B] (sinkhorn) | rho [B] | mass_q [H][B]
+//                       (sinkhorn and unbalanced: a reach without eps adds nothing) | the caller's partners [H][B][N] (float64 with
+//                       a match_in) | the caller's d loss / d s_pred [B][H][N][3] (given; floats, float64: doubles)
+//   the results         terms [H][B] | the float64 weight-gradient sums [DRP_N_WEIGHTS] (no result of the loss: they lie between
+//                       the terms and the rest) | margin [H][B] (float64 Chamfer) | col_err [H][B] (sinkhorn) | self_err [H][B][2]
+//                       (divergence) | transported [H][B] (unbalanced) | cost [H][B][2] (float64 match) | partners [H][B][N] (match)
+//   the scratch         the divergence's value sums [3][H][B] | gradient sums [2][H][B][N][3]: behind the fp32 trainer's results;
+//                       the float64 yardstick carves them per chunk (Tr64Ws, from the same two rows at B = the chunk's samples)
+// Inputs and results are carved apart (tr_carve): every block on a multiple of 16 bytes of its buffer, so every double on one of
+// 8 and the fp32 arena, which kt_unpack_inputs copies in float4 units, a multiple of 16 long; a block that is absent (count 0)
+// takes no byte, has offset 0 and a null address in the view, and moves nothing ahead of it.
+enum { TRB_STATES, TRB_IMPULSES, TRB_ATTRS, TRB_DENS, TRB_NUMS,
+       TRB_TARGETS, TRB_TNUMS, TRB_EPS, TRB_RHO, TRB_MASS_Q, TRB_MATCH_IN, TRB_SEED,
+       TRB_TERMS, TRB_TOTAL, TRB_MARGIN, TRB_COL_ERR, TRB_SELF_ERR, TRB_TRANSPORTED, TRB_COST, TRB_MATCH,
+       TRB_VALS, TRB_GSUM, TRB_COUNT, TRB_IN_END = TRB_TERMS, TRB_SCRATCH = TRB_VALS };
+struct TrBlocks {
+    size_t elem[TRB_COUNT], count[TRB_COUNT], off[TRB_COUNT];
+    size_t bytes, res_bytes;        // the staged inputs; the results (fp32: with the scratch)
+    int res_end;                    // the first row behind the carved results
+    size_t size(int id) const { return elem[id] * count[id]; }
+};
+// rows [first, end) laid one behind the other from offset 0 -> the bytes they take
+inline size_t tr_carve(TrBlocks& t, int first, int end) {
+    size_t at = 0;
+    for (int id = first; id < end; ++id) {
+        t.off[id] = t.count[id] ? at : 0;
+        at = (at + t.size(id) + 15) & ~(size_t)15;
+    }
+    return at;
 }
-inline TrArena tr_layout(int B, int H, int N, int M = 0, bool actions = false, bool eps = false, bool reach = false,
-                         bool seed = false) {
-    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    TrArena a{};
-    a.states = 0;
-    a.sdelta = up(a.states + (size_t)B * (H + 1) * N * 3 * sizeof(float));
-    a.attrs = up(a.sdelta + tr_impulse_bytes(B, H, N, actions));
-    a.dens = up(a.attrs + (size_t)B * (H + 1) * N * sizeof(float));
-    a.nums = up(a.dens + (size_t)B * sizeof(float));
-    a.bytes = up(a.nums + (size_t)B * sizeof(int));
-    if (M > 0) {
-        a.targets = a.bytes;
-        a.tnums = up(a.targets + (size_t)B * H * M * 3 * sizeof(float));
-        a.bytes = up(a.tnums + (size_t)B * H * sizeof(int));
-    }
-    if (eps) {
-        a.eps = a.bytes;
-        a.bytes = up(a.eps + (size_t)B * sizeof(double));
-    }
-    if (eps && reach) {
-        a.rho = a.bytes;
-        a.mass_q = up(a.rho + (size_t)B * sizeof(double));
-        a.bytes = up(a.mass_q + (size_t)H * B * sizeof(double));
-    }
-    if (seed) {
-        a.seed = a.bytes;
-        a.bytes = up(a.seed + (size_t)B * H * N * 3 * sizeof(float));
-    }
-    return a;
+inline TrBlocks tr_blocks(const TrShape& s, int B, int H, int N, bool actions, bool f64) {
+    const size_t F = sizeof(float), I = sizeof(int32_t), D = sizeof(double);
+    const size_t b = (size_t)B, hb = (size_t)H * B, hbn = hb * N, m = s.targeted ? (size_t)s.M : 0;
+    const bool reach = s.sinkhorn && s.unbalanced, div = s.sinkhorn && s.divergence;
+    TrBlocks t{};
+    auto row = [&t](int id, size_t elem, size_t count) { t.elem[id] = elem; t.count[id] = count; };
+    row(TRB_STATES, F, b * (H + 1) * N * 3);
+    row(TRB_IMPULSES, F, actions ? hb * 4 : hbn * 3);
+    row(TRB_ATTRS, F, f64 ? b * N : b * (H + 1) * N);
+    row(TRB_DENS, F, b);
+    row(TRB_NUMS, I, b);
+    row(TRB_TARGETS, F, hb * m * 3);
+    row(TRB_TNUMS, I, m ? hb : 0);
+    row(TRB_EPS, D, s.sinkhorn ? b : 0);
+    row(TRB_RHO, D, reach ? b : 0);
+    row(TRB_MASS_Q, D, reach ? hb : 0);
+    row(TRB_MATCH_IN, I, f64 && s.match_in ? hbn : 0);
+    row(TRB_SEED, f64 ? D : F, s.given ? hbn * 3 : 0);
+    row(TRB_TERMS, D, hb);
+    row(TRB_TOTAL, D, f64 ? DRP_N_WEIGHTS : 0);
+    row(TRB_MARGIN, D, f64 && s.chamfer ? hb : 0);
+    row(TRB_COL_ERR, D, s.sinkhorn ? hb : 0);
+    row(TRB_SELF_ERR, D, div ? 2 * hb : 0);
+    row(TRB_TRANSPORTED, D, div && reach ? hb : 0);
+    row(TRB_COST, D, f64 && s.match ? 2 * hb : 0);
+    row(TRB_MATCH, I, s.match ? hbn : 0);
+    row(TRB_VALS, D, div ? 3 * hb : 0);
+    row(TRB_GSUM, D, div ? 2 * hbn * 3 : 0);
+    t.bytes = tr_carve(t, TRB_STATES, TRB_IN_END);
+    t.res_end = f64 ? TRB_SCRATCH : TRB_COUNT;
+    t.res_bytes = tr_carve(t, TRB_TERMS, t.res_end);
+    return t;
+}
+// the loss's input rows copied from the caller's arrays to their places in the staged batch at `dst`
+inline void tr_stage_loss_inputs(char* dst, const TrBlocks& t, const TrLoss& lk) {
+    const void* src[TRB_IN_END] = {};
+    src[TRB_TARGETS] = lk.targets; src[TRB_TNUMS] = lk.target_nums; src[TRB_EPS] = lk.eps; src[TRB_RHO] = lk.rho;
+    src[TRB_MASS_Q] = lk.mass_q; src[TRB_MATCH_IN] = lk.match_in;
+    src[TRB_SEED] = t.elem[TRB_SEED] == sizeof(double) ? static_cast<const void*>(lk.seed64) : lk.seed;
+    for (int id = TRB_TARGETS; id < TRB_IN_END; ++id)
+        if (t.count[id]) memcpy(dst + t.off[id], src[id], t.size(id));
+}
+// every result row behind the terms and the sums that the caller gave a pointer for: copy(dst, src, bytes) -> 0 or the error
+// that ends the walk (the trainers: a d2h on the stream).  The terms stay with the trainers: they differ in where those land
+template <typename Copy>
+inline int tr_read_results(const TrBlocks& t, const void* res, const TrLoss& lk, Copy copy) {
+    void* dst[TRB_COUNT] = {};
+    dst[TRB_MARGIN] = lk.margin_out; dst[TRB_COL_ERR] = lk.col_err_out; dst[TRB_SELF_ERR] = lk.self_err_out;
+    dst[TRB_TRANSPORTED] = lk.transported_out; dst[TRB_COST] = lk.cost_out; dst[TRB_MATCH] = lk.match_out;
+    for (int id = TRB_MARGIN; id < TRB_SCRATCH; ++id)
+        if (t.count[id] && dst[id])
+            if (const int rc = copy(dst[id], static_cast<const char*>(res) + t.off[id], t.size(id))) return rc;
+    return 0;
+}
+// the addresses of the loss's blocks: `in` the staged batch, `res` the results; null where a block is absent
+struct TrView {
+    const float* targets; const int32_t* tnums; const double *eps, *rho, *mass_q; const int32_t* match_in; const void* seed;
+    double *terms, *total, *margin, *col_err, *self_err, *transported, *cost; int32_t* match; double *vals, *gsum;
+};
+inline TrView tr_view(const void* in, void* res, const TrBlocks& t) {
+    auto at = [&t](const void* base, int id) -> void* {
+        return t.count[id] && id < t.res_end ? const_cast<char*>(static_cast<const char*>(base)) + t.off[id] : nullptr;
+    };
+    auto f64 = [&](int id) { return static_cast<double*>(at(id < TRB_IN_END ? in : res, id)); };
+    auto i32 = [&](int id) { return static_cast<int32_t*>(at(id < TRB_IN_END ? in : res, id)); };
+    return TrView{static_cast<const float*>(at(in, TRB_TARGETS)), i32(TRB_TNUMS), f64(TRB_EPS), f64(TRB_RHO), f64(TRB_MASS_Q),
+                  i32(TRB_MATCH_IN), at(in, TRB_SEED), f64(TRB_TERMS), f64(TRB_TOTAL), f64(TRB_MARGIN), f64(TRB_COL_ERR),
+                  f64(TRB_SELF_ERR), f64(TRB_TRANSPORTED), f64(TRB_COST), i32(TRB_MATCH), f64(TRB_VALS), f64(TRB_GSUM)};
 }
 
-// the batch as the float64 yardsticks upload it (capi_grad_f64.h: train_grad_f64_body), in 4-byte words, packed: states
-// [B][H+1][N][3] | impulses [B][H][N][3] (`actions`: the pushes [B][H][4]) | attrs[:, 0] [B][N] | densities [B] | particle counts
-// [B] (ints); drp_train_grad_f64_untracked (M > 0): behind them the target clouds [B][H][M][3] | their counts [B][H] (ints) --
-// with M = 0 the layout, and so the one copy, is drp_train_grad_f64's; drp_train_grad_f64_divergence (`eps`): behind everything
-// the regularisation strengths [B] (doubles, two words each) on the next even word -- the vector's base is 256-byte aligned on
-// the device, so an even word is an 8-byte boundary -- and nothing ahead of them moves; drp_train_grad_f64_divergence_unbalanced
-// (`reach`, with `eps`): behind eps the reaches [B] | the targets' masses [H][B] (doubles too); drp_train_grad_f64_match with a matching
-// of the caller's (`match_in`): behind everything the partners [H][B][N] (ints), nothing ahead of them moving either;
-// drp_train_grad_f64_seeded (`seed`): behind everything the caller's d loss / d s_pred [B][H][N][3] (doubles, two words each) on
-// the next multiple of four words -- a 16-byte boundary on the device --, nothing ahead of it moving
-struct Tr64Arena { size_t states, sdelta, attr, dens, nums, targets, tnums, words, eps, match_in, rho, mass_q, seed; };
-inline Tr64Arena tr64_layout(int B, int H, int N, int M = 0, bool actions = false, bool eps = false, bool match_in = false,
-                             bool reach = false, bool seed = false) {
-    Tr64Arena a{};
-    a.states = 0;
-    a.sdelta = a.states + (size_t)B * (H + 1) * N * 3;
-    a.attr = a.sdelta + tr_impulse_bytes(B, H, N, actions) / sizeof(float);
-    a.dens = a.attr + (size_t)B * N;
-    a.nums = a.dens + (size_t)B;
-    a.words = a.nums + (size_t)B;
-    a.targets = a.tnums = a.words;
-    if (M > 0) {
-        a.tnums = a.targets + (size_t)B * H * M * 3;
-        a.words = a.tnums + (size_t)B * H;
-    }
-    if (eps) {
-        a.eps = (a.words + 1) & ~(size_t)1;
-        a.words = a.eps + 2 * (size_t)B;
-    }
-    if (eps && reach) {
-        a.rho = a.words;
-        a.mass_q = a.rho + 2 * (size_t)B;
-        a.words = a.mass_q + 2 * (size_t)H * B;
-    }
-    if (match_in) {
-        a.match_in = a.words;
-        a.words = a.match_in + (size_t)H * B * N;
-    }
-    if (seed) {
-        a.seed = (a.words + 3) & ~(size_t)3;
-        a.words = a.seed + 2 * (size_t)B * H * N * 3;
-    }
-    return a;
-}
 
 // The one buffer of a one-shot on two clouds (capi_pipeline.h: cloud_begin), every block 16-byte aligned.  Up: p [B][N][3]
 // (elements of p_elem bytes: floats, or the float64 divergence's doubles) | q [B][M][3] | n_p [B] | n_q [B] (ints); down, behind
@@ -226,25 +301,6 @@ inline const char* matching_fault(int why) {
          : why == MATCH_PAD ? "is padding and has a partner" : "has no partner: too few pairs";
 }
 
-// drp_train_step_divergence's device doubles (c->tr_loss), in doubles: terms [H][B] | col_err [H][B] | self_err [H][B][2] | the
-// value sums [3][H][B] | the gradient sums [2][H][B][N][3]; drp_train_step_divergence_unbalanced (`unbalanced`): behind them
-// transported [H][B]
-struct TrDivLoss { size_t terms, col_err, self_err, vals, gsum, count, transported; };
-inline TrDivLoss tr_div_loss_layout(int B, int H, int N, bool unbalanced = false) {
-    const size_t hb = (size_t)H * B;
-    TrDivLoss a{};
-    a.terms = 0;
-    a.col_err = a.terms + hb;
-    a.self_err = a.col_err + hb;
-    a.vals = a.self_err + 2 * hb;
-    a.gsum = a.vals + 3 * hb;
-    a.count = a.gsum + 2 * hb * N * 3;
-    if (unbalanced) {
-        a.transported = a.count;
-        a.count = a.transported + hb;
-    }
-    return a;
-}
 // the first of the B regularisation strengths that is zero, negative, infinite or no number, or -1
 inline int first_bad_eps(const double* eps, int B) {
     for (int b = 0; b < B; ++b)

@@ -6,7 +6,7 @@ for granted, and the host side of the feature.
 (b) THE PRECONDITION of the stand-alone shapes the GPU tests add (tests/_chamfer_f64_cases.py): every arg-min of chamfer64 wins by
     more than MARGIN_MIN, and where a shape has a second 1024-point tile or a second 256-row chunk some arg-min lies in it.
     Asserted here, where the seeds were picked; nothing is skipped at run time.
-(c) tr64_layout (csrc/train_host.h), the one upload of the float64 trainer calls, against sizes summed by hand; the function is
+(c) tr_blocks (csrc/train_host.h) for the one upload of the float64 trainer calls, against sizes summed by hand; the function is
     plain C++, so tools/train_host_check.cpp is built for the host and asked."""
 import os
 import subprocess
@@ -153,18 +153,23 @@ def host_check(tmp_path_factory):
 
 
 @pytest.mark.parametrize('B,H,N,M,actions', [(4, 3, 64, 50, 0), (3, 5, 23, 17, 1), (2, 1, 7, 0, 0)])
-def test_tr64_layout_is_the_hand_summed_size(host_check, B, H, N, M, actions):
-    out = subprocess.check_output([host_check, 'layout64'] + [str(v) for v in (B, H, N, M, actions)]).decode().split()
-    states, sdelta, attr, dens, nums, targets, tnums, words = [int(v) for v in out]
-    n_st = B * (H + 1) * N * 3
-    n_imp = B * H * 4 if actions else B * H * N * 3
-    assert (states, sdelta, attr, dens, nums) == (0, n_st, n_st + n_imp, n_st + n_imp + B * N, n_st + n_imp + B * N + B)
-    head = n_st + n_imp + B * N + 2 * B                     # drp_train_grad_f64's whole upload
-    assert targets == head
+def test_float64_upload_is_the_hand_summed_size(host_check, B, H, N, M, actions):
+    out = subprocess.check_output([host_check, 'layout'] + [str(v) for v in (B, H, N, M, actions, 0, 0, 0, 1, 0)]).decode().split()
+    states, sdelta, attr, dens, nums, targets, tnums, nbytes = [int(v) for v in out[:8]]
+    assert [int(v) for v in out[8:]] == [0] * 5             # no eps, rho, mass_q, seed or match_in was asked for
+
+    def up(v):
+        return (v + 15) // 16 * 16
+    n_st = B * (H + 1) * N * 3 * 4
+    n_imp = (B * H * 4 if actions else B * H * N * 3) * 4
+    at_attr = up(n_st) + up(n_imp)
+    at_dens = at_attr + up(B * N * 4)                       # a_cur = attrs[:, 0] alone
+    assert (states, sdelta, attr, dens, nums) == (0, up(n_st), at_attr, at_dens, at_dens + up(B * 4))
+    head = at_dens + 2 * up(B * 4)                          # drp_train_grad_f64's whole upload
     if M > 0:
-        assert tnums == head + B * H * M * 3 and words == head + B * H * M * 3 + B * H
+        assert targets == head and tnums == head + up(B * H * M * 3 * 4) and nbytes == tnums + up(B * H * 4)
     else:
-        assert tnums == head and words == head
+        assert targets == 0 and tnums == 0 and nbytes == head
 
 
 def test_the_host_check_program_passes(host_check):

@@ -18,7 +18,8 @@ unchanged at either commit.  The cases:
               engine selected
   float64     train_grad_f64 / _actions / _untracked, train_grad_f64_divergence (both ways), train_grad_f64_match (its own
               matching, and match_in = the fp32 side's), train_predict_f64 and train_grad_f64_seeded on the same batches: every
-              output
+              output; on b2_r5 once more, behind the probes, under a set_f64_cap that cuts the batch into chunks of one sample
+              (then set_f64_cap(0)): the loss launches at a sample offset
   probes      train_gradient_probe with no targets, targets, eps / iters, eps / iters / reach, loss='match', 'chamfer+match', and
               train_gradient_probe_custom, on the same batches: every scalar of the dict by repr in sorted key order, the
               per-tensor table hashed"""
@@ -96,6 +97,14 @@ def sinkhorn_args(five, tnums):
     dens, nums = np.asarray(five[4], np.float64).reshape(-1), np.asarray(five[3], np.float64).reshape(-1, 1)
     eps = 1.0 / dens
     return eps, REACH_PER_EPS * eps, np.ascontiguousarray(np.clip(np.asarray(tnums, np.float64) / nums, 0.125, 8.0).T)
+
+
+def one_sample_cap(states):
+    """a float64 cap that holds one sample of the batch and not two (the arithmetic of tests/test_gpu_train_f64.py's _lib_cap_for,
+    from include/drp.h's figures: tape 24 KB per particle and step, reverse pass and operands 52 KB per particle, 307 KB of
+    accumulators per sample)"""
+    _, T1, N, _ = states.shape
+    return int(((24 * 1024 * (T1 - 1) + 52 * 1024) * N + 307 * 1024) * 1.5)
 
 
 def fp32_steps(golden, name, five, by_actions, targets, tnums):
@@ -178,15 +187,6 @@ def trainers(golden):
         eng.load_weights(blob, 0.08)
         eng.set_camera(*A.camera_args())
         states, imp, attrs, nums, dens = five
-        if by_actions:
-            calls = (('train_grad_f64_actions', eng.train_grad_f64_actions(*five)),
-                     ('train_grad_f64_untracked', eng.train_grad_f64_untracked(states, None, attrs, nums, dens, targets, tnums, actions=imp)))
-        else:
-            calls = (('train_grad_f64', eng.train_grad_f64(*five)),
-                     ('train_grad_f64_untracked', eng.train_grad_f64_untracked(*five, targets, tnums)))
-        for label, out in calls:
-            for k, v in zip(('loss', 'terms', 'blob', 'margin'), out):
-                show('%s %s %s' % (name, label, k), np.float64(v) if k == 'loss' else v)
         # the yardsticks of the targeted losses and of a caller's loss: states_delta positionally (None beside actions)
         sd, act = (None, imp) if by_actions else (imp, None)
         imp_kw = {'actions': imp} if by_actions else {'states_delta': imp}
@@ -195,24 +195,38 @@ def trainers(golden):
         eng.train_begin(H, 1e-3, 0.9)
         match32 = eng.train_step_loss(states, attrs, nums, dens, targets, tnums, loss='match', mode='grad', want_match=True,
                                       **imp_kw)[2]
-        pred64 = eng.train_predict_f64(states, attrs, nums, dens, **imp_kw)
-        calls = (('train_grad_f64_divergence', eng.train_grad_f64_divergence(*seven64, eps, ITERS, actions=act, want_state=True,
-                                                                             want_err=True)),
-                 ('train_grad_f64_divergence reach', eng.train_grad_f64_divergence(*seven64, eps, ITERS, actions=act, want_state=True,
-                                                                                   want_err=True, reach=reach, mass_q=mass_q)),
-                 ('train_grad_f64_divergence reach scalar', eng.train_grad_f64_divergence(*seven64, float(eps[0]), ITERS, actions=act,
-                                                                                          reach=float(reach[0]))),
-                 ('train_grad_f64_match', eng.train_grad_f64_match(*seven64, actions=act, want_state=True, want_info=True)),
-                 ('train_grad_f64_match mix', eng.train_grad_f64_match(*seven64, 'chamfer+match', MIX, actions=act, want_info=True)),
-                 ('train_grad_f64_match match_in', eng.train_grad_f64_match(*seven64, actions=act, match_in=match32, want_info=True)),
-                 ('train_predict_f64', (pred64,)),
-                 ('train_grad_f64_seeded', eng.train_grad_f64_seeded(states, attrs, nums, dens, losses.mse_loss(pred64, five)[1],
-                                                                     want_state=True, **imp_kw)))
-        for label, out in calls:
-            for k, v in enumerate(out):
-                for key, item in (sorted(v.items()) if isinstance(v, dict) else (('', v),)):
-                    if item is not None:
-                        show('%s %s out %d %s' % (name, label, k, key), item)
+
+        def float64_calls(tag):
+            """every float64 trainer call of the batch, every output"""
+            if by_actions:
+                calls = (('train_grad_f64_actions', eng.train_grad_f64_actions(*five)),
+                         ('train_grad_f64_untracked', eng.train_grad_f64_untracked(states, None, attrs, nums, dens, targets, tnums,
+                                                                                   actions=imp)))
+            else:
+                calls = (('train_grad_f64', eng.train_grad_f64(*five)),
+                         ('train_grad_f64_untracked', eng.train_grad_f64_untracked(*five, targets, tnums)))
+            for label, out in calls:
+                for k, v in zip(('loss', 'terms', 'blob', 'margin'), out):
+                    show('%s %s %s' % (tag, label, k), np.float64(v) if k == 'loss' else v)
+            pred64 = eng.train_predict_f64(states, attrs, nums, dens, **imp_kw)
+            calls = (('train_grad_f64_divergence', eng.train_grad_f64_divergence(*seven64, eps, ITERS, actions=act, want_state=True,
+                                                                                 want_err=True)),
+                     ('train_grad_f64_divergence reach', eng.train_grad_f64_divergence(*seven64, eps, ITERS, actions=act, want_state=True,
+                                                                                       want_err=True, reach=reach, mass_q=mass_q)),
+                     ('train_grad_f64_divergence reach scalar', eng.train_grad_f64_divergence(*seven64, float(eps[0]), ITERS, actions=act,
+                                                                                              reach=float(reach[0]))),
+                     ('train_grad_f64_match', eng.train_grad_f64_match(*seven64, actions=act, want_state=True, want_info=True)),
+                     ('train_grad_f64_match mix', eng.train_grad_f64_match(*seven64, 'chamfer+match', MIX, actions=act, want_info=True)),
+                     ('train_grad_f64_match match_in', eng.train_grad_f64_match(*seven64, actions=act, match_in=match32, want_info=True)),
+                     ('train_predict_f64', (pred64,)),
+                     ('train_grad_f64_seeded', eng.train_grad_f64_seeded(states, attrs, nums, dens, losses.mse_loss(pred64, five)[1],
+                                                                         want_state=True, **imp_kw)))
+            for label, out in calls:
+                for k, v in enumerate(out):
+                    for key, item in (sorted(v.items()) if isinstance(v, dict) else (('', v),)):
+                        if item is not None:
+                            show('%s %s out %d %s' % (tag, label, k, key), item)
+        float64_calls(name)
         probes = (('mse', {}), ('chamfer', {'targets': targets, 'target_nums': tnums}),
                   ('sinkhorn', {'targets': targets, 'target_nums': tnums, 'eps': eps, 'iters': ITERS}),
                   ('sinkhorn reach', {'targets': targets, 'target_nums': tnums, 'eps': eps, 'iters': ITERS, 'reach': reach,
@@ -224,6 +238,13 @@ def trainers(golden):
                                                                                               **kw))
         show_probe('%s train_gradient_probe_custom' % name, eng.train_gradient_probe_custom(losses.mse_loss, states, attrs, nums, dens,
                                                                                              context=five, **imp_kw))
+        if name == 'b2_r5':
+            # the same calls in chunks of one sample: every float64 loss launch at a sample offset b0 > 0
+            eng.set_f64_cap(one_sample_cap(states))
+            try:
+                float64_calls(name + ' one-sample chunks')
+            finally:
+                eng.set_f64_cap(0)
         eng.close()
 
 

@@ -1,38 +1,32 @@
-// Host-code hygiene of the trainer's entry points (csrc/train_host.h): where the blocks of a staged batch lie, with data impulses,
-// with pushes and with target clouds, and which pushes a call refuses.  A stand-alone program for the host sanitizers:
+// Host-code hygiene of the trainer's entry points (csrc/train_host.h): the table of the blocks a trainer call stages and brings
+// back, the one-shots' buffers, and what a call refuses.  A stand-alone program for the host sanitizers:
 //
 //   hipcc -x hip --offload-arch=gfx950 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
 //         tools/train_host_check.cpp -o build/train_host_check && build/train_host_check
 //   (or any C++17 compiler: c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all ...)
 //
-// It stages batches as train_stage_batch does -- the same copies, to the offsets tr_layout gives, into a heap block of exactly
-// TrArena::bytes -- so a block that overlaps the next one or runs past the end is the sanitizer's finding; the offsets are held
-// to the documented layout as well.  The float64 yardsticks' upload (tr64_layout: train_grad_f64_body's one vector, with and
-// without target clouds) is staged the same way, and so is the one buffer of the three one-shots on two clouds (cloud_layout with
-// cm_layout's, chamfer_layout's and chamfer64_layout's blocks: the inputs staged, every output block written in full; the two
-// Chamfer layouts held to offset chains written out by hand here, an independent restatement), with the check
-// that refuses a real row that is no number.  The transport loss: transport_layout's blocks staged like the matching's, the
-// eps block behind a training batch (tr_layout with `eps`), and the check of the regularisation strengths.  The Sinkhorn divergence:
-// divergence_layout's five blocks that come back staged the same way, eps and the kernels' scratch behind them written in full
-// inside a block of exactly its `bytes`, and the trainer's doubles (tr_div_loss_layout) likewise.  Its float64 yardstick: eps [B]
-// (doubles) behind the float64 upload on an even word (tr64_layout with `eps`), nothing ahead of it moved, and
-// drp_cloud_divergence_f64's buffer (divergence_layout with 8-byte elements: p and the gradient as doubles, staged through the same
-// cloud_layout as every one-shot), every block written in full; the finiteness check on double rows.  The matching losses' float64 yardstick: the caller's partners [H][B][N] behind the float64 upload
-// (tr64_layout with `match_in`), drp_cloud_match_f64's buffer of its own (match64_layout, with and without match_in), and the
-// check of a matching given by the caller (check_matching) on arrays of exactly [N].  The unbalanced Sinkhorn divergence:
-// divergence_layout with `reach` (eps | rho | mass_q side by side, the scratch, transported, inside a block of exactly its `bytes`,
-// the five blocks that come back where they are without it, no rho or mass_q without it), the trainer's rho [B] | mass_q [H][B] behind eps (tr_layout
-// with `reach`) and transported behind its doubles (tr_div_loss_layout with `unbalanced`), nothing ahead of them moved, and the
-// check of a reach and a target mass (check_reach) at the edges of its ranges.  Its float64 yardstick: rho [B] | mass_q [H][B]
-// (doubles) behind eps in the float64 upload (tr64_layout with `reach`), and drp_cloud_divergence_unbalanced_f64's buffer
-// (divergence_layout with `reach` and 8-byte elements: the same blocks, every double on a multiple of 8).  The seeded step: the caller's d loss / d s_pred [B][H][N][3] behind a training batch (tr_layout with
-// `seed`: floats, 16-byte aligned) and behind the float64 upload (tr64_layout with `seed`: doubles on a multiple of four words),
-// staged as train_stage_batch and train_grad_f64_body stage them and read back as kt_seed_given and k64_seed_given address them,
-// nothing ahead of either moved and a call without a seed taking no byte for it; and the scan that refuses a real row of a seed
-// that is no number (first_bad_seed) on arrays of exactly [B][H][N][3].  No device is touched.
+// The block table (tr_blocks; both trainers, every combination of the loss shape's predicates, odd and large sizes, data impulses
+// and pushes): every count against a restatement written out here; the input rows and the result rows each disjoint, in order,
+// inside `bytes` / `res_bytes`, every block on 16 bytes and every double on 8, no more than the alignment between two blocks; an
+// absent block takes no byte and has a null address in the view; adding a block moves nothing ahead of it and everything behind it
+// by its own rounded size; a reach without eps adds nothing; the fp32 arena against its offset chain written out by hand.  Then
+// the copies themselves: a batch staged as train_stage_batch and train_grad_f64_body stage it (the fixed five, then
+// tr_stage_loss_inputs) from arrays of exactly the caller's sizes into a heap block of exactly `bytes`, read back through tr_view as
+// the kernels address it; every result row written in full inside a block of exactly `res_bytes` and brought back by
+// tr_read_results into arrays of exactly the caller's sizes, a null caller pointer copying nothing -- so a block that overlaps the
+// next one or runs past an end is the sanitizer's finding.  The seed block once more as kt_seed_given and k64_seed_given address it.
+// The one buffer of the one-shots on two clouds (cloud_layout with cm_layout's, chamfer_layout's and chamfer64_layout's blocks: the
+// inputs staged, every output block written in full; the two Chamfer layouts held to offset chains written out by hand here, an
+// independent restatement), transport_layout, divergence_layout (balanced and with `reach`, 4- and 8-byte elements),
+// drp_cloud_match_f64's buffer of its own (match64_layout, with and without match_in).  The checks: a real row that is no number
+// (first_nonfinite_row), the regularisation strengths (first_bad_eps), a matching given by the caller (check_matching), a reach and
+// a target mass (check_reach), a seed's real rows (first_bad_seed), a push of no length (first_bad_push).  No device is touched.
 //
-//   train_host_check layout64 B H N M actions     prints tr64_layout's eight fields (4-byte words) and exits
-//   train_host_check layout B H N M actions eps reach seed     prints tr_layout's twelve fields (bytes) and exits
+//   train_host_check layout B H N M actions eps reach seed [f64 match_in]
+//       prints the offsets of states, impulses, attributes, densities, counts, targets, their counts, then `bytes`, then the offsets
+//       of eps, rho, mass_q, seed (bytes; 0 for an absent block) of the fp32 trainer's staged batch and exits; with the two further
+//       flags: of the float64 yardstick's upload (f64 = 1), and the offset of the caller's partners behind them
+#include <array>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -50,158 +44,151 @@ static int failures = 0;
         }                                                                    \
     } while (0)
 
-static void stage(int B, int H, int N, int M, bool actions) {
-    const TrArena lay = tr_layout(B, H, N, M, actions);
-    const size_t n_st = (size_t)B * (H + 1) * N * 3, n_imp = actions ? (size_t)B * H * 4 : (size_t)B * H * N * 3;
-    const size_t n_at = (size_t)B * (H + 1) * N, n_tg = (size_t)B * H * M * 3;
-    std::vector<float> states(n_st, 1.0f), imp(n_imp, 2.0f), attrs(n_at, 3.0f), dens(B, 4.0f), targets(n_tg, 6.0f);
-    std::vector<int32_t> nums(B, 5), tnums((size_t)B * H, 7);
-    // every block starts on 16 bytes, in the documented order, and ends before the next one starts
-    const size_t off[] = {lay.states, lay.sdelta, lay.attrs, lay.dens, lay.nums, M > 0 ? lay.targets : lay.bytes,
-                          M > 0 ? lay.tnums : lay.bytes, lay.bytes};
-    const size_t len[] = {n_st * 4, n_imp * 4, n_at * 4, (size_t)B * 4, (size_t)B * 4, n_tg * 4, M > 0 ? (size_t)B * H * 4 : 0};
-    for (int k = 0; k < 7; ++k) {
-        EXPECT(off[k] % 16 == 0);
-        EXPECT(off[k] + len[k] <= off[k + 1]);
-        EXPECT(off[k + 1] - (off[k] + len[k]) < 16);             // no more than the alignment between two blocks
+// the loss shape of a bit pattern: every combination of the predicates, meaningful or not -- the table must hold for all
+static TrShape shape_of(unsigned bits, int M) {
+    return TrShape{(bits & 1) != 0, (bits & 2) != 0, (bits & 4) != 0, (bits & 8) != 0, (bits & 16) != 0, (bits & 32) != 0, (bits & 64) != 0,
+                   (bits & 128) != 0, M};
+}
+static size_t up16(size_t v) { return (v + 15) / 16 * 16; }
+
+// rows [first, end) of a carved range: in order, disjoint, aligned, inside `total`, an absent one at offset 0 and costing nothing
+static void check_carved(const TrBlocks& t, int first, int end, size_t total) {
+    size_t prev_end = 0;
+    for (int id = first; id < end; ++id) {
+        if (t.count[id] == 0) {
+            EXPECT(t.off[id] == 0);
+            continue;
+        }
+        EXPECT(t.off[id] % 16 == 0 && t.off[id] % t.elem[id] == 0);            // every block on 16 bytes: every double on 8
+        EXPECT(t.off[id] >= prev_end && t.off[id] - prev_end < 16);            // no more than the alignment between two blocks
+        prev_end = t.off[id] + t.size(id);
     }
-    EXPECT(tr_impulse_bytes(B, H, N, actions) == n_imp * 4);
-    if (!actions && M == 0) {                                    // the existing call's layout, restated from its description
-        auto up = [](size_t v) { return (v + 15) / 16 * 16; };
-        size_t at = up(n_st * 4);
-        EXPECT(lay.sdelta == at);
-        at = up(at + (size_t)B * H * N * 3 * 4);
-        EXPECT(lay.attrs == at);
-        at = up(at + n_at * 4);
-        EXPECT(lay.dens == at);
-        at = up(at + (size_t)B * 4);
-        EXPECT(lay.nums == at);
-        EXPECT(lay.bytes == up(at + (size_t)B * 4));
+    EXPECT(total % 16 == 0 && total >= prev_end && total - prev_end < 16);
+}
+// `more` is `less` with blocks added: nothing ahead of the first added block moves, everything behind by the added rounded sizes
+static void check_added(const TrBlocks& more, const TrBlocks& less, int first, int end, size_t total_more, size_t total_less) {
+    size_t shift = 0;
+    for (int id = first; id < end; ++id) {
+        EXPECT(more.count[id] >= less.count[id]);
+        if (less.count[id]) EXPECT(more.off[id] == less.off[id] + shift);
+        shift += up16(more.size(id)) - up16(less.size(id));
     }
-    if (actions) {                                               // the pushes shrink the impulse block: nothing else moves ahead of it
-        const TrArena data = tr_layout(B, H, N, M, false);
-        EXPECT(lay.states == data.states && lay.sdelta == data.sdelta);
-        EXPECT(lay.bytes <= data.bytes);
+    EXPECT(total_more == total_less + shift);
+}
+// the layout of one call: the counts restated, both carved ranges, and what adding each predicate's blocks moves
+static void check_layout(unsigned bits, int B, int H, int N, int M, bool actions, bool f64) {
+    const TrShape s = shape_of(bits, M);
+    const TrBlocks t = tr_blocks(s, B, H, N, actions, f64);
+    const size_t b = (size_t)B, hb = (size_t)H * B, hbn = hb * N, m = s.targeted ? (size_t)M : 0;
+    const bool reach = s.sinkhorn && s.unbalanced, div = s.sinkhorn && s.divergence;
+    const size_t count[TRB_COUNT] = {b * (H + 1) * N * 3, actions ? hb * 4 : hbn * 3, f64 ? b * N : b * (H + 1) * N, b, b,
+                                     hb * m * 3, m ? hb : 0, s.sinkhorn ? b : 0, reach ? b : 0, reach ? hb : 0,
+                                     f64 && s.match_in ? hbn : 0, s.given ? hbn * 3 : 0,
+                                     hb, f64 ? (size_t)DRP_N_WEIGHTS : 0, f64 && s.chamfer ? hb : 0, s.sinkhorn ? hb : 0, div ? 2 * hb : 0,
+                                     div && reach ? hb : 0, f64 && s.match ? 2 * hb : 0, s.match ? hbn : 0, div ? 3 * hb : 0,
+                                     div ? 2 * hbn * 3 : 0};
+    const size_t elem[TRB_COUNT] = {4, 4, 4, 4, 4, 4, 4, 8, 8, 8, 4, f64 ? (size_t)8 : 4, 8, 8, 8, 8, 8, 8, 8, 4, 8, 8};
+    for (int id = 0; id < TRB_COUNT; ++id) EXPECT(t.count[id] == count[id] && t.elem[id] == elem[id]);
+    EXPECT(t.res_end == (f64 ? (int)TRB_SCRATCH : (int)TRB_COUNT));     // the float64 scratch is the chunk's, not the batch's
+    check_carved(t, TRB_STATES, TRB_IN_END, t.bytes);
+    check_carved(t, TRB_TERMS, t.res_end, t.res_bytes);
+    EXPECT(t.off[TRB_STATES] == 0 && t.off[TRB_TERMS] == 0);
+    for (unsigned bit = 1; bit < 256; bit <<= 1)
+        if (bits & bit) {               // without this predicate (a reach without eps: nothing differs, nothing moves)
+            const TrBlocks less = tr_blocks(shape_of(bits & ~bit, M), B, H, N, actions, f64);
+            check_added(t, less, TRB_STATES, TRB_IN_END, t.bytes, less.bytes);
+            check_added(t, less, TRB_TERMS, t.res_end, t.res_bytes, less.res_bytes);
+        }
+    if (!s.sinkhorn) EXPECT(t.count[TRB_RHO] == 0 && t.count[TRB_MASS_Q] == 0 && t.count[TRB_TRANSPORTED] == 0);
+    if (actions) {                      // the pushes shrink the impulse block: nothing else moves ahead of it
+        const TrBlocks data = tr_blocks(s, B, H, N, false, f64);
+        EXPECT(t.off[TRB_STATES] == data.off[TRB_STATES] && t.off[TRB_IMPULSES] == data.off[TRB_IMPULSES] && t.bytes <= data.bytes);
     }
-    // train_stage_batch's copies into a block of exactly lay.bytes
-    char* pin = static_cast<char*>(std::malloc(lay.bytes));
-    std::memset(pin, 0xff, lay.bytes);
-    std::memcpy(pin + lay.states, states.data(), n_st * sizeof(float));
-    std::memcpy(pin + lay.sdelta, imp.data(), tr_impulse_bytes(B, H, N, actions));
-    std::memcpy(pin + lay.attrs, attrs.data(), n_at * sizeof(float));
-    std::memcpy(pin + lay.dens, dens.data(), (size_t)B * sizeof(float));
-    std::memcpy(pin + lay.nums, nums.data(), (size_t)B * sizeof(int));
-    if (M > 0) {
-        std::memcpy(pin + lay.targets, targets.data(), n_tg * sizeof(float));
-        std::memcpy(pin + lay.tnums, tnums.data(), (size_t)B * H * sizeof(int));
+    if (!f64) {                         // the fp32 arena, restated from its description: kt_unpack_inputs copies it in float4 units
+        size_t at = up16(count[0] * 4);
+        EXPECT(t.off[TRB_IMPULSES] == at);
+        at = up16(at + count[1] * 4);
+        EXPECT(t.off[TRB_ATTRS] == at);
+        at = up16(at + count[2] * 4);
+        EXPECT(t.off[TRB_DENS] == at);
+        at = up16(at + b * 4);
+        EXPECT(t.off[TRB_NUMS] == at);
+        at = up16(at + b * 4);
+        if (m) EXPECT(t.off[TRB_TARGETS] == at && t.off[TRB_TNUMS] == up16(at + count[5] * 4));
+        EXPECT(t.bytes % 16 == 0 && t.count[TRB_MATCH_IN] == 0 && t.count[TRB_TOTAL] == 0);
     }
-    // read back as the kernels address it: no copy overwrote another block
-    auto f = [&](size_t o, size_t i) { float v; std::memcpy(&v, pin + o + i * 4, 4); return v; };
-    auto n = [&](size_t o, size_t i) { int32_t v; std::memcpy(&v, pin + o + i * 4, 4); return v; };
-    EXPECT(f(lay.states, 0) == 1.0f && f(lay.states, n_st - 1) == 1.0f);
-    EXPECT(f(lay.sdelta, 0) == 2.0f && f(lay.sdelta, n_imp - 1) == 2.0f);
-    EXPECT(f(lay.attrs, 0) == 3.0f && f(lay.attrs, n_at - 1) == 3.0f);
-    EXPECT(f(lay.dens, 0) == 4.0f && f(lay.dens, B - 1) == 4.0f);
-    EXPECT(n(lay.nums, 0) == 5 && n(lay.nums, B - 1) == 5);
-    if (M > 0) {
-        EXPECT(f(lay.targets, 0) == 6.0f && f(lay.targets, n_tg - 1) == 6.0f);
-        EXPECT(n(lay.tnums, 0) == 7 && n(lay.tnums, (size_t)B * H - 1) == 7);
+}
+
+// One call's copies.  Up: arrays of exactly the caller's sizes staged into a block of exactly `bytes` as train_stage_batch and
+// train_grad_f64_body do, read back through tr_view as the kernels address them.  Down: every result row written in full inside a
+// block of exactly `res_bytes`, brought back by tr_read_results into arrays of exactly the caller's sizes
+static void stage(unsigned bits, int B, int H, int N, int M, bool actions, bool f64) {
+    const TrShape s = shape_of(bits, M);
+    const TrBlocks t = tr_blocks(s, B, H, N, actions, f64);
+    std::vector<std::vector<char>> arr(TRB_COUNT);
+    for (int id = 0; id < TRB_COUNT; ++id) arr[id].assign(t.size(id), (char)(id + 1));
+    arr[TRB_ATTRS].assign((size_t)B * (H + 1) * N * 4, (char)(TRB_ATTRS + 1));          // the caller's attributes are [B][H+1][N] either way
+    auto in = [&](int id) { return arr[id].empty() ? nullptr : arr[id].data(); };
+    TrLoss lk;
+    lk.targets = reinterpret_cast<const float*>(in(TRB_TARGETS)); lk.target_nums = reinterpret_cast<const int32_t*>(in(TRB_TNUMS));
+    lk.eps = reinterpret_cast<const double*>(in(TRB_EPS)); lk.rho = reinterpret_cast<const double*>(in(TRB_RHO));
+    lk.mass_q = reinterpret_cast<const double*>(in(TRB_MASS_Q)); lk.match_in = reinterpret_cast<const int32_t*>(in(TRB_MATCH_IN));
+    if (f64) lk.seed64 = reinterpret_cast<const double*>(in(TRB_SEED));
+    else lk.seed = reinterpret_cast<const float*>(in(TRB_SEED));
+    char* pin = static_cast<char*>(std::malloc(t.bytes));
+    std::memset(pin, 0xff, t.bytes);
+    for (int id = TRB_STATES; id <= TRB_NUMS; ++id)
+        if (id == TRB_ATTRS && f64)
+            for (int b = 0; b < B; ++b) std::memcpy(pin + t.off[id] + (size_t)b * N * 4, arr[id].data() + (size_t)b * (H + 1) * N * 4, (size_t)N * 4);
+        else
+            std::memcpy(pin + t.off[id], arr[id].data(), t.size(id));
+    tr_stage_loss_inputs(pin, t, lk);
+    char* res = static_cast<char*>(std::malloc(t.res_bytes));
+    const TrView v = tr_view(pin, res, t);
+    const void* seen[TRB_COUNT] = {pin, pin + t.off[TRB_IMPULSES], pin + t.off[TRB_ATTRS], pin + t.off[TRB_DENS], pin + t.off[TRB_NUMS],
+                                   v.targets, v.tnums, v.eps, v.rho, v.mass_q, v.match_in, v.seed,
+                                   v.terms, v.total, v.margin, v.col_err, v.self_err, v.transported, v.cost, v.match, v.vals, v.gsum};
+    for (int id = 0; id < TRB_IN_END; ++id) {           // the staged bytes are the caller's: no copy overwrote another block
+        EXPECT((seen[id] != nullptr) == (t.count[id] != 0));
+        if (seen[id]) EXPECT(std::memcmp(seen[id], arr[id].data(), t.size(id)) == 0 && reinterpret_cast<uintptr_t>(seen[id]) % t.elem[id] == 0);
     }
+    for (int id = TRB_TERMS; id < TRB_COUNT; ++id) {
+        EXPECT((seen[id] != nullptr) == (t.count[id] != 0 && id < t.res_end));
+        if (seen[id]) {
+            EXPECT(seen[id] == res + t.off[id] && t.off[id] + t.size(id) <= t.res_bytes);
+            std::memset(res + t.off[id], id + 1, t.size(id));                          // as the kernels write it: in full
+        }
+    }
+    auto out = [&](int id) { arr[id].assign(t.size(id), 0); return arr[id].empty() ? nullptr : arr[id].data(); };
+    lk.margin_out = reinterpret_cast<double*>(out(TRB_MARGIN)); lk.col_err_out = reinterpret_cast<double*>(out(TRB_COL_ERR));
+    lk.self_err_out = reinterpret_cast<double*>(out(TRB_SELF_ERR)); lk.transported_out = reinterpret_cast<double*>(out(TRB_TRANSPORTED));
+    lk.cost_out = reinterpret_cast<double*>(out(TRB_COST)); lk.match_out = reinterpret_cast<int32_t*>(out(TRB_MATCH));
+    int copies = 0;
+    auto copy = [&copies](void* dst, const void* src, size_t n) { std::memcpy(dst, src, n); ++copies; return 0; };
+    EXPECT(tr_read_results(t, res, lk, copy) == 0);
+    int present = 0;
+    for (int id = TRB_MARGIN; id < TRB_SCRATCH; ++id) {
+        present += t.count[id] != 0;
+        if (t.count[id]) EXPECT(arr[id].front() == (char)(id + 1) && arr[id].back() == (char)(id + 1));
+    }
+    EXPECT(copies == present);
+    EXPECT(tr_read_results(t, res, TrLoss{}, copy) == 0 && copies == present);          // no caller pointer: nothing is copied
+    EXPECT(tr_read_results(t, res, lk, [](void*, const void*, size_t) { return 7; }) == (present ? 7 : 0));    // a copy's error ends the walk
+    std::free(res);
     std::free(pin);
 }
 
-// the float64 yardsticks' batch as train_grad_f64_body stages it: one vector of exactly Tr64Arena::words 4-byte words
-static void stage64(int B, int H, int N, int M, bool actions) {
-    const Tr64Arena lay = tr64_layout(B, H, N, M, actions);
-    const size_t n_st = (size_t)B * (H + 1) * N * 3, n_imp = actions ? (size_t)B * H * 4 : (size_t)B * H * N * 3;
-    const size_t n_at_in = (size_t)B * (H + 1) * N, n_tg = (size_t)B * H * M * 3;
-    std::vector<float> states(n_st, 1.0f), imp(n_imp, 2.0f), attrs(n_at_in, 3.0f), dens(B, 4.0f), targets(n_tg, 6.0f);
-    std::vector<int32_t> nums(B, 5), tnums((size_t)B * H, 7);
-    // packed, in the documented order: every block ends where the next one starts
-    const size_t off[] = {lay.states, lay.sdelta, lay.attr, lay.dens, lay.nums, lay.targets, lay.tnums, lay.words};
-    const size_t len[] = {n_st, n_imp, (size_t)B * N, (size_t)B, (size_t)B, n_tg, M > 0 ? (size_t)B * H : 0};
-    for (int k = 0; k < 7; ++k) EXPECT(off[k] + len[k] == off[k + 1]);
-    EXPECT(lay.states == 0);
-    if (M == 0) EXPECT(lay.words == n_st + n_imp + (size_t)B * N + 2 * (size_t)B);      // drp_train_grad_f64's vector, restated
-    // train_grad_f64_body's copies into a block of exactly lay.words words
-    float* host = static_cast<float*>(std::malloc(lay.words * sizeof(float)));
-    std::memset(host, 0xff, lay.words * sizeof(float));
-    std::memcpy(host + lay.states, states.data(), (lay.sdelta - lay.states) * sizeof(float));
-    std::memcpy(host + lay.sdelta, imp.data(), (lay.attr - lay.sdelta) * sizeof(float));
-    for (int b = 0; b < B; ++b) std::memcpy(host + lay.attr + (size_t)b * N, attrs.data() + (size_t)b * (H + 1) * N, (size_t)N * sizeof(float));
-    std::memcpy(host + lay.dens, dens.data(), (size_t)B * sizeof(float));
-    std::memcpy(host + lay.nums, nums.data(), (size_t)B * sizeof(int32_t));
-    if (M > 0) {
-        std::memcpy(host + lay.targets, targets.data(), n_tg * sizeof(float));
-        std::memcpy(host + lay.tnums, tnums.data(), (size_t)B * H * sizeof(int32_t));
-    }
-    auto n = [&](size_t o, size_t i) { int32_t v; std::memcpy(&v, host + o + i, 4); return v; };
-    EXPECT(host[lay.states] == 1.0f && host[lay.sdelta - 1] == 1.0f);
-    EXPECT(host[lay.sdelta] == 2.0f && host[lay.attr - 1] == 2.0f);
-    EXPECT(host[lay.attr] == 3.0f && host[lay.dens - 1] == 3.0f);
-    EXPECT(host[lay.dens] == 4.0f && host[lay.nums - 1] == 4.0f);
-    EXPECT(n(lay.nums, 0) == 5 && n(lay.nums, B - 1) == 5);
-    if (M > 0) {
-        EXPECT(host[lay.targets] == 6.0f && host[lay.tnums - 1] == 6.0f);
-        EXPECT(n(lay.tnums, 0) == 7 && n(lay.tnums, (size_t)B * H - 1) == 7 && lay.tnums + (size_t)B * H == lay.words);
-    }
-    std::free(host);
-}
-
-// drp_train_grad_f64_divergence's upload: eps [B] (doubles) behind everything else on an 8-byte boundary of a vector whose base is
-// aligned, the other blocks where they were
-static void stage64_eps(int B, int H, int N, int M, bool actions) {
-    const Tr64Arena lay = tr64_layout(B, H, N, M, actions, true), plain = tr64_layout(B, H, N, M, actions);
-    EXPECT(lay.states == plain.states && lay.sdelta == plain.sdelta && lay.attr == plain.attr && lay.dens == plain.dens &&
-           lay.nums == plain.nums && lay.targets == plain.targets && lay.tnums == plain.tnums);
-    EXPECT(lay.eps % 2 == 0 && lay.eps >= plain.words && lay.eps - plain.words < 2);
-    EXPECT(lay.words == lay.eps + 2 * (size_t)B);
-    EXPECT(plain.eps == 0);
-    std::vector<double> eps(B, 0.5);
-    float* host = static_cast<float*>(std::malloc(lay.words * sizeof(float)));      // (malloc aligns to 16: the device buffer to 256)
-    std::memset(host, 0xff, lay.words * sizeof(float));
-    std::memcpy(host + lay.eps, eps.data(), (size_t)B * sizeof(double));
-    EXPECT(reinterpret_cast<uintptr_t>(host + lay.eps) % sizeof(double) == 0);
-    const double* as_kernel = reinterpret_cast<const double*>(host + lay.eps);       // as kd64_sweeps addresses it
-    EXPECT(as_kernel[0] == 0.5 && as_kernel[B - 1] == 0.5);
-    std::free(host);
-}
-
-// drp_train_grad_f64_divergence_unbalanced's upload: rho [B] | mass_q [H][B] (doubles) behind eps, 8-byte aligned, everything ahead
-// of them where it was; both written and read back as the kernels address them, in a block of exactly `words`
-static void stage64_reach(int B, int H, int N, int M, bool actions) {
-    const Tr64Arena lay = tr64_layout(B, H, N, M, actions, true, false, true), plain = tr64_layout(B, H, N, M, actions, true);
-    EXPECT(lay.states == plain.states && lay.sdelta == plain.sdelta && lay.attr == plain.attr && lay.dens == plain.dens &&
-           lay.nums == plain.nums && lay.targets == plain.targets && lay.tnums == plain.tnums && lay.eps == plain.eps);
-    EXPECT(lay.rho == plain.words && lay.rho % 2 == 0);
-    EXPECT(lay.mass_q == lay.rho + 2 * (size_t)B && lay.words == lay.mass_q + 2 * (size_t)H * B);
-    EXPECT(plain.rho == 0 && plain.mass_q == 0);
-    EXPECT(tr64_layout(B, H, N, M, actions, false, false, true).words == tr64_layout(B, H, N, M, actions).words);  // (no reach without eps)
-    std::vector<double> rho(B, 0.25), w((size_t)H * B, 1.5);
-    float* host = static_cast<float*>(std::malloc(lay.words * sizeof(float)));
-    std::memset(host, 0xff, lay.words * sizeof(float));
-    std::memcpy(host + lay.rho, rho.data(), (size_t)B * sizeof(double));
-    std::memcpy(host + lay.mass_q, w.data(), (size_t)H * B * sizeof(double));
-    EXPECT(reinterpret_cast<uintptr_t>(host + lay.rho) % sizeof(double) == 0);
-    const double* r = reinterpret_cast<const double*>(host + lay.rho);               // as kd64_sweeps_unbalanced addresses them
-    const double* m = reinterpret_cast<const double*>(host + lay.mass_q);
-    EXPECT(r[0] == 0.25 && r[B - 1] == 0.25 && m[0] == 1.5 && m[(size_t)(H - 1) * B + (B - 1)] == 1.5);
-    std::free(host);
-}
-
-// drp_train_grad_f64_match's upload: the caller's partners [H][B][N] (ints) behind everything else, the other blocks where they were
-static void stage64_match(int B, int H, int N, int M, bool actions) {
-    const Tr64Arena lay = tr64_layout(B, H, N, M, actions, false, true), plain = tr64_layout(B, H, N, M, actions);
-    EXPECT(lay.states == plain.states && lay.sdelta == plain.sdelta && lay.attr == plain.attr && lay.dens == plain.dens &&
-           lay.nums == plain.nums && lay.targets == plain.targets && lay.tnums == plain.tnums);
-    EXPECT(lay.match_in == plain.words && lay.words == lay.match_in + (size_t)H * B * N && plain.match_in == 0);
-    std::vector<int32_t> match((size_t)H * B * N, 7);
-    float* host = static_cast<float*>(std::malloc(lay.words * sizeof(float)));
-    std::memset(host, 0xff, lay.words * sizeof(float));
-    std::memcpy(host + lay.match_in, match.data(), match.size() * sizeof(int32_t));
-    const int* as_kernel = reinterpret_cast<const int*>(host + lay.match_in);          // as ka64_match addresses it
-    EXPECT(as_kernel[0] == 7 && as_kernel[((size_t)(H - 1) * B + (B - 1)) * N + (N - 1)] == 7);
-    std::free(host);
+// the seed block [B][H][N][3] as kt_seed_given (floats) and k64_seed_given (doubles) address it behind a batch of every kind
+static void stage_seed(int B, int H, int N, int M, bool actions) {
+    const size_t n_seed = (size_t)B * H * N * 3, last = ((size_t)(B - 1) * H + (H - 1)) * N * 3 + (size_t)N * 3 - 1;
+    EXPECT(last == n_seed - 1);
+    for (unsigned bits : {128u, 128u | 1u, 128u | 1u | 16u, 128u | 1u | 16u | 64u})
+        for (int f64 = 0; f64 < 2; ++f64) {
+            const TrBlocks t = tr_blocks(shape_of(bits, M), B, H, N, actions, f64 != 0), plain = tr_blocks(shape_of(bits & ~128u, M), B, H, N, actions, f64 != 0);
+            EXPECT(plain.count[TRB_SEED] == 0 && plain.off[TRB_SEED] == 0 && t.off[TRB_SEED] == plain.bytes);
+            EXPECT(t.bytes == up16(plain.bytes + n_seed * (f64 ? 8 : 4)));
+            if (!f64 && (N * 3) % 4 == 0) EXPECT((t.off[TRB_SEED] + ((size_t)(B - 1) * H + (H - 1)) * N * 3 * 4) % 16 == 0);  // its float4 path's premise
+        }
 }
 
 // drp_cloud_match_f64's buffer: the inputs (p as doubles, the caller's partners last and optional) staged into a vector of exactly
@@ -353,21 +340,6 @@ static void stage_divergence(int B, int N, int M, size_t p_elem) {
     reinterpret_cast<double*>(io + lay.vals)[2 * (size_t)B + (B - 1)] = 1.0;
     std::free(io);
 }
-// drp_train_step_divergence's doubles on the device: the terms, the certificates and the kernels' scratch, packed, in doubles
-static void stage_div_loss(int B, int H, int N) {
-    const TrDivLoss dl = tr_div_loss_layout(B, H, N);
-    const size_t hb = (size_t)H * B;
-    const size_t off[] = {dl.terms, dl.col_err, dl.self_err, dl.vals, dl.gsum, dl.count};
-    const size_t len[] = {hb, hb, 2 * hb, 3 * hb, 2 * hb * N * 3};
-    EXPECT(dl.terms == 0 && dl.col_err == hb);                       // the transport loss's two blocks where they were
-    double* d = static_cast<double*>(std::malloc(dl.count * sizeof(double)));
-    for (int k = 0; k < 5; ++k) {
-        EXPECT(off[k] + len[k] == off[k + 1]);
-        for (size_t e = 0; e < len[k]; ++e) d[off[k] + e] = (double)k;
-    }
-    for (int k = 0; k < 5; ++k) EXPECT(d[off[k]] == (double)k && d[off[k + 1] - 1] == (double)k);
-    std::free(d);
-}
 // drp_cloud_divergence_unbalanced (divergence_layout with `reach`): the five blocks where they were; behind them eps | rho | mass_q [B] each, side
 // by side (one copy up), the same scratch, then transported [B], all inside a block of exactly `bytes`.  p_elem 8:
 // drp_cloud_divergence_unbalanced_f64
@@ -392,37 +364,6 @@ static void stage_divergence_unbalanced(int B, int N, int M, size_t p_elem) {
     reinterpret_cast<double*>(io + lay.mass_q)[B - 1] = 1.0;
     std::free(io);
 }
-// drp_train_step_divergence_unbalanced: the balanced step's doubles where they were, transported [H][B] behind them; and its batch:
-// rho [B] | mass_q [H][B] behind eps, nothing ahead of them moved
-static void stage_div_unbalanced_train(int B, int H, int N, int M, bool actions) {
-    const TrDivLoss dl = tr_div_loss_layout(B, H, N, true), plain = tr_div_loss_layout(B, H, N);
-    const size_t hb = (size_t)H * B;
-    EXPECT(dl.terms == plain.terms && dl.col_err == plain.col_err && dl.self_err == plain.self_err && dl.vals == plain.vals &&
-           dl.gsum == plain.gsum);
-    EXPECT(dl.transported == plain.count && dl.count == dl.transported + hb && plain.transported == 0);
-    double* d = static_cast<double*>(std::malloc(dl.count * sizeof(double)));
-    for (size_t e = 0; e < hb; ++e) d[dl.transported + e] = 1.0;
-    EXPECT(d[dl.count - 1] == 1.0);
-    std::free(d);
-    const TrArena lay = tr_layout(B, H, N, M, actions, true, true), bal = tr_layout(B, H, N, M, actions, true);
-    EXPECT(lay.states == bal.states && lay.sdelta == bal.sdelta && lay.attrs == bal.attrs && lay.dens == bal.dens && lay.nums == bal.nums &&
-           lay.targets == bal.targets && lay.tnums == bal.tnums && lay.eps == bal.eps);
-    EXPECT(lay.rho == bal.bytes && lay.rho % 16 == 0 && lay.mass_q % 16 == 0 && lay.bytes % 16 == 0);
-    EXPECT(lay.rho + (size_t)B * 8 <= lay.mass_q && lay.mass_q - (lay.rho + (size_t)B * 8) < 16);
-    EXPECT(lay.mass_q + hb * 8 <= lay.bytes && lay.bytes - (lay.mass_q + hb * 8) < 16);
-    EXPECT(tr_layout(B, H, N, M, actions, false, true).bytes == tr_layout(B, H, N, M, actions).bytes);     // a reach without eps: nothing
-    std::vector<double> rho(B, 0.5), w(hb, 2.0);
-    char* pin = static_cast<char*>(std::malloc(lay.bytes));
-    std::memset(pin, 0xff, lay.bytes);
-    std::memcpy(pin + lay.rho, rho.data(), (size_t)B * sizeof(double));
-    std::memcpy(pin + lay.mass_q, w.data(), hb * sizeof(double));
-    double last;
-    std::memcpy(&last, pin + lay.mass_q + (hb - 1) * 8, 8);
-    EXPECT(last == 2.0);
-    std::memcpy(&last, pin + lay.rho + (size_t)(B - 1) * 8, 8);
-    EXPECT(last == 0.5);
-    std::free(pin);
-}
 // the reach and the target mass a problem of the unbalanced divergence is served with (check_reach)
 static void check_reaches() {
     const double inf64 = std::numeric_limits<double>::infinity(), nan64 = std::numeric_limits<double>::quiet_NaN();
@@ -434,63 +375,6 @@ static void check_reaches() {
     EXPECT(check_reach(eps, 4 * eps, 0.1249) == REACH_MASS && check_reach(eps, 4 * eps, 8.001) == REACH_MASS);
     EXPECT(check_reach(eps, 4 * eps, nan64) == REACH_MASS && check_reach(eps, 4 * eps, 0.0) == REACH_MASS && check_reach(eps, inf64, nan64) == REACH_MASS);
     EXPECT(check_reach(eps, inf64, 0.6) == REACH_INF_MASS && check_reach(eps, inf64, 8.0) == REACH_INF_MASS);
-}
-// drp_train_step_transport's batch: eps [B] (doubles) behind everything else, the other blocks where they were
-static void stage_eps(int B, int H, int N, int M, bool actions) {
-    const TrArena lay = tr_layout(B, H, N, M, actions, true), plain = tr_layout(B, H, N, M, actions);
-    EXPECT(lay.states == plain.states && lay.sdelta == plain.sdelta && lay.attrs == plain.attrs && lay.dens == plain.dens &&
-           lay.nums == plain.nums && lay.targets == plain.targets && lay.tnums == plain.tnums);
-    EXPECT(lay.eps == plain.bytes && lay.eps % 16 == 0);
-    EXPECT(lay.eps + (size_t)B * 8 <= lay.bytes && lay.bytes - (lay.eps + (size_t)B * 8) < 16 && lay.bytes % 16 == 0);
-    std::vector<double> eps(B, 0.5);
-    char* pin = static_cast<char*>(std::malloc(lay.bytes));
-    std::memset(pin, 0xff, lay.bytes);
-    std::memcpy(pin + lay.eps, eps.data(), (size_t)B * sizeof(double));
-    double last;
-    std::memcpy(&last, pin + lay.eps + (size_t)(B - 1) * 8, 8);
-    EXPECT(last == 0.5);
-    std::free(pin);
-}
-
-// drp_train_step_seeded's batch: the seed [B][H][N][3] (floats) behind everything else, the other blocks where they were, with every
-// combination of the older blocks; drp_train_grad_f64_seeded's upload: the same in doubles behind the float64 batch
-static void stage_seed(int B, int H, int N, int M, bool actions) {
-    const size_t n_seed = (size_t)B * H * N * 3;
-    for (int eps = 0; eps < 2; ++eps)
-        for (int reach = 0; reach < 2; ++reach) {
-            const TrArena lay = tr_layout(B, H, N, M, actions, eps != 0, reach != 0, true), plain = tr_layout(B, H, N, M, actions, eps != 0, reach != 0);
-            EXPECT(lay.states == plain.states && lay.sdelta == plain.sdelta && lay.attrs == plain.attrs && lay.dens == plain.dens &&
-                   lay.nums == plain.nums && lay.targets == plain.targets && lay.tnums == plain.tnums && lay.eps == plain.eps &&
-                   lay.rho == plain.rho && lay.mass_q == plain.mass_q);
-            EXPECT(plain.seed == 0 && lay.seed == plain.bytes && lay.seed % 16 == 0 && lay.bytes % 16 == 0);
-            EXPECT(lay.seed + n_seed * 4 <= lay.bytes && lay.bytes - (lay.seed + n_seed * 4) < 16);
-        }
-    const TrArena lay = tr_layout(B, H, N, M, actions, false, false, true);
-    std::vector<float> seed(n_seed);
-    for (size_t e = 0; e < n_seed; ++e) seed[e] = (float)(e % 1021);
-    char* pin = static_cast<char*>(std::malloc(lay.bytes));
-    std::memset(pin, 0xff, lay.bytes);
-    std::memcpy(pin + lay.seed, seed.data(), n_seed * sizeof(float));           // train_stage_batch's copy
-    // as kt_seed_given addresses it: sample b, step t at ((b H + t) N) 3 floats, the last element of the last slice included
-    const float* as_kernel = reinterpret_cast<const float*>(pin + lay.seed);
-    const size_t last = ((size_t)(B - 1) * H + (H - 1)) * N * 3 + (size_t)N * 3 - 1;
-    EXPECT(last == n_seed - 1 && as_kernel[0] == 0.0f && as_kernel[last] == (float)(last % 1021));
-    if ((N * 3) % 4 == 0) EXPECT((lay.seed + ((size_t)(B - 1) * H + (H - 1)) * N * 3 * 4) % 16 == 0);      // its float4 path's premise
-    std::free(pin);
-
-    const Tr64Arena l64 = tr64_layout(B, H, N, M, actions, false, false, false, true), p64 = tr64_layout(B, H, N, M, actions);
-    EXPECT(l64.states == p64.states && l64.sdelta == p64.sdelta && l64.attr == p64.attr && l64.dens == p64.dens && l64.nums == p64.nums &&
-           l64.targets == p64.targets && l64.tnums == p64.tnums);
-    EXPECT(p64.seed == 0 && l64.seed % 4 == 0 && l64.seed >= p64.words && l64.seed - p64.words < 4 && l64.words == l64.seed + 2 * n_seed);
-    std::vector<double> seed64(n_seed, 0.5);
-    seed64[n_seed - 1] = 0.25;
-    float* host = static_cast<float*>(std::malloc(l64.words * sizeof(float)));
-    std::memset(host, 0xff, l64.words * sizeof(float));
-    std::memcpy(host + l64.seed, seed64.data(), n_seed * sizeof(double));       // train_grad_f64_body's copy
-    EXPECT(reinterpret_cast<uintptr_t>(host + l64.seed) % 16 == 0);              // (malloc aligns to 16: the device buffer to 256)
-    const double* k64 = reinterpret_cast<const double*>(host + l64.seed);        // as k64_seed_given addresses it
-    EXPECT(k64[0] == 0.5 && k64[last] == 0.25);
-    std::free(host);
 }
 // the scan of a seed's real rows: every one of them read, in every step, and nothing of the padding
 template <typename T>
@@ -545,31 +429,34 @@ static void stage_chamfer(int B, int N, int M) {
 }
 
 int main(int argc, char** argv) {
-    if (argc == 7 && std::strcmp(argv[1], "layout64") == 0) {
-        const Tr64Arena a = tr64_layout(std::atoi(argv[2]), std::atoi(argv[3]), std::atoi(argv[4]), std::atoi(argv[5]), std::atoi(argv[6]) != 0);
-        std::printf("%zu %zu %zu %zu %zu %zu %zu %zu\n", a.states, a.sdelta, a.attr, a.dens, a.nums, a.targets, a.tnums, a.words);
-        return 0;
-    }
-    if (argc == 10 && std::strcmp(argv[1], "layout") == 0) {
-        const TrArena a = tr_layout(std::atoi(argv[2]), std::atoi(argv[3]), std::atoi(argv[4]), std::atoi(argv[5]), std::atoi(argv[6]) != 0,
-                                    std::atoi(argv[7]) != 0, std::atoi(argv[8]) != 0, std::atoi(argv[9]) != 0);
-        std::printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", a.states, a.sdelta, a.attrs, a.dens, a.nums, a.targets, a.tnums,
-                    a.bytes, a.eps, a.rho, a.mass_q, a.seed);
+    if ((argc == 10 || argc == 12) && std::strcmp(argv[1], "layout") == 0) {
+        int x[10] = {};
+        for (int k = 2; k < argc; ++k) x[k - 2] = std::atoi(argv[k]);
+        TrShape s{};
+        s.targeted = x[3] > 0; s.M = x[3]; s.sinkhorn = x[5] != 0; s.unbalanced = x[6] != 0; s.given = x[7] != 0; s.match = s.match_in = x[9] != 0;
+        const TrBlocks t = tr_blocks(s, x[0], x[1], x[2], x[4] != 0, x[8] != 0);
+        const int ids[] = {TRB_STATES, TRB_IMPULSES, TRB_ATTRS, TRB_DENS, TRB_NUMS, TRB_TARGETS, TRB_TNUMS, -1, TRB_EPS, TRB_RHO, TRB_MASS_Q,
+                           TRB_SEED, TRB_MATCH_IN};
+        for (int k = 0; k < (argc == 10 ? 12 : 13); ++k) std::printf(k ? " %zu" : "%zu", ids[k] < 0 ? t.bytes : t.off[ids[k]]);
+        std::printf("\n");
         return 0;
     }
     // odd sizes (no block a multiple of 16 bytes), one sample, the reference's batch, a large one
     const int shapes[][4] = {{1, 1, 1, 0}, {1, 1, 5, 3}, {3, 3, 24, 0}, {3, 3, 23, 17}, {2, 5, 11, 0}, {4, 5, 300, 0}, {4, 5, 300, 300},
-                             {7, 2, 301, 299}, {32, 5, 300, 0}, {2, 64, 9, 1}};
+                             {7, 2, 301, 299}, {32, 5, 300, 0}, {2, 64, 9, 1}, {3, 3, 5, 3}};
+    // the loss shapes the entry points form (targeted 1, chamfer 2, match 4, match_in 8, sinkhorn 16, divergence 32, unbalanced 64,
+    // given 128): MSE, Chamfer, match (with a match_in too), the mix (likewise), transport, divergence, with a reach, a given seed
+    const unsigned kinds[] = {0, 1 | 2, 1 | 4, 1 | 4 | 8, 1 | 2 | 4, 1 | 2 | 4 | 8, 1 | 16, 1 | 16 | 32, 1 | 16 | 32 | 64, 128};
     for (const auto& s : shapes)
         for (int actions = 0; actions < 2; ++actions) {
-            stage(s[0], s[1], s[2], s[3], actions != 0);
-            stage64(s[0], s[1], s[2], s[3], actions != 0);
+            for (int f64 = 0; f64 < 2; ++f64) {
+                for (unsigned bits = 0; bits < 256; ++bits) check_layout(bits, s[0], s[1], s[2], s[3], actions != 0, f64 != 0);
+                for (unsigned bits : kinds)
+                    if (s[3] > 0 || !(bits & 1)) stage(bits, s[0], s[1], s[2], s[3], actions != 0, f64 != 0);
+            }
             stage_seed(s[0], s[1], s[2], s[3], actions != 0);
-            if (s[3] > 0) stage64_eps(s[0], s[1], s[2], s[3], actions != 0);
-            if (s[3] > 0) stage64_match(s[0], s[1], s[2], s[3], actions != 0);
-            if (s[3] > 0) stage64_reach(s[0], s[1], s[2], s[3], actions != 0);
         }
-    stage64(1, 1, 4096, 4096, false);                            // the largest clouds of one (sample, step)
+    for (int f64 = 0; f64 < 2; ++f64) stage(1 | 2, 1, 1, 4096, 4096, false, f64 != 0);      // the largest clouds of one (sample, step)
     const int mshapes[][3] = {{1, 1, 1}, {1, 5, 3}, {3, 7, 9}, {2, 65, 64}, {1, 1024, 1024}, {5, 1024, 1}, {4, 300, 257}};
     for (const auto& s : mshapes) {
         stage_match(s[0], s[1], s[2]);
@@ -582,14 +469,8 @@ int main(int argc, char** argv) {
         stage_match64(s[0], s[1], s[2], true);
     }
     check_matchings();
-    const int dshapes[][3] = {{1, 1, 1}, {2, 2, 9}, {4, 5, 100}, {3, 1, 1024}};
-    for (const auto& s : dshapes) stage_div_loss(s[0], s[1], s[2]);
-    for (const auto& s : shapes)
-        for (int actions = 0; actions < 2; ++actions)
-            if (s[3] > 0) {
-                stage_eps(s[0], s[1], s[2], s[3], actions != 0);
-                stage_div_unbalanced_train(s[0], s[1], s[2], s[3], actions != 0);
-            }
+    for (unsigned bits : {1u | 16u | 32u, 1u | 16u | 32u | 64u})                               // the divergence's results at its caps
+        for (const auto& s : {std::array<int, 3>{4, 5, 100}, std::array<int, 3>{3, 1, 1024}}) stage(bits, s[0], s[1], s[2], s[2], false, false);
     check_reaches();
     check_seeds<float>();
     check_seeds<double>();
