@@ -144,6 +144,18 @@ SIGNATURES = {
     'drp_gd_get': (ctypes.c_int, [ctypes.c_void_p, c_float_p]),
     'drp_gd_step_async': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'drp_gd_wait': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_float_p, c_float_p]),
+    'drp_gd_begin_cost': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.c_int, ctypes.c_int,
+                                         c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_float_p, c_float_p]),
+    'drp_gd_predict': (ctypes.c_int, [ctypes.c_void_p, c_float_p]),
+    'drp_gd_grad_seeded': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p]),
+    'drp_gd_step_seeded': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p]),
+    'drp_gd_predict_f64': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.c_int, ctypes.c_int, c_float_p,
+                                          ctypes.c_int, ctypes.c_int, c_double_p]),
+    'drp_gd_grad_f64_seeded': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.c_int, ctypes.c_int,
+                                              c_float_p, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p]),
+    'drp_mpc_begin_cost': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(MpcParams), c_float_p, c_float_p, c_float_p,
+                                          c_double_p]),
+    'drp_mpc_set_rewards': (ctypes.c_int, [ctypes.c_void_p, c_float_p]),
     'drp_comm_unique_id': (ctypes.c_int, [ctypes.c_char_p]),
     'drp_comm_init': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int]),
     'drp_comm_destroy': (ctypes.c_int, [ctypes.c_void_p]),

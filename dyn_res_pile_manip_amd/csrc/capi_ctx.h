@@ -264,6 +264,11 @@ struct drp_ctx {
     float gd_lo[4] = {0, 0, 0, 0}, gd_hi[4] = {0, 0, 0, 0};
     DevBuf eff_hist, g_eff, g_cnode, g_agg, g_proj, g_state, g_sdelta, g_act, adam_m, adam_v;
     DevBuf tape_sdelta, tape_idx, tape_cnt, tape_mask, g_agg_hist, rev_off, rev, gpos_edge;
+    // planning on a caller's cost (drp_gd_begin_cost, drp_gd_*_seeded; drp_mpc_begin_cost, drp_mpc_set_rewards)
+    bool gd_cost = false;           // the GD session was begun without a goal: the built-in reward's calls are refused
+    DevBuf gd_seed_in, gd_seed;     // the caller's seed as it arrives [B][H][N][3], and steps 0 .. H-2 of it step-major [H-1][B,N,3]
+    bool mpc_cost = false;          // the sampling session was begun without a goal: its rollout runs no reward kernel
+    bool mpc_rewards_ok = true;     // a cost session: the final-step rewards of the last rollout are in (drp_mpc_set_rewards)
 
     // particle extraction (row f2)
     DevBuf px_depth, px_mask, px_blk, px_bmin, px_bmax, px_grid, px_pcd, px_keys, px_cellcnt, px_cellfill,

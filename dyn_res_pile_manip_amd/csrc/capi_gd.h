@@ -16,7 +16,12 @@ void launch_edge_encode_mfma(drp_ctx* c, const float* s_prev, int prev_mod, size
 }
 // what one pass of the session does beside the gradients: the optimiser step that rides on the last kb_sdelta launch (a null
 // adam.act: gradients only) and where kb_reward also stores the rewards (pinned host memory; null: the device buffer only)
-struct GdPass { KbAdam adam = KbAdam{}; float* host_rewards = nullptr; };
+// `seeded`: no reward -- the caller's d loss / d s_pred (staged in c->gd_seed_in, [B][H][N][3]) seeds the reverse pass in kb_reward's
+// place.  Step H-1's slice IS d loss / d state_{H-1}, as kb_reward's gradient is; the slice of a step t < H-1 joins d loss /
+// d state_t where that is summed: residual share (the copy of g_out), THEN THE SEED, then the relation encoder's own slots and
+// reversed lists (kb_gather_pos: its g_add, "added first"), then gen_s_delta's position share (kb_sdelta).  `forward_only`: the tape's
+// forward alone (drp_gd_predict).
+struct GdPass { KbAdam adam = KbAdam{}; float* host_rewards = nullptr; bool seeded = false; bool forward_only = false; };
 int gd_forward_backward(drp_ctx* c, const GdPass& pass) {
     const int nb = c->gd_nb, N = c->gd_N, B = c->gd_B, H = c->gd_H;
     const size_t bn = (size_t)B * N;
@@ -46,9 +51,17 @@ int gd_forward_backward(drp_ctx* c, const GdPass& pass) {
         if (H == 1) { f.rev_off = ptr<int>(c->rev_off); f.rev = ptr<int>(c->rev); f.rev_built = &rev_built; }   // one set of reversed lists: the only step's
         CHK(run_tape_forward(c, c->gd_engine, B, N, H, f));
     }
+    if (pass.forward_only) { HIPCHK(c, hipGetLastError()); return DRP_OK; }
     // reward of the final step only (planners.py:436-438) and its gradient, in one launch
     float* g_state = ptr<float>(c->g_state);                 // [H][B,N,3]
-    {
+    const float* seed_mid = nullptr;                         // [H-1][B,N,3]: the seeds of the steps before the last
+    if (pass.seeded) {
+        CHK(ensure(c, c->gd_seed, (size_t)(H > 1 ? H - 1 : 1) * bn * 3 * sizeof(float)));
+        seed_mid = ptr<float>(c->gd_seed);
+        ProbeScope ps(c, KC_BWD_REWARD);
+        hipLaunchKernelGGL(kb_seed_stage, dim3(B, H), dim3(256), 0, st, ptr<float>(c->gd_seed_in), N, ptr<float>(c->gd_seed),
+                           g_state + (size_t)(H - 1) * bn * 3);
+    } else {
         ProbeScope ps(c, KC_BWD_REWARD);
         c->dv(DV_BWD_REWARD);
         if (c->gd_S > 0) {          // a goal per row: row r belongs to scene (r / gd_scene_nb) % gd_S (drp_gd_begin_scenes)
@@ -110,7 +123,8 @@ int gd_forward_backward(drp_ctx* c, const GdPass& pass) {
             }
             { ProbeScope ps(c, KC_BWD_EDGE);
             hipLaunchKernelGGL(kb_gather_pos, dim3((N + 255) / 256, B), dim3(256), 0, st, ptr<float>(c->gpos_edge),
-                               s.rev_off, s.rev, N, g_prev, (size_t)N * 3, s.cnt);
+                               s.rev_off, s.rev, N, g_prev, (size_t)N * 3, s.cnt,
+                               seed_mid ? seed_mid + (size_t)(t - 1) * bn * 3 : (const float*)nullptr);
             }
         }
         { ProbeScope ps(c, KC_BWD_PUSH);
@@ -124,9 +138,12 @@ int gd_forward_backward(drp_ctx* c, const GdPass& pass) {
 }
 }  // namespace
 
-// S = 0: drp_gd_begin (the single goal).  S >= 1: drp_gd_begin_scenes -- nb is then S * (columns per scene)
-static int gd_begin_common(drp_ctx* c, int S, const float* s0, const float* attr, const float* dens, int nb, int N,
+// S = 0: drp_gd_begin (the single goal).  S >= 1: drp_gd_begin_scenes -- nb is then S * (columns per scene).  S = -1:
+// drp_gd_begin_cost -- a single-scene session that reads no goal
+static int gd_begin_common(drp_ctx* c, int S_or_cost, const float* s0, const float* attr, const float* dens, int nb, int N,
                            const float* actions, int B, int H, double lr, const float act_lo[4], const float act_hi[4]) {
+    const bool cost = S_or_cost < 0;
+    const int S = cost ? 0 : S_or_cost;
     CHK(check_bn(c, B, N));
     if (!s0 || !attr || !dens || !actions || !act_lo || !act_hi) return fail(c, DRP_EINVAL, "null argument");
     if (H < 1 || H > 64) return fail(c, DRP_EINVAL, "bad horizon H=%d", H);
@@ -158,6 +175,7 @@ static int gd_begin_common(drp_ctx* c, int S, const float* s0, const float* attr
     HIPCHK(c, hipMemsetAsync(c->adam_v.p, 0, (size_t)B * H * 4 * sizeof(float), c->stream));
     CHK(guarded_wait(c, nullptr));
     c->gd_S = S; c->gd_scene_nb = S > 0 ? nb / S : 0;
+    c->gd_cost = cost;
     c->gd_nb = nb; c->gd_N = N; c->gd_B = B; c->gd_H = H; c->gd_iter = 0; c->gd_lr = lr;
     for (int q = 0; q < DRP_GD_SLOTS; ++q) c->gd_pending[q] = false;           // a new problem drops what the last one left in flight
     c->gd_cself_tag = 0;
@@ -175,6 +193,12 @@ int drp_gd_begin(drp_ctx* c, const float* s0, const float* attr, const float* de
     return gd_begin_common(c, 0, s0, attr, dens, nb, N, actions, B, H, lr, act_lo, act_hi);
 }
 
+int drp_gd_begin_cost(drp_ctx* c, const float* s0, const float* attr, const float* dens, int nb, int N,
+                      const float* actions, int B, int H, double lr, const float act_lo[4], const float act_hi[4]) {
+    CHK(need(c, true, true, false));
+    return gd_begin_common(c, -1, s0, attr, dens, nb, N, actions, B, H, lr, act_lo, act_hi);
+}
+
 int drp_gd_begin_scenes(drp_ctx* c, int S, const float* s0, const float* attr, const float* dens, int nb, int N,
                         const float* actions, int B, int H, double lr, const float act_lo[4], const float act_hi[4]) {
     CHK(need(c, true, true, false));
@@ -185,22 +209,34 @@ int drp_gd_begin_scenes(drp_ctx* c, int S, const float* s0, const float* attr, c
     return gd_begin_common(c, S, s0, attr, dens, S * nb, N, actions, B, H, lr, act_lo, act_hi);
 }
 
+// what a session begun by drp_gd_begin_cost cannot do: everything that reads the built-in reward
+static int no_cost_session(drp_ctx* c, const char* what) {
+    if (c->gd_cost)
+        return fail(c, DRP_ESTATE, "%s: the session was begun by drp_gd_begin_cost and has no reward of its own "
+                                   "(drp_gd_predict, drp_gd_grad_seeded, drp_gd_step_seeded)", what);
+    return DRP_OK;
+}
+
+// device layout [H][B,N,3] -> caller layout [B,H,N,3]
+static int gd_copy_state_grad(drp_ctx* c, float* grad_state_out) {
+    const size_t bn = (size_t)c->gd_B * c->gd_N;
+    const size_t row = (size_t)c->gd_N * 3 * sizeof(float);
+    for (int t = 0; t < c->gd_H; ++t)
+        HIPCHK(c, hipMemcpy2DAsync(grad_state_out + (size_t)t * c->gd_N * 3, (size_t)c->gd_H * row,
+                                   ptr<float>(c->g_state) + (size_t)t * bn * 3, row, row, c->gd_B,
+                                   hipMemcpyDeviceToHost, c->stream));
+    return DRP_OK;
+}
+
 int drp_gd_grad(drp_ctx* c, float* rewards_out, float* grad_act_out, float* grad_state_out) {
     if (!c || !c->gd_on) return fail(c, DRP_ESTATE, "drp_gd_begin not called");
+    CHK(no_cost_session(c, "drp_gd_grad"));
     HIPCHK(c, hipSetDevice(c->device));
     DrainOnError drain(c);
     CHK(gd_forward_backward(c, GdPass{}));
-    const size_t bn = (size_t)c->gd_B * c->gd_N;
     if (rewards_out) CHK(d2h(c, rewards_out, c->rewards.p, (size_t)c->gd_B * sizeof(float)));
     if (grad_act_out) CHK(d2h(c, grad_act_out, c->g_act.p, (size_t)c->gd_B * c->gd_H * 4 * sizeof(float)));
-    if (grad_state_out) {
-        // device layout [H][B,N,3] -> caller layout [B,H,N,3]
-        const size_t row = (size_t)c->gd_N * 3 * sizeof(float);
-        for (int t = 0; t < c->gd_H; ++t)
-            HIPCHK(c, hipMemcpy2DAsync(grad_state_out + (size_t)t * c->gd_N * 3, (size_t)c->gd_H * row,
-                                       ptr<float>(c->g_state) + (size_t)t * bn * 3, row, row, c->gd_B,
-                                       hipMemcpyDeviceToHost, c->stream));
-    }
+    if (grad_state_out) CHK(gd_copy_state_grad(c, grad_state_out));
     CHK(drp_sync(c));
     return drain.ok();
 }
@@ -209,11 +245,12 @@ namespace {
 // one iteration on the stream: forward, backward, Adam, clip -- the optimiser step of a row in the kb_sdelta launch that
 // completes the row's gradient (rollout step 0's, the last of the backward pass): one launch fewer per iteration.
 // host_rewards / host_actions (pinned; null for none): where the iteration's kernels also store its rewards and updated pushes
-int gd_iteration(drp_ctx* c, float* host_rewards, float* host_actions) {
+int gd_iteration(drp_ctx* c, float* host_rewards, float* host_actions, bool seeded = false /* drp_gd_step_seeded */) {
     // torch.optim.Adam: step_size = lr / (1 - beta1^t), denom = sqrt(v) / sqrt(1 - beta2^t) + eps
     const double it = (double)(c->gd_iter + 1);
     const double bc1 = 1.0 - pow(0.9, it), bc2 = 1.0 - pow(0.999, it);
     GdPass pass{KbAdam{}, host_rewards};
+    pass.seeded = seeded;
     KbAdam& a = pass.adam;
     a.act = ptr<float>(c->actions); a.m = ptr<float>(c->adam_m); a.v = ptr<float>(c->adam_v); a.act_copy = host_actions;
     a.n_row = c->gd_H * 4;
@@ -229,6 +266,7 @@ int gd_iteration(drp_ctx* c, float* host_rewards, float* host_actions) {
 
 int drp_gd_step(drp_ctx* c, float* rewards_out) {
     if (!c || !c->gd_on) return fail(c, DRP_ESTATE, "drp_gd_begin not called");
+    CHK(no_cost_session(c, "drp_gd_step"));
     HIPCHK(c, hipSetDevice(c->device));
     DrainOnError drain(c);
     CHK(gd_iteration(c, nullptr, nullptr));
@@ -244,6 +282,7 @@ int drp_gd_step(drp_ctx* c, float* rewards_out) {
 // memory behind the kernels, the caller enqueues the NEXT iteration before it waits for this one.
 int drp_gd_step_async(drp_ctx* c, int slot) {
     if (!c || !c->gd_on) return fail(c, DRP_ESTATE, "drp_gd_begin not called");
+    CHK(no_cost_session(c, "drp_gd_step_async"));
     if (slot < 0 || slot >= DRP_GD_SLOTS) return fail(c, DRP_EINVAL, "slot must be 0 .. %d", DRP_GD_SLOTS - 1);
     if (c->gd_pending[slot]) return fail(c, DRP_ESTATE, "slot %d holds an iteration nobody has waited for", slot);
     HIPCHK(c, hipSetDevice(c->device));
@@ -266,6 +305,7 @@ int drp_gd_step_async(drp_ctx* c, int slot) {
 
 int drp_gd_wait(drp_ctx* c, int slot, float* rewards_out, float* actions_out) {
     if (!c) return DRP_EINVAL;
+    if (c->gd_on) CHK(no_cost_session(c, "drp_gd_wait"));
     if (slot < 0 || slot >= DRP_GD_SLOTS || !c->gd_pending[slot]) return fail(c, DRP_ESTATE, "no iteration in flight in slot %d", slot);
     HIPCHK(c, hipSetDevice(c->device));
     c->gd_pending[slot] = false;
@@ -274,6 +314,69 @@ int drp_gd_wait(drp_ctx* c, int slot, float* rewards_out, float* actions_out) {
     if (rewards_out) memcpy(rewards_out, c->gd_pin[slot].p, nr * sizeof(float));
     if (actions_out) memcpy(actions_out, ptr<float>(c->gd_pin[slot]) + nr, na * sizeof(float));
     return DRP_OK;
+}
+
+// ---- planning on a caller's cost: every step's predicted state out, the caller's d loss / d s_pred in (GdPass: seeded) ----------
+// Stateless between the calls, as the trainer's pair is: each seeded call runs the forward again (deterministic: the bits
+// drp_gd_predict returned), so nothing has to mark the tape valid across whatever else touches the workspace in between.
+namespace {
+// a single-scene GD session, of either kind
+int gd_seeded_session(drp_ctx* c, const char* what) {
+    if (!c) return DRP_EINVAL;
+    if (!c->gd_on) return fail(c, DRP_ESTATE, "%s: no GD session (drp_gd_begin, drp_gd_begin_cost)", what);
+    if (c->gd_S > 0) return fail(c, DRP_ESTATE, "%s: a session of %d scenes takes no seed (drp_gd_begin, drp_gd_begin_cost)", what, c->gd_S);
+    return DRP_OK;
+}
+// the seed's check and its one upload, the caller's layout (kb_seed_stage re-lays it on the device)
+int gd_stage_seed(drp_ctx* c, const float* seed) {
+    const int B = c->gd_B, H = c->gd_H, N = c->gd_N;
+    const long bad = first_bad_plan_seed(seed, B, H, N);
+    if (bad >= 0)
+        return fail(c, DRP_EINVAL, "the seed of row %ld, step %ld, particle %ld is infinite or not a number", bad / ((long)H * N),
+                    (bad / N) % H, bad % N);
+    return h2d(c, c->gd_seed_in, seed, (size_t)B * H * N * 3 * sizeof(float));
+}
+}  // namespace
+
+int drp_gd_predict(drp_ctx* c, float* states_out) {
+    CHK(gd_seeded_session(c, "drp_gd_predict"));
+    if (!states_out) return fail(c, DRP_EINVAL, "null buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    DrainOnError drain(c);
+    GdPass pass{};
+    pass.forward_only = true;
+    CHK(gd_forward_backward(c, pass));
+    // the rollout's own layout is the caller's: [B][H][N][3]
+    CHK(d2h(c, states_out, c->states.p, (size_t)c->gd_B * c->gd_H * c->gd_N * 3 * sizeof(float)));
+    CHK(drp_sync(c));
+    return drain.ok();
+}
+
+int drp_gd_grad_seeded(drp_ctx* c, const float* seed, float* grad_act_out, float* grad_state_out) {
+    CHK(gd_seeded_session(c, "drp_gd_grad_seeded"));
+    if (!seed) return fail(c, DRP_EINVAL, "null seed");
+    HIPCHK(c, hipSetDevice(c->device));
+    DrainOnError drain(c);
+    CHK(gd_stage_seed(c, seed));
+    GdPass pass{};
+    pass.seeded = true;
+    CHK(gd_forward_backward(c, pass));
+    if (grad_act_out) CHK(d2h(c, grad_act_out, c->g_act.p, (size_t)c->gd_B * c->gd_H * 4 * sizeof(float)));
+    if (grad_state_out) CHK(gd_copy_state_grad(c, grad_state_out));
+    CHK(drp_sync(c));
+    return drain.ok();
+}
+
+int drp_gd_step_seeded(drp_ctx* c, const float* seed, float* actions_out) {
+    CHK(gd_seeded_session(c, "drp_gd_step_seeded"));
+    if (!seed) return fail(c, DRP_EINVAL, "null seed");
+    HIPCHK(c, hipSetDevice(c->device));
+    DrainOnError drain(c);
+    CHK(gd_stage_seed(c, seed));
+    CHK(gd_iteration(c, nullptr, nullptr, true));
+    if (actions_out) CHK(d2h(c, actions_out, c->actions.p, (size_t)c->gd_B * c->gd_H * 4 * sizeof(float)));
+    CHK(drp_sync(c));
+    return drain.ok();
 }
 
 int drp_gd_get(drp_ctx* c, float* actions_out) {

@@ -216,19 +216,25 @@ struct Gd64Ws {
     F64Rev rev;
     double *px, *py, *gx, *gy, *r1t, *dist;
     int* arg;
-    size_t carve(void* base, size_t bc, size_t N, size_t H, size_t M) {         // -> its bytes
+    double* seed_mid;               // seeded: the caller's seeds of the steps before the last [H-1][pn,3] (kg_seed_in); else nothing
+    size_t carve(void* base, size_t bc, size_t N, size_t H, size_t M, bool seeded = false) {         // -> its bytes
         F64Carver a{static_cast<char*>(base)};
         const size_t pn = bc * N;
         tape.carve(a, pn, H);
         rev.carve(a, bc, N, H, pn * 4);
         a.take(px, pn); a.take(py, pn); a.take(gx, pn); a.take(gy, pn); a.take(r1t, pn); a.take(dist, bc * M); a.take(arg, bc * M);
+        a.take(seed_mid, seeded ? (H - 1) * pn * 3 : 0);
         return a.off;
     }
 };
+// what takes the reward's place (drp_gd_predict_f64, drp_gd_grad_f64_seeded): nothing -- the forward alone, every step's state to
+// grad_state_out -- or the caller's seed, the whole batch's on the device [B][H][N][3], sliced per chunk by kg_seed_in
+struct Gd64Given { bool predict = false; const double* seed = nullptr; };
 
 // forward with tape, reward, reverse pass of the rows [b0, b0 + bc): launches and the copies of its results
 int gd64_chunk(drp_ctx* c, const Gd64Ws& k, int b0, int bc, int nb, int N, int H, const float* s0, const float* attr_x,
-               const float* dens_x, const float* actions, double* rewards, double* g_act, double* grad_state_out) {
+               const float* dens_x, const float* actions, double* rewards, double* g_act, double* grad_state_out,
+               const Gd64Given& given = Gd64Given{}) {
     hipStream_t st = c->stream;
     const size_t pn = (size_t)bc * N;
     const float* attr = attr_x + (size_t)b0 * N;
@@ -240,10 +246,14 @@ int gd64_chunk(drp_ctx* c, const Gd64Ws& k, int b0, int bc, int nb, int N, int H
         hipLaunchKernelGGL(kg_sdelta, dim3(bc), dim3(256), 0, st, s.state, act + (size_t)t * 4, (size_t)H * 4, N, c->cam, s.sd,
                            ptr<float>(c->ws.s_in), ptr<float>(c->ws.s_delta));
     }));
-    // ---- reward of the final state and its gradient
-    hipLaunchKernelGGL(kg_reward, dim3(bc), dim3(256), 0, st, k.tape.state + (size_t)H * pn * 3, N, ptr<float>(c->goal_field), c->goal_h,
-                       c->goal_w, ptr<float>(c->goal_coor), c->goal_m, c->cam, k.px, k.py, k.gx, k.gy, k.r1t, k.dist, k.arg, rewards + b0,
-                       k.rev.g_state + (size_t)(H - 1) * pn * 3);
+    if (given.predict) return f64_copy_state_grad(c, k.tape.state + pn * 3, b0, bc, N, H, grad_state_out);
+    // ---- reward of the final state and its gradient, or the caller's seed in its place
+    if (given.seed)
+        hipLaunchKernelGGL(kg_seed_in, dim3(bc, H), dim3(256), 0, st, given.seed, b0, N, k.seed_mid, k.rev.g_state + (size_t)(H - 1) * pn * 3);
+    else
+        hipLaunchKernelGGL(kg_reward, dim3(bc), dim3(256), 0, st, k.tape.state + (size_t)H * pn * 3, N, ptr<float>(c->goal_field), c->goal_h,
+                           c->goal_w, ptr<float>(c->goal_coor), c->goal_m, c->cam, k.px, k.py, k.gx, k.gy, k.r1t, k.dist, k.arg, rewards + b0,
+                           k.rev.g_state + (size_t)(H - 1) * pn * 3);
     // ---- reverse pass, step by step; its tail: gen_s_delta backward and the step's share of d loss / d input state
     for (int t = H - 1; t >= 0; --t) {
         const F64Tape s = k.tape.step(t, pn);
@@ -251,7 +261,8 @@ int gd64_chunk(drp_ctx* c, const Gd64Ws& k, int b0, int bc, int nb, int N, int H
         f64_reverse_step(c, s, k.rev, g_out, t, bc, N, attr, dens, nullptr);
         hipLaunchKernelGGL(kg_sdelta_bwd, dim3(bc), dim3(256), 0, st, s.state, act + (size_t)t * 4, (size_t)H * 4, k.rev.g_sd, g_out,
                            k.rev.g_diff, s.cnt, k.rev.rev_off, k.rev.rev, N, c->cam, k.rev.part, g_act + (size_t)b0 * H * 4 + (size_t)t * 4,
-                           (size_t)H * 4, t > 0 ? k.rev.g_state + (size_t)(t - 1) * pn * 3 : (double*)nullptr);
+                           (size_t)H * 4, t > 0 ? k.rev.g_state + (size_t)(t - 1) * pn * 3 : (double*)nullptr,
+                           t > 0 && given.seed ? k.seed_mid + (size_t)(t - 1) * pn * 3 : (const double*)nullptr);
         HIPCHK(c, hipGetLastError());
     }
     if (grad_state_out) CHK(f64_copy_state_grad(c, k.rev.g_state, b0, bc, N, H, grad_state_out));
@@ -407,9 +418,12 @@ int tr64_chunk(drp_ctx* c, const Tr64Ws& k, const Tr64Io& io, const TrLoss& lk, 
 
 }  // namespace
 
-int drp_gd_grad_f64(drp_ctx* c, const float* s0, const float* attr, const float* dens, int nb, int N, const float* actions, int B,
-                    int H, double* rewards_out, double* grad_act_out, double* grad_state_out) {
-    CHK(need(c, true, true, true));
+// drp_gd_grad_f64, drp_gd_predict_f64 and drp_gd_grad_f64_seeded: one body.  `seed` (host, [B][H][N][3]) / `predict`: what
+// takes the reward's place (Gd64Given); neither reads the goal
+static int gd_grad_f64_body(drp_ctx* c, const float* s0, const float* attr, const float* dens, int nb, int N, const float* actions, int B,
+                            int H, const double* seed, bool predict, double* rewards_out, double* grad_act_out, double* grad_state_out) {
+    const bool goal = !seed && !predict;
+    CHK(need(c, true, true, goal));
     CHK(check_bn(c, B, N));
     if (!s0 || !attr || !dens || !actions) return fail(c, DRP_EINVAL, "null argument");
     if (H < 1 || H > 64) return fail(c, DRP_EINVAL, "bad horizon H=%d", H);
@@ -418,12 +432,12 @@ int drp_gd_grad_f64(drp_ctx* c, const float* s0, const float* attr, const float*
     F64Scope scope(c);
     if (!c->f64_w_valid) CHK(f64_refresh_weights(c));
     // rows per chunk: tape, reverse pass and reward scratch together
-    const size_t M = (size_t)c->goal_m;
+    const size_t M = goal ? (size_t)c->goal_m : 0;
     Gd64Ws k{};
-    auto bytes_of = [&](size_t bc) { return k.carve(nullptr, bc, (size_t)N, (size_t)H, M); };
+    auto bytes_of = [&](size_t bc) { return k.carve(nullptr, bc, (size_t)N, (size_t)H, M, seed != nullptr); };
     size_t Bc;
     CHK(f64_size_chunks(c, B, N, ((size_t)1 << 24) / (size_t)N, bytes_of, &Bc));
-    k.carve(c->grad64_ws.p, Bc, (size_t)N, (size_t)H, M);
+    k.carve(c->grad64_ws.p, Bc, (size_t)N, (size_t)H, M, seed != nullptr);
     // the whole batch's inputs (attributes and densities per row: row = traj * nb + batch) and results
     const size_t n_s0 = (size_t)nb * N * 3, n_attr = (size_t)B * N, n_act = (size_t)B * H * 4;
     std::vector<float> host(n_s0 + n_attr + (size_t)B + n_act);
@@ -434,15 +448,45 @@ int drp_gd_grad_f64(drp_ctx* c, const float* s0, const float* attr, const float*
     }
     memcpy(host.data() + n_s0 + n_attr + B, actions, n_act * sizeof(float));
     double* d_rew;
-    CHK(f64_upload_batch(c, host, (size_t)B + n_act, &d_rew));
+    const size_t n_seed = seed ? (size_t)B * H * N * 3 : 0;
+    CHK(f64_upload_batch(c, host, (size_t)B + n_act + n_seed, &d_rew));
     const float* d_in = ptr<float>(c->grad64_io);
     double* d_gact = d_rew + B;
+    Gd64Given given{};
+    given.predict = predict;
+    if (seed) {                             // the whole batch's seed behind the results, as it lies at the caller's
+        HIPCHK(c, hipMemcpyAsync(d_gact + n_act, seed, n_seed * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        given.seed = d_gact + n_act;
+    }
     for (int b0 = 0; b0 < B; b0 += (int)Bc)
         CHK(gd64_chunk(c, k, b0, std::min((int)Bc, B - b0), nb, N, H, d_in, d_in + n_s0, d_in + n_s0 + n_attr, d_in + n_s0 + n_attr + B,
-                       d_rew, d_gact, grad_state_out));
+                       d_rew, d_gact, grad_state_out, given));
     if (rewards_out) CHK(d2h(c, rewards_out, d_rew, (size_t)B * sizeof(double)));
     if (grad_act_out) CHK(d2h(c, grad_act_out, d_gact, n_act * sizeof(double)));
     return guarded_wait(c, nullptr);        // (the upload's host block lives until here)
+}
+
+int drp_gd_grad_f64(drp_ctx* c, const float* s0, const float* attr, const float* dens, int nb, int N, const float* actions, int B,
+                    int H, double* rewards_out, double* grad_act_out, double* grad_state_out) {
+    return gd_grad_f64_body(c, s0, attr, dens, nb, N, actions, B, H, nullptr, false, rewards_out, grad_act_out, grad_state_out);
+}
+
+int drp_gd_predict_f64(drp_ctx* c, const float* s0, const float* attr, const float* dens, int nb, int N, const float* actions, int B,
+                       int H, double* states_out) {
+    if (c && !states_out) return fail(c, DRP_EINVAL, "null buffer");
+    return gd_grad_f64_body(c, s0, attr, dens, nb, N, actions, B, H, nullptr, true, nullptr, nullptr, states_out);
+}
+
+int drp_gd_grad_f64_seeded(drp_ctx* c, const float* s0, const float* attr, const float* dens, int nb, int N, const float* actions,
+                           int B, int H, const double* seed, double* grad_act_out, double* grad_state_out) {
+    if (c && !seed) return fail(c, DRP_EINVAL, "null seed");
+    if (c && s0 && attr && dens && actions && B > 0 && N > 0 && N <= 4096 && H >= 1 && H <= 64) {
+        const long bad = first_bad_plan_seed(seed, B, H, N);
+        if (bad >= 0)
+            return fail(c, DRP_EINVAL, "the seed of row %ld, step %ld, particle %ld is infinite or not a number", bad / ((long)H * N),
+                        (bad / N) % H, bad % N);
+    }
+    return gd_grad_f64_body(c, s0, attr, dens, nb, N, actions, B, H, seed, false, nullptr, grad_act_out, grad_state_out);
 }
 
 namespace {

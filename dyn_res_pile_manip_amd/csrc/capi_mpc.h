@@ -46,6 +46,7 @@ static int mpc_begin_common(drp_ctx* c, const drp_mpc_params* p, int S, const fl
     c->mpc_pending[0] = c->mpc_pending[1] = false;         // a new problem drops what the last one left in flight
     c->mpc_on = true;
     c->gd_on = false;
+    c->mpc_cost = false; c->mpc_rewards_ok = true;         // (drp_mpc_begin_cost sets them behind this)
     c->mpc_cself_tag = 0;           // new attributes / densities / batch size
     return DRP_OK;
 }
@@ -55,6 +56,24 @@ int drp_mpc_begin(drp_ctx* c, const drp_mpc_params* p, const float* s0, const fl
     CHK(need(c, true, true, true));
     if (!p || !s0 || !attr || !dens || !nominal) return fail(c, DRP_EINVAL, "null argument");
     return mpc_begin_common(c, p, 0, s0, attr, dens, nominal, nullptr);
+}
+
+// drp_mpc_begin without the goal: the rollout runs no reward kernel, the caller computes the rewards from the states
+// (drp_mpc_get) and hands them in (drp_mpc_set_rewards) before anything reads them
+int drp_mpc_begin_cost(drp_ctx* c, const drp_mpc_params* p, const float* s0, const float* attr,
+                       const float* dens, const double* nominal) {
+    CHK(need(c, true, true, false));
+    if (!p || !s0 || !attr || !dens || !nominal) return fail(c, DRP_EINVAL, "null argument");
+    CHK(mpc_begin_common(c, p, 0, s0, attr, dens, nominal, nullptr));
+    c->mpc_cost = true; c->mpc_rewards_ok = false;
+    return DRP_OK;
+}
+
+// what reads the final-step rewards, in a cost session whose last rollout has none yet
+static int mpc_rewards_in(drp_ctx* c, const char* what) {
+    if (c->mpc_cost && !c->mpc_rewards_ok)
+        return fail(c, DRP_ESTATE, "%s: the session was begun by drp_mpc_begin_cost and the rollout's rewards are not in (drp_mpc_set_rewards)", what);
+    return DRP_OK;
 }
 
 int drp_mpc_begin_scenes(drp_ctx* c, const drp_mpc_params* p, int S, const float* s0, const float* attr,
@@ -109,8 +128,28 @@ int drp_mpc_rollout(drp_ctx* c, int reward_all_steps) {
     if (!c || !c->mpc_on) return fail(c, DRP_ESTATE, "drp_mpc_begin not called");
     HIPCHK(c, hipSetDevice(c->device));
     const drp_mpc_params& p = c->mpc;
+    if (c->mpc_cost) {
+        if (reward_all_steps != 0) return fail(c, DRP_EINVAL, "drp_mpc_rollout: a session begun by drp_mpc_begin_cost has no reward of its own (reward_all_steps must be 0)");
+        c->mpc_rewards_ok = false;
+        return run_rollout(c, p.n_batch, p.n_particles, mpc_rows(c), p.n_look_ahead, false, false, true, 0, p.n_batch);
+    }
     return run_rollout(c, p.n_batch * mpc_scenes(c), p.n_particles, mpc_rows(c), p.n_look_ahead,
                        reward_all_steps != 0, reward_all_steps == 0, true, c->mpc_S, p.n_batch);
+}
+
+// the caller's final-step rewards [rows] into the slot the update kernels read (rewards + (H-1), stride H); NaN is theirs to handle
+int drp_mpc_set_rewards(drp_ctx* c, const float* rewards) {
+    if (!c || !c->mpc_on) return fail(c, DRP_ESTATE, "drp_mpc_begin not called");
+    if (c->mpc_S > 0) return fail(c, DRP_ESTATE, "drp_mpc_set_rewards: a session of %d scenes takes no rewards", c->mpc_S);
+    if (!rewards) return fail(c, DRP_EINVAL, "null rewards");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int H = c->mpc.n_look_ahead, B = mpc_rows(c);
+    CHK(ensure(c, c->rewards, (size_t)B * H * sizeof(float)));
+    HIPCHK(c, hipMemcpy2DAsync(ptr<float>(c->rewards) + (H - 1), H * sizeof(float), rewards, sizeof(float), sizeof(float), B,
+                               hipMemcpyHostToDevice, c->stream));
+    CHK(guarded_wait(c, nullptr));          // (the caller's block is free when this returns)
+    c->mpc_rewards_ok = true;
+    return DRP_OK;
 }
 
 static int launch_partials(drp_ctx* c, double* out, int scene_stride = 0) {
@@ -126,6 +165,7 @@ static int launch_partials(drp_ctx* c, double* out, int scene_stride = 0) {
 
 int drp_mpc_partials(drp_ctx* c, double* out) {
     if (!c || !c->mpc_on) return fail(c, DRP_ESTATE, "drp_mpc_begin not called");
+    CHK(mpc_rewards_in(c, "drp_mpc_partials"));
     CHK(no_scene_sharding(c, "drp_mpc_partials"));
     HIPCHK(c, hipSetDevice(c->device));
     CHK(launch_partials(c, ptr<double>(c->partials)));
@@ -149,6 +189,7 @@ static int launch_update(drp_ctx* c, const double* dev_partials, int n_ranks, in
 
 int drp_mpc_update(drp_ctx* c, const double* partials, int n_ranks, double* nominal_out) {
     if (!c || !c->mpc_on) return fail(c, DRP_ESTATE, "drp_mpc_begin not called");
+    CHK(mpc_rewards_in(c, "drp_mpc_update"));
     CHK(no_scene_sharding(c, "drp_mpc_update"));
     HIPCHK(c, hipSetDevice(c->device));
     if (!partials || n_ranks <= 0) return fail(c, DRP_EINVAL, "bad partials");
@@ -164,6 +205,7 @@ int drp_mpc_update(drp_ctx* c, const double* partials, int n_ranks, double* nomi
 
 int drp_mpc_update_device(drp_ctx* c) {
     if (!c || !c->mpc_on) return fail(c, DRP_ESTATE, "drp_mpc_begin not called");
+    CHK(mpc_rewards_in(c, "drp_mpc_update_device"));
     HIPCHK(c, hipSetDevice(c->device));
     if (c->comm_failed) return comm_failed_error(c);
     if (c->comm && c->n_ranks > 1) CHK(no_scene_sharding(c, "drp_mpc_update_device with a communicator of several ranks"));
@@ -182,6 +224,7 @@ int drp_mpc_update_device(drp_ctx* c) {
 // ---- elite (CEM-style) update: nominal = mean of the k best sequences over all ranks
 static int elite_check(drp_ctx* c, int k) {
     if (!c || !c->mpc_on) return fail(c, DRP_ESTATE, "drp_mpc_begin not called");
+    CHK(mpc_rewards_in(c, "the elite update"));
     if (k < 1 || k > 1024) return fail(c, DRP_EINVAL, "elite size %d outside 1..1024", k);
     if ((size_t)c->mpc.n_sample * 16 + (size_t)k * 4 > 150 * 1024)
         return fail(c, DRP_EINVAL, "elite update supports up to 9 000 samples per rank");
@@ -314,6 +357,7 @@ int drp_mpc_fetch_async(drp_ctx* c, int slot) {
     if (!c || !c->mpc_on) return fail(c, DRP_ESTATE, "drp_mpc_begin not called");
     if (slot < 0 || slot > 1) return fail(c, DRP_EINVAL, "slot must be 0 or 1");
     if (c->mpc_pending[slot]) return fail(c, DRP_ESTATE, "slot %d holds an iteration nobody has waited for", slot);
+    CHK(mpc_rewards_in(c, "drp_mpc_fetch_async"));
     HIPCHK(c, hipSetDevice(c->device));
     const drp_mpc_params& p = c->mpc;
     const int H = p.n_look_ahead, B = mpc_rows(c);

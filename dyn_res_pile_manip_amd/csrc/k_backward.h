@@ -499,6 +499,26 @@ kb_gather_pos(const float* __restrict__ gpos_edge, const int* __restrict__ rev_o
     gp[0] = g0 - ax; gp[1] = g1 - ay; gp[2] = g2 - az;
 }
 
+// d loss / d s_pred as the CALLER gives it (drp_gd_grad_seeded, drp_gd_step_seeded), in kb_reward's slot of the stream: the staged
+// seed [B][H][N][3] (the caller's layout) to the backward pass's step-major layout, bit for bit, on grid B x H.  The last step's
+// slice goes where kb_reward writes its gradient (g_last [B,N,3]: g_state's slice H-1), the slices of the steps before it to
+// g_mid [H-1][B,N,3], from where kb_gather_pos adds them (its g_add).  Where N * 3 is a multiple of four every slice starts on
+// 16 bytes (the buffers do) and the copy is float4s.
+__global__ void __launch_bounds__(256)
+kb_seed_stage(const float* __restrict__ seed /* [B][H][N][3] */, int N, float* __restrict__ g_mid, float* __restrict__ g_last) {
+    const int b = blockIdx.x, t = blockIdx.y, B = gridDim.x, H = gridDim.y;
+    const int n3 = N * 3;
+    const float* s = seed + ((size_t)b * H + t) * n3;
+    float* g = (t == H - 1) ? g_last + (size_t)b * n3 : g_mid + ((size_t)t * B + b) * n3;
+    if ((n3 & 3) == 0) {
+        const float4* s4 = reinterpret_cast<const float4*>(s);
+        float4* g4 = reinterpret_cast<float4*>(g);
+        for (int i = threadIdx.x; i < n3 / 4; i += 256) g4[i] = s4[i];
+    } else {
+        for (int i = threadIdx.x; i < n3; i += 256) g[i] = s[i];
+    }
+}
+
 // the same step as a launch of its own (the trainer's weights; a planner row whose gradient needs no kb_sdelta launch)
 __global__ void k_adam(float* __restrict__ act, const float* __restrict__ grad, float* __restrict__ m,
                        float* __restrict__ v, int n, float step_size, float bc2_sqrt, float4 lo, float4 hi,

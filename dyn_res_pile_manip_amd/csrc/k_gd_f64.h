@@ -477,16 +477,32 @@ __device__ __forceinline__ double kg_state_share(double v, const double* __restr
     return v;
 }
 
+// ---- the caller's seed in kg_reward's place (drp_gd_grad_f64_seeded) ---------------------------------------------------------
+// the batch's seed [B][H][N][3] (doubles, the caller's layout) at the chunk's row offset b0, on grid (bc, H): step H-1's slice to
+// g_last [bc*N,3] (g_state's slice H-1, where kg_reward writes), the steps before it to g_mid [H-1][bc*N,3] (kg_sdelta_bwd's
+// g_add), bit for bit -- kb_seed_stage in double
+__global__ __launch_bounds__(256) void kg_seed_in(const double* __restrict__ seed_in, int b0, int N, double* __restrict__ g_mid,
+                                                  double* __restrict__ g_last) {
+    const int b = blockIdx.x, t = blockIdx.y, bc = gridDim.x, H = gridDim.y;
+    const int n3 = N * 3;
+    const double* s = seed_in + ((size_t)(b0 + b) * H + t) * n3;
+    double* g = (t == H - 1) ? g_last + (size_t)b * n3 : g_mid + ((size_t)t * bc + b) * n3;
+    for (int i = threadIdx.x; i < n3; i += 256) g[i] = s[i];
+}
+
 // ---- gen_s_delta backward and the step's d loss / d input state ---------------------------------------------------------
-// g_act[b, 0:4] = sum_n J_n^T g_sd[n] (particles ascending); g_prev[n] (nullable) = g_out[n] (the + s_cur of the output) + the
-// relation encoder's share (kg_state_share) + gen_s_delta's dependence on the position.  One workgroup per row; part
+// g_act[b, 0:4] = sum_n J_n^T g_sd[n] (particles ascending); g_prev[n] (nullable) = g_out[n] (the + s_cur of the output) [+ the
+// caller's seed of that step, g_add] + the relation encoder's share (kg_state_share) + gen_s_delta's dependence on the position.  One workgroup per row; part
 // [rows*N,4]: scratch.
 __global__ __launch_bounds__(256) void kg_sdelta_bwd(const double* __restrict__ s, const float* __restrict__ act, size_t act_stride,
                                                      const double* __restrict__ g_sd, const double* __restrict__ g_out,
                                                      const double* __restrict__ g_diff, const uint8_t* __restrict__ cnt,
                                                      const int* __restrict__ rev_off, const int* __restrict__ rev, int N, DrpCam cam,
                                                      double* __restrict__ part, double* __restrict__ g_act, size_t gact_stride,
-                                                     double* __restrict__ g_prev) {
+                                                     double* __restrict__ g_prev,
+                                                     const double* __restrict__ g_add = nullptr /* nullable, laid out as g_prev: the
+                                                        caller's seed of the step before (drp_gd_grad_f64_seeded), added to g_out
+                                                        first -- the point where kb_gather_pos adds it in fp32 */) {
     const int b = blockIdx.x;
     KgDual a[4];
 #pragma unroll
@@ -509,8 +525,10 @@ __global__ __launch_bounds__(256) void kg_sdelta_bwd(const double* __restrict__ 
         for (int k = 0; k < 4; ++k) part[i * 4 + k] = g7[k];
         if (g_prev != nullptr) {
 #pragma unroll
-            for (int k = 0; k < 3; ++k)
-                g_prev[i * 3 + k] = kg_state_share(g_out[i * 3 + k], g_diff, cnt, rev_off, rev, N, (size_t)b, n, k) + g7[4 + k];
+            for (int k = 0; k < 3; ++k) {
+                const double v = g_add != nullptr ? g_out[i * 3 + k] + g_add[i * 3 + k] : g_out[i * 3 + k];
+                g_prev[i * 3 + k] = kg_state_share(v, g_diff, cnt, rev_off, rev, N, (size_t)b, n, k) + g7[4 + k];
+            }
         }
     }
     __syncthreads();

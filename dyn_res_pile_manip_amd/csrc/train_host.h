@@ -319,6 +319,15 @@ inline long first_bad_seed(const T* seed, const int32_t* counts, int B, int H, i
                     if (!std::isfinite(seed[(((size_t)b * H + t) * N + i) * 3 + d])) return ((long)b * H + t) * N + i;
     return -1;
 }
+// the planner's seed [B][H][N][3] (drp_gd_grad_seeded's d loss / d s_pred; no padding: every row is a particle): the first
+// coordinate that is infinite or no number, as (b * H + t) * N + row, or -1 -- first_nonfinite_row over the B * H blocks
+template <typename T>
+inline long first_bad_plan_seed(const T* seed, int B, int H, int N) {
+    for (size_t r = 0; r < (size_t)B * H * N; ++r)
+        for (int d = 0; d < 3; ++d)
+            if (!std::isfinite(seed[r * 3 + d])) return (long)r;
+    return -1;
+}
 // the unbalanced divergence's reach and target mass of one problem (include/drp.h: drp_cloud_divergence_unbalanced): 0 where it
 // is served, else what is refused
 enum { REACH_OK = 0, REACH_RHO = 1, REACH_MASS = 2, REACH_INF_MASS = 3 };

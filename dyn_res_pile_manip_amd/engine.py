@@ -1710,6 +1710,131 @@ class Engine(object):
         self._ck(self.lib.drp_gd_get(self.h, _fp(a)))
         return a
 
+    # ---- planning on a caller's cost (include/drp.h: drp_gd_begin_cost, drp_gd_predict, drp_gd_*_seeded) --------------------
+    def gd_begin_cost(self, s0, attr, dens, actions, lr, act_lo, act_hi):
+        """gd_begin without a goal: a session on a cost of the caller's.  gd_predict, gd_grad_seeded, gd_step_seeded and
+        gd_actions run in it; gd_grad, gd_step and gd_step_async are refused."""
+        s0, attr, dens, actions = _f32(s0), _f32(attr), _f32(dens), _f32(actions)
+        nb, N, _ = s0.shape
+        B, H, _ = actions.shape
+        lo, hi = _f32(act_lo), _f32(act_hi)
+        self._ck(self.lib.drp_gd_begin_cost(self.h, _fp(s0), _fp(attr), _fp(dens), nb, N, _fp(actions), B, H,
+                                            float(lr), _fp(lo), _fp(hi)))
+        self._gd = (B, H, N)
+
+    def _gd_seed(self, seed):
+        B, H, N = self._gd
+        seed = _f32(seed)
+        if seed.shape != (B, H, N, 3):
+            raise ValueError('seed %s, the session wants %s' % (seed.shape, (B, H, N, 3)))
+        return seed
+
+    def gd_predict(self):
+        """Every step's predicted state [B,H,N,3] on the session's current pushes: the forward as gd_grad runs it, no reward;
+        the session is left as it was."""
+        B, H, N = self._gd
+        out = np.empty((B, H, N, 3), np.float32)
+        self._ck(self.lib.drp_gd_predict(self.h, _fp(out)))
+        return out
+
+    def gd_grad_seeded(self, seed, want_state_grad=False):
+        """The reverse pass from the caller's complete d loss / d s_pred [B,H,N,3] (the library minimises) -> (d loss / d pushes
+        [B,H,4], d loss / d state [B,H,N,3] with the seed included, or None)."""
+        B, H, N = self._gd
+        seed = self._gd_seed(seed)
+        g = np.empty((B, H, 4), np.float32)
+        gs = np.empty((B, H, N, 3), np.float32) if want_state_grad else None
+        self._ck(self.lib.drp_gd_grad_seeded(self.h, _fp(seed), _fp(g), _fp(gs) if want_state_grad else None))
+        return g, gs
+
+    def gd_step_seeded(self, seed):
+        """gd_grad_seeded plus gd_step's Adam step and clip -> the updated pushes [B,H,4]."""
+        B, H, N = self._gd
+        seed = self._gd_seed(seed)
+        a = np.empty((B, H, 4), np.float32)
+        self._ck(self.lib.drp_gd_step_seeded(self.h, _fp(seed), _fp(a)))
+        return a
+
+    def gd_predict_f64(self, s0, attr, dens, actions):
+        """The float64 forward of one GD iteration -> every step's predicted state [B,H,N,3] float64; gd_grad_f64's one-shot
+        contract, no goal needed."""
+        s0, attr, dens, actions = _f32(s0), _f32(attr), _f32(dens), _f32(actions)
+        nb, N, _ = s0.shape
+        B, H, _ = actions.shape
+        out = np.empty((B, H, N, 3), np.float64)
+        self._ck(self.lib.drp_gd_predict_f64(self.h, _fp(s0), _fp(attr), _fp(dens), int(nb), int(N), _fp(actions), int(B), int(H),
+                                             _dp(out)))
+        return out
+
+    def gd_grad_f64_seeded(self, s0, attr, dens, actions, seed, want_state_grad=False):
+        """The float64 reverse pass from the caller's seed [B,H,N,3] (float64) -> d loss / d pushes [B,H,4][, d loss / d state
+        [B,H,N,3]] as float64: the yardstick of gd_grad_seeded."""
+        s0, attr, dens, actions = _f32(s0), _f32(attr), _f32(dens), _f32(actions)
+        nb, N, _ = s0.shape
+        B, H, _ = actions.shape
+        seed = np.ascontiguousarray(seed, dtype=np.float64)
+        if seed.shape != (B, H, N, 3):
+            raise ValueError('seed %s, the inputs want %s' % (seed.shape, (B, H, N, 3)))
+        g = np.empty((B, H, 4), np.float64)
+        gs = np.empty((B, H, N, 3), np.float64) if want_state_grad else None
+        self._ck(self.lib.drp_gd_grad_f64_seeded(self.h, _fp(s0), _fp(attr), _fp(dens), int(nb), int(N), _fp(actions), int(B),
+                                                 int(H), _dp(seed), _dp(g), _dp(gs) if want_state_grad else None))
+        return (g, gs) if want_state_grad else g
+
+    def gradient_probe_cost(self, cost, s0, attr, dens, actions, act_lo, act_hi, context=None):
+        """gradient_probe for a cost of the caller's (costs.py: cost(pred, context, want_grad) -> (values [B], grad [B,H,N,3])):
+        gd_begin_cost + gd_predict + cost + gd_grad_seeded on whatever tape the selection gives, against gd_predict_f64 + the
+        cost on the float64 prediction + gd_grad_f64_seeded on the same inputs -> gradient_probe's dict ('reward_rel' compares
+        -values) plus 'seed_rel': max |seed(pred32) - seed(pred64)| / max |seed(pred64)|, how far the cost's own gradient moves
+        under the fp32 drift of the prediction.  It ENDS a running planner session and resets the dispatch marks."""
+        self.dispatch_reset()
+        self.gd_begin_cost(s0, attr, dens, actions, 0.05, act_lo, act_hi)
+        pred32 = self.gd_predict()
+        v32, seed32 = cost(pred32, context, True)
+        g32, _ = self.gd_grad_seeded(seed32)
+        tape = 'mfma' if 'k_aggregate_tape' in self.last_dispatch() else 'fused'
+        pred64 = self.gd_predict_f64(s0, attr, dens, actions)
+        v64, seed64 = cost(pred64, context, True)
+        seed64 = np.asarray(seed64, np.float64)
+        g64 = self.gd_grad_f64_seeded(s0, attr, dens, actions, seed64)
+        err = np.abs(g32.astype(np.float64) - g64).ravel()
+        err = np.where(np.isnan(err), np.inf, err)
+        scale = float(np.abs(g64).max())
+        a = float(err.max())
+        v64 = np.asarray(v64, np.float64)
+        rscale = float(np.abs(v64).max())
+        sscale = float(np.abs(seed64).max())
+        return {'abs': a, 'scale': scale, 'rel': a / max(scale, 1e-300), 'worst': int(np.argmax(err)),
+                'reward_rel': float(np.abs(np.asarray(v32, np.float64) - v64).max()) / max(rscale, 1e-300), 'tape': tape,
+                'seed_rel': float(np.abs(np.asarray(seed32, np.float64) - seed64).max()) / max(sscale, 1e-300)}
+
+    def mpc_begin_cost(self, s0, attr, dens, nominal, n_sample, sigma, beta_filter, reward_weight,
+                       act_lo, act_hi, seed=0, sample_offset=0, noise_type='normal'):
+        """mpc_begin without a goal: mpc_rollout then runs no reward kernel; read the states (mpc_get), compute a reward per
+        row and hand them in (mpc_set_rewards) before the update."""
+        s0, attr, dens = _f32(s0), _f32(attr), _f32(dens)
+        nominal = np.ascontiguousarray(nominal, dtype=np.float64)
+        nb, N, _ = s0.shape
+        H = nominal.shape[0]
+        p = L.MpcParams()
+        p.n_batch, p.n_particles, p.n_sample, p.n_look_ahead = nb, N, int(n_sample), H
+        p.sigma, p.beta_filter, p.reward_weight = float(sigma), float(beta_filter), float(reward_weight)
+        for i in range(4):
+            p.act_lo[i] = float(act_lo[i])
+            p.act_hi[i] = float(act_hi[i])
+        p.seed, p.sample_offset = int(seed), int(sample_offset)
+        p.noise_type, p.reserved = L.NOISE_TYPES[noise_type], 0
+        self._ranged(lambda: self.lib.drp_mpc_begin_cost(self.h, ctypes.byref(p), _fp(s0), _fp(attr), _fp(dens), _dp(nominal)))
+        self.H, self.nb, self.N, self.ns = H, nb, N, int(n_sample)
+        self.S = 0
+
+    def mpc_set_rewards(self, rewards):
+        """The final-step reward of every row [n_sample * nb] of the last rollout, in the slot the update kernels read."""
+        rewards = _f32(rewards)
+        if rewards.shape != (self.ns * self.nb,):
+            raise ValueError('rewards %s, the session has %d rows' % (rewards.shape, self.ns * self.nb))
+        self._ck(self.lib.drp_mpc_set_rewards(self.h, _fp(rewards)))
+
     # ---- multi-GPU ------------------------------------------------------------------
     def comm_unique_id(self):
         buf = ctypes.create_string_buffer(128)

@@ -536,6 +536,157 @@ class PlannerGD(Planner):
                           'best_rollout_time': (time.perf_counter() - t_best) * 1e3},
                 'iter_num': i}
 
+    def trajectory_optimization_ptcl_cost(self, state_cur_np, state_param, attr_cur_np, cost, model_dy, act_seq, act_label_seq,
+                                          n_sample, n_look_ahead, n_update_iter, action_lower_lim, action_upper_lim, context=None,
+                                          seed=None, noise_type='normal', rollout_best_action_sequence=True, comm=None):
+        """trajectory_optimization_ptcl_multi_traj on a cost of the caller's in the goal image's place (costs.py:
+        cost(pred [rows,H,N,3], context, want_grad) -> (values [rows], grad or None); the reward of a row is -values[row]).  No
+        goal is installed or read.  The same bookkeeping, voting rule and returned dict keys; `reward`, `reward_full`, `rew_mean`
+        and `rew_std` are in units of -cost, and `next_r` [H,1] holds the winner's reward at its last entry and NaN before it (a
+        cost has one value per horizon, not one per step).  The cost is called with `context` as given, on traj_num * n_batch
+        rows (GD), n_sample * n_batch rows (MPPI / CEM) and, for the winner's re-rollout, one row of column 0.
+
+        mpc_type 'GD': gd_iteration_count(n_update_iter, inf, N) iterations of gd_predict -> cost(want_grad=True) ->
+        gd_step_seeded.  MPPI / CEM: each iteration is mpc_sample -> mpc_rollout -> mpc_get(states) -> cost(want_grad=False) ->
+        mpc_set_rewards -> the update of the built-in loop.  The cost runs on the host between device calls, so nothing is
+        enqueued ahead.  Sharding (`comm`) and a multi-scene form are refused."""
+        from .costs import check_cost_output
+        if comm is not None:
+            raise ValueError('planning on a cost is not sharded over ranks: comm must be None')
+        if not callable(cost):
+            raise TypeError('cost must be callable: cost(pred, context, want_grad) -> (values, grad)')
+        assert type(state_cur_np) == np.ndarray and state_cur_np.ndim == 3, 'one scene: state_cur_np [n_batch,N,3]'
+        assert state_cur_np.shape[0] == state_param.shape[0] and state_cur_np.shape[2] == 3
+        assert type(act_seq) == np.ndarray and act_seq.ndim == 3
+        assert act_seq.shape[0] == act_label_seq.shape[0] and act_label_seq.ndim == 1
+        assert act_seq.shape[0] == n_look_ahead
+        mpc_type = self.config['mpc'].get('mpc_type', 'MPPI')
+        if mpc_type not in ('GD', 'MPPI', 'CEM'):
+            raise ValueError('unknown mpc_type %r' % (mpc_type,))
+        if noise_type not in ('normal', 'uniform', 'total_rand'):
+            raise ValueError('unknown noise type: %s' % noise_type)
+        start = time.time()
+        self.particle_num = N = state_cur_np.shape[1]
+        n_batch = state_cur_np.shape[0]
+        H = n_look_ahead
+        traj_num = int(act_seq.shape[1])
+        eng = self._bind(model_dy)
+        self._eng = eng
+        lo, hi = self._clip_box(0)
+        cfg = self.config['mpc']
+        sigma = 2.0 * self.global_scale / 12.0 if noise_type == 'uniform' else cfg['sigma'] * self.global_scale / 12.0
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 31 - 1))
+
+        max_reward = -np.inf * np.ones(n_batch, dtype=np.float32)
+        max_reward_traj_idx = np.zeros(n_batch, dtype=np.int64)
+        best_actions_of_samples = np.zeros((n_batch, H, self.action_dim), dtype=np.float32)
+        rew_mean = np.zeros((1, int(n_update_iter)), dtype=np.float32)
+        rew_std = np.zeros((1, int(n_update_iter)), dtype=np.float32)
+        rollout_time = 0.0
+        optim_time = 0.0
+        cost_time = 0.0
+
+        def evaluate(pred, want_grad):
+            """the cost on the host, its answer checked before anything reaches the device -> (rewards, grad)"""
+            nonlocal cost_time
+            t0 = time.perf_counter()
+            values, grad = cost(pred, context, want_grad)
+            values = check_cost_output(values, grad, pred.shape, want_grad)
+            cost_time += (time.perf_counter() - t0) * 1e3
+            return -np.asarray(values, np.float32), grad
+
+        def aggregate(it, rewards, actions, ns):
+            """planners.py:721-727,736-738, as the built-in loop's"""
+            r = rewards.reshape(ns, n_batch)
+            cur_max, idx = r.max(0), r.argmax(0)
+            acts = actions.reshape(ns, n_batch, H, self.action_dim)[idx, np.arange(n_batch)]
+            better = np.asarray(cur_max) > max_reward
+            max_reward[better] = np.asarray(cur_max)[better]
+            max_reward_traj_idx[better] = np.asarray(idx)[better]
+            best_actions_of_samples[better] = np.asarray(acts)[better]
+            if it < rew_mean.shape[1]:
+                rew_mean[0, it] = r[:, 0].mean()
+                rew_std[0, it] = r[:, 0].std(ddof=1) if ns > 1 else 0.0
+
+        i = 0
+        if mpc_type == 'GD':
+            assert n_sample == traj_num, 'GD optimises the traj_num given trajectories (n_sample == traj_num)'
+            n_iter = gd_iteration_count(n_update_iter, float('inf'), N)
+            if n_iter < 1:
+                raise ValueError('n_update_iter %r admits no iteration' % (n_update_iter,))
+            cand = np.repeat(act_seq.transpose(1, 0, 2), n_batch, axis=0).astype(np.float32)      # [traj*nb,H,4]
+            eng.gd_begin_cost(state_cur_np, attr_cur_np, state_param, cand, cfg['gd']['lr'], lo, hi)
+            act_seqs_last = cand
+            t0 = time.perf_counter()
+            for i in range(n_iter):
+                before = act_seqs_last
+                reward_seqs, grad = evaluate(eng.gd_predict(), True)
+                act_seqs_last = eng.gd_step_seeded(grad)
+                aggregate(i, reward_seqs, before, traj_num)         # the rewards belong to the pushes before the update
+            optim_time += (time.perf_counter() - t0) * 1e3
+            nominal = None
+        else:
+            n_iter = int(n_update_iter)
+            mp = dict(sigma=sigma, beta_filter=cfg['mppi']['beta_filter'], reward_weight=cfg['mppi']['reward_weight'],
+                      act_lo=lo, act_hi=hi, seed=seed, noise_type=noise_type)
+            cand = np.repeat(act_seq.transpose(1, 0, 2), n_batch, axis=0).astype(np.float32)      # [traj*nb,H,4]
+            eng.mpc_begin_cost(state_cur_np, attr_cur_np, state_param, act_seq[:, 0, :], n_sample=traj_num, **mp)
+            eng.mpc_set_actions(cand)
+            t0 = time.perf_counter()
+            eng.mpc_rollout(False)
+            reward_seqs, _ = evaluate(eng.mpc_get(states=True)['states'], False)
+            rollout_time += (time.perf_counter() - t0) * 1e3
+            aggregate(0, reward_seqs, cand, traj_num)
+            act_seqs_last = cand
+            r0 = reward_seqs.reshape(traj_num, n_batch)
+            nominal = act_seq[:, int(np.argmax(r0.mean(1))), :].astype(np.float64)
+            if n_iter > 1:
+                eng.mpc_begin_cost(state_cur_np, attr_cur_np, state_param, nominal, n_sample=int(n_sample), **mp)
+            k_elite = int(cfg.get('cem', {}).get('n_elite', max(1, n_sample // 10)))
+            t0 = time.perf_counter()
+            for i in range(1, n_iter):
+                eng.mpc_sample(i)
+                eng.mpc_rollout(False)
+                got = eng.mpc_get(actions=True, states=True)
+                reward_seqs, _ = evaluate(got['states'], False)
+                eng.mpc_set_rewards(reward_seqs)
+                if mpc_type == 'CEM':
+                    eng.mpc_update_elite_device(k_elite)
+                else:
+                    eng.mpc_update_device()
+                act_seqs_last = got['actions']
+                aggregate(i, reward_seqs, act_seqs_last, int(n_sample))
+            optim_time += (time.perf_counter() - t0) * 1e3
+            if n_iter > 1:
+                nominal = eng.mpc_get(nominal=True)['nominal']
+
+        best_seq = _vote(max_reward_traj_idx, max_reward, best_actions_of_samples)       # [1,H,4]
+        obs_seq_best, reward_best, next_r = None, None, None
+        t_best = time.perf_counter()
+        if rollout_best_action_sequence:
+            states, _ = eng.rollout(state_cur_np[0:1], attr_cur_np[0:1], state_param[0:1], best_seq,
+                                    want_states=True, want_reward=False)
+            obs_seq_best = states[0]
+            reward_best, _ = evaluate(states, False)                    # [1]
+            next_r = np.full((H, 1), np.nan, np.float32)
+            next_r[-1, 0] = reward_best[0]
+        ns_last = reward_seqs.shape[0] // n_batch
+        return {'action_sequence': best_seq[0],
+                'action_full': act_seqs_last[:, 0, :],
+                'reward_full': reward_seqs.reshape(ns_last, n_batch)[:, 0],
+                'observation_sequence': obs_seq_best,
+                'observation_distractor_sequence': None,
+                'reward': reward_best,
+                'next_r': next_r,
+                'rew_mean': rew_mean,
+                'rew_std': rew_std,
+                'nominal_sequence': nominal,
+                'times': {'total_time': time.time() - start, 'rollout_time': rollout_time,
+                          'optim_time': optim_time, 'cost_time': cost_time, 'goal_time': 0.0, 'goal_cached': False,
+                          'best_rollout_time': (time.perf_counter() - t_best) * 1e3},
+                'iter_num': i}
+
     def trajectory_optimization_ptcl_multi_scene(self, state_cur_np, state_param, attr_cur_np, obs_goals, model_dy, act_seq,
                                                  act_label_seq, n_sample, n_look_ahead, n_update_iter, action_lower_lim,
                                                  action_upper_lim, use_gpu=True, rollout_best_action_sequence=True,

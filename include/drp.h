@@ -205,6 +205,16 @@ typedef struct drp_mpc_params {
 
 int drp_mpc_begin(drp_ctx* ctx, const drp_mpc_params* p, const float* s0, const float* attr,
                   const float* dens, const double* nominal /* [H,4] */);
+/* drp_mpc_begin without the goal (weights and a camera only): a session on a cost of the caller's.  drp_mpc_rollout(ctx, 0) then
+ * runs the rollout and no reward kernel (a non-zero reward_all_steps: DRP_EINVAL); the caller reads the states (drp_mpc_get),
+ * computes a reward per row and hands them in: drp_mpc_set_rewards(rewards [rows]) writes the final-step slot the update kernels
+ * read.  After a rollout and before drp_mpc_set_rewards, drp_mpc_partials, drp_mpc_update*, drp_mpc_elite and
+ * drp_mpc_fetch_async return DRP_ESTATE in such a session (drp_mpc_get's rewards are then undefined).  drp_mpc_set_rewards is
+ * accepted in a session begun by drp_mpc_begin too, where it replaces the rewards; NaN rewards are the update kernels' to handle
+ * as they handle their own; a null pointer gives DRP_EINVAL, a multi-scene session DRP_ESTATE.  Cost sessions are single-scene. */
+int drp_mpc_begin_cost(drp_ctx* ctx, const drp_mpc_params* p, const float* s0, const float* attr,
+                       const float* dens, const double* nominal /* [H,4] */);
+int drp_mpc_set_rewards(drp_ctx* ctx, const float* rewards /* [rows] */);
 /* A session over S scenes (1 <= S <= DRP_MAX_SCENES, the S of the installed goal table): S piles, S goals, S nominal
  * sequences, planned in one rollout batch.  p is shared by all scenes (shapes, sigma, beta_filter, reward_weight, clip box,
  * noise type, sample_offset); p->n_sample is PER SCENE; p->seed is ignored for seeds [S].  s0 [S * nb][N][3], attr
@@ -428,6 +438,36 @@ int drp_gd_wait(drp_ctx* ctx, int slot, float* rewards_out, float* actions_out);
  * of scope, as for the sampling sessions. */
 int drp_gd_begin_scenes(drp_ctx* ctx, int S, const float* s0, const float* attr, const float* dens, int nb, int N,
                         const float* actions, int B, int H, double lr, const float act_lo[4], const float act_hi[4]);
+
+/* ---- planning on a caller's cost: predicted states out, state-gradient seed in ----------------------------------------------
+ * The planner's counterpart of drp_train_predict / drp_train_step_seeded: the loss is the caller's, everything behind its state
+ * gradient is the session's own code (forward with tape, reverse mode through every step, Adam, clip).
+ * drp_gd_begin_cost: drp_gd_begin without the goal -- weights and a camera only; the same engine pick, buffers and Adam reset.
+ * In such a session drp_gd_grad, drp_gd_step, drp_gd_step_async and drp_gd_wait return DRP_ESTATE (the message names the
+ * seeded calls); drp_gd_get works.  The three calls below also work in a session begun by drp_gd_begin (the goal is not read);
+ * after drp_gd_begin_scenes they return DRP_ESTATE.
+ * drp_gd_predict: the forward with tape on the session's current pushes EXACTLY as drp_gd_grad runs it (the same tape engine, the
+ * same self-edge constants), no reward: states_out [B][H][N][3], every step's predicted state.  No push, Adam moment or
+ * iteration count changes.
+ * drp_gd_grad_seeded: the forward again (deterministic: the bits drp_gd_predict returned), then the reverse pass with seed
+ * [B][H][N][3], seed[b, t, n, :] = d loss / d s_pred_t[b, n], COMPLETE: nothing is scaled, the sign is the caller's, the library
+ * minimises.  Step H-1's seed is d loss / d state_{H-1} as the built-in reward's gradient is; the seed of a step t < H-1 joins
+ * d loss / d state_t at ONE point of its sum, in fp32 and in float64 alike: residual share of step t+1's gradient, THEN THE SEED,
+ * then the relation encoder's share (own slots, then the reversed lists), then gen_s_delta's position share.  grad_act_out
+ * [B][H][4], grad_state_out [B][H][N][3] = the total d loss / d state_t, seed included (each nullable).  With seed = 0 but
+ * seed[:, H-1] = drp_gd_grad's grad_state[:, H-1], both outputs equal drp_gd_grad's as numbers (x + 0.0 may turn -0.0 into +0.0).
+ * drp_gd_step_seeded: the same plus the Adam step and the clip of drp_gd_step -- the update rides on the last kb_sdelta launch,
+ * the same arithmetic --, the iteration count advances, one wait; actions_out [B][H][4] (nullable): the updated pushes.
+ * The seed goes up in one copy and is re-laid step-major on the device.  DRP_ESTATE outside a GD session or in a multi-scene one;
+ * DRP_EINVAL for a null seed / states_out, or a seed value that is infinite or not a number (the message names row, step and
+ * particle).  A refused call leaves pushes, moments and iteration count as they were.  Stateless on purpose: drp_gd_predict's
+ * tape is not kept for the following step (that would need a validity mark over every call that touches the workspace); the
+ * price is one forward per iteration. */
+int drp_gd_begin_cost(drp_ctx* ctx, const float* s0, const float* attr, const float* dens, int nb, int N,
+                      const float* actions, int B, int H, double lr, const float act_lo[4], const float act_hi[4]);
+int drp_gd_predict(drp_ctx* ctx, float* states_out /*[B][H][N][3]*/);
+int drp_gd_grad_seeded(drp_ctx* ctx, const float* seed /*[B][H][N][3]*/, float* grad_act_out, float* grad_state_out);
+int drp_gd_step_seeded(drp_ctx* ctx, const float* seed /*[B][H][N][3]*/, float* actions_out /*[B][H][4], nullable*/);
 
 /* ---- multi-GPU (RCCL over xGMI) ------------------------------------------------------
  * The library does not link librccl: the first of these calls binds, at run time, $DRP_RCCL_LIB, else the librccl that
@@ -684,6 +724,15 @@ int drp_accuracy_probe(drp_ctx* ctx, int engine, const float* a_cur, const float
  * not a multiple of nb, N beyond drp_forward's limit.  A zero-length push gives NaN, as the reference. */
 int drp_gd_grad_f64(drp_ctx* ctx, const float* s0, const float* attr, const float* dens, int nb, int N, const float* actions,
                     int B, int H, double* rewards_out, double* grad_act_out, double* grad_state_out);
+/* The float64 yardstick of drp_gd_predict / drp_gd_grad_seeded: the same tape and reverse pass with the caller's seed [B][H][N][3]
+ * (doubles) in the reward's place, joined at the point drp_gd_grad_seeded documents.  One-shots with drp_gd_grad_f64's contract
+ * (no session begun or ended, buffers of their own, chunked under drp_debug_set_f64_cap with the seed sliced per chunk, the same
+ * bits run to run and under any cap), but they need no goal.  states_out [B][H][N][3]; grad_act_out, grad_state_out as
+ * drp_gd_grad_f64's, nullable.  DRP_EINVAL for a null seed / states_out or a seed value that is infinite or not a number. */
+int drp_gd_predict_f64(drp_ctx* ctx, const float* s0, const float* attr, const float* dens, int nb, int N, const float* actions,
+                       int B, int H, double* states_out);
+int drp_gd_grad_f64_seeded(drp_ctx* ctx, const float* s0, const float* attr, const float* dens, int nb, int N, const float* actions,
+                           int B, int H, const double* seed, double* grad_act_out, double* grad_state_out);
 
 /* ---- the float64 yardstick of the trainer's gradients (row y3): what drp_train_step(mode = DRP_TRAIN_GRAD) computes
  * (train/train_gnn_dyn.py:167-203; layouts as there: states [B, n_rollout+1, N, 3], states_delta [B, n_rollout, N, 3], attrs

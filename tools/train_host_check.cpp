@@ -20,7 +20,7 @@
 // independent restatement), transport_layout, divergence_layout (balanced and with `reach`, 4- and 8-byte elements),
 // drp_cloud_match_f64's buffer of its own (match64_layout, with and without match_in).  The checks: a real row that is no number
 // (first_nonfinite_row), the regularisation strengths (first_bad_eps), a matching given by the caller (check_matching), a reach and
-// a target mass (check_reach), a seed's real rows (first_bad_seed), a push of no length (first_bad_push).  No device is touched.
+// a target mass (check_reach), a seed's real rows (first_bad_seed), the planner's seed (first_bad_plan_seed), a push of no length (first_bad_push).  No device is touched.
 //
 //   train_host_check layout B H N M actions eps reach seed [f64 match_in]
 //       prints the offsets of states, impulses, attributes, densities, counts, targets, their counts, then `bytes`, then the offsets
@@ -519,6 +519,31 @@ int main(int argc, char** argv) {
         y[(1 * N + 2) * 3 + 2] = inf64;
         EXPECT(first_nonfinite_row(y, counts, B, N) == 1 * N + 2);
         std::free(y);
+    }
+    {
+        // the planner's seed [B][H][N][3] (drp_gd_grad_seeded, drp_gd_grad_f64_seeded): no padding, every coordinate read once and
+        // none beyond the block; the index names row, step and particle as the entry points' message splits it
+        const int B = 3, H = 2, N = 5;
+        const size_t n = (size_t)B * H * N * 3;
+        float* s = static_cast<float*>(std::malloc(n * sizeof(float)));                     // exactly [B][H][N][3]
+        for (size_t e = 0; e < n; ++e) s[e] = 0.5f - 0.125f * (float)e;
+        EXPECT(first_bad_plan_seed(s, B, H, N) == -1);
+        s[n - 1] = std::numeric_limits<float>::infinity();                                  // the last coordinate of the block
+        EXPECT(first_bad_plan_seed(s, B, H, N) == (long)(B * H * N - 1));
+        const long at = ((long)1 * H + 1) * N + 3;                                          // row 1, step 1, particle 3
+        s[at * 3 + 1] = std::numeric_limits<float>::quiet_NaN();
+        const long bad = first_bad_plan_seed(s, B, H, N);
+        EXPECT(bad == at && bad / ((long)H * N) == 1 && (bad / N) % H == 1 && bad % N == 3);
+        s[0] = -std::numeric_limits<float>::infinity();
+        EXPECT(first_bad_plan_seed(s, B, H, N) == 0);
+        std::free(s);
+        double* d = static_cast<double*>(std::malloc(n * sizeof(double)));
+        for (size_t e = 0; e < n; ++e) d[e] = 1e-300 * (double)(e + 1);                     // tiny is finite
+        EXPECT(first_bad_plan_seed(d, B, H, N) == -1);
+        d[(size_t)at * 3] = std::numeric_limits<double>::quiet_NaN();
+        EXPECT(first_bad_plan_seed(d, B, H, N) == at);
+        EXPECT(first_bad_plan_seed(d, 1, 1, 1) == -1);                                      // a smaller view reads no further
+        std::free(d);
     }
 
     // the push check, with the demo camera's map (x, z, -y + 18 scaled by 1 / 24: a camera that looks straight down)
