@@ -113,9 +113,12 @@ __device__ __forceinline__ void kb_reward_row(const float* __restrict__ s, int N
         }
         const float dist = drp_sqrt_rn(best);
         r2 += dist;
-        // d |q - p| / d p = -(q - p) / dist
-        atomicAdd(reinterpret_cast<unsigned long long*>(&gx[arg]), (unsigned long long)__float2ll_rn(-scale * (qx - px[arg]) / dist * FIX));
-        atomicAdd(reinterpret_cast<unsigned long long*>(&gy[arg]), (unsigned long long)__float2ll_rn(-scale * (qy - py[arg]) / dist * FIX));
+        // d |q - p| / d p = -(q - p) / dist; a goal pixel that IS the particle's pixel contributes nothing (torch.norm's
+        // backward gives 0 at 0, not 0 / 0 -- and a NaN has no defined conversion to the fixed point)
+        if (dist > 0.0f) {
+            atomicAdd(reinterpret_cast<unsigned long long*>(&gx[arg]), (unsigned long long)__float2ll_rn(-scale * (qx - px[arg]) / dist * FIX));
+            atomicAdd(reinterpret_cast<unsigned long long*>(&gy[arg]), (unsigned long long)__float2ll_rn(-scale * (qy - py[arg]) / dist * FIX));
+        }
     }
     __syncthreads();
     for (int n = threadIdx.x; n < N; n += blockDim.x) {

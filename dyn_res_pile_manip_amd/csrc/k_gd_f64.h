@@ -205,7 +205,7 @@ __global__ __launch_bounds__(256) void kg_reward(const double* __restrict__ stat
     for (int n = threadIdx.x; n < N; n += blockDim.x) {
         double ax = gx[n], ay = gy[n];
         for (int m = 0; m < M; ++m) {                        // d |q - p| / d p = -(q - p) / dist, goal points ascending
-            if (arg[m] != n) continue;
+            if (arg[m] != n || !(dist[m] > 0.0)) continue;   // at distance 0: nothing, as torch.norm's backward (not 0 / 0)
             ax += -scale * ((double)goal[m * 2] - px[n]) / dist[m];
             ay += -scale * ((double)goal[m * 2 + 1] - py[n]) / dist[m];
         }

@@ -414,7 +414,11 @@ int drp_obs2ptcl(drp_ctx* ctx, const float* depth_raw, int h, int w, float globa
 int drp_gd_begin(drp_ctx* ctx, const float* s0, const float* attr, const float* dens, int nb, int N,
                  const float* actions, int B, int H, double lr, const float act_lo[4], const float act_hi[4]);
 /* forward + backward only: rewards [B], d loss / d actions [B,H,4], d loss / d state_pred
- * [B,H,N,3] (each nullable) */
+ * [B,H,N,3] (each nullable).  The reward's gradient follows the reference's own operations where they are not smooth
+ * (drp_gd_grad_f64 too): grid_sample's border clamp passes no gradient where ix <= 0 or ix >= W - 1, the border itself
+ * included; a goal pixel equidistant from several particles belongs to the one of the lowest index; and a goal pixel that IS
+ * its nearest particle's pixel (distance 0) contributes nothing to the gradient -- torch.norm's backward at 0, never 0 / 0.
+ * The rewards are drp_reward's bits. */
 int drp_gd_grad(drp_ctx* ctx, float* rewards_out, float* grad_act_out, float* grad_state_out);
 /* one full iteration (forward, backward, Adam, clip); rewards of the iterate BEFORE the update */
 int drp_gd_step(drp_ctx* ctx, float* rewards_out);
