@@ -51,6 +51,14 @@ class MpcParams(ctypes.Structure):
                 ('noise_type', ctypes.c_int), ('reserved', ctypes.c_int)]
 
 
+class CloudGoalParams(ctypes.Structure):
+    """struct drp_cloud_goal_params (include/drp.h)."""
+    _fields_ = [('kind', ctypes.c_int), ('iters', ctypes.c_int), ('weight', ctypes.c_double), ('eps_scale', ctypes.c_double)]
+
+
+CLOUD_GOAL_KINDS = {'chamfer': 0, 'sinkhorn': 1}    # DRP_CLOUD_CHAMFER, DRP_CLOUD_SINKHORN
+CLOUD_GOAL_MAX_POINTS = {'chamfer': 4096, 'sinkhorn': 1024}     # KC_MAX_POINTS, KT_MAX_POINTS: either cloud of a cloud goal
+
 # name -> (restype, argtypes); exactly the symbols include/drp.h declares
 SIGNATURES = {
     'drp_create': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
@@ -156,6 +164,13 @@ SIGNATURES = {
     'drp_mpc_begin_cost': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(MpcParams), c_float_p, c_float_p, c_float_p,
                                           c_double_p]),
     'drp_mpc_set_rewards': (ctypes.c_int, [ctypes.c_void_p, c_float_p]),
+    'drp_set_goal_cloud': (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int, ctypes.POINTER(CloudGoalParams)]),
+    'drp_mpc_begin_cloud': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(MpcParams), c_float_p, c_float_p, c_float_p,
+                                           c_double_p]),
+    'drp_gd_begin_cloud': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.c_int, ctypes.c_int,
+                                          c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_float_p, c_float_p]),
+    'drp_cloud_goal_eval': (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_int32_p, c_float_p, ctypes.c_int, ctypes.c_int,
+                                           c_float_p, c_double_p, c_float_p]),
     'drp_comm_unique_id': (ctypes.c_int, [ctypes.c_char_p]),
     'drp_comm_init': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int]),
     'drp_comm_destroy': (ctypes.c_int, [ctypes.c_void_p]),

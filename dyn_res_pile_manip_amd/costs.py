@@ -12,6 +12,7 @@ planners) grad is None and need not be computed.  context is whatever the caller
   quadratic_cost(targets, step_weights)       a tracked target per step, seeds on every step
   keep_out_cost(center, radius, weight)       a smooth penalty, on every step, for particles inside a disc of the world plane
   cloud_divergence_cost(engine, target, ...)  Sinkhorn divergence of the final state to a target cloud: a density-aware goal
+  cloud_chamfer_cost(engine, target, ...)     symmetric Chamfer distance of the final state to a target cloud
   sum_costs(*costs)                           the sum of costs
   torch_cost(fn)                              a cost written in torch -- fn(pred_tensor, context) -> [B] tensor -- through autograd
 
@@ -106,6 +107,35 @@ def cloud_divergence_cost(engine, target, n_target=None, eps_scale=1.0, iters=50
             return values, None
         grad = np.zeros_like(pred)
         grad[:, H - 1] = out['grad']
+        return values, grad
+    return cost
+
+
+def cloud_chamfer_cost(engine, target, n_target=None, weight=1.0):
+    """values[b] = weight * Engine.cloud_chamfer(pred[b, H-1], target)['fwd' + 'bwd']: the symmetric squared Chamfer distance of
+    the FINAL predicted state to a target cloud [M, 3] (or [B, M, 3]; n_target: how many of its rows are points) -- the host
+    twin of the device-resident cloud goal (Engine.set_goal_cloud(kind='chamfer'), the counterpart of cloud_divergence_cost):
+    on a float32 pred its values are that goal's numbers (the product with the weight formed in float64 and rounded once).  Its
+    gradient is weight x the one-shot's fp32 gradient, formed in float64 and rounded again: the goal's kernel rounds weight x the
+    double expression ONCE, so the two are the same numbers for a weight that is a power of two and may differ in the last place
+    otherwise.  A float64 pred goes through cloud_chamfer_f64 (float64 gradient).  The gradient is non-zero on the final
+    step only."""
+    target = np.asarray(target, np.float32)
+    w = np.float64(weight)
+
+    def cost(pred, context=None, want_grad=True):
+        pred = _pred(pred)
+        B, H, N, _ = pred.shape
+        q = np.broadcast_to(target if target.ndim == 3 else target[None], (B,) + target.shape[-2:])
+        q = np.ascontiguousarray(q)
+        n_q = None if n_target is None else np.broadcast_to(np.asarray(n_target, np.int32), (B,)).copy()
+        call = engine.cloud_chamfer_f64 if pred.dtype == np.float64 else engine.cloud_chamfer
+        out = call(np.ascontiguousarray(pred[:, H - 1], np.float32), q, None, n_q, want_grad=want_grad)
+        values = (w * (np.asarray(out['fwd'], np.float64) + np.asarray(out['bwd'], np.float64))).astype(pred.dtype)
+        if not want_grad:
+            return values, None
+        grad = np.zeros_like(pred)
+        grad[:, H - 1] = (w * np.asarray(out['grad'], np.float64)).astype(pred.dtype)
         return values, grad
     return cost
 

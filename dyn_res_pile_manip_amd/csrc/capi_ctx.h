@@ -269,6 +269,16 @@ struct drp_ctx {
     DevBuf gd_seed_in, gd_seed;     // the caller's seed as it arrives [B][H][N][3], and steps 0 .. H-2 of it step-major [H-1][B,N,3]
     bool mpc_cost = false;          // the sampling session was begun without a goal: its rollout runs no reward kernel
     bool mpc_rewards_ok = true;     // a cost session: the final-step rewards of the last rollout are in (drp_mpc_set_rewards)
+    // planning to a target cloud (capi_cloud_goal.h: drp_set_goal_cloud, drp_mpc_begin_cloud, drp_gd_begin_cloud): one cloud beside
+    // the image goal and the goal table (cg_q), its kind and parameters; cg_tab: the running cloud session's tables per start
+    // column, eps [n_batch] then the target's self problem's value sums [n_batch]; cg_scratch: kg_sinkhorn's [2][rows] value sums and, in a GD
+    // session, [2][rows][N][3] gradient sums; cg_io: the one-shot's inputs, tables, scratch and results (it shares nothing with a session)
+    bool have_cloud_goal = false;
+    int cg_kind = 0, cg_M = 0, cg_iters = 0;
+    double cg_weight = 1.0, cg_eps_scale = 1.0;
+    DevBuf cg_q, cg_tab, cg_scratch, cg_io;
+    bool mpc_cloud = false;         // the sampling session was begun by drp_mpc_begin_cloud: its rollout ends in the cloud reward kernel
+    bool gd_cloud = false;          // the GD session was begun by drp_gd_begin_cloud: the cloud kernel stands in kb_reward's place
 
     // particle extraction (row f2)
     DevBuf px_depth, px_mask, px_blk, px_bmin, px_bmax, px_grid, px_pcd, px_keys, px_cellcnt, px_cellfill,

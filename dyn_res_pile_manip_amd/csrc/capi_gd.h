@@ -61,6 +61,10 @@ int gd_forward_backward(drp_ctx* c, const GdPass& pass) {
         ProbeScope ps(c, KC_BWD_REWARD);
         hipLaunchKernelGGL(kb_seed_stage, dim3(B, H), dim3(256), 0, st, ptr<float>(c->gd_seed_in), N, ptr<float>(c->gd_seed),
                            g_state + (size_t)(H - 1) * bn * 3);
+    } else if (c->gd_cloud) {       // the installed cloud goal (capi_cloud_goal.h): rewards and g_state[H-1] in kb_reward's place, no seed staged
+        ProbeScope ps(c, KC_BWD_REWARD);
+        c->dv(DV_BWD_REWARD);
+        CHK(cloud_goal_session_launch(c, B, N, H, nb, ptr<float>(c->rewards), 1, pass.host_rewards, g_state + (size_t)(H - 1) * bn * 3));
     } else {
         ProbeScope ps(c, KC_BWD_REWARD);
         c->dv(DV_BWD_REWARD);
@@ -176,6 +180,7 @@ static int gd_begin_common(drp_ctx* c, int S_or_cost, const float* s0, const flo
     CHK(guarded_wait(c, nullptr));
     c->gd_S = S; c->gd_scene_nb = S > 0 ? nb / S : 0;
     c->gd_cost = cost;
+    c->gd_cloud = false;            // (drp_gd_begin_cloud sets it behind this)
     c->gd_nb = nb; c->gd_N = N; c->gd_B = B; c->gd_H = H; c->gd_iter = 0; c->gd_lr = lr;
     for (int q = 0; q < DRP_GD_SLOTS; ++q) c->gd_pending[q] = false;           // a new problem drops what the last one left in flight
     c->gd_cself_tag = 0;
@@ -197,6 +202,19 @@ int drp_gd_begin_cost(drp_ctx* c, const float* s0, const float* attr, const floa
                       const float* actions, int B, int H, double lr, const float act_lo[4], const float act_hi[4]) {
     CHK(need(c, true, true, false));
     return gd_begin_common(c, -1, s0, attr, dens, nb, N, actions, B, H, lr, act_lo, act_hi);
+}
+
+// drp_gd_begin with the installed cloud goal in the image's place (capi_cloud_goal.h)
+int drp_gd_begin_cloud(drp_ctx* c, const float* s0, const float* attr, const float* dens, int nb, int N,
+                       const float* actions, int B, int H, double lr, const float act_lo[4], const float act_hi[4]) {
+    CHK(need(c, true, true, false));
+    CHK(cloud_goal_session_check(c, N));
+    CHK(gd_begin_common(c, 0, s0, attr, dens, nb, N, actions, B, H, lr, act_lo, act_hi));
+    c->gd_on = false;               // until the goal's tables are in
+    CHK(cloud_goal_session_begin(c, dens, nb, B, N, true));
+    c->gd_cloud = true;
+    c->gd_on = true;
+    return DRP_OK;
 }
 
 int drp_gd_begin_scenes(drp_ctx* c, int S, const float* s0, const float* attr, const float* dens, int nb, int N,

@@ -47,6 +47,7 @@ static int mpc_begin_common(drp_ctx* c, const drp_mpc_params* p, int S, const fl
     c->mpc_on = true;
     c->gd_on = false;
     c->mpc_cost = false; c->mpc_rewards_ok = true;         // (drp_mpc_begin_cost sets them behind this)
+    c->mpc_cloud = false;                                  // (drp_mpc_begin_cloud likewise)
     c->mpc_cself_tag = 0;           // new attributes / densities / batch size
     return DRP_OK;
 }
@@ -66,6 +67,21 @@ int drp_mpc_begin_cost(drp_ctx* c, const drp_mpc_params* p, const float* s0, con
     if (!p || !s0 || !attr || !dens || !nominal) return fail(c, DRP_EINVAL, "null argument");
     CHK(mpc_begin_common(c, p, 0, s0, attr, dens, nominal, nullptr));
     c->mpc_cost = true; c->mpc_rewards_ok = false;
+    return DRP_OK;
+}
+
+// drp_mpc_begin with the installed cloud goal in the image's place (capi_cloud_goal.h): the rollout ends in the cloud reward kernel
+// on every row's final state, writing the slot the update kernels read; every later session call is drp_mpc_begin's
+int drp_mpc_begin_cloud(drp_ctx* c, const drp_mpc_params* p, const float* s0, const float* attr,
+                        const float* dens, const double* nominal) {
+    CHK(need(c, true, true, false));
+    if (!p || !s0 || !attr || !dens || !nominal) return fail(c, DRP_EINVAL, "null argument");
+    CHK(cloud_goal_session_check(c, p->n_particles));
+    CHK(mpc_begin_common(c, p, 0, s0, attr, dens, nominal, nullptr));
+    c->mpc_on = false;              // until the goal's tables are in
+    CHK(cloud_goal_session_begin(c, dens, p->n_batch, mpc_rows(c), p->n_particles, false));
+    c->mpc_cloud = true;
+    c->mpc_on = true;
     return DRP_OK;
 }
 
@@ -132,6 +148,15 @@ int drp_mpc_rollout(drp_ctx* c, int reward_all_steps) {
         if (reward_all_steps != 0) return fail(c, DRP_EINVAL, "drp_mpc_rollout: a session begun by drp_mpc_begin_cost has no reward of its own (reward_all_steps must be 0)");
         c->mpc_rewards_ok = false;
         return run_rollout(c, p.n_batch, p.n_particles, mpc_rows(c), p.n_look_ahead, false, false, true, 0, p.n_batch);
+    }
+    if (c->mpc_cloud) {
+        if (reward_all_steps != 0) return fail(c, DRP_EINVAL, "drp_mpc_rollout: a session begun by drp_mpc_begin_cloud rewards the final state alone (reward_all_steps must be 0)");
+        const int H = p.n_look_ahead;
+        CHK(run_rollout(c, p.n_batch, p.n_particles, mpc_rows(c), H, false, false, true, 0, p.n_batch));
+        // the final-step slot directly: no scratch vector, no strided copy behind the kernel
+        ProbeScope ps(c, KC_REWARD);
+        c->dv(DV_REWARD);
+        return cloud_goal_session_launch(c, mpc_rows(c), p.n_particles, H, p.n_batch, ptr<float>(c->rewards) + (H - 1), (size_t)H, nullptr, nullptr);
     }
     return run_rollout(c, p.n_batch * mpc_scenes(c), p.n_particles, mpc_rows(c), p.n_look_ahead,
                        reward_all_steps != 0, reward_all_steps == 0, true, c->mpc_S, p.n_batch);

@@ -54,10 +54,12 @@
 #include "k_match.h"
 #include "k_match_f64.h"
 #include "k_sinkhorn.h"
+#include "k_cloud_goal.h"
 #include "k_prop_inst.h"       // km_prop / km_prop3 / km_rollout: declared here, instantiated in inst_*.hip
 
 #include "dispatch.h"          // host-only: policy, variant flags, plan functions
 #include "train_host.h"        // host-only: the trainer's staged-batch layout and push check
+#include "cloud_goal_host.h"   // host-only: the cloud goal's parameter checks, eps table and row-to-column mapping
 #include "ptcl_dataset_host.h" // host-only: the dataset calls' upload arena and per-image checks
 #include "capi_ctx.h"
 #include "capi_pipeline.h"
@@ -65,6 +67,7 @@
 extern "C" {
 
 #include "capi_core.h"
+#include "capi_cloud_goal.h"
 #include "capi_mpc.h"
 #include "capi_prep.h"
 #include "capi_gd.h"

@@ -1835,6 +1835,89 @@ class Engine(object):
             raise ValueError('rewards %s, the session has %d rows' % (rewards.shape, self.ns * self.nb))
         self._ck(self.lib.drp_mpc_set_rewards(self.h, _fp(rewards)))
 
+    # ---- planning to a target cloud on the device (include/drp.h: drp_set_goal_cloud, drp_mpc_begin_cloud, drp_gd_begin_cloud) ----
+    cloud_goal = None       # the installed cloud goal: {'kind', 'weight', 'eps_scale', 'iters', 'M'}
+
+    def set_goal_cloud(self, target, kind='chamfer', weight=1.0, eps_scale=1.0, iters=50):
+        """Install one target cloud [M, 3] (camera frame, as the predicted states) beside the image goal: the goal of
+        mpc_begin_cloud / gd_begin_cloud sessions and of cloud_goal_eval.  kind 'chamfer': reward = -weight * (fwd + bwd) of
+        cloud_chamfer(final state, target); 'sinkhorn': -weight * cloud_divergence(final state, target) with eps = eps_scale /
+        dens[column] and `iters` sweeps.  One cloud for every row: a cloud per scene ([S, M, 3]) and a reach (unbalanced
+        masses) are not supported."""
+        if kind not in L.CLOUD_GOAL_KINDS:
+            raise ValueError('unknown cloud goal kind %r (one of %s)' % (kind, sorted(L.CLOUD_GOAL_KINDS)))
+        target = _f32(target)
+        if target.ndim == 3:
+            raise ValueError('a cloud goal is ONE target [M, 3] shared by every row, got %s: a goal cloud per scene '
+                             '(multi-scene sessions) is not supported' % (target.shape,))
+        if target.ndim != 2 or target.shape[1] != 3:
+            raise ValueError('target must be [M, 3], got %s' % (target.shape,))
+        p = L.CloudGoalParams()
+        p.kind, p.iters, p.weight, p.eps_scale = L.CLOUD_GOAL_KINDS[kind], int(iters), float(weight), float(eps_scale)
+        self._ck(self.lib.drp_set_goal_cloud(self.h, _fp(target), int(target.shape[0]), ctypes.byref(p)))
+        self.cloud_goal = {'kind': kind, 'weight': float(weight), 'eps_scale': float(eps_scale), 'iters': int(iters),
+                           'M': int(target.shape[0])}
+
+    def mpc_begin_cloud(self, s0, attr, dens, nominal, n_sample, sigma, beta_filter, reward_weight,
+                        act_lo, act_hi, seed=0, sample_offset=0, noise_type='normal'):
+        """mpc_begin with the installed cloud goal in the image's place: mpc_rollout then ends in the cloud reward kernel on every
+        row's final state; every later session call works as after mpc_begin.  Single-scene (s0 [nb, N, 3])."""
+        s0, attr, dens = _f32(s0), _f32(attr), _f32(dens)
+        if s0.ndim != 3:
+            raise ValueError('a cloud session plans one scene: s0 must be [n_batch, N, 3], got %s (multi-scene cloud sessions '
+                             'are not supported)' % (s0.shape,))
+        nominal = np.ascontiguousarray(nominal, dtype=np.float64)
+        nb, N, _ = s0.shape
+        H = nominal.shape[0]
+        p = L.MpcParams()
+        p.n_batch, p.n_particles, p.n_sample, p.n_look_ahead = nb, N, int(n_sample), H
+        p.sigma, p.beta_filter, p.reward_weight = float(sigma), float(beta_filter), float(reward_weight)
+        for i in range(4):
+            p.act_lo[i] = float(act_lo[i])
+            p.act_hi[i] = float(act_hi[i])
+        p.seed, p.sample_offset = int(seed), int(sample_offset)
+        p.noise_type, p.reserved = L.NOISE_TYPES[noise_type], 0
+        self._ranged(lambda: self.lib.drp_mpc_begin_cloud(self.h, ctypes.byref(p), _fp(s0), _fp(attr), _fp(dens), _dp(nominal)))
+        self.H, self.nb, self.N, self.ns = H, nb, N, int(n_sample)
+        self.S = 0
+
+    def gd_begin_cloud(self, s0, attr, dens, actions, lr, act_lo, act_hi):
+        """gd_begin with the installed cloud goal in the image's place: gd_grad, gd_step, gd_step_async / gd_wait and gd_actions
+        run as in a goal session, one forward per iteration and no seed on the bus.  Single-scene (s0 [nb, N, 3])."""
+        s0, attr, dens, actions = _f32(s0), _f32(attr), _f32(dens), _f32(actions)
+        if s0.ndim != 3:
+            raise ValueError('a cloud session plans one scene: s0 must be [n_batch, N, 3], got %s (multi-scene cloud sessions '
+                             'are not supported)' % (s0.shape,))
+        nb, N, _ = s0.shape
+        B, H, _ = actions.shape
+        lo, hi = _f32(act_lo), _f32(act_hi)
+        self._ck(self.lib.drp_gd_begin_cloud(self.h, _fp(s0), _fp(attr), _fp(dens), nb, N, _fp(actions), B, H,
+                                             float(lr), _fp(lo), _fp(hi)))
+        self._gd = (B, H, N)
+
+    def cloud_goal_eval(self, p, n_p=None, dens=None, want_grad=False):
+        """The installed cloud goal on the caller's clouds p [B, N, 3] (or one cloud [N, 3]; n_p [B]: real rows, default all;
+        dens [B] or a number: the sinkhorn kind's eps = eps_scale / dens) -> {'rewards' [B] float32, 'values' [B] float64 =
+        weight * value[, 'grad' [B, N, 3] float32 = d values / d p, +0.0 on padding]}.  A one-shot: it needs no weights and ends
+        no session.  A row with a non-finite coordinate gets a NaN reward; the other rows are untouched by it."""
+        p = _f32(p)
+        if p.ndim == 2:
+            p = p[None]
+        assert p.ndim == 3 and p.shape[2] == 3
+        B, N = int(p.shape[0]), int(p.shape[1])
+        n_p = None if n_p is None else np.ascontiguousarray(np.broadcast_to(_i32(n_p).reshape(-1), (B,)))
+        dens = None if dens is None else np.ascontiguousarray(np.broadcast_to(_f32(dens).reshape(-1), (B,)))
+        rewards = np.empty((B,), np.float32)
+        values = np.empty((B,), np.float64)
+        grad = np.empty((B, N, 3), np.float32) if want_grad else None
+        self._ck(self.lib.drp_cloud_goal_eval(self.h, _fp(p), _ip(n_p) if n_p is not None else None,
+                                              _fp(dens) if dens is not None else None, B, N, _fp(rewards), _dp(values),
+                                              _fp(grad) if want_grad else None))
+        out = {'rewards': rewards, 'values': values}
+        if want_grad:
+            out['grad'] = grad
+        return out
+
     # ---- multi-GPU ------------------------------------------------------------------
     def comm_unique_id(self):
         buf = ctypes.create_string_buffer(128)

@@ -54,6 +54,72 @@ def _vote(max_reward_traj_idx, max_reward, best_actions):
     return best_actions[idx_best_sample][None]
 
 
+class _Bookkeeping(object):
+    """What the single-scene planner forms on a cost and on a cloud goal keep per call (planners.py:721-727,736-738, as the
+    built-in loop's): per start column the running best reward, its trajectory index and pushes; per iteration the mean and
+    spread of column 0's rewards; and from them the vote and the returned dict."""
+
+    def __init__(self, n_batch, H, action_dim, n_update_iter):
+        self.n_batch, self.H, self.action_dim = n_batch, H, action_dim
+        self.max_reward = -np.inf * np.ones(n_batch, dtype=np.float32)
+        self.max_reward_traj_idx = np.zeros(n_batch, dtype=np.int64)
+        self.best_actions_of_samples = np.zeros((n_batch, H, action_dim), dtype=np.float32)
+        self.rew_mean = np.zeros((1, int(n_update_iter)), dtype=np.float32)
+        self.rew_std = np.zeros((1, int(n_update_iter)), dtype=np.float32)
+
+    def aggregate(self, it, rewards, actions, ns):
+        n_batch = self.n_batch
+        r = rewards.reshape(ns, n_batch)
+        cur_max, idx = r.max(0), r.argmax(0)
+        acts = actions.reshape(ns, n_batch, self.H, self.action_dim)[idx, np.arange(n_batch)]
+        better = np.asarray(cur_max) > self.max_reward
+        self.max_reward[better] = np.asarray(cur_max)[better]
+        self.max_reward_traj_idx[better] = np.asarray(idx)[better]
+        self.best_actions_of_samples[better] = np.asarray(acts)[better]
+        if it < self.rew_mean.shape[1]:
+            self.rew_mean[0, it] = r[:, 0].mean()
+            self.rew_std[0, it] = r[:, 0].std(ddof=1) if ns > 1 else 0.0
+
+    def vote(self):
+        return _vote(self.max_reward_traj_idx, self.max_reward, self.best_actions_of_samples)       # [1,H,4]
+
+    def result(self, best_seq, act_seqs_last, reward_seqs, obs_seq_best, reward_best, nominal, times, iter_num):
+        """the reference's dict; `next_r` [H,1] holds the winner's reward at its last entry and NaN before it (one value per
+        horizon, not one per step)"""
+        next_r = None
+        if reward_best is not None:
+            next_r = np.full((self.H, 1), np.nan, np.float32)
+            next_r[-1, 0] = reward_best[0]
+        ns_last = reward_seqs.shape[0] // self.n_batch
+        return {'action_sequence': best_seq[0],
+                'action_full': act_seqs_last[:, 0, :],
+                'reward_full': reward_seqs.reshape(ns_last, self.n_batch)[:, 0],
+                'observation_sequence': obs_seq_best,
+                'observation_distractor_sequence': None,
+                'reward': reward_best,
+                'next_r': next_r,
+                'rew_mean': self.rew_mean,
+                'rew_std': self.rew_std,
+                'nominal_sequence': nominal,
+                'times': times,
+                'iter_num': iter_num}
+
+
+def _check_single_scene(config, state_cur_np, state_param, act_seq, act_label_seq, n_look_ahead, noise_type):
+    """the argument checks the cost and the cloud forms share -> mpc_type"""
+    assert type(state_cur_np) == np.ndarray and state_cur_np.ndim == 3, 'one scene: state_cur_np [n_batch,N,3]'
+    assert state_cur_np.shape[0] == state_param.shape[0] and state_cur_np.shape[2] == 3
+    assert type(act_seq) == np.ndarray and act_seq.ndim == 3
+    assert act_seq.shape[0] == act_label_seq.shape[0] and act_label_seq.ndim == 1
+    assert act_seq.shape[0] == n_look_ahead
+    mpc_type = config['mpc'].get('mpc_type', 'MPPI')
+    if mpc_type not in ('GD', 'MPPI', 'CEM'):
+        raise ValueError('unknown mpc_type %r' % (mpc_type,))
+    if noise_type not in ('normal', 'uniform', 'total_rand'):
+        raise ValueError('unknown noise type: %s' % noise_type)
+    return mpc_type
+
+
 def world2cam_affine(cam_extrinsic):
     """planners.py:197-203: rows 0..2 of inv(inv(cam_ext) diag(1,-1,-1,1)), built in
     float64 and cast to fp32 as the reference does."""
@@ -555,16 +621,7 @@ class PlannerGD(Planner):
             raise ValueError('planning on a cost is not sharded over ranks: comm must be None')
         if not callable(cost):
             raise TypeError('cost must be callable: cost(pred, context, want_grad) -> (values, grad)')
-        assert type(state_cur_np) == np.ndarray and state_cur_np.ndim == 3, 'one scene: state_cur_np [n_batch,N,3]'
-        assert state_cur_np.shape[0] == state_param.shape[0] and state_cur_np.shape[2] == 3
-        assert type(act_seq) == np.ndarray and act_seq.ndim == 3
-        assert act_seq.shape[0] == act_label_seq.shape[0] and act_label_seq.ndim == 1
-        assert act_seq.shape[0] == n_look_ahead
-        mpc_type = self.config['mpc'].get('mpc_type', 'MPPI')
-        if mpc_type not in ('GD', 'MPPI', 'CEM'):
-            raise ValueError('unknown mpc_type %r' % (mpc_type,))
-        if noise_type not in ('normal', 'uniform', 'total_rand'):
-            raise ValueError('unknown noise type: %s' % noise_type)
+        mpc_type = _check_single_scene(self.config, state_cur_np, state_param, act_seq, act_label_seq, n_look_ahead, noise_type)
         start = time.time()
         self.particle_num = N = state_cur_np.shape[1]
         n_batch = state_cur_np.shape[0]
@@ -578,11 +635,8 @@ class PlannerGD(Planner):
         if seed is None:
             seed = int(np.random.randint(0, 2 ** 31 - 1))
 
-        max_reward = -np.inf * np.ones(n_batch, dtype=np.float32)
-        max_reward_traj_idx = np.zeros(n_batch, dtype=np.int64)
-        best_actions_of_samples = np.zeros((n_batch, H, self.action_dim), dtype=np.float32)
-        rew_mean = np.zeros((1, int(n_update_iter)), dtype=np.float32)
-        rew_std = np.zeros((1, int(n_update_iter)), dtype=np.float32)
+        book = _Bookkeeping(n_batch, H, self.action_dim, n_update_iter)
+        aggregate = book.aggregate
         rollout_time = 0.0
         optim_time = 0.0
         cost_time = 0.0
@@ -595,19 +649,6 @@ class PlannerGD(Planner):
             values = check_cost_output(values, grad, pred.shape, want_grad)
             cost_time += (time.perf_counter() - t0) * 1e3
             return -np.asarray(values, np.float32), grad
-
-        def aggregate(it, rewards, actions, ns):
-            """planners.py:721-727,736-738, as the built-in loop's"""
-            r = rewards.reshape(ns, n_batch)
-            cur_max, idx = r.max(0), r.argmax(0)
-            acts = actions.reshape(ns, n_batch, H, self.action_dim)[idx, np.arange(n_batch)]
-            better = np.asarray(cur_max) > max_reward
-            max_reward[better] = np.asarray(cur_max)[better]
-            max_reward_traj_idx[better] = np.asarray(idx)[better]
-            best_actions_of_samples[better] = np.asarray(acts)[better]
-            if it < rew_mean.shape[1]:
-                rew_mean[0, it] = r[:, 0].mean()
-                rew_std[0, it] = r[:, 0].std(ddof=1) if ns > 1 else 0.0
 
         i = 0
         if mpc_type == 'GD':
@@ -661,31 +702,132 @@ class PlannerGD(Planner):
             if n_iter > 1:
                 nominal = eng.mpc_get(nominal=True)['nominal']
 
-        best_seq = _vote(max_reward_traj_idx, max_reward, best_actions_of_samples)       # [1,H,4]
-        obs_seq_best, reward_best, next_r = None, None, None
+        best_seq = book.vote()
+        obs_seq_best, reward_best = None, None
         t_best = time.perf_counter()
         if rollout_best_action_sequence:
             states, _ = eng.rollout(state_cur_np[0:1], attr_cur_np[0:1], state_param[0:1], best_seq,
                                     want_states=True, want_reward=False)
             obs_seq_best = states[0]
             reward_best, _ = evaluate(states, False)                    # [1]
-            next_r = np.full((H, 1), np.nan, np.float32)
-            next_r[-1, 0] = reward_best[0]
-        ns_last = reward_seqs.shape[0] // n_batch
-        return {'action_sequence': best_seq[0],
-                'action_full': act_seqs_last[:, 0, :],
-                'reward_full': reward_seqs.reshape(ns_last, n_batch)[:, 0],
-                'observation_sequence': obs_seq_best,
-                'observation_distractor_sequence': None,
-                'reward': reward_best,
-                'next_r': next_r,
-                'rew_mean': rew_mean,
-                'rew_std': rew_std,
-                'nominal_sequence': nominal,
-                'times': {'total_time': time.time() - start, 'rollout_time': rollout_time,
-                          'optim_time': optim_time, 'cost_time': cost_time, 'goal_time': 0.0, 'goal_cached': False,
-                          'best_rollout_time': (time.perf_counter() - t_best) * 1e3},
-                'iter_num': i}
+        times = {'total_time': time.time() - start, 'rollout_time': rollout_time, 'optim_time': optim_time, 'cost_time': cost_time,
+                 'goal_time': 0.0, 'goal_cached': False, 'best_rollout_time': (time.perf_counter() - t_best) * 1e3}
+        return book.result(best_seq, act_seqs_last, reward_seqs, obs_seq_best, reward_best, nominal, times, i)
+
+    def trajectory_optimization_ptcl_cloud(self, state_cur_np, state_param, attr_cur_np, target_cloud, model_dy, act_seq,
+                                           act_label_seq, n_sample, n_look_ahead, n_update_iter, action_lower_lim,
+                                           action_upper_lim, kind='chamfer', weight=1.0, eps_scale=1.0, iters=50, seed=None,
+                                           noise_type='normal', rollout_best_action_sequence=True, comm=None):
+        """Plan to a target cloud [M, 3] (camera frame) on the device: trajectory_optimization_ptcl_cost with
+        costs.cloud_chamfer_cost (kind 'chamfer') or costs.cloud_divergence_cost (kind 'sinkhorn', eps = eps_scale / state_param
+        per start column, `iters` sweeps) as the cost -- the same bookkeeping, voting rule, dict keys and units (-cost; `next_r`
+        holds the winner's reward at its last entry and NaN before it) -- but through the built-in loops: the target is
+        installed once (Engine.set_goal_cloud), the rewards and the reverse pass's seed are computed where the states lie, and
+        iterations are enqueued ahead of the host as trajectory_optimization_ptcl_multi_traj enqueues them (mpc_sample ->
+        mpc_rollout -> update with mpc_fetch_async / mpc_wait; gd_step_async / gd_wait).  The winner's reward is
+        Engine.cloud_goal_eval on its re-rollout.  Sharding (`comm`), a multi-scene form and a reach are refused."""
+        if comm is not None:
+            raise ValueError('planning to a cloud goal is not sharded over ranks: comm must be None')
+        mpc_type = _check_single_scene(self.config, state_cur_np, state_param, act_seq, act_label_seq, n_look_ahead, noise_type)
+        target_cloud = np.asarray(target_cloud, np.float32)
+        if target_cloud.ndim != 2 or target_cloud.shape[1] != 3:
+            raise ValueError('target_cloud must be ONE cloud [M, 3], got %s (a target per scene is not supported)'
+                             % (target_cloud.shape,))
+        start = time.time()
+        self.particle_num = N = state_cur_np.shape[1]
+        n_batch = state_cur_np.shape[0]
+        H = n_look_ahead
+        traj_num = int(act_seq.shape[1])
+        eng = self._bind(model_dy)
+        self._eng = eng
+        t_goal = time.time()
+        eng.set_goal_cloud(target_cloud, kind=kind, weight=weight, eps_scale=eps_scale, iters=iters)
+        goal_time = time.time() - t_goal
+        lo, hi = self._clip_box(0)
+        cfg = self.config['mpc']
+        sigma = 2.0 * self.global_scale / 12.0 if noise_type == 'uniform' else cfg['sigma'] * self.global_scale / 12.0
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 31 - 1))
+
+        book = _Bookkeeping(n_batch, H, self.action_dim, n_update_iter)
+        aggregate = book.aggregate
+        rollout_time = 0.0
+        optim_time = 0.0
+
+        i = 0
+        if mpc_type == 'GD':
+            assert n_sample == traj_num, 'GD optimises the traj_num given trajectories (n_sample == traj_num)'
+            n_iter = gd_iteration_count(n_update_iter, float('inf'), N)
+            if n_iter < 1:
+                raise ValueError('n_update_iter %r admits no iteration' % (n_update_iter,))
+            cand = np.repeat(act_seq.transpose(1, 0, 2), n_batch, axis=0).astype(np.float32)      # [traj*nb,H,4]
+            eng.gd_begin_cloud(state_cur_np, attr_cur_np, state_param, cand, cfg['gd']['lr'], lo, hi)
+            reward_seqs = np.zeros((cand.shape[0],), np.float32)
+            act_seqs_last = cand
+            t0 = time.perf_counter()
+            enqueued = 0
+            for i in range(n_iter):
+                before = act_seqs_last
+                while enqueued < n_iter and enqueued <= i + GD_AHEAD:
+                    eng.gd_step_async(enqueued % GD_SLOTS)
+                    enqueued += 1
+                reward_seqs, act_seqs_last = eng.gd_wait(i % GD_SLOTS)
+                aggregate(i, reward_seqs, before, traj_num)         # the rewards belong to the pushes before the update
+            optim_time += (time.perf_counter() - t0) * 1e3
+            nominal = None
+        else:
+            n_iter = int(n_update_iter)
+            mp = dict(sigma=sigma, beta_filter=cfg['mppi']['beta_filter'], reward_weight=cfg['mppi']['reward_weight'],
+                      act_lo=lo, act_hi=hi, seed=seed, noise_type=noise_type)
+            cand = np.repeat(act_seq.transpose(1, 0, 2), n_batch, axis=0).astype(np.float32)      # [traj*nb,H,4]
+            eng.mpc_begin_cloud(state_cur_np, attr_cur_np, state_param, act_seq[:, 0, :], n_sample=traj_num, **mp)
+            eng.mpc_set_actions(cand)
+            t0 = time.perf_counter()
+            eng.mpc_rollout(False)
+            reward_seqs = eng.mpc_get(rewards=True)['rewards'].copy()
+            rollout_time += (time.perf_counter() - t0) * 1e3
+            aggregate(0, reward_seqs, cand, traj_num)
+            act_seqs_last = cand
+            r0 = reward_seqs.reshape(traj_num, n_batch)
+            nominal = act_seq[:, int(np.argmax(r0.mean(1))), :].astype(np.float64)
+            if n_iter > 1:
+                eng.mpc_begin_cloud(state_cur_np, attr_cur_np, state_param, nominal, n_sample=int(n_sample), **mp)
+            k_elite = int(cfg.get('cem', {}).get('n_elite', max(1, n_sample // 10)))
+
+            def enqueue(it):
+                """One iteration on the stream: sample, rollout with the cloud reward, update, its results on their way to the host."""
+                eng.mpc_sample(it)
+                eng.mpc_rollout(False)
+                if mpc_type == 'CEM':
+                    eng.mpc_update_elite_device(k_elite)
+                else:
+                    eng.mpc_update_device()
+                eng.mpc_fetch_async(it & 1)
+
+            t0 = time.perf_counter()
+            if n_iter > 1:
+                enqueue(1)
+            for i in range(1, n_iter):
+                if i + 1 < n_iter:
+                    enqueue(i + 1)          # before the host waits for iteration i: the bookkeeping runs beside the device
+                got = eng.mpc_wait(i & 1)
+                reward_seqs, act_seqs_last = got['rewards'], got['actions']
+                aggregate(i, reward_seqs, act_seqs_last, int(n_sample))
+            optim_time += (time.perf_counter() - t0) * 1e3
+            if n_iter > 1:
+                nominal = eng.mpc_get(nominal=True)['nominal']
+
+        best_seq = book.vote()
+        obs_seq_best, reward_best = None, None
+        t_best = time.perf_counter()
+        if rollout_best_action_sequence:
+            states, _ = eng.rollout(state_cur_np[0:1], attr_cur_np[0:1], state_param[0:1], best_seq,
+                                    want_states=True, want_reward=False)
+            obs_seq_best = states[0]
+            reward_best = eng.cloud_goal_eval(states[:, H - 1], dens=np.asarray(state_param, np.float32).reshape(-1)[0:1])['rewards']
+        times = {'total_time': time.time() - start, 'rollout_time': rollout_time, 'optim_time': optim_time, 'cost_time': 0.0,
+                 'goal_time': goal_time, 'goal_cached': False, 'best_rollout_time': (time.perf_counter() - t_best) * 1e3}
+        return book.result(best_seq, act_seqs_last, reward_seqs, obs_seq_best, reward_best, nominal, times, i)
 
     def trajectory_optimization_ptcl_multi_scene(self, state_cur_np, state_param, attr_cur_np, obs_goals, model_dy, act_seq,
                                                  act_label_seq, n_sample, n_look_ahead, n_update_iter, action_lower_lim,

@@ -473,6 +473,55 @@ int drp_gd_predict(drp_ctx* ctx, float* states_out /*[B][H][N][3]*/);
 int drp_gd_grad_seeded(drp_ctx* ctx, const float* seed /*[B][H][N][3]*/, float* grad_act_out, float* grad_state_out);
 int drp_gd_step_seeded(drp_ctx* ctx, const float* seed /*[B][H][N][3]*/, float* actions_out /*[B][H][4], nullable*/);
 
+/* ---- planning to a target cloud on the device ----------------------------------------------------------------------------------
+ * The goal as a cloud: how much material belongs where, in the camera frame the predicted states live in.  One target cloud is
+ * installed on the context BESIDE the image goal and the goal table (it touches neither); a cloud session is drp_mpc_begin /
+ * drp_gd_begin with that cloud in the image's place, and no state, reward or seed crosses the bus inside an iteration.
+ *   value(row) = chamfer: fwd + bwd of drp_cloud_chamfer(final state of the row, target)            (their bits)
+ *                sinkhorn: drp_cloud_divergence(final state, target) with eps = eps_scale / dens[row % n_batch], `iters` sweeps
+ *                          and scale 1 (its bits; the target's own self problem is solved once per start column at the begin)
+ *   reward(row) = (float)(-((double)weight * value));   gradient = weight x d value / d state_{H-1}: the one-shot's double
+ *                 expression times the weight, rounded to fp32 ONCE (a weight that is a power of two gives weight x the
+ *                 one-shot's fp32 gradient exactly).
+ * drp_set_goal_cloud: q [M][3], M <= 4096 (chamfer) or 1024 (sinkhorn); weight > 0 and finite; eps_scale > 0 and iters in
+ * 1..DRP_TRANSPORT_MAX_ITERS are read for the sinkhorn kind only.  DRP_EINVAL for a null or non-finite q, M out of range, a bad
+ * kind or parameter.  Installing a goal ends a running CLOUD session (its tables were the old goal's); other sessions go on.
+ * drp_mpc_begin_cloud: drp_mpc_begin's arguments; needs weights, a camera and a cloud goal (DRP_ESTATE without), N within the
+ * kind's limit and for sinkhorn positive finite densities (DRP_EINVAL).  drp_mpc_rollout(ctx, 0) then runs the rollout and the
+ * cloud reward kernel on every row's final state, writing the slot the update kernels read (a non-zero reward_all_steps:
+ * DRP_EINVAL).  Every later session call works as after drp_mpc_begin; drp_mpc_set_rewards stays accepted and replaces the rewards.
+ * drp_gd_begin_cloud: drp_gd_begin's arguments; drp_gd_grad, drp_gd_step, drp_gd_step_async, drp_gd_wait and drp_gd_get work as
+ * in a goal session: the cloud kernel stands where the image reward's launch stood, writes the rewards (and their pinned copy) and
+ * d loss / d state_{H-1}; no seed is staged and the forward runs once per iteration.  The seeded calls work as after drp_gd_begin.
+ * drp_cloud_goal_eval: the installed goal on the caller's clouds p [B][N][3] with n_p [B] real rows (null: all N; counts outside
+ * 1..N: DRP_EINVAL) and for sinkhorn dens [B] (eps = eps_scale / dens[b]; ignored, nullable, for chamfer): rewards_out [B],
+ * values_out [B] = weight x value as a double, grad_out [B][N][3] (padded rows +0.0), each nullable.  A one-shot: it needs no
+ * weights and ends no session.  A non-finite coordinate is not refused: that row's reward is NaN after the same number of
+ * steps, every other row's outputs keep their bits.
+ * Cloud sessions are single-scene and balanced: a goal cloud per scene and a reach (unbalanced masses) are out of scope.
+ * Cost, measured on one MI355X (profiles/cloud_goal_timing.txt; target as large as the pile): a chamfer session runs at the
+ * image goal's speed (0.59 / 2.79 / 8.86 ms per MPPI iteration at 1 024 samples x 20 / 100 / 300 particles x H 10 against 0.59 /
+ * 2.81 / 9.12 ms; 0.79 / 3.39 ms per GD iteration at 1 500 rows x 20 / 100 x H 3 against 0.78 / 3.38 ms).  A sinkhorn goal at
+ * iters 50 is K N M double exponentials per row and costs MORE than the rollout: 1.83 / 8.16 / 40.1 ms and 2.55 / 11.4 ms, 2.9 -
+ * 4.4 image-goal iterations; linear in iters.  Both are faster than the same cost through drp_mpc_set_rewards /
+ * drp_gd_step_seeded (1.2 - 1.8 x and 1.3 - 1.5 x). */
+#define DRP_CLOUD_CHAMFER 0
+#define DRP_CLOUD_SINKHORN 1
+typedef struct drp_cloud_goal_params {
+    int kind;                   /* DRP_CLOUD_CHAMFER, DRP_CLOUD_SINKHORN */
+    int iters;                  /* sinkhorn: sweeps, 1..DRP_TRANSPORT_MAX_ITERS */
+    double weight;              /* > 0, finite */
+    double eps_scale;           /* sinkhorn: > 0, finite */
+} drp_cloud_goal_params;
+int drp_set_goal_cloud(drp_ctx* ctx, const float* q /*[M][3]*/, int M, const drp_cloud_goal_params* p);
+int drp_mpc_begin_cloud(drp_ctx* ctx, const drp_mpc_params* p, const float* s0, const float* attr,
+                        const float* dens, const double* nominal /* [H,4] */);
+int drp_gd_begin_cloud(drp_ctx* ctx, const float* s0, const float* attr, const float* dens, int nb, int N,
+                       const float* actions, int B, int H, double lr, const float act_lo[4], const float act_hi[4]);
+int drp_cloud_goal_eval(drp_ctx* ctx, const float* p /*[B][N][3]*/, const int32_t* n_p /*[B], nullable*/,
+                        const float* dens /*[B], sinkhorn only*/, int B, int N, float* rewards_out /*[B]*/,
+                        double* values_out /*[B]*/, float* grad_out /*[B][N][3]*/);
+
 /* ---- multi-GPU (RCCL over xGMI) ------------------------------------------------------
  * The library does not link librccl: the first of these calls binds, at run time, $DRP_RCCL_LIB, else the librccl that
  * sits NEXT TO THE HIP RUNTIME THIS LIBRARY RUNS ON (PyTorch's bundled pair when the host imported torch first, /opt/rocm's
